@@ -17,14 +17,18 @@ STEADY STATE.  Before the W warm-up steps the batch is rolled, untimed, for `pre
 `horizon` steps), whatever --warmup says; a batch timed right after reset is ~25 % faster than the one a training run
 sees (fewer envs braking or in contact, no auto-resets).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
   roofline     — HBM roofline of the step kernel: ALGORITHMIC bytes per launch / average kernel time measured
                  live with HIP events on the launch stream (hrg_batch_kernel_time).  `traffic`, `valu_*` and `fp64_*`
                  are PMC figures of a committed capture of this same command (`traffic_source` names the file): a
                  counter pass slows the kernel and cannot run inside the timed region.
-  cpu_baseline — the CPU oracle (oracle/hrg_oracle.c, kind "port") on the host: P worker threads, barrier per vec-step
-                 (the SubprocVecEnv shape), envs of a vec-step drawn dynamically; several legs (all physical cores pinned,
-                 16 threads, the cgroup's cpu quota), `value` = the best, each with worker-busy and throttling figures.
+  cpu_baseline — with --full only: the CPU oracle (oracle/hrg_oracle.c, kind "port") on the host: P worker threads, barrier
+                 per vec-step (the SubprocVecEnv shape), envs of a vec-step drawn dynamically; several legs (all physical cores
+                 pinned, 16 threads, the cgroup's cpu quota), `value` = the best, each with worker-busy and throttling figures.
+
+A plain run sets up, pre-rolls and warms up, times the --steps steps and prints its line; everything else it can measure
+sits behind --full.  --dump-outputs DIR writes what the last timed step returned (obs, reward, done, info, terminal
+observations: DUMP_NAMES) as DIR/<name>.npy, float32 / float64; the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -333,6 +337,28 @@ def bench_action_pool(n, dev, rank=0, ik=False, n_pool=32):
     return pool
 
 
+DUMP_NAMES = ("obs", "reward", "done", "info", "term_obs")
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(G, out_dir, rank=0):
+    """The outputs of the batch's last step as <out_dir>/<name>.npy (rank r > 0: rank<r>_<name>.npy): obs, reward, terminal observations in float32,
+    done as float32 0 / 1, the integer info block as float64 (exact).  A few MB at the benchmark's sizes; a batch whose outputs exceed DUMP_MAX_BYTES
+    is written for a fixed, seeded sample of its envs, whose indices go to env_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cast = {"done": np.float32, "info": np.float64}
+    arrays = {name: getattr(G, name).cpu().numpy().astype(cast.get(name, np.float32)) for name in DUMP_NAMES}
+    n = len(arrays["obs"])
+    row_bytes = sum(a[0].nbytes for a in arrays.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, (f"rank{rank}_" if rank else "") + name + ".npy"), a)
+
+
 def bench_preroll_steps(desc, preroll=None):
     """Untimed steps before the warm-up: one horizon, at most 1000."""
     return preroll if preroll is not None else min(int(desc.horizon), 1000)
@@ -356,7 +382,9 @@ def main():
                     "replace_type 0, 20 resamples), as human_reach_ppo_parallel.yaml trains; named in config.workload")
     ap.add_argument("--robot-geometry", default="capsule", choices=["capsule", "hull"], help="collision geometry of the arm links: bounding capsules (default) or the convex "
                     "hulls of the link meshes (ReachHuman only; DESIGN.md D3); named in config.robot_geometry")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the CPU oracle baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU work for the all-cores leg of cpu_baseline (the 16-thread leg gets 0.6 x)")
     ap.add_argument("--pmc-json", default=DEFAULT_PMC, help="committed PMC capture of this command (tools/profile_capture.sh): source of roofline.traffic / valu_* / fp64_*")
     ap.add_argument("--variant-lib", default=None, help="tuning experiments only: time another build of the library; echoed as `variant_lib` in the JSON line")
@@ -364,6 +392,8 @@ def main():
     ap.add_argument("--force-gather", action="store_true", help="rehearse the N > 1 all-gather on one GPU (world size 1)")
     ap.add_argument("--gather-mode", default="serial", choices=["serial", "overlap"])
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     for var in ("HRG_PHASE_MASK", "HRG_LIB_PATH"):   # round-1 tuning switches: refuse rather than print a number that means something else
         if os.environ.get(var):
@@ -449,6 +479,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(G, args.dump_outputs, rank)
     if rank == 0:
         lib = load_library()
         obj_bytes = lib.hrg_stack_bytes() if args.env == "CollaborativeStackingCart" else (lib.hrg_hammer_bytes() if args.env == "CollaborativeHammeringCart" else (lib.hrg_box_bytes() if pick_place else 0))   # the task's object block, streamed next to the env block
@@ -513,7 +545,7 @@ def main():
             out["config"]["tasks"] = mixed_tasks
         if args.variant_lib:
             out["variant_lib"] = os.path.abspath(args.variant_lib)
-        if world == 1 and not args.no_cpu_baseline and not mixed_tasks:
+        if args.full and world == 1 and not args.no_cpu_baseline and not mixed_tasks:
             out["cpu_baseline"] = cpu_baseline(env_kwargs, 0, budget_s=args.cpu_budget, env_id=args.env, n_envs=n, wrappers=wrappers, preroll=preroll)
         print(json.dumps(out), flush=True)
     G.close()

@@ -1,7 +1,8 @@
-"""The compiled model tables against the reference's own DATA files (MJCF / STL): where the reference checkout is readable -- the build container; it does not
-travel to the GPU box, so these tests skip there -- tools/compile_model.py is run again and has to reproduce the committed assets.  This pins the model constants
-(kinematic chain, inertials, joint parameters, bounding capsules, hull vertex tables, the human tree) to the reference's files; it says nothing about MuJoCo's
-behaviour on them (PARITY UNPINNED)."""
+"""The compiled model tables against the reference's own DATA files (MJCF / STL): tools/compile_model.py is run again on the copies stored under
+tests/golden/reference/ (tools/make_reference_fixtures.py: the MJCF and settings files verbatim, the meshes as their vertex sets, values read from the
+reference's sources recorded in extracted.json) and has to reproduce the committed assets.  This pins the model constants (kinematic chain, inertials,
+joint parameters, bounding capsules, hull vertex tables, the human tree) to the reference's files; it says nothing about MuJoCo's behaviour on them
+(PARITY UNPINNED)."""
 import json
 import os
 import sys
@@ -10,15 +11,24 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_ASSETS = "/root/reference/human_robot_gym/models/assets"
+REF = os.path.join(ROOT, "tests", "golden", "reference")     # the reference's files, as tools/make_reference_fixtures.py stores them
+REF_ASSETS = os.path.join(REF, "models", "assets")
 ASSETS = os.path.join(ROOT, "human-robot-gym_amd", "assets")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="the reference checkout is not on this machine")
+
+def _extracted():
+    with open(os.path.join(REF, "extracted.json")) as f:
+        return json.load(f)
 
 
-def _tool():
+@pytest.fixture
+def cm(monkeypatch):
+    """compile_model, reading each STL mesh as the vertex set stored in mesh_vertices.npz (all that load_stl keeps of the file)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import compile_model
+    with np.load(os.path.join(REF, "mesh_vertices.npz"), allow_pickle=False) as z:
+        verts = {k: z[k].astype(np.float64) for k in z.files}
+    monkeypatch.setattr(compile_model, "load_stl", lambda path: verts[os.path.relpath(path, REF_ASSETS)])
     return compile_model
 
 
@@ -37,16 +47,14 @@ def _close(a, b, path=""):
         assert a == b, path
 
 
-def test_robot_and_human_tables_are_what_the_reference_files_compile_to():
-    cm = _tool()
+def test_robot_and_human_tables_are_what_the_reference_files_compile_to(cm):
     have = json.load(open(os.path.join(ASSETS, "reach_human_schunk.json")))
     _close(cm.compile_robot(REF_ASSETS), have["robot"], "robot")
     _close(cm.compile_human(REF_ASSETS), have["human"], "human")
     assert len(have["robot"]["chain"]) == 8 and len(have["human"]["bodies"]) == 24      # robot.xml: six arm links + two fingers; human.xml: 24 bodies
 
 
-def test_hull_vertex_tables_are_what_the_reference_meshes_compile_to():
-    cm = _tool()
+def test_hull_vertex_tables_are_what_the_reference_meshes_compile_to(cm):
     have = json.load(open(os.path.join(ASSETS, "reach_human_schunk.json")))
     hv, ho = cm.compile_hulls(REF_ASSETS, have["robot"]["chain"])
     with np.load(os.path.join(ASSETS, "schunk_hulls.npz"), allow_pickle=False) as z:
@@ -92,7 +100,7 @@ def test_task_defaults_are_the_reference_training_configs(env_id):
     no experiment config); the task's own default file is followed here (model.py): its animation frequency differs, and `object_gripped_reward` is a keyword the
     hammering task does not have."""
     from human_robot_gym_amd import model as M
-    ref = _compose(os.path.join("/root/reference/human_robot_gym/training/config/environment", YAML_OF[env_id] + ".yaml"))
+    ref = _compose(os.path.join(REF, "training", "config", "environment", YAML_OF[env_id] + ".yaml"))
     mine = M.ENV_DEFAULTS[env_id]
     common = [k for k in mine if k in ref]
     assert len(common) >= 20
@@ -100,7 +108,7 @@ def test_task_defaults_are_the_reference_training_configs(env_id):
     bad = {k: (mine[k], ref[k]) for k in common if not _same(mine[k], ref[k]) and k not in known}
     assert not bad, bad
     if env_id == "CollaborativeHammeringCart":        # ... the frequency is the task's own default file's
-        own = _compose(os.path.join("/root/reference/human_robot_gym/training/config/environment/default", YAML_OF[env_id] + ".yaml"))
+        own = _compose(os.path.join(REF, "training", "config", "environment", "default", YAML_OF[env_id] + ".yaml"))
         assert _same(mine["human_animation_freq"], own["human_animation_freq"]) and "object_gripped_reward" not in own
 
 
@@ -110,7 +118,7 @@ def test_controller_robot_and_wrapper_constants_are_the_reference_config_files()
     import yaml
     import human_robot_gym_amd as hrg
     from human_robot_gym_amd import model as M
-    R = "/root/reference/human_robot_gym"
+    R = REF
     fs = json.load(open(f"{R}/controllers/failsafe_controller/config/failsafe.json"))
     for k, v in M.FAILSAFE_CONFIG.items():
         assert fs[k] == v, k
@@ -126,11 +134,8 @@ def test_controller_robot_and_wrapper_constants_are_the_reference_config_files()
     cp = yaml.safe_load(open(f"{R}/training/config/wrappers/collision_prevention/default_collision_prevention.yaml"))
     dd = hrg.build_model_desc(None, collision_prevention={})
     assert (dd.cp_replace_type, dd.cp_n_resamples) == (cp["replace_type"], cp["n_resamples"])
-    # the measured joints, in the order human.py hands them to the shield: read from the source text as a list of string literals
-    import re
-    src = open(f"{R}/models/objects/human/human.py").read()
-    blk = src[src.index("joint_elements"):]
-    names = re.findall(r'"([A-Za-z_]+)"', blk[:blk.index("]")])
+    # the measured joints, in the order human.py hands them to the shield: read from the source text as a list of string literals (extracted.json)
+    names = _extracted()["human_joint_elements"]
     assert names == M.HUMAN_JOINT_ELEMENTS and len(names) == 23
 
 
@@ -140,30 +145,17 @@ SRC_OF = {"ReachHuman": "reach_human_env.py", "PickPlaceHumanCart": "pick_place_
           "CollaborativeStackingCart": "collaborative_stacking_cartesian_env.py", "CollaborativeHammeringCart": "collaborative_hammering_cartesian_env.py"}
 
 
-def _constructor_defaults(path):
-    """keyword -> default of the first class's __init__ in a source file, from its syntax tree (the file is parsed as text, never imported)"""
-    import ast
-    for node in ast.walk(ast.parse(open(path).read())):
-        if isinstance(node, ast.ClassDef):
-            for f in node.body:
-                if isinstance(f, ast.FunctionDef) and f.name == "__init__":
-                    args, defs, out = f.args.args[1:], f.args.defaults, {}
-                    for a, dv in zip(args[len(args) - len(defs):], defs):
-                        try:
-                            v = ast.literal_eval(dv)
-                            out[a.arg] = list(v) if isinstance(v, tuple) else v
-                        except ValueError:
-                            pass
-                    return out
-    return {}
+def _constructor_defaults(src):
+    """keyword -> default of the first class's __init__ in an environment source file, read from its syntax tree (extracted.json)"""
+    return _extracted()["constructor_defaults"][src]
 
 
 @pytest.mark.parametrize("env_id", sorted(SRC_OF))
 def test_keywords_outside_the_training_configs_are_the_constructor_defaults(env_id):
     """What the yamls leave open falls to the environment class's own defaults (environments/manipulation/*.py, `__init__` signatures)."""
     from human_robot_gym_amd import model as M
-    ctor = _constructor_defaults(os.path.join("/root/reference/human_robot_gym/environments/manipulation", SRC_OF[env_id]))
-    ref = _compose(os.path.join("/root/reference/human_robot_gym/training/config/environment", YAML_OF[env_id] + ".yaml"))
+    ctor = _constructor_defaults(SRC_OF[env_id])
+    ref = _compose(os.path.join(REF, "training", "config", "environment", YAML_OF[env_id] + ".yaml"))
     mine = M.ENV_DEFAULTS[env_id]
     assert len(ctor) > 30
     # (CollaborativeHammeringCart follows its own default file, which the top-level yaml does not compose: n_nail_placements_sampled_per_100_steps 1 there, 3 in the class)
@@ -175,12 +167,11 @@ def test_keywords_outside_the_training_configs_are_the_constructor_defaults(env_
 def test_mixed_batch_tasks_are_the_icra_2024_experiment_configs():
     """BASELINE configs[4]: training/icra_2024_run_experiments.sh:4-9 names the six tasks and their horizons; the `environment` block of each
     config_icra_2024/environment_evaluation/training/<task>-SAC.yaml is what the experiment steps.  ENV_DEFAULTS overlaid with mixed.ICRA_TASKS has to agree with it."""
-    import re
     import yaml
     from human_robot_gym_amd import mixed, model as M
-    R = "/root/reference/human_robot_gym/training"
+    R = os.path.join(REF, "training")
     short = {"R": "ReachHuman", "PP": "PickPlaceHumanCart", "CL": "CollaborativeLiftingCart", "RHH": "RobotHumanHandoverCart", "HRH": "HumanRobotHandoverCart", "CS": "CollaborativeStackingCart"}
-    runs = re.findall(r"icra_2024_environment_evaluation\.sh (\w+) \w+ \d+ \d+ (\d+) ", open(f"{R}/icra_2024_run_experiments.sh").read())
+    runs = _extracted()["icra_2024_runs"]   # (task, horizon) of each icra_2024_environment_evaluation.sh call in the script
     assert [short[s] for s, _ in runs] == [t for t, _ in mixed.ICRA_TASKS]                      # the same six tasks, in the script's order
     for (s, hz), (env_id, kw) in zip(runs, mixed.ICRA_TASKS):
         assert int(hz) == kw["horizon"]
@@ -196,7 +187,7 @@ def test_nail_constants_are_nail_xml():
     joint (axis -z, range 0 .. 0.06, frictionloss 10 000, solreffriction (-100, -100))."""
     import xml.etree.ElementTree as ET
     from human_robot_gym_amd import model as M
-    root = ET.parse("/root/reference/human_robot_gym/models/assets/objects/nail.xml").getroot()
+    root = ET.parse(os.path.join(REF_ASSETS, "objects", "nail.xml")).getroot()
     head = root.find("body")
     assert root.get("name") == "nail_base" and head.get("name") == "nail_head"
     assert [float(x) for x in head.get("pos").split()] == [0.0, 0.0, M.NAIL["stem"]]

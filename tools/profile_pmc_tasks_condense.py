@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """On the GPU box, after tools/profile_capture_tasks_pmc.sh <tag>: condense the raw FETCH_SIZE / WRITE_SIZE counter CSVs (too large for gpurun's return limit) into
-gpurun_out/summ/<tag>_tasks_pmc.json = {task: {FETCH_SIZE, WRITE_SIZE (KiB per launch, mean over the step-kernel dispatches), vgpr, scratch}}."""
+captures/summ/<tag>_tasks_pmc.json = {task: {FETCH_SIZE, WRITE_SIZE (KiB per launch, mean over the step-kernel dispatches), vgpr, scratch}}."""
 import csv, glob, json, os, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02t"
-go = "gpurun_out"
+go = "captures"
 out = {}
 for d in sorted(glob.glob(f"{go}/{tag}_*_fetch")):
     t = os.path.basename(d)[len(tag) + 1:-len("_fetch")]

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Condense rocprofv3 CSVs under gpurun_out/<tag>_* into profiles/<tag>_*.{md,json} (the tracked, judged evidence)."""
+"""Condense rocprofv3 CSVs under captures/<tag>_* into profiles/<tag>_*.{md,json} (the tracked, judged evidence)."""
 import csv, glob, json, os, sys, collections
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-go, pr = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+go, pr = os.path.join(root, "captures"), os.path.join(root, "profiles")
 os.makedirs(pr, exist_ok=True)
 what = sys.argv[2] if len(sys.argv) > 2 else "`python3 bench.py --steps N --warmup W --no-cpu-baseline` (1 x MI355X, ReachHuman, 4096 envs, SSM)"
 lines = [f"# rocprofv3 summary `{tag}` — {what}", ""]

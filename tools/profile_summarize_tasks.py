@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Condense gpurun_out/<tag>_<task>_{trace,fetch,write,bench} (tools/profile_capture_tasks*.sh) into profiles/<tag>_tasks_summary.md + bench JSONs."""
+"""Condense captures/<tag>_<task>_{trace,fetch,write,bench} (tools/profile_capture_tasks*.sh) into profiles/<tag>_tasks_summary.md + bench JSONs."""
 import csv, glob, json, os, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02t"
-go, pr = "gpurun_out", "profiles"
+go, pr = "captures", "profiles"
 tasks = ["HumanObjectInspectionCart", "HumanRobotHandoverCart", "RobotHumanHandoverCart", "CollaborativeLiftingCart", "CollaborativeStackingCart", "CollaborativeHammeringCart"]
 L = [f"# rocprofv3 summary `{tag}` — the collaboration tasks' kernel variants (`bash tools/profile_capture_tasks.sh {tag}`, 1 x MI355X, 4096 envs each)", "",
      "`rocprofv3 --kernel-trace --stats -- python3 bench.py --env TASK --steps 40 --warmup 10 --preroll 200 --no-cpu-baseline` per task (kernel_stats.csv row of the step kernel), and the",
-     f"un-profiled `python3 bench.py --env TASK --steps 60 --warmup 10 --cpu-budget 6` JSON line (steady state: pre-roll of min(horizon, 1000) steps, staggered episode phases) (`{tag}_<task>_bench.json`).", "",
+     f"un-profiled `python3 bench.py --full --env TASK --steps 60 --warmup 10 --cpu-budget 6` JSON line (steady state: pre-roll of min(horizon, 1000) steps, staggered episode phases) (`{tag}_<task>_bench.json`).", "",
      "| task | step kernel | calls | average ns (rocprof) | min ns | max ns | bench: env steps/s | ms/step | kernel ms (HIP events) | algorithmic MB/launch | roofline frac | CPU oracle steps/s (all physical cores / 16 threads) |",
      "|---|---|---|---|---|---|---|---|---|---|---|---|"]
 T = ["", f"## HBM traffic per launch (separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes, `bash tools/profile_capture_tasks_pmc.sh {tag}`; KiB counters, FETCH_SIZE doubled as "
