@@ -19,6 +19,7 @@ SRC_LIFT = os.path.join(_HERE, "csrc", "hrgym_lift.hip")     # ... and with the 
 SRC_STACK = os.path.join(_HERE, "csrc", "hrgym_stack.hip")   # ... and the four-cube system of CollaborativeStackingCart
 SRC_HAMMER = os.path.join(_HERE, "csrc", "hrgym_hammer.hip")  # ... and board + nail + hammer of CollaborativeHammeringCart
 SRC_HULLS = os.path.join(_HERE, "csrc", "hrgym_hulls.hip")    # ... and the ReachHuman kernels with the arm links' convex hulls as collision geometry
+SRC_BOX_HULLS = os.path.join(_HERE, "csrc", "hrgym_box_hulls.hip")   # ... and the cube kernels with the convex hulls (hull - cube pairs by MPR)
 
 EXPORTS = [
     "hrg_last_error", "hrg_version", "hrg_state_bytes", "hrg_batch_create", "hrg_batch_destroy", "hrg_batch_reset",
@@ -26,12 +27,13 @@ EXPORTS = [
     "hrg_batch_kernel_time", "hrg_batch_enable_taps", "hrg_box_bytes", "hrg_batch_get_box", "hrg_batch_set_box", "hrg_batch_get_states", "hrg_batch_set_states",
     "hrg_batch_check_actions", "hrg_stack_bytes", "hrg_batch_get_stack", "hrg_batch_set_stack", "hrg_batch_launch_order",
     "hrg_hammer_bytes", "hrg_batch_get_hammer", "hrg_batch_set_hammer", "hrg_test_hull_queries",
+    "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks",
 ]
 
 
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = [SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS] + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h")] + [
+    deps = [SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS] + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h")] + [
         os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
@@ -43,7 +45,7 @@ def build_library(force=False, verbose=False):
     # pair spilled.  Without it the ReachHuman kernel allocates 120 VGPRs with no VGPR spill (was 128 + 5 spilled; SGPR spills 93 -> 64) and every variant is
     # 3 - 6 % faster (profiles/r03_*).
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Xarch_device", "-fapprox-func", "-mllvm", "-disable-machine-licm", "-o", LIB_PATH,
-           SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS]
+           SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -102,6 +104,8 @@ def load_library():
     lib.hrg_batch_get_hammer.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.hrg_batch_set_hammer.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.hrg_test_hull_queries.argtypes = [vp, vp, vp, i32, vp]
+    lib.hrg_test_hull_box_queries.argtypes = [vp, vp, vp, i32, vp]
+    lib.hrg_batch_mpr_fallbacks.argtypes = [vp, ctypes.POINTER(i64)]
     lib.hrg_stack_bytes.restype = ctypes.c_size_t
     lib.hrg_batch_get_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.hrg_batch_set_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
@@ -288,6 +292,12 @@ class HipBatch:
         nb = ctypes.c_int32(0)
         _check(self.lib, self.lib.hrg_batch_launch_order(self.h, order.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nb)))
         return order, int(nb.value)
+
+    def mpr_fallbacks(self):
+        """Hull - cube pairs (robot_geometry="hull", cube tasks) whose MPR did not converge and kept the capsule contact, summed over every substep since create."""
+        c = ctypes.c_int64()
+        _check(self.lib, self.lib.hrg_batch_mpr_fallbacks(self.h, ctypes.byref(c)))
+        return c.value
 
     def enable_taps(self, on=True):
         _check(self.lib, self.lib.hrg_batch_enable_taps(self.h, int(bool(on))))

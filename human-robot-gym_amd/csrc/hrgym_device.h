@@ -141,7 +141,18 @@ struct DevModel {
   // animation clips (frames in device memory)
   hrg_clip_table clips;
   const double* hull_dev;    // hull vertices of the arm links in device memory (m.robot_hulls; m.hull_verts is the creator's host pointer)
+  double hull_cen[HRG_NHULL][3];   // vertex centroid of each hull, body frame: the interior point of the hull - cube penetration (MPR)
+  unsigned long long* mpr_fallback;   // device counter: hull - cube pairs whose MPR did not converge and kept the capsule contact (hrg_batch_mpr_fallbacks)
 };
+
+// vertex centroid of each hull (body frame): the interior point MPR starts from (hrg_batch_create, hrg_test_hull_box_queries)
+static inline void hull_centroids(const double* verts, const int32_t* off, double cen[HRG_NHULL][3]) {
+  for (int h = 0; h < HRG_NHULL; h++) {
+    double s[3] = {0, 0, 0};
+    for (int i = off[h]; i < off[h + 1]; i++) for (int a = 0; a < 3; a++) s[a] += verts[3 * i + a];
+    for (int a = 0; a < 3; a++) cen[h][a] = s[a] / (double)(off[h + 1] - off[h]);
+  }
+}
 
 struct Contact {
   int32_t g1, g2, b1, b2;
@@ -175,6 +186,9 @@ struct Contact {
 // per-workgroup (= per-env) LDS image.  Sized to <= 10 KB so that 16 envs (4 waves/SIMD) are resident per CU:
 // 4096 envs on 256 CUs then run in one round.  Phase-local scratch shares one union.
 struct GjkLds { double y[4][3], a[4][3], b[4][3], l[4], lam[4]; int ia[4], ib[4]; };   // GJK simplex: points of the Minkowski difference, their witnesses on the hull / the segment, weights
+#if HRG_HULLS && HRG_BOX
+struct MprLds { double v[5][3], a[5][3], b[5][3]; };   // MPR portal v0 .. v3 + the candidate support point (slot 4): points of the Minkowski difference hull - box, their witnesses on each
+#endif
 struct Lds {
   hrg_env_state st;
   // robot tree at the simulation state (live across the whole cycle)
@@ -224,7 +238,9 @@ struct Lds {
       double hcap[HRG_NHB][6], rcapw[HRG_NRCAP][6];
       int hnear[HRG_NHB];                // human capsules whose bounding sphere comes near the robot (the pair rounds of collide run over these)
       double rcen[HRG_NRCAP][3];         // capsule centres: collide -> classify (the speed of a robot geom at a human contact)
-#if HRG_HULLS
+#if HRG_HULLS && HRG_BOX
+      union { GjkLds gjk; MprLds mpr; }; // the simplex of a hull query / the portal of a hull - cube query (hrgym_hull.h): one pair at a time
+#elif HRG_HULLS
       GjkLds gjk;                        // the simplex of a hull query (hrgym_hull.h)
 #endif
 #if HRG_STACK

@@ -2890,7 +2890,7 @@ typedef hrg_stack_state ObjState;   // the per-env object block this variant str
 #define hrg_step_kernel hrg_step_kernel_hammer
 #define hrg_reset_kernel hrg_reset_kernel_hammer
 typedef hrg_hammer_state ObjState;
-#elif HRG_HULLS
+#elif HRG_HULLS && !HRG_BOX
 #define hrg_step_kernel hrg_step_kernel_hull
 #define hrg_reset_kernel hrg_reset_kernel_hull
 typedef hrg_box_state ObjState;     // (ReachHuman streams no object block: the pointer is null)
@@ -2907,6 +2907,11 @@ typedef hrg_box_state ObjState;
 #define hrg_reset_kernel hrg_reset_kernel_lift
 #define hrg_box_launch_step hrg_lift_launch_step
 #define hrg_box_launch_reset hrg_lift_launch_reset
+#elif HRG_BOX && HRG_HULLS
+#define hrg_step_kernel hrg_step_kernel_box_hull   // the cube tasks with the arm links' convex hulls (hrgym_box_hulls.hip)
+#define hrg_reset_kernel hrg_reset_kernel_box_hull
+#define hrg_box_launch_step hrg_box_hull_launch_step
+#define hrg_box_launch_reset hrg_box_hull_launch_reset
 #elif HRG_BOX
 #define hrg_step_kernel hrg_step_kernel_box
 #define hrg_reset_kernel hrg_reset_kernel_box
@@ -3082,6 +3087,12 @@ extern "C" __attribute__((visibility("hidden"))) void hrg_lift_launch_reset(int 
                                                                              int64_t env_id0, hrg_box_state* boxes);
 #endif
 #if HRG_BASE_TU
+// ... of the hull variant of the cube kernels (hrgym_box_hulls.hip)
+extern "C" __attribute__((visibility("hidden"))) void hrg_box_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
+                                                                                float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
+                                                                                float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
+extern "C" __attribute__((visibility("hidden"))) void hrg_box_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
+                                                                                 int64_t env_id0, hrg_box_state* boxes);
 // ... of the hull variant of the ReachHuman kernels (hrgym_hulls.hip)
 extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
                                                                             float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
@@ -3089,7 +3100,7 @@ extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_step(int n
 extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
                                                                              int64_t env_id0);
 #endif
-#if HRG_HULLS
+#if HRG_HULLS && !HRG_BOX
 extern "C" void hrg_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
                                      int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, StepOrder ord) {
   hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, (ObjState*)nullptr, n_envs, ord);
@@ -3131,6 +3142,8 @@ extern "C" void hrg_box_launch_reset(int n_envs, hipStream_t st, const DevModel*
 #define hrg_debug_stamps hrg_debug_stamps_stack
 #elif HRG_HAMMER
 #define hrg_debug_stamps hrg_debug_stamps_hammer
+#elif HRG_BOX && HRG_HULLS
+#define hrg_debug_stamps hrg_debug_stamps_box_hull
 #elif HRG_HANDOVER
 #define hrg_debug_stamps hrg_debug_stamps_ho
 #elif HRG_LIFT
@@ -3164,6 +3177,9 @@ extern "C" int hrg_debug_stamps(double* out, int reset) {
 #elif HRG_STACK
 #define hrg_debug_envacc hrg_debug_envacc_stack
 #define hrg_debug_envcyc hrg_debug_envcyc_stack
+#elif HRG_BOX && HRG_HULLS
+#define hrg_debug_envacc hrg_debug_envacc_box_hull
+#define hrg_debug_envcyc hrg_debug_envcyc_box_hull
 #elif HRG_HANDOVER
 #define hrg_debug_envacc hrg_debug_envacc_ho
 #define hrg_debug_envcyc hrg_debug_envcyc_ho
@@ -3201,7 +3217,8 @@ struct hrg_batch {
   DevModel* d_model = nullptr;
   double* d_frames = nullptr;
   double* d_hull = nullptr;            // hull vertices of the arm links (robot_hulls)
-  bool hulls = false;                  // the hull variant of the ReachHuman kernels steps this batch (hrgym_hulls.hip)
+  bool hulls = false;                  // the hull variant of the ReachHuman kernels steps this batch (hrgym_hulls.hip) -- or of the cube kernels (hrgym_box_hulls.hip)
+  unsigned long long* d_mpr_fallback = nullptr;   // hull - cube pairs whose MPR did not converge (DevModel::mpr_fallback; hrg_batch_mpr_fallbacks)
   hrg_env_state* d_states = nullptr;
   double* d_rcaps = nullptr;
   double* d_hcaps = nullptr;
@@ -3398,7 +3415,9 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   hm->clips.frames = b->d_frames;
   hm->hull_dev = nullptr;
   if (desc->robot_hulls) {   // convex hulls of the arm links: the vertex table goes to device memory like the clip frames
-    if (desc->task != HRG_TASK_REACH) return bail(HRG_ERR_UNSUPPORTED, "robot_hulls: the hull variant of the step kernel exists for ReachHuman (the lean model) so far");
+    // the ReachHuman kernel and the cube kernel (hrg_step_kernel_box: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman with its box) have hull variants
+    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX))
+      return bail(HRG_ERR_UNSUPPORTED, "robot_hulls: the hull variants of the step kernel exist for ReachHuman and the cube tasks (PickPlace, Inspection, ReachHuman with reach_box)");
     b->hulls = true;
     if (!desc->hull_verts || desc->hull_off[0] != 0) return bail(HRG_ERR_INVALID, "robot_hulls: hull_verts / hull_off missing");
     for (int h = 0; h < HRG_NHULL; h++)
@@ -3407,6 +3426,10 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
     HIPCHK_C(hipMalloc(&b->d_hull, hbytes));
     HIPCHK_C(hipMemcpy(b->d_hull, desc->hull_verts, hbytes, hipMemcpyHostToDevice));
     hm->hull_dev = b->d_hull;
+    hull_centroids(desc->hull_verts, desc->hull_off, hm->hull_cen);
+    HIPCHK_C(hipMalloc(&b->d_mpr_fallback, sizeof(unsigned long long)));
+    HIPCHK_C(hipMemset(b->d_mpr_fallback, 0, sizeof(unsigned long long)));
+    hm->mpr_fallback = b->d_mpr_fallback;
   }
   HIPCHK_C(hipMalloc(&b->d_model, sizeof(DevModel)));
   HIPCHK_C(hipMemcpy(b->d_model, hm, sizeof(DevModel), hipMemcpyHostToDevice));
@@ -3450,7 +3473,7 @@ void hrg_batch_destroy(hrg_batch* b) {
   hipDeviceSynchronize();
   for (auto& p : b->events) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
   for (auto& p : b->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_hull); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
+  hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
   delete b;
 }
 
@@ -3461,6 +3484,7 @@ int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void*
   else if (b->task == HRG_TASK_STACKING) hrg_stack_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_stacks);
   else if (b->task == HRG_TASK_LIFTING) hrg_lift_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (HRG_IS_HANDOVER(b->task)) hrg_ho_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
+  else if (b->task != HRG_TASK_REACH && b->hulls) hrg_box_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (b->task != HRG_TASK_REACH) hrg_box_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (b->hulls) hrg_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0);
   else hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(b->n_envs), 0, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes, b->n_envs);
@@ -3501,6 +3525,9 @@ int hrg_batch_step(hrg_batch* b, double* actions_dev, float* obs_dev, float* ter
   else if (HRG_IS_HANDOVER(b->task))
     hrg_ho_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                        b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
+  else if (b->task != HRG_TASK_REACH && b->hulls)
+    hrg_box_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
+                             b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
   else if (b->task != HRG_TASK_REACH)
     hrg_box_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                         b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
@@ -3642,6 +3669,18 @@ int hrg_batch_set_states(hrg_batch* b, const int32_t* envs_host, int32_t n, cons
     if (boxes_host) HIPCHK(hipMemcpyAsync(b->d_boxes + e, (const hrg_box_state*)boxes_host + k, sizeof(hrg_box_state), hipMemcpyHostToDevice, 0));
   }
   HIPCHK(hipDeviceSynchronize());
+  return HRG_OK;
+}
+
+int hrg_batch_mpr_fallbacks(hrg_batch* b, int64_t* count_host) {
+  if (!b || !count_host) return fail(HRG_ERR_INVALID, "null argument");
+  *count_host = 0;
+  if (!b->d_mpr_fallback) return HRG_OK;   // no hulls: no MPR
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  unsigned long long c = 0;
+  HIPCHK(hipMemcpy(&c, b->d_mpr_fallback, sizeof c, hipMemcpyDeviceToHost));
+  *count_host = (int64_t)c;
   return HRG_OK;
 }
 

@@ -202,3 +202,181 @@ DI void hull_lowest_wave(const HullRef& H, double* out) {
   const double tc = wave_sum(cnt);
   out[0] = wave_sum(sx) / tc; out[1] = wave_sum(sy) / tc; out[2] = zmin;
 }
+
+#if HRG_BOX
+// ------------------------------------------------------------------------------------------------ hull x cube: penetration by MPR
+// MuJoCo 2.1 (the version the reference pins) collides a mesh geom with a box through its convex-convex path: Minkowski Portal Refinement (Snethen, "XenoCollide",
+// Game Programming Gems 7), ONE contact per pair -- depth, direction, position.  Restated here from that description, wave-uniform like the GJK above: the hull's
+// support mapping is hull_support_wave (lanes = vertices), the cube's is closed form, and the portal (four points of the Minkowski difference hull - cube with their
+// witnesses, plus the candidate point) lives in the collide part of the LDS union (Lds::mpr), written by lane 0, read by every lane.
+#define HRG_MPR_TOLERANCE 1e-6    // mjOption.mpr_tolerance (MuJoCo 2.1 default): a support point this close to the portal's plane ends the refinement
+#define HRG_MPR_ITERATIONS 50     // mjOption.mpr_iterations (MuJoCo 2.1 default): bound on every loop of the routine; beyond it the pair is "not converged"
+#define HRG_MPR_EPS 2.220446049250313e-16   // zero test of the portal's sign decisions (double epsilon)
+enum { MPR_SEPARATED = 0, MPR_PENETRATING = 1, MPR_NOT_CONVERGED = 2 };
+
+// corner of the cube (rotation R row-major, centre p, half extents h) farthest along the world direction d: the sign of each component of d in the cube's frame
+DI void box_support(const double* R, const double* p, const double* h, const double* d, double* out) {
+  double s[3];
+  for (int a = 0; a < 3; a++) s[a] = R[a] * d[0] + R[3 + a] * d[1] + R[6 + a] * d[2] >= 0 ? h[a] : -h[a];
+  for (int k = 0; k < 3; k++) out[k] = p[k] + R[3 * k] * s[0] + R[3 * k + 1] * s[1] + R[3 * k + 2] * s[2];
+}
+
+// support point of the Minkowski difference hull - cube along d into portal slot k: hull vertex farthest along d minus cube corner farthest along -d
+DI void mpr_support(const HullRef& H, const double* bR, const double* bp, const double* bh, const double* d, int k) {
+  MprLds& P = g_L.mpr;
+  double a[3], b[3];
+  const double nd[3] = {-d[0], -d[1], -d[2]};
+  hull_support_wave(H, d, a);
+  box_support(bR, bp, bh, nd, b);
+  if (hrg_lane() == 0) { v3cpy(P.a[k], a); v3cpy(P.b[k], b); for (int c = 0; c < 3; c++) P.v[k][c] = a[c] - b[c]; }
+  wave_sync();
+}
+DI void mpr_copy(int dst, int src) {
+  MprLds& P = g_L.mpr;
+  if (hrg_lane() == 0) { v3cpy(P.v[dst], P.v[src]); v3cpy(P.a[dst], P.a[src]); v3cpy(P.b[dst], P.b[src]); }
+  wave_sync();
+}
+DI void mpr_normalize(double* d) { const double l = v3norm(d); if (l > 0) v3scl(d, d, 1.0 / l); }
+// normal of the portal triangle (v1, v2, v3), pointing away from v0
+DI void mpr_portal_dir(double* d) {
+  const MprLds& P = g_L.mpr;
+  double e1[3], e2[3];
+  v3sub(e1, P.v[2], P.v[1]); v3sub(e2, P.v[3], P.v[1]);
+  v3cross(d, e1, e2);
+  mpr_normalize(d);
+}
+// the candidate (slot 4) lies within the tolerance of the portal's plane along d
+DI bool mpr_reached(const double* d) {
+  const MprLds& P = g_L.mpr;
+  const double d4 = v3dot(P.v[4], d);
+  const double m = fmin(d4 - v3dot(P.v[1], d), fmin(d4 - v3dot(P.v[2], d), d4 - v3dot(P.v[3], d)));
+  return m <= HRG_MPR_TOLERANCE;
+}
+// the candidate replaces the portal vertex on the far side of the plane through v0, v4 that keeps the origin inside the new portal's cone
+DI void mpr_expand() {
+  const MprLds& P = g_L.mpr;
+  double c[3];
+  v3cross(c, P.v[4], P.v[0]);
+  int r;
+  if (v3dot(P.v[1], c) > 0) r = v3dot(P.v[2], c) > 0 ? 1 : 3;
+  else r = v3dot(P.v[3], c) > 0 ? 2 : 1;
+  mpr_copy(r, 4);
+}
+
+// Penetration of hull H and the cube (bR, bp, bh), `hc` = world position of the hull's vertex centroid (the interior point).  MPR_PENETRATING: depth > 0, the unit
+// normal n from the hull into the cube (moving the hull by -depth n separates the two), pos = half way between the two witnesses of the origin in the final portal.
+// MPR is not a minimum-depth method: n is the normal of the boundary face the ray from the interior point through the origin leaves by, not of the nearest one.
+// MPR_SEPARATED: the origin lies outside the Minkowski difference (or on its boundary).  MPR_NOT_CONVERGED: a loop ran out of HRG_MPR_ITERATIONS.  Wave-uniform.
+DI int mpr_hull_box_wave(const HullRef& H, const double* hc, const double* bR, const double* bp, const double* bh, double& depth, double* n, double* pos) {
+  MprLds& P = g_L.mpr;
+  const bool w0 = hrg_lane() == 0;
+  depth = 0; v3set(n, 0, 0, 0); v3set(pos, 0, 0, 0);
+  // ---- phase 1: portal discovery.  v0 = an interior point of the Minkowski difference (centroid of the hull - centre of the cube)
+  {
+    double v0[3];
+    v3sub(v0, hc, bp);
+    if (v0[0] == 0 && v0[1] == 0 && v0[2] == 0) v0[0] = 10 * HRG_MPR_EPS;   // on the origin: nudged, so that the ray from it has a direction
+    if (w0) { v3cpy(P.v[0], v0); v3cpy(P.a[0], hc); v3cpy(P.b[0], bp); }
+    wave_sync();
+  }
+  double d[3];
+  v3scl(d, P.v[0], -1.0);
+  mpr_normalize(d);
+  mpr_support(H, bR, bp, bh, d, 1);
+  {
+    const double t = v3dot(P.v[1], d);
+    if (t < HRG_MPR_EPS) return MPR_SEPARATED;   // the farthest point towards the origin does not pass it
+  }
+  v3cross(d, P.v[0], P.v[1]);
+  if (v3dot(d, d) < HRG_MPR_EPS) {   // the origin lies on the line v0 - v1
+    const double l = v3norm(P.v[1]);
+    if (!(l > 0)) return MPR_SEPARATED;   // ... on v1: the boundary, touching
+    depth = l;
+    v3scl(n, P.v[1], 1.0 / l);
+    for (int c = 0; c < 3; c++) pos[c] = 0.5 * (P.a[1][c] + P.b[1][c]);
+    return MPR_PENETRATING;
+  }
+  mpr_normalize(d);
+  mpr_support(H, bR, bp, bh, d, 2);
+  if (v3dot(P.v[2], d) < HRG_MPR_EPS) return MPR_SEPARATED;
+  {
+    double e1[3], e2[3];
+    v3sub(e1, P.v[1], P.v[0]); v3sub(e2, P.v[2], P.v[0]);
+    v3cross(d, e1, e2);
+    mpr_normalize(d);
+    if (v3dot(d, P.v[0]) > 0) {   // orient the portal's faces away from the origin: swap v1 and v2
+      mpr_copy(4, 1); mpr_copy(1, 2); mpr_copy(2, 4);
+      v3scl(d, d, -1.0);
+    }
+  }
+  bool found = false;
+#pragma unroll 1
+  for (int it = 0; it < HRG_MPR_ITERATIONS; it++) {
+    mpr_support(H, bR, bp, bh, d, 3);
+    if (v3dot(P.v[3], d) < HRG_MPR_EPS) return MPR_SEPARATED;
+    double c[3];
+    v3cross(c, P.v[1], P.v[3]);
+    double t = v3dot(c, P.v[0]);
+    int r = 0;
+    if (t < 0 && !(fabs(t) < HRG_MPR_EPS)) r = 2;   // the origin is outside the face (v1, v0, v3): v3 takes v2's place
+    else {
+      v3cross(c, P.v[3], P.v[2]);
+      t = v3dot(c, P.v[0]);
+      if (t < 0 && !(fabs(t) < HRG_MPR_EPS)) r = 1;   // ... outside (v3, v0, v2): v3 takes v1's place
+    }
+    if (!r) { found = true; break; }
+    mpr_copy(r, 3);
+    double e1[3], e2[3];
+    v3sub(e1, P.v[1], P.v[0]); v3sub(e2, P.v[2], P.v[0]);
+    v3cross(d, e1, e2);
+    mpr_normalize(d);
+  }
+  if (!found) return MPR_NOT_CONVERGED;
+  // ---- phase 2: refine the portal until the origin lies on its inner side (intersection) or a support point shows it outside (separation)
+  found = false;
+#pragma unroll 1
+  for (int it = 0; it < HRG_MPR_ITERATIONS; it++) {
+    mpr_portal_dir(d);
+    if (v3dot(d, P.v[1]) > -HRG_MPR_EPS) { found = true; break; }
+    mpr_support(H, bR, bp, bh, d, 4);
+    if (v3dot(P.v[4], d) < HRG_MPR_EPS || mpr_reached(d)) return MPR_SEPARATED;
+    mpr_expand();
+  }
+  if (!found) return MPR_NOT_CONVERGED;
+  // ---- phase 3: push the portal out to the boundary along its normal; the depth is the origin's distance to the final portal triangle
+  found = false;
+#pragma unroll 1
+  for (int it = 0; it < HRG_MPR_ITERATIONS; it++) {
+    mpr_portal_dir(d);
+    mpr_support(H, bR, bp, bh, d, 4);
+    if (mpr_reached(d)) { found = true; break; }
+    mpr_expand();
+  }
+  if (!found) return MPR_NOT_CONVERGED;
+  // the final portal's normal is the contact normal; the depth is the extent of the Minkowski difference along it (the support point's distance: the overlap of the
+  // two shapes' projections on n, how far the hull must move back along n to clear the cube), within the tolerance of the portal plane's distance from the origin
+  depth = v3dot(P.v[4], d);
+  if (!(depth > 0)) { depth = 0; return MPR_SEPARATED; }   // the origin on the boundary: touching, no contact at margin 0
+  v3cpy(n, d);
+  // position: barycentric coordinates of the origin in the tetrahedron (v0 .. v3) -- signed volumes -- applied to the witnesses on each shape, then the midpoint.
+  // A flat tetrahedron falls back to the coordinates of the origin's projection along the portal's normal in the triangle (v1, v2, v3).
+  double w[4], cr[3];
+  v3cross(cr, P.v[1], P.v[2]); w[0] = v3dot(cr, P.v[3]);
+  v3cross(cr, P.v[3], P.v[2]); w[1] = v3dot(cr, P.v[0]);
+  v3cross(cr, P.v[0], P.v[1]); w[2] = v3dot(cr, P.v[3]);
+  v3cross(cr, P.v[2], P.v[1]); w[3] = v3dot(cr, P.v[0]);
+  double sw = w[0] + w[1] + w[2] + w[3];
+  if (sw < HRG_MPR_EPS) {
+    w[0] = 0;
+    v3cross(cr, P.v[2], P.v[3]); w[1] = v3dot(cr, d);
+    v3cross(cr, P.v[3], P.v[1]); w[2] = v3dot(cr, d);
+    v3cross(cr, P.v[1], P.v[2]); w[3] = v3dot(cr, d);
+    sw = w[1] + w[2] + w[3];
+  }
+  const double inv = 1.0 / sw;
+#pragma unroll
+  for (int k = 0; k < 4; k++) for (int c = 0; c < 3; c++) pos[c] += w[k] * (P.a[k][c] + P.b[k][c]);
+  v3scl(pos, pos, 0.5 * inv);
+  return MPR_PENETRATING;
+}
+#endif

@@ -1515,6 +1515,33 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
         c.g1 = pl ? GEOM_FLOOR : GEOM_TABLE; c.g2 = GEOM_BOX; c.b1 = -1; c.b2 = BODY_BOX; c.dist = dist;
       }
     }
+#if HRG_HULLS
+    // hrg_model_desc.robot_hulls (cube kernel): the capsule - cube test above is the BROADPHASE of an arm link (geoms 0 .. 6).  A pair that passed runs the penetration
+    // of the link's CONVEX HULL with the cube by MPR (hrgym_hull.h), one pair at a time in lane order, the whole wave on the support mappings; ONE contact per pair
+    // (MuJoCo 2.1's convex path), so the second-point lanes stay empty for hull links.  A hull clear of the cube drops the pair; an MPR that does not converge keeps the
+    // capsule contact and counts itself (DevModel::mpr_fallback).  Normal from the link into the cube, dist = -depth, position = MPR's.
+    if (pass == 0 && m.robot_hulls) {
+      if (second && i < HRG_NHULL) hit = false;
+      uint64_t todo = __ballot(hit && cap_lane && !second && i < HRG_NHULL);
+      while (todo) {
+        const int src = __ffsll((unsigned long long)todo) - 1;
+        todo &= todo - 1;
+        const int lb = m.rcap_body[src];
+        const double* R = lb < 0 ? dm_->Rbase : L.kR[lb];
+        const double* p = lb < 0 ? dm_->m.base_pos : L.kp[lb];
+        const HullRef H = {dm_->hull_dev + 3 * m.hull_off[src], m.hull_off[src + 1] - m.hull_off[src], R, p};
+        double hc[3], dep, nn[3], pp[3];
+        m3mulv(hc, R, dm_->hull_cen[src]);
+        v3add(hc, hc, p);
+        const int r = mpr_hull_box_wave(H, hc, L.bR, bx.pos, hb, dep, nn, pp);
+        if (lane == src) {
+          if (r == MPR_SEPARATED) hit = false;
+          else if (r == MPR_PENETRATING) { v3cpy(c.n, nn); v3cpy(c.pos, pp); c.dist = -dep; }
+        }
+        if (r == MPR_NOT_CONVERGED && lane == 0) atomicAdd(dm_->mpr_fallback, 1ull);
+      }
+    }
+#endif
 #if HRG_HANDOVER
     if (pass == 0) { // RobotHumanHandoverCart._get_object_palm_contact_pos (476-505): does the cube touch the palm (= the collision capsule of the holding hand's body)?
       bool palm = false;

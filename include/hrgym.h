@@ -442,6 +442,13 @@ int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t
  * pad} = 152 bytes each, against the vertex table (verts_host, off_host[HRG_NHULL + 1]) -> out_host[n][10] = GJK distance hull - segment, witness on the hull 3, witness
  * on the segment 3, lowest point over a horizontal plane 3.  One wavefront per query runs the step kernel's own wave routines (csrc/hrgym_hull.h).  0 / -1. */
 int hrg_test_hull_queries(const double* verts_host, const int32_t* off_host, const void* queries_host, int32_t n, double* out_host);
+/* test tap of the hull variant of the cube kernels (no oracle counterpart: tests/hullbox_ref.py restates it): n queries {R[9] row-major, p[3] (link pose), box centre[3],
+ * box rotation[9] row-major, box half extents[3], hull, pad} = 224 bytes each -> out_host[n][9] = penetrating (1 / 0), depth, unit normal from the hull into the box 3,
+ * position 3, converged (1 / 0).  One wavefront per query runs the step kernel's own MPR routine (csrc/hrgym_hull.h, mpr_hull_box_wave).  0 / -1. */
+int hrg_test_hull_box_queries(const double* verts_host, const int32_t* off_host, const void* queries_host, int32_t n, double* out_host);
+/* hull - cube pairs (robot_hulls, cube tasks) whose MPR penetration did not converge within 50 iterations and kept the capsule contact, counted over the batch's life
+ * (every substep): count_host int64.  0 for a batch without hulls. */
+int hrg_batch_mpr_fallbacks(hrg_batch* b, int64_t* count_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the

@@ -1,0 +1,415 @@
+"""Hull x box on the GPU (robot_geometry="hull" in the cube kernels: hrg_step_kernel_box_hull).  -m gpu.
+
+1. the step kernel's MPR wave routine (hrg_test_hull_box_queries) against the numpy restatement (tests/hullbox_ref.py): random poses of all seven hulls and the
+   unit-cube known answers;
+2. the wiring against the unchanged oracle, which refines link x human and link x plane pairs but keeps capsules for link x cube: every env-step whose contact
+   list has no (arm link, cube) pair on either side is compared bit-exactly (contacts, info, done) and to RTOL (obs, reward, state);
+3. what the new pairs change: a cube inside a link's bounding capsule but clear of its hull is left alone, a cube inside the hull gets ONE contact that resolves;
+4. the steady state at the benchmark's size (bench.py's own batch, pre-roll and action pool).
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch  # noqa: F401  (first: the HIP library must bind to the HIP runtime torch ships -- the tap tests load it before any batch exists)
+
+import human_robot_gym_amd as hrg
+from human_robot_gym_amd._cstruct import CONST
+from human_robot_gym_amd.model import load_robot_hulls, robot_fk_numpy
+from helpers import RTOL, assert_state_close, compare_states_bulk, states_as_bytes
+from pp_scenarios import grasp_and_carry, put_box, random_actions
+import hullbox_ref as ref
+from test_hull_box import CUBE, kat_cases, rot
+
+pytestmark = pytest.mark.gpu
+
+NH = CONST["HRG_NHULL"]
+GEOM_BOX = CONST["HRG_NRCAP"] + CONST["HRG_NHB"] + 2
+GEOM_HUMAN0, GEOM_TABLE = CONST["HRG_NRCAP"], CONST["HRG_NRCAP"] + CONST["HRG_NHB"]
+QDT = np.dtype([("R", "f8", 9), ("p", "f8", 3), ("bp", "f8", 3), ("bR", "f8", 9), ("bh", "f8", 3), ("hull", "i4"), ("pad", "i4")])
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _run_tap(V, off, queries):
+    from human_robot_gym_amd._lib import load_library
+    lib = load_library()
+    q = np.zeros(len(queries), dtype=QDT)
+    assert QDT.itemsize == 224
+    for k, (h, R, p, bc, bR, bh) in enumerate(queries):
+        q[k] = (np.ravel(R), p, bc, np.ravel(bR), bh, h, 0)
+    out = np.zeros((len(queries), 9))
+    Vc, offc = np.ascontiguousarray(V, float), np.ascontiguousarray(off, np.int32)
+    assert lib.hrg_test_hull_box_queries(_p(Vc), _p(offc), q.ctypes.data_as(ctypes.c_void_p), len(queries), _p(out)) == 0
+    return out
+
+
+def _compare_tap(V, off, queries, got, min_exact=0.99):
+    """Verdicts (penetrating / separated) and converged flags identical; depth, normal, position to 1e-9 relative / 1e-10 absolute on at least `min_exact` of the
+    penetrating queries.  The rest took another path through MPR: its discrete choices (the support vertex, the portal vertex a new point replaces, the stop) meet
+    near-ties once the portal has shrunk, and a last-bit difference in a portal normal (FMA contraction on the GPU, BLAS order in numpy) can pick the other branch --
+    both answers are then valid MPR results within the tolerance.  Those must still agree in depth to 2 x mpr_tolerance and the GPU's answer must carry its own
+    certificate (the two shapes' projections on its normal overlap by exactly its depth)."""
+    pen = conv = exact = 0
+    for k, (h, R, p, bc, bR, bh) in enumerate(queries):
+        Vb = V[off[h]:off[h + 1]]
+        st, depth, n, pos = ref.mpr_penetration(Vb, R, p, bc, bR, bh)
+        assert got[k, 0] == (st == ref.PENETRATING), (k, h, st, got[k])
+        assert got[k, 8] == (st != ref.NOT_CONVERGED), (k, h, st, got[k])
+        conv += st != ref.NOT_CONVERGED
+        if st != ref.PENETRATING:
+            continue
+        pen += 1
+        g = got[k]
+        same = (abs(g[1] - depth) <= 1e-10 + 1e-9 * abs(depth) and np.all(np.abs(g[2:5] - n) <= 1e-10 + 1e-9 * np.abs(n)) and
+                np.all(np.abs(g[5:8] - pos) <= 1e-10 + 1e-9 * np.abs(pos)))
+        exact += same
+        if not same:
+            assert abs(g[1] - depth) <= 2 * ref.TOL, (k, h, g, depth)
+            cert = ref.support_value_hull(Vb, R, p, g[2:5]) - ref.support_value_box(bc, bR, bh, g[2:5])
+            assert abs(cert - g[1]) <= 1e-8 and abs(np.linalg.norm(g[2:5]) - 1) <= 1e-12, (k, h, g, cert)
+    assert exact >= min_exact * pen, (exact, pen)
+    return pen, conv, exact
+
+
+def test_wave_routine_matches_the_numpy_reference():
+    """>= 3000 random queries over the seven hulls (link 4: 2211 vertices) against 4 cm .. 10 cm boxes: far, grazing, shallow and deep placements."""
+    V, off = load_robot_hulls()
+    rng = np.random.RandomState(21)
+    queries = []
+    for k in range(3200):
+        h = k % NH
+        Vb = V[off[h]:off[h + 1]]
+        R, p = rot(rng), rng.uniform(-0.4, 0.4, 3)
+        bh = rng.uniform(0.02, 0.05, 3) if k % 4 == 0 else np.full(3, 0.02)
+        kind = (k // NH) % 4
+        if kind == 3:   # deep: near the hull's centroid
+            bc = R @ Vb.mean(axis=0) + p + rng.randn(3) * 0.01
+        else:           # far / grazing / shallow: around a surface vertex
+            bc = (Vb @ R.T + p)[rng.randint(len(Vb))] + rng.randn(3) * (0.06, 0.003, 0.015)[kind]
+        queries.append((h, R, p, bc, rot(rng), bh))
+    got = _run_tap(V, off, queries)
+    pen, conv, exact = _compare_tap(V, off, queries, got)
+    print(f"[hull_box tap] {len(queries)} queries: {pen} penetrating ({exact} on the same path to 1e-9), {conv} converged")
+    assert 0.2 * len(queries) < pen < 0.9 * len(queries)
+
+
+def test_wave_routine_unit_cube_known_answers():
+    cases = kat_cases()
+    V = np.tile(CUBE, (NH, 1))
+    off = np.arange(NH + 1, dtype=np.int32) * len(CUBE)
+    queries = [(i % NH, R, p, bc, bR, bh) for i, (name, R, p, bc, bR, bh, dep, n) in enumerate(cases)]
+    got = _run_tap(V, off, queries)
+    pen, conv, exact = _compare_tap(V, off, queries, got, min_exact=1.0)
+    for (name, R, p, bc, bR, bh, dep, n), g in zip(cases, got):
+        assert g[0] == (dep is not None), name
+        if dep is not None:
+            assert abs(g[1] - dep) <= 1e-12, (name, g[1], dep)
+            np.testing.assert_allclose(g[2:5], n, atol=1e-12, err_msg=name)
+
+
+# ---------------------------------------------------------------------------------------------------------------- wiring vs the oracle
+def _link_cube(pairs, ncon):
+    """per env: the contact list holds an (arm link 0..6, cube) pair"""
+    k = np.arange(pairs.shape[1])[None, :] < ncon[:, None]
+    return np.any(k & (pairs[:, :, 0] < NH) & (pairs[:, :, 1] == GEOM_BOX), axis=1)
+
+
+def _quat_mat(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def _near_link_cube(desc, pre, bpre, post, bpost, slack=0.01):
+    """per env: some arm link's bounding capsule came within reach of the cube during the step -- the contact list holds the last substep only, so an (arm link,
+    cube) pair of an earlier substep is caught here: capsule - box distance below the radius plus how far the capsule's end points and the cube moved, plus `slack`"""
+    h = np.array(desc.box_half[:])
+    t = np.linspace(0, 1, 24)[:, None]
+    out = np.zeros(len(pre), bool)
+    for e in range(len(pre)):
+        if bpre[e] is None:
+            continue
+        ends = []
+        for st in (pre[e], post[e]):
+            R, p = robot_fk_numpy(desc, np.asarray(list(st.qpos)[:8]))
+            ends.append([(p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p1[L][:]), p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p2[L][:]))
+                         for L in range(NH) if desc.rcap_body[L] >= 0])
+        cubes = [(np.array(b.pos[:]), _quat_mat(b.quat[:])) for b in (bpre[e], bpost[e])]
+        move = np.linalg.norm(cubes[0][0] - cubes[1][0])
+        for (a0, b0), (a1, b1), L in zip(ends[0], ends[1], [L for L in range(NH) if desc.rcap_body[L] >= 0]):
+            reach = desc.rcap_r[L] + max(np.linalg.norm(a1 - a0), np.linalg.norm(b1 - b0)) + move + slack
+            for (a, b), (c, Rc) in (((a0, b0), cubes[0]), ((a1, b1), cubes[1])):
+                P = (a + t * (b - a) - c) @ Rc
+                q = np.maximum(np.abs(P) - h, 0.0)
+                if np.sqrt((q * q).sum(axis=1)).min() < reach:
+                    out[e] = True
+    return out
+
+
+def _parity(env_id, kw, n_envs, n_steps, scenario, extra=None):
+    import torch
+    from oracle.oracle import OracleBatch
+    from human_robot_gym_amd._lib import HipBatch
+    extra = extra or {}
+    clips = hrg.synthetic_clips(3, seed=0, min_frames=300, max_frames=600)
+    mk = lambda: hrg.build_model_desc(kw, n_clips=clips.n_clips, env_id=env_id, robot_geometry="hull", **extra)  # noqa: E731
+    desc = mk()
+    O, G = OracleBatch(mk(), clips, n_envs), HipBatch(mk(), clips, n_envs)
+    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=1e-7)
+    rng = np.random.RandomState(4)
+    t = dict(compared=0, total=0, finger_cube=0, hull_refined=0, link_cube=0)
+    for k in range(n_steps):
+        a = scenario(k, [O, G], rng, n_envs, desc)
+        pre, bpre = [O.get_state(e) for e in range(n_envs)], [O.get_box(e) for e in range(n_envs)]
+        o_o, r_o, d_o, i_o = O.step(a)
+        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
+        torch.cuda.synchronize()
+        post = [O.get_state(e) for e in range(n_envs)]
+        pbox = [O.get_box(e) for e in range(n_envs)]
+        po, no = O.contacts()
+        pg, ng = G.contacts()
+        lc = _link_cube(po, no) | _link_cube(pg, ng) | (_near_link_cube(desc, pre, bpre, post, pbox) & (d_o == 0))
+        violent = np.array([i_o[e, 11] != 0 or max(abs(v) for v in post[e].qvel) > 5.0 or max(abs(v) for v in pbox[e].vel[:3]) > 5.0 for e in range(n_envs)])
+        chk = ~lc & ~violent
+        msg = f"{env_id} step {k}"
+        np.testing.assert_array_equal(ng[chk], no[chk], err_msg=msg)
+        np.testing.assert_array_equal(pg[chk], po[chk], err_msg=msg)
+        np.testing.assert_array_equal(i_g.cpu().numpy()[chk], i_o[chk], err_msg=msg)
+        np.testing.assert_array_equal(d_g.cpu().numpy()[chk], d_o[chk], err_msg=msg)
+        np.testing.assert_allclose(o_g.cpu().numpy()[chk], o_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
+        np.testing.assert_allclose(r_g.cpu().numpy()[chk], r_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
+        for e in range(n_envs):
+            if chk[e]:
+                assert_state_close(post[e], G.get_state(e), f"{msg} env {e}")
+                assert_state_close(pbox[e], G.get_box(e), f"{msg} env {e} box")
+            G.set_state(e, post[e])
+            G.set_box(e, pbox[e])
+        live = np.arange(po.shape[1])[None, :] < no[:, None]
+        sel = live & chk[:, None]
+        t["finger_cube"] += int((sel & (po[:, :, 0] >= NH) & (po[:, :, 0] < GEOM_HUMAN0) & (po[:, :, 1] == GEOM_BOX)).sum())
+        t["hull_refined"] += int((sel & (po[:, :, 0] < NH) & (po[:, :, 1] >= GEOM_HUMAN0) & (po[:, :, 1] < GEOM_BOX)).sum())
+        t["link_cube"] += int(lc.sum())
+        t["compared"] += int(chk.sum()); t["total"] += n_envs
+    t["mpr_fallbacks"] = G.mpr_fallbacks()
+    print(f"[hull_box parity] {env_id} {kw.get('shield_type')} {getattr(scenario, '__name__', '')}: {t}")
+    O.close(); G.close()
+    return t
+
+
+@pytest.mark.parametrize("shield", ["OFF", "SSM"])
+def test_pick_place_hull_matches_the_oracle_away_from_link_cube_pairs(shield):
+    kw = dict(shield_type=shield, horizon=40, reward_shaping=True, done_at_collision=False)
+    ta = _parity("PickPlaceHumanCart", kw, 16, 36, lambda k, b, rng, n, d: grasp_and_carry(k, b, rng, n, d))
+    tb = _parity("PickPlaceHumanCart", kw, 16, 30, lambda k, b, rng, n, d: random_actions(k, b, rng, n))
+    tc = _parity("PickPlaceHumanCart", kw, 16, 36, _fold_onto_table)
+    for t in (ta, tb, tc):
+        assert t["compared"] >= 0.5 * t["total"], t
+    assert ta["finger_cube"] > 0, ta
+    assert ta["hull_refined"] + tb["hull_refined"] + tc["hull_refined"] > 0, (ta, tb, tc)
+
+
+def _fold_onto_table(k, batches, rng, n_envs, desc):
+    """random small actions with the shoulder folding down: arm links come to rest on the table (hull-refined link x table contacts)"""
+    a = rng.uniform(-0.3, 0.3, (n_envs, 7))
+    a[:, 1] = 1.0
+    a[:, 2] = np.where(np.arange(n_envs) % 2 == 0, 0.6, -0.2)
+    return a
+
+
+def test_inspection_and_reach_box_hull_match_the_oracle():
+    kw = dict(shield_type="SSM", horizon=30, done_at_collision=False)
+    for env_id, extra in (("HumanObjectInspectionCart", {}), ("ReachHuman", dict(reach_box=True))):
+        from human_robot_gym_amd.mixed import task_env_kwargs
+        k2 = dict(kw, **task_env_kwargs(env_id)) if env_id != "ReachHuman" else kw
+        t = _parity(env_id, k2, 8, 12, lambda k, b, rng, n, d: random_actions(k, b, rng, n), extra)
+        assert t["compared"] >= 0.5 * t["total"], t
+
+
+# ---------------------------------------------------------------------------------------------------------------- behaviour of the new pairs
+def _seg_box_dist(a, b, c, h, m=400):
+    """distance of segment [a, b] to the axis-aligned box (centre c, half h), sampled finely along the segment"""
+    t = np.linspace(0, 1, m)[:, None]
+    P = a + t * (b - a)
+    q = np.maximum(np.abs(P - c) - h, 0.0)
+    return float(np.sqrt((q * q).sum(axis=1)).min())
+
+
+def _one_step_batch(geometry, n_cycles):
+    from human_robot_gym_amd._lib import HipBatch
+    clips = hrg.synthetic_clips(1, seed=0, min_frames=300, max_frames=600)
+    kw = dict(shield_type="OFF", horizon=100, done_at_collision=False)
+    d = hrg.build_model_desc(kw, n_clips=1, env_id="PickPlaceHumanCart", robot_geometry=geometry)
+    d.n_cycles = n_cycles
+    G = HipBatch(d, clips, 1)
+    G.reset()
+    return G, hrg.build_model_desc(kw, n_clips=1, env_id="PickPlaceHumanCart")
+
+
+def _cap_world(desc, qpos, j):
+    R, p = robot_fk_numpy(desc, np.asarray(qpos))
+    b = desc.rcap_body[j]
+    return p[b] + R[b] @ np.array(desc.rcap_p1[j][:]), p[b] + R[b] @ np.array(desc.rcap_p2[j][:])
+
+
+def _link_world(desc, qpos, L):
+    """world pose of arm link L's body, its bounding capsule's end points and radius, its hull's world vertices"""
+    V, off = load_robot_hulls()
+    R, p = robot_fk_numpy(desc, np.asarray(qpos))
+    b = desc.rcap_body[L]
+    Rb, pb = R[b], p[b]
+    a1, a2 = pb + Rb @ np.array(desc.rcap_p1[L][:]), pb + Rb @ np.array(desc.rcap_p2[L][:])
+    return Rb, pb, a1, a2, desc.rcap_r[L], V[off[L]:off[L + 1]]
+
+
+def _find_placement(desc, qpos, h, want_hull_hit, rng):
+    """a cube centre (axis-aligned, half h) overlapping link 5's or 6's bounding capsule by >= 1 mm, and either clear of the hull (numpy MPR: separated, and no
+    hull vertex within 1 mm of the box) or inside it by 2 .. 8 mm"""
+    for L in (5, 6):
+        Rb, pb, a1, a2, r, Vb = _link_world(desc, qpos, L)
+        for _ in range(4000):
+            t = rng.uniform(0.1, 0.9)
+            u = rng.randn(3); u -= (u @ (a2 - a1)) * (a2 - a1) / max((a2 - a1) @ (a2 - a1), 1e-12); u /= np.linalg.norm(u)
+            c = a1 + t * (a2 - a1) + u * (r + h - rng.uniform(0.002, 0.012))
+            if _seg_box_dist(a1, a2, c, h) > r - 0.001:
+                continue
+            if any(_seg_box_dist(*_cap_world(desc, qpos, j)[:2], c, h) < desc.rcap_r[j] + 0.003 for j in range(CONST["HRG_NRCAP"]) if j != L and desc.rcap_body[j] >= 0):
+                continue   # clear of every other robot geom
+            st, depth, n, pos = ref.mpr_penetration(Vb, Rb, pb, c, np.eye(3), np.full(3, h))
+            if want_hull_hit and st == ref.PENETRATING and 0.002 <= depth <= 0.008:
+                return L, c
+            if not want_hull_hit and st == ref.SEPARATED:
+                gap = np.maximum(np.abs(Vb @ Rb.T + pb - c) - h, 0.0)
+                if np.sqrt((gap * gap).sum(axis=1)).min() > 0.001:
+                    return L, c
+    raise AssertionError("no placement found")
+
+
+def test_cube_inside_the_capsule_but_clear_of_the_hull_is_left_alone():
+    G_c, desc = _one_step_batch("capsule", 1)
+    G_h, _ = _one_step_batch("hull", 1)
+    import torch
+    qpos = list(G_h.get_state(0).qpos)
+    assert np.allclose(qpos, list(G_c.get_state(0).qpos))
+    h = desc.box_half[0]
+    L, c = _find_placement(desc, qpos, h, False, np.random.RandomState(2))
+    put_box([G_c, G_h], 0, pos=c, quat=[1, 0, 0, 0], vel=[0] * 6)
+    a = torch.zeros((1, 7), dtype=torch.float64, device="cuda")
+    for G in (G_c, G_h):
+        G.step(a)
+    torch.cuda.synchronize()
+    (pc, nc), (ph, nh) = G_c.contacts(), G_h.contacts()
+    pair = lambda P, N: [tuple(P[0, i]) for i in range(N[0])]  # noqa: E731
+    assert (L, GEOM_BOX) in pair(pc, nc), pair(pc, nc)           # the capsule reports the pair ...
+    assert (L, GEOM_BOX) not in pair(ph, nh), pair(ph, nh)       # ... the hull does not
+    bc_, bh_ = G_c.get_box(0), G_h.get_box(0)
+    v_c, v_h = np.array(bc_.vel[:3]), np.array(bh_.vel[:3])
+    assert (L, GEOM_BOX) in pair(pc, nc) and all(g1 == GEOM_TABLE or g2 != GEOM_BOX for g1, g2 in pair(ph, nh)), (pair(pc, nc), pair(ph, nh))
+    assert np.abs(v_h[:2]).max() < 1e-9 and np.abs(np.array(bh_.vel[3:])).max() < 1e-9   # the hull variant's cube only falls
+    assert np.abs(v_c - v_h).max() > 1e-3                                                # the capsule pushed it
+    print(f"[hull_box] link {L}: capsule pushes the cube to {v_c}, hull leaves it at {v_h}; fallbacks {G_h.mpr_fallbacks()}")
+    G_c.close(); G_h.close()
+
+
+def test_cube_inside_the_hull_gets_one_contact_that_resolves():
+    import torch
+    G1, desc = _one_step_batch("hull", 1)
+    qpos = list(G1.get_state(0).qpos)
+    h = desc.box_half[0]
+    L, c = _find_placement(desc, qpos, h, True, np.random.RandomState(3))
+    put_box([G1], 0, pos=c, quat=[1, 0, 0, 0], vel=[0] * 6)
+    a = torch.zeros((1, 7), dtype=torch.float64, device="cuda")
+    G1.step(a)
+    torch.cuda.synchronize()
+    p1, n1 = G1.contacts()
+    pairs = [tuple(p1[0, i]) for i in range(n1[0])]
+    assert pairs.count((L, GEOM_BOX)) == 1, pairs            # one contact per hull - cube pair (the capsule would give two along a face)
+    fb1 = G1.mpr_fallbacks()
+    G1.close()
+    # the same placement stepped at the normal rate: the contact pushes the cube out of the hull
+    G, _ = _one_step_batch("hull", desc.n_cycles)
+    put_box([G], 0, pos=c, quat=[1, 0, 0, 0], vel=[0] * 6)
+    for _ in range(3):
+        G.step(a)
+    torch.cuda.synchronize()
+    qpos2, bx = list(G.get_state(0).qpos), G.get_box(0)
+    Rb, pb, *_ , Vb = _link_world(desc, qpos2, L)
+    from pp_scenarios import mat2quat  # noqa: F401  (quat convention: w, x, y, z)
+    w, x, y, z = bx.quat[:]
+    Rc = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                   [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    st, depth, n, pos = ref.mpr_penetration(Vb, Rb, pb, np.array(bx.pos[:]), Rc, np.full(3, h))
+    assert st != ref.PENETRATING or depth < 1e-3, (st, depth)
+    print(f"[hull_box] link {L}: one contact; after 3 steps depth {depth if st == ref.PENETRATING else 0.0:.2e}; fallbacks {fb1} / {G.mpr_fallbacks()}")
+    G.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- steady state at the benchmark's size
+def test_pick_place_hull_steady_state_at_bench_size():
+    """bench.py's PickPlaceHumanCart batch with hulls (8192 envs, SSM) after its pre-roll: finite outputs, no more simulation crashes than the capsule kernel on
+    the same action pool, and oracle parity on the env-steps without an (arm link, cube) pair."""
+    import torch
+    import bench
+    from oracle.oracle import OracleBatch
+    crashes = {}
+    for geom in ("capsule", "hull"):
+        W = bench.bench_workload("PickPlaceHumanCart", "SSM", robot_geometry=geom)
+        G, desc, _, _ = bench.make_bench_batch(W)
+        n = W["n"]
+        assert n == 8192
+        pool = bench.bench_action_pool(n, G.device)
+        pre = bench.bench_preroll_steps(desc) + 20
+        crash = torch.zeros((), dtype=torch.int64, device=G.device)
+        for k in range(pre):
+            G.step(pool[k % len(pool)])
+            crash += (G.info[:, 11] != 0).sum()
+        torch.cuda.synchronize()
+        crashes[geom] = int(crash.item())
+        for t in (G.obs, G.reward, G.term_obs):
+            assert torch.isfinite(t).all(), geom
+        if geom == "capsule":
+            G.close()
+            continue
+        clips = bench._bench_clips("PickPlaceHumanCart", 0)
+        O = OracleBatch(hrg.build_model_desc(W["env_kwargs"], n_clips=clips.n_clips, env_id="PickPlaceHumanCart", **W["wrappers"]), clips, n, env_id0=0)
+        idx = np.arange(n, dtype=np.int32)
+        st, bx = G.get_states(idx)
+        O.set_states_all(st, bx)
+        cmp_n = tot = lc_n = 0
+        for k in range(3):
+            a = pool[(pre + k) % len(pool)]
+            G.step(a)
+            torch.cuda.synchronize()
+            pre_o, pre_b = O.get_states_all(box=True)[:2]
+            o_o, r_o, d_o, i_o = O.step_parallel(a.cpu().numpy().copy())
+            post = O.get_states_all(box=True)
+            o_g, r_g, d_g, i_g = [x.cpu().numpy() for x in (G.obs, G.reward, G.done, G.info)]
+            po, no = O.contacts()
+            pg, ng = G.contacts()
+            lc = _link_cube(po, no) | _link_cube(pg, ng)
+            lc |= _near_link_cube(desc, pre_o, pre_b, post[0], post[1]) & (d_o == 0)
+            qv = lambda s: np.abs(np.ascontiguousarray(states_as_bytes(s)[:, _QOFF:_QOFF + 64]).view(np.float64)).max(axis=1)  # noqa: E731
+            violent = (i_o[:, 11] != 0) | (qv(pre_o) > 5.0) | (qv(post[0]) > 5.0)
+            st_g, bx_g = G.get_states(idx)
+            ok, why = compare_states_bulk(post[0], st_g, skip=("ncon", "con_pairs", "n_prev", "prev_pairs", "ltt.dur", "ltt.jerk", "safe_path.dur", "safe_path.jerk"))
+            okb, whyb = compare_states_bulk(post[1], bx_g)
+            con_same = (no == ng) & np.all(po == pg, axis=(1, 2))
+            chk = ~lc & ~violent
+            good = chk & con_same & ok & okb
+            good &= np.all(i_g == i_o, axis=1) & (d_g == d_o)
+            good &= np.all(np.abs(o_g - o_o) <= 1e-6 + RTOL * np.abs(o_o), axis=1) & (np.abs(r_g - r_o) <= 1e-6 + RTOL * np.abs(r_o))
+            cmp_n += int(good.sum()); tot += int(chk.sum()); lc_n += int(lc.sum())
+            G.set_states(idx, post[0], post[1])
+        share = cmp_n / max(tot, 1)
+        fb = G.mpr_fallbacks()
+        print(f"[hull_box steady] crashes capsule {crashes['capsule']} hull {crashes['hull']}; link-cube env-steps {lc_n} of {3 * n}; parity {cmp_n} / {tot} = {share:.4f}; "
+              f"MPR fallbacks {fb} over {pre + 3} steps ({fb / ((pre + 3) * n * desc.n_cycles):.2e} per env-substep)")
+        O.close(); G.close()
+        assert share >= 0.9, (cmp_n, tot)
+    assert crashes["hull"] <= crashes["capsule"], crashes
+
+
+from human_robot_gym_amd._cstruct import EnvState  # noqa: E402
+_QOFF = EnvState.qvel.offset
