@@ -27,7 +27,7 @@ EXPORTS = [
     "hrg_batch_kernel_time", "hrg_batch_enable_taps", "hrg_box_bytes", "hrg_batch_get_box", "hrg_batch_set_box", "hrg_batch_get_states", "hrg_batch_set_states",
     "hrg_batch_check_actions", "hrg_stack_bytes", "hrg_batch_get_stack", "hrg_batch_set_stack", "hrg_batch_launch_order",
     "hrg_hammer_bytes", "hrg_batch_get_hammer", "hrg_batch_set_hammer", "hrg_test_hull_queries",
-    "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks",
+    "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks", "hrg_batch_pose_table_bytes", "hrg_debug_pose_compare",
 ]
 
 
@@ -106,6 +106,8 @@ def load_library():
     lib.hrg_test_hull_queries.argtypes = [vp, vp, vp, i32, vp]
     lib.hrg_test_hull_box_queries.argtypes = [vp, vp, vp, i32, vp]
     lib.hrg_batch_mpr_fallbacks.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.hrg_batch_pose_table_bytes.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.hrg_debug_pose_compare.argtypes = [vp, vp, i32, vp]
     lib.hrg_stack_bytes.restype = ctypes.c_size_t
     lib.hrg_batch_get_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.hrg_batch_set_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
@@ -297,6 +299,12 @@ class HipBatch:
         """Hull - cube pairs (robot_geometry="hull", cube tasks) whose MPR did not converge and kept the capsule contact, summed over every substep since create."""
         c = ctypes.c_int64()
         _check(self.lib, self.lib.hrg_batch_mpr_fallbacks(self.h, ctypes.byref(c)))
+        return c.value
+
+    def pose_table_bytes(self):
+        """Device memory of the batch's human pose table (built at create for ReachHuman and CollaborativeLiftingCart; 0 for the tasks whose kernels keep the live tree kinematics)."""
+        c = ctypes.c_int64()
+        _check(self.lib, self.lib.hrg_batch_pose_table_bytes(self.h, ctypes.byref(c)))
         return c.value
 
     def enable_taps(self, on=True):

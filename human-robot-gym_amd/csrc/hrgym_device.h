@@ -44,6 +44,14 @@
 #define HRG_HAMMER 0  // HRG_HAMMER=1 (hrgym_hammer.hip, HRG_BOX=0): CollaborativeHammeringCart -- board + nail + hammer, a 24-DoF system in three 8-wide blocks; its own collision tail and solver
 #endif
 #define HRG_BASE_TU (!HRG_BOX && !HRG_STACK && !HRG_HAMMER && !HRG_HULLS)   // hrgym_hip.hip itself: the ReachHuman kernels, the pre-check kernel and the host side (C ABI)
+// The human pose comes from the per-frame pose table (DevModel::pose_tab, built once per batch) in the ReachHuman kernels (capsule and hull) and the lifting
+// kernel; the hand-mocap variants (handover, stacking, hammering) need the hand bodies' rotations, and the cube kernels keep the live tree kinematics too (DESIGN.md
+// section 6).  Host side: hrg_task_uses_pose_table.
+#define HRG_POSE_TABLE ((!HRG_BOX && !HRG_STACK && !HRG_HAMMER) || HRG_LIFT)
+#define HRG_POSE_HCAP 0                          // pose table entry (doubles): the 24 capsules (p1, p2) | the 23 sites | the root term c
+#define HRG_POSE_SITE (6 * HRG_NHB)
+#define HRG_POSE_ROOT (HRG_POSE_SITE + 3 * HRG_NHJ)
+#define HRG_POSE_DIM (HRG_POSE_ROOT + 3)         // 216 doubles = 1728 B: 16-byte multiple, so every entry starts 16-byte aligned
 #define NVT HRG_NVT
 #if HRG_HAMMER
 #define NVS HRG_NV_HAMMER       // robot tree | board + nail (+ pad) | hammer (+ 2 pads)
@@ -140,7 +148,8 @@ struct DevModel {
   int32_t chk_i[32], chk_j[32];
   // animation clips (frames in device memory)
   hrg_clip_table clips;
-  const double* hull_dev;    // hull vertices of the arm links in device memory (m.robot_hulls; m.hull_verts is the creator's host pointer)
+  const double* pose_tab;    // per-frame human pose of the clip set, root yaw and episode offset factored out (HRG_POSE_TABLE; null for the hand-mocap tasks)
+  const double* hull_dev;   // hull vertices of the arm links in device memory (m.robot_hulls; m.hull_verts is the creator's host pointer)
   double hull_cen[HRG_NHULL][3];   // vertex centroid of each hull, body frame: the interior point of the hull - cube penetration (MPR)
   unsigned long long* mpr_fallback;   // device counter: hull - cube pairs whose MPR did not converge and kept the capsule contact (hrg_batch_mpr_fallbacks)
 };

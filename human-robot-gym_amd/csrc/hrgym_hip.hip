@@ -3050,6 +3050,62 @@ __global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void hrg_check
   const bool hit = config_collides(dm_, lane);
   if (lane == 0) collides[e] = hit ? 1 : 0;
 }
+
+// The pose table (DevModel::pose_tab, HRG_POSE_TABLE): one wave per frame of the clip set, launched once at batch create.  The root pose chain of
+// human_pose_fk without the episode's offsets (pelvis at the origin, rotation qbi qa), the tree kinematics of human_fk_lanes, then the capsules, the sites
+// and the root term c copied out: human_pose_from_table adds the episode's offsets back.  Every variant shares the table (the tree is the same model).
+__global__ __launch_bounds__(64) void hrg_pose_table_kernel(const DevModel* __restrict__ dm_, double* __restrict__ tab) {
+  const ModelPtr dm = uniform_model(dm_);
+  const int lane = hrg_lane();
+  const int64_t f = (int64_t)blockIdx.x;
+  if (f >= dm->clips.total_frames) return;
+  Lds& L = g_L;
+  int clip = 0;
+  for (int c = 1; c < dm->clips.n_clips; c++)
+    if (f >= dm->clips.clip_offset[c]) clip = c;
+  const double* fr = dm->clips.frames + f * HRG_FRAME_DIM;
+  double qbi[4], qa[4], c[3], mq[4];
+  human_root(dm, clip, fr, c, qbi, qa);
+  quatmul(mq, qbi, qa);
+  const double p0[3] = {0, 0, 0};
+  human_fk_lanes(dm_, lane, p0, mq, fr + 7);
+  double* e = tab + f * HRG_POSE_DIM;
+  for (int k = lane; k < 6 * HRG_NHB; k += 64) e[HRG_POSE_HCAP + k] = (&L.hcap[0][0])[k];
+  for (int k = lane; k < 3 * HRG_NHJ; k += 64) e[HRG_POSE_SITE + k] = (&L.st.human_site[0][0])[k];
+  if (lane < 3) e[HRG_POSE_ROOT + lane] = c[lane];
+}
+
+// test tap (hrg_debug_pose_compare): the human pose at frame `at` of clip `clip` under the episode offsets pos_off / rot_off, both ways -- the live chain
+// (human_root, the offsets composed before the tree kinematics) and the pose table -- one query per wave: out = [live hcap 144 | live sites 69 | table
+// hcap 144 | table sites 69]
+struct PoseQuery { double pos_off[3], rot_off[4]; int32_t clip, at; };
+__global__ __launch_bounds__(64) void hrg_pose_compare_kernel(const DevModel* __restrict__ dm_, const PoseQuery* __restrict__ q, int n, double* __restrict__ out) {
+  const ModelPtr dm = uniform_model(dm_);
+  const int lane = hrg_lane(), k = (int)blockIdx.x;
+  if (k >= n) return;
+  Lds& L = g_L;
+  hrg_env_state& s = L.st;
+  if (lane < 3) s.human_pos_offset[lane] = q[k].pos_off[lane];
+  if (lane < 4) s.human_rot_offset[lane] = q[k].rot_off[lane];
+  wave_sync();
+  const int clip = __builtin_amdgcn_readfirstlane(q[k].clip), at = __builtin_amdgcn_readfirstlane(q[k].at);
+  const int64_t f = dm->clips.clip_offset[clip] + at;
+  const double* fr = dm->clips.frames + f * HRG_FRAME_DIM;
+  double qbi[4], qa[4], c[3], mp[3], mq[4], q1[4];
+  human_root(dm, clip, fr, c, qbi, qa);
+  v3add(mp, c, s.human_pos_offset);
+  quatmul(q1, s.human_rot_offset, qbi);
+  quatmul(mq, q1, qa);
+  human_fk_lanes(dm_, lane, mp, mq, fr + 7);
+  constexpr int NP = 6 * HRG_NHB + 3 * HRG_NHJ;
+  double* o = out + (size_t)k * 2 * NP;
+  for (int j = lane; j < 6 * HRG_NHB; j += 64) o[j] = (&L.hcap[0][0])[j];
+  for (int j = lane; j < 3 * HRG_NHJ; j += 64) o[6 * HRG_NHB + j] = (&s.human_site[0][0])[j];
+  wave_sync();
+  human_pose_from_table(dm, lane, f);
+  for (int j = lane; j < 6 * HRG_NHB; j += 64) o[NP + j] = (&L.hcap[0][0])[j];
+  for (int j = lane; j < 3 * HRG_NHJ; j += 64) o[NP + 6 * HRG_NHB + j] = (&s.human_site[0][0])[j];
+}
 #endif
 
 // launch shims of the cube variant: defined by hrgym_box.hip (this file compiled with HRG_BOX=1), called by the host side below
@@ -3216,6 +3272,8 @@ struct hrg_batch {
   int64_t env_id0 = 0;
   DevModel* d_model = nullptr;
   double* d_frames = nullptr;
+  double* d_pose = nullptr;            // per-frame human pose table (DevModel::pose_tab): the tasks whose kernels read it (hrg_task_uses_pose_table)
+  size_t pose_bytes = 0;
   double* d_hull = nullptr;            // hull vertices of the arm links (robot_hulls)
   bool hulls = false;                  // the hull variant of the ReachHuman kernels steps this batch (hrgym_hulls.hip) -- or of the cube kernels (hrgym_box_hulls.hip)
   unsigned long long* d_mpr_fallback = nullptr;   // hull - cube pairs whose MPR did not converge (DevModel::mpr_fallback; hrg_batch_mpr_fallbacks)
@@ -3248,6 +3306,10 @@ static int32_t* fair_table(int device) {
   }
   return tab[device];
 }
+
+// the kernels built with HRG_POSE_TABLE: ReachHuman (hrgym_hip.hip, hrgym_hulls.hip) and lifting (hrgym_lift.hip); every other task steps with a cube kernel
+// or a hand-mocap kernel, which keep the live tree kinematics
+static bool hrg_task_uses_pose_table(int task) { return task == HRG_TASK_REACH || task == HRG_TASK_LIFTING; }
 
 static void mat_from_quat(double* M, const double* q) {
   double w = q[0], x = q[1], y = q[2], z = q[3];
@@ -3413,6 +3475,12 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   HIPCHK_C(hipMemcpy(b->d_frames, clips->frames, fbytes, hipMemcpyHostToDevice));
   hm->clips = *clips;
   hm->clips.frames = b->d_frames;
+  hm->pose_tab = nullptr;
+  if (hrg_task_uses_pose_table(desc->task)) {   // filled by hrg_pose_table_kernel once the model is on the device
+    b->pose_bytes = sizeof(double) * HRG_POSE_DIM * (size_t)clips->total_frames;
+    HIPCHK_C(hipMalloc(&b->d_pose, b->pose_bytes));
+    hm->pose_tab = b->d_pose;
+  }
   hm->hull_dev = nullptr;
   if (desc->robot_hulls) {   // convex hulls of the arm links: the vertex table goes to device memory like the clip frames
     // the ReachHuman kernel and the cube kernel (hrg_step_kernel_box: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman with its box) have hull variants
@@ -3433,6 +3501,11 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   }
   HIPCHK_C(hipMalloc(&b->d_model, sizeof(DevModel)));
   HIPCHK_C(hipMemcpy(b->d_model, hm, sizeof(DevModel), hipMemcpyHostToDevice));
+  if (b->d_pose) {
+    hipLaunchKernelGGL(hrg_pose_table_kernel, dim3((unsigned)clips->total_frames), dim3(64), 0, 0, b->d_model, b->d_pose);
+    HIPCHK_C(hipGetLastError());
+    HIPCHK_C(hipDeviceSynchronize());
+  }
   // ---- state ----
   HIPCHK_C(hipMalloc(&b->d_states, sizeof(hrg_env_state) * (size_t)n_envs));
   std::vector<hrg_env_state> init((size_t)n_envs);
@@ -3473,8 +3546,36 @@ void hrg_batch_destroy(hrg_batch* b) {
   hipDeviceSynchronize();
   for (auto& p : b->events) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
   for (auto& p : b->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
+  hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_pose); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
   delete b;
+}
+
+int hrg_batch_pose_table_bytes(hrg_batch* b, int64_t* bytes_host) {
+  if (!b || !bytes_host) return fail(HRG_ERR_INVALID, "null argument");
+  *bytes_host = (int64_t)b->pose_bytes;
+  return HRG_OK;
+}
+
+int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, double* out_host) {
+  if (!b || !queries_host || !out_host || n <= 0) return fail(HRG_ERR_INVALID, "null argument or n <= 0");
+  if (!b->d_pose) return fail(HRG_ERR_UNSUPPORTED, "this batch's task keeps the live tree kinematics (no pose table)");
+  DevModel hm;
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpy(&hm, b->d_model, sizeof hm, hipMemcpyDeviceToHost));
+  const PoseQuery* qh = (const PoseQuery*)queries_host;
+  for (int k = 0; k < n; k++)
+    if (qh[k].clip < 0 || qh[k].clip >= hm.clips.n_clips || qh[k].at < 0 || qh[k].at >= hm.clips.clip_len[qh[k].clip]) return fail(HRG_ERR_INVALID, "query outside the clip set");
+  const size_t ob = sizeof(double) * 2 * (6 * HRG_NHB + 3 * HRG_NHJ) * (size_t)n;
+  PoseQuery* dq = nullptr;
+  double* dout = nullptr;
+  bool ok = false;
+  if (hipMalloc(&dq, sizeof(PoseQuery) * (size_t)n) == hipSuccess && hipMalloc(&dout, ob) == hipSuccess &&
+      hipMemcpy(dq, qh, sizeof(PoseQuery) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
+    hipLaunchKernelGGL(hrg_pose_compare_kernel, dim3((unsigned)n), dim3(64), 0, 0, b->d_model, dq, (int)n, dout);
+    ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, dout, ob, hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  hipFree(dq); hipFree(dout);
+  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_pose_compare: device allocation / copy / launch failed");
 }
 
 int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {

@@ -335,24 +335,66 @@ DI void human_fk_lanes(const DevModel* __restrict__ dm_, int lane, const double*
   wave_sync();
 }
 
+// root pose chain (human_env.py:1736-1763) of frame `fr` of clip `clip` without the episode's offsets: pelvis at c + human_pos_offset with the rotation
+// human_rot_offset qbi qa, where c = Rbi (frame position + clip offset) and qbi = human base quat x clip quat
+DI void human_root(ModelPtr dm, int clip, const double* fr, double* c, double* qbi, double* qa) {
+  const double qi[4] = {dm->clips.clip_quat[clip][3], dm->clips.clip_quat[clip][0], dm->clips.clip_quat[clip][1], dm->clips.clip_quat[clip][2]};
+  double Rbi[9], pa[3];
+  quatmul(qbi, dm->m.human_base_quat, qi);
+  quat2mat(Rbi, qbi);
+  for (int a = 0; a < 3; a++) pa[a] = fr[a] + dm->clips.clip_pos_offset[clip][a];
+  m3mulv(c, Rbi, pa);
+  qa[0] = fr[6]; qa[1] = fr[3]; qa[2] = fr[4]; qa[3] = fr[5];
+}
+
+// pose of the human from pose table entry f (DevModel::pose_tab, hrg_pose_table_kernel): every capsule end point and site is
+// x = human_pos_offset + c + R(human_rot_offset) Y, where (Y, c) = the entry's points (the tree kinematics under pelvis position 0 and rotation qbi qa) and
+// root term.  Lanes 0..23 take one capsule, lanes 24..46 one site -> L.hcap, human_site
+DI void human_pose_from_table(ModelPtr dm, int lane, int64_t f) {
+  Lds& L = g_L;
+  hrg_env_state& s = L.st;
+  const double* e = dm->pose_tab + f * HRG_POSE_DIM;
+  const bool cap = lane < HRG_NHB, site = !cap && lane < HRG_NHB + HRG_NHJ;
+  double y[6] = {0, 0, 0, 0, 0, 0};
+  if (cap) {
+    const double2* p = (const double2*)(e + HRG_POSE_HCAP + 6 * lane);
+    const double2 a = p[0], b = p[1], d = p[2];
+    y[0] = a.x; y[1] = a.y; y[2] = b.x; y[3] = b.y; y[4] = d.x; y[5] = d.y;
+  } else if (site) {
+    const double* p = e + HRG_POSE_SITE + 3 * (lane - HRG_NHB);
+    y[0] = p[0]; y[1] = p[1]; y[2] = p[2];
+  }
+  // the root term: wave-uniform, through the scalar cache
+  const double __attribute__((address_space(4)))* ec = (const double __attribute__((address_space(4)))*)(e + HRG_POSE_ROOT);
+  double R[9], o[3], x[3];
+  quat2mat(R, s.human_rot_offset);
+  v3add(o, s.human_pos_offset, ec);
+  m3mulv(x, R, y);
+  if (cap) {
+    v3add(&L.hcap[lane][0], o, x);
+    m3mulv(x, R, y + 3);
+    v3add(&L.hcap[lane][3], o, x);
+  } else if (site) v3add(L.st.human_site[lane - HRG_NHB], o, x);
+  wave_sync();
+}
+
 // pose of the human at frame `at` of clip `clip`: root pose chain (human_env.py:1736-1763) + tree kinematics -> L.hcap, human_site
 DI void human_pose_fk(const DevModel* __restrict__ dm_, int lane, int clip, int at, int hold_body = -1, int hold_left = 0) {
   const ModelPtr dm = uniform_model(dm_);
+#if HRG_POSE_TABLE
+  (void)hold_body; (void)hold_left;
+  human_pose_from_table(dm, lane, (int64_t)dm->clips.clip_offset[clip] + at);
+#else
   Lds& L = g_L;
-  const auto& m = dm->m;
   hrg_env_state& s = L.st;
   const double* fr = dm->clips.frames + (dm->clips.clip_offset[clip] + at) * HRG_FRAME_DIM;
-  double qi[4] = {dm->clips.clip_quat[clip][3], dm->clips.clip_quat[clip][0], dm->clips.clip_quat[clip][1], dm->clips.clip_quat[clip][2]};
-  double qbi[4], Rbi[9], pa[3], pr[3], mp[3], mq[4], q1[4];
-  quatmul(qbi, m.human_base_quat, qi);
-  quat2mat(Rbi, qbi);
-  for (int a = 0; a < 3; a++) pa[a] = fr[a] + dm->clips.clip_pos_offset[clip][a];
-  m3mulv(pr, Rbi, pa);
-  v3add(mp, pr, s.human_pos_offset);
-  double qa[4] = {fr[6], fr[3], fr[4], fr[5]};
+  double qbi[4], qa[4], c[3], mp[3], mq[4], q1[4];
+  human_root(dm, clip, fr, c, qbi, qa);
+  v3add(mp, c, s.human_pos_offset);
   quatmul(q1, s.human_rot_offset, qbi);
   quatmul(mq, q1, qa);
   human_fk_lanes(dm_, lane, mp, mq, fr + 7, hold_body, hold_left);
+#endif
 }
 
 #if HRG_BOX || HRG_STACK || HRG_HAMMER

@@ -449,6 +449,13 @@ int hrg_test_hull_box_queries(const double* verts_host, const int32_t* off_host,
 /* hull - cube pairs (robot_hulls, cube tasks) whose MPR penetration did not converge within 50 iterations and kept the capsule contact, counted over the batch's life
  * (every substep): count_host int64.  0 for a batch without hulls. */
 int hrg_batch_mpr_fallbacks(hrg_batch* b, int64_t* count_host);
+/* device memory of the batch's human pose table (one entry of HRG_POSE_DIM = 216 doubles per frame of its clip set, built at create): bytes_host int64.
+ * 0 for the tasks whose kernels run the human tree kinematics every cycle (all but ReachHuman and CollaborativeLiftingCart).  0 / -1. */
+int hrg_batch_pose_table_bytes(hrg_batch* b, int64_t* bytes_host);
+/* test tap of the pose table: n queries {pos_off[3], rot_off[4] (w, x, y, z), clip, at} = 64 bytes each -> out_host[n][2][213] = the human pose at frame `at` of
+ * `clip` under those episode offsets, [0] by the live tree kinematics (the offsets composed before the tree), [1] from the pose table: 24 capsules (p1, p2) | 23
+ * sites.  One wavefront per query.  HRG_ERR_UNSUPPORTED for a batch without a pose table. */
+int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, double* out_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the
