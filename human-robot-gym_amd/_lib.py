@@ -20,6 +20,11 @@ SRC_STACK = os.path.join(_HERE, "csrc", "hrgym_stack.hip")   # ... and the four-
 SRC_HAMMER = os.path.join(_HERE, "csrc", "hrgym_hammer.hip")  # ... and board + nail + hammer of CollaborativeHammeringCart
 SRC_HULLS = os.path.join(_HERE, "csrc", "hrgym_hulls.hip")    # ... and the ReachHuman kernels with the arm links' convex hulls as collision geometry
 SRC_BOX_HULLS = os.path.join(_HERE, "csrc", "hrgym_box_hulls.hip")   # ... and the cube kernels with the convex hulls (hull - cube pairs by MPR)
+SRC_HO_HULLS = os.path.join(_HERE, "csrc", "hrgym_handover_hulls.hip")   # ... and the handover, lifting, stacking, hammering kernels with the convex hulls
+SRC_LIFT_HULLS = os.path.join(_HERE, "csrc", "hrgym_lift_hulls.hip")
+SRC_STACK_HULLS = os.path.join(_HERE, "csrc", "hrgym_stack_hulls.hip")
+SRC_HAMMER_HULLS = os.path.join(_HERE, "csrc", "hrgym_hammer_hulls.hip")
+SOURCES = [SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS, SRC_HO_HULLS, SRC_LIFT_HULLS, SRC_STACK_HULLS, SRC_HAMMER_HULLS]
 
 EXPORTS = [
     "hrg_last_error", "hrg_version", "hrg_state_bytes", "hrg_batch_create", "hrg_batch_destroy", "hrg_batch_reset",
@@ -33,7 +38,7 @@ EXPORTS = [
 
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = [SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS] + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h")] + [
+    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h")] + [
         os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
@@ -45,7 +50,7 @@ def build_library(force=False, verbose=False):
     # pair spilled.  Without it the ReachHuman kernel allocates 120 VGPRs with no VGPR spill (was 128 + 5 spilled; SGPR spills 93 -> 64) and every variant is
     # 3 - 6 % faster (profiles/r03_*).
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-Xarch_device", "-fapprox-func", "-mllvm", "-disable-machine-licm", "-o", LIB_PATH,
-           SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS]
+           *SOURCES]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
@@ -296,7 +301,7 @@ class HipBatch:
         return order, int(nb.value)
 
     def mpr_fallbacks(self):
-        """Hull - cube pairs (robot_geometry="hull", cube tasks) whose MPR did not converge and kept the capsule contact, summed over every substep since create."""
+        """Arm link hull - box pairs (robot_geometry="hull", every task with an object) whose MPR did not converge and kept the capsule contact, summed over every substep since create."""
         c = ctypes.c_int64()
         _check(self.lib, self.lib.hrg_batch_mpr_fallbacks(self.h, ctypes.byref(c)))
         return c.value

@@ -38,7 +38,7 @@
 #define HRG_STACK 0   // HRG_STACK=1 (hrgym_stack.hip, HRG_BOX=0): CollaborativeStackingCart -- four free cubes, box-box contacts, two welds; its own collision tail and solver
 #endif
 #ifndef HRG_HULLS
-#define HRG_HULLS 0   // HRG_HULLS=1 (hrgym_hulls.hip, ReachHuman): the arm links collide as the convex hulls of their meshes (hrg_model_desc.robot_hulls; hrgym_hull.h)
+#define HRG_HULLS 0   // HRG_HULLS=1 (hrgym_hulls.hip and hrgym_*_hulls.hip: a hull variant of every kernel): the arm links collide as the convex hulls of their meshes (hrg_model_desc.robot_hulls; hrgym_hull.h)
 #endif
 #ifndef HRG_HAMMER
 #define HRG_HAMMER 0  // HRG_HAMMER=1 (hrgym_hammer.hip, HRG_BOX=0): CollaborativeHammeringCart -- board + nail + hammer, a 24-DoF system in three 8-wide blocks; its own collision tail and solver
@@ -195,7 +195,8 @@ struct Contact {
 // per-workgroup (= per-env) LDS image.  Sized to <= 10 KB so that 16 envs (4 waves/SIMD) are resident per CU:
 // 4096 envs on 256 CUs then run in one round.  Phase-local scratch shares one union.
 struct GjkLds { double y[4][3], a[4][3], b[4][3], l[4], lam[4]; int ia[4], ib[4]; };   // GJK simplex: points of the Minkowski difference, their witnesses on the hull / the segment, weights
-#if HRG_HULLS && HRG_BOX
+#define HRG_HULL_MPR (HRG_HULLS && (HRG_BOX || HRG_STACK || HRG_HAMMER))   // a hull variant with manipulation objects: arm link x object pairs by MPR (hrgym_hull.h)
+#if HRG_HULL_MPR
 struct MprLds { double v[5][3], a[5][3], b[5][3]; };   // MPR portal v0 .. v3 + the candidate support point (slot 4): points of the Minkowski difference hull - box, their witnesses on each
 #endif
 struct Lds {
@@ -247,8 +248,8 @@ struct Lds {
       double hcap[HRG_NHB][6], rcapw[HRG_NRCAP][6];
       int hnear[HRG_NHB];                // human capsules whose bounding sphere comes near the robot (the pair rounds of collide run over these)
       double rcen[HRG_NRCAP][3];         // capsule centres: collide -> classify (the speed of a robot geom at a human contact)
-#if HRG_HULLS && HRG_BOX
-      union { GjkLds gjk; MprLds mpr; }; // the simplex of a hull query / the portal of a hull - cube query (hrgym_hull.h): one pair at a time
+#if HRG_HULL_MPR
+      union { GjkLds gjk; MprLds mpr; }; // the simplex of a hull query / the portal of a hull - box query (hrgym_hull.h): one pair at a time
 #elif HRG_HULLS
       GjkLds gjk;                        // the simplex of a hull query (hrgym_hull.h)
 #endif

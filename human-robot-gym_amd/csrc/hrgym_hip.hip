@@ -2882,10 +2882,22 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
 }
 
 // ================================================================================================ kernels
-#if HRG_STACK
+#if HRG_STACK && HRG_HULLS
+#define hrg_step_kernel hrg_step_kernel_stack_hull   // the stacking task with the arm links' convex hulls (hrgym_stack_hulls.hip)
+#define hrg_reset_kernel hrg_reset_kernel_stack_hull
+#define hrg_stack_launch_step hrg_stack_hull_launch_step
+#define hrg_stack_launch_reset hrg_stack_hull_launch_reset
+typedef hrg_stack_state ObjState;
+#elif HRG_STACK
 #define hrg_step_kernel hrg_step_kernel_stack
 #define hrg_reset_kernel hrg_reset_kernel_stack
 typedef hrg_stack_state ObjState;   // the per-env object block this variant streams next to hrg_env_state
+#elif HRG_HAMMER && HRG_HULLS
+#define hrg_step_kernel hrg_step_kernel_hammer_hull   // the hammering task with the arm links' convex hulls (hrgym_hammer_hulls.hip)
+#define hrg_reset_kernel hrg_reset_kernel_hammer_hull
+#define hrg_hammer_launch_step hrg_hammer_hull_launch_step
+#define hrg_hammer_launch_reset hrg_hammer_hull_launch_reset
+typedef hrg_hammer_state ObjState;
 #elif HRG_HAMMER
 #define hrg_step_kernel hrg_step_kernel_hammer
 #define hrg_reset_kernel hrg_reset_kernel_hammer
@@ -2897,11 +2909,21 @@ typedef hrg_box_state ObjState;     // (ReachHuman streams no object block: the 
 #else
 typedef hrg_box_state ObjState;
 #endif
-#if HRG_BOX && HRG_HANDOVER
+#if HRG_BOX && HRG_HANDOVER && HRG_HULLS
+#define hrg_step_kernel hrg_step_kernel_ho_hull   // the handover tasks with the arm links' convex hulls (hrgym_handover_hulls.hip)
+#define hrg_reset_kernel hrg_reset_kernel_ho_hull
+#define hrg_box_launch_step hrg_ho_hull_launch_step
+#define hrg_box_launch_reset hrg_ho_hull_launch_reset
+#elif HRG_BOX && HRG_HANDOVER
 #define hrg_step_kernel hrg_step_kernel_ho
 #define hrg_reset_kernel hrg_reset_kernel_ho
 #define hrg_box_launch_step hrg_ho_launch_step
 #define hrg_box_launch_reset hrg_ho_launch_reset
+#elif HRG_BOX && HRG_LIFT && HRG_HULLS
+#define hrg_step_kernel hrg_step_kernel_lift_hull   // the lifting task with the arm links' convex hulls (hrgym_lift_hulls.hip)
+#define hrg_reset_kernel hrg_reset_kernel_lift_hull
+#define hrg_box_launch_step hrg_lift_hull_launch_step
+#define hrg_box_launch_reset hrg_lift_hull_launch_reset
 #elif HRG_BOX && HRG_LIFT
 #define hrg_step_kernel hrg_step_kernel_lift
 #define hrg_reset_kernel hrg_reset_kernel_lift
@@ -3155,8 +3177,30 @@ extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_step(int n
                                                                             float* scratch_obs, StepOrder ord);
 extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
                                                                              int64_t env_id0);
+// ... of the hull variants of the handover, lifting, stacking and hammering kernels (hrgym_handover_hulls.hip, hrgym_lift_hulls.hip, hrgym_stack_hulls.hip,
+// hrgym_hammer_hulls.hip)
+extern "C" __attribute__((visibility("hidden"))) void hrg_ho_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
+                                                                               float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
+                                                                               float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
+extern "C" __attribute__((visibility("hidden"))) void hrg_ho_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
+                                                                                int64_t env_id0, hrg_box_state* boxes);
+extern "C" __attribute__((visibility("hidden"))) void hrg_lift_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
+                                                                                 float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
+                                                                                 float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
+extern "C" __attribute__((visibility("hidden"))) void hrg_lift_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
+                                                                                  int64_t env_id0, hrg_box_state* boxes);
+extern "C" __attribute__((visibility("hidden"))) void hrg_stack_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
+                                                                                  float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
+                                                                                  float* scratch_obs, hrg_stack_state* stacks, StepOrder ord);
+extern "C" __attribute__((visibility("hidden"))) void hrg_stack_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
+                                                                                   int64_t env_id0, hrg_stack_state* stacks);
+extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
+                                                                                   float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
+                                                                                   float* scratch_obs, hrg_hammer_state* hammers, StepOrder ord);
+extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
+                                                                                    int64_t env_id0, hrg_hammer_state* hammers);
 #endif
-#if HRG_HULLS && !HRG_BOX
+#if HRG_HULLS && !HRG_BOX && !HRG_STACK && !HRG_HAMMER
 extern "C" void hrg_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
                                      int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, StepOrder ord) {
   hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, (ObjState*)nullptr, n_envs, ord);
@@ -3194,10 +3238,18 @@ extern "C" void hrg_box_launch_reset(int n_envs, hipStream_t st, const DevModel*
 #endif
 
 #ifdef HRG_STAMPS
-#if HRG_STACK
+#if HRG_STACK && HRG_HULLS
+#define hrg_debug_stamps hrg_debug_stamps_stack_hull
+#elif HRG_STACK
 #define hrg_debug_stamps hrg_debug_stamps_stack
+#elif HRG_HAMMER && HRG_HULLS
+#define hrg_debug_stamps hrg_debug_stamps_hammer_hull
 #elif HRG_HAMMER
 #define hrg_debug_stamps hrg_debug_stamps_hammer
+#elif HRG_BOX && HRG_HULLS && HRG_HANDOVER
+#define hrg_debug_stamps hrg_debug_stamps_ho_hull
+#elif HRG_BOX && HRG_HULLS && HRG_LIFT
+#define hrg_debug_stamps hrg_debug_stamps_lift_hull
 #elif HRG_BOX && HRG_HULLS
 #define hrg_debug_stamps hrg_debug_stamps_box_hull
 #elif HRG_HANDOVER
@@ -3227,12 +3279,24 @@ extern "C" int hrg_debug_stamps(double* out, int reset) {
   if (reset) { memset(h, 0, sizeof h); hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), h, sizeof h); }
   return 0;
 }
-#if HRG_HAMMER
+#if HRG_HAMMER && HRG_HULLS
+#define hrg_debug_envacc hrg_debug_envacc_hammer_hull
+#define hrg_debug_envcyc hrg_debug_envcyc_hammer_hull
+#elif HRG_HAMMER
 #define hrg_debug_envacc hrg_debug_envacc_hammer
 #define hrg_debug_envcyc hrg_debug_envcyc_hammer
+#elif HRG_STACK && HRG_HULLS
+#define hrg_debug_envacc hrg_debug_envacc_stack_hull
+#define hrg_debug_envcyc hrg_debug_envcyc_stack_hull
 #elif HRG_STACK
 #define hrg_debug_envacc hrg_debug_envacc_stack
 #define hrg_debug_envcyc hrg_debug_envcyc_stack
+#elif HRG_BOX && HRG_HULLS && HRG_HANDOVER
+#define hrg_debug_envacc hrg_debug_envacc_ho_hull
+#define hrg_debug_envcyc hrg_debug_envcyc_ho_hull
+#elif HRG_BOX && HRG_HULLS && HRG_LIFT
+#define hrg_debug_envacc hrg_debug_envacc_lift_hull
+#define hrg_debug_envcyc hrg_debug_envcyc_lift_hull
 #elif HRG_BOX && HRG_HULLS
 #define hrg_debug_envacc hrg_debug_envacc_box_hull
 #define hrg_debug_envcyc hrg_debug_envcyc_box_hull
@@ -3275,7 +3339,7 @@ struct hrg_batch {
   double* d_pose = nullptr;            // per-frame human pose table (DevModel::pose_tab): the tasks whose kernels read it (hrg_task_uses_pose_table)
   size_t pose_bytes = 0;
   double* d_hull = nullptr;            // hull vertices of the arm links (robot_hulls)
-  bool hulls = false;                  // the hull variant of the ReachHuman kernels steps this batch (hrgym_hulls.hip) -- or of the cube kernels (hrgym_box_hulls.hip)
+  bool hulls = false;                  // a hull variant steps this batch: of the ReachHuman kernels (hrgym_hulls.hip), the cube kernels (hrgym_box_hulls.hip) or a task's own (hrgym_*_hulls.hip)
   unsigned long long* d_mpr_fallback = nullptr;   // hull - cube pairs whose MPR did not converge (DevModel::mpr_fallback; hrg_batch_mpr_fallbacks)
   hrg_env_state* d_states = nullptr;
   double* d_rcaps = nullptr;
@@ -3483,9 +3547,11 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   }
   hm->hull_dev = nullptr;
   if (desc->robot_hulls) {   // convex hulls of the arm links: the vertex table goes to device memory like the clip frames
-    // the ReachHuman kernel and the cube kernel (hrg_step_kernel_box: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman with its box) have hull variants
-    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX))
-      return bail(HRG_ERR_UNSUPPORTED, "robot_hulls: the hull variants of the step kernel exist for ReachHuman and the cube tasks (PickPlace, Inspection, ReachHuman with reach_box)");
+    // every kernel has a hull variant: ReachHuman (hrg_step_kernel_hull), the cube tasks (_box_hull: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman
+    // with its box), the handover tasks (_ho_hull), lifting (_lift_hull), stacking (_stack_hull) and hammering (_hammer_hull)
+    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX ||
+          HRG_IS_HANDOVER(desc->task) || desc->task == HRG_TASK_LIFTING || desc->task == HRG_TASK_STACKING || desc->task == HRG_TASK_HAMMERING))
+      return bail(HRG_ERR_UNSUPPORTED, "robot_hulls: no hull variant of the step kernel for this task");
     b->hulls = true;
     if (!desc->hull_verts || desc->hull_off[0] != 0) return bail(HRG_ERR_INVALID, "robot_hulls: hull_verts / hull_off missing");
     for (int h = 0; h < HRG_NHULL; h++)
@@ -3581,9 +3647,13 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
 int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!b) return fail(HRG_ERR_INVALID, "null batch");
   HIPCHK(hipSetDevice(b->device));
-  if (b->task == HRG_TASK_HAMMERING) hrg_hammer_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_hammers);
+  if (b->task == HRG_TASK_HAMMERING && b->hulls) hrg_hammer_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_hammers);
+  else if (b->task == HRG_TASK_HAMMERING) hrg_hammer_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_hammers);
+  else if (b->task == HRG_TASK_STACKING && b->hulls) hrg_stack_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_stacks);
   else if (b->task == HRG_TASK_STACKING) hrg_stack_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_stacks);
+  else if (b->task == HRG_TASK_LIFTING && b->hulls) hrg_lift_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (b->task == HRG_TASK_LIFTING) hrg_lift_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
+  else if (HRG_IS_HANDOVER(b->task) && b->hulls) hrg_ho_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (HRG_IS_HANDOVER(b->task)) hrg_ho_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (b->task != HRG_TASK_REACH && b->hulls) hrg_box_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
   else if (b->task != HRG_TASK_REACH) hrg_box_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
@@ -3614,15 +3684,27 @@ int hrg_batch_step(hrg_batch* b, double* actions_dev, float* obs_dev, float* ter
   int32_t* fair = fair_table(b->device);
   if (!fair) return fail(HRG_ERR_HIP, "cannot allocate the wave-progress table");
   const StepOrder ord{b->d_order, b->n_envs, b->parity, fair};
-  if (b->task == HRG_TASK_HAMMERING)
+  if (b->task == HRG_TASK_HAMMERING && b->hulls)
+    hrg_hammer_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
+                                b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_hammers, ord);
+  else if (b->task == HRG_TASK_HAMMERING)
     hrg_hammer_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                            b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_hammers, ord);
+  else if (b->task == HRG_TASK_STACKING && b->hulls)
+    hrg_stack_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
+                               b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_stacks, ord);
   else if (b->task == HRG_TASK_STACKING)
     hrg_stack_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                           b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_stacks, ord);
+  else if (b->task == HRG_TASK_LIFTING && b->hulls)
+    hrg_lift_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
+                              b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
   else if (b->task == HRG_TASK_LIFTING)
     hrg_lift_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                          b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
+  else if (HRG_IS_HANDOVER(b->task) && b->hulls)
+    hrg_ho_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
+                            b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
   else if (HRG_IS_HANDOVER(b->task))
     hrg_ho_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
                        b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);

@@ -203,7 +203,7 @@ DI void hull_lowest_wave(const HullRef& H, double* out) {
   out[0] = wave_sum(sx) / tc; out[1] = wave_sum(sy) / tc; out[2] = zmin;
 }
 
-#if HRG_BOX
+#if HRG_HULL_MPR
 // ------------------------------------------------------------------------------------------------ hull x cube: penetration by MPR
 // MuJoCo 2.1 (the version the reference pins) collides a mesh geom with a box through its convex-convex path: Minkowski Portal Refinement (Snethen, "XenoCollide",
 // Game Programming Gems 7), ONE contact per pair -- depth, direction, position.  Restated here from that description, wave-uniform like the GJK above: the hull's

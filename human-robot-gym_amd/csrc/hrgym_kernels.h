@@ -988,6 +988,25 @@ DI int box_box2(const double* pa, const double* Ra, const double* ha, const doub
 }
 DI int box_box(const double* pa, const double* Ra, const double* pb, const double* Rb, const double* h, BBContact* out, double* T) { return box_box2(pa, Ra, h, pb, Rb, h, out, T); }
 #endif
+#if HRG_HULLS && (HRG_STACK || HRG_HAMMER)
+// hrg_model_desc.robot_hulls, stacking / hammering: the penetration of arm link g's CONVEX HULL (g < HRG_NHULL, wave-uniform) with the box (bR, bp, bh: world rotation,
+// centre, half extents) by MPR (hrgym_hull.h), the whole wave on the support mappings.  A pair that does not converge counts itself (DevModel::mpr_fallback).
+DI int mpr_link_box(const DevModel* __restrict__ dm_, int g, const double* bR, const double* bp, const double* bh, double& depth, double* n, double* pos) {
+  const ModelPtr dm = uniform_model(dm_);
+  Lds& L = g_L;
+  const auto& m = dm->m;
+  const int lb = m.rcap_body[g];
+  const double* R = lb < 0 ? dm_->Rbase : L.kR[lb];
+  const double* p = lb < 0 ? dm_->m.base_pos : L.kp[lb];
+  const HullRef H = {dm_->hull_dev + 3 * m.hull_off[g], m.hull_off[g + 1] - m.hull_off[g], R, p};
+  double hc[3];
+  m3mulv(hc, R, dm_->hull_cen[g]);
+  v3add(hc, hc, p);
+  const int r = mpr_hull_box_wave(H, hc, bR, bp, bh, depth, n, pos);
+  if (r == MPR_NOT_CONVERGED && hrg_lane() == 0) atomicAdd(dm_->mpr_fallback, 1ull);
+  return r;
+}
+#endif
 #if HRG_STACK
 
 // The cubes' part of the stacking task's contact list (after the robot's own rounds): robot capsule x cube first points (cube-major), table corners,
@@ -1042,6 +1061,27 @@ DI void collide_cubes(const DevModel* __restrict__ dm_, int lane, int* base_io) 
           c.g1 = i; c.g2 = GEOM_BOX + cb; c.b1 = m.rcap_body[i]; c.b2 = BODY_BOX + cb; c.dist = dist;
         }
       }
+#if HRG_HULLS
+      // hrg_model_desc.robot_hulls: the capsule - cube test above is the BROADPHASE of an arm link (geoms 0 .. 6) against cube cb.  A first-point pair that passed runs
+      // the penetration of the link's CONVEX HULL with that cube by MPR, one pair at a time in lane (= contact) order; ONE contact per pair, so the second points of
+      // hull links are dropped.  A hull clear of the cube drops the pair; an MPR that does not converge keeps the capsule contact.  The fingers (7 .. 9) stay capsules.
+      if (m.robot_hulls) {
+        const bool link = lane < NCUBE * HRG_NRCAP && i < HRG_NHULL;
+        if (second && link) hit = false;
+        uint64_t todo = second ? 0ull : __ballot(hit && link);
+        while (todo) {
+          const int src = __ffsll((unsigned long long)todo) - 1;
+          todo &= todo - 1;
+          const int cs_ = src / HRG_NRCAP;
+          double dep, nn[3], pp[3];
+          const int r = mpr_link_box(dm_, src - cs_ * HRG_NRCAP, L.cR[cs_], sk.pos[cs_], hb, dep, nn, pp);
+          if (lane == src) {
+            if (r == MPR_SEPARATED) hit = false;
+            else if (r == MPR_PENETRATING) { v3cpy(c.n, nn); v3cpy(c.pos, pp); c.dist = -dep; }
+          }
+        }
+      }
+#endif
       const uint64_t mask = __ballot(hit);
       const int slot = base + __popcll(mask & lt);
       if (hit) {
@@ -1087,6 +1127,11 @@ DI void collide_cubes(const DevModel* __restrict__ dm_, int lane, int* base_io) 
         v3sub(d, sk.pos[pb_], sk.pos[pa_]);
         // candidate scratch: the tail of the (dead) solver rows; the collide arrays (hcap, rcapw, cur) sit in the first 1.7 KB of the same union
         static_assert(40 * 21 + 6 * BB_WORK <= 4 * NCON_DYN * 21, "box_box2 workspace of the six cube pairs");
+#if HRG_HULLS
+        static_assert(__builtin_offsetof(Lds, gjk) + sizeof(GjkLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 40 &&
+                      __builtin_offsetof(Lds, mpr) + sizeof(MprLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 40 &&
+                      __builtin_offsetof(Lds, cR) + sizeof(L.cR) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 40, "the GJK simplex / MPR portal and the box_box2 workspace alias");
+#endif
         if (!(v3dot(d, d) > 4.0 * circ2)) nc = box_box(sk.pos[pa_], L.cR[pa_], sk.pos[pb_], L.cR[pb_], hb, bc, &L.Jc[40][0] + BB_WORK * lane);
       }
       // exclusive prefix of the contact counts over lanes 0..5
@@ -1207,6 +1252,28 @@ DI void collide_hammer(const DevModel* __restrict__ dm_, int lane, int* base_io)
           c.g1 = i; c.g2 = GEOM_BOX + g; c.b1 = m.rcap_body[i]; c.b2 = BODY_BOX + (g == HRG_HG_NAIL ? HRG_HM_NAIL : fb); c.dist = dist;
         }
       }
+#if HRG_HULLS
+      // hrg_model_desc.robot_hulls: as in collide_cubes -- the capsule - box test above is the BROADPHASE of an arm link (geoms 0 .. 6) against geom g; a first-point
+      // pair that passed runs the MPR of the link's CONVEX HULL with that box, its own extents (m.hm_geom_half[g]) and pose (L.gc[g], L.gR[board | hammer]); ONE contact
+      // per pair, second points of hull links dropped, a hull clear of the box drops the pair, an MPR that does not converge keeps the capsule contact.
+      if (m.robot_hulls) {
+        const bool link = lane < HRG_HM_NGEOM * HRG_NRCAP && i < HRG_NHULL;
+        if (second && link) hit = false;
+        uint64_t todo = second ? 0ull : __ballot(hit && link);
+        while (todo) {
+          const int src = __ffsll((unsigned long long)todo) - 1;
+          todo &= todo - 1;
+          const int gs = src / HRG_NRCAP, fs = (gs == HRG_HG_HANDLE || gs == HRG_HG_HEAD) ? 1 : 0;
+          const double hs[3] = {m.hm_geom_half[gs][0], m.hm_geom_half[gs][1], m.hm_geom_half[gs][2]};
+          double dep, nn[3], pp[3];
+          const int r = mpr_link_box(dm_, src - gs * HRG_NRCAP, L.gR[fs], L.gc[gs], hs, dep, nn, pp);
+          if (lane == src) {
+            if (r == MPR_SEPARATED) hit = false;
+            else if (r == MPR_PENETRATING) { v3cpy(c.n, nn); v3cpy(c.pos, pp); c.dist = -dep; }
+          }
+        }
+      }
+#endif
       const uint64_t mask = __ballot(hit);
       const int slot = base + __popcll(mask & lt);
       if (hit) {
@@ -1260,6 +1327,10 @@ DI void collide_hammer(const DevModel* __restrict__ dm_, int lane, int* base_io)
         const double ra = fsqrt(ha[0] * ha[0] + ha[1] * ha[1] + ha[2] * ha[2]) + 1e-9;
         // candidate scratch: the tail of the (dead) solver rows; the collide arrays (hcap, rcapw, cur) sit in the first 1.7 KB of the same union
         static_assert(40 * (NVS + 1) + 4 * BB_WORK <= (4 * NCON_DYN + HROW_NEQ) * (NVS + 1), "box_box2 workspace of the four box pairs");
+#if HRG_HULLS
+        static_assert(__builtin_offsetof(Lds, gjk) + sizeof(GjkLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 40 &&
+                      __builtin_offsetof(Lds, mpr) + sizeof(MprLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 40, "the GJK simplex / MPR portal and the box_box2 workspace alias");
+#endif
         if (!(d2 > ra * ra)) nc = box_box2(L.gc[ga], L.gR[1], ha, L.gc[gb], L.gR[0], hb, bc, &L.Jc[40][0] + BB_WORK * lane);
       }
       int pre = 0, tot = 0;
@@ -1511,6 +1582,10 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
       double* T = &L.Jc[20][0];      // scratch behind the collide arrays (the solver rows are dead here): BB_WORK doubles for box_box2, then the contacts
       double* res = &L.Jc[34][0];
       static_assert(20 * (NVS + 1) + BB_WORK <= 32 * (NVS + 1) && 34 * (NVS + 1) + 28 <= (4 * NCON_DYN + 6) * (NVS + 1), "box_box2 workspace");
+#if HRG_HULLS
+      static_assert(__builtin_offsetof(Lds, gjk) + sizeof(GjkLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 20 &&
+                    __builtin_offsetof(Lds, mpr) + sizeof(MprLds) <= __builtin_offsetof(Lds, Jc) + sizeof(L.Jc[0]) * 20, "the GJK simplex / MPR portal and the box_box2 workspace alias");
+#endif
       int nb = 0;
       if (lane == 16) {
         const double pt[3] = {m.table_center[0], m.table_center[1], m.table_top_z - 0.025}, ht[3] = {m.table_half[0], m.table_half[1], 0.025};

@@ -151,8 +151,9 @@ class MixedBatch:
         self.batches = []
 
 
-def make_mixed_batch(n_envs, tasks=ICRA_TASKS, env_kwargs=None, clips=None, n_clips=13, seed=None, env_id0=0, device=0, concurrent=True):
-    """`n_envs` environments split evenly over `tasks` = [(env_id, kwargs), ...]; `env_kwargs` are applied to every task first."""
+def make_mixed_batch(n_envs, tasks=ICRA_TASKS, env_kwargs=None, clips=None, n_clips=13, seed=None, env_id0=0, device=0, concurrent=True, robot_geometry="capsule"):
+    """`n_envs` environments split evenly over `tasks` = [(env_id, kwargs), ...]; `env_kwargs` are applied to every task first.
+    `robot_geometry` ("capsule" | "hull", see `build_model_desc`) goes to every part."""
     counts = split_evenly(n_envs, len(tasks))
     parts = []
     for (env_id, kw), k in zip(tasks, counts):
@@ -163,7 +164,7 @@ def make_mixed_batch(n_envs, tasks=ICRA_TASKS, env_kwargs=None, clips=None, n_cl
             kw["seed"] = int(seed)
         c = (clips or {}).get(env_id) if isinstance(clips, dict) else None
         c = c if c is not None else task_clips(env_id, n_clips)
-        parts.append((env_id, build_model_desc(kw, n_clips=c.n_clips, env_id=env_id), c, k))
+        parts.append((env_id, build_model_desc(kw, n_clips=c.n_clips, env_id=env_id, robot_geometry=robot_geometry), c, k))
     return MixedBatch(parts, env_id0=env_id0, device=device, concurrent=concurrent)
 
 
@@ -210,12 +211,13 @@ class _MixedBackend:
 
 
 def make_mixed_vec_env(n_envs, tasks=ICRA_TASKS, obs_keys=None, env_kwargs=None, seed=None, start_index=0, clips=None, n_clips=13,
-                       device=0, info_dicts=True, concurrent=True):
+                       device=0, info_dicts=True, concurrent=True, robot_geometry="capsule"):
     """A `HipVecEnv`-shaped VecEnv over a mixed batch.  One policy sees every task, so the observation is the same columns for all
     of them: `obs_keys` (names valid for every task) or, by default, the whole 64-column observation superset (columns a task does
-    not fill are zero).  `infos[i]["task"]` names the task of row i; `env.task_slices` maps env ids to row ranges."""
+    not fill are zero).  `infos[i]["task"]` names the task of row i; `env.task_slices` maps env ids to row ranges.
+    `robot_geometry` as in `make_mixed_batch`."""
     batch = make_mixed_batch(n_envs, tasks, env_kwargs=env_kwargs, clips=clips, n_clips=n_clips, seed=seed, env_id0=start_index,
-                             device=device, concurrent=concurrent)
+                             device=device, concurrent=concurrent, robot_geometry=robot_geometry)
     return __getattr__("MixedHipVecEnv")(batch, obs_keys=obs_keys, info_dicts=info_dicts)
 
 

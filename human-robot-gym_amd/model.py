@@ -351,9 +351,9 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
     `ik_position_delta` takes the keys of config/wrappers/ik_position_delta/*.yaml (action_limit, x_output_max,
     x_position_limits, residual_threshold, max_iter): actions become [dx, dy, dz, gripper]; None = joint-space actions.
     `robot_geometry`: "capsule" = every arm link collides as the bounding capsule of its mesh; "hull" = as the convex hull of its mesh
-    (what MuJoCo makes of a mesh geom) against the human's capsules and the table / floor planes, the capsule being the broadphase.  "hull" covers ReachHuman
-    (also with `reach_box=True`) and the cube tasks (PickPlaceHumanCart and its variants, HumanObjectInspectionCart), where a link x cube pair is the hull's
-    penetration of the cube by MPR, one contact per pair; the handover, lifting, stacking and hammering tasks refuse it."""
+    (what MuJoCo makes of a mesh geom) against the human's capsules and the table / floor planes, the capsule being the broadphase.  "hull" covers every task:
+    a pair of an arm link with a manipulated object (the cube, the lifting board, a stacking cube, the hammering board, hammer and nail head) is the hull's
+    penetration of that box by MPR, one contact per pair; the finger and gripper capsules stay capsules."""
     if env_id not in ENV_DEFAULTS:
         raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)}")
     kw = dict(ENV_DEFAULTS[env_id])

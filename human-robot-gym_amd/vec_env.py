@@ -298,7 +298,7 @@ class HipVecEnv(_VecEnvBase):
         # [dx, dy, dz, gripper] (IKPositionDeltaWrapper, wrappers/ik_position_delta_wrapper.py), converted in the kernel
         self._cp, self._goal_check, self._ik = collision_prevention, goal_check, ik_position_delta
         self._reach_box = bool(reach_box)   # ReachHuman with its free smallBox object (stepped by the cube kernel); default: the lean model
-        self._robot_geometry = robot_geometry   # "capsule" (default) | "hull": the arm links collide as the convex hulls of their meshes (ReachHuman and the cube tasks)
+        self._robot_geometry = robot_geometry   # "capsule" (default) | "hull": the arm links collide as the convex hulls of their meshes (every task)
         self._desc = build_model_desc(kw, n_clips=self._clips.n_clips, collision_prevention=collision_prevention, goal_check=goal_check, env_id=env_id,
                                       ik_position_delta=ik_position_delta, reach_box=self._reach_box, robot_geometry=robot_geometry)
         self._device, self._env_id0 = device, env_id0

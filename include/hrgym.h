@@ -332,7 +332,9 @@ typedef struct hrg_model_desc {
   int32_t noslip_iterations;      /* opt.noslip_iterations: sweeps of the pass at most; 0 = off (every task but CollaborativeHammeringCart) */
   /* ---- collision geometry of the seven arm links (robot.xml:29-55: mesh geoms, which MuJoCo convexifies at compile time) ----
    * robot_hulls = 1: contacts of an arm link with the human's capsules and with the table / floor planes are those of the link's CONVEX HULL (support mapping
-   * over its vertices: GJK distance to a capsule's axis, deepest vertex under a plane); the link's bounding capsule is then only the broadphase.  0: the bounding
+   * over its vertices: GJK distance to a capsule's axis, deepest vertex under a plane), and with a manipulated object's box (the cube, the lifting board, a stacking
+   * cube, the hammering board / head / nail head) the hull's penetration by MPR, one contact per pair; the link's bounding capsule is then only the broadphase.
+   * Accepted by every task (each kernel has a hull variant).  0: the bounding
    * capsule itself is the collision geom (rounds 1-2).  Hull vertices: body frame, hull h = vertices hull_off[h] .. hull_off[h + 1] - 1 of
    * hull_verts[.][3] (host memory, copied at create like the clip frames; compiled from the STL files by tools/compile_model.py). */
   int32_t robot_hulls;
@@ -442,11 +444,11 @@ int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t
  * pad} = 152 bytes each, against the vertex table (verts_host, off_host[HRG_NHULL + 1]) -> out_host[n][10] = GJK distance hull - segment, witness on the hull 3, witness
  * on the segment 3, lowest point over a horizontal plane 3.  One wavefront per query runs the step kernel's own wave routines (csrc/hrgym_hull.h).  0 / -1. */
 int hrg_test_hull_queries(const double* verts_host, const int32_t* off_host, const void* queries_host, int32_t n, double* out_host);
-/* test tap of the hull variant of the cube kernels (no oracle counterpart: tests/hullbox_ref.py restates it): n queries {R[9] row-major, p[3] (link pose), box centre[3],
+/* test tap of the hull - box MPR of the hull variants (no oracle counterpart: tests/hullbox_ref.py restates it; any box extents): n queries {R[9] row-major, p[3] (link pose), box centre[3],
  * box rotation[9] row-major, box half extents[3], hull, pad} = 224 bytes each -> out_host[n][9] = penetrating (1 / 0), depth, unit normal from the hull into the box 3,
  * position 3, converged (1 / 0).  One wavefront per query runs the step kernel's own MPR routine (csrc/hrgym_hull.h, mpr_hull_box_wave).  0 / -1. */
 int hrg_test_hull_box_queries(const double* verts_host, const int32_t* off_host, const void* queries_host, int32_t n, double* out_host);
-/* hull - cube pairs (robot_hulls, cube tasks) whose MPR penetration did not converge within 50 iterations and kept the capsule contact, counted over the batch's life
+/* arm link hull - box pairs (robot_hulls, every task with an object) whose MPR penetration did not converge within 50 iterations and kept the capsule contact, counted over the batch's life
  * (every substep): count_host int64.  0 for a batch without hulls. */
 int hrg_batch_mpr_fallbacks(hrg_batch* b, int64_t* count_host);
 /* device memory of the batch's human pose table (one entry of HRG_POSE_DIM = 216 doubles per frame of its clip set, built at create): bytes_host int64.

@@ -1,4 +1,6 @@
-"""Statistics of long random-action runs of the collaboration tasks on the HIP stepper (finite values, crash rate, phase histogram)."""
+"""Statistics of long random-action runs of the collaboration tasks on the HIP stepper (finite values, crash rate, phase histogram).
+python tools/soak_tasks.py [--robot-geometry capsule|hull] [--envs N] [--steps K] [--tasks A,B,...]: with hulls it also reports the MPR fallbacks."""
+import argparse
 import os
 import sys
 
@@ -9,11 +11,21 @@ import human_robot_gym_amd as hrg  # noqa: E402
 from human_robot_gym_amd import mixed  # noqa: E402
 from human_robot_gym_amd._lib import HipBatch  # noqa: E402
 
-n, steps = 4096, 600
-for env_id, shield in (("ReachHuman", "SSM"), ("PickPlaceHumanCart", "SSM"), ("HumanObjectInspectionCart", "SSM"), ("HumanRobotHandoverCart", "PFL"), ("RobotHumanHandoverCart", "PFL"),
-                       ("CollaborativeLiftingCart", "SSM"), ("CollaborativeStackingCart", "SSM"), ("CollaborativeHammeringCart", "SSM")):
+ap = argparse.ArgumentParser()
+ap.add_argument("--robot-geometry", default="capsule", choices=("capsule", "hull"))
+ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--steps", type=int, default=600)
+ap.add_argument("--tasks", default=None, help="comma-separated env ids (default: all)")
+args = ap.parse_args()
+n, steps = args.envs, args.steps
+TASKS = (("ReachHuman", "SSM"), ("PickPlaceHumanCart", "SSM"), ("HumanObjectInspectionCart", "SSM"), ("HumanRobotHandoverCart", "PFL"), ("RobotHumanHandoverCart", "PFL"),
+         ("CollaborativeLiftingCart", "SSM"), ("CollaborativeStackingCart", "SSM"), ("CollaborativeHammeringCart", "SSM"))
+for env_id, shield in TASKS:
+    if args.tasks and env_id not in args.tasks.split(","):
+        continue
     clips = mixed.task_clips(env_id, 5, min_frames=300, max_frames=600) if env_id != "ReachHuman" else hrg.synthetic_clips(5, seed=0)
-    d = hrg.build_model_desc(dict(shield_type=shield, horizon=150, seed=31, **mixed.task_env_kwargs(env_id)), n_clips=clips.n_clips, env_id=env_id)
+    d = hrg.build_model_desc(dict(shield_type=shield, horizon=150, seed=31, **mixed.task_env_kwargs(env_id)), n_clips=clips.n_clips, env_id=env_id,
+                             robot_geometry=args.robot_geometry)
     G = HipBatch(d, clips, n)
     G.reset()
     g = torch.Generator(device="cpu").manual_seed(4)
@@ -48,4 +60,7 @@ for env_id, shield in (("ReachHuman", "SSM"), ("PickPlaceHumanCart", "SSM"), ("H
         qn = max(abs(np.linalg.norm(list(b.quat)) - 1) for b in bx) if env_id != "ReachHuman" else 0.0
         print(f"{env_id}: crashes {crashes} dones {dones} positive rewards {wins} non-finite {bad} phases {ph.tolist()} weld_active {np.mean([b.weld_active for b in bx]):.3f} "
               f"handed over {sum(b.n_handed_over for b in bx)} |quat|-1 {qn:.2e} launch order a permutation {perm_ok} busy {nb}", flush=True)
+    if args.robot_geometry == "hull":
+        fb = G.mpr_fallbacks()
+        print(f"{env_id}: MPR fallbacks {fb} ({fb / (n * steps):.2e} per env-step)", flush=True)
     G.close()

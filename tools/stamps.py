@@ -10,7 +10,7 @@ lib = load_library()
 env_id = sys.argv[2] if len(sys.argv) > 2 else "ReachHuman"
 N = int(sys.argv[3]) if len(sys.argv) > 3 else 4096
 SLOW = int(float(sys.argv[4])) if len(sys.argv) > 4 else 0     # > 0: also profile the waves that live longer than this many cycles (ReachHuman kernel only)
-GEOM = os.environ.get("HRG_GEOMETRY", "capsule")                # "hull": the hull variant of the ReachHuman kernel
+GEOM = os.environ.get("HRG_GEOMETRY", "capsule")                # "hull": the task's hull variant
 from human_robot_gym_amd.mixed import task_clips
 clips = task_clips(env_id, 13)
 from human_robot_gym_amd.mixed import task_env_kwargs
@@ -19,7 +19,9 @@ if env_id == "ReachHuman":
     kw.update(horizon=100, done_at_success=True, reward_shaping=True)
 G = HipBatch(hrg.build_model_desc(kw, n_clips=13, env_id=env_id, robot_geometry=GEOM), clips, N); G.reset()
 if os.environ.get("HRG_STAGGER", "1") != "0": G.stagger_episode_phases(100)
-stamps = (lib.hrg_debug_stamps_hull if GEOM == "hull" else lib.hrg_debug_stamps) if env_id == "ReachHuman" else (lib.hrg_debug_stamps_hammer if "Hammering" in env_id else lib.hrg_debug_stamps_stack if "Stacking" in env_id else (lib.hrg_debug_stamps_ho if "Handover" in env_id else lib.hrg_debug_stamps_box))
+# the accumulators of the kernel variant that steps this batch (each translation unit has its own): hrg_debug_stamps[_<task>][_hull]
+suffix = "" if env_id == "ReachHuman" else ("_hammer" if "Hammering" in env_id else "_stack" if "Stacking" in env_id else "_ho" if "Handover" in env_id else "_lift" if "Lifting" in env_id else "_box")
+stamps = getattr(lib, "hrg_debug_stamps" + suffix + ("_hull" if GEOM == "hull" else ""))
 gen = torch.Generator(device="cuda"); gen.manual_seed(0)
 acts = [torch.rand((N, 7), generator=gen, device="cuda", dtype=torch.float64) * 2 - 1 for _ in range(16)]
 out = np.zeros(32)
