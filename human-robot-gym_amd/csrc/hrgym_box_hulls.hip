@@ -39,18 +39,9 @@ extern "C" int hrg_test_hull_box_queries(const double* verts_host, const int32_t
   for (int k = 0; k < n; k++) if (qh[k].hull < 0 || qh[k].hull >= HRG_NHULL) return -1;
   double cen[HRG_NHULL][3];
   hull_centroids(verts_host, off_host, cen);
-  double *dv = nullptr, *dc = nullptr, *dout = nullptr;
-  int32_t* doff = nullptr;
-  HullBoxQuery* dq = nullptr;
-  const size_t vb = sizeof(double) * 3 * (size_t)off_host[HRG_NHULL];
-  int rc = -1;
-  if (hipMalloc(&dv, vb) == hipSuccess && hipMalloc(&doff, sizeof(int32_t) * (HRG_NHULL + 1)) == hipSuccess && hipMalloc(&dc, sizeof cen) == hipSuccess &&
-      hipMalloc(&dq, sizeof(HullBoxQuery) * (size_t)n) == hipSuccess && hipMalloc(&dout, sizeof(double) * 9 * (size_t)n) == hipSuccess &&
-      hipMemcpy(dv, verts_host, vb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(doff, off_host, sizeof(int32_t) * (HRG_NHULL + 1), hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(dc, cen, sizeof cen, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dq, qh, sizeof(HullBoxQuery) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-    hipLaunchKernelGGL(hrg_test_hull_box_kernel, dim3((unsigned)n), dim3(64), 0, 0, dv, doff, dc, dq, (int)n, dout);
-    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, dout, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-  }
-  hipFree(dv); hipFree(doff); hipFree(dc); hipFree(dq); hipFree(dout);
-  return rc;
+  const TapBuf in[] = {{verts_host, sizeof(double) * 3 * (size_t)off_host[HRG_NHULL]}, {off_host, sizeof(int32_t) * (HRG_NHULL + 1)}, {cen, sizeof cen}, {qh, sizeof(HullBoxQuery) * (size_t)n}};
+  const bool ok = hrg_run_tap(in, 4, out_host, sizeof(double) * 9 * (size_t)n, [&](void** d) {
+    hipLaunchKernelGGL(hrg_test_hull_box_kernel, dim3((unsigned)n), dim3(64), 0, 0, (const double*)d[0], (const int32_t*)d[1], (const double*)d[2], (const HullBoxQuery*)d[3], (int)n, (double*)d[4]);
+  });
+  return ok ? 0 : -1;
 }

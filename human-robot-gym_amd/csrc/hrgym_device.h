@@ -44,6 +44,56 @@
 #define HRG_HAMMER 0  // HRG_HAMMER=1 (hrgym_hammer.hip, HRG_BOX=0): CollaborativeHammeringCart -- board + nail + hammer, a 24-DoF system in three 8-wide blocks; its own collision tail and solver
 #endif
 #define HRG_BASE_TU (!HRG_BOX && !HRG_STACK && !HRG_HAMMER && !HRG_HULLS)   // hrgym_hip.hip itself: the ReachHuman kernels, the pre-check kernel and the host side (C ABI)
+// The name of this translation unit's kernel variant: <stem><family><hull>, family = the task's kernel family, hull = the arm links' collision geometry.  HRG_SYM names
+// the kernels (hrg_step_kernel_lift_hull), their launch shims and the -DHRG_STAMPS exports; the host side lists the twelve combinations once (HRG_VARIANTS, hrgym_hip.hip).
+#if HRG_HAMMER
+#define HRG_FAMILY_SFX _hammer
+#elif HRG_STACK
+#define HRG_FAMILY_SFX _stack
+#elif HRG_LIFT
+#define HRG_FAMILY_SFX _lift
+#elif HRG_HANDOVER
+#define HRG_FAMILY_SFX _ho
+#elif HRG_BOX
+#define HRG_FAMILY_SFX _box
+#else
+#define HRG_FAMILY_SFX
+#endif
+#if HRG_HULLS
+#define HRG_HULL_SFX _hull
+#else
+#define HRG_HULL_SFX
+#endif
+#define HRG_PASTE3_(a, b, c) a##b##c
+#define HRG_PASTE3(a, b, c) HRG_PASTE3_(a, b, c)
+#define HRG_SYM(stem) HRG_PASTE3(stem, HRG_FAMILY_SFX, HRG_HULL_SFX)
+// Per family: ObjState = the per-env object block the variant streams next to hrg_env_state, HRG_OBJ_LDS = its image in Lds, HRG_KERNEL_WAVES = the waves per SIMD
+// the kernels are compiled for (launch bounds).
+#if HRG_HAMMER
+typedef hrg_hammer_state ObjState;
+#define HRG_OBJ_LDS hm
+#ifndef HRG_HAMMER_WAVES
+#define HRG_HAMMER_WAVES 1   // the allocator's budget (512 registers); it uses 209 without a spill, so the hardware runs a second wave on a SIMD whenever LDS allows
+#endif
+#define HRG_KERNEL_WAVES HRG_HAMMER_WAVES   // 29.5 KB of LDS per env (65 dense rows of J over 24 DoF, the noslip pass's Gram matrix): 5 workgroups per CU
+#elif HRG_STACK
+typedef hrg_stack_state ObjState;
+#define HRG_OBJ_LDS sk
+#ifndef HRG_STACK_WAVES
+#define HRG_STACK_WAVES 2   // measured: 8.05 -> 7.45 ms per 4096-env step (mixed six-task batch 5.68 -> 5.33 ms), 768 B/lane of scratch
+#endif
+#define HRG_KERNEL_WAVES HRG_STACK_WAVES   // 28 KB of LDS per env (92 compact contact rows): 1 = 4 workgroups per CU, one wave per SIMD, up to 512 VGPRs; 2 = 256 registers, five per CU
+#elif HRG_BOX
+typedef hrg_box_state ObjState;
+#define HRG_OBJ_LDS bx
+#ifndef HRG_BOX_WAVES
+#define HRG_BOX_WAVES 3
+#endif
+#define HRG_KERNEL_WAVES HRG_BOX_WAVES   // the variant with the cube needs more registers and LDS
+#else
+typedef hrg_box_state ObjState;     // (ReachHuman streams no object block: the pointer is null)
+#define HRG_KERNEL_WAVES HRG_MIN_WAVES
+#endif
 // The human pose comes from the per-frame pose table (DevModel::pose_tab, built once per batch) in the ReachHuman kernels (capsule and hull) and the lifting
 // kernel; the hand-mocap variants (handover, stacking, hammering) need the hand bodies' rotations, and the cube kernels keep the live tree kinematics too (DESIGN.md
 // section 6).  Host side: hrg_task_uses_pose_table.
@@ -161,6 +211,22 @@ static inline void hull_centroids(const double* verts, const int32_t* off, doubl
     for (int i = off[h]; i < off[h + 1]; i++) for (int a = 0; a < 3; a++) s[a] += verts[3 * i + a];
     for (int a = 0; a < 3; a++) cen[h][a] = s[a] / (double)(off[h + 1] - off[h]);
   }
+}
+
+// host side of a test tap (hrg_test_hull_queries, hrg_test_hull_box_queries, hrg_debug_pose_compare): the n_in host buffers copied to the device, one launch, the
+// output copied back.  launch(d) gets the device buffers, d[0 .. n_in - 1] the inputs in order and d[n_in] the output; all of them are freed on every path.
+struct TapBuf { const void* host; size_t bytes; };
+template <class Launch>
+static bool hrg_run_tap(const TapBuf* in, int n_in, void* out_host, size_t out_bytes, Launch launch) {
+  void* d[8] = {nullptr};
+  bool ok = n_in < 8;
+  for (int i = 0; ok && i < n_in; i++) ok = hipMalloc(&d[i], in[i].bytes) == hipSuccess && hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && hipMalloc(&d[n_in], out_bytes) == hipSuccess) {
+    launch(d);
+    ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, d[n_in], out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+  } else ok = false;
+  for (int i = 0; i < 8; i++) hipFree(d[i]);
+  return ok;
 }
 
 struct Contact {

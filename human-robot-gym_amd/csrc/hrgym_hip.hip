@@ -2882,118 +2882,25 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
 }
 
 // ================================================================================================ kernels
-#if HRG_STACK && HRG_HULLS
-#define hrg_step_kernel hrg_step_kernel_stack_hull   // the stacking task with the arm links' convex hulls (hrgym_stack_hulls.hip)
-#define hrg_reset_kernel hrg_reset_kernel_stack_hull
-#define hrg_stack_launch_step hrg_stack_hull_launch_step
-#define hrg_stack_launch_reset hrg_stack_hull_launch_reset
-typedef hrg_stack_state ObjState;
-#elif HRG_STACK
-#define hrg_step_kernel hrg_step_kernel_stack
-#define hrg_reset_kernel hrg_reset_kernel_stack
-typedef hrg_stack_state ObjState;   // the per-env object block this variant streams next to hrg_env_state
-#elif HRG_HAMMER && HRG_HULLS
-#define hrg_step_kernel hrg_step_kernel_hammer_hull   // the hammering task with the arm links' convex hulls (hrgym_hammer_hulls.hip)
-#define hrg_reset_kernel hrg_reset_kernel_hammer_hull
-#define hrg_hammer_launch_step hrg_hammer_hull_launch_step
-#define hrg_hammer_launch_reset hrg_hammer_hull_launch_reset
-typedef hrg_hammer_state ObjState;
-#elif HRG_HAMMER
-#define hrg_step_kernel hrg_step_kernel_hammer
-#define hrg_reset_kernel hrg_reset_kernel_hammer
-typedef hrg_hammer_state ObjState;
-#elif HRG_HULLS && !HRG_BOX
-#define hrg_step_kernel hrg_step_kernel_hull
-#define hrg_reset_kernel hrg_reset_kernel_hull
-typedef hrg_box_state ObjState;     // (ReachHuman streams no object block: the pointer is null)
-#else
-typedef hrg_box_state ObjState;
-#endif
-#if HRG_BOX && HRG_HANDOVER && HRG_HULLS
-#define hrg_step_kernel hrg_step_kernel_ho_hull   // the handover tasks with the arm links' convex hulls (hrgym_handover_hulls.hip)
-#define hrg_reset_kernel hrg_reset_kernel_ho_hull
-#define hrg_box_launch_step hrg_ho_hull_launch_step
-#define hrg_box_launch_reset hrg_ho_hull_launch_reset
-#elif HRG_BOX && HRG_HANDOVER
-#define hrg_step_kernel hrg_step_kernel_ho
-#define hrg_reset_kernel hrg_reset_kernel_ho
-#define hrg_box_launch_step hrg_ho_launch_step
-#define hrg_box_launch_reset hrg_ho_launch_reset
-#elif HRG_BOX && HRG_LIFT && HRG_HULLS
-#define hrg_step_kernel hrg_step_kernel_lift_hull   // the lifting task with the arm links' convex hulls (hrgym_lift_hulls.hip)
-#define hrg_reset_kernel hrg_reset_kernel_lift_hull
-#define hrg_box_launch_step hrg_lift_hull_launch_step
-#define hrg_box_launch_reset hrg_lift_hull_launch_reset
-#elif HRG_BOX && HRG_LIFT
-#define hrg_step_kernel hrg_step_kernel_lift
-#define hrg_reset_kernel hrg_reset_kernel_lift
-#define hrg_box_launch_step hrg_lift_launch_step
-#define hrg_box_launch_reset hrg_lift_launch_reset
-#elif HRG_BOX && HRG_HULLS
-#define hrg_step_kernel hrg_step_kernel_box_hull   // the cube tasks with the arm links' convex hulls (hrgym_box_hulls.hip)
-#define hrg_reset_kernel hrg_reset_kernel_box_hull
-#define hrg_box_launch_step hrg_box_hull_launch_step
-#define hrg_box_launch_reset hrg_box_hull_launch_reset
-#elif HRG_BOX
-#define hrg_step_kernel hrg_step_kernel_box
-#define hrg_reset_kernel hrg_reset_kernel_box
-#endif
-#if HRG_BOX
-#ifndef HRG_BOX_WAVES
-#define HRG_BOX_WAVES 3
-#endif
-#define HRG_KERNEL_WAVES HRG_BOX_WAVES   // the variant with the cube needs more registers and LDS
-// the cube's state block: streamed like the env block
-DI void box_load(const hrg_box_state* __restrict__ boxes, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_box_state) / sizeof(double));
-  const double* src = (const double*)(boxes + e);
-  double* dst = (double*)&g_L.bx;
-  if (lane < NB) dst[lane] = src[lane];
+// (the variant's name suffix, ObjState and HRG_KERNEL_WAVES: hrgym_device.h, HRG_SYM)
+#if HRG_BOX || HRG_STACK || HRG_HAMMER
+// the object's state block: streamed like the env block (the cube's fits one pass of the wave)
+DI void box_load(const ObjState* __restrict__ objs, int e, int lane) {
+  constexpr int NB = (int)(sizeof(ObjState) / sizeof(double));
+  const double* src = (const double*)(objs + e);
+  double* dst = (double*)&g_L.HRG_OBJ_LDS;
+  if constexpr (HRG_BOX) { if (lane < NB) dst[lane] = src[lane]; }
+  else for (int k = lane; k < NB; k += 64) dst[k] = src[k];
 }
-DI void box_store(hrg_box_state* __restrict__ boxes, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_box_state) / sizeof(double));
-  double* out = (double*)(boxes + e);
-  const double* src = (const double*)&g_L.bx;
-  if (lane < NB) out[lane] = src[lane];
+DI void box_store(ObjState* __restrict__ objs, int e, int lane) {
+  constexpr int NB = (int)(sizeof(ObjState) / sizeof(double));
+  double* out = (double*)(objs + e);
+  const double* src = (const double*)&g_L.HRG_OBJ_LDS;
+  if constexpr (HRG_BOX) { if (lane < NB) out[lane] = src[lane]; }
+  else for (int k = lane; k < NB; k += 64) out[k] = src[k];
 }
-#elif HRG_STACK
-#ifndef HRG_STACK_WAVES
-#define HRG_STACK_WAVES 2   // measured: 8.05 -> 7.45 ms per 4096-env step (mixed six-task batch 5.68 -> 5.33 ms), 768 B/lane of scratch
 #endif
-#define HRG_KERNEL_WAVES HRG_STACK_WAVES   // 28 KB of LDS per env (92 compact contact rows): 1 = 4 workgroups per CU, one wave per SIMD, up to 512 VGPRs; 2 = 256 registers, five per CU
-DI void box_load(const hrg_stack_state* __restrict__ stacks, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_stack_state) / sizeof(double));
-  const double* src = (const double*)(stacks + e);
-  double* dst = (double*)&g_L.sk;
-  for (int k = lane; k < NB; k += 64) dst[k] = src[k];
-}
-DI void box_store(hrg_stack_state* __restrict__ stacks, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_stack_state) / sizeof(double));
-  double* out = (double*)(stacks + e);
-  const double* src = (const double*)&g_L.sk;
-  for (int k = lane; k < NB; k += 64) out[k] = src[k];
-}
-#elif HRG_HAMMER
-#ifndef HRG_HAMMER_WAVES
-#define HRG_HAMMER_WAVES 1   // the allocator's budget (512 registers); it uses 209 without a spill, so the hardware runs a second wave on a SIMD whenever LDS allows
-#endif
-#define HRG_KERNEL_WAVES HRG_HAMMER_WAVES   // 29.5 KB of LDS per env (65 dense rows of J over 24 DoF, the noslip pass's Gram matrix): 5 workgroups per CU
-DI void box_load(const hrg_hammer_state* __restrict__ hammers, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_hammer_state) / sizeof(double));
-  const double* src = (const double*)(hammers + e);
-  double* dst = (double*)&g_L.hm;
-  for (int k = lane; k < NB; k += 64) dst[k] = src[k];
-}
-DI void box_store(hrg_hammer_state* __restrict__ hammers, int e, int lane) {
-  constexpr int NB = (int)(sizeof(hrg_hammer_state) / sizeof(double));
-  double* out = (double*)(hammers + e);
-  const double* src = (const double*)&g_L.hm;
-  for (int k = lane; k < NB; k += 64) out[k] = src[k];
-}
-#else
-#define HRG_KERNEL_WAVES HRG_MIN_WAVES
-#endif
-__global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void hrg_step_kernel(const DevModel* __restrict__ dm, hrg_env_state* __restrict__ states, double* __restrict__ actions,
+__global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void HRG_SYM(hrg_step_kernel)(const DevModel* __restrict__ dm, hrg_env_state* __restrict__ states, double* __restrict__ actions,
                                                      float* __restrict__ obs, float* __restrict__ term_obs, float* __restrict__ reward, uint8_t* __restrict__ done,
                                                      int32_t* __restrict__ info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* __restrict__ scratch_obs,
                                                      ObjState* __restrict__ boxes, int n_envs, StepOrder ord) {
@@ -3030,7 +2937,7 @@ __global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void hrg_step_
 #endif
 }
 
-__global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void hrg_reset_kernel(const DevModel* __restrict__ dm, hrg_env_state* __restrict__ states, const uint8_t* __restrict__ mask,
+__global__ __launch_bounds__(64 * HRG_WG_WAVES, HRG_KERNEL_WAVES) void HRG_SYM(hrg_reset_kernel)(const DevModel* __restrict__ dm, hrg_env_state* __restrict__ states, const uint8_t* __restrict__ mask,
                                                       float* __restrict__ obs, int64_t env_id0, ObjState* __restrict__ boxes, int n_envs) {
   const int e = hrg_env(), lane = hrg_lane();
   if (e >= n_envs) return;
@@ -3130,137 +3037,23 @@ __global__ __launch_bounds__(64) void hrg_pose_compare_kernel(const DevModel* __
 }
 #endif
 
-// launch shims of the cube variant: defined by hrgym_box.hip (this file compiled with HRG_BOX=1), called by the host side below
-extern "C" __attribute__((visibility("hidden"))) void hrg_box_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                           float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                           float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_box_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                            int64_t env_id0, hrg_box_state* boxes);
-#if HRG_BASE_TU
-// ... of the stacking variant (hrgym_stack.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_stack_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                             float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                             float* scratch_obs, hrg_stack_state* stacks, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_stack_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                              int64_t env_id0, hrg_stack_state* stacks);
-#endif
-#if HRG_BASE_TU
-// ... of the hammering variant (hrgym_hammer.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                              float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                              float* scratch_obs, hrg_hammer_state* hammers, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                               int64_t env_id0, hrg_hammer_state* hammers);
-// the same shims of the handover variant (hrgym_handover.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_ho_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                          float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                          float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_ho_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                           int64_t env_id0, hrg_box_state* boxes);
-// ... and of the lifting variant (hrgym_lift.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_lift_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                            float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                            float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_lift_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                             int64_t env_id0, hrg_box_state* boxes);
-#endif
-#if HRG_BASE_TU
-// ... of the hull variant of the cube kernels (hrgym_box_hulls.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_box_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                                float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                                float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_box_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                                 int64_t env_id0, hrg_box_state* boxes);
-// ... of the hull variant of the ReachHuman kernels (hrgym_hulls.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                            float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                            float* scratch_obs, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                             int64_t env_id0);
-// ... of the hull variants of the handover, lifting, stacking and hammering kernels (hrgym_handover_hulls.hip, hrgym_lift_hulls.hip, hrgym_stack_hulls.hip,
-// hrgym_hammer_hulls.hip)
-extern "C" __attribute__((visibility("hidden"))) void hrg_ho_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                               float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                               float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_ho_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                                int64_t env_id0, hrg_box_state* boxes);
-extern "C" __attribute__((visibility("hidden"))) void hrg_lift_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                                 float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                                 float* scratch_obs, hrg_box_state* boxes, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_lift_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                                  int64_t env_id0, hrg_box_state* boxes);
-extern "C" __attribute__((visibility("hidden"))) void hrg_stack_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                                  float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                                  float* scratch_obs, hrg_stack_state* stacks, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_stack_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                                   int64_t env_id0, hrg_stack_state* stacks);
-extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs,
-                                                                                   float* reward, uint8_t* done, int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0,
-                                                                                   float* scratch_obs, hrg_hammer_state* hammers, StepOrder ord);
-extern "C" __attribute__((visibility("hidden"))) void hrg_hammer_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs,
-                                                                                    int64_t env_id0, hrg_hammer_state* hammers);
-#endif
-#if HRG_HULLS && !HRG_BOX && !HRG_STACK && !HRG_HAMMER
-extern "C" void hrg_hull_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
-                                     int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, StepOrder ord) {
-  hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, (ObjState*)nullptr, n_envs, ord);
+// Launch shims: every translation unit defines this pair for its own kernels, under the variant's name and with hidden visibility; the host side (the base
+// translation unit) reaches them through its variant table (HRG_VARIANTS).  objs = the variant's object array (ObjState), null for the ReachHuman kernels.
+typedef void hrg_launch_step_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
+                                int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, void* objs, StepOrder ord);
+typedef void hrg_launch_reset_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, void* objs);
+extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn HRG_SYM(hrg_launch_step);
+extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn HRG_SYM(hrg_launch_reset);
+extern "C" void HRG_SYM(hrg_launch_step)(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
+                                         int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, void* objs, StepOrder ord) {
+  hipLaunchKernelGGL(HRG_SYM(hrg_step_kernel), HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, (ObjState*)objs,
+                     n_envs, ord);
 }
-extern "C" void hrg_hull_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0) {
-  hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, (ObjState*)nullptr, n_envs);
+extern "C" void HRG_SYM(hrg_launch_reset)(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, void* objs) {
+  hipLaunchKernelGGL(HRG_SYM(hrg_reset_kernel), HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, (ObjState*)objs, n_envs);
 }
-#endif
-#if HRG_HAMMER
-extern "C" void hrg_hammer_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
-                                       int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, hrg_hammer_state* hammers, StepOrder ord) {
-  hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, hammers, n_envs, ord);
-}
-extern "C" void hrg_hammer_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, hrg_hammer_state* hammers) {
-  hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, hammers, n_envs);
-}
-#endif
-#if HRG_STACK
-extern "C" void hrg_stack_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
-                                      int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, hrg_stack_state* stacks, StepOrder ord) {
-  hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, stacks, n_envs, ord);
-}
-extern "C" void hrg_stack_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, hrg_stack_state* stacks) {
-  hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, stacks, n_envs);
-}
-#endif
-#if HRG_BOX
-extern "C" void hrg_box_launch_step(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
-                                    int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, hrg_box_state* boxes, StepOrder ord) {
-  hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, actions, obs, term_obs, reward, done, info, dbg_r, dbg_h, dbg_nh, env_id0, scratch_obs, boxes, n_envs, ord);
-}
-extern "C" void hrg_box_launch_reset(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, hrg_box_state* boxes) {
-  hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, boxes, n_envs);
-}
-#endif
 
 #ifdef HRG_STAMPS
-#if HRG_STACK && HRG_HULLS
-#define hrg_debug_stamps hrg_debug_stamps_stack_hull
-#elif HRG_STACK
-#define hrg_debug_stamps hrg_debug_stamps_stack
-#elif HRG_HAMMER && HRG_HULLS
-#define hrg_debug_stamps hrg_debug_stamps_hammer_hull
-#elif HRG_HAMMER
-#define hrg_debug_stamps hrg_debug_stamps_hammer
-#elif HRG_BOX && HRG_HULLS && HRG_HANDOVER
-#define hrg_debug_stamps hrg_debug_stamps_ho_hull
-#elif HRG_BOX && HRG_HULLS && HRG_LIFT
-#define hrg_debug_stamps hrg_debug_stamps_lift_hull
-#elif HRG_BOX && HRG_HULLS
-#define hrg_debug_stamps hrg_debug_stamps_box_hull
-#elif HRG_HANDOVER
-#define hrg_debug_stamps hrg_debug_stamps_ho
-#elif HRG_LIFT
-#define hrg_debug_stamps hrg_debug_stamps_lift
-#elif HRG_BOX
-#define hrg_debug_stamps hrg_debug_stamps_box
-#elif HRG_HULLS
-#define hrg_debug_stamps hrg_debug_stamps_hull
-#endif
 #if HRG_BASE_TU
 // waves that live longer than `thresh` shader cycles are also summed into a second set of accumulators: out[0..31] phase sums, out[32] their number, out[33] lifetime sum
 extern "C" int hrg_debug_stamps_slow(double* out, unsigned long long thresh, int reset) {
@@ -3272,51 +3065,16 @@ extern "C" int hrg_debug_stamps_slow(double* out, unsigned long long thresh, int
   return 0;
 }
 #endif
-extern "C" int hrg_debug_stamps(double* out, int reset) {
+// each translation unit has its own accumulators, read through exports that carry the variant's name (tools/stamps.py, tools/env_top.py)
+extern "C" int HRG_SYM(hrg_debug_stamps)(double* out, int reset) {
   unsigned long long h[32];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_stamps), sizeof h) != hipSuccess) return -1;
   for (int i = 0; i < 32; i++) out[i] = (double)h[i];
   if (reset) { memset(h, 0, sizeof h); hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), h, sizeof h); }
   return 0;
 }
-#if HRG_HAMMER && HRG_HULLS
-#define hrg_debug_envacc hrg_debug_envacc_hammer_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_hammer_hull
-#elif HRG_HAMMER
-#define hrg_debug_envacc hrg_debug_envacc_hammer
-#define hrg_debug_envcyc hrg_debug_envcyc_hammer
-#elif HRG_STACK && HRG_HULLS
-#define hrg_debug_envacc hrg_debug_envacc_stack_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_stack_hull
-#elif HRG_STACK
-#define hrg_debug_envacc hrg_debug_envacc_stack
-#define hrg_debug_envcyc hrg_debug_envcyc_stack
-#elif HRG_BOX && HRG_HULLS && HRG_HANDOVER
-#define hrg_debug_envacc hrg_debug_envacc_ho_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_ho_hull
-#elif HRG_BOX && HRG_HULLS && HRG_LIFT
-#define hrg_debug_envacc hrg_debug_envacc_lift_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_lift_hull
-#elif HRG_BOX && HRG_HULLS
-#define hrg_debug_envacc hrg_debug_envacc_box_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_box_hull
-#elif HRG_HANDOVER
-#define hrg_debug_envacc hrg_debug_envacc_ho
-#define hrg_debug_envcyc hrg_debug_envcyc_ho
-#elif HRG_LIFT
-#define hrg_debug_envacc hrg_debug_envacc_lift
-#define hrg_debug_envcyc hrg_debug_envcyc_lift
-#elif HRG_BOX
-#define hrg_debug_envacc hrg_debug_envacc_box
-#define hrg_debug_envcyc hrg_debug_envcyc_box
-#elif HRG_HULLS
-#define hrg_debug_envacc hrg_debug_envacc_hull
-#define hrg_debug_envcyc hrg_debug_envcyc_hull
-#endif
-#if 1
-extern "C" int hrg_debug_envacc(unsigned long long* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_envacc), sizeof(unsigned long long) * 32 * n) == hipSuccess ? 0 : -1; }
-extern "C" int hrg_debug_envcyc(unsigned long long* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_envcyc), sizeof(unsigned long long) * 3 * n) == hipSuccess ? 0 : -1; }
-#endif
+extern "C" int HRG_SYM(hrg_debug_envacc)(unsigned long long* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_envacc), sizeof(unsigned long long) * 32 * n) == hipSuccess ? 0 : -1; }
+extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_envcyc), sizeof(unsigned long long) * 3 * n) == hipSuccess ? 0 : -1; }
 #endif
 
 #if HRG_BASE_TU
@@ -3369,6 +3127,59 @@ static int32_t* fair_table(int device) {
     tab[device] = p;
   }
   return tab[device];
+}
+
+// Every kernel variant of the library, once: X(family, hulls, name suffix).  The suffix is the one HRG_SYM gives the variant's translation unit (hrgym_device.h);
+// a line here, the wrapper .hip that sets its flags and its entry in _lib.SOURCES are what a new variant needs.
+enum { HRG_FAM_REACH, HRG_FAM_BOX, HRG_FAM_HO, HRG_FAM_LIFT, HRG_FAM_STACK, HRG_FAM_HAMMER, HRG_NFAMILY };
+#define HRG_VARIANTS(X)                                              \
+  X(HRG_FAM_REACH, 0, )          X(HRG_FAM_REACH, 1, _hull)          \
+  X(HRG_FAM_BOX, 0, _box)        X(HRG_FAM_BOX, 1, _box_hull)        \
+  X(HRG_FAM_HO, 0, _ho)          X(HRG_FAM_HO, 1, _ho_hull)          \
+  X(HRG_FAM_LIFT, 0, _lift)      X(HRG_FAM_LIFT, 1, _lift_hull)      \
+  X(HRG_FAM_STACK, 0, _stack)    X(HRG_FAM_STACK, 1, _stack_hull)    \
+  X(HRG_FAM_HAMMER, 0, _hammer)  X(HRG_FAM_HAMMER, 1, _hammer_hull)
+#define X(family, hulls, sfx)                                                                  \
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn hrg_launch_step##sfx;    \
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;
+HRG_VARIANTS(X)
+#undef X
+struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; };
+struct VariantTable { Variant v[HRG_NFAMILY][2]; };   // [family][hulls]
+static constexpr VariantTable make_variants() {
+  VariantTable t{};
+#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx};
+  HRG_VARIANTS(X)
+#undef X
+  return t;
+}
+static const VariantTable g_variants = make_variants();
+
+// the variant that steps a batch, and the object array its kernels stream (null: the ReachHuman kernels stream none)
+static const Variant& batch_variant(const hrg_batch* b, void** objs) {
+  int family = HRG_FAM_REACH;
+  *objs = nullptr;
+  if (b->task == HRG_TASK_HAMMERING) { family = HRG_FAM_HAMMER; *objs = b->d_hammers; }
+  else if (b->task == HRG_TASK_STACKING) { family = HRG_FAM_STACK; *objs = b->d_stacks; }
+  else if (b->task != HRG_TASK_REACH) {
+    family = b->task == HRG_TASK_LIFTING ? HRG_FAM_LIFT : (HRG_IS_HANDOVER(b->task) ? HRG_FAM_HO : HRG_FAM_BOX);
+    *objs = b->d_boxes;
+  }
+  return g_variants.v[family][b->hulls ? 1 : 0];
+}
+
+// one env's block of a per-env device array <-> the host (hrg_batch_get_ / set_ state, box, stack, hammer); missing = the error of a batch of another task,
+// which has no such array (null: every batch has it)
+template <class T>
+static int env_block_copy(hrg_batch* b, int32_t env, T* hrg_batch::*arr, void* buf_host, size_t bytes, bool get, const char* missing) {
+  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(T)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
+  T* const dev = b->*arr;
+  if (missing && !dev) return fail(HRG_ERR_INVALID, missing);
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (get) HIPCHK(hipMemcpy(buf_host, dev + env, bytes, hipMemcpyDeviceToHost));
+  else HIPCHK(hipMemcpy(dev + env, buf_host, bytes, hipMemcpyHostToDevice));
+  return HRG_OK;
 }
 
 // the kernels built with HRG_POSE_TABLE: ReachHuman (hrgym_hip.hip, hrgym_hulls.hip) and lifting (hrgym_lift.hip); every other task steps with a cube kernel
@@ -3632,33 +3443,19 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
   for (int k = 0; k < n; k++)
     if (qh[k].clip < 0 || qh[k].clip >= hm.clips.n_clips || qh[k].at < 0 || qh[k].at >= hm.clips.clip_len[qh[k].clip]) return fail(HRG_ERR_INVALID, "query outside the clip set");
   const size_t ob = sizeof(double) * 2 * (6 * HRG_NHB + 3 * HRG_NHJ) * (size_t)n;
-  PoseQuery* dq = nullptr;
-  double* dout = nullptr;
-  bool ok = false;
-  if (hipMalloc(&dq, sizeof(PoseQuery) * (size_t)n) == hipSuccess && hipMalloc(&dout, ob) == hipSuccess &&
-      hipMemcpy(dq, qh, sizeof(PoseQuery) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-    hipLaunchKernelGGL(hrg_pose_compare_kernel, dim3((unsigned)n), dim3(64), 0, 0, b->d_model, dq, (int)n, dout);
-    ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, dout, ob, hipMemcpyDeviceToHost) == hipSuccess;
-  }
-  hipFree(dq); hipFree(dout);
+  const TapBuf in[] = {{qh, sizeof(PoseQuery) * (size_t)n}};
+  const bool ok = hrg_run_tap(in, 1, out_host, ob, [&](void** d) {
+    hipLaunchKernelGGL(hrg_pose_compare_kernel, dim3((unsigned)n), dim3(64), 0, 0, b->d_model, (const PoseQuery*)d[0], (int)n, (double*)d[1]);
+  });
   return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_pose_compare: device allocation / copy / launch failed");
 }
 
 int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {
   if (!b) return fail(HRG_ERR_INVALID, "null batch");
   HIPCHK(hipSetDevice(b->device));
-  if (b->task == HRG_TASK_HAMMERING && b->hulls) hrg_hammer_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_hammers);
-  else if (b->task == HRG_TASK_HAMMERING) hrg_hammer_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_hammers);
-  else if (b->task == HRG_TASK_STACKING && b->hulls) hrg_stack_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_stacks);
-  else if (b->task == HRG_TASK_STACKING) hrg_stack_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_stacks);
-  else if (b->task == HRG_TASK_LIFTING && b->hulls) hrg_lift_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (b->task == HRG_TASK_LIFTING) hrg_lift_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (HRG_IS_HANDOVER(b->task) && b->hulls) hrg_ho_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (HRG_IS_HANDOVER(b->task)) hrg_ho_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (b->task != HRG_TASK_REACH && b->hulls) hrg_box_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (b->task != HRG_TASK_REACH) hrg_box_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes);
-  else if (b->hulls) hrg_hull_launch_reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0);
-  else hipLaunchKernelGGL(hrg_reset_kernel, HRG_LAUNCH_DIMS(b->n_envs), 0, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, b->d_boxes, b->n_envs);
+  void* objs;
+  const Variant& v = batch_variant(b, &objs);
+  v.reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, objs);
   HIPCHK(hipGetLastError());
   return HRG_OK;
 }
@@ -3684,42 +3481,10 @@ int hrg_batch_step(hrg_batch* b, double* actions_dev, float* obs_dev, float* ter
   int32_t* fair = fair_table(b->device);
   if (!fair) return fail(HRG_ERR_HIP, "cannot allocate the wave-progress table");
   const StepOrder ord{b->d_order, b->n_envs, b->parity, fair};
-  if (b->task == HRG_TASK_HAMMERING && b->hulls)
-    hrg_hammer_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                                b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_hammers, ord);
-  else if (b->task == HRG_TASK_HAMMERING)
-    hrg_hammer_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                           b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_hammers, ord);
-  else if (b->task == HRG_TASK_STACKING && b->hulls)
-    hrg_stack_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                               b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_stacks, ord);
-  else if (b->task == HRG_TASK_STACKING)
-    hrg_stack_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                          b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_stacks, ord);
-  else if (b->task == HRG_TASK_LIFTING && b->hulls)
-    hrg_lift_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                              b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (b->task == HRG_TASK_LIFTING)
-    hrg_lift_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                         b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (HRG_IS_HANDOVER(b->task) && b->hulls)
-    hrg_ho_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                            b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (HRG_IS_HANDOVER(b->task))
-    hrg_ho_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                       b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (b->task != HRG_TASK_REACH && b->hulls)
-    hrg_box_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                             b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (b->task != HRG_TASK_REACH)
-    hrg_box_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                        b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, ord);
-  else if (b->hulls)
-    hrg_hull_launch_step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                         b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, ord);
-  else
-    hipLaunchKernelGGL(hrg_step_kernel, HRG_LAUNCH_DIMS(b->n_envs), 0, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev,
-                       b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr, b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, b->d_boxes, b->n_envs, ord);
+  void* objs;
+  const Variant& v = batch_variant(b, &objs);
+  v.step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr,
+         b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, objs, ord);
   HIPCHK(hipGetLastError());
   b->parity ^= 1;
   if (b->timing) { HIPCHK(hipEventRecord(ev.second, st)); b->events.push_back(ev); }
@@ -3759,72 +3524,21 @@ int hrg_batch_capsules(hrg_batch* b, double* robot_host, double* human_host, int
   return HRG_OK;
 }
 
-int hrg_batch_get_state(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_env_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(buf_host, b->d_states + env, bytes, hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-int hrg_batch_set_state(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_env_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_states + env, buf_host, bytes, hipMemcpyHostToDevice));
-  return HRG_OK;
-}
-
-int hrg_batch_get_box(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_box_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(buf_host, b->d_boxes + env, bytes, hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-int hrg_batch_set_box(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_box_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_boxes + env, buf_host, bytes, hipMemcpyHostToDevice));
-  return HRG_OK;
-}
-
+int hrg_batch_get_state(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, buf_host, bytes, true, nullptr); }
+int hrg_batch_set_state(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, (void*)buf_host, bytes, false, nullptr); }
+int hrg_batch_get_box(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, buf_host, bytes, true, nullptr); }
+int hrg_batch_set_box(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, (void*)buf_host, bytes, false, nullptr); }
 int hrg_batch_get_stack(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_stack_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  if (!b->d_stacks) return fail(HRG_ERR_INVALID, "not a CollaborativeStackingCart batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(buf_host, b->d_stacks + env, bytes, hipMemcpyDeviceToHost));
-  return HRG_OK;
+  return env_block_copy(b, env, &hrg_batch::d_stacks, buf_host, bytes, true, "not a CollaborativeStackingCart batch");
 }
-
 int hrg_batch_set_stack(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_stack_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  if (!b->d_stacks) return fail(HRG_ERR_INVALID, "not a CollaborativeStackingCart batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_stacks + env, buf_host, bytes, hipMemcpyHostToDevice));
-  return HRG_OK;
+  return env_block_copy(b, env, &hrg_batch::d_stacks, (void*)buf_host, bytes, false, "not a CollaborativeStackingCart batch");
 }
-
 int hrg_batch_get_hammer(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_hammer_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  if (!b->d_hammers) return fail(HRG_ERR_INVALID, "not a CollaborativeHammeringCart batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(buf_host, b->d_hammers + env, bytes, hipMemcpyDeviceToHost));
-  return HRG_OK;
+  return env_block_copy(b, env, &hrg_batch::d_hammers, buf_host, bytes, true, "not a CollaborativeHammeringCart batch");
 }
-
 int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(hrg_hammer_state)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  if (!b->d_hammers) return fail(HRG_ERR_INVALID, "not a CollaborativeHammeringCart batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(b->d_hammers + env, buf_host, bytes, hipMemcpyHostToDevice));
-  return HRG_OK;
+  return env_block_copy(b, env, &hrg_batch::d_hammers, (void*)buf_host, bytes, false, "not a CollaborativeHammeringCart batch");
 }
 
 int hrg_batch_get_states(hrg_batch* b, const int32_t* envs_host, int32_t n, void* states_host, void* boxes_host) {

@@ -32,17 +32,9 @@ extern "C" int hrg_test_hull_queries(const double* verts_host, const int32_t* of
   for (int h = 0; h < HRG_NHULL; h++) if (!(off_host[h + 1] > off_host[h] + 3)) return -1;
   const HullQuery* qh = (const HullQuery*)queries_host;
   for (int k = 0; k < n; k++) if (qh[k].hull < 0 || qh[k].hull >= HRG_NHULL) return -1;
-  double *dv = nullptr, *dout = nullptr;
-  int32_t* doff = nullptr;
-  HullQuery* dq = nullptr;
-  const size_t vb = sizeof(double) * 3 * (size_t)off_host[HRG_NHULL];
-  int rc = -1;
-  if (hipMalloc(&dv, vb) == hipSuccess && hipMalloc(&doff, sizeof(int32_t) * (HRG_NHULL + 1)) == hipSuccess && hipMalloc(&dq, sizeof(HullQuery) * (size_t)n) == hipSuccess &&
-      hipMalloc(&dout, sizeof(double) * 10 * (size_t)n) == hipSuccess && hipMemcpy(dv, verts_host, vb, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(doff, off_host, sizeof(int32_t) * (HRG_NHULL + 1), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dq, qh, sizeof(HullQuery) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-    hipLaunchKernelGGL(hrg_test_hull_kernel, dim3((unsigned)n), dim3(64), 0, 0, dv, doff, dq, (int)n, dout);
-    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, dout, sizeof(double) * 10 * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-  }
-  hipFree(dv); hipFree(doff); hipFree(dq); hipFree(dout);
-  return rc;
+  const TapBuf in[] = {{verts_host, sizeof(double) * 3 * (size_t)off_host[HRG_NHULL]}, {off_host, sizeof(int32_t) * (HRG_NHULL + 1)}, {qh, sizeof(HullQuery) * (size_t)n}};
+  const bool ok = hrg_run_tap(in, 3, out_host, sizeof(double) * 10 * (size_t)n, [&](void** d) {
+    hipLaunchKernelGGL(hrg_test_hull_kernel, dim3((unsigned)n), dim3(64), 0, 0, (const double*)d[0], (const int32_t*)d[1], (const HullQuery*)d[2], (int)n, (double*)d[3]);
+  });
+  return ok ? 0 : -1;
 }

@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
-"""Per-function register / scratch usage of the gfx950 code object (tuning aid): python tools/regs.py [-DHRG_PHASE='__device__ __noinline__' ...]"""
+"""Per-function register / scratch usage of the gfx950 code object (tuning aid): python tools/regs.py [UNIT.hip] [-DHRG_PHASE='__device__ __noinline__' ...]
+UNIT.hip: one of the library's translation units by file name (hrgym_lift_hulls.hip; _lib.SOURCES); the default is the base one, hrgym_hip.hip."""
 import glob, os, re, subprocess, sys, tempfile
-src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "human-robot-gym_amd", "csrc", "hrgym_hip.hip")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from human_robot_gym_amd import _lib
+args = sys.argv[1:]
+src = _lib.SRC
+if args and args[0].endswith(".hip"):
+    src = {os.path.basename(s): s for s in _lib.SOURCES}[os.path.basename(args.pop(0))]
 d = tempfile.mkdtemp()
-subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-save-temps", "-Wno-unused-value", "-Xarch_device", "-fapprox-func", "-mllvm", "-disable-machine-licm", *sys.argv[1:], "-o", "t.o", src], cwd=d, stderr=subprocess.DEVNULL)
+subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-save-temps", "-Wno-unused-value", "-Xarch_device", "-fapprox-func", "-mllvm", "-disable-machine-licm", *args, "-o", "t.o", src], cwd=d, stderr=subprocess.DEVNULL)
 s = open(glob.glob(d + "/*gfx950*.s")[0]).read()
 for m in re.finditer(r"\.type\s+(\S+),@function", s):
     name = m.group(1)
