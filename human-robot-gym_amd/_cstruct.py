@@ -78,6 +78,7 @@ EnvState = _STRUCTS["hrg_env_state"]
 BoxState = _STRUCTS["hrg_box_state"]
 StackState = _STRUCTS["hrg_stack_state"]
 HammerState = _STRUCTS["hrg_hammer_state"]
+ExpertDesc = _STRUCTS["hrg_expert_desc"]
 
 
 def struct_to_dict(s):

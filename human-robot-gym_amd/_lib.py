@@ -7,7 +7,7 @@ import ctypes
 import os
 import subprocess
 
-from ._cstruct import CONST, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable
+from ._cstruct import CONST, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhrgym_hip.so")   # the one shipping library; no environment variable redirects it
@@ -33,12 +33,13 @@ EXPORTS = [
     "hrg_batch_check_actions", "hrg_stack_bytes", "hrg_batch_get_stack", "hrg_batch_set_stack", "hrg_batch_launch_order",
     "hrg_hammer_bytes", "hrg_batch_get_hammer", "hrg_batch_set_hammer", "hrg_test_hull_queries",
     "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks", "hrg_batch_pose_table_bytes", "hrg_debug_pose_compare",
+    "hrg_batch_expert_attach", "hrg_batch_expert_actions", "hrg_batch_step_imitation",
 ]
 
 
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h")] + [
+    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h")] + [
         os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
@@ -118,6 +119,9 @@ def load_library():
     lib.hrg_batch_set_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
     lib.hrg_batch_enable_taps.argtypes = [vp, i32]
     lib.hrg_batch_check_actions.argtypes = [vp, vp, vp, vp]
+    lib.hrg_batch_expert_attach.argtypes = [vp, ctypes.POINTER(ExpertDesc)]
+    lib.hrg_batch_expert_actions.argtypes = [vp, vp, vp, vp]
+    lib.hrg_batch_step_imitation.argtypes = [vp] * 9
     lib.hrg_batch_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
     if lib.hrg_state_bytes() != ctypes.sizeof(EnvState):
         raise RuntimeError("hrg_env_state layout mismatch between header mirror and library: rebuild")
@@ -222,6 +226,54 @@ class HipBatch:
             _check(self.lib, self.lib.hrg_batch_check_actions(self.h, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()))
         self._keep_chk = actions
         return out
+
+    def attach_expert(self, desc):
+        """Attach a scripted expert (and, with desc.reward_enabled, the action-based imitation reward): `desc` is an ExpertDesc, e.g. from
+        expert.build_expert_desc.  Allocates and zeroes the expert's per-env buffers (synchronous; not on the step path).  HrgError when the expert does
+        not fit the batch's task or action form."""
+        t = self.torch
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_expert_attach(self.h, ctypes.byref(desc)))
+        self.expert_desc = desc
+        self.imit = t.zeros(self.n, CONST["HRG_IMIT_DIM"], dtype=t.float32, device=self.device)
+        self._expert_act = t.zeros(self.n, CONST["HRG_ACT_DIM"], dtype=t.float64, device=self.device)
+
+    def expert_actions(self, obs=None):
+        """The expert's action for every env: float64 tensor [n, 7] on device (Cartesian experts fill the first four columns).  `obs`: float32 [n, 64]
+        rows of the observation superset (default: the batch's own, as the last reset / step left them).  Every call advances the expert's noise once.
+        The returned tensor is reused by the next call."""
+        t = self.torch
+        if getattr(self, "expert_desc", None) is None:
+            raise HrgError("no expert attached: call attach_expert() first")
+        if obs is None:
+            obs = self.obs
+        elif obs.dtype != t.float32 or obs.device != self.device or not obs.is_contiguous():
+            obs = obs.to(device=self.device, dtype=t.float32).contiguous()
+        if tuple(obs.shape) != (self.n, CONST["HRG_OBS_DIM"]):
+            raise ValueError(f"obs must be [{self.n}, {CONST['HRG_OBS_DIM']}]")
+        vp = ctypes.c_void_p
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_expert_actions(self.h, vp(obs.data_ptr()), vp(self._expert_act.data_ptr()), self._stream()))
+        self._keep_obs = obs
+        return self._expert_act
+
+    def step_imitation(self, actions):
+        """`step` with the attached imitation reward: returns (obs, reward, done, info, imit); `reward` is r_im alpha + r_env (1 - alpha), `imit` the
+        float32 [n, HRG_IMIT_DIM] row per env (r_im, r_env, r_motion, r_gripper, episode sums of r_im / r_env, episode length, combined reward)."""
+        t = self.torch
+        if getattr(self, "expert_desc", None) is None:
+            raise HrgError("no expert attached: call attach_expert() first")
+        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
+        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
+            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
+        vp = ctypes.c_void_p
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_step_imitation(self.h, vp(actions.data_ptr()), vp(self.obs.data_ptr()), vp(self.term_obs.data_ptr()),
+                                                             vp(self.reward.data_ptr()), vp(self.done.data_ptr()), vp(self.info.data_ptr()), vp(self.imit.data_ptr()),
+                                                             self._stream()))
+        self._keep = actions
+        return self.obs, self.reward, self.done, self.info, self.imit
 
     def get_state(self, e):
         s = EnvState()

@@ -3078,6 +3078,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #endif
 
 #if HRG_BASE_TU
+#include "hrgym_expert.h"   // the scripted experts + imitation reward kernels (hrg_batch_expert_*, hrg_batch_step_imitation)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -3110,6 +3111,10 @@ struct hrg_batch {
   int32_t* d_order = nullptr;          // launch order of the step kernel (StepOrder): two orders of n_envs + two pairs of counters
   int32_t parity = 0;                  // which of the two orders the next step launch reads
   int32_t task = HRG_TASK_REACH;
+  bool ik = false;                     // the Cartesian action front-end is on: action rows are [dx, dy, dz, gripper, -, -, -]
+  bool has_expert = false;             // hrg_batch_expert_attach
+  hrg_expert_desc expert;              // the attached expert (a kernel argument of the two expert kernels)
+  ExpertBuffers ex;
   bool timing = false;
   bool taps = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -3259,7 +3264,7 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
     return fail(HRG_ERR_INVALID, "PickPlaceHumanCart needs box_half, box_mass, box_inertia, n_targets, n_obj_placements > 0");
   HIPCHK(hipSetDevice(device));
   hrg_batch* b = new hrg_batch();
-  b->device = device; b->n_envs = n_envs; b->env_id0 = env_id0; b->task = desc->task;
+  b->device = device; b->n_envs = n_envs; b->env_id0 = env_id0; b->task = desc->task; b->ik = desc->ik_enabled != 0;
   // ---- device model ----
   std::unique_ptr<DevModel> hm_own(new DevModel());
   DevModel* hm = hm_own.get();
@@ -3424,6 +3429,7 @@ void hrg_batch_destroy(hrg_batch* b) {
   for (auto& p : b->events) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
   for (auto& p : b->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
   hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_pose); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
+  hipFree(b->ex.act); hipFree(b->ex.sim); hipFree(b->ex.ou_y); hipFree(b->ex.ou_calls); hipFree(b->ex.acc);
   delete b;
 }
 
@@ -3488,6 +3494,82 @@ int hrg_batch_step(hrg_batch* b, double* actions_dev, float* obs_dev, float* ter
   HIPCHK(hipGetLastError());
   b->parity ^= 1;
   if (b->timing) { HIPCHK(hipEventRecord(ev.second, st)); b->events.push_back(ev); }
+  return HRG_OK;
+}
+
+// ---- scripted experts + action-based imitation reward (csrc/hrgym_expert.h) ----
+static bool expert_fits_task(int expert, int task) {
+  switch (expert) {
+    case HRG_EXPERT_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
+    case HRG_EXPERT_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || task == HRG_TASK_STACKING || HRG_IS_HANDOVER(task);   // PP-AIR, CS-AIR, HRH-AIR, RHH-AIR
+    case HRG_EXPERT_LIFTING: return task == HRG_TASK_LIFTING;
+    case HRG_EXPERT_HAMMERING: return task == HRG_TASK_HAMMERING;
+  }
+  return false;
+}
+
+int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc) {
+  if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
+  if (desc->expert < HRG_EXPERT_REACH || desc->expert > HRG_EXPERT_HAMMERING) return fail(HRG_ERR_UNSUPPORTED, "unknown expert");
+  if (!expert_fits_task(desc->expert, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this expert does not read the observation of the batch's task");
+  if ((desc->cartesian != 0) != (desc->expert != HRG_EXPERT_REACH)) return fail(HRG_ERR_UNSUPPORTED, "ReachHumanExpert acts in joint space, every other expert in Cartesian space");
+  if ((desc->cartesian != 0) != b->ik) return fail(HRG_ERR_UNSUPPORTED, "the expert's action form is not the batch's (Cartesian experts need the IK front-end, ik_enabled)");
+  const int width = desc->cartesian ? 4 : HRG_ACT_DIM;
+  for (int k = 0; k < width; k++)
+    if (!(desc->act_low[k] < desc->act_high[k])) return fail(HRG_ERR_INVALID, "expert: action bounds need low < high");
+  if (!(desc->signal_to_noise_ratio >= 0 && desc->signal_to_noise_ratio <= 1 && desc->delta_time >= 0)) return fail(HRG_ERR_INVALID, "expert: need 0 <= signal_to_noise_ratio <= 1 and delta_time >= 0");
+  if (desc->reward_enabled) {
+    if (!(desc->iota_m > 0 && desc->iota_g > 0)) return fail(HRG_ERR_INVALID, "imitation reward: iota_m and iota_g must be positive");
+    if (!(desc->alpha >= 0 && desc->alpha <= 1 && desc->beta >= 0 && desc->beta <= 1)) return fail(HRG_ERR_INVALID, "imitation reward: alpha and beta must lie in [0, 1]");
+    for (int fn : {desc->m_sim_fn, desc->g_sim_fn})
+      if (fn != HRG_SIM_GAUSSIAN && fn != HRG_SIM_TANH) return fail(HRG_ERR_INVALID, "imitation reward: unknown similarity function");
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t n = (size_t)b->n_envs;
+  ExpertBuffers& x = b->ex;
+  b->has_expert = false;   // until every buffer below exists and is zeroed
+  if (!x.act) HIPCHK(hipMalloc(&x.act, sizeof(double) * HRG_ACT_DIM * n));
+  if (!x.sim) HIPCHK(hipMalloc(&x.sim, sizeof(double) * 2 * n));
+  if (!x.ou_y) HIPCHK(hipMalloc(&x.ou_y, sizeof(double) * HRG_ACT_DIM * n));
+  if (!x.ou_calls) HIPCHK(hipMalloc(&x.ou_calls, sizeof(int64_t) * n));
+  if (!x.acc) HIPCHK(hipMalloc(&x.acc, sizeof(double) * 3 * n));
+  HIPCHK(hipMemset(x.act, 0, sizeof(double) * HRG_ACT_DIM * n));
+  HIPCHK(hipMemset(x.sim, 0, sizeof(double) * 2 * n));
+  HIPCHK(hipMemset(x.ou_y, 0, sizeof(double) * HRG_ACT_DIM * n));
+  HIPCHK(hipMemset(x.ou_calls, 0, sizeof(int64_t) * n));
+  HIPCHK(hipMemset(x.acc, 0, sizeof(double) * 3 * n));
+  HIPCHK(hipDeviceSynchronize());
+  b->expert = *desc;
+  b->has_expert = true;
+  return HRG_OK;
+}
+
+int hrg_batch_expert_actions(hrg_batch* b, const float* obs_dev, double* actions_out_dev, void* stream) {
+  if (!b || !obs_dev || !actions_out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!b->has_expert) return fail(HRG_ERR_INVALID, "no expert attached (hrg_batch_expert_attach)");
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(hrg_expert_pre_kernel, dim3((unsigned)((b->n_envs + HRG_EXPERT_BLOCK - 1) / HRG_EXPERT_BLOCK)), dim3(HRG_EXPERT_BLOCK), 0, (hipStream_t)stream, b->expert, obs_dev,
+                     (const double*)nullptr, actions_out_dev, (double*)nullptr, b->ex.ou_y, b->ex.ou_calls, b->env_id0, b->n_envs);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev, float* imit_dev,
+                             void* stream) {
+  if (!b || !actions_dev || !obs_dev || !reward_dev || !done_dev || !info_dev || !imit_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!b->has_expert) return fail(HRG_ERR_INVALID, "no expert attached (hrg_batch_expert_attach)");
+  if (!b->expert.reward_enabled) return fail(HRG_ERR_INVALID, "the expert was attached without an imitation reward (reward_enabled = 0)");
+  HIPCHK(hipSetDevice(b->device));
+  const dim3 grid((unsigned)((b->n_envs + HRG_EXPERT_BLOCK - 1) / HRG_EXPERT_BLOCK)), block(HRG_EXPERT_BLOCK);
+  hipLaunchKernelGGL(hrg_expert_pre_kernel, grid, block, 0, (hipStream_t)stream, b->expert, (const float*)obs_dev, (const double*)actions_dev, b->ex.act, b->ex.sim, b->ex.ou_y,
+                     b->ex.ou_calls, b->env_id0, b->n_envs);
+  HIPCHK(hipGetLastError());
+  const int rc = hrg_batch_step(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, stream);
+  if (rc != HRG_OK) return rc;
+  hipLaunchKernelGGL(hrg_imitation_post_kernel, grid, block, 0, (hipStream_t)stream, b->expert, (const double*)b->ex.sim, (const uint8_t*)done_dev, reward_dev, b->ex.acc, imit_dev,
+                     b->n_envs);
+  HIPCHK(hipGetLastError());
   return HRG_OK;
 }
 

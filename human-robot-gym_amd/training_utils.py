@@ -11,7 +11,10 @@ wrappers the stepper implements in its kernels are read from the same config nod
                                            given (mean / std in the config, or datasets/<name>/observations.csv)
   config.wrappers.action_based_expert_imitation_reward with alpha == 0 and rsi_prob == 0 (the *-SAC baselines of config_icra_2024): the
                                            wrapper then returns the environment reward unchanged and never resets to a dataset state; it is skipped
-  anything else that is configured (state/action based imitation rewards with a weight, reference-state initialisation, visualisation) raises.
+  config.wrappers.action_based_expert_imitation_reward with rsi_prob: null and a config.expert node (the *-AIR configs with that one key set to
+                                           null) -> the scripted expert + Cart/JointActionBasedExpertImitationRewardWrapper in two kernels around
+                                           the step kernel (HipVecEnv expert= / imitation_reward=; csrc/hrgym_expert.h)
+  anything else that is configured (state based imitation rewards, reference-state initialisation, visualisation) raises.
 
 `config` may be the reference's OmegaConf `TrainingConfig`, or any object / dict with the same attribute tree (the tests use a plain namespace).
 """
@@ -104,9 +107,26 @@ def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
     ab = _get(w, "action_based_expert_imitation_reward")
     if ab is not None:
         abk = dict(_plain(ab))
-        if float(abk.get("alpha") or 0.0) != 0.0 or float(abk.get("rsi_prob") or 0.0) != 0.0:
-            raise NotImplementedError("wrappers.action_based_expert_imitation_reward with alpha != 0 or rsi_prob != 0: imitation rewards / reference-state "
-                                      "initialisation are outside the batched stepper (alpha = 0, rsi_prob = 0 leaves the environment reward unchanged and is skipped)")
+        rsi_prob = abk.pop("rsi_prob", None)
+        abk.pop("dataset_name", None)   # _compose_action_based_expert_imitation_reward_wrapper_kwargs (training_utils.py:252-271)
+        expert = _get(config, "expert")
+        if rsi_prob is not None:
+            # action_based_expert_imitation_reward_wrap_fn (training_utils.py:297-307) wraps DatasetRSIWrapper whenever rsi_prob is not None
+            if float(abk.get("alpha") or 0.0) != 0.0 or float(rsi_prob) != 0.0:
+                raise NotImplementedError(f"wrappers.action_based_expert_imitation_reward with rsi_prob = {rsi_prob}: the reference then wraps DatasetRSIWrapper, "
+                                          "which resets episodes to the states of a recorded dataset (datasets/<dataset_name>/); no such dataset files exist "
+                                          "for the batched stepper.  Set rsi_prob to null for the imitation reward alone (alpha = 0, rsi_prob = 0 leaves the "
+                                          "environment reward unchanged and is skipped)")
+        elif expert is None:
+            if float(abk.get("alpha") or 0.0) != 0.0:   # alpha = 0 without an expert: the environment reward unchanged; skipped as before
+                raise NotImplementedError("wrappers.action_based_expert_imitation_reward without a config.expert node (the reference asserts: No expert specified in config!)")
+        else:
+            from .expert import expert_kwargs
+            ek = dict(_plain(expert))   # _compose_expert_kwargs / create_expert (training_utils.py:138-174): id selects the class, obs_keys is dropped
+            ek.pop("obs_keys", None)
+            expert_kwargs(ek)           # unknown ids (ReachHumanCart: no such environment here) and arguments raise now, not at the first step
+            out["expert"] = ek
+            out["imitation_reward"] = abk
     dn = _get(w, "dataset_obs_norm")
     if dn is not None:
         out["obs_norm"] = _obs_norm_from_config(dn)

@@ -125,7 +125,10 @@ for _k in ("hammer_quat", "hammer_gripped", "vec_eef_to_hammer", "vec_eef_to_nai
 OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (hammering overrides it with its constant zeros)
 
 
-_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated"))   # what SB3's rollout loops look up on every info
+# ActionBasedExpertImitationRewardWrapper._add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130): on the infos of done steps
+IMITATION_INFO_KEYS = ("ep_im_rew_mean", "ep_env_rew_mean", "ep_full_rew_mean", "im_rew_mean", "env_rew_mean", "full_rew_mean")
+# what SB3's rollout loops (and the reference's logging callback, for the imitation keys) look up on every info: stored eagerly where they exist
+_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated") + IMITATION_INFO_KEYS)
 
 
 class LazyInfo(dict):
@@ -217,9 +220,21 @@ class _TorchBackend:
         self.reward = hb[o[2]:o[2] + s[2]].view(np.float32)
         self.info = hb[o[3]:o[3] + s[3]].view(np.int32).reshape(n_envs, idim)
         self.done = hb[o[4]:o[4] + s[4]]
+        self.imit = None   # host copy of the imitation rows, once an expert with a reward is attached
 
     def _fetch(self):
+        if self.imit is not None:   # queued ahead of the packed block on the same stream: the one blocking copy below completes both
+            self._imit_host.copy_(self.batch.imit, non_blocking=True)
         self._host.copy_(self.batch.packed, non_blocking=False)
+
+    def attach_expert(self, desc):
+        self.batch.attach_expert(desc)
+        if desc.reward_enabled:
+            self._imit_host = self.torch.zeros(self.n, CONST["HRG_IMIT_DIM"], dtype=self.torch.float32, pin_memory=True)
+            self.imit = self._imit_host.numpy()
+
+    def expert_actions(self):
+        return self.batch.expert_actions().cpu().numpy()
 
     def reset(self):
         self.batch.reset()
@@ -228,7 +243,10 @@ class _TorchBackend:
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
-        self.batch.step(self._act)
+        if self.imit is not None:
+            self.batch.step_imitation(self._act)
+        else:
+            self.batch.step(self._act)
 
     def step_wait(self):
         self._fetch()
@@ -252,12 +270,29 @@ class HipVecEnv(_VecEnvBase):
     _monitor = None   # open Monitor csv, when monitor_dir is given
     _monitor_keys = ()
     _info_keys = INFO_KEYS   # names of the info columns (a task may rename its task-specific column: INFO_KEY_ALIASES)
+    _expert_desc = None   # hrg_expert_desc of the attached scripted expert
+    _imit_alpha = None    # alpha of the imitation reward, when one is configured
 
     def __init__(self, n_envs=1, env_id="ReachHuman", env_kwargs=None, obs_keys=None, seed=None, clips=None,
                  device=0, env_id0=0, backend=None, info_dicts=True, collision_prevention=None, goal_check=True, ik_position_delta=None,
-                 expert_obs_keys=None, goal_env=False, obs_norm=None, monitor_dir=None, monitor_kwargs=None, reach_box=False, robot_geometry="capsule"):
+                 expert_obs_keys=None, goal_env=False, obs_norm=None, monitor_dir=None, monitor_kwargs=None, reach_box=False, robot_geometry="capsule",
+                 expert=None, imitation_reward=None):
         if env_id not in ENV_DEFAULTS:
             raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)} (DESIGN.md §6)")
+        # expert: dict(id=..., signal_to_noise_ratio=..., ...) = config.expert (a scripted expert of demonstrations/experts/, evaluated on the device:
+        # env.expert_actions()); imitation_reward: dict(alpha, beta, iota_m, iota_g, m_sim_fn, g_sim_fn, normalize_joint_actions) =
+        # config.wrappers.action_based_expert_imitation_reward: the step reward becomes r_im alpha + r_env (1 - alpha) (csrc/hrgym_expert.h)
+        if imitation_reward is not None and expert is None:
+            raise ValueError("imitation_reward needs an expert (the reference asserts: No expert specified in config!)")
+        if expert is not None:
+            from .expert import EXPERT_ENVS, expert_kwargs
+            if backend is not None:
+                raise NotImplementedError("expert / imitation_reward: the experts run in the HIP library; another backend has none")
+            if goal_env:
+                raise NotImplementedError("expert / imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
+            eid, _ = expert_kwargs(expert)
+            if env_id not in EXPERT_ENVS[eid] or reach_box:
+                raise NotImplementedError(f"expert {eid}: it reads the observation of {EXPERT_ENVS[eid]}, not of {env_id}")
         self.env_id = env_id
         self._info_keys = [INFO_KEY_ALIASES.get(env_id, {}).get(k, k) for k in INFO_KEYS]
         # GoalEnvironmentGymWrapper (wrappers/goal_env_wrapper.py): dict observations {observation, achieved_goal, desired_goal} and an
@@ -316,6 +351,15 @@ class HipVecEnv(_VecEnvBase):
             lim = float(self._desc.ik_action_limit)
             act_space = _Box(np.array([-lim] * 3 + [-1.0], np.float32), np.array([lim] * 3 + [1.0], np.float32), dtype=np.float32)
         super().__init__(n_envs, obs_space, act_space)
+        self._imit_alpha = None
+        if expert is not None:
+            from .expert import build_expert_desc
+            # the bounds in FP64 as configured (the f32 action space rounds action_limit = 0.1 to 0.100000001)
+            hi = [1.0] * CONST["HRG_ACT_DIM"] if ik_position_delta is None else [float(self._desc.ik_action_limit)] * 3 + [1.0]
+            self._expert_desc = build_expert_desc(expert, [-x for x in hi], hi, imitation_reward, default_seed=int(self._desc.seed))
+            self._backend.attach_expert(self._expert_desc)
+            if imitation_reward is not None:
+                self._imit_alpha = float(self._expert_desc.alpha)
         self.info_dicts = info_dicts
         self._ep_ret = np.zeros(n_envs, np.float64)
         self._ep_len = np.zeros(n_envs, np.int64)
@@ -378,12 +422,19 @@ class HipVecEnv(_VecEnvBase):
         self._last_full = full
         obs, reward = self._view(full), np.array(reward, copy=True)
         dones = np.asarray(done).astype(bool)
-        self._ep_ret += reward
+        imit = None
+        if self._imit_alpha is not None:   # the reward is the combined one; Monitor sits inside the imitation wrapper (SB3 make_vec_env), so its return is r_env
+            imit = np.array(self._backend.imit, copy=True)
+            self._ep_ret += imit[:, 1]
+        else:
+            self._ep_ret += reward
         self._ep_len += 1
         if (self._cp is not None or self._ik is not None) and self.info_dicts:
             self._actions = np.array(self._backend.executed_actions(), copy=True)
         if self.info_dicts:
             infos = self._make_infos(info, dones, term_obs)
+            if imit is not None:
+                self._imitation_infos(infos, imit, np.nonzero(dones)[0])
         else:
             infos = [{} for _ in range(self.num_envs)]
             if self._monitor is not None:   # the Monitor csv does not depend on the per-env dicts: episode rows from the done mask and the info block
@@ -419,6 +470,30 @@ class HipVecEnv(_VecEnvBase):
                 self._monitor_rows(info, idx, now)
         return infos
 
+    def _imitation_infos(self, infos, imit, idx):
+        """_add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130) from the imitation rows of the envs that finished an episode."""
+        a = self._imit_alpha
+        set_ = dict.__setitem__
+        for i in idx.tolist():
+            ep_im, ep_env, n = float(imit[i, 4]), float(imit[i, 5]), float(imit[i, 6])
+            d = infos[i]
+            set_(d, "ep_im_rew_mean", ep_im)
+            set_(d, "ep_env_rew_mean", ep_env)
+            set_(d, "ep_full_rew_mean", ep_im * a + ep_env * (1 - a))
+            set_(d, "im_rew_mean", ep_im / n)
+            set_(d, "env_rew_mean", ep_env / n)
+            set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+
+    def expert_actions(self):
+        """The attached expert's action for every env's current observation (the one the last reset / step returned): float64 [n, 4] for the
+        Cartesian experts, [n, 7] for ReachHuman's.  Every call advances the expert's noise process once, like a call of the reference's expert."""
+        if self._expert_desc is None:
+            raise NotImplementedError("expert_actions: construct the env with expert=dict(id=..., ...)")
+        if self._last_full is None:
+            raise RuntimeError("expert_actions: call reset() first")
+        a = np.asarray(self._backend.expert_actions(), np.float64)
+        return np.array(a[:, :4] if self._expert_desc.cartesian else a, copy=True)
+
     def _monitor_rows(self, info, idx, now=None):
         """One r,l,t(+info_keywords) row per finished episode (SB3 Monitor [UPSTREAM]); info_keywords are columns of the kernel's info block."""
         if not len(idx):
@@ -451,6 +526,8 @@ class HipVecEnv(_VecEnvBase):
         if isinstance(self._backend, _TorchBackend):
             self._backend.close()
             self._backend = _TorchBackend(self._desc, self._clips, self.num_envs, self._env_id0, self._device)
+            if self._expert_desc is not None:
+                self._backend.attach_expert(self._expert_desc)
         else:
             self._backend.reseed(self._desc)
         return [int(seed) + i for i in range(self.num_envs)]

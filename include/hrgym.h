@@ -377,6 +377,41 @@ typedef struct hrg_clip_table {
   int32_t clip_stack_keyframes[HRG_MAX_CLIPS][5];
 } hrg_clip_table;
 
+/* ------------------------------------------------------------------------- scripted experts + action imitation reward (POD) */
+/* the scripted experts of demonstrations/experts/ (REGISTERED_EXPERTS, __init__.py:8-14; ReachHumanCart has no environment here) */
+enum { HRG_EXPERT_REACH = 0           /* ReachHumanExpert (reach_human_expert.py): joint action, reads goal_difference */,
+       HRG_EXPERT_PICK_PLACE = 1      /* PickPlaceHumanCartExpert (pick_place_human_cart_expert.py): PickPlaceHumanCart, CollaborativeStackingCart, both handover tasks */,
+       HRG_EXPERT_LIFTING = 2         /* CollaborativeLiftingCartExpert (collaborative_lifting_cart_expert.py) */,
+       HRG_EXPERT_HAMMERING = 3       /* CollaborativeHammeringCartExpert (collaborative_hammering_cart_expert.py) */ };
+/* similarity functions of utils/expert_imitation_reward_utils.py */
+enum { HRG_SIM_GAUSSIAN = 0 /* 2^-(delta / iota)^2 */, HRG_SIM_TANH = 1 /* 1 - tanh(tan(0.5) delta / iota) */ };
+#define HRG_IMIT_DIM 8    /* floats per env of the imitation row (hrg_batch_step_imitation) */
+/* columns of the imitation row; on a done step the episode columns are the finished episode's (the accumulators restart after it) */
+enum { HRG_IMIT_R_IM = 0, HRG_IMIT_R_ENV = 1, HRG_IMIT_R_MOTION = 2, HRG_IMIT_R_GRIPPER = 3, HRG_IMIT_EP_IM = 4 /* sum of r_im over the episode so far */,
+       HRG_IMIT_EP_ENV = 5 /* sum of r_env */, HRG_IMIT_EP_LEN = 6 /* steps */, HRG_IMIT_R_FULL = 7 /* the combined reward (= reward_dev) */ };
+
+/* One scripted expert (its constructor arguments) and, optionally, the ActionBasedExpertImitationRewardWrapper on top of it
+ * (wrappers/action_based_expert_imitation_reward_wrapper.py: the Cart form when `cartesian`, the Joint form otherwise). */
+typedef struct hrg_expert_desc {
+  int32_t expert;                 /* HRG_EXPERT_* */
+  int32_t cartesian;              /* 1: actions are [dx, dy, dz, gripper] (the batch has the IK front-end); 0: the 7-wide joint action */
+  double act_low[HRG_ACT_DIM], act_high[HRG_ACT_DIM]; /* action_space.low / high (the first four entries when cartesian) */
+  double signal_to_noise_ratio;   /* 1: the expert alone; 0: Ornstein-Uhlenbeck noise alone */
+  double delta_time;              /* time step of the noise process per expert call */
+  uint64_t seed;                  /* keys the noise draws (with the global env id and the env's call counter) */
+  /* PickPlaceHumanCartExpert (88-102) */
+  double hover_dist, tan_theta, horizontal_epsilon, vertical_epsilon, goal_dist, gripper_fully_opened_threshold;
+  int32_t release_when_delivered;
+  /* ActionBasedExpertImitationRewardWrapper */
+  int32_t reward_enabled;         /* 0: expert actions only (hrg_batch_expert_actions) */
+  /* CollaborativeLiftingCartExpert (69-78) */
+  double board_size[3], human_grip_offset;
+  double alpha, beta, iota_m, iota_g;
+  int32_t m_sim_fn, g_sim_fn;     /* HRG_SIM_* */
+  int32_t normalize_joint_actions; /* Joint form: rescale both actions to [-1, 1] by the action bounds before the distance */
+  int32_t reserved;
+} hrg_expert_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
@@ -464,6 +499,23 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
  * controller would set for each env (current joint angles + scaled action, clipped to the joint limits) is tested with the pre-check capsule
  * model; nothing is stepped.  actions: device, [n_envs][HRG_ACT_DIM] f64 (not modified); collides: device, [n_envs] u8 (1 = collision). */
 int hrg_batch_check_actions(hrg_batch* b, const double* actions_dev, uint8_t* collides_dev, void* hip_stream);
+
+/* Scripted experts and the action-based expert imitation reward, next to the step kernel (csrc/hrgym_expert.h).
+ *   hrg_batch_expert_attach   <- create_expert (utils/training_utils.py:153-174) + ActionBasedExpertImitationRewardWrapper.__init__; allocates and zeroes the
+ *                                per-env buffers (noise state and call counter, expert action, similarities, episode sums).  Synchronous; never on the step path.
+ *                                HRG_ERR_UNSUPPORTED when the expert does not fit the batch's task or action form.  Attaching again replaces the expert and
+ *                                restarts its noise.
+ *   hrg_batch_expert_actions  <- Expert.__call__ for every env (demonstrations/create_expert_dataset.py's role): obs_dev float[n_envs][HRG_OBS_DIM] (the rows a
+ *                                reset / step wrote) -> actions_out_dev double[n_envs][HRG_ACT_DIM] (the first four entries when cartesian, the rest zero);
+ *                                advances every env's noise process once.
+ *   hrg_batch_step_imitation  <- ActionBasedExpertImitationRewardWrapper.step (70-105): the expert acts on obs_dev as the previous step / reset left it
+ *                                (info["previous_expert_observation"]) and is compared with the agent's action rows BEFORE the step rewrites them; then the
+ *                                unchanged step launch; then reward_dev <- r_im alpha + r_env (1 - alpha) and imit_dev float[n_envs][HRG_IMIT_DIM].
+ * A batch without an attached expert answers HRG_ERR_INVALID (hrg_batch_step_imitation also when the expert was attached with reward_enabled = 0). */
+int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc);
+int hrg_batch_expert_actions(hrg_batch* b, const float* obs_dev, double* actions_out_dev, void* stream);
+int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev,
+                             float* imit_dev, void* stream);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
