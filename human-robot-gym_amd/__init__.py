@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("MixedBatch", "MixedHipVecEnv", "make_mixed_batch", "make_mixed_vec_env", "ICRA_TASKS"):
         from . import mixed
         return getattr(mixed, name)
+    if name in ("ExpertDataset", "collect_expert_dataset"):
+        from . import dataset
+        return getattr(dataset, name)
     if name == "HipBatch":
         from ._lib import HipBatch
         return HipBatch

@@ -19,6 +19,9 @@ _CTYPES = {
     "uint64_t": ctypes.c_uint64,
     "uint8_t": ctypes.c_uint8,
     "const double*": ctypes.POINTER(ctypes.c_double),
+    "const float*": ctypes.c_void_p,     # host arrays of hrg_dataset_desc: handed over as addresses (numpy .ctypes.data)
+    "const int64_t*": ctypes.c_void_p,
+    "const void*": ctypes.c_void_p,
 }
 
 
@@ -54,7 +57,7 @@ def _parse(paths):
                 decl = " ".join(decl.split())
                 if not decl:
                     continue
-                mm = re.match(r"(const double\*|\w+)\s+(.*)", decl)
+                mm = re.match(r"(const \w+\*|\w+)\s+(.*)", decl)
                 tname, rest = mm.group(1), mm.group(2)
                 base = structs[tname] if tname in structs else _CTYPES[tname]
                 for var in rest.split(","):
@@ -79,6 +82,7 @@ BoxState = _STRUCTS["hrg_box_state"]
 StackState = _STRUCTS["hrg_stack_state"]
 HammerState = _STRUCTS["hrg_hammer_state"]
 ExpertDesc = _STRUCTS["hrg_expert_desc"]
+DatasetDesc = _STRUCTS["hrg_dataset_desc"]
 
 
 def struct_to_dict(s):

@@ -7,7 +7,7 @@ import ctypes
 import os
 import subprocess
 
-from ._cstruct import CONST, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc
+from ._cstruct import CONST, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc, DatasetDesc  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhrgym_hip.so")   # the one shipping library; no environment variable redirects it
@@ -34,12 +34,13 @@ EXPORTS = [
     "hrg_hammer_bytes", "hrg_batch_get_hammer", "hrg_batch_set_hammer", "hrg_test_hull_queries",
     "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks", "hrg_batch_pose_table_bytes", "hrg_debug_pose_compare",
     "hrg_batch_expert_attach", "hrg_batch_expert_actions", "hrg_batch_step_imitation",
+    "hrg_batch_snapshot", "hrg_batch_dataset_attach", "hrg_batch_dataset_reset", "hrg_batch_step_dataset", "hrg_batch_dataset_cursor",
 ]
 
 
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h")] + [
+    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h", "hrgym_dataset.h")] + [
         os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
@@ -122,6 +123,11 @@ def load_library():
     lib.hrg_batch_expert_attach.argtypes = [vp, ctypes.POINTER(ExpertDesc)]
     lib.hrg_batch_expert_actions.argtypes = [vp, vp, vp, vp]
     lib.hrg_batch_step_imitation.argtypes = [vp] * 9
+    lib.hrg_batch_snapshot.argtypes = [vp] * 4
+    lib.hrg_batch_dataset_attach.argtypes = [vp, ctypes.POINTER(DatasetDesc)]
+    lib.hrg_batch_dataset_reset.argtypes = [vp] * 4
+    lib.hrg_batch_step_dataset.argtypes = [vp] * 10
+    lib.hrg_batch_dataset_cursor.argtypes = [vp, vp]
     lib.hrg_batch_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
     if lib.hrg_state_bytes() != ctypes.sizeof(EnvState):
         raise RuntimeError("hrg_env_state layout mismatch between header mirror and library: rebuild")
@@ -274,6 +280,69 @@ class HipBatch:
                                                              self._stream()))
         self._keep = actions
         return self.obs, self.reward, self.done, self.info, self.imit
+
+    def snapshot(self, states_out, boxes_out=None):
+        """One asynchronous device-to-device copy of every env's state block into `states_out` (uint8 [n, hrg_state_bytes()] on the batch's device) and,
+        for a task with a box block, of the box blocks into `boxes_out` (uint8 [n, hrg_box_bytes()])."""
+        t = self.torch
+        for x, nb in ((states_out, ctypes.sizeof(EnvState)), (boxes_out, ctypes.sizeof(BoxState))):
+            if x is not None and (x.dtype != t.uint8 or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != (self.n, nb)):
+                raise ValueError(f"snapshot: expected a contiguous uint8 tensor [{self.n}, {nb}] on {self.device}")
+        vp = ctypes.c_void_p
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_snapshot(self.h, vp(states_out.data_ptr()), vp(boxes_out.data_ptr()) if boxes_out is not None else None, self._stream()))
+
+    def attach_dataset(self, dataset, rsi_prob=0.0, state_imitation_reward=None, seed=0):
+        """Upload a demonstration dataset (dataset.ExpertDataset) for reference state initialisation and, with `state_imitation_reward`
+        (dict: dataset.sir_kwargs), the state-based imitation reward.  Synchronous; not on the step path.  HrgError when the task cannot be restored from
+        a dataset (stacking, hammering) or the reward does not read its observation."""
+        from .dataset import build_dataset_desc
+        t = self.torch
+        desc, keep = build_dataset_desc(dataset, rsi_prob=rsi_prob, state_imitation_reward=state_imitation_reward, seed=seed)
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_dataset_attach(self.h, ctypes.byref(desc)))
+        del keep   # host arrays: read by the attach only
+        self.dataset_desc = desc
+        self.sir = t.zeros(self.n, CONST["HRG_SIR_DIM"], dtype=t.float32, device=self.device)
+
+    def dataset_reset(self, mask=None):
+        """`reset`, then every reset env starts from a dataset state (DatasetRSIWrapper.reset).  Returns the obs tensor (dataset observation rows)."""
+        if getattr(self, "dataset_desc", None) is None:
+            raise HrgError("no dataset attached: call attach_dataset() first")
+        mp = None
+        if mask is not None:
+            mask = mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
+            mp = ctypes.c_void_p(mask.data_ptr())
+        with self.torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_dataset_reset(self.h, mp, ctypes.c_void_p(self.obs.data_ptr()), self._stream()))
+        self._keep_mask = mask
+        return self.obs
+
+    def step_dataset(self, actions):
+        """`step` (or `step_imitation`, with an expert reward attached) followed by the dataset kernels: returns (obs, reward, done, info, sir); `sir` is the
+        float32 [n, HRG_SIR_DIM] row per env (dataset.SIR_COLUMNS); finished envs (done, or early termination) restart from a dataset state."""
+        t = self.torch
+        if getattr(self, "dataset_desc", None) is None:
+            raise HrgError("no dataset attached: call attach_dataset() first")
+        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
+            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
+        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
+            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
+        vp = ctypes.c_void_p
+        imit = getattr(self, "imit", None)
+        with t.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_step_dataset(self.h, vp(actions.data_ptr()), vp(self.obs.data_ptr()), vp(self.term_obs.data_ptr()),
+                                                           vp(self.reward.data_ptr()), vp(self.done.data_ptr()), vp(self.info.data_ptr()),
+                                                           vp(imit.data_ptr()) if imit is not None else None, vp(self.sir.data_ptr()), self._stream()))
+        self._keep = actions
+        return self.obs, self.reward, self.done, self.info, self.sir
+
+    def dataset_cursor(self):
+        """(episode, step, T) of every env: int32 [n, 3] (synchronous parity hook)."""
+        import numpy as np
+        cur = np.zeros((self.n, 3), np.int32)
+        _check(self.lib, self.lib.hrg_batch_dataset_cursor(self.h, cur.ctypes.data_as(ctypes.c_void_p)))
+        return cur
 
     def get_state(self, e):
         s = EnvState()

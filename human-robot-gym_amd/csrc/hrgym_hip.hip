@@ -3079,6 +3079,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 
 #if HRG_BASE_TU
 #include "hrgym_expert.h"   // the scripted experts + imitation reward kernels (hrg_batch_expert_*, hrg_batch_step_imitation)
+#include "hrgym_dataset.h"  // demonstration datasets: restore + state imitation reward kernels (hrg_batch_dataset_*, hrg_batch_step_dataset)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -3115,11 +3116,20 @@ struct hrg_batch {
   bool has_expert = false;             // hrg_batch_expert_attach
   hrg_expert_desc expert;              // the attached expert (a kernel argument of the two expert kernels)
   ExpertBuffers ex;
+  bool has_dataset = false;            // hrg_batch_dataset_attach
+  hrg_dataset_desc dataset;            // the attached dataset's parameters (a kernel argument of the two dataset kernels; its host pointers are nulled)
+  DatasetDev ds;
   bool timing = false;
   bool taps = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
 };
+
+static void dataset_free(hrg_batch* b) {
+  DatasetDev& d = b->ds;
+  hipFree((void*)d.ep_offset); hipFree((void*)d.states); hipFree((void*)d.boxes); hipFree((void*)d.obs); hipFree(d.cursor); hipFree(d.resets); hipFree(d.acc); hipFree(d.finished);
+  d = DatasetDev{};
+}
 
 // the progress table of the level-waves priority (StepOrder.fair): one per device, shared by the batches and kernel variants that run on it; never freed
 static int32_t* fair_table(int device) {
@@ -3430,6 +3440,7 @@ void hrg_batch_destroy(hrg_batch* b) {
   for (auto& p : b->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
   hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_pose); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
   hipFree(b->ex.act); hipFree(b->ex.sim); hipFree(b->ex.ou_y); hipFree(b->ex.ou_calls); hipFree(b->ex.acc);
+  dataset_free(b);
   delete b;
 }
 
@@ -3570,6 +3581,124 @@ int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, 
   hipLaunchKernelGGL(hrg_imitation_post_kernel, grid, block, 0, (hipStream_t)stream, b->expert, (const double*)b->ex.sim, (const uint8_t*)done_dev, reward_dev, b->ex.acc, imit_dev,
                      b->n_envs);
   HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+// ---- demonstration datasets: reference state initialisation + state-based imitation reward (csrc/hrgym_dataset.h) ----
+static bool dataset_task_ok(int task) { return task != HRG_TASK_STACKING && task != HRG_TASK_HAMMERING; }   // their state lives in further arrays (d_stacks, d_hammers)
+static bool sir_fits_task(int kind, int task) {
+  switch (kind) {
+    case HRG_SIR_NONE: return true;
+    case HRG_SIR_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
+    case HRG_SIR_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || HRG_IS_HANDOVER(task);   // "any environment that can be solved using the PickPlaceHumanCartExpert"
+    case HRG_SIR_LIFTING: return task == HRG_TASK_LIFTING;
+  }
+  return false;
+}
+
+int hrg_batch_snapshot(hrg_batch* b, void* states_out_dev, void* boxes_out_dev, void* stream) {
+  if (!b || !states_out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "snapshot: the stacking and hammering tasks keep their state in further arrays");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipMemcpyAsync(states_out_dev, b->d_states, sizeof(hrg_env_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (boxes_out_dev && b->task != HRG_TASK_REACH)
+    HIPCHK(hipMemcpyAsync(boxes_out_dev, b->d_boxes, sizeof(hrg_box_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return HRG_OK;
+}
+
+int hrg_batch_dataset_attach(hrg_batch* b, const hrg_dataset_desc* desc) {
+  if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
+  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "dataset: the stacking and hammering tasks keep their state in further arrays, which a dataset does not hold");
+  if (desc->sir_kind < HRG_SIR_NONE || desc->sir_kind > HRG_SIR_LIFTING) return fail(HRG_ERR_UNSUPPORTED, "unknown sir_kind");
+  if (!sir_fits_task(desc->sir_kind, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this state imitation reward does not read the observation of the batch's task");
+  if (!desc->ep_offset || !desc->states || !desc->obs || desc->n_episodes <= 0) return fail(HRG_ERR_INVALID, "dataset: null array or no episode");
+  if ((desc->boxes != nullptr) != (b->task != HRG_TASK_REACH)) return fail(HRG_ERR_INVALID, "dataset: a box array is needed exactly when the batch's task has a box block");
+  if (desc->ep_offset[0] != 0 || desc->ep_offset[desc->n_episodes] != desc->total_T) return fail(HRG_ERR_INVALID, "dataset: ep_offset must run from 0 to total_T");
+  for (int64_t k = 0; k < desc->n_episodes; k++) {
+    const int64_t T = desc->ep_offset[k + 1] - desc->ep_offset[k];
+    if (T <= 0) return fail(HRG_ERR_INVALID, "dataset: an episode without a transition (T = 0)");
+    if (T > INT32_MAX) return fail(HRG_ERR_INVALID, "dataset: episode too long");
+  }
+  if (desc->n_episodes > INT32_MAX) return fail(HRG_ERR_INVALID, "dataset: too many episodes");
+  if (!(desc->rsi_prob >= 0 && desc->rsi_prob <= 1)) return fail(HRG_ERR_INVALID, "dataset: rsi_prob must lie in [0, 1]");
+  if (desc->sir_kind != HRG_SIR_NONE) {
+    if (!(desc->iota_m > 0 && desc->iota_g > 0)) return fail(HRG_ERR_INVALID, "state imitation reward: iota_m and iota_g must be positive");
+    if (!(desc->alpha >= 0 && desc->alpha <= 1 && desc->beta >= 0 && desc->beta <= 1)) return fail(HRG_ERR_INVALID, "state imitation reward: alpha and beta must lie in [0, 1]");
+    if (!(desc->et_dist >= 0)) return fail(HRG_ERR_INVALID, "state imitation reward: et_dist must not be negative");
+    for (int fn : {desc->m_sim_fn, desc->g_sim_fn})
+      if (fn != HRG_SIM_GAUSSIAN && fn != HRG_SIM_TANH) return fail(HRG_ERR_INVALID, "state imitation reward: unknown similarity function");
+  }
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  b->has_dataset = false;   // until every buffer below exists
+  dataset_free(b);
+  DatasetDev& d = b->ds;
+  const size_t n = (size_t)b->n_envs, nep = (size_t)desc->n_episodes, tt = (size_t)desc->total_T;
+  HIPCHK(hipMalloc((void**)&d.ep_offset, sizeof(int64_t) * (nep + 1)));
+  HIPCHK(hipMalloc((void**)&d.states, sizeof(hrg_env_state) * tt));
+  if (desc->boxes) HIPCHK(hipMalloc((void**)&d.boxes, sizeof(hrg_box_state) * tt));
+  HIPCHK(hipMalloc((void**)&d.obs, sizeof(float) * HRG_OBS_DIM * (tt + nep)));
+  HIPCHK(hipMalloc(&d.cursor, sizeof(int32_t) * 3 * n));
+  HIPCHK(hipMalloc(&d.resets, sizeof(int32_t) * n));
+  HIPCHK(hipMalloc(&d.acc, sizeof(double) * 6 * n));
+  HIPCHK(hipMalloc(&d.finished, n));
+  HIPCHK(hipMemcpy((void*)d.ep_offset, desc->ep_offset, sizeof(int64_t) * (nep + 1), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((void*)d.states, desc->states, sizeof(hrg_env_state) * tt, hipMemcpyHostToDevice));
+  if (desc->boxes) HIPCHK(hipMemcpy((void*)d.boxes, desc->boxes, sizeof(hrg_box_state) * tt, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy((void*)d.obs, desc->obs, sizeof(float) * HRG_OBS_DIM * (tt + nep), hipMemcpyHostToDevice));
+  {   // until the first restore every env follows episode 0 from its first state
+    std::vector<int32_t> cur(3 * n);
+    for (size_t e = 0; e < n; e++) { cur[3 * e] = 0; cur[3 * e + 1] = 0; cur[3 * e + 2] = (int32_t)(desc->ep_offset[1] - desc->ep_offset[0]); }
+    HIPCHK(hipMemcpy(d.cursor, cur.data(), sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemset(d.resets, 0, sizeof(int32_t) * n));
+  HIPCHK(hipMemset(d.acc, 0, sizeof(double) * 6 * n));
+  HIPCHK(hipMemset(d.finished, 0, n));
+  HIPCHK(hipDeviceSynchronize());
+  d.n_ep = desc->n_episodes;
+  d.total_T = desc->total_T;
+  b->dataset = *desc;
+  b->dataset.ep_offset = nullptr; b->dataset.states = nullptr; b->dataset.boxes = nullptr; b->dataset.obs = nullptr;
+  b->has_dataset = true;
+  return HRG_OK;
+}
+
+int hrg_batch_dataset_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {
+  if (!b || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
+  const int rc = hrg_batch_reset(b, mask_dev, obs_dev, stream);
+  if (rc != HRG_OK) return rc;
+  hipLaunchKernelGGL(hrg_dataset_restore_kernel, dim3((unsigned)b->n_envs), dim3(64), 0, (hipStream_t)stream, b->dataset, b->ds, mask_dev, b->d_states, b->d_boxes, obs_dev,
+                     (float*)nullptr, (float*)nullptr, b->env_id0, b->n_envs);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_batch_step_dataset(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev, float* imit_dev,
+                           float* sir_dev, void* stream) {
+  if (!b || !actions_dev || !obs_dev || !reward_dev || !done_dev || !info_dev || !sir_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!term_obs_dev) return fail(HRG_ERR_INVALID, "hrg_batch_step_dataset needs term_obs_dev: the state a finished env reached is its terminal observation");
+  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
+  const bool air = b->has_expert && b->expert.reward_enabled;
+  if (air && !imit_dev) return fail(HRG_ERR_INVALID, "an expert with an imitation reward is attached: imit_dev must not be null");
+  const int rc = air ? hrg_batch_step_imitation(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, imit_dev, stream)
+                     : hrg_batch_step(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, stream);
+  if (rc != HRG_OK) return rc;
+  hipLaunchKernelGGL(hrg_sir_post_kernel, dim3((unsigned)((b->n_envs + HRG_DATASET_BLOCK - 1) / HRG_DATASET_BLOCK)), dim3(HRG_DATASET_BLOCK), 0, (hipStream_t)stream, b->dataset, b->ds,
+                     (const float*)obs_dev, (const float*)term_obs_dev, reward_dev, done_dev, sir_dev, b->n_envs);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(hrg_dataset_restore_kernel, dim3((unsigned)b->n_envs), dim3(64), 0, (hipStream_t)stream, b->dataset, b->ds, (const uint8_t*)b->ds.finished, b->d_states, b->d_boxes,
+                     obs_dev, term_obs_dev, sir_dev, b->env_id0, b->n_envs);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host) {
+  if (!b || !cursor_host) return fail(HRG_ERR_INVALID, "null argument");
+  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(cursor_host, b->ds.cursor, sizeof(int32_t) * 3 * (size_t)b->n_envs, hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 

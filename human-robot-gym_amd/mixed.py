@@ -211,13 +211,16 @@ class _MixedBackend:
 
 
 def make_mixed_vec_env(n_envs, tasks=ICRA_TASKS, obs_keys=None, env_kwargs=None, seed=None, start_index=0, clips=None, n_clips=13,
-                       device=0, info_dicts=True, concurrent=True, robot_geometry="capsule", expert=None, imitation_reward=None):
+                       device=0, info_dicts=True, concurrent=True, robot_geometry="capsule", expert=None, imitation_reward=None, dataset=None, rsi_prob=None,
+                       state_imitation_reward=None):
     """A `HipVecEnv`-shaped VecEnv over a mixed batch.  One policy sees every task, so the observation is the same columns for all
     of them: `obs_keys` (names valid for every task) or, by default, the whole 64-column observation superset (columns a task does
     not fill are zero).  `infos[i]["task"]` names the task of row i; `env.task_slices` maps env ids to row ranges.
     `robot_geometry` as in `make_mixed_batch`."""
     if expert is not None or imitation_reward is not None:
         raise NotImplementedError("expert / imitation_reward: scripted experts are per task and action form; use one HipVecEnv(expert=...) per task")
+    if dataset is not None or rsi_prob is not None or state_imitation_reward is not None:
+        raise NotImplementedError("dataset / rsi_prob / state_imitation_reward: a demonstration dataset is per task; use one HipVecEnv(dataset=...) per task")
     batch = make_mixed_batch(n_envs, tasks, env_kwargs=env_kwargs, clips=clips, n_clips=n_clips, seed=seed, env_id0=start_index,
                              device=device, concurrent=concurrent, robot_geometry=robot_geometry)
     return __getattr__("MixedHipVecEnv")(batch, obs_keys=obs_keys, info_dicts=info_dicts)

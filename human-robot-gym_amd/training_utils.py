@@ -14,7 +14,11 @@ wrappers the stepper implements in its kernels are read from the same config nod
   config.wrappers.action_based_expert_imitation_reward with rsi_prob: null and a config.expert node (the *-AIR configs with that one key set to
                                            null) -> the scripted expert + Cart/JointActionBasedExpertImitationRewardWrapper in two kernels around
                                            the step kernel (HipVecEnv expert= / imitation_reward=; csrc/hrgym_expert.h)
-  anything else that is configured (state based imitation rewards, reference-state initialisation, visualisation) raises.
+  config.wrappers.state_based_expert_imitation_reward, and action_based_expert_imitation_reward with a non-null rsi_prob, when
+                                           datasets/<dataset_name>/hrg_dataset.npz exists (tools/create_expert_dataset.py records one) -> the dataset on
+                                           the device: every episode starts from one of its states, and the state based reward compares the state reached
+                                           with the demonstration's (HipVecEnv dataset= / rsi_prob= / state_imitation_reward=; csrc/hrgym_dataset.h)
+  anything else that is configured (an imitation wrapper whose dataset file does not exist, visualisation) raises.
 
 `config` may be the reference's OmegaConf `TrainingConfig`, or any object / dict with the same attribute tree (the tests use a plain namespace).
 """
@@ -90,6 +94,14 @@ def _obs_norm_from_config(node) -> Optional[Dict[str, Any]]:
                 allow_different_observation_shapes=bool(kw.get("allow_different_observation_shapes", False)))
 
 
+def _dataset_file(name) -> str:
+    return os.path.join("datasets", str(name), "hrg_dataset.npz")   # dataset.dataset_path: relative to the working directory, like observations.csv above
+
+
+def _dataset_file_exists(name) -> bool:
+    return name is not None and os.path.exists(_dataset_file(name))
+
+
 def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
     """`get_environment_wrap_fn(config)` (utils/training_utils.py:350-410), translated into HipVecEnv keyword arguments."""
     w = _get(config, "wrappers")
@@ -102,20 +114,31 @@ def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
         ikw = dict(_plain(ik))
         ikw.pop("urdf_file", None)   # the kernel's chain is the stepper's own model of robot_pybullet.urdf
         out["ik_position_delta"] = ikw
-    if _get(w, "state_based_expert_imitation_reward") is not None:
-        raise NotImplementedError("wrappers.state_based_expert_imitation_reward: imitation-reward wrappers run per env in Python and are outside the batched stepper")
+    sb = _get(w, "state_based_expert_imitation_reward")
+    if sb is not None:   # state_based_expert_imitation_reward_wrap_fn (training_utils.py): the wrapper of the task, on a dataset recorded for the batched stepper
+        sbk = dict(_plain(sb))
+        name, rsi_prob = sbk.pop("dataset_name", None), sbk.pop("rsi_prob", 0.0)
+        if not _dataset_file_exists(name):
+            raise NotImplementedError(f"wrappers.state_based_expert_imitation_reward: the wrapper compares with the states of a recorded dataset and no "
+                                      f"{_dataset_file(name)} exists for the batched stepper (the reference's per-episode folders are not read; record one "
+                                      "with tools/create_expert_dataset.py)")
+        out["dataset"], out["rsi_prob"], out["state_imitation_reward"] = str(name), float(rsi_prob or 0.0), sbk
     ab = _get(w, "action_based_expert_imitation_reward")
     if ab is not None:
         abk = dict(_plain(ab))
         rsi_prob = abk.pop("rsi_prob", None)
-        abk.pop("dataset_name", None)   # _compose_action_based_expert_imitation_reward_wrapper_kwargs (training_utils.py:252-271)
+        name = abk.pop("dataset_name", None)   # _compose_action_based_expert_imitation_reward_wrapper_kwargs (training_utils.py:252-271)
         expert = _get(config, "expert")
-        if rsi_prob is not None:
-            # action_based_expert_imitation_reward_wrap_fn (training_utils.py:297-307) wraps DatasetRSIWrapper whenever rsi_prob is not None
+        rsi = rsi_prob is not None and _dataset_file_exists(name)
+        if rsi:   # action_based_expert_imitation_reward_wrap_fn (training_utils.py:297-307) wraps DatasetRSIWrapper whenever rsi_prob is not None
+            if "dataset" in out:
+                raise NotImplementedError("wrappers: state_based_ and action_based_expert_imitation_reward together (the reference wraps one of them)")
+            out["dataset"], out["rsi_prob"] = str(name), float(rsi_prob)
+        if rsi_prob is not None and not rsi:
             if float(abk.get("alpha") or 0.0) != 0.0 or float(rsi_prob) != 0.0:
                 raise NotImplementedError(f"wrappers.action_based_expert_imitation_reward with rsi_prob = {rsi_prob}: the reference then wraps DatasetRSIWrapper, "
-                                          "which resets episodes to the states of a recorded dataset (datasets/<dataset_name>/); no such dataset files exist "
-                                          "for the batched stepper.  Set rsi_prob to null for the imitation reward alone (alpha = 0, rsi_prob = 0 leaves the "
+                                          f"which resets episodes to the states of a recorded dataset; no {_dataset_file(name)} exists "
+                                          "for the batched stepper (tools/create_expert_dataset.py records one).  Set rsi_prob to null for the imitation reward alone (alpha = 0, rsi_prob = 0 leaves the "
                                           "environment reward unchanged and is skipped)")
         elif expert is None:
             if float(abk.get("alpha") or 0.0) != 0.0:   # alpha = 0 without an expert: the environment reward unchanged; skipped as before

@@ -127,8 +127,10 @@ OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (h
 
 # ActionBasedExpertImitationRewardWrapper._add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130): on the infos of done steps
 IMITATION_INFO_KEYS = ("ep_im_rew_mean", "ep_env_rew_mean", "ep_full_rew_mean", "im_rew_mean", "env_rew_mean", "full_rew_mean")
+# PickPlaceHumanCartStateBasedExpertImitationRewardWrapper._add_reward_to_info (state_based_expert_imitation_reward_wrapper.py:529-540) adds four more
+STATE_IMITATION_PP_INFO_KEYS = ("ep_m_im_rew_mean", "ep_g_im_rew_mean", "m_im_rew_mean", "g_im_rew_mean")
 # what SB3's rollout loops (and the reference's logging callback, for the imitation keys) look up on every info: stored eagerly where they exist
-_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated") + IMITATION_INFO_KEYS)
+_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated") + IMITATION_INFO_KEYS + STATE_IMITATION_PP_INFO_KEYS)
 
 
 class LazyInfo(dict):
@@ -181,9 +183,10 @@ class LazyInfo(dict):
 class _InfoSource:
     """What the infos of one step are filled from: a copy of the info block, the executed actions, the expert views."""
 
-    def __init__(self, rows, acts, expert, prev_full, term_obs, keys=None):
+    def __init__(self, rows, acts, expert, prev_full, term_obs, keys=None, early=None):
         self.rows, self.acts, self.expert, self.prev_full, self.term_obs = rows, acts, expert, prev_full, term_obs
         self.keys = keys or INFO_KEYS
+        self.early = early   # early_termination per env (state imitation reward with use_et), or None
 
     def fill(self, d, i):
         row = self.rows[i].tolist()
@@ -195,6 +198,8 @@ class _InfoSource:
             if k != "TimeLimit.truncated":
                 set_(d, k, row[j] != 0)
         set_(d, "action", self.acts[i])  # collision_prevention_wrapper.py:42-43: the executed action
+        if self.early is not None:       # state_based_expert_imitation_reward_wrapper.py:152: on every info when use_et
+            set_(d, "early_termination", int(self.early[i]))
         if self.expert is not None:  # expert_obs_wrapper.py:171-175 (the step's own observation: pre-reset where done)
             prev, cur = self.prev_full[i], self.term_obs[i]
             set_(d, "previous_expert_observation", {k: np.array(prev[list(OBS_COLUMNS[k])]) for k in self.expert})
@@ -221,8 +226,11 @@ class _TorchBackend:
         self.info = hb[o[3]:o[3] + s[3]].view(np.int32).reshape(n_envs, idim)
         self.done = hb[o[4]:o[4] + s[4]]
         self.imit = None   # host copy of the imitation rows, once an expert with a reward is attached
+        self.sir = None    # host copy of the state imitation rows, once a dataset is attached
 
     def _fetch(self):
+        if self.sir is not None:
+            self._sir_host.copy_(self.batch.sir, non_blocking=True)
         if self.imit is not None:   # queued ahead of the packed block on the same stream: the one blocking copy below completes both
             self._imit_host.copy_(self.batch.imit, non_blocking=True)
         self._host.copy_(self.batch.packed, non_blocking=False)
@@ -233,17 +241,29 @@ class _TorchBackend:
             self._imit_host = self.torch.zeros(self.n, CONST["HRG_IMIT_DIM"], dtype=self.torch.float32, pin_memory=True)
             self.imit = self._imit_host.numpy()
 
+    def attach_dataset(self, dataset, rsi_prob, state_imitation_reward, seed):
+        self.batch.attach_dataset(dataset, rsi_prob=rsi_prob, state_imitation_reward=state_imitation_reward, seed=seed)
+        self._sir_host = self.torch.zeros(self.n, CONST["HRG_SIR_DIM"], dtype=self.torch.float32, pin_memory=True)
+        self.sir = self._sir_host.numpy()
+
     def expert_actions(self):
         return self.batch.expert_actions().cpu().numpy()
 
     def reset(self):
-        self.batch.reset()
+        if self.sir is not None:
+            self.batch.dataset_reset()
+            cur = self.batch.dataset_cursor()   # (synchronous; a whole-batch reset is not on the step path)
+            self.reset_time = (cur[:, 1] / cur[:, 2]).astype(np.float32)   # StateBasedExpertImitationRewardWrapper.reset (107): start step / T
+        else:
+            self.batch.reset()
         self._fetch()
         return self.obs
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
-        if self.imit is not None:
+        if self.sir is not None:   # (runs the expert's kernels too when an imitation reward is attached)
+            self.batch.step_dataset(self._act)
+        elif self.imit is not None:
             self.batch.step_imitation(self._act)
         else:
             self.batch.step(self._act)
@@ -272,13 +292,43 @@ class HipVecEnv(_VecEnvBase):
     _info_keys = INFO_KEYS   # names of the info columns (a task may rename its task-specific column: INFO_KEY_ALIASES)
     _expert_desc = None   # hrg_expert_desc of the attached scripted expert
     _imit_alpha = None    # alpha of the imitation reward, when one is configured
+    _dataset = None       # the attached demonstration dataset (dataset.ExpertDataset)
+    _sir = None           # arguments of the state imitation reward (dataset.sir_kwargs), when one is configured
+    _observe_time = False  # the state imitation reward appends its time column to the observation
 
     def __init__(self, n_envs=1, env_id="ReachHuman", env_kwargs=None, obs_keys=None, seed=None, clips=None,
                  device=0, env_id0=0, backend=None, info_dicts=True, collision_prevention=None, goal_check=True, ik_position_delta=None,
                  expert_obs_keys=None, goal_env=False, obs_norm=None, monitor_dir=None, monitor_kwargs=None, reach_box=False, robot_geometry="capsule",
-                 expert=None, imitation_reward=None):
+                 expert=None, imitation_reward=None, dataset=None, rsi_prob=None, state_imitation_reward=None):
         if env_id not in ENV_DEFAULTS:
             raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)} (DESIGN.md §6)")
+        # dataset: a name (datasets/<name>/hrg_dataset.npz) or a loaded dataset.ExpertDataset: every episode starts from a state of the dataset
+        # (DatasetRSIWrapper: a random state with probability rsi_prob, otherwise an episode's first); state_imitation_reward: dict(alpha, beta,
+        # iota | iota_m, iota_g, sim_fn | m_sim_fn, g_sim_fn, observe_time, use_et, et_dist) = config.wrappers.state_based_expert_imitation_reward:
+        # the step reward becomes r_im alpha + r_env (1 - alpha), r_im from the demonstration state of the same step (csrc/hrgym_dataset.h)
+        if dataset is None and (rsi_prob is not None or state_imitation_reward is not None):
+            raise ValueError("rsi_prob / state_imitation_reward need a dataset (the reference's wrappers load one by dataset_name)")
+        if dataset is not None:
+            from .dataset import NO_DATASET_ENVS, ExpertDataset, sir_kwargs
+            if backend is not None:
+                raise NotImplementedError("dataset / state_imitation_reward: the restore and reward kernels run in the HIP library; another backend has none")
+            if goal_env:
+                raise NotImplementedError("dataset / state_imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
+            if env_id in NO_DATASET_ENVS:
+                raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
+            if state_imitation_reward is not None and imitation_reward is not None:
+                raise NotImplementedError("state_imitation_reward with imitation_reward: the reference wraps one imitation reward, state based or action based")
+            has_box = env_id != "ReachHuman" or bool(reach_box)
+            if not isinstance(dataset, ExpertDataset):
+                dataset = ExpertDataset.load(dataset, env_id=env_id, has_box=has_box)
+            elif dataset.env_id != env_id or (dataset.boxes is not None) != has_box:
+                raise ValueError(f"dataset of {dataset.env_id} ({'with' if dataset.boxes is not None else 'without'} box array) for {env_id}")
+            if state_imitation_reward is not None:
+                if reach_box:
+                    raise NotImplementedError("state_imitation_reward with reach_box: the cube kernel serves object_quat in the goal_difference columns")
+                self._sir = sir_kwargs(env_id, state_imitation_reward)
+                self._observe_time = self._sir["observe_time"]
+            self._dataset = dataset
         # expert: dict(id=..., signal_to_noise_ratio=..., ...) = config.expert (a scripted expert of demonstrations/experts/, evaluated on the device:
         # env.expert_actions()); imitation_reward: dict(alpha, beta, iota_m, iota_g, m_sim_fn, g_sim_fn, normalize_joint_actions) =
         # config.wrappers.action_based_expert_imitation_reward: the step reward becomes r_im alpha + r_env (1 - alpha) (csrc/hrgym_expert.h)
@@ -341,6 +391,8 @@ class HipVecEnv(_VecEnvBase):
             backend = backend(self._desc, self._clips, n_envs, env_id0)    # backend itself when the model description is composed here (create_training_vec_env)
         self._backend = backend if backend is not None else _TorchBackend(self._desc, self._clips, n_envs, env_id0, device)
         obs_space = _Box(-np.inf, np.inf, shape=(len(self._cols),), dtype=np.float32)
+        if self._observe_time:   # _add_time_to_observation_space (state_based_expert_imitation_reward_wrapper.py:202-208): one more value, bound to [0, 1]
+            obs_space = _Box(np.concatenate([obs_space.low, [0.0]]).astype(np.float32), np.concatenate([obs_space.high, [1.0]]).astype(np.float32), dtype=np.float32)
         if self.goal_env:
             goal_space = _Box(-np.inf, np.inf, shape=(len(self._dg_cols),), dtype=np.float32)
             ag_space = _Box(-np.inf, np.inf, shape=(len(self._ag_cols),), dtype=np.float32)
@@ -360,6 +412,10 @@ class HipVecEnv(_VecEnvBase):
             self._backend.attach_expert(self._expert_desc)
             if imitation_reward is not None:
                 self._imit_alpha = float(self._expert_desc.alpha)
+        if self._dataset is not None:
+            self._rsi_prob = float(rsi_prob or 0.0)
+            self._sir_arg = state_imitation_reward
+            self._backend.attach_dataset(self._dataset, self._rsi_prob, state_imitation_reward, int(self._desc.seed))
         self.info_dicts = info_dicts
         self._ep_ret = np.zeros(n_envs, np.float64)
         self._ep_len = np.zeros(n_envs, np.int64)
@@ -374,7 +430,7 @@ class HipVecEnv(_VecEnvBase):
             if self.goal_env:
                 raise NotImplementedError("obs_norm with goal_env: the reference normalises flat observations only")
             mean, std = np.array(obs_norm["mean"], np.float64), np.array(obs_norm["std"], np.float64)
-            k = len(self._cols)
+            k = len(self._cols) + int(self._observe_time)   # the time column is appended inside the normalisation (the imitation wrapper sits below it)
             if mean.shape != (k,) or std.shape != (k,):
                 if not obs_norm.get("allow_different_observation_shapes", False):
                     raise ValueError(f"obs_norm: statistics of length {mean.shape[0]} for an observation of length {k} (Environment and dataset observation space do not match!)")
@@ -405,7 +461,7 @@ class HipVecEnv(_VecEnvBase):
         self._last_full = full
         if self.expert_obs_keys is not None:
             self._expert_cur = np.array(full, copy=True)
-        return self._view(full)
+        return self._view(full, self._backend.reset_time if self._observe_time else None)
 
     def step_async(self, actions):
         if self._ik is not None:  # [dx, dy, dz, gripper] in the first four columns of the 7-wide action rows
@@ -420,10 +476,14 @@ class HipVecEnv(_VecEnvBase):
         obs, term_obs, reward, done, info = self._backend.step_wait()
         full = np.asarray(obs)
         self._last_full = full
-        obs, reward = self._view(full), np.array(reward, copy=True)
-        dones = np.asarray(done).astype(bool)
+        sir = np.array(self._backend.sir, copy=True) if self._dataset is not None else None
+        obs, reward = self._view(full, sir[:, CONST["HRG_SIR_TIME_OBS"]] if self._observe_time else None), np.array(reward, copy=True)
+        dones = np.asarray(done).astype(bool)   # (with early termination: where the episode ended for either reason)
+        self._step_sir = sir
         imit = None
-        if self._imit_alpha is not None:   # the reward is the combined one; Monitor sits inside the imitation wrapper (SB3 make_vec_env), so its return is r_env
+        if self._sir is not None:   # as below: Monitor sits inside the imitation wrapper, its return is r_env (it does not see ET in the reference; here an
+            self._ep_ret += sir[:, CONST["HRG_SIR_R_ENV"]]   # ET step ends the Monitor episode like any other done: DESIGN.md deviations)
+        elif self._imit_alpha is not None:   # the reward is the combined one; Monitor sits inside the imitation wrapper (SB3 make_vec_env), so its return is r_env
             imit = np.array(self._backend.imit, copy=True)
             self._ep_ret += imit[:, 1]
         else:
@@ -435,6 +495,8 @@ class HipVecEnv(_VecEnvBase):
             infos = self._make_infos(info, dones, term_obs)
             if imit is not None:
                 self._imitation_infos(infos, imit, np.nonzero(dones)[0])
+            if self._sir is not None:
+                self._state_imitation_infos(infos, sir, np.nonzero(dones)[0])
         else:
             infos = [{} for _ in range(self.num_envs)]
             if self._monitor is not None:   # the Monitor csv does not depend on the per-env dicts: episode rows from the done mask and the info block
@@ -448,8 +510,9 @@ class HipVecEnv(_VecEnvBase):
     def _make_infos(self, info, dones, term_obs):
         # the per-env dicts are filled from a copy of the info block on first use (LazyInfo)
         info = np.array(info, copy=True)
+        sir = getattr(self, "_step_sir", None)
         src = _InfoSource(info, self._actions, self.expert_obs_keys, self._expert_cur, np.array(term_obs, copy=True) if self.expert_obs_keys is not None else None,
-                          keys=self._info_keys)
+                          keys=self._info_keys, early=sir[:, CONST["HRG_SIR_EARLY"]] if self._sir is not None and self._sir["use_et"] else None)
         n = self.num_envs
         new = LazyInfo.__new__
         infos = [new(LazyInfo) for _ in range(n)]
@@ -464,7 +527,7 @@ class HipVecEnv(_VecEnvBase):
             for i, tr in zip(idx.tolist(), trunc.tolist()):
                 d = infos[i]
                 set_(d, "TimeLimit.truncated", tr)
-                set_(d, "terminal_observation", self._view(np.array(term_obs[i])))
+                set_(d, "terminal_observation", self._view(np.array(term_obs[i]), sir[i, CONST["HRG_SIR_TIME"]] if self._observe_time else None))
                 set_(d, "episode", {"r": float(self._ep_ret[i]), "l": int(self._ep_len[i]), "t": now})
             if self._monitor is not None:
                 self._monitor_rows(info, idx, now)
@@ -483,6 +546,30 @@ class HipVecEnv(_VecEnvBase):
             set_(d, "im_rew_mean", ep_im / n)
             set_(d, "env_rew_mean", ep_env / n)
             set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+
+    def _state_imitation_infos(self, infos, sir, idx):
+        """_add_reward_to_info of the state-based wrappers (state_based_expert_imitation_reward_wrapper.py:176-200, 529-540) from the rows of the envs that
+        finished an episode; the pick-place means divide by the steps that entered the motion / gripper sums (535)."""
+        a = self._sir["alpha"]
+        C = CONST
+        pp = self._backend.batch.dataset_desc.sir_kind == C["HRG_SIR_PICK_PLACE"]
+        set_ = dict.__setitem__
+        for i in idx.tolist():
+            row = sir[i]
+            ep_im, ep_env, n = float(row[C["HRG_SIR_EP_IM"]]), float(row[C["HRG_SIR_EP_ENV"]]), float(row[C["HRG_SIR_EP_LEN"]])
+            d = infos[i]
+            set_(d, "ep_im_rew_mean", ep_im)
+            set_(d, "ep_env_rew_mean", ep_env)
+            set_(d, "ep_full_rew_mean", ep_im * a + ep_env * (1 - a))
+            set_(d, "im_rew_mean", ep_im / n)
+            set_(d, "env_rew_mean", ep_env / n)
+            set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+            if pp:
+                ep_m, ep_g, n_mg = float(row[C["HRG_SIR_EP_MOTION"]]), float(row[C["HRG_SIR_EP_GRIPPER"]]), float(row[C["HRG_SIR_EP_LEN_MG"]])
+                set_(d, "ep_m_im_rew_mean", ep_m)
+                set_(d, "ep_g_im_rew_mean", ep_g)
+                set_(d, "m_im_rew_mean", float("nan") if n_mg == 0 else ep_m / n_mg)
+                set_(d, "g_im_rew_mean", float("nan") if n_mg == 0 else ep_g / n_mg)
 
     def expert_actions(self):
         """The attached expert's action for every env's current observation (the one the last reset / step returned): float64 [n, 4] for the
@@ -528,6 +615,8 @@ class HipVecEnv(_VecEnvBase):
             self._backend = _TorchBackend(self._desc, self._clips, self.num_envs, self._env_id0, self._device)
             if self._expert_desc is not None:
                 self._backend.attach_expert(self._expert_desc)
+            if self._dataset is not None:
+                self._backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
         else:
             self._backend.reseed(self._desc)
         return [int(seed) + i for i in range(self.num_envs)]
@@ -588,11 +677,13 @@ class HipVecEnv(_VecEnvBase):
     def set_attr(self, attr_name, value, indices=None):
         raise NotImplementedError("per-env attributes are fixed at construction (hrg_model_desc)")
 
-    def _view(self, full):
-        """Policy view of rows of the observation superset: flat array, or the goal-env dict."""
+    def _view(self, full, time=None):
+        """Policy view of rows of the observation superset: flat array, or the goal-env dict.  `time`: the state imitation reward's time column (observe_time)."""
         full = np.asarray(full)
         if not self.goal_env:
             v = full[..., self._cols]
+            if time is not None:
+                v = np.concatenate([v, np.asarray(time, np.float32)[..., None]], axis=-1)
             if getattr(self, "_norm", None) is not None:
                 mean, std, squash = self._norm
                 v = (v - mean) / std

@@ -412,6 +412,38 @@ typedef struct hrg_expert_desc {
   int32_t reserved;
 } hrg_expert_desc;
 
+/* ------------------------------------------------------------------------- demonstration datasets: RSI + state imitation reward (POD) */
+/* StateBasedExpertImitationRewardWrapper subclasses (wrappers/state_based_expert_imitation_reward_wrapper.py) */
+enum { HRG_SIR_NONE = 0        /* DatasetRSIWrapper alone (dataset_wrapper.py:88-157): resets to dataset states, no state reward */,
+       HRG_SIR_REACH = 1       /* ReachHumanStateBasedExpertImitationRewardWrapper (283-413): goal_difference, all six columns */,
+       HRG_SIR_PICK_PLACE = 2  /* PickPlaceHumanCartStateBasedExpertImitationRewardWrapper (416-619): vec_eef_to_target, robot0_gripper_qpos, object_gripped */,
+       HRG_SIR_LIFTING = 3     /* CollaborativeLiftingCartStateBasedExpertImitationRewardWrapper (622-758): vec_eef_to_human_lh, board_gripped */ };
+#define HRG_SIR_DIM 16    /* floats per env of the state imitation row (hrg_batch_step_dataset) */
+/* columns of the state imitation row; on a finished step the episode columns are the finished episode's (the accumulators restart after it) */
+enum { HRG_SIR_R_IM = 0, HRG_SIR_R_ENV = 1, HRG_SIR_R_MOTION = 2, HRG_SIR_R_GRIPPER = 3 /* pick-place only; 0 elsewhere and on a gripped-mismatch step */,
+       HRG_SIR_R_FULL = 4 /* the combined reward (= reward_dev) */, HRG_SIR_EP_IM = 5, HRG_SIR_EP_ENV = 6, HRG_SIR_EP_MOTION = 7, HRG_SIR_EP_GRIPPER = 8 /* episode sums */,
+       HRG_SIR_EP_LEN = 9 /* steps of the episode (len(_imitation_rewards)) */,
+       HRG_SIR_EP_LEN_MG = 10 /* steps that entered the motion / gripper sums (len(_gripper_imitation_rewards), 535: without the gripped-mismatch steps) */,
+       HRG_SIR_EARLY = 11 /* early_termination (152) */, HRG_SIR_TIME = 12 /* _dataset_ep_step_idx / _dataset_transition_count after the step (159): the time column of the
+                                                                            * step's own observation (the terminal one where the env finished) */,
+       HRG_SIR_TIME_OBS = 13 /* the time column of the obs_dev row: HRG_SIR_TIME, or the new episode's start step / T where the env finished (reset(), 107) */ };
+
+/* One demonstration dataset (episodes concatenated) + what is done with it.  The pointers are HOST memory, read by hrg_batch_dataset_attach only. */
+typedef struct hrg_dataset_desc {
+  int64_t n_episodes, total_T;    /* total_T = ep_offset[n_episodes]: transitions over all episodes */
+  const int64_t* ep_offset;       /* [n_episodes + 1]; episode k has T_k = ep_offset[k + 1] - ep_offset[k] >= 1 transitions */
+  const void* states;             /* [total_T] hrg_env_state: the state BEFORE transition t */
+  const void* boxes;              /* [total_T] hrg_box_state; NULL exactly when the batch's task is ReachHuman */
+  const float* obs;               /* [total_T + n_episodes][HRG_OBS_DIM]: per episode rows 0 .. T_k, row T_k the terminal observation */
+  double rsi_prob;                /* DatasetRSIWrapper rsi_prob (153-157) */
+  uint64_t seed;                  /* keys the episode / start step draws (with the global env id and the env's reset counter) */
+  int32_t sir_kind;               /* HRG_SIR_* */
+  int32_t use_et;                 /* early termination (143-152) */
+  double alpha, beta, iota_m, iota_g; /* `iota` of the Reach / Lifting wrappers is iota_m */
+  double et_dist;
+  int32_t m_sim_fn, g_sim_fn;     /* HRG_SIM_*; `sim_fn` of the Reach / Lifting wrappers is m_sim_fn */
+} hrg_dataset_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
@@ -516,6 +548,34 @@ int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc);
 int hrg_batch_expert_actions(hrg_batch* b, const float* obs_dev, double* actions_out_dev, void* stream);
 int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev,
                              float* imit_dev, void* stream);
+
+/* Demonstration datasets on the device (csrc/hrgym_dataset.h): reference state initialisation and the state-based expert imitation reward, in two small
+ * kernels behind the (unchanged) step launch.
+ *   hrg_batch_snapshot        <- DatasetCollectionWrapper.step's get_environment_state (wrappers/dataset_collection_wrapper.py; training/create_expert_dataset.py):
+ *                                ONE asynchronous device-to-device copy of the whole hrg_env_state array into states_out_dev [n_envs] (caller-owned device
+ *                                memory), and of the hrg_box_state array into boxes_out_dev when that is non-null.  HRG_ERR_UNSUPPORTED for the stacking and
+ *                                hammering batches (their state lives in further arrays).
+ *   hrg_batch_dataset_attach  <- DatasetWrapper.load_dataset + DatasetRSIWrapper.__init__ / StateBasedExpertImitationRewardWrapper.__init__
+ *                                (dataset_wrapper.py:35-113, state_based_expert_imitation_reward_wrapper.py:74-99): uploads the arrays once, allocates the per-env
+ *                                cursor (episode, step, T), reset counter and episode sums.  Synchronous; never on the step path.  HRG_ERR_UNSUPPORTED for the
+ *                                stacking and hammering batches and for a sir_kind that does not read the task's observation; HRG_ERR_INVALID for an episode
+ *                                with T = 0, a broken episode table, a boxes pointer that does not fit the task.  Attaching again replaces the dataset.
+ *   hrg_batch_dataset_reset   <- DatasetRSIWrapper.reset (115-135): hrg_batch_reset, then the masked envs (NULL: all) are restored to a dataset state: episode
+ *                                floor(u0 n_episodes), step u1 < rsi_prob ? floor(u2 T) : 0, u = rng_u01(seed, global env id, reset counter, stream 9, 0..2);
+ *                                state block, box block and observation row are copied, obs_dev rows of restored envs hold the dataset's observation.
+ *   hrg_batch_step_dataset    <- DatasetRSIWrapper.step (137-151) + StateBasedExpertImitationRewardWrapper.step (115-174) + the reset of a finished env:
+ *                                [expert pre kernel] -> hrg_batch_step -> [action imitation post kernel] -> state reward / ET / cursor -> restore of the finished
+ *                                envs.  The bracketed kernels run when an expert with a reward is attached (then imit_dev must be non-null; otherwise it is
+ *                                ignored).  term_obs_dev is REQUIRED: the policy's state of a finished env is its terminal observation; an env that only early
+ *                                termination finished gets its obs_dev row copied there before the restore.  done_dev is set where ET fires.
+ *                                sir_dev float[n_envs][HRG_SIR_DIM].  With sir_kind = HRG_SIR_NONE the state reward columns stay zero and reward_dev is untouched.
+ *   hrg_batch_dataset_cursor  parity hook (synchronous): cursor_host int32[n_envs][3] = (episode, step, T) of every env. */
+int hrg_batch_snapshot(hrg_batch* b, void* states_out_dev, void* boxes_out_dev, void* stream);
+int hrg_batch_dataset_attach(hrg_batch* b, const hrg_dataset_desc* desc);
+int hrg_batch_dataset_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream);
+int hrg_batch_step_dataset(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev,
+                           float* imit_dev, float* sir_dev, void* stream);
+int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
