@@ -1,4 +1,4 @@
-"""ctypes mirrors of the POD structs in include/hrgym.h and include/hrgym_state.h.
+"""ctypes mirrors of the POD structs in include/hrgym.h and include/hrgym_state.h, and the prototypes of the functions hrgym.h declares.
 
 The mirrors are generated from the headers themselves (one source of truth); `sizeof` is cross-checked
 against the compiled library (`hrg_state_bytes`) when it is loaded.
@@ -72,6 +72,35 @@ def _parse(paths):
     return consts, structs
 
 
+_SCALARS = dict({k: v for k, v in _CTYPES.items() if "*" not in k}, int=ctypes.c_int, size_t=ctypes.c_size_t)
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p, "void": None}
+
+
+def parse_prototypes(src):
+    """{name: (restype, [argtypes])} of every `hrg_*(...)` declaration in the header text `src`.  Every pointer (structs and `hrg_batch**` included) is a
+    c_void_p: callers pass addresses, byref(...) or None.  A return or parameter type without a ctypes counterpart raises, naming the declaration."""
+    protos, src = {}, _strip_comments(src)
+    for m in re.finditer(r"([^;{}#]*?)\b(hrg_\w+)\s*\(([^()]*)\)\s*;", src):
+        decl = " ".join(m.group(0).split())
+        norm = lambda t: re.sub(r"\s*\*\s*", "* ", " ".join(t.split())).strip()   # noqa: E731
+        ret, params = norm(m.group(1)), [norm(p) for p in m.group(3).split(",")]
+        if ret not in _RETURNS:
+            raise ValueError(f"include/hrgym.h: return type {ret!r} has no ctypes counterpart: {decl}")
+        args = []
+        for p in ([] if params == ["void"] else params):
+            words = [w for w in p.split() if w != "const"]
+            scalar = " ".join(words[:-1] if len(words) > 1 else words)   # (without the parameter's name)
+            pointer = "*" in p or "[" in p   # (an array parameter is a pointer)
+            if not pointer and scalar not in _SCALARS:
+                raise ValueError(f"include/hrgym.h: parameter {p!r} has no ctypes counterpart: {decl}")
+            args.append(ctypes.c_void_p if pointer else _SCALARS[scalar])
+        protos[m.group(2)] = (_RETURNS[ret], args)
+    skipped = sorted(set(re.findall(r"\b(hrg_\w+)\s*\(", src)) - set(protos))   # e.g. a function-pointer parameter: nested parentheses
+    if skipped:
+        raise ValueError(f"include/hrgym.h: cannot parse the declaration of {skipped}")
+    return protos
+
+
 CONST, _STRUCTS = _parse([os.path.join(_INCLUDE, "hrgym.h"), os.path.join(_INCLUDE, "hrgym_state.h")])
 ModelDesc = _STRUCTS["hrg_model_desc"]
 ClipTable = _STRUCTS["hrg_clip_table"]
@@ -83,6 +112,7 @@ StackState = _STRUCTS["hrg_stack_state"]
 HammerState = _STRUCTS["hrg_hammer_state"]
 ExpertDesc = _STRUCTS["hrg_expert_desc"]
 DatasetDesc = _STRUCTS["hrg_dataset_desc"]
+PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 
 def struct_to_dict(s):

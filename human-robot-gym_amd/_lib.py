@@ -7,35 +7,19 @@ import ctypes
 import os
 import subprocess
 
-from ._cstruct import CONST, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc, DatasetDesc  # noqa: F401
+from ._cstruct import CONST, PROTOTYPES, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc, DatasetDesc  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhrgym_hip.so")   # the one shipping library; no environment variable redirects it
 _variant = None   # tuning experiments only: set through use_variant_library(), reported by bench.py as "variant_lib"
 SRC = os.path.join(_HERE, "csrc", "hrgym_hip.hip")
-SRC_BOX = os.path.join(_HERE, "csrc", "hrgym_box.hip")   # the same sources compiled with the manipulation object (PickPlaceHumanCart)
-SRC_HO = os.path.join(_HERE, "csrc", "hrgym_handover.hip")   # ... and once more with the object <-> hand weld of the handover tasks
-SRC_LIFT = os.path.join(_HERE, "csrc", "hrgym_lift.hip")     # ... and with the connect equalities / task logic of CollaborativeLiftingCart
-SRC_STACK = os.path.join(_HERE, "csrc", "hrgym_stack.hip")   # ... and the four-cube system of CollaborativeStackingCart
-SRC_HAMMER = os.path.join(_HERE, "csrc", "hrgym_hammer.hip")  # ... and board + nail + hammer of CollaborativeHammeringCart
-SRC_HULLS = os.path.join(_HERE, "csrc", "hrgym_hulls.hip")    # ... and the ReachHuman kernels with the arm links' convex hulls as collision geometry
-SRC_BOX_HULLS = os.path.join(_HERE, "csrc", "hrgym_box_hulls.hip")   # ... and the cube kernels with the convex hulls (hull - cube pairs by MPR)
-SRC_HO_HULLS = os.path.join(_HERE, "csrc", "hrgym_handover_hulls.hip")   # ... and the handover, lifting, stacking, hammering kernels with the convex hulls
-SRC_LIFT_HULLS = os.path.join(_HERE, "csrc", "hrgym_lift_hulls.hip")
-SRC_STACK_HULLS = os.path.join(_HERE, "csrc", "hrgym_stack_hulls.hip")
-SRC_HAMMER_HULLS = os.path.join(_HERE, "csrc", "hrgym_hammer_hulls.hip")
-SOURCES = [SRC, SRC_BOX, SRC_HO, SRC_LIFT, SRC_STACK, SRC_HAMMER, SRC_HULLS, SRC_BOX_HULLS, SRC_HO_HULLS, SRC_LIFT_HULLS, SRC_STACK_HULLS, SRC_HAMMER_HULLS]
-
-EXPORTS = [
-    "hrg_last_error", "hrg_version", "hrg_state_bytes", "hrg_batch_create", "hrg_batch_destroy", "hrg_batch_reset",
-    "hrg_batch_step", "hrg_batch_contacts", "hrg_batch_capsules", "hrg_batch_get_state", "hrg_batch_set_state",
-    "hrg_batch_kernel_time", "hrg_batch_enable_taps", "hrg_box_bytes", "hrg_batch_get_box", "hrg_batch_set_box", "hrg_batch_get_states", "hrg_batch_set_states",
-    "hrg_batch_check_actions", "hrg_stack_bytes", "hrg_batch_get_stack", "hrg_batch_set_stack", "hrg_batch_launch_order",
-    "hrg_hammer_bytes", "hrg_batch_get_hammer", "hrg_batch_set_hammer", "hrg_test_hull_queries",
-    "hrg_test_hull_box_queries", "hrg_batch_mpr_fallbacks", "hrg_batch_pose_table_bytes", "hrg_debug_pose_compare",
-    "hrg_batch_expert_attach", "hrg_batch_expert_actions", "hrg_batch_step_imitation",
-    "hrg_batch_snapshot", "hrg_batch_dataset_attach", "hrg_batch_dataset_reset", "hrg_batch_step_dataset", "hrg_batch_dataset_cursor",
-]
+# SRC is the base unit (the ReachHuman kernels); every other unit is the same sources compiled with a task's additions: the manipulation object (box), the
+# object <-> hand weld (handover), the connect equalities of the lifting task, the four cubes (stack), board + nail + hammer; *_hulls: the same kernels with the
+# arm links' convex hulls as collision geometry (hull - cube pairs by MPR)
+SOURCES = [os.path.join(_HERE, "csrc", f"hrgym_{unit}.hip") for unit in (
+    "hip", "box", "handover", "lift", "stack", "hammer", "hulls", "box_hulls", "handover_hulls", "lift_hulls", "stack_hulls", "hammer_hulls")]
+SRC_BOX_HULLS = SOURCES[7]   # the one unit a test looks up by name (tests/test_hull_box.py)
+EXPORTS = list(PROTOTYPES)   # every function include/hrgym.h declares
 
 
 def build_library(force=False, verbose=False):
@@ -88,47 +72,9 @@ def load_library():
         raise RuntimeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                            "There is no CPU fallback for the stepper.")
     lib = ctypes.CDLL(path)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.hrg_last_error.restype = ctypes.c_char_p
-    lib.hrg_version.restype = ctypes.c_char_p
-    lib.hrg_state_bytes.restype = ctypes.c_size_t
-    lib.hrg_batch_create.argtypes = [ctypes.POINTER(ModelDesc), ctypes.POINTER(ClipTable), i32, i64, i32, ctypes.POINTER(vp)]
-    lib.hrg_batch_destroy.argtypes = [vp]
-    lib.hrg_batch_destroy.restype = None
-    lib.hrg_batch_reset.argtypes = [vp, vp, vp, vp]
-    lib.hrg_batch_step.argtypes = [vp] * 8
-    lib.hrg_batch_contacts.argtypes = [vp, vp, vp]
-    lib.hrg_batch_launch_order.argtypes = [vp, vp, vp]
-    lib.hrg_batch_capsules.argtypes = [vp, vp, vp, vp]
-    lib.hrg_batch_get_state.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_set_state.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_get_states.argtypes = [vp, vp, i32, vp, vp]
-    lib.hrg_batch_set_states.argtypes = [vp, vp, i32, vp, vp]
-    lib.hrg_box_bytes.restype = ctypes.c_size_t
-    lib.hrg_batch_get_box.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_set_box.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_hammer_bytes.restype = ctypes.c_size_t
-    lib.hrg_batch_get_hammer.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_set_hammer.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_test_hull_queries.argtypes = [vp, vp, vp, i32, vp]
-    lib.hrg_test_hull_box_queries.argtypes = [vp, vp, vp, i32, vp]
-    lib.hrg_batch_mpr_fallbacks.argtypes = [vp, ctypes.POINTER(i64)]
-    lib.hrg_batch_pose_table_bytes.argtypes = [vp, ctypes.POINTER(i64)]
-    lib.hrg_debug_pose_compare.argtypes = [vp, vp, i32, vp]
-    lib.hrg_stack_bytes.restype = ctypes.c_size_t
-    lib.hrg_batch_get_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_set_stack.argtypes = [vp, i32, vp, ctypes.c_size_t]
-    lib.hrg_batch_enable_taps.argtypes = [vp, i32]
-    lib.hrg_batch_check_actions.argtypes = [vp, vp, vp, vp]
-    lib.hrg_batch_expert_attach.argtypes = [vp, ctypes.POINTER(ExpertDesc)]
-    lib.hrg_batch_expert_actions.argtypes = [vp, vp, vp, vp]
-    lib.hrg_batch_step_imitation.argtypes = [vp] * 9
-    lib.hrg_batch_snapshot.argtypes = [vp] * 4
-    lib.hrg_batch_dataset_attach.argtypes = [vp, ctypes.POINTER(DatasetDesc)]
-    lib.hrg_batch_dataset_reset.argtypes = [vp] * 4
-    lib.hrg_batch_step_dataset.argtypes = [vp] * 10
-    lib.hrg_batch_dataset_cursor.argtypes = [vp, vp]
-    lib.hrg_batch_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]
+    for name, (restype, argtypes) in PROTOTYPES.items():   # the signatures are the header's own (_cstruct.parse_prototypes)
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.hrg_state_bytes() != ctypes.sizeof(EnvState):
         raise RuntimeError("hrg_env_state layout mismatch between header mirror and library: rebuild")
     _lib = lib
@@ -142,6 +88,42 @@ class HrgError(RuntimeError):
 def _check(lib, rc):
     if rc != 0:
         raise HrgError(f"hrgym error {rc}: {lib.hrg_last_error().decode()}")
+
+
+def _coerce(x, dtype, device):
+    """`x` itself when it already is a contiguous `dtype` tensor on `device`, otherwise a converted copy (which the caller keeps alive until the kernel
+    has read it)."""
+    if x.dtype != dtype or x.device != device or not x.is_contiguous():
+        x = x.to(device=device, dtype=dtype).contiguous()
+    return x
+
+
+def as_actions(actions, n, device):
+    """Actions as the kernels read them: float64 [n, HRG_ACT_DIM], contiguous, on `device`."""
+    import torch
+    actions = _coerce(actions, torch.float64, device)
+    if tuple(actions.shape) != (n, CONST["HRG_ACT_DIM"]):
+        raise ValueError(f"actions must be [{n}, {CONST['HRG_ACT_DIM']}]")
+    return actions
+
+
+def as_obs(obs, n, device):
+    """Rows of the observation superset: float32 [n, HRG_OBS_DIM], contiguous, on `device`."""
+    import torch
+    obs = _coerce(obs, torch.float32, device)
+    if tuple(obs.shape) != (n, CONST["HRG_OBS_DIM"]):
+        raise ValueError(f"obs must be [{n}, {CONST['HRG_OBS_DIM']}]")
+    return obs
+
+
+def as_mask(mask, device):
+    """A reset mask: uint8, contiguous, on `device` (None: every env)."""
+    import torch
+    return None if mask is None else _coerce(mask, torch.uint8, device)
+
+
+def _ptr(x):
+    return None if x is None else ctypes.c_void_p(x.data_ptr())
 
 
 class HipBatch:
@@ -171,7 +153,7 @@ class HipBatch:
             # one contiguous SoA output block so that multi-GPU runs need ONE all-gather per step (dist.packed_layout):
             # [obs f32 n*57 | reward f32 n | info i32 n*13 | done u8 n | term_obs f32 n*57]; `packed_head` (everything but the terminal
             # observations) is the part a step publishes to the other ranks
-            from .dist import packed_layout
+            from .dist import packed_layout, packed_views
             n, od, idim = self.n, C["HRG_OBS_DIM"], C["HRG_INFO_DIM"]
             if out is not None:
                 self.obs, self.term_obs, self.reward, self.info, self.done = out
@@ -179,57 +161,49 @@ class HipBatch:
                 for t, (shape, dt) in zip(out, want):
                     if tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
                         raise ValueError(f"out tensor {tuple(t.shape)} {t.dtype} on {t.device}: expected contiguous {shape} {dt} on {self.device}")
-                self.packed = self.packed_head = self.packed_layout = None
+                self.packed = self.packed_head = None
                 return
             lay = packed_layout(n)
-            offs, sizes, tot = lay["offsets"], lay["sizes"], lay["total"]
-            self.packed = torch.zeros(tot, dtype=torch.uint8, device=self.device)
+            self.packed = torch.zeros(lay["total"], dtype=torch.uint8, device=self.device)
             self.packed_head = self.packed[:lay["head"]]
-            self.packed_layout = dict(offsets=offs, sizes=sizes)
-            self.obs = self.packed[offs[0]:offs[0] + sizes[0]].view(torch.float32).view(n, od)
-            self.term_obs = self.packed[offs[1]:offs[1] + sizes[1]].view(torch.float32).view(n, od)
-            self.reward = self.packed[offs[2]:offs[2] + sizes[2]].view(torch.float32)
-            self.info = self.packed[offs[3]:offs[3] + sizes[3]].view(torch.int32).view(n, idim)
-            self.done = self.packed[offs[4]:offs[4] + sizes[4]]
+            v = packed_views(self.packed, n)
+            self.obs, self.term_obs, self.reward, self.info, self.done = v["obs"], v["term_obs"], v["reward"], v["info"], v["done"]
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _reset(self, fn, mask):
+        mask = as_mask(mask, self.device)
+        with self.torch.cuda.device(self.device):
+            _check(self.lib, fn(self.h, _ptr(mask), _ptr(self.obs), self._stream()))
+        self._keep_mask = mask
+        return self.obs
+
     def reset(self, mask=None):
         """Reset all envs (mask None) or those with mask != 0 (uint8 tensor on device). Returns obs tensor."""
-        mp = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
-            mp = ctypes.c_void_p(mask.data_ptr())
+        return self._reset(self.lib.hrg_batch_reset, mask)
+
+    def _step(self, fn, actions, *extra):
+        """One of the three step entries of the ABI: `fn(batch, actions, obs, term_obs, reward, done, info, *extra, stream)`."""
+        actions = as_actions(actions, self.n, self.device)
         with self.torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_reset(self.h, mp, ctypes.c_void_p(self.obs.data_ptr()), self._stream()))
-        return self.obs
+            _check(self.lib, fn(self.h, _ptr(actions), _ptr(self.obs), _ptr(self.term_obs), _ptr(self.reward), _ptr(self.done), _ptr(self.info),
+                                *map(_ptr, extra), self._stream()))
+        self._keep = actions
 
     def step(self, actions):
         """actions: float64 tensor [n, 7] on device. Returns (obs, reward, done, info) device tensors (views)."""
-        t = self.torch
-        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
-        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
-            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
-        vp = ctypes.c_void_p
-        with t.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_step(self.h, vp(actions.data_ptr()), vp(self.obs.data_ptr()), vp(self.term_obs.data_ptr()),
-                                                   vp(self.reward.data_ptr()), vp(self.done.data_ptr()), vp(self.info.data_ptr()), self._stream()))
-        self._keep = actions
+        self._step(self.lib.hrg_batch_step, actions)
         return self.obs, self.reward, self.done, self.info
 
     def check_actions(self, actions):
         """HumanEnv.check_collision_action for the whole batch: uint8 tensor [n], 1 where the joint-space action's goal configuration collides
         with the static scene or the robot itself (nothing is stepped)."""
         t = self.torch
-        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
-        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
-            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
+        actions = as_actions(actions, self.n, self.device)
         out = t.empty(self.n, dtype=t.uint8, device=self.device)
         with t.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_check_actions(self.h, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()))
+            _check(self.lib, self.lib.hrg_batch_check_actions(self.h, _ptr(actions), _ptr(out), self._stream()))
         self._keep_chk = actions
         return out
 
@@ -248,37 +222,20 @@ class HipBatch:
         """The expert's action for every env: float64 tensor [n, 7] on device (Cartesian experts fill the first four columns).  `obs`: float32 [n, 64]
         rows of the observation superset (default: the batch's own, as the last reset / step left them).  Every call advances the expert's noise once.
         The returned tensor is reused by the next call."""
-        t = self.torch
         if getattr(self, "expert_desc", None) is None:
             raise HrgError("no expert attached: call attach_expert() first")
-        if obs is None:
-            obs = self.obs
-        elif obs.dtype != t.float32 or obs.device != self.device or not obs.is_contiguous():
-            obs = obs.to(device=self.device, dtype=t.float32).contiguous()
-        if tuple(obs.shape) != (self.n, CONST["HRG_OBS_DIM"]):
-            raise ValueError(f"obs must be [{self.n}, {CONST['HRG_OBS_DIM']}]")
-        vp = ctypes.c_void_p
-        with t.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_expert_actions(self.h, vp(obs.data_ptr()), vp(self._expert_act.data_ptr()), self._stream()))
+        obs = self.obs if obs is None else as_obs(obs, self.n, self.device)
+        with self.torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_batch_expert_actions(self.h, _ptr(obs), _ptr(self._expert_act), self._stream()))
         self._keep_obs = obs
         return self._expert_act
 
     def step_imitation(self, actions):
         """`step` with the attached imitation reward: returns (obs, reward, done, info, imit); `reward` is r_im alpha + r_env (1 - alpha), `imit` the
         float32 [n, HRG_IMIT_DIM] row per env (r_im, r_env, r_motion, r_gripper, episode sums of r_im / r_env, episode length, combined reward)."""
-        t = self.torch
         if getattr(self, "expert_desc", None) is None:
             raise HrgError("no expert attached: call attach_expert() first")
-        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
-        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
-            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
-        vp = ctypes.c_void_p
-        with t.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_step_imitation(self.h, vp(actions.data_ptr()), vp(self.obs.data_ptr()), vp(self.term_obs.data_ptr()),
-                                                             vp(self.reward.data_ptr()), vp(self.done.data_ptr()), vp(self.info.data_ptr()), vp(self.imit.data_ptr()),
-                                                             self._stream()))
-        self._keep = actions
+        self._step(self.lib.hrg_batch_step_imitation, actions, self.imit)
         return self.obs, self.reward, self.done, self.info, self.imit
 
     def snapshot(self, states_out, boxes_out=None):
@@ -309,32 +266,14 @@ class HipBatch:
         """`reset`, then every reset env starts from a dataset state (DatasetRSIWrapper.reset).  Returns the obs tensor (dataset observation rows)."""
         if getattr(self, "dataset_desc", None) is None:
             raise HrgError("no dataset attached: call attach_dataset() first")
-        mp = None
-        if mask is not None:
-            mask = mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
-            mp = ctypes.c_void_p(mask.data_ptr())
-        with self.torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_dataset_reset(self.h, mp, ctypes.c_void_p(self.obs.data_ptr()), self._stream()))
-        self._keep_mask = mask
-        return self.obs
+        return self._reset(self.lib.hrg_batch_dataset_reset, mask)
 
     def step_dataset(self, actions):
         """`step` (or `step_imitation`, with an expert reward attached) followed by the dataset kernels: returns (obs, reward, done, info, sir); `sir` is the
         float32 [n, HRG_SIR_DIM] row per env (dataset.SIR_COLUMNS); finished envs (done, or early termination) restart from a dataset state."""
-        t = self.torch
         if getattr(self, "dataset_desc", None) is None:
             raise HrgError("no dataset attached: call attach_dataset() first")
-        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
-        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
-            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
-        vp = ctypes.c_void_p
-        imit = getattr(self, "imit", None)
-        with t.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_batch_step_dataset(self.h, vp(actions.data_ptr()), vp(self.obs.data_ptr()), vp(self.term_obs.data_ptr()),
-                                                           vp(self.reward.data_ptr()), vp(self.done.data_ptr()), vp(self.info.data_ptr()),
-                                                           vp(imit.data_ptr()) if imit is not None else None, vp(self.sir.data_ptr()), self._stream()))
-        self._keep = actions
+        self._step(self.lib.hrg_batch_step_dataset, actions, getattr(self, "imit", None), self.sir)
         return self.obs, self.reward, self.done, self.info, self.sir
 
     def dataset_cursor(self):

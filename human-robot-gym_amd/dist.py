@@ -29,20 +29,24 @@ def packed_layout(n):
     return dict(offsets=offs, sizes=sizes, total=tot, head=offs[1])
 
 
-def unpack(block, n):
-    """uint8 numpy block of one rank (whole, or only its published head) -> dict of typed views."""
+def packed_views(block, n):
+    """The typed views of one rank's output block of `n` envs: dict obs, term_obs, reward, info, done (no copies).  `block` is a uint8 torch tensor (device
+    or pinned host) or a uint8 numpy array: the whole block, or only its published head, which has no `term_obs`.  The one place that slices the block."""
     lay = packed_layout(n)
     o, s = lay["offsets"], lay["sizes"]
     od, idim = CONST["HRG_OBS_DIM"], CONST["HRG_INFO_DIM"]
-    out = dict(
-        obs=block[o[0]:o[0] + s[0]].view(np.float32).reshape(n, od),
-        reward=block[o[2]:o[2] + s[2]].view(np.float32),
-        info=block[o[3]:o[3] + s[3]].view(np.int32).reshape(n, idim),
-        done=block[o[4]:o[4] + s[4]],
-    )
-    if block.shape[0] >= lay["total"]:
-        out["term_obs"] = block[o[1]:o[1] + s[1]].view(np.float32).reshape(n, od)
-    return out
+    if isinstance(block, np.ndarray):
+        f32, i32 = np.float32, np.int32
+    else:
+        import torch
+        f32, i32 = torch.float32, torch.int32
+    items = [("obs", 0, f32, (n, od)), ("term_obs", 1, f32, (n, od)), ("reward", 2, f32, (n,)), ("info", 3, i32, (n, idim)), ("done", 4, None, (n,))]
+    if block.shape[0] < lay["total"]:
+        del items[1]
+    return {k: (block[o[i]:o[i] + s[i]] if dt is None else block[o[i]:o[i] + s[i]].view(dt)).reshape(shape) for k, i, dt, shape in items}
+
+
+unpack = packed_views   # (the name the multi-GPU callers use)
 
 
 def all_gather_packed(packed, group=None):

@@ -8,6 +8,7 @@ the variants fill the chip together instead of one after the other."""
 import numpy as np
 
 from ._cstruct import CONST
+from ._lib import HipBatch, as_actions
 from .animation import synthetic_clips
 from .model import build_model_desc
 
@@ -65,24 +66,17 @@ class MixedBatch:
 
     def __init__(self, parts, env_id0=0, device=0, concurrent=True):
         import torch
-        from ._lib import HipBatch
-        from .dist import packed_layout
+        from .dist import packed_layout, packed_views
         if not torch.cuda.is_available():
             raise RuntimeError("MixedBatch needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.torch = torch
         self.device = torch.device("cuda", device)
         self.n = sum(int(p[3]) for p in parts)
-        n, od, idim = self.n, CONST["HRG_OBS_DIM"], CONST["HRG_INFO_DIM"]
-        lay = packed_layout(n)
-        offs, sizes = lay["offsets"], lay["sizes"]
+        lay = packed_layout(self.n)
         self.packed = torch.zeros(lay["total"], dtype=torch.uint8, device=self.device)
         self.packed_head = self.packed[:lay["head"]]
-        self.packed_layout = dict(offsets=offs, sizes=sizes)
-        self.obs = self.packed[offs[0]:offs[0] + sizes[0]].view(torch.float32).view(n, od)
-        self.term_obs = self.packed[offs[1]:offs[1] + sizes[1]].view(torch.float32).view(n, od)
-        self.reward = self.packed[offs[2]:offs[2] + sizes[2]].view(torch.float32)
-        self.info = self.packed[offs[3]:offs[3] + sizes[3]].view(torch.int32).view(n, idim)
-        self.done = self.packed[offs[4]:offs[4] + sizes[4]]
+        v = packed_views(self.packed, self.n)
+        self.obs, self.term_obs, self.reward, self.info, self.done = v["obs"], v["term_obs"], v["reward"], v["info"], v["done"]
         self.env_ids, self.slices, self.batches = [], [], []
         r0 = 0
         for env_id, desc, clips, k in parts:
@@ -119,11 +113,7 @@ class MixedBatch:
 
     def step(self, actions):
         """actions: float64 [n, 7] on the device (rows in part order).  Returns (obs, reward, done, info) views of the shared block."""
-        t = self.torch
-        if actions.dtype != t.float64 or actions.device != self.device or not actions.is_contiguous():
-            actions = actions.to(device=self.device, dtype=t.float64).contiguous()
-        if tuple(actions.shape) != (self.n, CONST["HRG_ACT_DIM"]):
-            raise ValueError(f"actions must be [{self.n}, {CONST['HRG_ACT_DIM']}]")
+        actions = as_actions(actions, self.n, self.device)
         self._each(lambda i, b: b.step(actions[self.slices[i]]))
         self._keep = actions
         return self.obs, self.reward, self.done, self.info
@@ -168,48 +158,6 @@ def make_mixed_batch(n_envs, tasks=ICRA_TASKS, env_kwargs=None, clips=None, n_cl
     return MixedBatch(parts, env_id0=env_id0, device=device, concurrent=concurrent)
 
 
-class _MixedBackend:
-    """numpy <-> MixedBatch adapter with the interface of vec_env._TorchBackend (one H2D action copy, one D2H copy of the block)."""
-
-    def __init__(self, batch):
-        import torch
-        self.torch = torch
-        self.batch = batch
-        n = self.n = batch.n
-        lay = batch.packed_layout
-        self._host = torch.empty(batch.packed.numel(), dtype=torch.uint8, pin_memory=True)
-        o, s = lay["offsets"], lay["sizes"]
-        hb = self._host.numpy()
-        od, idim = CONST["HRG_OBS_DIM"], CONST["HRG_INFO_DIM"]
-        self.obs = hb[o[0]:o[0] + s[0]].view(np.float32).reshape(n, od)
-        self.term_obs = hb[o[1]:o[1] + s[1]].view(np.float32).reshape(n, od)
-        self.reward = hb[o[2]:o[2] + s[2]].view(np.float32)
-        self.info = hb[o[3]:o[3] + s[3]].view(np.int32).reshape(n, idim)
-        self.done = hb[o[4]:o[4] + s[4]]
-
-    def _fetch(self):
-        self._host.copy_(self.batch.packed, non_blocking=False)
-
-    def reset(self):
-        self.batch.reset()
-        self._fetch()
-        return self.obs
-
-    def step_async(self, actions):
-        self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
-        self.batch.step(self._act)
-
-    def step_wait(self):
-        self._fetch()
-        return self.obs, self.term_obs, self.reward, self.done, self.info
-
-    def executed_actions(self):
-        return self._act.cpu().numpy()
-
-    def close(self):
-        self.batch.close()
-
-
 def make_mixed_vec_env(n_envs, tasks=ICRA_TASKS, obs_keys=None, env_kwargs=None, seed=None, start_index=0, clips=None, n_clips=13,
                        device=0, info_dicts=True, concurrent=True, robot_geometry="capsule", expert=None, imitation_reward=None, dataset=None, rsi_prob=None,
                        state_imitation_reward=None):
@@ -227,40 +175,28 @@ def make_mixed_vec_env(n_envs, tasks=ICRA_TASKS, obs_keys=None, env_kwargs=None,
 
 
 def _mixed_cls():
-    from .vec_env import OBS_COLUMNS, HipVecEnv, _Box, _VecEnvBase
-    import time
+    from .vec_env import OBS_COLUMNS, HipVecEnv, _TorchBackend
 
     class MixedHipVecEnv(HipVecEnv):
-        """VecEnv over a `MixedBatch` (see `make_mixed_vec_env`).  Joint-space actions [n, 7] for every task."""
+        """VecEnv over a `MixedBatch` (see `make_mixed_vec_env`).  Joint-space actions [n, 7] for every task.  `batch`: the MixedBatch, or any backend
+        (protocol: vec_env._TorchBackend) that carries its parts' `env_ids` and row `slices`."""
 
         def __init__(self, batch, obs_keys=None, info_dicts=True):
+            n = sum(sl.stop - sl.start for sl in batch.slices)
             self.env_id = "mixed(" + ",".join(batch.env_ids) + ")"
             self.task_slices = dict(zip(batch.env_ids, batch.slices))
-            self.goal_env = False
-            self.expert_obs_keys, self._expert_cur = None, None
-            self._cp = self._ik = None
-            if obs_keys is None:
-                self.obs_keys = None
-                self._cols = np.arange(CONST["HRG_OBS_DIM"], dtype=np.int64)
-            else:
-                unknown = [k for k in obs_keys if k not in OBS_COLUMNS]
-                if unknown:
-                    raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(OBS_COLUMNS)}")
-                self.obs_keys = list(obs_keys)
-                self._cols = np.array([c for k in obs_keys for c in OBS_COLUMNS[k]], dtype=np.int64)
-            self._backend = _MixedBackend(batch)
-            _VecEnvBase.__init__(self, batch.n, _Box(-np.inf, np.inf, shape=(len(self._cols),), dtype=np.float32),
-                                 _Box(-1.0, 1.0, shape=(CONST["HRG_ACT_DIM"],), dtype=np.float32))
-            self.info_dicts = info_dicts
-            self._ep_ret = np.zeros(batch.n, np.float64)
-            self._ep_len = np.zeros(batch.n, np.int64)
-            self._t_start = time.time()
-            self._actions = None
-            self._last_full = None
             self._task_of_row = [eid for eid, sl in zip(batch.env_ids, batch.slices) for _ in range(sl.stop - sl.start)]
+            self._init_dataset()    # the steps of HipVecEnv.__init__, without the per-task wrappers: no dataset, no expert, no action front-end
+            self._init_expert()
+            self._init_columns(obs_keys, OBS_COLUMNS)
+            self._backend = batch if hasattr(batch, "step_async") else _TorchBackend(batch=batch)
+            self._init_spaces(n)
+            self._init_accounting(n, info_dicts)
+            self._init_obs_norm()
+            self._init_monitor()
 
-        def _make_infos(self, info, dones, term_obs):
-            infos = super()._make_infos(info, dones, term_obs)
+        def _make_infos(self, info, dones, term_obs, sir=None):
+            infos = super()._make_infos(info, dones, term_obs, sir)
             for d, task in zip(infos, self._task_of_row):
                 dict.__setitem__(d, "task", task)   # (not d[...] = ...: that would fill the lazy rows)
             return infos

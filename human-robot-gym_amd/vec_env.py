@@ -82,8 +82,9 @@ STACKING_OBS_KEYS = ["object_gripped", "vec_eef_to_all_objects", "gripper_apertu
 LIFTING_OBS_KEYS = ["board_quat", "dist_eef_to_human_head", "vec_eef_to_human_lh", "vec_eef_to_human_rh"]   # CL-SAC.yaml run.obs_keys
 HAMMERING_OBS_KEYS = ["hammer_gripped", "vec_eef_to_nail", "nail_hammering_progress", "vec_eef_to_board", "board_quat", "dist_eef_to_human_head", "dist_eef_to_human_lh",
                       "dist_eef_to_human_rh"]   # no run config ships for this task; the expert reads vec_eef_to_nail (collaborative_hammering_cart_expert.py:24-25)
-DEFAULT_OBS_KEYS = {k: (HAMMERING_OBS_KEYS if k == "CollaborativeHammeringCart" else OBS_KEYS if k == "ReachHuman" else (LIFTING_OBS_KEYS if k == "CollaborativeLiftingCart" else (STACKING_OBS_KEYS if k == "CollaborativeStackingCart" else PICK_PLACE_OBS_KEYS)))
-                    for k in ENV_DEFAULTS}
+_TASK_OBS_KEYS = {"ReachHuman": OBS_KEYS, "CollaborativeLiftingCart": LIFTING_OBS_KEYS, "CollaborativeStackingCart": STACKING_OBS_KEYS,
+                  "CollaborativeHammeringCart": HAMMERING_OBS_KEYS}
+DEFAULT_OBS_KEYS = {k: _TASK_OBS_KEYS.get(k, PICK_PLACE_OBS_KEYS) for k in ENV_DEFAULTS}   # the pick-place, inspection and handover tasks: the pick-place keys
 # columns of the kernel's observation superset (include/hrgym.h HRG_OBS_DIM) per robosuite observable / modality key
 OBS_COLUMNS = {
     "object-state": range(0, 12), "goal_difference": range(12, 18), "robot0_joint_pos": range(18, 24),
@@ -125,19 +126,29 @@ for _k in ("hammer_quat", "hammer_gripped", "vec_eef_to_hammer", "vec_eef_to_nai
 OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (hammering overrides it with its constant zeros)
 
 
+def task_columns(env_id):
+    """OBS_COLUMNS as `env_id` fills them."""
+    cols_of = dict(OBS_COLUMNS)
+    if env_id != "ReachHuman":
+        cols_of["desired_goal"] = OBS_COLUMNS["target_pos"]   # _get_desired_goal_from_obs of the cube tasks
+    cols_of.update(OBS_COLUMNS_TASK.get(env_id, {}))
+    return cols_of
+
+
 # ActionBasedExpertImitationRewardWrapper._add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130): on the infos of done steps
 IMITATION_INFO_KEYS = ("ep_im_rew_mean", "ep_env_rew_mean", "ep_full_rew_mean", "im_rew_mean", "env_rew_mean", "full_rew_mean")
 # PickPlaceHumanCartStateBasedExpertImitationRewardWrapper._add_reward_to_info (state_based_expert_imitation_reward_wrapper.py:529-540) adds four more
 STATE_IMITATION_PP_INFO_KEYS = ("ep_m_im_rew_mean", "ep_g_im_rew_mean", "m_im_rew_mean", "g_im_rew_mean")
 # what SB3's rollout loops (and the reference's logging callback, for the imitation keys) look up on every info: stored eagerly where they exist
-_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated") + IMITATION_INFO_KEYS + STATE_IMITATION_PP_INFO_KEYS)
+# (and "task", which a mixed batch stores on every info: reading it must not fill the row)
+_EAGER_KEYS = frozenset(("terminal_observation", "episode", "TimeLimit.truncated", "task") + IMITATION_INFO_KEYS + STATE_IMITATION_PP_INFO_KEYS)
 
 
 class LazyInfo(dict):
     """Per-env info dict whose kernel-derived entries (INFO_KEYS, "action", the expert observations) are filled in on first use.
 
     SB3's collect loops only `.get()` "episode" / "terminal_observation" / "TimeLimit.truncated" on every info of every step; those
-    are stored eagerly, so a 4096-env step does not pay for 4096 x 15 dict entries nobody reads.  Any other access (indexing, `in`,
+    (with the imitation reward means of done steps and a mixed batch's "task": _EAGER_KEYS) are stored eagerly where they exist, so a 4096-env step does not pay for 4096 x 15 dict entries nobody reads.  Any other access (indexing, `in`,
     iteration, `len`, `==`, `dict(info)`, copy / pickle) materialises the row first; afterwards the object is an ordinary dict."""
     __slots__ = ("_src", "_i")
 
@@ -207,24 +218,25 @@ class _InfoSource:
 
 
 class _TorchBackend:
-    """numpy <-> HipBatch adapter: one H2D copy of the actions, one D2H copy of the packed output block per step."""
+    """numpy <-> HipBatch / mixed.MixedBatch adapter: one H2D copy of the actions, one D2H copy of the packed output block per step.
 
-    def __init__(self, desc, clips, n_envs, env_id0, device):
+    The backend protocol `HipVecEnv` relies on (tests/helpers.OracleBackend is its second implementation):
+      required  reset() -> obs [n, HRG_OBS_DIM];  step_async(actions float64 [n, HRG_ACT_DIM]);  step_wait() -> (obs, term_obs, reward, done, info), arrays
+                that stay valid until the next step;  executed_actions() -> the action rows as the kernel left them;  close()
+      optional  batch (the device batch: state access, collision checks, the dataset collector);  attach_expert(desc) / expert_actions();
+                attach_dataset(dataset, rsi_prob, state_imitation_reward, seed);  imit / sir (host rows of the last step, None until attached);
+                reset_time (after a dataset reset);  reseed(desc) (for seed(); this backend is rebuilt instead)"""
+
+    def __init__(self, desc=None, clips=None, n_envs=None, env_id0=0, device=0, batch=None):
         import torch
         from ._lib import HipBatch
+        from .dist import packed_views
         self.torch = torch
-        self.batch = HipBatch(desc, clips, n_envs, env_id0=env_id0, device=device)
-        self.n = n_envs
-        lay = self.batch.packed_layout
+        self.batch = batch if batch is not None else HipBatch(desc, clips, n_envs, env_id0=env_id0, device=device)
+        self.n = self.batch.n
         self._host = torch.empty(self.batch.packed.numel(), dtype=torch.uint8, pin_memory=True)
-        o, s = lay["offsets"], lay["sizes"]
-        hb = self._host.numpy()
-        od, idim = CONST["HRG_OBS_DIM"], CONST["HRG_INFO_DIM"]
-        self.obs = hb[o[0]:o[0] + s[0]].view(np.float32).reshape(n_envs, od)
-        self.term_obs = hb[o[1]:o[1] + s[1]].view(np.float32).reshape(n_envs, od)
-        self.reward = hb[o[2]:o[2] + s[2]].view(np.float32)
-        self.info = hb[o[3]:o[3] + s[3]].view(np.int32).reshape(n_envs, idim)
-        self.done = hb[o[4]:o[4] + s[4]]
+        v = packed_views(self._host.numpy(), self.n)
+        self.obs, self.term_obs, self.reward, self.info, self.done = v["obs"], v["term_obs"], v["reward"], v["info"], v["done"]
         self.imit = None   # host copy of the imitation rows, once an expert with a reward is attached
         self.sir = None    # host copy of the state imitation rows, once a dataset is attached
 
@@ -286,93 +298,20 @@ class HipVecEnv(_VecEnvBase):
     Args mirror the reference factory (`utils/env_util_SB3.py:19-87`): `env_kwargs` is the dict composed at
     `utils/training_utils.py:71-88`; `seed` plays the role of `seed + rank` (per-env streams are keyed by the
     global env id, so sharding does not change results)."""
-    _norm = None      # (mean, std, squash_factor) of DatasetObsNormWrapper, when configured
-    _monitor = None   # open Monitor csv, when monitor_dir is given
-    _monitor_keys = ()
-    _info_keys = INFO_KEYS   # names of the info columns (a task may rename its task-specific column: INFO_KEY_ALIASES)
-    _expert_desc = None   # hrg_expert_desc of the attached scripted expert
-    _imit_alpha = None    # alpha of the imitation reward, when one is configured
-    _dataset = None       # the attached demonstration dataset (dataset.ExpertDataset)
-    _sir = None           # arguments of the state imitation reward (dataset.sir_kwargs), when one is configured
-    _observe_time = False  # the state imitation reward appends its time column to the observation
-
     def __init__(self, n_envs=1, env_id="ReachHuman", env_kwargs=None, obs_keys=None, seed=None, clips=None,
                  device=0, env_id0=0, backend=None, info_dicts=True, collision_prevention=None, goal_check=True, ik_position_delta=None,
                  expert_obs_keys=None, goal_env=False, obs_norm=None, monitor_dir=None, monitor_kwargs=None, reach_box=False, robot_geometry="capsule",
                  expert=None, imitation_reward=None, dataset=None, rsi_prob=None, state_imitation_reward=None):
         if env_id not in ENV_DEFAULTS:
             raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)} (DESIGN.md §6)")
-        # dataset: a name (datasets/<name>/hrg_dataset.npz) or a loaded dataset.ExpertDataset: every episode starts from a state of the dataset
-        # (DatasetRSIWrapper: a random state with probability rsi_prob, otherwise an episode's first); state_imitation_reward: dict(alpha, beta,
-        # iota | iota_m, iota_g, sim_fn | m_sim_fn, g_sim_fn, observe_time, use_et, et_dist) = config.wrappers.state_based_expert_imitation_reward:
-        # the step reward becomes r_im alpha + r_env (1 - alpha), r_im from the demonstration state of the same step (csrc/hrgym_dataset.h)
-        if dataset is None and (rsi_prob is not None or state_imitation_reward is not None):
-            raise ValueError("rsi_prob / state_imitation_reward need a dataset (the reference's wrappers load one by dataset_name)")
-        if dataset is not None:
-            from .dataset import NO_DATASET_ENVS, ExpertDataset, sir_kwargs
-            if backend is not None:
-                raise NotImplementedError("dataset / state_imitation_reward: the restore and reward kernels run in the HIP library; another backend has none")
-            if goal_env:
-                raise NotImplementedError("dataset / state_imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
-            if env_id in NO_DATASET_ENVS:
-                raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
-            if state_imitation_reward is not None and imitation_reward is not None:
-                raise NotImplementedError("state_imitation_reward with imitation_reward: the reference wraps one imitation reward, state based or action based")
-            has_box = env_id != "ReachHuman" or bool(reach_box)
-            if not isinstance(dataset, ExpertDataset):
-                dataset = ExpertDataset.load(dataset, env_id=env_id, has_box=has_box)
-            elif dataset.env_id != env_id or (dataset.boxes is not None) != has_box:
-                raise ValueError(f"dataset of {dataset.env_id} ({'with' if dataset.boxes is not None else 'without'} box array) for {env_id}")
-            if state_imitation_reward is not None:
-                if reach_box:
-                    raise NotImplementedError("state_imitation_reward with reach_box: the cube kernel serves object_quat in the goal_difference columns")
-                self._sir = sir_kwargs(env_id, state_imitation_reward)
-                self._observe_time = self._sir["observe_time"]
-            self._dataset = dataset
-        # expert: dict(id=..., signal_to_noise_ratio=..., ...) = config.expert (a scripted expert of demonstrations/experts/, evaluated on the device:
-        # env.expert_actions()); imitation_reward: dict(alpha, beta, iota_m, iota_g, m_sim_fn, g_sim_fn, normalize_joint_actions) =
-        # config.wrappers.action_based_expert_imitation_reward: the step reward becomes r_im alpha + r_env (1 - alpha) (csrc/hrgym_expert.h)
-        if imitation_reward is not None and expert is None:
-            raise ValueError("imitation_reward needs an expert (the reference asserts: No expert specified in config!)")
-        if expert is not None:
-            from .expert import EXPERT_ENVS, expert_kwargs
-            if backend is not None:
-                raise NotImplementedError("expert / imitation_reward: the experts run in the HIP library; another backend has none")
-            if goal_env:
-                raise NotImplementedError("expert / imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
-            eid, _ = expert_kwargs(expert)
-            if env_id not in EXPERT_ENVS[eid] or reach_box:
-                raise NotImplementedError(f"expert {eid}: it reads the observation of {EXPERT_ENVS[eid]}, not of {env_id}")
         self.env_id = env_id
-        self._info_keys = [INFO_KEY_ALIASES.get(env_id, {}).get(k, k) for k in INFO_KEYS]
-        # GoalEnvironmentGymWrapper (wrappers/goal_env_wrapper.py): dict observations {observation, achieved_goal, desired_goal} and an
-        # externalised reward for hindsight relabelling.  Goals per task: ReachHuman joint angles (reach_human_env.py:477-507),
-        # the cube tasks [eef_pos, object_pos, object_gripped] vs target_pos (pick_place_human_cartesian_env.py:574-611)
-        self.goal_env = bool(goal_env)
-        if self.goal_env:
-            if env_id in ("HumanObjectInspectionCart", "CollaborativeLiftingCart", "CollaborativeStackingCart", "CollaborativeHammeringCart"):
-                raise NotImplementedError("goal_env: this task's success is a task phase, not a function of the goals")
-            if obs_keys is None:  # goal_env_wrapper.py:62-71
-                obs_keys = ["object-state", "robot0_proprio-state", "desired_goal"]
-            self._ag_cols = np.array(list(range(18, 24)) if env_id == "ReachHuman" else [30, 31, 32, 47, 48, 49, 39], dtype=np.int64)
-            self._dg_cols = np.array(list(range(33, 39)) if env_id == "ReachHuman" else [50, 51, 52], dtype=np.int64)
-        keys = list(obs_keys) if obs_keys is not None else DEFAULT_OBS_KEYS[env_id]
-        unknown = [k for k in keys if k not in OBS_COLUMNS]
-        if unknown:
-            raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(OBS_COLUMNS)}")
-        self.obs_keys = keys
-        # ExpertObsWrapper (wrappers/expert_obs_wrapper.py:155-184): infos carry the expert's view of the state before and after the step
-        bad = [k for k in (expert_obs_keys or []) if k not in OBS_COLUMNS]
-        if bad:
-            raise NotImplementedError(f"expert_obs_keys {bad!r}: available {sorted(OBS_COLUMNS)}")
-        self.expert_obs_keys = list(expert_obs_keys) if expert_obs_keys is not None else None
-        self._expert_cur = None
-        cols_of = dict(OBS_COLUMNS)
-        if env_id != "ReachHuman":
-            cols_of["desired_goal"] = OBS_COLUMNS["target_pos"]   # _get_desired_goal_from_obs of the cube tasks
-        cols_of.update(OBS_COLUMNS_TASK.get(env_id, {}))
-        self._cols_of = cols_of
-        self._cols = np.array([c for k in keys for c in cols_of[k]], dtype=np.int64)  # GymWrapper: concatenate in key order
+        self._reach_box = bool(reach_box)   # ReachHuman with its free smallBox object (stepped by the cube kernel); default: the lean model (DESIGN.md D2)
+        self._robot_geometry = robot_geometry   # "capsule" (default) | "hull": the arm links collide as the convex hulls of their meshes (DESIGN.md D3; every task)
+        self._init_dataset(self._check_dataset(dataset, rsi_prob, state_imitation_reward, imitation_reward, backend, goal_env), rsi_prob, state_imitation_reward)
+        self._check_expert(expert, imitation_reward, backend, goal_env)
+        if goal_env and obs_keys is None:  # goal_env_wrapper.py:62-71
+            obs_keys = ["object-state", "robot0_proprio-state", "desired_goal"]
+        self._init_columns(obs_keys if obs_keys is not None else DEFAULT_OBS_KEYS[env_id], task_columns(env_id), goal_env=goal_env, expert_obs_keys=expert_obs_keys)
         kw = dict(env_kwargs or {})
         if seed is not None:
             kw["seed"] = int(seed)
@@ -381,15 +320,126 @@ class HipVecEnv(_VecEnvBase):
         # collision_prevention: dict(replace_type=0|1|2, n_resamples=20) = config/wrappers/collision_prevention/*.yaml
         # ik_position_delta: dict(action_limit=0.15, x_output_max=1, ...) = config/wrappers/ik_position_delta/*.yaml: actions become
         # [dx, dy, dz, gripper] (IKPositionDeltaWrapper, wrappers/ik_position_delta_wrapper.py), converted in the kernel
-        self._cp, self._goal_check, self._ik = collision_prevention, goal_check, ik_position_delta
-        self._reach_box = bool(reach_box)   # ReachHuman with its free smallBox object (stepped by the cube kernel); default: the lean model
-        self._robot_geometry = robot_geometry   # "capsule" (default) | "hull": the arm links collide as the convex hulls of their meshes (every task)
-        self._desc = build_model_desc(kw, n_clips=self._clips.n_clips, collision_prevention=collision_prevention, goal_check=goal_check, env_id=env_id,
-                                      ik_position_delta=ik_position_delta, reach_box=self._reach_box, robot_geometry=robot_geometry)
+        self._model_args = dict(collision_prevention=collision_prevention, goal_check=goal_check, env_id=env_id, ik_position_delta=ik_position_delta,
+                                reach_box=self._reach_box, robot_geometry=robot_geometry)
+        self._desc = self._compose_desc()
         self._device, self._env_id0 = device, env_id0
+        self._init_expert(expert, imitation_reward)
         if backend is not None and (isinstance(backend, type) or not hasattr(backend, "step_async")):   # a factory (desc, clips, n_envs, env_id0) -> backend: the caller cannot build the
             backend = backend(self._desc, self._clips, n_envs, env_id0)    # backend itself when the model description is composed here (create_training_vec_env)
-        self._backend = backend if backend is not None else _TorchBackend(self._desc, self._clips, n_envs, env_id0, device)
+        self._backend = backend if backend is not None else self._build_backend(n_envs)
+        self._init_spaces(n_envs, collision_prevention, ik_position_delta)
+        self._init_accounting(n_envs, info_dicts)
+        self.horizon = int(self._desc.horizon)
+        self._init_obs_norm(obs_norm)
+        self._init_monitor(monitor_dir, monitor_kwargs, n_envs, env_id0)
+
+    # ---- construction, step by step (mixed.MixedHipVecEnv runs the same steps over its own backend) -------------------
+    def _check_dataset(self, dataset, rsi_prob, state_imitation_reward, imitation_reward, backend, goal_env):
+        """dataset: a name (datasets/<name>/hrg_dataset.npz) or a loaded dataset.ExpertDataset: every episode starts from a state of the dataset
+        (DatasetRSIWrapper: a random state with probability rsi_prob, otherwise an episode's first); state_imitation_reward: dict(alpha, beta,
+        iota | iota_m, iota_g, sim_fn | m_sim_fn, g_sim_fn, observe_time, use_et, et_dist) = config.wrappers.state_based_expert_imitation_reward:
+        the step reward becomes r_im alpha + r_env (1 - alpha), r_im from the demonstration state of the same step (csrc/hrgym_dataset.h).
+        Returns the loaded dataset, or None."""
+        if dataset is None:
+            if rsi_prob is not None or state_imitation_reward is not None:
+                raise ValueError("rsi_prob / state_imitation_reward need a dataset (the reference's wrappers load one by dataset_name)")
+            return None
+        from .dataset import NO_DATASET_ENVS, ExpertDataset
+        env_id, has_box = self.env_id, self._has_box
+        if backend is not None:
+            raise NotImplementedError("dataset / state_imitation_reward: the restore and reward kernels run in the HIP library; another backend has none")
+        if goal_env:
+            raise NotImplementedError("dataset / state_imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
+        if env_id in NO_DATASET_ENVS:
+            raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
+        if state_imitation_reward is not None and imitation_reward is not None:
+            raise NotImplementedError("state_imitation_reward with imitation_reward: the reference wraps one imitation reward, state based or action based")
+        if not isinstance(dataset, ExpertDataset):
+            dataset = ExpertDataset.load(dataset, env_id=env_id, has_box=has_box)
+        elif dataset.env_id != env_id or (dataset.boxes is not None) != has_box:
+            raise ValueError(f"dataset of {dataset.env_id} ({'with' if dataset.boxes is not None else 'without'} box array) for {env_id}")
+        if state_imitation_reward is not None and self._reach_box:
+            raise NotImplementedError("state_imitation_reward with reach_box: the cube kernel serves object_quat in the goal_difference columns")
+        return dataset
+
+    def _init_dataset(self, dataset=None, rsi_prob=None, state_imitation_reward=None):
+        self._dataset = dataset      # the attached demonstration dataset (dataset.ExpertDataset)
+        self._sir = None             # arguments of the state imitation reward (dataset.sir_kwargs), when one is configured
+        self._observe_time = False   # the state imitation reward appends its time column to the observation
+        if dataset is not None:
+            self._rsi_prob, self._sir_arg = float(rsi_prob or 0.0), state_imitation_reward
+            if state_imitation_reward is not None:
+                from .dataset import sir_kwargs
+                self._sir = sir_kwargs(self.env_id, state_imitation_reward)
+                self._observe_time = self._sir["observe_time"]
+
+    def _check_expert(self, expert, imitation_reward, backend, goal_env):
+        """expert: dict(id=..., signal_to_noise_ratio=..., ...) = config.expert (a scripted expert of demonstrations/experts/, evaluated on the device:
+        env.expert_actions()); imitation_reward: dict(alpha, beta, iota_m, iota_g, m_sim_fn, g_sim_fn, normalize_joint_actions) =
+        config.wrappers.action_based_expert_imitation_reward: the step reward becomes r_im alpha + r_env (1 - alpha) (csrc/hrgym_expert.h)"""
+        if imitation_reward is not None and expert is None:
+            raise ValueError("imitation_reward needs an expert (the reference asserts: No expert specified in config!)")
+        if expert is None:
+            return
+        from .expert import EXPERT_ENVS, expert_kwargs
+        if backend is not None:
+            raise NotImplementedError("expert / imitation_reward: the experts run in the HIP library; another backend has none")
+        if goal_env:
+            raise NotImplementedError("expert / imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
+        eid, _ = expert_kwargs(expert)
+        if self.env_id not in EXPERT_ENVS[eid] or self._reach_box:
+            raise NotImplementedError(f"expert {eid}: it reads the observation of {EXPERT_ENVS[eid]}, not of {self.env_id}")
+
+    def _init_expert(self, expert=None, imitation_reward=None):
+        self._expert_desc = None   # hrg_expert_desc of the attached scripted expert
+        self._imit_alpha = None    # alpha of the imitation reward, when one is configured
+        if expert is not None:
+            from .expert import build_expert_desc
+            # the bounds in FP64 as configured (the f32 action space rounds action_limit = 0.1 to 0.100000001)
+            hi = [1.0] * CONST["HRG_ACT_DIM"] if self._model_args["ik_position_delta"] is None else [float(self._desc.ik_action_limit)] * 3 + [1.0]
+            self._expert_desc = build_expert_desc(expert, [-x for x in hi], hi, imitation_reward, default_seed=int(self._desc.seed))
+            if imitation_reward is not None:
+                self._imit_alpha = float(self._expert_desc.alpha)
+
+    def _init_columns(self, keys, cols_of, goal_env=False, expert_obs_keys=None):
+        """The policy's view of the kernel's observation superset: `keys` concatenated in order (GymWrapper), each looked up in `cols_of`; None: every column."""
+        env_id = self.env_id
+        # GoalEnvironmentGymWrapper (wrappers/goal_env_wrapper.py): dict observations {observation, achieved_goal, desired_goal} and an
+        # externalised reward for hindsight relabelling.  Goals per task: ReachHuman joint angles (reach_human_env.py:477-507),
+        # the cube tasks [eef_pos, object_pos, object_gripped] vs target_pos (pick_place_human_cartesian_env.py:574-611)
+        self.goal_env = bool(goal_env)
+        if self.goal_env:
+            if env_id in ("HumanObjectInspectionCart", "CollaborativeLiftingCart", "CollaborativeStackingCart", "CollaborativeHammeringCart"):
+                raise NotImplementedError("goal_env: this task's success is a task phase, not a function of the goals")
+            self._ag_cols = np.array(list(range(18, 24)) if env_id == "ReachHuman" else [30, 31, 32, 47, 48, 49, 39], dtype=np.int64)
+            self._dg_cols = np.array(list(range(33, 39)) if env_id == "ReachHuman" else [50, 51, 52], dtype=np.int64)
+        unknown = [k for k in keys or [] if k not in OBS_COLUMNS]
+        if unknown:
+            raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(OBS_COLUMNS)}")
+        self.obs_keys = list(keys) if keys is not None else None
+        # ExpertObsWrapper (wrappers/expert_obs_wrapper.py:155-184): infos carry the expert's view of the state before and after the step
+        bad = [k for k in (expert_obs_keys or []) if k not in OBS_COLUMNS]
+        if bad:
+            raise NotImplementedError(f"expert_obs_keys {bad!r}: available {sorted(OBS_COLUMNS)}")
+        self.expert_obs_keys = list(expert_obs_keys) if expert_obs_keys is not None else None
+        self._expert_cur = None
+        self._cols = np.array([c for k in keys for c in cols_of[k]] if keys is not None else range(CONST["HRG_OBS_DIM"]), dtype=np.int64)
+
+    def _compose_desc(self):
+        return build_model_desc(self.env_kwargs, n_clips=self._clips.n_clips, **self._model_args)
+
+    def _build_backend(self, n_envs):
+        """The HIP batch of `self._desc` with the configured expert and dataset attached (construction, and again after seed())."""
+        backend = _TorchBackend(self._desc, self._clips, n_envs, self._env_id0, self._device)
+        if self._expert_desc is not None:
+            backend.attach_expert(self._expert_desc)
+        if self._dataset is not None:
+            backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
+        return backend
+
+    def _init_spaces(self, n_envs, collision_prevention=None, ik_position_delta=None):
+        self._cp, self._ik = collision_prevention, ik_position_delta   # the action front-ends: with either, the kernel rewrites the action rows
         obs_space = _Box(-np.inf, np.inf, shape=(len(self._cols),), dtype=np.float32)
         if self._observe_time:   # _add_time_to_observation_space (state_based_expert_imitation_reward_wrapper.py:202-208): one more value, bound to [0, 1]
             obs_space = _Box(np.concatenate([obs_space.low, [0.0]]).astype(np.float32), np.concatenate([obs_space.high, [1.0]]).astype(np.float32), dtype=np.float32)
@@ -402,56 +452,56 @@ class HipVecEnv(_VecEnvBase):
         else:  # ik_position_delta_wrapper.py:84-88: position delta limits + one gripper dof
             lim = float(self._desc.ik_action_limit)
             act_space = _Box(np.array([-lim] * 3 + [-1.0], np.float32), np.array([lim] * 3 + [1.0], np.float32), dtype=np.float32)
-        super().__init__(n_envs, obs_space, act_space)
-        self._imit_alpha = None
-        if expert is not None:
-            from .expert import build_expert_desc
-            # the bounds in FP64 as configured (the f32 action space rounds action_limit = 0.1 to 0.100000001)
-            hi = [1.0] * CONST["HRG_ACT_DIM"] if ik_position_delta is None else [float(self._desc.ik_action_limit)] * 3 + [1.0]
-            self._expert_desc = build_expert_desc(expert, [-x for x in hi], hi, imitation_reward, default_seed=int(self._desc.seed))
-            self._backend.attach_expert(self._expert_desc)
-            if imitation_reward is not None:
-                self._imit_alpha = float(self._expert_desc.alpha)
-        if self._dataset is not None:
-            self._rsi_prob = float(rsi_prob or 0.0)
-            self._sir_arg = state_imitation_reward
-            self._backend.attach_dataset(self._dataset, self._rsi_prob, state_imitation_reward, int(self._desc.seed))
+        _VecEnvBase.__init__(self, n_envs, obs_space, act_space)
+
+    def _init_accounting(self, n_envs, info_dicts):
         self.info_dicts = info_dicts
+        self._info_keys = [INFO_KEY_ALIASES.get(self.env_id, {}).get(k, k) for k in INFO_KEYS]   # names of the info columns (a task may rename its task-specific one)
         self._ep_ret = np.zeros(n_envs, np.float64)
         self._ep_len = np.zeros(n_envs, np.int64)
         self._t_start = time.time()
         self._actions = None
         self._last_full = None
-        self.horizon = int(self._desc.horizon)
-        # DatasetObsNormWrapper (wrappers/dataset_wrapper.py:160-300): (obs - mean) / std, optionally tanh(squash_factor * .), applied to the policy's
-        # flat observation (and to terminal observations); std == 0 -> 1; shorter / longer statistics are padded / cut when allowed (223-239)
-        self._norm = None
-        if obs_norm is not None:
-            if self.goal_env:
-                raise NotImplementedError("obs_norm with goal_env: the reference normalises flat observations only")
-            mean, std = np.array(obs_norm["mean"], np.float64), np.array(obs_norm["std"], np.float64)
-            k = len(self._cols) + int(self._observe_time)   # the time column is appended inside the normalisation (the imitation wrapper sits below it)
-            if mean.shape != (k,) or std.shape != (k,):
-                if not obs_norm.get("allow_different_observation_shapes", False):
-                    raise ValueError(f"obs_norm: statistics of length {mean.shape[0]} for an observation of length {k} (Environment and dataset observation space do not match!)")
-                mean = np.concatenate([mean, np.zeros(max(0, k - len(mean)))])[:k]
-                std = np.concatenate([std, np.ones(max(0, k - len(std)))])[:k]
-            std[std == 0] = 1
-            self._norm = (mean, std, obs_norm.get("squash_factor"))
-            if self._norm[2] is not None:
-                self.observation_space = _Box(-1.0, 1.0, shape=(k,), dtype=np.float32)
-        # Monitor (SB3 [UPSTREAM]; utils/env_util_SB3.py:60-66 gives every worker <monitor_dir>/<rank>.monitor.csv): ONE csv for the batch, same header and
-        # r,l,t rows (+ info_keywords columns), which stable_baselines3.common.monitor.load_results() reads like any other *.monitor.csv
-        self._monitor = None
-        if monitor_dir is not None:
-            import json
-            os.makedirs(monitor_dir, exist_ok=True)
-            self._monitor_keys = tuple((monitor_kwargs or {}).get("info_keywords", ()))
-            path = os.path.join(monitor_dir, f"hip_batch_{int(env_id0)}.monitor.csv")
-            self._monitor = open(path, "w", newline="")
-            self._monitor.write("#" + json.dumps({"t_start": self._t_start, "env_id": env_id, "n_envs": int(n_envs)}) + "\n")
-            self._monitor.write(",".join(("r", "l", "t") + self._monitor_keys) + "\n")
-            self._monitor.flush()
+
+    def _init_obs_norm(self, obs_norm=None):
+        """DatasetObsNormWrapper (wrappers/dataset_wrapper.py:160-300): (obs - mean) / std, optionally tanh(squash_factor * .), applied to the policy's
+        flat observation (and to terminal observations); std == 0 -> 1; shorter / longer statistics are padded / cut when allowed (223-239)"""
+        self._norm = None   # (mean, std, squash_factor), when configured
+        if obs_norm is None:
+            return
+        if self.goal_env:
+            raise NotImplementedError("obs_norm with goal_env: the reference normalises flat observations only")
+        mean, std = np.array(obs_norm["mean"], np.float64), np.array(obs_norm["std"], np.float64)
+        k = len(self._cols) + int(self._observe_time)   # the time column is appended inside the normalisation (the imitation wrapper sits below it)
+        if mean.shape != (k,) or std.shape != (k,):
+            if not obs_norm.get("allow_different_observation_shapes", False):
+                raise ValueError(f"obs_norm: statistics of length {mean.shape[0]} for an observation of length {k} (Environment and dataset observation space do not match!)")
+            mean = np.concatenate([mean, np.zeros(max(0, k - len(mean)))])[:k]
+            std = np.concatenate([std, np.ones(max(0, k - len(std)))])[:k]
+        std[std == 0] = 1
+        self._norm = (mean, std, obs_norm.get("squash_factor"))
+        if self._norm[2] is not None:
+            self.observation_space = _Box(-1.0, 1.0, shape=(k,), dtype=np.float32)
+
+    def _init_monitor(self, monitor_dir=None, monitor_kwargs=None, n_envs=None, env_id0=0):
+        """Monitor (SB3 [UPSTREAM]; utils/env_util_SB3.py:60-66 gives every worker <monitor_dir>/<rank>.monitor.csv): ONE csv for the batch, same header and
+        r,l,t rows (+ info_keywords columns), which stable_baselines3.common.monitor.load_results() reads like any other *.monitor.csv"""
+        self._monitor, self._monitor_keys = None, ()   # the open csv, when monitor_dir is given
+        if monitor_dir is None:
+            return
+        import json
+        os.makedirs(monitor_dir, exist_ok=True)
+        self._monitor_keys = tuple((monitor_kwargs or {}).get("info_keywords", ()))
+        path = os.path.join(monitor_dir, f"hip_batch_{int(env_id0)}.monitor.csv")
+        self._monitor = open(path, "w", newline="")
+        self._monitor.write("#" + json.dumps({"t_start": self._t_start, "env_id": self.env_id, "n_envs": int(n_envs)}) + "\n")
+        self._monitor.write(",".join(("r", "l", "t") + self._monitor_keys) + "\n")
+        self._monitor.flush()
+
+    @property
+    def _has_box(self):
+        """Does an env carry the object block (hrg_box_state)?  Every task but the lean ReachHuman (with reach_box it does too)."""
+        return self._reach_box or self.env_id != "ReachHuman"
 
     # ---- VecEnv API -------------------------------------------------------------------------------------
     def reset(self):
@@ -479,7 +529,6 @@ class HipVecEnv(_VecEnvBase):
         sir = np.array(self._backend.sir, copy=True) if self._dataset is not None else None
         obs, reward = self._view(full, sir[:, CONST["HRG_SIR_TIME_OBS"]] if self._observe_time else None), np.array(reward, copy=True)
         dones = np.asarray(done).astype(bool)   # (with early termination: where the episode ended for either reason)
-        self._step_sir = sir
         imit = None
         if self._sir is not None:   # as below: Monitor sits inside the imitation wrapper, its return is r_env (it does not see ET in the reference; here an
             self._ep_ret += sir[:, CONST["HRG_SIR_R_ENV"]]   # ET step ends the Monitor episode like any other done: DESIGN.md deviations)
@@ -492,7 +541,7 @@ class HipVecEnv(_VecEnvBase):
         if (self._cp is not None or self._ik is not None) and self.info_dicts:
             self._actions = np.array(self._backend.executed_actions(), copy=True)
         if self.info_dicts:
-            infos = self._make_infos(info, dones, term_obs)
+            infos = self._make_infos(info, dones, term_obs, sir)
             if imit is not None:
                 self._imitation_infos(infos, imit, np.nonzero(dones)[0])
             if self._sir is not None:
@@ -507,10 +556,9 @@ class HipVecEnv(_VecEnvBase):
         self._ep_len[dones] = 0
         return obs, reward, dones, infos
 
-    def _make_infos(self, info, dones, term_obs):
-        # the per-env dicts are filled from a copy of the info block on first use (LazyInfo)
+    def _make_infos(self, info, dones, term_obs, sir=None):
+        # the per-env dicts are filled from a copy of the info block on first use (LazyInfo); `sir`: the step's state imitation rows, with a dataset
         info = np.array(info, copy=True)
-        sir = getattr(self, "_step_sir", None)
         src = _InfoSource(info, self._actions, self.expert_obs_keys, self._expert_cur, np.array(term_obs, copy=True) if self.expert_obs_keys is not None else None,
                           keys=self._info_keys, early=sir[:, CONST["HRG_SIR_EARLY"]] if self._sir is not None and self._sir["use_et"] else None)
         n = self.num_envs
@@ -533,37 +581,31 @@ class HipVecEnv(_VecEnvBase):
                 self._monitor_rows(info, idx, now)
         return infos
 
+    @staticmethod
+    def _reward_means(d, ep_im, ep_env, n, a):
+        """The six entries both _add_reward_to_info write on the info of a done step: episode sums and per-step means of r_im, r_env and their mix by alpha."""
+        set_ = dict.__setitem__
+        set_(d, "ep_im_rew_mean", ep_im)
+        set_(d, "ep_env_rew_mean", ep_env)
+        set_(d, "ep_full_rew_mean", ep_im * a + ep_env * (1 - a))
+        set_(d, "im_rew_mean", ep_im / n)
+        set_(d, "env_rew_mean", ep_env / n)
+        set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+
     def _imitation_infos(self, infos, imit, idx):
         """_add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130) from the imitation rows of the envs that finished an episode."""
-        a = self._imit_alpha
-        set_ = dict.__setitem__
         for i in idx.tolist():
-            ep_im, ep_env, n = float(imit[i, 4]), float(imit[i, 5]), float(imit[i, 6])
-            d = infos[i]
-            set_(d, "ep_im_rew_mean", ep_im)
-            set_(d, "ep_env_rew_mean", ep_env)
-            set_(d, "ep_full_rew_mean", ep_im * a + ep_env * (1 - a))
-            set_(d, "im_rew_mean", ep_im / n)
-            set_(d, "env_rew_mean", ep_env / n)
-            set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+            self._reward_means(infos[i], float(imit[i, 4]), float(imit[i, 5]), float(imit[i, 6]), self._imit_alpha)
 
     def _state_imitation_infos(self, infos, sir, idx):
         """_add_reward_to_info of the state-based wrappers (state_based_expert_imitation_reward_wrapper.py:176-200, 529-540) from the rows of the envs that
         finished an episode; the pick-place means divide by the steps that entered the motion / gripper sums (535)."""
-        a = self._sir["alpha"]
         C = CONST
         pp = self._backend.batch.dataset_desc.sir_kind == C["HRG_SIR_PICK_PLACE"]
         set_ = dict.__setitem__
         for i in idx.tolist():
-            row = sir[i]
-            ep_im, ep_env, n = float(row[C["HRG_SIR_EP_IM"]]), float(row[C["HRG_SIR_EP_ENV"]]), float(row[C["HRG_SIR_EP_LEN"]])
-            d = infos[i]
-            set_(d, "ep_im_rew_mean", ep_im)
-            set_(d, "ep_env_rew_mean", ep_env)
-            set_(d, "ep_full_rew_mean", ep_im * a + ep_env * (1 - a))
-            set_(d, "im_rew_mean", ep_im / n)
-            set_(d, "env_rew_mean", ep_env / n)
-            set_(d, "full_rew_mean", (ep_im / n) * a + (ep_env / n) * (1 - a))
+            row, d = sir[i], infos[i]
+            self._reward_means(d, float(row[C["HRG_SIR_EP_IM"]]), float(row[C["HRG_SIR_EP_ENV"]]), float(row[C["HRG_SIR_EP_LEN"]]), self._sir["alpha"])
             if pp:
                 ep_m, ep_g, n_mg = float(row[C["HRG_SIR_EP_MOTION"]]), float(row[C["HRG_SIR_EP_GRIPPER"]]), float(row[C["HRG_SIR_EP_LEN_MG"]])
                 set_(d, "ep_m_im_rew_mean", ep_m)
@@ -598,7 +640,7 @@ class HipVecEnv(_VecEnvBase):
         self._monitor.flush()
 
     def close(self):
-        if getattr(self, "_monitor", None) is not None:
+        if self._monitor is not None:
             self._monitor.close()
             self._monitor = None
         self._backend.close()
@@ -608,15 +650,10 @@ class HipVecEnv(_VecEnvBase):
         if seed is None:
             return [None] * self.num_envs
         self.env_kwargs["seed"] = int(seed)
-        self._desc = build_model_desc(self.env_kwargs, n_clips=self._clips.n_clips, collision_prevention=self._cp, goal_check=self._goal_check,
-                                      env_id=self.env_id, ik_position_delta=self._ik, reach_box=self._reach_box, robot_geometry=self._robot_geometry)
+        self._desc = self._compose_desc()
         if isinstance(self._backend, _TorchBackend):
             self._backend.close()
-            self._backend = _TorchBackend(self._desc, self._clips, self.num_envs, self._env_id0, self._device)
-            if self._expert_desc is not None:
-                self._backend.attach_expert(self._expert_desc)
-            if self._dataset is not None:
-                self._backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
+            self._backend = self._build_backend(self.num_envs)
         else:
             self._backend.reseed(self._desc)
         return [int(seed) + i for i in range(self.num_envs)]
@@ -633,23 +670,25 @@ class HipVecEnv(_VecEnvBase):
 
     # HumanEnv.get_environment_state / set_environment_state (human_env.py:1845-1900; used by the dataset / reference-state-initialisation wrappers):
     # the stepper's state blocks, batched.  Each entry is (hrg_env_state, hrg_box_state or None); a restored episode keeps its own random streams.
-    def get_environment_state(self, indices=None):
+    def _hip_batch(self, method, what):
         batch = getattr(self._backend, "batch", None)
-        if batch is None or not hasattr(batch, "get_states"):
-            raise NotImplementedError("get_environment_state needs the HIP batch backend")
+        if batch is None or not hasattr(batch, method):
+            raise NotImplementedError(f"{what} needs the HIP batch backend")
+        return batch
+
+    def get_environment_state(self, indices=None):
+        batch = self._hip_batch("get_states", "get_environment_state")
         idx = self._indices(indices)
         states, boxes = batch.get_states(np.asarray(idx, np.int32))
         if self.env_id == "CollaborativeStackingCart":   # CollaborativeStackingEnvState (collaborative_stacking_cartesian_env.py:63-97): the four cubes + stack bookkeeping
             return [(st, batch.get_stack(i)) for st, i in zip(states, idx)]
         if self.env_id == "CollaborativeHammeringCart":  # CollaborativeHammeringEnvState (collaborative_hammering_cartesian_env.py:56-89): board, hammer, nail + bookkeeping
             return [(st, batch.get_hammer(i)) for st, i in zip(states, idx)]
-        has_box = self._reach_box or self.env_id != "ReachHuman"   # ReachHuman with its smallBox carries the object block too
+        has_box = self._has_box
         return [(st, boxes[k] if has_box else None) for k, st in enumerate(states)]
 
     def set_environment_state(self, states, indices=None):
-        batch = getattr(self._backend, "batch", None)
-        if batch is None or not hasattr(batch, "set_states"):
-            raise NotImplementedError("set_environment_state needs the HIP batch backend")
+        batch = self._hip_batch("set_states", "set_environment_state")
         idx = self._indices(indices)
         if len(states) != len(idx):
             raise ValueError(f"{len(states)} states for {len(idx)} envs")
@@ -661,15 +700,13 @@ class HipVecEnv(_VecEnvBase):
                 (batch.set_stack if self.env_id == "CollaborativeStackingCart" else batch.set_hammer)(i, sk)
             return
         boxes = [b for _, b in states]
-        bx_arr = (BoxState * len(idx))(*boxes) if all(b is not None for b in boxes) and (self._reach_box or self.env_id != "ReachHuman") else None
+        bx_arr = (BoxState * len(idx))(*boxes) if all(b is not None for b in boxes) and self._has_box else None
         batch.set_states(np.asarray(idx, np.int32), st_arr, bx_arr)
 
     def check_collision_action(self, actions):
         """HumanEnv.check_collision_action (human_env.py:588-627) for every env: bool array, True where the joint-space action would drive the robot
         into the static scene or itself.  Nothing is stepped."""
-        batch = getattr(self._backend, "batch", None)
-        if batch is None or not hasattr(batch, "check_actions"):
-            raise NotImplementedError("check_collision_action needs the HIP batch backend")
+        batch = self._hip_batch("check_actions", "check_collision_action")
         a = np.asarray(actions, np.float64).reshape(self.num_envs, CONST["HRG_ACT_DIM"])
         import torch
         return batch.check_actions(torch.from_numpy(np.ascontiguousarray(a))).cpu().numpy().astype(bool)
@@ -684,7 +721,7 @@ class HipVecEnv(_VecEnvBase):
             v = full[..., self._cols]
             if time is not None:
                 v = np.concatenate([v, np.asarray(time, np.float32)[..., None]], axis=-1)
-            if getattr(self, "_norm", None) is not None:
+            if self._norm is not None:
                 mean, std, squash = self._norm
                 v = (v - mean) / std
                 if squash is not None:

@@ -367,6 +367,45 @@ def test_infos_and_time_column_through_the_vec_env():
     env.close()
 
 
+def test_step_entries_coerce_their_actions_alike():
+    """The three step entries share one routine (HipBatch._step): float64 contiguous actions and the same values as a float32, non-contiguous tensor give
+    byte-identical packed blocks, imitation rows and state imitation rows through hrg_batch_step, _step_imitation and _step_dataset; a [4, 6] tensor raises
+    from each of them before anything is launched (the block is untouched)."""
+    import torch
+    from human_robot_gym_amd._lib import HipBatch
+    from human_robot_gym_amd.expert import build_expert_desc
+    n, ds = 4, _dataset("ReachHuman")
+    batches = []
+    for _ in range(2):
+        clips = _clips("ReachHuman")
+        desc = hrg.build_model_desc(dict(shield_type="SSM", horizon=5, seed=SEED), n_clips=clips.n_clips, env_id="ReachHuman")
+        B = HipBatch(desc, clips, n)
+        B.attach_expert(build_expert_desc(dict(id="ReachHuman", seed=7), [-1.0] * 7, [1.0] * 7, dict(alpha=0.25, beta=0.7, iota_m=0.1, iota_g=0.5, m_sim_fn="gaussian", g_sim_fn="tanh")))
+        B.attach_dataset(ds, rsi_prob=0.5, state_imitation_reward=dict(alpha=0.4, iota=0.1, sim_fn="gaussian"), seed=9)
+        B.dataset_reset()
+        batches.append(B)
+    A, B = batches
+    rng = np.random.RandomState(6)
+    raw = lambda t: t.cpu().numpy().tobytes()      # noqa: E731
+    for entry in ("step", "step_imitation", "step_dataset"):
+        a32 = rng.uniform(-1, 1, (n, 7)).astype(np.float32)            # drawn as float32: the cast to float64 is exact
+        wide = torch.zeros(n, 14, dtype=torch.float32, device="cuda")
+        wide[:, ::2] = torch.from_numpy(a32).cuda()
+        conforming, other = torch.from_numpy(a32.astype(np.float64)).cuda(), wide[:, ::2]
+        assert conforming.is_contiguous() and not other.is_contiguous() and other.dtype == torch.float32
+        getattr(A, entry)(conforming)
+        getattr(B, entry)(other)
+        torch.cuda.synchronize()
+        assert raw(A.packed) == raw(B.packed) and raw(A.imit) == raw(B.imit) and raw(A.sir) == raw(B.sir), entry
+        before = raw(A.packed)
+        with pytest.raises(ValueError, match=r"actions must be \[4, 7\]"):
+            getattr(A, entry)(torch.zeros(n, 6, dtype=torch.float64, device="cuda"))
+        torch.cuda.synchronize()
+        assert raw(A.packed) == before, entry
+    assert np.any(A.imit.cpu().numpy() != 0) and np.any(A.sir.cpu().numpy() != 0)      # the imitation and dataset entries wrote their rows
+    A.close(); B.close()
+
+
 def test_collected_dataset_replays_bit_for_bit(tmp_path, monkeypatch):
     """The loop closed: collect (ReachHuman, shield off), save, load, replay every episode's recorded actions from its first recorded state: the recorded
     observation rows come back bit for bit.  Statistics files are written next to the dataset."""

@@ -36,6 +36,29 @@ def test_packed_layout_matches_hip_batch_layout():
     assert "term_obs" not in head and (head["info"] == u["info"]).all() and (head["done"] == u["done"]).all() and u["term_obs"].shape == (4096, od)
 
 
+@pytest.mark.parametrize("n", [1, 5, 4096])
+def test_packed_views_of_numpy_and_torch_blocks(n):
+    """dist.packed_views, the one place the block is sliced: the same bytes as a numpy array and as a CPU torch tensor give equal typed views, which are the
+    explicit slices by packed_layout's offsets; a block that is only the published head has no term_obs."""
+    import torch
+    lay = hdist.packed_layout(n)
+    blk = np.random.RandomState(n).randint(0, 256, lay["total"]).astype(np.uint8)
+    vn, vt = hdist.packed_views(blk, n), hdist.packed_views(torch.from_numpy(blk.copy()), n)
+    od, idim = CONST["HRG_OBS_DIM"], CONST["HRG_INFO_DIM"]
+    want = dict(obs=(0, np.float32, (n, od)), term_obs=(1, np.float32, (n, od)), reward=(2, np.float32, (n,)), info=(3, np.int32, (n, idim)), done=(4, np.uint8, (n,)))
+    assert list(vn) == list(vt) == ["obs", "term_obs", "reward", "info", "done"]
+    for k, (i, dt, shape) in want.items():
+        o, s = lay["offsets"][i], lay["sizes"][i]
+        ref = np.frombuffer(blk[o:o + s].tobytes(), dtype=dt).reshape(shape)
+        for v in (vn[k], vt[k].numpy()):
+            assert v.dtype == dt and v.shape == shape and v.tobytes() == ref.tobytes(), k      # (bytes: the random floats hold NaNs)
+    assert np.shares_memory(vn["info"], blk)                                                   # views, not copies
+    hn, ht = hdist.packed_views(blk[:lay["head"]], n), hdist.packed_views(torch.from_numpy(blk.copy())[:lay["head"]], n)
+    assert list(hn) == list(ht) == ["obs", "reward", "info", "done"]
+    for k in hn:
+        assert hn[k].tobytes() == vn[k].tobytes() == ht[k].numpy().tobytes()
+
+
 def _rollout(lo, hi, steps, env_id="ReachHuman"):
     from oracle.oracle import OracleBatch
     clips = hrg.synthetic_clips(2, seed=0, min_frames=200, max_frames=300, inspection=True)

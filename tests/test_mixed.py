@@ -26,6 +26,67 @@ def test_mixed_batch_fails_loudly_without_a_gpu():
         mixed.make_mixed_batch(8)
 
 
+class _TwoOracles:
+    """Backend protocol over two OracleBackends, rows part by part, with the `env_ids` / `slices` a MixedHipVecEnv reads."""
+
+    def __init__(self, parts, horizon, n_clips):
+        from helpers import OracleBackend
+        self.env_ids, self.slices, self.backends = [], [], []
+        r0 = 0
+        for env_id, k in parts:
+            clips = mixed.task_clips(env_id, n_clips, min_frames=60, max_frames=80)
+            desc = hrg.build_model_desc(dict(mixed.task_env_kwargs(env_id), horizon=horizon, shield_type="SSM", seed=1), n_clips=clips.n_clips, env_id=env_id)
+            self.backends.append(OracleBackend(desc, clips, k, env_id0=r0))
+            self.env_ids.append(env_id)
+            self.slices.append(slice(r0, r0 + k))
+            r0 += k
+
+    def reset(self):
+        return np.concatenate([b.reset() for b in self.backends])
+
+    def step_async(self, actions):
+        for b, sl in zip(self.backends, self.slices):
+            b.step_async(np.ascontiguousarray(actions[sl]))
+
+    def step_wait(self):
+        return tuple(np.concatenate(x) for x in zip(*[b.step_wait() for b in self.backends]))
+
+    def executed_actions(self):
+        return np.concatenate([b.executed_actions() for b in self.backends])
+
+    def close(self):
+        for b in self.backends:
+            b.close()
+
+
+def test_mixed_vec_env_surface_on_the_oracle_backends(oracle_lib):
+    """MixedHipVecEnv over any backend of the protocol: what test_mixed_vec_env_surface asserts on the GPU, row for row, on two CPU oracle batches; and the
+    "task" entry does not materialise the lazy info rows."""
+    env = mixed.MixedHipVecEnv(_TwoOracles([("ReachHuman", 2), ("PickPlaceHumanCart", 2)], horizon=4, n_clips=2))
+    assert env.num_envs == 4 and env.observation_space.shape == (64,) and env.action_space.shape == (7,)
+    assert env.task_slices == {"ReachHuman": slice(0, 2), "PickPlaceHumanCart": slice(2, 4)}
+    obs = env.reset()
+    assert obs.shape == (4, 64) and obs.dtype == np.float32
+    assert np.all(obs[env.task_slices["ReachHuman"], 39:53] == 0)              # cube columns: zero for ReachHuman
+    assert np.any(obs[env.task_slices["PickPlaceHumanCart"], 47:50] != 0)      # object_pos
+    rng = np.random.RandomState(0)
+    n_done = 0
+    for _ in range(6):
+        obs, rew, dones, infos = env.step(rng.uniform(-1, 1, (4, 7)))
+        assert [d["task"] for d in infos] == env.get_attr("task") == ["ReachHuman"] * 2 + ["PickPlaceHumanCart"] * 2
+        assert all(d._src is not None for d in infos)                           # reading "task" left the rows lazy
+        for d, done in zip(infos, dones):
+            assert ("terminal_observation" in d) == bool(done)
+            if done:
+                assert d["terminal_observation"].shape == (64,) and d["episode"]["l"] <= 4
+        n_done += int(dones.sum())
+    assert n_done >= 4                                                          # horizon 4: every env timed out once
+    env.close()
+    env2 = mixed.MixedHipVecEnv(_TwoOracles([("ReachHuman", 2), ("PickPlaceHumanCart", 2)], horizon=4, n_clips=2), obs_keys=["robot0_eef_pos", "dist_eef_to_human_head"])
+    assert env2.reset().shape == (4, 4) and env2.obs_keys == ["robot0_eef_pos", "dist_eef_to_human_head"]
+    env2.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("concurrent,tasks", [(True, "ICRA_TASKS"), (False, "ICRA_TASKS"), (True, "ALL_TASKS")])
 def test_mixed_batch_equals_the_per_task_batches(concurrent, tasks):
