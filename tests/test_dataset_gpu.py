@@ -14,6 +14,7 @@ import sir_ref as R
 from human_robot_gym_amd import dataset as D
 from human_robot_gym_amd._cstruct import CONST, EnvState
 from human_robot_gym_amd.mixed import task_clips, task_env_kwargs
+from helpers import ulps32
 
 pytestmark = pytest.mark.gpu
 
@@ -61,12 +62,6 @@ def _bytes(arr, width):
 def _states(B):
     st, bx = B.get_states(np.arange(B.n, dtype=np.int32))
     return _bytes(st, SB), _bytes(bx, BB), st, bx
-
-
-def _ulps32(got, want):
-    """|got - want| in units of the f32 spacing at want (want: f64 reference, got: f32 from the device)."""
-    w32 = np.asarray(want, np.float64).astype(np.float32)
-    return np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)) / np.spacing(np.maximum(np.abs(w32), np.float32(1e-30))).astype(np.float64)
 
 
 def _actions(rng, env_id, n=N):
@@ -215,7 +210,7 @@ def _rollout(B, ds, env_id, sir, steps, seed, u01, rsi_prob=0.5, dseed=9):
         acc += np.stack([r_im, r_env, r_m, r_g, np.ones(N), counted.astype(np.float64)], axis=1)
         want = {"R_IM": r_im, "R_MOTION": r_m, "R_GRIPPER": r_g, "R_FULL": R.combine(r_im, r_env, p["alpha"]), "EP_IM": acc[:, 0], "EP_ENV": acc[:, 1], "EP_MOTION": acc[:, 2],
                 "EP_GRIPPER": acc[:, 3]}
-        worst = {c: float(_ulps32(srow[ok, C["HRG_SIR_" + c]], w[ok]).max()) for c, w in want.items()}
+        worst = {c: float(ulps32(srow[ok, C["HRG_SIR_" + c]], w[ok]).max()) for c, w in want.items()}
         print(f"[sir] {env_id} step {k}: worst f32 ulps {worst}; early {int(early.sum())} done {int(done.sum())} mismatch {int(R.mismatch(kind, demo, policy).sum())} dropped {int((~ok).sum())}")
         msg = f"{env_id} step {k}"
         assert max(worst.values()) <= 1, msg

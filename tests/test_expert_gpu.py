@@ -12,6 +12,7 @@ import human_robot_gym_amd as hrg
 import expert_ref as R
 from human_robot_gym_amd.expert import build_expert_desc
 from human_robot_gym_amd.mixed import task_clips, task_env_kwargs
+from helpers import ulps32
 
 pytestmark = pytest.mark.gpu
 
@@ -59,12 +60,6 @@ def _fixture_obs(fx, expert, n=None):
     else:
         full[:, 43:46] = fx["hm_vec_eef_to_nail"]
     return full[:n] if n else full
-
-
-def _ulps32(got, want):
-    """|got - want| in units of the f32 spacing at want (want: f64 reference, got: f32 from the device)."""
-    w32 = np.asarray(want, np.float64).astype(np.float32)
-    return np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)) / np.spacing(np.maximum(np.abs(w32), np.float32(1e-30))).astype(np.float64)
 
 
 @pytest.mark.parametrize("expert,key,params", [("ReachHuman", "reach", {}), ("PickPlaceHumanCart", "pp", PP_AIR), ("CollaborativeLiftingCart", "cl", None),
@@ -123,9 +118,9 @@ def _twin_rollout(alpha, n=65, horizon=4, steps=6):
         r_im, r_m, r_g = R.imitation_reward(agent[:, :4], x, rw["beta"], rw["iota_m"], rw["iota_g"], rw["m_sim_fn"], rw["g_sim_fn"])
         ep += np.stack([r_im, r2.astype(np.float64), np.ones(n)], axis=1)
         want = np.stack([r_im, r2.astype(np.float64), r_m, r_g, ep[:, 0], ep[:, 1], ep[:, 2], R.combine(r_im, r2.astype(np.float64), alpha)], axis=1)
-        u = _ulps32(imit, want)
-        print(f"[imitation] alpha {alpha} {msg}: worst f32 ulps per imit column {u.max(axis=0)}; reward {_ulps32(r1, want[:, 7]).max()}; done {int(d1.sum())}")
-        assert u.max() <= 2 and _ulps32(r1, want[:, 7]).max() <= 2, msg
+        u = ulps32(imit, want)
+        print(f"[imitation] alpha {alpha} {msg}: worst f32 ulps per imit column {u.max(axis=0)}; reward {ulps32(r1, want[:, 7]).max()}; done {int(d1.sum())}")
+        assert u.max() <= 2 and ulps32(r1, want[:, 7]).max() <= 2, msg
         assert np.array_equal(imit[:, 7].view(np.uint32), r1.view(np.uint32)), msg
         if k == horizon - 1:
             assert np.all(d1[ep[:, 2] == horizon] != 0) and np.any(ep[:, 2] == horizon), msg   # TimeLimit: the row above carried the finished episode's sums and length

@@ -9,6 +9,7 @@ import pytest
 import human_robot_gym_amd as hrg
 from human_robot_gym_amd._cstruct import CONST
 from human_robot_gym_amd.mixed import task_clips, task_env_kwargs
+from helpers import quat_mat
 
 ENV = "CollaborativeHammeringCart"
 
@@ -20,12 +21,6 @@ def _batch(n=2, clips=None, **kw):
     env_kw.update(kw)
     d = hrg.build_model_desc(env_kw, n_clips=clips.n_clips, env_id=ENV)
     return OracleBatch(d, clips, n), d, clips
-
-
-def _quat2mat(q):
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
 def test_model_constants_follow_the_reference_files():
@@ -84,7 +79,7 @@ def test_reset_puts_board_in_the_hands_and_hammer_in_the_gripper():
     obs = B.reset()
     for e in range(2):
         hm, st = B.get_hammer(e), B.get_state(e)
-        Rb = _quat2mat(hm.quat[0])
+        Rb = quat_mat(hm.quat[0])
         # the weld is satisfied exactly: right grip at the right-hand mocap body; the synthetic human holds the board level, nail side towards the robot
         np.testing.assert_allclose(np.array(hm.pos[0]) + Rb @ np.array(d.hm_anchor[1][:]), hm.mocap_pos[1], atol=1e-12)
         assert Rb[2, 2] > 0.999 and Rb[0, 0] < -0.99
@@ -131,7 +126,7 @@ def test_gripper_holds_the_hammer_and_hammer_contacts_are_whitelisted():
     assert info[0, 1] & CONST["HRG_COL_STATIC"] and info[0, 3] >= 1
     # ... and so is one with the nail head (not white-listed either): the board moved so that the nail sits at a finger bar
     hm, st = B.get_hammer(1), B.get_state(1)
-    Rb = _quat2mat(hm.quat[0])
+    Rb = quat_mat(hm.quat[0])
     nail = Rb @ np.array([hm.nail_xy[0], hm.nail_xy[1], d.hm_nail_z0])
     hm.pos[0][:] = (np.array(st.eef_pos) + [0.0, 0.03, -0.02] - nail).tolist()
     hm.pos[1][:] = [0.3, -0.8, 3.0]                                                      # the hammer out of the way
@@ -187,7 +182,7 @@ def _nail_run(steps, hammer=None, **kw):
     for k in range(12):
         B.step(np.zeros((1, 7)))
     hm = B.get_hammer(0)
-    Rb = _quat2mat(hm.quat[0])
+    Rb = quat_mat(hm.quat[0])
     hm.nail_q = hm.nail_v = 0.0
     top = np.array(hm.pos[0]) + Rb @ np.array([hm.nail_xy[0], hm.nail_xy[1], d.hm_nail_z0 + 0.003])
     hm.vel[1][:] = [0.0] * 6
@@ -196,7 +191,7 @@ def _nail_run(steps, hammer=None, **kw):
     else:
         hm.quat[1][:] = [np.sqrt(0.5), 0, np.sqrt(0.5), 0]
         head = np.array(d.hm_geom_pos[CONST["HRG_HG_HEAD"]][:])
-        Rh = _quat2mat(hm.quat[1])
+        Rh = quat_mat(hm.quat[1])
         gap = 0.0 if hammer == "rest" else 0.01
         hm.pos[1][:] = (top + [0, 0, d.hm_geom_half[CONST["HRG_HG_HEAD"]][0] + gap] - Rh @ head).tolist()
         if hammer != "rest":

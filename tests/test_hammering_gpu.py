@@ -5,50 +5,32 @@ import pytest
 import human_robot_gym_amd as hrg
 from human_robot_gym_amd._cstruct import CONST
 from human_robot_gym_amd.mixed import task_clips, task_env_kwargs
-from helpers import ATOL, RTOL, assert_state_close, record_live
+from helpers import make_pair, quat_mat
+from parity import GEOM_BOX as G0, Run, pose_vectors
 
 pytestmark = pytest.mark.gpu
 ENV = "CollaborativeHammeringCart"
-G0 = 10 + 24 + 2   # GEOM_BOX: robot capsules, human bodies, table, floor
 
 
 def _pair(n, kw, clips=None):
-    from oracle.oracle import OracleBatch
-    from human_robot_gym_amd._lib import HipBatch
-    clips = clips or task_clips(ENV, 3, min_frames=300, max_frames=420)
-    kw = dict(task_env_kwargs(ENV), **kw)
-    mk = lambda: hrg.build_model_desc(kw, n_clips=clips.n_clips, env_id=ENV)  # noqa: E731
-    return OracleBatch(mk(), clips, n), HipBatch(mk(), clips, n), mk()
-
-
-def _quat2mat(q):
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def _bodies(B, e):
-    hm = B.get_hammer(e)
-    return np.array([x for b in range(2) for x in list(hm.pos[b]) + list(hm.quat[b])] + [hm.nail_q])
+    O, G = make_pair(n, kw, clips=clips, task_frames=(300, 420), env_id=ENV)
+    return O, G, O.desc
 
 
 def _rollout(O, G, n, n_steps, seed, resync, name, scenario=None, min_live=0.9, act_scale=1.0, twin=None):
-    """`twin` (resynchronised runs): a second oracle batch that takes every step from the first one's state with the hammer moved by 1e-12 m.  An env whose two oracle
+    """violent here: a violent arm, a crash, a free body that moves at > 3 m/s.  An env-step whose contact list differs at agreeing floats leaves the comparison
+    (parity.Step.drop_flicker: free-running for good, resynchronised for this step), counted in `flicker` and bounded.
+    `twin` (resynchronised runs): a second oracle batch that takes every step from the first one's state with the hammer moved by 1e-12 m.  An env whose two oracle
     results then differ by more than 1e-7 sits on a knife edge of the step itself (a box-box reference face or a noslip bound that flips within the 25 substeps: the
     fuzz scenario throws the hammer into the board at random poses) -- no implementation can be expected to land on the oracle's side of it.  Such env-steps leave the
     comparison, counted in `knife` and bounded."""
-    import torch
-    oo, og = O.reset(), G.reset().cpu().numpy()
+    run = Run(O, G, f"test_hammering_gpu::{name}", free_running=not resync)
     if twin is not None:
         twin.reset()
-    np.testing.assert_allclose(og, oo, rtol=RTOL, atol=ATOL)
-    for e in range(n):
-        assert_state_close(O.get_hammer(e), G.get_hammer(e), f"reset env {e} objects")
-        assert_state_close(O.get_state(e), G.get_state(e), f"reset env {e}")
     rng = np.random.RandomState(seed)
-    live = np.ones(n, bool)
     stats = dict(hammer_contacts=0, box_box=0, nail_contacts=0, phases=set(), max_ncon=0, gripped=0, static=0, flicker=0, knife=0)
-    for k in range(n_steps):
+
+    def actions(k):
         if scenario is not None:
             scenario(k, [O, G])
         a = rng.uniform(-1, 1, (n, 7)) * act_scale
@@ -58,60 +40,31 @@ def _rollout(O, G, n, n_steps, seed, resync, name, scenario=None, min_live=0.9, 
                 hm.pos[1][0] += 1e-12
                 twin.set_state(e, O.get_state(e)); twin.set_hammer(e, hm)
             twin.step(a.copy())
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
-        torch.cuda.synchronize()
-        msg = f"{name} step {k}"
-        post = [O.get_state(e) for e in range(n)]
-        phm = [O.get_hammer(e) for e in range(n)]
-        po, no = O.contacts()
-        # chaotic from then on: a violent arm, a crash, a free body that moves at > 3 m/s
-        violent = np.array([i_o[e, 11] != 0 or max(abs(v) for v in post[e].qvel) > 5.0 or max(abs(v) for b in range(2) for v in phm[e].vel[b][:3]) > 3.0 for e in range(n)])
-        if not resync:
-            live &= ~violent
-        chk = live & ~violent if resync else live
+        return a
+    for s in run.steps(n_steps, actions):
         if twin is not None:
-            knife = np.array([np.abs(_bodies(O, e) - _bodies(twin, e)).max() > 1e-7 for e in range(n)])
-            stats["knife"] += int((chk & knife).sum())
-            chk &= ~knife
-        pg, ng = G.contacts()
-        # a resting contact that carries no load sits at distance zero: whether it is listed is decided by rounding-level state differences.  Such an env leaves
-        # the comparison (free-running: for good, counted in the dropped fraction; resynchronised: for this step, counted in `flicker`) -- but only while its bodies
-        # still agree to 1e-7
-        for e in np.nonzero(chk & ((ng != no) | (pg != po).any((1, 2))))[0]:
-            fo, fg = (np.array([x for b in range(2) for x in list(B.get_hammer(e).pos[b]) + list(B.get_hammer(e).quat[b])] + [B.get_hammer(e).nail_q]) for B in (O, G))
-            assert np.abs(fo - fg).max() < 1e-7, f"{msg} env {e}: contact lists differ and so do the bodies ({np.abs(fo - fg).max():.2e})"
-            chk[e] = False
-            stats["flicker"] += 1
-            if not resync:
-                live[e] = False
-        np.testing.assert_array_equal(ng[chk], no[chk], err_msg=msg)
-        np.testing.assert_array_equal(pg[chk], po[chk], err_msg=msg)
-        np.testing.assert_array_equal(i_g.cpu().numpy()[chk], i_o[chk], err_msg=msg)
-        np.testing.assert_array_equal(d_g.cpu().numpy()[chk], d_o[chk], err_msg=msg)
-        np.testing.assert_allclose(o_g.cpu().numpy()[chk], o_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(r_g.cpu().numpy()[chk], r_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(G.term_obs.cpu().numpy()[chk], O.term_obs[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
+            knife = np.abs(pose_vectors("hammer", s.o.objects) - pose_vectors("hammer", twin.get_states_all(hammer=True)[3])).max(axis=1) > 1e-7
+            stats["knife"] += int((s.chk & knife).sum())
+            s.chk &= ~knife
+        s.drop_flicker()
+        s.compare()
+        po, chk = s.o.pairs, s.chk
         stats["hammer_contacts"] += int(((po[chk][:, :, 1] == G0 + 1) | (po[chk][:, :, 1] == G0 + 2)).sum())
         stats["box_box"] += int(((po[chk][:, :, 0] >= G0) & (po[chk][:, :, 1] >= G0)).sum())
         stats["nail_contacts"] += int((po[chk][:, :, 1] == G0 + 3).sum())
-        stats["max_ncon"] = max(stats["max_ncon"], int(no[chk].max()) if chk.any() else 0)
-        stats["static"] = max(stats["static"], int(i_o[chk, 3].max()) if chk.any() else 0)
-        for e in range(n):
-            stats["phases"].add(int(phm[e].task_phase)); stats["gripped"] += int(phm[e].gripped)
-            if chk[e]:
-                assert_state_close(post[e], G.get_state(e), f"{msg} env {e}")
-                assert_state_close(phm[e], G.get_hammer(e), f"{msg} env {e} objects")
-            if resync:
-                G.set_state(e, post[e])
-                G.set_hammer(e, phm[e])
-    record_live(f"test_hammering_gpu::{name}", live, min_live)
+        stats["max_ncon"] = max(stats["max_ncon"], int(s.o.ncon[chk].max()) if chk.any() else 0)
+        stats["static"] = max(stats["static"], int(s.o.info[chk, 3].max()) if chk.any() else 0)
+        stats["phases"] |= {int(hm.task_phase) for hm in s.o.objects}
+        stats["gripped"] += sum(int(hm.gripped) for hm in s.o.objects)
+        if resync:
+            s.resync()
+    stats["flicker"] = run.flicker
+    run.finish(min_live)
     assert stats["flicker"] <= max(2, (n * n_steps) // 100), f"{name}: {stats['flicker']} env-steps with a contact list that differs at agreeing bodies"
     assert stats["knife"] <= max(2, (n * n_steps) // 50), f"{name}: {stats['knife']} env-steps on a knife edge of the oracle itself"
     if twin is not None:
         print(f"[parity] {name}: {stats['knife']} of {n * n_steps} env-steps on a knife edge of the oracle (left out), {stats['flicker']} contact-list flickers")
         twin.close()
-    O.close(); G.close()
     return stats
 
 
@@ -138,10 +91,10 @@ def _on_the_nail(k, Bs):
         for e in range(4):
             hm = B.get_hammer(e)
             d = B.desc if hasattr(B, "desc") else None
-            Rb = _quat2mat(hm.quat[0])
+            Rb = quat_mat(hm.quat[0])
             hm.nail_q = hm.nail_v = 0.0
             hm.quat[1][:] = [np.sqrt(0.5), 0, np.sqrt(0.5), 0]
-            Rh = _quat2mat(hm.quat[1])
+            Rh = quat_mat(hm.quat[1])
             head = np.array([0.0, 0.0, 0.0875 + 0.01925 - 0.06726677713338856])
             if e < 3:
                 top = np.array(hm.pos[0]) + Rb @ np.array([hm.nail_xy[0], hm.nail_xy[1], 0.086 + 0.003])
@@ -161,7 +114,7 @@ def _nail_at_the_finger(k, Bs):
         return
     for B in Bs:
         hm, st = B.get_hammer(0), B.get_state(0)
-        Rb = _quat2mat(hm.quat[0])
+        Rb = quat_mat(hm.quat[0])
         nail = Rb @ np.array([hm.nail_xy[0], hm.nail_xy[1], 0.086])
         hm.pos[0][:] = (np.array(st.eef_pos) + [0.0, 0.03, -0.02] - nail).tolist()
         hm.pos[1][:] = [0.3, -0.8, 3.0]
@@ -242,14 +195,14 @@ def test_box_box_fuzz_parity():
         poses = []
         for e in range(n):
             hm = hm0[e]
-            Rb = _quat2mat(hm.quat[0])
+            Rb = quat_mat(hm.quat[0])
             ax = rs.randn(3); ax /= np.linalg.norm(ax)
             ang = rs.uniform(0, 0.6)
             qt = np.concatenate([[np.cos(ang / 2)], np.sin(ang / 2) * ax])
             base = np.array([np.sqrt(0.5), 0, np.sqrt(0.5), 0])                    # handle level, head pointing down
             w1, v1, w2, v2 = qt[0], qt[1:], base[0], base[1:]
             q = np.concatenate([[w1 * w2 - v1 @ v2], w1 * v2 + w2 * v1 + np.cross(v1, v2)])
-            Rh = _quat2mat(q)
+            Rh = quat_mat(q)
             head = np.array([0.0, 0.0, 0.0875 + 0.01925 - 0.06726677713338856])
             if e % 3 == 0:    # head over the nail
                 tgt = np.array(hm.pos[0]) + Rb @ np.array([hm.nail_xy[0], hm.nail_xy[1], 0.086 + 0.003 + 0.0616 - rs.uniform(0, 0.004)])

@@ -90,36 +90,24 @@ def test_weld_follows_the_hand_then_handover_phases():
 
 @pytest.mark.gpu
 def test_hip_matches_oracle_on_the_handover_task():
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
-    clips = _clips()
-    kw = dict(KW, shield_type="PFL")
-    O, G = make_pair(6, kw, clips=clips, **H2R)
-    d = hrg.build_model_desc(kw, n_clips=clips.n_clips, **H2R)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
-    for e in range(6):
-        assert_state_close(O.get_box(e), G.get_box(e), f"reset env {e} box")
+    from helpers import make_pair
+    from parity import Run
+    O, G = make_pair(6, dict(KW, shield_type="PFL"), clips=_clips(), **H2R)
+    run = Run(O, G, "handover", free_running=True, violent=None, atol=2e-6)
     rng = np.random.RandomState(0)
     wins = 0
-    for k in range(70):
-        a = _scenario(k, [O, G], 6, d)
+
+    def actions(k):
+        a = _scenario(k, [O, G], 6, O.desc)
         a[:, :6] = rng.uniform(-0.2, 0.2, (6, 6)) if not 14 <= k <= 22 else 0.0
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        wins += int((r_o > 0).sum())
-        for e in range(6):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 8 == 7:
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
-    assert wins >= 3 and i_o[:, 13].max() >= 1
-    O.close(); G.close()
+        return a
+    for s in run.steps(70, actions):
+        s.compare()
+        wins += int((s.o.reward > 0).sum())
+        if s.k % 8 == 7:
+            s.resync()
+    assert wins >= 3 and s.o.info[:, 13].max() >= 1
+    run.finish()
 
 
 # ------------------------------------------------------------------------------------------------ robot -> human
@@ -179,35 +167,24 @@ def test_robot_to_human_handover_on_the_oracle():
 
 @pytest.mark.gpu
 def test_hip_matches_oracle_on_the_robot_to_human_handover():
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
-    clips = _clips2()
-    kw = dict(KW2, shield_type="PFL")
-    O, G = make_pair(6, kw, clips=clips, **R2H)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
-    for e in range(6):
-        assert_state_close(O.get_box(e), G.get_box(e), f"reset env {e} box")
+    from helpers import make_pair
+    from parity import Run
+    O, G = make_pair(6, dict(KW2, shield_type="PFL"), clips=_clips2(), **R2H)
+    run = Run(O, G, "robot to human handover", free_running=True, violent=None, atol=2e-6)
     rng = np.random.RandomState(0)
     wins = 0
-    for k in range(130):
+
+    def actions(k):
         a = _scenario2(k, [O, G], 6)
         a[:, :6] = rng.uniform(-0.2, 0.2, (6, 6))
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        wins += int((r_o > 0).sum())
-        for e in range(6):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 8 == 7:
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
+        return a
+    for s in run.steps(130, actions):
+        s.compare()
+        wins += int((s.o.reward > 0).sum())
+        if s.k % 8 == 7:
+            s.resync()
     assert wins >= 3
-    O.close(); G.close()
+    run.finish()
 
 
 @pytest.mark.gpu

@@ -16,15 +16,14 @@ import torch  # noqa: F401  (first: the HIP library must bind to the HIP runtime
 import human_robot_gym_amd as hrg
 from human_robot_gym_amd._cstruct import CONST
 from human_robot_gym_amd.model import load_robot_hulls, robot_fk_numpy
-from helpers import RTOL, assert_state_close, compare_states_bulk, states_as_bytes
+from helpers import (GEOM_BOX, NH, RTOL, compare_states_bulk, fold_onto_table, link_object, make_pair, near_link_object, quat_mat)
+from parity import Run, field
 from pp_scenarios import grasp_and_carry, put_box, random_actions
 import hullbox_ref as ref
 from test_hull_box import CUBE, kat_cases, rot
 
 pytestmark = pytest.mark.gpu
 
-NH = CONST["HRG_NHULL"]
-GEOM_BOX = CONST["HRG_NRCAP"] + CONST["HRG_NHB"] + 2
 GEOM_HUMAN0, GEOM_TABLE = CONST["HRG_NRCAP"], CONST["HRG_NRCAP"] + CONST["HRG_NHB"]
 QDT = np.dtype([("R", "f8", 9), ("p", "f8", 3), ("bp", "f8", 3), ("bR", "f8", 9), ("bh", "f8", 3), ("hull", "i4"), ("pad", "i4")])
 
@@ -111,91 +110,27 @@ def test_wave_routine_unit_cube_known_answers():
 
 
 # ---------------------------------------------------------------------------------------------------------------- wiring vs the oracle
-def _link_cube(pairs, ncon):
-    """per env: the contact list holds an (arm link 0..6, cube) pair"""
-    k = np.arange(pairs.shape[1])[None, :] < ncon[:, None]
-    return np.any(k & (pairs[:, :, 0] < NH) & (pairs[:, :, 1] == GEOM_BOX), axis=1)
-
-
-def _quat_mat(q):
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def _near_link_cube(desc, pre, bpre, post, bpost, slack=0.01):
-    """per env: some arm link's bounding capsule came within reach of the cube during the step -- the contact list holds the last substep only, so an (arm link,
-    cube) pair of an earlier substep is caught here: capsule - box distance below the radius plus how far the capsule's end points and the cube moved, plus `slack`"""
-    h = np.array(desc.box_half[:])
-    t = np.linspace(0, 1, 24)[:, None]
-    out = np.zeros(len(pre), bool)
-    for e in range(len(pre)):
-        if bpre[e] is None:
-            continue
-        ends = []
-        for st in (pre[e], post[e]):
-            R, p = robot_fk_numpy(desc, np.asarray(list(st.qpos)[:8]))
-            ends.append([(p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p1[L][:]), p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p2[L][:]))
-                         for L in range(NH) if desc.rcap_body[L] >= 0])
-        cubes = [(np.array(b.pos[:]), _quat_mat(b.quat[:])) for b in (bpre[e], bpost[e])]
-        move = np.linalg.norm(cubes[0][0] - cubes[1][0])
-        for (a0, b0), (a1, b1), L in zip(ends[0], ends[1], [L for L in range(NH) if desc.rcap_body[L] >= 0]):
-            reach = desc.rcap_r[L] + max(np.linalg.norm(a1 - a0), np.linalg.norm(b1 - b0)) + move + slack
-            for (a, b), (c, Rc) in (((a0, b0), cubes[0]), ((a1, b1), cubes[1])):
-                P = (a + t * (b - a) - c) @ Rc
-                q = np.maximum(np.abs(P) - h, 0.0)
-                if np.sqrt((q * q).sum(axis=1)).min() < reach:
-                    out[e] = True
-    return out
-
-
 def _parity(env_id, kw, n_envs, n_steps, scenario, extra=None):
-    import torch
-    from oracle.oracle import OracleBatch
-    from human_robot_gym_amd._lib import HipBatch
-    extra = extra or {}
-    clips = hrg.synthetic_clips(3, seed=0, min_frames=300, max_frames=600)
-    mk = lambda: hrg.build_model_desc(kw, n_clips=clips.n_clips, env_id=env_id, robot_geometry="hull", **extra)  # noqa: E731
-    desc = mk()
-    O, G = OracleBatch(mk(), clips, n_envs), HipBatch(mk(), clips, n_envs)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=1e-7)
+    """violent as in the cube tasks' own rollouts; on top of that the env-steps with an (arm link, cube) pair listed or near leave the comparison"""
+    O, G = make_pair(n_envs, kw, env_id=env_id, robot_geometry="hull", **(extra or {}))
+    desc = O.desc
+    run = Run(O, G, f"{env_id} hull")
     rng = np.random.RandomState(4)
     t = dict(compared=0, total=0, finger_cube=0, hull_refined=0, link_cube=0)
-    for k in range(n_steps):
-        a = scenario(k, [O, G], rng, n_envs, desc)
-        pre, bpre = [O.get_state(e) for e in range(n_envs)], [O.get_box(e) for e in range(n_envs)]
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
-        torch.cuda.synchronize()
-        post = [O.get_state(e) for e in range(n_envs)]
-        pbox = [O.get_box(e) for e in range(n_envs)]
-        po, no = O.contacts()
-        pg, ng = G.contacts()
-        lc = _link_cube(po, no) | _link_cube(pg, ng) | (_near_link_cube(desc, pre, bpre, post, pbox) & (d_o == 0))
-        violent = np.array([i_o[e, 11] != 0 or max(abs(v) for v in post[e].qvel) > 5.0 or max(abs(v) for v in pbox[e].vel[:3]) > 5.0 for e in range(n_envs)])
-        chk = ~lc & ~violent
-        msg = f"{env_id} step {k}"
-        np.testing.assert_array_equal(ng[chk], no[chk], err_msg=msg)
-        np.testing.assert_array_equal(pg[chk], po[chk], err_msg=msg)
-        np.testing.assert_array_equal(i_g.cpu().numpy()[chk], i_o[chk], err_msg=msg)
-        np.testing.assert_array_equal(d_g.cpu().numpy()[chk], d_o[chk], err_msg=msg)
-        np.testing.assert_allclose(o_g.cpu().numpy()[chk], o_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(r_g.cpu().numpy()[chk], r_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        for e in range(n_envs):
-            if chk[e]:
-                assert_state_close(post[e], G.get_state(e), f"{msg} env {e}")
-                assert_state_close(pbox[e], G.get_box(e), f"{msg} env {e} box")
-            G.set_state(e, post[e])
-            G.set_box(e, pbox[e])
-        live = np.arange(po.shape[1])[None, :] < no[:, None]
-        sel = live & chk[:, None]
+    for s in run.steps(n_steps, lambda k: scenario(k, [O, G], rng, n_envs, desc)):
+        po, no = s.o.pairs, s.o.ncon
+        lc = link_object(po, no) | link_object(s.g.pairs, s.g.ncon) | (near_link_object(desc, "box", s.pre_states, s.pre_objects, s.o.states, s.o.objects) & (s.o.done == 0))
+        s.chk &= ~lc
+        s.compare()
+        s.resync()
+        sel = (np.arange(po.shape[1])[None, :] < no[:, None]) & s.chk[:, None]
         t["finger_cube"] += int((sel & (po[:, :, 0] >= NH) & (po[:, :, 0] < GEOM_HUMAN0) & (po[:, :, 1] == GEOM_BOX)).sum())
         t["hull_refined"] += int((sel & (po[:, :, 0] < NH) & (po[:, :, 1] >= GEOM_HUMAN0) & (po[:, :, 1] < GEOM_BOX)).sum())
         t["link_cube"] += int(lc.sum())
-        t["compared"] += int(chk.sum()); t["total"] += n_envs
+        t["compared"] += int(s.chk.sum()); t["total"] += n_envs
     t["mpr_fallbacks"] = G.mpr_fallbacks()
     print(f"[hull_box parity] {env_id} {kw.get('shield_type')} {getattr(scenario, '__name__', '')}: {t}")
-    O.close(); G.close()
+    run.finish()
     return t
 
 
@@ -204,19 +139,11 @@ def test_pick_place_hull_matches_the_oracle_away_from_link_cube_pairs(shield):
     kw = dict(shield_type=shield, horizon=40, reward_shaping=True, done_at_collision=False)
     ta = _parity("PickPlaceHumanCart", kw, 16, 36, lambda k, b, rng, n, d: grasp_and_carry(k, b, rng, n, d))
     tb = _parity("PickPlaceHumanCart", kw, 16, 30, lambda k, b, rng, n, d: random_actions(k, b, rng, n))
-    tc = _parity("PickPlaceHumanCart", kw, 16, 36, _fold_onto_table)
+    tc = _parity("PickPlaceHumanCart", kw, 16, 36, lambda k, b, rng, n, d: fold_onto_table(rng, n))
     for t in (ta, tb, tc):
         assert t["compared"] >= 0.5 * t["total"], t
     assert ta["finger_cube"] > 0, ta
     assert ta["hull_refined"] + tb["hull_refined"] + tc["hull_refined"] > 0, (ta, tb, tc)
-
-
-def _fold_onto_table(k, batches, rng, n_envs, desc):
-    """random small actions with the shoulder folding down: arm links come to rest on the table (hull-refined link x table contacts)"""
-    a = rng.uniform(-0.3, 0.3, (n_envs, 7))
-    a[:, 1] = 1.0
-    a[:, 2] = np.where(np.arange(n_envs) % 2 == 0, 0.6, -0.2)
-    return a
 
 
 def test_inspection_and_reach_box_hull_match_the_oracle():
@@ -336,10 +263,7 @@ def test_cube_inside_the_hull_gets_one_contact_that_resolves():
     torch.cuda.synchronize()
     qpos2, bx = list(G.get_state(0).qpos), G.get_box(0)
     Rb, pb, *_ , Vb = _link_world(desc, qpos2, L)
-    from pp_scenarios import mat2quat  # noqa: F401  (quat convention: w, x, y, z)
-    w, x, y, z = bx.quat[:]
-    Rc = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                   [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    Rc = quat_mat(bx.quat[:])
     st, depth, n, pos = ref.mpr_penetration(Vb, Rb, pb, np.array(bx.pos[:]), Rc, np.full(3, h))
     assert st != ref.PENETRATING or depth < 1e-3, (st, depth)
     print(f"[hull_box] link {L}: one contact; after 3 steps depth {depth if st == ref.PENETRATING else 0.0:.2e}; fallbacks {fb1} / {G.mpr_fallbacks()}")
@@ -388,9 +312,9 @@ def test_pick_place_hull_steady_state_at_bench_size():
             o_g, r_g, d_g, i_g = [x.cpu().numpy() for x in (G.obs, G.reward, G.done, G.info)]
             po, no = O.contacts()
             pg, ng = G.contacts()
-            lc = _link_cube(po, no) | _link_cube(pg, ng)
-            lc |= _near_link_cube(desc, pre_o, pre_b, post[0], post[1]) & (d_o == 0)
-            qv = lambda s: np.abs(np.ascontiguousarray(states_as_bytes(s)[:, _QOFF:_QOFF + 64]).view(np.float64)).max(axis=1)  # noqa: E731
+            lc = link_object(po, no) | link_object(pg, ng)
+            lc |= near_link_object(desc, "box", pre_o, pre_b, post[0], post[1]) & (d_o == 0)
+            qv = lambda s: np.abs(field(s, "qvel")).max(axis=1)  # noqa: E731
             violent = (i_o[:, 11] != 0) | (qv(pre_o) > 5.0) | (qv(post[0]) > 5.0)
             st_g, bx_g = G.get_states(idx)
             ok, why = compare_states_bulk(post[0], st_g, skip=("ncon", "con_pairs", "n_prev", "prev_pairs", "ltt.dur", "ltt.jerk", "safe_path.dur", "safe_path.jerk"))
@@ -410,6 +334,3 @@ def test_pick_place_hull_steady_state_at_bench_size():
         assert share >= 0.9, (cmp_n, tot)
     assert crashes["hull"] <= crashes["capsule"], crashes
 
-
-from human_robot_gym_amd._cstruct import EnvState  # noqa: E402
-_QOFF = EnvState.qvel.offset

@@ -20,20 +20,17 @@ import human_robot_gym_amd as hrg
 from human_robot_gym_amd._cstruct import CONST
 from human_robot_gym_amd.mixed import task_clips, task_env_kwargs
 from human_robot_gym_amd.model import load_robot_hulls, robot_fk_numpy
-from helpers import RTOL, assert_state_close
+from helpers import GEOM_BOX, NH, RTOL, link_object, make_pair, near_link_object, quat_mat
+from parity import KINDS, Run, field, kind_of, read_blocks
 import hullbox_ref as ref
-from test_hull_box_gpu import _compare_tap, _find_placement, _link_world, _run_tap, _quat_mat
+from test_hull_box_gpu import _compare_tap, _find_placement, _link_world, _run_tap
 from test_hull_tasks import TASKS, surface_queries, task_boxes
 
 pytestmark = pytest.mark.gpu
 
-NH = CONST["HRG_NHULL"]
 NRCAP = CONST["HRG_NRCAP"]
 GEOM_HUMAN0 = NRCAP
-GEOM_BOX = NRCAP + CONST["HRG_NHB"] + 2
-HG_BOARD, HG_HANDLE, HG_HEAD, HG_NAIL = (CONST[k] for k in ("HRG_HG_BOARD", "HRG_HG_HANDLE", "HRG_HG_HEAD", "HRG_HG_NAIL"))
-KIND = {"HumanRobotHandoverCart": "box", "RobotHumanHandoverCart": "box", "CollaborativeLiftingCart": "box", "CollaborativeStackingCart": "stack",
-        "CollaborativeHammeringCart": "hammer"}
+HG_HEAD = CONST["HRG_HG_HEAD"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. the wave routine at these extents
@@ -75,53 +72,6 @@ def test_hull_batch_is_created_and_steps(env_id):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. wiring vs the oracle
-def _obj_boxes(desc, kind, ob):
-    """world boxes (centre, rotation, half extents) of the object block `ob` an arm link can meet"""
-    if kind == "box":
-        return [(np.array(ob.pos[:]), _quat_mat(ob.quat[:]), np.array(desc.box_half[:]))]
-    if kind == "stack":
-        return [(np.array(ob.pos[c][:]), _quat_mat(ob.quat[c][:]), np.array(desc.box_half[:])) for c in range(CONST["HRG_NCUBE"])]
-    R0, R1 = _quat_mat(ob.quat[0][:]), _quat_mat(ob.quat[1][:])
-    p0, p1 = np.array(ob.pos[0][:]), np.array(ob.pos[1][:])
-    gp = lambda g: np.array(desc.hm_geom_pos[g][:])  # noqa: E731
-    gh = lambda g: np.array(desc.hm_geom_half[g][:])  # noqa: E731
-    org = p0 + R0 @ np.array([ob.nail_xy[0], ob.nail_xy[1], desc.hm_nail_z0 - ob.nail_q])
-    return [(p0, R0, gh(HG_BOARD)), (p1 + R1 @ gp(HG_HANDLE), R1, gh(HG_HANDLE)), (p1 + R1 @ gp(HG_HEAD), R1, gh(HG_HEAD)), (org + R0 @ gp(HG_NAIL), R0, gh(HG_NAIL))]
-
-
-def _near_link_object(desc, kind, pre, opre, post, opost, slack=0.01):
-    """per env: some arm link's bounding capsule came within reach of an object box during the step (the contact list holds the last substep only): capsule - box
-    distance below the radius plus how far the capsule's end points and the box moved, plus `slack`"""
-    t = np.linspace(0, 1, 24)[:, None]
-    links = [L for L in range(NH) if desc.rcap_body[L] >= 0]
-    out = np.zeros(len(pre), bool)
-    for e in range(len(pre)):
-        ends = []
-        for st in (pre[e], post[e]):
-            R, p = robot_fk_numpy(desc, np.asarray(list(st.qpos)[:8]))
-            ends.append([(p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p1[L][:]), p[desc.rcap_body[L]] + R[desc.rcap_body[L]] @ np.array(desc.rcap_p2[L][:]))
-                         for L in links])
-        b0, b1 = _obj_boxes(desc, kind, opre[e]), _obj_boxes(desc, kind, opost[e])
-        for (a0, e0), (a1, e1), L in zip(ends[0], ends[1], links):
-            for (c0, R0, h), (c1, R1, _) in zip(b0, b1):
-                reach = desc.rcap_r[L] + max(np.linalg.norm(a1 - a0), np.linalg.norm(e1 - e0)) + np.linalg.norm(c1 - c0) + slack
-                for (a, b), (c, Rc) in (((a0, e0), (c0, R0)), ((a1, e1), (c1, R1))):
-                    q = np.maximum(np.abs((a + t * (b - a) - c) @ Rc) - h, 0.0)
-                    if np.sqrt((q * q).sum(axis=1)).min() < reach:
-                        out[e] = True
-                        break
-                if out[e]:
-                    break
-            if out[e]:
-                break
-    return out
-
-
-def _link_object(pairs, ncon):
-    k = np.arange(pairs.shape[1])[None, :] < ncon[:, None]
-    return np.any(k & (pairs[:, :, 0] < NH) & (pairs[:, :, 1] >= GEOM_BOX), axis=1)
-
-
 def _fold_onto_table(rng, n):
     """random small actions with the shoulder, elbow and wrist driven to their limits, each env in another combination of directions: arm links come down onto
     the table or the floor (hull-refined link x plane contacts)"""
@@ -133,76 +83,31 @@ def _fold_onto_table(rng, n):
     return a
 
 
-def _state_doubles(s):
-    """every float of an env state (the doubles come first, up to `timestep`)"""
-    from human_robot_gym_amd._cstruct import EnvState
-    return np.frombuffer(bytes(s), dtype=np.float64, count=EnvState.timestep.offset // 8)
-
-
-def _object_flat(kind, ob):
-    if kind == "box":
-        return np.array(list(ob.pos[:]) + list(ob.quat[:]))
-    if kind == "stack":
-        return np.array([x for c in range(CONST["HRG_NCUBE"]) for x in list(ob.pos[c][:]) + list(ob.quat[c][:])])
-    return np.array([x for b in range(2) for x in list(ob.pos[b][:]) + list(ob.quat[b][:])] + [ob.nail_q])
-
-
 def _parity(env_id, shield, n, steps, fold):
-    from oracle.oracle import OracleBatch
-    from human_robot_gym_amd._lib import HipBatch
-    kind = KIND[env_id]
-    clips = _clips(env_id)
-    kw = dict(shield_type=shield, horizon=40, done_at_collision=False)
-    mk = lambda: _desc(env_id, kw, clips)  # noqa: E731
-    desc = mk()
-    O, G = OracleBatch(mk(), clips, n), HipBatch(mk(), clips, n)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=1e-7)
-    get = lambda B, e: getattr(B, "get_" + kind)(e)  # noqa: E731
+    """violent here: the base rule alone.  The env-steps with an (arm link, object box) pair listed or near leave the comparison; so does, counted in `flicker` and
+    bounded by the caller, an env-step whose contact list differs at agreeing floats (parity.Step.drop_flicker: the two kernels round differently, 2e-16 m measured)"""
+    O, G = make_pair(n, dict(shield_type=shield, horizon=40, done_at_collision=False), task_frames=(300, 600), env_id=env_id, robot_geometry="hull")
+    desc, kind = O.desc, kind_of(O.desc)
+    run = Run(O, G, f"{env_id} {shield} hull", violent="base")
     rng = np.random.RandomState(4)
     t = dict(compared=0, total=0, hull_refined=0, link_object=0, flicker=0)
-    for k in range(steps):
-        a = _fold_onto_table(rng, n) if fold else rng.uniform(-1, 1, (n, 7))
-        pre, opre = [O.get_state(e) for e in range(n)], [get(O, e) for e in range(n)]
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
-        torch.cuda.synchronize()
-        post, opost = [O.get_state(e) for e in range(n)], [get(O, e) for e in range(n)]
-        po, no = O.contacts()
-        pg, ng = G.contacts()
+    for s in run.steps(steps, lambda k: _fold_onto_table(rng, n) if fold else rng.uniform(-1, 1, (n, 7))):
+        po, no, pre = s.o.pairs, s.o.ncon, (s.pre_states, s.pre_objects)
         # an env that finished its episode in this step holds its reset state: its arm is checked at the step's start, with a margin for the whole step's motion
-        lo = _link_object(po, no) | _link_object(pg, ng) | np.where(d_o == 0, _near_link_object(desc, kind, pre, opre, post, opost),
-                                                                     _near_link_object(desc, kind, pre, opre, pre, opre, slack=0.15))
-        violent = np.array([i_o[e, 11] != 0 or max(abs(v) for v in post[e].qvel) > 5.0 for e in range(n)])
-        chk = ~lo & ~violent
-        msg = f"{env_id} {shield} step {k}"
-        # a resting box - box contact that carries no load sits AT distance zero, and whether it is listed is decided by rounding-level state differences (the two
-        # kernels round differently: 2e-16 m measured): such an env-step leaves the comparison as in test_bench_state_gpu.py -- only while EVERY float of the env
-        # state and of the object block agrees to 1e-7 (a wrong robot contact moves the robot), and at most 1 % of the env-steps may (asserted by the caller)
-        for e in np.nonzero(chk & ((ng != no) | (pg != po).any((1, 2))))[0]:
-            so, sg = _state_doubles(post[e]), _state_doubles(G.get_state(e))
-            fo, fg = _object_flat(kind, opost[e]), _object_flat(kind, get(G, e))
-            if np.all(np.abs(so - sg) <= 1e-7 + 1e-7 * np.abs(so)) and np.all(np.abs(fo - fg) <= 1e-7 + 1e-7 * np.abs(fo)):
-                chk[e] = False
-                t["flicker"] += 1
-        np.testing.assert_array_equal(ng[chk], no[chk], err_msg=msg)
-        np.testing.assert_array_equal(pg[chk], po[chk], err_msg=msg)
-        np.testing.assert_array_equal(i_g.cpu().numpy()[chk], i_o[chk], err_msg=msg)
-        np.testing.assert_array_equal(d_g.cpu().numpy()[chk], d_o[chk], err_msg=msg)
-        np.testing.assert_allclose(o_g.cpu().numpy()[chk], o_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(r_g.cpu().numpy()[chk], r_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        for e in range(n):
-            if chk[e]:
-                assert_state_close(post[e], G.get_state(e), f"{msg} env {e}")
-                assert_state_close(opost[e], get(G, e), f"{msg} env {e} objects")
-            G.set_state(e, post[e])
-            getattr(G, "set_" + kind)(e, opost[e])
+        lo = link_object(po, no) | link_object(s.g.pairs, s.g.ncon) | np.where(s.o.done == 0, near_link_object(desc, kind, *pre, s.o.states, s.o.objects),
+                                                                               near_link_object(desc, kind, *pre, *pre, slack=0.15))
+        s.chk &= ~lo
+        s.drop_flicker()
+        s.compare()
+        s.resync()
         live = np.arange(po.shape[1])[None, :] < no[:, None]
-        t["hull_refined"] += int((live & chk[:, None] & (po[:, :, 0] < NH) & (po[:, :, 1] >= GEOM_HUMAN0) & (po[:, :, 1] < GEOM_BOX)).sum())
+        t["hull_refined"] += int((live & s.chk[:, None] & (po[:, :, 0] < NH) & (po[:, :, 1] >= GEOM_HUMAN0) & (po[:, :, 1] < GEOM_BOX)).sum())
         t["link_object"] += int(lo.sum())
-        t["compared"] += int(chk.sum()); t["total"] += n
+        t["compared"] += int(s.chk.sum()); t["total"] += n
+    t["flicker"] = run.flicker
     t["mpr_fallbacks"] = G.mpr_fallbacks()
     print(f"[hull_tasks parity] {env_id} {shield} {'fold' if fold else 'random'}: {t}")
-    O.close(); G.close()
+    run.finish()
     return t
 
 
@@ -290,7 +195,7 @@ def test_stacking_cube_clear_of_the_hull_is_left_alone_and_inside_gets_one_conta
     torch.cuda.synchronize()
     sk = G.get_stack(0)
     Rb, pb, *_, Vb = _link_world(desc, list(G.get_state(0).qpos), L)
-    st, depth, _, _ = ref.mpr_penetration(Vb, Rb, pb, np.array(sk.pos[0][:]), _quat_mat(sk.quat[0][:]), np.full(3, h))
+    st, depth, _, _ = ref.mpr_penetration(Vb, Rb, pb, np.array(sk.pos[0][:]), quat_mat(sk.quat[0][:]), np.full(3, h))
     print(f"[hull_tasks] stacking link {L}: after 3 steps depth {depth if st == ref.PENETRATING else 0.0:.2e}; crashes {crash}; fallbacks {G.mpr_fallbacks()}")
     assert (st != ref.PENETRATING or depth < 1e-3) and crash == 0, (st, depth, crash)
     G.close()
@@ -336,7 +241,7 @@ def test_hammer_head_clear_of_the_hull_is_left_alone_and_inside_gets_one_contact
         G_h, _ = _one_env(env_id, "hull", 1)
         qpos = list(G_h.get_state(0).qpos)
         hm = G_h.get_hammer(0)
-        R1 = _quat_mat(hm.quat[1][:])
+        R1 = quat_mat(hm.quat[1][:])
         bh = np.array(desc.hm_geom_half[HG_HEAD][:])
         L, c = _find_box_placement(desc, qpos, R1, bh, want, np.random.RandomState(5 + want))
         for G in (G_c, G_h):
@@ -378,7 +283,6 @@ def test_steady_state_at_bench_size(env_id):
     The bench's pre-roll (one horizon, at most 1000 steps), then 2 steps compared on the first 512 envs (the oracle steps those only)."""
     import bench
     from oracle.oracle import OracleBatch
-    kind = KIND[env_id]
     crashes = {}
     for geom in ("capsule", "hull"):
         W = bench.bench_workload(env_id, "SSM", robot_geometry=geom)
@@ -403,31 +307,32 @@ def test_steady_state_at_bench_size(env_id):
         m = 512
         envs = np.arange(m)
         O = OracleBatch(hrg.build_model_desc(W["env_kwargs"], n_clips=clips.n_clips, env_id=env_id, **W["wrappers"]), clips, m, env_id0=0)
-        get = lambda B, e: getattr(B, "get_" + kind)(e)  # noqa: E731
+        kind = kind_of(desc)
+        get, put = KINDS[kind]["get"], KINDS[kind]["set"]
         for e in envs:
             O.set_state(int(e), G.get_state(int(e)))
-            getattr(O, "set_" + kind)(int(e), get(G, int(e)))
+            getattr(O, put)(int(e), getattr(G, get)(int(e)))
         good = tot = lo_n = 0
         for k in range(2):
             a = pool[(pre + k) % len(pool)]
-            pre_s, pre_o = [O.get_state(int(e)) for e in envs], [get(O, int(e)) for e in envs]
+            pre_s, pre_o = read_blocks(O, kind)
             G.step(a)
             o_o, r_o, d_o, i_o = O.step_parallel(np.ascontiguousarray(a.cpu().numpy()[:m]), n_workers=16)
             torch.cuda.synchronize()
-            post_s, post_o = [O.get_state(int(e)) for e in envs], [get(O, int(e)) for e in envs]
+            post_s, post_o = read_blocks(O, kind)
             o_g, r_g, d_g, i_g = [x.cpu().numpy()[envs] for x in (G.obs, G.reward, G.done, G.info)]
             po, no = O.contacts()
             pg, ng = G.contacts()
             pg, ng = pg[:m], ng[:m]
-            lo = _link_object(po, no) | _link_object(pg, ng) | (_near_link_object(desc, kind, pre_s, pre_o, post_s, post_o) & (d_o == 0))
-            violent = (i_o[:, 11] != 0) | np.array([max(abs(v) for v in s.qvel) > 5.0 for s in post_s])
+            lo = link_object(po, no) | link_object(pg, ng) | (near_link_object(desc, kind, pre_s, pre_o, post_s, post_o) & (d_o == 0))
+            violent = (i_o[:, 11] != 0) | (np.abs(field(post_s, "qvel")).max(axis=1) > 5.0)
             chk = ~lo & ~violent
             same = (no == ng) & np.all(po == pg, axis=(1, 2)) & np.all(i_g == i_o, axis=1) & (d_g == d_o)
             same &= np.all(np.abs(o_g - o_o) <= 1e-6 + RTOL * np.abs(o_o), axis=1) & (np.abs(r_g - r_o) <= 1e-6 + RTOL * np.abs(r_o))
             good += int((chk & same).sum()); tot += int(chk.sum()); lo_n += int(lo.sum())
             for j, e in enumerate(envs):   # the GPU's envs continue from the oracle's states
                 G.set_state(int(e), post_s[j])
-                getattr(G, "set_" + kind)(int(e), post_o[j])
+                getattr(G, put)(int(e), post_o[j])
         share = good / max(tot, 1)
         print(f"[hull_tasks steady] {env_id} {n} envs: crashes capsule {crashes['capsule']} hull {crashes['hull']}; MPR fallbacks {fb} over {pre} steps "
               f"({rate:.2e} per env-substep); link-object env-steps {lo_n} of {2 * m}; parity {good} / {tot} = {share:.4f}")

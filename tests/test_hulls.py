@@ -179,82 +179,46 @@ def test_hull_geometry_needs_the_hull_variant_on_the_product_path():
 @pytest.mark.parametrize("shield", ["OFF", "SSM"])
 def test_hip_hull_variant_matches_oracle(shield):
     """hrg_step_kernel_hull vs the oracle with hull geometry: the contact scenario (arm links against the human's arm), resynchronised every step."""
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close
-    from oracle.oracle import OracleBatch
-    from human_robot_gym_amd._lib import HipBatch
+    from helpers import make_pair
+    from parity import Run
     clips = hrg.static_clip(600, pelvis=(-0.8, 1.0, 0.3))
     for c in clips.infos:
         c["position_offset"] = [0.0, 0.0, 0.0]
-    kw = dict(shield_type=shield, horizon=30, done_at_collision=False, collision_reward=-10)
     n = 16
-    mk = lambda: hrg.build_model_desc(kw, n_clips=clips.n_clips, robot_geometry="hull")  # noqa: E731
-    O, G = OracleBatch(mk(), clips, n), HipBatch(mk(), clips, n)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    O, G = make_pair(n, dict(shield_type=shield, horizon=30, done_at_collision=False, collision_reward=-10), clips=clips, robot_geometry="hull")
+    run = Run(O, G, f"hull {shield}", violent="base")
     rng = np.random.RandomState(5)
     n_con = 0
-    for k in range(26):
+
+    def actions(k):
         a = rng.uniform(-1, 1, (n, 7))
         a[:, 1] = np.where(np.arange(n) % 2 == 0, 1.0, -1.0)
         a[:, [0, 2, 3, 4, 5]] *= 0.2
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        post = [O.get_state(e) for e in range(n)]
-        ok = np.array([i_o[e, 11] == 0 and max(abs(v) for v in post[e].qvel) < 5.0 for e in range(n)])
-        po, no = O.contacts()
-        pg, ng = G.contacts()
-        np.testing.assert_array_equal(ng[ok], no[ok], err_msg=f"step {k}")
-        np.testing.assert_array_equal(pg[ok], po[ok], err_msg=f"step {k}")
-        np.testing.assert_array_equal(i_g.cpu().numpy()[ok], i_o[ok], err_msg=f"step {k}")
-        np.testing.assert_allclose(o_g.cpu().numpy()[ok], o_o[ok], rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy()[ok], r_o[ok], rtol=RTOL, atol=1e-6)
-        n_con += int(no[ok].sum())
-        for e in range(n):
-            if ok[e]:
-                assert_state_close(post[e], G.get_state(e), f"step {k} env {e}")
-            G.set_state(e, post[e])
-    assert (n_con > 0 or shield == "SSM") and ok.mean() >= 0.75     # (the SSM shield stops the arm before the human touches it)
-    O.close(); G.close()
+        return a
+    for s in run.steps(26, actions):
+        s.compare()
+        n_con += int(s.o.ncon[s.chk].sum())
+        s.resync()
+    assert (n_con > 0 or shield == "SSM") and s.chk.mean() >= 0.75     # (the SSM shield stops the arm before the human touches it)
+    run.finish()
 
 
 @pytest.mark.gpu
 def test_hip_hull_variant_against_the_table():
     """An arm folded onto the table: link hulls against the table plane (the lowest point of the hull), HIP vs oracle."""
-    import torch
-    from helpers import RTOL, assert_state_close
-    from oracle.oracle import OracleBatch
-    from human_robot_gym_amd._lib import HipBatch
-    clips = hrg.synthetic_clips(1, seed=0, min_frames=200, max_frames=300)
-    kw = dict(shield_type="OFF", horizon=80, done_at_collision=False)
+    from helpers import fold_onto_table, make_pair
+    from parity import Run
     n = 8
-    mk = lambda: hrg.build_model_desc(kw, n_clips=1, robot_geometry="hull")  # noqa: E731
-    O, G = OracleBatch(mk(), clips, n), HipBatch(mk(), clips, n)
-    O.reset(); G.reset()
+    O, G = make_pair(n, dict(shield_type="OFF", horizon=80, done_at_collision=False), clips=hrg.synthetic_clips(1, seed=0, min_frames=200, max_frames=300), robot_geometry="hull")
+    run = Run(O, G, "hull on the table", violent="base")
     rng = np.random.RandomState(3)
     table = 0
-    for k in range(60):
-        a = rng.uniform(-0.3, 0.3, (n, 7))
-        a[:, 1] = 1.0                                                        # keep folding the shoulder towards the table
-        a[:, 2] = np.where(np.arange(n) % 2 == 0, 0.6, -0.2)
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        post = [O.get_state(e) for e in range(n)]
-        ok = np.array([i_o[e, 11] == 0 and max(abs(v) for v in post[e].qvel) < 5.0 for e in range(n)])
-        po, no = O.contacts()
-        pg, ng = G.contacts()
-        np.testing.assert_array_equal(ng[ok], no[ok], err_msg=f"step {k}")
-        np.testing.assert_array_equal(pg[ok], po[ok], err_msg=f"step {k}")
-        np.testing.assert_array_equal(i_g.cpu().numpy()[ok], i_o[ok], err_msg=f"step {k}")
-        np.testing.assert_allclose(o_g.cpu().numpy()[ok], o_o[ok], rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        table += int(((po[ok][:, :, 1] == 10 + 24) & (po[ok][:, :, 0] < 7)).sum())
-        for e in range(n):
-            if ok[e]:
-                assert_state_close(post[e], G.get_state(e), f"step {k} env {e}")
-            G.set_state(e, post[e])
+    for s in run.steps(60, lambda k: fold_onto_table(rng, n)):   # keep folding the shoulder towards the table
+        s.compare()
+        table += int(((s.o.pairs[s.chk][:, :, 1] == 10 + 24) & (s.o.pairs[s.chk][:, :, 0] < 7)).sum())
+        s.resync()
     assert table > 0, "the scenario was meant to bring an arm link onto the table"
-    O.close(); G.close()
+    run.finish()
 
 
 @pytest.mark.gpu

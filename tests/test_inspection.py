@@ -84,33 +84,24 @@ def test_phases_loop_rewards_and_next_animation():
 
 @pytest.mark.gpu
 def test_hip_matches_oracle_on_the_inspection_task():
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
-    clips = _clips()
-    kw = dict(shield_type="SSM", horizon=400, seed=3, object_at_target_reward=-0.5)
-    O, G = make_pair(6, kw, clips=clips, **INSP)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    from helpers import make_pair
+    from parity import Run
+    O, G = make_pair(6, dict(shield_type="SSM", horizon=400, seed=3, object_at_target_reward=-0.5), clips=_clips(), **INSP)
+    run = Run(O, G, "inspection", free_running=True, violent=None)
     rng = np.random.RandomState(0)
     successes = 0
-    for k in range(70):
+
+    def actions(k):
         a = _scenario(k, [O, G], 6)
         a[:, :6] = rng.uniform(-0.3, 0.3, (6, 6))
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        successes += int((r_o > 0).sum())
-        for e in range(6):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 8 == 7:   # re-synchronise now and then: second-derivative quantities (des_a) sit on jerk ramps and drift apart at 1e-5 after ~60 free steps
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
+        return a
+    for s in run.steps(70, actions):
+        s.compare()
+        successes += int((s.o.reward > 0).sum())
+        if s.k % 8 == 7:   # re-synchronise now and then: second-derivative quantities (des_a) sit on jerk ramps and drift apart at 1e-5 after ~60 free steps
+            s.resync()
     assert successes >= 3
-    O.close(); G.close()
+    run.finish()
 
 
 def _inspection_expert(obs_obj, obs_tgt, gripped):

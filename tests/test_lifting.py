@@ -145,34 +145,19 @@ def test_animation_complete_is_the_success_and_starts_the_next_task():
 
 @pytest.mark.gpu
 def test_hip_matches_oracle_on_the_lifting_task():
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
-    clips = _clips(3, 100, 150)
-    O, G = make_pair(6, dict(seed=3, horizon=40, shield_type="SSM"), clips=clips, env_id=ENV)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
-    for e in range(6):
-        assert_state_close(O.get_box(e), G.get_box(e), f"reset env {e} box")
+    from helpers import make_pair
+    from parity import Run
+    O, G = make_pair(6, dict(seed=3, horizon=40, shield_type="SSM"), clips=_clips(3, 100, 150), env_id=ENV)
+    run = Run(O, G, "lifting", free_running=True, violent=None, atol=2e-6, reward_atol=2e-6)
     rng = np.random.RandomState(0)
     held = 0
-    for k in range(90):
-        a = rng.uniform(-0.3, 0.3, (6, 7))
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(G.term_obs.cpu().numpy(), O.term_obs, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        held += int(O.term_obs[:, 39].sum())
-        for e in range(6):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 4 == 3:      # three-point support with sliding finger contacts: resynchronise before rounding differences grow
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
+    for s in run.steps(90, lambda k: rng.uniform(-0.3, 0.3, (6, 7))):
+        s.compare()
+        held += int(s.o.term_obs[:, 39].sum())
+        if s.k % 4 == 3:      # three-point support with sliding finger contacts: resynchronise before rounding differences grow
+            s.resync()
     assert held > 100
-    O.close(); G.close()
+    run.finish()
 
 
 @pytest.mark.gpu
@@ -299,67 +284,47 @@ def test_a_following_robot_carries_the_board_through_and_a_resting_one_tips_it()
 def test_hip_matches_oracle_through_success_and_the_next_task():
     """done_at_success=False: when the animation completes, _on_goal_reached puts the robot back to its initial posture, resets the controller / shield
     memory, starts the next animation and puts the board back into the gripper, inside the same episode."""
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
+    from helpers import make_pair
+    from parity import Run
     nominal = lifting_hands_nominal(hrg.build_model_desc(None, env_id=ENV))
     clips = hrg.synthetic_clips(3, fps=20.0, lifting=nominal, lift_height=0.1, min_frames=20, max_frames=26)
     O, G = make_pair(4, dict(seed=5, horizon=200, done_at_success=False, shield_type="SSM"), clips=clips, env_id=ENV)
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    run = Run(O, G, "lifting through success", free_running=True, violent=None, atol=2e-6, reward_atol=2e-6)
     rng = np.random.RandomState(1)
     goals = 0
-    for k in range(45):
-        a = rng.uniform(-0.2, 0.2, (4, 7))
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        goals = max(goals, int(i_o[:, 9].max()))
-        for e in range(4):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 4 == 3:
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
+    for s in run.steps(45, lambda k: rng.uniform(-0.2, 0.2, (4, 7))):
+        s.compare()
+        goals = max(goals, int(s.o.info[:, 9].max()))
+        if s.k % 4 == 3:
+            s.resync()
     assert goals >= 2          # several tasks in a row within one episode
-    O.close(); G.close()
+    run.finish()
 
 
 @pytest.mark.gpu
 def test_hip_matches_oracle_with_cartesian_actions_and_the_follower():
     """The IK front-end + collision prevention in front of the lifting task (config/wrappers/safe_ik.yaml), driven by the scripted follower."""
-    import torch
-    from helpers import ATOL, RTOL, assert_state_close, make_pair
-    clips = _clips(2, 100, 130)
-    O, G = make_pair(4, dict(seed=7, horizon=200), clips=clips, env_id=ENV, ik_position_delta=dict(action_limit=0.15),
+    from helpers import make_pair
+    from parity import Run
+    O, G = make_pair(4, dict(seed=7, horizon=200), clips=_clips(2, 100, 130), env_id=ENV, ik_position_delta=dict(action_limit=0.15),
                      collision_prevention=dict(replace_type=0, n_resamples=20))
-    obs = O.reset()
-    np.testing.assert_allclose(G.reset().cpu().numpy(), obs, rtol=RTOL, atol=ATOL)
+    run = Run(O, G, "lifting follower", free_running=True, violent=None, atol=2e-6, reward_atol=2e-6, actions=(1e-6, 1e-9))
+    obs = O.obs.copy()
     held = 0
-    for k in range(48):
+
+    def actions(k):
         mid = 0.5 * (obs[:, 0:3] + obs[:, 4:7])
         a = np.zeros((4, 7))
         a[:, 0], a[:, 1], a[:, 2] = np.clip(mid[:, 0] - 0.95, -0.15, 0.15), np.clip(mid[:, 1], -0.15, 0.15), np.clip(1.5 * mid[:, 2], -0.15, 0.15)
-        ag = torch.from_numpy(a.copy()).cuda()
-        obs, r_o, d_o, i_o = O.step(a)                       # (both rewrite the action rows in place with the executed joint action)
-        o_g, r_g, d_g, i_g = G.step(ag)
-        torch.cuda.synchronize()
-        np.testing.assert_allclose(ag.cpu().numpy(), a, rtol=1e-6, atol=1e-9, err_msg=f"executed action, step {k}")
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), obs, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=2e-6, err_msg=f"step {k}")
-        held += int(O.term_obs[:, 39].sum())
-        for e in range(4):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-            if k % 4 == 3:
-                G.set_state(e, O.get_state(e))
-                G.set_box(e, O.get_box(e))
+        return a
+    for s in run.steps(48, actions):
+        s.compare()
+        obs = s.o.obs
+        held += int(s.o.term_obs[:, 39].sum())
+        if s.k % 4 == 3:
+            s.resync()
     assert held > 4 * 30
-    O.close(); G.close()
+    run.finish()
 
 
 @pytest.mark.gpu

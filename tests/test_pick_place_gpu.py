@@ -2,7 +2,8 @@
 import numpy as np
 import pytest
 
-from helpers import ATOL, RTOL, assert_state_close, make_pair, record_live
+from helpers import make_pair
+from parity import Run
 from pp_scenarios import PP, deliver, grasp_and_carry, random_actions, tumble
 
 pytestmark = pytest.mark.gpu
@@ -11,51 +12,18 @@ pytestmark = pytest.mark.gpu
 def _rollout(kw, n_envs, n_steps, seed, scenario, resync, min_live=0.9, name="", **desc_kw):
     """Oracle and HIP side by side.  resync=True copies the oracle's state into the HIP batch after every step (per-step
     parity); free-running mode drops an env once its oracle trajectory turned violent (see test_parity_gpu._rollout)."""
-    import torch
     O, G = make_pair(n_envs, kw, **PP, **desc_kw)
-    oo = O.reset()
-    og = G.reset().cpu().numpy()
-    np.testing.assert_allclose(og, oo, rtol=RTOL, atol=ATOL)
-    for e in range(n_envs):
-        assert_state_close(O.get_box(e), G.get_box(e), f"reset env {e} box")
+    run = Run(O, G, f"test_pick_place_gpu::{name or getattr(scenario, '__name__', 'scenario')}_{kw.get('shield_type')}{'' if resync else '_free'}", free_running=not resync)
     rng = np.random.RandomState(seed)
-    live = np.ones(n_envs, bool)
     stats = dict(gripped=0, success=0, box_contacts=0)
-    for k in range(n_steps):
-        a = scenario(k, [O, G], rng, n_envs)
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
-        torch.cuda.synchronize()
-        msg = f"step {k}"
-        post = [O.get_state(e) for e in range(n_envs)]
-        pbox = [O.get_box(e) for e in range(n_envs)]
-        violent = np.array([i_o[e, 11] != 0 or max(abs(v) for v in post[e].qvel) > 5.0 or max(abs(v) for v in pbox[e].vel[:3]) > 5.0 for e in range(n_envs)])
-        if not resync:
-            live &= ~violent
-        chk = live & ~violent if resync else live
-        np.testing.assert_array_equal(i_g.cpu().numpy()[chk], i_o[chk], err_msg=msg)
-        np.testing.assert_array_equal(d_g.cpu().numpy()[chk], d_o[chk], err_msg=msg)
-        np.testing.assert_allclose(o_g.cpu().numpy()[chk], o_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(r_g.cpu().numpy()[chk], r_o[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        np.testing.assert_allclose(G.term_obs.cpu().numpy()[chk], O.term_obs[chk], rtol=RTOL, atol=1e-6, err_msg=msg)
-        po, no = O.contacts()
-        pg, ng = G.contacts()
-        np.testing.assert_array_equal(ng[chk], no[chk], err_msg=msg)
-        np.testing.assert_array_equal(pg[chk], po[chk], err_msg=msg)
-        stats["gripped"] += int(o_o[chk][:, 39].sum())
-        stats["success"] += int((r_o[chk] > 0).sum())
-        stats["box_contacts"] += int((po[chk][:, :, 1] == 36).sum())
-        for e in range(n_envs):
-            if chk[e]:
-                assert_state_close(post[e], G.get_state(e), f"{msg} env {e}")
-                assert_state_close(pbox[e], G.get_box(e), f"{msg} env {e} box")
-            if resync:
-                G.set_state(e, post[e])
-                G.set_box(e, pbox[e])
-    record_live(f"test_pick_place_gpu::{name or getattr(scenario, '__name__', 'scenario')}_{kw.get('shield_type')}{'' if resync else '_free'}", live, min_live)
-    desc = O.lib  # keep the library alive until both are closed
-    O.close(); G.close()
-    del desc
+    for s in run.steps(n_steps, lambda k: scenario(k, [O, G], rng, n_envs)):
+        s.compare()
+        stats["gripped"] += int(s.o.obs[s.chk][:, 39].sum())
+        stats["success"] += int((s.o.reward[s.chk] > 0).sum())
+        stats["box_contacts"] += int((s.o.pairs[s.chk][:, :, 1] == 36).sum())
+        if resync:
+            s.resync()
+    run.finish(min_live)
     return stats
 
 
@@ -138,44 +106,37 @@ def test_full_size_properties():
 def test_cartesian_action_front_end_parity():
     """IKPositionDeltaWrapper in the kernel: [dx, dy, dz, gripper] rows are converted by the damped-least-squares IK, screened
     by the collision prevention, executed; the executed joint actions written back must agree with the oracle's."""
-    import torch
     kw = dict(shield_type="SSM", horizon=40, seed=8)
     ik = dict(action_limit=0.15)
     O, G = make_pair(12, kw, **PP, ik_position_delta=ik, collision_prevention=dict(replace_type=0, n_resamples=20))
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    run = Run(O, G, "cartesian_front_end", free_running=True, violent=None, actions=(1e-6, 1e-9))
     rng = np.random.RandomState(4)
     moved = 0.0
-    for k in range(30):
+
+    def actions(k):
         a = np.zeros((12, 7))
         a[:, :3] = rng.uniform(-0.2, 0.2, (12, 3))
         a[:, 3] = rng.uniform(-1.5, 1.5, 12)
-        ag = torch.from_numpy(a.copy()).cuda()
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(ag)
-        torch.cuda.synchronize()
-        np.testing.assert_allclose(ag.cpu().numpy(), O.last_actions, rtol=1e-6, atol=1e-9, err_msg=f"executed joint actions, step {k}")
-        moved = max(moved, float(np.abs(O.last_actions[:, :6]).max()))
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        for e in range(12):
-            assert_state_close(O.get_state(e), G.get_state(e), f"step {k} env {e}")
+        return a
+    for s in run.steps(30, actions):
+        s.compare()
+        moved = max(moved, float(np.abs(s.o.executed[:, :6]).max()))
     assert moved > 0.05
-    O.close(); G.close()
+    run.finish()
 
 
 def test_pointing_variant_parity():
     """PickPlacePointingHumanCart: the target follows the pointing arm of the human; deliveries re-place the object."""
-    import torch
     import human_robot_gym_amd as hrg
     clips = hrg.synthetic_clips(2, seed=0, min_frames=300, max_frames=600)
     clips.infos[1]["pointing_hand"] = "left"
     kw = dict(shield_type="SSM", horizon=30, seed=11, human_rand=[0.2, 0.2, 0.5], reward_shaping=True)
     O, G = make_pair(8, kw, clips=clips, env_id="PickPlacePointingHumanCart")
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    run = Run(O, G, "pointing", free_running=True, violent=None)
     rng = np.random.RandomState(2)
     wins = 0
-    for k in range(36):
+
+    def actions(k):
         if k in (5, 14):   # put the cube where the human points
             for e in range(8):
                 bx = O.get_box(e)
@@ -185,18 +146,11 @@ def test_pointing_variant_parity():
                     for i in range(6):
                         b.vel[i] = 0.0
                     B_.set_box(e, b)
-        a = rng.uniform(-1, 1, (8, 7))
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=1e-6, err_msg=f"step {k}")
-        wins += int(i_o[:, 9].max() > 0)
-        for e in range(8):
-            assert_state_close(O.get_box(e), G.get_box(e), f"step {k} env {e} box")
-    O.close(); G.close()
+        return rng.uniform(-1, 1, (8, 7))
+    for s in run.steps(36, actions):
+        s.compare()
+        wins += int(s.o.info[:, 9].max() > 0)
+    run.finish()
 
 
 def test_long_run_stays_finite_and_on_the_table():
@@ -266,40 +220,32 @@ def test_reach_human_with_its_small_box_parity():
     """ReachHuman + smallBox (task HRG_TASK_REACH_BOX, cube kernel with ReachHuman's task logic): HIP vs oracle, incl. an arm that is handed the box."""
     import torch
     import human_robot_gym_amd as hrg
-    from oracle.oracle import OracleBatch
     from human_robot_gym_amd._lib import HipBatch
     clips = hrg.synthetic_clips(3, seed=0, min_frames=300, max_frames=600)
     kw = dict(shield_type="SSM", horizon=25, reward_shaping=True, seed=6)
-    O = OracleBatch(hrg.build_model_desc(kw, n_clips=3, reach_box=True), clips, 12)
-    G = HipBatch(hrg.build_model_desc(kw, n_clips=3, reach_box=True), clips, 12)
+    O, G = make_pair(12, kw, clips=clips, reach_box=True)
     L = HipBatch(hrg.build_model_desc(kw, n_clips=3), clips, 12)                     # the lean kernel: same episodes while nothing touches the box
-    np.testing.assert_allclose(G.reset().cpu().numpy(), O.reset(), rtol=RTOL, atol=ATOL)
+    run = Run(O, G, "reach_box", violent=None)
     L.reset()
     rng = np.random.RandomState(3)
     n_static = 0
-    for k in range(40):
+
+    def actions(k):
         a = rng.uniform(-1, 1, (12, 7))
         if k == 8:    # hand the box to the arm
             for e in range(0, 12, 2):
-                s, bx = O.get_state(e), O.get_box(e)
-                bx.pos[:] = [s.eef_pos[0], s.eef_pos[1], s.eef_pos[2] - 0.02]
+                st, bx = O.get_state(e), O.get_box(e)
+                bx.pos[:] = [st.eef_pos[0], st.eef_pos[1], st.eef_pos[2] - 0.02]
                 bx.vel[:] = [0.0] * 6
                 O.set_box(e, bx); G.set_box(e, bx)
-        o_o, r_o, d_o, i_o = O.step(a)
-        o_g, r_g, d_g, i_g = G.step(torch.from_numpy(a).cuda())
-        o_l, r_l, d_l, i_l = L.step(torch.from_numpy(a).cuda())
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(i_g.cpu().numpy(), i_o, err_msg=f"step {k}")
-        np.testing.assert_array_equal(d_g.cpu().numpy(), d_o)
-        np.testing.assert_allclose(o_g.cpu().numpy(), o_o, rtol=RTOL, atol=1e-6)
-        np.testing.assert_allclose(r_g.cpu().numpy(), r_o, rtol=RTOL, atol=1e-6)
-        if k < 8:
-            np.testing.assert_allclose(o_l.cpu().numpy(), o_o, rtol=RTOL, atol=1e-6)    # lean model == box model while the box is left alone
-        n_static += int(i_o[:, 3].sum())
-        for e in range(12):
-            post, pbox = O.get_state(e), O.get_box(e)
-            assert_state_close(post, G.get_state(e), f"step {k} env {e}")
-            assert_state_close(pbox, G.get_box(e), f"step {k} env {e} box")
-            G.set_state(e, post); G.set_box(e, pbox)
+        return a
+    for s in run.steps(40, actions):
+        o_l = L.step(torch.from_numpy(s.a).cuda())[0]
+        s.compare()
+        if s.k < 8:
+            np.testing.assert_allclose(o_l.cpu().numpy(), s.o.obs, rtol=1e-5, atol=1e-6)    # lean model == box model while the box is left alone
+        n_static += int(s.o.info[:, 3].sum())
+        s.resync()
     assert n_static > 0
-    O.close(); G.close(); L.close()
+    run.finish()
+    L.close()
