@@ -386,7 +386,7 @@ static double layered_sines(const hrgo_batch* b, int64_t gid, const hrg_env_stat
 
 static void stack_animation_time(const hrgo_batch* b, int64_t gid, const hrg_env_state* s, hrg_stack_state* sk, int clip, int* at_io);
 static void hammer_animation_time(const hrgo_batch* b, int64_t gid, const hrg_env_state* s, hrg_hammer_state* hm, int clip, int* at_io);
-static void human_control_all(const hrgo_batch* b, int64_t gid, hrg_env_state* s, hrg_box_state* bx, hrg_stack_state* sk, hrg_hammer_state* hm, double* mocap_pos, double* mocap_quat, const double** qh) {
+static void human_control(const hrgo_batch* b, int64_t gid, hrg_env_state* s, hrg_box_state* bx, hrg_stack_state* sk, hrg_hammer_state* hm, double* mocap_pos, double* mocap_quat, const double** qh) {
   const hrg_model_desc* m = &b->m;
   /* human_env.py:1719-1731 */
   int control_time = (int)floor((double)s->low_level_time / m->anim_step_length);
@@ -462,13 +462,6 @@ static void human_control_all(const hrgo_batch* b, int64_t gid, hrg_env_state* s
   quatmul(q1, s->human_rot_offset, qbi);
   quatmul(mocap_quat, q1, qa);
   *qh = fr + 7;
-}
-
-static void human_control_sk(const hrgo_batch* b, int64_t gid, hrg_env_state* s, hrg_box_state* bx, hrg_stack_state* sk, double* mocap_pos, double* mocap_quat, const double** qh) {
-  human_control_all(b, gid, s, bx, sk, NULL, mocap_pos, mocap_quat, qh);
-}
-static void human_control(const hrgo_batch* b, int64_t gid, hrg_env_state* s, hrg_box_state* bx, double* mocap_pos, double* mocap_quat, const double** qh) {
-  human_control_all(b, gid, s, bx, NULL, NULL, mocap_pos, mocap_quat, qh);
 }
 
 static void human_fk(const hrg_model_desc* m, const double* mocap_pos, const double* mocap_quat, const double* qh, human_kin* h, double site[HRG_NHJ][3]) {
@@ -1930,6 +1923,279 @@ static void eef_of(const hrg_model_desc* m, const robot_kin* k, double* eef) {
   v3add(eef, k->p[NARM - 1], t);
 }
 
+static void env_reset(hrgo_batch* B, int e, float* obs);
+
+/* =============================================================================================== stages of a policy step
+ * What env_step, env_step_stack and env_step_hammer have in common, in the order a cycle runs them; each stepper is these stages plus its family's own
+ * parts.  nv = width of the stepper's constrained system (NV, NVT, NVMAX or NVH): the robot tree's DoF come first, then the free bodies'.
+ * A stage is inlined into each stepper that runs it: as functions of their own they cost the stacking and hammering tasks 10 - 17 % of the CPU baseline's
+ * rate (bench.py's cpu_baseline leg; profiles/r09_oracle_refactor.txt). */
+#define STAGE static inline __attribute__((always_inline))
+
+/* a free body of the constrained system beyond the robot tree: contact_t.b1 / b2 = BODY_BOX + its index in the stepper's table */
+typedef struct {
+  const double *pos, *quat;       /* world pose of the free joint */
+  int dof;                        /* first of its six DoF */
+  double invweight, invweight_rot; /* body_invweight0: translational (1/m for a free body), rotational */
+  const double* slide_axis;       /* a body riding on this one on a slide joint (the nail): world axis, or NULL */
+  int slide_dof;
+} free_body;
+
+/* _control_human (human_env.py:516-519): animation frame -> pelvis mocap pose -> FK of the human tree and its measurement sites */
+STAGE void pose_human(const hrgo_batch* B, int64_t gid, hrg_env_state* s, hrg_box_state* bx, hrg_stack_state* sk, hrg_hammer_state* hm, human_kin* hk) {
+  double mp[3], mq[4];
+  const double* qh;
+  human_control(B, gid, s, bx, sk, hm, mp, mq, &qh);
+  human_fk(&B->m, mp, mq, qh, hk, s->human_site);
+}
+
+/* controller goal of a policy step (SingleArm.control -> set_goal): failsafe_controller.py:252-300 */
+STAGE void controller_goal(const hrg_model_desc* m, hrg_env_state* s, const double* M, const double* action) {
+  for (int i = 0; i < NARM; i++) for (int j = 0; j < NARM; j++) s->mass_matrix[i * NARM + j] = M[i * NV + j];
+  double scale = fabs(m->act_out_max - m->act_out_min) / fabs(m->act_in_max - m->act_in_min);
+  double otr = 0.5 * (m->act_out_max + m->act_out_min), itr = 0.5 * (m->act_in_max + m->act_in_min);
+  for (int j = 0; j < NARM; j++) {
+    double a = clampd(action[j], m->act_in_min, m->act_in_max);
+    double g = s->qpos[j] + ((a - itr) * scale + otr);
+    s->goal_qpos[j] = clampd(g, m->qpos_limits[0][j], m->qpos_limits[1][j]);
+    s->new_goal_q[j] = s->goal_qpos[j];
+  }
+  s->new_goal = 1; /* newLongTermTrajectory, failsafe_controller.py:300 */
+}
+
+/* run_controller after the shield's step: PD+ arm torques, gripper command, and the count of fail-safe interventions (once per policy step) */
+STAGE void arm_and_gripper_ctrl(const hrg_model_desc* m, hrg_env_state* s, const double* bias, const double* action, double* ctrl, int* failsafe_intervention) {
+  for (int i = 0; i < NARM; i++) { /* failsafe_controller.py:356-369 */
+    double t = 0;
+    for (int j = 0; j < NARM; j++) t += s->mass_matrix[i * NARM + j] * (m->kp * (s->des_q[j] - s->qpos[j]) + m->kd * (s->des_v[j] - s->qvel[j]) + s->des_a[j]);
+    ctrl[i] = clampd(t + bias[i], m->arm_ctrlrange[i][0], m->arm_ctrlrange[i][1]);
+  }
+  { /* RethinkGripper.format_action + actuator ctrl range mapping; +1 closes, -1 opens (experts/pick_place_human_cart_expert.py:282-288), finger 0 opens towards positive qpos (rethink_valid_gripper.py:25-42) */
+    double a = action[NARM], sg = a > 0 ? 1.0 : (a < 0 ? -1.0 : 0.0);
+    s->grip_action = clampd(s->grip_action - m->gripper_speed * sg, -1.0, 1.0);
+    for (int f = 0; f < HRG_NFINGER; f++) {
+      double lo = m->finger_ctrlrange[f][0], hi = m->finger_ctrlrange[f][1];
+      ctrl[NARM + f] = 0.5 * (hi + lo) + 0.5 * (hi - lo) * (f == 0 ? s->grip_action : -s->grip_action);
+    }
+  }
+  if (!*failsafe_intervention && !s->is_safe) { *failsafe_intervention = 1; s->failsafe_interventions++; } /* human_env.py:509-513 */
+}
+
+/* contact bookkeeping of a cycle (human_env.py:522): collision classification at the robot capsules' centres, contact pairs kept for hrgo_contacts */
+STAGE void record_contacts(const hrg_model_desc* m, const robot_kin* k, hrg_env_state* s, const contact_t* con, int ncon, int* has_collision, int* collision_type) {
+  double rc[HRG_NRCAP][3], Rb[9];
+  quat2mat(Rb, m->base_quat);
+  for (int c = 0; c < HRG_NRCAP; c++) {
+    int b = m->rcap_body[c];
+    double t[3], mid[3];
+    for (int a = 0; a < 3; a++) mid[a] = 0.5 * (m->rcap_p1[c][a] + m->rcap_p2[c][a]);
+    m3mulv(t, b < 0 ? Rb : k->R[b], mid);
+    v3add(rc[c], b < 0 ? m->base_pos : k->p[b], t);
+  }
+  classify(m, k, s, con, ncon, rc, has_collision, collision_type);
+  s->ncon = ncon;
+  for (int c = 0; c < HRG_NCON_MAX; c++) { s->con_pairs[c][0] = c < ncon ? con[c].g1 : -1; s->con_pairs[c][1] = c < ncon ? con[c].g2 : -1; }
+}
+
+/* the robot tree's part of sim.step() (human_env.py:523): applied force (arm torques, finger position actuators, damping, bias) -> smooth acceleration
+ * a0[0..NV) and velocity qd[0..NV); M into the top-left block of the (zeroed) nv x nv mass matrix Mt.  0: M is not positive definite */
+STAGE int robot_smooth(const hrg_model_desc* m, const hrg_env_state* s, const double* M, const double* bias, const double* ctrl, int nv, double* Mt, double* a0, double* qd) {
+  double LM[NV * NV];
+  memcpy(LM, M, sizeof LM);
+  if (!chol(LM, NV)) return 0;
+  for (int i = 0; i < NV; i++) {
+    double act = ctrl[i];
+    if (i >= NARM) act = clampd(m->finger_kp * (ctrl[i] - s->qpos[i]), m->finger_forcerange[0], m->finger_forcerange[1]);
+    a0[i] = act - m->jnt_damping[i] * s->qvel[i] - bias[i];
+    qd[i] = s->qvel[i];
+  }
+  chol_solve(LM, NV, a0);
+  for (int i = 0; i < NV; i++) for (int j = 0; j < NV; j++) Mt[i * nv + j] = M[i * NV + j];
+  return 1;
+}
+
+/* a cube (box_mass, box_inertia) on a free joint at DoF o, world-frame angular velocity: M = blockdiag(m 1, R diag(I) R'), bias torque w x (R diag(I) R' w),
+ * gravity.  The rotational inertia is split into mean * 1 + R diag(I - mean) R': a cube keeps an exactly diagonal M and no gyroscopic term */
+STAGE void free_body_block(const hrg_model_desc* m, const double* quat, const double* vel, int nv, int o, double* Mt, double* a0, double* qd) {
+  double Rx[9], Mdev[9], w[3] = {vel[3], vel[4], vel[5]}, Ld[3], Lw[3], tau[3], tl[3];
+  quat2mat(Rx, quat);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
+    double t = 0;
+    for (int kk = 0; kk < 3; kk++) t += Rx[3 * i + kk] * (m->box_inertia[kk] - m->box_inertia_mean) * Rx[3 * j + kk];
+    Mdev[3 * i + j] = t;
+  }
+  for (int kk = 0; kk < 3; kk++) Ld[kk] = (m->box_inertia[kk] - m->box_inertia_mean) * (Rx[kk] * w[0] + Rx[3 + kk] * w[1] + Rx[6 + kk] * w[2]);
+  m3mulv(Lw, Rx, Ld); /* R diag(I - mean) R' w */
+  v3cross(tau, Lw, w); /* -(w x L) */
+  for (int kk = 0; kk < 3; kk++) tl[kk] = (Rx[kk] * tau[0] + Rx[3 + kk] * tau[1] + Rx[6 + kk] * tau[2]) / m->box_inertia[kk]; /* diag(1/I) R' tau */
+  for (int a = 0; a < 3; a++) {
+    Mt[(o + a) * nv + o + a] = m->box_mass;
+    for (int b = 0; b < 3; b++) Mt[(o + 3 + a) * nv + o + 3 + b] = (a == b ? m->box_inertia_mean : 0.0) + Mdev[3 * a + b];
+    a0[o + a] = m->gravity[a];
+    a0[o + 3 + a] = Rx[3 * a] * tl[0] + Rx[3 * a + 1] * tl[1] + Rx[3 * a + 2] * tl[2];
+  }
+  for (int a = 0; a < HRG_NBOXV; a++) qd[o + a] = vel[a];
+}
+
+/* constraint rows of the robot tree: friction loss of its joints ... */
+STAGE void friction_rows(const hrg_model_desc* m, efc_t* E, const double* qd) {
+  for (int i = 0; i < NV; i++)
+    if (m->jnt_frictionloss[i] > 0) { double J[NVMAX] = {0}; J[i] = 1; efc_add(m, E, J, qd, ROW_FRICTION, 0, 0, m->jnt_frictionloss[i], m->dof_invweight0[i]); }
+}
+/* ... and joint limits; limit_row: the two unilateral rows of one joint at distances dlo / dhi from the ends of its range */
+STAGE void limit_row(const hrg_model_desc* m, efc_t* E, const double* qd, int dof, double dlo, double dhi, double invweight) {
+  if (dlo < 0) { double J[NVMAX] = {0}; J[dof] = 1; efc_add(m, E, J, qd, ROW_UNILATERAL, dlo, 0, 0, invweight); }
+  if (dhi < 0) { double J[NVMAX] = {0}; J[dof] = -1; efc_add(m, E, J, qd, ROW_UNILATERAL, dhi, 0, 0, invweight); }
+}
+STAGE void limit_rows(const hrg_model_desc* m, const hrg_env_state* s, efc_t* E, const double* qd) {
+  for (int i = 0; i < NV; i++) limit_row(m, E, qd, i, s->qpos[i] - m->jnt_range[i][0], m->jnt_range[i][1] - s->qpos[i], m->dof_invweight0[i]);
+}
+
+/* pyramidal frictional contact rows of the first ncon_dyn contacts; fb: the stepper's free bodies (body code BODY_BOX + index) */
+STAGE void contact_rows(const hrg_model_desc* m, const robot_kin* k, const contact_t* con, int ncon, int ncon_dyn, const free_body* fb, efc_t* E, const double* qd) {
+  for (int c = 0; c < ncon && c < ncon_dyn; c++) {
+    const double* n = con[c].n;
+    double t1[3], t2[3], e1[3] = {1, 0, 0}, e2[3] = {0, 1, 0};
+    v3cross(t1, n, fabs(n[0]) < 0.5 ? e1 : e2);
+    v3scl(t1, t1, 1.0 / v3norm(t1));
+    v3cross(t2, n, t1);
+    double margin = (con[c].g2 >= GEOM_HUMAN0 && con[c].g2 < GEOM_TABLE) || (con[c].g1 >= GEOM_HUMAN0 && con[c].g1 < GEOM_TABLE) ? m->contact_margin_human : 0.0; /* a human geom on either side */
+    for (int d = 0; d < 4; d++) {
+      double dir[3], J[NVMAX] = {0};
+      const double* tt = d < 2 ? t1 : t2;
+      double sg = (d & 1) ? -1.0 : 1.0;
+      for (int a = 0; a < 3; a++) dir[a] = n[a] + sg * m->friction_static * tt[a];
+      /* separation velocity along n (from geom1 to geom2): v2 - v1 */
+      if (con[c].b1 >= 0 && con[c].b1 < NV) robot_point_jac(m, k, con[c].b1, con[c].pos, dir, -1.0, J);
+      if (con[c].b2 >= 0 && con[c].b2 < NV) robot_point_jac(m, k, con[c].b2, con[c].pos, dir, +1.0, J);
+      double diag = (con[c].b1 >= 0 && con[c].b1 < NV ? m->body_invweight0[con[c].b1] : 0.0) + (con[c].b2 >= 0 && con[c].b2 < NV ? m->body_invweight0[con[c].b2] : 0.0);
+      for (int side = 0; side < 2; side++) { /* free bodies: J = +-dir . (v + w x r), body_invweight0 = 1/m; the nail's point moves with the board and along the slide axis */
+        const int body = side ? con[c].b2 : con[c].b1;
+        if (body < BODY_BOX) continue;
+        const free_body* f = &fb[body - BODY_BOX];
+        const double sgn = side ? 1.0 : -1.0;
+        double r[3], rxd[3];
+        v3sub(r, con[c].pos, f->pos);
+        v3cross(rxd, r, dir);
+        for (int a = 0; a < 3; a++) { J[f->dof + a] = sgn * dir[a]; J[f->dof + 3 + a] = sgn * rxd[a]; }
+        if (f->slide_axis) J[f->slide_dof] = sgn * v3dot(dir, f->slide_axis);
+        diag += f->invweight;
+      }
+      const int n_before = E->n;
+      efc_add(m, E, J, qd, ROW_UNILATERAL, con[c].dist, margin, 0, diag * (1.0 + m->friction_static * m->friction_static));
+      if (E->n > n_before) E->grp[n_before] = 4 * c + d; /* noslip pairs the opposing edges */
+    }
+  }
+}
+
+/* connect equality: the body's point `anchor` (body frame) follows the mocap position mp; residual = p + R anchor - mp, velocity of the point = v + w x r */
+STAGE void connect_rows(const hrg_model_desc* m, efc_t* E, const double* qd, const free_body* f, const double* anchor, const double* mp) {
+  double R[9], rr[3], pt[3];
+  quat2mat(R, f->quat);
+  m3mulv(rr, R, anchor);
+  v3add(pt, f->pos, rr);
+  for (int a = 0; a < 3; a++) {
+    double J[NVMAX] = {0}, ea[3] = {a == 0, a == 1, a == 2}, rxe[3];
+    v3cross(rxe, rr, ea); /* (w x r) . e_a = w . (r x e_a) */
+    J[f->dof + a] = 1;
+    for (int b_ = 0; b_ < 3; b_++) J[f->dof + 3 + b_] = rxe[b_];
+    efc_add(m, E, J, qd, ROW_EQUALITY, pt[a] - mp[a], 0, 0, f->invweight);
+  }
+}
+
+/* weld equality of the body's frame onto the pose (tp, qt): residual = [p - tp; rotation vector of q qt^-1] on the body's own DoF; the target has no
+ * velocity.  tp = NULL: the three rotation rows only (the position is held by connects) */
+STAGE void weld_rows(const hrg_model_desc* m, efc_t* E, const double* qd, const free_body* f, const double* tp, const double* qt) {
+  double erot[3], qe[4];
+  const double qc[4] = {qt[0], -qt[1], -qt[2], -qt[3]};
+  quatmul(qe, f->quat, qc);
+  if (qe[0] < 0) for (int a = 0; a < 4; a++) qe[a] = -qe[a];
+  const double sn = sqrt(qe[1] * qe[1] + qe[2] * qe[2] + qe[3] * qe[3]), ang = 2.0 * atan2(sn, qe[0]);
+  for (int a = 0; a < 3; a++) erot[a] = sn > 1e-12 ? qe[1 + a] / sn * ang : 0.0;
+  if (tp) {
+    double epos[3];
+    v3sub(epos, f->pos, tp);
+    for (int a = 0; a < 3; a++) { double J[NVMAX] = {0}; J[f->dof + a] = 1; efc_add(m, E, J, qd, ROW_EQUALITY, epos[a], 0, 0, f->invweight); }
+  }
+  for (int a = 0; a < 3; a++) { double J[NVMAX] = {0}; J[f->dof + 3 + a] = 1; efc_add(m, E, J, qd, ROW_EQUALITY, erot[a], 0, 0, f->invweight_rot); }
+}
+
+/* the end of sim.step() for the robot tree; qacc = the nv accelerations the solver returned.  0: the simulation crashed */
+STAGE int robot_euler(const hrg_model_desc* m, hrg_env_state* s, const double* M, const double* qacc, int nv) {
+  const double h = m->timestep;
+  /* mj_checkAcc -> MujocoException handler (human_env.py:527-546) */
+  for (int i = 0; i < nv; i++) if (!(fabs(qacc[i]) < 1e10)) return 0;
+  memcpy(s->qacc_warmstart, qacc, sizeof(double) * NV);
+  /* mj_Euler with implicit joint damping: (M + h D) qacc' = M qacc */
+  double Mh[NV * NV], rhs[NV];
+  memcpy(Mh, M, sizeof Mh);
+  for (int i = 0; i < NV; i++) { Mh[i * NV + i] += h * m->jnt_damping[i]; double t = 0; for (int j = 0; j < NV; j++) t += M[i * NV + j] * qacc[j]; rhs[i] = t; }
+  if (!chol(Mh, NV)) return 0;
+  chol_solve(Mh, NV, rhs);
+  for (int i = 0; i < NV; i++) { s->qvel[i] += h * rhs[i]; s->qpos[i] += h * s->qvel[i]; }
+  return 1;
+}
+
+/* mj_Euler of a free joint: no damping; quaternion integrated with the world-frame angular velocity */
+STAGE void free_body_euler(double h, const double* qacc, double* pos, double* quat, double* vel, double* acc_warmstart) {
+  memcpy(acc_warmstart, qacc, sizeof(double) * HRG_NBOXV);
+  for (int a = 0; a < HRG_NBOXV; a++) vel[a] += h * qacc[a];
+  for (int a = 0; a < 3; a++) pos[a] += h * vel[a];
+  double w[3] = {vel[3], vel[4], vel[5]}, wn = v3norm(w), ang = h * wn;
+  if (wn > 1e-12) {
+    double sh = sin(0.5 * ang) / wn, dq[4] = {cos(0.5 * ang), w[0] * sh, w[1] * sh, w[2] * sh}, qn[4];
+    quatmul(qn, dq, quat);
+    double nn = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+    for (int a = 0; a < 4; a++) quat[a] = qn[a] / nn;
+  }
+}
+
+/* _progress_to_next_animation, human_env.py:1698-1708 + 663-670 */
+STAGE void next_animation(const hrg_model_desc* m, hrg_env_state* s) {
+  s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
+  s->animation_time = 0;
+  s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+}
+
+/* the info columns every task has (human_env.py:561-581); column 13 is the task's own */
+STAGE void fill_info(const hrg_model_desc* m, const hrg_env_state* s, int has_collision, int collision_type, int crash, int32_t* info) {
+  int ncoll = s->n_collisions_static + s->n_collisions_robot + s->n_collisions_human + s->n_collisions_critical;
+  info[HRG_INFO_COLLISION] = has_collision;
+  info[HRG_INFO_COLLISION_TYPE] = collision_type;
+  info[HRG_INFO_N_COLLISIONS] = ncoll;
+  info[HRG_INFO_N_COLLISIONS_STATIC] = s->n_collisions_static;
+  info[HRG_INFO_N_COLLISIONS_ROBOT] = s->n_collisions_robot;
+  info[HRG_INFO_N_COLLISIONS_HUMAN] = s->n_collisions_human;
+  info[HRG_INFO_N_COLLISIONS_CRITICAL] = s->n_collisions_critical;
+  info[HRG_INFO_TIMEOUT] = s->timestep >= m->horizon;
+  info[HRG_INFO_FAILSAFE_INTERVENTIONS] = s->failsafe_interventions;
+  info[HRG_INFO_N_GOAL_REACHED] = s->n_goal_reached;
+  info[HRG_INFO_SIM_CRASH] = crash;
+  info[HRG_INFO_TRUNCATED] = 0;
+  info[HRG_INFO_ACTION_RESAMPLES] = s->action_resamples;
+}
+
+/* HumanEnv.reward / _check_done around the task's sparse reward *r (dense: the task's _dense_reward); returns done */
+STAGE int reward_and_done(const hrg_model_desc* m, hrg_env_state* s, int collision_type, int crash, int goal_reached, double dense, double* r) {
+  if (goal_reached) s->n_goal_reached++;
+  int illegal = (collision_type & (HRG_COL_STATIC | HRG_COL_ROBOT | HRG_COL_HUMAN_CRIT)) != 0; /* human_env.py:860-878 */
+  if (m->reward_shaping) *r += 1.0 + dense; /* human_env.py:650-651 */
+  if (illegal) *r += m->collision_reward;
+  *r *= m->reward_scale;
+  if (crash) { *r += m->sim_crash_reward; return 1; }
+  return (m->done_at_collision && illegal) || (m->done_at_success && goal_reached); /* human_env.py:835-858 */
+}
+
+/* time limit, outputs, auto-reset */
+STAGE void finish_step(hrgo_batch* B, int e, double r, int d, float* obs, const float* term_obs, float* reward, uint8_t* done, int32_t* info) {
+  const hrg_env_state* s = &B->st[e];
+  if (s->timestep >= B->m.horizon) { info[HRG_INFO_TRUNCATED] = !d; d = 1; } /* time_limit.py:40-43 */
+  *reward = (float)r;
+  *done = (uint8_t)d;
+  if (d) env_reset(B, e, obs); /* VecEnv auto-reset; terminal observation stays in term_obs */
+  else memcpy(obs, term_obs, sizeof(float) * HRG_OBS_DIM);
+}
+
 static void env_reset_stack(hrgo_batch* B, int e, const robot_kin* k);
 static void compute_obs_stack(const hrgo_batch* B, int64_t gid, const hrg_env_state* s, hrg_stack_state* sk, float* obs);
 static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, float* term_obs, float* reward, uint8_t* done, int32_t* info);
@@ -1996,20 +2262,14 @@ static void env_reset(hrgo_batch* B, int e, float* obs) {
                                              * with the object welded into the holding hand.  The reference teleports it to the stale mocap pose first
                                              * and lets the weld drag it over; here the hand pose of the first animation frame is used directly */
       human_kin hk;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk, s->human_site);
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
       handover_mocap(B, gid, s, bx, &hk);
       handover_pickup(bx);
     }
     if (m->task == HRG_TASK_LIFTING) { /* _reset_internal (670-681): _control_human + _reset_animation; the human holds the board from the start (reset's
                                         * deterministic branch, 696-700: the grasp-and-retry loop of 702-735 is not run) */
       human_kin hk;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk, s->human_site);
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
       lifting_mocap(m, s, bx);
       lifting_place_board(m, &k, s->eef_pos, bx);
       bx->weld_active = 1;
@@ -2017,10 +2277,7 @@ static void env_reset(hrgo_batch* B, int e, float* obs) {
     }
     if (m->task == HRG_TASK_HANDOVER_R2H) { /* _reset_animation (the human holds nothing) + _control_human (650-660, 700-706): object in its bin, hand = target */
       human_kin hk;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk, s->human_site);
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
       handover_mocap(B, gid, s, bx, &hk);
     }
     if (m->task != HRG_TASK_LIFTING) v3cpy(bx->obs_pos, bx->pos);
@@ -2046,6 +2303,8 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
   double M[NV * NV], bias[NV];
   hrg_box_state* bx = m->task != HRG_TASK_REACH ? &B->box[e] : NULL;
   const int nvt = bx ? NVT : NV, ncon_dyn = bx ? HRG_NCON_DYN_BOX : HRG_NCON_DYN;
+  free_body box = {0}; /* the cube is always geom 2 of its contacts */
+  if (bx) box = (free_body){bx->pos, bx->quat, NV, 1.0 / m->box_mass, m->box_invweight_rot, NULL, 0};
   int palm_hit = 0;
   for (int cyc = 0; cyc < m->n_cycles && !crash; cyc++) {
     /* ---- sim.forward() #1 (human_env.py:504): positions, M, bias at the current state ---- */
@@ -2053,212 +2312,73 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
     robot_crba(m, &k, M);
     robot_bias(m, &k, s->qvel, bias);
     /* ---- controller (SingleArm.control -> set_goal / run_controller) ---- */
-    if (cyc == 0) { /* policy step: failsafe_controller.py:252-300 */
-      for (int i = 0; i < NARM; i++) for (int j = 0; j < NARM; j++) s->mass_matrix[i * NARM + j] = M[i * NV + j];
-      double scale = fabs(m->act_out_max - m->act_out_min) / fabs(m->act_in_max - m->act_in_min);
-      double otr = 0.5 * (m->act_out_max + m->act_out_min), itr = 0.5 * (m->act_in_max + m->act_in_min);
-      for (int j = 0; j < NARM; j++) {
-        double a = clampd(action[j], m->act_in_min, m->act_in_max);
-        double g = s->qpos[j] + ((a - itr) * scale + otr);
-        s->goal_qpos[j] = clampd(g, m->qpos_limits[0][j], m->qpos_limits[1][j]);
-        s->new_goal_q[j] = s->goal_qpos[j];
-      }
-      s->new_goal = 1; /* newLongTermTrajectory, failsafe_controller.py:300 */
-    }
+    if (cyc == 0) controller_goal(m, s, M, action);
     shield_step(B, e, s->time); /* humanMeasurement + SafetyShield.step, human_env.py:505, failsafe_controller.py:329 */
     double ctrl[NV];
-    for (int i = 0; i < NARM; i++) { /* failsafe_controller.py:356-369 */
-      double t = 0;
-      for (int j = 0; j < NARM; j++) t += s->mass_matrix[i * NARM + j] * (m->kp * (s->des_q[j] - s->qpos[j]) + m->kd * (s->des_v[j] - s->qvel[j]) + s->des_a[j]);
-      ctrl[i] = clampd(t + bias[i], m->arm_ctrlrange[i][0], m->arm_ctrlrange[i][1]);
-    }
-    { /* RethinkGripper.format_action + actuator ctrl range mapping; +1 closes, -1 opens (experts/pick_place_human_cart_expert.py:282-288), finger 0 opens towards positive qpos (rethink_valid_gripper.py:25-42) */
-      double a = action[NARM], sg = a > 0 ? 1.0 : (a < 0 ? -1.0 : 0.0);
-      s->grip_action = clampd(s->grip_action - m->gripper_speed * sg, -1.0, 1.0);
-      for (int f = 0; f < HRG_NFINGER; f++) {
-        double lo = m->finger_ctrlrange[f][0], hi = m->finger_ctrlrange[f][1];
-        ctrl[NARM + f] = 0.5 * (hi + lo) + 0.5 * (hi - lo) * (f == 0 ? s->grip_action : -s->grip_action);
-      }
-    }
-    if (!failsafe_intervention && !s->is_safe) { failsafe_intervention = 1; s->failsafe_interventions++; } /* human_env.py:509-513 */
+    arm_and_gripper_ctrl(m, s, bias, action, ctrl, &failsafe_intervention);
     /* ---- _control_human + sim.forward() #2 (human_env.py:516-519) ---- */
-    double mp[3], mq[4];
-    const double* qh;
-    human_control(B, gid, s, bx, mp, mq, &qh);
-    human_fk(m, mp, mq, qh, &hk, s->human_site);
+    pose_human(B, gid, s, bx, NULL, NULL, &hk);
     if (m->task == HRG_TASK_LIFTING) lifting_mocap(m, s, bx); /* CollaborativeLiftingCart._control_human (583-588) */
     /* HumanRobotHandoverCart._control_human (human_robot_handover_cartesian_env.py:598-633) runs one more sim.step() with the new human
      * pose before it re-poses the hand mocap body: pass 0 = that step (no bookkeeping), pass 1 = the cycle's regular step */
     for (int pass = HRG_IS_HANDOVER(m->task) ? 0 : 1; pass < 2 && !crash; pass++) {
-    /* ---- contacts + bookkeeping (human_env.py:522) ---- */
-    contact_t con[HRG_NCON_MAX];
-    int ncon = collide(m, &k, &hk, bx, con);
-    if (bx) { /* _check_grasp [UPSTREAM robosuite]: both fingers touch the object (pick_place_human_cartesian_env.py:804-809) */
-      int f0 = 0, f1 = 0;
-      for (int c = 0; c < ncon; c++) if (con[c].g2 == GEOM_BOX) { f0 |= con[c].g1 == HRG_NRCAP - 2; f1 |= con[c].g1 == HRG_NRCAP - 1; }
-      bx->gripped = f0 && f1;
-    }
-    double rc[HRG_NRCAP][3], Rb[9];
-    quat2mat(Rb, m->base_quat);
-    for (int c = 0; c < HRG_NRCAP; c++) {
-      int b = m->rcap_body[c];
-      double t[3], mid[3];
-      for (int a = 0; a < 3; a++) mid[a] = 0.5 * (m->rcap_p1[c][a] + m->rcap_p2[c][a]);
-      m3mulv(t, b < 0 ? Rb : k.R[b], mid);
-      v3add(rc[c], b < 0 ? m->base_pos : k.p[b], t);
-    }
-    if (pass == 1) {
-      if (m->task == HRG_TASK_HANDOVER_R2H) palm_hit = palm_contact(B, gid, s, bx, &hk); /* sim.data.contact of the cycle's collision phase */
-      classify(m, &k, s, con, ncon, rc, &has_collision, &collision_type);
-      s->ncon = ncon;
-      for (int c = 0; c < HRG_NCON_MAX; c++) { s->con_pairs[c][0] = c < ncon ? con[c].g1 : -1; s->con_pairs[c][1] = c < ncon ? con[c].g2 : -1; }
-    }
-    /* ---- sim.step() (human_env.py:523): smooth acceleration, constraints, Euler ---- */
-    double LM[NV * NV], a0[NVT], frc[NV], qd[NVT], Mt[NVT * NVT];
-    memcpy(LM, M, sizeof LM);
-    if (!chol(LM, NV)) { crash = 1; break; }
-    for (int i = 0; i < NV; i++) {
-      double act = ctrl[i];
-      if (i >= NARM) act = clampd(m->finger_kp * (ctrl[i] - s->qpos[i]), m->finger_forcerange[0], m->finger_forcerange[1]);
-      frc[i] = act - m->jnt_damping[i] * s->qvel[i] - bias[i];
-      a0[i] = frc[i];
-      qd[i] = s->qvel[i];
-    }
-    chol_solve(LM, NV, a0);
-    if (bx) { /* free box, world-frame angular velocity: M = blockdiag(m 1, R diag(I) R'), bias torque w x (R diag(I) R' w), gravity.
-               * The rotational inertia is split into mean * 1 + R diag(I - mean) R': a cube keeps an exactly diagonal M and no gyroscopic term */
-      double Rx[9], Mdev[9], w[3] = {bx->vel[3], bx->vel[4], bx->vel[5]}, Ld[3], Lw[3], tau[3], tl[3];
-      quat2mat(Rx, bx->quat);
-      for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-        double t = 0;
-        for (int kk = 0; kk < 3; kk++) t += Rx[3 * i + kk] * (m->box_inertia[kk] - m->box_inertia_mean) * Rx[3 * j + kk];
-        Mdev[3 * i + j] = t;
+      /* ---- contacts + bookkeeping (human_env.py:522) ---- */
+      contact_t con[HRG_NCON_MAX];
+      int ncon = collide(m, &k, &hk, bx, con);
+      if (bx) { /* _check_grasp [UPSTREAM robosuite]: both fingers touch the object (pick_place_human_cartesian_env.py:804-809) */
+        int f0 = 0, f1 = 0;
+        for (int c = 0; c < ncon; c++) if (con[c].g2 == GEOM_BOX) { f0 |= con[c].g1 == HRG_NRCAP - 2; f1 |= con[c].g1 == HRG_NRCAP - 1; }
+        bx->gripped = f0 && f1;
       }
-      for (int kk = 0; kk < 3; kk++) Ld[kk] = (m->box_inertia[kk] - m->box_inertia_mean) * (Rx[kk] * w[0] + Rx[3 + kk] * w[1] + Rx[6 + kk] * w[2]);
-      m3mulv(Lw, Rx, Ld); /* R diag(I - mean) R' w */
-      v3cross(tau, Lw, w); /* -(w x L) */
-      for (int kk = 0; kk < 3; kk++) tl[kk] = (Rx[kk] * tau[0] + Rx[3 + kk] * tau[1] + Rx[6 + kk] * tau[2]) / m->box_inertia[kk]; /* diag(1/I) R' tau */
+      if (pass == 1) {
+        if (m->task == HRG_TASK_HANDOVER_R2H) palm_hit = palm_contact(B, gid, s, bx, &hk); /* sim.data.contact of the cycle's collision phase */
+        record_contacts(m, &k, s, con, ncon, &has_collision, &collision_type);
+      }
+      /* ---- sim.step() (human_env.py:523): smooth acceleration, constraints, Euler ---- */
+      double a0[NVT], qd[NVT], Mt[NVT * NVT];
       memset(Mt, 0, sizeof Mt);
-      for (int i = 0; i < NV; i++) for (int j = 0; j < NV; j++) Mt[i * NVT + j] = M[i * NV + j];
-      for (int a = 0; a < 3; a++) {
-        Mt[(NV + a) * NVT + NV + a] = m->box_mass;
-        for (int b = 0; b < 3; b++) Mt[(NV + 3 + a) * NVT + NV + 3 + b] = (a == b ? m->box_inertia_mean : 0.0) + Mdev[3 * a + b];
-        a0[NV + a] = m->gravity[a];
-        a0[NV + 3 + a] = Rx[3 * a] * tl[0] + Rx[3 * a + 1] * tl[1] + Rx[3 * a + 2] * tl[2];
+      if (!robot_smooth(m, s, M, bias, ctrl, nvt, Mt, a0, qd)) { crash = 1; break; }
+      if (bx) free_body_block(m, bx->quat, bx->vel, nvt, NV, Mt, a0, qd);
+      efc_t E;
+      E.n = 0;
+      E.nv = nvt;
+      friction_rows(m, &E, qd);
+      limit_rows(m, s, &E, qd);
+      contact_rows(m, &k, con, ncon, ncon_dyn, &box, &E, qd);
+      if (bx && bx->weld_active && m->task == HRG_TASK_LIFTING) { /* two connect equalities (collaborative_lifting_cartesian_env.py:924-958): the board's grip points follow the
+                                                                    * hand mocap bodies (lifting_mocap keeps the right hand's in weld_off) */
+        for (int hd = 0; hd < 2; hd++) connect_rows(m, &E, qd, &box, m->lift_anchor[hd], hd ? bx->weld_off : bx->mocap_pos);
+      } else if (bx && bx->weld_active) { /* weld of the object frame onto the hand mocap frame (human_robot_handover_cartesian_env.py:870-903); relpose = (weld_off, weld_rel) */
+        double qt[4], Rm[9], tp[3];
+        quat2mat(Rm, bx->mocap_quat);
+        m3mulv(tp, Rm, bx->weld_off);
+        v3add(tp, tp, bx->mocap_pos);          /* where the weld wants the object: mocap frame o relative pose */
+        quatmul(qt, bx->mocap_quat, bx->weld_rel);
+        weld_rows(m, &E, qd, &box, tp, qt);
       }
-      for (int a = 0; a < HRG_NBOXV; a++) qd[NV + a] = bx->vel[a];
-    } else memcpy(Mt, M, sizeof M);
-    efc_t E;
-    E.n = 0;
-    E.nv = nvt;
-    for (int i = 0; i < NV; i++) /* friction loss rows */
-      if (m->jnt_frictionloss[i] > 0) { double J[NVT] = {0}; J[i] = 1; efc_add(m, &E, J, qd, ROW_FRICTION, 0, 0, m->jnt_frictionloss[i], m->dof_invweight0[i]); }
-    for (int i = 0; i < NV; i++) { /* joint limit rows */
-      double dlo = s->qpos[i] - m->jnt_range[i][0], dhi = m->jnt_range[i][1] - s->qpos[i];
-      if (dlo < 0) { double J[NVT] = {0}; J[i] = 1; efc_add(m, &E, J, qd, ROW_UNILATERAL, dlo, 0, 0, m->dof_invweight0[i]); }
-      if (dhi < 0) { double J[NVT] = {0}; J[i] = -1; efc_add(m, &E, J, qd, ROW_UNILATERAL, dhi, 0, 0, m->dof_invweight0[i]); }
-    }
-    for (int c = 0; c < ncon && c < ncon_dyn; c++) { /* pyramidal frictional contact rows */
-      const double* n = con[c].n;
-      double t1[3], t2[3], e1[3] = {1, 0, 0}, e2[3] = {0, 1, 0};
-      v3cross(t1, n, fabs(n[0]) < 0.5 ? e1 : e2);
-      v3scl(t1, t1, 1.0 / v3norm(t1));
-      v3cross(t2, n, t1);
-      double margin = (con[c].g2 >= GEOM_HUMAN0 && con[c].g2 < GEOM_TABLE) || (con[c].g1 >= GEOM_HUMAN0 && con[c].g1 < GEOM_TABLE) ? m->contact_margin_human : 0.0; /* a human geom on either side */
-      for (int d = 0; d < 4; d++) {
-        double dir[3], J[NVT] = {0};
-        const double* tt = d < 2 ? t1 : t2;
-        double sg = (d & 1) ? -1.0 : 1.0;
-        for (int a = 0; a < 3; a++) dir[a] = n[a] + sg * m->friction_static * tt[a];
-        /* separation velocity along n (from geom1 to geom2): v2 - v1 */
-        if (con[c].b1 >= 0 && con[c].b1 < NV) robot_point_jac(m, &k, con[c].b1, con[c].pos, dir, -1.0, J);
-        if (con[c].b2 >= 0 && con[c].b2 < NV) robot_point_jac(m, &k, con[c].b2, con[c].pos, dir, +1.0, J);
-        double diag = (con[c].b1 >= 0 && con[c].b1 < NV ? m->body_invweight0[con[c].b1] : 0.0) + (con[c].b2 >= 0 && con[c].b2 < NV ? m->body_invweight0[con[c].b2] : 0.0);
-        if (con[c].b2 == BODY_BOX) { /* the cube is always geom 2: J = dir . (v + w x r), body_invweight0 of a free body = 1/m */
-          double r[3], rxd[3];
-          v3sub(r, con[c].pos, bx->pos);
-          v3cross(rxd, r, dir);
-          for (int a = 0; a < 3; a++) { J[NV + a] = dir[a]; J[NV + 3 + a] = rxd[a]; }
-          diag += 1.0 / m->box_mass;
-        }
-        efc_add(m, &E, J, qd, ROW_UNILATERAL, con[c].dist, margin, 0, diag * (1.0 + m->friction_static * m->friction_static));
+      double qacc[NVT];
+      memcpy(qacc, s->qacc_warmstart, sizeof(double) * NV);
+      if (bx) memcpy(qacc + NV, bx->acc_warmstart, sizeof(double) * HRG_NBOXV);
+      solve(m, Mt, a0, &E, qacc);
+      if (g_debug && (ncon > 0 || g_debug > 1)) {
+        double mx = 0; for (int i = 0; i < nvt; i++) if (fabs(qacc[i]) > mx) mx = fabs(qacc[i]);
+        fprintf(stderr, "[oracle] env %d cyc %d ncon %d nefc %d max|qacc| %.3e", e, cyc, ncon, E.n, mx);
+        for (int c = 0; c < ncon; c++) fprintf(stderr, " (%d,%d d=%.4f)", con[c].g1, con[c].g2, con[c].dist);
+        fprintf(stderr, "\n");
       }
-    }
-    if (bx && bx->weld_active && m->task == HRG_TASK_LIFTING) { /* two connect equalities (collaborative_lifting_cartesian_env.py:924-958): the board's grip points follow the
-                                                                  * hand mocap bodies; residual = p_board + R anchor - p_mocap, velocity of the point = v + w x r */
-      double Rx[9];
-      quat2mat(Rx, bx->quat);
-      for (int hd = 0; hd < 2; hd++) {
-        double rr[3], pt[3];
-        const double* mp_ = hd ? bx->weld_off : bx->mocap_pos;
-        m3mulv(rr, Rx, m->lift_anchor[hd]);
-        v3add(pt, bx->pos, rr);
-        for (int a = 0; a < 3; a++) {
-          double J[NVT] = {0}, ea[3] = {a == 0, a == 1, a == 2}, rxe[3];
-          v3cross(rxe, rr, ea); /* (w x r) . e_a = w . (r x e_a) */
-          J[NV + a] = 1;
-          for (int b_ = 0; b_ < 3; b_++) J[NV + 3 + b_] = rxe[b_];
-          efc_add(m, &E, J, qd, ROW_EQUALITY, pt[a] - mp_[a], 0, 0, 1.0 / m->box_mass);
-        }
+      if (!robot_euler(m, s, M, qacc, nvt)) { crash = 1; break; }
+      if (bx) {
+        v3cpy(bx->obs_pos, bx->pos); /* body_xpos of the forward pass inside mj_step (pre-integration) */
+        free_body_euler(h, qacc + NV, bx->pos, bx->quat, bx->vel, bx->acc_warmstart);
       }
-    } else if (bx && bx->weld_active) { /* weld of the object frame onto the hand mocap frame (human_robot_handover_cartesian_env.py:870-903): residual =
-                                  * [p_obj - p_mocap; rotation vector of q_obj q_mocap^-1]; the mocap body has no velocity; relpose = identity */
-      double epos[3], erot[3], qt[4], qe[4], Rm[9], tp[3];
-      quat2mat(Rm, bx->mocap_quat);
-      m3mulv(tp, Rm, bx->weld_off);
-      v3add(tp, tp, bx->mocap_pos);          /* where the weld wants the object: mocap frame o relative pose */
-      v3sub(epos, bx->pos, tp);
-      quatmul(qt, bx->mocap_quat, bx->weld_rel);
-      double qc[4] = {qt[0], -qt[1], -qt[2], -qt[3]};
-      quatmul(qe, bx->quat, qc);
-      if (qe[0] < 0) for (int a = 0; a < 4; a++) qe[a] = -qe[a];
-      const double sn = sqrt(qe[1] * qe[1] + qe[2] * qe[2] + qe[3] * qe[3]), ang = 2.0 * atan2(sn, qe[0]);
-      for (int a = 0; a < 3; a++) erot[a] = sn > 1e-12 ? qe[1 + a] / sn * ang : 0.0;
-      for (int a = 0; a < 3; a++) { double J[NVT] = {0}; J[NV + a] = 1; efc_add(m, &E, J, qd, ROW_EQUALITY, epos[a], 0, 0, 1.0 / m->box_mass); }
-      for (int a = 0; a < 3; a++) { double J[NVT] = {0}; J[NV + 3 + a] = 1; efc_add(m, &E, J, qd, ROW_EQUALITY, erot[a], 0, 0, m->box_invweight_rot); }
-    }
-    double qacc[NVT];
-    memcpy(qacc, s->qacc_warmstart, sizeof(double) * NV);
-    if (bx) memcpy(qacc + NV, bx->acc_warmstart, sizeof(double) * HRG_NBOXV);
-    solve(m, Mt, a0, &E, qacc);
-    if (g_debug && (ncon > 0 || g_debug > 1)) {
-      double mx = 0; for (int i = 0; i < nvt; i++) if (fabs(qacc[i]) > mx) mx = fabs(qacc[i]);
-      fprintf(stderr, "[oracle] env %d cyc %d ncon %d nefc %d max|qacc| %.3e", e, cyc, ncon, E.n, mx);
-      for (int c = 0; c < ncon; c++) fprintf(stderr, " (%d,%d d=%.4f)", con[c].g1, con[c].g2, con[c].dist);
-      fprintf(stderr, "\n");
-    }
-    /* mj_checkAcc -> MujocoException handler (human_env.py:527-546) */
-    for (int i = 0; i < nvt; i++) if (!(fabs(qacc[i]) < 1e10)) crash = 1;
-    if (crash) break;
-    memcpy(s->qacc_warmstart, qacc, sizeof(double) * NV);
-    /* mj_Euler with implicit joint damping: (M + h D) qacc' = M qacc */
-    double Mh[NV * NV], rhs[NV];
-    memcpy(Mh, M, sizeof Mh);
-    for (int i = 0; i < NV; i++) { Mh[i * NV + i] += h * m->jnt_damping[i]; double t = 0; for (int j = 0; j < NV; j++) t += M[i * NV + j] * qacc[j]; rhs[i] = t; }
-    if (!chol(Mh, NV)) { crash = 1; break; }
-    chol_solve(Mh, NV, rhs);
-    for (int i = 0; i < NV; i++) { s->qvel[i] += h * rhs[i]; s->qpos[i] += h * s->qvel[i]; }
-    if (bx) { /* free joint: no damping; quaternion integrated with the world-frame angular velocity */
-      memcpy(bx->acc_warmstart, qacc + NV, sizeof(double) * HRG_NBOXV);
-      v3cpy(bx->obs_pos, bx->pos); /* body_xpos of the forward pass inside mj_step (pre-integration) */
-      for (int a = 0; a < HRG_NBOXV; a++) bx->vel[a] += h * qacc[NV + a];
-      for (int a = 0; a < 3; a++) bx->pos[a] += h * bx->vel[a];
-      double w[3] = {bx->vel[3], bx->vel[4], bx->vel[5]}, wn = v3norm(w), ang = h * wn;
-      if (wn > 1e-12) {
-        double sh = sin(0.5 * ang) / wn, dq[4] = {cos(0.5 * ang), w[0] * sh, w[1] * sh, w[2] * sh}, qn[4];
-        quatmul(qn, dq, bx->quat);
-        double nn = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-        for (int a = 0; a < 4; a++) bx->quat[a] = qn[a] / nn;
+      s->time += h;
+      eef_of(m, &k, s->eef_pos); /* site_xpos of the forward pass inside mj_step (pre-integration) */
+      if (pass == 0) { /* _update_mocap_body_transform (609-633) + sim.forward() (human_env.py:519) */
+        handover_mocap(B, gid, s, bx, &hk);
+        robot_fk(m, s->qpos, &k);
+        robot_crba(m, &k, M);
+        robot_bias(m, &k, s->qvel, bias);
       }
-    }
-    s->time += h;
-    eef_of(m, &k, s->eef_pos); /* site_xpos of the forward pass inside mj_step (pre-integration) */
-    if (pass == 0) { /* _update_mocap_body_transform (609-633) + sim.forward() (human_env.py:519) */
-      handover_mocap(B, gid, s, bx, &hk);
-      robot_fk(m, s->qpos, &k);
-      robot_crba(m, &k, M);
-      robot_bias(m, &k, s->qvel, bias);
-    }
     } /* pass */
     if (crash) break;
     s->low_level_time += 1; /* human_env.py:526 */
@@ -2314,37 +2434,14 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
     r = goal_reached ? m->task_reward : -1.0; /* human_env.py:666-691 */
     dense = -0.1 * dist; /* reach_human_env.py:437-455 */
   }
-  if (goal_reached) s->n_goal_reached++;
-  int illegal = (collision_type & (HRG_COL_STATIC | HRG_COL_ROBOT | HRG_COL_HUMAN_CRIT)) != 0; /* human_env.py:860-878 */
-  if (m->reward_shaping) r += 1.0 + dense; /* human_env.py:650-651 */
-  if (illegal) r += m->collision_reward;
-  r *= m->reward_scale;
-  int d = 0;
-  if (crash) { r += m->sim_crash_reward; d = 1; }
-  else {
-    if (m->done_at_collision && illegal) d = 1; /* human_env.py:835-858 */
-    if (m->done_at_success && goal_reached) d = 1;
-    if (m->task == HRG_TASK_LIFTING) { /* _check_done (509-561): unbalanced, or the board out of the gripper for more than 5 steps in a row */
-      double Rx[9];
-      quat2mat(Rx, bx->quat);
-      bx->n_delayed = bx->gripped ? 0 : bx->n_delayed + 1;
-      if (Rx[8] < m->min_balance || bx->n_delayed > 5) d = 1;
-    }
+  int d = reward_and_done(m, s, collision_type, crash, goal_reached, dense, &r);
+  if (!crash && m->task == HRG_TASK_LIFTING) { /* _check_done (509-561): unbalanced, or the board out of the gripper for more than 5 steps in a row */
+    double Rx[9];
+    quat2mat(Rx, bx->quat);
+    bx->n_delayed = bx->gripped ? 0 : bx->n_delayed + 1;
+    if (Rx[8] < m->min_balance || bx->n_delayed > 5) d = 1;
   }
-  int ncoll = s->n_collisions_static + s->n_collisions_robot + s->n_collisions_human + s->n_collisions_critical;
-  info[HRG_INFO_COLLISION] = has_collision;
-  info[HRG_INFO_COLLISION_TYPE] = collision_type;
-  info[HRG_INFO_N_COLLISIONS] = ncoll;
-  info[HRG_INFO_N_COLLISIONS_STATIC] = s->n_collisions_static;
-  info[HRG_INFO_N_COLLISIONS_ROBOT] = s->n_collisions_robot;
-  info[HRG_INFO_N_COLLISIONS_HUMAN] = s->n_collisions_human;
-  info[HRG_INFO_N_COLLISIONS_CRITICAL] = s->n_collisions_critical;
-  info[HRG_INFO_TIMEOUT] = s->timestep >= m->horizon;
-  info[HRG_INFO_FAILSAFE_INTERVENTIONS] = s->failsafe_interventions;
-  info[HRG_INFO_N_GOAL_REACHED] = s->n_goal_reached;
-  info[HRG_INFO_SIM_CRASH] = crash;
-  info[HRG_INFO_TRUNCATED] = 0;
-  info[HRG_INFO_ACTION_RESAMPLES] = s->action_resamples;
+  fill_info(m, s, has_collision, collision_type, crash, info);
   info[HRG_INFO_N_OBJECT_HANDED_OVER] = bx ? bx->n_handed_over : 0;
   if (bx && m->task == HRG_TASK_LIFTING) {
     if (goal_reached && !m->done_at_success) { /* _on_goal_reached (631-642): the robot back at its initial posture (deterministic), controller reset, next
@@ -2356,15 +2453,9 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
       eef_of(m, &k, s->eef_pos);
       shield_reset(m, s, s->qpos);
       for (int j = 0; j < NARM; j++) s->goal_qpos[j] = s->qpos[j];
-      s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
-      s->animation_time = 0;
-      s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+      next_animation(m, s);
       bx->task_phase = HRG_PHASE_APPROACH; bx->n_delayed = 0;
-      human_kin hk2;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk2, s->human_site);
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
       lifting_mocap(m, s, bx);
       lifting_place_board(m, &k, s->eef_pos, bx);
     }
@@ -2373,17 +2464,10 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
       bx->obj_index = (bx->obj_index + 1) % m->n_obj_placements;
       placement_of(B, gid, s->episode, bx->obj_index, 0, bx->pos);
       bx->quat[0] = 1; bx->quat[1] = bx->quat[2] = bx->quat[3] = 0;
-      s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
-      s->animation_time = 0;
-      s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+      next_animation(m, s);
       bx->task_phase = HRG_R2H_APPROACH; bx->n_delayed = 0; bx->weld_active = 0;
-      human_kin hk2;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk2, s->human_site);
-      handover_mocap(B, gid, s, bx, &hk2);
-      hk = hk2;
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
+      handover_mocap(B, gid, s, bx, &hk);
     }
     /* RobotHumanHandoverCart.step (452-474): the human takes the object when it touches the palm of the extended hand */
     if (bx->task_phase == HRG_R2H_REACH_OUT && palm_hit) { handover_attach(bx); bx->task_phase = HRG_R2H_RETREAT; bx->n_handed_over++; }
@@ -2393,16 +2477,10 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
     if (goal_reached && !m->done_at_success) { /* _on_goal_reached (649-668): next target, next animation, the human picks the object up again */
       bx->tgt_index = (bx->tgt_index + 1) % m->n_targets;
       placement_of(B, gid, s->episode, bx->tgt_index, 1, bx->target);
-      s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
-      s->animation_time = 0;
-      s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+      next_animation(m, s);
       bx->task_phase = HRG_PHASE_APPROACH; bx->n_delayed = 0; bx->n_delayed2 = 0;
-      human_kin hk2;
-      double mp[3], mq[4];
-      const double* qh;
-      human_control(B, gid, s, bx, mp, mq, &qh);
-      human_fk(m, mp, mq, qh, &hk2, s->human_site);
-      handover_mocap(B, gid, s, bx, &hk2);
+      pose_human(B, gid, s, bx, NULL, NULL, &hk);
+      handover_mocap(B, gid, s, bx, &hk);
       handover_pickup(bx);
     }
     /* HumanRobotHandoverCart.step (465-483): the human lets go once the robot has gripped the object; the retreat starts when it is placed */
@@ -2415,9 +2493,7 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
       bx->obj_index = (bx->obj_index + 1) % m->n_obj_placements;
       placement_of(B, gid, s->episode, bx->obj_index, 0, bx->pos);
       bx->quat[0] = 1; bx->quat[1] = bx->quat[2] = bx->quat[3] = 0;
-      s->anim_index = (s->anim_index + 1) % m->n_anim_ids; /* _progress_to_next_animation, human_env.py:1698-1708 + 663-670 */
-      s->animation_time = 0;
-      s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+      next_animation(m, s);
       bx->task_phase = HRG_PHASE_APPROACH;
       bx->n_delayed = 0;
     }
@@ -2435,11 +2511,7 @@ static void env_step(hrgo_batch* B, int e, double* action, float* obs, float* te
     s->goal_index = (s->goal_index + 1) % m->n_goals;
     goal_of(B, gid, s, s->goal_index, s->cur_goal);
   }
-  if (s->timestep >= m->horizon) { info[HRG_INFO_TRUNCATED] = !d; d = 1; } /* time_limit.py:40-43 */
-  *reward = (float)r;
-  *done = (uint8_t)d;
-  if (d) env_reset(B, e, obs); /* VecEnv auto-reset; terminal observation stays in term_obs */
-  else memcpy(obs, term_obs, sizeof(float) * HRG_OBS_DIM);
+  finish_step(B, e, r, d, obs, term_obs, reward, done, info);
 }
 
 /* =============================================================================================== CollaborativeStackingCart
@@ -2854,10 +2926,7 @@ static void env_reset_stack(hrgo_batch* B, int e, const robot_kin* k) {
     v3cpy(sk->obs_pos[c], sk->pos[c]);
   }
   human_kin hk;
-  double mp[3], mq[4];
-  const double* qh;
-  human_control_sk(B, gid, s, NULL, sk, mp, mq, &qh); /* _reset_animation + _control_human: phase APPROACH, the human holds both cubes */
-  human_fk(m, mp, mq, qh, &hk, s->human_site);
+  pose_human(B, gid, s, NULL, sk, NULL, &hk); /* _reset_animation + _control_human: phase APPROACH, the human holds both cubes */
   stack_mocap(m, s, sk, &hk);
   stack_reset_animation(m, sk);
 }
@@ -2875,150 +2944,43 @@ static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, flo
   robot_kin k;
   human_kin hk;
   double M[NV * NV], bias[NV];
+  static const int NVK = NVMAX;
+  free_body cube[NCUBE];
+  for (int c = 0; c < NCUBE; c++) cube[c] = (free_body){sk->pos[c], sk->quat[c], NV + 6 * c, 1.0 / m->box_mass, m->box_invweight_rot, NULL, 0};
   for (int cyc = 0; cyc < m->n_cycles && !crash; cyc++) {
     robot_fk(m, s->qpos, &k);
     robot_crba(m, &k, M);
     robot_bias(m, &k, s->qvel, bias);
-    if (cyc == 0) { /* failsafe_controller.py:252-300 */
-      for (int i = 0; i < NARM; i++) for (int j = 0; j < NARM; j++) s->mass_matrix[i * NARM + j] = M[i * NV + j];
-      double scale = fabs(m->act_out_max - m->act_out_min) / fabs(m->act_in_max - m->act_in_min);
-      double otr = 0.5 * (m->act_out_max + m->act_out_min), itr = 0.5 * (m->act_in_max + m->act_in_min);
-      for (int j = 0; j < NARM; j++) {
-        double a = clampd(action[j], m->act_in_min, m->act_in_max);
-        double g = s->qpos[j] + ((a - itr) * scale + otr);
-        s->goal_qpos[j] = clampd(g, m->qpos_limits[0][j], m->qpos_limits[1][j]);
-        s->new_goal_q[j] = s->goal_qpos[j];
-      }
-      s->new_goal = 1;
-    }
+    if (cyc == 0) controller_goal(m, s, M, action);
     shield_step(B, e, s->time);
     double ctrl[NV];
-    for (int i = 0; i < NARM; i++) {
-      double t = 0;
-      for (int j = 0; j < NARM; j++) t += s->mass_matrix[i * NARM + j] * (m->kp * (s->des_q[j] - s->qpos[j]) + m->kd * (s->des_v[j] - s->qvel[j]) + s->des_a[j]);
-      ctrl[i] = clampd(t + bias[i], m->arm_ctrlrange[i][0], m->arm_ctrlrange[i][1]);
-    }
-    {
-      double a = action[NARM], sg = a > 0 ? 1.0 : (a < 0 ? -1.0 : 0.0);
-      s->grip_action = clampd(s->grip_action - m->gripper_speed * sg, -1.0, 1.0);
-      for (int f = 0; f < HRG_NFINGER; f++) {
-        double lo = m->finger_ctrlrange[f][0], hi = m->finger_ctrlrange[f][1];
-        ctrl[NARM + f] = 0.5 * (hi + lo) + 0.5 * (hi - lo) * (f == 0 ? s->grip_action : -s->grip_action);
-      }
-    }
-    if (!failsafe_intervention && !s->is_safe) { failsafe_intervention = 1; s->failsafe_interventions++; }
+    arm_and_gripper_ctrl(m, s, bias, action, ctrl, &failsafe_intervention);
     /* _control_human (899-903): super + sim.forward() + the two hand mocap bodies */
-    double mp[3], mq[4];
-    const double* qh;
-    human_control_sk(B, gid, s, NULL, sk, mp, mq, &qh);
-    human_fk(m, mp, mq, qh, &hk, s->human_site);
+    pose_human(B, gid, s, NULL, sk, NULL, &hk);
     stack_mocap(m, s, sk, &hk);
     contact_t con[HRG_NCON_MAX];
     int ncon = collide_stack(m, &k, &hk, sk, con);
-    double rc[HRG_NRCAP][3], Rb[9];
-    quat2mat(Rb, m->base_quat);
-    for (int c = 0; c < HRG_NRCAP; c++) {
-      int b = m->rcap_body[c];
-      double t[3], mid[3];
-      for (int a = 0; a < 3; a++) mid[a] = 0.5 * (m->rcap_p1[c][a] + m->rcap_p2[c][a]);
-      m3mulv(t, b < 0 ? Rb : k.R[b], mid);
-      v3add(rc[c], b < 0 ? m->base_pos : k.p[b], t);
-    }
-    classify(m, &k, s, con, ncon, rc, &has_collision, &collision_type);
-    s->ncon = ncon;
-    for (int c = 0; c < HRG_NCON_MAX; c++) { s->con_pairs[c][0] = c < ncon ? con[c].g1 : -1; s->con_pairs[c][1] = c < ncon ? con[c].g2 : -1; }
+    record_contacts(m, &k, s, con, ncon, &has_collision, &collision_type);
     /* ---- sim.step(): robot tree + four free cubes (block-diagonal M; cubes: m 1, R diag(I) R' with the mean / deviation split of the single cube) ---- */
-    double LM[NV * NV], a0[NVMAX], qd[NVMAX], frc[NV];
-    static const int NVK = NVMAX;
+    double a0[NVMAX], qd[NVMAX];
     double* Mt = (double*)calloc((size_t)NVK * NVK, sizeof(double));
-    memcpy(LM, M, sizeof LM);
-    if (!chol(LM, NV)) { crash = 1; free(Mt); break; }
-    for (int i = 0; i < NV; i++) {
-      double act = ctrl[i];
-      if (i >= NARM) act = clampd(m->finger_kp * (ctrl[i] - s->qpos[i]), m->finger_forcerange[0], m->finger_forcerange[1]);
-      frc[i] = act - m->jnt_damping[i] * s->qvel[i] - bias[i];
-      a0[i] = frc[i];
-      qd[i] = s->qvel[i];
-    }
-    chol_solve(LM, NV, a0);
-    for (int i = 0; i < NV; i++) for (int j = 0; j < NV; j++) Mt[i * NVK + j] = M[i * NV + j];
-    for (int c = 0; c < NCUBE; c++) {
-      const int o = NV + 6 * c;
-      double Rx[9], Mdev[9], w[3] = {sk->vel[c][3], sk->vel[c][4], sk->vel[c][5]}, Ld[3], Lw[3], tau[3], tl[3];
-      quat2mat(Rx, sk->quat[c]);
-      for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) {
-        double t = 0;
-        for (int kk = 0; kk < 3; kk++) t += Rx[3 * i + kk] * (m->box_inertia[kk] - m->box_inertia_mean) * Rx[3 * j + kk];
-        Mdev[3 * i + j] = t;
-      }
-      for (int kk = 0; kk < 3; kk++) Ld[kk] = (m->box_inertia[kk] - m->box_inertia_mean) * (Rx[kk] * w[0] + Rx[3 + kk] * w[1] + Rx[6 + kk] * w[2]);
-      m3mulv(Lw, Rx, Ld);
-      v3cross(tau, Lw, w);
-      for (int kk = 0; kk < 3; kk++) tl[kk] = (Rx[kk] * tau[0] + Rx[3 + kk] * tau[1] + Rx[6 + kk] * tau[2]) / m->box_inertia[kk];
-      for (int a = 0; a < 3; a++) {
-        Mt[(o + a) * NVK + o + a] = m->box_mass;
-        for (int b = 0; b < 3; b++) Mt[(o + 3 + a) * NVK + o + 3 + b] = (a == b ? m->box_inertia_mean : 0.0) + Mdev[3 * a + b];
-        a0[o + a] = m->gravity[a];
-        a0[o + 3 + a] = Rx[3 * a] * tl[0] + Rx[3 * a + 1] * tl[1] + Rx[3 * a + 2] * tl[2];
-      }
-      for (int a = 0; a < 6; a++) qd[o + a] = sk->vel[c][a];
-    }
+    if (!robot_smooth(m, s, M, bias, ctrl, NVK, Mt, a0, qd)) { crash = 1; free(Mt); break; }
+    for (int c = 0; c < NCUBE; c++) free_body_block(m, sk->quat[c], sk->vel[c], NVK, cube[c].dof, Mt, a0, qd);
     efc_t* E = (efc_t*)malloc(sizeof(efc_t));
     E->n = 0;
     E->nv = NVK;
-    for (int i = 0; i < NV; i++)
-      if (m->jnt_frictionloss[i] > 0) { double J[NVMAX] = {0}; J[i] = 1; efc_add(m, E, J, qd, ROW_FRICTION, 0, 0, m->jnt_frictionloss[i], m->dof_invweight0[i]); }
-    for (int i = 0; i < NV; i++) {
-      double dlo = s->qpos[i] - m->jnt_range[i][0], dhi = m->jnt_range[i][1] - s->qpos[i];
-      if (dlo < 0) { double J[NVMAX] = {0}; J[i] = 1; efc_add(m, E, J, qd, ROW_UNILATERAL, dlo, 0, 0, m->dof_invweight0[i]); }
-      if (dhi < 0) { double J[NVMAX] = {0}; J[i] = -1; efc_add(m, E, J, qd, ROW_UNILATERAL, dhi, 0, 0, m->dof_invweight0[i]); }
-    }
-    for (int c = 0; c < ncon && c < HRG_NCON_DYN_STACK; c++) {
-      const double* n = con[c].n;
-      double t1[3], t2[3], e1[3] = {1, 0, 0}, e2[3] = {0, 1, 0};
-      v3cross(t1, n, fabs(n[0]) < 0.5 ? e1 : e2);
-      v3scl(t1, t1, 1.0 / v3norm(t1));
-      v3cross(t2, n, t1);
-      double margin = (con[c].g2 >= GEOM_HUMAN0 && con[c].g2 < GEOM_TABLE) || (con[c].g1 >= GEOM_HUMAN0 && con[c].g1 < GEOM_TABLE) ? m->contact_margin_human : 0.0; /* a human geom on either side */
-      for (int d = 0; d < 4; d++) {
-        double dir[3], J[NVMAX] = {0};
-        const double* tt = d < 2 ? t1 : t2;
-        double sg = (d & 1) ? -1.0 : 1.0;
-        for (int a = 0; a < 3; a++) dir[a] = n[a] + sg * m->friction_static * tt[a];
-        if (con[c].b1 >= 0 && con[c].b1 < NV) robot_point_jac(m, &k, con[c].b1, con[c].pos, dir, -1.0, J);
-        if (con[c].b2 >= 0 && con[c].b2 < NV) robot_point_jac(m, &k, con[c].b2, con[c].pos, dir, +1.0, J);
-        double diag = (con[c].b1 >= 0 && con[c].b1 < NV ? m->body_invweight0[con[c].b1] : 0.0) + (con[c].b2 >= 0 && con[c].b2 < NV ? m->body_invweight0[con[c].b2] : 0.0);
-        for (int side = 0; side < 2; side++) { /* free bodies: J = +-dir . (v + w x r), body_invweight0 = 1/m */
-          const int body = side ? con[c].b2 : con[c].b1;
-          if (body < BODY_BOX) continue;
-          const int cb = body - BODY_BOX, o = NV + 6 * cb;
-          const double sgn = side ? 1.0 : -1.0;
-          double r[3], rxd[3];
-          v3sub(r, con[c].pos, sk->pos[cb]);
-          v3cross(rxd, r, dir);
-          for (int a = 0; a < 3; a++) { J[o + a] = sgn * dir[a]; J[o + 3 + a] = sgn * rxd[a]; }
-          diag += 1.0 / m->box_mass;
-        }
-        efc_add(m, E, J, qd, ROW_UNILATERAL, con[c].dist, margin, 0, diag * (1.0 + m->friction_static * m->friction_static));
-      }
-    }
-    for (int hd = 0; hd < 2; hd++) { /* lh_weld_eq / rh_weld_eq (1255-1284): residual [p_cube - p_target; rotation vector of q_cube q_mocap^-1] on the cube's own DoF */
+    friction_rows(m, E, qd);
+    limit_rows(m, s, E, qd);
+    contact_rows(m, &k, con, ncon, HRG_NCON_DYN_STACK, cube, E, qd);
+    for (int hd = 0; hd < 2; hd++) { /* lh_weld_eq / rh_weld_eq (1255-1284): the cube in hand hd onto its mocap frame, relpose = (stack_weld_relpos, identity) */
       if (!sk->weld_active[hd]) continue;
-      const int cb = HRG_CUBE_L + hd, o = NV + 6 * cb;
-      double tp[3], epos[3], erot[3], qe[4];
+      double tp[3];
       stack_weld_target(m, sk, hd, tp);
-      v3sub(epos, sk->pos[cb], tp);
-      double qc[4] = {sk->mocap_quat[hd][0], -sk->mocap_quat[hd][1], -sk->mocap_quat[hd][2], -sk->mocap_quat[hd][3]};
-      quatmul(qe, sk->quat[cb], qc);
-      if (qe[0] < 0) for (int a = 0; a < 4; a++) qe[a] = -qe[a];
-      const double sn = sqrt(qe[1] * qe[1] + qe[2] * qe[2] + qe[3] * qe[3]), ang = 2.0 * atan2(sn, qe[0]);
-      for (int a = 0; a < 3; a++) erot[a] = sn > 1e-12 ? qe[1 + a] / sn * ang : 0.0;
-      for (int a = 0; a < 3; a++) { double J[NVMAX] = {0}; J[o + a] = 1; efc_add(m, E, J, qd, ROW_EQUALITY, epos[a], 0, 0, 1.0 / m->box_mass); }
-      for (int a = 0; a < 3; a++) { double J[NVMAX] = {0}; J[o + 3 + a] = 1; efc_add(m, E, J, qd, ROW_EQUALITY, erot[a], 0, 0, m->box_invweight_rot); }
+      weld_rows(m, E, qd, &cube[HRG_CUBE_L + hd], tp, sk->mocap_quat[hd]);
     }
     double qacc[NVMAX];
     memcpy(qacc, s->qacc_warmstart, sizeof(double) * NV);
-    for (int c = 0; c < NCUBE; c++) memcpy(qacc + NV + 6 * c, sk->acc_warmstart[c], sizeof(double) * 6);
+    for (int c = 0; c < NCUBE; c++) memcpy(qacc + cube[c].dof, sk->acc_warmstart[c], sizeof(double) * 6);
     solve(m, Mt, a0, E, qacc);
     if (g_debug && (ncon > 0 || g_debug > 1)) {
       double mx = 0; for (int i = 0; i < NVK; i++) if (fabs(qacc[i]) > mx) mx = fabs(qacc[i]);
@@ -3027,27 +2989,10 @@ static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, flo
       fprintf(stderr, "\n");
     }
     free(E); free(Mt);
-    for (int i = 0; i < NVK; i++) if (!(fabs(qacc[i]) < 1e10)) crash = 1;
-    if (crash) break;
-    memcpy(s->qacc_warmstart, qacc, sizeof(double) * NV);
-    double Mh[NV * NV], rhs[NV];
-    memcpy(Mh, M, sizeof Mh);
-    for (int i = 0; i < NV; i++) { Mh[i * NV + i] += h * m->jnt_damping[i]; double t = 0; for (int j = 0; j < NV; j++) t += M[i * NV + j] * qacc[j]; rhs[i] = t; }
-    if (!chol(Mh, NV)) { crash = 1; break; }
-    chol_solve(Mh, NV, rhs);
-    for (int i = 0; i < NV; i++) { s->qvel[i] += h * rhs[i]; s->qpos[i] += h * s->qvel[i]; }
+    if (!robot_euler(m, s, M, qacc, NVK)) { crash = 1; break; }
     for (int c = 0; c < NCUBE; c++) {
-      memcpy(sk->acc_warmstart[c], qacc + NV + 6 * c, sizeof(double) * 6);
       v3cpy(sk->obs_pos[c], sk->pos[c]);
-      for (int a = 0; a < 6; a++) sk->vel[c][a] += h * qacc[NV + 6 * c + a];
-      for (int a = 0; a < 3; a++) sk->pos[c][a] += h * sk->vel[c][a];
-      double w[3] = {sk->vel[c][3], sk->vel[c][4], sk->vel[c][5]}, wn = v3norm(w), ang = h * wn;
-      if (wn > 1e-12) {
-        double sh = sin(0.5 * ang) / wn, dq[4] = {cos(0.5 * ang), w[0] * sh, w[1] * sh, w[2] * sh}, qn[4];
-        quatmul(qn, dq, sk->quat[c]);
-        double nn = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-        for (int a = 0; a < 4; a++) sk->quat[c][a] = qn[a] / nn;
-      }
+      free_body_euler(h, qacc + cube[c].dof, sk->pos[c], sk->quat[c], sk->vel[c], sk->acc_warmstart[c]);
     }
     s->time += h;
     eef_of(m, &k, s->eef_pos);
@@ -3066,32 +3011,9 @@ static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, flo
     else r = -1.0;
     if (sk->gripped) r += m->object_gripped_reward;
   }
-  if (goal_reached) s->n_goal_reached++;
-  int illegal = (collision_type & (HRG_COL_STATIC | HRG_COL_ROBOT | HRG_COL_HUMAN_CRIT)) != 0;
-  if (m->reward_shaping) r += 1.0 + 0.0; /* _dense_reward is a TODO returning 0 (681-698) */
-  if (illegal) r += m->collision_reward;
-  r *= m->reward_scale;
-  int d = 0;
-  if (crash) { r += m->sim_crash_reward; d = 1; }
-  else {
-    if (toppled) d = 1; /* _check_done (758-778) */
-    if (m->done_at_collision && illegal) d = 1;
-    if (m->done_at_success && goal_reached) d = 1;
-  }
-  int ncoll = s->n_collisions_static + s->n_collisions_robot + s->n_collisions_human + s->n_collisions_critical;
-  info[HRG_INFO_COLLISION] = has_collision;
-  info[HRG_INFO_COLLISION_TYPE] = collision_type;
-  info[HRG_INFO_N_COLLISIONS] = ncoll;
-  info[HRG_INFO_N_COLLISIONS_STATIC] = s->n_collisions_static;
-  info[HRG_INFO_N_COLLISIONS_ROBOT] = s->n_collisions_robot;
-  info[HRG_INFO_N_COLLISIONS_HUMAN] = s->n_collisions_human;
-  info[HRG_INFO_N_COLLISIONS_CRITICAL] = s->n_collisions_critical;
-  info[HRG_INFO_TIMEOUT] = s->timestep >= m->horizon;
-  info[HRG_INFO_FAILSAFE_INTERVENTIONS] = s->failsafe_interventions;
-  info[HRG_INFO_N_GOAL_REACHED] = s->n_goal_reached;
-  info[HRG_INFO_SIM_CRASH] = crash;
-  info[HRG_INFO_TRUNCATED] = 0;
-  info[HRG_INFO_ACTION_RESAMPLES] = s->action_resamples;
+  int d = reward_and_done(m, s, collision_type, crash, goal_reached, 0.0, &r); /* _dense_reward is a TODO returning 0 (681-698) */
+  if (toppled) d = 1; /* _check_done (758-778) */
+  fill_info(m, s, has_collision, collision_type, crash, info);
   info[HRG_INFO_MAX_STACK_HEIGHT] = sk->max_stack_height; /* _get_info (673-679): the value before this step's transitions */
   /* ---- CollaborativeStackingCart.step tail (550-588) ---- */
   if (goal_reached && !m->done_at_success && !d) { /* _on_goal_reached (961-977): next placements of the robot's cubes (velocities kept), next animation */
@@ -3100,16 +3022,10 @@ static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, flo
       stack_placement(B, gid, s->episode, sk->obj_index, c, sk->pos[c]);
       sk->quat[c][0] = 1; sk->quat[c][1] = sk->quat[c][2] = sk->quat[c][3] = 0;
     }
-    s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
-    s->animation_time = 0;
-    s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+    next_animation(m, s);
     sk->task_phase = HRG_STK_APPROACH; sk->n_delayed[0] = sk->n_delayed[1] = 0;
-    human_kin hk2;
-    double mp[3], mq[4];
-    const double* qh;
-    human_control_sk(B, gid, s, NULL, sk, mp, mq, &qh);
-    human_fk(m, mp, mq, qh, &hk2, s->human_site);
-    stack_mocap(m, s, sk, &hk2);
+    pose_human(B, gid, s, NULL, sk, NULL, &hk);
+    stack_mocap(m, s, sk, &hk);
     stack_reset_animation(m, sk);
   }
   if (!d) {
@@ -3139,11 +3055,7 @@ static void env_step_stack(hrgo_batch* B, int e, double* action, float* obs, flo
     }
     if (sk->n_stack > sk->max_stack_height) sk->max_stack_height = sk->n_stack;
   }
-  if (s->timestep >= m->horizon) { info[HRG_INFO_TRUNCATED] = !d; d = 1; }
-  *reward = (float)r;
-  *done = (uint8_t)d;
-  if (d) env_reset(B, e, obs);
-  else memcpy(obs, term_obs, sizeof(float) * HRG_OBS_DIM);
+  finish_step(B, e, r, d, obs, term_obs, reward, done, info);
 }
 
 /* =============================================================================================== CollaborativeHammeringCart
@@ -3361,10 +3273,8 @@ static void env_reset_hammer(hrgo_batch* B, int e, const robot_kin* k) {
   memset(hm, 0, sizeof *hm);
   hm->quat[0][0] = 1;
   human_kin hk;
-  double mp[3], mq[4], Rg[9], t[3];
-  const double* qh;
-  human_control_all(B, gid, s, NULL, NULL, hm, mp, mq, &qh); /* _control_human + _reset_animation: phase APPROACH (memset), the human holds the board */
-  human_fk(m, mp, mq, qh, &hk, s->human_site);
+  double Rg[9], t[3];
+  pose_human(B, gid, s, NULL, NULL, hm, &hk); /* _control_human + _reset_animation: phase APPROACH (memset), the human holds the board */
   hammer_mocap(m, s, hm, &hk);
   hammer_take_board(B, gid, s, hm);
   /* _put_hammer_into_gripper (790-812): the hammer's root body at the grip site, turned 90 deg about y; at rest */
@@ -3423,46 +3333,23 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
   int has_collision = 0, collision_type = HRG_COL_NULL, failsafe_intervention = 0, crash = 0;
   robot_kin k;
   human_kin hk;
+  hammer_geo G;
   double M[NV * NV], bias[NV];
+  const free_body fb[3] = { /* by HRG_HM_BOARD / _HAMMER / _NAIL: the nail's contacts act on the board's DoF and on the slide joint */
+    {hm->pos[0], hm->quat[0], HM_OB, 1.0 / m->hm_board_mass, m->hm_board_invweight_rot, NULL, 0},
+    {hm->pos[1], hm->quat[1], HM_OH, 1.0 / m->hm_hammer_mass, 0.0, NULL, 0},
+    {hm->pos[0], hm->quat[0], HM_OB, m->hm_nail_invweight, 0.0, G.axis, HM_ON}};
   for (int cyc = 0; cyc < m->n_cycles && !crash; cyc++) {
     robot_fk(m, s->qpos, &k);
     robot_crba(m, &k, M);
     robot_bias(m, &k, s->qvel, bias);
-    if (cyc == 0) { /* failsafe_controller.py:252-300 */
-      for (int i = 0; i < NARM; i++) for (int j = 0; j < NARM; j++) s->mass_matrix[i * NARM + j] = M[i * NV + j];
-      double scale = fabs(m->act_out_max - m->act_out_min) / fabs(m->act_in_max - m->act_in_min);
-      double otr = 0.5 * (m->act_out_max + m->act_out_min), itr = 0.5 * (m->act_in_max + m->act_in_min);
-      for (int j = 0; j < NARM; j++) {
-        double a = clampd(action[j], m->act_in_min, m->act_in_max);
-        double g = s->qpos[j] + ((a - itr) * scale + otr);
-        s->goal_qpos[j] = clampd(g, m->qpos_limits[0][j], m->qpos_limits[1][j]);
-        s->new_goal_q[j] = s->goal_qpos[j];
-      }
-      s->new_goal = 1;
-    }
+    if (cyc == 0) controller_goal(m, s, M, action);
     shield_step(B, e, s->time);
     double ctrl[NV];
-    for (int i = 0; i < NARM; i++) {
-      double t = 0;
-      for (int j = 0; j < NARM; j++) t += s->mass_matrix[i * NARM + j] * (m->kp * (s->des_q[j] - s->qpos[j]) + m->kd * (s->des_v[j] - s->qvel[j]) + s->des_a[j]);
-      ctrl[i] = clampd(t + bias[i], m->arm_ctrlrange[i][0], m->arm_ctrlrange[i][1]);
-    }
-    {
-      double a = action[NARM], sg = a > 0 ? 1.0 : (a < 0 ? -1.0 : 0.0);
-      s->grip_action = clampd(s->grip_action - m->gripper_speed * sg, -1.0, 1.0);
-      for (int f = 0; f < HRG_NFINGER; f++) {
-        double lo = m->finger_ctrlrange[f][0], hi = m->finger_ctrlrange[f][1];
-        ctrl[NARM + f] = 0.5 * (hi + lo) + 0.5 * (hi - lo) * (f == 0 ? s->grip_action : -s->grip_action);
-      }
-    }
-    if (!failsafe_intervention && !s->is_safe) { failsafe_intervention = 1; s->failsafe_interventions++; }
+    arm_and_gripper_ctrl(m, s, bias, action, ctrl, &failsafe_intervention);
     /* _control_human (682-686): super + sim.forward() + the two hand mocap bodies */
-    double mp[3], mq[4];
-    const double* qh;
-    human_control_all(B, gid, s, NULL, NULL, hm, mp, mq, &qh);
-    human_fk(m, mp, mq, qh, &hk, s->human_site);
+    pose_human(B, gid, s, NULL, NULL, hm, &hk);
     hammer_mocap(m, s, hm, &hk);
-    hammer_geo G;
     hammer_geometry(m, hm, &G);
     contact_t con[HRG_NCON_MAX];
     int ncon = collide_hammer(m, &k, &hk, hm, &G, con);
@@ -3470,34 +3357,13 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
       const int gn = GEOM_BOX + HRG_HG_NAIL, o = con[c].g1 == gn ? con[c].g2 : (con[c].g2 == gn ? con[c].g1 : -1);
       if (o >= 0 && o != GEOM_BOX + HRG_HG_BOARD) hm->nail_touch |= (o == GEOM_BOX + HRG_HG_HANDLE || o == GEOM_BOX + HRG_HG_HEAD) ? 1 : 2;
     }
-    double rc[HRG_NRCAP][3], Rb[9];
-    quat2mat(Rb, m->base_quat);
-    for (int c = 0; c < HRG_NRCAP; c++) {
-      int b = m->rcap_body[c];
-      double t[3], mid[3];
-      for (int a = 0; a < 3; a++) mid[a] = 0.5 * (m->rcap_p1[c][a] + m->rcap_p2[c][a]);
-      m3mulv(t, b < 0 ? Rb : k.R[b], mid);
-      v3add(rc[c], b < 0 ? m->base_pos : k.p[b], t);
-    }
-    classify(m, &k, s, con, ncon, rc, &has_collision, &collision_type);
-    s->ncon = ncon;
-    for (int c = 0; c < HRG_NCON_MAX; c++) { s->con_pairs[c][0] = c < ncon ? con[c].g1 : -1; s->con_pairs[c][1] = c < ncon ? con[c].g2 : -1; }
+    record_contacts(m, &k, s, con, ncon, &has_collision, &collision_type);
     /* ---- sim.step(): robot tree | board + nail | hammer ---- */
-    double LM[NV * NV], a0[NVH], qd[NVH], frc[NV], Mt[NVH * NVH], M8[64], f8[8];
-    memcpy(LM, M, sizeof LM);
-    if (!chol(LM, NV)) { crash = 1; break; }
+    double a0[NVH], qd[NVH], Mt[NVH * NVH], M8[64], f8[8];
     memset(Mt, 0, sizeof Mt);
     memset(a0, 0, sizeof a0);
     memset(qd, 0, sizeof qd);
-    for (int i = 0; i < NV; i++) {
-      double act = ctrl[i];
-      if (i >= NARM) act = clampd(m->finger_kp * (ctrl[i] - s->qpos[i]), m->finger_forcerange[0], m->finger_forcerange[1]);
-      frc[i] = act - m->jnt_damping[i] * s->qvel[i] - bias[i];
-      a0[i] = frc[i];
-      qd[i] = s->qvel[i];
-    }
-    chol_solve(LM, NV, a0);
-    for (int i = 0; i < NV; i++) for (int j = 0; j < NV; j++) Mt[i * NVH + j] = M[i * NV + j];
+    if (!robot_smooth(m, s, M, bias, ctrl, NVH, Mt, a0, qd)) { crash = 1; break; }
     hammer_board_block(m, hm, &G, M8, f8);
     for (int i = 0; i < 8; i++) for (int j = 0; j < 8; j++) Mt[(HM_OB + i) * NVH + HM_OB + j] = M8[8 * i + j];
     {
@@ -3507,7 +3373,7 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
       chol_solve(L8, 8, x8);
       for (int i = 0; i < 8; i++) a0[HM_OB + i] = x8[i];
     }
-    { /* the hammer: free body, M = blockdiag(m 1, R diag(I) R'), gyroscopic torque -(w x I w), gravity */
+    { /* the hammer: free body, M = blockdiag(m 1, R diag(I) R'), gyroscopic torque -(w x I w), gravity (no mean / deviation split: not a cube) */
       const double* R = G.R[1];
       double Iw[9], w[3] = {hm->vel[1][3], hm->vel[1][4], hm->vel[1][5]}, Lw[3], tau[3], tl[3];
       for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { double t = 0; for (int kk = 0; kk < 3; kk++) t += R[3 * i + kk] * m->hm_hammer_inertia[kk] * R[3 * j + kk]; Iw[3 * i + j] = t; }
@@ -3527,77 +3393,20 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
     efc_t* E = (efc_t*)malloc(sizeof(efc_t));
     E->n = 0;
     E->nv = NVH;
-    for (int i = 0; i < NV; i++)
-      if (m->jnt_frictionloss[i] > 0) { double J[NVMAX] = {0}; J[i] = 1; efc_add(m, E, J, qd, ROW_FRICTION, 0, 0, m->jnt_frictionloss[i], m->dof_invweight0[i]); }
+    friction_rows(m, E, qd);
     if (m->hm_nail_frictionloss > 0) { /* nail_head_joint0: frictionloss with its own solreffriction (nail.xml:7) */
       double J[NVMAX] = {0}; J[HM_ON] = 1;
       efc_add_b(m, E, J, qd, ROW_FRICTION, 0, 0, m->hm_nail_frictionloss, m->hm_nail_invweight, m->hm_nail_fric_damping / m->solimp[1]);
     }
-    for (int i = 0; i < NV; i++) {
-      double dlo = s->qpos[i] - m->jnt_range[i][0], dhi = m->jnt_range[i][1] - s->qpos[i];
-      if (dlo < 0) { double J[NVMAX] = {0}; J[i] = 1; efc_add(m, E, J, qd, ROW_UNILATERAL, dlo, 0, 0, m->dof_invweight0[i]); }
-      if (dhi < 0) { double J[NVMAX] = {0}; J[i] = -1; efc_add(m, E, J, qd, ROW_UNILATERAL, dhi, 0, 0, m->dof_invweight0[i]); }
-    }
-    { /* the slide joint's range [0, hm_nail_range] */
-      double dlo = hm->nail_q, dhi = m->hm_nail_range - hm->nail_q;
-      if (dlo < 0) { double J[NVMAX] = {0}; J[HM_ON] = 1; efc_add(m, E, J, qd, ROW_UNILATERAL, dlo, 0, 0, m->hm_nail_invweight); }
-      if (dhi < 0) { double J[NVMAX] = {0}; J[HM_ON] = -1; efc_add(m, E, J, qd, ROW_UNILATERAL, dhi, 0, 0, m->hm_nail_invweight); }
-    }
-    for (int c = 0; c < ncon && c < HRG_NCON_DYN_HAMMER; c++) {
-      const double* n = con[c].n;
-      double t1[3], t2[3], e1[3] = {1, 0, 0}, e2[3] = {0, 1, 0};
-      v3cross(t1, n, fabs(n[0]) < 0.5 ? e1 : e2);
-      v3scl(t1, t1, 1.0 / v3norm(t1));
-      v3cross(t2, n, t1);
-      double margin = (con[c].g2 >= GEOM_HUMAN0 && con[c].g2 < GEOM_TABLE) || (con[c].g1 >= GEOM_HUMAN0 && con[c].g1 < GEOM_TABLE) ? m->contact_margin_human : 0.0; /* a human geom on either side */
-      for (int d = 0; d < 4; d++) {
-        double dir[3], J[NVMAX] = {0};
-        const double* tt = d < 2 ? t1 : t2;
-        double sg = (d & 1) ? -1.0 : 1.0;
-        for (int a = 0; a < 3; a++) dir[a] = n[a] + sg * m->friction_static * tt[a];
-        if (con[c].b1 >= 0 && con[c].b1 < NV) robot_point_jac(m, &k, con[c].b1, con[c].pos, dir, -1.0, J);
-        if (con[c].b2 >= 0 && con[c].b2 < NV) robot_point_jac(m, &k, con[c].b2, con[c].pos, dir, +1.0, J);
-        double diag = (con[c].b1 >= 0 && con[c].b1 < NV ? m->body_invweight0[con[c].b1] : 0.0) + (con[c].b2 >= 0 && con[c].b2 < NV ? m->body_invweight0[con[c].b2] : 0.0);
-        for (int side = 0; side < 2; side++) { /* free bodies: J = +-dir . (v + w x r); the nail's point moves with the board and along the slide axis */
-          const int body = side ? con[c].b2 : con[c].b1;
-          if (body < BODY_BOX) continue;
-          const int fb = body - BODY_BOX, o = fb == HRG_HM_HAMMER ? HM_OH : HM_OB;
-          const double sgn = side ? 1.0 : -1.0;
-          double r[3], rxd[3];
-          v3sub(r, con[c].pos, hm->pos[fb == HRG_HM_HAMMER ? 1 : 0]);
-          v3cross(rxd, r, dir);
-          for (int a = 0; a < 3; a++) { J[o + a] = sgn * dir[a]; J[o + 3 + a] = sgn * rxd[a]; }
-          if (fb == HRG_HM_NAIL) { J[HM_ON] = sgn * v3dot(dir, G.axis); diag += m->hm_nail_invweight; }
-          else diag += 1.0 / (fb == HRG_HM_HAMMER ? m->hm_hammer_mass : m->hm_board_mass);
-        }
-        const int n_before = E->n;
-        efc_add(m, E, J, qd, ROW_UNILATERAL, con[c].dist, margin, 0, diag * (1.0 + m->friction_static * m->friction_static));
-        if (E->n > n_before) E->grp[n_before] = 4 * c + d;
-      }
-    }
-    { /* lh_eq: connect(lh_grip, lh_mocap); rh_eq: weld(rh_grip, rh_mocap) (1100-1145); both stay active (the switch to rh_backup_eq is commented out, 650) */
-      const double* R = G.R[0];
-      for (int hd = 0; hd < 2; hd++) {
-        double rr[3], pt[3];
-        m3mulv(rr, R, m->hm_anchor[hd]);
-        v3add(pt, hm->pos[0], rr);
-        for (int a = 0; a < 3; a++) {
-          double J[NVMAX] = {0}, ea[3] = {a == 0, a == 1, a == 2}, rxe[3];
-          v3cross(rxe, rr, ea);
-          J[HM_OB + a] = 1;
-          for (int b_ = 0; b_ < 3; b_++) J[HM_OB + 3 + b_] = rxe[b_];
-          efc_add(m, E, J, qd, ROW_EQUALITY, pt[a] - hm->mocap_pos[hd][a], 0, 0, 1.0 / m->hm_board_mass);
-        }
-      }
-      double qt[4], qe[4], erot[3];
-      hammer_weld_quat(m, hm, qt);
-      const double qc[4] = {qt[0], -qt[1], -qt[2], -qt[3]};
-      quatmul(qe, hm->quat[0], qc);
-      if (qe[0] < 0) for (int a = 0; a < 4; a++) qe[a] = -qe[a];
-      const double sn = sqrt(qe[1] * qe[1] + qe[2] * qe[2] + qe[3] * qe[3]), ang = 2.0 * atan2(sn, qe[0]);
-      for (int a = 0; a < 3; a++) erot[a] = sn > 1e-12 ? qe[1 + a] / sn * ang : 0.0;
-      for (int a = 0; a < 3; a++) { double J[NVMAX] = {0}; J[HM_OB + 3 + a] = 1; efc_add(m, E, J, qd, ROW_EQUALITY, erot[a], 0, 0, m->hm_board_invweight_rot); }
-    }
+    limit_rows(m, s, E, qd);
+    limit_row(m, E, qd, HM_ON, hm->nail_q, m->hm_nail_range - hm->nail_q, m->hm_nail_invweight); /* the slide joint's range [0, hm_nail_range] */
+    contact_rows(m, &k, con, ncon, HRG_NCON_DYN_HAMMER, fb, E, qd);
+    /* lh_eq: connect(lh_grip, lh_mocap); rh_eq: weld(rh_grip, rh_mocap) (1100-1145) = a connect plus the weld's rotation rows; both stay active (the
+     * switch to rh_backup_eq is commented out, 650) */
+    for (int hd = 0; hd < 2; hd++) connect_rows(m, E, qd, &fb[HRG_HM_BOARD], m->hm_anchor[hd], hm->mocap_pos[hd]);
+    double qt[4];
+    hammer_weld_quat(m, hm, qt);
+    weld_rows(m, E, qd, &fb[HRG_HM_BOARD], NULL, qt);
     double qacc[NVH];
     memset(qacc, 0, sizeof qacc);
     memcpy(qacc, s->qacc_warmstart, sizeof(double) * NV);
@@ -3612,28 +3421,9 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
       fprintf(stderr, "\n");
     }
     free(E);
-    for (int i = 0; i < NVH; i++) if (!(fabs(qacc[i]) < 1e10)) crash = 1;
-    if (crash) break;
-    memcpy(s->qacc_warmstart, qacc, sizeof(double) * NV);
-    double Mh[NV * NV], rhs[NV];
-    memcpy(Mh, M, sizeof Mh);
-    for (int i = 0; i < NV; i++) { Mh[i * NV + i] += h * m->jnt_damping[i]; double t = 0; for (int j = 0; j < NV; j++) t += M[i * NV + j] * qacc[j]; rhs[i] = t; }
-    if (!chol(Mh, NV)) { crash = 1; break; }
-    chol_solve(Mh, NV, rhs);
-    for (int i = 0; i < NV; i++) { s->qvel[i] += h * rhs[i]; s->qpos[i] += h * s->qvel[i]; }
+    if (!robot_euler(m, s, M, qacc, NVH)) { crash = 1; break; }
     hammer_obs_pos(m, hm); /* body_xpos of the forward pass inside mj_step (pre-integration) */
-    for (int fb = 0; fb < 2; fb++) {
-      const int o = fb ? HM_OH : HM_OB;
-      for (int a = 0; a < 6; a++) { hm->acc_warmstart[fb][a] = qacc[o + a]; hm->vel[fb][a] += h * qacc[o + a]; }
-      for (int a = 0; a < 3; a++) hm->pos[fb][a] += h * hm->vel[fb][a];
-      double w[3] = {hm->vel[fb][3], hm->vel[fb][4], hm->vel[fb][5]}, wn = v3norm(w), ang = h * wn;
-      if (wn > 1e-12) {
-        double sh = sin(0.5 * ang) / wn, dq[4] = {cos(0.5 * ang), w[0] * sh, w[1] * sh, w[2] * sh}, qn[4];
-        quatmul(qn, dq, hm->quat[fb]);
-        double nn = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
-        for (int a = 0; a < 4; a++) hm->quat[fb][a] = qn[a] / nn;
-      }
-    }
+    for (int b = 0; b < 2; b++) free_body_euler(h, qacc + fb[b].dof, hm->pos[b], hm->quat[b], hm->vel[b], hm->acc_warmstart[b]);
     if (g_debug > 2) fprintf(stderr, "[nail] cyc %d qacc %.4e v %.4e q %.4e ncon %d nefc %d\n", cyc, qacc[HM_ON], hm->nail_v, hm->nail_q, ncon, 0);
     hm->nail_acc_warmstart = qacc[HM_ON];
     hm->nail_v += h * qacc[HM_ON];
@@ -3653,54 +3443,21 @@ static void env_step_hammer(hrgo_batch* B, int e, double* action, float* obs, fl
     r = hammered_in ? m->nail_hammered_in_reward : -1.0;
     if (hm->gripped) r += m->hammer_gripped_reward_bonus;
   }
-  if (goal_reached) s->n_goal_reached++;
-  int illegal = (collision_type & (HRG_COL_STATIC | HRG_COL_ROBOT | HRG_COL_HUMAN_CRIT)) != 0;
-  if (m->reward_shaping) r += 1.0 + 0.0; /* _dense_reward is a TODO returning 0 (558-574) */
-  if (illegal) r += m->collision_reward;
-  r *= m->reward_scale;
-  int d = 0;
-  if (crash) { r += m->sim_crash_reward; d = 1; }
-  else {
-    if (m->done_at_collision && illegal) d = 1;
-    if (m->done_at_success && goal_reached) d = 1;
-  }
-  int ncoll = s->n_collisions_static + s->n_collisions_robot + s->n_collisions_human + s->n_collisions_critical;
-  info[HRG_INFO_COLLISION] = has_collision;
-  info[HRG_INFO_COLLISION_TYPE] = collision_type;
-  info[HRG_INFO_N_COLLISIONS] = ncoll;
-  info[HRG_INFO_N_COLLISIONS_STATIC] = s->n_collisions_static;
-  info[HRG_INFO_N_COLLISIONS_ROBOT] = s->n_collisions_robot;
-  info[HRG_INFO_N_COLLISIONS_HUMAN] = s->n_collisions_human;
-  info[HRG_INFO_N_COLLISIONS_CRITICAL] = s->n_collisions_critical;
-  info[HRG_INFO_TIMEOUT] = s->timestep >= m->horizon;
-  info[HRG_INFO_FAILSAFE_INTERVENTIONS] = s->failsafe_interventions;
-  info[HRG_INFO_N_GOAL_REACHED] = s->n_goal_reached;
-  info[HRG_INFO_SIM_CRASH] = crash;
-  info[HRG_INFO_TRUNCATED] = 0;
-  info[HRG_INFO_ACTION_RESAMPLES] = s->action_resamples;
+  const int d = reward_and_done(m, s, collision_type, crash, goal_reached, 0.0, &r); /* _dense_reward is a TODO returning 0 (558-574) */
+  fill_info(m, s, has_collision, collision_type, crash, info);
   info[HRG_INFO_N_OBJECT_HANDED_OVER] = 0;
   /* ---- CollaborativeHammeringCart.step tail (490-503) ---- */
   if (goal_reached && !m->done_at_success && !d) { /* _on_goal_reached (749-767): next nail placement, board and nail reset, next animation */
     hm->nail_index = (hm->nail_index + 1) % m->n_obj_placements;
-    s->anim_index = (s->anim_index + 1) % m->n_anim_ids;
-    s->animation_time = 0;
-    s->anim_start_time = (int)((double)s->low_level_time / m->anim_step_length);
+    next_animation(m, s);
     hm->task_phase = HRG_HM_APPROACH; hm->n_delayed = 0;
-    human_kin hk2;
-    double mp[3], mq[4];
-    const double* qh;
-    human_control_all(B, gid, s, NULL, NULL, hm, mp, mq, &qh);
-    human_fk(m, mp, mq, qh, &hk2, s->human_site);
-    hammer_mocap(m, s, hm, &hk2);
+    pose_human(B, gid, s, NULL, NULL, hm, &hk);
+    hammer_mocap(m, s, hm, &hk);
     hm->task_phase = HRG_HM_APPROACH; hm->n_delayed = 0; /* _reset_animation (764-767, 770-774) */
     hammer_take_board(B, gid, s, hm);
   }
   if (!d && hm->task_phase == HRG_HM_PRESENT && hammered_in) hm->task_phase = HRG_HM_RETREAT; /* 496-501 */
-  if (s->timestep >= m->horizon) { info[HRG_INFO_TRUNCATED] = !d; d = 1; }
-  *reward = (float)r;
-  *done = (uint8_t)d;
-  if (d) env_reset(B, e, obs);
-  else memcpy(obs, term_obs, sizeof(float) * HRG_OBS_DIM);
+  finish_step(B, e, r, d, obs, term_obs, reward, done, info);
 }
 
 /* =============================================================================================== API */
@@ -3845,46 +3602,22 @@ int hrgo_set_states(hrgo_batch* B, const hrg_env_state* st, const hrg_box_state*
   if (hmr) memcpy(B->hmr, hmr, n * sizeof *hmr);
   return 0;
 }
-int hrgo_get_state(hrgo_batch* B, int e, void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_env_state)) return -1;
-  memcpy(buf, &B->st[e], bytes);
+/* one env's state block of one kind, out of (set = 0) or into (set = 1) the batch; bytes must be the block's size */
+static int block_copy(hrgo_batch* B, int e, void* blocks, size_t block, void* buf, size_t bytes, int set) {
+  if (e < 0 || e >= B->n_envs || bytes != block) return -1;
+  char* p = (char*)blocks + (size_t)e * block;
+  if (set) memcpy(p, buf, bytes);
+  else memcpy(buf, p, bytes);
   return 0;
 }
-int hrgo_set_state(hrgo_batch* B, int e, const void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_env_state)) return -1;
-  memcpy(&B->st[e], buf, bytes);
-  return 0;
-}
-int hrgo_get_box(hrgo_batch* B, int e, void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_box_state)) return -1;
-  memcpy(buf, &B->box[e], bytes);
-  return 0;
-}
-int hrgo_set_box(hrgo_batch* B, int e, const void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_box_state)) return -1;
-  memcpy(&B->box[e], buf, bytes);
-  return 0;
-}
-int hrgo_get_stack(hrgo_batch* B, int e, void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_stack_state)) return -1;
-  memcpy(buf, &B->stk[e], bytes);
-  return 0;
-}
-int hrgo_get_hammer(hrgo_batch* B, int e, void* buf, size_t bytes) {
-  if (e < 0 || e >= B->n_envs || bytes != sizeof(hrg_hammer_state)) return -1;
-  memcpy(buf, &B->hmr[e], bytes);
-  return 0;
-}
-int hrgo_set_hammer(hrgo_batch* B, int e, const void* buf, size_t bytes) {
-  if (e < 0 || e >= B->n_envs || bytes != sizeof(hrg_hammer_state)) return -1;
-  memcpy(&B->hmr[e], buf, bytes);
-  return 0;
-}
-int hrgo_set_stack(hrgo_batch* B, int e, const void* buf, size_t bytes) {
-  if (bytes != sizeof(hrg_stack_state)) return -1;
-  memcpy(&B->stk[e], buf, bytes);
-  return 0;
-}
+int hrgo_get_state(hrgo_batch* B, int e, void* buf, size_t bytes) { return block_copy(B, e, B->st, sizeof(hrg_env_state), buf, bytes, 0); }
+int hrgo_set_state(hrgo_batch* B, int e, const void* buf, size_t bytes) { return block_copy(B, e, B->st, sizeof(hrg_env_state), (void*)buf, bytes, 1); }
+int hrgo_get_box(hrgo_batch* B, int e, void* buf, size_t bytes) { return block_copy(B, e, B->box, sizeof(hrg_box_state), buf, bytes, 0); }
+int hrgo_set_box(hrgo_batch* B, int e, const void* buf, size_t bytes) { return block_copy(B, e, B->box, sizeof(hrg_box_state), (void*)buf, bytes, 1); }
+int hrgo_get_stack(hrgo_batch* B, int e, void* buf, size_t bytes) { return block_copy(B, e, B->stk, sizeof(hrg_stack_state), buf, bytes, 0); }
+int hrgo_set_stack(hrgo_batch* B, int e, const void* buf, size_t bytes) { return block_copy(B, e, B->stk, sizeof(hrg_stack_state), (void*)buf, bytes, 1); }
+int hrgo_get_hammer(hrgo_batch* B, int e, void* buf, size_t bytes) { return block_copy(B, e, B->hmr, sizeof(hrg_hammer_state), buf, bytes, 0); }
+int hrgo_set_hammer(hrgo_batch* B, int e, const void* buf, size_t bytes) { return block_copy(B, e, B->hmr, sizeof(hrg_hammer_state), (void*)buf, bytes, 1); }
 size_t hrgo_stack_bytes(void) { return sizeof(hrg_stack_state); }
 /* known-answer tap: contacts of two equal boxes (tests/test_stacking.py); out = n x [pos 3, normal 3, dist] */
 int hrgo_test_boxbox(const double* pa, const double* qa, const double* pb, const double* qb, const double* half, double* out) {

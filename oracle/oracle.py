@@ -17,10 +17,13 @@ def build(force=False):
     return _SO
 
 
-def load():
-    if not os.path.exists(_SO):
-        build()
-    lib = ctypes.CDLL(_SO)
+def load(path=None):
+    """The oracle library: the one built in oracle/_build, or the build at `path` (tools/oracle_diff.py compares two)."""
+    if path is None:
+        if not os.path.exists(_SO):
+            build()
+        path = _SO
+    lib = ctypes.CDLL(os.path.abspath(path))
     lib.hrgo_state_bytes.restype = ctypes.c_size_t
     lib.hrgo_desc_bytes.restype = ctypes.c_size_t
     lib.hrgo_test_segseg.restype = ctypes.c_double
@@ -39,11 +42,11 @@ def _p(a):
 class OracleBatch:
     """Same surface as human_robot_gym_amd._lib.HipBatch, on numpy arrays."""
 
-    def __init__(self, desc, clips, n_envs, env_id0=0):
+    def __init__(self, desc, clips, n_envs, env_id0=0, lib_path=None):
         from human_robot_gym_amd._cstruct import CONST, EnvState
         self.C = CONST
         self.EnvState = EnvState
-        self.lib = load()
+        self.lib = load(lib_path)
         assert self.lib.hrgo_state_bytes() == ctypes.sizeof(EnvState)
         assert self.lib.hrgo_desc_bytes() == ctypes.sizeof(type(desc))
         self.n = n_envs
