@@ -112,6 +112,7 @@ StackState = _STRUCTS["hrg_stack_state"]
 HammerState = _STRUCTS["hrg_hammer_state"]
 ExpertDesc = _STRUCTS["hrg_expert_desc"]
 DatasetDesc = _STRUCTS["hrg_dataset_desc"]
+HerDesc = _STRUCTS["hrg_her_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 

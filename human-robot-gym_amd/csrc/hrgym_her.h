@@ -1,0 +1,225 @@
+// hrgym_her.h -- hindsight experience replay on the device: the replay buffer of SAC + HER (SB3's HerReplayBuffer with the reference's patches,
+// wrappers/HER_buffer_add_monkey_patch.py) for a batch of goal envs, in four small kernels next to the (unchanged) step launch.  Included into the base
+// translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_dataset.h.
+//
+//   hrg_her_add_kernel           custom_add (26-117) for every env: one transition into the env's ring, episode bookkeeping.  One wavefront per env, lane l
+//                                moves column l of each 256-byte observation row.
+//   hrg_her_observe_kernel       the first observation of an episode after a reset; the unfinished episode of a reset env is discarded.
+//   hrg_her_sample_kernel        _custom_sample_transitions (120-286), online sampling: one wavefront per sample, four per block, no LDS, no atomics.
+//   hrg_goal_reward_done_kernel  HumanEnv._compute_reward / _check_done of caller-supplied goal rows, one thread per row; the sample kernel calls the same
+//                                device function for its relabelled samples.
+//
+// The ring of env e: slot = write counter % capacity.  Three counters per env: w (next write), tail (oldest valid transition), open (first transition of
+// the running episode); tail <= open <= w, w - tail <= capacity.  Every slot carries ep_start (counter of its episode's first transition) and ep_len (0 while
+// the episode runs; back-filled over the episode when it ends).  When the ring is full the oldest episode leaves whole, so the closed transitions of an env
+// are always the contiguous counter range [tail, open): the sampler needs one prefix sum over the envs and no episode table.
+//
+// Draws: rng_u01 keyed by (buffer seed, sample call counter, index of the sample in its batch, STREAM_HER, 0..2): independent of the grid and of the batch
+// size, and no stream of the step / reset / expert / dataset kernels moves.
+#pragma once
+
+enum { STREAM_HER = 10 };   // after STREAM_DATASET = 9 (hrgym_dataset.h)
+#define HRG_HER_BLOCK 256
+
+// the buffers of one hrg_her; passed to the kernels by value
+struct HerDev {
+  float* pre = nullptr;        // [n][cap][HRG_OBS_DIM] the row before the step
+  float* post = nullptr;       // [n][cap][HRG_OBS_DIM] the row after it (the terminal observation where the step finished the env)
+  float* act = nullptr;        // [n][cap][act_dim]
+  float* reward = nullptr;     // [n][cap]
+  uint8_t* done = nullptr;     // [n][cap]
+  uint8_t* trunc = nullptr;    // [n][cap] TimeLimit.truncated
+  int32_t* ctype = nullptr;    // [n][cap] collision_type
+  int64_t* ep_start = nullptr; // [n][cap]
+  int32_t* ep_len = nullptr;   // [n][cap]
+  int64_t* w = nullptr;        // [n]
+  int64_t* tail = nullptr;     // [n]
+  int64_t* open = nullptr;     // [n]
+  float* cur_obs = nullptr;    // [n][HRG_OBS_DIM] the row the next transition starts from
+  const int32_t* obs_cols = nullptr;   // [HRG_OBS_DIM] hrg_her_desc::obs_cols (a per-lane lookup: device memory, not a kernel argument)
+};
+
+// columns of the observation superset behind the goals (vec_env.HipVecEnv._init_columns)
+DI int her_ag_dim(int kind) { return kind == HRG_GOAL_REACH ? 6 : 7; }
+DI int her_dg_dim(int kind) { return kind == HRG_GOAL_REACH ? 6 : 3; }
+DI int her_ag_col(int kind, int d) { return kind == HRG_GOAL_REACH ? 18 + d : d < 3 ? 30 + d : d < 6 ? 44 + d : 39; }   // joint positions | eef_pos, object_pos, object_gripped
+DI int her_dg_col(int kind, int d) { return kind == HRG_GOAL_REACH ? 33 + d : 50 + d; }                               // desired_goal | target_pos
+DI int her_new_goal_col(int kind, int d) { return kind == HRG_GOAL_REACH ? 18 + d : 47 + d; }                         // what a reached state offers as a goal
+
+// HumanEnv._compute_reward (human_env.py:629-664, 766-792) and _check_done (835-858) of one goal pair, the arithmetic of HipVecEnv.compute_reward /
+// compute_done: FP64 over the f32 values.  ag: her_ag_dim values, dg: her_dg_dim values.
+DI void goal_reward_done(const hrg_her_desc& p, const double* ag, const double* dg, int ctype, float* reward, bool* done) {
+  double r, dense, dist;
+  if (p.goal_kind == HRG_GOAL_REACH) {
+    double d2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) { const double d = ag[k] - dg[k]; d2 += d * d; }
+    dist = sqrt(d2);
+    r = dist <= p.goal_dist ? p.task_reward : -1.0;
+    dense = -0.1 * dist;
+  } else {
+    double a2 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { const double a = ag[3 + k] - ag[k], b = dg[k] - ag[3 + k]; a2 += a * a; b2 += b * b; }
+    const double e2o = sqrt(a2);
+    dist = sqrt(b2);
+    r = dist <= p.goal_dist ? p.task_reward : ag[6] != 0.0 ? p.object_gripped_reward : -1.0;
+    dense = -(e2o * 0.2 + dist) * 0.1;
+  }
+  if (p.reward_shaping) r = r + 1.0 + dense;
+  const bool illegal = (ctype & (HRG_COL_STATIC | HRG_COL_ROBOT | HRG_COL_HUMAN_CRIT)) != 0;
+  *reward = (float)((r + (illegal ? p.collision_reward : 0.0)) * p.reward_scale);
+  *done = (p.done_at_collision != 0 && illegal) || (p.done_at_success != 0 && dist <= p.goal_dist);
+}
+
+__global__ __launch_bounds__(HRG_HER_BLOCK) void hrg_goal_reward_done_kernel(const hrg_her_desc p, const float* __restrict__ ag, const float* __restrict__ dg,
+                                                                             const int32_t* __restrict__ ctype, int n, float* __restrict__ reward,
+                                                                             uint8_t* __restrict__ done) {
+  const int i = (int)(blockIdx.x * HRG_HER_BLOCK + threadIdx.x);
+  if (i >= n) return;
+  const int na = her_ag_dim(p.goal_kind), ng = her_dg_dim(p.goal_kind);
+  double a[7], g[6];
+#pragma unroll
+  for (int k = 0; k < 7; k++) a[k] = k < na ? (double)ag[(size_t)i * na + k] : 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) g[k] = k < ng ? (double)dg[(size_t)i * ng + k] : 0.0;
+  float r;
+  bool d;
+  goal_reward_done(p, a, g, ctype[i], &r, &d);
+  reward[i] = r;
+  done[i] = d ? 1 : 0;
+}
+
+// grid = n_envs blocks of one wavefront
+__global__ __launch_bounds__(64) void hrg_her_add_kernel(const hrg_her_desc p, const HerDev h, const double* __restrict__ actions, const float* __restrict__ obs,
+                                                         const float* __restrict__ term_obs, const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                                         const int32_t* __restrict__ info, int64_t* __restrict__ counts) {
+  const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (e >= p.n_envs) return;
+  const int64_t cap = p.capacity;
+  int64_t w = h.w[e], tail = h.tail[e], open = h.open[e];
+  const size_t ring = (size_t)e * (size_t)cap;
+  if (w - tail == cap) {   // full: the oldest episode leaves whole
+    const size_t ts = ring + (size_t)(tail % cap);
+    const int32_t len = h.ep_len[ts];
+    if (len > 0) tail = h.ep_start[ts] + len;
+    else tail = open = w;   // an episode longer than the ring (the caller's horizon was wrong): it is dropped, the ring stays consistent
+  }
+  const size_t s = ring + (size_t)(w % cap);
+  const bool dn = done[e] != 0;
+  h.pre[s * HRG_OBS_DIM + lane] = h.cur_obs[(size_t)e * HRG_OBS_DIM + lane];
+  const float o = obs[(size_t)e * HRG_OBS_DIM + lane];
+  h.post[s * HRG_OBS_DIM + lane] = dn ? term_obs[(size_t)e * HRG_OBS_DIM + lane] : o;
+  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = o;   // after an auto-reset: the new episode's first row
+  if (lane < p.act_dim) {
+    double a = actions[(size_t)e * HRG_ACT_DIM + lane];
+    if (p.rescale_actions) {   // HER_buffer_add_monkey_patch.py:64-76
+      a = 2.0 * ((a - p.act_low[lane]) / (p.act_high[lane] - p.act_low[lane])) - 1.0;
+      a = fmin(fmax(a, -1.0), 1.0);
+    }
+    h.act[s * (size_t)p.act_dim + lane] = (float)a;
+  }
+  if (lane == 0) {
+    h.reward[s] = reward[e];
+    h.done[s] = dn ? 1 : 0;
+    h.trunc[s] = info[(size_t)e * HRG_INFO_DIM + HRG_INFO_TRUNCATED] != 0 ? 1 : 0;
+    h.ctype[s] = info[(size_t)e * HRG_INFO_DIM + HRG_INFO_COLLISION_TYPE];
+    h.ep_start[s] = open;
+    if (!dn) h.ep_len[s] = 0;   // (where done, the back-fill below writes it)
+  }
+  w++;
+  if (dn) {
+    const int64_t len = w - open;   // <= cap
+    for (int64_t k = lane; k < len; k += 64) h.ep_len[ring + (size_t)((open + k) % cap)] = (int32_t)len;
+    open = w;
+  }
+  if (lane == 0) {
+    h.w[e] = w; h.tail[e] = tail; h.open[e] = open;
+    if (counts) counts[e] = open - tail;
+  }
+}
+
+// grid = n_envs blocks of one wavefront; mask null: every env
+__global__ __launch_bounds__(64) void hrg_her_observe_kernel(const hrg_her_desc p, const HerDev h, const float* __restrict__ obs, const uint8_t* __restrict__ mask,
+                                                             int64_t* __restrict__ counts) {
+  const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
+  if (e >= p.n_envs) return;
+  if (!mask || mask[e]) {
+    h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];
+    if (lane == 0) h.w[e] = h.open[e];   // the slots of the unfinished episode are written again
+  }
+  if (lane == 0 && counts) counts[e] = h.open[e] - h.tail[e];
+}
+
+// grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  `cum`: [n_envs + 1] exclusive prefix sums of the envs' closed transitions.
+__global__ __launch_bounds__(HRG_HER_BLOCK) void hrg_her_sample_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call, int batch,
+                                                                       float* __restrict__ o_obs, float* __restrict__ o_ag, float* __restrict__ o_dg,
+                                                                       float* __restrict__ o_nobs, float* __restrict__ o_nag, float* __restrict__ o_ndg,
+                                                                       float* __restrict__ o_act, float* __restrict__ o_rew, float* __restrict__ o_done,
+                                                                       int64_t* __restrict__ o_idx) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int k = (int)(blockIdx.x * (HRG_HER_BLOCK / 64) + (threadIdx.x >> 6));
+  if (k >= batch) return;
+  const int64_t N = cum[p.n_envs];
+  if (N <= 0) return;   // (the host refuses the call)
+  const double u0 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 0), u1 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 1), u2 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 2);
+  const int64_t j = min((int64_t)floor(u0 * (double)N), N - 1);
+  int lo = 0, hi = p.n_envs;   // the env with cum[e] <= j < cum[e + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cum[mid] <= j) lo = mid; else hi = mid;
+  }
+  const int e = lo;
+  const int64_t cap = p.capacity;
+  const size_t ring = (size_t)e * (size_t)cap;
+  const int64_t tail = h.tail[e], closed = h.open[e] - tail;
+  const int64_t i = tail + min(max(j - cum[e], (int64_t)0), max(closed - 1, (int64_t)0));   // (clamped: `cum` is the caller's)
+  const size_t s = ring + (size_t)(i % cap);
+  const int64_t es = h.ep_start[s];
+  const int64_t L = max((int64_t)h.ep_len[s], (int64_t)1), t = min(max(i - es, (int64_t)0), L - 1);
+  const bool relabel = u1 < p.her_ratio;
+  int64_t f = L - 1;   // HRG_HER_FINAL
+  if (p.strategy == HRG_HER_FUTURE) f = t + min((int64_t)floor(u2 * (double)(L - t)), L - t - 1);
+  else if (p.strategy == HRG_HER_EPISODE) f = min((int64_t)floor(u2 * (double)L), L - 1);
+  const float pre = h.pre[s * HRG_OBS_DIM + lane], post = h.post[s * HRG_OBS_DIM + lane];
+  const int kind = p.goal_kind, na = her_ag_dim(kind), ng = her_dg_dim(kind);
+  // the goal of lane d < ng: the stored desired goal, or what the transition `f` of the episode reached
+  float goal = __shfl(pre, her_dg_col(kind, lane < ng ? lane : 0));
+  float rew = h.reward[s];
+  bool dn = h.done[s] != 0 && h.trunc[s] == 0;   // custom_add 52-58: a timeout is no termination
+  if (relabel) {
+    const float grow = h.post[(ring + (size_t)((es + f) % cap)) * HRG_OBS_DIM + lane];
+    goal = __shfl(grow, her_new_goal_col(kind, lane < ng ? lane : 0));
+    double a[7], g[6];
+#pragma unroll
+    for (int d = 0; d < 7; d++) a[d] = d < na ? (double)__shfl(post, her_ag_col(kind, d)) : 0.0;
+#pragma unroll
+    for (int d = 0; d < 6; d++) g[d] = d < ng ? (double)__shfl(goal, d) : 0.0;
+    goal_reward_done(p, a, g, h.ctype[s], &rew, &dn);
+  }
+  // the policy's view of both rows
+  {   // value `lane` of the observation entry (n_obs_cols <= 64); every lane takes part in the shuffles
+    const int col = h.obs_cols[lane];   // (entries past n_obs_cols are zero)
+    float v0 = __shfl(pre, col), v1 = __shfl(post, col);
+    if (relabel && p.relabel_observation) {   // (wave-uniform)
+#pragma unroll
+      for (int d = 0; d < 6; d++) {
+        const float gd = __shfl(goal, d);
+        if (d < p.n_dg_in_obs && lane == p.dg_in_obs[d]) v0 = v1 = gd;
+      }
+    }
+    if (lane < p.n_obs_cols) {
+      o_obs[(size_t)k * p.n_obs_cols + lane] = v0;
+      o_nobs[(size_t)k * p.n_obs_cols + lane] = v1;
+    }
+  }
+  const float ag0 = __shfl(pre, her_ag_col(kind, lane < na ? lane : 0)), ag1 = __shfl(post, her_ag_col(kind, lane < na ? lane : 0));
+  if (lane < na) { o_ag[(size_t)k * na + lane] = ag0; o_nag[(size_t)k * na + lane] = ag1; }
+  if (lane < ng) { o_dg[(size_t)k * ng + lane] = goal; o_ndg[(size_t)k * ng + lane] = goal; }
+  if (lane < p.act_dim) o_act[(size_t)k * p.act_dim + lane] = h.act[s * (size_t)p.act_dim + lane];
+  if (lane == 0) {
+    o_rew[k] = rew;
+    o_done[k] = dn ? 1.0f : 0.0f;
+    if (o_idx) { o_idx[(size_t)k * HRG_HER_INDEX_DIM] = e; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 1] = i; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 2] = relabel ? es + f : -1; }
+  }
+}

@@ -3080,6 +3080,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #if HRG_BASE_TU
 #include "hrgym_expert.h"   // the scripted experts + imitation reward kernels (hrg_batch_expert_*, hrg_batch_step_imitation)
 #include "hrgym_dataset.h"  // demonstration datasets: restore + state imitation reward kernels (hrg_batch_dataset_*, hrg_batch_step_dataset)
+#include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -3699,6 +3700,188 @@ int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host) {
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(cursor_host, b->ds.cursor, sizeof(int32_t) * 3 * (size_t)b->n_envs, hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+// ---- hindsight experience replay (csrc/hrgym_her.h) ----
+struct hrg_her {
+  int device = 0;
+  hrg_her_desc desc;
+  HerDev d;
+  int64_t* d_total = nullptr;   // pinned host word the sampler's total is read back into
+  uint64_t calls = 0;           // sample calls so far (key of the draws)
+};
+
+static void her_free(hrg_her* h) {
+  HerDev& d = h->d;
+  hipFree(d.pre); hipFree(d.post); hipFree(d.act); hipFree(d.reward); hipFree(d.done); hipFree(d.trunc); hipFree(d.ctype); hipFree(d.ep_start); hipFree(d.ep_len);
+  hipFree(d.w); hipFree(d.tail); hipFree(d.open); hipFree(d.cur_obs); hipFree((void*)d.obs_cols);
+  if (h->d_total) hipHostFree(h->d_total);
+  delete h;
+}
+
+static int her_desc_check(const hrg_her_desc* p, bool ring) {
+  if (p->goal_kind != HRG_GOAL_REACH && p->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal kind");
+  if (!ring) return HRG_OK;
+  if (p->strategy != HRG_HER_FUTURE && p->strategy != HRG_HER_FINAL && p->strategy != HRG_HER_EPISODE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal selection strategy");
+  if (p->n_envs < 1 || p->horizon < 1) return fail(HRG_ERR_INVALID, "her: n_envs and horizon must be positive");
+  if (p->capacity <= p->horizon) return fail(HRG_ERR_INVALID, "her: capacity must exceed the horizon (a whole episode and one more transition have to fit the ring)");
+  if (p->act_dim < 1 || p->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "her: act_dim must lie in [1, HRG_ACT_DIM]");
+  if (p->n_obs_cols < 1 || p->n_obs_cols > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: n_obs_cols must lie in [1, HRG_OBS_DIM]");
+  for (int c = 0; c < p->n_obs_cols; c++)
+    if (p->obs_cols[c] < 0 || p->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: an observation column outside the superset");
+  const int ng = p->goal_kind == HRG_GOAL_REACH ? 6 : 3;
+  if (p->n_dg_in_obs != 0 && p->n_dg_in_obs != ng) return fail(HRG_ERR_INVALID, "her: n_dg_in_obs must be 0 or the goal's length");
+  for (int d = 0; d < p->n_dg_in_obs; d++)
+    if (p->dg_in_obs[d] < 0 || p->dg_in_obs[d] >= p->n_obs_cols) return fail(HRG_ERR_INVALID, "her: dg_in_obs outside the observation");
+  if (!(p->her_ratio >= 0 && p->her_ratio <= 1)) return fail(HRG_ERR_INVALID, "her: her_ratio must lie in [0, 1]");
+  if (p->rescale_actions)
+    for (int k = 0; k < p->act_dim; k++)
+      if (!(p->act_high[k] > p->act_low[k])) return fail(HRG_ERR_INVALID, "her: rescale_actions needs act_high > act_low");
+  return HRG_OK;
+}
+
+int hrg_her_create(const hrg_her_desc* desc, int32_t device, hrg_her** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  const int rc = her_desc_check(desc, true);
+  if (rc != HRG_OK) return rc;
+  HIPCHK(hipSetDevice(device));
+  hrg_her* h = new hrg_her();
+  h->device = device;
+  h->desc = *desc;
+  HerDev& d = h->d;
+  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity, row = sizeof(float) * HRG_OBS_DIM;
+  int32_t cols[HRG_OBS_DIM] = {0};
+  for (int c = 0; c < desc->n_obs_cols; c++) cols[c] = desc->obs_cols[c];
+#define HER_ALLOC(ptr, bytes)                                                                                                  \
+  do {                                                                                                                         \
+    const size_t _b = (bytes);                                                                                                 \
+    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
+      her_free(h);                                                                                                             \
+      return fail(HRG_ERR_NOMEM, "her: device allocation failed");                                                             \
+    }                                                                                                                          \
+  } while (0)
+  HER_ALLOC(d.pre, slots * row);
+  HER_ALLOC(d.post, slots * row);
+  HER_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
+  HER_ALLOC(d.reward, slots * sizeof(float));
+  HER_ALLOC(d.done, slots);
+  HER_ALLOC(d.trunc, slots);
+  HER_ALLOC(d.ctype, slots * sizeof(int32_t));
+  HER_ALLOC(d.ep_start, slots * sizeof(int64_t));
+  HER_ALLOC(d.ep_len, slots * sizeof(int32_t));
+  HER_ALLOC(d.w, n * sizeof(int64_t));
+  HER_ALLOC(d.tail, n * sizeof(int64_t));
+  HER_ALLOC(d.open, n * sizeof(int64_t));
+  HER_ALLOC(d.cur_obs, n * row);
+  HER_ALLOC(d.obs_cols, sizeof cols);
+#undef HER_ALLOC
+  if (hipHostMalloc((void**)&h->d_total, sizeof(int64_t)) != hipSuccess || hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess) {
+    her_free(h);
+    return fail(HRG_ERR_HIP, "her: upload failed");
+  }
+  *out = h;
+  return HRG_OK;
+}
+
+void hrg_her_destroy(hrg_her* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();
+  her_free(h);
+}
+
+int hrg_her_observe(hrg_her* h, const float* obs_dev, const uint8_t* mask_dev, int64_t* counts_dev, void* stream) {
+  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_her_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, obs_dev, mask_dev, counts_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_her_add(hrg_her* h, const double* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                const int32_t* info_dev, int64_t* counts_dev, void* stream) {
+  if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_her_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev,
+                     info_dev, counts_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* observation_dev, float* achieved_goal_dev, float* desired_goal_dev,
+                   float* next_observation_dev, float* next_achieved_goal_dev, float* next_desired_goal_dev, float* action_dev, float* reward_dev,
+                   float* done_dev, int64_t* index_dev, void* stream) {
+  if (!h || !counts_cum_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (batch_size < 1) return fail(HRG_ERR_INVALID, "her: batch_size must be positive");
+  if (!observation_dev || !achieved_goal_dev || !desired_goal_dev || !next_observation_dev || !next_achieved_goal_dev || !next_desired_goal_dev || !action_dev ||
+      !reward_dev || !done_dev)
+    return fail(HRG_ERR_INVALID, "her: null output");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemcpyAsync(h->d_total, counts_cum_dev + h->desc.n_envs, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  if (*h->d_total < 1) return fail(HRG_ERR_INVALID, "her: no finished episode in the buffer yet (nothing to sample)");
+  const unsigned per = HRG_HER_BLOCK / 64;
+  hipLaunchKernelGGL(hrg_her_sample_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_HER_BLOCK), 0, (hipStream_t)stream, h->desc, h->d, counts_cum_dev, h->calls,
+                     (int)batch_size, observation_dev, achieved_goal_dev, desired_goal_dev, next_observation_dev, next_achieved_goal_dev, next_desired_goal_dev, action_dev,
+                     reward_dev, done_dev, index_dev);
+  HIPCHK(hipGetLastError());
+  h->calls++;
+  return HRG_OK;
+}
+
+int hrg_her_counts(hrg_her* h, int64_t* counts_host) {
+  if (!h || !counts_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t n = (size_t)h->desc.n_envs;
+  std::vector<int64_t> w(n), tail(n), open(n);
+  HIPCHK(hipMemcpy(w.data(), h->d.w, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(tail.data(), h->d.tail, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(open.data(), h->d.open, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
+  counts_host[0] = counts_host[1] = 0;
+  for (size_t e = 0; e < n; e++) { counts_host[0] += w[e] - tail[e]; counts_host[1] += open[e] - tail[e]; }
+  counts_host[2] = (int64_t)h->calls;
+  return HRG_OK;
+}
+
+int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, float* action_host, float* reward_host, uint8_t* done_host,
+                   uint8_t* truncated_host, int32_t* ctype_host, int64_t* ep_start_host, int32_t* ep_len_host, int64_t* state_host, float* cur_obs_host) {
+  if (!h || !pre_host || !post_host || !action_host || !reward_host || !done_host || !truncated_host || !ctype_host || !ep_start_host || !ep_len_host || !state_host ||
+      !cur_obs_host)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (env < 0 || env >= h->desc.n_envs) return fail(HRG_ERR_INVALID, "bad env index");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const HerDev& d = h->d;
+  const size_t cap = (size_t)h->desc.capacity, r0 = (size_t)env * cap, row = sizeof(float) * HRG_OBS_DIM, ad = (size_t)h->desc.act_dim;
+  HIPCHK(hipMemcpy(pre_host, d.pre + r0 * HRG_OBS_DIM, cap * row, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(post_host, d.post + r0 * HRG_OBS_DIM, cap * row, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(action_host, d.act + r0 * ad, cap * ad * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(reward_host, d.reward + r0, cap * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(done_host, d.done + r0, cap, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(truncated_host, d.trunc + r0, cap, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ctype_host, d.ctype + r0, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ep_start_host, d.ep_start + r0, cap * sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ep_len_host, d.ep_len + r0, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(state_host + 0, d.w + env, sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(state_host + 1, d.tail + env, sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(state_host + 2, d.open + env, sizeof(int64_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs + (size_t)env * HRG_OBS_DIM, row, hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const float* dg_dev, const int32_t* ctype_dev, int32_t n, float* reward_dev,
+                         uint8_t* done_dev, void* stream) {
+  if (!desc || !ag_dev || !dg_dev || !ctype_dev || !reward_dev || !done_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (n < 1) return fail(HRG_ERR_INVALID, "her: n must be positive");
+  const int rc = her_desc_check(desc, false);
+  if (rc != HRG_OK) return rc;
+  hipLaunchKernelGGL(hrg_goal_reward_done_kernel, dim3(((unsigned)n + HRG_HER_BLOCK - 1) / HRG_HER_BLOCK), dim3(HRG_HER_BLOCK), 0, (hipStream_t)stream, *desc, ag_dev, dg_dev,
+                     ctype_dev, (int)n, reward_dev, done_dev);
+  HIPCHK(hipGetLastError());
   return HRG_OK;
 }
 

@@ -1,0 +1,189 @@
+"""Hindsight experience replay on the device: the replay buffer of SAC + HER (training/config/algorithm/sac_her.yaml) for a batch of goal envs.
+
+The reference trains with SB3's `HerReplayBuffer`, patched by wrappers/HER_buffer_add_monkey_patch.py, and refuses more than one env
+(utils/training_utils_SB3.py:154).  Here every env of a `HipVecEnv(goal_env=True)` has a ring of transitions in device memory; the step's rows go into
+it without leaving the device, and `sample()` returns device tensors (csrc/hrgym_her.h: kernels, ring rules and the sampling rule).
+
+    env = HipVecEnv(4096, goal_env=True)
+    env.attach_her(buffer_size=256)            # transitions per env
+    ...                                        # reset() / step() fill env.her
+    batch = env.her.sample(256)                # DictReplayBufferSamples of device tensors
+"""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+
+from ._cstruct import CONST, HerDesc
+
+# the fields SB3's SAC reads (stable_baselines3.common.type_aliases.DictReplayBufferSamples); observations / next_observations are dicts
+DictReplayBufferSamples = namedtuple("DictReplayBufferSamples", ["observations", "actions", "next_observations", "dones", "rewards"])
+
+STRATEGIES = {"future": CONST["HRG_HER_FUTURE"], "final": CONST["HRG_HER_FINAL"], "episode": CONST["HRG_HER_EPISODE"]}
+GOAL_KINDS = {"reach": CONST["HRG_GOAL_REACH"], "cube": CONST["HRG_GOAL_CUBE"]}
+AG_DIM = {CONST["HRG_GOAL_REACH"]: 6, CONST["HRG_GOAL_CUBE"]: 7}
+DG_DIM = {CONST["HRG_GOAL_REACH"]: 6, CONST["HRG_GOAL_CUBE"]: 3}
+
+
+def her_ratio(n_sampled_goal):
+    """Share of the samples that are relabelled (HerReplayBuffer.__init__)."""
+    return 1.0 - 1.0 / (1.0 + int(n_sampled_goal))
+
+
+def build_her_desc(n_envs, capacity, horizon, goal_kind, obs_cols, act_dim=CONST["HRG_ACT_DIM"], model_desc=None, n_sampled_goal=4, goal_selection_strategy="future",
+                   ratio=None, seed=0, act_low=None, act_high=None, dg_in_obs=(), relabel_observation=False, **reward):
+    """hrg_her_desc (include/hrgym.h).  The reward / done parameters come from `model_desc` (an hrg_model_desc), overridden by keywords (goal_dist,
+    task_reward, object_gripped_reward, reward_shaping, collision_reward, reward_scale, done_at_success, done_at_collision).  `act_low` / `act_high`:
+    the action bounds, given when the stored actions are to be rescaled to [-1, 1].  `ratio`: her_ratio itself, instead of n_sampled_goal."""
+    if goal_selection_strategy not in STRATEGIES:
+        raise ValueError(f"goal_selection_strategy {goal_selection_strategy!r}: one of {sorted(STRATEGIES)}")
+    d = HerDesc()
+    d.n_envs, d.capacity, d.horizon = int(n_envs), int(capacity), int(horizon)
+    d.goal_kind = GOAL_KINDS[goal_kind] if isinstance(goal_kind, str) else int(goal_kind)
+    d.strategy = STRATEGIES[goal_selection_strategy]
+    d.her_ratio = her_ratio(n_sampled_goal) if ratio is None else float(ratio)
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    fields = ("goal_dist", "task_reward", "object_gripped_reward", "reward_shaping", "collision_reward", "reward_scale", "done_at_success", "done_at_collision")
+    unknown = sorted(set(reward) - set(fields))
+    if unknown:
+        raise TypeError(f"build_her_desc: unexpected arguments {unknown}")
+    for k in fields:
+        if k in reward:
+            setattr(d, k, type(getattr(d, k))(reward[k]))
+        elif model_desc is not None:
+            setattr(d, k, getattr(model_desc, k))
+    d.act_dim = int(act_dim)
+    d.rescale_actions = int(act_low is not None)
+    if act_low is not None:
+        for k in range(d.act_dim):
+            d.act_low[k], d.act_high[k] = float(act_low[k]), float(act_high[k])
+    cols = [int(c) for c in obs_cols]
+    if not 1 <= len(cols) <= CONST["HRG_OBS_DIM"]:
+        raise NotImplementedError(f"her: an observation of {len(cols)} values (the sample kernel writes one value per lane: 1 .. {CONST['HRG_OBS_DIM']})")
+    d.n_obs_cols = len(cols)
+    for k, c in enumerate(cols):
+        d.obs_cols[k] = c
+    d.relabel_observation = int(bool(relabel_observation))
+    d.n_dg_in_obs = len(dg_in_obs)
+    for k, c in enumerate(dg_in_obs):
+        d.dg_in_obs[k] = int(c)
+    return d
+
+
+class HerBuffer:
+    """A device-resident hindsight replay buffer of `desc.n_envs` rings (hrg_her_desc; `build_her_desc`).  All arguments and results are torch tensors on
+    the buffer's device; the calls are asynchronous, ordered on torch's current stream (`sample` waits for the prefix sum's total)."""
+
+    def __init__(self, desc, device=0):
+        import torch
+        from ._lib import _check, load_library
+        if not torch.cuda.is_available():
+            raise RuntimeError("HerBuffer needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.torch, self.lib, self._check = torch, load_library(), _check
+        self.desc = desc
+        self.device = torch.device("cuda", device)
+        self.n, self.capacity, self.act_dim, self.obs_dim = int(desc.n_envs), int(desc.capacity), int(desc.act_dim), int(desc.n_obs_cols)
+        self.ag_dim, self.dg_dim = AG_DIM.get(desc.goal_kind, 0), DG_DIM.get(desc.goal_kind, 0)
+        self.h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_her_create(ctypes.byref(desc), device, ctypes.byref(self.h)))
+            self.counts = torch.zeros(self.n, dtype=torch.int64, device=self.device)   # closed transitions per env, written by the add / observe kernels
+        self.record_index = False   # tests: keep the (env, counter, goal counter) rows of the last sample() in `last_index`
+        self.last_index = None
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _tensor(self, x, dtype, shape, what):
+        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        return ctypes.c_void_p(x.data_ptr())
+
+    def observe(self, obs, mask=None):
+        """The rows an episode starts from, after a reset: `obs` float32 [n, 64]; `mask` uint8 [n] (None: every env).  The unfinished episode of a masked
+        env is discarded."""
+        t = self.torch
+        o = self._tensor(obs, t.float32, (self.n, CONST["HRG_OBS_DIM"]), "obs")
+        m = None if mask is None else self._tensor(mask, t.uint8, (self.n,), "mask")
+        with t.cuda.device(self.device):
+            self._check(self.lib, self.lib.hrg_her_observe(self.h, o, m, ctypes.c_void_p(self.counts.data_ptr()), self._stream()))
+
+    def add_step(self, actions, obs, term_obs, reward, done, info):
+        """One transition per env, from the tensors a step wrote: `actions` float64 [n, 7] as the step left them, `obs` / `term_obs` float32 [n, 64], `reward`
+        float32 [n], `done` uint8 [n], `info` int32 [n, HRG_INFO_DIM]."""
+        t, C = self.torch, CONST
+        args = (self._tensor(actions, t.float64, (self.n, C["HRG_ACT_DIM"]), "actions"), self._tensor(obs, t.float32, (self.n, C["HRG_OBS_DIM"]), "obs"),
+                self._tensor(term_obs, t.float32, (self.n, C["HRG_OBS_DIM"]), "term_obs"), self._tensor(reward, t.float32, (self.n,), "reward"),
+                self._tensor(done, t.uint8, (self.n,), "done"), self._tensor(info, t.int32, (self.n, C["HRG_INFO_DIM"]), "info"))
+        with t.cuda.device(self.device):
+            self._check(self.lib, self.lib.hrg_her_add(self.h, *args, ctypes.c_void_p(self.counts.data_ptr()), self._stream()))
+
+    def add(self, *args, **kwargs):
+        """Nothing: the transition went into the buffer on the device when the env stepped.  Lets the object stand where an off-policy loop expects a
+        replay buffer."""
+
+    def sample(self, batch_size, env=None):
+        """`batch_size` transitions, uniform over the finished episodes' transitions of all envs, a share `her_ratio` of them relabelled.  `env` (SB3 passes
+        its VecNormalize) is not used."""
+        t = self.torch
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError("sample: batch_size must be positive")
+        with t.cuda.device(self.device):
+            cum = t.zeros(self.n + 1, dtype=t.int64, device=self.device)
+            t.cumsum(self.counts, 0, out=cum[1:])
+            new = lambda w: t.empty(B, w, dtype=t.float32, device=self.device)   # noqa: E731
+            obs, ag, dg, nobs, nag, ndg = new(self.obs_dim), new(self.ag_dim), new(self.dg_dim), new(self.obs_dim), new(self.ag_dim), new(self.dg_dim)
+            act, rew, done = new(self.act_dim), new(1), new(1)
+            idx = t.empty(B, CONST["HRG_HER_INDEX_DIM"], dtype=t.int64, device=self.device) if self.record_index else None
+            p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())   # noqa: E731
+            self._check(self.lib, self.lib.hrg_her_sample(self.h, B, p(cum), p(obs), p(ag), p(dg), p(nobs), p(nag), p(ndg), p(act), p(rew), p(done), p(idx), self._stream()))
+        self.last_index = idx
+        return DictReplayBufferSamples(observations=dict(observation=obs, achieved_goal=ag, desired_goal=dg), actions=act,
+                                       next_observations=dict(observation=nobs, achieved_goal=nag, desired_goal=ndg), dones=done, rewards=rew)
+
+    def compute_reward_done(self, achieved_goal, desired_goal, collision_type):
+        """HipVecEnv.compute_reward / compute_done of device rows (hrg_goal_reward_done): float32 [n, ag_dim], float32 [n, dg_dim], int32 [n] ->
+        (reward float32 [n], done bool [n])."""
+        t = self.torch
+        n = int(achieved_goal.shape[0])
+        args = (self._tensor(achieved_goal, t.float32, (n, self.ag_dim), "achieved_goal"), self._tensor(desired_goal, t.float32, (n, self.dg_dim), "desired_goal"),
+                self._tensor(collision_type, t.int32, (n,), "collision_type"))
+        reward, done = t.empty(n, dtype=t.float32, device=self.device), t.empty(n, dtype=t.uint8, device=self.device)
+        with t.cuda.device(self.device):   # (the entry point launches on the current device)
+            self._check(self.lib, self.lib.hrg_goal_reward_done(ctypes.byref(self.desc), *args, n, ctypes.c_void_p(reward.data_ptr()), ctypes.c_void_p(done.data_ptr()),
+                                                                self._stream()))
+        return reward, done.bool()
+
+    def counts_host(self):
+        """(transitions stored, transitions of finished episodes, sample calls so far); synchronous."""
+        c = (ctypes.c_int64 * 3)()
+        self._check(self.lib, self.lib.hrg_her_counts(self.h, c))
+        return tuple(int(x) for x in c)
+
+    def size(self):
+        """Transitions that can be sampled (synchronous)."""
+        return self.counts_host()[1]
+
+    def export(self, env):
+        """Env's whole ring on the host (synchronous; tests): dict of pre, post [cap, 64], action [cap, act_dim], reward, done, truncated, collision_type,
+        ep_start, ep_len [cap], w, tail, open, cur_obs [64]."""
+        cap, od = self.capacity, CONST["HRG_OBS_DIM"]
+        out = dict(pre=np.zeros((cap, od), np.float32), post=np.zeros((cap, od), np.float32), action=np.zeros((cap, self.act_dim), np.float32),
+                   reward=np.zeros(cap, np.float32), done=np.zeros(cap, np.uint8), truncated=np.zeros(cap, np.uint8), collision_type=np.zeros(cap, np.int32),
+                   ep_start=np.zeros(cap, np.int64), ep_len=np.zeros(cap, np.int32), state=np.zeros(3, np.int64), cur_obs=np.zeros(od, np.float32))
+        self._check(self.lib, self.lib.hrg_her_export(self.h, int(env), *(a.ctypes.data_as(ctypes.c_void_p) for a in out.values())))
+        st = out.pop("state")
+        out.update(w=int(st[0]), tail=int(st[1]), open=int(st[2]))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.hrg_her_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -214,6 +214,12 @@ def _mixed_cls():
         def compute_reward(self, *a, **k):
             raise NotImplementedError("goal-env relabelling is per task; use one HipVecEnv(goal_env=True) per task")
 
+        def compute_done(self, *a, **k):
+            raise NotImplementedError("goal-env relabelling is per task; use one HipVecEnv(goal_env=True) per task")
+
+        def attach_her(self, *a, **k):
+            raise NotImplementedError("goal-env relabelling is per task; use one HipVecEnv(goal_env=True) per task")
+
         def expert_actions(self):
             raise NotImplementedError("scripted experts are per task and action form; use one HipVecEnv(expert=...) per task")
 

@@ -158,6 +158,28 @@ def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
     return out
 
 
+def her_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
+    """`config.algorithm.replay_buffer_kwargs` of a goal-env run (training/config/algorithm/sac_her.yaml: n_sampled_goal, goal_selection_strategy,
+    online_sampling) -> the keyword arguments of HipVecEnv.attach_her, or None when the run has no such node.  `buffer_size` is per env there: the
+    algorithm's buffer_size (transitions in all) divided over run.n_envs, but never less than two episodes."""
+    run, alg = _get(config, "run"), _get(config, "algorithm")
+    node = _get(alg, "replay_buffer_kwargs")
+    if node is None or _get(run, "env_type", "env") != "goal_env":
+        return None
+    kw = dict(_plain(node))
+    unknown = sorted(set(kw) - {"n_sampled_goal", "goal_selection_strategy", "online_sampling", "max_episode_length", "handle_timeout_termination"})
+    if unknown:
+        raise NotImplementedError(f"algorithm.replay_buffer_kwargs {unknown}: the device buffer takes n_sampled_goal, goal_selection_strategy, online_sampling")
+    if kw.pop("handle_timeout_termination", True) is not True:
+        raise NotImplementedError("algorithm.replay_buffer_kwargs.handle_timeout_termination = false: the device buffer never stores a timeout as a termination")
+    kw.pop("max_episode_length", None)   # the horizon of the env
+    horizon = int(_get(_get(config, "environment"), "horizon", 0) or 0)
+    n_envs = int(_get(run, "n_envs", 1))
+    total = int(_get(alg, "buffer_size", 1_000_000))
+    kw["buffer_size"] = max(total // n_envs, 2 * horizon + 2)
+    return kw
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""
@@ -166,7 +188,8 @@ def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class
     vec_kw = dict(_plain(_get(run, "vec_env_kwargs")) or {})
     vec_kw.update(wrapper_kwargs_from_config(config))
     vec_kw["_wrappers_from_config"] = True   # tells make_vec_env that `wrapper_class` (if any) has been translated above
-    return make_vec_env(
+    her = her_kwargs_from_config(config)
+    env = make_vec_env(
         env_id=_get(_get(config, "environment"), "env_id"),
         type=_get(run, "env_type", "env"),
         obs_keys=_plain(_get(run, "obs_keys")),
@@ -182,3 +205,8 @@ def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class
         monitor_kwargs=_plain(_get(run, "monitor_kwargs")),
         wrapper_kwargs=None,
     )
+    if her is not None:   # SAC + HER: the replay buffer lives beside the stepper (env.her)
+        if her["buffer_size"] <= env.horizon:
+            her["buffer_size"] = 2 * env.horizon + 2
+        env.attach_her(**her)
+    return env

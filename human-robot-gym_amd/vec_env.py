@@ -239,6 +239,8 @@ class _TorchBackend:
         self.obs, self.term_obs, self.reward, self.info, self.done = v["obs"], v["term_obs"], v["reward"], v["info"], v["done"]
         self.imit = None   # host copy of the imitation rows, once an expert with a reward is attached
         self.sir = None    # host copy of the state imitation rows, once a dataset is attached
+        self.her = None    # the hindsight replay buffer (her.HerBuffer), once attached: filled on the device behind every reset / step
+        self._her_agent = False
 
     def _fetch(self):
         if self.sir is not None:
@@ -261,6 +263,14 @@ class _TorchBackend:
     def expert_actions(self):
         return self.batch.expert_actions().cpu().numpy()
 
+    def attach_her(self, desc, keep_agent_actions=False):
+        """`keep_agent_actions`: the buffer stores the rows the agent sent (copied before the step rewrites them), not the rows the step left."""
+        from .her import HerBuffer
+        if self.her is not None:
+            self.her.close()
+        self.her = HerBuffer(desc, device=self.batch.device.index)
+        self._her_agent = bool(keep_agent_actions)
+
     def reset(self):
         if self.sir is not None:
             self.batch.dataset_reset()
@@ -268,11 +278,14 @@ class _TorchBackend:
             self.reset_time = (cur[:, 1] / cur[:, 2]).astype(np.float32)   # StateBasedExpertImitationRewardWrapper.reset (107): start step / T
         else:
             self.batch.reset()
+        if self.her is not None:
+            self.her.observe(self.batch.obs)
         self._fetch()
         return self.obs
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
+        self._her_act = self._act.clone() if self.her is not None and self._her_agent else self._act
         if self.sir is not None:   # (runs the expert's kernels too when an imitation reward is attached)
             self.batch.step_dataset(self._act)
         elif self.imit is not None:
@@ -281,6 +294,9 @@ class _TorchBackend:
             self.batch.step(self._act)
 
     def step_wait(self):
+        if self.her is not None:   # on the step's stream, ahead of the host copy: the transition never leaves the device
+            b = self.batch
+            self.her.add_step(self._her_act, b.obs, b.term_obs, b.reward, b.done, b.info)
         self._fetch()
         return self.obs, self.term_obs, self.reward, self.done, self.info
 
@@ -289,6 +305,8 @@ class _TorchBackend:
         return self._act.cpu().numpy()
 
     def close(self):
+        if self.her is not None:
+            self.her.close()
         self.batch.close()
 
 
@@ -436,6 +454,8 @@ class HipVecEnv(_VecEnvBase):
             backend.attach_expert(self._expert_desc)
         if self._dataset is not None:
             backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
+        if getattr(self, "_her_args", None) is not None:   # after seed(): a new, empty buffer
+            backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None)
         return backend
 
     def _init_spaces(self, n_envs, collision_prevention=None, ik_position_delta=None):
@@ -754,6 +774,76 @@ class HipVecEnv(_VecEnvBase):
         r = (r + np.where(illegal, d.collision_reward, 0.0)) * d.reward_scale
         return float(r[0]) if isinstance(info, dict) and np.ndim(achieved_goal) == 1 else r.astype(np.float32)
 
+    def compute_done(self, achieved_goal, desired_goal, info):
+        """HumanEnv._check_done (human_env.py:835-858), vectorised, in the calling forms of `compute_reward`: (done_at_collision and an illegal collision in
+        info["collision_type"]) or (done_at_success and success); success is ||achieved - desired|| <= goal_dist (reach_human_env.py:457-475), for the
+        cube tasks ||desired - object_pos|| <= goal_dist (pick_place_human_cartesian_env.py:528-548).  What the patched HerReplayBuffer asks for every
+        relabelled transition (wrappers/HER_buffer_add_monkey_patch.py:234-246)."""
+        if not self.goal_env:
+            raise NotImplementedError("compute_done: construct with goal_env=True / make_vec_env(type='goal_env')")
+        d = self._desc
+        ag, dg = np.atleast_2d(np.asarray(achieved_goal, np.float64)), np.atleast_2d(np.asarray(desired_goal, np.float64))
+        infos = [info] if isinstance(info, dict) else list(info)
+        ctype = np.array([int(i.get("collision_type", 0)) for i in infos])
+        dist = np.linalg.norm(ag - dg, axis=-1) if self.env_id == "ReachHuman" else np.linalg.norm(dg - ag[:, 3:6], axis=-1)
+        illegal = (ctype & (CONST["HRG_COL_STATIC"] | CONST["HRG_COL_ROBOT"] | CONST["HRG_COL_HUMAN_CRIT"])) != 0
+        done = (bool(d.done_at_collision) & illegal) | (bool(d.done_at_success) & (dist <= d.goal_dist))
+        return bool(done[0]) if isinstance(info, dict) and np.ndim(achieved_goal) == 1 else done
+
+    def _her_desc(self, n_envs, buffer_size, n_sampled_goal, goal_selection_strategy, relabel_observation, seed):
+        """hrg_her_desc of this env: the ring, the sampler, the reward / done rule of `compute_reward` / `compute_done`, the policy's view of a row."""
+        from .her import build_her_desc
+        cols = [int(c) for c in self._cols]
+        dg_in_obs = ()
+        if relabel_observation:   # where the `desired_goal` key sits inside `observation`
+            keys, at, k0 = self.obs_keys or [], [], 0
+            cols_of = task_columns(self.env_id)
+            for key in keys:
+                if key == "desired_goal":
+                    at.append(k0)
+                k0 += len(cols_of[key])
+            if len(at) != 1:
+                raise NotImplementedError("attach_her(relabel_observation=True): obs_keys must list desired_goal exactly once")
+            dg_in_obs = range(at[0], at[0] + len(self._dg_cols))
+        # custom_add (64-79) stores info["action"] where a wrapper wrote one (CollisionPreventionWrapper, collision_prevention_wrapper.py:43), rescaled to
+        # [-1, 1] by the action bounds and clipped; otherwise SB3's buffer_action, which is the policy's action in [-1, 1] already.  IKPositionDeltaWrapper
+        # writes none, so behind the IK front-end the buffer keeps the agent's own [dx, dy, dz, gripper] (copied before the step rewrites the row), and
+        # since the env receives it at env scale (+-ik_action_limit), the same rescaling brings it back to the policy's scale
+        front_end = self._cp is not None or self._ik is not None
+        low, high = self.action_space.low, self.action_space.high
+        return build_her_desc(n_envs, buffer_size, self.horizon, "reach" if self.env_id == "ReachHuman" else "cube", cols, act_dim=len(low), model_desc=self._desc,
+                              n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=int(self._desc.seed) if seed is None else seed,
+                              act_low=low if front_end else None, act_high=high if front_end else None, dg_in_obs=dg_in_obs, relabel_observation=relabel_observation)
+
+    def attach_her(self, buffer_size, n_sampled_goal=4, goal_selection_strategy="future", online_sampling=True, relabel_observation=False, seed=None):
+        """A hindsight replay buffer on the device (her.HerBuffer; the keywords of SB3's HerReplayBuffer, training/config/algorithm/sac_her.yaml):
+        `buffer_size` transitions PER ENV.  From now on reset() and every step put their rows into it without leaving the device; `env.her.sample(n)`
+        returns device tensors.  Attaching again replaces the buffer with an empty one.  Returns the buffer."""
+        if not self.goal_env:
+            raise NotImplementedError("attach_her: construct with goal_env=True / make_vec_env(type='goal_env')")
+        if not online_sampling:
+            raise NotImplementedError("attach_her(online_sampling=False): offline sampling copies relabelled transitions into a second buffer; the device buffer "
+                                      "relabels when it samples")
+        if int(buffer_size) <= self.horizon:
+            raise ValueError(f"attach_her: buffer_size = {buffer_size} transitions per env cannot hold an episode of horizon {self.horizon} and one more transition")
+        if self._cp is not None and self._ik is not None:
+            raise NotImplementedError("attach_her: with collision prevention behind the IK front-end the executed action is a joint action, not one of the policy's "
+                                      "Cartesian action space")
+        if not isinstance(self._backend, _TorchBackend):
+            raise NotImplementedError("attach_her: the add and sample kernels run in the HIP library; another backend has none")
+        args = dict(buffer_size=int(buffer_size), n_sampled_goal=int(n_sampled_goal), goal_selection_strategy=goal_selection_strategy,
+                    relabel_observation=bool(relabel_observation), seed=seed)
+        self._backend.attach_her(self._her_desc(self.num_envs, **args), keep_agent_actions=self._ik is not None)
+        self._her_args = args
+        if self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
+            self._backend.her.observe(self._backend.batch.obs)
+        return self._backend.her
+
+    @property
+    def her(self):
+        """The attached hindsight replay buffer (attach_her), or None."""
+        return getattr(self._backend, "her", None)
+
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
         if method_name == "check_collision_action":   # per-env call of the reference: env_method("check_collision_action", action, indices=[i])
             idx = self._indices(indices)
@@ -762,6 +852,8 @@ class HipVecEnv(_VecEnvBase):
             return [bool(x) for x in self.check_collision_action(acts)[idx]]
         if method_name == "compute_reward":   # SB3 HerReplayBuffer: env_method("compute_reward", achieved, desired, infos, indices=[0])
             return [self.compute_reward(*method_args, **method_kwargs) for _ in self._indices(indices)]
+        if method_name == "compute_done":     # the reference's patched buffer: env_method("compute_done", next_achieved, desired, infos)
+            return [self.compute_done(*method_args, **method_kwargs) for _ in self._indices(indices)]
         raise NotImplementedError(f"env_method({method_name!r}) is not available on the batched stepper")
 
     def env_is_wrapped(self, wrapper_class, indices=None):

@@ -444,7 +444,43 @@ typedef struct hrg_dataset_desc {
   int32_t m_sim_fn, g_sim_fn;     /* HRG_SIM_*; `sim_fn` of the Reach / Lifting wrappers is m_sim_fn */
 } hrg_dataset_desc;
 
+/* ------------------------------------------------------------------------- hindsight experience replay on the device (POD) */
+/* which columns of the observation superset are the goals (GoalEnvironmentGymWrapper, wrappers/goal_env_wrapper.py):
+ * HRG_GOAL_REACH  achieved = robot0_joint_pos [18:24], desired = desired_goal [33:39], a relabelled goal = the joint positions reached
+ *                 (reach_human_env.py:477-507)
+ * HRG_GOAL_CUBE   achieved = [eef_pos 30:33, object_pos 47:50, object_gripped 39], desired = target_pos [50:53], a relabelled goal = the object
+ *                 position reached [47:50] (pick_place_human_cartesian_env.py:574-611) */
+enum { HRG_GOAL_REACH = 0, HRG_GOAL_CUBE = 1 };
+/* GoalSelectionStrategy of SB3's HerReplayBuffer */
+enum { HRG_HER_FUTURE = 0, HRG_HER_FINAL = 1, HRG_HER_EPISODE = 2 };
+#define HRG_HER_INDEX_DIM 3 /* int64 per sample of the optional index output of hrg_her_sample: env, write counter of the transition, write counter of the
+                             * transition the new goal was taken from (-1: not relabelled) */
+
+/* One replay buffer: the ring's shape, the sampler, the reward / done rule of relabelled transitions (copied from hrg_model_desc), the action
+ * rescaling of the patched HerReplayBuffer.add (wrappers/HER_buffer_add_monkey_patch.py:64-79) and the policy's view of an observation row. */
+typedef struct hrg_her_desc {
+  int32_t n_envs;
+  int32_t capacity;               /* transitions per env; must exceed horizon */
+  int32_t horizon;                /* longest episode (TimeLimit) */
+  int32_t goal_kind;              /* HRG_GOAL_* */
+  int32_t strategy;               /* HRG_HER_* */
+  int32_t reward_shaping, done_at_success, done_at_collision;
+  double her_ratio;               /* 1 - 1 / (1 + n_sampled_goal): share of the samples that are relabelled */
+  uint64_t seed;                  /* keys the sampler's draws (with the sample call counter and the sample's index in its batch) */
+  double goal_dist, task_reward, object_gripped_reward, collision_reward, reward_scale;
+  int32_t act_dim;                /* action values the policy sees: 7 joint space, 4 with the Cartesian front-end */
+  int32_t rescale_actions;        /* 1: stored actions are 2 (a - low) / (high - low) - 1, clipped to [-1, 1] */
+  double act_low[HRG_ACT_DIM], act_high[HRG_ACT_DIM];
+  int32_t n_obs_cols;             /* length of the policy's `observation` entry, at most HRG_OBS_DIM */
+  int32_t relabel_observation;    /* 0: a relabelled sample changes its desired_goal entry only (the reference); 1: also the copy of the goal inside
+                                   * observation / next_observation */
+  int32_t obs_cols[HRG_OBS_DIM];  /* column of the superset behind each value of `observation` */
+  int32_t n_dg_in_obs;            /* 0, or the goal's length */
+  int32_t dg_in_obs[8];           /* where component j of the desired goal sits inside `observation` */
+} hrg_her_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
+typedef struct hrg_her hrg_her;     /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -576,6 +612,47 @@ int hrg_batch_dataset_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_de
 int hrg_batch_step_dataset(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev,
                            float* imit_dev, float* sir_dev, void* stream);
 int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host);
+
+/* Hindsight experience replay on the device (csrc/hrgym_her.h): the replay buffer of SAC + HER (training/config/algorithm/sac_her.yaml; SB3's
+ * HerReplayBuffer with wrappers/HER_buffer_add_monkey_patch.py) for a batch of goal envs.  Every env has a ring of `capacity` transitions in device
+ * memory; whole episodes leave it, oldest first.  The entry points take raw device pointers (the tensors a step wrote, or synthetic ones), no hrg_batch.
+ *   hrg_her_create     <- HerReplayBuffer.__init__: allocates and zeroes everything (synchronous; nothing is allocated later).  HRG_ERR_INVALID for
+ *                         capacity <= horizon, n_envs < 1, act_dim or n_obs_cols out of range, a column outside the superset; HRG_ERR_UNSUPPORTED for an
+ *                         unknown goal kind or strategy.
+ *   hrg_her_observe    <- the first observation of an episode after a reset (SB3's _last_obs): for envs whose mask byte is non-zero (NULL: all) the
+ *                         current row becomes obs_dev's and the transitions of the unfinished episode are discarded.
+ *   hrg_her_add        <- custom_add (26-117), after a step: one transition per env -- the row before the step, the row after it (term_obs_dev where
+ *                         done), the first act_dim values of the action row as the step left it (info["action"]; rescaled when rescale_actions), reward,
+ *                         done, TimeLimit.truncated and collision_type of the info block.  A done flag closes the env's episode.
+ *                         counts_dev (observe and add; may be NULL): int64 [n_envs], the closed transitions of every env after the call -- what
+ *                         hrg_her_sample's prefix sums are made from.
+ *   hrg_her_sample     <- _custom_sample_transitions (120-286), online sampling: batch_size transitions, uniform over the closed transitions of all envs;
+ *                         counts_cum_dev int64 [n_envs + 1] = exclusive prefix sums of the counts (last entry: their total).  Sample k of call c draws
+ *                         rng_u01(seed, c, k, stream 10, 0..2): transition, relabel (u1 < her_ratio), goal.  Outputs, float [batch_size][.]: observation
+ *                         n_obs_cols, achieved_goal 6 / 7, desired_goal 6 / 3 (reach / cube), the same three of the next observation (next_desired_goal =
+ *                         desired_goal), action act_dim, reward 1, done 1; index_dev int64 [batch_size][HRG_HER_INDEX_DIM] or NULL.  Relabelled samples:
+ *                         reward and done of hrg_goal_reward_done; the others: the stored reward, done without timeouts.  Advances the call counter.
+ *                         HRG_ERR_INVALID for batch_size < 1, null outputs, no closed transition (reads the total back: synchronises the stream).
+ *   hrg_her_counts     synchronous: counts_host int64[3] = transitions stored (closed or not), closed transitions, sample calls so far.
+ *   hrg_her_export     synchronous parity hook: env's whole ring -- pre / post float [capacity][HRG_OBS_DIM], action float [capacity][act_dim], reward
+ *                         float, done / truncated uint8, collision_type int32, ep_start int64, ep_len int32 [capacity] each, state int64[3] = write counter,
+ *                         tail, open, cur_obs float [HRG_OBS_DIM].
+ *   hrg_goal_reward_done  HumanEnv._compute_reward / _check_done (human_env.py:629-664, 835-858) of n caller-supplied rows on the current device: ag_dev
+ *                         float [n][6 / 7], dg_dev float [n][6 / 3], ctype_dev int32 [n] -> reward_dev float [n], done_dev uint8 [n].  Reads the goal kind and
+ *                         the reward / done parameters of desc. */
+int hrg_her_create(const hrg_her_desc* desc, int32_t device, hrg_her** out);
+void hrg_her_destroy(hrg_her* h);
+int hrg_her_observe(hrg_her* h, const float* obs_dev, const uint8_t* mask_dev, int64_t* counts_dev, void* stream);
+int hrg_her_add(hrg_her* h, const double* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                const int32_t* info_dev, int64_t* counts_dev, void* stream);
+int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* observation_dev, float* achieved_goal_dev, float* desired_goal_dev,
+                   float* next_observation_dev, float* next_achieved_goal_dev, float* next_desired_goal_dev, float* action_dev, float* reward_dev,
+                   float* done_dev, int64_t* index_dev, void* stream);
+int hrg_her_counts(hrg_her* h, int64_t* counts_host);
+int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, float* action_host, float* reward_host, uint8_t* done_host,
+                   uint8_t* truncated_host, int32_t* ctype_host, int64_t* ep_start_host, int32_t* ep_len_host, int64_t* state_host, float* cur_obs_host);
+int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const float* dg_dev, const int32_t* ctype_dev, int32_t n, float* reward_dev,
+                         uint8_t* done_dev, void* stream);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
