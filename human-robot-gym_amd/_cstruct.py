@@ -113,6 +113,7 @@ HammerState = _STRUCTS["hrg_hammer_state"]
 ExpertDesc = _STRUCTS["hrg_expert_desc"]
 DatasetDesc = _STRUCTS["hrg_dataset_desc"]
 HerDesc = _STRUCTS["hrg_her_desc"]
+RolloutDesc = _STRUCTS["hrg_rollout_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 

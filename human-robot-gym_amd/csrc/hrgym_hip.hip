@@ -3081,6 +3081,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_expert.h"   // the scripted experts + imitation reward kernels (hrg_batch_expert_*, hrg_batch_step_imitation)
 #include "hrgym_dataset.h"  // demonstration datasets: restore + state imitation reward kernels (hrg_batch_dataset_*, hrg_batch_step_dataset)
 #include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
+#include "hrgym_rollout.h"  // the PPO rollout buffer: view / observe / add / GAE / get kernels (hrg_rollout_*)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -3882,6 +3883,189 @@ int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const fl
   hipLaunchKernelGGL(hrg_goal_reward_done_kernel, dim3(((unsigned)n + HRG_HER_BLOCK - 1) / HRG_HER_BLOCK), dim3(HRG_HER_BLOCK), 0, (hipStream_t)stream, *desc, ag_dev, dg_dev,
                      ctype_dev, (int)n, reward_dev, done_dev);
   HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+// ---- PPO rollout buffer (csrc/hrgym_rollout.h) ----
+struct hrg_rollout {
+  int device = 0;
+  hrg_rollout_desc desc;
+  RolloutDev d;
+  int32_t pos = 0;         // the next slot (the write position lives on the host)
+  bool computed = false;   // advantages and returns belong to the stored steps
+};
+
+static void rollout_free(hrg_rollout* h) {
+  RolloutDev& d = h->d;
+  hipFree(d.obs); hipFree(d.act); hipFree(d.reward); hipFree(d.value); hipFree(d.log_prob); hipFree(d.ep_start); hipFree(d.adv); hipFree(d.ret); hipFree(d.cur_obs);
+  hipFree(d.flag); hipFree(d.run_ret); hipFree(d.run_len); hipFree(d.acc); hipFree((void*)d.obs_cols);
+  delete h;
+}
+
+int hrg_rollout_create(const hrg_rollout_desc* desc, int32_t device, hrg_rollout** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->n_envs < 1 || desc->n_steps < 1) return fail(HRG_ERR_INVALID, "rollout: n_envs and n_steps must be positive");
+  if (desc->n_obs_cols < 1 || desc->n_obs_cols > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "rollout: n_obs_cols must lie in [1, HRG_OBS_DIM]");
+  for (int c = 0; c < desc->n_obs_cols; c++)
+    if (desc->obs_cols[c] < 0 || desc->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "rollout: an observation column outside the superset");
+  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "rollout: act_dim must lie in [1, HRG_ACT_DIM]");
+  if (!(desc->gamma >= 0 && desc->gamma <= 1)) return fail(HRG_ERR_INVALID, "rollout: gamma must lie in [0, 1]");
+  if (!(desc->gae_lambda >= 0 && desc->gae_lambda <= 1)) return fail(HRG_ERR_INVALID, "rollout: gae_lambda must lie in [0, 1]");
+  HIPCHK(hipSetDevice(device));
+  hrg_rollout* h = new hrg_rollout();
+  h->device = device;
+  h->desc = *desc;
+  RolloutDev& d = h->d;
+  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->n_steps;
+  int32_t cols[HRG_OBS_DIM] = {0};
+  for (int c = 0; c < desc->n_obs_cols; c++) cols[c] = desc->obs_cols[c];
+#define ROLLOUT_ALLOC(ptr, bytes)                                                                                              \
+  do {                                                                                                                         \
+    const size_t _b = (bytes);                                                                                                 \
+    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
+      rollout_free(h);                                                                                                         \
+      return fail(HRG_ERR_NOMEM, "rollout: device allocation failed");                                                         \
+    }                                                                                                                          \
+  } while (0)
+  ROLLOUT_ALLOC(d.obs, slots * sizeof(float) * (size_t)desc->n_obs_cols);
+  ROLLOUT_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
+  ROLLOUT_ALLOC(d.reward, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.value, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.log_prob, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.ep_start, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.adv, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.ret, slots * sizeof(float));
+  ROLLOUT_ALLOC(d.cur_obs, n * sizeof(float) * HRG_OBS_DIM);
+  ROLLOUT_ALLOC(d.flag, n * sizeof(float));
+  ROLLOUT_ALLOC(d.run_ret, n * sizeof(double));
+  ROLLOUT_ALLOC(d.run_len, n * sizeof(int32_t));
+  ROLLOUT_ALLOC(d.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM);
+  ROLLOUT_ALLOC(d.obs_cols, sizeof cols);
+#undef ROLLOUT_ALLOC
+  if (hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    rollout_free(h);
+    return fail(HRG_ERR_HIP, "rollout: upload failed");
+  }
+  *out = h;
+  return HRG_OK;
+}
+
+void hrg_rollout_destroy(hrg_rollout* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();
+  rollout_free(h);
+}
+
+int hrg_rollout_view(hrg_rollout* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream) {
+  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!rows_dev) {   // the envs' current rows
+    rows_dev = h->d.cur_obs;
+    n_rows = h->desc.n_envs;
+  }
+  if (n_rows < 1) return fail(HRG_ERR_INVALID, "rollout: n_rows must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  const unsigned per = HRG_ROLLOUT_BLOCK / 64;
+  hipLaunchKernelGGL(hrg_rollout_view_kernel, dim3(((unsigned)n_rows + per - 1) / per), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->d, (int)h->desc.n_obs_cols, rows_dev,
+                     (int)n_rows, out_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_rollout_observe(hrg_rollout* h, const float* obs_dev, const uint8_t* mask_dev, void* stream) {
+  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_rollout_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, obs_dev, mask_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_rollout_add(hrg_rollout* h, const float* actions_dev, const float* values_dev, const float* log_probs_dev, const float* terminal_values_dev,
+                    const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, void* stream) {
+  if (!h || !actions_dev || !values_dev || !log_probs_dev || !obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (h->pos >= h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is full (hrg_rollout_reset starts the next rollout)");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_rollout_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, (int)h->pos, actions_dev, values_dev, log_probs_dev,
+                     terminal_values_dev, obs_dev, reward_dev, done_dev, info_dev);
+  HIPCHK(hipGetLastError());
+  h->pos++;
+  h->computed = false;
+  return HRG_OK;
+}
+
+int hrg_rollout_compute(hrg_rollout* h, const float* last_values_dev, void* stream) {
+  if (!h || !last_values_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (h->pos < h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is not full yet (returns and advantages are computed over n_steps steps)");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_rollout_gae_kernel, dim3(((unsigned)h->desc.n_envs + HRG_ROLLOUT_BLOCK - 1) / HRG_ROLLOUT_BLOCK), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->desc,
+                     h->d, last_values_dev);
+  HIPCHK(hipGetLastError());
+  h->computed = true;
+  return HRG_OK;
+}
+
+int hrg_rollout_get(hrg_rollout* h, const int64_t* index_dev, int32_t batch_size, float* observations_dev, float* actions_dev, float* old_values_dev,
+                    float* old_log_prob_dev, float* advantages_dev, float* returns_dev, void* stream) {
+  if (!h || !index_dev || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (batch_size < 1) return fail(HRG_ERR_INVALID, "rollout: batch_size must be positive");
+  if (!h->computed) return fail(HRG_ERR_INVALID, "rollout: no returns and advantages yet (hrg_rollout_compute comes first)");
+  HIPCHK(hipSetDevice(h->device));
+  const unsigned per = HRG_ROLLOUT_BLOCK / 64;
+  hipLaunchKernelGGL(hrg_rollout_get_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->desc, h->d, index_dev, (int)batch_size,
+                     observations_dev, actions_dev, old_values_dev, old_log_prob_dev, advantages_dev, returns_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_rollout_reset(hrg_rollout* h) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->pos = 0;
+  h->computed = false;
+  return HRG_OK;
+}
+
+int hrg_rollout_stats(hrg_rollout* h, double* per_env_host, int32_t clear) {
+  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t bytes = sizeof(double) * HRG_ROLLOUT_STATS_DIM * (size_t)h->desc.n_envs;
+  HIPCHK(hipMemcpy(per_env_host, h->d.acc, bytes, hipMemcpyDeviceToHost));
+  if (clear) {
+    HIPCHK(hipMemset(h->d.acc, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  return HRG_OK;
+}
+
+int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_host, float* rewards_host, float* values_host, float* log_probs_host,
+                       float* episode_starts_host, float* advantages_host, float* returns_host, float* cur_obs_host, float* flags_host, double* run_return_host,
+                       int32_t* run_length_host, double* stats_host, int64_t* state_host) {
+  if (!h || !observations_host || !actions_host || !rewards_host || !values_host || !log_probs_host || !episode_starts_host || !advantages_host || !returns_host ||
+      !cur_obs_host || !flags_host || !run_return_host || !run_length_host || !stats_host || !state_host)
+    return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const RolloutDev& d = h->d;
+  const size_t n = (size_t)h->desc.n_envs, T = (size_t)h->desc.n_steps, slots = n * T;
+  HIPCHK(hipMemcpy(observations_host, d.obs, slots * sizeof(float) * (size_t)h->desc.n_obs_cols, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(actions_host, d.act, slots * sizeof(float) * (size_t)h->desc.act_dim, hipMemcpyDeviceToHost));
+  std::vector<float> tm(slots);   // a time-major array on its way into the flat order
+  const float* scalars[6] = {d.reward, d.value, d.log_prob, d.ep_start, d.adv, d.ret};
+  float* flat[6] = {rewards_host, values_host, log_probs_host, episode_starts_host, advantages_host, returns_host};
+  for (int a = 0; a < 6; a++) {
+    HIPCHK(hipMemcpy(tm.data(), scalars[a], slots * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < n; e++)
+      for (size_t t = 0; t < T; t++) flat[a][e * T + t] = tm[t * n + e];
+  }
+  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(flags_host, d.flag, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_return_host, d.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_length_host, d.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stats_host, d.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM, hipMemcpyDeviceToHost));
+  state_host[0] = h->pos;
+  state_host[1] = h->computed ? 1 : 0;
   return HRG_OK;
 }
 

@@ -180,6 +180,15 @@ def her_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
     return kw
 
 
+def rollout_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
+    """`config.algorithm` of an on-policy run (training/config/algorithm/ppo.yaml: name PPO, n_steps, gamma, gae_lambda) on flat observations
+    (run.env_type "env") -> the keyword arguments of HipVecEnv.attach_rollout; None for any other config.  Missing keys take SB3's PPO defaults."""
+    run, alg = _get(config, "run"), _get(config, "algorithm")
+    if str(_get(alg, "name", "")).upper() != "PPO" or _get(run, "env_type", "env") != "env":
+        return None
+    return dict(n_steps=int(_get(alg, "n_steps", 2048)), gamma=float(_get(alg, "gamma", 0.99)), gae_lambda=float(_get(alg, "gae_lambda", 0.95)))
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""
@@ -209,4 +218,9 @@ def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class
         if her["buffer_size"] <= env.horizon:
             her["buffer_size"] = 2 * env.horizon + 2
         env.attach_her(**her)
+    rollout = rollout_kwargs_from_config(config)
+    # PPO: the rollout buffer lives beside the stepper (env.rollout, env.collect_rollout).  Only where the device path covers the env: another backend, or a
+    # wrapper that works on the host path (obs_norm, a dataset, an imitation reward), trains through step() as before
+    if rollout is not None and hasattr(env, "_rollout_refusal") and env._rollout_refusal() is None:
+        env.attach_rollout(**rollout)
     return env

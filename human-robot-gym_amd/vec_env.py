@@ -241,6 +241,7 @@ class _TorchBackend:
         self.sir = None    # host copy of the state imitation rows, once a dataset is attached
         self.her = None    # the hindsight replay buffer (her.HerBuffer), once attached: filled on the device behind every reset / step
         self._her_agent = False
+        self.rollout = None   # the PPO rollout buffer (rollout.RolloutBuffer), once attached: filled by HipVecEnv.collect_rollout
 
     def _fetch(self):
         if self.sir is not None:
@@ -270,6 +271,12 @@ class _TorchBackend:
             self.her.close()
         self.her = HerBuffer(desc, device=self.batch.device.index)
         self._her_agent = bool(keep_agent_actions)
+
+    def attach_rollout(self, desc, info_keys=None):
+        from .rollout import RolloutBuffer
+        if self.rollout is not None:
+            self.rollout.close()
+        self.rollout = RolloutBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
 
     def reset(self):
         if self.sir is not None:
@@ -307,6 +314,8 @@ class _TorchBackend:
     def close(self):
         if self.her is not None:
             self.her.close()
+        if self.rollout is not None:
+            self.rollout.close()
         self.batch.close()
 
 
@@ -456,6 +465,8 @@ class HipVecEnv(_VecEnvBase):
             backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
         if getattr(self, "_her_args", None) is not None:   # after seed(): a new, empty buffer
             backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None)
+        if getattr(self, "_rollout_args", None) is not None:   # after seed(): a new, empty buffer
+            backend.attach_rollout(self._rollout_desc(n_envs, **self._rollout_args), info_keys=self._info_keys)
         return backend
 
     def _init_spaces(self, n_envs, collision_prevention=None, ik_position_delta=None):
@@ -482,6 +493,8 @@ class HipVecEnv(_VecEnvBase):
         self._t_start = time.time()
         self._actions = None
         self._last_full = None
+        self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
+        self._device_loop = False    # collect_rollout has stepped the envs past the host accounting: step_async waits for a reset()
 
     def _init_obs_norm(self, obs_norm=None):
         """DatasetObsNormWrapper (wrappers/dataset_wrapper.py:160-300): (obs - mean) / std, optionally tanh(squash_factor * .), applied to the policy's
@@ -527,6 +540,7 @@ class HipVecEnv(_VecEnvBase):
     def reset(self):
         self._ep_ret[:] = 0
         self._ep_len[:] = 0
+        self._device_loop = False
         full = np.asarray(self._backend.reset())
         self._last_full = full
         if self.expert_obs_keys is not None:
@@ -534,6 +548,9 @@ class HipVecEnv(_VecEnvBase):
         return self._view(full, self._backend.reset_time if self._observe_time else None)
 
     def step_async(self, actions):
+        if self._device_loop:
+            raise RuntimeError("step_async after collect_rollout: the device loop moved the envs on without the host accounting (episode returns, the last "
+                               "observation); call reset() first")
         if self._ik is not None:  # [dx, dy, dz, gripper] in the first four columns of the 7-wide action rows
             a4 = np.asarray(actions, np.float64).reshape(self.num_envs, 4)
             actions = np.zeros((self.num_envs, CONST["HRG_ACT_DIM"]))
@@ -674,6 +691,7 @@ class HipVecEnv(_VecEnvBase):
         if isinstance(self._backend, _TorchBackend):
             self._backend.close()
             self._backend = self._build_backend(self.num_envs)
+            self._device_loop = False
         else:
             self._backend.reseed(self._desc)
         return [int(seed) + i for i in range(self.num_envs)]
@@ -843,6 +861,78 @@ class HipVecEnv(_VecEnvBase):
     def her(self):
         """The attached hindsight replay buffer (attach_her), or None."""
         return getattr(self._backend, "her", None)
+
+    # ---- the on-policy device path: SB3's RolloutBuffer and collect_rollouts next to the stepper (rollout.py, csrc/hrgym_rollout.h) ----
+    def _rollout_refusal(self):
+        """Why this env cannot carry a device rollout buffer, or None."""
+        if not isinstance(self._backend, _TorchBackend):
+            return "the rollout kernels run in the HIP library; another backend has none"
+        if self.goal_env:
+            return "goal_env: dict observations belong to the off-policy path (attach_her)"
+        if self._norm is not None:
+            return "obs_norm: the normalisation runs on the host path"
+        if self._dataset is not None or self._sir is not None or self._imit_alpha is not None:
+            return "a dataset or an imitation reward: their rewards and time column live on the host path"
+        return None
+
+    def _rollout_desc(self, n_envs, n_steps, gamma, gae_lambda):
+        from .rollout import build_rollout_desc
+        return build_rollout_desc(n_envs, n_steps, [int(c) for c in self._cols], act_dim=len(self.action_space.low), gamma=gamma, gae_lambda=gae_lambda)
+
+    def attach_rollout(self, n_steps, gamma=0.99, gae_lambda=0.95):
+        """A PPO rollout buffer on the device (rollout.RolloutBuffer; the arguments of SB3's RolloutBuffer, training/config/algorithm/ppo.yaml): `n_steps`
+        slots per env.  `collect_rollout` fills it; `env.rollout.get(batch_size)` yields minibatches of device tensors.  Attaching again replaces the
+        buffer with an empty one (and, between two rollouts of the device loop, resets the envs).  Collision prevention and the IK front-end run in the step kernel and are accepted.  Returns the buffer."""
+        why = self._rollout_refusal()
+        if why is not None:
+            raise NotImplementedError(f"attach_rollout: {why}")
+        args = dict(n_steps=int(n_steps), gamma=float(gamma), gae_lambda=float(gae_lambda))
+        self._backend.attach_rollout(self._rollout_desc(self.num_envs, **args), info_keys=self._info_keys)
+        self._rollout_args = args
+        if self._device_loop:   # attached between two rollouts of the device loop: the new buffer has no current rows, so the envs start again
+            self._backend.batch.reset()
+            self._backend.rollout.observe(self._backend.batch.obs)
+        return self._backend.rollout
+
+    @property
+    def rollout(self):
+        """The attached rollout buffer (attach_rollout), or None."""
+        return getattr(self._backend, "rollout", None)
+
+    def collect_rollout(self, policy, value_fn):
+        """OnPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env into `env.rollout`, then its returns and advantages.
+        `policy(obs float32 [n, K]) -> (actions float32 [n, act_dim], values [n], log_probs [n])` and `value_fn(obs) -> values [n]` take and return
+        tensors on the env's device.  Per step: the current observation, the policy, the actions clipped to the action bounds and widened to the
+        float64 rows the kernel reads, the step, the value of every env's terminal observation (used where the time limit truncated), the slot.  No
+        device-to-host copy and no stream synchronisation.  The first call (and the first after reset() or seed()) resets the envs.  Afterwards step_async
+        raises until reset(): the host accounting did not see these steps; `env.rollout.episode_stats()` is this path's account of episodes."""
+        rb = self.rollout
+        if rb is None:
+            raise NotImplementedError("collect_rollout: call attach_rollout(n_steps, gamma, gae_lambda) first")
+        if self._monitor is not None:
+            raise NotImplementedError("collect_rollout with monitor_dir: the Monitor csv is written by the host path; env.rollout.episode_stats() is the device "
+                                      "path's account of episodes")
+        import torch
+        b = self._backend.batch
+        dev, n, A = b.device, self.num_envs, rb.act_dim
+        if not self._device_loop:
+            b.reset()
+            rb.observe(b.obs)
+            self._device_loop = True
+            self._last_full = None   # (the host's copy of the rows is stale from here on)
+        rb.reset()
+        low, high = torch.from_numpy(self.action_space.low).to(dev), torch.from_numpy(self.action_space.high).to(dev)
+        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
+        for _ in range(rb.n_steps):
+            actions, values, log_probs = policy(rb.observation())
+            rows[:, :A] = torch.clamp(actions, low, high)   # SB3 clips what the env gets, not what the buffer stores
+            if A < CONST["HRG_ACT_DIM"]:
+                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
+            b.step(rows)
+            terminal_values = value_fn(rb.view(b.term_obs))
+            rb.add_step(actions, values, log_probs, terminal_values, b.obs, b.term_obs, b.reward, b.done, b.info)
+        rb.compute_returns_and_advantage(value_fn(rb.observation()))
+        return rb
 
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
         if method_name == "check_collision_action":   # per-env call of the reference: env_method("check_collision_action", action, indices=[i])

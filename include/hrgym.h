@@ -479,8 +479,20 @@ typedef struct hrg_her_desc {
   int32_t dg_in_obs[8];           /* where component j of the desired goal sits inside `observation` */
 } hrg_her_desc;
 
+/* ------------------------------------------------------------------------- the PPO rollout buffer on the device (POD) */
+/* One rollout buffer: SB3's RolloutBuffer(buffer_size = n_steps, n_envs, gamma, gae_lambda) and the policy's view of an observation row. */
+typedef struct hrg_rollout_desc {
+  int32_t n_envs;
+  int32_t n_steps;                /* slots per env (algorithm/ppo.yaml: n_steps) */
+  double gamma, gae_lambda;       /* both in [0, 1]; the device computes with (float)gamma and (float)(gamma * gae_lambda) */
+  int32_t act_dim;                /* action values the policy emits: 7 joint space, 4 with the Cartesian front-end */
+  int32_t n_obs_cols;             /* length of the policy's observation, at most HRG_OBS_DIM */
+  int32_t obs_cols[HRG_OBS_DIM];  /* column of the superset behind each value of the observation */
+} hrg_rollout_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 typedef struct hrg_her hrg_her;     /* opaque */
+typedef struct hrg_rollout hrg_rollout; /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -653,6 +665,54 @@ int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, f
                    uint8_t* truncated_host, int32_t* ctype_host, int64_t* ep_start_host, int32_t* ep_len_host, int64_t* state_host, float* cur_obs_host);
 int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const float* dg_dev, const int32_t* ctype_dev, int32_t n, float* reward_dev,
                          uint8_t* done_dev, void* stream);
+
+/* The PPO rollout buffer on the device (csrc/hrgym_rollout.h): SB3's RolloutBuffer and the bookkeeping of OnPolicyAlgorithm.collect_rollouts for a batch of
+ * envs (training/config/algorithm/ppo.yaml), plus the episode sums Monitor and callbacks/logging_callback.py keep on the host.  n_steps slots per env in device
+ * memory.  The flat order of everything gathered or exported is SB3's swap_and_flatten: i = env * n_steps + step.  The entry points take raw device pointers
+ * (the tensors a step wrote, or synthetic ones), no hrg_batch; all but create / destroy / stats / export are asynchronous on `stream`.  The write position
+ * lives in the handle on the host.
+ *   hrg_rollout_create   <- RolloutBuffer.__init__: allocates and zeroes everything (synchronous; nothing is allocated later).  HRG_ERR_INVALID for n_envs < 1,
+ *                           n_steps < 1, n_obs_cols outside 1 .. HRG_OBS_DIM, a column outside 0 .. 63, act_dim outside 1 .. HRG_ACT_DIM, gamma or gae_lambda
+ *                           outside [0, 1].
+ *   hrg_rollout_view     the policy's view of n_rows rows of the observation superset: rows_dev float [n_rows][HRG_OBS_DIM] -> out_dev float
+ *                           [n_rows][n_obs_cols], value k = column obs_cols[k].  rows_dev NULL: the envs' current rows (SB3's _last_obs; n_rows is then
+ *                           n_envs, whatever was passed).
+ *   hrg_rollout_observe  <- _last_obs = env.reset(), _last_episode_starts = True: for envs whose mask byte is non-zero (NULL: all) the current row becomes
+ *                           obs_dev's, the episode_start flag 1, the running return and length 0.
+ *   hrg_rollout_add      <- collect_rollouts + RolloutBuffer.add, after a step: slot `position` of every env takes the policy's view of the current (pre-step)
+ *                           row, actions_dev float [n_envs][act_dim] (the policy's own output: SB3 stores the unclipped action), values_dev, log_probs_dev
+ *                           float [n_envs], the env's episode_start flag, and reward_dev -- plus (float)gamma * terminal_values_dev[e] (one float32
+ *                           multiply, one float32 add) where done_dev[e], info column HRG_INFO_TRUNCATED and terminal_values_dev are all non-zero / non-NULL.
+ *                           Then the current row becomes obs_dev's (the row after auto-reset), the flag done_dev[e]; the running return adds reward_dev[e]
+ *                           (no bootstrap term), the running length 1; on done the env's episode accumulators add 1 episode, the running return and
+ *                           length and every info column, and the running pair is zeroed.  Advances the position.  HRG_ERR_INVALID on a full buffer.
+ *   hrg_rollout_compute  <- compute_returns_and_advantage(last_values, dones = the flags): last_values_dev float [n_envs].  float32, in numpy's operation
+ *                           order, no fused multiply-add.  HRG_ERR_INVALID before the buffer is full.
+ *   hrg_rollout_get      <- _get_samples: index_dev int64 [batch_size] flat indices (repeats allowed) -> observations float [batch_size][n_obs_cols],
+ *                           actions float [batch_size][act_dim], old_values, old_log_prob, advantages, returns float [batch_size].  The indices are TRUSTED to
+ *                           lie in [0, n_envs * n_steps): the kernel does not check them (rollout.RolloutBuffer.get does, for caller-supplied ones).
+ *                           HRG_ERR_INVALID before hrg_rollout_compute, for batch_size < 1, for a null argument.
+ *   hrg_rollout_reset    <- RolloutBuffer.reset(): the position back to 0.  Current rows, flags, running returns and episode accumulators stay.
+ *   hrg_rollout_stats    synchronous: per_env_host double [n_envs][3 + HRG_INFO_DIM] = finished episodes, sum of their returns, sum of their lengths, sums of
+ *                           the info columns of their last steps, since the last clear; clear != 0 zeroes the accumulators afterwards.
+ *   hrg_rollout_export   synchronous parity hook, every array in the flat order: observations float [n_envs * n_steps][n_obs_cols], actions float
+ *                           [n_envs * n_steps][act_dim], rewards, values, log_probs, episode_starts, advantages, returns float [n_envs * n_steps], cur_obs
+ *                           float [n_envs][HRG_OBS_DIM], flags float [n_envs], running return double [n_envs], running length int32 [n_envs], the
+ *                           accumulators double [n_envs][3 + HRG_INFO_DIM], state int64[2] = position, 1 once computed. */
+int hrg_rollout_create(const hrg_rollout_desc* desc, int32_t device, hrg_rollout** out);
+void hrg_rollout_destroy(hrg_rollout* h);
+int hrg_rollout_view(hrg_rollout* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream);
+int hrg_rollout_observe(hrg_rollout* h, const float* obs_dev, const uint8_t* mask_dev, void* stream);
+int hrg_rollout_add(hrg_rollout* h, const float* actions_dev, const float* values_dev, const float* log_probs_dev, const float* terminal_values_dev,
+                    const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, void* stream);
+int hrg_rollout_compute(hrg_rollout* h, const float* last_values_dev, void* stream);
+int hrg_rollout_get(hrg_rollout* h, const int64_t* index_dev, int32_t batch_size, float* observations_dev, float* actions_dev, float* old_values_dev,
+                    float* old_log_prob_dev, float* advantages_dev, float* returns_dev, void* stream);
+int hrg_rollout_reset(hrg_rollout* h);
+int hrg_rollout_stats(hrg_rollout* h, double* per_env_host, int32_t clear);
+int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_host, float* rewards_host, float* values_host, float* log_probs_host,
+                       float* episode_starts_host, float* advantages_host, float* returns_host, float* cur_obs_host, float* flags_host, double* run_return_host,
+                       int32_t* run_length_host, double* stats_host, int64_t* state_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
