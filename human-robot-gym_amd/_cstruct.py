@@ -114,6 +114,7 @@ ExpertDesc = _STRUCTS["hrg_expert_desc"]
 DatasetDesc = _STRUCTS["hrg_dataset_desc"]
 HerDesc = _STRUCTS["hrg_her_desc"]
 RolloutDesc = _STRUCTS["hrg_rollout_desc"]
+ReplayDesc = _STRUCTS["hrg_replay_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 

@@ -3082,6 +3082,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_dataset.h"  // demonstration datasets: restore + state imitation reward kernels (hrg_batch_dataset_*, hrg_batch_step_dataset)
 #include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
 #include "hrgym_rollout.h"  // the PPO rollout buffer: view / observe / add / GAE / get kernels (hrg_rollout_*)
+#include "hrgym_replay.h"   // the uniform replay buffer of SAC: view / observe / add / sample kernels (hrg_replay_*)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -4066,6 +4067,204 @@ int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_
   HIPCHK(hipMemcpy(stats_host, d.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM, hipMemcpyDeviceToHost));
   state_host[0] = h->pos;
   state_host[1] = h->computed ? 1 : 0;
+  return HRG_OK;
+}
+
+// ---- uniform replay buffer (csrc/hrgym_replay.h) ----
+struct hrg_replay {
+  int device = 0;
+  hrg_replay_desc desc;
+  ReplayDev d;
+  int32_t pos = 0;      // the next slot (the write position lives on the host)
+  bool full = false;    // every slot holds a transition
+  uint64_t calls = 0;   // sample calls that drew their indices (key of the draws)
+  size_t bytes = 0;     // device memory held
+};
+
+static void replay_free(hrg_replay* h) {
+  ReplayDev& d = h->d;
+  hipFree(d.obs); hipFree(d.nobs); hipFree(d.act); hipFree(d.reward); hipFree(d.done); hipFree(d.timeout); hipFree(d.cur_obs); hipFree(d.cur_time); hipFree(d.run_ret);
+  hipFree(d.run_len); hipFree(d.acc); hipFree((void*)d.obs_cols); hipFree((void*)d.mean); hipFree((void*)d.std);
+  delete h;
+}
+
+int hrg_replay_create(const hrg_replay_desc* desc, int32_t device, hrg_replay** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->n_envs < 1 || desc->capacity < 1) return fail(HRG_ERR_INVALID, "replay: n_envs and capacity must be positive");
+  const bool with_time = desc->observe_time != 0;
+  if (desc->n_obs_cols < 1 || desc->n_obs_cols + (with_time ? 1 : 0) > HRG_OBS_DIM)
+    return fail(HRG_ERR_INVALID, "replay: n_obs_cols (+ 1 with observe_time) must lie in [1, HRG_OBS_DIM]");
+  const int K = desc->n_obs_cols + (with_time ? 1 : 0);
+  for (int c = 0; c < desc->n_obs_cols; c++)
+    if (desc->obs_cols[c] < 0 || desc->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "replay: an observation column outside the superset");
+  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "replay: act_dim must lie in [1, HRG_ACT_DIM]");
+  if (desc->squash && !desc->normalize) return fail(HRG_ERR_INVALID, "replay: squash needs normalize");
+  if (desc->normalize) {
+    for (int k = 0; k < K; k++)
+      if (!std::isfinite(desc->mean[k]) || !std::isfinite(desc->std[k]) || desc->std[k] == 0.0) return fail(HRG_ERR_INVALID, "replay: mean must be finite, std finite and non-zero");
+    if (desc->squash && !std::isfinite(desc->squash_factor)) return fail(HRG_ERR_INVALID, "replay: squash_factor must be finite");
+  }
+  HIPCHK(hipSetDevice(device));
+  hrg_replay* h = new hrg_replay();
+  h->device = device;
+  h->desc = *desc;
+  ReplayDev& d = h->d;
+  d.n_envs = desc->n_envs; d.capacity = desc->capacity; d.act_dim = desc->act_dim; d.n_obs_cols = desc->n_obs_cols;
+  d.observe_time = with_time ? 1 : 0; d.normalize = desc->normalize ? 1 : 0; d.squash = desc->squash ? 1 : 0;
+  d.squash_factor = desc->squash_factor; d.seed = desc->seed;
+  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
+  int32_t cols[HRG_OBS_DIM] = {0};
+  double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
+  for (int k = 0; k < HRG_OBS_DIM; k++) {
+    if (k < desc->n_obs_cols) cols[k] = desc->obs_cols[k];
+    mean[k] = desc->normalize && k < K ? desc->mean[k] : 0.0;
+    sd[k] = desc->normalize && k < K ? desc->std[k] : 1.0;
+  }
+#define REPLAY_ALLOC(ptr, nbytes)                                                                                              \
+  do {                                                                                                                         \
+    const size_t _b = (nbytes);                                                                                                \
+    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
+      (void)hipGetLastError();                                                                                                 \
+      replay_free(h);                                                                                                          \
+      return fail(HRG_ERR_NOMEM, "replay: device allocation of " + std::to_string(_b) + " bytes failed");                      \
+    }                                                                                                                          \
+    h->bytes += _b;                                                                                                            \
+  } while (0)
+  REPLAY_ALLOC(d.obs, slots * sizeof(float) * (size_t)K);
+  REPLAY_ALLOC(d.nobs, slots * sizeof(float) * (size_t)K);
+  REPLAY_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
+  REPLAY_ALLOC(d.reward, slots * sizeof(float));
+  REPLAY_ALLOC(d.done, slots);
+  REPLAY_ALLOC(d.timeout, slots);
+  REPLAY_ALLOC(d.cur_obs, n * sizeof(float) * HRG_OBS_DIM);
+  REPLAY_ALLOC(d.cur_time, n * sizeof(float));
+  REPLAY_ALLOC(d.run_ret, n * sizeof(double));
+  REPLAY_ALLOC(d.run_len, n * sizeof(int32_t));
+  REPLAY_ALLOC(d.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM);
+  REPLAY_ALLOC(d.obs_cols, sizeof cols);
+  REPLAY_ALLOC(d.mean, sizeof mean);
+  REPLAY_ALLOC(d.std, sizeof sd);
+#undef REPLAY_ALLOC
+  if (hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy((void*)d.mean, mean, sizeof mean, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((void*)d.std, sd, sizeof sd, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    replay_free(h);
+    return fail(HRG_ERR_HIP, "replay: upload failed");
+  }
+  *out = h;
+  return HRG_OK;
+}
+
+void hrg_replay_destroy(hrg_replay* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();
+  replay_free(h);
+}
+
+int hrg_replay_view(hrg_replay* h, const float* rows_dev, const float* time_dev, int32_t n_rows, float* out_dev, void* stream) {
+  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!rows_dev) {   // the envs' current rows
+    rows_dev = h->d.cur_obs;
+    time_dev = h->d.cur_time;
+    n_rows = h->desc.n_envs;
+  }
+  if (n_rows < 1) return fail(HRG_ERR_INVALID, "replay: n_rows must be positive");
+  if (h->d.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
+  HIPCHK(hipSetDevice(h->device));
+  const unsigned per = HRG_REPLAY_BLOCK / 64;
+  hipLaunchKernelGGL(hrg_replay_view_kernel, dim3(((unsigned)n_rows + per - 1) / per), dim3(HRG_REPLAY_BLOCK), 0, (hipStream_t)stream, h->d, rows_dev, time_dev, (int)n_rows, out_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_replay_observe(hrg_replay* h, const float* obs_dev, const float* time_dev, const uint8_t* mask_dev, void* stream) {
+  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (h->d.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_replay_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->d, obs_dev, time_dev, mask_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_replay_add(hrg_replay* h, const float* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                   const int32_t* info_dev, const float* imit_dev, const float* sir_dev, void* stream) {
+  if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "replay: an imitation row or a state imitation row, not both");
+  if (h->d.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the state imitation rows (their time columns)");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_replay_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->d, (int)h->pos, actions_dev, obs_dev, term_obs_dev, reward_dev,
+                     done_dev, info_dev, imit_dev, sir_dev);
+  HIPCHK(hipGetLastError());
+  if (++h->pos == h->desc.capacity) {   // ReplayBuffer.add: self.full = True; self.pos = 0
+    h->pos = 0;
+    h->full = true;
+  }
+  return HRG_OK;
+}
+
+int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in_dev, float* observations_dev, float* actions_dev, float* next_observations_dev,
+                      float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  if (batch_size < 1) return fail(HRG_ERR_INVALID, "replay: batch_size must be positive");
+  if (!observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev) return fail(HRG_ERR_INVALID, "replay: null output");
+  const int64_t upper = h->full ? h->desc.capacity : h->pos;
+  if (upper < 1) return fail(HRG_ERR_INVALID, "replay: the buffer is empty (nothing to sample)");
+  HIPCHK(hipSetDevice(h->device));
+  const unsigned per = HRG_REPLAY_BLOCK / 64;
+  hipLaunchKernelGGL(hrg_replay_sample_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_REPLAY_BLOCK), 0, (hipStream_t)stream, h->d, upper, h->calls, index_in_dev,
+                     (int)batch_size, observations_dev, actions_dev, next_observations_dev, dones_dev, rewards_dev, index_out_dev);
+  HIPCHK(hipGetLastError());
+  if (!index_in_dev) h->calls++;
+  return HRG_OK;
+}
+
+int hrg_replay_stats(hrg_replay* h, double* per_env_host, int32_t clear) {
+  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t bytes = sizeof(double) * HRG_REPLAY_STATS_DIM * (size_t)h->desc.n_envs;
+  HIPCHK(hipMemcpy(per_env_host, h->d.acc, bytes, hipMemcpyDeviceToHost));
+  if (clear) {
+    HIPCHK(hipMemset(h->d.acc, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  return HRG_OK;
+}
+
+int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_observations_host, float* actions_host, float* rewards_host, uint8_t* dones_host,
+                      uint8_t* timeouts_host, float* cur_obs_host, float* cur_time_host, double* run_return_host, int32_t* run_length_host, double* stats_host,
+                      int64_t* state_host) {
+  if (!h || !observations_host || !next_observations_host || !actions_host || !rewards_host || !dones_host || !timeouts_host || !cur_obs_host || !cur_time_host ||
+      !run_return_host || !run_length_host || !stats_host || !state_host)
+    return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const ReplayDev& d = h->d;
+  const size_t n = (size_t)h->desc.n_envs, slots = n * (size_t)h->desc.capacity, K = (size_t)(d.n_obs_cols + d.observe_time);
+  HIPCHK(hipMemcpy(observations_host, d.obs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(next_observations_host, d.nobs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(actions_host, d.act, slots * sizeof(float) * (size_t)d.act_dim, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(rewards_host, d.reward, slots * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(dones_host, d.done, slots, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(timeouts_host, d.timeout, slots, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_time_host, d.cur_time, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_return_host, d.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_length_host, d.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stats_host, d.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM, hipMemcpyDeviceToHost));
+  state_host[0] = h->pos;
+  state_host[1] = h->full ? 1 : 0;
+  state_host[2] = (int64_t)h->calls;
+  return HRG_OK;
+}
+
+int hrg_replay_size(hrg_replay* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->pos;
+  size_host[1] = h->full ? 1 : 0;
+  size_host[2] = (int64_t)h->calls;
+  size_host[3] = (int64_t)h->bytes;
   return HRG_OK;
 }
 

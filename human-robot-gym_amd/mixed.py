@@ -223,6 +223,9 @@ def _mixed_cls():
         def _rollout_refusal(self):
             return "the mixed batch steps one HipBatch per task; use one HipVecEnv per task"
 
+        def _replay_refusal(self):
+            return "the mixed batch has its observation columns per task; use one HipVecEnv per task"
+
         def expert_actions(self):
             raise NotImplementedError("scripted experts are per task and action form; use one HipVecEnv(expert=...) per task")
 

@@ -189,6 +189,23 @@ def rollout_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
     return dict(n_steps=int(_get(alg, "n_steps", 2048)), gamma=float(_get(alg, "gamma", 0.99)), gae_lambda=float(_get(alg, "gae_lambda", 0.95)))
 
 
+def replay_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
+    """`config.algorithm` of an off-policy run on flat observations (training/config_icra_2024/.../*-SAC.yaml: name SAC, buffer_size; run.env_type "env")
+    -> the keyword arguments of HipVecEnv.attach_replay; None for any other config (a goal-env run's buffer is her_kwargs_from_config's).  `buffer_size` is
+    the algorithm's, transitions in all (SB3's default 1 000 000).  optimize_memory_usage and replay_buffer_kwargs.handle_timeout_termination are handed on
+    where the config sets them, so that attach_replay refuses what the device buffer does not do."""
+    run, alg = _get(config, "run"), _get(config, "algorithm")
+    if str(_get(alg, "name", "")).upper() != "SAC" or _get(run, "env_type", "env") != "env":
+        return None
+    kw: Dict[str, Any] = dict(buffer_size=int(_get(alg, "buffer_size", 1_000_000)))
+    if _get(alg, "optimize_memory_usage") is not None:
+        kw["optimize_memory_usage"] = bool(_get(alg, "optimize_memory_usage"))
+    node = _plain(_get(alg, "replay_buffer_kwargs")) or {}
+    if "handle_timeout_termination" in node:
+        kw["handle_timeout_termination"] = bool(node["handle_timeout_termination"])
+    return kw
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""
@@ -223,4 +240,9 @@ def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class
     # wrapper that works on the host path (obs_norm, a dataset, an imitation reward), trains through step() as before
     if rollout is not None and hasattr(env, "_rollout_refusal") and env._rollout_refusal() is None:
         env.attach_rollout(**rollout)
+    replay = replay_kwargs_from_config(config)
+    # SAC on flat observations: the replay buffer lives beside the stepper (env.replay, env.collect_steps), with the wrappers of the config on; another
+    # backend and the mixed batch train through step() as before
+    if replay is not None and hasattr(env, "_replay_refusal") and env._replay_refusal() is None:
+        env.attach_replay(**replay)
     return env

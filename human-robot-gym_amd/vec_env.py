@@ -242,6 +242,9 @@ class _TorchBackend:
         self.her = None    # the hindsight replay buffer (her.HerBuffer), once attached: filled on the device behind every reset / step
         self._her_agent = False
         self.rollout = None   # the PPO rollout buffer (rollout.RolloutBuffer), once attached: filled by HipVecEnv.collect_rollout
+        self.replay = None    # the uniform replay buffer (replay.ReplayBuffer), once attached: filled on the device behind every reset / step
+        self._replay_bounds = None   # (low, high) float64 device tensors: the action bounds the agent's rows are brought back to [-1, 1] by
+        self._stepped = False        # the rows on the device are a step's (their time column: the state imitation row's), not a reset's
 
     def _fetch(self):
         if self.sir is not None:
@@ -278,32 +281,78 @@ class _TorchBackend:
             self.rollout.close()
         self.rollout = RolloutBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
 
-    def reset(self):
+    def attach_replay(self, desc, low, high, info_keys=None):
+        """`low` / `high`: the bounds of the action space; the buffer stores the rows the agent sent (copied before the step rewrites them), brought back to
+        the policy's scale [-1, 1] by them."""
+        from .replay import ReplayBuffer
+        if self.replay is not None:
+            self.replay.close()
+        t = self.torch
+        self.replay = ReplayBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
+        self._replay_bounds = tuple(t.from_numpy(np.asarray(x, np.float64)).to(self.batch.device) for x in (low, high))
+
+    def reset_device(self):
+        """The reset and what the attached buffers take from it, without the copy to the host (the device loops start here)."""
         if self.sir is not None:
             self.batch.dataset_reset()
             cur = self.batch.dataset_cursor()   # (synchronous; a whole-batch reset is not on the step path)
             self.reset_time = (cur[:, 1] / cur[:, 2]).astype(np.float32)   # StateBasedExpertImitationRewardWrapper.reset (107): start step / T
         else:
             self.batch.reset()
+        self._stepped = False
         if self.her is not None:
             self.her.observe(self.batch.obs)
+        if self.replay is not None:
+            self.replay_observe()
+
+    def reset(self):
+        self.reset_device()
         self._fetch()
         return self.obs
+
+    def launch_step(self, act):
+        """The step entry that fits what is attached; `act`: float64 [n, HRG_ACT_DIM] on the device (the kernel may rewrite the rows)."""
+        if self.sir is not None:   # (runs the expert's kernels too when an imitation reward is attached)
+            self.batch.step_dataset(act)
+        elif self.imit is not None:
+            self.batch.step_imitation(act)
+        else:
+            self.batch.step(act)
+        self._stepped = True
+
+    def replay_observe(self):
+        """The rows on the device (a reset's or the last step's) become the replay buffer's current rows."""
+        time = None
+        if self.replay.observe_time:
+            time = (self.batch.sir[:, CONST["HRG_SIR_TIME_OBS"]].contiguous() if self._stepped else
+                    self.torch.from_numpy(np.ascontiguousarray(self.reset_time, np.float32)).to(self.batch.device))
+        self.replay.observe(self.batch.obs, time=time)
+
+    def replay_add(self, actions):
+        """The last step's transition into the replay buffer; `actions`: float32 [n, act_dim] at the policy's scale.  The imitation rows go along where a
+        reward of that kind is attached: the episode return is the env's own reward, the time columns are the state imitation reward's."""
+        b, rows = self.batch, {}
+        if self.sir is not None and b.dataset_desc.sir_kind != CONST["HRG_SIR_NONE"]:
+            rows = dict(sir=b.sir)
+        elif self.imit is not None:
+            rows = dict(imit=b.imit)
+        self.replay.add_step(actions, b.obs, b.term_obs, b.reward, b.done, b.info, **rows)
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
         self._her_act = self._act.clone() if self.her is not None and self._her_agent else self._act
-        if self.sir is not None:   # (runs the expert's kernels too when an imitation reward is attached)
-            self.batch.step_dataset(self._act)
-        elif self.imit is not None:
-            self.batch.step_imitation(self._act)
-        else:
-            self.batch.step(self._act)
+        if self.replay is not None:   # the agent's own rows, before collision prevention or the IK front-end rewrite them, at the policy's scale
+            low, high = self._replay_bounds
+            A = self.replay.act_dim
+            self._replay_act = (2.0 * ((self._act[:, :A] - low) / (high - low)) - 1.0).to(self.torch.float32).contiguous()
+        self.launch_step(self._act)
 
     def step_wait(self):
         if self.her is not None:   # on the step's stream, ahead of the host copy: the transition never leaves the device
             b = self.batch
             self.her.add_step(self._her_act, b.obs, b.term_obs, b.reward, b.done, b.info)
+        if self.replay is not None:
+            self.replay_add(self._replay_act)
         self._fetch()
         return self.obs, self.term_obs, self.reward, self.done, self.info
 
@@ -316,6 +365,8 @@ class _TorchBackend:
             self.her.close()
         if self.rollout is not None:
             self.rollout.close()
+        if self.replay is not None:
+            self.replay.close()
         self.batch.close()
 
 
@@ -467,6 +518,8 @@ class HipVecEnv(_VecEnvBase):
             backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None)
         if getattr(self, "_rollout_args", None) is not None:   # after seed(): a new, empty buffer
             backend.attach_rollout(self._rollout_desc(n_envs, **self._rollout_args), info_keys=self._info_keys)
+        if getattr(self, "_replay_args", None) is not None:   # after seed(): a new, empty buffer
+            backend.attach_replay(self._replay_desc(n_envs, **self._replay_args), self.action_space.low, self.action_space.high, info_keys=self._info_keys)
         return backend
 
     def _init_spaces(self, n_envs, collision_prevention=None, ik_position_delta=None):
@@ -494,7 +547,8 @@ class HipVecEnv(_VecEnvBase):
         self._actions = None
         self._last_full = None
         self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
-        self._device_loop = False    # collect_rollout has stepped the envs past the host accounting: step_async waits for a reset()
+        self._replay_args = None     # arguments of attach_replay, likewise
+        self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
 
     def _init_obs_norm(self, obs_norm=None):
         """DatasetObsNormWrapper (wrappers/dataset_wrapper.py:160-300): (obs - mean) / std, optionally tanh(squash_factor * .), applied to the policy's
@@ -549,7 +603,7 @@ class HipVecEnv(_VecEnvBase):
 
     def step_async(self, actions):
         if self._device_loop:
-            raise RuntimeError("step_async after collect_rollout: the device loop moved the envs on without the host accounting (episode returns, the last "
+            raise RuntimeError(f"step_async after {self._device_loop}: the device loop moved the envs on without the host accounting (episode returns, the last "
                                "observation); call reset() first")
         if self._ik is not None:  # [dx, dy, dz, gripper] in the first four columns of the 7-wide action rows
             a4 = np.asarray(actions, np.float64).reshape(self.num_envs, 4)
@@ -909,17 +963,10 @@ class HipVecEnv(_VecEnvBase):
         rb = self.rollout
         if rb is None:
             raise NotImplementedError("collect_rollout: call attach_rollout(n_steps, gamma, gae_lambda) first")
-        if self._monitor is not None:
-            raise NotImplementedError("collect_rollout with monitor_dir: the Monitor csv is written by the host path; env.rollout.episode_stats() is the device "
-                                      "path's account of episodes")
+        self._enter_device_loop("collect_rollout", "env.rollout.episode_stats()")
         import torch
         b = self._backend.batch
         dev, n, A = b.device, self.num_envs, rb.act_dim
-        if not self._device_loop:
-            b.reset()
-            rb.observe(b.obs)
-            self._device_loop = True
-            self._last_full = None   # (the host's copy of the rows is stale from here on)
         rb.reset()
         low, high = torch.from_numpy(self.action_space.low).to(dev), torch.from_numpy(self.action_space.high).to(dev)
         rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
@@ -932,6 +979,88 @@ class HipVecEnv(_VecEnvBase):
             terminal_values = value_fn(rb.view(b.term_obs))
             rb.add_step(actions, values, log_probs, terminal_values, b.obs, b.term_obs, b.reward, b.done, b.info)
         rb.compute_returns_and_advantage(value_fn(rb.observation()))
+        return rb
+
+    def _enter_device_loop(self, name, account):
+        """What collect_rollout and collect_steps share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs -- to a dataset
+        state where a dataset is attached -- and hands the rows to the attached buffers; from then on step_async raises until reset()."""
+        if self._monitor is not None:
+            raise NotImplementedError(f"{name} with monitor_dir: the Monitor csv is written by the host path; {account} is the device path's account of episodes")
+        if not self._device_loop:
+            be = self._backend
+            be.reset_device()
+            if be.rollout is not None:
+                be.rollout.observe(be.batch.obs)
+            self._last_full = None   # (the host's copy of the rows is stale from here on)
+        self._device_loop = name
+
+    # ---- the off-policy device path on flat observations: SB3's ReplayBuffer next to the stepper (replay.py, csrc/hrgym_replay.h) ----
+    def _replay_refusal(self):
+        """Why this env cannot carry a device replay buffer, or None."""
+        if not isinstance(self._backend, _TorchBackend):
+            return "the replay kernels run in the HIP library; another backend has none"
+        if self.goal_env:
+            return "goal_env: dict observations and relabelling belong to attach_her"
+        return None
+
+    def _replay_desc(self, n_envs, buffer_size, seed):
+        from .replay import build_replay_desc
+        mean, std, squash = self._norm if self._norm is not None else (None, None, None)
+        return build_replay_desc(n_envs, buffer_size, [int(c) for c in self._cols], act_dim=len(self.action_space.low), observe_time=self._observe_time, mean=mean,
+                                 std=std, squash_factor=squash, seed=int(self._desc.seed) if seed is None else seed)
+
+    def attach_replay(self, buffer_size, handle_timeout_termination=True, optimize_memory_usage=False, seed=None):
+        """A uniform replay buffer on the device (replay.ReplayBuffer; the keywords of SB3's ReplayBuffer, training/config_icra_2024/.../*-SAC.yaml):
+        `buffer_size` transitions IN ALL, max(buffer_size // n_envs, 1) slots of one transition per env.  From now on reset() and every step put their rows
+        into it without leaving the device -- as the policy sees them: obs_norm, the time column of a state imitation reward --, `collect_steps` does the same
+        without the host; `env.replay.sample(n)` returns device tensors.  The action-based and the state-based imitation reward, a dataset, collision
+        prevention and the IK front-end are accepted (the ICRA stack).  Attaching again replaces the buffer with an empty one.  Returns the buffer."""
+        why = self._replay_refusal()
+        if why is not None:
+            raise NotImplementedError(f"attach_replay: {why}")
+        if not handle_timeout_termination:
+            raise NotImplementedError("attach_replay(handle_timeout_termination=False): the device buffer never hands a timeout out as a termination")
+        if optimize_memory_usage:
+            raise NotImplementedError("attach_replay(optimize_memory_usage=True): the device buffer keeps observations and next observations apart")
+        args = dict(buffer_size=int(buffer_size), seed=seed)
+        self._backend.attach_replay(self._replay_desc(self.num_envs, **args), self.action_space.low, self.action_space.high, info_keys=self._info_keys)
+        self._replay_args = args
+        if self._device_loop:   # attached between two runs of a device loop: the new buffer has no current rows, so the envs start again
+            self._backend.reset_device()
+            if self._backend.rollout is not None:
+                self._backend.rollout.observe(self._backend.batch.obs)
+        elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
+            self._backend.replay_observe()
+        return self._backend.replay
+
+    @property
+    def replay(self):
+        """The attached replay buffer (attach_replay), or None."""
+        return getattr(self._backend, "replay", None)
+
+    def collect_steps(self, policy, n_steps):
+        """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`.  `policy(obs float32 [n, K]) ->
+        actions float32 [n, act_dim]` in [-1, 1] takes and returns tensors on the env's device.  Per step: the current observation, the policy, the actions
+        brought to the action bounds (low + 0.5 (a + 1) (high - low)) and widened to the float64 rows the kernel reads, the step with whatever reward kernels
+        are attached, the slot (which stores the policy's own action).  No device-to-host copy and no stream synchronisation.  The first call (and the first
+        after reset() or seed()) resets the envs.  Afterwards step_async raises until reset(): the host accounting did not see these steps;
+        `env.replay.episode_stats()` is this path's account of episodes."""
+        rb = self.replay
+        if rb is None:
+            raise NotImplementedError("collect_steps: call attach_replay(buffer_size) first")
+        self._enter_device_loop("collect_steps", "env.replay.episode_stats()")
+        import torch
+        be = self._backend
+        dev, n, A = be.batch.device, self.num_envs, rb.act_dim
+        low, high = be._replay_bounds
+        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
+        for _ in range(int(n_steps)):
+            actions = policy(rb.observation())
+            rows[:, :A] = low + 0.5 * (actions.to(torch.float64) + 1.0) * (high - low)   # SB3's unscale_action
+            if A < CONST["HRG_ACT_DIM"]:
+                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
+            be.launch_step(rows)
+            be.replay_add(actions)
         return rb
 
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):

@@ -490,9 +490,31 @@ typedef struct hrg_rollout_desc {
   int32_t obs_cols[HRG_OBS_DIM];  /* column of the superset behind each value of the observation */
 } hrg_rollout_desc;
 
+/* ------------------------------------------------------------------------- the uniform replay buffer of SAC on the device (POD) */
+#define HRG_REPLAY_STATS_DIM (4 + HRG_INFO_DIM) /* doubles per env of hrg_replay_stats: finished episodes, sum of their returns, sum of their lengths, sums of the info
+                                                   columns of their last steps, sum of their imitation reward sums (0 without an imitation row) */
+#define HRG_REPLAY_INDEX_DIM 2 /* int64 per sample of the index input / output of hrg_replay_sample: slot, env */
+/* One replay buffer: SB3's ReplayBuffer(buffer_size, n_envs = n_envs, optimize_memory_usage = False, handle_timeout_termination = True) and the policy's view of
+ * an observation row: the selected columns, the state imitation reward's time column, DatasetObsNormWrapper's normalisation. */
+typedef struct hrg_replay_desc {
+  int32_t n_envs;
+  int32_t capacity;               /* slots; each holds one transition of every env: max(buffer_size / n_envs, 1), as SB3 computes it */
+  int32_t act_dim;                /* action values the policy emits: 7 joint space, 4 with the Cartesian front-end */
+  int32_t n_obs_cols;             /* columns of the superset in the policy's observation */
+  int32_t obs_cols[HRG_OBS_DIM];  /* column of the superset behind each value of the observation */
+  int32_t observe_time;           /* 1: one more value behind the columns, the time column of the state imitation reward; n_obs_cols + observe_time <= HRG_OBS_DIM */
+  int32_t normalize;              /* 1: value k becomes (v - mean[k]) / std[k], computed in double, rounded to float once */
+  int32_t squash;                 /* 1 (with normalize): ... tanh(squash_factor * .) before the rounding */
+  double squash_factor;
+  double mean[HRG_OBS_DIM];       /* the first n_obs_cols + observe_time entries are read */
+  double std[HRG_OBS_DIM];        /* non-zero (the wrapper maps 0 to 1) */
+  uint64_t seed;                  /* key of the sampler's draws */
+} hrg_replay_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 typedef struct hrg_her hrg_her;     /* opaque */
 typedef struct hrg_rollout hrg_rollout; /* opaque */
+typedef struct hrg_replay hrg_replay;   /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -713,6 +735,53 @@ int hrg_rollout_stats(hrg_rollout* h, double* per_env_host, int32_t clear);
 int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_host, float* rewards_host, float* values_host, float* log_probs_host,
                        float* episode_starts_host, float* advantages_host, float* returns_host, float* cur_obs_host, float* flags_host, double* run_return_host,
                        int32_t* run_length_host, double* stats_host, int64_t* state_host);
+
+/* The uniform replay buffer of SAC on the device (csrc/hrgym_replay.h): SB3's ReplayBuffer and the bookkeeping of OffPolicyAlgorithm._store_transition for a
+ * batch of envs on flat observations (training/config_icra_2024: algorithm.name SAC, run.env_type env), plus the episode sums Monitor and the imitation wrappers'
+ * _add_reward_to_info keep on the host.  Storage is time-major, [capacity][n_envs][.]; observations are stored as the policy sees them, K = n_obs_cols +
+ * observe_time floats.  The entry points take raw device pointers (the tensors a step wrote, or synthetic ones), no hrg_batch; all but create / destroy / stats /
+ * export / size are asynchronous on `stream`.  The write position, the `full` flag and the sample call counter live in the handle on the host.
+ *   hrg_replay_create   <- ReplayBuffer.__init__: allocates and zeroes everything (synchronous; nothing is allocated later).  HRG_ERR_INVALID for n_envs < 1,
+ *                          capacity < 1, n_obs_cols < 1, n_obs_cols + observe_time > HRG_OBS_DIM, a column outside 0 .. 63, act_dim outside 1 .. HRG_ACT_DIM, squash
+ *                          without normalize, a std that is zero or not finite, a mean or squash_factor that is not finite; HRG_ERR_NOMEM with the number of bytes
+ *                          asked for when the device has no room.
+ *   hrg_replay_view     the policy's view of n_rows rows of the observation superset: rows_dev float [n_rows][HRG_OBS_DIM], time_dev float [n_rows] (needed
+ *                          with observe_time, otherwise not read) -> out_dev float [n_rows][K].  rows_dev NULL: the envs' current rows and time values (SB3's
+ *                          _last_obs; n_rows is then n_envs, whatever was passed).
+ *   hrg_replay_observe  <- _last_obs = env.reset(): for envs whose mask byte is non-zero (NULL: all) the current row becomes obs_dev's, the current time value
+ *                          time_dev's (float [n_envs]; needed with observe_time), the running return and length 0.
+ *   hrg_replay_add      <- _store_transition + ReplayBuffer.add, after a step: slot `pos` of every env takes the view of the current (pre-step) row with the
+ *                          current time value; as next observation the view of term_obs_dev with sir column HRG_SIR_TIME where done_dev[e], otherwise of obs_dev
+ *                          with HRG_SIR_TIME_OBS; actions_dev float [n_envs][act_dim] as given (the agent's action at the policy's scale); reward_dev; done_dev;
+ *                          info column HRG_INFO_TRUNCATED.  Then the current row becomes obs_dev's (the row after auto-reset) and the current time value
+ *                          HRG_SIR_TIME_OBS; the running return adds the env's own reward (column HRG_SIR_R_ENV of sir_dev, HRG_IMIT_R_ENV of imit_dev, or
+ *                          reward_dev without either), the running length 1; on done the env's accumulators add 1 episode, the running return and length,
+ *                          every info column and the row's EP_IM column, and the running pair is zeroed.  imit_dev float [n_envs][HRG_IMIT_DIM] and sir_dev float
+ *                          [n_envs][HRG_SIR_DIM] may be NULL; not both given; sir_dev is needed with observe_time.  Advances pos; at capacity it wraps and the
+ *                          buffer is full.
+ *   hrg_replay_sample   <- sample + _get_samples: slot = floor(u0 * upper), upper = full ? capacity : pos, env = floor(u1 * n_envs), u = rng_u01(seed, sample call
+ *                          counter, index in the batch, 11, 0..1) -> observations float [batch_size][K], actions float [batch_size][act_dim], next_observations
+ *                          float [batch_size][K], dones float [batch_size] = done * (1 - timeout), rewards float [batch_size].  index_in_dev int64
+ *                          [batch_size][HRG_REPLAY_INDEX_DIM] (slot, env) replaces the draws when non-NULL (clamped to the stored slots; the call counter does not
+ *                          move); index_out_dev, when non-NULL, records the pairs.  HRG_ERR_INVALID for an empty buffer, batch_size < 1, a null output.
+ *   hrg_replay_stats    synchronous: per_env_host double [n_envs][HRG_REPLAY_STATS_DIM], since the last clear; clear != 0 zeroes the accumulators afterwards.
+ *   hrg_replay_export   synchronous parity hook, the arrays as stored: observations, next_observations float [capacity][n_envs][K], actions float
+ *                          [capacity][n_envs][act_dim], rewards float, dones, timeouts uint8 [capacity][n_envs], cur_obs float [n_envs][HRG_OBS_DIM], cur_time
+ *                          float [n_envs], running return double [n_envs], running length int32 [n_envs], the accumulators, state int64[3] = pos, full, sample calls.
+ *   hrg_replay_size     size_host int64[4] = pos, full, sample calls so far, bytes of device memory the buffer holds. */
+int hrg_replay_create(const hrg_replay_desc* desc, int32_t device, hrg_replay** out);
+void hrg_replay_destroy(hrg_replay* h);
+int hrg_replay_view(hrg_replay* h, const float* rows_dev, const float* time_dev, int32_t n_rows, float* out_dev, void* stream);
+int hrg_replay_observe(hrg_replay* h, const float* obs_dev, const float* time_dev, const uint8_t* mask_dev, void* stream);
+int hrg_replay_add(hrg_replay* h, const float* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
+                   const int32_t* info_dev, const float* imit_dev, const float* sir_dev, void* stream);
+int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in_dev, float* observations_dev, float* actions_dev, float* next_observations_dev,
+                      float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream);
+int hrg_replay_stats(hrg_replay* h, double* per_env_host, int32_t clear);
+int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_observations_host, float* actions_host, float* rewards_host, uint8_t* dones_host,
+                      uint8_t* timeouts_host, float* cur_obs_host, float* cur_time_host, double* run_return_host, int32_t* run_length_host, double* stats_host,
+                      int64_t* state_host);
+int hrg_replay_size(hrg_replay* h, int64_t* size_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
