@@ -115,6 +115,7 @@ DatasetDesc = _STRUCTS["hrg_dataset_desc"]
 HerDesc = _STRUCTS["hrg_her_desc"]
 RolloutDesc = _STRUCTS["hrg_rollout_desc"]
 ReplayDesc = _STRUCTS["hrg_replay_desc"]
+SacDesc = _STRUCTS["hrg_sac_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 

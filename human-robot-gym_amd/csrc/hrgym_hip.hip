@@ -3083,6 +3083,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
 #include "hrgym_rollout.h"  // the PPO rollout buffer: view / observe / add / GAE / get kernels (hrg_rollout_*)
 #include "hrgym_replay.h"   // the uniform replay buffer of SAC: view / observe / add / sample kernels (hrg_replay_*)
+#include "hrgym_sac.h"      // the SAC gradient step and the actor's forward pass: policy / critic / actor / Adam kernels (hrg_sac_*)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -4265,6 +4266,159 @@ int hrg_replay_size(hrg_replay* h, int64_t* size_host) {
   size_host[1] = h->full ? 1 : 0;
   size_host[2] = (int64_t)h->calls;
   size_host[3] = (int64_t)h->bytes;
+  return HRG_OK;
+}
+
+// ---- SAC learner (csrc/hrgym_sac.h) ----
+struct hrg_sac {
+  int device = 0;
+  hrg_sac_desc desc;
+  SacDev d;
+  uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
+  uint64_t act_calls = 0;   // act calls that drew their noise
+  size_t bytes = 0;
+  float* scratch = nullptr; // one allocation behind every pointer of `d`
+};
+
+// the offsets of the parameter layout (csrc/hrgym_sac.h) into d; returns the number of parameters
+static int32_t sac_layout(const hrg_sac_desc& c, SacDev& d) {
+  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_SAC_HIDDEN;
+  int32_t o = 0;
+  for (int l = 0; l < c.depth; l++) {
+    d.a_w[l] = o; o += H * (l ? H : K);
+    d.a_b[l] = o; o += H;
+  }
+  d.a_hw = o; o += 2 * A * H;
+  d.a_hb = o; o += 2 * A;
+  d.n_actor = o;
+  for (int q = 0; q < 2; q++) {
+    for (int l = 0; l < c.depth; l++) {
+      d.q_w[q][l] = o; o += H * (l ? H : K + A);
+      d.q_b[q][l] = o; o += H;
+    }
+    d.q_ow[q] = o; o += H;
+    d.q_ob[q] = o; o += 1;
+  }
+  d.n_critic = (o - d.n_actor) / 2;
+  d.n_params = o + 1;   // log_ent_coef
+  return d.n_params;
+}
+
+int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->hidden != HRG_SAC_HIDDEN) return fail(HRG_ERR_UNSUPPORTED, "sac: hidden = " + std::to_string(desc->hidden) + ": the kernels cover hidden width 64 only");
+  if (desc->depth < 1 || desc->depth > HRG_SAC_MAX_DEPTH) return fail(HRG_ERR_UNSUPPORTED, "sac: depth = " + std::to_string(desc->depth) + " outside 1 .. 3");
+  if (desc->obs_dim < 1 || desc->obs_dim > HRG_OBS_DIM) return fail(HRG_ERR_UNSUPPORTED, "sac: obs_dim = " + std::to_string(desc->obs_dim) + " outside 1 .. HRG_OBS_DIM");
+  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_UNSUPPORTED, "sac: act_dim = " + std::to_string(desc->act_dim) + " outside 1 .. HRG_ACT_DIM");
+  if (desc->batch_size < HRG_SAC_TILE || desc->batch_size > HRG_SAC_MAX_BATCH || desc->batch_size % HRG_SAC_TILE)
+    return fail(HRG_ERR_UNSUPPORTED, "sac: batch_size = " + std::to_string(desc->batch_size) + " is not a multiple of 32 in 32 .. 256");
+  if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
+  if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
+    return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
+  if (!desc->auto_ent_coef && desc->ent_coef <= 0.0) return fail(HRG_ERR_INVALID, "sac: a fixed ent_coef must be positive");
+  HIPCHK(hipSetDevice(device));
+  hrg_sac* h = new hrg_sac();
+  h->device = device;
+  h->desc = *desc;
+  SacDev& d = h->d;
+  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE;
+  d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
+  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
+  const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
+  const size_t n_float = B * A + 3 * B + SAC_NQ * B + 2 * B * A + (size_t)d.tiles * P + P + (size_t)d.tiles * SAC_NLOSS + 4;
+  h->bytes = n_float * sizeof(float);
+  if (hipMalloc((void**)&h->scratch, h->bytes) != hipSuccess || hipMemset(h->scratch, 0, h->bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    (void)hipGetLastError();
+    hipFree(h->scratch);
+    const size_t b = h->bytes;
+    delete h;
+    return fail(HRG_ERR_NOMEM, "sac: device allocation of " + std::to_string(b) + " bytes failed");
+  }
+  float* p = h->scratch;
+  d.a_pi = p; p += B * A;
+  d.logp = p; p += B;
+  d.logp_next = p; p += B;
+  d.y = p; p += B;
+  d.q = p; p += SAC_NQ * B;
+  d.dqda = p; p += 2 * B * A;
+  d.part = p; p += (size_t)d.tiles * P;
+  d.grad = p; p += P;
+  d.loss_part = p; p += (size_t)d.tiles * SAC_NLOSS;
+  d.losses = p;
+  *out = h;
+  return HRG_OK;
+}
+
+void hrg_sac_destroy(hrg_sac* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();
+  hipFree(h->scratch);
+  delete h;
+}
+
+int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_params;
+  size_host[1] = h->d.n_actor;
+  size_host[2] = h->d.n_critic;
+  size_host[3] = (int64_t)h->steps;
+  size_host[4] = (int64_t)h->act_calls;
+  size_host[5] = (int64_t)h->bytes;
+  return HRG_OK;
+}
+
+int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions_dev, const float* next_observations_dev, const float* dones_dev, const float* rewards_dev,
+                 const float* eps_pi_dev, const float* eps_next_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, float* target_dev, double learning_rate,
+                 void* stream) {
+  if (!h || !observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev || !params_dev || !adam_m_dev || !adam_v_dev || !target_dev)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "sac: learning_rate must be finite and not negative");
+  HIPCHK(hipSetDevice(h->device));
+  const SacDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 pair((unsigned)d.tiles, 2), block(SAC_BLOCK);
+  const double t = (double)(h->steps + 1), bc1 = 1.0 - std::pow(0.9, t), bc2 = 1.0 - std::pow(0.999, t);   // Adam's bias corrections, by the optimisers' step count
+  const bool polyak = h->steps % (uint64_t)h->desc.target_update_interval == 0;
+  const int n_crit2 = 2 * d.n_critic;
+  hipLaunchKernelGGL(hrg_sac_policy_kernel, pair, block, 0, st, d, (const float*)params_dev, (const float*)target_dev, observations_dev, next_observations_dev, dones_dev,
+                     rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
+  hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + SAC_BLOCK - 1) / SAC_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
+                     (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
+  hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
+  hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + SAC_BLOCK - 1) / SAC_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
+                     learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream) {
+  if (!h || !params_dev || !obs_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (n < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + SAC_T - 1) / SAC_T), dim3(SAC_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
+                     (int)(deterministic != 0), h->act_calls, actions_dev);
+  HIPCHK(hipGetLastError());
+  if (!deterministic && !eps_dev) h->act_calls++;
+  return HRG_OK;
+}
+
+int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const SacDev& d = h->d;
+  const size_t B = (size_t)d.B * sizeof(float);
+  if (y_host) HIPCHK(hipMemcpy(y_host, d.y, B, hipMemcpyDeviceToHost));
+  if (logp_host) HIPCHK(hipMemcpy(logp_host, d.logp, B, hipMemcpyDeviceToHost));
+  if (logp_next_host) HIPCHK(hipMemcpy(logp_next_host, d.logp_next, B, hipMemcpyDeviceToHost));
+  if (q_host) HIPCHK(hipMemcpy(q_host, d.q, SAC_NQ * B, hipMemcpyDeviceToHost));
+  if (grad_host) HIPCHK(hipMemcpy(grad_host, d.grad, (size_t)d.n_params * sizeof(float), hipMemcpyDeviceToHost));
+  if (losses_host) HIPCHK(hipMemcpy(losses_host, d.losses, 4 * sizeof(float), hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 

@@ -1,0 +1,281 @@
+"""The SAC gradient step on the device: SB3 1.5.0's `SAC.train` for `MlpPolicy` with hidden width 64 and `use_sde=False` (training/config_icra_2024/
+.../*-SAC.yaml: net_arch [64, 64, 64], batch_size 128, ent_coef auto_0.2), next to the replay buffer it reads (replay.ReplayBuffer).
+
+One gradient step is six kernel launches with no vendor BLAS and no autograd (csrc/hrgym_sac.h: the launches, the parameter layout, the draws, what differs
+from SB3).  Parameters, Adam moments and target parameters are flat float32 torch tensors; `state_dict()` hands out views under SB3's parameter names.
+
+    env = HipVecEnv(4096, env_id="ReachHuman", obs_norm=...)
+    env.attach_replay(buffer_size=1_000_000)
+    learner = env.attach_sac(batch_size=128, learning_rate=5e-4, ent_coef="auto_0.2", seed=0)
+    env.collect_steps(learner.act, 100)            # train_freq steps with the learner's actor as the policy
+    learner.train(env.replay, 400)                 # 400 x (sample, gradient step): nothing leaves the device, nothing synchronises
+    learner.diagnostics()                          # ent_coef, actor_loss, critic_loss, ent_coef_loss of the last step (synchronous)
+"""
+import ctypes
+import math
+from collections import OrderedDict
+
+import numpy as np
+
+from ._cstruct import CONST, SacDesc
+
+HIDDEN = CONST["HRG_SAC_HIDDEN"]
+MAX_DEPTH = CONST["HRG_SAC_MAX_DEPTH"]
+TILE = CONST["HRG_SAC_TILE"]
+MAX_BATCH = CONST["HRG_SAC_MAX_BATCH"]
+NQ = CONST["HRG_SAC_NQ"]
+Q_COLUMNS = ("q1", "q2", "q1_target", "q2_target", "q1_pi", "q2_pi")   # the rows of hrg_sac_export's q, in its order
+
+
+def depth_of(net_arch):
+    """Hidden layers of `net_arch`; NotImplementedError for what the kernels do not cover."""
+    if isinstance(net_arch, dict):
+        raise NotImplementedError(f"net_arch = {net_arch}: separate actor and critic architectures are not supported (a list of hidden widths)")
+    arch = [int(w) for w in net_arch]
+    if not 1 <= len(arch) <= MAX_DEPTH or any(w != HIDDEN for w in arch):
+        raise NotImplementedError(f"net_arch = {arch}: the kernels cover hidden width {HIDDEN} and depth 1 .. {MAX_DEPTH} (the ICRA configs' [64, 64, 64])")
+    return len(arch)
+
+
+def parse_ent_coef(ent_coef):
+    """SB3's ent_coef: "auto" (learned, from 1), "auto_<x>" (learned, from x) or a float (fixed) -> (learned, initial or fixed value)."""
+    if isinstance(ent_coef, str):
+        if not ent_coef.startswith("auto"):
+            raise ValueError(f"ent_coef = {ent_coef!r}: 'auto', 'auto_<initial value>' or a float")
+        init = float(ent_coef.split("_")[1]) if "_" in ent_coef else 1.0
+        if not init > 0.0:
+            raise ValueError("ent_coef: the initial value of the entropy coefficient must be greater than 0")
+        return True, init
+    value = float(ent_coef)
+    if not value > 0.0 or not math.isfinite(value):
+        raise ValueError(f"ent_coef = {ent_coef}: a fixed entropy coefficient must be positive and finite")
+    return False, value
+
+
+def build_sac_desc(obs_dim, act_dim, net_arch=(64, 64, 64), gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto", batch_size=256,
+                   target_update_interval=1, seed=0):
+    """hrg_sac_desc (include/hrgym.h).  Everything the kernels do not cover is refused here, before anything is allocated or launched."""
+    depth = depth_of(net_arch)
+    obs_dim, act_dim, batch_size = int(obs_dim), int(act_dim), int(batch_size)
+    if not 1 <= obs_dim <= CONST["HRG_OBS_DIM"]:
+        raise NotImplementedError(f"obs_dim = {obs_dim}: the kernels cover observations of 1 .. {CONST['HRG_OBS_DIM']} values")
+    if not 1 <= act_dim <= CONST["HRG_ACT_DIM"]:
+        raise NotImplementedError(f"act_dim = {act_dim}: the kernels cover actions of 1 .. {CONST['HRG_ACT_DIM']} values")
+    if batch_size % TILE or not TILE <= batch_size <= MAX_BATCH:
+        raise NotImplementedError(f"batch_size = {batch_size}: the kernels cover multiples of {TILE} from {TILE} to {MAX_BATCH}")
+    if int(target_update_interval) < 1:
+        raise ValueError(f"target_update_interval = {target_update_interval} must be positive")
+    learned, value = parse_ent_coef(ent_coef)
+    d = SacDesc()
+    d.obs_dim, d.act_dim, d.depth, d.hidden, d.batch_size = obs_dim, act_dim, depth, HIDDEN, batch_size
+    d.auto_ent_coef, d.target_update_interval = int(learned), int(target_update_interval)
+    d.gamma, d.tau, d.ent_coef = float(gamma), float(tau), value
+    d.target_entropy = -float(act_dim) if isinstance(target_entropy, str) and target_entropy == "auto" else float(target_entropy)   # -prod(action_space.shape)
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return d
+
+
+def param_layout(obs_dim, act_dim, depth):
+    """The flat parameter vector (csrc/hrgym_sac.h): OrderedDict name -> (offset, shape) under SB3 1.5.0's names ([UPSTREAM]: from knowledge of that release),
+    actor | critic.qf0 | critic.qf1 | log_ent_coef, and (n_params, n_actor, n_critic).  The targets are the two critics' entries as `critic_target.*`, offsets
+    less n_actor, in a vector of their own."""
+    K, A, H = int(obs_dim), int(act_dim), HIDDEN
+    out, o = OrderedDict(), 0
+
+    def put(name, shape):
+        nonlocal o
+        out[name] = (o, shape)
+        o += int(np.prod(shape))
+
+    for l in range(depth):
+        put(f"actor.latent_pi.{2 * l}.weight", (H, H if l else K))
+        put(f"actor.latent_pi.{2 * l}.bias", (H,))
+    put("actor.mu.weight", (A, H))
+    put("actor.log_std.weight", (A, H))
+    put("actor.mu.bias", (A,))
+    put("actor.log_std.bias", (A,))
+    n_actor = o
+    for q in range(2):
+        for l in range(depth):
+            put(f"critic.qf{q}.{2 * l}.weight", (H, H if l else K + A))
+            put(f"critic.qf{q}.{2 * l}.bias", (H,))
+        put(f"critic.qf{q}.{2 * depth}.weight", (1, H))
+        put(f"critic.qf{q}.{2 * depth}.bias", (1,))
+    n_critic = (o - n_actor) // 2
+    put("log_ent_coef", (1,))
+    return out, (o, n_actor, n_critic)
+
+
+class SacParams:
+    """The learner's tensors, on any torch device: `params`, `adam_m`, `adam_v` float32 [n_params] and `target` float32 [2 n_critic], with `state_dict()`
+    views under SB3's names.  Initial weights: torch.nn.Linear's own initialisation under a generator seeded with `seed` (actor, mu, log_std, qf0, qf1, in
+    that order); the targets start as copies; log_ent_coef = log(`ent_coef_init`)."""
+
+    def __init__(self, obs_dim, act_dim, depth, seed=0, ent_coef_init=1.0, device="cpu"):
+        import torch
+        self.torch = torch
+        self.obs_dim, self.act_dim, self.depth = int(obs_dim), int(act_dim), int(depth)
+        self.layout, (self.n_params, self.n_actor, self.n_critic) = param_layout(obs_dim, act_dim, depth)
+        flat = torch.zeros(self.n_params, dtype=torch.float32)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(int(seed))
+            for name, (off, shape) in self.layout.items():   # a Linear per weight entry; its bias is the entry that follows (or, for the heads, follows the pair)
+                if not name.endswith(".weight"):
+                    continue
+                lin = torch.nn.Linear(shape[1], shape[0])
+                flat[off:off + lin.weight.numel()] = lin.weight.detach().reshape(-1)
+                boff, _ = self.layout[name[:-len("weight")] + "bias"]
+                flat[boff:boff + shape[0]] = lin.bias.detach()
+        flat[-1] = math.log(float(ent_coef_init))
+        self.params = flat.to(device)
+        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.target = self.params[self.n_actor:self.n_actor + 2 * self.n_critic].clone()
+
+    def state_dict(self):
+        """OrderedDict of views into `params` and `target` under SB3's names (writing into one writes the learner's parameter)."""
+        out = OrderedDict()
+        for name, (off, shape) in self.layout.items():
+            out[name] = self.params[off:off + int(np.prod(shape))].view(shape)
+        for name, (off, shape) in self.layout.items():
+            if name.startswith("critic."):
+                o = off - self.n_actor
+                out["critic_target." + name[len("critic."):]] = self.target[o:o + int(np.prod(shape))].view(shape)
+        return out
+
+    def load_state_dict(self, state):
+        """Copies every entry of `state` (tensors or arrays of the entries' shapes, every name of `state_dict()` present) into the learner's tensors."""
+        t = self.torch
+        own = self.state_dict()
+        missing, unknown = sorted(set(own) - set(state)), sorted(set(state) - set(own))
+        if missing or unknown:
+            raise KeyError(f"load_state_dict: missing {missing}, unknown {unknown}")
+        with t.no_grad():
+            for name, view in own.items():
+                src = t.as_tensor(state[name])
+                if tuple(src.shape) != tuple(view.shape):
+                    raise ValueError(f"load_state_dict: {name} has shape {tuple(src.shape)}, expected {tuple(view.shape)}")
+                view.copy_(src.to(device=view.device, dtype=view.dtype))
+
+    def group(self, flat, which):
+        """The slice of a parameter-shaped vector that belongs to "actor", "qf0", "qf1" or "log_ent_coef"."""
+        a, c = self.n_actor, self.n_critic
+        lo, hi = dict(actor=(0, a), qf0=(a, a + c), qf1=(a + c, a + 2 * c), log_ent_coef=(a + 2 * c, a + 2 * c + 1))[which]
+        return flat[lo:hi]
+
+
+class SacLearner:
+    """SB3's SAC on the device for the shapes the kernels cover (`build_sac_desc` refuses the rest).  `learning_rate` is a plain attribute, passed with every
+    step: a caller may schedule it.  All tensor arguments and results live on the learner's device; `step`, `train` and `act` are asynchronous, ordered on
+    torch's current stream; `diagnostics` and `export` synchronise."""
+
+    def __init__(self, obs_dim, act_dim, net_arch=(64, 64, 64), learning_rate=3e-4, gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto",
+                 batch_size=256, target_update_interval=1, seed=0, device=0):
+        self.desc = build_sac_desc(obs_dim, act_dim, net_arch=net_arch, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy,
+                                   batch_size=batch_size, target_update_interval=target_update_interval, seed=seed)
+        import torch
+        from ._lib import _check, load_library
+        if not torch.cuda.is_available():
+            raise RuntimeError("SacLearner needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
+        self.torch, self.lib, self._check = torch, load_library(), _check
+        self.device = torch.device("cuda", device)
+        self.obs_dim, self.act_dim, self.depth, self.batch_size = int(obs_dim), int(act_dim), int(self.desc.depth), int(batch_size)
+        self.learning_rate = float(learning_rate)
+        self.auto_ent_coef = bool(self.desc.auto_ent_coef)
+        self.p = SacParams(obs_dim, act_dim, self.depth, seed=seed, ent_coef_init=self.desc.ent_coef, device=self.device)
+        self.h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _check(self.lib, self.lib.hrg_sac_create(ctypes.byref(self.desc), device, ctypes.byref(self.h)))
+        sizes = self._sizes()
+        if sizes[:3] != [self.p.n_params, self.p.n_actor, self.p.n_critic]:
+            raise RuntimeError(f"SacLearner: the library lays out {sizes[:3]} parameters, sac.param_layout {[self.p.n_params, self.p.n_actor, self.p.n_critic]}: rebuild")
+        self._keep = None
+
+    def _sizes(self):
+        w = (ctypes.c_int64 * 6)()
+        self._check(self.lib, self.lib.hrg_sac_sizes(self.h, w))
+        return [int(x) for x in w]
+
+    @property
+    def n_updates(self):
+        """Gradient steps so far (SB3's _n_updates)."""
+        return self._sizes()[3]
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _tensor(self, x, shape, what):
+        t = self.torch
+        if x.dtype != t.float32 or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
+            raise ValueError(f"{what}: expected a contiguous float32 tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        return ctypes.c_void_p(x.data_ptr())
+
+    def step(self, batch, eps_pi=None, eps_next=None):
+        """One gradient step on `batch`, a ReplayBufferSamples of `batch_size` rows (observations, next_observations [B, obs_dim], actions [B, act_dim], dones,
+        rewards [B, 1]).  `eps_pi` / `eps_next` float32 [B, act_dim]: the standard normal noise of the actor on the observations / the next observations, instead
+        of the learner's own draws (tests)."""
+        B, K, A, p = self.batch_size, self.obs_dim, self.act_dim, self.p
+        args = (self._tensor(batch.observations, (B, K), "observations"), self._tensor(batch.actions, (B, A), "actions"),
+                self._tensor(batch.next_observations, (B, K), "next_observations"), self._tensor(batch.dones, (B, 1), "dones"),
+                self._tensor(batch.rewards, (B, 1), "rewards"), None if eps_pi is None else self._tensor(eps_pi, (B, A), "eps_pi"),
+                None if eps_next is None else self._tensor(eps_next, (B, A), "eps_next"))
+        ptr = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib, self.lib.hrg_sac_step(self.h, *args, ptr(p.params), ptr(p.adam_m), ptr(p.adam_v), ptr(p.target), float(self.learning_rate), self._stream()))
+        self._keep = (batch, eps_pi, eps_next)
+
+    def train(self, replay, gradient_steps):
+        """SAC.train(gradient_steps, batch_size): `gradient_steps` x (replay.sample(batch_size), step), with no copy to the host and no synchronisation."""
+        if (int(replay.obs_dim), int(replay.act_dim)) != (self.obs_dim, self.act_dim):
+            raise ValueError(f"train: the buffer holds observations of {replay.obs_dim} and actions of {replay.act_dim} values, the learner takes {self.obs_dim} and {self.act_dim}")
+        for _ in range(int(gradient_steps)):
+            self.step(replay.sample(self.batch_size))
+
+    def act(self, obs, deterministic=False, eps=None):
+        """The actor's actions for `obs` float32 [n, obs_dim]: float32 [n, act_dim] in (-1, 1), tanh(mu + std eps), or tanh(mu) with `deterministic`.  This is the
+        `policy` HipVecEnv.collect_steps takes.  `eps` float32 [n, act_dim] replaces the draws (tests)."""
+        t = self.torch
+        if obs.dim() != 2:
+            raise ValueError(f"obs: expected [n, {self.obs_dim}], got {tuple(obs.shape)}")
+        n = int(obs.shape[0])
+        o = self._tensor(obs, (n, self.obs_dim), "obs")
+        e = None if eps is None else self._tensor(eps, (n, self.act_dim), "eps")
+        out = t.empty(n, self.act_dim, dtype=t.float32, device=self.device)
+        with t.cuda.device(self.device):
+            self._check(self.lib, self.lib.hrg_sac_act(self.h, ctypes.c_void_p(self.p.params.data_ptr()), o, n, e, int(bool(deterministic)),
+                                                       ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def state_dict(self):
+        """Views of the parameters under SB3's names (SacParams.state_dict): actor.latent_pi.{0,2,4}.*, actor.mu.*, actor.log_std.*, critic.qf{0,1}.{0,2,4,6}.*,
+        critic_target.qf{0,1}.*, log_ent_coef; torch's [out, in] weight layout."""
+        return self.p.state_dict()
+
+    def load_state_dict(self, state):
+        self.p.load_state_dict(state)
+
+    def export(self):
+        """The last step's intermediates on the host (synchronous; tests): y, logp, logp_next [B]; q [6, B] (Q_COLUMNS); grad [n_params] in the parameters'
+        layout (`self.p.group(grad, "actor")`, ...; the last entry is the coefficient's gradient); losses [4]."""
+        B = self.batch_size
+        y, logp, logp_next, q = (np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros((NQ, B), np.float32))
+        grad, losses = np.zeros(self.p.n_params, np.float32), np.zeros(4, np.float32)
+        self._check(self.lib, self.lib.hrg_sac_export(self.h, *(a.ctypes.data_as(ctypes.c_void_p) for a in (y, logp, logp_next, q, grad, losses))))
+        return dict(y=y, logp=logp, logp_next=logp_next, q=q, grad=grad, losses=losses)
+
+    def diagnostics(self):
+        """What SB3 logs under train/ after a call of train(): ent_coef (the one the last step used), actor_loss, critic_loss, ent_coef_loss of the last step, and
+        n_updates.  Synchronous."""
+        losses = np.zeros(4, np.float32)
+        self._check(self.lib, self.lib.hrg_sac_export(self.h, None, None, None, None, None, losses.ctypes.data_as(ctypes.c_void_p)))
+        return dict(ent_coef=float(losses[3]), actor_loss=float(losses[0]), critic_loss=float(losses[1]), ent_coef_loss=float(losses[2]), n_updates=self.n_updates)
+
+    def close(self):
+        if getattr(self, "h", None) and self.h.value:
+            self.lib.hrg_sac_destroy(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

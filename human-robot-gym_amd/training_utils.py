@@ -206,6 +206,38 @@ def replay_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
     return kw
 
 
+def sac_kwargs_from_config(config) -> Dict[str, Any]:
+    """`config.algorithm` of a SAC run (training/config_icra_2024/.../*-SAC.yaml) -> the keyword arguments of HipVecEnv.attach_sac / sac.SacLearner:
+    net_arch, learning_rate, gamma, tau, ent_coef, target_entropy, batch_size, target_update_interval, seed (missing keys take SB3's SAC defaults).
+    What the kernels do not cover is refused by the name of its key: use_sde, action_noise, policy, policy_kwargs.net_arch.  train_freq, gradient_steps,
+    learning_starts and buffer_size belong to the loop and the buffer (tools/train_sac.py, replay_kwargs_from_config), not to the learner."""
+    alg = _get(config, "algorithm")
+    if str(_get(alg, "name", "SAC")).upper() != "SAC":
+        raise NotImplementedError(f"algorithm.name = {_get(alg, 'name')}: the device learner is SAC")
+    if _get(alg, "policy", "MlpPolicy") != "MlpPolicy":
+        raise NotImplementedError(f"algorithm.policy = {_get(alg, 'policy')}: the device learner covers MlpPolicy")
+    if _get(alg, "use_sde", False):
+        raise NotImplementedError("algorithm.use_sde = true: state dependent exploration is not covered by the device learner")
+    if _get(alg, "action_noise") is not None:
+        raise NotImplementedError("algorithm.action_noise: the device learner adds no action noise")
+    from .sac import depth_of
+    pk = _plain(_get(alg, "policy_kwargs")) or {}
+    net_arch = pk.get("net_arch", [256, 256])   # SB3's default for SAC
+    try:
+        depth_of(net_arch)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"algorithm.policy_kwargs.net_arch: {e}") from None
+    unknown = sorted(set(pk) - {"net_arch"})
+    if unknown:
+        raise NotImplementedError(f"algorithm.policy_kwargs {unknown}: the device learner takes net_arch")
+    kw: Dict[str, Any] = dict(net_arch=[int(w) for w in net_arch], learning_rate=float(_get(alg, "learning_rate", 3e-4)), gamma=float(_get(alg, "gamma", 0.99)),
+                              tau=float(_get(alg, "tau", 0.005)), ent_coef=_get(alg, "ent_coef", "auto"), target_entropy=_get(alg, "target_entropy", "auto"),
+                              batch_size=int(_get(alg, "batch_size", 256)), target_update_interval=int(_get(alg, "target_update_interval", 1)))
+    if _get(alg, "seed") is not None:
+        kw["seed"] = int(_get(alg, "seed"))
+    return kw
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""

@@ -548,6 +548,7 @@ class HipVecEnv(_VecEnvBase):
         self._last_full = None
         self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
         self._replay_args = None     # arguments of attach_replay, likewise
+        self.sac = None              # the SAC learner (sac.SacLearner), once attached
         self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
 
     def _init_obs_norm(self, obs_norm=None):
@@ -734,6 +735,9 @@ class HipVecEnv(_VecEnvBase):
         if self._monitor is not None:
             self._monitor.close()
             self._monitor = None
+        if self.sac is not None:
+            self.sac.close()
+            self.sac = None
         self._backend.close()
 
     def seed(self, seed=None):
@@ -1037,6 +1041,20 @@ class HipVecEnv(_VecEnvBase):
     def replay(self):
         """The attached replay buffer (attach_replay), or None."""
         return getattr(self._backend, "replay", None)
+
+    def attach_sac(self, **kwargs):
+        """The SAC learner on the device next to the replay buffer (sac.SacLearner; its keywords: net_arch, learning_rate, gamma, tau, ent_coef,
+        target_entropy, batch_size, target_update_interval, seed).  Needs attach_replay first: `obs_dim` and `act_dim` are the buffer's.  Returns the learner
+        and keeps it as `env.sac`: `env.collect_steps(env.sac.act, train_freq)`, then `env.sac.train(env.replay, gradient_steps)`."""
+        rb = self.replay
+        if rb is None:
+            raise NotImplementedError("attach_sac: call attach_replay(buffer_size) first (the learner takes its observation and action widths from the buffer)")
+        from .sac import SacLearner
+        kwargs.setdefault("seed", int(self._desc.seed))
+        if self.sac is not None:
+            self.sac.close()
+        self.sac = SacLearner(rb.obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
+        return self.sac
 
     def collect_steps(self, policy, n_steps):
         """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`.  `policy(obs float32 [n, K]) ->

@@ -511,10 +511,34 @@ typedef struct hrg_replay_desc {
   uint64_t seed;                  /* key of the sampler's draws */
 } hrg_replay_desc;
 
+/* ------------------------------------------------------------------------- the SAC learner on the device (POD) */
+#define HRG_SAC_HIDDEN 64     /* hidden width the kernels cover (net_arch [64] * depth) */
+#define HRG_SAC_MAX_DEPTH 3   /* hidden layers: 1 .. 3 */
+#define HRG_SAC_TILE 32       /* rows of the batch per workgroup: batch_size is a multiple */
+#define HRG_SAC_MAX_BATCH 256
+#define HRG_SAC_NQ 6          /* Q columns of hrg_sac_export: Q1, Q2 on (obs, act); the targets' Q1, Q2 on (next_obs, a'); the updated Q1, Q2 on (obs, a_pi) */
+/* One learner: SB3 1.5.0's SAC(MlpPolicy, net_arch = [64] * depth, use_sde = False).  The learning rate is an argument of hrg_sac_step. */
+typedef struct hrg_sac_desc {
+  int32_t obs_dim;                /* 1 .. HRG_OBS_DIM */
+  int32_t act_dim;                /* 1 .. HRG_ACT_DIM */
+  int32_t depth;                  /* hidden layers, 1 .. HRG_SAC_MAX_DEPTH */
+  int32_t hidden;                 /* HRG_SAC_HIDDEN */
+  int32_t batch_size;             /* a multiple of HRG_SAC_TILE, HRG_SAC_TILE .. HRG_SAC_MAX_BATCH */
+  int32_t auto_ent_coef;          /* 1: the entropy coefficient is learned ("auto", "auto_<x>") */
+  int32_t target_update_interval; /* the targets move after gradient step s (counted from 0) when s % target_update_interval == 0 */
+  int32_t reserved_;
+  double gamma;
+  double tau;
+  double ent_coef;                /* the fixed coefficient (auto_ent_coef = 0); the learned one starts from the log_ent_coef entry of the parameters */
+  double target_entropy;
+  uint64_t seed;                  /* key of the noise draws */
+} hrg_sac_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 typedef struct hrg_her hrg_her;     /* opaque */
 typedef struct hrg_rollout hrg_rollout; /* opaque */
 typedef struct hrg_replay hrg_replay;   /* opaque */
+typedef struct hrg_sac hrg_sac;         /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -782,6 +806,31 @@ int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_obser
                       uint8_t* timeouts_host, float* cur_obs_host, float* cur_time_host, double* run_return_host, int32_t* run_length_host, double* stats_host,
                       int64_t* state_host);
 int hrg_replay_size(hrg_replay* h, int64_t* size_host);
+
+/* The SAC learner on the device (csrc/hrgym_sac.h): one gradient step of SB3 1.5.0's SAC.train (use_sde = False) in six launches on one stream, and the actor's
+ * forward pass.  Parameters, Adam moments and target parameters are flat float32 device arrays of the caller's (layout: csrc/hrgym_sac.h; sizes: hrg_sac_sizes);
+ * the handle owns the descriptor, the counters and the scratch.  Every entry selects the handle's device; hrg_sac_step and hrg_sac_act are asynchronous on `stream`.
+ *   hrg_sac_create   checks the descriptor before anything is launched or allocated: HRG_ERR_UNSUPPORTED for a hidden width other than HRG_SAC_HIDDEN, a depth
+ *                    outside 1 .. HRG_SAC_MAX_DEPTH, obs_dim outside 1 .. HRG_OBS_DIM, act_dim outside 1 .. HRG_ACT_DIM, a batch_size that is not a multiple of
+ *                    HRG_SAC_TILE in HRG_SAC_TILE .. HRG_SAC_MAX_BATCH; HRG_ERR_INVALID for target_update_interval < 1 or values that are not finite.
+ *   hrg_sac_sizes    size_host int64[6] = parameters in all (actor | critic 0 | critic 1 | log_ent_coef), of the actor, of one critic, gradient steps so far,
+ *                    act calls that drew their noise, bytes of device memory held.
+ *   hrg_sac_step     one gradient step on a batch of batch_size rows (the outputs of hrg_replay_sample): observations, next_observations float [B][obs_dim],
+ *                    actions float [B][act_dim], dones, rewards float [B].  eps_pi_dev / eps_next_dev float [B][act_dim], when non-NULL, replace the draws.
+ *                    params_dev, adam_m_dev, adam_v_dev float [n_params], target_dev float [2 n_critic] are updated in place.
+ *   hrg_sac_act      actions_dev float [n][act_dim] = tanh(mu + std eps) of the actor on obs_dev float [n][obs_dim]; deterministic != 0: tanh(mu).  eps_dev float
+ *                    [n][act_dim] replaces the draws when non-NULL (the call counter then does not move).
+ *   hrg_sac_export   synchronous parity hook, the last step's intermediates on the host: y, logp, logp_next float [B], q float [HRG_SAC_NQ][B], grad float
+ *                    [n_params] (the parameters' layout; the last entry is the coefficient's gradient, 0 when it is fixed), losses float [4] = actor_loss,
+ *                    critic_loss, ent_coef_loss, the ent_coef the step used.  Any pointer may be NULL. */
+int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out);
+void hrg_sac_destroy(hrg_sac* h);
+int hrg_sac_sizes(hrg_sac* h, int64_t* size_host);
+int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions_dev, const float* next_observations_dev, const float* dones_dev, const float* rewards_dev,
+                 const float* eps_pi_dev, const float* eps_next_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, float* target_dev, double learning_rate,
+                 void* stream);
+int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream);
+int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */
