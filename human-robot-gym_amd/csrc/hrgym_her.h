@@ -1,6 +1,6 @@
 // hrgym_her.h -- hindsight experience replay on the device: the replay buffer of SAC + HER (SB3's HerReplayBuffer with the reference's patches,
 // wrappers/HER_buffer_add_monkey_patch.py) for a batch of goal envs, in four small kernels next to the (unchanged) step launch.  Included into the base
-// translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_dataset.h.
+// translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_buffer.h (the policy's view of a row, the grid of the one-wavefront-per-sample kernels).
 //
 //   hrg_her_add_kernel           custom_add (26-117) for every env: one transition into the env's ring, episode bookkeeping.  One wavefront per env, lane l
 //                                moves column l of each 256-byte observation row.
@@ -19,7 +19,6 @@
 #pragma once
 
 enum { STREAM_HER = 10 };   // after STREAM_DATASET = 9 (hrgym_dataset.h)
-#define HRG_HER_BLOCK 256
 
 // the buffers of one hrg_her; passed to the kernels by value
 struct HerDev {
@@ -36,7 +35,7 @@ struct HerDev {
   int64_t* tail = nullptr;     // [n]
   int64_t* open = nullptr;     // [n]
   float* cur_obs = nullptr;    // [n][HRG_OBS_DIM] the row the next transition starts from
-  const int32_t* obs_cols = nullptr;   // [HRG_OBS_DIM] hrg_her_desc::obs_cols (a per-lane lookup: device memory, not a kernel argument)
+  BufferView view;             // hrg_her_desc::obs_cols (the view is a plain selection: no time column, no normalisation)
 };
 
 // columns of the observation superset behind the goals (vec_env.HipVecEnv._init_columns)
@@ -72,10 +71,10 @@ DI void goal_reward_done(const hrg_her_desc& p, const double* ag, const double* 
   *done = (p.done_at_collision != 0 && illegal) || (p.done_at_success != 0 && dist <= p.goal_dist);
 }
 
-__global__ __launch_bounds__(HRG_HER_BLOCK) void hrg_goal_reward_done_kernel(const hrg_her_desc p, const float* __restrict__ ag, const float* __restrict__ dg,
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_goal_reward_done_kernel(const hrg_her_desc p, const float* __restrict__ ag, const float* __restrict__ dg,
                                                                              const int32_t* __restrict__ ctype, int n, float* __restrict__ reward,
                                                                              uint8_t* __restrict__ done) {
-  const int i = (int)(blockIdx.x * HRG_HER_BLOCK + threadIdx.x);
+  const int i = (int)(blockIdx.x * HRG_BUFFER_BLOCK + threadIdx.x);
   if (i >= n) return;
   const int na = her_ag_dim(p.goal_kind), ng = her_dg_dim(p.goal_kind);
   double a[7], g[6];
@@ -152,13 +151,13 @@ __global__ __launch_bounds__(64) void hrg_her_observe_kernel(const hrg_her_desc 
 }
 
 // grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  `cum`: [n_envs + 1] exclusive prefix sums of the envs' closed transitions.
-__global__ __launch_bounds__(HRG_HER_BLOCK) void hrg_her_sample_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call, int batch,
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_sample_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call, int batch,
                                                                        float* __restrict__ o_obs, float* __restrict__ o_ag, float* __restrict__ o_dg,
                                                                        float* __restrict__ o_nobs, float* __restrict__ o_nag, float* __restrict__ o_ndg,
                                                                        float* __restrict__ o_act, float* __restrict__ o_rew, float* __restrict__ o_done,
                                                                        int64_t* __restrict__ o_idx) {
   const int lane = (int)(threadIdx.x & 63);
-  const int k = (int)(blockIdx.x * (HRG_HER_BLOCK / 64) + (threadIdx.x >> 6));
+  const int k = buffer_wave_item();
   if (k >= batch) return;
   const int64_t N = cum[p.n_envs];
   if (N <= 0) return;   // (the host refuses the call)
@@ -199,8 +198,7 @@ __global__ __launch_bounds__(HRG_HER_BLOCK) void hrg_her_sample_kernel(const hrg
   }
   // the policy's view of both rows
   {   // value `lane` of the observation entry (n_obs_cols <= 64); every lane takes part in the shuffles
-    const int col = h.obs_cols[lane];   // (entries past n_obs_cols are zero)
-    float v0 = __shfl(pre, col), v1 = __shfl(post, col);
+    float v0 = view_select(h.view, pre, lane), v1 = view_select(h.view, post, lane);   // (entries past n_obs_cols are zero)
     if (relabel && p.relabel_observation) {   // (wave-uniform)
 #pragma unroll
       for (int d = 0; d < 6; d++) {

@@ -3080,9 +3080,10 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #if HRG_BASE_TU
 #include "hrgym_expert.h"   // the scripted experts + imitation reward kernels (hrg_batch_expert_*, hrg_batch_step_imitation)
 #include "hrgym_dataset.h"  // demonstration datasets: restore + state imitation reward kernels (hrg_batch_dataset_*, hrg_batch_step_dataset)
+#include "hrgym_buffer.h"   // what the three buffers below share: the policy's view of a row, the episode tracker, the grid of a wavefront per row
 #include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
-#include "hrgym_rollout.h"  // the PPO rollout buffer: view / observe / add / GAE / get kernels (hrg_rollout_*)
-#include "hrgym_replay.h"   // the uniform replay buffer of SAC: view / observe / add / sample kernels (hrg_replay_*)
+#include "hrgym_rollout.h"  // the PPO rollout buffer: observe / add / GAE / get kernels (hrg_rollout_*)
+#include "hrgym_replay.h"   // the uniform replay buffer of SAC: observe / add / sample kernels (hrg_replay_*)
 #include "hrgym_sac.h"      // the SAC gradient step and the actor's forward pass: policy / critic / actor / Adam kernels (hrg_sac_*)
 
 // ================================================================================================ host side
@@ -3210,6 +3211,93 @@ static void mat_from_quat(double* M, const double* q) {
   M[0] = 1 - 2 * (y * y + z * z); M[1] = 2 * (x * y - w * z); M[2] = 2 * (x * z + w * y);
   M[3] = 2 * (x * y + w * z); M[4] = 1 - 2 * (x * x + z * z); M[5] = 2 * (y * z - w * x);
   M[6] = 2 * (x * z - w * y); M[7] = 2 * (y * z + w * x); M[8] = 1 - 2 * (x * x + y * y);
+}
+
+// ---- what the handles of the training buffers and the learner share (csrc/hrgym_buffer.h) ----
+// every device allocation of one handle: zeroed, counted, freed together
+struct DeviceMem {
+  std::vector<void*> ptrs;
+  size_t bytes = 0;    // device memory held
+  size_t failed = 0;   // the request the device refused
+  DeviceMem() = default;
+  DeviceMem(const DeviceMem&) = delete;
+  DeviceMem& operator=(const DeviceMem&) = delete;
+  ~DeviceMem() {
+    for (void* p : ptrs) hipFree(p);
+  }
+  // `count` zeroed values behind `out`; false where the device refuses (HIP's sticky error is cleared, `failed` is the request)
+  template <class T> bool zeros(T*& out, size_t count) {
+    const size_t b = count * sizeof(T);
+    void* p = nullptr;
+    if (hipMalloc(&p, b) != hipSuccess) p = nullptr;
+    if (p) ptrs.push_back(p);
+    if (!p || hipMemset(p, 0, b) != hipSuccess) {
+      (void)hipGetLastError();
+      failed = b;
+      return false;
+    }
+    bytes += b;
+    out = (T*)p;
+    return true;
+  }
+};
+
+static int nomem(const char* name, const DeviceMem& mem) {
+  return fail(HRG_ERR_NOMEM, std::string(name) + ": device allocation of " + std::to_string(mem.failed) + " bytes failed");
+}
+
+// hrg_*_destroy of a handle with `device` (its DeviceMem member frees what it holds)
+template <class H> static void destroy_handle(H* h) {
+  if (!h) return;
+  hipSetDevice(h->device);
+  hipDeviceSynchronize();
+  delete h;
+}
+
+// What every buffer checks of its observation columns and action width, and the column table on the current device: obs_cols, zero behind n_obs_cols (a per-lane
+// lookup).  `name`: the buffer's message prefix; observe_time: the descriptor's switch, null for a buffer without a time column.
+static int buffer_columns(const char* name, int32_t n_obs_cols, const int32_t* obs_cols, const int32_t* observe_time, int32_t act_dim, DeviceMem& mem,
+                          const int32_t*& table) {
+  const std::string pre = std::string(name) + ": ";
+  if (n_obs_cols < 1 || n_obs_cols + (observe_time && *observe_time ? 1 : 0) > HRG_OBS_DIM)
+    return fail(HRG_ERR_INVALID, pre + (observe_time ? "n_obs_cols (+ 1 with observe_time) must lie in [1, HRG_OBS_DIM]" : "n_obs_cols must lie in [1, HRG_OBS_DIM]"));
+  int32_t cols[HRG_OBS_DIM] = {0};
+  for (int c = 0; c < n_obs_cols; c++) {
+    if (obs_cols[c] < 0 || obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, pre + "an observation column outside the superset");
+    cols[c] = obs_cols[c];
+  }
+  if (act_dim < 1 || act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, pre + "act_dim must lie in [1, HRG_ACT_DIM]");
+  int32_t* dev = nullptr;
+  if (!mem.zeros(dev, HRG_OBS_DIM)) return nomem(name, mem);
+  if (hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess) return fail(HRG_ERR_HIP, pre + "upload failed");
+  table = dev;
+  return HRG_OK;
+}
+
+// hrg_*_stats: the tracker's sums [n_envs][cols] to the host, cleared on the device on request
+static int buffer_stats(int device, double* acc_dev, int32_t n_envs, int cols, double* per_env_host, int32_t clear) {
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipDeviceSynchronize());
+  const size_t bytes = sizeof(double) * (size_t)cols * (size_t)n_envs;
+  HIPCHK(hipMemcpy(per_env_host, acc_dev, bytes, hipMemcpyDeviceToHost));
+  if (clear) {
+    HIPCHK(hipMemset(acc_dev, 0, bytes));
+    HIPCHK(hipDeviceSynchronize());
+  }
+  return HRG_OK;
+}
+
+// the two grids of the buffer kernels: a wavefront per env, and blocks of four wavefronts with one of `n` rows, samples or indices each
+template <class K, class... A> static int launch_per_env(K kernel, int32_t n_envs, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_envs), dim3(64), 0, (hipStream_t)stream, args...);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+template <class K, class... A> static int launch_per_wave(K kernel, int32_t n, void* stream, A... args) {
+  const unsigned per = HRG_BUFFER_BLOCK / 64;
+  hipLaunchKernelGGL(kernel, dim3(((unsigned)n + per - 1) / per), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, args...);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
 }
 
 extern "C" {
@@ -3711,17 +3799,13 @@ struct hrg_her {
   int device = 0;
   hrg_her_desc desc;
   HerDev d;
+  DeviceMem mem;                // behind every pointer of `d`
   int64_t* d_total = nullptr;   // pinned host word the sampler's total is read back into
   uint64_t calls = 0;           // sample calls so far (key of the draws)
+  ~hrg_her() {
+    if (d_total) hipHostFree(d_total);
+  }
 };
-
-static void her_free(hrg_her* h) {
-  HerDev& d = h->d;
-  hipFree(d.pre); hipFree(d.post); hipFree(d.act); hipFree(d.reward); hipFree(d.done); hipFree(d.trunc); hipFree(d.ctype); hipFree(d.ep_start); hipFree(d.ep_len);
-  hipFree(d.w); hipFree(d.tail); hipFree(d.open); hipFree(d.cur_obs); hipFree((void*)d.obs_cols);
-  if (h->d_total) hipHostFree(h->d_total);
-  delete h;
-}
 
 static int her_desc_check(const hrg_her_desc* p, bool ring) {
   if (p->goal_kind != HRG_GOAL_REACH && p->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal kind");
@@ -3729,10 +3813,11 @@ static int her_desc_check(const hrg_her_desc* p, bool ring) {
   if (p->strategy != HRG_HER_FUTURE && p->strategy != HRG_HER_FINAL && p->strategy != HRG_HER_EPISODE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal selection strategy");
   if (p->n_envs < 1 || p->horizon < 1) return fail(HRG_ERR_INVALID, "her: n_envs and horizon must be positive");
   if (p->capacity <= p->horizon) return fail(HRG_ERR_INVALID, "her: capacity must exceed the horizon (a whole episode and one more transition have to fit the ring)");
-  if (p->act_dim < 1 || p->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "her: act_dim must lie in [1, HRG_ACT_DIM]");
-  if (p->n_obs_cols < 1 || p->n_obs_cols > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: n_obs_cols must lie in [1, HRG_OBS_DIM]");
-  for (int c = 0; c < p->n_obs_cols; c++)
-    if (p->obs_cols[c] < 0 || p->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: an observation column outside the superset");
+  return HRG_OK;
+}
+
+// the rest of the descriptor, behind buffer_columns (n_obs_cols and act_dim are in range)
+static int her_goal_check(const hrg_her_desc* p) {
   const int ng = p->goal_kind == HRG_GOAL_REACH ? 6 : 3;
   if (p->n_dg_in_obs != 0 && p->n_dg_in_obs != ng) return fail(HRG_ERR_INVALID, "her: n_dg_in_obs must be 0 or the goal's length");
   for (int d = 0; d < p->n_dg_in_obs; d++)
@@ -3747,71 +3832,41 @@ static int her_desc_check(const hrg_her_desc* p, bool ring) {
 int hrg_her_create(const hrg_her_desc* desc, int32_t device, hrg_her** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
-  const int rc = her_desc_check(desc, true);
+  int rc = her_desc_check(desc, true);
   if (rc != HRG_OK) return rc;
   HIPCHK(hipSetDevice(device));
-  hrg_her* h = new hrg_her();
+  std::unique_ptr<hrg_her> h(new hrg_her());
   h->device = device;
   h->desc = *desc;
   HerDev& d = h->d;
-  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity, row = sizeof(float) * HRG_OBS_DIM;
-  int32_t cols[HRG_OBS_DIM] = {0};
-  for (int c = 0; c < desc->n_obs_cols; c++) cols[c] = desc->obs_cols[c];
-#define HER_ALLOC(ptr, bytes)                                                                                                  \
-  do {                                                                                                                         \
-    const size_t _b = (bytes);                                                                                                 \
-    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
-      her_free(h);                                                                                                             \
-      return fail(HRG_ERR_NOMEM, "her: device allocation failed");                                                             \
-    }                                                                                                                          \
-  } while (0)
-  HER_ALLOC(d.pre, slots * row);
-  HER_ALLOC(d.post, slots * row);
-  HER_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
-  HER_ALLOC(d.reward, slots * sizeof(float));
-  HER_ALLOC(d.done, slots);
-  HER_ALLOC(d.trunc, slots);
-  HER_ALLOC(d.ctype, slots * sizeof(int32_t));
-  HER_ALLOC(d.ep_start, slots * sizeof(int64_t));
-  HER_ALLOC(d.ep_len, slots * sizeof(int32_t));
-  HER_ALLOC(d.w, n * sizeof(int64_t));
-  HER_ALLOC(d.tail, n * sizeof(int64_t));
-  HER_ALLOC(d.open, n * sizeof(int64_t));
-  HER_ALLOC(d.cur_obs, n * row);
-  HER_ALLOC(d.obs_cols, sizeof cols);
-#undef HER_ALLOC
-  if (hipHostMalloc((void**)&h->d_total, sizeof(int64_t)) != hipSuccess || hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess) {
-    her_free(h);
-    return fail(HRG_ERR_HIP, "her: upload failed");
-  }
-  *out = h;
+  DeviceMem& m = h->mem;
+  rc = buffer_columns("her", desc->n_obs_cols, desc->obs_cols, nullptr, desc->act_dim, m, d.view.obs_cols);
+  if (rc == HRG_OK) rc = her_goal_check(desc);
+  if (rc != HRG_OK) return rc;
+  d.view.n_obs_cols = desc->n_obs_cols;
+  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
+  if (!(m.zeros(d.pre, slots * HRG_OBS_DIM) && m.zeros(d.post, slots * HRG_OBS_DIM) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
+        m.zeros(d.done, slots) && m.zeros(d.trunc, slots) && m.zeros(d.ctype, slots) && m.zeros(d.ep_start, slots) && m.zeros(d.ep_len, slots) && m.zeros(d.w, n) &&
+        m.zeros(d.tail, n) && m.zeros(d.open, n) && m.zeros(d.cur_obs, n * HRG_OBS_DIM)))
+    return nomem("her", m);
+  if (hipHostMalloc((void**)&h->d_total, sizeof(int64_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(HRG_ERR_HIP, "her: upload failed");
+  *out = h.release();
   return HRG_OK;
 }
 
-void hrg_her_destroy(hrg_her* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  her_free(h);
-}
+void hrg_her_destroy(hrg_her* h) { destroy_handle(h); }
 
 int hrg_her_observe(hrg_her* h, const float* obs_dev, const uint8_t* mask_dev, int64_t* counts_dev, void* stream) {
   if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_her_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, obs_dev, mask_dev, counts_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_env(hrg_her_observe_kernel, h->desc.n_envs, stream, h->desc, h->d, obs_dev, mask_dev, counts_dev);
 }
 
 int hrg_her_add(hrg_her* h, const double* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
                 const int32_t* info_dev, int64_t* counts_dev, void* stream) {
   if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_her_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev,
-                     info_dev, counts_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_env(hrg_her_add_kernel, h->desc.n_envs, stream, h->desc, h->d, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, counts_dev);
 }
 
 int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* observation_dev, float* achieved_goal_dev, float* desired_goal_dev,
@@ -3826,11 +3881,9 @@ int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev
   HIPCHK(hipMemcpyAsync(h->d_total, counts_cum_dev + h->desc.n_envs, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   if (*h->d_total < 1) return fail(HRG_ERR_INVALID, "her: no finished episode in the buffer yet (nothing to sample)");
-  const unsigned per = HRG_HER_BLOCK / 64;
-  hipLaunchKernelGGL(hrg_her_sample_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_HER_BLOCK), 0, (hipStream_t)stream, h->desc, h->d, counts_cum_dev, h->calls,
-                     (int)batch_size, observation_dev, achieved_goal_dev, desired_goal_dev, next_observation_dev, next_achieved_goal_dev, next_desired_goal_dev, action_dev,
-                     reward_dev, done_dev, index_dev);
-  HIPCHK(hipGetLastError());
+  const int rc = launch_per_wave(hrg_her_sample_kernel, batch_size, stream, h->desc, h->d, counts_cum_dev, h->calls, (int)batch_size, observation_dev, achieved_goal_dev,
+                                 desired_goal_dev, next_observation_dev, next_achieved_goal_dev, next_desired_goal_dev, action_dev, reward_dev, done_dev, index_dev);
+  if (rc != HRG_OK) return rc;
   h->calls++;
   return HRG_OK;
 }
@@ -3882,7 +3935,7 @@ int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const fl
   if (n < 1) return fail(HRG_ERR_INVALID, "her: n must be positive");
   const int rc = her_desc_check(desc, false);
   if (rc != HRG_OK) return rc;
-  hipLaunchKernelGGL(hrg_goal_reward_done_kernel, dim3(((unsigned)n + HRG_HER_BLOCK - 1) / HRG_HER_BLOCK), dim3(HRG_HER_BLOCK), 0, (hipStream_t)stream, *desc, ag_dev, dg_dev,
+  hipLaunchKernelGGL(hrg_goal_reward_done_kernel, dim3(((unsigned)n + HRG_BUFFER_BLOCK - 1) / HRG_BUFFER_BLOCK), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, *desc, ag_dev, dg_dev,
                      ctype_dev, (int)n, reward_dev, done_dev);
   HIPCHK(hipGetLastError());
   return HRG_OK;
@@ -3893,94 +3946,53 @@ struct hrg_rollout {
   int device = 0;
   hrg_rollout_desc desc;
   RolloutDev d;
+  DeviceMem mem;           // behind every pointer of `d`
   int32_t pos = 0;         // the next slot (the write position lives on the host)
   bool computed = false;   // advantages and returns belong to the stored steps
 };
-
-static void rollout_free(hrg_rollout* h) {
-  RolloutDev& d = h->d;
-  hipFree(d.obs); hipFree(d.act); hipFree(d.reward); hipFree(d.value); hipFree(d.log_prob); hipFree(d.ep_start); hipFree(d.adv); hipFree(d.ret); hipFree(d.cur_obs);
-  hipFree(d.flag); hipFree(d.run_ret); hipFree(d.run_len); hipFree(d.acc); hipFree((void*)d.obs_cols);
-  delete h;
-}
 
 int hrg_rollout_create(const hrg_rollout_desc* desc, int32_t device, hrg_rollout** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
   if (desc->n_envs < 1 || desc->n_steps < 1) return fail(HRG_ERR_INVALID, "rollout: n_envs and n_steps must be positive");
-  if (desc->n_obs_cols < 1 || desc->n_obs_cols > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "rollout: n_obs_cols must lie in [1, HRG_OBS_DIM]");
-  for (int c = 0; c < desc->n_obs_cols; c++)
-    if (desc->obs_cols[c] < 0 || desc->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "rollout: an observation column outside the superset");
-  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "rollout: act_dim must lie in [1, HRG_ACT_DIM]");
-  if (!(desc->gamma >= 0 && desc->gamma <= 1)) return fail(HRG_ERR_INVALID, "rollout: gamma must lie in [0, 1]");
-  if (!(desc->gae_lambda >= 0 && desc->gae_lambda <= 1)) return fail(HRG_ERR_INVALID, "rollout: gae_lambda must lie in [0, 1]");
   HIPCHK(hipSetDevice(device));
-  hrg_rollout* h = new hrg_rollout();
+  std::unique_ptr<hrg_rollout> h(new hrg_rollout());
   h->device = device;
   h->desc = *desc;
   RolloutDev& d = h->d;
+  DeviceMem& m = h->mem;
+  const int rc = buffer_columns("rollout", desc->n_obs_cols, desc->obs_cols, nullptr, desc->act_dim, m, d.view.obs_cols);
+  if (rc != HRG_OK) return rc;
+  if (!(desc->gamma >= 0 && desc->gamma <= 1)) return fail(HRG_ERR_INVALID, "rollout: gamma must lie in [0, 1]");
+  if (!(desc->gae_lambda >= 0 && desc->gae_lambda <= 1)) return fail(HRG_ERR_INVALID, "rollout: gae_lambda must lie in [0, 1]");
+  d.view.n_obs_cols = desc->n_obs_cols;
   const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->n_steps;
-  int32_t cols[HRG_OBS_DIM] = {0};
-  for (int c = 0; c < desc->n_obs_cols; c++) cols[c] = desc->obs_cols[c];
-#define ROLLOUT_ALLOC(ptr, bytes)                                                                                              \
-  do {                                                                                                                         \
-    const size_t _b = (bytes);                                                                                                 \
-    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
-      rollout_free(h);                                                                                                         \
-      return fail(HRG_ERR_NOMEM, "rollout: device allocation failed");                                                         \
-    }                                                                                                                          \
-  } while (0)
-  ROLLOUT_ALLOC(d.obs, slots * sizeof(float) * (size_t)desc->n_obs_cols);
-  ROLLOUT_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
-  ROLLOUT_ALLOC(d.reward, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.value, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.log_prob, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.ep_start, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.adv, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.ret, slots * sizeof(float));
-  ROLLOUT_ALLOC(d.cur_obs, n * sizeof(float) * HRG_OBS_DIM);
-  ROLLOUT_ALLOC(d.flag, n * sizeof(float));
-  ROLLOUT_ALLOC(d.run_ret, n * sizeof(double));
-  ROLLOUT_ALLOC(d.run_len, n * sizeof(int32_t));
-  ROLLOUT_ALLOC(d.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM);
-  ROLLOUT_ALLOC(d.obs_cols, sizeof cols);
-#undef ROLLOUT_ALLOC
-  if (hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    rollout_free(h);
-    return fail(HRG_ERR_HIP, "rollout: upload failed");
-  }
-  *out = h;
+  if (!(m.zeros(d.obs, slots * (size_t)desc->n_obs_cols) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) && m.zeros(d.value, slots) &&
+        m.zeros(d.log_prob, slots) && m.zeros(d.ep_start, slots) && m.zeros(d.adv, slots) && m.zeros(d.ret, slots) && m.zeros(d.flag, n) &&
+        m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_ROLLOUT_STATS_DIM)))
+    return nomem("rollout", m);
+  if (hipDeviceSynchronize() != hipSuccess) return fail(HRG_ERR_HIP, "rollout: upload failed");
+  *out = h.release();
   return HRG_OK;
 }
 
-void hrg_rollout_destroy(hrg_rollout* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  rollout_free(h);
-}
+void hrg_rollout_destroy(hrg_rollout* h) { destroy_handle(h); }
 
 int hrg_rollout_view(hrg_rollout* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream) {
   if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (!rows_dev) {   // the envs' current rows
-    rows_dev = h->d.cur_obs;
+    rows_dev = h->d.ep.cur_obs;
     n_rows = h->desc.n_envs;
   }
   if (n_rows < 1) return fail(HRG_ERR_INVALID, "rollout: n_rows must be positive");
   HIPCHK(hipSetDevice(h->device));
-  const unsigned per = HRG_ROLLOUT_BLOCK / 64;
-  hipLaunchKernelGGL(hrg_rollout_view_kernel, dim3(((unsigned)n_rows + per - 1) / per), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->d, (int)h->desc.n_obs_cols, rows_dev,
-                     (int)n_rows, out_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_wave(hrg_buffer_view_kernel, n_rows, stream, h->d.view, rows_dev, (const float*)nullptr, (int)n_rows, out_dev);
 }
 
 int hrg_rollout_observe(hrg_rollout* h, const float* obs_dev, const uint8_t* mask_dev, void* stream) {
   if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_rollout_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, obs_dev, mask_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_env(hrg_rollout_observe_kernel, h->desc.n_envs, stream, h->desc, h->d, obs_dev, mask_dev);
 }
 
 int hrg_rollout_add(hrg_rollout* h, const float* actions_dev, const float* values_dev, const float* log_probs_dev, const float* terminal_values_dev,
@@ -3988,9 +4000,9 @@ int hrg_rollout_add(hrg_rollout* h, const float* actions_dev, const float* value
   if (!h || !actions_dev || !values_dev || !log_probs_dev || !obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (h->pos >= h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is full (hrg_rollout_reset starts the next rollout)");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_rollout_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->desc, h->d, (int)h->pos, actions_dev, values_dev, log_probs_dev,
-                     terminal_values_dev, obs_dev, reward_dev, done_dev, info_dev);
-  HIPCHK(hipGetLastError());
+  const int rc = launch_per_env(hrg_rollout_add_kernel, h->desc.n_envs, stream, h->desc, h->d, (int)h->pos, actions_dev, values_dev, log_probs_dev, terminal_values_dev, obs_dev,
+                                reward_dev, done_dev, info_dev);
+  if (rc != HRG_OK) return rc;
   h->pos++;
   h->computed = false;
   return HRG_OK;
@@ -4000,7 +4012,7 @@ int hrg_rollout_compute(hrg_rollout* h, const float* last_values_dev, void* stre
   if (!h || !last_values_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (h->pos < h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is not full yet (returns and advantages are computed over n_steps steps)");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_rollout_gae_kernel, dim3(((unsigned)h->desc.n_envs + HRG_ROLLOUT_BLOCK - 1) / HRG_ROLLOUT_BLOCK), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->desc,
+  hipLaunchKernelGGL(hrg_rollout_gae_kernel, dim3(((unsigned)h->desc.n_envs + HRG_BUFFER_BLOCK - 1) / HRG_BUFFER_BLOCK), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, h->desc,
                      h->d, last_values_dev);
   HIPCHK(hipGetLastError());
   h->computed = true;
@@ -4014,11 +4026,8 @@ int hrg_rollout_get(hrg_rollout* h, const int64_t* index_dev, int32_t batch_size
   if (batch_size < 1) return fail(HRG_ERR_INVALID, "rollout: batch_size must be positive");
   if (!h->computed) return fail(HRG_ERR_INVALID, "rollout: no returns and advantages yet (hrg_rollout_compute comes first)");
   HIPCHK(hipSetDevice(h->device));
-  const unsigned per = HRG_ROLLOUT_BLOCK / 64;
-  hipLaunchKernelGGL(hrg_rollout_get_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_ROLLOUT_BLOCK), 0, (hipStream_t)stream, h->desc, h->d, index_dev, (int)batch_size,
-                     observations_dev, actions_dev, old_values_dev, old_log_prob_dev, advantages_dev, returns_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_wave(hrg_rollout_get_kernel, batch_size, stream, h->desc, h->d, index_dev, (int)batch_size, observations_dev, actions_dev, old_values_dev, old_log_prob_dev,
+                         advantages_dev, returns_dev);
 }
 
 int hrg_rollout_reset(hrg_rollout* h) {
@@ -4030,15 +4039,7 @@ int hrg_rollout_reset(hrg_rollout* h) {
 
 int hrg_rollout_stats(hrg_rollout* h, double* per_env_host, int32_t clear) {
   if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t bytes = sizeof(double) * HRG_ROLLOUT_STATS_DIM * (size_t)h->desc.n_envs;
-  HIPCHK(hipMemcpy(per_env_host, h->d.acc, bytes, hipMemcpyDeviceToHost));
-  if (clear) {
-    HIPCHK(hipMemset(h->d.acc, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  return HRG_OK;
+  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_ROLLOUT_STATS_DIM, per_env_host, clear);
 }
 
 int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_host, float* rewards_host, float* values_host, float* log_probs_host,
@@ -4061,11 +4062,11 @@ int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_
     for (size_t e = 0; e < n; e++)
       for (size_t t = 0; t < T; t++) flat[a][e * T + t] = tm[t * n + e];
   }
-  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(flags_host, d.flag, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_return_host, d.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_length_host, d.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(stats_host, d.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_return_host, d.ep.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_length_host, d.ep.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stats_host, d.ep.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM, hipMemcpyDeviceToHost));
   state_host[0] = h->pos;
   state_host[1] = h->computed ? 1 : 0;
   return HRG_OK;
@@ -4079,124 +4080,79 @@ struct hrg_replay {
   int32_t pos = 0;      // the next slot (the write position lives on the host)
   bool full = false;    // every slot holds a transition
   uint64_t calls = 0;   // sample calls that drew their indices (key of the draws)
-  size_t bytes = 0;     // device memory held
+  DeviceMem mem;        // behind every pointer of `d`
 };
-
-static void replay_free(hrg_replay* h) {
-  ReplayDev& d = h->d;
-  hipFree(d.obs); hipFree(d.nobs); hipFree(d.act); hipFree(d.reward); hipFree(d.done); hipFree(d.timeout); hipFree(d.cur_obs); hipFree(d.cur_time); hipFree(d.run_ret);
-  hipFree(d.run_len); hipFree(d.acc); hipFree((void*)d.obs_cols); hipFree((void*)d.mean); hipFree((void*)d.std);
-  delete h;
-}
 
 int hrg_replay_create(const hrg_replay_desc* desc, int32_t device, hrg_replay** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
   if (desc->n_envs < 1 || desc->capacity < 1) return fail(HRG_ERR_INVALID, "replay: n_envs and capacity must be positive");
-  const bool with_time = desc->observe_time != 0;
-  if (desc->n_obs_cols < 1 || desc->n_obs_cols + (with_time ? 1 : 0) > HRG_OBS_DIM)
-    return fail(HRG_ERR_INVALID, "replay: n_obs_cols (+ 1 with observe_time) must lie in [1, HRG_OBS_DIM]");
-  const int K = desc->n_obs_cols + (with_time ? 1 : 0);
-  for (int c = 0; c < desc->n_obs_cols; c++)
-    if (desc->obs_cols[c] < 0 || desc->obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "replay: an observation column outside the superset");
-  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, "replay: act_dim must lie in [1, HRG_ACT_DIM]");
-  if (desc->squash && !desc->normalize) return fail(HRG_ERR_INVALID, "replay: squash needs normalize");
-  if (desc->normalize) {
-    for (int k = 0; k < K; k++)
-      if (!std::isfinite(desc->mean[k]) || !std::isfinite(desc->std[k]) || desc->std[k] == 0.0) return fail(HRG_ERR_INVALID, "replay: mean must be finite, std finite and non-zero");
-    if (desc->squash && !std::isfinite(desc->squash_factor)) return fail(HRG_ERR_INVALID, "replay: squash_factor must be finite");
-  }
   HIPCHK(hipSetDevice(device));
-  hrg_replay* h = new hrg_replay();
+  std::unique_ptr<hrg_replay> h(new hrg_replay());
   h->device = device;
   h->desc = *desc;
   ReplayDev& d = h->d;
-  d.n_envs = desc->n_envs; d.capacity = desc->capacity; d.act_dim = desc->act_dim; d.n_obs_cols = desc->n_obs_cols;
-  d.observe_time = with_time ? 1 : 0; d.normalize = desc->normalize ? 1 : 0; d.squash = desc->squash ? 1 : 0;
-  d.squash_factor = desc->squash_factor; d.seed = desc->seed;
+  BufferView& v = d.view;
+  DeviceMem& m = h->mem;
   const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
-  int32_t cols[HRG_OBS_DIM] = {0};
+  v.observe_time = desc->observe_time ? 1 : 0;
+  const int K = desc->n_obs_cols + v.observe_time;
+  const int rc = buffer_columns("replay", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols);
+  if (rc != HRG_OK) return rc;
+  if (desc->squash && !desc->normalize) return fail(HRG_ERR_INVALID, "replay: squash needs normalize");
   double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
   for (int k = 0; k < HRG_OBS_DIM; k++) {
-    if (k < desc->n_obs_cols) cols[k] = desc->obs_cols[k];
     mean[k] = desc->normalize && k < K ? desc->mean[k] : 0.0;
     sd[k] = desc->normalize && k < K ? desc->std[k] : 1.0;
+    if (!std::isfinite(mean[k]) || !std::isfinite(sd[k]) || sd[k] == 0.0) return fail(HRG_ERR_INVALID, "replay: mean must be finite, std finite and non-zero");
   }
-#define REPLAY_ALLOC(ptr, nbytes)                                                                                              \
-  do {                                                                                                                         \
-    const size_t _b = (nbytes);                                                                                                \
-    if (hipMalloc((void**)&(ptr), _b) != hipSuccess || hipMemset((void*)(ptr), 0, _b) != hipSuccess) {                         \
-      (void)hipGetLastError();                                                                                                 \
-      replay_free(h);                                                                                                          \
-      return fail(HRG_ERR_NOMEM, "replay: device allocation of " + std::to_string(_b) + " bytes failed");                      \
-    }                                                                                                                          \
-    h->bytes += _b;                                                                                                            \
-  } while (0)
-  REPLAY_ALLOC(d.obs, slots * sizeof(float) * (size_t)K);
-  REPLAY_ALLOC(d.nobs, slots * sizeof(float) * (size_t)K);
-  REPLAY_ALLOC(d.act, slots * sizeof(float) * (size_t)desc->act_dim);
-  REPLAY_ALLOC(d.reward, slots * sizeof(float));
-  REPLAY_ALLOC(d.done, slots);
-  REPLAY_ALLOC(d.timeout, slots);
-  REPLAY_ALLOC(d.cur_obs, n * sizeof(float) * HRG_OBS_DIM);
-  REPLAY_ALLOC(d.cur_time, n * sizeof(float));
-  REPLAY_ALLOC(d.run_ret, n * sizeof(double));
-  REPLAY_ALLOC(d.run_len, n * sizeof(int32_t));
-  REPLAY_ALLOC(d.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM);
-  REPLAY_ALLOC(d.obs_cols, sizeof cols);
-  REPLAY_ALLOC(d.mean, sizeof mean);
-  REPLAY_ALLOC(d.std, sizeof sd);
-#undef REPLAY_ALLOC
-  if (hipMemcpy((void*)d.obs_cols, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy((void*)d.mean, mean, sizeof mean, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((void*)d.std, sd, sizeof sd, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    replay_free(h);
+  if (desc->normalize && desc->squash && !std::isfinite(desc->squash_factor)) return fail(HRG_ERR_INVALID, "replay: squash_factor must be finite");
+  d.n_envs = desc->n_envs; d.capacity = desc->capacity; d.act_dim = desc->act_dim; d.seed = desc->seed;
+  v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
+  double *mean_dev = nullptr, *std_dev = nullptr;
+  if (!(m.zeros(d.obs, slots * (size_t)K) && m.zeros(d.nobs, slots * (size_t)K) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
+        m.zeros(d.done, slots) && m.zeros(d.timeout, slots) && m.zeros(d.cur_time, n) && m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) &&
+        m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_REPLAY_STATS_DIM) && m.zeros(mean_dev, HRG_OBS_DIM) && m.zeros(std_dev, HRG_OBS_DIM)))
+    return nomem("replay", m);
+  if (hipMemcpy(mean_dev, mean, sizeof mean, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(std_dev, sd, sizeof sd, hipMemcpyHostToDevice) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess)
     return fail(HRG_ERR_HIP, "replay: upload failed");
-  }
-  *out = h;
+  v.mean = mean_dev;
+  v.std = std_dev;
+  *out = h.release();
   return HRG_OK;
 }
 
-void hrg_replay_destroy(hrg_replay* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  replay_free(h);
-}
+void hrg_replay_destroy(hrg_replay* h) { destroy_handle(h); }
 
 int hrg_replay_view(hrg_replay* h, const float* rows_dev, const float* time_dev, int32_t n_rows, float* out_dev, void* stream) {
   if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (!rows_dev) {   // the envs' current rows
-    rows_dev = h->d.cur_obs;
+    rows_dev = h->d.ep.cur_obs;
     time_dev = h->d.cur_time;
     n_rows = h->desc.n_envs;
   }
   if (n_rows < 1) return fail(HRG_ERR_INVALID, "replay: n_rows must be positive");
-  if (h->d.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
+  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
   HIPCHK(hipSetDevice(h->device));
-  const unsigned per = HRG_REPLAY_BLOCK / 64;
-  hipLaunchKernelGGL(hrg_replay_view_kernel, dim3(((unsigned)n_rows + per - 1) / per), dim3(HRG_REPLAY_BLOCK), 0, (hipStream_t)stream, h->d, rows_dev, time_dev, (int)n_rows, out_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_wave(hrg_buffer_view_kernel, n_rows, stream, h->d.view, rows_dev, time_dev, (int)n_rows, out_dev);
 }
 
 int hrg_replay_observe(hrg_replay* h, const float* obs_dev, const float* time_dev, const uint8_t* mask_dev, void* stream) {
   if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (h->d.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
+  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_replay_observe_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->d, obs_dev, time_dev, mask_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
+  return launch_per_env(hrg_replay_observe_kernel, h->desc.n_envs, stream, h->d, obs_dev, time_dev, mask_dev);
 }
 
 int hrg_replay_add(hrg_replay* h, const float* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
                    const int32_t* info_dev, const float* imit_dev, const float* sir_dev, void* stream) {
   if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "replay: an imitation row or a state imitation row, not both");
-  if (h->d.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the state imitation rows (their time columns)");
+  if (h->d.view.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the state imitation rows (their time columns)");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_replay_add_kernel, dim3((unsigned)h->desc.n_envs), dim3(64), 0, (hipStream_t)stream, h->d, (int)h->pos, actions_dev, obs_dev, term_obs_dev, reward_dev,
-                     done_dev, info_dev, imit_dev, sir_dev);
-  HIPCHK(hipGetLastError());
+  const int rc = launch_per_env(hrg_replay_add_kernel, h->desc.n_envs, stream, h->d, (int)h->pos, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, imit_dev, sir_dev);
+  if (rc != HRG_OK) return rc;
   if (++h->pos == h->desc.capacity) {   // ReplayBuffer.add: self.full = True; self.pos = 0
     h->pos = 0;
     h->full = true;
@@ -4212,25 +4168,16 @@ int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in
   const int64_t upper = h->full ? h->desc.capacity : h->pos;
   if (upper < 1) return fail(HRG_ERR_INVALID, "replay: the buffer is empty (nothing to sample)");
   HIPCHK(hipSetDevice(h->device));
-  const unsigned per = HRG_REPLAY_BLOCK / 64;
-  hipLaunchKernelGGL(hrg_replay_sample_kernel, dim3(((unsigned)batch_size + per - 1) / per), dim3(HRG_REPLAY_BLOCK), 0, (hipStream_t)stream, h->d, upper, h->calls, index_in_dev,
-                     (int)batch_size, observations_dev, actions_dev, next_observations_dev, dones_dev, rewards_dev, index_out_dev);
-  HIPCHK(hipGetLastError());
+  const int rc = launch_per_wave(hrg_replay_sample_kernel, batch_size, stream, h->d, upper, h->calls, index_in_dev, (int)batch_size, observations_dev, actions_dev,
+                                 next_observations_dev, dones_dev, rewards_dev, index_out_dev);
+  if (rc != HRG_OK) return rc;
   if (!index_in_dev) h->calls++;
   return HRG_OK;
 }
 
 int hrg_replay_stats(hrg_replay* h, double* per_env_host, int32_t clear) {
   if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t bytes = sizeof(double) * HRG_REPLAY_STATS_DIM * (size_t)h->desc.n_envs;
-  HIPCHK(hipMemcpy(per_env_host, h->d.acc, bytes, hipMemcpyDeviceToHost));
-  if (clear) {
-    HIPCHK(hipMemset(h->d.acc, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  return HRG_OK;
+  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_REPLAY_STATS_DIM, per_env_host, clear);
 }
 
 int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_observations_host, float* actions_host, float* rewards_host, uint8_t* dones_host,
@@ -4242,18 +4189,18 @@ int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_obser
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipDeviceSynchronize());
   const ReplayDev& d = h->d;
-  const size_t n = (size_t)h->desc.n_envs, slots = n * (size_t)h->desc.capacity, K = (size_t)(d.n_obs_cols + d.observe_time);
+  const size_t n = (size_t)h->desc.n_envs, slots = n * (size_t)h->desc.capacity, K = (size_t)(d.view.n_obs_cols + d.view.observe_time);
   HIPCHK(hipMemcpy(observations_host, d.obs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(next_observations_host, d.nobs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(actions_host, d.act, slots * sizeof(float) * (size_t)d.act_dim, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(rewards_host, d.reward, slots * sizeof(float), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(dones_host, d.done, slots, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(timeouts_host, d.timeout, slots, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(cur_time_host, d.cur_time, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_return_host, d.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_length_host, d.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(stats_host, d.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_return_host, d.ep.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(run_length_host, d.ep.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(stats_host, d.ep.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM, hipMemcpyDeviceToHost));
   state_host[0] = h->pos;
   state_host[1] = h->full ? 1 : 0;
   state_host[2] = (int64_t)h->calls;
@@ -4265,7 +4212,7 @@ int hrg_replay_size(hrg_replay* h, int64_t* size_host) {
   size_host[0] = h->pos;
   size_host[1] = h->full ? 1 : 0;
   size_host[2] = (int64_t)h->calls;
-  size_host[3] = (int64_t)h->bytes;
+  size_host[3] = (int64_t)h->mem.bytes;
   return HRG_OK;
 }
 
@@ -4276,7 +4223,7 @@ struct hrg_sac {
   SacDev d;
   uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
   uint64_t act_calls = 0;   // act calls that drew their noise
-  size_t bytes = 0;
+  DeviceMem mem;
   float* scratch = nullptr; // one allocation behind every pointer of `d`
 };
 
@@ -4318,7 +4265,7 @@ int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
     return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
   if (!desc->auto_ent_coef && desc->ent_coef <= 0.0) return fail(HRG_ERR_INVALID, "sac: a fixed ent_coef must be positive");
   HIPCHK(hipSetDevice(device));
-  hrg_sac* h = new hrg_sac();
+  std::unique_ptr<hrg_sac> h(new hrg_sac());
   h->device = device;
   h->desc = *desc;
   SacDev& d = h->d;
@@ -4327,14 +4274,8 @@ int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
   d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
   const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
   const size_t n_float = B * A + 3 * B + SAC_NQ * B + 2 * B * A + (size_t)d.tiles * P + P + (size_t)d.tiles * SAC_NLOSS + 4;
-  h->bytes = n_float * sizeof(float);
-  if (hipMalloc((void**)&h->scratch, h->bytes) != hipSuccess || hipMemset(h->scratch, 0, h->bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipGetLastError();
-    hipFree(h->scratch);
-    const size_t b = h->bytes;
-    delete h;
-    return fail(HRG_ERR_NOMEM, "sac: device allocation of " + std::to_string(b) + " bytes failed");
-  }
+  if (!h->mem.zeros(h->scratch, n_float)) return nomem("sac", h->mem);
+  HIPCHK(hipDeviceSynchronize());
   float* p = h->scratch;
   d.a_pi = p; p += B * A;
   d.logp = p; p += B;
@@ -4346,17 +4287,11 @@ int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
   d.grad = p; p += P;
   d.loss_part = p; p += (size_t)d.tiles * SAC_NLOSS;
   d.losses = p;
-  *out = h;
+  *out = h.release();
   return HRG_OK;
 }
 
-void hrg_sac_destroy(hrg_sac* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  hipFree(h->scratch);
-  delete h;
-}
+void hrg_sac_destroy(hrg_sac* h) { destroy_handle(h); }
 
 int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
   if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
@@ -4365,7 +4300,7 @@ int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
   size_host[2] = h->d.n_critic;
   size_host[3] = (int64_t)h->steps;
   size_host[4] = (int64_t)h->act_calls;
-  size_host[5] = (int64_t)h->bytes;
+  size_host[5] = (int64_t)h->mem.bytes;
   return HRG_OK;
 }
 

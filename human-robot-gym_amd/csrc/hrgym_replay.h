@@ -1,10 +1,10 @@
 // hrgym_replay.h -- the uniform replay buffer of SAC on flat observations on the device: SB3's ReplayBuffer (add, sample, _get_samples with
 // optimize_memory_usage = False) and the bookkeeping of OffPolicyAlgorithm._store_transition (the terminal observation as the next observation of a done step,
 // _last_obs), the policy's view of a row with DatasetObsNormWrapper's normalisation and the state imitation reward's time column, plus the episode statistics
-// Monitor and the imitation wrappers' _add_reward_to_info would have produced on the host, in four small kernels next to the (unchanged) step launch.  Included
-// into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_rollout.h.  No LDS, no atomics.
+// Monitor and the imitation wrappers' _add_reward_to_info would have produced on the host, in three small kernels next to the (unchanged) step launch.  Included
+// into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_rollout.h.  No LDS, no atomics.  The policy's view of rows (hrg_replay_view) is
+// hrg_buffer_view_kernel, the view of a stored row replay_view, the episode statistics the shared tracker (hrgym_buffer.h).
 //
-//   hrg_replay_view_kernel     rows of the observation superset (+ a time value per row) -> the policy's view; one wavefront per row, lane k computes value k.
 //   hrg_replay_observe_kernel  after a reset: the current row and time value of the masked envs, their running return and length.
 //   hrg_replay_add_kernel      _store_transition + ReplayBuffer.add for slot `pos` of every env; one wavefront per env.
 //   hrg_replay_sample_kernel   ReplayBuffer.sample + _get_samples: B (slot, env) pairs, drawn or supplied -> observations, actions, next observations,
@@ -13,17 +13,11 @@
 // Layout.  Everything is time-major, [capacity][n_envs][.], as SB3 keeps it: one step writes one contiguous block of each array.  Observations are stored as the
 // policy sees them (selected, with the time column, normalised): K = n_obs_cols + observe_time floats, not the 64 of the superset.
 //
-// The view.  Lane k < n_obs_cols takes column obs_cols[k] of the row, lane n_obs_cols the time value (observe_time); with `normalize`, (v - mean[k]) / std[k] in
-// double, tanh(squash_factor * .) with `squash`, rounded to float32 once (HipVecEnv._view).  The translation unit is compiled with -fapprox-func: the double
-// division is the reciprocal refinement, within an ulp of the quotient in double, so that the float32 result differs from numpy's only where the exact value
-// sits next to a rounding boundary.
-//
 // Draws: rng_u01 keyed by (buffer seed, sample call counter, index of the sample in its batch, STREAM_REPLAY, 0..1): independent of the grid and of the batch
 // size, and no stream of the step / reset / expert / dataset / HER kernels moves.
 #pragma once
 
 enum { STREAM_REPLAY = 11 };   // after STREAM_HER = 10 (hrgym_her.h)
-#define HRG_REPLAY_BLOCK 256
 
 // one hrg_replay: its sizes and switches (from hrg_replay_desc) and its buffers; passed to the kernels by value
 struct ReplayDev {
@@ -33,41 +27,12 @@ struct ReplayDev {
   float* reward = nullptr;      // [cap][n]
   uint8_t* done = nullptr;      // [cap][n]
   uint8_t* timeout = nullptr;   // [cap][n] TimeLimit.truncated
-  float* cur_obs = nullptr;     // [n][HRG_OBS_DIM] the row the next transition starts from (SB3's _last_obs, as a row of the superset)
-  float* cur_time = nullptr;    // [n] its time value
-  double* run_ret = nullptr;    // [n] return of the running episode (Monitor's sum: the env's own reward)
-  int32_t* run_len = nullptr;   // [n] its length
-  double* acc = nullptr;        // [n][HRG_REPLAY_STATS_DIM] sums over the finished episodes since the last clear
-  const int32_t* obs_cols = nullptr;   // [HRG_OBS_DIM] hrg_replay_desc::obs_cols, zero behind n_obs_cols (per-lane lookups: device memory, not kernel arguments)
-  const double* mean = nullptr;        // [HRG_OBS_DIM] zero behind K
-  const double* std = nullptr;         // [HRG_OBS_DIM] one behind K
-  double squash_factor = 0.0;
+  float* cur_time = nullptr;    // [n] the time value of the env's current row
+  EpisodeTracker ep;            // the current rows; the returns are the env's own reward; HRG_REPLAY_STATS_DIM columns, the last the imitation reward sums
+  BufferView view;              // hrg_replay_desc: obs_cols, observe_time, mean / std, squash
   uint64_t seed = 0;
-  int32_t n_envs = 0, capacity = 0, act_dim = 0, n_obs_cols = 0, observe_time = 0, normalize = 0, squash = 0;
+  int32_t n_envs = 0, capacity = 0, act_dim = 0;
 };
-
-// value `lane` of the policy's view of a row: x = column `lane` of the row, t = its time value.  Every lane of the wave takes part (the shuffle).
-DI float replay_view(const ReplayDev& h, float x, float t, int lane) {
-  float v = __shfl(x, h.obs_cols[lane]);
-  if (h.observe_time && lane == h.n_obs_cols) v = t;
-  if (h.normalize) {
-    double d = ((double)v - h.mean[lane]) / h.std[lane];
-    if (h.squash) d = tanh(h.squash_factor * d);
-    v = (float)d;
-  }
-  return v;
-}
-
-// grid = ceil(n_rows / 4) blocks of four wavefronts, one row each; time may be null without observe_time
-__global__ __launch_bounds__(HRG_REPLAY_BLOCK) void hrg_replay_view_kernel(const ReplayDev h, const float* __restrict__ rows, const float* __restrict__ time, int n_rows,
-                                                                           float* __restrict__ out) {
-  const int lane = (int)(threadIdx.x & 63);
-  const int r = (int)(blockIdx.x * (HRG_REPLAY_BLOCK / 64) + (threadIdx.x >> 6));
-  if (r >= n_rows) return;   // (wave-uniform)
-  const int K = h.n_obs_cols + h.observe_time;
-  const float v = replay_view(h, rows[(size_t)r * HRG_OBS_DIM + lane], h.observe_time ? time[r] : 0.0f, lane);
-  if (lane < K) out[(size_t)r * K + lane] = v;
-}
 
 // grid = n_envs blocks of one wavefront; mask null: every env; time may be null without observe_time
 __global__ __launch_bounds__(64) void hrg_replay_observe_kernel(const ReplayDev h, const float* __restrict__ obs, const float* __restrict__ time,
@@ -75,12 +40,8 @@ __global__ __launch_bounds__(64) void hrg_replay_observe_kernel(const ReplayDev 
   const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (e >= h.n_envs) return;
   if (mask && !mask[e]) return;
-  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];
-  if (lane == 0) {
-    h.cur_time[e] = h.observe_time ? time[e] : 0.0f;
-    h.run_ret[e] = 0.0;
-    h.run_len[e] = 0;
-  }
+  tracker_start(h.ep, e, lane, obs);
+  if (lane == 0) h.cur_time[e] = h.view.observe_time ? time[e] : 0.0f;
 }
 
 // grid = n_envs blocks of one wavefront; pos: the slot (0 <= pos < capacity, kept by the host).  imit / sir: the step's imitation rows or null (at most one of
@@ -90,54 +51,43 @@ __global__ __launch_bounds__(64) void hrg_replay_add_kernel(const ReplayDev h, i
                                                             const int32_t* __restrict__ info, const float* __restrict__ imit, const float* __restrict__ sir) {
   const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (e >= h.n_envs) return;
-  const int K = h.n_obs_cols + h.observe_time;
+  const int K = h.view.n_obs_cols + h.view.observe_time;
   const size_t s = (size_t)pos * (size_t)h.n_envs + (size_t)e;
   const bool dn = done[e] != 0;
   const float* srow = sir ? sir + (size_t)e * HRG_SIR_DIM : nullptr;
   const float* irow = imit ? imit + (size_t)e * HRG_IMIT_DIM : nullptr;
-  const float t_next = h.observe_time ? srow[dn ? HRG_SIR_TIME : HRG_SIR_TIME_OBS] : 0.0f;   // the terminal observation carries the time after the step
-  const float t_obs = h.observe_time ? srow[HRG_SIR_TIME_OBS] : 0.0f;
+  const float t_next = h.view.observe_time ? srow[dn ? HRG_SIR_TIME : HRG_SIR_TIME_OBS] : 0.0f;   // the terminal observation carries the time after the step
+  const float t_obs = h.view.observe_time ? srow[HRG_SIR_TIME_OBS] : 0.0f;
   const float o = obs[(size_t)e * HRG_OBS_DIM + lane];
   const float nx = dn ? term_obs[(size_t)e * HRG_OBS_DIM + lane] : o;
-  const float v0 = replay_view(h, h.cur_obs[(size_t)e * HRG_OBS_DIM + lane], h.cur_time[e], lane);
-  const float v1 = replay_view(h, nx, t_next, lane);
+  const float v0 = replay_view(h.view, h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane], h.cur_time[e], lane);
+  const float v1 = replay_view(h.view, nx, t_next, lane);
   if (lane < K) {
     h.obs[s * (size_t)K + lane] = v0;
     h.nobs[s * (size_t)K + lane] = v1;
   }
-  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = o;   // after an auto-reset: the new episode's first row
+  h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = o;   // after an auto-reset: the new episode's first row
   if (lane < h.act_dim) h.act[s * (size_t)h.act_dim + lane] = actions[(size_t)e * h.act_dim + lane];
   const float r = reward[e];
   const float r_env = srow ? srow[HRG_SIR_R_ENV] : irow ? irow[HRG_IMIT_R_ENV] : r;   // Monitor sits inside the imitation wrapper: its return is the env's own reward
-  const double ep_ret = h.run_ret[e] + (double)r_env;   // (the same value on every lane)
-  const int32_t ep_len = h.run_len[e] + 1;
+  const double ep_im = !dn ? 0.0 : srow ? (double)srow[HRG_SIR_EP_IM] : irow ? (double)irow[HRG_IMIT_EP_IM] : 0.0;   // the episode's sum of imitation rewards (ep_im_rew_mean)
+  tracker_step(h.ep, e, lane, r_env, dn, info + (size_t)e * HRG_INFO_DIM, HRG_REPLAY_STATS_DIM, ep_im);
   if (lane == 0) {
     h.reward[s] = r;
     h.done[s] = dn ? 1 : 0;
     h.timeout[s] = info[(size_t)e * HRG_INFO_DIM + HRG_INFO_TRUNCATED] != 0 ? 1 : 0;
     h.cur_time[e] = t_obs;
-    h.run_ret[e] = dn ? 0.0 : ep_ret;
-    h.run_len[e] = dn ? 0 : ep_len;
-  }
-  if (dn && lane < HRG_REPLAY_STATS_DIM) {   // lane j adds column j of the env's episode accumulators
-    double x;
-    if (lane == 0) x = 1.0;
-    else if (lane == 1) x = ep_ret;
-    else if (lane == 2) x = (double)ep_len;
-    else if (lane < 3 + HRG_INFO_DIM) x = (double)info[(size_t)e * HRG_INFO_DIM + (lane - 3)];
-    else x = srow ? (double)srow[HRG_SIR_EP_IM] : irow ? (double)irow[HRG_IMIT_EP_IM] : 0.0;   // the episode's sum of imitation rewards (ep_im_rew_mean)
-    h.acc[(size_t)e * HRG_REPLAY_STATS_DIM + lane] += x;
   }
 }
 
 // grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  upper: slots that hold a transition (>= 1, checked by the host); index_in [batch][2]
 // (slot, env) or null: drawn; index_out [batch][2] or null.  Slot and env are clamped to the buffer: a supplied pair never reads outside it.
-__global__ __launch_bounds__(HRG_REPLAY_BLOCK) void hrg_replay_sample_kernel(const ReplayDev h, int64_t upper, uint64_t call, const int64_t* __restrict__ index_in,
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_replay_sample_kernel(const ReplayDev h, int64_t upper, uint64_t call, const int64_t* __restrict__ index_in,
                                                                              int batch, float* __restrict__ o_obs, float* __restrict__ o_act,
                                                                              float* __restrict__ o_nobs, float* __restrict__ o_done, float* __restrict__ o_rew,
                                                                              int64_t* __restrict__ index_out) {
   const int lane = (int)(threadIdx.x & 63);
-  const int k = (int)(blockIdx.x * (HRG_REPLAY_BLOCK / 64) + (threadIdx.x >> 6));
+  const int k = buffer_wave_item();
   if (k >= batch) return;
   int64_t slot, env;
   if (index_in) {
@@ -150,7 +100,7 @@ __global__ __launch_bounds__(HRG_REPLAY_BLOCK) void hrg_replay_sample_kernel(con
   }
   slot = min(max(slot, (int64_t)0), min(upper, (int64_t)h.capacity) - 1);
   env = min(max(env, (int64_t)0), (int64_t)h.n_envs - 1);
-  const int K = h.n_obs_cols + h.observe_time;
+  const int K = h.view.n_obs_cols + h.view.observe_time;
   const size_t s = (size_t)slot * (size_t)h.n_envs + (size_t)env;
   if (lane < K) {
     o_obs[(size_t)k * K + lane] = h.obs[s * (size_t)K + lane];

@@ -1,9 +1,9 @@
 // hrgym_rollout.h -- the PPO rollout buffer on the device: SB3's RolloutBuffer and the bookkeeping of OnPolicyAlgorithm.collect_rollouts (storage behind the
 // step, bootstrapping of time-limit truncations, GAE(lambda), minibatch gather) plus the episode statistics Monitor and callbacks/logging_callback.py would have
-// produced on the host, in five small kernels next to the (unchanged) step launch.  Included into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU),
-// after hrgym_her.h.  No LDS, no atomics, no random draws.
+// produced on the host, in four small kernels next to the (unchanged) step launch.  Included into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU),
+// after hrgym_her.h.  No LDS, no atomics, no random draws.  The policy's view of rows (hrg_rollout_view) is hrg_buffer_view_kernel, the episode statistics are
+// the shared tracker (hrgym_buffer.h).
 //
-//   hrg_rollout_view_kernel     rows of the observation superset -> the policy's view (column obs_cols[k]); one wavefront per row, lane k moves value k.
 //   hrg_rollout_observe_kernel  after a reset: the current row of the masked envs, their episode_start flag, their running return and length.
 //   hrg_rollout_add_kernel      collect_rollouts + RolloutBuffer.add for slot t of every env; one wavefront per env.
 //   hrg_rollout_gae_kernel      compute_returns_and_advantage; one lane per env, the time loop serial from t = T - 1 down.
@@ -17,7 +17,6 @@
 // multiply-add pair becomes an FMA and the device gives the restatement's bits (tests/rollout_ref.py).
 #pragma once
 
-#define HRG_ROLLOUT_BLOCK 256
 #define HRG_ROLLOUT_STATS_DIM (3 + HRG_INFO_DIM)   // episodes, return, length, the info columns
 
 // the buffers of one hrg_rollout; passed to the kernels by value
@@ -30,12 +29,9 @@ struct RolloutDev {
   float* ep_start = nullptr;   // [T][n] 1 where slot t is the first step of an episode
   float* adv = nullptr;        // [T][n]
   float* ret = nullptr;        // [T][n]
-  float* cur_obs = nullptr;    // [n][HRG_OBS_DIM] the row the next step starts from (SB3's _last_obs)
   float* flag = nullptr;       // [n] episode_start flag of the next slot (SB3's _last_episode_starts)
-  double* run_ret = nullptr;   // [n] return of the running episode, without bootstrap terms (Monitor's sum)
-  int32_t* run_len = nullptr;  // [n] its length
-  double* acc = nullptr;       // [n][HRG_ROLLOUT_STATS_DIM] sums over the finished episodes since the last clear
-  const int32_t* obs_cols = nullptr;   // [HRG_OBS_DIM] hrg_rollout_desc::obs_cols, zero behind n_obs_cols (a per-lane lookup: device memory, not a kernel argument)
+  EpisodeTracker ep;           // the current rows; the returns are the step rewards without bootstrap terms; HRG_ROLLOUT_STATS_DIM columns
+  BufferView view;             // hrg_rollout_desc::obs_cols (a plain selection: no time column, no normalisation)
 };
 
 // reward + gamma * terminal value as two float32 operations (collect_rollouts: rewards[idx] += self.gamma * terminal_value)
@@ -57,29 +53,14 @@ DI float rollout_gae_step(float r, float v, float nv, float nnt, float g, float 
   return delta + carry;
 }
 
-// grid = ceil(n_rows / 4) blocks of four wavefronts, one row each
-__global__ __launch_bounds__(HRG_ROLLOUT_BLOCK) void hrg_rollout_view_kernel(const RolloutDev h, int n_obs_cols, const float* __restrict__ rows, int n_rows,
-                                                                             float* __restrict__ out) {
-  const int lane = (int)(threadIdx.x & 63);
-  const int r = (int)(blockIdx.x * (HRG_ROLLOUT_BLOCK / 64) + (threadIdx.x >> 6));
-  if (r >= n_rows) return;   // (wave-uniform)
-  const float x = rows[(size_t)r * HRG_OBS_DIM + lane];
-  const float v = __shfl(x, h.obs_cols[lane]);
-  if (lane < n_obs_cols) out[(size_t)r * n_obs_cols + lane] = v;
-}
-
 // grid = n_envs blocks of one wavefront; mask null: every env
 __global__ __launch_bounds__(64) void hrg_rollout_observe_kernel(const hrg_rollout_desc p, const RolloutDev h, const float* __restrict__ obs,
                                                                  const uint8_t* __restrict__ mask) {
   const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (e >= p.n_envs) return;
   if (mask && !mask[e]) return;
-  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];
-  if (lane == 0) {
-    h.flag[e] = 1.0f;
-    h.run_ret[e] = 0.0;
-    h.run_len[e] = 0;
-  }
+  tracker_start(h.ep, e, lane, obs);
+  if (lane == 0) h.flag[e] = 1.0f;
 }
 
 // grid = n_envs blocks of one wavefront; t: the slot (0 <= t < n_steps, checked by the host); terminal_values may be null
@@ -91,14 +72,12 @@ __global__ __launch_bounds__(64) void hrg_rollout_add_kernel(const hrg_rollout_d
   if (e >= p.n_envs) return;
   const size_t row = (size_t)e * (size_t)p.n_steps + (size_t)t, s = (size_t)t * (size_t)p.n_envs + (size_t)e;
   const bool dn = done[e] != 0;
-  const float cur = h.cur_obs[(size_t)e * HRG_OBS_DIM + lane];
-  const float v = __shfl(cur, h.obs_cols[lane]);   // every lane takes part
+  const float v = view_select(h.view, h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane], lane);   // every lane takes part
   if (lane < p.n_obs_cols) h.obs[row * (size_t)p.n_obs_cols + lane] = v;
-  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];   // after an auto-reset: the new episode's first row
+  h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];   // after an auto-reset: the new episode's first row
   if (lane < p.act_dim) h.act[row * (size_t)p.act_dim + lane] = actions[(size_t)e * p.act_dim + lane];
   const float r = reward[e];
-  const double ep_ret = h.run_ret[e] + (double)r;   // (the same value on every lane)
-  const int32_t ep_len = h.run_len[e] + 1;
+  tracker_step(h.ep, e, lane, r, dn, info + (size_t)e * HRG_INFO_DIM, HRG_ROLLOUT_STATS_DIM, 0.0);   // Monitor's return: the step reward, no bootstrap term
   if (lane == 0) {
     const bool boot = dn && terminal_values != nullptr && info[(size_t)e * HRG_INFO_DIM + HRG_INFO_TRUNCATED] != 0;
     h.reward[s] = boot ? rollout_bootstrap(r, (float)p.gamma, terminal_values[e]) : r;
@@ -106,18 +85,12 @@ __global__ __launch_bounds__(64) void hrg_rollout_add_kernel(const hrg_rollout_d
     h.log_prob[s] = log_probs[e];
     h.ep_start[s] = h.flag[e];
     h.flag[e] = dn ? 1.0f : 0.0f;
-    h.run_ret[e] = dn ? 0.0 : ep_ret;
-    h.run_len[e] = dn ? 0 : ep_len;
-  }
-  if (dn && lane < HRG_ROLLOUT_STATS_DIM) {   // lane j adds column j of the env's episode accumulators
-    const double x = lane == 0 ? 1.0 : lane == 1 ? ep_ret : lane == 2 ? (double)ep_len : (double)info[(size_t)e * HRG_INFO_DIM + (lane - 3)];
-    h.acc[(size_t)e * HRG_ROLLOUT_STATS_DIM + lane] += x;
   }
 }
 
 // grid = ceil(n_envs / 256) blocks, one lane per env
-__global__ __launch_bounds__(HRG_ROLLOUT_BLOCK) void hrg_rollout_gae_kernel(const hrg_rollout_desc p, const RolloutDev h, const float* __restrict__ last_values) {
-  const int e = (int)(blockIdx.x * HRG_ROLLOUT_BLOCK + threadIdx.x);
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_rollout_gae_kernel(const hrg_rollout_desc p, const RolloutDev h, const float* __restrict__ last_values) {
+  const int e = (int)(blockIdx.x * HRG_BUFFER_BLOCK + threadIdx.x);
   if (e >= p.n_envs) return;
   const size_t n = (size_t)p.n_envs;
   const float g = (float)p.gamma, gl = (float)(p.gamma * p.gae_lambda);   // (the product in double, as Python takes it)
@@ -134,11 +107,11 @@ __global__ __launch_bounds__(HRG_ROLLOUT_BLOCK) void hrg_rollout_gae_kernel(cons
 }
 
 // grid = ceil(batch / 4) blocks of four wavefronts, one flat index (env * n_steps + step) each.  The indices are the caller's: not checked here.
-__global__ __launch_bounds__(HRG_ROLLOUT_BLOCK) void hrg_rollout_get_kernel(const hrg_rollout_desc p, const RolloutDev h, const int64_t* __restrict__ index, int batch,
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_rollout_get_kernel(const hrg_rollout_desc p, const RolloutDev h, const int64_t* __restrict__ index, int batch,
                                                                             float* __restrict__ o_obs, float* __restrict__ o_act, float* __restrict__ o_val,
                                                                             float* __restrict__ o_logp, float* __restrict__ o_adv, float* __restrict__ o_ret) {
   const int lane = (int)(threadIdx.x & 63);
-  const int k = (int)(blockIdx.x * (HRG_ROLLOUT_BLOCK / 64) + (threadIdx.x >> 6));
+  const int k = buffer_wave_item();
   if (k >= batch) return;
   const int64_t i = index[k];
   const int64_t e = i / p.n_steps, t = i - e * p.n_steps;

@@ -15,6 +15,8 @@ from collections import namedtuple
 import numpy as np
 
 from ._cstruct import CONST, HerDesc
+from ._device import DeviceHandle, check_columns
+from ._lib import _ptr
 
 # the fields SB3's SAC reads (stable_baselines3.common.type_aliases.DictReplayBufferSamples); observations / next_observations are dicts
 DictReplayBufferSamples = namedtuple("DictReplayBufferSamples", ["observations", "actions", "next_observations", "dones", "rewards"])
@@ -57,9 +59,7 @@ def build_her_desc(n_envs, capacity, horizon, goal_kind, obs_cols, act_dim=CONST
     if act_low is not None:
         for k in range(d.act_dim):
             d.act_low[k], d.act_high[k] = float(act_low[k]), float(act_high[k])
-    cols = [int(c) for c in obs_cols]
-    if not 1 <= len(cols) <= CONST["HRG_OBS_DIM"]:
-        raise NotImplementedError(f"her: an observation of {len(cols)} values (the sample kernel writes one value per lane: 1 .. {CONST['HRG_OBS_DIM']})")
+    cols = check_columns("her", obs_cols, ranges=False)   # (columns outside the superset and act_dim: hrg_her_create's refusals)
     d.n_obs_cols = len(cols)
     for k, c in enumerate(cols):
         d.obs_cols[k] = c
@@ -70,34 +70,20 @@ def build_her_desc(n_envs, capacity, horizon, goal_kind, obs_cols, act_dim=CONST
     return d
 
 
-class HerBuffer:
+class HerBuffer(DeviceHandle):
     """A device-resident hindsight replay buffer of `desc.n_envs` rings (hrg_her_desc; `build_her_desc`).  All arguments and results are torch tensors on
     the buffer's device; the calls are asynchronous, ordered on torch's current stream (`sample` waits for the prefix sum's total)."""
 
+    _create, _destroy = "hrg_her_create", "hrg_her_destroy"
+
     def __init__(self, desc, device=0):
-        import torch
-        from ._lib import _check, load_library
-        if not torch.cuda.is_available():
-            raise RuntimeError("HerBuffer needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.torch, self.lib, self._check = torch, load_library(), _check
-        self.desc = desc
-        self.device = torch.device("cuda", device)
+        self._open(desc, device)
         self.n, self.capacity, self.act_dim, self.obs_dim = int(desc.n_envs), int(desc.capacity), int(desc.act_dim), int(desc.n_obs_cols)
         self.ag_dim, self.dg_dim = AG_DIM.get(desc.goal_kind, 0), DG_DIM.get(desc.goal_kind, 0)
-        self.h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_her_create(ctypes.byref(desc), device, ctypes.byref(self.h)))
-            self.counts = torch.zeros(self.n, dtype=torch.int64, device=self.device)   # closed transitions per env, written by the add / observe kernels
+        with self.torch.cuda.device(self.device):
+            self.counts = self.torch.zeros(self.n, dtype=self.torch.int64, device=self.device)   # closed transitions per env, written by the add / observe kernels
         self.record_index = False   # tests: keep the (env, counter, goal counter) rows of the last sample() in `last_index`
         self.last_index = None
-
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _tensor(self, x, dtype, shape, what):
-        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        return ctypes.c_void_p(x.data_ptr())
 
     def observe(self, obs, mask=None):
         """The rows an episode starts from, after a reset: `obs` float32 [n, 64]; `mask` uint8 [n] (None: every env).  The unfinished episode of a masked
@@ -106,7 +92,7 @@ class HerBuffer:
         o = self._tensor(obs, t.float32, (self.n, CONST["HRG_OBS_DIM"]), "obs")
         m = None if mask is None else self._tensor(mask, t.uint8, (self.n,), "mask")
         with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_her_observe(self.h, o, m, ctypes.c_void_p(self.counts.data_ptr()), self._stream()))
+            self._check(self.lib, self.lib.hrg_her_observe(self.h, o, m, _ptr(self.counts), self._stream()))
 
     def add_step(self, actions, obs, term_obs, reward, done, info):
         """One transition per env, from the tensors a step wrote: `actions` float64 [n, 7] as the step left them, `obs` / `term_obs` float32 [n, 64], `reward`
@@ -116,7 +102,7 @@ class HerBuffer:
                 self._tensor(term_obs, t.float32, (self.n, C["HRG_OBS_DIM"]), "term_obs"), self._tensor(reward, t.float32, (self.n,), "reward"),
                 self._tensor(done, t.uint8, (self.n,), "done"), self._tensor(info, t.int32, (self.n, C["HRG_INFO_DIM"]), "info"))
         with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_her_add(self.h, *args, ctypes.c_void_p(self.counts.data_ptr()), self._stream()))
+            self._check(self.lib, self.lib.hrg_her_add(self.h, *args, _ptr(self.counts), self._stream()))
 
     def add(self, *args, **kwargs):
         """Nothing: the transition went into the buffer on the device when the env stepped.  Lets the object stand where an off-policy loop expects a
@@ -136,8 +122,7 @@ class HerBuffer:
             obs, ag, dg, nobs, nag, ndg = new(self.obs_dim), new(self.ag_dim), new(self.dg_dim), new(self.obs_dim), new(self.ag_dim), new(self.dg_dim)
             act, rew, done = new(self.act_dim), new(1), new(1)
             idx = t.empty(B, CONST["HRG_HER_INDEX_DIM"], dtype=t.int64, device=self.device) if self.record_index else None
-            p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())   # noqa: E731
-            self._check(self.lib, self.lib.hrg_her_sample(self.h, B, p(cum), p(obs), p(ag), p(dg), p(nobs), p(nag), p(ndg), p(act), p(rew), p(done), p(idx), self._stream()))
+            self._check(self.lib, self.lib.hrg_her_sample(self.h, B, *map(_ptr, (cum, obs, ag, dg, nobs, nag, ndg, act, rew, done, idx)), self._stream()))
         self.last_index = idx
         return DictReplayBufferSamples(observations=dict(observation=obs, achieved_goal=ag, desired_goal=dg), actions=act,
                                        next_observations=dict(observation=nobs, achieved_goal=nag, desired_goal=ndg), dones=done, rewards=rew)
@@ -151,8 +136,7 @@ class HerBuffer:
                 self._tensor(collision_type, t.int32, (n,), "collision_type"))
         reward, done = t.empty(n, dtype=t.float32, device=self.device), t.empty(n, dtype=t.uint8, device=self.device)
         with t.cuda.device(self.device):   # (the entry point launches on the current device)
-            self._check(self.lib, self.lib.hrg_goal_reward_done(ctypes.byref(self.desc), *args, n, ctypes.c_void_p(reward.data_ptr()), ctypes.c_void_p(done.data_ptr()),
-                                                                self._stream()))
+            self._check(self.lib, self.lib.hrg_goal_reward_done(ctypes.byref(self.desc), *args, n, _ptr(reward), _ptr(done), self._stream()))
         return reward, done.bool()
 
     def counts_host(self):
@@ -176,14 +160,3 @@ class HerBuffer:
         st = out.pop("state")
         out.update(w=int(st[0]), tail=int(st[1]), open=int(st[2]))
         return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.hrg_her_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

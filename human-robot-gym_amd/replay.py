@@ -18,6 +18,8 @@ from collections import namedtuple
 import numpy as np
 
 from ._cstruct import CONST, ReplayDesc
+from ._device import EpisodeBuffer, check_columns
+from ._lib import _ptr
 
 # the fields SB3's SAC.train reads (stable_baselines3.common.type_aliases.ReplayBufferSamples), in its order
 ReplayBufferSamples = namedtuple("ReplayBufferSamples", ["observations", "actions", "next_observations", "dones", "rewards"])
@@ -40,15 +42,8 @@ def build_replay_desc(n_envs, buffer_size, obs_cols, act_dim=CONST["HRG_ACT_DIM"
     n_envs, act_dim = int(n_envs), int(act_dim)
     if n_envs < 1 or int(buffer_size) < 1:
         raise ValueError(f"replay: n_envs = {n_envs} and buffer_size = {buffer_size} must be positive")
-    if not 1 <= act_dim <= CONST["HRG_ACT_DIM"]:
-        raise ValueError(f"replay: act_dim = {act_dim} outside 1 .. {CONST['HRG_ACT_DIM']}")
-    cols = [int(c) for c in obs_cols]
+    cols = check_columns("replay", obs_cols, act_dim, observe_time)
     K = len(cols) + int(bool(observe_time))
-    if not cols or not 1 <= K <= CONST["HRG_OBS_DIM"]:
-        raise NotImplementedError(f"replay: an observation of {K} values{' (time column included)' if observe_time else ''} (the kernels compute one value per lane: "
-                                  f"1 .. {CONST['HRG_OBS_DIM']}, at least one of them a column)")
-    if min(cols) < 0 or max(cols) >= CONST["HRG_OBS_DIM"]:
-        raise ValueError(f"replay: observation columns {sorted(set(c for c in cols if not 0 <= c < CONST['HRG_OBS_DIM']))} outside the superset")
     if (mean is None) != (std is None):
         raise ValueError("replay: mean and std come together")
     if squash_factor is not None and mean is None:
@@ -73,80 +68,31 @@ def build_replay_desc(n_envs, buffer_size, obs_cols, act_dim=CONST["HRG_ACT_DIM"
     return d
 
 
-class ReplayBuffer:
+class ReplayBuffer(EpisodeBuffer):
     """A device-resident replay buffer of `desc.capacity` slots, each one transition of every one of `desc.n_envs` envs (hrg_replay_desc;
     `build_replay_desc`).  All arguments and results are torch tensors on the buffer's device; the calls are asynchronous, ordered on torch's current
     stream (`episode_stats`, `export` and `memory_bytes` synchronise or read the handle).  `info_keys`: names of the info block's columns, for `episode_stats`."""
 
+    _prefix, _has_time, _stats_dim = "hrg_replay", True, STATS_DIM
+
     def __init__(self, desc, device=0, info_keys=None):
-        import torch
-        from ._lib import _check, load_library
-        if not torch.cuda.is_available():
-            raise RuntimeError("ReplayBuffer needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.torch, self.lib, self._check = torch, load_library(), _check
-        self.desc = desc
-        self.device = torch.device("cuda", device)
+        self._open(desc, device, info_keys)
         self.n, self.capacity, self.act_dim = int(desc.n_envs), int(desc.capacity), int(desc.act_dim)
         self.observe_time = bool(desc.observe_time)
         self.obs_dim = int(desc.n_obs_cols) + int(self.observe_time)   # K
-        if info_keys is None:
-            from .vec_env import INFO_KEYS
-            info_keys = INFO_KEYS
-        self.info_keys = list(info_keys)
-        self.h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_replay_create(ctypes.byref(desc), device, ctypes.byref(self.h)))
         self.pos, self.full = 0, False   # as the handle keeps them
         self.record_index = False        # tests: keep the (slot, env) rows of the last sample() in `last_index`
         self.last_index = None
 
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _tensor(self, x, dtype, shape, what):
-        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        return ctypes.c_void_p(x.data_ptr())
-
-    def _time(self, time, m, what):
-        if not self.observe_time:
-            return None
-        if time is None:
-            raise ValueError(f"{what}: the observation has a time column; pass the rows' time values (float32 [{m}])")
-        return self._tensor(time, self.torch.float32, (m,), what)
-
     def view(self, rows, time=None, out=None):
         """The policy's view of rows of the observation superset: float32 [m, 64] (and `time` float32 [m] when the observation has a time column) -> float32
         [m, K]: the columns, the time value, normalised and squashed as configured."""
-        t = self.torch
-        if rows.dim() != 2:
-            raise ValueError(f"rows: expected [m, {CONST['HRG_OBS_DIM']}], got {tuple(rows.shape)}")
-        m = int(rows.shape[0])
-        r = self._tensor(rows, t.float32, (m, CONST["HRG_OBS_DIM"]), "rows")
-        tm = self._time(time, m, "time")
-        if out is None:
-            out = t.empty(m, self.obs_dim, dtype=t.float32, device=self.device)
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_replay_view(self.h, r, tm, m, self._tensor(out, t.float32, (m, self.obs_dim), "out"), self._stream()))
-        return out
+        return self._view(rows, time, out)
 
     def observe(self, obs, time=None, mask=None):
         """The rows an episode starts from, after a reset: `obs` float32 [n, 64], `time` float32 [n] (with a time column); `mask` uint8 [n] (None: every
         env).  A masked env's running return and length start again."""
-        t = self.torch
-        o = self._tensor(obs, t.float32, (self.n, CONST["HRG_OBS_DIM"]), "obs")
-        tm = self._time(time, self.n, "time")
-        m = None if mask is None else self._tensor(mask, t.uint8, (self.n,), "mask")
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_replay_observe(self.h, o, tm, m, self._stream()))
-
-    def observation(self):
-        """The policy's view of every env's current row (SB3's _last_obs): float32 [n, K]."""
-        t = self.torch
-        out = t.empty(self.n, self.obs_dim, dtype=t.float32, device=self.device)
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_replay_view(self.h, None, None, self.n, ctypes.c_void_p(out.data_ptr()), self._stream()))
-        return out
+        self._observe(obs, time, mask)
 
     def add_step(self, actions, obs, term_obs, reward, done, info, imit=None, sir=None):
         """One transition per env, from the agent's actions and the tensors a step wrote: `actions` float32 [n, act_dim] at the policy's scale ([-1, 1]), `obs`
@@ -189,31 +135,13 @@ class ReplayBuffer:
                 lo, hi = indices.min(dim=0).values.tolist(), indices.max(dim=0).values.tolist()
                 if lo[0] < 0 or hi[0] >= upper or lo[1] < 0 or hi[1] >= self.n:
                     raise IndexError(f"indices: slots {lo[0]} .. {hi[0]}, envs {lo[1]} .. {hi[1]} outside the {upper} stored slots of {self.n} envs")
+        new = lambda w: t.empty(B, w, dtype=t.float32, device=self.device)   # noqa: E731
+        obs, act, nobs, done, rew = new(self.obs_dim), new(self.act_dim), new(self.obs_dim), new(1), new(1)
+        idx = t.empty(B, INDEX_DIM, dtype=t.int64, device=self.device) if self.record_index else None
         with t.cuda.device(self.device):
-            new = lambda w: t.empty(B, w, dtype=t.float32, device=self.device)   # noqa: E731
-            obs, act, nobs, done, rew = new(self.obs_dim), new(self.act_dim), new(self.obs_dim), new(1), new(1)
-            idx = t.empty(B, INDEX_DIM, dtype=t.int64, device=self.device) if self.record_index else None
-            p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())   # noqa: E731
-            self._check(self.lib, self.lib.hrg_replay_sample(self.h, B, pi, p(obs), p(act), p(nobs), p(done), p(rew), p(idx), self._stream()))
+            self._check(self.lib, self.lib.hrg_replay_sample(self.h, B, pi, *map(_ptr, (obs, act, nobs, done, rew, idx)), self._stream()))
         self.last_index = idx
         return ReplayBufferSamples(observations=obs, actions=act, next_observations=nobs, dones=done, rewards=rew)
-
-    def episode_stats_per_env(self, clear=True):
-        """float64 [n, HRG_REPLAY_STATS_DIM]: finished episodes, sum of returns, sum of lengths, sums of the info columns of their last steps, sum of their
-        imitation reward sums (synchronous)."""
-        acc = np.zeros((self.n, STATS_DIM), np.float64)
-        self._check(self.lib, self.lib.hrg_replay_stats(self.h, acc.ctypes.data_as(ctypes.c_void_p), int(bool(clear))))
-        return acc
-
-    def episode_stats(self, clear=True):
-        """The episodes that finished since the last clear, summed over the envs on the host: dict(episodes, r, l, **sums of the info columns at the
-        episodes' last steps, by key name, ep_im_rew) -- what safe_mean over SB3's ep_info_buffer and LoggingCallback._info_buffer divide by `episodes`; `r`
-        is Monitor's return (the env's own reward), `ep_im_rew` the sum of the infos' ep_im_rew_mean.  Synchronous."""
-        tot = self.episode_stats_per_env(clear).sum(axis=0)
-        out = dict(episodes=int(tot[0]), r=float(tot[1]), l=int(tot[2]))
-        out.update({k: float(v) for k, v in zip(self.info_keys, tot[3:3 + CONST["HRG_INFO_DIM"]])})
-        out["ep_im_rew"] = float(tot[3 + CONST["HRG_INFO_DIM"]])
-        return out
 
     def _size_words(self):
         w = (ctypes.c_int64 * 4)()
@@ -237,14 +165,3 @@ class ReplayBuffer:
         out = dict(zip(_EXPORT_KEYS, arrays))
         out.update(pos=int(state[0]), full=bool(state[1]), calls=int(state[2]))
         return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.hrg_replay_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -18,6 +18,8 @@ from collections import namedtuple
 import numpy as np
 
 from ._cstruct import CONST, RolloutDesc
+from ._device import EpisodeBuffer, check_columns
+from ._lib import _ptr
 
 # the fields SB3's PPO.train reads (stable_baselines3.common.type_aliases.RolloutBufferSamples)
 RolloutBufferSamples = namedtuple("RolloutBufferSamples", ["observations", "actions", "old_values", "old_log_prob", "advantages", "returns"])
@@ -32,15 +34,9 @@ def build_rollout_desc(n_envs, n_steps, obs_cols, act_dim=CONST["HRG_ACT_DIM"], 
     n_envs, n_steps, act_dim, gamma, gae_lambda = int(n_envs), int(n_steps), int(act_dim), float(gamma), float(gae_lambda)
     if n_envs < 1 or n_steps < 1:
         raise ValueError(f"rollout: n_envs = {n_envs} and n_steps = {n_steps} must be positive")
-    if not 1 <= act_dim <= CONST["HRG_ACT_DIM"]:
-        raise ValueError(f"rollout: act_dim = {act_dim} outside 1 .. {CONST['HRG_ACT_DIM']}")
     if not (0.0 <= gamma <= 1.0 and 0.0 <= gae_lambda <= 1.0):
         raise ValueError(f"rollout: gamma = {gamma} and gae_lambda = {gae_lambda} must lie in [0, 1]")
-    cols = [int(c) for c in obs_cols]
-    if not 1 <= len(cols) <= CONST["HRG_OBS_DIM"]:
-        raise NotImplementedError(f"rollout: an observation of {len(cols)} values (the kernels move one value per lane: 1 .. {CONST['HRG_OBS_DIM']})")
-    if min(cols) < 0 or max(cols) >= CONST["HRG_OBS_DIM"]:
-        raise ValueError(f"rollout: observation columns {sorted(set(c for c in cols if not 0 <= c < CONST['HRG_OBS_DIM']))} outside the superset")
+    cols = check_columns("rollout", obs_cols, act_dim)
     d = RolloutDesc()
     d.n_envs, d.n_steps, d.gamma, d.gae_lambda, d.act_dim, d.n_obs_cols = n_envs, n_steps, gamma, gae_lambda, act_dim, len(cols)
     for k, c in enumerate(cols):
@@ -48,28 +44,19 @@ def build_rollout_desc(n_envs, n_steps, obs_cols, act_dim=CONST["HRG_ACT_DIM"], 
     return d
 
 
-class RolloutBuffer:
+class RolloutBuffer(EpisodeBuffer):
     """A device-resident rollout buffer of `desc.n_steps` slots for each of `desc.n_envs` envs (hrg_rollout_desc; `build_rollout_desc`).  All arguments and
     results are torch tensors on the buffer's device; the calls are asynchronous, ordered on torch's current stream (`episode_stats` and `export`
     synchronise).  `info_keys`: names of the info block's columns, for `episode_stats`.  `seed`: of the generator `get` draws its permutations with."""
 
+    _prefix = "hrg_rollout"
+
     def __init__(self, desc, device=0, info_keys=None, seed=0):
-        import torch
-        from ._lib import _check, load_library
-        if not torch.cuda.is_available():
-            raise RuntimeError("RolloutBuffer needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.torch, self.lib, self._check = torch, load_library(), _check
-        self.desc = desc
-        self.device = torch.device("cuda", device)
+        self._open(desc, device, info_keys)
+        torch = self.torch
         self.n, self.n_steps, self.act_dim, self.obs_dim = int(desc.n_envs), int(desc.n_steps), int(desc.act_dim), int(desc.n_obs_cols)
         self.gamma, self.gae_lambda = float(desc.gamma), float(desc.gae_lambda)
-        if info_keys is None:
-            from .vec_env import INFO_KEYS
-            info_keys = INFO_KEYS
-        self.info_keys = list(info_keys)
-        self.h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_rollout_create(ctypes.byref(desc), device, ctypes.byref(self.h)))
             self.generator = torch.Generator(device=self.device)
             self.generator.manual_seed(int(seed))
         self.pos = 0               # slots written since the last reset()
@@ -79,14 +66,6 @@ class RolloutBuffer:
     def full(self):
         return self.pos == self.n_steps
 
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _tensor(self, x, dtype, shape, what):
-        if x.dtype != dtype or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{what}: expected a contiguous {dtype} tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        return ctypes.c_void_p(x.data_ptr())
-
     def _per_env(self, x, what):
         """A float32 value per env: [n] or [n, 1] (a value head's output), contiguous."""
         if x.dim() == 2 and x.shape[1] == 1:
@@ -95,33 +74,12 @@ class RolloutBuffer:
 
     def view(self, rows, out=None):
         """The policy's view of rows of the observation superset: float32 [m, 64] -> float32 [m, n_obs_cols] (value k = column obs_cols[k])."""
-        t = self.torch
-        if rows.dim() != 2:
-            raise ValueError(f"rows: expected [m, {CONST['HRG_OBS_DIM']}], got {tuple(rows.shape)}")
-        m = int(rows.shape[0])
-        r = self._tensor(rows, t.float32, (m, CONST["HRG_OBS_DIM"]), "rows")
-        if out is None:
-            out = t.empty(m, self.obs_dim, dtype=t.float32, device=self.device)
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_rollout_view(self.h, r, m, self._tensor(out, t.float32, (m, self.obs_dim), "out"), self._stream()))
-        return out
+        return self._view(rows, None, out)
 
     def observe(self, obs, mask=None):
         """The rows an episode starts from, after a reset: `obs` float32 [n, 64]; `mask` uint8 [n] (None: every env).  A masked env's next slot is an
         episode start, and its running return and length start again."""
-        t = self.torch
-        o = self._tensor(obs, t.float32, (self.n, CONST["HRG_OBS_DIM"]), "obs")
-        m = None if mask is None else self._tensor(mask, t.uint8, (self.n,), "mask")
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_rollout_observe(self.h, o, m, self._stream()))
-
-    def observation(self):
-        """The policy's view of every env's current row (SB3's _last_obs): float32 [n, n_obs_cols]."""
-        t = self.torch
-        out = t.empty(self.n, self.obs_dim, dtype=t.float32, device=self.device)
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_rollout_view(self.h, None, self.n, ctypes.c_void_p(out.data_ptr()), self._stream()))
-        return out
+        self._observe(obs, None, mask)
 
     def add_step(self, actions, values, log_probs, terminal_values, obs, term_obs, reward, done, info):
         """One slot per env, from the policy's outputs and the tensors a step wrote: `actions` float32 [n, act_dim] as the policy emitted them (not
@@ -156,7 +114,7 @@ class RolloutBuffer:
         new = lambda *shape: t.empty(*shape, dtype=t.float32, device=self.device)   # noqa: E731
         out = (new(B, self.obs_dim), new(B, self.act_dim), new(B), new(B), new(B), new(B))
         with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_rollout_get(self.h, ctypes.c_void_p(idx.data_ptr()), B, *(ctypes.c_void_p(x.data_ptr()) for x in out), self._stream()))
+            self._check(self.lib, self.lib.hrg_rollout_get(self.h, _ptr(idx), B, *map(_ptr, out), self._stream()))
         return RolloutBufferSamples(*out)
 
     def get(self, batch_size=None, generator=None, indices=None):
@@ -191,20 +149,6 @@ class RolloutBuffer:
         self._check(self.lib, self.lib.hrg_rollout_reset(self.h))
         self.pos = 0
 
-    def episode_stats_per_env(self, clear=True):
-        """float64 [n, 3 + HRG_INFO_DIM]: finished episodes, sum of returns, sum of lengths, sums of the info columns of their last steps (synchronous)."""
-        acc = np.zeros((self.n, STATS_DIM), np.float64)
-        self._check(self.lib, self.lib.hrg_rollout_stats(self.h, acc.ctypes.data_as(ctypes.c_void_p), int(bool(clear))))
-        return acc
-
-    def episode_stats(self, clear=True):
-        """The episodes that finished since the last clear, summed over the envs on the host: dict(episodes, r, l, **sums of the info columns at the
-        episodes' last steps, by key name) -- what safe_mean over SB3's ep_info_buffer and LoggingCallback._info_buffer divide by `episodes`.  Synchronous."""
-        tot = self.episode_stats_per_env(clear).sum(axis=0)
-        out = dict(episodes=int(tot[0]), r=float(tot[1]), l=int(tot[2]))
-        out.update({k: float(v) for k, v in zip(self.info_keys, tot[3:])})
-        return out
-
     def export(self):
         """Every array of the buffer on the host, in the flat order (synchronous; tests): dict of observations [N, n_obs_cols], actions [N, act_dim], rewards,
         values, log_probs, episode_starts, advantages, returns [N], cur_obs [n, 64], flags [n], run_return, run_length [n], stats [n, 3 + HRG_INFO_DIM],
@@ -218,14 +162,3 @@ class RolloutBuffer:
         out = dict(zip(_EXPORT_KEYS, arrays))
         out.update(pos=int(state[0]), computed=bool(state[1]))
         return out
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.hrg_rollout_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

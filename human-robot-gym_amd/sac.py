@@ -18,6 +18,8 @@ from collections import OrderedDict
 import numpy as np
 
 from ._cstruct import CONST, SacDesc
+from ._device import DeviceHandle
+from ._lib import _ptr
 
 HIDDEN = CONST["HRG_SAC_HIDDEN"]
 MAX_DEPTH = CONST["HRG_SAC_MAX_DEPTH"]
@@ -163,28 +165,22 @@ class SacParams:
         return flat[lo:hi]
 
 
-class SacLearner:
+class SacLearner(DeviceHandle):
     """SB3's SAC on the device for the shapes the kernels cover (`build_sac_desc` refuses the rest).  `learning_rate` is a plain attribute, passed with every
     step: a caller may schedule it.  All tensor arguments and results live on the learner's device; `step`, `train` and `act` are asynchronous, ordered on
     torch's current stream; `diagnostics` and `export` synchronise."""
 
+    _create, _destroy = "hrg_sac_create", "hrg_sac_destroy"
+
     def __init__(self, obs_dim, act_dim, net_arch=(64, 64, 64), learning_rate=3e-4, gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto",
                  batch_size=256, target_update_interval=1, seed=0, device=0):
-        self.desc = build_sac_desc(obs_dim, act_dim, net_arch=net_arch, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy,
-                                   batch_size=batch_size, target_update_interval=target_update_interval, seed=seed)
-        import torch
-        from ._lib import _check, load_library
-        if not torch.cuda.is_available():
-            raise RuntimeError("SacLearner needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
-        self.torch, self.lib, self._check = torch, load_library(), _check
-        self.device = torch.device("cuda", device)
+        desc = build_sac_desc(obs_dim, act_dim, net_arch=net_arch, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, batch_size=batch_size,
+                              target_update_interval=target_update_interval, seed=seed)
+        self._open(desc, device)
         self.obs_dim, self.act_dim, self.depth, self.batch_size = int(obs_dim), int(act_dim), int(self.desc.depth), int(batch_size)
         self.learning_rate = float(learning_rate)
         self.auto_ent_coef = bool(self.desc.auto_ent_coef)
         self.p = SacParams(obs_dim, act_dim, self.depth, seed=seed, ent_coef_init=self.desc.ent_coef, device=self.device)
-        self.h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(self.lib, self.lib.hrg_sac_create(ctypes.byref(self.desc), device, ctypes.byref(self.h)))
         sizes = self._sizes()
         if sizes[:3] != [self.p.n_params, self.p.n_actor, self.p.n_critic]:
             raise RuntimeError(f"SacLearner: the library lays out {sizes[:3]} parameters, sac.param_layout {[self.p.n_params, self.p.n_actor, self.p.n_critic]}: rebuild")
@@ -200,14 +196,8 @@ class SacLearner:
         """Gradient steps so far (SB3's _n_updates)."""
         return self._sizes()[3]
 
-    def _stream(self):
-        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def _tensor(self, x, shape, what):
-        t = self.torch
-        if x.dtype != t.float32 or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != tuple(shape):
-            raise ValueError(f"{what}: expected a contiguous float32 tensor {tuple(shape)} on {self.device}, got {x.dtype} {tuple(x.shape)} on {x.device}")
-        return ctypes.c_void_p(x.data_ptr())
+        return super()._tensor(x, self.torch.float32, shape, what)
 
     def step(self, batch, eps_pi=None, eps_next=None):
         """One gradient step on `batch`, a ReplayBufferSamples of `batch_size` rows (observations, next_observations [B, obs_dim], actions [B, act_dim], dones,
@@ -218,9 +208,8 @@ class SacLearner:
                 self._tensor(batch.next_observations, (B, K), "next_observations"), self._tensor(batch.dones, (B, 1), "dones"),
                 self._tensor(batch.rewards, (B, 1), "rewards"), None if eps_pi is None else self._tensor(eps_pi, (B, A), "eps_pi"),
                 None if eps_next is None else self._tensor(eps_next, (B, A), "eps_next"))
-        ptr = lambda x: ctypes.c_void_p(x.data_ptr())   # noqa: E731
         with self.torch.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_sac_step(self.h, *args, ptr(p.params), ptr(p.adam_m), ptr(p.adam_v), ptr(p.target), float(self.learning_rate), self._stream()))
+            self._check(self.lib, self.lib.hrg_sac_step(self.h, *args, _ptr(p.params), _ptr(p.adam_m), _ptr(p.adam_v), _ptr(p.target), float(self.learning_rate), self._stream()))
         self._keep = (batch, eps_pi, eps_next)
 
     def train(self, replay, gradient_steps):
@@ -241,8 +230,7 @@ class SacLearner:
         e = None if eps is None else self._tensor(eps, (n, self.act_dim), "eps")
         out = t.empty(n, self.act_dim, dtype=t.float32, device=self.device)
         with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_sac_act(self.h, ctypes.c_void_p(self.p.params.data_ptr()), o, n, e, int(bool(deterministic)),
-                                                       ctypes.c_void_p(out.data_ptr()), self._stream()))
+            self._check(self.lib, self.lib.hrg_sac_act(self.h, _ptr(self.p.params), o, n, e, int(bool(deterministic)), _ptr(out), self._stream()))
         return out
 
     def state_dict(self):
@@ -268,14 +256,3 @@ class SacLearner:
         losses = np.zeros(4, np.float32)
         self._check(self.lib, self.lib.hrg_sac_export(self.h, None, None, None, None, None, losses.ctypes.data_as(ctypes.c_void_p)))
         return dict(ent_coef=float(losses[3]), actor_loss=float(losses[0]), critic_loss=float(losses[1]), ent_coef_loss=float(losses[2]), n_updates=self.n_updates)
-
-    def close(self):
-        if getattr(self, "h", None) and self.h.value:
-            self.lib.hrg_sac_destroy(self.h)
-            self.h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

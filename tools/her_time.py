@@ -1,11 +1,11 @@
-"""What the device replay buffer costs (csrc/hrgym_her.h), written to profiles/r08_her.json:
+"""What the device replay buffer costs (csrc/hrgym_her.h), written to profiles/r08_her.json (or --out PATH):
   * ms per 4096-env ReachHuman step with and without the add kernel behind it: alternating blocks of 50 steps on ONE batch in one run (HIP events around each
     block), as tools/dataset_step_time.py; the step kernel is the same code object in both, and finished envs restart alike;
   * ms per sample() call at B = 256, 4096 and 65536 from a full buffer of 4096 x 256 transitions (wall clock over 20 calls each: a call reads the prefix sum's
     total back, so it ends with a stream synchronisation);
   * for the record, the host route this replaces: two observation rows per env, reward, done and info to the host every step, and a numpy gather +
     numpy compute_reward per batch.
-python tools/her_time.py [--host]"""
+python tools/her_time.py [--host] [--out PATH]"""
 import json
 import os
 import sys
@@ -103,8 +103,9 @@ if "--host" in sys.argv:   # the route this replaces
         torch.cuda.synchronize()
         out["host_sample_ms"][str(bs)] = 1e3 * (time.perf_counter() - t0) / 5
         print("host route, numpy gather + reward + upload of %d samples: %.3f ms per call" % (bs, out["host_sample_ms"][str(bs)]))
-os.makedirs("profiles", exist_ok=True)
-with open("profiles/r08_her.json", "w") as f:
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else "profiles/r08_her.json"
+os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+with open(out_path, "w") as f:
     json.dump(out, f, indent=1)
     f.write("\n")
 her.close()

@@ -1,11 +1,11 @@
-"""What the device replay buffer costs (csrc/hrgym_replay.h), written to profiles/r11_replay.json:
+"""What the device replay buffer costs (csrc/hrgym_replay.h), written to profiles/r11_replay.json (or --out PATH):
   * ms per 4096-env ReachHuman step with and without `add_step` behind it: alternating blocks of 100 steps (train_freq) on ONE batch in one run (HIP events
     around each block), as tools/rollout_time.py; the step kernel is the same code object in both, and finished envs restart alike.  Two layouts: the ICRA one
     (R-SAC.yaml: obs_keys [goal_difference], 6 values, dataset_obs_norm without squash) and, to set beside r10, the PPO layout of 18 plain values;
   * ms per sample(128) and sample(4096) on a full buffer of 1 000 000 transitions (HIP events around 200 calls), and the bytes each call moves against the
     card's HBM figure;
   * the bytes the buffer holds for the ICRA buffer_size at 4096 envs.
-python tools/replay_time.py"""
+python tools/replay_time.py [--out PATH]"""
 import json
 import os
 import sys
@@ -85,7 +85,8 @@ for name, lay in layouts.items():
     out[name] = res
     rb.close()
 B.close()
-os.makedirs("profiles", exist_ok=True)
-with open("profiles/r11_replay.json", "w") as f:
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else "profiles/r11_replay.json"
+os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+with open(out_path, "w") as f:
     json.dump(out, f, indent=1)
     f.write("\n")

@@ -1,11 +1,11 @@
-"""What the device rollout buffer costs (csrc/hrgym_rollout.h), written to profiles/r10_rollout.json:
+"""What the device rollout buffer costs (csrc/hrgym_rollout.h), written to profiles/r10_rollout.json (or --out PATH):
   * ms per 4096-env ReachHuman step with and without `view(term_obs)` + `add_step` behind it: alternating blocks of 64 steps (one rollout) on ONE batch in one
     run (HIP events around each block), as tools/her_time.py; the step kernel is the same code object in both, and finished envs restart alike;
   * ms per compute_returns_and_advantage at T = 64 (HIP events around 20 calls);
   * ms per epoch of get() at B = 4096: one randperm and 64 gathers over the 262144 samples (HIP events around each of 5 epochs);
   * with --host, for the record, the host route an on-policy learner takes without the buffer (unchanged by it): HipVecEnv.step for 64 steps, the packed block
     to pinned memory and the numpy views and info dicts every step (wall clock; every step ends in a blocking copy).
-python tools/rollout_time.py [--host]"""
+python tools/rollout_time.py [--host] [--out PATH]"""
 import json
 import os
 import sys
@@ -97,7 +97,8 @@ if "--host" in sys.argv:   # the route without the buffer
     print("host route, HipVecEnv.step x %d (block to pinned memory, numpy views, info dicts; no policy, no buffer): %.2f ms, %.3f ms per step"
           % (T, out["host_rollout_ms"], out["host_step_ms"]))
     env.close()
-os.makedirs("profiles", exist_ok=True)
-with open("profiles/r10_rollout.json", "w") as f:
+out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else "profiles/r10_rollout.json"
+os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+with open(out_path, "w") as f:
     json.dump(out, f, indent=1)
     f.write("\n")
