@@ -17,7 +17,7 @@ def __getattr__(name):
     if name == "make_vec_env":
         from .env_util import make_vec_env
         return make_vec_env
-    if name in ("create_training_vec_env", "compose_environment_kwargs", "wrapper_kwargs_from_config", "her_kwargs_from_config", "rollout_kwargs_from_config", "replay_kwargs_from_config", "sac_kwargs_from_config"):
+    if name in ("create_training_vec_env", "compose_environment_kwargs", "wrapper_kwargs_from_config", "her_kwargs_from_config", "rollout_kwargs_from_config", "replay_kwargs_from_config", "sac_kwargs_from_config", "ppo_kwargs_from_config"):
         from . import training_utils
         return getattr(training_utils, name)
     if name in ("MixedBatch", "MixedHipVecEnv", "make_mixed_batch", "make_mixed_vec_env", "ICRA_TASKS"):
@@ -38,6 +38,9 @@ def __getattr__(name):
     if name == "SacLearner":
         from .sac import SacLearner
         return SacLearner
+    if name == "PpoLearner":
+        from .ppo import PpoLearner
+        return PpoLearner
     if name == "HipBatch":
         from ._lib import HipBatch
         return HipBatch

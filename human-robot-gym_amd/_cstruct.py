@@ -116,6 +116,7 @@ HerDesc = _STRUCTS["hrg_her_desc"]
 RolloutDesc = _STRUCTS["hrg_rollout_desc"]
 ReplayDesc = _STRUCTS["hrg_replay_desc"]
 SacDesc = _STRUCTS["hrg_sac_desc"]
+PpoDesc = _STRUCTS["hrg_ppo_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 
 

@@ -7,7 +7,7 @@ import ctypes
 import os
 import subprocess
 
-from ._cstruct import CONST, PROTOTYPES, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc, DatasetDesc, HerDesc, RolloutDesc, ReplayDesc, SacDesc  # noqa: F401
+from ._cstruct import CONST, PROTOTYPES, EnvState, BoxState, StackState, HammerState, ModelDesc, ClipTable, ExpertDesc, DatasetDesc, HerDesc, RolloutDesc, ReplayDesc, SacDesc, PpoDesc  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhrgym_hip.so")   # the one shipping library; no environment variable redirects it
@@ -24,7 +24,7 @@ EXPORTS = list(PROTOTYPES)   # every function include/hrgym.h declares
 
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h", "hrgym_dataset.h", "hrgym_buffer.h", "hrgym_her.h", "hrgym_rollout.h", "hrgym_replay.h", "hrgym_sac.h")] + [
+    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h", "hrgym_dataset.h", "hrgym_buffer.h", "hrgym_her.h", "hrgym_rollout.h", "hrgym_replay.h", "hrgym_sac.h", "hrgym_ppo.h")] + [
         os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH

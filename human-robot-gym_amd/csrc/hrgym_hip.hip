@@ -3085,6 +3085,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_rollout.h"  // the PPO rollout buffer: observe / add / GAE / get kernels (hrg_rollout_*)
 #include "hrgym_replay.h"   // the uniform replay buffer of SAC: observe / add / sample kernels (hrg_replay_*)
 #include "hrgym_sac.h"      // the SAC gradient step and the actor's forward pass: policy / critic / actor / Adam kernels (hrg_sac_*)
+#include "hrgym_ppo.h"      // the PPO minibatch step and the policy's forward pass: advantage / gradient / reduce / Adam kernels (hrg_ppo_*)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -4354,6 +4355,146 @@ int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next
   if (q_host) HIPCHK(hipMemcpy(q_host, d.q, SAC_NQ * B, hipMemcpyDeviceToHost));
   if (grad_host) HIPCHK(hipMemcpy(grad_host, d.grad, (size_t)d.n_params * sizeof(float), hipMemcpyDeviceToHost));
   if (losses_host) HIPCHK(hipMemcpy(losses_host, d.losses, 4 * sizeof(float), hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+// ---- PPO learner (csrc/hrgym_ppo.h) ----
+struct hrg_ppo {
+  int device = 0;
+  hrg_ppo_desc desc;
+  PpoDev d;
+  uint64_t steps = 0;           // minibatch steps so far: Adam's step count
+  uint64_t forward_calls = 0;   // forward calls that drew their noise
+  int n_blocks = 0;             // blocks of 256 parameters
+  DeviceMem mem;
+  float* scratch = nullptr;     // one allocation behind every float pointer of `d`
+  double* dscratch = nullptr;   // ... every double pointer
+};
+
+// the offsets of the parameter layout (csrc/hrgym_ppo.h) into d; returns the number of parameters
+static int32_t ppo_layout(const hrg_ppo_desc& c, PpoDev& d) {
+  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_PPO_HIDDEN;
+  int32_t o = 0;
+  for (int n = 0; n < d.nets; n++)
+    for (int l = 0; l < c.depth; l++) {
+      d.w[n][l] = o; o += H * (l ? H : K);
+      d.b[n][l] = o; o += H;
+    }
+  d.hw = o; o += (A + 1) * H;
+  d.hb = o; o += A + 1;
+  d.ls = o; o += A;
+  d.n_params = o;
+  return o;
+}
+
+int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->use_sde) return fail(HRG_ERR_UNSUPPORTED, "ppo: use_sde: state dependent exploration is not covered");
+  if (desc->target_kl_set) return fail(HRG_ERR_UNSUPPORTED, "ppo: target_kl: the early stop needs a host readback per minibatch");
+  if (desc->policy != HRG_PPO_MLP_POLICY) return fail(HRG_ERR_UNSUPPORTED, "ppo: policy = " + std::to_string(desc->policy) + ": the kernels cover MlpPolicy");
+  if (desc->hidden != HRG_PPO_HIDDEN) return fail(HRG_ERR_UNSUPPORTED, "ppo: hidden = " + std::to_string(desc->hidden) + ": the kernels cover hidden width 64 only");
+  if (desc->depth < 1 || desc->depth > HRG_PPO_MAX_DEPTH) return fail(HRG_ERR_UNSUPPORTED, "ppo: depth = " + std::to_string(desc->depth) + " outside 1 .. 3");
+  if (desc->separate != 0 && desc->separate != 1) return fail(HRG_ERR_UNSUPPORTED, "ppo: separate must be 0 (shared trunk) or 1 (separate trunks)");
+  if (desc->obs_dim < 1 || desc->obs_dim > HRG_OBS_DIM) return fail(HRG_ERR_UNSUPPORTED, "ppo: obs_dim = " + std::to_string(desc->obs_dim) + " outside 1 .. HRG_OBS_DIM");
+  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_UNSUPPORTED, "ppo: act_dim = " + std::to_string(desc->act_dim) + " outside 1 .. HRG_ACT_DIM");
+  if (desc->batch_size < HRG_PPO_TILE || desc->batch_size > HRG_PPO_MAX_BATCH || desc->batch_size % HRG_PPO_TILE)
+    return fail(HRG_ERR_UNSUPPORTED, "ppo: batch_size = " + std::to_string(desc->batch_size) + " is not a multiple of 32 in 32 .. 4096");
+  if (desc->rollout_size < 0 || desc->rollout_size % desc->batch_size)
+    return fail(HRG_ERR_UNSUPPORTED, "ppo: rollout_size = " + std::to_string(desc->rollout_size) + " is not divisible by batch_size = " + std::to_string(desc->batch_size) +
+                                         ": the learner takes no short last minibatch");
+  if (!std::isfinite(desc->ent_coef) || !std::isfinite(desc->vf_coef) || !std::isfinite(desc->max_grad_norm) || desc->ent_coef < 0.0 || desc->vf_coef < 0.0 ||
+      desc->max_grad_norm <= 0.0)
+    return fail(HRG_ERR_INVALID, "ppo: ent_coef and vf_coef must be finite and not negative, max_grad_norm finite and positive");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_ppo> h(new hrg_ppo());
+  h->device = device;
+  h->desc = *desc;
+  PpoDev& d = h->d;
+  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_PPO_TILE;
+  d.nets = desc->separate ? 2 : 1;
+  d.normalize = desc->normalize_advantage ? 1 : 0;
+  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm; d.seed = desc->seed;
+  const size_t P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;
+  h->n_blocks = (int)((P + PPO_BLOCK - 1) / PPO_BLOCK);
+  const size_t n_float = 3 * B + (size_t)d.tiles * P + P + (size_t)d.tiles * PPO_NPART + HRG_PPO_NDIAG;
+  if (!h->mem.zeros(h->scratch, n_float) || !h->mem.zeros(h->dscratch, 2 + (size_t)h->n_blocks)) return nomem("ppo", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  float* p = h->scratch;
+  d.values = p; p += B;
+  d.logp = p; p += B;
+  d.ratio = p; p += B;
+  d.part = p; p += (size_t)d.tiles * P;
+  d.grad = p; p += P;
+  d.loss_part = p; p += (size_t)d.tiles * PPO_NPART;
+  d.diag = p;
+  d.adv_stat = h->dscratch;
+  d.block_sq = h->dscratch + 2;
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_ppo_destroy(hrg_ppo* h) { destroy_handle(h); }
+
+int hrg_ppo_sizes(hrg_ppo* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_params;
+  size_host[1] = h->d.nets == 2 ? h->d.w[1][0] : h->d.hw;   // (the first network starts at 0)
+  size_host[2] = h->d.nets;
+  size_host[3] = (int64_t)h->steps;
+  size_host[4] = (int64_t)h->forward_calls;
+  size_host[5] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions_dev, const float* old_values_dev, const float* old_log_prob_dev,
+                 const float* advantages_dev, const float* returns_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, double learning_rate, double clip_range,
+                 double clip_range_vf, void* stream) {
+  if (!h || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev || !params_dev || !adam_m_dev || !adam_v_dev)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "ppo: learning_rate must be finite and not negative");
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(HRG_ERR_INVALID, "ppo: clip_range must be finite and positive");
+  if (std::isnan(clip_range_vf)) return fail(HRG_ERR_INVALID, "ppo: clip_range_vf must be a number (negative: no clipping)");
+  HIPCHK(hipSetDevice(h->device));
+  const PpoDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(PPO_BLOCK), flat((unsigned)h->n_blocks);
+  const double t = (double)(h->steps + 1), bc1 = 1.0 - std::pow(0.9, t), bc2 = 1.0 - std::pow(0.999, t);   // Adam's bias corrections, by the optimiser's step count
+  if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1), block, 0, st, d, advantages_dev);
+  hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
+                     old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
+  hipLaunchKernelGGL(hrg_ppo_reduce_kernel, flat, block, 0, st, d);
+  hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, learning_rate, bc1, bc2);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                    float* values_dev, float* log_probs_dev, void* stream) {
+  if (!h || !params_dev || !obs_dev || !values_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (actions_dev && !log_probs_dev) return fail(HRG_ERR_INVALID, "ppo: actions without log_probs");
+  if (n < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  const int value_only = actions_dev ? 0 : 1;
+  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + SAC_T - 1) / SAC_T, value_only ? 1u : (unsigned)h->d.nets), dim3(PPO_BLOCK), 0, (hipStream_t)stream, h->d,
+                     params_dev, obs_dev, (int)n, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev, log_probs_dev);
+  HIPCHK(hipGetLastError());
+  if (!value_only && !deterministic && !eps_dev) h->forward_calls++;
+  return HRG_OK;
+}
+
+int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const PpoDev& d = h->d;
+  const size_t B = (size_t)d.B * sizeof(float);
+  if (values_host) HIPCHK(hipMemcpy(values_host, d.values, B, hipMemcpyDeviceToHost));
+  if (log_prob_host) HIPCHK(hipMemcpy(log_prob_host, d.logp, B, hipMemcpyDeviceToHost));
+  if (ratio_host) HIPCHK(hipMemcpy(ratio_host, d.ratio, B, hipMemcpyDeviceToHost));
+  if (grad_host) HIPCHK(hipMemcpy(grad_host, d.grad, (size_t)d.n_params * sizeof(float), hipMemcpyDeviceToHost));
+  if (diag_host) HIPCHK(hipMemcpy(diag_host, d.diag, HRG_PPO_NDIAG * sizeof(float), hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 

@@ -76,14 +76,17 @@ struct SacLds {
   float row[4][SAC_T];          // per-row scalars
 };
 
-// ---- products on a tile.  Every thread of the workgroup calls them; the caller places the barriers.
+// ---- products on a tile.  Every thread of the workgroup calls them; the caller places the barriers.  hrgym_ppo.h runs the same products with tanh units:
+// `act` is a layer's activation, a constant at every call.  The tanh stores are loops of their own in front of the ReLU / linear ones, which stand as they stood: in
+// that form the SAC kernels compile to the instructions they had before the parameter.
+enum { SAC_ACT_NONE = 0, SAC_ACT_RELU = 1, SAC_ACT_TANH = 2 };   // tanh: evaluated in double on the double accumulator, rounded once
 // Ws[j][k] = Wg[j * in + k]
 DI void sac_stage(float* Ws, const float* __restrict__ Wg, int nout, int in) {
   for (int i = (int)threadIdx.x; i < nout * in; i += (int)blockDim.x) Ws[(i / in) * SAC_WLD + (i % in)] = Wg[i];
 }
 
 // out[r][j] = act(b[j] + sum_k X[r][k] Ws[j][k]), k ascending.  An item is a row and eight consecutive outputs.
-DI void sac_forward(const float* X, int ldx, int in, const float* Ws, const float* __restrict__ bg, int nout, bool relu, float* out, int ldo) {
+DI void sac_forward(const float* X, int ldx, int in, const float* Ws, const float* __restrict__ bg, int nout, int act, float* out, int ldo) {
   const int groups = (nout + 7) >> 3;
   for (int it = (int)threadIdx.x; it < SAC_T * groups; it += (int)blockDim.x) {
     const int r = it % SAC_T, j0 = (it / SAC_T) << 3, jn = min(8, nout - j0);
@@ -96,15 +99,22 @@ DI void sac_forward(const float* X, int ldx, int in, const float* Ws, const floa
       for (int jj = 0; jj < 8; jj++)
         if (jj < jn) acc[jj] = fma((double)Ws[(j0 + jj) * SAC_WLD + k], (double)x, acc[jj]);
     }
+    if (act == SAC_ACT_TANH) {
+#pragma unroll
+      for (int jj = 0; jj < 8; jj++)
+        if (jj < jn) out[r * ldo + j0 + jj] = (float)tanh(acc[jj]);
+      continue;
+    }
+    const bool relu = act == SAC_ACT_RELU;
 #pragma unroll
     for (int jj = 0; jj < 8; jj++)
       if (jj < jn) out[r * ldo + j0 + jj] = relu ? fmaxf((float)acc[jj], 0.0f) : (float)acc[jj];
   }
 }
 
-// dst[r][k - k_lo] = sum_j dP[r][j] Ws[j][k] for k_lo <= k < in, j ascending; with `mask`, dst holds the ReLU output the gradient passes through and becomes the
-// gradient at its input (0 where the unit was off).  An item is a row and eight consecutive k.
-DI void sac_backward_x(const float* dP, int ldp, int nout, const float* Ws, int in, int k_lo, float* dst, int ldd, bool mask) {
+// dst[r][k - k_lo] = sum_j dP[r][j] Ws[j][k] for k_lo <= k < in, j ascending; with an activation, dst holds the unit's output h the gradient passes through and
+// becomes the gradient at its input (ReLU: 0 where the unit was off; tanh: times 1 - h^2).  An item is a row and eight consecutive k.
+DI void sac_backward_x(const float* dP, int ldp, int nout, const float* Ws, int in, int k_lo, float* dst, int ldd, int act) {
   const int groups = (in - k_lo + 7) >> 3;
   for (int it = (int)threadIdx.x; it < SAC_T * groups; it += (int)blockDim.x) {
     const int r = it % SAC_T, k0 = k_lo + ((it / SAC_T) << 3), kn = min(8, in - k0);
@@ -117,6 +127,16 @@ DI void sac_backward_x(const float* dP, int ldp, int nout, const float* Ws, int 
       for (int kk = 0; kk < 8; kk++)
         if (kk < kn) acc[kk] = fma((double)Ws[j * SAC_WLD + k0 + kk], (double)d, acc[kk]);
     }
+    if (act == SAC_ACT_TANH) {
+#pragma unroll
+      for (int kk = 0; kk < 8; kk++)
+        if (kk < kn) {
+          float* p = dst + r * ldd + (k0 - k_lo) + kk;
+          *p = (float)(acc[kk] * (1.0 - (double)*p * (double)*p));
+        }
+      continue;
+    }
+    const bool mask = act == SAC_ACT_RELU;
 #pragma unroll
     for (int kk = 0; kk < 8; kk++)
       if (kk < kn) {
@@ -142,13 +162,13 @@ DI void sac_weight_grad(const float* dP, int ldp, int nout, const float* X, int 
 }
 
 // the hidden layers: s.X [.][in0] -> s.H[0 .. depth - 1].  Ends with a barrier.
-DI void sac_trunk(SacLds& s, const float* __restrict__ P, const int32_t* w, const int32_t* b, int depth, int in0) {
+DI void sac_trunk(SacLds& s, const float* __restrict__ P, const int32_t* w, const int32_t* b, int depth, int in0, int act = SAC_ACT_RELU) {
   for (int l = 0; l < depth; l++) {
     const int in = l ? SAC_H : in0;
     __syncthreads();   // the input is written, the previous layer's weights are read
     sac_stage(s.W, P + w[l], SAC_H, in);
     __syncthreads();
-    sac_forward(l ? s.H[l - 1] : s.X, l ? SAC_HLD : SAC_XLD, in, s.W, P + b[l], SAC_H, true, s.H[l], SAC_HLD);
+    sac_forward(l ? s.H[l - 1] : s.X, l ? SAC_HLD : SAC_XLD, in, s.W, P + b[l], SAC_H, act, s.H[l], SAC_HLD);
   }
   __syncthreads();
 }
@@ -157,7 +177,7 @@ DI void sac_trunk(SacLds& s, const float* __restrict__ P, const int32_t* w, cons
 DI void sac_head(SacLds& s, const float* __restrict__ P, int w, int b, int depth, int nout) {
   sac_stage(s.W, P + w, nout, SAC_H);   // (the trunk's barrier is behind the last read of s.W)
   __syncthreads();
-  sac_forward(s.H[depth - 1], SAC_HLD, SAC_H, s.W, P + b, nout, false, s.D, SAC_DLD);
+  sac_forward(s.H[depth - 1], SAC_HLD, SAC_H, s.W, P + b, nout, SAC_ACT_NONE, s.D, SAC_DLD);
   __syncthreads();
 }
 
@@ -165,11 +185,11 @@ DI void sac_head(SacLds& s, const float* __restrict__ P, int w, int b, int depth
 // offsets of the parameters.  With `to_input` (0 or a first column k_lo + 1) the gradient at columns k_lo .. in0 - 1 of the input goes to s.D instead of the first
 // layer's weight gradient being the end; `weights` = false skips every weight gradient (the actor's pass through a critic).  Ends with a barrier.
 DI void sac_backward(SacLds& s, const float* __restrict__ P, const int32_t* w, const int32_t* b, int hw, int hb, int depth, int in0, int nout, float* g, bool weights,
-                     int k_lo_plus1) {
+                     int k_lo_plus1, int act = SAC_ACT_RELU) {
   if (weights) sac_weight_grad(s.D, SAC_DLD, nout, s.H[depth - 1], SAC_HLD, SAC_H, g + hw, g + hb);
   sac_stage(s.W, P + hw, nout, SAC_H);
   __syncthreads();
-  sac_backward_x(s.D, SAC_DLD, nout, s.W, SAC_H, 0, s.H[depth - 1], SAC_HLD, true);
+  sac_backward_x(s.D, SAC_DLD, nout, s.W, SAC_H, 0, s.H[depth - 1], SAC_HLD, act);
   __syncthreads();
   for (int l = depth - 1; l >= 0; l--) {   // s.H[l] holds the gradient at layer l's pre-activation
     const int in = l ? SAC_H : in0;
@@ -177,8 +197,8 @@ DI void sac_backward(SacLds& s, const float* __restrict__ P, const int32_t* w, c
     if (l == 0 && !k_lo_plus1) break;
     sac_stage(s.W, P + w[l], SAC_H, in);
     __syncthreads();
-    if (l) sac_backward_x(s.H[l], SAC_HLD, SAC_H, s.W, SAC_H, 0, s.H[l - 1], SAC_HLD, true);
-    else sac_backward_x(s.H[0], SAC_HLD, SAC_H, s.W, in0, k_lo_plus1 - 1, s.D, SAC_DLD, false);
+    if (l) sac_backward_x(s.H[l], SAC_HLD, SAC_H, s.W, SAC_H, 0, s.H[l - 1], SAC_HLD, act);
+    else sac_backward_x(s.H[0], SAC_HLD, SAC_H, s.W, in0, k_lo_plus1 - 1, s.D, SAC_DLD, SAC_ACT_NONE);
     __syncthreads();
   }
   __syncthreads();

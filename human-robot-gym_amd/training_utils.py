@@ -238,6 +238,42 @@ def sac_kwargs_from_config(config) -> Dict[str, Any]:
     return kw
 
 
+def ppo_kwargs_from_config(config) -> Dict[str, Any]:
+    """`config.algorithm` of a PPO run (training/config/algorithm/ppo.yaml) -> the keyword arguments of HipVecEnv.attach_ppo / ppo.PpoLearner: net_arch,
+    learning_rate, batch_size, n_epochs, clip_range, clip_range_vf, normalize_advantage, ent_coef, vf_coef, max_grad_norm, log_std_init, ortho_init, seed
+    (missing keys take SB3's PPO defaults).  What the kernels do not cover is refused by the name of its key: use_sde, target_kl, policy,
+    policy_kwargs.net_arch, any other policy_kwargs key.  policy_kwargs.full_std, use_expln and squash_output are dropped: in SB3 1.5.0 they reach gSDE and
+    predict() only.  n_steps, gamma and gae_lambda belong to the buffer (rollout_kwargs_from_config), sde_sample_freq to gSDE."""
+    alg = _get(config, "algorithm")
+    if str(_get(alg, "name", "PPO")).upper() != "PPO":
+        raise NotImplementedError(f"algorithm.name = {_get(alg, 'name')}: the device learner is PPO")
+    if _get(alg, "policy", "MlpPolicy") != "MlpPolicy":
+        raise NotImplementedError(f"algorithm.policy = {_get(alg, 'policy')}: the device learner covers MlpPolicy")
+    if _get(alg, "use_sde", False):
+        raise NotImplementedError("algorithm.use_sde = true: state dependent exploration is not covered by the device learner")
+    if _get(alg, "target_kl") is not None:
+        raise NotImplementedError(f"algorithm.target_kl = {_get(alg, 'target_kl')}: the early stop needs a host readback per minibatch; the device learner runs every epoch")
+    from .ppo import IGNORED_POLICY_KWARGS, parse_net_arch
+    pk = _plain(_get(alg, "policy_kwargs")) or {}
+    net_arch = pk.get("net_arch", [dict(pi=[64, 64], vf=[64, 64])])   # SB3's default for an ActorCriticPolicy
+    try:
+        parse_net_arch(net_arch)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"algorithm.policy_kwargs.net_arch: {e}") from None
+    unknown = sorted(set(pk) - {"net_arch", "log_std_init", "ortho_init"} - set(IGNORED_POLICY_KWARGS))
+    if unknown:
+        raise NotImplementedError(f"algorithm.policy_kwargs {unknown}: the device learner takes net_arch, log_std_init and ortho_init")
+    clip_range_vf = _get(alg, "clip_range_vf")
+    kw: Dict[str, Any] = dict(net_arch=net_arch, learning_rate=float(_get(alg, "learning_rate", 3e-4)), batch_size=int(_get(alg, "batch_size", 64)),
+                              n_epochs=int(_get(alg, "n_epochs", 10)), clip_range=float(_get(alg, "clip_range", 0.2)),
+                              clip_range_vf=None if clip_range_vf is None else float(clip_range_vf), normalize_advantage=bool(_get(alg, "normalize_advantage", True)),
+                              ent_coef=float(_get(alg, "ent_coef", 0.0)), vf_coef=float(_get(alg, "vf_coef", 0.5)), max_grad_norm=float(_get(alg, "max_grad_norm", 0.5)),
+                              log_std_init=float(pk.get("log_std_init", 0.0)), ortho_init=bool(pk.get("ortho_init", True)))
+    if _get(alg, "seed") is not None:
+        kw["seed"] = int(_get(alg, "seed"))
+    return kw
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""

@@ -549,6 +549,7 @@ class HipVecEnv(_VecEnvBase):
         self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
         self._replay_args = None     # arguments of attach_replay, likewise
         self.sac = None              # the SAC learner (sac.SacLearner), once attached
+        self.ppo = None              # the PPO learner (ppo.PpoLearner), once attached
         self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
 
     def _init_obs_norm(self, obs_norm=None):
@@ -738,6 +739,9 @@ class HipVecEnv(_VecEnvBase):
         if self.sac is not None:
             self.sac.close()
             self.sac = None
+        if self.ppo is not None:
+            self.ppo.close()
+            self.ppo = None
         self._backend.close()
 
     def seed(self, seed=None):
@@ -984,6 +988,22 @@ class HipVecEnv(_VecEnvBase):
             rb.add_step(actions, values, log_probs, terminal_values, b.obs, b.term_obs, b.reward, b.done, b.info)
         rb.compute_returns_and_advantage(value_fn(rb.observation()))
         return rb
+
+    def attach_ppo(self, **kwargs):
+        """The PPO learner on the device next to the rollout buffer (ppo.PpoLearner; its keywords: net_arch, learning_rate, batch_size, n_epochs, clip_range,
+        clip_range_vf, normalize_advantage, ent_coef, vf_coef, max_grad_norm, log_std_init, ortho_init, seed).  Needs attach_rollout first: `obs_dim`, `act_dim`
+        and the rollout's size are the buffer's, and batch_size must divide n_envs * n_steps.  Returns the learner and keeps it as `env.ppo`:
+        `env.collect_rollout(env.ppo.policy, env.ppo.value)`, then `env.ppo.train(env.rollout)`."""
+        rb = self.rollout
+        if rb is None:
+            raise NotImplementedError("attach_ppo: call attach_rollout(n_steps, gamma, gae_lambda) first (the learner takes its observation and action widths from the buffer)")
+        from .ppo import PpoLearner
+        kwargs.setdefault("seed", int(self._desc.seed))
+        learner = PpoLearner(rb.obs_dim, rb.act_dim, device=rb.device.index, rollout_size=rb.n * rb.n_steps, **kwargs)
+        if self.ppo is not None:
+            self.ppo.close()
+        self.ppo = learner
+        return learner
 
     def _enter_device_loop(self, name, account):
         """What collect_rollout and collect_steps share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs -- to a dataset

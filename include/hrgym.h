@@ -534,11 +534,38 @@ typedef struct hrg_sac_desc {
   uint64_t seed;                  /* key of the noise draws */
 } hrg_sac_desc;
 
+/* ------------------------------------------------------------------------- the PPO learner on the device (POD) */
+#define HRG_PPO_HIDDEN HRG_SAC_HIDDEN       /* hidden width the kernels cover */
+#define HRG_PPO_MAX_DEPTH HRG_SAC_MAX_DEPTH /* hidden layers: 1 .. 3 */
+#define HRG_PPO_TILE HRG_SAC_TILE           /* rows of the minibatch per workgroup: batch_size is a multiple */
+#define HRG_PPO_MAX_BATCH 4096
+#define HRG_PPO_NDIAG 8                     /* floats of hrg_ppo_export's diag */
+#define HRG_PPO_MLP_POLICY 0                /* hrg_ppo_desc.policy: SB3's "MlpPolicy", the only one covered */
+/* One learner: SB3 1.5.0's PPO(MlpPolicy, use_sde = False) with net_arch = [64] * depth (separate = 0: the shared trunk) or [dict(pi = [64] * depth, vf = [64] * depth)]
+ * (separate = 1).  The learning rate and the two clip ranges are arguments of hrg_ppo_step. */
+typedef struct hrg_ppo_desc {
+  int32_t obs_dim;                /* 1 .. HRG_OBS_DIM */
+  int32_t act_dim;                /* 1 .. HRG_ACT_DIM */
+  int32_t depth;                  /* hidden layers of a network, 1 .. HRG_PPO_MAX_DEPTH */
+  int32_t hidden;                 /* HRG_PPO_HIDDEN */
+  int32_t separate;               /* 0: one trunk under both heads; 1: a network for the policy and one for the value function */
+  int32_t batch_size;             /* a multiple of HRG_PPO_TILE, HRG_PPO_TILE .. HRG_PPO_MAX_BATCH */
+  int32_t rollout_size;           /* n_envs * n_steps of the rollout buffer the minibatches come from: a multiple of batch_size; 0: not known */
+  int32_t normalize_advantage;
+  int32_t policy;                 /* HRG_PPO_MLP_POLICY */
+  int32_t use_sde;                /* refused when set */
+  int32_t target_kl_set;          /* refused when set: the early stop needs a readback per minibatch */
+  int32_t reserved_;
+  double ent_coef, vf_coef, max_grad_norm;
+  uint64_t seed;                  /* key of the noise draws */
+} hrg_ppo_desc;
+
 typedef struct hrg_batch hrg_batch; /* opaque */
 typedef struct hrg_her hrg_her;     /* opaque */
 typedef struct hrg_rollout hrg_rollout; /* opaque */
 typedef struct hrg_replay hrg_replay;   /* opaque */
 typedef struct hrg_sac hrg_sac;         /* opaque */
+typedef struct hrg_ppo hrg_ppo;         /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -831,6 +858,35 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
                  void* stream);
 int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream);
 int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
+
+/* The PPO learner on the device (csrc/hrgym_ppo.h): one minibatch step of SB3 1.5.0's PPO.train (MlpPolicy, use_sde = False, Box actions) in four launches on one
+ * stream, and the forward pass of the policy and of the value function.  Parameters and Adam moments are flat float32 device arrays of the caller's (layout:
+ * csrc/hrgym_ppo.h; sizes: hrg_ppo_sizes); the handle owns the descriptor, the counters and the scratch.  Every entry selects the handle's device; hrg_ppo_step and
+ * hrg_ppo_forward are asynchronous on `stream`.
+ *   hrg_ppo_create   checks the descriptor before anything is launched or allocated: HRG_ERR_UNSUPPORTED for use_sde, a target_kl, a policy other than
+ *                    HRG_PPO_MLP_POLICY, a hidden width other than HRG_PPO_HIDDEN, a depth outside 1 .. HRG_PPO_MAX_DEPTH, obs_dim outside 1 .. HRG_OBS_DIM, act_dim
+ *                    outside 1 .. HRG_ACT_DIM, a batch_size that is not a multiple of HRG_PPO_TILE in HRG_PPO_TILE .. HRG_PPO_MAX_BATCH, a rollout_size that
+ *                    batch_size does not divide (the learner takes no short last minibatch); HRG_ERR_INVALID for coefficients that are negative or not finite.
+ *   hrg_ppo_sizes    size_host int64[6] = parameters in all, of one network's hidden layers, networks (1 shared, 2 separate), minibatch steps so far, forward
+ *                    calls that drew their noise, bytes of device memory held.
+ *   hrg_ppo_step     one minibatch step on batch_size rows (the outputs of hrg_rollout_get): observations float [B][obs_dim], actions float [B][act_dim],
+ *                    old_values, old_log_prob, advantages, returns float [B].  clip_range_vf < 0: the value function is not clipped.  params_dev, adam_m_dev,
+ *                    adam_v_dev float [n_params] are updated in place.
+ *   hrg_ppo_forward  actions_dev float [n][act_dim] = mu + exp(log_std) eps (not clipped; deterministic != 0: mu), values_dev float [n], log_probs_dev float [n] of
+ *                    the float32 actions, on obs_dev float [n][obs_dim].  eps_dev float [n][act_dim] replaces the draws when non-NULL (the call counter then does
+ *                    not move).  actions_dev NULL: the values only.
+ *   hrg_ppo_export   synchronous parity hook, the last step's intermediates on the host: values, log_prob, ratio float [B], grad float [n_params] (the parameters'
+ *                    layout, before clipping), diag float [HRG_PPO_NDIAG] = policy_gradient_loss, value_loss, entropy_loss, loss, approx_kl, clip_fraction, std,
+ *                    the gradient norm before clipping.  Any pointer may be NULL. */
+int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out);
+void hrg_ppo_destroy(hrg_ppo* h);
+int hrg_ppo_sizes(hrg_ppo* h, int64_t* size_host);
+int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions_dev, const float* old_values_dev, const float* old_log_prob_dev,
+                 const float* advantages_dev, const float* returns_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, double learning_rate, double clip_range,
+                 double clip_range_vf, void* stream);
+int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                    float* values_dev, float* log_probs_dev, void* stream);
+int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */

@@ -1,0 +1,46 @@
+"""The whole PPO alternation on one GPU, nothing leaving the device between the rollouts: `env.collect_rollout(learner.policy, learner.value)`, then
+`learner.train(env.rollout)` -- n_epochs passes over the buffer in minibatches of batch_size.  One JSON line per rollout: `env.rollout.episode_stats()` and
+`learner.diagnostics()`.  The defaults are training/config/algorithm/ppo.yaml's (n_steps 64, batch_size 64, n_epochs 20, learning_rate 7e-5, net_arch [64, 64],
+log_std_init -2.7, ortho_init false).  A demonstration of the plumbing; it carries no claim about learning curves.
+
+With n_envs * n_steps rows per rollout, n_epochs 20 and batch_size 64 a rollout of 4096 envs is 81 920 minibatch steps: whether a run at thousands of envs
+keeps the reference's batch size is the user's decision.
+
+python tools/train_ppo.py --n-envs 256 --rollouts 10"""
+import argparse
+import json
+import sys
+import time
+
+sys.path.insert(0, '.')
+import human_robot_gym_amd as hrg   # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--env-id", default="ReachHuman")
+ap.add_argument("--n-envs", type=int, default=256)
+ap.add_argument("--horizon", type=int, default=100)
+ap.add_argument("--n-steps", type=int, default=64)
+ap.add_argument("--rollouts", type=int, default=10)
+ap.add_argument("--batch-size", type=int, default=64)
+ap.add_argument("--n-epochs", type=int, default=20)
+ap.add_argument("--learning-rate", type=float, default=7e-5)
+ap.add_argument("--gamma", type=float, default=0.99)
+ap.add_argument("--gae-lambda", type=float, default=0.9)
+ap.add_argument("--log-std-init", type=float, default=-2.7)
+ap.add_argument("--separate", action="store_true", help="net_arch [dict(pi=[64, 64], vf=[64, 64])] instead of the shared [64, 64]")
+ap.add_argument("--seed", type=int, default=0)
+args = ap.parse_args()
+
+env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
+env.attach_rollout(n_steps=args.n_steps, gamma=args.gamma, gae_lambda=args.gae_lambda)
+learner = env.attach_ppo(batch_size=args.batch_size, n_epochs=args.n_epochs, learning_rate=args.learning_rate, log_std_init=args.log_std_init, ortho_init=False,
+                         net_arch=[dict(pi=[64, 64], vf=[64, 64])] if args.separate else [64, 64], seed=args.seed)
+t0 = time.time()
+for k in range(args.rollouts):
+    env.collect_rollout(learner.policy, learner.value)
+    learner.train(env.rollout)
+    line = dict(rollout=k, env_steps=(k + 1) * args.n_steps * args.n_envs, seconds=round(time.time() - t0, 3))
+    line.update(env.rollout.episode_stats())
+    line.update(learner.diagnostics())
+    print(json.dumps(line), flush=True)
+env.close()
