@@ -66,7 +66,8 @@ class DeviceHandle:
 class EpisodeBuffer(DeviceHandle):
     """What RolloutBuffer and ReplayBuffer share: the policy's view of rows and of the envs' current rows, the rows an episode starts from, and the episode
     statistics.  A subclass names its entry points (`_prefix`: hrg_rollout / hrg_replay), says whether they take time values (`_has_time`: the argument is there;
-    `observe_time`: the observation has the column) and how many statistics columns it keeps (`_stats_dim`), and sets `n` and `obs_dim`."""
+    `observe_time`: the observation has the column) and how many statistics columns it keeps (`_stats_dim`), and sets `n` and `obs_dim`.  her.HerBuffer
+    (`_prefix` hrg_her) takes the handle, `_call` and the episode statistics from here; its view of a row is the feature row of its own `observation`."""
     _prefix, _has_time, _stats_dim = None, False, 3 + CONST["HRG_INFO_DIM"]
     observe_time = False
 

@@ -1,13 +1,24 @@
 // hrgym_her.h -- hindsight experience replay on the device: the replay buffer of SAC + HER (SB3's HerReplayBuffer with the reference's patches,
-// wrappers/HER_buffer_add_monkey_patch.py) for a batch of goal envs, in four small kernels next to the (unchanged) step launch.  Included into the base
-// translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_buffer.h (the policy's view of a row, the grid of the one-wavefront-per-sample kernels).
+// wrappers/HER_buffer_add_monkey_patch.py) for a batch of goal envs, in six small kernels next to the (unchanged) step launch.  Included into the base
+// translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_buffer.h (the policy's view of a row, the episode tracker, the grid of the
+// one-wavefront-per-sample kernels).
 //
 //   hrg_her_add_kernel           custom_add (26-117) for every env: one transition into the env's ring, episode bookkeeping.  One wavefront per env, lane l
 //                                moves column l of each 256-byte observation row.
 //   hrg_her_observe_kernel       the first observation of an episode after a reset; the unfinished episode of a reset env is discarded.
 //   hrg_her_sample_kernel        _custom_sample_transitions (120-286), online sampling: one wavefront per sample, four per block, no LDS, no atomics.
-//   hrg_goal_reward_done_kernel  HumanEnv._compute_reward / _check_done of caller-supplied goal rows, one thread per row; the sample kernel calls the same
-//                                device function for its relabelled samples.
+//   hrg_her_sample_features_kernel  the same samples (her_draw: the draws, the relabelling, reward and done, the rewritten observation) as the rows a
+//                                MultiInputPolicy's CombinedExtractor feeds its MLPs: features[k][F] and next_features[k][F], F = ag_dim + dg_dim + n_obs_cols
+//                                <= 64, laid out achieved_goal | desired_goal | observation (gym.spaces.Dict orders its keys alphabetically).  Lane l < F stores
+//                                value l: one coalesced row store per row.  Where the prefix sums' total is <= 0 the kernel returns and leaves its outputs
+//                                unwritten (the caller checks for an empty buffer once per train call, not per sample).
+//   hrg_her_features_kernel      the same feature row of caller-supplied rows of the superset, or of the envs' current rows (SB3's _last_obs): one wavefront
+//                                per row, like hrg_buffer_view_kernel.
+//   hrg_goal_reward_done_kernel  HumanEnv._compute_reward / _check_done of caller-supplied goal rows, one thread per row; the sample kernels call the same
+//                                device function for their relabelled samples.
+//
+// Episode statistics: the shared tracker (hrgym_buffer.h) with HRG_HER_STATS_DIM columns; the return is the env's own step reward.  A masked observe starts the
+// env's running return and length again, as it discards the env's open episode.
 //
 // The ring of env e: slot = write counter % capacity.  Three counters per env: w (next write), tail (oldest valid transition), open (first transition of
 // the running episode); tail <= open <= w, w - tail <= capacity.  Every slot carries ep_start (counter of its episode's first transition) and ep_len (0 while
@@ -19,6 +30,7 @@
 #pragma once
 
 enum { STREAM_HER = 10 };   // after STREAM_DATASET = 9 (hrgym_dataset.h)
+#define HRG_HER_STATS_DIM (3 + HRG_INFO_DIM)   // episodes, return, length, the info columns
 
 // the buffers of one hrg_her; passed to the kernels by value
 struct HerDev {
@@ -34,7 +46,7 @@ struct HerDev {
   int64_t* w = nullptr;        // [n]
   int64_t* tail = nullptr;     // [n]
   int64_t* open = nullptr;     // [n]
-  float* cur_obs = nullptr;    // [n][HRG_OBS_DIM] the row the next transition starts from
+  EpisodeTracker ep;           // the current rows (the row the next transition starts from); the returns are the env's own reward; HRG_HER_STATS_DIM columns
   BufferView view;             // hrg_her_desc::obs_cols (the view is a plain selection: no time column, no normalisation)
 };
 
@@ -106,10 +118,11 @@ __global__ __launch_bounds__(64) void hrg_her_add_kernel(const hrg_her_desc p, c
   }
   const size_t s = ring + (size_t)(w % cap);
   const bool dn = done[e] != 0;
-  h.pre[s * HRG_OBS_DIM + lane] = h.cur_obs[(size_t)e * HRG_OBS_DIM + lane];
+  h.pre[s * HRG_OBS_DIM + lane] = h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane];
   const float o = obs[(size_t)e * HRG_OBS_DIM + lane];
   h.post[s * HRG_OBS_DIM + lane] = dn ? term_obs[(size_t)e * HRG_OBS_DIM + lane] : o;
-  h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = o;   // after an auto-reset: the new episode's first row
+  h.ep.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = o;   // after an auto-reset: the new episode's first row
+  tracker_step(h.ep, e, lane, reward[e], dn, info + (size_t)e * HRG_INFO_DIM, HRG_HER_STATS_DIM, 0.0);
   if (lane < p.act_dim) {
     double a = actions[(size_t)e * HRG_ACT_DIM + lane];
     if (p.rescale_actions) {   // HER_buffer_add_monkey_patch.py:64-76
@@ -144,23 +157,27 @@ __global__ __launch_bounds__(64) void hrg_her_observe_kernel(const hrg_her_desc 
   const int e = (int)blockIdx.x, lane = (int)threadIdx.x;
   if (e >= p.n_envs) return;
   if (!mask || mask[e]) {
-    h.cur_obs[(size_t)e * HRG_OBS_DIM + lane] = obs[(size_t)e * HRG_OBS_DIM + lane];
+    tracker_start(h.ep, e, lane, obs);
     if (lane == 0) h.w[e] = h.open[e];   // the slots of the unfinished episode are written again
   }
   if (lane == 0 && counts) counts[e] = h.open[e] - h.tail[e];
 }
 
-// grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  `cum`: [n_envs + 1] exclusive prefix sums of the envs' closed transitions.
-__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_sample_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call, int batch,
-                                                                       float* __restrict__ o_obs, float* __restrict__ o_ag, float* __restrict__ o_dg,
-                                                                       float* __restrict__ o_nobs, float* __restrict__ o_nag, float* __restrict__ o_ndg,
-                                                                       float* __restrict__ o_act, float* __restrict__ o_rew, float* __restrict__ o_done,
-                                                                       int64_t* __restrict__ o_idx) {
-  const int lane = (int)(threadIdx.x & 63);
-  const int k = buffer_wave_item();
-  if (k >= batch) return;
-  const int64_t N = cum[p.n_envs];
-  if (N <= 0) return;   // (the host refuses the call)
+// One sample as its wavefront holds it: what both sample kernels store.
+struct HerSample {
+  float pre, post;    // column `lane` of the row before the step and of the row after it
+  float goal;         // lane d < dg_dim: component d of the desired goal, stored or relabelled
+  float v0, v1;       // value `lane` of the observation entry of both rows (zero past n_obs_cols), the goal columns rewritten with relabel_observation
+  float rew;
+  bool dn, relabel;
+  int e;              // the env
+  int64_t i, g;       // write counter of the transition, of the transition the new goal came from (-1: not relabelled)
+  size_t s;           // the transition's slot
+};
+
+// Sample k of call `call`: the draws, the transition, the relabelling, reward and done.  N = cum[n_envs] > 0.  Every lane of the wave takes part (the shuffles).
+DI HerSample her_draw(const hrg_her_desc& p, const HerDev& h, const int64_t* __restrict__ cum, int64_t N, uint64_t call, int k, int lane) {
+  HerSample o;
   const double u0 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 0), u1 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 1), u2 = rng_u01(p.seed, call, (uint64_t)k, STREAM_HER, 2);
   const int64_t j = min((int64_t)floor(u0 * (double)N), N - 1);
   int lo = 0, hi = p.n_envs;   // the env with cum[e] <= j < cum[e + 1]
@@ -196,28 +213,92 @@ __global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_sample_kernel(const 
     for (int d = 0; d < 6; d++) g[d] = d < ng ? (double)__shfl(goal, d) : 0.0;
     goal_reward_done(p, a, g, h.ctype[s], &rew, &dn);
   }
-  // the policy's view of both rows
-  {   // value `lane` of the observation entry (n_obs_cols <= 64); every lane takes part in the shuffles
-    float v0 = view_select(h.view, pre, lane), v1 = view_select(h.view, post, lane);   // (entries past n_obs_cols are zero)
-    if (relabel && p.relabel_observation) {   // (wave-uniform)
+  // the policy's view of both rows: value `lane` of the observation entry (n_obs_cols <= 64); every lane takes part in the shuffles
+  float v0 = view_select(h.view, pre, lane), v1 = view_select(h.view, post, lane);   // (entries past n_obs_cols are zero)
+  if (relabel && p.relabel_observation) {   // (wave-uniform)
 #pragma unroll
-      for (int d = 0; d < 6; d++) {
-        const float gd = __shfl(goal, d);
-        if (d < p.n_dg_in_obs && lane == p.dg_in_obs[d]) v0 = v1 = gd;
-      }
-    }
-    if (lane < p.n_obs_cols) {
-      o_obs[(size_t)k * p.n_obs_cols + lane] = v0;
-      o_nobs[(size_t)k * p.n_obs_cols + lane] = v1;
+    for (int d = 0; d < 6; d++) {
+      const float gd = __shfl(goal, d);
+      if (d < p.n_dg_in_obs && lane == p.dg_in_obs[d]) v0 = v1 = gd;
     }
   }
-  const float ag0 = __shfl(pre, her_ag_col(kind, lane < na ? lane : 0)), ag1 = __shfl(post, her_ag_col(kind, lane < na ? lane : 0));
-  if (lane < na) { o_ag[(size_t)k * na + lane] = ag0; o_nag[(size_t)k * na + lane] = ag1; }
-  if (lane < ng) { o_dg[(size_t)k * ng + lane] = goal; o_ndg[(size_t)k * ng + lane] = goal; }
-  if (lane < p.act_dim) o_act[(size_t)k * p.act_dim + lane] = h.act[s * (size_t)p.act_dim + lane];
+  o.pre = pre; o.post = post; o.goal = goal; o.v0 = v0; o.v1 = v1; o.rew = rew; o.dn = dn; o.relabel = relabel;
+  o.e = e; o.i = i; o.g = relabel ? es + f : -1; o.s = s;
+  return o;
+}
+
+// what both sample kernels store once per sample: the action (lanes < act_dim), reward, done and the optional index row (lane 0)
+DI void her_store_scalars(const hrg_her_desc& p, const HerDev& h, const HerSample& x, int k, int lane, float* __restrict__ o_act, float* __restrict__ o_rew,
+                          float* __restrict__ o_done, int64_t* __restrict__ o_idx) {
+  if (lane < p.act_dim) o_act[(size_t)k * p.act_dim + lane] = h.act[x.s * (size_t)p.act_dim + lane];
   if (lane == 0) {
-    o_rew[k] = rew;
-    o_done[k] = dn ? 1.0f : 0.0f;
-    if (o_idx) { o_idx[(size_t)k * HRG_HER_INDEX_DIM] = e; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 1] = i; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 2] = relabel ? es + f : -1; }
+    o_rew[k] = x.rew;
+    o_done[k] = x.dn ? 1.0f : 0.0f;
+    if (o_idx) { o_idx[(size_t)k * HRG_HER_INDEX_DIM] = x.e; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 1] = x.i; o_idx[(size_t)k * HRG_HER_INDEX_DIM + 2] = x.g; }
   }
+}
+
+// grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  `cum`: [n_envs + 1] exclusive prefix sums of the envs' closed transitions.
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_sample_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call, int batch,
+                                                                       float* __restrict__ o_obs, float* __restrict__ o_ag, float* __restrict__ o_dg,
+                                                                       float* __restrict__ o_nobs, float* __restrict__ o_nag, float* __restrict__ o_ndg,
+                                                                       float* __restrict__ o_act, float* __restrict__ o_rew, float* __restrict__ o_done,
+                                                                       int64_t* __restrict__ o_idx) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int k = buffer_wave_item();
+  if (k >= batch) return;
+  const int64_t N = cum[p.n_envs];
+  if (N <= 0) return;   // (the host refuses the call)
+  const HerSample x = her_draw(p, h, cum, N, call, k, lane);
+  const int kind = p.goal_kind, na = her_ag_dim(kind), ng = her_dg_dim(kind);
+  if (lane < p.n_obs_cols) {
+    o_obs[(size_t)k * p.n_obs_cols + lane] = x.v0;
+    o_nobs[(size_t)k * p.n_obs_cols + lane] = x.v1;
+  }
+  const float ag0 = __shfl(x.pre, her_ag_col(kind, lane < na ? lane : 0)), ag1 = __shfl(x.post, her_ag_col(kind, lane < na ? lane : 0));
+  if (lane < na) { o_ag[(size_t)k * na + lane] = ag0; o_nag[(size_t)k * na + lane] = ag1; }
+  if (lane < ng) { o_dg[(size_t)k * ng + lane] = x.goal; o_ndg[(size_t)k * ng + lane] = x.goal; }
+  her_store_scalars(p, h, x, k, lane, o_act, o_rew, o_done, o_idx);
+}
+
+// Value `lane` of the feature row achieved_goal | desired_goal | observation (F = na + ng + n_obs_cols <= 64; zero past F).  row: column `lane` of the row of
+// the superset, goal: component `lane` < ng of the desired goal, v: value `lane` of the observation entry.  Every lane of the wave takes part (the shuffles).
+DI float her_feature(int kind, int n_obs_cols, float row, float goal, float v, int lane) {
+  const int na = her_ag_dim(kind), ng = her_dg_dim(kind);
+  const float a = __shfl(row, her_ag_col(kind, lane < na ? lane : 0));
+  const float g = __shfl(goal, min(max(lane - na, 0), ng - 1));
+  const float o = __shfl(v, min(max(lane - na - ng, 0), 63));   // value j of the observation entry moves from lane j to lane na + ng + j
+  return lane < na ? a : lane < na + ng ? g : lane < na + ng + n_obs_cols ? o : 0.0f;
+}
+
+// grid = ceil(batch / 4) blocks of four wavefronts, one sample each; F <= HRG_OBS_DIM (the host checks).  Outputs are left unwritten where cum[n_envs] <= 0.
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_sample_features_kernel(const hrg_her_desc p, const HerDev h, const int64_t* __restrict__ cum, uint64_t call,
+                                                                                int batch, float* __restrict__ o_feat, float* __restrict__ o_nfeat,
+                                                                                float* __restrict__ o_act, float* __restrict__ o_rew, float* __restrict__ o_done,
+                                                                                int64_t* __restrict__ o_idx) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int k = buffer_wave_item();
+  if (k >= batch) return;
+  const int64_t N = cum[p.n_envs];
+  if (N <= 0) return;   // (the caller checks once per train call)
+  const HerSample x = her_draw(p, h, cum, N, call, k, lane);
+  const int kind = p.goal_kind, F = her_ag_dim(kind) + her_dg_dim(kind) + p.n_obs_cols;
+  const float f0 = her_feature(kind, p.n_obs_cols, x.pre, x.goal, x.v0, lane), f1 = her_feature(kind, p.n_obs_cols, x.post, x.goal, x.v1, lane);
+  if (lane < F) {
+    o_feat[(size_t)k * F + lane] = f0;
+    o_nfeat[(size_t)k * F + lane] = f1;
+  }
+  her_store_scalars(p, h, x, k, lane, o_act, o_rew, o_done, o_idx);
+}
+
+// grid = ceil(n_rows / 4) blocks of four wavefronts, one row each; F <= HRG_OBS_DIM (the host checks)
+__global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_her_features_kernel(const BufferView w, int kind, const float* __restrict__ rows, int n_rows, float* __restrict__ out) {
+  const int lane = (int)(threadIdx.x & 63);
+  const int r = buffer_wave_item();
+  if (r >= n_rows) return;   // (wave-uniform)
+  const int ng = her_dg_dim(kind), F = her_ag_dim(kind) + ng + w.n_obs_cols;
+  const float x = rows[(size_t)r * HRG_OBS_DIM + lane];
+  const float goal = __shfl(x, her_dg_col(kind, lane < ng ? lane : 0));
+  const float f = her_feature(kind, w.n_obs_cols, x, goal, view_select(w, x, lane), lane);
+  if (lane < F) out[(size_t)r * F + lane] = f;
 }

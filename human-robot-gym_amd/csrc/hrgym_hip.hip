@@ -3848,7 +3848,8 @@ int hrg_her_create(const hrg_her_desc* desc, int32_t device, hrg_her** out) {
   const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
   if (!(m.zeros(d.pre, slots * HRG_OBS_DIM) && m.zeros(d.post, slots * HRG_OBS_DIM) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
         m.zeros(d.done, slots) && m.zeros(d.trunc, slots) && m.zeros(d.ctype, slots) && m.zeros(d.ep_start, slots) && m.zeros(d.ep_len, slots) && m.zeros(d.w, n) &&
-        m.zeros(d.tail, n) && m.zeros(d.open, n) && m.zeros(d.cur_obs, n * HRG_OBS_DIM)))
+        m.zeros(d.tail, n) && m.zeros(d.open, n) && m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) &&
+        m.zeros(d.ep.acc, n * HRG_HER_STATS_DIM)))
     return nomem("her", m);
   if (hipHostMalloc((void**)&h->d_total, sizeof(int64_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(HRG_ERR_HIP, "her: upload failed");
   *out = h.release();
@@ -3889,6 +3890,46 @@ int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev
   return HRG_OK;
 }
 
+// the width of the feature row achieved_goal | desired_goal | observation; the feature kernels keep one value per lane
+static int her_feature_dim(const hrg_her_desc& p) { return (p.goal_kind == HRG_GOAL_REACH ? 6 + 6 : 7 + 3) + p.n_obs_cols; }
+static int her_feature_check(const hrg_her_desc& p) {
+  if (her_feature_dim(p) > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: achieved_goal + desired_goal + observation exceed HRG_OBS_DIM values (the feature kernels keep one per lane)");
+  return HRG_OK;
+}
+
+int hrg_her_sample_features(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* features_dev, float* next_features_dev, float* action_dev,
+                            float* reward_dev, float* done_dev, int64_t* index_dev, void* stream) {
+  if (!h || !counts_cum_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (batch_size < 1) return fail(HRG_ERR_INVALID, "her: batch_size must be positive");
+  if (!features_dev || !next_features_dev || !action_dev || !reward_dev || !done_dev) return fail(HRG_ERR_INVALID, "her: null output");
+  int rc = her_feature_check(h->desc);
+  if (rc != HRG_OK) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  rc = launch_per_wave(hrg_her_sample_features_kernel, batch_size, stream, h->desc, h->d, counts_cum_dev, h->calls, (int)batch_size, features_dev, next_features_dev,
+                       action_dev, reward_dev, done_dev, index_dev);
+  if (rc != HRG_OK) return rc;
+  h->calls++;
+  return HRG_OK;
+}
+
+int hrg_her_features(hrg_her* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream) {
+  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!rows_dev) {   // the envs' current rows
+    rows_dev = h->d.ep.cur_obs;
+    n_rows = h->desc.n_envs;
+  }
+  if (n_rows < 1) return fail(HRG_ERR_INVALID, "her: n_rows must be positive");
+  const int rc = her_feature_check(h->desc);
+  if (rc != HRG_OK) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  return launch_per_wave(hrg_her_features_kernel, n_rows, stream, h->d.view, (int)h->desc.goal_kind, rows_dev, (int)n_rows, out_dev);
+}
+
+int hrg_her_stats(hrg_her* h, double* per_env_host, int32_t clear) {
+  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
+  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_HER_STATS_DIM, per_env_host, clear);
+}
+
 int hrg_her_counts(hrg_her* h, int64_t* counts_host) {
   if (!h || !counts_host) return fail(HRG_ERR_INVALID, "null argument");
   HIPCHK(hipSetDevice(h->device));
@@ -3926,7 +3967,7 @@ int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, f
   HIPCHK(hipMemcpy(state_host + 0, d.w + env, sizeof(int64_t), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(state_host + 1, d.tail + env, sizeof(int64_t), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(state_host + 2, d.open + env, sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cur_obs_host, d.cur_obs + (size_t)env * HRG_OBS_DIM, row, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs + (size_t)env * HRG_OBS_DIM, row, hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 

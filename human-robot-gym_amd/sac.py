@@ -10,6 +10,16 @@ from SB3).  Parameters, Adam moments and target parameters are flat float32 torc
     env.collect_steps(learner.act, 100)            # train_freq steps with the learner's actor as the policy
     learner.train(env.replay, 400)                 # 400 x (sample, gradient step): nothing leaves the device, nothing synchronises
     learner.diagnostics()                          # ent_coef, actor_loss, critic_loss, ent_coef_loss of the last step (synchronous)
+
+SAC + HER (training/config/algorithm/sac_her.yaml: policy MultiInputPolicy) runs on the same kernels.  SB3 1.5.0's MultiInputPolicy with its default
+CombinedExtractor flattens the Box entries of the dict observation and concatenates them in the Dict space's (alphabetical) key order [UPSTREAM], so the MLPs
+read the row achieved_goal | desired_goal | observation; her.HerBuffer hands out exactly that row (`observation`, `sample_features`):
+
+    env = HipVecEnv(4096, goal_env=True, obs_keys=["object-state", "robot0_joint_pos", "robot0_joint_vel"])
+    env.attach_her(buffer_size=256)
+    learner = env.attach_sac(batch_size=128)       # policy="MultiInputPolicy", obs_dim = env.her.obs_features
+    env.collect_steps(learner.act, 100)
+    learner.train(env.her, 400)                    # 400 x (env.her.sample_features(128), step): one read of the buffer's size, then nothing synchronises
 """
 import ctypes
 import math
@@ -27,6 +37,21 @@ TILE = CONST["HRG_SAC_TILE"]
 MAX_BATCH = CONST["HRG_SAC_MAX_BATCH"]
 NQ = CONST["HRG_SAC_NQ"]
 Q_COLUMNS = ("q1", "q2", "q1_target", "q2_target", "q1_pi", "q2_pi")   # the rows of hrg_sac_export's q, in its order
+
+
+POLICIES = {False: "MlpPolicy", True: "MultiInputPolicy"}   # by goal_env: what SB3 takes for a Box and for a Dict observation space
+
+
+def check_policy(policy, goal_env):
+    """`policy` (None: the default) for an env with flat (`goal_env` False) or dict observations; the other policy is refused by name."""
+    want = POLICIES[bool(goal_env)]
+    if policy is None:
+        return want
+    if policy not in POLICIES.values():
+        raise NotImplementedError(f"policy = {policy!r}: the device learner covers {sorted(POLICIES.values())}")
+    if policy != want:
+        raise NotImplementedError(f"policy = {policy!r}: {'a goal env has dict observations' if goal_env else 'this env has flat observations'}, which SB3 gives to {want}")
+    return policy
 
 
 def depth_of(net_arch):
@@ -202,8 +227,14 @@ class SacLearner(DeviceHandle):
     def step(self, batch, eps_pi=None, eps_next=None):
         """One gradient step on `batch`, a ReplayBufferSamples of `batch_size` rows (observations, next_observations [B, obs_dim], actions [B, act_dim], dones,
         rewards [B, 1]).  `eps_pi` / `eps_next` float32 [B, act_dim]: the standard normal noise of the actor on the observations / the next observations, instead
-        of the learner's own draws (tests)."""
+        of the learner's own draws (tests).  A DictReplayBufferSamples (her.HerBuffer.sample) is accepted too: its entries are concatenated in the feature row's
+        order (her.FEATURE_KEYS) first -- a convenience; `train` reads the buffer's feature rows directly."""
         B, K, A, p = self.batch_size, self.obs_dim, self.act_dim, self.p
+        if isinstance(batch.observations, dict):
+            from .her import FEATURE_KEYS
+            from .replay import ReplayBufferSamples
+            cat = lambda d: self.torch.cat([d[k] for k in FEATURE_KEYS], dim=1)   # noqa: E731
+            batch = ReplayBufferSamples(cat(batch.observations), batch.actions, cat(batch.next_observations), batch.dones, batch.rewards)
         args = (self._tensor(batch.observations, (B, K), "observations"), self._tensor(batch.actions, (B, A), "actions"),
                 self._tensor(batch.next_observations, (B, K), "next_observations"), self._tensor(batch.dones, (B, 1), "dones"),
                 self._tensor(batch.rewards, (B, 1), "rewards"), None if eps_pi is None else self._tensor(eps_pi, (B, A), "eps_pi"),
@@ -213,11 +244,18 @@ class SacLearner(DeviceHandle):
         self._keep = (batch, eps_pi, eps_next)
 
     def train(self, replay, gradient_steps):
-        """SAC.train(gradient_steps, batch_size): `gradient_steps` x (replay.sample(batch_size), step), with no copy to the host and no synchronisation."""
-        if (int(replay.obs_dim), int(replay.act_dim)) != (self.obs_dim, self.act_dim):
-            raise ValueError(f"train: the buffer holds observations of {replay.obs_dim} and actions of {replay.act_dim} values, the learner takes {self.obs_dim} and {self.act_dim}")
+        """SAC.train(gradient_steps, batch_size): `gradient_steps` x (replay.sample(batch_size), step), with no copy to the host and no synchronisation.
+        `replay`: a replay.ReplayBuffer, or a her.HerBuffer, whose samples are its feature rows (`sample_features`): its size is read once, first (an empty
+        hindsight buffer raises); after that line nothing on the host waits for the device."""
+        hindsight = hasattr(replay, "sample_features")
+        obs_dim = int(replay.obs_features if hindsight else replay.obs_dim)
+        if (obs_dim, int(replay.act_dim)) != (self.obs_dim, self.act_dim):
+            raise ValueError(f"train: the buffer holds observations of {obs_dim} and actions of {replay.act_dim} values, the learner takes {self.obs_dim} and {self.act_dim}")
+        if hindsight:
+            replay.require_samples()
+        sample = replay.sample_features if hindsight else replay.sample
         for _ in range(int(gradient_steps)):
-            self.step(replay.sample(self.batch_size))
+            self.step(sample(self.batch_size))
 
     def act(self, obs, deterministic=False, eps=None):
         """The actor's actions for `obs` float32 [n, obs_dim]: float32 [n, act_dim] in (-1, 1), tanh(mu + std eps), or tanh(mu) with `deterministic`.  This is the
@@ -235,7 +273,8 @@ class SacLearner(DeviceHandle):
 
     def state_dict(self):
         """Views of the parameters under SB3's names (SacParams.state_dict): actor.latent_pi.{0,2,4}.*, actor.mu.*, actor.log_std.*, critic.qf{0,1}.{0,2,4,6}.*,
-        critic_target.qf{0,1}.*, log_ent_coef; torch's [out, in] weight layout."""
+        critic_target.qf{0,1}.*, log_ent_coef; torch's [out, in] weight layout.  The same names under MultiInputPolicy: its CombinedExtractor over Box
+        entries is a Flatten per entry and has no parameters ([UPSTREAM]: from knowledge of SB3 1.5.0), so a dict-observation SAC holds the MLPs' entries only."""
         return self.p.state_dict()
 
     def load_state_dict(self, state):

@@ -209,13 +209,20 @@ def replay_kwargs_from_config(config) -> Optional[Dict[str, Any]]:
 def sac_kwargs_from_config(config) -> Dict[str, Any]:
     """`config.algorithm` of a SAC run (training/config_icra_2024/.../*-SAC.yaml) -> the keyword arguments of HipVecEnv.attach_sac / sac.SacLearner:
     net_arch, learning_rate, gamma, tau, ent_coef, target_entropy, batch_size, target_update_interval, seed (missing keys take SB3's SAC defaults).
-    What the kernels do not cover is refused by the name of its key: use_sde, action_noise, policy, policy_kwargs.net_arch.  train_freq, gradient_steps,
-    learning_starts and buffer_size belong to the loop and the buffer (tools/train_sac.py, replay_kwargs_from_config), not to the learner."""
+    What the kernels do not cover is refused by the name of its key: use_sde, action_noise, policy, policy_kwargs.net_arch.  `policy`: MlpPolicy, or
+    MultiInputPolicy exactly when run.env_type is goal_env (training/config/algorithm/sac_her.yaml); the result carries it for a goal env.  train_freq --
+    sac_her.yaml's [1, episode] included, which SB3 1.5.0 itself forbids with more than one env --, gradient_steps, learning_starts, buffer_size and
+    replay_buffer_kwargs belong to the loop and the buffer (tools/train_sac.py, tools/train_sac_her.py, replay_kwargs_from_config, create_training_vec_env),
+    not to the learner."""
     alg = _get(config, "algorithm")
     if str(_get(alg, "name", "SAC")).upper() != "SAC":
         raise NotImplementedError(f"algorithm.name = {_get(alg, 'name')}: the device learner is SAC")
-    if _get(alg, "policy", "MlpPolicy") != "MlpPolicy":
-        raise NotImplementedError(f"algorithm.policy = {_get(alg, 'policy')}: the device learner covers MlpPolicy")
+    from .sac import check_policy
+    goal_env = _get(_get(config, "run"), "env_type", "env") == "goal_env"
+    try:
+        policy = check_policy(_get(alg, "policy"), goal_env)
+    except NotImplementedError as e:
+        raise NotImplementedError(f"algorithm.policy with run.env_type = {'goal_env' if goal_env else 'env'}: {e}") from None
     if _get(alg, "use_sde", False):
         raise NotImplementedError("algorithm.use_sde = true: state dependent exploration is not covered by the device learner")
     if _get(alg, "action_noise") is not None:
@@ -235,6 +242,8 @@ def sac_kwargs_from_config(config) -> Dict[str, Any]:
                               batch_size=int(_get(alg, "batch_size", 256)), target_update_interval=int(_get(alg, "target_update_interval", 1)))
     if _get(alg, "seed") is not None:
         kw["seed"] = int(_get(alg, "seed"))
+    if goal_env:
+        kw["policy"] = policy
     return kw
 
 

@@ -267,12 +267,12 @@ class _TorchBackend:
     def expert_actions(self):
         return self.batch.expert_actions().cpu().numpy()
 
-    def attach_her(self, desc, keep_agent_actions=False):
+    def attach_her(self, desc, keep_agent_actions=False, info_keys=None):
         """`keep_agent_actions`: the buffer stores the rows the agent sent (copied before the step rewrites them), not the rows the step left."""
         from .her import HerBuffer
         if self.her is not None:
             self.her.close()
-        self.her = HerBuffer(desc, device=self.batch.device.index)
+        self.her = HerBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
         self._her_agent = bool(keep_agent_actions)
 
     def attach_rollout(self, desc, info_keys=None):
@@ -515,7 +515,7 @@ class HipVecEnv(_VecEnvBase):
         if self._dataset is not None:
             backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
         if getattr(self, "_her_args", None) is not None:   # after seed(): a new, empty buffer
-            backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None)
+            backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None, info_keys=self._info_keys)
         if getattr(self, "_rollout_args", None) is not None:   # after seed(): a new, empty buffer
             backend.attach_rollout(self._rollout_desc(n_envs, **self._rollout_args), info_keys=self._info_keys)
         if getattr(self, "_replay_args", None) is not None:   # after seed(): a new, empty buffer
@@ -897,8 +897,9 @@ class HipVecEnv(_VecEnvBase):
 
     def attach_her(self, buffer_size, n_sampled_goal=4, goal_selection_strategy="future", online_sampling=True, relabel_observation=False, seed=None):
         """A hindsight replay buffer on the device (her.HerBuffer; the keywords of SB3's HerReplayBuffer, training/config/algorithm/sac_her.yaml):
-        `buffer_size` transitions PER ENV.  From now on reset() and every step put their rows into it without leaving the device; `env.her.sample(n)`
-        returns device tensors.  Attaching again replaces the buffer with an empty one.  Returns the buffer."""
+        `buffer_size` transitions PER ENV.  From now on reset() and every step put their rows into it without leaving the device, `collect_steps` does the
+        same without the host; `env.her.sample(n)` returns device tensors, `env.her.sample_features(n)` the rows `attach_sac`'s learner reads.  Attaching
+        again replaces the buffer with an empty one (and, between two runs of the device loop, resets the envs).  Returns the buffer."""
         if not self.goal_env:
             raise NotImplementedError("attach_her: construct with goal_env=True / make_vec_env(type='goal_env')")
         if not online_sampling:
@@ -913,9 +914,13 @@ class HipVecEnv(_VecEnvBase):
             raise NotImplementedError("attach_her: the add and sample kernels run in the HIP library; another backend has none")
         args = dict(buffer_size=int(buffer_size), n_sampled_goal=int(n_sampled_goal), goal_selection_strategy=goal_selection_strategy,
                     relabel_observation=bool(relabel_observation), seed=seed)
-        self._backend.attach_her(self._her_desc(self.num_envs, **args), keep_agent_actions=self._ik is not None)
+        self._backend.attach_her(self._her_desc(self.num_envs, **args), keep_agent_actions=self._ik is not None, info_keys=self._info_keys)
         self._her_args = args
-        if self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
+        if self._device_loop:   # attached between two runs of the device loop: the new buffer has no current rows, so the envs start again
+            self._backend.reset_device()
+            if self._backend.rollout is not None:
+                self._backend.rollout.observe(self._backend.batch.obs)
+        elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
             self._backend.her.observe(self._backend.batch.obs)
         return self._backend.her
 
@@ -1063,29 +1068,46 @@ class HipVecEnv(_VecEnvBase):
         return getattr(self._backend, "replay", None)
 
     def attach_sac(self, **kwargs):
-        """The SAC learner on the device next to the replay buffer (sac.SacLearner; its keywords: net_arch, learning_rate, gamma, tau, ent_coef,
-        target_entropy, batch_size, target_update_interval, seed).  Needs attach_replay first: `obs_dim` and `act_dim` are the buffer's.  Returns the learner
-        and keeps it as `env.sac`: `env.collect_steps(env.sac.act, train_freq)`, then `env.sac.train(env.replay, gradient_steps)`."""
-        rb = self.replay
+        """The SAC learner on the device next to its buffer (sac.SacLearner; its keywords: net_arch, learning_rate, gamma, tau, ent_coef, target_entropy,
+        batch_size, target_update_interval, seed).  Needs attach_replay first, or on a goal env attach_her: `obs_dim` and `act_dim` are the buffer's -- with
+        the hindsight buffer the width of the feature row achieved_goal | desired_goal | observation, which has to fit the kernels' 64 values (select the
+        observation's columns with obs_keys).  `policy`: "MlpPolicy" on flat observations, "MultiInputPolicy" on a goal env (the defaults; the other one is
+        refused).  Returns the learner and keeps it as `env.sac`: `env.collect_steps(env.sac.act, train_freq)`, then `env.sac.train(env.replay or env.her,
+        gradient_steps)`."""
+        from .sac import check_policy
+        policy = check_policy(kwargs.pop("policy", None), self.goal_env)
+        rb = self.her if self.goal_env else self.replay
         if rb is None:
-            raise NotImplementedError("attach_sac: call attach_replay(buffer_size) first (the learner takes its observation and action widths from the buffer)")
+            raise NotImplementedError("attach_sac: call attach_replay(buffer_size) first, or attach_her(buffer_size) on a goal env (the learner takes its observation "
+                                      "and action widths from the buffer)")
+        obs_dim = rb.obs_dim
+        if self.goal_env:
+            obs_dim = rb.obs_features
+            if obs_dim > CONST["HRG_OBS_DIM"]:
+                raise NotImplementedError(f"attach_sac: {policy} would see {rb.ag_dim} + {rb.dg_dim} + {rb.obs_dim} = {obs_dim} values (achieved_goal, desired_goal, "
+                                          f"observation); the kernels cover {CONST['HRG_OBS_DIM']}: construct the env with obs_keys that select fewer columns")
         from .sac import SacLearner
         kwargs.setdefault("seed", int(self._desc.seed))
+        learner = SacLearner(obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
         if self.sac is not None:
             self.sac.close()
-        self.sac = SacLearner(rb.obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
+        self.sac = learner
         return self.sac
 
     def collect_steps(self, policy, n_steps):
-        """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`.  `policy(obs float32 [n, K]) ->
-        actions float32 [n, act_dim]` in [-1, 1] takes and returns tensors on the env's device.  Per step: the current observation, the policy, the actions
+        """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`, on a goal env into `env.her`.
+        `policy(obs float32 [n, K]) -> actions float32 [n, act_dim]` in [-1, 1] takes and returns tensors on the env's device; on a goal env `obs` is the
+        feature row achieved_goal | desired_goal | observation (`env.her.observation()`).  Per step: the current observation, the policy, the actions
         brought to the action bounds (low + 0.5 (a + 1) (high - low)) and widened to the float64 rows the kernel reads, the step with whatever reward kernels
-        are attached, the slot (which stores the policy's own action).  No device-to-host copy and no stream synchronisation.  The first call (and the first
-        after reset() or seed()) resets the envs.  Afterwards step_async raises until reset(): the host accounting did not see these steps;
-        `env.replay.episode_stats()` is this path's account of episodes."""
+        are attached, the slot (the replay buffer stores the policy's own action, the hindsight buffer what reset() / step() hand it: the rows the step left,
+        or behind the IK front-end a copy of the agent's rows).  No device-to-host copy and no stream synchronisation.  The first call (and the first after
+        reset() or seed()) resets the envs.  Afterwards step_async raises until reset(): the host accounting did not see these steps;
+        `env.replay.episode_stats()` / `env.her.episode_stats()` is this path's account of episodes."""
+        if self.her is not None:
+            return self._collect_steps_her(policy, n_steps)
         rb = self.replay
         if rb is None:
-            raise NotImplementedError("collect_steps: call attach_replay(buffer_size) first")
+            raise NotImplementedError("collect_steps: call attach_replay(buffer_size) first, or attach_her(buffer_size) on a goal env")
         self._enter_device_loop("collect_steps", "env.replay.episode_stats()")
         import torch
         be = self._backend
@@ -1100,6 +1122,26 @@ class HipVecEnv(_VecEnvBase):
             be.launch_step(rows)
             be.replay_add(actions)
         return rb
+
+    def _collect_steps_her(self, policy, n_steps):
+        """collect_steps into the hindsight buffer: the tensors step_async / step_wait hand it, without the copy to the host."""
+        hb = self.her
+        self._enter_device_loop("collect_steps", "env.her.episode_stats()")
+        import torch
+        be = self._backend
+        b = be.batch
+        dev, n, A = b.device, self.num_envs, hb.act_dim
+        low, high = (torch.from_numpy(np.asarray(x, np.float64)).to(dev) for x in (self.action_space.low, self.action_space.high))
+        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
+        for _ in range(int(n_steps)):
+            actions = policy(hb.observation())
+            rows[:, :A] = low + 0.5 * (actions.to(torch.float64) + 1.0) * (high - low)   # SB3's unscale_action
+            if A < CONST["HRG_ACT_DIM"]:
+                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
+            sent = rows.clone() if be._her_agent else rows   # (as step_async keeps them)
+            be.launch_step(rows)
+            hb.add_step(sent, b.obs, b.term_obs, b.reward, b.done, b.info)
+        return hb
 
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
         if method_name == "check_collision_action":   # per-env call of the reference: env_method("check_collision_action", action, indices=[i])

@@ -718,6 +718,18 @@ int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host);
  *                         desired_goal), action act_dim, reward 1, done 1; index_dev int64 [batch_size][HRG_HER_INDEX_DIM] or NULL.  Relabelled samples:
  *                         reward and done of hrg_goal_reward_done; the others: the stored reward, done without timeouts.  Advances the call counter.
  *                         HRG_ERR_INVALID for batch_size < 1, null outputs, no closed transition (reads the total back: synchronises the stream).
+ *   hrg_her_sample_features  the samples of hrg_her_sample -- the same draws, relabelling, reward, done and call counter: a call of either advances it -- as
+ *                         the rows SB3 1.5.0's MultiInputPolicy feeds its MLPs (CombinedExtractor [UPSTREAM]: the flattened entries concatenated in
+ *                         gym.spaces.Dict's alphabetical key order): features_dev / next_features_dev float [batch_size][F], F = 6 + 6 + n_obs_cols (reach) or
+ *                         7 + 3 + n_obs_cols (cube), laid out achieved_goal | desired_goal | observation; action, reward, done and index_dev as above.  No
+ *                         device-to-host copy and no synchronisation: the emptiness check is the caller's (hrg_her_counts, once before a run of calls); where
+ *                         counts_cum_dev's total is <= 0 the kernel leaves the outputs unwritten.  HRG_ERR_INVALID for F > HRG_OBS_DIM, batch_size < 1,
+ *                         null outputs.
+ *   hrg_her_features   the same feature row of n_rows rows of the superset: rows_dev float [n_rows][HRG_OBS_DIM] -> out_dev float [n_rows][F].  rows_dev
+ *                         NULL: the envs' current rows (SB3's _last_obs), n_rows is not read, out_dev float [n_envs][F].  HRG_ERR_INVALID for F > HRG_OBS_DIM.
+ *   hrg_her_stats      synchronous: per_env_host double [n_envs][3 + HRG_INFO_DIM], since the last clear -- finished episodes, sum of their returns (the
+ *                         env's own step rewards), sum of their lengths, sums of the info columns at their last steps; clear != 0 zeroes the accumulators
+ *                         afterwards.  hrg_her_observe starts a masked env's running return and length again.
  *   hrg_her_counts     synchronous: counts_host int64[3] = transitions stored (closed or not), closed transitions, sample calls so far.
  *   hrg_her_export     synchronous parity hook: env's whole ring -- pre / post float [capacity][HRG_OBS_DIM], action float [capacity][act_dim], reward
  *                         float, done / truncated uint8, collision_type int32, ep_start int64, ep_len int32 [capacity] each, state int64[3] = write counter,
@@ -733,6 +745,10 @@ int hrg_her_add(hrg_her* h, const double* actions_dev, const float* obs_dev, con
 int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* observation_dev, float* achieved_goal_dev, float* desired_goal_dev,
                    float* next_observation_dev, float* next_achieved_goal_dev, float* next_desired_goal_dev, float* action_dev, float* reward_dev,
                    float* done_dev, int64_t* index_dev, void* stream);
+int hrg_her_sample_features(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* features_dev, float* next_features_dev, float* action_dev,
+                            float* reward_dev, float* done_dev, int64_t* index_dev, void* stream);
+int hrg_her_features(hrg_her* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream);
+int hrg_her_stats(hrg_her* h, double* per_env_host, int32_t clear);
 int hrg_her_counts(hrg_her* h, int64_t* counts_host);
 int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, float* action_host, float* reward_host, uint8_t* done_host,
                    uint8_t* truncated_host, int32_t* ctype_host, int64_t* ep_start_host, int32_t* ep_len_host, int64_t* state_host, float* cur_obs_host);

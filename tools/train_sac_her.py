@@ -1,0 +1,64 @@
+"""The whole SAC + HER alternation (training/config/algorithm/sac_her.yaml) on one GPU, nothing leaving the device between the blocks:
+`env.collect_steps(learner.act, horizon)` into the hindsight buffer, then `learner.train(env.her, gradient_steps)`; uniform random actions until
+`learning_starts` transitions are stored (SB3's warm-up).  One JSON line per block: `env.her.episode_stats()` and `learner.diagnostics()`.  The counterpart of
+tools/train_sac.py for goal envs; a demonstration of the plumbing, it carries no claim about learning curves.
+
+A block is one episode of every env: the config's `train_freq: [1, episode]` is SB3's form for a single env (SB3 1.5.0 forbids episodic train_freq with more
+than one), and at a fixed horizon `horizon` steps of every env are that many episodes.
+
+--gradient-steps is explicit, for the reason tools/train_sac.py gives: the config's `gradient_steps: -1` means "as many gradient steps as transitions were
+collected", horizon * n_envs per block; whether a run at thousands of envs keeps that ratio is the user's decision.
+
+--obs-keys: the policy reads achieved_goal | desired_goal | observation in one row of at most 64 values, so the observation entry is a short list of keys.
+
+python tools/train_sac_her.py --n-envs 1024 --gradient-steps 800 --blocks 5"""
+import argparse
+import json
+import sys
+import time
+
+sys.path.insert(0, '.')
+import torch   # noqa: E402
+import human_robot_gym_amd as hrg   # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--env-id", default="ReachHuman")
+ap.add_argument("--obs-keys", nargs="+", default=["object-state", "robot0_joint_pos"], help="the keys of the dict observation's `observation` entry")
+ap.add_argument("--n-envs", type=int, default=1024)
+ap.add_argument("--horizon", type=int, default=100, help="the time limit, and the env steps (of every env) per block")
+ap.add_argument("--gradient-steps", type=int, required=True, help="gradient steps per block")
+ap.add_argument("--blocks", type=int, default=10)
+ap.add_argument("--learning-starts", type=int, default=1000, help="transitions stored before the first gradient step; uniform random actions until then")
+ap.add_argument("--buffer-size", type=int, default=1000, help="transitions per env (must exceed the horizon)")
+ap.add_argument("--n-sampled-goal", type=int, default=4)
+ap.add_argument("--goal-selection-strategy", default="future", choices=["future", "final", "episode"])
+ap.add_argument("--batch-size", type=int, default=128)
+ap.add_argument("--learning-rate", type=float, default=5e-4)
+ap.add_argument("--ent-coef", default="auto_0.2")
+ap.add_argument("--seed", type=int, default=0)
+args = ap.parse_args()
+
+env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, goal_env=True, obs_keys=args.obs_keys, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
+env.attach_her(args.buffer_size, n_sampled_goal=args.n_sampled_goal, goal_selection_strategy=args.goal_selection_strategy)
+learner = env.attach_sac(policy="MultiInputPolicy", batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef, seed=args.seed)
+gen = torch.Generator(device=learner.device).manual_seed(args.seed)
+
+
+def uniform(features):
+    return torch.rand(features.shape[0], learner.act_dim, generator=gen, device=features.device) * 2.0 - 1.0
+
+
+t0 = time.time()
+for block in range(args.blocks):
+    warm = env.her.counts_host()[0] < args.learning_starts
+    env.collect_steps(uniform if warm else learner.act, args.horizon)
+    stored, closed, _ = env.her.counts_host()
+    if stored >= args.learning_starts and closed > 0:
+        learner.train(env.her, args.gradient_steps)
+    line = dict(block=block, env_steps=(block + 1) * args.horizon * args.n_envs, policy="uniform" if warm else "actor", stored=stored, sampleable=closed,
+                seconds=round(time.time() - t0, 3))
+    line.update(env.her.episode_stats())
+    if learner.n_updates:
+        line.update(learner.diagnostics())
+    print(json.dumps(line), flush=True)
+env.close()
