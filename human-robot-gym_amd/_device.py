@@ -1,6 +1,6 @@
-"""What the device-side training objects share (her.HerBuffer, rollout.RolloutBuffer, replay.ReplayBuffer, sac.SacLearner): a handle of the library on a torch
-device, the column check of the buffers' descriptors, and the part of the rollout and the replay buffer that is the same code in the library
-(csrc/hrgym_buffer.h: the policy's view of a row, the episode tracker)."""
+"""What the device-side training objects share (her.HerBuffer, rollout.RolloutBuffer, replay.ReplayBuffer, sac.SacLearner, ppo.PpoLearner): a handle of the
+library on a torch device, the column check of the buffers' descriptors, and the part of the rollout and the replay buffer that is the same code in the library
+(csrc/hrgym_buffer.h: the policy's view of a row, the episode tracker).  What the two learners share beyond the handle is in _learner.py."""
 import ctypes
 
 import numpy as np

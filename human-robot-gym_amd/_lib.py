@@ -4,6 +4,7 @@ There is NO CPU fallback: if the HIP library is missing or the GPU is unavailabl
 PyTorch-ROCm is used only to own device buffers / streams (plumbing); all compute is in the HIP library.
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -22,11 +23,14 @@ SRC_BOX_HULLS = SOURCES[7]   # the one unit a test looks up by name (tests/test_
 EXPORTS = list(PROTOTYPES)   # every function include/hrgym.h declares
 
 
+def library_dependencies():
+    """Every file the library is compiled from: the translation units and every header under csrc/ and include/, as the directories hold them."""
+    return SOURCES + sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h")) + glob.glob(os.path.join(os.path.dirname(_HERE), "include", "*.h")))
+
+
 def build_library(force=False, verbose=False):
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    deps = SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("hrgym_device.h", "hrgym_kernels.h", "hrgym_hull.h", "hrgym_expert.h", "hrgym_dataset.h", "hrgym_buffer.h", "hrgym_her.h", "hrgym_rollout.h", "hrgym_replay.h", "hrgym_sac.h", "hrgym_ppo.h")] + [
-        os.path.join(os.path.dirname(_HERE), "include", f) for f in ("hrgym.h", "hrgym_state.h")]
-    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
+    if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in library_dependencies()):
         return LIB_PATH
     # -fapprox-func, device code only: FP64 divisions become v_rcp_f64 + two Newton steps + one residual correction (8 instructions, within an ulp) instead of the
     # IEEE-exact sequence with scaling and fix-up (12+): 140 division sites in the ReachHuman kernel alone, 5 % of its vector instructions.  The host side and the

@@ -3084,6 +3084,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_her.h"      // hindsight experience replay: add / observe / sample / reward-done kernels (hrg_her_*, hrg_goal_reward_done)
 #include "hrgym_rollout.h"  // the PPO rollout buffer: observe / add / GAE / get kernels (hrg_rollout_*)
 #include "hrgym_replay.h"   // the uniform replay buffer of SAC: observe / add / sample kernels (hrg_replay_*)
+#include "hrgym_mlp.h"      // what the two learners below share: the tile products of a 64-wide MLP, forward and backward, and Adam's update of a parameter
 #include "hrgym_sac.h"      // the SAC gradient step and the actor's forward pass: policy / critic / actor / Adam kernels (hrg_sac_*)
 #include "hrgym_ppo.h"      // the PPO minibatch step and the policy's forward pass: advantage / gradient / reduce / Adam kernels (hrg_ppo_*)
 
@@ -3272,6 +3273,56 @@ static int buffer_columns(const char* name, int32_t n_obs_cols, const int32_t* o
   if (!mem.zeros(dev, HRG_OBS_DIM)) return nomem(name, mem);
   if (hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess) return fail(HRG_ERR_HIP, pre + "upload failed");
   table = dev;
+  return HRG_OK;
+}
+
+// Pieces of one zeroed allocation of T, handed out in order: take(p, n) asks for n values behind p, alloc() makes the allocation and sets every pointer asked for
+template <class T> struct Carver {
+  std::vector<std::pair<T**, size_t>> pieces;   // where the pointer goes, the piece's first value
+  size_t count = 0;
+  void take(T*& out, size_t n) {
+    pieces.push_back({&out, count});
+    count += n;
+  }
+  bool alloc(DeviceMem& mem) {
+    T* base = nullptr;
+    if (!mem.zeros(base, count)) return false;
+    for (const auto& p : pieces) *p.first = base + p.second;
+    return true;
+  }
+};
+
+// What both learners check of their networks and batch (csrc/hrgym_mlp.h).  `name`: the learner's message prefix; max_batch: its largest batch.
+static int learner_shape(const char* name, int32_t hidden, int32_t depth, int32_t obs_dim, int32_t act_dim, int32_t batch_size, int32_t max_batch) {
+  const auto refuse = [name](const char* what, int32_t value, const std::string& why) {
+    return fail(HRG_ERR_UNSUPPORTED, std::string(name) + ": " + what + " = " + std::to_string(value) + why);
+  };
+  if (hidden != HRG_SAC_HIDDEN) return refuse("hidden", hidden, ": the kernels cover hidden width 64 only");
+  if (depth < 1 || depth > HRG_SAC_MAX_DEPTH) return refuse("depth", depth, " outside 1 .. 3");
+  if (obs_dim < 1 || obs_dim > HRG_OBS_DIM) return refuse("obs_dim", obs_dim, " outside 1 .. HRG_OBS_DIM");
+  if (act_dim < 1 || act_dim > HRG_ACT_DIM) return refuse("act_dim", act_dim, " outside 1 .. HRG_ACT_DIM");
+  if (batch_size < MLP_T || batch_size > max_batch || batch_size % MLP_T) return refuse("batch_size", batch_size, " is not a multiple of 32 in 32 .. " + std::to_string(max_batch));
+  return HRG_OK;
+}
+
+// Adam's bias corrections 1 - beta^t for the step after `steps` finished ones (betas 0.9, 0.999)
+static void adam_bias_corrections(uint64_t steps, double& bc1, double& bc2) {
+  const double t = (double)(steps + 1);
+  bc1 = 1.0 - std::pow(0.9, t);
+  bc2 = 1.0 - std::pow(0.999, t);
+}
+
+// hrg_*_export of a learner: once the device is idle, every array the caller asked for (a non-null `host`) to the host
+struct ExportFloats {
+  float* host;
+  const float* dev;
+  size_t count;
+};
+static int export_floats(int device, std::initializer_list<ExportFloats> arrays) {
+  HIPCHK(hipSetDevice(device));
+  HIPCHK(hipDeviceSynchronize());
+  for (const ExportFloats& a : arrays)
+    if (a.host) HIPCHK(hipMemcpy(a.host, a.dev, a.count * sizeof(float), hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 
@@ -4265,8 +4316,7 @@ struct hrg_sac {
   SacDev d;
   uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
   uint64_t act_calls = 0;   // act calls that drew their noise
-  DeviceMem mem;
-  float* scratch = nullptr; // one allocation behind every pointer of `d`
+  DeviceMem mem;            // one allocation behind every pointer of `d`
 };
 
 // the offsets of the parameter layout (csrc/hrgym_sac.h) into d; returns the number of parameters
@@ -4296,12 +4346,7 @@ static int32_t sac_layout(const hrg_sac_desc& c, SacDev& d) {
 int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (desc->hidden != HRG_SAC_HIDDEN) return fail(HRG_ERR_UNSUPPORTED, "sac: hidden = " + std::to_string(desc->hidden) + ": the kernels cover hidden width 64 only");
-  if (desc->depth < 1 || desc->depth > HRG_SAC_MAX_DEPTH) return fail(HRG_ERR_UNSUPPORTED, "sac: depth = " + std::to_string(desc->depth) + " outside 1 .. 3");
-  if (desc->obs_dim < 1 || desc->obs_dim > HRG_OBS_DIM) return fail(HRG_ERR_UNSUPPORTED, "sac: obs_dim = " + std::to_string(desc->obs_dim) + " outside 1 .. HRG_OBS_DIM");
-  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_UNSUPPORTED, "sac: act_dim = " + std::to_string(desc->act_dim) + " outside 1 .. HRG_ACT_DIM");
-  if (desc->batch_size < HRG_SAC_TILE || desc->batch_size > HRG_SAC_MAX_BATCH || desc->batch_size % HRG_SAC_TILE)
-    return fail(HRG_ERR_UNSUPPORTED, "sac: batch_size = " + std::to_string(desc->batch_size) + " is not a multiple of 32 in 32 .. 256");
+  if (int rc = learner_shape("sac", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_SAC_MAX_BATCH)) return rc;
   if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
   if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
     return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
@@ -4315,20 +4360,19 @@ int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
   d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
   d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
   const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
-  const size_t n_float = B * A + 3 * B + SAC_NQ * B + 2 * B * A + (size_t)d.tiles * P + P + (size_t)d.tiles * SAC_NLOSS + 4;
-  if (!h->mem.zeros(h->scratch, n_float)) return nomem("sac", h->mem);
+  Carver<float> f;
+  f.take(d.a_pi, B * A);
+  f.take(d.logp, B);
+  f.take(d.logp_next, B);
+  f.take(d.y, B);
+  f.take(d.q, SAC_NQ * B);
+  f.take(d.dqda, 2 * B * A);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.loss_part, (size_t)d.tiles * SAC_NLOSS);
+  f.take(d.losses, 4);
+  if (!f.alloc(h->mem)) return nomem("sac", h->mem);
   HIPCHK(hipDeviceSynchronize());
-  float* p = h->scratch;
-  d.a_pi = p; p += B * A;
-  d.logp = p; p += B;
-  d.logp_next = p; p += B;
-  d.y = p; p += B;
-  d.q = p; p += SAC_NQ * B;
-  d.dqda = p; p += 2 * B * A;
-  d.part = p; p += (size_t)d.tiles * P;
-  d.grad = p; p += P;
-  d.loss_part = p; p += (size_t)d.tiles * SAC_NLOSS;
-  d.losses = p;
   *out = h.release();
   return HRG_OK;
 }
@@ -4355,18 +4399,19 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
   HIPCHK(hipSetDevice(h->device));
   const SacDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 pair((unsigned)d.tiles, 2), block(SAC_BLOCK);
-  const double t = (double)(h->steps + 1), bc1 = 1.0 - std::pow(0.9, t), bc2 = 1.0 - std::pow(0.999, t);   // Adam's bias corrections, by the optimisers' step count
+  const dim3 pair((unsigned)d.tiles, 2), block(MLP_BLOCK);
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimisers' step count
   const bool polyak = h->steps % (uint64_t)h->desc.target_update_interval == 0;
   const int n_crit2 = 2 * d.n_critic;
   hipLaunchKernelGGL(hrg_sac_policy_kernel, pair, block, 0, st, d, (const float*)params_dev, (const float*)target_dev, observations_dev, next_observations_dev, dones_dev,
                      rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
   hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + SAC_BLOCK - 1) / SAC_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
                      (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
   hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
   hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + SAC_BLOCK - 1) / SAC_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
                      learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
   HIPCHK(hipGetLastError());
   h->steps++;
@@ -4377,7 +4422,7 @@ int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32
   if (!h || !params_dev || !obs_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (n < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + SAC_T - 1) / SAC_T), dim3(SAC_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
+  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
                      (int)(deterministic != 0), h->act_calls, actions_dev);
   HIPCHK(hipGetLastError());
   if (!deterministic && !eps_dev) h->act_calls++;
@@ -4386,17 +4431,10 @@ int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32
 
 int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
   if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
   const SacDev& d = h->d;
-  const size_t B = (size_t)d.B * sizeof(float);
-  if (y_host) HIPCHK(hipMemcpy(y_host, d.y, B, hipMemcpyDeviceToHost));
-  if (logp_host) HIPCHK(hipMemcpy(logp_host, d.logp, B, hipMemcpyDeviceToHost));
-  if (logp_next_host) HIPCHK(hipMemcpy(logp_next_host, d.logp_next, B, hipMemcpyDeviceToHost));
-  if (q_host) HIPCHK(hipMemcpy(q_host, d.q, SAC_NQ * B, hipMemcpyDeviceToHost));
-  if (grad_host) HIPCHK(hipMemcpy(grad_host, d.grad, (size_t)d.n_params * sizeof(float), hipMemcpyDeviceToHost));
-  if (losses_host) HIPCHK(hipMemcpy(losses_host, d.losses, 4 * sizeof(float), hipMemcpyDeviceToHost));
-  return HRG_OK;
+  const size_t B = (size_t)d.B;
+  return export_floats(h->device, {{y_host, d.y, B}, {logp_host, d.logp, B}, {logp_next_host, d.logp_next, B}, {q_host, d.q, SAC_NQ * B},
+                                   {grad_host, d.grad, (size_t)d.n_params}, {losses_host, d.losses, 4}});
 }
 
 // ---- PPO learner (csrc/hrgym_ppo.h) ----
@@ -4407,9 +4445,7 @@ struct hrg_ppo {
   uint64_t steps = 0;           // minibatch steps so far: Adam's step count
   uint64_t forward_calls = 0;   // forward calls that drew their noise
   int n_blocks = 0;             // blocks of 256 parameters
-  DeviceMem mem;
-  float* scratch = nullptr;     // one allocation behind every float pointer of `d`
-  double* dscratch = nullptr;   // ... every double pointer
+  DeviceMem mem;                // one allocation behind every float pointer of `d`, one behind every double pointer
 };
 
 // the offsets of the parameter layout (csrc/hrgym_ppo.h) into d; returns the number of parameters
@@ -4434,13 +4470,8 @@ int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
   if (desc->use_sde) return fail(HRG_ERR_UNSUPPORTED, "ppo: use_sde: state dependent exploration is not covered");
   if (desc->target_kl_set) return fail(HRG_ERR_UNSUPPORTED, "ppo: target_kl: the early stop needs a host readback per minibatch");
   if (desc->policy != HRG_PPO_MLP_POLICY) return fail(HRG_ERR_UNSUPPORTED, "ppo: policy = " + std::to_string(desc->policy) + ": the kernels cover MlpPolicy");
-  if (desc->hidden != HRG_PPO_HIDDEN) return fail(HRG_ERR_UNSUPPORTED, "ppo: hidden = " + std::to_string(desc->hidden) + ": the kernels cover hidden width 64 only");
-  if (desc->depth < 1 || desc->depth > HRG_PPO_MAX_DEPTH) return fail(HRG_ERR_UNSUPPORTED, "ppo: depth = " + std::to_string(desc->depth) + " outside 1 .. 3");
+  if (int rc = learner_shape("ppo", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_PPO_MAX_BATCH)) return rc;
   if (desc->separate != 0 && desc->separate != 1) return fail(HRG_ERR_UNSUPPORTED, "ppo: separate must be 0 (shared trunk) or 1 (separate trunks)");
-  if (desc->obs_dim < 1 || desc->obs_dim > HRG_OBS_DIM) return fail(HRG_ERR_UNSUPPORTED, "ppo: obs_dim = " + std::to_string(desc->obs_dim) + " outside 1 .. HRG_OBS_DIM");
-  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_UNSUPPORTED, "ppo: act_dim = " + std::to_string(desc->act_dim) + " outside 1 .. HRG_ACT_DIM");
-  if (desc->batch_size < HRG_PPO_TILE || desc->batch_size > HRG_PPO_MAX_BATCH || desc->batch_size % HRG_PPO_TILE)
-    return fail(HRG_ERR_UNSUPPORTED, "ppo: batch_size = " + std::to_string(desc->batch_size) + " is not a multiple of 32 in 32 .. 4096");
   if (desc->rollout_size < 0 || desc->rollout_size % desc->batch_size)
     return fail(HRG_ERR_UNSUPPORTED, "ppo: rollout_size = " + std::to_string(desc->rollout_size) + " is not divisible by batch_size = " + std::to_string(desc->batch_size) +
                                          ": the learner takes no short last minibatch");
@@ -4457,20 +4488,20 @@ int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
   d.normalize = desc->normalize_advantage ? 1 : 0;
   d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm; d.seed = desc->seed;
   const size_t P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;
-  h->n_blocks = (int)((P + PPO_BLOCK - 1) / PPO_BLOCK);
-  const size_t n_float = 3 * B + (size_t)d.tiles * P + P + (size_t)d.tiles * PPO_NPART + HRG_PPO_NDIAG;
-  if (!h->mem.zeros(h->scratch, n_float) || !h->mem.zeros(h->dscratch, 2 + (size_t)h->n_blocks)) return nomem("ppo", h->mem);
+  h->n_blocks = (int)((P + MLP_BLOCK - 1) / MLP_BLOCK);
+  Carver<float> f;
+  f.take(d.values, B);
+  f.take(d.logp, B);
+  f.take(d.ratio, B);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.loss_part, (size_t)d.tiles * PPO_NPART);
+  f.take(d.diag, HRG_PPO_NDIAG);
+  Carver<double> dbl;
+  dbl.take(d.adv_stat, 2);
+  dbl.take(d.block_sq, (size_t)h->n_blocks);
+  if (!f.alloc(h->mem) || !dbl.alloc(h->mem)) return nomem("ppo", h->mem);
   HIPCHK(hipDeviceSynchronize());
-  float* p = h->scratch;
-  d.values = p; p += B;
-  d.logp = p; p += B;
-  d.ratio = p; p += B;
-  d.part = p; p += (size_t)d.tiles * P;
-  d.grad = p; p += P;
-  d.loss_part = p; p += (size_t)d.tiles * PPO_NPART;
-  d.diag = p;
-  d.adv_stat = h->dscratch;
-  d.block_sq = h->dscratch + 2;
   *out = h.release();
   return HRG_OK;
 }
@@ -4499,8 +4530,9 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
   HIPCHK(hipSetDevice(h->device));
   const PpoDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 block(PPO_BLOCK), flat((unsigned)h->n_blocks);
-  const double t = (double)(h->steps + 1), bc1 = 1.0 - std::pow(0.9, t), bc2 = 1.0 - std::pow(0.999, t);   // Adam's bias corrections, by the optimiser's step count
+  const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks);
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimiser's step count
   if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1), block, 0, st, d, advantages_dev);
   hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
                      old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
@@ -4518,7 +4550,7 @@ int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, i
   if (n < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
   HIPCHK(hipSetDevice(h->device));
   const int value_only = actions_dev ? 0 : 1;
-  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + SAC_T - 1) / SAC_T, value_only ? 1u : (unsigned)h->d.nets), dim3(PPO_BLOCK), 0, (hipStream_t)stream, h->d,
+  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T, value_only ? 1u : (unsigned)h->d.nets), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d,
                      params_dev, obs_dev, (int)n, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev, log_probs_dev);
   HIPCHK(hipGetLastError());
   if (!value_only && !deterministic && !eps_dev) h->forward_calls++;
@@ -4527,16 +4559,10 @@ int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, i
 
 int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
   if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
   const PpoDev& d = h->d;
-  const size_t B = (size_t)d.B * sizeof(float);
-  if (values_host) HIPCHK(hipMemcpy(values_host, d.values, B, hipMemcpyDeviceToHost));
-  if (log_prob_host) HIPCHK(hipMemcpy(log_prob_host, d.logp, B, hipMemcpyDeviceToHost));
-  if (ratio_host) HIPCHK(hipMemcpy(ratio_host, d.ratio, B, hipMemcpyDeviceToHost));
-  if (grad_host) HIPCHK(hipMemcpy(grad_host, d.grad, (size_t)d.n_params * sizeof(float), hipMemcpyDeviceToHost));
-  if (diag_host) HIPCHK(hipMemcpy(diag_host, d.diag, HRG_PPO_NDIAG * sizeof(float), hipMemcpyDeviceToHost));
-  return HRG_OK;
+  const size_t B = (size_t)d.B;
+  return export_floats(h->device, {{values_host, d.values, B}, {log_prob_host, d.logp, B}, {ratio_host, d.ratio, B}, {grad_host, d.grad, (size_t)d.n_params},
+                                   {diag_host, d.diag, HRG_PPO_NDIAG}});
 }
 
 int hrg_batch_launch_order(hrg_batch* b, int32_t* order_host, int32_t* n_busy_host) {

@@ -1,8 +1,8 @@
 // hrgym_ppo.h -- one minibatch step of PPO on the device: [UPSTREAM] stable-baselines3 1.5.0 PPO.train and ActorCriticPolicy for MlpPolicy, use_sde = False and Box
 // actions (written out from knowledge of that release; the package is not a dependency), with hidden layers of width 64 and tanh units, depth 1 .. 3, plus the
 // policy's and the value function's forward pass as the two callables HipVecEnv.collect_rollout takes.  Included into the base translation unit only
-// (hrgym_hip.hip, HRG_BASE_TU), after hrgym_sac.h, whose tile products it runs with SAC_ACT_TANH.  The rules are hrgym_sac.h's: no vendor BLAS, no autograd, no
-// atomics, no waiting of one workgroup on another (a dependency is a launch boundary on one stream), every loop has a bound known at launch.
+// (hrgym_hip.hip, HRG_BASE_TU), after hrgym_mlp.h: the networks are its tile products with tanh units, and its rules hold here (no vendor BLAS, no autograd, no
+// atomics, a fixed order of every sum).
 //
 // One step is four launches (hrg_ppo_step), three without normalize_advantage:
 //   1 hrg_ppo_adv_kernel     one workgroup: the minibatch's advantage mean and unbiased standard deviation (torch's), two passes.
@@ -22,8 +22,8 @@
 // The gradient of min(.,.) follows torch: where the ratio lies inside [1 - c, 1 + c] both arguments are equal and the two halves add up to the whole; outside, the
 // clamp passes nothing, and the unclipped argument passes when it is the smaller one.
 //
-// Every sum has a fixed order that does not depend on the launch (hrgym_sac.h: products k ascending, a weight gradient rows ascending, then tiles ascending); the
-// norm sums a block's 256 squares as a fixed tree and the blocks ascending.  Two learners fed the same minibatches end bit-identical.
+// The tiles' parts of a weight gradient are summed in tile order in the reduce kernel; the norm sums a block's 256 squares as a fixed tree and the blocks
+// ascending.  With hrgym_mlp.h's orders that fixes every sum: two learners fed the same minibatches end bit-identical.
 //
 // Parameters (float32, flat, allocated by the caller; torch's [out][in] weight layout).  in_0 = K, in = 64 afterwards:
 //   network n (one when shared, policy | value when separate): for l < depth: W_l [64][in_l], b_l [64]
@@ -34,9 +34,7 @@
 #pragma once
 
 enum { STREAM_PPO_ACT = 14 };   // after STREAM_SAC_ACT = 13 (hrgym_sac.h)
-#define PPO_BLOCK SAC_BLOCK
 #define PPO_NPART 6   // per tile: sum of -min(.,.), of (ratio - 1) - log ratio, of [|ratio - 1| > c], of (return - vpred)^2; a row's entropy; mean_j exp(log_std_j)
-#define PPO_HALF_LOG_2PI 0.91893853320467274178
 
 // one hrg_ppo: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
 struct PpoDev {
@@ -76,24 +74,24 @@ DI double ppo_block_sum(double* red, double mine) {
   __syncthreads();
   if (threadIdx.x == 0) {
     double sum = 0.0;
-    for (int i = 0; i < PPO_BLOCK; i++) sum += red[i];
-    red[PPO_BLOCK] = sum;
+    for (int i = 0; i < MLP_BLOCK; i++) sum += red[i];
+    red[MLP_BLOCK] = sum;
   }
   __syncthreads();
-  const double out = red[PPO_BLOCK];
+  const double out = red[MLP_BLOCK];
   __syncthreads();
   return out;
 }
 
 // ---- 1: mean and unbiased standard deviation of the minibatch's advantages
-__global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, const float* __restrict__ adv) {
-  __shared__ double red[PPO_BLOCK + 1];
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, const float* __restrict__ adv) {
+  __shared__ double red[MLP_BLOCK + 1];
   const int t = (int)threadIdx.x;
   double sum = 0.0;
-  for (int i = t; i < h.B; i += PPO_BLOCK) sum += (double)adv[i];
+  for (int i = t; i < h.B; i += MLP_BLOCK) sum += (double)adv[i];
   const double mean = ppo_block_sum(red, sum) / (double)h.B;
   double sq = 0.0;
-  for (int i = t; i < h.B; i += PPO_BLOCK) sq += ((double)adv[i] - mean) * ((double)adv[i] - mean);
+  for (int i = t; i < h.B; i += MLP_BLOCK) sq += ((double)adv[i] - mean) * ((double)adv[i] - mean);
   const double var = ppo_block_sum(red, sq) / (double)(h.B - 1);
   if (t == 0) {
     h.adv_stat[0] = mean;
@@ -102,35 +100,35 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, 
 }
 
 // ---- 2: network blockIdx.y on the tile: forward, the rows' losses and their gradients at the heads, backward
-__global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act,
                                                                  const float* __restrict__ old_values, const float* __restrict__ old_logp, const float* __restrict__ adv,
                                                                  const float* __restrict__ returns, double clip_range, double clip_range_vf) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, net = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, net = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
   const PpoHead hd = ppo_head(h, net, false);
-  const int hw = h.hw + hd.first * SAC_H, hb = h.hb + hd.first;
+  const int hw = h.hw + hd.first * MLP_H, hb = h.hb + hd.first;
   float* part = h.part + (size_t)blockIdx.x * h.n_params;
-  sac_load(s, obs, K, 0, row0, h.B);
-  sac_trunk(s, P, h.w[net], h.b[net], h.depth, K, SAC_ACT_TANH);
-  sac_head(s, P, hw, hb, h.depth, hd.nout);
+  mlp_load(s, obs, K, 0, row0, h.B);
+  mlp_trunk(s, P, h.w[net], h.b[net], h.depth, K, MLP_ACT_TANH);
+  mlp_head(s, P, hw, hb, h.depth, hd.nout);
   const double inv_b = 1.0 / (double)h.B;
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) {
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const int i = row0 + r;
     if (hd.val) {
-      const float v = s.D[r * SAC_DLD + hd.vcol], ov = old_values[i];
+      const float v = s.D[r * MLP_DLD + hd.vcol], ov = old_values[i];
       const double dv = (double)v - (double)ov;
       const bool clip = clip_range_vf >= 0.0, pass = !clip || (dv >= -clip_range_vf && dv <= clip_range_vf);
       const double vp = clip ? (double)ov + fmin(fmax(dv, -clip_range_vf), clip_range_vf) : (double)v, d = vp - (double)returns[i];
       h.values[i] = v;
       s.row[3][r] = (float)(d * d);
-      s.D[r * SAC_DLD + hd.vcol] = pass ? (float)((double)h.vf_coef * 2.0 * d * inv_b) : 0.0f;
+      s.D[r * MLP_DLD + hd.vcol] = pass ? (float)((double)h.vf_coef * 2.0 * d * inv_b) : 0.0f;
     }
     if (hd.pol) {
       double lp = 0.0;
       for (int j = 0; j < A; j++) {
-        const double ls = (double)P[h.ls + j], d = (double)act[(size_t)i * A + j] - (double)s.D[r * SAC_DLD + j];
-        lp += -0.5 * d * d * exp(-2.0 * ls) - ls - PPO_HALF_LOG_2PI;
+        const double ls = (double)P[h.ls + j], d = (double)act[(size_t)i * A + j] - (double)s.D[r * MLP_DLD + j];
+        lp += -0.5 * d * d * exp(-2.0 * ls) - ls - MLP_HALF_LOG_2PI;
       }
       const double log_ratio = lp - (double)old_logp[i], ratio = exp(log_ratio), c = clip_range;
       const double a = h.normalize ? ((double)adv[i] - h.adv_stat[0]) / (h.adv_stat[1] + 1e-8) : (double)adv[i];
@@ -138,8 +136,8 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
       const double s1 = a * ratio, s2 = a * fmin(fmax(ratio, 1.0 - c), 1.0 + c);
       const double g = (inside || s1 < s2) ? -a * ratio * inv_b : 0.0;   // d loss / d log_prob
       for (int j = 0; j < A; j++) {
-        const double ls = (double)P[h.ls + j], iv = exp(-2.0 * ls), d = (double)act[(size_t)i * A + j] - (double)s.D[r * SAC_DLD + j];
-        s.D[r * SAC_DLD + j] = (float)(g * d * iv);                                          // ... / d mu_j
+        const double ls = (double)P[h.ls + j], iv = exp(-2.0 * ls), d = (double)act[(size_t)i * A + j] - (double)s.D[r * MLP_DLD + j];
+        s.D[r * MLP_DLD + j] = (float)(g * d * iv);                                          // ... / d mu_j
         s.std[r * 8 + j] = (float)(g * (d * d * iv - 1.0) - (double)h.ent_coef * inv_b);     // ... / d log_std_j, with the entropy bonus's share of the row
       }
       h.logp[i] = (float)lp;
@@ -154,13 +152,13 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
     float* lpart = h.loss_part + (size_t)blockIdx.x * PPO_NPART;
     for (int k = hd.pol ? 0 : 3; k < (hd.val ? 4 : 3); k++) {
       double sum = 0.0;
-      for (int r = 0; r < SAC_T; r++) sum += (double)s.row[k][r];
+      for (int r = 0; r < MLP_T; r++) sum += (double)s.row[k][r];
       lpart[k] = (float)sum;
     }
     if (hd.pol) {
       double ent = 0.0, sd = 0.0;
       for (int j = 0; j < A; j++) {
-        ent += 0.5 + PPO_HALF_LOG_2PI + (double)P[h.ls + j];
+        ent += 0.5 + MLP_HALF_LOG_2PI + (double)P[h.ls + j];
         sd += exp((double)P[h.ls + j]);
       }
       lpart[4] = (float)ent;
@@ -169,15 +167,15 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
   }
   if (hd.pol && t >= 64 && t < 64 + A) {   // (a wave of its own: thread 0 is busy with the loss sums)
     double sum = 0.0;
-    for (int r = 0; r < SAC_T; r++) sum += (double)s.std[r * 8 + (t - 64)];
+    for (int r = 0; r < MLP_T; r++) sum += (double)s.std[r * 8 + (t - 64)];
     part[h.ls + t - 64] = (float)sum;
   }
-  sac_backward(s, P, h.w[net], h.b[net], hw, hb, h.depth, K, hd.nout, part, true, 0, SAC_ACT_TANH);
+  mlp_backward(s, P, h.w[net], h.b[net], hw, hb, h.depth, K, hd.nout, part, true, 0, MLP_ACT_TANH);
 }
 
 // ---- 3: the gradient (the tiles' parts in tile order) and each block's squared norm (a fixed tree over the block's 256 entries)
-__global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev h) {
-  __shared__ double red[PPO_BLOCK];
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev h) {
+  __shared__ double red[MLP_BLOCK];
   const int t = (int)threadIdx.x, i = (int)(blockIdx.x * blockDim.x) + t;
   float g = 0.0f;
   if (i < h.n_params) {
@@ -188,7 +186,7 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev 
   }
   red[t] = (double)g * (double)g;
   __syncthreads();
-  for (int w = PPO_BLOCK / 2; w > 0; w >>= 1) {
+  for (int w = MLP_BLOCK / 2; w > 0; w >>= 1) {
     if (t < w) red[t] += red[t + w];
     __syncthreads();
   }
@@ -196,13 +194,13 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev 
 }
 
 // ---- 4: clip_grad_norm_ over all parameters, torch's Adam (eps 1e-5) in double, rounded once into the float32 parameter; thread 0 of block 0: the diagnostics
-__global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int n_blocks, double lr,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int n_blocks, double lr,
                                                                  double bc1, double bc2) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   double sq = 0.0;
   for (int b = 0; b < n_blocks; b++) sq += h.block_sq[b];
   const double norm = sqrt(sq), coef = fmin(1.0, (double)h.max_grad_norm / (norm + 1e-6));
-  if (i < h.n_params) {
+  if (i < h.n_params) {   // (mlp_adam's update written out: through the helper the compiler contracts v's products the other way round, a different rounding)
     const double gd = (double)h.grad[i] * coef, m = 0.9 * (double)M[i] + 0.1 * gd, v = 0.999 * (double)V[i] + 0.001 * gd * gd;
     P[i] = (float)((double)P[i] - lr * (m / bc1) / (sqrt(v / bc2) + 1e-5));
     M[i] = (float)m;
@@ -226,35 +224,35 @@ __global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h,
 
 // ---- the forward pass on any number of rows, a tile of rows per workgroup.  value_only = 0, grid (tiles, networks): actions = mu + exp(log_std) eps (not clipped;
 // deterministic: mu), their log_prob, and the values.  value_only = 1, grid (tiles): the values.
-__global__ __launch_bounds__(PPO_BLOCK) void hrg_ppo_forward_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, int n,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_forward_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, int n,
                                                                     const float* __restrict__ eps_in, int deterministic, uint64_t call, int value_only,
                                                                     float* __restrict__ actions, float* __restrict__ values, float* __restrict__ logp) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, net = value_only ? h.nets - 1 : (int)blockIdx.y, K = h.K, A = h.A;
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, net = value_only ? h.nets - 1 : (int)blockIdx.y, K = h.K, A = h.A;
   if (row0 >= n) return;
   const PpoHead hd = ppo_head(h, net, value_only != 0);
-  sac_load(s, obs, K, 0, row0, n);
+  mlp_load(s, obs, K, 0, row0, n);
   if (hd.pol) {
     if (deterministic) {
-      for (int i = (int)threadIdx.x; i < SAC_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
+      for (int i = (int)threadIdx.x; i < MLP_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
     } else {
-      sac_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_PPO_ACT, 0);
+      mlp_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_PPO_ACT, 0);
     }
   }
-  sac_trunk(s, P, h.w[net], h.b[net], h.depth, K, SAC_ACT_TANH);
-  sac_head(s, P, h.hw + hd.first * SAC_H, h.hb + hd.first, h.depth, hd.nout);
-  for (int r = (int)threadIdx.x; r < SAC_T; r += (int)blockDim.x) {
+  mlp_trunk(s, P, h.w[net], h.b[net], h.depth, K, MLP_ACT_TANH);
+  mlp_head(s, P, h.hw + hd.first * MLP_H, h.hb + hd.first, h.depth, hd.nout);
+  for (int r = (int)threadIdx.x; r < MLP_T; r += (int)blockDim.x) {
     const int i = row0 + r;
     if (i >= n) continue;
-    if (hd.val) values[i] = s.D[r * SAC_DLD + hd.vcol];
+    if (hd.val) values[i] = s.D[r * MLP_DLD + hd.vcol];
     if (hd.pol) {
       double lp = 0.0;
       for (int j = 0; j < A; j++) {
-        const double ls = (double)P[h.ls + j], mu = (double)s.D[r * SAC_DLD + j];
+        const double ls = (double)P[h.ls + j], mu = (double)s.D[r * MLP_DLD + j];
         const float a = (float)(mu + exp(ls) * (double)s.eps[r * 8 + j]);   // the log_prob is that of the float32 action the buffer stores
         const double d = (double)a - mu;
         actions[(size_t)i * A + j] = a;
-        lp += -0.5 * d * d * exp(-2.0 * ls) - ls - PPO_HALF_LOG_2PI;
+        lp += -0.5 * d * d * exp(-2.0 * ls) - ls - MLP_HALF_LOG_2PI;
       }
       logp[i] = (float)lp;
     }

@@ -1,7 +1,7 @@
 // hrgym_sac.h -- one gradient step of SAC on the device: [UPSTREAM] stable-baselines3 1.5.0 SAC.train for use_sde = False (written out from knowledge of that
 // release; the package is not a dependency) with MlpPolicy networks of hidden width 64 and depth 1 .. 3, plus the actor's forward pass as the `policy` that
-// HipVecEnv.collect_steps takes.  Included into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_replay.h.  No vendor BLAS, no
-// autograd, no atomics, no waiting of one workgroup on another: a dependency is a launch boundary on one stream, and every loop has a bound known at launch.
+// HipVecEnv.collect_steps takes.  Included into the base translation unit only (hrgym_hip.hip, HRG_BASE_TU), after hrgym_mlp.h: the networks are its tile
+// products with ReLU units, and its rules hold here (no vendor BLAS, no autograd, no atomics, a fixed order of every sum).
 //
 // One step is six launches (hrg_sac_step):
 //   1 hrg_sac_policy_kernel   grid (tiles, 2).  y = 0: the actor on `obs` with eps_pi -> a_pi, logp.  y = 1: the actor on `next_obs` with eps_next -> a', logp',
@@ -14,14 +14,7 @@
 //   6 hrg_sac_adam_kernel     the actor's parameters, and the entropy coefficient's gradient -mean(logp + target_entropy) with its Adam step when it is learned.
 // alpha = exp(log_ent_coef) is read in 1 and 5, the coefficient moves in 6: every use in a step sees the value from before the step's update.
 //
-// A tile is SAC_T = 32 rows of the batch (the batch is a multiple of 32, at most 256: 1 .. 8 tiles), one workgroup of 256 threads, activations in LDS, the layer's
-// weights staged into LDS before each product.  Plain FMA through LDS, float32 operands and double accumulators: a 32 x 64 x 64 product is 512 FMAs per thread.
-// The exact-f32 MFMA was not taken: it accumulates in float32, and with double accumulators the device sits below the float32 noise floor the tests measure
-// instead of around it (the measured step time is in DESIGN.md D22 and profiles/r12_sac.json).
-//
-// Every sum has a fixed order that does not depend on the launch: a product sums k ascending with fma in a double accumulator (the float32
-// operands' products are exact there) and is rounded to float32 once, a weight gradient sums the tile's rows ascending and
-// then the tiles ascending (in the Adam kernel), a loss sums rows then tiles.  Two learners fed the same batches end bit-identical.
+// The batch is at most 256 rows: 1 .. 8 tiles.  The tiles' parts of a weight gradient are summed in tile order in the Adam kernel.
 //
 // What differs from SB3: the draws (rng_gauss below, not torch's generator), the summation order, the transcendentals (-fapprox-func: expf, logf, tanhf are
 // within a few ulps and are kept out of the
@@ -38,13 +31,6 @@
 #pragma once
 
 enum { STREAM_SAC = 12, STREAM_SAC_ACT = 13 };   // after STREAM_REPLAY = 11 (hrgym_replay.h)
-#define SAC_T HRG_SAC_TILE   // rows per tile
-#define SAC_BLOCK 256     // threads per workgroup
-#define SAC_H HRG_SAC_HIDDEN
-#define SAC_XLD 73        // row stride of the input tile (in0 <= 64 + 7 = 71; odd: lanes on consecutive rows meet distinct banks)
-#define SAC_HLD 65        // ... of a hidden activation
-#define SAC_WLD 72        // ... of the staged weights (read as broadcasts)
-#define SAC_DLD 17        // ... of the heads' outputs (2 A <= 14 columns)
 #define SAC_NQ HRG_SAC_NQ   // Q columns kept for the export: Q1, Q2 on (obs, act); Q1t, Q2t on (next_obs, a'); Q1, Q2 (updated) on (obs, a_pi)
 #define SAC_NLOSS 4       // per tile: sum (Q1 - y)^2, sum (Q2 - y)^2, sum (alpha logp - min Q), sum logp
 
@@ -67,172 +53,17 @@ struct SacDev {
   float* losses = nullptr;     // [4] actor_loss, critic_loss, ent_coef_loss, ent_coef (the alpha the step used)
 };
 
-struct SacLds {
-  float X[SAC_T * SAC_XLD];
-  float H[HRG_SAC_MAX_DEPTH][SAC_T * SAC_HLD];
-  float W[SAC_H * SAC_WLD];
-  float D[SAC_T * SAC_DLD];     // the heads' outputs, then their gradients
-  float eps[SAC_T * 8], act[SAC_T * 8], std[SAC_T * 8];
-  float row[4][SAC_T];          // per-row scalars
-};
-
-// ---- products on a tile.  Every thread of the workgroup calls them; the caller places the barriers.  hrgym_ppo.h runs the same products with tanh units:
-// `act` is a layer's activation, a constant at every call.  The tanh stores are loops of their own in front of the ReLU / linear ones, which stand as they stood: in
-// that form the SAC kernels compile to the instructions they had before the parameter.
-enum { SAC_ACT_NONE = 0, SAC_ACT_RELU = 1, SAC_ACT_TANH = 2 };   // tanh: evaluated in double on the double accumulator, rounded once
-// Ws[j][k] = Wg[j * in + k]
-DI void sac_stage(float* Ws, const float* __restrict__ Wg, int nout, int in) {
-  for (int i = (int)threadIdx.x; i < nout * in; i += (int)blockDim.x) Ws[(i / in) * SAC_WLD + (i % in)] = Wg[i];
-}
-
-// out[r][j] = act(b[j] + sum_k X[r][k] Ws[j][k]), k ascending.  An item is a row and eight consecutive outputs.
-DI void sac_forward(const float* X, int ldx, int in, const float* Ws, const float* __restrict__ bg, int nout, int act, float* out, int ldo) {
-  const int groups = (nout + 7) >> 3;
-  for (int it = (int)threadIdx.x; it < SAC_T * groups; it += (int)blockDim.x) {
-    const int r = it % SAC_T, j0 = (it / SAC_T) << 3, jn = min(8, nout - j0);
-    double acc[8];
-#pragma unroll
-    for (int jj = 0; jj < 8; jj++) acc[jj] = jj < jn ? bg[j0 + jj] : 0.0f;
-    for (int k = 0; k < in; k++) {
-      const float x = X[r * ldx + k];
-#pragma unroll
-      for (int jj = 0; jj < 8; jj++)
-        if (jj < jn) acc[jj] = fma((double)Ws[(j0 + jj) * SAC_WLD + k], (double)x, acc[jj]);
-    }
-    if (act == SAC_ACT_TANH) {
-#pragma unroll
-      for (int jj = 0; jj < 8; jj++)
-        if (jj < jn) out[r * ldo + j0 + jj] = (float)tanh(acc[jj]);
-      continue;
-    }
-    const bool relu = act == SAC_ACT_RELU;
-#pragma unroll
-    for (int jj = 0; jj < 8; jj++)
-      if (jj < jn) out[r * ldo + j0 + jj] = relu ? fmaxf((float)acc[jj], 0.0f) : (float)acc[jj];
-  }
-}
-
-// dst[r][k - k_lo] = sum_j dP[r][j] Ws[j][k] for k_lo <= k < in, j ascending; with an activation, dst holds the unit's output h the gradient passes through and
-// becomes the gradient at its input (ReLU: 0 where the unit was off; tanh: times 1 - h^2).  An item is a row and eight consecutive k.
-DI void sac_backward_x(const float* dP, int ldp, int nout, const float* Ws, int in, int k_lo, float* dst, int ldd, int act) {
-  const int groups = (in - k_lo + 7) >> 3;
-  for (int it = (int)threadIdx.x; it < SAC_T * groups; it += (int)blockDim.x) {
-    const int r = it % SAC_T, k0 = k_lo + ((it / SAC_T) << 3), kn = min(8, in - k0);
-    double acc[8];
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++) acc[kk] = 0.0f;
-    for (int j = 0; j < nout; j++) {
-      const float d = dP[r * ldp + j];
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++)
-        if (kk < kn) acc[kk] = fma((double)Ws[j * SAC_WLD + k0 + kk], (double)d, acc[kk]);
-    }
-    if (act == SAC_ACT_TANH) {
-#pragma unroll
-      for (int kk = 0; kk < 8; kk++)
-        if (kk < kn) {
-          float* p = dst + r * ldd + (k0 - k_lo) + kk;
-          *p = (float)(acc[kk] * (1.0 - (double)*p * (double)*p));
-        }
-      continue;
-    }
-    const bool mask = act == SAC_ACT_RELU;
-#pragma unroll
-    for (int kk = 0; kk < 8; kk++)
-      if (kk < kn) {
-        float* p = dst + r * ldd + (k0 - k_lo) + kk;
-        *p = (!mask || *p > 0.0f) ? (float)acc[kk] : 0.0f;
-      }
-  }
-}
-
-// gw[j * in + k] = sum_r dP[r][j] X[r][k], gb[j] = sum_r dP[r][j], r ascending over the tile's rows
-DI void sac_weight_grad(const float* dP, int ldp, int nout, const float* X, int ldx, int in, float* __restrict__ gw, float* __restrict__ gb) {
-  for (int i = (int)threadIdx.x; i < nout * in; i += (int)blockDim.x) {
-    const int j = i / in, k = i % in;
-    double acc = 0.0;
-    for (int r = 0; r < SAC_T; r++) acc = fma((double)dP[r * ldp + j], (double)X[r * ldx + k], acc);
-    gw[i] = (float)acc;
-  }
-  for (int j = (int)threadIdx.x; j < nout; j += (int)blockDim.x) {
-    double acc = 0.0;
-    for (int r = 0; r < SAC_T; r++) acc += (double)dP[r * ldp + j];
-    gb[j] = (float)acc;
-  }
-}
-
-// the hidden layers: s.X [.][in0] -> s.H[0 .. depth - 1].  Ends with a barrier.
-DI void sac_trunk(SacLds& s, const float* __restrict__ P, const int32_t* w, const int32_t* b, int depth, int in0, int act = SAC_ACT_RELU) {
-  for (int l = 0; l < depth; l++) {
-    const int in = l ? SAC_H : in0;
-    __syncthreads();   // the input is written, the previous layer's weights are read
-    sac_stage(s.W, P + w[l], SAC_H, in);
-    __syncthreads();
-    sac_forward(l ? s.H[l - 1] : s.X, l ? SAC_HLD : SAC_XLD, in, s.W, P + b[l], SAC_H, act, s.H[l], SAC_HLD);
-  }
-  __syncthreads();
-}
-
-// a head of `nout` outputs on s.H[depth - 1] -> s.D.  Ends with a barrier.
-DI void sac_head(SacLds& s, const float* __restrict__ P, int w, int b, int depth, int nout) {
-  sac_stage(s.W, P + w, nout, SAC_H);   // (the trunk's barrier is behind the last read of s.W)
-  __syncthreads();
-  sac_forward(s.H[depth - 1], SAC_HLD, SAC_H, s.W, P + b, nout, SAC_ACT_NONE, s.D, SAC_DLD);
-  __syncthreads();
-}
-
-// the backward pass below a head whose gradient sits in s.D [.][nout]: the head's and every hidden layer's weight gradients into `g` (this tile's part), at the
-// offsets of the parameters.  With `to_input` (0 or a first column k_lo + 1) the gradient at columns k_lo .. in0 - 1 of the input goes to s.D instead of the first
-// layer's weight gradient being the end; `weights` = false skips every weight gradient (the actor's pass through a critic).  Ends with a barrier.
-DI void sac_backward(SacLds& s, const float* __restrict__ P, const int32_t* w, const int32_t* b, int hw, int hb, int depth, int in0, int nout, float* g, bool weights,
-                     int k_lo_plus1, int act = SAC_ACT_RELU) {
-  if (weights) sac_weight_grad(s.D, SAC_DLD, nout, s.H[depth - 1], SAC_HLD, SAC_H, g + hw, g + hb);
-  sac_stage(s.W, P + hw, nout, SAC_H);
-  __syncthreads();
-  sac_backward_x(s.D, SAC_DLD, nout, s.W, SAC_H, 0, s.H[depth - 1], SAC_HLD, act);
-  __syncthreads();
-  for (int l = depth - 1; l >= 0; l--) {   // s.H[l] holds the gradient at layer l's pre-activation
-    const int in = l ? SAC_H : in0;
-    if (weights) sac_weight_grad(s.H[l], SAC_HLD, SAC_H, l ? s.H[l - 1] : s.X, l ? SAC_HLD : SAC_XLD, in, g + w[l], g + b[l]);
-    if (l == 0 && !k_lo_plus1) break;
-    sac_stage(s.W, P + w[l], SAC_H, in);
-    __syncthreads();
-    if (l) sac_backward_x(s.H[l], SAC_HLD, SAC_H, s.W, SAC_H, 0, s.H[l - 1], SAC_HLD, act);
-    else sac_backward_x(s.H[0], SAC_HLD, SAC_H, s.W, in0, k_lo_plus1 - 1, s.D, SAC_DLD, SAC_ACT_NONE);
-    __syncthreads();
-  }
-  __syncthreads();
-}
-
-// rows [row0, row0 + SAC_T) of src [n][width] into columns col0 .. of s.X; rows behind n become zero
-DI void sac_load(SacLds& s, const float* __restrict__ src, int width, int col0, int row0, int n) {
-  for (int i = (int)threadIdx.x; i < SAC_T * width; i += (int)blockDim.x) {
-    const int r = i / width, c = i % width;
-    s.X[r * SAC_XLD + col0 + c] = row0 + r < n ? src[(size_t)(row0 + r) * width + c] : 0.0f;
-  }
-}
-
-// the noise of the tile's rows: supplied, or drawn
-DI void sac_noise(SacLds& s, const float* __restrict__ eps_in, int A, int row0, int n, uint64_t seed, uint64_t count, uint64_t stream, int comp0) {
-  for (int i = (int)threadIdx.x; i < SAC_T * A; i += (int)blockDim.x) {
-    const int r = i / A, j = i % A;
-    float e = 0.0f;
-    if (row0 + r < n) e = eps_in ? eps_in[(size_t)(row0 + r) * A + j] : (float)rng_gauss(seed, count, (uint64_t)(row0 + r), stream, (uint64_t)(comp0 + j));
-    s.eps[r * 8 + j] = e;
-  }
-}
-
 // [UPSTREAM] SquashedDiagGaussianDistribution: s.D [.][0 .. A) = mu, [A .. 2A) = the log_std head (kept: the clamp's gradient reads it); s.eps -> s.act = tanh(u),
 // s.std = exp(clamp(log_std, -20, 2)), s.row[0] = logp, in double and rounded once.  One thread per row, components ascending.  The caller places the barriers.
-DI void sac_squash(SacLds& s, int A) {
-  for (int r = (int)threadIdx.x; r < SAC_T; r += (int)blockDim.x) {
+DI void sac_squash(MlpLds& s, int A) {
+  for (int r = (int)threadIdx.x; r < MLP_T; r += (int)blockDim.x) {
     double gauss = 0.0, corr = 0.0;
     for (int j = 0; j < A; j++) {
-      const double mu = (double)s.D[r * SAC_DLD + j], ls = (double)fminf(fmaxf(s.D[r * SAC_DLD + A + j], -20.0f), 2.0f), e = (double)s.eps[r * 8 + j];
+      const double mu = (double)s.D[r * MLP_DLD + j], ls = (double)fminf(fmaxf(s.D[r * MLP_DLD + A + j], -20.0f), 2.0f), e = (double)s.eps[r * 8 + j];
       const double sd = exp(ls), a = (double)(float)tanh(mu + sd * e);   // the action is the float32 value the critics read
       s.std[r * 8 + j] = (float)sd;
       s.act[r * 8 + j] = (float)a;
-      gauss += -0.5 * e * e - ls - 0.91893853320467274178;   // 0.5 log(2 pi)
+      gauss += -0.5 * e * e - ls - MLP_HALF_LOG_2PI;
       corr += log(1.0 - a * a + 1e-6);
     }
     s.row[0][r] = (float)(gauss - corr);
@@ -242,36 +73,36 @@ DI void sac_squash(SacLds& s, int A) {
 DI float sac_alpha(const SacDev& h, const float* __restrict__ P) { return h.auto_alpha ? expf(P[h.n_params - 1]) : h.alpha_fixed; }
 
 // ---- 1: the actor on obs (blockIdx.y = 0); the actor on next_obs and the targets (blockIdx.y = 1)
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_policy_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ PT, const float* __restrict__ obs,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ PT, const float* __restrict__ obs,
                                                                    const float* __restrict__ nobs, const float* __restrict__ dones, const float* __restrict__ rewards,
                                                                    const float* __restrict__ eps_pi, const float* __restrict__ eps_next, uint64_t count) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, next = (int)blockIdx.y, K = h.K, A = h.A;
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, next = (int)blockIdx.y, K = h.K, A = h.A;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
-  sac_load(s, next ? nobs : obs, K, 0, row0, h.B);
-  sac_noise(s, next ? eps_next : eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, next ? HRG_ACT_DIM : 0);
-  sac_trunk(s, P, h.a_w, h.a_b, h.depth, K);
-  sac_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
+  mlp_load(s, next ? nobs : obs, K, 0, row0, h.B);
+  mlp_noise(s, next ? eps_next : eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, next ? HRG_ACT_DIM : 0);
+  mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
+  mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
   const int t = (int)threadIdx.x;
   if (!next) {
-    for (int i = t; i < SAC_T * A; i += (int)blockDim.x) h.a_pi[(size_t)(row0 + i / A) * A + i % A] = s.act[(i / A) * 8 + i % A];
-    for (int r = t; r < SAC_T; r += (int)blockDim.x) h.logp[row0 + r] = s.row[0][r];
+    for (int i = t; i < MLP_T * A; i += (int)blockDim.x) h.a_pi[(size_t)(row0 + i / A) * A + i % A] = s.act[(i / A) * 8 + i % A];
+    for (int r = t; r < MLP_T; r += (int)blockDim.x) h.logp[row0 + r] = s.row[0][r];
     return;
   }
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) s.row[3][r] = s.row[0][r];   // logp' (s.row[0] is each head's scratch no longer, but keep it apart)
-  for (int i = t; i < SAC_T * A; i += (int)blockDim.x) s.X[(i / A) * SAC_XLD + K + i % A] = s.act[(i / A) * 8 + i % A];
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) s.row[3][r] = s.row[0][r];   // logp' (s.row[0] is each head's scratch no longer, but keep it apart)
+  for (int i = t; i < MLP_T * A; i += (int)blockDim.x) s.X[(i / A) * MLP_XLD + K + i % A] = s.act[(i / A) * 8 + i % A];
   for (int c = 0; c < 2; c++) {
     const int32_t w[HRG_SAC_MAX_DEPTH] = {h.q_w[c][0] - h.n_actor, h.q_w[c][1] - h.n_actor, h.q_w[c][2] - h.n_actor};
     const int32_t b[HRG_SAC_MAX_DEPTH] = {h.q_b[c][0] - h.n_actor, h.q_b[c][1] - h.n_actor, h.q_b[c][2] - h.n_actor};
-    sac_trunk(s, PT, w, b, h.depth, K + A);
-    sac_head(s, PT, h.q_ow[c] - h.n_actor, h.q_ob[c] - h.n_actor, h.depth, 1);
-    for (int r = t; r < SAC_T; r += (int)blockDim.x) s.row[1 + c][r] = s.D[r * SAC_DLD];
+    mlp_trunk(s, PT, w, b, h.depth, K + A, MLP_ACT_RELU);
+    mlp_head(s, PT, h.q_ow[c] - h.n_actor, h.q_ob[c] - h.n_actor, h.depth, 1);
+    for (int r = t; r < MLP_T; r += (int)blockDim.x) s.row[1 + c][r] = s.D[r * MLP_DLD];
     __syncthreads();
   }
   const float alpha = sac_alpha(h, P);
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) {
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const float q1 = s.row[1][r], q2 = s.row[2][r], lp = s.row[3][r];
     h.q[2 * h.B + row0 + r] = q1;
     h.q[3 * h.B + row0 + r] = q2;
@@ -281,101 +112,96 @@ __global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_policy_kernel(const SacDev 
 }
 
 // ---- 2: critic blockIdx.y on (obs, act): forward, (q - y) / B, backward
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_critic_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_critic_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act) {
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
-  sac_load(s, obs, K, 0, row0, h.B);
-  sac_load(s, act, A, K, row0, h.B);
-  sac_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A);
-  sac_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
+  mlp_load(s, obs, K, 0, row0, h.B);
+  mlp_load(s, act, A, K, row0, h.B);
+  mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
+  mlp_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
   const float inv_b = 1.0f / (float)h.B;
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) {
-    const float q = s.D[r * SAC_DLD], d = q - h.y[row0 + r];
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) {
+    const float q = s.D[r * MLP_DLD], d = q - h.y[row0 + r];
     h.q[c * h.B + row0 + r] = q;
     s.row[0][r] = d * d;
-    s.D[r * SAC_DLD] = d * inv_b;   // d (0.5 (mean (Q1 - y)^2 + mean (Q2 - y)^2)) / d q
+    s.D[r * MLP_DLD] = d * inv_b;   // d (0.5 (mean (Q1 - y)^2 + mean (Q2 - y)^2)) / d q
   }
   __syncthreads();
   if (t == 0) {
     double sum = 0.0;
-    for (int r = 0; r < SAC_T; r++) sum += (double)s.row[0][r];
+    for (int r = 0; r < MLP_T; r++) sum += (double)s.row[0][r];
     h.loss_part[blockIdx.x * SAC_NLOSS + c] = (float)sum;
   }
-  sac_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, h.part + (size_t)blockIdx.x * h.n_params, true, 0);
+  mlp_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, h.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
 }
 
 // ---- 4: the updated critic blockIdx.y on (obs, a_pi): q and d q / d a
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_actor_q_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_q_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs) {
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
-  sac_load(s, obs, K, 0, row0, h.B);
-  sac_load(s, h.a_pi, A, K, row0, h.B);
-  sac_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A);
-  sac_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) {
-    h.q[(4 + c) * h.B + row0 + r] = s.D[r * SAC_DLD];
-    s.D[r * SAC_DLD] = 1.0f;
+  mlp_load(s, obs, K, 0, row0, h.B);
+  mlp_load(s, h.a_pi, A, K, row0, h.B);
+  mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
+  mlp_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) {
+    h.q[(4 + c) * h.B + row0 + r] = s.D[r * MLP_DLD];
+    s.D[r * MLP_DLD] = 1.0f;
   }
   __syncthreads();
-  sac_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, nullptr, false, K + 1);
-  for (int i = t; i < SAC_T * A; i += (int)blockDim.x) h.dqda[((size_t)c * h.B + row0 + i / A) * A + i % A] = s.D[(i / A) * SAC_DLD + i % A];
+  mlp_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, nullptr, false, K + 1, MLP_ACT_RELU);
+  for (int i = t; i < MLP_T * A; i += (int)blockDim.x) h.dqda[((size_t)c * h.B + row0 + i / A) * A + i % A] = s.D[(i / A) * MLP_DLD + i % A];
 }
 
 // ---- 5: the actor's loss mean(alpha logp - min(Q1, Q2)(obs, a_pi)) and its gradient
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_actor_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ eps_pi,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ eps_pi,
                                                                   uint64_t count) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, K = h.K, A = h.A, t = (int)threadIdx.x;
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
-  sac_load(s, obs, K, 0, row0, h.B);
-  sac_noise(s, eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, 0);
-  sac_trunk(s, P, h.a_w, h.a_b, h.depth, K);
-  sac_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
+  mlp_load(s, obs, K, 0, row0, h.B);
+  mlp_noise(s, eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, 0);
+  mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
+  mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
   const float alpha = sac_alpha(h, P), inv_b = 1.0f / (float)h.B;
-  for (int r = t; r < SAC_T; r += (int)blockDim.x) {
+  for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const float q1 = h.q[4 * h.B + row0 + r], q2 = h.q[5 * h.B + row0 + r];
     const float* dq = h.dqda + ((size_t)(q1 <= q2 ? 0 : 1) * h.B + row0 + r) * A;
     s.row[1][r] = alpha * s.row[0][r] - fminf(q1, q2);
     for (int j = 0; j < A; j++) {
-      const float raw = s.D[r * SAC_DLD + A + j];
+      const float raw = s.D[r * MLP_DLD + A + j];
       const double a = (double)s.act[r * 8 + j], one = 1.0 - a * a;
       const double da = (double)alpha * (2.0 * a / (one + 1e-6)) - (double)dq[j];   // d / d a_j: logp's squash correction -log(1 - a^2 + 1e-6), and -Q
       const double du = da * one;                                                      // tanh
       const bool pass = raw >= -20.0f && raw <= 2.0f;                                  // the clamp passes a gradient inside its bounds only
-      s.D[r * SAC_DLD + j] = (float)(du * (double)inv_b);                              // u = mu + std eps
-      s.D[r * SAC_DLD + A + j] = pass ? (float)((du * (double)s.std[r * 8 + j] * (double)s.eps[r * 8 + j] - (double)alpha) * (double)inv_b) : 0.0f;   // ... and logp's own -log_std
+      s.D[r * MLP_DLD + j] = (float)(du * (double)inv_b);                              // u = mu + std eps
+      s.D[r * MLP_DLD + A + j] = pass ? (float)((du * (double)s.std[r * 8 + j] * (double)s.eps[r * 8 + j] - (double)alpha) * (double)inv_b) : 0.0f;   // ... and logp's own -log_std
     }
   }
   __syncthreads();
   if (t == 0) {
     double la = 0.0, lp = 0.0;
-    for (int r = 0; r < SAC_T; r++) { la += (double)s.row[1][r]; lp += (double)s.row[0][r]; }
+    for (int r = 0; r < MLP_T; r++) { la += (double)s.row[1][r]; lp += (double)s.row[0][r]; }
     h.loss_part[blockIdx.x * SAC_NLOSS + 2] = (float)la;
     h.loss_part[blockIdx.x * SAC_NLOSS + 3] = (float)lp;
   }
-  sac_backward(s, P, h.a_w, h.a_b, h.a_hw, h.a_hb, h.depth, K, 2 * A, h.part + (size_t)blockIdx.x * h.n_params, true, 0);
+  mlp_backward(s, P, h.a_w, h.a_b, h.a_hw, h.a_hb, h.depth, K, 2 * A, h.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
 }
 
-// ---- 3 and 6: parameters [lo, hi): the gradient (the tiles' parts in tile order), torch's Adam (betas 0.9, 0.999, eps 1e-8, no weight decay; bias corrections bc1,
-// bc2 = 1 - beta^t from the host) in double, rounded once into the float32 parameter.  `target` non-null: target[i - lo] <- (1 - tau) target + tau param, the polyak
-// update of the critics (lo = n_actor).  `coef` (the actor's launch): thread 0 of block 0 also sums the losses and, when the coefficient is learned, takes its
-// gradient -mean(logp + target_entropy) and its Adam step.
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_adam_kernel(const SacDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int lo, int hi, double lr,
+// ---- 3 and 6: parameters [lo, hi): the gradient (the tiles' parts in tile order), torch's Adam with eps 1e-8 (mlp_adam).  `target` non-null: target[i - lo] <-
+// (1 - tau) target + tau param, the polyak update of the critics (lo = n_actor).  `coef` (the actor's launch): thread 0 of block 0 also sums the losses and, when
+// the coefficient is learned, takes its gradient -mean(logp + target_entropy) and its Adam step.
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int lo, int hi, double lr,
                                                                  double bc1, double bc2, float* __restrict__ target, double tau, int coef) {
   const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i < hi) {
     float g = h.part[i];
     for (int tl = 1; tl < h.tiles; tl++) g += h.part[(size_t)tl * h.n_params + i];
     h.grad[i] = g;
-    const double gd = (double)g, m = 0.9 * (double)M[i] + 0.1 * gd, v = 0.999 * (double)V[i] + 0.001 * gd * gd;
-    const float p = (float)((double)P[i] - lr * (m / bc1) / (sqrt(v / bc2) + 1e-8));
-    M[i] = (float)m;
-    V[i] = (float)v;
-    P[i] = p;
+    const float p = mlp_adam(P, M, V, i, (double)g, lr, bc1, bc2, 1e-8);
     if (target) target[i - lo] = (float)((1.0 - tau) * (double)target[i - lo] + tau * (double)p);
   }
   if (coef && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -397,30 +223,27 @@ __global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_adam_kernel(const SacDev h,
     if (h.auto_alpha) {
       const float g = -mean_lp;
       h.grad[ia] = g;
-      const double gd = (double)g, m = 0.9 * (double)M[ia] + 0.1 * gd, v = 0.999 * (double)V[ia] + 0.001 * gd * gd;
-      P[ia] = (float)((double)P[ia] - lr * (m / bc1) / (sqrt(v / bc2) + 1e-8));
-      M[ia] = (float)m;
-      V[ia] = (float)v;
+      mlp_adam(P, M, V, ia, (double)g, lr, bc1, bc2, 1e-8);
     }
   }
 }
 
 // ---- the actor's forward pass on any number of rows: tanh(mu + std eps) or, deterministic, tanh(mu); a tile of rows per workgroup
-__global__ __launch_bounds__(SAC_BLOCK) void hrg_sac_act_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, int n, const float* __restrict__ eps_in,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_act_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, int n, const float* __restrict__ eps_in,
                                                                 int deterministic, uint64_t call, float* __restrict__ out) {
-  __shared__ SacLds s;
-  const int row0 = (int)blockIdx.x * SAC_T, K = h.K, A = h.A;
+  __shared__ MlpLds s;
+  const int row0 = (int)blockIdx.x * MLP_T, K = h.K, A = h.A;
   if (row0 >= n) return;
-  sac_load(s, obs, K, 0, row0, n);
+  mlp_load(s, obs, K, 0, row0, n);
   if (deterministic) {
-    for (int i = (int)threadIdx.x; i < SAC_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
+    for (int i = (int)threadIdx.x; i < MLP_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
   } else {
-    sac_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_SAC_ACT, 0);
+    mlp_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_SAC_ACT, 0);
   }
-  sac_trunk(s, P, h.a_w, h.a_b, h.depth, K);
-  sac_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
+  mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
+  mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
-  for (int i = (int)threadIdx.x; i < SAC_T * A; i += (int)blockDim.x)
+  for (int i = (int)threadIdx.x; i < MLP_T * A; i += (int)blockDim.x)
     if (row0 + i / A < n) out[(size_t)(row0 + i / A) * A + i % A] = s.act[(i / A) * 8 + i % A];
 }

@@ -12,14 +12,12 @@ and Adam moments are flat float32 torch tensors; `state_dict()` hands out views 
     learner.train(env.rollout)                           # n_epochs x (rollout.get(batch_size) -> step): no host copy, no synchronisation
     learner.diagnostics()                                # SB3's train/ keys of the last minibatch (synchronous)
 """
-import ctypes
 import math
-from collections import OrderedDict
 
 import numpy as np
 
 from ._cstruct import CONST, PpoDesc
-from ._device import DeviceHandle
+from ._learner import Learner, LearnerParams, build_layout, check_widths, mlp_entries
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_PPO_HIDDEN"]
@@ -74,13 +72,7 @@ def build_ppo_desc(obs_dim, act_dim, net_arch=None, batch_size=64, rollout_size=
     if policy != "MlpPolicy":
         raise NotImplementedError(f"policy = {policy!r}: the device learner covers MlpPolicy (dict observations belong to the off-policy path)")
     depth, separate = parse_net_arch([dict(pi=[64, 64], vf=[64, 64])] if net_arch is None else net_arch)
-    obs_dim, act_dim, batch_size, rollout_size = int(obs_dim), int(act_dim), int(batch_size), int(rollout_size)
-    if not 1 <= obs_dim <= CONST["HRG_OBS_DIM"]:
-        raise NotImplementedError(f"obs_dim = {obs_dim}: the kernels cover observations of 1 .. {CONST['HRG_OBS_DIM']} values")
-    if not 1 <= act_dim <= CONST["HRG_ACT_DIM"]:
-        raise NotImplementedError(f"act_dim = {act_dim}: the kernels cover actions of 1 .. {CONST['HRG_ACT_DIM']} values")
-    if batch_size % TILE or not TILE <= batch_size <= MAX_BATCH:
-        raise NotImplementedError(f"batch_size = {batch_size}: the kernels cover multiples of {TILE} from {TILE} to {MAX_BATCH}")
+    (obs_dim, act_dim, batch_size), rollout_size = check_widths(obs_dim, act_dim, batch_size, TILE, MAX_BATCH), int(rollout_size)
     if rollout_size < 0 or rollout_size % batch_size:
         raise NotImplementedError(f"batch_size = {batch_size} does not divide n_envs * n_steps = {rollout_size}: the learner takes no short last minibatch")
     ent_coef, vf_coef, max_grad_norm = float(ent_coef), float(vf_coef), float(max_grad_norm)
@@ -101,23 +93,8 @@ def param_layout(obs_dim, act_dim, depth, separate):
     mlp_extractor.shared_net.{0,2,4}.* or mlp_extractor.policy_net.* | mlp_extractor.value_net.*, then action_net.weight, value_net.weight, action_net.bias,
     value_net.bias (the two heads are one [A + 1][64] product), then log_std."""
     K, A, H = int(obs_dim), int(act_dim), HIDDEN
-    out, o = OrderedDict(), 0
-
-    def put(name, shape):
-        nonlocal o
-        out[name] = (o, shape)
-        o += int(np.prod(shape))
-
-    for net in (("policy_net", "value_net") if separate else ("shared_net",)):
-        for l in range(depth):
-            put(f"mlp_extractor.{net}.{2 * l}.weight", (H, H if l else K))
-            put(f"mlp_extractor.{net}.{2 * l}.bias", (H,))
-    put("action_net.weight", (A, H))
-    put("value_net.weight", (1, H))
-    put("action_net.bias", (A,))
-    put("value_net.bias", (1,))
-    put("log_std", (A,))
-    return out, o
+    entries = [e for net in (("policy_net", "value_net") if separate else ("shared_net",)) for e in mlp_entries(f"mlp_extractor.{net}", depth, K, H)]
+    return build_layout(entries + [("action_net.weight", (A, H)), ("value_net.weight", (1, H)), ("action_net.bias", (A,)), ("value_net.bias", (1,)), ("log_std", (A,))])
 
 
 def group_of(name):
@@ -125,65 +102,39 @@ def group_of(name):
     return "trunk" if name.startswith("mlp_extractor.") else name.split(".")[0]
 
 
-class PpoParams:
-    """The learner's tensors, on any torch device: `params`, `adam_m`, `adam_v` float32 [n_params], with `state_dict()` views under SB3's names.  Initial weights
-    are drawn under a forked generator seeded with `seed`, a layer after the other in the layout's order.  [UPSTREAM] `ortho_init` True: ActorCriticPolicy's
-    orthogonal_ with gain sqrt 2 for the hidden layers, 0.01 for action_net and 1 for value_net, biases zero; False: torch.nn.Linear's own initialisation.
-    log_std = `log_std_init` in every component."""
+class PpoParams(LearnerParams):
+    """The learner's tensors, on any torch device: `params`, `adam_m`, `adam_v` float32 [n_params], with `state_dict()` views under SB3's names (log_std,
+    mlp_extractor.shared_net.{0,2,4}.* or mlp_extractor.policy_net.* / mlp_extractor.value_net.*, action_net.*, value_net.*).  Initial weights are drawn under a
+    forked generator seeded with `seed`, a layer after the other in the layout's order.  [UPSTREAM] `ortho_init` True: ActorCriticPolicy's orthogonal_ with gain
+    sqrt 2 for the hidden layers, 0.01 for action_net and 1 for value_net, biases zero; False: torch.nn.Linear's own initialisation.  log_std = `log_std_init`
+    in every component."""
 
     def __init__(self, obs_dim, act_dim, depth, separate, seed=0, log_std_init=0.0, ortho_init=True, device="cpu"):
-        import torch
-        self.torch = torch
         self.obs_dim, self.act_dim, self.depth, self.separate = int(obs_dim), int(act_dim), int(depth), bool(separate)
-        self.layout, self.n_params = param_layout(obs_dim, act_dim, depth, separate)
-        flat = torch.zeros(self.n_params, dtype=torch.float32)
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(int(seed))
-            for name, (off, shape) in self.layout.items():   # a Linear per weight entry
-                if not name.endswith(".weight"):
-                    continue
-                lin = torch.nn.Linear(shape[1], shape[0])
-                if ortho_init:
-                    gain = {"trunk": math.sqrt(2.0), "action_net": 0.01, "value_net": 1.0}[group_of(name)]
-                    torch.nn.init.orthogonal_(lin.weight, gain=gain)
-                    lin.bias.data.fill_(0.0)
-                flat[off:off + lin.weight.numel()] = lin.weight.detach().reshape(-1)
-                boff, _ = self.layout[name[:-len("weight")] + "bias"]
-                flat[boff:boff + shape[0]] = lin.bias.detach()
+        self.log_std_init, self.ortho_init = float(log_std_init), bool(ortho_init)
+        super().__init__(*param_layout(obs_dim, act_dim, depth, separate), seed, device)
+
+    def _init_linear(self, name, lin):
+        if self.ortho_init:
+            gain = {"trunk": math.sqrt(2.0), "action_net": 0.01, "value_net": 1.0}[group_of(name)]
+            self.torch.nn.init.orthogonal_(lin.weight, gain=gain)
+            lin.bias.data.fill_(0.0)
+
+    def _init_rest(self, flat):
         off, _ = self.layout["log_std"]
-        flat[off:off + self.act_dim] = float(log_std_init)
-        self.params = flat.to(device)
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-
-    def state_dict(self):
-        """OrderedDict of views into `params` under SB3's names (writing into one writes the learner's parameter)."""
-        return OrderedDict((name, self.params[off:off + int(np.prod(shape))].view(shape)) for name, (off, shape) in self.layout.items())
-
-    def load_state_dict(self, state):
-        """Copies every entry of `state` (tensors or arrays of the entries' shapes, every name of `state_dict()` present) into the learner's tensors."""
-        t = self.torch
-        own = self.state_dict()
-        missing, unknown = sorted(set(own) - set(state)), sorted(set(state) - set(own))
-        if missing or unknown:
-            raise KeyError(f"load_state_dict: missing {missing}, unknown {unknown}")
-        with t.no_grad():
-            for name, view in own.items():
-                src = t.as_tensor(state[name])
-                if tuple(src.shape) != tuple(view.shape):
-                    raise ValueError(f"load_state_dict: {name} has shape {tuple(src.shape)}, expected {tuple(view.shape)}")
-                view.copy_(src.to(device=view.device, dtype=view.dtype))
+        flat[off:off + self.act_dim] = self.log_std_init
 
     def group(self, flat, which):
         """The entries of a parameter-shaped vector that belong to "trunk" (every hidden layer), "action_net", "value_net" or "log_std", in the layout's order."""
         return self.torch.cat([flat[off:off + int(np.prod(shape))] for name, (off, shape) in self.layout.items() if group_of(name) == which])
 
 
-class PpoLearner(DeviceHandle):
+class PpoLearner(Learner):
     """SB3's PPO update on the device for the shapes the kernels cover (`build_ppo_desc` refuses the rest).  `learning_rate`, `clip_range` and `clip_range_vf`
     (None: the value function is not clipped) are plain attributes, passed with every step: a caller may schedule them.  All tensor arguments and results live
     on the learner's device; `step`, `train`, `policy` and `value` are asynchronous, ordered on torch's current stream; `diagnostics` and `export` synchronise."""
 
-    _create, _destroy = "hrg_ppo_create", "hrg_ppo_destroy"
+    _prefix = "hrg_ppo"
 
     def __init__(self, obs_dim, act_dim, net_arch=None, learning_rate=3e-4, batch_size=64, n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, use_sde=False, target_kl=None, policy="MlpPolicy", log_std_init=0.0, ortho_init=True, rollout_size=0,
@@ -205,19 +156,6 @@ class PpoLearner(DeviceHandle):
             raise RuntimeError(f"PpoLearner: the library lays out {self._sizes()[0]} parameters, ppo.param_layout {self.p.n_params}: rebuild")
         self._keep = None
 
-    def _sizes(self):
-        w = (ctypes.c_int64 * 6)()
-        self._check(self.lib, self.lib.hrg_ppo_sizes(self.h, w))
-        return [int(x) for x in w]
-
-    @property
-    def n_updates(self):
-        """Minibatch steps so far (the optimiser's step count)."""
-        return self._sizes()[3]
-
-    def _tensor(self, x, shape, what):
-        return super()._tensor(x, self.torch.float32, shape, what)
-
     def step(self, batch):
         """One minibatch step on `batch`, a RolloutBufferSamples of `batch_size` rows (observations [B, obs_dim], actions [B, act_dim], old_values,
         old_log_prob, advantages, returns [B])."""
@@ -234,9 +172,8 @@ class PpoLearner(DeviceHandle):
     def train(self, rollout):
         """PPO.train: `n_epochs` x (rollout.get(batch_size) -> step), with no copy to the host and no synchronisation.  batch_size must divide the buffer's
         n_envs * n_steps: the learner takes no short last minibatch."""
-        if (int(rollout.obs_dim), int(rollout.act_dim)) != (self.obs_dim, self.act_dim):
-            raise ValueError(f"train: the buffer holds observations of {rollout.obs_dim} and actions of {rollout.act_dim} values, the learner takes {self.obs_dim} and {self.act_dim}")
-        N = int(rollout.n) * int(rollout.n_steps)
+        self._check_buffer(rollout.obs_dim, rollout.act_dim)
+        N =int(rollout.n) * int(rollout.n_steps)
         if N % self.batch_size:
             raise NotImplementedError(f"train: batch_size = {self.batch_size} does not divide n_envs * n_steps = {N}: the learner takes no short last minibatch")
         for _ in range(self.n_epochs):
@@ -245,12 +182,8 @@ class PpoLearner(DeviceHandle):
 
     def _forward(self, obs, eps, deterministic, with_actions):
         t = self.torch
-        if obs.dim() != 2:
-            raise ValueError(f"obs: expected [n, {self.obs_dim}], got {tuple(obs.shape)}")
-        n = int(obs.shape[0])
-        o = self._tensor(obs, (n, self.obs_dim), "obs")
-        e = None if eps is None else self._tensor(eps, (n, self.act_dim), "eps")
-        values = t.empty(n, dtype=t.float32, device=self.device)
+        n, o, e = self._rows(obs, eps)
+        values =t.empty(n, dtype=t.float32, device=self.device)
         actions = t.empty(n, self.act_dim, dtype=t.float32, device=self.device) if with_actions else None
         log_probs = t.empty(n, dtype=t.float32, device=self.device) if with_actions else None
         with t.cuda.device(self.device):
@@ -268,28 +201,20 @@ class PpoLearner(DeviceHandle):
         """ActorCriticPolicy.predict_values on `obs` float32 [n, obs_dim]: float32 [n].  This is the `value_fn` HipVecEnv.collect_rollout takes."""
         return self._forward(obs, None, True, False)[1]
 
-    def state_dict(self):
-        """Views of the parameters under SB3's names (PpoParams.state_dict): log_std, mlp_extractor.shared_net.{0,2,4}.* or mlp_extractor.policy_net.* /
-        mlp_extractor.value_net.*, action_net.*, value_net.*; torch's [out, in] weight layout."""
-        return self.p.state_dict()
-
-    def load_state_dict(self, state):
-        self.p.load_state_dict(state)
-
     def export(self):
         """The last step's intermediates on the host (synchronous; tests): values, log_prob, ratio [B]; grad [n_params] in the parameters' layout, before
         clipping (`self.p.group(grad, "trunk")`, ...); diag: dict of DIAG_KEYS."""
         B = self.batch_size
         values, log_prob, ratio = np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)
         grad, diag = np.zeros(self.p.n_params, np.float32), np.zeros(NDIAG, np.float32)
-        self._check(self.lib, self.lib.hrg_ppo_export(self.h, *(a.ctypes.data_as(ctypes.c_void_p) for a in (values, log_prob, ratio, grad, diag))))
+        self._export(values, log_prob, ratio, grad, diag)
         return dict(values=values, log_prob=log_prob, ratio=ratio, grad=grad, diag=dict(zip(DIAG_KEYS, (float(x) for x in diag))))
 
     def diagnostics(self):
         """What SB3 logs under train/ after a call of train(), from the last minibatch: policy_gradient_loss, value_loss, entropy_loss, loss, approx_kl,
         clip_fraction, std, plus grad_norm (before clipping), clip_range, clip_range_vf where set, learning_rate and n_updates.  Synchronous."""
         diag = np.zeros(NDIAG, np.float32)
-        self._check(self.lib, self.lib.hrg_ppo_export(self.h, None, None, None, None, diag.ctypes.data_as(ctypes.c_void_p)))
+        self._export(None, None, None, None, diag)
         out = dict(zip(DIAG_KEYS, (float(x) for x in diag)))
         out.update(clip_range=self.clip_range, learning_rate=self.learning_rate, n_updates=self.n_updates)
         if self.clip_range_vf is not None:

@@ -21,14 +21,12 @@ read the row achieved_goal | desired_goal | observation; her.HerBuffer hands out
     env.collect_steps(learner.act, 100)
     learner.train(env.her, 400)                    # 400 x (env.her.sample_features(128), step): one read of the buffer's size, then nothing synchronises
 """
-import ctypes
 import math
-from collections import OrderedDict
 
 import numpy as np
 
 from ._cstruct import CONST, SacDesc
-from ._device import DeviceHandle
+from ._learner import Learner, LearnerParams, build_layout, check_widths, mlp_entries
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_SAC_HIDDEN"]
@@ -83,13 +81,7 @@ def build_sac_desc(obs_dim, act_dim, net_arch=(64, 64, 64), gamma=0.99, tau=0.00
                    target_update_interval=1, seed=0):
     """hrg_sac_desc (include/hrgym.h).  Everything the kernels do not cover is refused here, before anything is allocated or launched."""
     depth = depth_of(net_arch)
-    obs_dim, act_dim, batch_size = int(obs_dim), int(act_dim), int(batch_size)
-    if not 1 <= obs_dim <= CONST["HRG_OBS_DIM"]:
-        raise NotImplementedError(f"obs_dim = {obs_dim}: the kernels cover observations of 1 .. {CONST['HRG_OBS_DIM']} values")
-    if not 1 <= act_dim <= CONST["HRG_ACT_DIM"]:
-        raise NotImplementedError(f"act_dim = {act_dim}: the kernels cover actions of 1 .. {CONST['HRG_ACT_DIM']} values")
-    if batch_size % TILE or not TILE <= batch_size <= MAX_BATCH:
-        raise NotImplementedError(f"batch_size = {batch_size}: the kernels cover multiples of {TILE} from {TILE} to {MAX_BATCH}")
+    obs_dim, act_dim, batch_size = check_widths(obs_dim, act_dim, batch_size, TILE, MAX_BATCH)
     if int(target_update_interval) < 1:
         raise ValueError(f"target_update_interval = {target_update_interval} must be positive")
     learned, value = parse_ent_coef(ent_coef)
@@ -107,81 +99,40 @@ def param_layout(obs_dim, act_dim, depth):
     actor | critic.qf0 | critic.qf1 | log_ent_coef, and (n_params, n_actor, n_critic).  The targets are the two critics' entries as `critic_target.*`, offsets
     less n_actor, in a vector of their own."""
     K, A, H = int(obs_dim), int(act_dim), HIDDEN
-    out, o = OrderedDict(), 0
-
-    def put(name, shape):
-        nonlocal o
-        out[name] = (o, shape)
-        o += int(np.prod(shape))
-
-    for l in range(depth):
-        put(f"actor.latent_pi.{2 * l}.weight", (H, H if l else K))
-        put(f"actor.latent_pi.{2 * l}.bias", (H,))
-    put("actor.mu.weight", (A, H))
-    put("actor.log_std.weight", (A, H))
-    put("actor.mu.bias", (A,))
-    put("actor.log_std.bias", (A,))
-    n_actor = o
+    entries = [*mlp_entries("actor.latent_pi", depth, K, H), ("actor.mu.weight", (A, H)), ("actor.log_std.weight", (A, H)), ("actor.mu.bias", (A,)),
+               ("actor.log_std.bias", (A,))]
     for q in range(2):
-        for l in range(depth):
-            put(f"critic.qf{q}.{2 * l}.weight", (H, H if l else K + A))
-            put(f"critic.qf{q}.{2 * l}.bias", (H,))
-        put(f"critic.qf{q}.{2 * depth}.weight", (1, H))
-        put(f"critic.qf{q}.{2 * depth}.bias", (1,))
-    n_critic = (o - n_actor) // 2
-    put("log_ent_coef", (1,))
-    return out, (o, n_actor, n_critic)
+        entries += [*mlp_entries(f"critic.qf{q}", depth, K + A, H), (f"critic.qf{q}.{2 * depth}.weight", (1, H)), (f"critic.qf{q}.{2 * depth}.bias", (1,))]
+    out, n = build_layout(entries + [("log_ent_coef", (1,))])
+    n_actor = out["critic.qf0.0.weight"][0]
+    return out, (n, n_actor, (n - 1 - n_actor) // 2)
 
 
-class SacParams:
+class SacParams(LearnerParams):
     """The learner's tensors, on any torch device: `params`, `adam_m`, `adam_v` float32 [n_params] and `target` float32 [2 n_critic], with `state_dict()`
     views under SB3's names.  Initial weights: torch.nn.Linear's own initialisation under a generator seeded with `seed` (actor, mu, log_std, qf0, qf1, in
     that order); the targets start as copies; log_ent_coef = log(`ent_coef_init`)."""
 
     def __init__(self, obs_dim, act_dim, depth, seed=0, ent_coef_init=1.0, device="cpu"):
-        import torch
-        self.torch = torch
-        self.obs_dim, self.act_dim, self.depth = int(obs_dim), int(act_dim), int(depth)
-        self.layout, (self.n_params, self.n_actor, self.n_critic) = param_layout(obs_dim, act_dim, depth)
-        flat = torch.zeros(self.n_params, dtype=torch.float32)
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(int(seed))
-            for name, (off, shape) in self.layout.items():   # a Linear per weight entry; its bias is the entry that follows (or, for the heads, follows the pair)
-                if not name.endswith(".weight"):
-                    continue
-                lin = torch.nn.Linear(shape[1], shape[0])
-                flat[off:off + lin.weight.numel()] = lin.weight.detach().reshape(-1)
-                boff, _ = self.layout[name[:-len("weight")] + "bias"]
-                flat[boff:boff + shape[0]] = lin.bias.detach()
-        flat[-1] = math.log(float(ent_coef_init))
-        self.params = flat.to(device)
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.obs_dim, self.act_dim, self.depth, self.ent_coef_init = int(obs_dim), int(act_dim), int(depth), float(ent_coef_init)
+        layout, (n_params, self.n_actor, self.n_critic) = param_layout(obs_dim, act_dim, depth)
+        super().__init__(layout, n_params, seed, device)
         self.target = self.params[self.n_actor:self.n_actor + 2 * self.n_critic].clone()
 
+    def _init_rest(self, flat):
+        flat[-1] = math.log(self.ent_coef_init)
+
     def state_dict(self):
-        """OrderedDict of views into `params` and `target` under SB3's names (writing into one writes the learner's parameter)."""
-        out = OrderedDict()
-        for name, (off, shape) in self.layout.items():
-            out[name] = self.params[off:off + int(np.prod(shape))].view(shape)
+        """OrderedDict of views into `params` and `target` under SB3's names (writing into one writes the learner's parameter): actor.latent_pi.{0,2,4}.*,
+        actor.mu.*, actor.log_std.*, critic.qf{0,1}.{0,2,4,6}.*, log_ent_coef, then critic_target.qf{0,1}.*.  The same names under MultiInputPolicy: its
+        CombinedExtractor over Box entries is a Flatten per entry and has no parameters ([UPSTREAM]: from knowledge of SB3 1.5.0), so a dict-observation SAC
+        holds the MLPs' entries only."""
+        out = super().state_dict()
         for name, (off, shape) in self.layout.items():
             if name.startswith("critic."):
                 o = off - self.n_actor
                 out["critic_target." + name[len("critic."):]] = self.target[o:o + int(np.prod(shape))].view(shape)
         return out
-
-    def load_state_dict(self, state):
-        """Copies every entry of `state` (tensors or arrays of the entries' shapes, every name of `state_dict()` present) into the learner's tensors."""
-        t = self.torch
-        own = self.state_dict()
-        missing, unknown = sorted(set(own) - set(state)), sorted(set(state) - set(own))
-        if missing or unknown:
-            raise KeyError(f"load_state_dict: missing {missing}, unknown {unknown}")
-        with t.no_grad():
-            for name, view in own.items():
-                src = t.as_tensor(state[name])
-                if tuple(src.shape) != tuple(view.shape):
-                    raise ValueError(f"load_state_dict: {name} has shape {tuple(src.shape)}, expected {tuple(view.shape)}")
-                view.copy_(src.to(device=view.device, dtype=view.dtype))
 
     def group(self, flat, which):
         """The slice of a parameter-shaped vector that belongs to "actor", "qf0", "qf1" or "log_ent_coef"."""
@@ -190,12 +141,12 @@ class SacParams:
         return flat[lo:hi]
 
 
-class SacLearner(DeviceHandle):
+class SacLearner(Learner):
     """SB3's SAC on the device for the shapes the kernels cover (`build_sac_desc` refuses the rest).  `learning_rate` is a plain attribute, passed with every
     step: a caller may schedule it.  All tensor arguments and results live on the learner's device; `step`, `train` and `act` are asynchronous, ordered on
     torch's current stream; `diagnostics` and `export` synchronise."""
 
-    _create, _destroy = "hrg_sac_create", "hrg_sac_destroy"
+    _prefix = "hrg_sac"
 
     def __init__(self, obs_dim, act_dim, net_arch=(64, 64, 64), learning_rate=3e-4, gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto",
                  batch_size=256, target_update_interval=1, seed=0, device=0):
@@ -210,19 +161,6 @@ class SacLearner(DeviceHandle):
         if sizes[:3] != [self.p.n_params, self.p.n_actor, self.p.n_critic]:
             raise RuntimeError(f"SacLearner: the library lays out {sizes[:3]} parameters, sac.param_layout {[self.p.n_params, self.p.n_actor, self.p.n_critic]}: rebuild")
         self._keep = None
-
-    def _sizes(self):
-        w = (ctypes.c_int64 * 6)()
-        self._check(self.lib, self.lib.hrg_sac_sizes(self.h, w))
-        return [int(x) for x in w]
-
-    @property
-    def n_updates(self):
-        """Gradient steps so far (SB3's _n_updates)."""
-        return self._sizes()[3]
-
-    def _tensor(self, x, shape, what):
-        return super()._tensor(x, self.torch.float32, shape, what)
 
     def step(self, batch, eps_pi=None, eps_next=None):
         """One gradient step on `batch`, a ReplayBufferSamples of `batch_size` rows (observations, next_observations [B, obs_dim], actions [B, act_dim], dones,
@@ -248,9 +186,7 @@ class SacLearner(DeviceHandle):
         `replay`: a replay.ReplayBuffer, or a her.HerBuffer, whose samples are its feature rows (`sample_features`): its size is read once, first (an empty
         hindsight buffer raises); after that line nothing on the host waits for the device."""
         hindsight = hasattr(replay, "sample_features")
-        obs_dim = int(replay.obs_features if hindsight else replay.obs_dim)
-        if (obs_dim, int(replay.act_dim)) != (self.obs_dim, self.act_dim):
-            raise ValueError(f"train: the buffer holds observations of {obs_dim} and actions of {replay.act_dim} values, the learner takes {self.obs_dim} and {self.act_dim}")
+        self._check_buffer(replay.obs_features if hindsight else replay.obs_dim, replay.act_dim)
         if hindsight:
             replay.require_samples()
         sample = replay.sample_features if hindsight else replay.sample
@@ -261,24 +197,11 @@ class SacLearner(DeviceHandle):
         """The actor's actions for `obs` float32 [n, obs_dim]: float32 [n, act_dim] in (-1, 1), tanh(mu + std eps), or tanh(mu) with `deterministic`.  This is the
         `policy` HipVecEnv.collect_steps takes.  `eps` float32 [n, act_dim] replaces the draws (tests)."""
         t = self.torch
-        if obs.dim() != 2:
-            raise ValueError(f"obs: expected [n, {self.obs_dim}], got {tuple(obs.shape)}")
-        n = int(obs.shape[0])
-        o = self._tensor(obs, (n, self.obs_dim), "obs")
-        e = None if eps is None else self._tensor(eps, (n, self.act_dim), "eps")
+        n, o, e = self._rows(obs, eps)
         out = t.empty(n, self.act_dim, dtype=t.float32, device=self.device)
         with t.cuda.device(self.device):
             self._check(self.lib, self.lib.hrg_sac_act(self.h, _ptr(self.p.params), o, n, e, int(bool(deterministic)), _ptr(out), self._stream()))
         return out
-
-    def state_dict(self):
-        """Views of the parameters under SB3's names (SacParams.state_dict): actor.latent_pi.{0,2,4}.*, actor.mu.*, actor.log_std.*, critic.qf{0,1}.{0,2,4,6}.*,
-        critic_target.qf{0,1}.*, log_ent_coef; torch's [out, in] weight layout.  The same names under MultiInputPolicy: its CombinedExtractor over Box
-        entries is a Flatten per entry and has no parameters ([UPSTREAM]: from knowledge of SB3 1.5.0), so a dict-observation SAC holds the MLPs' entries only."""
-        return self.p.state_dict()
-
-    def load_state_dict(self, state):
-        self.p.load_state_dict(state)
 
     def export(self):
         """The last step's intermediates on the host (synchronous; tests): y, logp, logp_next [B]; q [6, B] (Q_COLUMNS); grad [n_params] in the parameters'
@@ -286,12 +209,12 @@ class SacLearner(DeviceHandle):
         B = self.batch_size
         y, logp, logp_next, q = (np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros((NQ, B), np.float32))
         grad, losses = np.zeros(self.p.n_params, np.float32), np.zeros(4, np.float32)
-        self._check(self.lib, self.lib.hrg_sac_export(self.h, *(a.ctypes.data_as(ctypes.c_void_p) for a in (y, logp, logp_next, q, grad, losses))))
+        self._export(y, logp, logp_next, q, grad, losses)
         return dict(y=y, logp=logp, logp_next=logp_next, q=q, grad=grad, losses=losses)
 
     def diagnostics(self):
         """What SB3 logs under train/ after a call of train(): ent_coef (the one the last step used), actor_loss, critic_loss, ent_coef_loss of the last step, and
         n_updates.  Synchronous."""
         losses = np.zeros(4, np.float32)
-        self._check(self.lib, self.lib.hrg_sac_export(self.h, None, None, None, None, None, losses.ctypes.data_as(ctypes.c_void_p)))
+        self._export(None, None, None, None, None, losses)
         return dict(ent_coef=float(losses[3]), actor_loss=float(losses[0]), critic_loss=float(losses[1]), ent_coef_loss=float(losses[2]), n_updates=self.n_updates)

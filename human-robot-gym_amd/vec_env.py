@@ -1003,11 +1003,16 @@ class HipVecEnv(_VecEnvBase):
         if rb is None:
             raise NotImplementedError("attach_ppo: call attach_rollout(n_steps, gamma, gae_lambda) first (the learner takes its observation and action widths from the buffer)")
         from .ppo import PpoLearner
+        return self._attach_learner("ppo", PpoLearner, rb.obs_dim, rb, rollout_size=rb.n * rb.n_steps, **kwargs)
+
+    def _attach_learner(self, slot, cls, obs_dim, rb, **kwargs):
+        """What attach_ppo and attach_sac end with: the learner of the buffer's action width and device, seeded like the env unless told otherwise, kept as
+        `env.<slot>` in place of the previous one, which is closed."""
         kwargs.setdefault("seed", int(self._desc.seed))
-        learner = PpoLearner(rb.obs_dim, rb.act_dim, device=rb.device.index, rollout_size=rb.n * rb.n_steps, **kwargs)
-        if self.ppo is not None:
-            self.ppo.close()
-        self.ppo = learner
+        learner = cls(obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
+        if getattr(self, slot) is not None:
+            getattr(self, slot).close()
+        setattr(self, slot, learner)
         return learner
 
     def _enter_device_loop(self, name, account):
@@ -1087,12 +1092,7 @@ class HipVecEnv(_VecEnvBase):
                 raise NotImplementedError(f"attach_sac: {policy} would see {rb.ag_dim} + {rb.dg_dim} + {rb.obs_dim} = {obs_dim} values (achieved_goal, desired_goal, "
                                           f"observation); the kernels cover {CONST['HRG_OBS_DIM']}: construct the env with obs_keys that select fewer columns")
         from .sac import SacLearner
-        kwargs.setdefault("seed", int(self._desc.seed))
-        learner = SacLearner(obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
-        if self.sac is not None:
-            self.sac.close()
-        self.sac = learner
-        return self.sac
+        return self._attach_learner("sac", SacLearner, obs_dim, rb, **kwargs)
 
     def collect_steps(self, policy, n_steps):
         """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`, on a goal env into `env.her`.

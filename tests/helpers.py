@@ -279,3 +279,16 @@ def fold_onto_table(rng, n_envs):
     a[:, 1] = 1.0
     a[:, 2] = np.where(np.arange(n_envs) % 2 == 0, 0.6, -0.2)
     return a
+
+
+def _dev(x):
+    """`x` as a contiguous float32 tensor on the GPU (the learners' tests)"""
+    import torch
+    return torch.as_tensor(x).to(torch.float32).contiguous().cuda()
+
+
+def _err(dev, ref64, ref32):
+    """(the device's, the float32 reference's) largest deviation from the float64 reference, relative to its largest magnitude (the learners' tests)"""
+    dev, ref64, ref32 = (np.asarray(x, np.float64) for x in (dev, ref64, ref32))
+    scale = np.abs(ref64).max()
+    return np.abs(dev - ref64).max() / scale, np.abs(ref32 - ref64).max() / scale

@@ -254,5 +254,4 @@ def test_abi_names_the_five_entry_points_and_the_header_stays_in_the_base_transl
     assert base.rindex("#if HRG_BASE_TU", 0, at) > base.rindex("#endif", 0, at)   # inside the block that only the base translation unit compiles
     for src in _lib.SOURCES[1:]:
         assert "hrgym_dataset.h" not in open(src).read(), src
-    deps = open(_lib.__file__).read()
-    assert '"hrgym_dataset.h"' in deps
+    assert any(os.path.basename(d) == "hrgym_dataset.h" for d in _lib.library_dependencies())

@@ -36,6 +36,16 @@ def test_hip_library_loads_and_exports_every_declared_symbol():
     assert lib.hrg_state_bytes() == ctypes.sizeof(EnvState)
 
 
+def test_every_header_is_a_dependency_of_the_library():
+    """A header the build does not know leaves a stale library behind: the dependencies are the directories' own listing, translation units included."""
+    deps = set(_lib.library_dependencies())
+    pkg = os.path.dirname(_lib.SRC)
+    headers = [os.path.join(d, f) for d in (pkg, os.path.join(ROOT, "include")) for f in sorted(os.listdir(d)) if f.endswith(".h")]
+    assert len(headers) >= 14 and os.path.join(pkg, "hrgym_mlp.h") in headers
+    assert all(any(os.path.samefile(h, d) for d in deps) for h in headers), [h for h in headers if not any(os.path.samefile(h, d) for d in deps)]
+    assert set(_lib.SOURCES) <= deps and all(os.path.isfile(d) for d in deps)
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

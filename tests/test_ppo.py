@@ -77,8 +77,9 @@ def test_the_header_declares_the_entries_and_only_the_base_unit_includes_the_ker
     from human_robot_gym_amd._cstruct import CONST, PROTOTYPES
     assert {"hrg_ppo_create", "hrg_ppo_destroy", "hrg_ppo_sizes", "hrg_ppo_step", "hrg_ppo_forward", "hrg_ppo_export"} <= set(PROTOTYPES)
     assert (CONST["HRG_PPO_HIDDEN"], CONST["HRG_PPO_MAX_DEPTH"], CONST["HRG_PPO_TILE"], CONST["HRG_PPO_MAX_BATCH"], CONST["HRG_PPO_NDIAG"]) == (64, 3, 32, 4096, len(ppo.DIAG_KEYS))
-    including = [os.path.basename(s) for s in _lib.SOURCES if '#include "hrgym_ppo.h"' in open(s).read()]
-    assert including == ["hrgym_hip.hip"]
+    for header in ("hrgym_mlp.h", "hrgym_ppo.h"):
+        including = [os.path.basename(s) for s in _lib.SOURCES if f'#include "{header}"' in open(s).read()]
+        assert including == ["hrgym_hip.hip"], header
 
 
 # ---- layout and names

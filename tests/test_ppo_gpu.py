@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import ppo_ref as R
+from helpers import _dev, _err
 import human_robot_gym_amd as hrg
 from human_robot_gym_amd._lib import HrgError
 from human_robot_gym_amd.ppo import DIAG_KEYS, PpoLearner
@@ -35,10 +36,6 @@ SCALARS = ("policy_gradient_loss", "value_loss", "entropy_loss", "approx_kl")
 
 def _net_arch(depth, separate):
     return [dict(pi=[64] * depth, vf=[64] * depth)] if separate else [64] * depth
-
-
-def _dev(x):
-    return torch.as_tensor(x).to(torch.float32).contiguous().cuda()
 
 
 def _samples(batch):
@@ -62,12 +59,6 @@ def _flat(named, prefix):
     """The entries of `named` under `prefix` as one vector, in the layout's order; None when there is none."""
     parts = [np.asarray(v.detach().cpu(), np.float64).reshape(-1) for k, v in named.items() if k.startswith(prefix)]
     return np.concatenate(parts) if parts else None
-
-
-def _err(dev, ref64, ref32):
-    dev, ref64, ref32 = (np.asarray(x, np.float64) for x in (dev, ref64, ref32))
-    scale = np.abs(ref64).max()
-    return np.abs(dev - ref64).max() / scale, np.abs(ref32 - ref64).max() / scale
 
 
 @functools.lru_cache(maxsize=None)

@@ -212,7 +212,7 @@ def test_abi_names_and_the_header_stays_in_the_base_translation_unit():
     for src in _lib.SOURCES[1:]:
         assert "hrgym_replay.h" not in open(src).read(), src
     assert len(_lib.SOURCES) == 12
-    assert '"hrgym_replay.h"' in open(_lib.__file__).read()   # a dependency of the build
+    assert any(os.path.basename(d) == "hrgym_replay.h" for d in _lib.library_dependencies())   # a dependency of the build
     header = open(_lib.SRC.replace("hrgym_hip.hip", "hrgym_replay.h")).read()
     assert "STREAM_REPLAY = 11" in header and R.STREAM_REPLAY == 11
     assert "__shared__" not in header and "atomic" not in header.replace("no atomics", "")

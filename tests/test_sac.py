@@ -153,5 +153,6 @@ def test_the_header_declares_the_entries_and_only_the_base_unit_includes_the_ker
     from human_robot_gym_amd import _lib
     from human_robot_gym_amd._cstruct import PROTOTYPES
     assert {"hrg_sac_create", "hrg_sac_destroy", "hrg_sac_sizes", "hrg_sac_step", "hrg_sac_act", "hrg_sac_export"} <= set(PROTOTYPES)
-    including = [os.path.basename(s) for s in _lib.SOURCES if '#include "hrgym_sac.h"' in open(s).read()]
-    assert including == ["hrgym_hip.hip"]
+    for header in ("hrgym_mlp.h", "hrgym_sac.h"):
+        including = [os.path.basename(s) for s in _lib.SOURCES if f'#include "{header}"' in open(s).read()]
+        assert including == ["hrgym_hip.hip"], header

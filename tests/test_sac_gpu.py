@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import sac_ref as R
+from helpers import _dev, _err
 import human_robot_gym_amd as hrg
 from human_robot_gym_amd._lib import HrgError
 from human_robot_gym_amd.replay import ReplayBufferSamples
@@ -27,10 +28,6 @@ pytestmark = pytest.mark.gpu
 LR, GAMMA, TAU = 5e-4, 0.99, 0.005
 SHAPES = list(itertools.product((1, 6, 64), (1, 4, 7), (1, 3), (32, 160)))   # obs_dim, act_dim, depth, batch
 GROUPS = (("actor", "actor."), ("qf0", "critic.qf0."), ("qf1", "critic.qf1."), ("log_ent_coef", "log_ent_coef"))
-
-
-def _dev(x):
-    return torch.as_tensor(x).to(torch.float32).contiguous().cuda()
 
 
 def _samples(batch):
@@ -51,12 +48,6 @@ def _cfg(A, depth, auto=True, ent_coef=0.2, interval=1, lr=LR):
 def _flat(named, prefix, layout):
     """The entries of `named` under `prefix` as one vector, in the order of the device's parameter vector."""
     return np.concatenate([np.asarray(named[k].detach().cpu(), np.float64).reshape(-1) for k in layout if k.startswith(prefix)])
-
-
-def _err(dev, ref64, ref32):
-    dev, ref64, ref32 = (np.asarray(x, np.float64) for x in (dev, ref64, ref32))
-    scale = np.abs(ref64).max()
-    return np.abs(dev - ref64).max() / scale, np.abs(ref32 - ref64).max() / scale
 
 
 @functools.lru_cache(maxsize=None)
