@@ -1,6 +1,7 @@
 """What the device learners share (sac.SacLearner, ppo.PpoLearner; csrc/hrgym_mlp.h): the refusal of widths the tile kernels do not cover, the flat parameter
 layout, the tensors behind `state_dict()` with their seeded initialisation, and the learner's calls that differ by the entry points' prefix only."""
 import ctypes
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -86,6 +87,70 @@ class LearnerParams:
                 view.copy_(src.to(device=view.device, dtype=view.dtype))
 
 
+# ---- checkpoints: one .npz per learner -- the descriptor's fields, the tensors, the counters, the scheduled attributes; arrays only, read without pickle ----
+CHECKPOINT_FORMAT = 1
+TENSORS = ("params", "adam_m", "adam_v", "target")   # `target`: where the learner keeps one (SAC)
+
+
+def desc_fields(desc):
+    """The fields of a ctypes descriptor as numpy scalars and arrays, by name (reserved_ left out)."""
+    out = {}
+    for name, _ in desc._fields_:
+        if not name.endswith("_"):
+            v = getattr(desc, name)
+            out[name] = np.array(list(v)) if isinstance(v, ctypes.Array) else np.array(v)
+    return out
+
+
+def save_checkpoint(path, kind, desc, p, counters, hyper):
+    """Writes the checkpoint of a learner of `kind` (its entry points' prefix) to `path`: `desc` its descriptor, `p` its LearnerParams (on any device), `counters`
+    (steps, forward calls that drew their noise), `hyper` name -> number: the attributes a caller may schedule (None is stored as NaN)."""
+    arrays = {"format": np.array(CHECKPOINT_FORMAT, np.int64), "kind": np.array(str(kind)), "counters": np.array([int(c) for c in counters], np.uint64)}
+    arrays.update({"desc." + k: v for k, v in desc_fields(desc).items()})
+    arrays.update({"hyper." + k: np.array(np.nan if v is None else v, np.float64) for k, v in hyper.items()})
+    for name in TENSORS:
+        if hasattr(p, name):
+            arrays[name] = getattr(p, name).detach().cpu().numpy()
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+    return path
+
+
+def load_checkpoint(path, kind):
+    """The arrays of a checkpoint of a learner of `kind` as a dict, with `desc` and `hyper` as dicts of their own; ValueError for a file of another kind or
+    format.  No pickle is read."""
+    with np.load(path, allow_pickle=False) as f:
+        arrays = {k: f[k] for k in f.files}
+    for name in ("format", "kind", "counters", "params", "adam_m", "adam_v"):
+        if name not in arrays:
+            raise ValueError(f"{path}: no checkpoint of a device learner: {name} is missing")
+    if int(arrays["format"]) != CHECKPOINT_FORMAT:
+        raise ValueError(f"{path}: format = {int(arrays['format'])}, this build reads {CHECKPOINT_FORMAT}")
+    if str(arrays["kind"]) != kind:
+        raise ValueError(f"{path}: kind = {str(arrays['kind'])!r}: a checkpoint of another learner than {kind!r}")
+    out = {k: v for k, v in arrays.items() if "." not in k}
+    for group in ("desc", "hyper"):
+        out[group] = {k[len(group) + 1:]: v for k, v in arrays.items() if k.startswith(group + ".")}
+    return out
+
+
+def restore_tensors(p, ckpt):
+    """Copies the checkpoint's tensors into the LearnerParams `p`; ValueError, naming the field, where a shape differs."""
+    import torch
+    for name in TENSORS:
+        if not hasattr(p, name):
+            continue
+        own = getattr(p, name)
+        if name not in ckpt:
+            raise ValueError(f"checkpoint: {name} is missing")
+        src = np.asarray(ckpt[name])
+        if tuple(src.shape) != tuple(own.shape) or src.dtype != np.float32:
+            raise ValueError(f"checkpoint: {name} is {src.dtype} {tuple(src.shape)}, the learner's is float32 {tuple(own.shape)} (a checkpoint of other shapes)")
+        with torch.no_grad():
+            own.copy_(torch.from_numpy(src).to(own.device))
+
+
 class Learner(DeviceHandle):
     """What SacLearner and PpoLearner share on the handle.  A subclass names its entry points (`_prefix`: hrg_sac / hrg_ppo), sets `obs_dim`, `act_dim` and
     keeps its LearnerParams as `p`."""
@@ -123,6 +188,27 @@ class Learner(DeviceHandle):
     def _export(self, *arrays):
         """hrg_*_export into the host arrays (None: not asked for).  Synchronous."""
         self._check(self.lib, getattr(self.lib, self._prefix + "_export")(self.h, *(None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrays)))
+
+    def save(self, path):
+        """The learner as one .npz (`save_checkpoint`): the descriptor's fields, params, adam_m, adam_v, target (SAC), the counters and the scheduled attributes.
+        Synchronous.  `load` makes a learner that continues bit for bit: Adam's bias corrections, the draws' keys and the phase of the target update follow
+        from the counters."""
+        sizes = self._sizes()
+        return save_checkpoint(path, self._prefix, self.desc, self.p, (sizes[3], sizes[4]), self._hyper())
+
+    @classmethod
+    def load(cls, path, device=0):
+        """A fresh learner from a checkpoint `save` wrote.  ValueError, naming the field, for a file of another learner or of other shapes."""
+        ckpt = load_checkpoint(path, cls._prefix)
+        learner = cls._from_checkpoint(ckpt["desc"], ckpt["hyper"], device)
+        try:
+            restore_tensors(learner.p, ckpt)
+            steps, calls = (int(c) for c in ckpt["counters"])
+            learner._check(learner.lib, getattr(learner.lib, cls._prefix + "_restore")(learner.h, steps, calls))
+        except Exception:
+            learner.close()
+            raise
+        return learner
 
     def state_dict(self):
         """Views of the parameters under SB3's names, torch's [out, in] weight layout (the names: `p`'s class)."""

@@ -3087,6 +3087,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_mlp.h"      // what the two learners below share: the tile products of a 64-wide MLP, forward and backward, and Adam's update of a parameter
 #include "hrgym_sac.h"      // the SAC gradient step and the actor's forward pass: policy / critic / actor / Adam kernels (hrg_sac_*)
 #include "hrgym_ppo.h"      // the PPO minibatch step and the policy's forward pass: advantage / gradient / reduce / Adam kernels (hrg_ppo_*)
+#include "hrgym_eval.h"     // evaluation of deterministic policies: begin / step (the episode ledger) / remaining / fused actor kernels (hrg_eval_*)
 
 // ================================================================================================ host side
 static thread_local std::string g_err;
@@ -3273,6 +3274,34 @@ static int buffer_columns(const char* name, int32_t n_obs_cols, const int32_t* o
   if (!mem.zeros(dev, HRG_OBS_DIM)) return nomem(name, mem);
   if (hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess) return fail(HRG_ERR_HIP, pre + "upload failed");
   table = dev;
+  return HRG_OK;
+}
+
+// What the replay buffer and the evaluator check of DatasetObsNormWrapper's statistics: mean / sd become the tables the view reads (mean 0 and std 1 behind the K
+// values, and everywhere without normalize).  `name`: the message prefix.
+static int view_statistics(const char* name, int K, int32_t normalize, int32_t squash, double squash_factor, const double* mean_in, const double* std_in, double* mean,
+                           double* sd) {
+  const std::string pre = std::string(name) + ": ";
+  if (squash && !normalize) return fail(HRG_ERR_INVALID, pre + "squash needs normalize");
+  for (int k = 0; k < HRG_OBS_DIM; k++) {
+    mean[k] = normalize && k < K ? mean_in[k] : 0.0;
+    sd[k] = normalize && k < K ? std_in[k] : 1.0;
+    if (!std::isfinite(mean[k]) || !std::isfinite(sd[k]) || sd[k] == 0.0) return fail(HRG_ERR_INVALID, pre + "mean must be finite, std finite and non-zero");
+  }
+  if (normalize && squash && !std::isfinite(squash_factor)) return fail(HRG_ERR_INVALID, pre + "squash_factor must be finite");
+  return HRG_OK;
+}
+
+// ... and the two tables on the current device, behind the view's pointers (synchronous)
+static int view_statistics_upload(const char* name, DeviceMem& mem, BufferView& v, const double* mean, const double* sd) {
+  double *mean_dev = nullptr, *std_dev = nullptr;
+  if (!(mem.zeros(mean_dev, HRG_OBS_DIM) && mem.zeros(std_dev, HRG_OBS_DIM))) return nomem(name, mem);
+  const size_t bytes = sizeof(double) * HRG_OBS_DIM;
+  if (hipMemcpy(mean_dev, mean, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(std_dev, sd, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess)
+    return fail(HRG_ERR_HIP, std::string(name) + ": upload failed");
+  v.mean = mean_dev;
+  v.std = std_dev;
   return HRG_OK;
 }
 
@@ -4192,26 +4221,15 @@ int hrg_replay_create(const hrg_replay_desc* desc, int32_t device, hrg_replay** 
   const int K = desc->n_obs_cols + v.observe_time;
   const int rc = buffer_columns("replay", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols);
   if (rc != HRG_OK) return rc;
-  if (desc->squash && !desc->normalize) return fail(HRG_ERR_INVALID, "replay: squash needs normalize");
   double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
-  for (int k = 0; k < HRG_OBS_DIM; k++) {
-    mean[k] = desc->normalize && k < K ? desc->mean[k] : 0.0;
-    sd[k] = desc->normalize && k < K ? desc->std[k] : 1.0;
-    if (!std::isfinite(mean[k]) || !std::isfinite(sd[k]) || sd[k] == 0.0) return fail(HRG_ERR_INVALID, "replay: mean must be finite, std finite and non-zero");
-  }
-  if (desc->normalize && desc->squash && !std::isfinite(desc->squash_factor)) return fail(HRG_ERR_INVALID, "replay: squash_factor must be finite");
+  if (int rs = view_statistics("replay", K, desc->normalize, desc->squash, desc->squash_factor, desc->mean, desc->std, mean, sd)) return rs;
   d.n_envs = desc->n_envs; d.capacity = desc->capacity; d.act_dim = desc->act_dim; d.seed = desc->seed;
   v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
-  double *mean_dev = nullptr, *std_dev = nullptr;
   if (!(m.zeros(d.obs, slots * (size_t)K) && m.zeros(d.nobs, slots * (size_t)K) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
         m.zeros(d.done, slots) && m.zeros(d.timeout, slots) && m.zeros(d.cur_time, n) && m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) &&
-        m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_REPLAY_STATS_DIM) && m.zeros(mean_dev, HRG_OBS_DIM) && m.zeros(std_dev, HRG_OBS_DIM)))
+        m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_REPLAY_STATS_DIM)))
     return nomem("replay", m);
-  if (hipMemcpy(mean_dev, mean, sizeof mean, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(std_dev, sd, sizeof sd, hipMemcpyHostToDevice) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess)
-    return fail(HRG_ERR_HIP, "replay: upload failed");
-  v.mean = mean_dev;
-  v.std = std_dev;
+  if (int ru = view_statistics_upload("replay", m, v, mean, sd)) return ru;
   *out = h.release();
   return HRG_OK;
 }
@@ -4563,6 +4581,175 @@ int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* 
   const size_t B = (size_t)d.B;
   return export_floats(h->device, {{values_host, d.values, B}, {log_prob_host, d.logp, B}, {ratio_host, d.ratio, B}, {grad_host, d.grad, (size_t)d.n_params},
                                    {diag_host, d.diag, HRG_PPO_NDIAG}});
+}
+
+int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->steps = steps;
+  h->act_calls = act_calls;
+  return HRG_OK;
+}
+
+int hrg_ppo_restore(hrg_ppo* h, uint64_t steps, uint64_t forward_calls) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->steps = steps;
+  h->forward_calls = forward_calls;
+  return HRG_OK;
+}
+
+// ---- evaluation (csrc/hrgym_eval.h) ----
+struct hrg_eval {
+  int device = 0;
+  hrg_eval_desc desc;
+  EvalDev d;
+  int64_t steps = 0;   // steps since begin: the finishing step index of the records
+  DeviceMem mem;       // behind every pointer of `d`
+};
+
+int hrg_eval_create(const hrg_eval_desc* desc, int32_t device, hrg_eval** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->n_envs < 1 || desc->n_policies < 1) return fail(HRG_ERR_INVALID, "eval: n_envs and n_policies must be positive");
+  if (desc->n_envs % desc->n_policies)
+    return fail(HRG_ERR_INVALID, "eval: n_envs = " + std::to_string(desc->n_envs) + " is not divisible by n_policies = " + std::to_string(desc->n_policies) +
+                                     ": every parameter set steps a group of the same size");
+  if (desc->n_eval_episodes < 1) return fail(HRG_ERR_INVALID, "eval: n_eval_episodes must be positive");
+  const int32_t group = desc->n_envs / desc->n_policies;
+  const int64_t max_quota = ((int64_t)desc->n_eval_episodes + group - 1) / group;
+  if (max_quota > HRG_EVAL_MAX_EPISODES_PER_ENV)
+    return fail(HRG_ERR_INVALID, "eval: " + std::to_string(desc->n_eval_episodes) + " episodes over groups of " + std::to_string(group) + " envs are " +
+                                     std::to_string(max_quota) + " per env, above HRG_EVAL_MAX_EPISODES_PER_ENV = " + std::to_string(HRG_EVAL_MAX_EPISODES_PER_ENV));
+  const int time_col = desc->observe_time ? 1 : 0;
+  int width = desc->n_obs_cols + time_col;
+  if (desc->goal_env) {
+    if (desc->observe_time || desc->normalize) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_env with observe_time or normalize: a goal env's feature row is a plain selection");
+    if (desc->goal_kind != HRG_GOAL_REACH && desc->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_kind = " + std::to_string(desc->goal_kind));
+    width = (desc->goal_kind == HRG_GOAL_REACH ? 6 + 6 : 7 + 3) + desc->n_obs_cols;
+    if (width > HRG_OBS_DIM)
+      return fail(HRG_ERR_UNSUPPORTED, "eval: a feature row of " + std::to_string(width) + " values; the kernels handle one value per lane, at most HRG_OBS_DIM");
+  }
+  for (int j = 0; j < HRG_ACT_DIM; j++)
+    if (j < desc->act_dim && (!std::isfinite(desc->act_low[j]) || !std::isfinite(desc->act_high[j]) || desc->act_low[j] > desc->act_high[j]))
+      return fail(HRG_ERR_INVALID, "eval: act_low and act_high must be finite and ordered");
+  double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
+  if (int rs = view_statistics("eval", desc->n_obs_cols + time_col, desc->normalize, desc->squash, desc->squash_factor, desc->mean, desc->std, mean, sd)) return rs;
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_eval> h(new hrg_eval());
+  h->device = device;
+  h->desc = *desc;
+  EvalDev& d = h->d;
+  BufferView& v = d.view;
+  DeviceMem& m = h->mem;
+  v.observe_time = time_col;
+  if (int rc = buffer_columns("eval", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols)) return rc;
+  v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
+  d.n_envs = desc->n_envs; d.n_policies = desc->n_policies; d.group = group; d.n_episodes = desc->n_eval_episodes; d.max_quota = (int32_t)max_quota;
+  d.act_dim = desc->act_dim; d.goal_env = desc->goal_env ? 1 : 0; d.goal_kind = desc->goal_kind; d.width = width;
+  const size_t n = (size_t)desc->n_envs;
+  double *low_dev = nullptr, *high_dev = nullptr;
+  if (!(m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) && m.zeros(d.cur_time, n) && m.zeros(d.count, n) &&
+        m.zeros(d.quota, n) && m.zeros(d.records, n * (size_t)max_quota * HRG_EVAL_RECORD_DIM) && m.zeros(d.remaining, 1) && m.zeros(low_dev, HRG_ACT_DIM) &&
+        m.zeros(high_dev, HRG_ACT_DIM)))
+    return nomem("eval", m);
+  if (hipMemcpy(low_dev, desc->act_low, sizeof desc->act_low, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(high_dev, desc->act_high, sizeof desc->act_high, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(HRG_ERR_HIP, "eval: upload failed");
+  d.act_low = low_dev;
+  d.act_high = high_dev;
+  if (int ru = view_statistics_upload("eval", m, v, mean, sd)) return ru;
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_eval_destroy(hrg_eval* h) { destroy_handle(h); }
+
+int hrg_eval_begin(hrg_eval* h, const float* obs_dev, const float* time_dev, float* view_dev, void* stream) {
+  if (!h || !obs_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the rows' time values");
+  HIPCHK(hipSetDevice(h->device));
+  h->steps = 0;
+  return launch_per_env(hrg_eval_begin_kernel, h->desc.n_envs, stream, h->d, obs_dev, time_dev, view_dev);
+}
+
+int hrg_eval_step(hrg_eval* h, const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, const float* imit_dev,
+                  const float* sir_dev, float* view_dev, void* stream) {
+  if (!h || !obs_dev || !reward_dev || !done_dev || !info_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "eval: an imitation row or a state imitation row, not both");
+  if (h->d.view.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the state imitation rows (their time columns)");
+  HIPCHK(hipSetDevice(h->device));
+  const int rc = launch_per_env(hrg_eval_step_kernel, h->desc.n_envs, stream, h->d, h->steps, obs_dev, reward_dev, done_dev, info_dev, imit_dev, sir_dev, view_dev);
+  if (rc != HRG_OK) return rc;
+  h->steps++;
+  return HRG_OK;
+}
+
+// what both policy entries end with: the widths of the learner against the evaluator's, then the launch
+static int eval_policy(hrg_eval* h, bool sac, const EvalActor& a, int learner_device, const char* name, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!params_dev || !view_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (learner_device != h->device)
+    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner lives on device " + std::to_string(learner_device) + ", the evaluator on device " +
+                                     std::to_string(h->device));
+  if (a.K != h->d.width || a.A != h->d.act_dim)
+    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner takes observations of " + std::to_string(a.K) + " and emits actions of " + std::to_string(a.A) +
+                                     " values, the evaluator's view has " + std::to_string(h->d.width) + " and its actions " + std::to_string(h->d.act_dim));
+  HIPCHK(hipSetDevice(h->device));
+  const dim3 grid(((unsigned)h->d.group + MLP_T - 1) / MLP_T, (unsigned)h->d.n_policies), block(MLP_BLOCK);
+  if (sac) hipLaunchKernelGGL(hrg_eval_policy_kernel<true>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
+  else hipLaunchKernelGGL(hrg_eval_policy_kernel<false>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_eval_policy_sac(hrg_eval* h, hrg_sac* sac, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!h || !sac) return fail(HRG_ERR_INVALID, "null argument");
+  const SacDev& s = sac->d;
+  EvalActor a;
+  for (int l = 0; l < HRG_SAC_MAX_DEPTH; l++) { a.w[l] = s.a_w[l]; a.b[l] = s.a_b[l]; }
+  a.hw = s.a_hw; a.hb = s.a_hb; a.nout = 2 * s.A;   // (sac_squash reads both heads)
+  a.depth = s.depth; a.K = s.K; a.A = s.A; a.n_params = s.n_params;
+  return eval_policy(h, true, a, sac->device, "sac", params_dev, view_dev, actions_dev, stream);
+}
+
+int hrg_eval_policy_ppo(hrg_eval* h, hrg_ppo* ppo, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!h || !ppo) return fail(HRG_ERR_INVALID, "null argument");
+  const PpoDev& p = ppo->d;
+  EvalActor a;
+  for (int l = 0; l < HRG_PPO_MAX_DEPTH; l++) { a.w[l] = p.w[0][l]; a.b[l] = p.b[0][l]; }   // network 0: the shared trunk, or the policy's
+  a.hw = p.hw; a.hb = p.hb; a.nout = p.A;   // the first A rows of the [A + 1][64] heads: action_net
+  a.depth = p.depth; a.K = p.K; a.A = p.A; a.n_params = p.n_params;
+  return eval_policy(h, false, a, ppo->device, "ppo", params_dev, view_dev, actions_dev, stream);
+}
+
+int hrg_eval_remaining(hrg_eval* h, int64_t* remaining_host, void* stream) {
+  if (!h || !remaining_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(hrg_eval_remaining_kernel, dim3(1), dim3(MLP_BLOCK), 0, st, h->d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(remaining_host, h->d.remaining, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return HRG_OK;
+}
+
+int hrg_eval_export(hrg_eval* h, int32_t* counts_host, int32_t* quota_host, double* records_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const EvalDev& d = h->d;
+  const size_t n = (size_t)d.n_envs;
+  if (counts_host) HIPCHK(hipMemcpy(counts_host, d.count, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (quota_host) HIPCHK(hipMemcpy(quota_host, d.quota, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (records_host) HIPCHK(hipMemcpy(records_host, d.records, n * (size_t)d.max_quota * HRG_EVAL_RECORD_DIM * sizeof(double), hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+int hrg_eval_size(hrg_eval* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.max_quota;
+  size_host[1] = h->steps;
+  size_host[2] = h->d.width;
+  size_host[3] = (int64_t)h->mem.bytes;
+  return HRG_OK;
 }
 
 int hrg_batch_launch_order(hrg_batch* b, int32_t* order_host, int32_t* n_busy_host) {

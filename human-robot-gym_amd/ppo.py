@@ -156,6 +156,20 @@ class PpoLearner(Learner):
             raise RuntimeError(f"PpoLearner: the library lays out {self._sizes()[0]} parameters, ppo.param_layout {self.p.n_params}: rebuild")
         self._keep = None
 
+    def _hyper(self):
+        return dict(learning_rate=self.learning_rate, clip_range=self.clip_range, clip_range_vf=self.clip_range_vf, n_epochs=self.n_epochs)
+
+    @classmethod
+    def _from_checkpoint(cls, d, hyper, device):
+        """The learner of a checkpoint's descriptor fields `d` and scheduled attributes `hyper` (Learner.load).  log_std_init and ortho_init shape the initial
+        parameters only, which the checkpoint's replace."""
+        layers = [int(d["hidden"])] * int(d["depth"])
+        vf = float(hyper["clip_range_vf"])
+        return cls(int(d["obs_dim"]), int(d["act_dim"]), net_arch=[dict(pi=layers, vf=list(layers))] if int(d["separate"]) else layers,
+                   learning_rate=float(hyper["learning_rate"]), batch_size=int(d["batch_size"]), n_epochs=int(hyper["n_epochs"]), clip_range=float(hyper["clip_range"]),
+                   clip_range_vf=None if math.isnan(vf) else vf, normalize_advantage=bool(int(d["normalize_advantage"])), ent_coef=float(d["ent_coef"]),
+                   vf_coef=float(d["vf_coef"]), max_grad_norm=float(d["max_grad_norm"]), rollout_size=int(d["rollout_size"]), seed=int(d["seed"]), device=device)
+
     def step(self, batch):
         """One minibatch step on `batch`, a RolloutBufferSamples of `batch_size` rows (observations [B, obs_dim], actions [B, act_dim], old_values,
         old_log_prob, advantages, returns [B])."""

@@ -162,6 +162,18 @@ class SacLearner(Learner):
             raise RuntimeError(f"SacLearner: the library lays out {sizes[:3]} parameters, sac.param_layout {[self.p.n_params, self.p.n_actor, self.p.n_critic]}: rebuild")
         self._keep = None
 
+    def _hyper(self):
+        return dict(learning_rate=self.learning_rate)
+
+    @classmethod
+    def _from_checkpoint(cls, d, hyper, device):
+        """The learner of a checkpoint's descriptor fields `d` and scheduled attributes `hyper` (Learner.load)."""
+        ent_coef = float(d["ent_coef"])
+        return cls(int(d["obs_dim"]), int(d["act_dim"]), net_arch=[int(d["hidden"])] * int(d["depth"]), learning_rate=float(hyper["learning_rate"]),
+                   gamma=float(d["gamma"]), tau=float(d["tau"]), ent_coef=f"auto_{ent_coef!r}" if int(d["auto_ent_coef"]) else ent_coef,
+                   target_entropy=float(d["target_entropy"]), batch_size=int(d["batch_size"]), target_update_interval=int(d["target_update_interval"]),
+                   seed=int(d["seed"]), device=device)
+
     def step(self, batch, eps_pi=None, eps_next=None):
         """One gradient step on `batch`, a ReplayBufferSamples of `batch_size` rows (observations, next_observations [B, obs_dim], actions [B, act_dim], dones,
         rewards [B, 1]).  `eps_pi` / `eps_next` float32 [B, act_dim]: the standard normal noise of the actor on the observations / the next observations, instead

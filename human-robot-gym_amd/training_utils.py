@@ -283,6 +283,89 @@ def ppo_kwargs_from_config(config) -> Dict[str, Any]:
     return kw
 
 
+CHECKPOINT_EXT = ".npz"   # a device learner's checkpoint (Learner.save), where the reference writes SB3's .zip
+
+
+def checkpoint_path(run_id, load_step, models_dir="models") -> str:
+    """`models/<run_id>/model_<step>` of the reference (utils/training_utils_SB3.py:240-243; callbacks/custom_wandb_callback.py writes the same names): an
+    integer step with `_` between the thousands (model_1_000_000), anything else as it is (model_final); the extension is a device checkpoint's."""
+    if isinstance(load_step, bool) or (isinstance(load_step, int) and load_step < 0):
+        raise ValueError("load_step must be a non-negative integer or 'final'")   # (the reference's check, load_step < 0, under its own wording "positive")
+    if not isinstance(load_step, int) and str(load_step) == "all":
+        raise ValueError("load_step 'all' names every checkpoint of the run: list_checkpoints(run_id)")
+    name = f"model_{load_step:_}" if isinstance(load_step, int) else f"model_{load_step}"
+    return os.path.join(models_dir, str(run_id), name + CHECKPOINT_EXT)
+
+
+def list_checkpoints(run_id, models_dir="models"):
+    """`load_step: all` (config_icra_2024/environment_evaluation/evaluation/*.yaml): [(step, path)] of every checkpoint of the run, by ascending step;
+    model_final, where it exists, comes last under the step "final"."""
+    folder = os.path.join(models_dir, str(run_id))
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"{folder}: no such run")
+    steps, final = [], []
+    for f in os.listdir(folder):
+        stem, ext = os.path.splitext(f)
+        if ext != CHECKPOINT_EXT or not stem.startswith("model_"):
+            continue
+        tag = stem[len("model_"):]
+        if tag == "final":
+            final.append(("final", os.path.join(folder, f)))
+        elif tag.replace("_", "").isdigit():
+            steps.append((int(tag.replace("_", "")), os.path.join(folder, f)))
+    return sorted(steps) + final
+
+
+def eval_kwargs_from_config(config) -> Dict[str, Any]:
+    """`config.run` of an evaluation (utils/training_utils_SB3.py:492-544) -> dict(n_eval_episodes = run.n_test_episodes, log_info_keys = run.log_info_keys,
+    eval_seed = run.eval_seed): the first is HipVecEnv.evaluate's argument, the second EvalResult.summary's, the third is what
+    create_training_vec_env(config, evaluation_mode=True) seeds the env with (None: the training seed)."""
+    run = _get(config, "run")
+    n = _get(run, "n_test_episodes")
+    if n is None or int(n) < 1:
+        raise ValueError(f"run.n_test_episodes = {n}: a positive number of evaluation episodes")
+    seed = _get(run, "eval_seed")
+    return dict(n_eval_episodes=int(n), log_info_keys=[str(k) for k in (_plain(_get(run, "log_info_keys")) or [])], eval_seed=None if seed is None else int(seed))
+
+
+class RunFolder:
+    """What a training loop of the tools does to `models/<run_id>` (utils/training_utils_SB3.py:399-461, callbacks/custom_wandb_callback.py): a checkpoint
+    whenever the env steps pass another multiple of `save_freq`, `model_final` at the end, and -- with `eval_env` and `eval_episodes` -- an evaluation of
+    the learner after every block, whose figures `after` returns for the block's log line.  With neither `model_dir` nor `eval_episodes` every call is a no-op."""
+
+    def __init__(self, model_dir=None, save_freq=None, eval_env=None, eval_episodes=0):
+        self.model_dir, self.save_freq, self.eval_env, self.eval_episodes = model_dir, int(save_freq or 0), eval_env, int(eval_episodes or 0)
+        self._saved_until = 0
+
+    def path(self, step):
+        folder = os.path.abspath(self.model_dir)
+        return checkpoint_path(os.path.basename(folder), step, models_dir=os.path.dirname(folder))
+
+    def after(self, learner, env_steps) -> Dict[str, Any]:
+        out: Dict[str, Any] = {}
+        if self.model_dir is not None and self.save_freq > 0 and env_steps // self.save_freq > self._saved_until:
+            self._saved_until = env_steps // self.save_freq
+            out["checkpoint"] = learner.save(self.path(int(env_steps)))
+        if self.eval_env is not None and self.eval_episodes > 0:
+            res = self.eval_env.evaluate(learner, self.eval_episodes)
+            out.update(eval_mean_reward=res.mean_reward, eval_std_reward=res.std_reward, eval_mean_ep_length=res.mean_ep_length)
+        return out
+
+    def finish(self, learner):
+        return None if self.model_dir is None else learner.save(self.path("final"))
+
+
+def run_folder_from_args(args, **env_kw) -> RunFolder:
+    """The RunFolder of a training tool's --model-dir / --save-freq / --eval-episodes / --eval-n-envs / --eval-seed, with a second env of the tool's task for
+    the evaluations (its own seed: the reference's eval_seed; `env_kw`: further HipVecEnv keywords).  Without the flags nothing is built."""
+    eval_env = None
+    if args.eval_episodes > 0:
+        from .vec_env import HipVecEnv
+        seed = args.seed + 1 if args.eval_seed is None else args.eval_seed
+        eval_env = HipVecEnv(args.eval_n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=seed), **env_kw)
+    return RunFolder(args.model_dir, args.save_freq, eval_env, args.eval_episodes)
+
+
 def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class=None):
     """Drop-in for `human_robot_gym.utils.training_utils_SB3.create_training_vec_env` (45-77).  `wrapper_class`, when given (the reference always
     builds one from the same config), is accepted and not called: what it would have wrapped is read from `config.wrappers` here."""

@@ -324,19 +324,28 @@ class _TorchBackend:
         """The rows on the device (a reset's or the last step's) become the replay buffer's current rows."""
         time = None
         if self.replay.observe_time:
-            time = (self.batch.sir[:, CONST["HRG_SIR_TIME_OBS"]].contiguous() if self._stepped else
-                    self.torch.from_numpy(np.ascontiguousarray(self.reset_time, np.float32)).to(self.batch.device))
+            time = self.batch.sir[:, CONST["HRG_SIR_TIME_OBS"]].contiguous() if self._stepped else self.reset_time_device()
         self.replay.observe(self.batch.obs, time=time)
+
+    def reset_time_device(self):
+        """The time values of the rows the last dataset reset left (the state imitation reward's time column): float32 [n] on the device."""
+        return self.torch.from_numpy(np.ascontiguousarray(self.reset_time, np.float32)).to(self.batch.device)
 
     def replay_add(self, actions):
         """The last step's transition into the replay buffer; `actions`: float32 [n, act_dim] at the policy's scale.  The imitation rows go along where a
         reward of that kind is attached: the episode return is the env's own reward, the time columns are the state imitation reward's."""
-        b, rows = self.batch, {}
+        b = self.batch
+        self.replay.add_step(actions, b.obs, b.term_obs, b.reward, b.done, b.info, **self.imitation_rows())
+
+    def imitation_rows(self):
+        """The last step's imitation rows as the replay buffer and the evaluator take them: dict(sir=...) with a state imitation reward, dict(imit=...) with an
+        action imitation reward, else nothing."""
+        b = self.batch
         if self.sir is not None and b.dataset_desc.sir_kind != CONST["HRG_SIR_NONE"]:
-            rows = dict(sir=b.sir)
-        elif self.imit is not None:
-            rows = dict(imit=b.imit)
-        self.replay.add_step(actions, b.obs, b.term_obs, b.reward, b.done, b.info, **rows)
+            return dict(sir=b.sir)
+        if self.imit is not None:
+            return dict(imit=b.imit)
+        return {}
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
@@ -550,6 +559,7 @@ class HipVecEnv(_VecEnvBase):
         self._replay_args = None     # arguments of attach_replay, likewise
         self.sac = None              # the SAC learner (sac.SacLearner), once attached
         self.ppo = None              # the PPO learner (ppo.PpoLearner), once attached
+        self._buffers_behind = False   # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
 
     def _init_obs_norm(self, obs_norm=None):
@@ -597,6 +607,7 @@ class HipVecEnv(_VecEnvBase):
         self._ep_ret[:] = 0
         self._ep_len[:] = 0
         self._device_loop = False
+        self._buffers_behind = False   # (the reset below hands the rows to the attached buffers)
         full = np.asarray(self._backend.reset())
         self._last_full = full
         if self.expert_obs_keys is not None:
@@ -917,9 +928,7 @@ class HipVecEnv(_VecEnvBase):
         self._backend.attach_her(self._her_desc(self.num_envs, **args), keep_agent_actions=self._ik is not None, info_keys=self._info_keys)
         self._her_args = args
         if self._device_loop:   # attached between two runs of the device loop: the new buffer has no current rows, so the envs start again
-            self._backend.reset_device()
-            if self._backend.rollout is not None:
-                self._backend.rollout.observe(self._backend.batch.obs)
+            self._restart_device_loop()
         elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
             self._backend.her.observe(self._backend.batch.obs)
         return self._backend.her
@@ -1015,18 +1024,25 @@ class HipVecEnv(_VecEnvBase):
         setattr(self, slot, learner)
         return learner
 
-    def _enter_device_loop(self, name, account):
-        """What collect_rollout and collect_steps share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs -- to a dataset
-        state where a dataset is attached -- and hands the rows to the attached buffers; from then on step_async raises until reset()."""
+    def _enter_device_loop(self, name, account, fresh=False):
+        """What collect_rollout, collect_steps and evaluate share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs -- to a
+        dataset state where a dataset is attached -- and hands the rows to the attached buffers; from then on step_async raises until reset().  `fresh`: reset
+        whatever ran before (evaluate).  A loop that follows an evaluation resets too: the evaluation stepped the envs past the attached buffers, whose current
+        rows, running returns and lengths are its reset's."""
         if self._monitor is not None:
             raise NotImplementedError(f"{name} with monitor_dir: the Monitor csv is written by the host path; {account} is the device path's account of episodes")
-        if not self._device_loop:
-            be = self._backend
-            be.reset_device()
-            if be.rollout is not None:
-                be.rollout.observe(be.batch.obs)
+        if fresh or not self._device_loop or self._buffers_behind:
+            self._restart_device_loop()
             self._last_full = None   # (the host's copy of the rows is stale from here on)
         self._device_loop = name
+
+    def _restart_device_loop(self):
+        """The reset a device loop starts from: the envs, and the rows handed to every attached buffer."""
+        be = self._backend
+        be.reset_device()
+        if be.rollout is not None:
+            be.rollout.observe(be.batch.obs)
+        self._buffers_behind = False
 
     # ---- the off-policy device path on flat observations: SB3's ReplayBuffer next to the stepper (replay.py, csrc/hrgym_replay.h) ----
     def _replay_refusal(self):
@@ -1060,9 +1076,7 @@ class HipVecEnv(_VecEnvBase):
         self._backend.attach_replay(self._replay_desc(self.num_envs, **args), self.action_space.low, self.action_space.high, info_keys=self._info_keys)
         self._replay_args = args
         if self._device_loop:   # attached between two runs of a device loop: the new buffer has no current rows, so the envs start again
-            self._backend.reset_device()
-            if self._backend.rollout is not None:
-                self._backend.rollout.observe(self._backend.batch.obs)
+            self._restart_device_loop()
         elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
             self._backend.replay_observe()
         return self._backend.replay
@@ -1142,6 +1156,69 @@ class HipVecEnv(_VecEnvBase):
             be.launch_step(rows)
             hb.add_step(sent, b.obs, b.term_obs, b.reward, b.done, b.info)
         return hb
+
+    # ---- evaluation on the device: SB3's evaluate_policy next to the stepper (evaluation.py, csrc/hrgym_eval.h) ----
+    def _eval_desc(self, n_envs, n_policies, n_eval_episodes):
+        """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature
+        row), the action bounds."""
+        from .evaluation import build_eval_desc
+        mean, std, squash = self._norm if self._norm is not None else (None, None, None)
+        return build_eval_desc(n_envs, n_policies, n_eval_episodes, [int(c) for c in self._cols], self.action_space.low, self.action_space.high,
+                               observe_time=self._observe_time, mean=mean, std=std, squash_factor=squash,
+                               goal_kind=None if not self.goal_env else "reach" if self.env_id == "ReachHuman" else "cube")
+
+    def evaluate(self, learner_or_params, n_eval_episodes=10, sync_every=16, learner=None, deterministic=True, render=False):
+        """SB3's evaluate_policy(deterministic=True) on the device: `n_eval_episodes` episodes of the deterministic policy, three launches per env step (the
+        step, the episode ledger, the fused actor) and no torch op or host copy between them.  `learner_or_params`: a sac.SacLearner / ppo.PpoLearner, or a
+        stacked float32 [P, n_params] tensor of parameter sets together with `learner`, whose shapes they follow: the batch is then P groups of num_envs / P
+        consecutive envs, group k stepped by row k, `n_eval_episodes` each.  Needs no attached buffer: the view is the env's own (obs_keys, obs_norm, the time
+        column of a state imitation reward, the feature row of a goal env).  The envs are reset first; afterwards step_async raises until reset().  Attached
+        buffers see none of the evaluation's steps (an open episode of theirs is dropped by the reset), and the next collect_steps / collect_rollout resets the
+        envs again, so that its transitions start from rows the buffers hold.  At most
+        max quota x horizon + `sync_every` steps (TimeLimit ends every episode); every `sync_every` steps one integer is read back.  Returns an
+        evaluation.EvalResult; the returns are the env's own reward, also under an imitation reward."""
+        if not deterministic:
+            raise NotImplementedError("evaluate(deterministic=False): the device loop runs the deterministic actor (the reference evaluates with deterministic=True)")
+        if render:
+            raise NotImplementedError("evaluate(render=True): the batched envs have no renderer")
+        if not isinstance(self._backend, _TorchBackend):
+            raise NotImplementedError("evaluate: the ledger and actor kernels run in the HIP library; another backend (the mixed batch included) has none")
+        params = None
+        if not hasattr(learner_or_params, "p"):
+            params = learner_or_params
+            if learner is None:
+                raise ValueError("evaluate: a stacked parameter tensor comes with learner=..., whose shapes it follows")
+            if params.dim() != 2 or int(params.shape[1]) != learner.p.n_params:
+                raise ValueError(f"evaluate: expected parameters [P, {learner.p.n_params}], got {tuple(params.shape)}")
+        else:
+            learner = learner_or_params
+        if getattr(learner, "_prefix", None) not in ("hrg_sac", "hrg_ppo"):
+            raise NotImplementedError(f"evaluate: {type(learner).__name__}: the fused actor covers sac.SacLearner and ppo.PpoLearner (an SB3 model is stepped on the host)")
+        sync_every = int(sync_every)
+        if sync_every < 1:
+            raise ValueError(f"evaluate: sync_every = {sync_every} must be positive")
+        from .evaluation import Evaluator
+        desc = self._eval_desc(self.num_envs, 1 if params is None else int(params.shape[0]), n_eval_episodes)
+        self._enter_device_loop("evaluate", "the EvalResult it returns", fresh=True)   # evaluate_policy starts from env.reset()
+        self._buffers_behind = True
+        be = self._backend
+        b = be.batch
+        ev = Evaluator(desc, device=b.device.index, info_keys=self._info_keys)
+        try:
+            ev.begin(b.obs, be.reset_time_device() if self._observe_time else None)
+            bound, missing = ev.max_quota * self.horizon + sync_every, -1
+            for step in range(1, bound + 1):
+                be.launch_step(ev.policy(learner, params))
+                ev.step(b.obs, b.reward, b.done, b.info, **be.imitation_rows())
+                if step % sync_every == 0 or step == bound:
+                    missing = ev.remaining()
+                    if missing == 0:
+                        break
+            if missing:
+                raise RuntimeError(f"evaluate: {missing} episodes missing after {bound} steps (horizon {self.horizon}): an episode outlived the time limit")
+            return ev.result()
+        finally:
+            ev.close()
 
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
         if method_name == "check_collision_action":   # per-env call of the reference: env_method("check_collision_action", action, indices=[i])

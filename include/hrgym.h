@@ -560,6 +560,36 @@ typedef struct hrg_ppo_desc {
   uint64_t seed;                  /* key of the noise draws */
 } hrg_ppo_desc;
 
+/* ------------------------------------------------------------------------- evaluation of deterministic policies on the device (POD) */
+#define HRG_EVAL_MAX_EPISODES_PER_ENV 4096 /* the largest quota of an env: ceil(n_eval_episodes / (n_envs / n_policies)) may not exceed it */
+#define HRG_EVAL_RECORD_DIM (5 + HRG_INFO_DIM) /* doubles per record of hrg_eval_export */
+/* columns of a record: Monitor's return (the env's own reward), the length, the index of the finishing step since hrg_eval_begin, TimeLimit.truncated, the info
+ * columns of the last step (HRG_EVAL_REC_INFO + HRG_INFO_*), the episode's sum of imitation rewards (0 without an imitation row) */
+enum { HRG_EVAL_REC_RETURN = 0, HRG_EVAL_REC_LENGTH = 1, HRG_EVAL_REC_STEP = 2, HRG_EVAL_REC_TRUNCATED = 3, HRG_EVAL_REC_INFO = 4, HRG_EVAL_REC_EP_IM = 4 + HRG_INFO_DIM };
+/* One evaluation: SB3 1.5.0's evaluate_policy(deterministic = True) for n_policies parameter sets at once.  The batch is n_policies groups of n_envs / n_policies
+ * consecutive envs, group k stepped by parameter set k, n_eval_episodes per group; and the policy's view of an observation row: the selected columns, the state
+ * imitation reward's time column, DatasetObsNormWrapper's normalisation (hrg_replay_desc's), or on a goal env the feature row achieved_goal | desired_goal |
+ * observation (hrg_her_features'). */
+typedef struct hrg_eval_desc {
+  int32_t n_envs;
+  int32_t n_policies;             /* parameter sets; divides n_envs */
+  int32_t n_eval_episodes;        /* per parameter set; env e of a group of m takes (n_eval_episodes + e % m) / m of them (SB3's episode_count_targets) */
+  int32_t act_dim;                /* action values the policy emits: 7 joint space, 4 with the Cartesian front-end */
+  int32_t goal_env;               /* 1: the view is the feature row of a goal env (no time column, no normalisation) */
+  int32_t goal_kind;              /* HRG_GOAL_* (goal_env = 1) */
+  int32_t n_obs_cols;             /* columns of the superset in the policy's observation (goal_env: in its `observation` entry) */
+  int32_t obs_cols[HRG_OBS_DIM];  /* column of the superset behind each value of the observation */
+  int32_t observe_time;           /* 1: one more value behind the columns, the time column of the state imitation reward */
+  int32_t normalize;              /* 1: value k becomes (v - mean[k]) / std[k], computed in double, rounded to float once */
+  int32_t squash;                 /* 1 (with normalize): ... tanh(squash_factor * .) before the rounding */
+  int32_t reserved_;
+  double squash_factor;
+  double mean[HRG_OBS_DIM];       /* the first n_obs_cols + observe_time entries are read */
+  double std[HRG_OBS_DIM];        /* non-zero */
+  double act_low[HRG_ACT_DIM], act_high[HRG_ACT_DIM]; /* the action space's bounds: SAC's actions are unscaled to them, PPO's clamped */
+} hrg_eval_desc;
+
+typedef struct hrg_eval hrg_eval;       /* opaque */
 typedef struct hrg_batch hrg_batch; /* opaque */
 typedef struct hrg_her hrg_her;     /* opaque */
 typedef struct hrg_rollout hrg_rollout; /* opaque */
@@ -903,6 +933,46 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
 int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
                     float* values_dev, float* log_probs_dev, void* stream);
 int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
+
+/* A learner's counters, for a checkpoint that is loaded into a fresh handle: Adam's bias corrections, the keys of the draws and (SAC) the phase of the target
+ * update follow from them.
+ *   hrg_sac_restore  gradient steps so far, act calls that drew their noise (hrg_sac_sizes' entries 3 and 4).
+ *   hrg_ppo_restore  minibatch steps so far, forward calls that drew their noise (hrg_ppo_sizes' entries 3 and 4). */
+int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls);
+int hrg_ppo_restore(hrg_ppo* h, uint64_t steps, uint64_t forward_calls);
+
+/* Evaluation on the device (csrc/hrgym_eval.h): SB3 1.5.0's evaluate_policy with deterministic = True as a loop of three launches per env step -- the step entry
+ * that fits what is attached, hrg_eval_step, hrg_eval_policy_* -- with no copy to the host between them.  The view float [n_envs][width] and the action rows double
+ * [n_envs][HRG_ACT_DIM] are the caller's device arrays, width = n_obs_cols + observe_time, on a goal env ag_dim + dg_dim + n_obs_cols.  All but create / destroy /
+ * remaining / export / size are asynchronous on `stream`.  The step counter lives in the handle on the host.
+ *   hrg_eval_create      checks the descriptor before anything is allocated: HRG_ERR_INVALID for n_envs < 1, n_policies < 1, n_envs % n_policies != 0,
+ *                        n_eval_episodes < 1, a quota ceil(n_eval_episodes / (n_envs / n_policies)) above HRG_EVAL_MAX_EPISODES_PER_ENV, what hrg_replay_create
+ *                        refuses of the columns and the statistics, bounds that are not finite or not ordered; HRG_ERR_UNSUPPORTED for goal_env with
+ *                        observe_time or normalize, a goal_kind that is no HRG_GOAL_*, a feature row wider than HRG_OBS_DIM.
+ *   hrg_eval_begin       after a reset: obs_dev float [n_envs][HRG_OBS_DIM], time_dev float [n_envs] (needed with observe_time) -> every env's running return,
+ *                        length and count 0, its quota, view_dev = the policy's view of obs_dev.  The step counter becomes 0.
+ *   hrg_eval_step        after a step (the tensors it wrote): the running return adds the env's own reward (column HRG_SIR_R_ENV of sir_dev, HRG_IMIT_R_ENV of
+ *                        imit_dev, or reward_dev without either), the running length 1; where done_dev[e] and the env's count is below its quota, record `count`
+ *                        of env e is written and the count moves; view_dev = the policy's view of obs_dev (the row after auto-reset) with sir column
+ *                        HRG_SIR_TIME_OBS.  imit_dev / sir_dev may be NULL; not both given; sir_dev is needed with observe_time.  Advances the step counter.
+ *   hrg_eval_policy_sac  actions_dev = low + 0.5 (tanh(mu) + 1) (high - low) of the actor of parameter set k on the rows of group k, in double, zero behind
+ *                        act_dim.  params_dev float [n_policies][n_params] in hrg_sac's layout (`sac` gives the offsets; its obs_dim must be the view's width, its
+ *                        act_dim the descriptor's, its device the evaluator's: HRG_ERR_INVALID otherwise).
+ *   hrg_eval_policy_ppo  the same with the policy network of hrg_ppo: actions_dev = clamp(mu, low, high).
+ *   hrg_eval_remaining   synchronous: remaining_host int64[1] = sum over the envs of quota - count (0: every group has its episodes).
+ *   hrg_eval_export      synchronous: counts_host, quota_host int32 [n_envs], records_host double [n_envs][max_quota][HRG_EVAL_RECORD_DIM] (record c of env e is
+ *                        valid for c < counts[e]).  Any pointer may be NULL.
+ *   hrg_eval_size        size_host int64[4] = max_quota, steps since begin, the view's width, bytes of device memory held. */
+int hrg_eval_create(const hrg_eval_desc* desc, int32_t device, hrg_eval** out);
+void hrg_eval_destroy(hrg_eval* h);
+int hrg_eval_begin(hrg_eval* h, const float* obs_dev, const float* time_dev, float* view_dev, void* stream);
+int hrg_eval_step(hrg_eval* h, const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, const float* imit_dev,
+                  const float* sir_dev, float* view_dev, void* stream);
+int hrg_eval_policy_sac(hrg_eval* h, hrg_sac* sac, const float* params_dev, const float* view_dev, double* actions_dev, void* stream);
+int hrg_eval_policy_ppo(hrg_eval* h, hrg_ppo* ppo, const float* params_dev, const float* view_dev, double* actions_dev, void* stream);
+int hrg_eval_remaining(hrg_eval* h, int64_t* remaining_host, void* stream);
+int hrg_eval_export(hrg_eval* h, int32_t* counts_host, int32_t* quota_host, double* records_host);
+int hrg_eval_size(hrg_eval* h, int64_t* size_host);
 
 /* Kernel timing hook for bench.py: records HIP events on the launch stream around every step kernel
  * since the last call; returns average kernel milliseconds and the number of launches measured. */

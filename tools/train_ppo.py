@@ -14,6 +14,7 @@ import time
 
 sys.path.insert(0, '.')
 import human_robot_gym_amd as hrg   # noqa: E402
+from human_robot_gym_amd.training_utils import run_folder_from_args   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--env-id", default="ReachHuman")
@@ -29,12 +30,18 @@ ap.add_argument("--gae-lambda", type=float, default=0.9)
 ap.add_argument("--log-std-init", type=float, default=-2.7)
 ap.add_argument("--separate", action="store_true", help="net_arch [dict(pi=[64, 64], vf=[64, 64])] instead of the shared [64, 64]")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
+ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
+ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
+ap.add_argument("--eval-n-envs", type=int, default=64)
+ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
 args = ap.parse_args()
 
 env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
 env.attach_rollout(n_steps=args.n_steps, gamma=args.gamma, gae_lambda=args.gae_lambda)
 learner = env.attach_ppo(batch_size=args.batch_size, n_epochs=args.n_epochs, learning_rate=args.learning_rate, log_std_init=args.log_std_init, ortho_init=False,
                          net_arch=[dict(pi=[64, 64], vf=[64, 64])] if args.separate else [64, 64], seed=args.seed)
+run = run_folder_from_args(args)
 t0 = time.time()
 for k in range(args.rollouts):
     env.collect_rollout(learner.policy, learner.value)
@@ -42,5 +49,7 @@ for k in range(args.rollouts):
     line = dict(rollout=k, env_steps=(k + 1) * args.n_steps * args.n_envs, seconds=round(time.time() - t0, 3))
     line.update(env.rollout.episode_stats())
     line.update(learner.diagnostics())
+    line.update(run.after(learner, line["env_steps"]))
     print(json.dumps(line), flush=True)
+run.finish(learner)
 env.close()

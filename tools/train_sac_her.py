@@ -20,6 +20,7 @@ import time
 sys.path.insert(0, '.')
 import torch   # noqa: E402
 import human_robot_gym_amd as hrg   # noqa: E402
+from human_robot_gym_amd.training_utils import run_folder_from_args   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--env-id", default="ReachHuman")
@@ -36,6 +37,11 @@ ap.add_argument("--batch-size", type=int, default=128)
 ap.add_argument("--learning-rate", type=float, default=5e-4)
 ap.add_argument("--ent-coef", default="auto_0.2")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
+ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
+ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
+ap.add_argument("--eval-n-envs", type=int, default=64)
+ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
 args = ap.parse_args()
 
 env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, goal_env=True, obs_keys=args.obs_keys, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
@@ -48,6 +54,7 @@ def uniform(features):
     return torch.rand(features.shape[0], learner.act_dim, generator=gen, device=features.device) * 2.0 - 1.0
 
 
+run = run_folder_from_args(args, goal_env=True, obs_keys=args.obs_keys)
 t0 = time.time()
 for block in range(args.blocks):
     warm = env.her.counts_host()[0] < args.learning_starts
@@ -60,5 +67,7 @@ for block in range(args.blocks):
     line.update(env.her.episode_stats())
     if learner.n_updates:
         line.update(learner.diagnostics())
+    line.update(run.after(learner, line["env_steps"]))
     print(json.dumps(line), flush=True)
+run.finish(learner)
 env.close()
