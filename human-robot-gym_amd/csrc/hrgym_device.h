@@ -392,7 +392,7 @@ DI double fsqrt(double x) {
   h = __builtin_fma(h, r, h);
   g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
   g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
-  return x > 0 ? g : 0.0;
+  return __builtin_fmax(g, 0.0);   // x <= 0 (or NaN) made g a NaN through v_rsq_f64, and the IEEE maximum returns the other operand: one v_max_f64 instead of a compare and two selects
 }
 // read-only operands are templated on the pointer type so that LDS / constant / private operands keep their address space
 DI void v3set(double* r, double a, double b, double c) { r[0] = a; r[1] = b; r[2] = c; }
@@ -474,41 +474,68 @@ DI void axisangle2mat(double* M, PA ax, double ang) {
 DI double clampd(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // wave-wide helpers (wave = 64 lanes on gfx950)
-// one DPP step of a 64-bit value: lanes outside row_mask receive 0.0
-template <int CTRL, int ROW_MASK>
+// one DPP step of a 64-bit value over every row: a lane whose source lies outside its row (row shifts) or is disabled in EXEC receives 0.0.  bound_ctrl makes the
+// hardware supply that zero, so no `old` value is materialised: two v_mov_b32_dpp and the consuming instruction.
+template <int CTRL>
 DI double dpp_f64(double v) {
   const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, ROW_MASK, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffLL), CTRL, 0xf, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
-// wave-wide sum on the DPP network (no LDS crossbar): quad swaps, row half-mirror / mirror, then the gfx9 row
-// broadcasts 15 and 31; the total lands in lane 63 and is read back as a scalar.
-DI double wave_sum(double v) {
-  v += dpp_f64<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141, 0xf>(v);  // row_half_mirror
-  v += dpp_f64<0x140, 0xf>(v);  // row_mirror
-  v += dpp_f64<0x142, 0xa>(v);  // row_bcast15 -> rows 1,3
-  v += dpp_f64<0x143, 0xc>(v);  // row_bcast31 -> rows 2,3
+// ... and over the rows of ROW_MASK only (the row broadcasts that end a wave-wide reduction): the lanes of the other rows hold an UNDEFINED value afterwards
+// (whatever the destination registers held; no zero is written for them), a disabled source lane still supplies 0.0
+template <int CTRL, int ROW_MASK>
+DI double dpp_f64_rows(double v) {
+  const long long b = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)(b & 0xffffffffLL), CTRL, ROW_MASK, 0xf, true);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, ROW_MASK, 0xf, true);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// lane 63 of a value as a scalar
+DI double last_lane(double v) {
   const long long b = __double_as_longlong(v);
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), 63);
   const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
-DI double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { double t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+// maximum of two doubles neither of which is a NaN, for the cross-lane reductions: exactly one v_max_f64.  (__builtin_fmax puts a canonicalising v_max_f64 x, x in
+// front for an operand that comes out of a DPP move, and a compare with two selects is three instructions.)  Against `a > b ? a : b` the value differs only in the
+// sign of a zero when both are zeros.  The compiler treats the statement's result like any VALU result: it pads the wait states a DPP move or v_readlane of it needs
+// (s_nop 1 between the steps of a chain, as after v_add_f64; tests/test_wave_helpers_gpu.py holds the chains to their values on the device).
+DI double max_f64(double a, double b) {
+  double r;
+  asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// wave-wide sum on the DPP network (no LDS crossbar): quad swaps, row half-mirror / mirror, then the gfx9 row
+// broadcasts 15 and 31; the total lands in lane 63 and is read back as a scalar.
+// The two broadcasts write rows 1, 3 and rows 2, 3; rows 0, 2 after the first and rows 0, 1 after the second add an undefined value and are garbage from then on.
+// Lane 63 never sees them: its fifth step reads lane 47 as the fourth step left it (row 2, not yet touched), its sixth reads lane 31 after the fifth step (row 1,
+// which that step wrote from lane 15 of the fourth), and the fifth step's garbage in row 2 and the sixth's in rows 0, 1 are read by no later step.
+DI double wave_sum(double v) {
+  v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_f64<0x141>(v);  // row_half_mirror
+  v += dpp_f64<0x140>(v);  // row_mirror
+  v += dpp_f64_rows<0x142, 0xa>(v);  // row_bcast15 -> rows 1,3
+  v += dpp_f64_rows<0x143, 0xc>(v);  // row_bcast31 -> rows 2,3
+  return last_lane(v);
+}
+// maximum over each row of 16 lanes on the DPP network (every lane of the row receives it); a disabled lane counts as 0.0
+DI double row16_max(double v) {
+  v = max_f64(dpp_f64<0xB1>(v), v);    // quad_perm [1,0,3,2]
+  v = max_f64(dpp_f64<0x4E>(v), v);    // quad_perm [2,3,0,1]
+  v = max_f64(dpp_f64<0x141>(v), v);   // row_half_mirror
+  v = max_f64(dpp_f64<0x140>(v), v);   // row_mirror
   return v;
 }
-// maximum over each row of 16 lanes on the DPP network (every lane of the row receives it)
-DI double row16_max(double v) {
-  double t;
-  t = dpp_f64<0xB1, 0xf>(v); v = t > v ? t : v;    // quad_perm [1,0,3,2]
-  t = dpp_f64<0x4E, 0xf>(v); v = t > v ? t : v;    // quad_perm [2,3,0,1]
-  t = dpp_f64<0x141, 0xf>(v); v = t > v ? t : v;   // row_half_mirror
-  t = dpp_f64<0x140, 0xf>(v); v = t > v ? t : v;   // row_mirror
-  return v;
+// wave-wide maximum, the network of wave_sum (a maximum does not depend on the order): lane 63 holds it, the rows the broadcasts leave undefined are not read
+DI double wave_max(double v) {
+  v = row16_max(v);
+  v = max_f64(dpp_f64_rows<0x142, 0xa>(v), v);  // row_bcast15 -> rows 1,3
+  v = max_f64(dpp_f64_rows<0x143, 0xc>(v), v);  // row_bcast31 -> rows 2,3
+  return last_lane(v);
 }
 // orders LDS traffic between the lane roles of ONE wave.  A wave's LDS instructions execute in issue order, so no hardware wait is needed between a
 // write by one lane and a read by another; what has to be stopped is the compiler moving one across the other.  (With one wave per workgroup
@@ -922,20 +949,30 @@ DI double chol_lanes(double a, int lane, bool* ok) {
 }
 // inclusive prefix sum along the robot's kinematic chain for lanes = bodies: lanes 0..5 the serial arm, lanes 6, 7 (fingers,
 // children of link 6) = prefix of lane 5 + own value.  DPP row shifts inside row 0; shifted-in lanes contribute 0.
+// ZEROS: the caller's x already is a zero (of either sign) in every lane >= NARM, so the first select is left out.
+template <bool ZEROS = false>
 DI double chain_prefix(double x, int lane) {
-  double y = lane < NARM ? x : 0.0;
-  y += dpp_f64<0x111, 0xf>(y);  // row_shr:1
-  y += dpp_f64<0x112, 0xf>(y);  // row_shr:2
-  y += dpp_f64<0x114, 0xf>(y);  // row_shr:4
+  double y = ZEROS || lane < NARM ? x : 0.0;
+  {
+#pragma clang fp contract(off)   // stays an add, as behind the select: with ZEROS it would fuse with the multiply that made x, and round differently
+    y += dpp_f64<0x111>(y);  // row_shr:1
+  }
+  y += dpp_f64<0x112>(y);  // row_shr:2
+  y += dpp_f64<0x114>(y);  // row_shr:4
   return lane < NARM ? y : y + x;
 }
 // sum over the subtree of body i = lane i of the robot's kinematic tree: bodies i..7 for the arm links 0..5 (the fingers 6, 7 hang off link 5), the body itself for
 // a finger.  DPP row shifts to the left inside row 0; lanes 8..15 contribute 0.
+// ZEROS: the caller's x already is a zero (of either sign) in every lane >= NV, so the first select is left out.
+template <bool ZEROS = false>
 DI double subtree_sum(double x, int lane) {
-  double y = lane < NV ? x : 0.0;
-  y += dpp_f64<0x101, 0xf>(y);  // row_shl:1
-  y += dpp_f64<0x102, 0xf>(y);  // row_shl:2
-  y += dpp_f64<0x104, 0xf>(y);  // row_shl:4
+  double y = ZEROS || lane < NV ? x : 0.0;
+  {
+#pragma clang fp contract(off)   // (as in chain_prefix)
+    y += dpp_f64<0x101>(y);  // row_shl:1
+  }
+  y += dpp_f64<0x102>(y);  // row_shl:2
+  y += dpp_f64<0x104>(y);  // row_shl:4
   return lane < NARM ? y : x;
 }
 // a wave-uniform double that arrived in a vector register (loaded from the LDS image, computed from such loads): moved to a scalar register pair.  A value that
@@ -1034,9 +1071,9 @@ DI void tiles_pivots(Tiles<N>& T, int i, int j, int np, bool& good) {
 }
 // sum over each group of 8 consecutive lanes (one matrix row in the (i,j) lane layout) on the DPP network; every lane of the group receives it
 DI double row8_sum(double v) {
-  v += dpp_f64<0xB1, 0xf>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E, 0xf>(v);    // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141, 0xf>(v);   // row_half_mirror: lane k <-> 7 - k within each half row
+  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
+  v += dpp_f64<0x141>(v);   // row_half_mirror: lane k <-> 7 - k within each half row
   return v;
 }
 // y = A x for lanes = (i, j): A_ij in a register, x in LDS; returns y_i in every lane of row i

@@ -3035,6 +3035,39 @@ __global__ __launch_bounds__(64) void hrg_pose_compare_kernel(const DevModel* __
   for (int j = lane; j < 6 * HRG_NHB; j += 64) o[NP + j] = (&L.hcap[0][0])[j];
   for (int j = lane; j < 3 * HRG_NHJ; j += 64) o[NP + 6 * HRG_NHB + j] = (&s.human_site[0][0])[j];
 }
+
+// test tap (hrg_debug_wave_helpers): the wave helpers of hrgym_device.h on their own, one wave over 64 doubles.  The lanes outside `mask` branch around every
+// call (they keep the NaN their rows of `out` are filled with), so the helpers run under that EXEC mask.  out[HRG_WAVE_NOUT][64], rows in the order of the header.
+__global__ __launch_bounds__(64) void hrg_wave_helpers_kernel(const double* __restrict__ in, unsigned long long mask, double* __restrict__ out) {
+  const int lane = hrg_lane();
+  const double x = in[lane];
+  for (int k = 0; k < HRG_WAVE_NOUT; k++) out[64 * k + lane] = __builtin_nan("");
+  if ((mask >> lane) & 1) {
+    double* o = out + lane;
+    o[64 * 0] = wave_sum(x);
+    o[64 * 1] = row8_sum(x);
+    o[64 * 2] = row16_max(x);
+    o[64 * 3] = wave_max(x);
+    o[64 * 4] = chain_prefix(x, lane);
+    o[64 * 5] = subtree_sum(x, lane);
+    o[64 * 6] = fsqrt(x);
+    o[64 * 7] = dpp_f64<0xB1>(x);
+    o[64 * 8] = dpp_f64<0x4E>(x);
+    o[64 * 9] = dpp_f64<0x141>(x);
+    o[64 * 10] = dpp_f64<0x140>(x);
+    o[64 * 11] = dpp_f64<0x111>(x);
+    o[64 * 12] = dpp_f64<0x112>(x);
+    o[64 * 13] = dpp_f64<0x114>(x);
+    o[64 * 14] = dpp_f64<0x101>(x);
+    o[64 * 15] = dpp_f64<0x102>(x);
+    o[64 * 16] = dpp_f64<0x104>(x);
+    o[64 * 17] = dpp_f64_rows<0x142, 0xa>(x);
+    o[64 * 18] = dpp_f64_rows<0x143, 0xc>(x);
+    o[64 * 19] = __builtin_amdgcn_rsq(x);   // the seed of fsqrt, so that a test can restate fsqrt's iteration from it
+    o[64 * 20] = chain_prefix<true>(lane < NARM ? x : 0.0, lane);   // the forms that trust the caller's zeros, on an input that has them
+    o[64 * 21] = subtree_sum<true>(lane < NV ? x : 0.0, lane);
+  }
+}
 #endif
 
 // Launch shims: every translation unit defines this pair for its own kernels, under the variant's name and with hidden visibility; the host side (the base
@@ -3638,6 +3671,15 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
     hipLaunchKernelGGL(hrg_pose_compare_kernel, dim3((unsigned)n), dim3(64), 0, 0, b->d_model, (const PoseQuery*)d[0], (int)n, (double*)d[1]);
   });
   return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_pose_compare: device allocation / copy / launch failed");
+}
+
+int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* out_host) {
+  if (!in_host || !out_host) return fail(HRG_ERR_INVALID, "null argument");
+  const TapBuf in[] = {{in_host, sizeof(double) * 64}};
+  const bool ok = hrg_run_tap(in, 1, out_host, sizeof(double) * 64 * HRG_WAVE_NOUT, [&](void** d) {
+    hipLaunchKernelGGL(hrg_wave_helpers_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (unsigned long long)lane_mask, (double*)d[1]);
+  });
+  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_wave_helpers: device allocation / copy / launch failed");
 }
 
 int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {

@@ -125,7 +125,7 @@ PH_DYNTERMS void robot_dynamics_terms(const DevModel* __restrict__ dm_, int lane
   {
     double cc[10];
 #pragma unroll
-    for (int a = 0; a < 10; a++) cc[a] = subtree_sum(bI[a], lane);
+    for (int a = 0; a < 10; a++) cc[a] = subtree_sum<true>(bI[a], lane);   // bI is 0.0 in the lanes >= NV
     double n[3], f[3];
     sinertia_mul(n, f, cc, Sw, Sv);
     if (lane < NV) {
@@ -143,14 +143,16 @@ PH_DYNTERMS void robot_dynamics_terms(const DevModel* __restrict__ dm_, int lane
     {
       double jw[3], jv[3];
       const double qd = lane < NV ? L.st.qvel[i] : 0.0;
+      // jw is a zero in every lane >= NARM (the fingers slide: Sw = 0), and so is t1 = vw x jw below: their scans skip the select in front (chain_prefix<true>);
+      // jv and t2 + t3 are not
       v3scl(jw, Sw, qd);
       v3scl(jv, Sv, qd);
-      for (int a = 0; a < 3; a++) { vw[a] = chain_prefix(jw[a], lane); vv[a] = chain_prefix(jv[a], lane); }
+      for (int a = 0; a < 3; a++) { vw[a] = chain_prefix<true>(jw[a], lane); vv[a] = chain_prefix(jv[a], lane); }
       double t1[3], t2[3], t3[3];
       v3cross(t1, vw, jw);
       v3cross(t2, vw, jv);
       v3cross(t3, vv, jw);
-      for (int a = 0; a < 3; a++) { aw[a] = chain_prefix(t1[a], lane); av[a] = chain_prefix(t2[a] + t3[a], lane) - m.gravity[a]; }
+      for (int a = 0; a < 3; a++) { aw[a] = chain_prefix<true>(t1[a], lane); av[a] = chain_prefix(t2[a] + t3[a], lane) - m.gravity[a]; }
     }
     if (lane < NV) { v3cpy(L.vw[i], vw); v3cpy(L.vv[i], vv); }
     __builtin_amdgcn_sched_barrier(0);
@@ -170,7 +172,7 @@ PH_DYNTERMS void robot_dynamics_terms(const DevModel* __restrict__ dm_, int lane
     __builtin_amdgcn_sched_barrier(0);
     double gm = 0;
 #pragma unroll
-    for (int a = 0; a < 3; a++) gm += Sw[a] * subtree_sum(fn[a], lane) + Sv[a] * subtree_sum(ff[a], lane);
+    for (int a = 0; a < 3; a++) gm += Sw[a] * subtree_sum<true>(fn[a], lane) + Sv[a] * subtree_sum<true>(ff[a], lane);   // products with bI: zeros in the lanes >= NV
     if (lane < NV) L.bias[i] = gm;
   }
   wave_sync();

@@ -676,6 +676,15 @@ int hrg_batch_pose_table_bytes(hrg_batch* b, int64_t* bytes_host);
  * `clip` under those episode offsets, [0] by the live tree kinematics (the offsets composed before the tree), [1] from the pose table: 24 capsules (p1, p2) | 23
  * sites.  One wavefront per query.  HRG_ERR_UNSUPPORTED for a batch without a pose table. */
 int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, double* out_host);
+/* test tap of the wave-wide helpers of the step kernels (csrc/hrgym_device.h): one wavefront over in_host[64], lane = index; the lanes whose bit of lane_mask is clear
+ * branch around every helper call, so the helpers run under that EXEC mask.  out_host[HRG_WAVE_NOUT][64] = every lane's value (NaN in a lane outside lane_mask) of, row
+ * by row: wave_sum (the scalar it returns; read from lane 63, so defined only with bit 63 set), row8_sum, row16_max, wave_max (as wave_sum), chain_prefix, subtree_sum,
+ * fsqrt, dpp_f64 with the controls 0xB1, 0x4E (quad_perm), 0x141 (row_half_mirror), 0x140 (row_mirror), 0x111, 0x112, 0x114 (row_shr 1, 2, 4), 0x101, 0x102, 0x104
+ * (row_shl 1, 2, 4), dpp_f64_rows with 0x142 under row mask 0xa (row_bcast15; rows 0, 2 undefined) and 0x143 under 0xc (row_bcast31; rows 0, 1 undefined), v_rsq_f64, the
+ * seed fsqrt iterates from, and chain_prefix<true> / subtree_sum<true> (the forms without the select in front) over the input with 0.0 in the lanes >= HRG_NARM / >= HRG_NV.
+ * 0 / -1. */
+enum { HRG_WAVE_NOUT = 22 /* rows of out_host */ };
+int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* out_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the
