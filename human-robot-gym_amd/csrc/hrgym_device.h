@@ -202,6 +202,14 @@ struct DevModel {
   const double* hull_dev;   // hull vertices of the arm links in device memory (m.robot_hulls; m.hull_verts is the creator's host pointer)
   double hull_cen[HRG_NHULL][3];   // vertex centroid of each hull, body frame: the interior point of the hull - cube penetration (MPR)
   unsigned long long* mpr_fallback;   // device counter: hull - cube pairs whose MPR did not converge and kept the capsule contact (hrg_batch_mpr_fallbacks)
+  // Expressions of model constants that a substep would otherwise evaluate again, FP64 divisions among them.  hrg_model_constants_kernel fills them on the device once
+  // the model is there, with the step kernels' own expressions: the device's division (-fapprox-func) is not the host's, and the entries must be the bits a substep
+  // would compute (tests/test_model_constants_gpu.py).
+  double fric_D[NV + 1], fric_lim[NV + 1];   // friction-loss rows (position term exactly 0, impedance solimp[0]): D = 1 / ((1 - imp) / imp * invweight) and the limit floss / D of
+                                             // dof r; [NV]: the nail's slide joint (hammering); 0 for a dof without friction loss
+  double eul_hd[NV], eul_rhd[2];             // mj_Euler's implicit joint damping (euler_robot_tree): h * jnt_damping of every joint; 1 / (h * jnt_damping) of the two
+  int32_t eul_fingers, eul_pad;              // fingers, 0 unless both are damped (eul_fingers: the Woodbury term is in)
+  double rcap_mid[HRG_NRCAP][3];             // mid point 0.5 (p1 + p2) of each robot collision capsule, body frame (classify: the speed of a robot geom at a human contact)
 };
 
 // vertex centroid of each hull (body frame): the interior point MPR starts from (hrg_batch_create, hrg_test_hull_box_queries)
@@ -282,6 +290,9 @@ struct Lds {
 #endif
 #endif
   double act[NV];                        // this step's action (7 used)
+#if HRG_POSE_TABLE
+  double hyaw[9];                        // rotation matrix of st.human_rot_offset, the episode's yaw: once per env_step and by env_reset (human_yaw_update), read by the pose table path every cycle
+#endif
   int acc_has_collision, acc_collision_type, acc_failsafe, acc_pad;  // per-policy-step accumulators
 #if HRG_HAMMER
   hrg_hammer_state hm;                   // board, hammer, nail + task bookkeeping (streamed from its own HBM array)
@@ -313,7 +324,6 @@ struct Lds {
     struct {  // human_control + collide + classify (the dynamics step's rows take this space afterwards)
       double hcap[HRG_NHB][6], rcapw[HRG_NRCAP][6];
       int hnear[HRG_NHB];                // human capsules whose bounding sphere comes near the robot (the pair rounds of collide run over these)
-      double rcen[HRG_NRCAP][3];         // capsule centres: collide -> classify (the speed of a robot geom at a human contact)
 #if HRG_HULL_MPR
       union { GjkLds gjk; MprLds mpr; }; // the simplex of a hull query / the portal of a hull - box query (hrgym_hull.h): one pair at a time
 #elif HRG_HULLS
@@ -339,6 +349,19 @@ struct Lds {
 #endif
   };
 };
+
+// Envs per CU that each variant's image has to keep fitting into the CU's 160 KiB: the number its registers allow where they bind first (ReachHuman: 4 waves per SIMD,
+// 10 240 B; cube and lifting kernels: 3 per SIMD; handover: 2 per SIMD), the number the image itself allows today for stacking and hammering (five of ~28 / ~30 KB).
+#if HRG_HAMMER || HRG_STACK
+#define HRG_LDS_ENVS_PER_CU 5
+#elif HRG_HANDOVER
+#define HRG_LDS_ENVS_PER_CU 8
+#elif HRG_BOX
+#define HRG_LDS_ENVS_PER_CU 12
+#else
+#define HRG_LDS_ENVS_PER_CU 16
+#endif
+static_assert(sizeof(Lds) * HRG_LDS_ENVS_PER_CU <= 160 * 1024, "the per-env LDS image has outgrown this variant's envs per CU");
 
 // The per-env LDS image is a file-scope __shared__ object: every device function addresses it directly (ds_* instructions),
 // nothing is passed around as a generic pointer.

@@ -30,6 +30,33 @@ DI void impedance(const MD& m, double x0, double* imp) {  // the stiffness / dam
   *imp = d0 + y * (dmax - d0);
 }
 
+// D of a constraint row whose position term is x = pos - margin (mj_makeImpedance): the steppers' general rows, and at x = 0 the friction-loss rows' constants
+// (DevModel.fric_D, fric_lim: hrg_model_constants_kernel)
+template <class MD>
+DI double row_D(const MD& m, double x, double diag, double* imp) {
+  impedance(m, x, imp);
+  return 1.0 / ((1 - *imp) / *imp * diag);
+}
+
+// aref, D and (friction rows) the limit of an active constraint row; x = pos - margin.  A friction-loss row has x == 0 exactly: its impedance is solimp[0], so its D
+// and floss / D are constants of the model (fD, fl: DevModel.fric_D, fric_lim) and its aref is what the general expression gives for a zero position term (v - (+0.0)
+// keeps the sign of a zero v).  The general path -- impedance, D and the limit, six FP64 divisions issued for the whole wave -- runs only in a substep in which some
+// joint-limit, contact or equality row is active: the test is wave-uniform, so the usual substep (friction rows alone) branches around it.  In such a substep every
+// active row takes the general path, friction rows included: the two paths share no operation, so that the compiler contracts the general aref as it always did (a
+// product with a second use fuses differently, and a contact row's aref then differs in its last bit).
+template <class MD>
+DI void row_softness(const MD& m, bool active, int type, double K, double Bd, double x, double vel, double diag, double floss, double fD, double fl, double* aref, double* D,
+                     double* flim) {
+  if (__any(active && type != 0)) {
+    if (active) {
+      double imp;
+      *D = row_D(m, x, diag, &imp);
+      *aref = -Bd * vel - K * imp * x;
+      if (type == 0) *flim = floss / *D;
+    }
+  } else if (active) { *aref = -Bd * vel - 0.0; *D = fD; *flim = fl; }
+}
+
 // lim = floss / D of a friction row, computed once per row and substep (an FP64 division is a ~30-instruction sequence)
 DI void row_cost(int type, double D, double floss, double lim, double x, double* c, double* g, double* h) {
   if (type == 2) { *c = 0.5 * D * x * x; *g = D * x; *h = D; }  // equality (weld) row: quadratic on both sides
@@ -59,9 +86,9 @@ DI void euler_robot_tree(ModelPtr dm, int lane, double Mij, double Minv) {
   hrg_env_state& s = L.st;
   const int mi = lane >> 3, mj = lane & 7;
   const double h = m.timestep;
-  const double hd6 = h * m.jnt_damping[NARM], hd7 = h * m.jnt_damping[NARM + 1];
-  const bool fingers = hd6 > 0 && hd7 > 0;
-  const double S00 = (fingers ? 1.0 / hd6 : 0.0) + lane_value<6 * 9>(Minv), S01 = lane_value<6 * 8 + 7>(Minv), S11 = (fingers ? 1.0 / hd7 : 0.0) + lane_value<7 * 9>(Minv);
+  // (h D_f)^-1 of the two fingers (0 without finger damping) and h D of every joint are constants of the model (DevModel.eul_*): no division per substep
+  const bool fingers = dm->eul_fingers != 0;
+  const double S00 = dm->eul_rhd[0] + lane_value<6 * 9>(Minv), S01 = lane_value<6 * 8 + 7>(Minv), S11 = dm->eul_rhd[1] + lane_value<7 * 9>(Minv);
   const double idet = 1.0 / (S00 * S11 - S01 * S01);
   auto Ainv = [&](const double* v) -> double {   // (A^-1 v)_mi in every lane of row mi
     const double y = row8_sum(Minv * v[mj]);
@@ -77,7 +104,7 @@ DI void euler_robot_tree(ModelPtr dm, int lane, double Mij, double Minv) {
   wave_sync();
   const double x0 = Ainv(L.d);
   wave_sync();
-  if (mj == 0) L.d[mi] = mi < NARM ? h * m.jnt_damping[mi] * x0 : 0.0;
+  if (mj == 0) L.d[mi] = mi < NARM ? dm->eul_hd[mi] * x0 : 0.0;
   wave_sync();
   const double x = x0 - Ainv(L.d);
   if (mj == 0) {
@@ -161,9 +188,9 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
     SRow& w = R[k];
     w.active = false; w.type = 1; w.kind = 0; w.dof = 0; w.sgn = 0; w.D = 0; w.floss = 0; w.flim = 0; w.aref = 0; w.y = 0; w.p = 0;
     bool cand = false;
-    double pos = 0, margin = 0, diag = 0, vel = 0;
+    double pos = 0, margin = 0, diag = 0, vel = 0, fD = 0, flim = 0;   // fD, flim: a friction row's D and limit (constants of the model)
     if (r < NV) {
-      if (m.jnt_frictionloss[r] > 0) { cand = true; w.type = 0; w.floss = m.jnt_frictionloss[r]; diag = m.dof_invweight0[r]; w.dof = r; w.sgn = 1.0; vel = s.qvel[r]; }
+      if (m.jnt_frictionloss[r] > 0) { cand = true; w.type = 0; w.floss = m.jnt_frictionloss[r]; diag = m.dof_invweight0[r]; w.dof = r; w.sgn = 1.0; vel = s.qvel[r]; fD = dm->fric_D[r]; flim = dm->fric_lim[r]; }
     } else if (r < SROW_WELD0) {
       const int q = r - NV, dof = q >> 1, side = q & 1;
       const double dist = side ? m.jnt_range[dof][1] - s.qpos[dof] : s.qpos[dof] - m.jnt_range[dof][0];
@@ -244,14 +271,8 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
       }
     }
     w.active = cand && diag > 0;
-    if (w.active) {
-      double imp;
-      const double K = dm->sol_K, Bd = dm->sol_Bd;
-      impedance(m, pos - margin, &imp);
-      w.aref = -Bd * vel - K * imp * (pos - margin);
-      w.D = 1.0 / ((1 - imp) / imp * diag);
-      if (w.type == 0) w.flim = w.floss / w.D;
-    }
+    const double K = dm->sol_K, Bd = dm->sol_Bd;
+    row_softness(m, w.active, w.type, K, Bd, pos - margin, vel, diag, w.floss, fD, flim, &w.aref, &w.D, &w.flim);
   }
   STAMP(21);
   COUNT(19, __popcll(__ballot(R[0].active)) + __popcll(__ballot(R[1].active)));
@@ -671,11 +692,11 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
     HRow& w = R[k];
     w.active = false; w.type = 1; w.kind = 0; w.dof = 0; w.sgn = 0; w.D = 0; w.floss = 0; w.flim = 0; w.aref = 0; w.y = 0; w.p = 0;
     bool cand = false;
-    double pos = 0, margin = 0, diag = 0, vel = 0, Bd_own = -1.0;
+    double pos = 0, margin = 0, diag = 0, vel = 0, Bd_own = -1.0, fD = 0, flim = 0;   // fD, flim: a friction row's D and limit (constants of the model)
     if (r < NV) {
-      if (m.jnt_frictionloss[r] > 0) { cand = true; w.type = 0; w.floss = m.jnt_frictionloss[r]; diag = m.dof_invweight0[r]; w.dof = r; w.sgn = 1.0; vel = s.qvel[r]; }
+      if (m.jnt_frictionloss[r] > 0) { cand = true; w.type = 0; w.floss = m.jnt_frictionloss[r]; diag = m.dof_invweight0[r]; w.dof = r; w.sgn = 1.0; vel = s.qvel[r]; fD = dm->fric_D[r]; flim = dm->fric_lim[r]; }
     } else if (r == HROW_NFRIC) {   // nail_head_joint0: frictionloss with its own solreffriction (nail.xml:7)
-      if (m.hm_nail_frictionloss > 0) { cand = true; w.type = 0; w.floss = m.hm_nail_frictionloss; diag = m.hm_nail_invweight; w.dof = HM_ON; w.sgn = 1.0; vel = hm.nail_v; Bd_own = m.hm_nail_fric_damping / m.solimp[1]; }
+      if (m.hm_nail_frictionloss > 0) { cand = true; w.type = 0; w.floss = m.hm_nail_frictionloss; diag = m.hm_nail_invweight; w.dof = HM_ON; w.sgn = 1.0; vel = hm.nail_v; Bd_own = m.hm_nail_fric_damping / m.solimp[1]; fD = dm->fric_D[NV]; flim = dm->fric_lim[NV]; }
     } else if (r < HROW_NLIM) {
       const int q = r - HROW_LIM0, dof = q >> 1, side = q & 1;
       const double dist = side ? m.jnt_range[dof][1] - s.qpos[dof] : s.qpos[dof] - m.jnt_range[dof][0];
@@ -776,14 +797,8 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
       }
     }
     w.active = cand && diag > 0;
-    if (w.active) {
-      double imp;
-      const double K = dm->sol_K, Bd = Bd_own >= 0 ? Bd_own : dm->sol_Bd;
-      impedance(m, pos - margin, &imp);
-      w.aref = -Bd * vel - K * imp * (pos - margin);
-      w.D = 1.0 / ((1 - imp) / imp * diag);
-      if (w.type == 0) w.flim = w.floss / w.D;
-    }
+    const double K = dm->sol_K, Bd = Bd_own >= 0 ? Bd_own : dm->sol_Bd;
+    row_softness(m, w.active, w.type, K, Bd, pos - margin, vel, diag, w.floss, fD, flim, &w.aref, &w.D, &w.flim);
   }
   STAMP(21);
   COUNT(19, __popcll(__ballot(R[0].active)) + __popcll(__ballot(R[1].active)));
@@ -1228,11 +1243,12 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
   int type = 1, rdof = 0;
   bool cand = false;
   [[maybe_unused]] bool rpart = true, bpart = false;  // row acts on the robot tree / on the cube
-  double rsgn = 0, pos = 0, margin = 0, floss = 0, diag = 0, vel = 0;
+  double rsgn = 0, pos = 0, margin = 0, floss = 0, diag = 0, vel = 0, fD = 0, fl = 0;   // fD, fl: a friction row's D and limit (constants of the model)
   if (r < NV) {
     if (m.jnt_frictionloss[r] > 0) {
       cand = true; type = 0; floss = m.jnt_frictionloss[r]; diag = m.dof_invweight0[r];
       rdof = r; rsgn = 1.0; vel = s.qvel[r];
+      fD = dm->fric_D[r]; fl = dm->fric_lim[r];
     }
   } else if (r < ROW_CON0) {
     const int k = r - NV, dof = k >> 1, side = k & 1;
@@ -1345,14 +1361,7 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
   const bool is_con = r >= ROW_CON0 && r < ROW_WELD0;
 #endif
   double aref = 0, D = 0, flim = 0;
-  if (active) {
-    double imp;
-    const double K = dm->sol_K, Bd = dm->sol_Bd;
-    impedance(m, pos - margin, &imp);
-    aref = -Bd * vel - K * imp * (pos - margin);
-    D = 1.0 / ((1 - imp) / imp * diag);
-    if (type == 0) flim = floss / D;
-  }
+  row_softness(m, active, type, dm->sol_K, dm->sol_Bd, pos - margin, vel, diag, floss, fD, fl, &aref, &D, &flim);
   const uint64_t mask = __ballot(active);
 #if HRG_HANDOVER
   const uint64_t cmask = (mask & ((1ull << ROW_WELD0) - 1)) >> ROW_CON0;  // active contact rows (the weld's unit rows are added on the diagonal, not through Jc)
@@ -2175,6 +2184,9 @@ __device__ __noinline__ void env_reset(const DevModel* __restrict__ dm_, int lan
   s.human_rot_offset[0] = cos(0.5 * yaw); s.human_rot_offset[1] = 0; s.human_rot_offset[2] = 0; s.human_rot_offset[3] = sin(0.5 * yaw);
   s.animation_time = -1;
   wave_sync();
+#if HRG_POSE_TABLE
+  human_yaw_update();   // the new episode's yaw: a pose in this reset (lifting) and in the rest of a reset kernel's wave reads it
+#endif
   const double p0[3] = {0, 0, 0}, q0[4] = {1, 0, 0, 0};
   human_fk_lanes(dm_, lane, p0, q0, nullptr);
   robot_chain_fk(dm_, lane, false);
@@ -2485,6 +2497,9 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
   STAMP_INIT(lane);
   if (lane < NV) L.act[lane] = lane < HRG_ACT_DIM ? action[lane] : 0.0;
   wave_sync();
+#if HRG_POSE_TABLE
+  human_yaw_update();   // once per step: the 25 cycles read the matrix from LDS
+#endif
   if (m.ik_enabled) ik_action(dm_, lane);  // IKPositionDeltaWrapper is the outermost action wrapper (utils/training_utils.py:358-373)
   if (m.cp_enabled) screen_action(dm_, lane, gid);  // CollisionPreventionWrapper.step wraps env.step: uses the pre-step state
 #if HRG_LIFT
@@ -3031,6 +3046,7 @@ __global__ __launch_bounds__(64) void hrg_pose_compare_kernel(const DevModel* __
   for (int j = lane; j < 6 * HRG_NHB; j += 64) o[j] = (&L.hcap[0][0])[j];
   for (int j = lane; j < 3 * HRG_NHJ; j += 64) o[6 * HRG_NHB + j] = (&s.human_site[0][0])[j];
   wave_sync();
+  human_yaw_update();
   human_pose_from_table(dm, lane, f);
   for (int j = lane; j < 6 * HRG_NHB; j += 64) o[NP + j] = (&L.hcap[0][0])[j];
   for (int j = lane; j < 3 * HRG_NHJ; j += 64) o[NP + 6 * HRG_NHB + j] = (&s.human_site[0][0])[j];
@@ -3067,6 +3083,65 @@ __global__ __launch_bounds__(64) void hrg_wave_helpers_kernel(const double* __re
     o[64 * 20] = chain_prefix<true>(lane < NARM ? x : 0.0, lane);   // the forms that trust the caller's zeros, on an input that has them
     o[64 * 21] = subtree_sum<true>(lane < NV ? x : 0.0, lane);
   }
+}
+
+// The model constants of DevModel that are expressions a substep (or cycle) used to evaluate (fric_*, eul_*, rcap_mid): one wave, launched once at batch create when the model is on
+// the device.  model_constants is those expressions as the step kernels hold them (row_D is the steppers' own), for one lane's share; x0 = the position term of a
+// friction row, 0.  The test tap (hrg_debug_model_constants) runs it again with x0 from a kernel argument, so that impedance() runs as it did in a substep instead of
+// folding, and returns its values next to the stored ones: out[0][HRG_MC_DIM] stored | out[1][HRG_MC_DIM] recomputed.
+struct ModelConstants { double fric_D, fric_lim, fric_imp, eul_hd, eul_rhd, rcap_mid; int eul_fingers; };
+static_assert(3 * HRG_NRCAP <= 64, "one lane per coordinate of a capsule's mid point");
+DI ModelConstants model_constants(ModelPtr dm, int lane, double x0) {
+  const auto& m = dm->m;
+  ModelConstants c = {0, 0, 0, 0, 0, 0, 0};
+  if (lane <= NV) {   // friction-loss row of dof `lane`; lane NV: the nail's slide joint
+    const bool nail = lane == NV;
+    const int r = nail ? 0 : lane;
+    const double floss = nail ? m.hm_nail_frictionloss : m.jnt_frictionloss[r], diag = nail ? m.hm_nail_invweight : m.dof_invweight0[r];
+    if (floss > 0 && diag > 0) {
+      c.fric_D = row_D(m, x0, diag, &c.fric_imp);
+      c.fric_lim = floss / c.fric_D;
+    }
+  }
+  {   // euler_robot_tree: lane i < NV the damping term of joint i, lanes 0 and 1 the reciprocal of a finger's
+    const double h = m.timestep;
+    const double hd6 = h * m.jnt_damping[NARM], hd7 = h * m.jnt_damping[NARM + 1];
+    const bool fingers = hd6 > 0 && hd7 > 0;
+    c.eul_fingers = fingers;
+    if (lane < NV) c.eul_hd = h * m.jnt_damping[lane];
+    if (lane < 2) c.eul_rhd = fingers ? 1.0 / (lane ? hd7 : hd6) : 0.0;
+  }
+  if (lane < 3 * HRG_NRCAP) {   // lane 3 c + a: coordinate a of the mid point of robot capsule c (collide's expression before the centre moved to classify)
+    const int cc = lane / 3, a = lane - 3 * cc;
+    c.rcap_mid = 0.5 * (m.rcap_p1[cc][a] + m.rcap_p2[cc][a]);
+  }
+  return c;
+}
+__global__ __launch_bounds__(64) void hrg_model_constants_kernel(DevModel* __restrict__ dmw) {
+  const ModelPtr dm = uniform_model(dmw);
+  const int lane = hrg_lane();
+  const ModelConstants c = model_constants(dm, lane, 0.0);
+  if (lane <= NV) { dmw->fric_D[lane] = c.fric_D; dmw->fric_lim[lane] = c.fric_lim; }
+  if (lane < NV) dmw->eul_hd[lane] = c.eul_hd;
+  if (lane < 2) dmw->eul_rhd[lane] = c.eul_rhd;
+  if (lane == 0) dmw->eul_fingers = c.eul_fingers;
+  if (lane < 3 * HRG_NRCAP) (&dmw->rcap_mid[0][0])[lane] = c.rcap_mid;
+}
+__global__ __launch_bounds__(64) void hrg_model_constants_tap_kernel(const DevModel* __restrict__ dm_, double x0, double* __restrict__ out) {
+  const ModelPtr dm = uniform_model(dm_);
+  const int lane = hrg_lane();
+  const ModelConstants c = model_constants(dm, lane, x0);
+  double* st = out, *re = out + HRG_MC_DIM;
+  if (lane <= NV) {
+    const bool fr = dm_->fric_D[lane] != 0;
+    st[HRG_MC_FRIC_D + lane] = dm_->fric_D[lane]; re[HRG_MC_FRIC_D + lane] = c.fric_D;
+    st[HRG_MC_FRIC_LIM + lane] = dm_->fric_lim[lane]; re[HRG_MC_FRIC_LIM + lane] = c.fric_lim;
+    st[HRG_MC_FRIC_IMP + lane] = fr ? dm->m.solimp[0] : 0.0; re[HRG_MC_FRIC_IMP + lane] = c.fric_imp;   // the impedance the stored entries assume
+  }
+  if (lane < NV) { st[HRG_MC_EUL_HD + lane] = dm_->eul_hd[lane]; re[HRG_MC_EUL_HD + lane] = c.eul_hd; }
+  if (lane < 2) { st[HRG_MC_EUL_RHD + lane] = dm_->eul_rhd[lane]; re[HRG_MC_EUL_RHD + lane] = c.eul_rhd; }
+  if (lane == 0) { st[HRG_MC_EUL_FINGERS] = dm_->eul_fingers; re[HRG_MC_EUL_FINGERS] = c.eul_fingers; }
+  if (lane < 3 * HRG_NRCAP) { st[HRG_MC_RCAP_MID + lane] = (&dm_->rcap_mid[0][0])[lane]; re[HRG_MC_RCAP_MID + lane] = c.rcap_mid; }
 }
 #endif
 
@@ -3599,6 +3674,9 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   }
   HIPCHK_C(hipMalloc(&b->d_model, sizeof(DevModel)));
   HIPCHK_C(hipMemcpy(b->d_model, hm, sizeof(DevModel), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(hrg_model_constants_kernel, dim3(1), dim3(64), 0, 0, b->d_model);   // fric_*, eul_*, rcap_mid: in the device's own arithmetic
+  HIPCHK_C(hipGetLastError());
+  HIPCHK_C(hipDeviceSynchronize());
   if (b->d_pose) {
     hipLaunchKernelGGL(hrg_pose_table_kernel, dim3((unsigned)clips->total_frames), dim3(64), 0, 0, b->d_model, b->d_pose);
     HIPCHK_C(hipGetLastError());
@@ -3680,6 +3758,16 @@ int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* ou
     hipLaunchKernelGGL(hrg_wave_helpers_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (unsigned long long)lane_mask, (double*)d[1]);
   });
   return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_wave_helpers: device allocation / copy / launch failed");
+}
+
+int hrg_debug_model_constants(hrg_batch* b, double* out_host) {
+  if (!b || !out_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(b->device));
+  const bool ok = hrg_run_tap(nullptr, 0, out_host, sizeof(double) * 2 * HRG_MC_DIM, [&](void** d) {
+    hipMemset(d[0], 0, sizeof(double) * 2 * HRG_MC_DIM);
+    hipLaunchKernelGGL(hrg_model_constants_tap_kernel, dim3(1), dim3(64), 0, 0, b->d_model, 0.0, (double*)d[0]);
+  });
+  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_model_constants: device allocation / copy / launch failed");
 }
 
 int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {

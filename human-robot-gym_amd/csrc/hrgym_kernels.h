@@ -349,6 +349,17 @@ DI void human_root(ModelPtr dm, int clip, const double* fr, double* c, double* q
   qa[0] = fr[6]; qa[1] = fr[3]; qa[2] = fr[4]; qa[3] = fr[5];
 }
 
+#if HRG_POSE_TABLE
+// L.hyaw <- the rotation matrix of the episode's yaw.  human_rot_offset changes at a reset only, so its nine entries are computed where it may have changed -- at the
+// start of an env_step (the state block has just arrived) and in env_reset -- instead of in every cycle.  Wave-uniform: every lane stores the same values.
+DI void human_yaw_update() {
+  Lds& L = g_L;
+  double R[9];
+  quat2mat(R, L.st.human_rot_offset);
+  for (int a = 0; a < 9; a++) L.hyaw[a] = R[a];
+  wave_sync();
+}
+
 // pose of the human from pose table entry f (DevModel::pose_tab, hrg_pose_table_kernel): every capsule end point and site is
 // x = human_pos_offset + c + R(human_rot_offset) Y, where (Y, c) = the entry's points (the tree kinematics under pelvis position 0 and rotation qbi qa) and
 // root term.  Lanes 0..23 take one capsule, lanes 24..46 one site -> L.hcap, human_site
@@ -369,7 +380,7 @@ DI void human_pose_from_table(ModelPtr dm, int lane, int64_t f) {
   // the root term: wave-uniform, through the scalar cache
   const double __attribute__((address_space(4)))* ec = (const double __attribute__((address_space(4)))*)(e + HRG_POSE_ROOT);
   double R[9], o[3], x[3];
-  quat2mat(R, s.human_rot_offset);
+  for (int a = 0; a < 9; a++) R[a] = L.hyaw[a];   // quat2mat(human_rot_offset): human_yaw_update
   v3add(o, s.human_pos_offset, ec);
   m3mulv(x, R, y);
   if (cap) {
@@ -379,6 +390,7 @@ DI void human_pose_from_table(ModelPtr dm, int lane, int64_t f) {
   } else if (site) v3add(L.st.human_site[lane - HRG_NHB], o, x);
   wave_sync();
 }
+#endif
 
 // pose of the human at frame `at` of clip `clip`: root pose chain (human_env.py:1736-1763) + tree kinematics -> L.hcap, human_site
 DI void human_pose_fk(const DevModel* __restrict__ dm_, int lane, int clip, int at, int hold_body = -1, int hold_left = 0) {
@@ -1358,15 +1370,12 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
   const auto& m = dm->m;
   if (lane < HRG_NRCAP) {
     const int c = lane, b = m.rcap_body[c];
-    double R[9], p[3], t[3], mid[3];
+    double R[9], p[3], t[3];
     if (b < 0) { for (int a = 0; a < 9; a++) R[a] = dm->Rbase[a]; v3cpy(p, m.base_pos); }
     else { for (int a = 0; a < 9; a++) R[a] = L.kR[b][a]; v3cpy(p, L.kp[b]); }
     m3mulv(t, R, m.rcap_p1[c]); v3add(&L.rcapw[c][0], p, t);
     m3mulv(t, R, m.rcap_p2[c]); v3add(&L.rcapw[c][3], p, t);
-    for (int a = 0; a < 3; a++) mid[a] = 0.5 * (m.rcap_p1[c][a] + m.rcap_p2[c][a]);
-    m3mulv(t, R, mid);
-    v3add(L.rcen[c], p, t);
-  }
+  }   // (the capsule's centre is computed by classify, for the one capsule whose speed it asks for)
   wave_sync();
   // Cull of the 240 robot-human pairs: the box around all robot capsules, each inflated by its radius and the human contact margin, against the bounding sphere
   // of every human capsule.  A human capsule whose sphere misses the box cannot be in contact with any robot capsule (conservative); the capsules that come near
@@ -1766,8 +1775,14 @@ PH_CLASSIFY void classify(const DevModel* __restrict__ dm_, int lane, int ncon, 
   if (human_counts) {
     const int first = __ffsll((long long)m_hu) - 1;
     if (lane == first) {
-      double v[3];
-      robot_point_vel(m.rcap_body[rg], L.rcen[rg], v);
+      // world centre of robot capsule rg: the body's pose of this cycle (kR / kp live across the whole cycle) applied to the capsule's mid point, a constant of the model
+      const int b = m.rcap_body[rg];
+      double R[9], p[3], t[3], cen[3], v[3];
+      if (b < 0) { for (int a = 0; a < 9; a++) R[a] = dm->Rbase[a]; v3cpy(p, m.base_pos); }
+      else { for (int a = 0; a < 9; a++) R[a] = L.kR[b][a]; v3cpy(p, L.kp[b]); }
+      m3mulv(t, R, dm->rcap_mid[rg]);
+      v3add(cen, p, t);
+      robot_point_vel(b, cen, v);
       crit = !(v3norm(v) <= m.safe_vel);
     }
     crit = __any(crit);

@@ -685,6 +685,16 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
  * 0 / -1. */
 enum { HRG_WAVE_NOUT = 22 /* rows of out_host */ };
 int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* out_host);
+/* test tap of the model constants that hrg_batch_create has the device precompute (expressions the step kernels evaluated in every substep before): out_host[2][HRG_MC_DIM],
+ * [0] = the stored entries as the kernels read them, [1] = the same values as one wavefront computes them now from the kernels' own expressions, the friction rows' zero
+ * position term passed in at run time so that the impedance code runs as in a substep.  Must be equal bit for bit.  Columns: HRG_MC_FRIC_D, HRG_MC_FRIC_LIM,
+ * HRG_MC_FRIC_IMP: D, the limit floss / D and the impedance ([0]: solimp[0]) of the HRG_NV friction-loss rows and of the nail's slide joint (hammering); 0 for a dof
+ * without friction loss.  HRG_MC_EUL_HD, HRG_MC_EUL_RHD, HRG_MC_EUL_FINGERS: the implicit joint damping of the integrator, h * damping of the HRG_NV joints, its
+ * reciprocal for the two fingers, and whether both fingers are damped (1 / 0).  HRG_MC_RCAP_MID: the mid point of each of the HRG_NRCAP robot collision capsules in its
+ * body's frame, [capsule][3].  0 / -1. */
+enum { HRG_MC_FRIC_D = 0, HRG_MC_FRIC_LIM = HRG_NV + 1, HRG_MC_FRIC_IMP = 2 * (HRG_NV + 1), HRG_MC_EUL_HD = 3 * (HRG_NV + 1), HRG_MC_EUL_RHD = HRG_MC_EUL_HD + HRG_NV,
+       HRG_MC_EUL_FINGERS = HRG_MC_EUL_RHD + 2, HRG_MC_RCAP_MID = HRG_MC_EUL_FINGERS + 1, HRG_MC_DIM = HRG_MC_RCAP_MID + 3 * HRG_NRCAP };
+int hrg_debug_model_constants(hrg_batch* b, double* out_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the
