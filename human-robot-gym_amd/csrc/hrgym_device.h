@@ -188,11 +188,12 @@ struct DevModel {
   double brake_T, brake_ds;
   // human reach capsule table (one entry per lane): kind 0 ACC, 1 VEL, 2 POS ball, 3 POS part
   int32_t hc_n;
-  int32_t hc_kind[HRG_NHCAP_MAX], hc_j1[HRG_NHCAP_MAX], hc_j2[HRG_NHCAP_MAX];
-  double hc_th[HRG_NHCAP_MAX], hc_v[HRG_NHCAP_MAX], hc_a[HRG_NHCAP_MAX], hc_len[HRG_NHCAP_MAX];
-  // robot self-collision candidate pairs in enumeration order
+  // One 32-byte record per capsule: the lane fetches its values with two 16-byte loads from one address instead of seven loads from seven.  th: thickness, v: v_max,
+  // al: a_max (ACC) or the ball's length (POS ball; no kind reads both), kj = kind | joint 1 << 8 | joint 2 << 16
+  struct alignas(32) HcRec { double th, v, al; int32_t kj, pad; } hc[HRG_NHCAP_MAX];
+  // robot self-collision candidate pairs (i, j) in enumeration order
   int32_t n_self;
-  int32_t self_i[64], self_j[64];
+  struct alignas(8) SelfPair { int32_t i, j; } self_ij[64];
   // pre-check model pairs (capsules 0..6 + gripper cylinder)
   int32_t n_chk;
   int32_t chk_i[32], chk_j[32];
@@ -1013,6 +1014,29 @@ DI double lane_value(double v) {
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffLL), K);
   const int hi = __builtin_amdgcn_readlane((int)(b >> 32), K);
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// Box around up to 16 capsules, each inflated by its own radius, for the culls of collide and shield_step: lo[3], hi[3], the same in every lane.  Lane l serves
+// capsule c = l & 15 and quantity g = l >> 4, so the four DPP rows reduce four of the six bounds at once: the first row16_max carries hi_x, -lo_x, hi_y, -lo_y in
+// rows 0..3, the second hi_z, -lo_z in rows 0, 1 (rows 2, 3 idle).  `cap`: the lane's capsule c, p1[3] p2[3] (read only with `has`); `rr`: its radius; `has`: c is
+// a capsule.  A lane computes its own bound alone: max(p1, p2) + rr, or -(min(p1, p2) - rr) = max(-p1, -p2) + rr (a negation is exact, and rounding is symmetric);
+// a lane without a capsule holds -1e300.  A maximum does not depend on the order it is taken in, so the bounds are the doubles of one reduction per bound over the
+// lanes 0..15; only the sign of a bound that is zero may differ (max_f64).
+DI void cull_box(const double* cap, double rr, bool has, int lane, double* lo, double* hi) {
+  const int g = lane >> 4;
+  const long long flip = (long long)(g & 1) << 63;   // the odd rows reduce the negated coordinates
+  double e1 = -1e300, e2 = -1e300;
+  if (has) {
+    const int a = g >> 1;
+    const double p1 = __longlong_as_double(__double_as_longlong(cap[a]) ^ flip), p2 = __longlong_as_double(__double_as_longlong(cap[3 + a]) ^ flip);
+    e1 = max_f64(p1, p2) + rr;
+    if (g < 2) {
+      const double z1 = __longlong_as_double(__double_as_longlong(cap[2]) ^ flip), z2 = __longlong_as_double(__double_as_longlong(cap[5]) ^ flip);
+      e2 = max_f64(z1, z2) + rr;
+    }
+  }
+  e1 = row16_max(e1); e2 = row16_max(e2);
+  hi[0] = lane_value<0>(e1); lo[0] = -lane_value<16>(e1); hi[1] = lane_value<32>(e1); lo[1] = -lane_value<48>(e1);
+  hi[2] = lane_value<0>(e2); lo[2] = -lane_value<16>(e2);
 }
 // Inverse of a symmetric positive definite 8x8 matrix across the wave: in-place Gauss-Jordan sweeps, lane (i,j) owns entry (i,j), three shuffles and one reciprocal
 // per pivot -- the cost of a factorisation, but what comes out turns every later solve with the matrix (unconstrained acceleration, the Newton direction while no

@@ -1577,7 +1577,14 @@ PH_DYNSTEP int dynamics_step(const DevModel* __restrict__ dm_, int lane, int nco
       }
 #endif
       STAMP(25);
+#if HRG_BOX
       const double dMd = wave_sum(dd * Mdi), gd0 = wave_sum(dd * gm);
+#else
+      // the addends are +0.0 in every lane >= NV: the first three steps of wave_sum are row8_sum, and the other three add +0.0 to the total of lanes 0..7, which changes
+      // it only when it is -0.0.  The sum of the first row of eight, read from lane 0, + 0.0 is the same double.
+      static_assert(NV == 8, "the robot's dof fill one row of eight lanes");
+      const double dMd = lane_value<0>(row8_sum(dd * Mdi)) + 0.0, gd0 = lane_value<0>(row8_sum(dd * gm)) + 0.0;
+#endif
       double al = 1.0, lo = 0, hi = -1;
       const double d1_0 = gd0 + wave_sum(gg * p);
       const double noise = fabs(gd0) + dMd + wave_sum(fabs(gg * p));   // magnitude of the terms phi' is summed from
@@ -3085,6 +3092,16 @@ __global__ __launch_bounds__(64) void hrg_wave_helpers_kernel(const double* __re
   }
 }
 
+// test tap (hrg_debug_cull_box): cull_box as collide and shield_step call it, one wave over n <= 16 capsules in[c] = p1[3] p2[3] r.  out[6] = lo[3] hi[3].
+__global__ __launch_bounds__(64) void hrg_cull_box_kernel(const double* __restrict__ in, int n, double* __restrict__ out) {
+  const int lane = hrg_lane();
+  const bool has = (lane & 15) < n;
+  const int c = has ? lane & 15 : 0;
+  double lo[3], hi[3];
+  cull_box(in + 7 * c, in[7 * c + 6], has, lane, lo, hi);
+  if (lane == 0) for (int a = 0; a < 3; a++) { out[a] = lo[a]; out[3 + a] = hi[a]; }
+}
+
 // The model constants of DevModel that are expressions a substep (or cycle) used to evaluate (fric_*, eul_*, rcap_mid): one wave, launched once at batch create when the model is on
 // the device.  model_constants is those expressions as the step kernels hold them (row_D is the steppers' own), for one lane's share; x0 = the position term of a
 // friction row, 0.  The test tap (hrg_debug_model_constants) runs it again with x0 from a kernel argument, so that impedance() runs as it did in a substep instead of
@@ -3602,13 +3619,20 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   hm->hb_njump = 0;
   while ((1 << hm->hb_njump) < maxd + 1) hm->hb_njump++;
   int n = 0;
-  for (int k = 0; k < desc->n_bodypart; k++, n++) { hm->hc_kind[n] = 0; hm->hc_j1[n] = desc->bp_joint[k][0]; hm->hc_j2[n] = desc->bp_joint[k][1]; hm->hc_th[n] = desc->bp_thickness[k]; hm->hc_a[n] = desc->bp_amax[k]; hm->hc_v[n] = desc->bp_vmax[k]; }
-  for (int k = 0; k < desc->n_bodypart; k++, n++) { hm->hc_kind[n] = 1; hm->hc_j1[n] = desc->bp_joint[k][0]; hm->hc_j2[n] = desc->bp_joint[k][1]; hm->hc_th[n] = desc->bp_thickness[k]; hm->hc_v[n] = desc->bp_vmax[k]; }
-  for (int k = 0; k < desc->n_extremity; k++, n++) { hm->hc_kind[n] = 2; hm->hc_j1[n] = desc->ext_joint[k]; hm->hc_j2[n] = desc->ext_joint[k]; hm->hc_th[n] = desc->ext_thickness[k]; hm->hc_v[n] = desc->ext_vmax[k]; hm->hc_len[n] = desc->ext_length[k]; }
+  // (kind, joints, thickness, v_max, a_max or ball length) of reach capsule n as the record the shield's lanes load
+  auto hc_set = [&](int n, int kind, int j1, int j2, double th, double v, double al) { hm->hc[n].th = th; hm->hc[n].v = v; hm->hc[n].al = al; hm->hc[n].kj = kind | (j1 << 8) | (j2 << 16); hm->hc[n].pad = 0; };
+  for (int k = 0; k < desc->n_bodypart; k++)
+    if (desc->bp_joint[k][0] < 0 || desc->bp_joint[k][0] >= HRG_NHJ || desc->bp_joint[k][1] < 0 || desc->bp_joint[k][1] >= HRG_NHJ) { return bail(HRG_ERR_INVALID, "body part joint outside the human's sites"); }
+  for (int k = 0; k < desc->n_extremity; k++)
+    if (desc->ext_joint[k] < 0 || desc->ext_joint[k] >= HRG_NHJ) { return bail(HRG_ERR_INVALID, "extremity joint outside the human's sites"); }
+  if (2 * desc->n_bodypart + desc->n_extremity > HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
+  for (int k = 0; k < desc->n_bodypart; k++, n++) hc_set(n, 0, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], desc->bp_amax[k]);
+  for (int k = 0; k < desc->n_bodypart; k++, n++) hc_set(n, 1, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], 0.0);
+  for (int k = 0; k < desc->n_extremity; k++, n++) hc_set(n, 2, desc->ext_joint[k], desc->ext_joint[k], desc->ext_thickness[k], desc->ext_vmax[k], desc->ext_length[k]);
   for (int k = 0; k < desc->n_bodypart; k++) {
     if (!desc->bp_in_pos[k]) continue;
     if (n >= HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
-    hm->hc_kind[n] = 3; hm->hc_j1[n] = desc->bp_joint[k][0]; hm->hc_j2[n] = desc->bp_joint[k][1]; hm->hc_th[n] = desc->bp_thickness[k]; hm->hc_v[n] = desc->bp_vmax[k];
+    hc_set(n, 3, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], 0.0);
     n++;
   }
   if (n > HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
@@ -3616,7 +3640,7 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   int ns = 0;
   for (int i = 0; i < HRG_NRCAP; i++)
     for (int j = i + 1; j < HRG_NRCAP; j++)
-      if ((desc->rcap_selfmask[i] >> j) & 1u) { hm->self_i[ns] = i; hm->self_j[ns] = j; ns++; }
+      if ((desc->rcap_selfmask[i] >> j) & 1u) { hm->self_ij[ns].i = i; hm->self_ij[ns].j = j; ns++; }
   hm->n_self = ns;
   int nc = 0;
   for (int i = 0; i < 8; i++)
@@ -3758,6 +3782,15 @@ int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* ou
     hipLaunchKernelGGL(hrg_wave_helpers_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (unsigned long long)lane_mask, (double*)d[1]);
   });
   return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_wave_helpers: device allocation / copy / launch failed");
+}
+
+int hrg_debug_cull_box(const double* in_host, int32_t n, double* out_host) {
+  if (!in_host || !out_host || n < 1 || n > 16) return fail(HRG_ERR_INVALID, "null argument or n outside 1..16");
+  const TapBuf in[] = {{in_host, sizeof(double) * 16 * 7}};
+  const bool ok = hrg_run_tap(in, 1, out_host, sizeof(double) * 6, [&](void** d) {
+    hipLaunchKernelGGL(hrg_cull_box_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (int)n, (double*)d[1]);
+  });
+  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_cull_box: device allocation / copy / launch failed");
 }
 
 int hrg_debug_model_constants(hrg_batch* b, double* out_host) {

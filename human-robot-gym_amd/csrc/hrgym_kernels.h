@@ -681,12 +681,9 @@ PH_SHIELD void shield_step(const DevModel* __restrict__ dm_, int lane, int e, do
     wave_sync();
     double rbl[3], rbh[3];   // box around the robot reach capsules (each inflated by its radius), the same in every lane
     {
-      double bl[3], bh[3];
-      if (lane < HRG_NSHIELD_RCAP) {
-        const double rr = L.rc[lane][6];
-        for (int a = 0; a < 3; a++) { const double p1 = L.rc[lane][a], p2 = L.rc[lane][3 + a]; bl[a] = (p1 < p2 ? p1 : p2) - rr; bh[a] = (p1 > p2 ? p1 : p2) + rr; }
-      } else for (int a = 0; a < 3; a++) { bl[a] = 1e300; bh[a] = -1e300; }
-      for (int a = 0; a < 3; a++) { rbh[a] = lane_value<0>(row16_max(bh[a])); rbl[a] = -lane_value<0>(row16_max(-bl[a])); }
+      const bool has = (lane & 15) < HRG_NSHIELD_RCAP;
+      const int c = has ? lane & 15 : 0;
+      cull_box(&L.rc[c][0], L.rc[c][6], has, lane, rbl, rbh);
     }
     // lanes = human reach capsules
     const int nh = dm->hc_n;
@@ -694,7 +691,8 @@ PH_SHIELD void shield_step(const DevModel* __restrict__ dm_, int lane, int e, do
     double c1[3] = {0, 0, 0}, c2[3] = {0, 0, 0}, r = 0, hc[3] = {0, 0, 0}, hl = 0;
     bool near_robot = false;
     if (lane < nh) {
-      const int kind = dm->hc_kind[lane], j1 = dm->hc_j1[lane], j2 = dm->hc_j2[lane];
+      const struct { double th, v, al; int kj; } rec = {dm->hc[lane].th, dm->hc[lane].v, dm->hc[lane].al, dm->hc[lane].kj};   // adjacent fields of one record: two 16-byte loads
+      const int kind = rec.kj & 0xff, j1 = (rec.kj >> 8) & 0xff, j2 = rec.kj >> 16;
       const double Td = dt + Tb + m.delay;
       if (kind == 0) {
         double va[3], vb[3];
@@ -703,21 +701,21 @@ PH_SHIELD void shield_step(const DevModel* __restrict__ dm_, int lane, int e, do
           va[a] = (s.human_site[j1][a] - s.meas_prev[j1][a]) * idt;   // finite-difference velocity: one reciprocal, six products
           vb[a] = (s.human_site[j2][a] - s.meas_prev[j2][a]) * idt;
         }
-        const double base = 0.5 * dm->hc_a[lane] * Td * Td + m.meas_err_pos + m.meas_err_vel * Td;
+        const double base = 0.5 * rec.al * Td * Td + m.meas_err_pos + m.meas_err_vel * Td;
         const double r1 = v3norm(va) * Td * 0.5 + base, r2 = v3norm(vb) * Td * 0.5 + base;
         v3madd(c1, s.human_site[j1], va, 0.5 * Td);
         v3madd(c2, s.human_site[j2], vb, 0.5 * Td);
-        r = (r1 > r2 ? r1 : r2) + dm->hc_th[lane];
+        r = (r1 > r2 ? r1 : r2) + rec.th;
         mdl = 0;
       } else if (kind == 2) {
         v3cpy(c1, s.human_site[j1]);
         v3cpy(c2, s.human_site[j1]);
-        r = dm->hc_len[lane] + dm->hc_th[lane] + m.meas_err_pos + dm->hc_v[lane] * Td;
+        r = rec.al + rec.th + m.meas_err_pos + rec.v * Td;
         mdl = 2;
       } else {
         v3cpy(c1, s.human_site[j1]);
         v3cpy(c2, s.human_site[j2]);
-        r = dm->hc_th[lane] + m.meas_err_pos + dm->hc_v[lane] * Td;
+        r = rec.th + m.meas_err_pos + rec.v * Td;
         mdl = kind == 1 ? 1 : 2;
       }
       double hh[3];
@@ -1384,20 +1382,18 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
   // order (robot capsule major, human capsule minor), so the contact list is the one of the full enumeration.
   int n_hnear;
   {
-    double bl[3], bh[3];
-    if (lane < HRG_NRCAP) {
-      const double rr = m.rcap_r[lane] + m.contact_margin_human + 1e-9;
-      for (int a = 0; a < 3; a++) {
-        const double p1 = L.rcapw[lane][a], p2 = L.rcapw[lane][3 + a];
-        bl[a] = (p1 < p2 ? p1 : p2) - rr; bh[a] = (p1 > p2 ? p1 : p2) + rr;
-      }
-    } else for (int a = 0; a < 3; a++) { bl[a] = 1e300; bh[a] = -1e300; }
+    static_assert(HRG_NRCAP <= 16 && HRG_NSHIELD_RCAP <= 16, "cull_box: one DPP row of capsules");
+    double lo[3], hi[3];
+    {
+      const bool has = (lane & 15) < HRG_NRCAP;
+      const int rc = has ? lane & 15 : 0;
+      cull_box(&L.rcapw[rc][0], m.rcap_r[rc] + m.contact_margin_human + 1e-9, has, lane, lo, hi);
+    }
     double d2 = 0;
     const int hb = lane < HRG_NHB ? lane : 0;
     for (int a = 0; a < 3; a++) {
-      const double hi = lane_value<0>(row16_max(bh[a])), lo = -lane_value<0>(row16_max(-bl[a]));
       const double c = 0.5 * (L.hcap[hb][a] + L.hcap[hb][3 + a]);
-      const double e = c < lo ? lo - c : (c > hi ? c - hi : 0.0);
+      const double e = c < lo[a] ? lo[a] - c : (c > hi[a] ? c - hi[a] : 0.0);
       d2 += e * e;
     }
     const double rad = dm->hcap_hl[hb] + m.hcap_r[hb] + 1e-9;
@@ -1424,8 +1420,9 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
       bool valid;
       if (round == 0) {
         valid = lane < dm->n_self;
-        i = valid ? dm->self_i[lane] : 0;
-        const int j = valid ? dm->self_j[lane] : 1;
+        const int sl = valid ? lane : 0;
+        i = valid ? dm->self_ij[sl].i : 0;
+        const int j = valid ? dm->self_ij[sl].j : 1;
         g2 = j; a1 = &L.rcapw[j][0]; a2 = &L.rcapw[j][3]; r2 = m.rcap_r[j]; hl2 = dm->rcap_hl[j];
         c.b2 = m.rcap_body[j];
       } else {

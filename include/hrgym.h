@@ -685,6 +685,9 @@ int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, do
  * 0 / -1. */
 enum { HRG_WAVE_NOUT = 22 /* rows of out_host */ };
 int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* out_host);
+/* test tap of the cull box of collide and shield_step (csrc/hrgym_device.h, cull_box): one wavefront over the first n (1..16) of in_host[16][7], a capsule each as
+ * p1[3] p2[3] radius (all 16 rows are copied; the rows >= n are not read) -> out_host[6] = lo[3] hi[3] of the box around the capsules, each inflated by its radius.  0 / -1. */
+int hrg_debug_cull_box(const double* in_host, int32_t n, double* out_host);
 /* test tap of the model constants that hrg_batch_create has the device precompute (expressions the step kernels evaluated in every substep before): out_host[2][HRG_MC_DIM],
  * [0] = the stored entries as the kernels read them, [1] = the same values as one wavefront computes them now from the kernels' own expressions, the friction rows' zero
  * position term passed in at run time so that the impedance code runs as in a substep.  Must be equal bit for bit.  Columns: HRG_MC_FRIC_D, HRG_MC_FRIC_LIM,

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Static mix of the vector (v_*) instructions of one kernel of the gfx950 code object, by class (tuning aid; needs no GPU):
-    python tools/valu_mix.py [UNIT.hip] [KERNEL] [-D... extra compiler flags]
+    python tools/valu_mix.py [UNIT.hip] [KERNEL] [--zeros] [-D... extra compiler flags]
+--zeros: instead of the mix, the zero-materialising moves (v_mov_b32 / v_mov_b64 of the constant 0) per source line, from a build with -gline-tables-only.
 UNIT.hip: one of the library's translation units by file name (_lib.SOURCES; default: the base one, hrgym_hip.hip); KERNEL: a function of that unit by its name
 without the parameter list, or by its symbol (default: hrg_step_kernel).  The unit is compiled with the flags of _lib.build_library.  A static count: every instruction of the function once,
 whether it sits on the always-executed path or in a cold branch; s_nop is counted next to it because the DPP and lane-access hazards pad with it."""
@@ -56,8 +57,30 @@ def mix(body):
     return by_class, by_op, nops
 
 
+def zero_moves(body, files):
+    """Counter {(file name, line): zero-materialising moves (v_mov_b32 / v_mov_b64 of the constant 0 into a vector register)} of an assembly text that carries
+    .loc directives (-gline-tables-only); `files`: {number: name} of the .file table."""
+    at, out = ("?", 0), collections.Counter()
+    for line in body.splitlines():
+        m = re.match(r"\s*\.loc\s+(\d+)\s+(\d+)", line)
+        if m:
+            at = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+        elif re.match(r"\s*v_mov_b(32|64)(_e32|_e64)?\s+v\S*,\s*0\s*(;.*)?$", line):
+            out[at] += 1
+    return out
+
+
+def file_table(asm):
+    """{number: base name} of the .file directives."""
+    return {int(n): os.path.basename(name) for n, name in re.findall(r'^\s*\.file\s+(\d+)\s+(?:"[^"]*"\s+)?"([^"]*)"', asm, re.M)}
+
+
 def main(argv):
     args = list(argv)
+    zeros = "--zeros" in args
+    if zeros:
+        args.remove("--zeros")
+        args.append("-gline-tables-only")
     src = _lib.SRC
     if args and args[0].endswith(".hip"):
         src = {os.path.basename(s): s for s in _lib.SOURCES}[os.path.basename(args.pop(0))]
@@ -65,7 +88,14 @@ def main(argv):
     d = tempfile.mkdtemp()
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "-save-temps", "-Wno-unused-value", "-Xarch_device", "-fapprox-func", "-mllvm", "-disable-machine-licm",
                     *args, "-o", "t.o", src], cwd=d, stderr=subprocess.DEVNULL, check=True)
-    by_class, by_op, nops = mix(kernel_body(open(glob.glob(d + "/*gfx950*.s")[0]).read(), kernel))
+    asm = open(glob.glob(d + "/*gfx950*.s")[0]).read()
+    if zeros:
+        z = zero_moves(kernel_body(asm, kernel), file_table(asm))
+        print("%s of %s: zero-materialising moves (v_mov_b32 / v_mov_b64 v, 0) by source line (static): %d" % (kernel, os.path.basename(src), sum(z.values())))
+        for (f, ln), n in sorted(z.items()):
+            print("  %-22s %5d  %4d" % (f, ln, n))
+        return
+    by_class, by_op, nops = mix(kernel_body(asm, kernel))
     print("%s of %s: v_* instructions by class (static)" % (kernel, os.path.basename(src)))
     for c in CLASSES:
         print("  %-18s %6d" % (c, by_class[c]))
