@@ -5,6 +5,7 @@
 #define HRG_BOX 1
 #define HRG_HULLS 1
 #include "hrgym_hip.hip"
+#include "hrgym_host.h"   // hrg_run_tap, hull_centroids
 
 // ---- test tap (include/hrgym.h: hrg_test_hull_box_queries): the MPR wave routine on its own, one query per wavefront -- tests/test_hull_box*.py compare it with
 // a numpy restatement.  Link pose and the cube go through LDS as in the step kernel (kR / kp, bR / bx.pos).

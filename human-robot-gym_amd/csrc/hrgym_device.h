@@ -43,9 +43,9 @@
 #ifndef HRG_HAMMER
 #define HRG_HAMMER 0  // HRG_HAMMER=1 (hrgym_hammer.hip, HRG_BOX=0): CollaborativeHammeringCart -- board + nail + hammer, a 24-DoF system in three 8-wide blocks; its own collision tail and solver
 #endif
-#define HRG_BASE_TU (!HRG_BOX && !HRG_STACK && !HRG_HAMMER && !HRG_HULLS)   // hrgym_hip.hip itself: the ReachHuman kernels, the pre-check kernel and the host side (C ABI)
+#define HRG_BASE_TU (!HRG_BOX && !HRG_STACK && !HRG_HAMMER && !HRG_HULLS)   // hrgym_hip.hip itself: the ReachHuman kernels, the pre-check kernel and the host side (C ABI: hrgym_host*.h)
 // The name of this translation unit's kernel variant: <stem><family><hull>, family = the task's kernel family, hull = the arm links' collision geometry.  HRG_SYM names
-// the kernels (hrg_step_kernel_lift_hull), their launch shims and the -DHRG_STAMPS exports; the host side lists the twelve combinations once (HRG_VARIANTS, hrgym_hip.hip).
+// the kernels (hrg_step_kernel_lift_hull), their launch shims and the -DHRG_STAMPS exports; the host side lists the twelve combinations once (HRG_VARIANTS, hrgym_host_batch.h).
 #if HRG_HAMMER
 #define HRG_FAMILY_SFX _hammer
 #elif HRG_STACK
@@ -212,31 +212,6 @@ struct DevModel {
   int32_t eul_fingers, eul_pad;              // fingers, 0 unless both are damped (eul_fingers: the Woodbury term is in)
   double rcap_mid[HRG_NRCAP][3];             // mid point 0.5 (p1 + p2) of each robot collision capsule, body frame (classify: the speed of a robot geom at a human contact)
 };
-
-// vertex centroid of each hull (body frame): the interior point MPR starts from (hrg_batch_create, hrg_test_hull_box_queries)
-static inline void hull_centroids(const double* verts, const int32_t* off, double cen[HRG_NHULL][3]) {
-  for (int h = 0; h < HRG_NHULL; h++) {
-    double s[3] = {0, 0, 0};
-    for (int i = off[h]; i < off[h + 1]; i++) for (int a = 0; a < 3; a++) s[a] += verts[3 * i + a];
-    for (int a = 0; a < 3; a++) cen[h][a] = s[a] / (double)(off[h + 1] - off[h]);
-  }
-}
-
-// host side of a test tap (hrg_test_hull_queries, hrg_test_hull_box_queries, hrg_debug_pose_compare): the n_in host buffers copied to the device, one launch, the
-// output copied back.  launch(d) gets the device buffers, d[0 .. n_in - 1] the inputs in order and d[n_in] the output; all of them are freed on every path.
-struct TapBuf { const void* host; size_t bytes; };
-template <class Launch>
-static bool hrg_run_tap(const TapBuf* in, int n_in, void* out_host, size_t out_bytes, Launch launch) {
-  void* d[8] = {nullptr};
-  bool ok = n_in < 8;
-  for (int i = 0; ok && i < n_in; i++) ok = hipMalloc(&d[i], in[i].bytes) == hipSuccess && hipMemcpy(d[i], in[i].host, in[i].bytes, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && hipMalloc(&d[n_in], out_bytes) == hipSuccess) {
-    launch(d);
-    ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(out_host, d[n_in], out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
-  } else ok = false;
-  for (int i = 0; i < 8; i++) hipFree(d[i]);
-  return ok;
-}
 
 struct Contact {
   int32_t g1, g2, b1, b2;

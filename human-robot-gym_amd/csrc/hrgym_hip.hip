@@ -1,4 +1,5 @@
-// hrgym_hip.hip — step/reset kernels and the extern "C" ABI of libhrgym_hip.so (include/hrgym.h).
+// hrgym_hip.hip — the stepper: step/reset kernels of every variant; the base translation unit also compiles the extern "C" ABI of libhrgym_hip.so (include/hrgym.h)
+// from the host files at the end (hrgym_host*.h).
 // One 64-lane wavefront per environment; see hrgym_device.h for the lane-role map.
 #include <hip/hip_runtime.h>
 
@@ -3163,7 +3164,7 @@ __global__ __launch_bounds__(64) void hrg_model_constants_tap_kernel(const DevMo
 #endif
 
 // Launch shims: every translation unit defines this pair for its own kernels, under the variant's name and with hidden visibility; the host side (the base
-// translation unit) reaches them through its variant table (HRG_VARIANTS).  objs = the variant's object array (ObjState), null for the ReachHuman kernels.
+// translation unit) reaches them through its variant table (HRG_VARIANTS, hrgym_host_batch.h).  objs = the variant's object array (ObjState), null for the ReachHuman kernels.
 typedef void hrg_launch_step_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
                                 int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, void* objs, StepOrder ord);
 typedef void hrg_launch_reset_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, void* objs);
@@ -3215,1821 +3216,8 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_eval.h"     // evaluation of deterministic policies: begin / step (the episode ledger) / remaining / fused actor kernels (hrg_eval_*)
 
 // ================================================================================================ host side
-static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIPCHK(x)                                                                                         \
-  do {                                                                                                    \
-    hipError_t _e = (x);                                                                                  \
-    if (_e != hipSuccess) return fail(HRG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e));        \
-  } while (0)
-
-struct hrg_batch {
-  int device = 0;
-  int32_t n_envs = 0;
-  int64_t env_id0 = 0;
-  DevModel* d_model = nullptr;
-  double* d_frames = nullptr;
-  double* d_pose = nullptr;            // per-frame human pose table (DevModel::pose_tab): the tasks whose kernels read it (hrg_task_uses_pose_table)
-  size_t pose_bytes = 0;
-  double* d_hull = nullptr;            // hull vertices of the arm links (robot_hulls)
-  bool hulls = false;                  // a hull variant steps this batch: of the ReachHuman kernels (hrgym_hulls.hip), the cube kernels (hrgym_box_hulls.hip) or a task's own (hrgym_*_hulls.hip)
-  unsigned long long* d_mpr_fallback = nullptr;   // hull - cube pairs whose MPR did not converge (DevModel::mpr_fallback; hrg_batch_mpr_fallbacks)
-  hrg_env_state* d_states = nullptr;
-  double* d_rcaps = nullptr;
-  double* d_hcaps = nullptr;
-  int32_t* d_nh = nullptr;
-  float* d_scratch_obs = nullptr;
-  hrg_box_state* d_boxes = nullptr;   // the manipulation object of each env (PickPlaceHumanCart)
-  hrg_stack_state* d_stacks = nullptr; // the four cubes of each env (CollaborativeStackingCart)
-  hrg_hammer_state* d_hammers = nullptr; // board, hammer, nail of each env (CollaborativeHammeringCart)
-  int32_t* d_order = nullptr;          // launch order of the step kernel (StepOrder): two orders of n_envs + two pairs of counters
-  int32_t parity = 0;                  // which of the two orders the next step launch reads
-  int32_t task = HRG_TASK_REACH;
-  bool ik = false;                     // the Cartesian action front-end is on: action rows are [dx, dy, dz, gripper, -, -, -]
-  bool has_expert = false;             // hrg_batch_expert_attach
-  hrg_expert_desc expert;              // the attached expert (a kernel argument of the two expert kernels)
-  ExpertBuffers ex;
-  bool has_dataset = false;            // hrg_batch_dataset_attach
-  hrg_dataset_desc dataset;            // the attached dataset's parameters (a kernel argument of the two dataset kernels; its host pointers are nulled)
-  DatasetDev ds;
-  bool timing = false;
-  bool taps = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
-};
-
-static void dataset_free(hrg_batch* b) {
-  DatasetDev& d = b->ds;
-  hipFree((void*)d.ep_offset); hipFree((void*)d.states); hipFree((void*)d.boxes); hipFree((void*)d.obs); hipFree(d.cursor); hipFree(d.resets); hipFree(d.acc); hipFree(d.finished);
-  d = DatasetDev{};
-}
-
-// the progress table of the level-waves priority (StepOrder.fair): one per device, shared by the batches and kernel variants that run on it; never freed
-static int32_t* fair_table(int device) {
-  static int32_t* tab[64] = {nullptr};
-  if (device < 0 || device >= 64) return nullptr;
-  if (!tab[device]) {
-    int32_t* p = nullptr;
-    if (hipMalloc(&p, sizeof(int32_t) * HRG_FAIR_SLOTS) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, sizeof(int32_t) * HRG_FAIR_SLOTS) != hipSuccess) { hipFree(p); return nullptr; }
-    tab[device] = p;
-  }
-  return tab[device];
-}
-
-// Every kernel variant of the library, once: X(family, hulls, name suffix).  The suffix is the one HRG_SYM gives the variant's translation unit (hrgym_device.h);
-// a line here, the wrapper .hip that sets its flags and its entry in _lib.SOURCES are what a new variant needs.
-enum { HRG_FAM_REACH, HRG_FAM_BOX, HRG_FAM_HO, HRG_FAM_LIFT, HRG_FAM_STACK, HRG_FAM_HAMMER, HRG_NFAMILY };
-#define HRG_VARIANTS(X)                                              \
-  X(HRG_FAM_REACH, 0, )          X(HRG_FAM_REACH, 1, _hull)          \
-  X(HRG_FAM_BOX, 0, _box)        X(HRG_FAM_BOX, 1, _box_hull)        \
-  X(HRG_FAM_HO, 0, _ho)          X(HRG_FAM_HO, 1, _ho_hull)          \
-  X(HRG_FAM_LIFT, 0, _lift)      X(HRG_FAM_LIFT, 1, _lift_hull)      \
-  X(HRG_FAM_STACK, 0, _stack)    X(HRG_FAM_STACK, 1, _stack_hull)    \
-  X(HRG_FAM_HAMMER, 0, _hammer)  X(HRG_FAM_HAMMER, 1, _hammer_hull)
-#define X(family, hulls, sfx)                                                                  \
-  extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn hrg_launch_step##sfx;    \
-  extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;
-HRG_VARIANTS(X)
-#undef X
-struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; };
-struct VariantTable { Variant v[HRG_NFAMILY][2]; };   // [family][hulls]
-static constexpr VariantTable make_variants() {
-  VariantTable t{};
-#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx};
-  HRG_VARIANTS(X)
-#undef X
-  return t;
-}
-static const VariantTable g_variants = make_variants();
-
-// the variant that steps a batch, and the object array its kernels stream (null: the ReachHuman kernels stream none)
-static const Variant& batch_variant(const hrg_batch* b, void** objs) {
-  int family = HRG_FAM_REACH;
-  *objs = nullptr;
-  if (b->task == HRG_TASK_HAMMERING) { family = HRG_FAM_HAMMER; *objs = b->d_hammers; }
-  else if (b->task == HRG_TASK_STACKING) { family = HRG_FAM_STACK; *objs = b->d_stacks; }
-  else if (b->task != HRG_TASK_REACH) {
-    family = b->task == HRG_TASK_LIFTING ? HRG_FAM_LIFT : (HRG_IS_HANDOVER(b->task) ? HRG_FAM_HO : HRG_FAM_BOX);
-    *objs = b->d_boxes;
-  }
-  return g_variants.v[family][b->hulls ? 1 : 0];
-}
-
-// one env's block of a per-env device array <-> the host (hrg_batch_get_ / set_ state, box, stack, hammer); missing = the error of a batch of another task,
-// which has no such array (null: every batch has it)
-template <class T>
-static int env_block_copy(hrg_batch* b, int32_t env, T* hrg_batch::*arr, void* buf_host, size_t bytes, bool get, const char* missing) {
-  if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(T)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
-  T* const dev = b->*arr;
-  if (missing && !dev) return fail(HRG_ERR_INVALID, missing);
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  if (get) HIPCHK(hipMemcpy(buf_host, dev + env, bytes, hipMemcpyDeviceToHost));
-  else HIPCHK(hipMemcpy(dev + env, buf_host, bytes, hipMemcpyHostToDevice));
-  return HRG_OK;
-}
-
-// the kernels built with HRG_POSE_TABLE: ReachHuman (hrgym_hip.hip, hrgym_hulls.hip) and lifting (hrgym_lift.hip); every other task steps with a cube kernel
-// or a hand-mocap kernel, which keep the live tree kinematics
-static bool hrg_task_uses_pose_table(int task) { return task == HRG_TASK_REACH || task == HRG_TASK_LIFTING; }
-
-static void mat_from_quat(double* M, const double* q) {
-  double w = q[0], x = q[1], y = q[2], z = q[3];
-  M[0] = 1 - 2 * (y * y + z * z); M[1] = 2 * (x * y - w * z); M[2] = 2 * (x * z + w * y);
-  M[3] = 2 * (x * y + w * z); M[4] = 1 - 2 * (x * x + z * z); M[5] = 2 * (y * z - w * x);
-  M[6] = 2 * (x * z - w * y); M[7] = 2 * (y * z + w * x); M[8] = 1 - 2 * (x * x + y * y);
-}
-
-// ---- what the handles of the training buffers and the learner share (csrc/hrgym_buffer.h) ----
-// every device allocation of one handle: zeroed, counted, freed together
-struct DeviceMem {
-  std::vector<void*> ptrs;
-  size_t bytes = 0;    // device memory held
-  size_t failed = 0;   // the request the device refused
-  DeviceMem() = default;
-  DeviceMem(const DeviceMem&) = delete;
-  DeviceMem& operator=(const DeviceMem&) = delete;
-  ~DeviceMem() {
-    for (void* p : ptrs) hipFree(p);
-  }
-  // `count` zeroed values behind `out`; false where the device refuses (HIP's sticky error is cleared, `failed` is the request)
-  template <class T> bool zeros(T*& out, size_t count) {
-    const size_t b = count * sizeof(T);
-    void* p = nullptr;
-    if (hipMalloc(&p, b) != hipSuccess) p = nullptr;
-    if (p) ptrs.push_back(p);
-    if (!p || hipMemset(p, 0, b) != hipSuccess) {
-      (void)hipGetLastError();
-      failed = b;
-      return false;
-    }
-    bytes += b;
-    out = (T*)p;
-    return true;
-  }
-};
-
-static int nomem(const char* name, const DeviceMem& mem) {
-  return fail(HRG_ERR_NOMEM, std::string(name) + ": device allocation of " + std::to_string(mem.failed) + " bytes failed");
-}
-
-// hrg_*_destroy of a handle with `device` (its DeviceMem member frees what it holds)
-template <class H> static void destroy_handle(H* h) {
-  if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  delete h;
-}
-
-// What every buffer checks of its observation columns and action width, and the column table on the current device: obs_cols, zero behind n_obs_cols (a per-lane
-// lookup).  `name`: the buffer's message prefix; observe_time: the descriptor's switch, null for a buffer without a time column.
-static int buffer_columns(const char* name, int32_t n_obs_cols, const int32_t* obs_cols, const int32_t* observe_time, int32_t act_dim, DeviceMem& mem,
-                          const int32_t*& table) {
-  const std::string pre = std::string(name) + ": ";
-  if (n_obs_cols < 1 || n_obs_cols + (observe_time && *observe_time ? 1 : 0) > HRG_OBS_DIM)
-    return fail(HRG_ERR_INVALID, pre + (observe_time ? "n_obs_cols (+ 1 with observe_time) must lie in [1, HRG_OBS_DIM]" : "n_obs_cols must lie in [1, HRG_OBS_DIM]"));
-  int32_t cols[HRG_OBS_DIM] = {0};
-  for (int c = 0; c < n_obs_cols; c++) {
-    if (obs_cols[c] < 0 || obs_cols[c] >= HRG_OBS_DIM) return fail(HRG_ERR_INVALID, pre + "an observation column outside the superset");
-    cols[c] = obs_cols[c];
-  }
-  if (act_dim < 1 || act_dim > HRG_ACT_DIM) return fail(HRG_ERR_INVALID, pre + "act_dim must lie in [1, HRG_ACT_DIM]");
-  int32_t* dev = nullptr;
-  if (!mem.zeros(dev, HRG_OBS_DIM)) return nomem(name, mem);
-  if (hipMemcpy(dev, cols, sizeof cols, hipMemcpyHostToDevice) != hipSuccess) return fail(HRG_ERR_HIP, pre + "upload failed");
-  table = dev;
-  return HRG_OK;
-}
-
-// What the replay buffer and the evaluator check of DatasetObsNormWrapper's statistics: mean / sd become the tables the view reads (mean 0 and std 1 behind the K
-// values, and everywhere without normalize).  `name`: the message prefix.
-static int view_statistics(const char* name, int K, int32_t normalize, int32_t squash, double squash_factor, const double* mean_in, const double* std_in, double* mean,
-                           double* sd) {
-  const std::string pre = std::string(name) + ": ";
-  if (squash && !normalize) return fail(HRG_ERR_INVALID, pre + "squash needs normalize");
-  for (int k = 0; k < HRG_OBS_DIM; k++) {
-    mean[k] = normalize && k < K ? mean_in[k] : 0.0;
-    sd[k] = normalize && k < K ? std_in[k] : 1.0;
-    if (!std::isfinite(mean[k]) || !std::isfinite(sd[k]) || sd[k] == 0.0) return fail(HRG_ERR_INVALID, pre + "mean must be finite, std finite and non-zero");
-  }
-  if (normalize && squash && !std::isfinite(squash_factor)) return fail(HRG_ERR_INVALID, pre + "squash_factor must be finite");
-  return HRG_OK;
-}
-
-// ... and the two tables on the current device, behind the view's pointers (synchronous)
-static int view_statistics_upload(const char* name, DeviceMem& mem, BufferView& v, const double* mean, const double* sd) {
-  double *mean_dev = nullptr, *std_dev = nullptr;
-  if (!(mem.zeros(mean_dev, HRG_OBS_DIM) && mem.zeros(std_dev, HRG_OBS_DIM))) return nomem(name, mem);
-  const size_t bytes = sizeof(double) * HRG_OBS_DIM;
-  if (hipMemcpy(mean_dev, mean, bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(std_dev, sd, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess)
-    return fail(HRG_ERR_HIP, std::string(name) + ": upload failed");
-  v.mean = mean_dev;
-  v.std = std_dev;
-  return HRG_OK;
-}
-
-// Pieces of one zeroed allocation of T, handed out in order: take(p, n) asks for n values behind p, alloc() makes the allocation and sets every pointer asked for
-template <class T> struct Carver {
-  std::vector<std::pair<T**, size_t>> pieces;   // where the pointer goes, the piece's first value
-  size_t count = 0;
-  void take(T*& out, size_t n) {
-    pieces.push_back({&out, count});
-    count += n;
-  }
-  bool alloc(DeviceMem& mem) {
-    T* base = nullptr;
-    if (!mem.zeros(base, count)) return false;
-    for (const auto& p : pieces) *p.first = base + p.second;
-    return true;
-  }
-};
-
-// What both learners check of their networks and batch (csrc/hrgym_mlp.h).  `name`: the learner's message prefix; max_batch: its largest batch.
-static int learner_shape(const char* name, int32_t hidden, int32_t depth, int32_t obs_dim, int32_t act_dim, int32_t batch_size, int32_t max_batch) {
-  const auto refuse = [name](const char* what, int32_t value, const std::string& why) {
-    return fail(HRG_ERR_UNSUPPORTED, std::string(name) + ": " + what + " = " + std::to_string(value) + why);
-  };
-  if (hidden != HRG_SAC_HIDDEN) return refuse("hidden", hidden, ": the kernels cover hidden width 64 only");
-  if (depth < 1 || depth > HRG_SAC_MAX_DEPTH) return refuse("depth", depth, " outside 1 .. 3");
-  if (obs_dim < 1 || obs_dim > HRG_OBS_DIM) return refuse("obs_dim", obs_dim, " outside 1 .. HRG_OBS_DIM");
-  if (act_dim < 1 || act_dim > HRG_ACT_DIM) return refuse("act_dim", act_dim, " outside 1 .. HRG_ACT_DIM");
-  if (batch_size < MLP_T || batch_size > max_batch || batch_size % MLP_T) return refuse("batch_size", batch_size, " is not a multiple of 32 in 32 .. " + std::to_string(max_batch));
-  return HRG_OK;
-}
-
-// Adam's bias corrections 1 - beta^t for the step after `steps` finished ones (betas 0.9, 0.999)
-static void adam_bias_corrections(uint64_t steps, double& bc1, double& bc2) {
-  const double t = (double)(steps + 1);
-  bc1 = 1.0 - std::pow(0.9, t);
-  bc2 = 1.0 - std::pow(0.999, t);
-}
-
-// hrg_*_export of a learner: once the device is idle, every array the caller asked for (a non-null `host`) to the host
-struct ExportFloats {
-  float* host;
-  const float* dev;
-  size_t count;
-};
-static int export_floats(int device, std::initializer_list<ExportFloats> arrays) {
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipDeviceSynchronize());
-  for (const ExportFloats& a : arrays)
-    if (a.host) HIPCHK(hipMemcpy(a.host, a.dev, a.count * sizeof(float), hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-// hrg_*_stats: the tracker's sums [n_envs][cols] to the host, cleared on the device on request
-static int buffer_stats(int device, double* acc_dev, int32_t n_envs, int cols, double* per_env_host, int32_t clear) {
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t bytes = sizeof(double) * (size_t)cols * (size_t)n_envs;
-  HIPCHK(hipMemcpy(per_env_host, acc_dev, bytes, hipMemcpyDeviceToHost));
-  if (clear) {
-    HIPCHK(hipMemset(acc_dev, 0, bytes));
-    HIPCHK(hipDeviceSynchronize());
-  }
-  return HRG_OK;
-}
-
-// the two grids of the buffer kernels: a wavefront per env, and blocks of four wavefronts with one of `n` rows, samples or indices each
-template <class K, class... A> static int launch_per_env(K kernel, int32_t n_envs, void* stream, A... args) {
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_envs), dim3(64), 0, (hipStream_t)stream, args...);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-template <class K, class... A> static int launch_per_wave(K kernel, int32_t n, void* stream, A... args) {
-  const unsigned per = HRG_BUFFER_BLOCK / 64;
-  hipLaunchKernelGGL(kernel, dim3(((unsigned)n + per - 1) / per), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, args...);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-extern "C" {
-
-const char* hrg_last_error(void) { return g_err.c_str(); }
-const char* hrg_version(void) { return "hrgym-hip 0.1.0 (gfx950)"; }
-size_t hrg_state_bytes(void) { return sizeof(hrg_env_state); }
-size_t hrg_box_bytes(void) { return sizeof(hrg_box_state); }
-size_t hrg_stack_bytes(void) { return sizeof(hrg_stack_state); }
-size_t hrg_hammer_bytes(void) { return sizeof(hrg_hammer_state); }
-
-int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, int32_t n_envs, int64_t env_id0, int32_t device, hrg_batch** out) {
-  if (!desc || !clips || !out || n_envs <= 0) return fail(HRG_ERR_INVALID, "null argument or n_envs <= 0");
-  if (desc->failsafe_sdot != 0.0) return fail(HRG_ERR_INVALID, "failsafe_sdot must be 0: SSM / OFF brake to a stop, PFL computes its speed from pfl_v_safe / pfl_reach");
-  if (desc->shield_type == HRG_SHIELD_PFL) {
-    if (!(desc->pfl_v_safe > 0)) return fail(HRG_ERR_INVALID, "PFL: pfl_v_safe must be positive");
-    for (int j = 0; j < NARM; j++) if (!(desc->pfl_reach[j] > 0)) return fail(HRG_ERR_INVALID, "PFL: pfl_reach must be positive");
-  }
-  for (int i = 0; i < NARM; i++)   // mj_Euler's implicit damping treats the arm's joint damping as a perturbation (euler_robot_tree): one Neumann term, error (h d / M)^2
-    if (!(desc->jnt_damping[i] >= 0 && desc->timestep * desc->jnt_damping[i] * desc->dof_invweight0[i] < 1e-3))
-      return fail(HRG_ERR_UNSUPPORTED, "arm joint damping too large for the implicit-damping expansion (h d / M must stay below 1e-3; robot.xml: 1e-4)");
-  if ((desc->jnt_damping[NARM] > 0) != (desc->jnt_damping[NARM + 1] > 0)) return fail(HRG_ERR_UNSUPPORTED, "the two finger slides must both carry damping, or neither");
-  if (desc->solimp[4] != 2.0) return fail(HRG_ERR_UNSUPPORTED, "solimp power must be 2 (MuJoCo's default): the HIP stepper evaluates the impedance sigmoid as a square");
-  if (clips->n_clips < 1 || clips->n_clips > HRG_MAX_CLIPS || clips->n_clips != desc->n_clips) return fail(HRG_ERR_INVALID, "clip table / desc.n_clips mismatch");
-  for (int i = 0; i < NV; i++) {
-    if ((i < NARM) != (desc->jnt_type[i] == 0)) return fail(HRG_ERR_INVALID, "expected 6 hinges followed by 2 slides");
-    if (i < NARM && desc->body_parent[i] != i - 1) return fail(HRG_ERR_INVALID, "arm must be a serial chain");
-    if (i < NARM && !(desc->jnt_axis[i][0] == 0 && desc->jnt_axis[i][1] == 0 && desc->jnt_axis[i][2] == 1)) return fail(HRG_ERR_INVALID, "arm hinges must turn about the local z axis");
-    if (i >= NARM && desc->body_parent[i] != NARM - 1) return fail(HRG_ERR_INVALID, "fingers must hang off the last link");
-  }
-  for (int c = 0; c < HRG_NSHIELD_RCAP; c++)
-    if (desc->scap_body[c] != (c < NARM ? c : NARM - 1)) return fail(HRG_ERR_INVALID, "shield capsule c must sit on link c (gripper on link 6)");
-  if (desc->n_bodypart > HRG_NBODYPART_MAX || desc->n_extremity > HRG_NEXTREMITY_MAX) return fail(HRG_ERR_INVALID, "too many body parts");
-  if (desc->task < HRG_TASK_REACH || desc->task > HRG_TASK_HAMMERING) return fail(HRG_ERR_UNSUPPORTED, "unknown task");
-  if (desc->task == HRG_TASK_STACKING) {
-    if (!(desc->box_inertia[0] == desc->box_inertia[1] && desc->box_inertia[1] == desc->box_inertia[2]))
-      return fail(HRG_ERR_UNSUPPORTED, "CollaborativeStackingCart: the HIP stepper stacks cubes (object_full_size with three equal edges)");
-    for (int c = 0; c < clips->n_clips; c++) {
-      const int32_t* kf = clips->clip_stack_keyframes[c];
-      if (!(kf[0] >= 0 && kf[0] <= kf[1] && kf[1] <= kf[2] && kf[2] <= kf[3] && kf[3] <= kf[4] && clips->clip_n_loop[c] >= 0 && clips->clip_n_loop[c] <= HRG_MAX_LOOP &&
-            clips->clip_n_loop2[c] >= 0 && clips->clip_n_loop2[c] <= HRG_MAX_LOOP))
-        return fail(HRG_ERR_INVALID, "CollaborativeStackingCart: every clip needs five ascending keyframes and at most 4 loop sines per waiting phase in its info");
-    }
-  }
-  if (desc->task == HRG_TASK_LIFTING && !(desc->min_balance > -1 && desc->min_balance < 1)) return fail(HRG_ERR_INVALID, "CollaborativeLiftingCart: min_balance must lie in (-1, 1)");
-  if (HRG_IS_HANDOVER(desc->task))
-    for (int c = 0; c < clips->n_clips; c++)
-      if (!(clips->clip_n_loop2[c] >= 0 && clips->clip_n_loop2[c] <= HRG_MAX_LOOP)) return fail(HRG_ERR_INVALID, "HumanRobotHandoverCart: at most 4 loop sines per stage");
-  if (desc->task == HRG_TASK_INSPECTION || HRG_IS_HANDOVER(desc->task))
-    for (int c = 0; c < clips->n_clips; c++)
-      if (!(clips->clip_n_loop[c] >= 0 && clips->clip_n_loop[c] <= HRG_MAX_LOOP && clips->clip_keyframes[c][0] >= 0 && clips->clip_keyframes[c][0] <= clips->clip_keyframes[c][1]))
-        return fail(HRG_ERR_INVALID, "HumanObjectInspectionCart: every clip needs keyframes (k0 <= k1) and at most 4 loop sines in its info");
-  if (desc->ik_enabled && !(desc->ik_max_iter >= 1 && desc->ik_max_iter <= 1000 && desc->ik_damping > 0 && desc->ik_action_limit > 0 && desc->ik_residual_threshold >= 0))
-    return fail(HRG_ERR_INVALID, "ik: need 1 <= max_iter <= 1000, damping > 0, action_limit > 0, residual_threshold >= 0");
-  if (desc->task == HRG_TASK_HAMMERING) {
-    if (!(desc->hm_board_mass > 0 && desc->hm_hammer_mass > 0 && desc->hm_nail_mass > 0 && desc->hm_nail_range > 0 && desc->hm_nail_invweight > 0 && desc->n_obj_placements > 0 &&
-          desc->hm_board_inertia[0] > 0 && desc->hm_board_inertia[1] > 0 && desc->hm_board_inertia[2] > 0 && desc->hm_hammer_inertia[0] > 0 && desc->hm_hammer_inertia[1] > 0 &&
-          desc->hm_hammer_inertia[2] > 0))
-      return fail(HRG_ERR_INVALID, "CollaborativeHammeringCart needs positive board / hammer / nail masses and inertias, a nail range and n_obj_placements > 0");
-    for (int c = 0; c < clips->n_clips; c++)
-      if (!(clips->clip_keyframes[c][0] >= 0 && clips->clip_keyframes[c][0] <= clips->clip_keyframes[c][1] && clips->clip_n_loop[c] >= 0 && clips->clip_n_loop[c] <= HRG_MAX_LOOP))
-        return fail(HRG_ERR_INVALID, "CollaborativeHammeringCart: every clip needs two ascending keyframes and at most 4 loop sines in its info");
-  } else
-  if (desc->task != HRG_TASK_REACH && !(desc->box_half[0] > 0 && desc->box_half[1] > 0 && desc->box_half[2] > 0 && desc->box_mass > 0 && desc->box_inertia[0] > 0 && desc->box_inertia[1] > 0 &&
-                                       desc->box_inertia[2] > 0 && desc->box_inertia_mean > 0 && desc->box_invweight_rot > 0 && desc->n_targets > 0 && desc->n_obj_placements > 0))
-    return fail(HRG_ERR_INVALID, "PickPlaceHumanCart needs box_half, box_mass, box_inertia, n_targets, n_obj_placements > 0");
-  HIPCHK(hipSetDevice(device));
-  hrg_batch* b = new hrg_batch();
-  b->device = device; b->n_envs = n_envs; b->env_id0 = env_id0; b->task = desc->task; b->ik = desc->ik_enabled != 0;
-  // ---- device model ----
-  std::unique_ptr<DevModel> hm_own(new DevModel());
-  DevModel* hm = hm_own.get();
-  memset(hm, 0, sizeof *hm);
-  // every early return below releases the batch and whatever device buffers it already owns
-  auto bail = [&](int code, const std::string& msg) { hrg_batch_destroy(b); return fail(code, msg); };
-#define HIPCHK_C(x)                                                                                       \
-  do {                                                                                                    \
-    hipError_t _e = (x);                                                                                  \
-    if (_e != hipSuccess) return bail(HRG_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(_e));        \
-  } while (0)
-  hm->m = *desc;
-  mat_from_quat(hm->Rbase, desc->base_quat);
-  for (int i = 0; i < NV; i++) {
-    mat_from_quat(hm->Rq[i], desc->body_quat[i]);
-    int mask = 0;
-    for (int k = i; k >= 0; k = desc->body_parent[k]) mask |= 1 << k;
-    hm->anc_mask[i] = mask;
-  }
-  int maxd = 0;
-  for (int i = 0; i < HRG_NHB; i++) maxd = desc->hb_depth[i] > maxd ? desc->hb_depth[i] : maxd;
-  hm->hb_maxdepth = maxd;
-  { // mj_makeImpedance constants of solref (the oracle's `impedance`)
-    double tc = desc->solref[0];
-    const double dr = desc->solref[1], dmax = desc->solimp[1];
-    if (tc < 2 * desc->timestep) tc = 2 * desc->timestep;
-    hm->sol_K = 1.0 / (dmax * dmax * tc * tc * dr * dr);
-    hm->sol_Bd = 2.0 / (dmax * tc);
-  }
-  for (int c = 0; c < HRG_NRCAP; c++) {
-    double d2 = 0;
-    for (int a = 0; a < 3; a++) d2 += (desc->rcap_p2[c][a] - desc->rcap_p1[c][a]) * (desc->rcap_p2[c][a] - desc->rcap_p1[c][a]);
-    hm->rcap_hl[c] = 0.5 * sqrt(d2);
-  }
-  for (int c = 0; c < HRG_NHB; c++) {
-    double d2 = 0;
-    for (int a = 0; a < 3; a++) d2 += (desc->hcap_p2[c][a] - desc->hcap_p1[c][a]) * (desc->hcap_p2[c][a] - desc->hcap_p1[c][a]);
-    hm->hcap_hl[c] = 0.5 * sqrt(d2);
-  }
-  if (maxd + 1 > 16) { return bail(HRG_ERR_INVALID, "human tree deeper than 15"); }
-  for (int i = 0; i < HRG_NHB; i++) hm->hb_jump[0][i] = desc->hb_parent[i];
-  for (int s = 1; s < 4; s++)
-    for (int i = 0; i < HRG_NHB; i++) { const int a = hm->hb_jump[s - 1][i]; hm->hb_jump[s][i] = a < 0 ? -1 : hm->hb_jump[s - 1][a]; }
-  hm->hb_njump = 0;
-  while ((1 << hm->hb_njump) < maxd + 1) hm->hb_njump++;
-  int n = 0;
-  // (kind, joints, thickness, v_max, a_max or ball length) of reach capsule n as the record the shield's lanes load
-  auto hc_set = [&](int n, int kind, int j1, int j2, double th, double v, double al) { hm->hc[n].th = th; hm->hc[n].v = v; hm->hc[n].al = al; hm->hc[n].kj = kind | (j1 << 8) | (j2 << 16); hm->hc[n].pad = 0; };
-  for (int k = 0; k < desc->n_bodypart; k++)
-    if (desc->bp_joint[k][0] < 0 || desc->bp_joint[k][0] >= HRG_NHJ || desc->bp_joint[k][1] < 0 || desc->bp_joint[k][1] >= HRG_NHJ) { return bail(HRG_ERR_INVALID, "body part joint outside the human's sites"); }
-  for (int k = 0; k < desc->n_extremity; k++)
-    if (desc->ext_joint[k] < 0 || desc->ext_joint[k] >= HRG_NHJ) { return bail(HRG_ERR_INVALID, "extremity joint outside the human's sites"); }
-  if (2 * desc->n_bodypart + desc->n_extremity > HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
-  for (int k = 0; k < desc->n_bodypart; k++, n++) hc_set(n, 0, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], desc->bp_amax[k]);
-  for (int k = 0; k < desc->n_bodypart; k++, n++) hc_set(n, 1, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], 0.0);
-  for (int k = 0; k < desc->n_extremity; k++, n++) hc_set(n, 2, desc->ext_joint[k], desc->ext_joint[k], desc->ext_thickness[k], desc->ext_vmax[k], desc->ext_length[k]);
-  for (int k = 0; k < desc->n_bodypart; k++) {
-    if (!desc->bp_in_pos[k]) continue;
-    if (n >= HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
-    hc_set(n, 3, desc->bp_joint[k][0], desc->bp_joint[k][1], desc->bp_thickness[k], desc->bp_vmax[k], 0.0);
-    n++;
-  }
-  if (n > HRG_NHCAP_MAX) { return bail(HRG_ERR_INVALID, "more than 64 human reach capsules"); }
-  hm->hc_n = n;
-  int ns = 0;
-  for (int i = 0; i < HRG_NRCAP; i++)
-    for (int j = i + 1; j < HRG_NRCAP; j++)
-      if ((desc->rcap_selfmask[i] >> j) & 1u) { hm->self_ij[ns].i = i; hm->self_ij[ns].j = j; ns++; }
-  hm->n_self = ns;
-  int nc = 0;
-  for (int i = 0; i < 8; i++)
-    for (int j = i + 1; j < 8; j++)
-      if (((desc->chk_selfmask[i] >> j) & 1u) && nc < 32) { hm->chk_i[nc] = i; hm->chk_j[nc] = j; nc++; }
-  hm->n_chk = nc;
-  hm->phase_mask = 0xff;
-  {
-    double se, ve, ae;
-    path_plan(&hm->brake_full, 0.0, 1.0, 0.0, desc->failsafe_sdot, desc->path_amax, desc->path_jmax);
-    hm->brake_T = path_total(&hm->brake_full);
-    path_eval(&hm->brake_full, hm->brake_T, desc->failsafe_sdot, &se, &ve, &ae);
-    hm->brake_ds = se;
-  }
-#ifdef HRG_STAMPS
-  if (const char* pm = getenv("HRG_PHASE_MASK")) hm->phase_mask = atoi(pm); // diagnostic build only: results are invalid
-#endif
-  // clips
-  const size_t fbytes = sizeof(double) * HRG_FRAME_DIM * (size_t)clips->total_frames;
-  int64_t tot = 0;
-  for (int c = 0; c < clips->n_clips; c++) {
-    if (clips->clip_len[c] < 1 || clips->clip_offset[c] != tot) { return bail(HRG_ERR_INVALID, "clip table must be densely packed"); }
-    tot += clips->clip_len[c];
-  }
-  if (tot != clips->total_frames) { return bail(HRG_ERR_INVALID, "clip table total_frames mismatch"); }
-  HIPCHK_C(hipMalloc(&b->d_frames, fbytes));
-  HIPCHK_C(hipMemcpy(b->d_frames, clips->frames, fbytes, hipMemcpyHostToDevice));
-  hm->clips = *clips;
-  hm->clips.frames = b->d_frames;
-  hm->pose_tab = nullptr;
-  if (hrg_task_uses_pose_table(desc->task)) {   // filled by hrg_pose_table_kernel once the model is on the device
-    b->pose_bytes = sizeof(double) * HRG_POSE_DIM * (size_t)clips->total_frames;
-    HIPCHK_C(hipMalloc(&b->d_pose, b->pose_bytes));
-    hm->pose_tab = b->d_pose;
-  }
-  hm->hull_dev = nullptr;
-  if (desc->robot_hulls) {   // convex hulls of the arm links: the vertex table goes to device memory like the clip frames
-    // every kernel has a hull variant: ReachHuman (hrg_step_kernel_hull), the cube tasks (_box_hull: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman
-    // with its box), the handover tasks (_ho_hull), lifting (_lift_hull), stacking (_stack_hull) and hammering (_hammer_hull)
-    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX ||
-          HRG_IS_HANDOVER(desc->task) || desc->task == HRG_TASK_LIFTING || desc->task == HRG_TASK_STACKING || desc->task == HRG_TASK_HAMMERING))
-      return bail(HRG_ERR_UNSUPPORTED, "robot_hulls: no hull variant of the step kernel for this task");
-    b->hulls = true;
-    if (!desc->hull_verts || desc->hull_off[0] != 0) return bail(HRG_ERR_INVALID, "robot_hulls: hull_verts / hull_off missing");
-    for (int h = 0; h < HRG_NHULL; h++)
-      if (!(desc->hull_off[h + 1] > desc->hull_off[h] + 3 && desc->hull_off[h + 1] <= 1000000)) return bail(HRG_ERR_INVALID, "robot_hulls: every hull needs at least four vertices");
-    const size_t hbytes = sizeof(double) * 3 * (size_t)desc->hull_off[HRG_NHULL];
-    HIPCHK_C(hipMalloc(&b->d_hull, hbytes));
-    HIPCHK_C(hipMemcpy(b->d_hull, desc->hull_verts, hbytes, hipMemcpyHostToDevice));
-    hm->hull_dev = b->d_hull;
-    hull_centroids(desc->hull_verts, desc->hull_off, hm->hull_cen);
-    HIPCHK_C(hipMalloc(&b->d_mpr_fallback, sizeof(unsigned long long)));
-    HIPCHK_C(hipMemset(b->d_mpr_fallback, 0, sizeof(unsigned long long)));
-    hm->mpr_fallback = b->d_mpr_fallback;
-  }
-  HIPCHK_C(hipMalloc(&b->d_model, sizeof(DevModel)));
-  HIPCHK_C(hipMemcpy(b->d_model, hm, sizeof(DevModel), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(hrg_model_constants_kernel, dim3(1), dim3(64), 0, 0, b->d_model);   // fric_*, eul_*, rcap_mid: in the device's own arithmetic
-  HIPCHK_C(hipGetLastError());
-  HIPCHK_C(hipDeviceSynchronize());
-  if (b->d_pose) {
-    hipLaunchKernelGGL(hrg_pose_table_kernel, dim3((unsigned)clips->total_frames), dim3(64), 0, 0, b->d_model, b->d_pose);
-    HIPCHK_C(hipGetLastError());
-    HIPCHK_C(hipDeviceSynchronize());
-  }
-  // ---- state ----
-  HIPCHK_C(hipMalloc(&b->d_states, sizeof(hrg_env_state) * (size_t)n_envs));
-  std::vector<hrg_env_state> init((size_t)n_envs);
-  memset(init.data(), 0, sizeof(hrg_env_state) * (size_t)n_envs);
-  for (auto& s : init) s.episode = -1;
-  HIPCHK_C(hipMemcpy(b->d_states, init.data(), sizeof(hrg_env_state) * (size_t)n_envs, hipMemcpyHostToDevice));
-  HIPCHK_C(hipMalloc(&b->d_rcaps, sizeof(double) * 7 * HRG_NSHIELD_RCAP * (size_t)n_envs));
-  HIPCHK_C(hipMalloc(&b->d_hcaps, sizeof(double) * 7 * HRG_NHCAP_MAX * (size_t)n_envs));
-  HIPCHK_C(hipMalloc(&b->d_nh, sizeof(int32_t) * (size_t)n_envs));
-  HIPCHK_C(hipMalloc(&b->d_scratch_obs, sizeof(float) * HRG_OBS_DIM * (size_t)n_envs));
-  HIPCHK_C(hipMemset(b->d_rcaps, 0, sizeof(double) * 7 * HRG_NSHIELD_RCAP * (size_t)n_envs));
-  HIPCHK_C(hipMemset(b->d_hcaps, 0, sizeof(double) * 7 * HRG_NHCAP_MAX * (size_t)n_envs));
-  HIPCHK_C(hipMemset(b->d_nh, 0, sizeof(int32_t) * (size_t)n_envs));
-  HIPCHK_C(hipMalloc(&b->d_boxes, sizeof(hrg_box_state) * (size_t)n_envs));
-  HIPCHK_C(hipMemset(b->d_boxes, 0, sizeof(hrg_box_state) * (size_t)n_envs));
-  if (desc->task == HRG_TASK_HAMMERING) {
-    HIPCHK_C(hipMalloc(&b->d_hammers, sizeof(hrg_hammer_state) * (size_t)n_envs));
-    HIPCHK_C(hipMemset(b->d_hammers, 0, sizeof(hrg_hammer_state) * (size_t)n_envs));
-  }
-  if (desc->task == HRG_TASK_STACKING) {
-    HIPCHK_C(hipMalloc(&b->d_stacks, sizeof(hrg_stack_state) * (size_t)n_envs));
-    HIPCHK_C(hipMemset(b->d_stacks, 0, sizeof(hrg_stack_state) * (size_t)n_envs));
-  }
-  {
-    std::vector<int32_t> ord(2 * (size_t)n_envs + 4, 0);
-    for (int32_t e = 0; e < n_envs; e++) ord[e] = ord[(size_t)n_envs + e] = e;
-    HIPCHK_C(hipMalloc(&b->d_order, sizeof(int32_t) * ord.size()));
-    HIPCHK_C(hipMemcpy(b->d_order, ord.data(), sizeof(int32_t) * ord.size(), hipMemcpyHostToDevice));
-  }
-#undef HIPCHK_C
-  *out = b;
-  return HRG_OK;
-}
-
-void hrg_batch_destroy(hrg_batch* b) {
-  if (!b) return;
-  hipSetDevice(b->device);
-  hipDeviceSynchronize();
-  for (auto& p : b->events) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  for (auto& p : b->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-  hipFree(b->d_model); hipFree(b->d_frames); hipFree(b->d_pose); hipFree(b->d_hull); hipFree(b->d_mpr_fallback); hipFree(b->d_states); hipFree(b->d_rcaps); hipFree(b->d_hcaps); hipFree(b->d_nh); hipFree(b->d_scratch_obs); hipFree(b->d_boxes); hipFree(b->d_stacks); hipFree(b->d_hammers); hipFree(b->d_order);
-  hipFree(b->ex.act); hipFree(b->ex.sim); hipFree(b->ex.ou_y); hipFree(b->ex.ou_calls); hipFree(b->ex.acc);
-  dataset_free(b);
-  delete b;
-}
-
-int hrg_batch_pose_table_bytes(hrg_batch* b, int64_t* bytes_host) {
-  if (!b || !bytes_host) return fail(HRG_ERR_INVALID, "null argument");
-  *bytes_host = (int64_t)b->pose_bytes;
-  return HRG_OK;
-}
-
-int hrg_debug_pose_compare(hrg_batch* b, const void* queries_host, int32_t n, double* out_host) {
-  if (!b || !queries_host || !out_host || n <= 0) return fail(HRG_ERR_INVALID, "null argument or n <= 0");
-  if (!b->d_pose) return fail(HRG_ERR_UNSUPPORTED, "this batch's task keeps the live tree kinematics (no pose table)");
-  DevModel hm;
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipMemcpy(&hm, b->d_model, sizeof hm, hipMemcpyDeviceToHost));
-  const PoseQuery* qh = (const PoseQuery*)queries_host;
-  for (int k = 0; k < n; k++)
-    if (qh[k].clip < 0 || qh[k].clip >= hm.clips.n_clips || qh[k].at < 0 || qh[k].at >= hm.clips.clip_len[qh[k].clip]) return fail(HRG_ERR_INVALID, "query outside the clip set");
-  const size_t ob = sizeof(double) * 2 * (6 * HRG_NHB + 3 * HRG_NHJ) * (size_t)n;
-  const TapBuf in[] = {{qh, sizeof(PoseQuery) * (size_t)n}};
-  const bool ok = hrg_run_tap(in, 1, out_host, ob, [&](void** d) {
-    hipLaunchKernelGGL(hrg_pose_compare_kernel, dim3((unsigned)n), dim3(64), 0, 0, b->d_model, (const PoseQuery*)d[0], (int)n, (double*)d[1]);
-  });
-  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_pose_compare: device allocation / copy / launch failed");
-}
-
-int hrg_debug_wave_helpers(const double* in_host, uint64_t lane_mask, double* out_host) {
-  if (!in_host || !out_host) return fail(HRG_ERR_INVALID, "null argument");
-  const TapBuf in[] = {{in_host, sizeof(double) * 64}};
-  const bool ok = hrg_run_tap(in, 1, out_host, sizeof(double) * 64 * HRG_WAVE_NOUT, [&](void** d) {
-    hipLaunchKernelGGL(hrg_wave_helpers_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (unsigned long long)lane_mask, (double*)d[1]);
-  });
-  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_wave_helpers: device allocation / copy / launch failed");
-}
-
-int hrg_debug_cull_box(const double* in_host, int32_t n, double* out_host) {
-  if (!in_host || !out_host || n < 1 || n > 16) return fail(HRG_ERR_INVALID, "null argument or n outside 1..16");
-  const TapBuf in[] = {{in_host, sizeof(double) * 16 * 7}};
-  const bool ok = hrg_run_tap(in, 1, out_host, sizeof(double) * 6, [&](void** d) {
-    hipLaunchKernelGGL(hrg_cull_box_kernel, dim3(1), dim3(64), 0, 0, (const double*)d[0], (int)n, (double*)d[1]);
-  });
-  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_cull_box: device allocation / copy / launch failed");
-}
-
-int hrg_debug_model_constants(hrg_batch* b, double* out_host) {
-  if (!b || !out_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  const bool ok = hrg_run_tap(nullptr, 0, out_host, sizeof(double) * 2 * HRG_MC_DIM, [&](void** d) {
-    hipMemset(d[0], 0, sizeof(double) * 2 * HRG_MC_DIM);
-    hipLaunchKernelGGL(hrg_model_constants_tap_kernel, dim3(1), dim3(64), 0, 0, b->d_model, 0.0, (double*)d[0]);
-  });
-  return ok ? HRG_OK : fail(HRG_ERR_HIP, "hrg_debug_model_constants: device allocation / copy / launch failed");
-}
-
-int hrg_batch_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {
-  if (!b) return fail(HRG_ERR_INVALID, "null batch");
-  HIPCHK(hipSetDevice(b->device));
-  void* objs;
-  const Variant& v = batch_variant(b, &objs);
-  v.reset(b->n_envs, (hipStream_t)stream, b->d_model, b->d_states, mask_dev, obs_dev, b->env_id0, objs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_batch_check_actions(hrg_batch* b, const double* actions_dev, uint8_t* collides_dev, void* stream) {
-  if (!b || !actions_dev || !collides_dev) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(hrg_check_kernel, HRG_LAUNCH_DIMS(b->n_envs), 0, (hipStream_t)stream, b->d_model, b->d_states, actions_dev, collides_dev, b->n_envs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_batch_step(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev, void* stream) {
-  if (!b || !actions_dev || !obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  hipStream_t st = (hipStream_t)stream;
-  std::pair<hipEvent_t, hipEvent_t> ev;
-  if (b->timing) {
-    if (!b->pool.empty()) { ev = b->pool.back(); b->pool.pop_back(); }
-    else { HIPCHK(hipEventCreate(&ev.first)); HIPCHK(hipEventCreate(&ev.second)); }
-    HIPCHK(hipEventRecord(ev.first, st));
-  }
-  int32_t* fair = fair_table(b->device);
-  if (!fair) return fail(HRG_ERR_HIP, "cannot allocate the wave-progress table");
-  const StepOrder ord{b->d_order, b->n_envs, b->parity, fair};
-  void* objs;
-  const Variant& v = batch_variant(b, &objs);
-  v.step(b->n_envs, st, b->d_model, b->d_states, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, b->taps ? b->d_rcaps : nullptr, b->taps ? b->d_hcaps : nullptr,
-         b->taps ? b->d_nh : nullptr, b->env_id0, b->d_scratch_obs, objs, ord);
-  HIPCHK(hipGetLastError());
-  b->parity ^= 1;
-  if (b->timing) { HIPCHK(hipEventRecord(ev.second, st)); b->events.push_back(ev); }
-  return HRG_OK;
-}
-
-// ---- scripted experts + action-based imitation reward (csrc/hrgym_expert.h) ----
-static bool expert_fits_task(int expert, int task) {
-  switch (expert) {
-    case HRG_EXPERT_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
-    case HRG_EXPERT_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || task == HRG_TASK_STACKING || HRG_IS_HANDOVER(task);   // PP-AIR, CS-AIR, HRH-AIR, RHH-AIR
-    case HRG_EXPERT_LIFTING: return task == HRG_TASK_LIFTING;
-    case HRG_EXPERT_HAMMERING: return task == HRG_TASK_HAMMERING;
-  }
-  return false;
-}
-
-int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc) {
-  if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
-  if (desc->expert < HRG_EXPERT_REACH || desc->expert > HRG_EXPERT_HAMMERING) return fail(HRG_ERR_UNSUPPORTED, "unknown expert");
-  if (!expert_fits_task(desc->expert, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this expert does not read the observation of the batch's task");
-  if ((desc->cartesian != 0) != (desc->expert != HRG_EXPERT_REACH)) return fail(HRG_ERR_UNSUPPORTED, "ReachHumanExpert acts in joint space, every other expert in Cartesian space");
-  if ((desc->cartesian != 0) != b->ik) return fail(HRG_ERR_UNSUPPORTED, "the expert's action form is not the batch's (Cartesian experts need the IK front-end, ik_enabled)");
-  const int width = desc->cartesian ? 4 : HRG_ACT_DIM;
-  for (int k = 0; k < width; k++)
-    if (!(desc->act_low[k] < desc->act_high[k])) return fail(HRG_ERR_INVALID, "expert: action bounds need low < high");
-  if (!(desc->signal_to_noise_ratio >= 0 && desc->signal_to_noise_ratio <= 1 && desc->delta_time >= 0)) return fail(HRG_ERR_INVALID, "expert: need 0 <= signal_to_noise_ratio <= 1 and delta_time >= 0");
-  if (desc->reward_enabled) {
-    if (!(desc->iota_m > 0 && desc->iota_g > 0)) return fail(HRG_ERR_INVALID, "imitation reward: iota_m and iota_g must be positive");
-    if (!(desc->alpha >= 0 && desc->alpha <= 1 && desc->beta >= 0 && desc->beta <= 1)) return fail(HRG_ERR_INVALID, "imitation reward: alpha and beta must lie in [0, 1]");
-    for (int fn : {desc->m_sim_fn, desc->g_sim_fn})
-      if (fn != HRG_SIM_GAUSSIAN && fn != HRG_SIM_TANH) return fail(HRG_ERR_INVALID, "imitation reward: unknown similarity function");
-  }
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)b->n_envs;
-  ExpertBuffers& x = b->ex;
-  b->has_expert = false;   // until every buffer below exists and is zeroed
-  if (!x.act) HIPCHK(hipMalloc(&x.act, sizeof(double) * HRG_ACT_DIM * n));
-  if (!x.sim) HIPCHK(hipMalloc(&x.sim, sizeof(double) * 2 * n));
-  if (!x.ou_y) HIPCHK(hipMalloc(&x.ou_y, sizeof(double) * HRG_ACT_DIM * n));
-  if (!x.ou_calls) HIPCHK(hipMalloc(&x.ou_calls, sizeof(int64_t) * n));
-  if (!x.acc) HIPCHK(hipMalloc(&x.acc, sizeof(double) * 3 * n));
-  HIPCHK(hipMemset(x.act, 0, sizeof(double) * HRG_ACT_DIM * n));
-  HIPCHK(hipMemset(x.sim, 0, sizeof(double) * 2 * n));
-  HIPCHK(hipMemset(x.ou_y, 0, sizeof(double) * HRG_ACT_DIM * n));
-  HIPCHK(hipMemset(x.ou_calls, 0, sizeof(int64_t) * n));
-  HIPCHK(hipMemset(x.acc, 0, sizeof(double) * 3 * n));
-  HIPCHK(hipDeviceSynchronize());
-  b->expert = *desc;
-  b->has_expert = true;
-  return HRG_OK;
-}
-
-int hrg_batch_expert_actions(hrg_batch* b, const float* obs_dev, double* actions_out_dev, void* stream) {
-  if (!b || !obs_dev || !actions_out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!b->has_expert) return fail(HRG_ERR_INVALID, "no expert attached (hrg_batch_expert_attach)");
-  HIPCHK(hipSetDevice(b->device));
-  hipLaunchKernelGGL(hrg_expert_pre_kernel, dim3((unsigned)((b->n_envs + HRG_EXPERT_BLOCK - 1) / HRG_EXPERT_BLOCK)), dim3(HRG_EXPERT_BLOCK), 0, (hipStream_t)stream, b->expert, obs_dev,
-                     (const double*)nullptr, actions_out_dev, (double*)nullptr, b->ex.ou_y, b->ex.ou_calls, b->env_id0, b->n_envs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev, float* imit_dev,
-                             void* stream) {
-  if (!b || !actions_dev || !obs_dev || !reward_dev || !done_dev || !info_dev || !imit_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!b->has_expert) return fail(HRG_ERR_INVALID, "no expert attached (hrg_batch_expert_attach)");
-  if (!b->expert.reward_enabled) return fail(HRG_ERR_INVALID, "the expert was attached without an imitation reward (reward_enabled = 0)");
-  HIPCHK(hipSetDevice(b->device));
-  const dim3 grid((unsigned)((b->n_envs + HRG_EXPERT_BLOCK - 1) / HRG_EXPERT_BLOCK)), block(HRG_EXPERT_BLOCK);
-  hipLaunchKernelGGL(hrg_expert_pre_kernel, grid, block, 0, (hipStream_t)stream, b->expert, (const float*)obs_dev, (const double*)actions_dev, b->ex.act, b->ex.sim, b->ex.ou_y,
-                     b->ex.ou_calls, b->env_id0, b->n_envs);
-  HIPCHK(hipGetLastError());
-  const int rc = hrg_batch_step(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, stream);
-  if (rc != HRG_OK) return rc;
-  hipLaunchKernelGGL(hrg_imitation_post_kernel, grid, block, 0, (hipStream_t)stream, b->expert, (const double*)b->ex.sim, (const uint8_t*)done_dev, reward_dev, b->ex.acc, imit_dev,
-                     b->n_envs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-// ---- demonstration datasets: reference state initialisation + state-based imitation reward (csrc/hrgym_dataset.h) ----
-static bool dataset_task_ok(int task) { return task != HRG_TASK_STACKING && task != HRG_TASK_HAMMERING; }   // their state lives in further arrays (d_stacks, d_hammers)
-static bool sir_fits_task(int kind, int task) {
-  switch (kind) {
-    case HRG_SIR_NONE: return true;
-    case HRG_SIR_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
-    case HRG_SIR_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || HRG_IS_HANDOVER(task);   // "any environment that can be solved using the PickPlaceHumanCartExpert"
-    case HRG_SIR_LIFTING: return task == HRG_TASK_LIFTING;
-  }
-  return false;
-}
-
-int hrg_batch_snapshot(hrg_batch* b, void* states_out_dev, void* boxes_out_dev, void* stream) {
-  if (!b || !states_out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "snapshot: the stacking and hammering tasks keep their state in further arrays");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipMemcpyAsync(states_out_dev, b->d_states, sizeof(hrg_env_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (boxes_out_dev && b->task != HRG_TASK_REACH)
-    HIPCHK(hipMemcpyAsync(boxes_out_dev, b->d_boxes, sizeof(hrg_box_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return HRG_OK;
-}
-
-int hrg_batch_dataset_attach(hrg_batch* b, const hrg_dataset_desc* desc) {
-  if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
-  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "dataset: the stacking and hammering tasks keep their state in further arrays, which a dataset does not hold");
-  if (desc->sir_kind < HRG_SIR_NONE || desc->sir_kind > HRG_SIR_LIFTING) return fail(HRG_ERR_UNSUPPORTED, "unknown sir_kind");
-  if (!sir_fits_task(desc->sir_kind, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this state imitation reward does not read the observation of the batch's task");
-  if (!desc->ep_offset || !desc->states || !desc->obs || desc->n_episodes <= 0) return fail(HRG_ERR_INVALID, "dataset: null array or no episode");
-  if ((desc->boxes != nullptr) != (b->task != HRG_TASK_REACH)) return fail(HRG_ERR_INVALID, "dataset: a box array is needed exactly when the batch's task has a box block");
-  if (desc->ep_offset[0] != 0 || desc->ep_offset[desc->n_episodes] != desc->total_T) return fail(HRG_ERR_INVALID, "dataset: ep_offset must run from 0 to total_T");
-  for (int64_t k = 0; k < desc->n_episodes; k++) {
-    const int64_t T = desc->ep_offset[k + 1] - desc->ep_offset[k];
-    if (T <= 0) return fail(HRG_ERR_INVALID, "dataset: an episode without a transition (T = 0)");
-    if (T > INT32_MAX) return fail(HRG_ERR_INVALID, "dataset: episode too long");
-  }
-  if (desc->n_episodes > INT32_MAX) return fail(HRG_ERR_INVALID, "dataset: too many episodes");
-  if (!(desc->rsi_prob >= 0 && desc->rsi_prob <= 1)) return fail(HRG_ERR_INVALID, "dataset: rsi_prob must lie in [0, 1]");
-  if (desc->sir_kind != HRG_SIR_NONE) {
-    if (!(desc->iota_m > 0 && desc->iota_g > 0)) return fail(HRG_ERR_INVALID, "state imitation reward: iota_m and iota_g must be positive");
-    if (!(desc->alpha >= 0 && desc->alpha <= 1 && desc->beta >= 0 && desc->beta <= 1)) return fail(HRG_ERR_INVALID, "state imitation reward: alpha and beta must lie in [0, 1]");
-    if (!(desc->et_dist >= 0)) return fail(HRG_ERR_INVALID, "state imitation reward: et_dist must not be negative");
-    for (int fn : {desc->m_sim_fn, desc->g_sim_fn})
-      if (fn != HRG_SIM_GAUSSIAN && fn != HRG_SIM_TANH) return fail(HRG_ERR_INVALID, "state imitation reward: unknown similarity function");
-  }
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  b->has_dataset = false;   // until every buffer below exists
-  dataset_free(b);
-  DatasetDev& d = b->ds;
-  const size_t n = (size_t)b->n_envs, nep = (size_t)desc->n_episodes, tt = (size_t)desc->total_T;
-  HIPCHK(hipMalloc((void**)&d.ep_offset, sizeof(int64_t) * (nep + 1)));
-  HIPCHK(hipMalloc((void**)&d.states, sizeof(hrg_env_state) * tt));
-  if (desc->boxes) HIPCHK(hipMalloc((void**)&d.boxes, sizeof(hrg_box_state) * tt));
-  HIPCHK(hipMalloc((void**)&d.obs, sizeof(float) * HRG_OBS_DIM * (tt + nep)));
-  HIPCHK(hipMalloc(&d.cursor, sizeof(int32_t) * 3 * n));
-  HIPCHK(hipMalloc(&d.resets, sizeof(int32_t) * n));
-  HIPCHK(hipMalloc(&d.acc, sizeof(double) * 6 * n));
-  HIPCHK(hipMalloc(&d.finished, n));
-  HIPCHK(hipMemcpy((void*)d.ep_offset, desc->ep_offset, sizeof(int64_t) * (nep + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy((void*)d.states, desc->states, sizeof(hrg_env_state) * tt, hipMemcpyHostToDevice));
-  if (desc->boxes) HIPCHK(hipMemcpy((void*)d.boxes, desc->boxes, sizeof(hrg_box_state) * tt, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy((void*)d.obs, desc->obs, sizeof(float) * HRG_OBS_DIM * (tt + nep), hipMemcpyHostToDevice));
-  {   // until the first restore every env follows episode 0 from its first state
-    std::vector<int32_t> cur(3 * n);
-    for (size_t e = 0; e < n; e++) { cur[3 * e] = 0; cur[3 * e + 1] = 0; cur[3 * e + 2] = (int32_t)(desc->ep_offset[1] - desc->ep_offset[0]); }
-    HIPCHK(hipMemcpy(d.cursor, cur.data(), sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice));
-  }
-  HIPCHK(hipMemset(d.resets, 0, sizeof(int32_t) * n));
-  HIPCHK(hipMemset(d.acc, 0, sizeof(double) * 6 * n));
-  HIPCHK(hipMemset(d.finished, 0, n));
-  HIPCHK(hipDeviceSynchronize());
-  d.n_ep = desc->n_episodes;
-  d.total_T = desc->total_T;
-  b->dataset = *desc;
-  b->dataset.ep_offset = nullptr; b->dataset.states = nullptr; b->dataset.boxes = nullptr; b->dataset.obs = nullptr;
-  b->has_dataset = true;
-  return HRG_OK;
-}
-
-int hrg_batch_dataset_reset(hrg_batch* b, const uint8_t* mask_dev, float* obs_dev, void* stream) {
-  if (!b || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
-  const int rc = hrg_batch_reset(b, mask_dev, obs_dev, stream);
-  if (rc != HRG_OK) return rc;
-  hipLaunchKernelGGL(hrg_dataset_restore_kernel, dim3((unsigned)b->n_envs), dim3(64), 0, (hipStream_t)stream, b->dataset, b->ds, mask_dev, b->d_states, b->d_boxes, obs_dev,
-                     (float*)nullptr, (float*)nullptr, b->env_id0, b->n_envs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_batch_step_dataset(hrg_batch* b, double* actions_dev, float* obs_dev, float* term_obs_dev, float* reward_dev, uint8_t* done_dev, int32_t* info_dev, float* imit_dev,
-                           float* sir_dev, void* stream) {
-  if (!b || !actions_dev || !obs_dev || !reward_dev || !done_dev || !info_dev || !sir_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!term_obs_dev) return fail(HRG_ERR_INVALID, "hrg_batch_step_dataset needs term_obs_dev: the state a finished env reached is its terminal observation");
-  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
-  const bool air = b->has_expert && b->expert.reward_enabled;
-  if (air && !imit_dev) return fail(HRG_ERR_INVALID, "an expert with an imitation reward is attached: imit_dev must not be null");
-  const int rc = air ? hrg_batch_step_imitation(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, imit_dev, stream)
-                     : hrg_batch_step(b, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, stream);
-  if (rc != HRG_OK) return rc;
-  hipLaunchKernelGGL(hrg_sir_post_kernel, dim3((unsigned)((b->n_envs + HRG_DATASET_BLOCK - 1) / HRG_DATASET_BLOCK)), dim3(HRG_DATASET_BLOCK), 0, (hipStream_t)stream, b->dataset, b->ds,
-                     (const float*)obs_dev, (const float*)term_obs_dev, reward_dev, done_dev, sir_dev, b->n_envs);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(hrg_dataset_restore_kernel, dim3((unsigned)b->n_envs), dim3(64), 0, (hipStream_t)stream, b->dataset, b->ds, (const uint8_t*)b->ds.finished, b->d_states, b->d_boxes,
-                     obs_dev, term_obs_dev, sir_dev, b->env_id0, b->n_envs);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_batch_dataset_cursor(hrg_batch* b, int32_t* cursor_host) {
-  if (!b || !cursor_host) return fail(HRG_ERR_INVALID, "null argument");
-  if (!b->has_dataset) return fail(HRG_ERR_INVALID, "no dataset attached (hrg_batch_dataset_attach)");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(cursor_host, b->ds.cursor, sizeof(int32_t) * 3 * (size_t)b->n_envs, hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-// ---- hindsight experience replay (csrc/hrgym_her.h) ----
-struct hrg_her {
-  int device = 0;
-  hrg_her_desc desc;
-  HerDev d;
-  DeviceMem mem;                // behind every pointer of `d`
-  int64_t* d_total = nullptr;   // pinned host word the sampler's total is read back into
-  uint64_t calls = 0;           // sample calls so far (key of the draws)
-  ~hrg_her() {
-    if (d_total) hipHostFree(d_total);
-  }
-};
-
-static int her_desc_check(const hrg_her_desc* p, bool ring) {
-  if (p->goal_kind != HRG_GOAL_REACH && p->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal kind");
-  if (!ring) return HRG_OK;
-  if (p->strategy != HRG_HER_FUTURE && p->strategy != HRG_HER_FINAL && p->strategy != HRG_HER_EPISODE) return fail(HRG_ERR_UNSUPPORTED, "her: unknown goal selection strategy");
-  if (p->n_envs < 1 || p->horizon < 1) return fail(HRG_ERR_INVALID, "her: n_envs and horizon must be positive");
-  if (p->capacity <= p->horizon) return fail(HRG_ERR_INVALID, "her: capacity must exceed the horizon (a whole episode and one more transition have to fit the ring)");
-  return HRG_OK;
-}
-
-// the rest of the descriptor, behind buffer_columns (n_obs_cols and act_dim are in range)
-static int her_goal_check(const hrg_her_desc* p) {
-  const int ng = p->goal_kind == HRG_GOAL_REACH ? 6 : 3;
-  if (p->n_dg_in_obs != 0 && p->n_dg_in_obs != ng) return fail(HRG_ERR_INVALID, "her: n_dg_in_obs must be 0 or the goal's length");
-  for (int d = 0; d < p->n_dg_in_obs; d++)
-    if (p->dg_in_obs[d] < 0 || p->dg_in_obs[d] >= p->n_obs_cols) return fail(HRG_ERR_INVALID, "her: dg_in_obs outside the observation");
-  if (!(p->her_ratio >= 0 && p->her_ratio <= 1)) return fail(HRG_ERR_INVALID, "her: her_ratio must lie in [0, 1]");
-  if (p->rescale_actions)
-    for (int k = 0; k < p->act_dim; k++)
-      if (!(p->act_high[k] > p->act_low[k])) return fail(HRG_ERR_INVALID, "her: rescale_actions needs act_high > act_low");
-  return HRG_OK;
-}
-
-int hrg_her_create(const hrg_her_desc* desc, int32_t device, hrg_her** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  int rc = her_desc_check(desc, true);
-  if (rc != HRG_OK) return rc;
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_her> h(new hrg_her());
-  h->device = device;
-  h->desc = *desc;
-  HerDev& d = h->d;
-  DeviceMem& m = h->mem;
-  rc = buffer_columns("her", desc->n_obs_cols, desc->obs_cols, nullptr, desc->act_dim, m, d.view.obs_cols);
-  if (rc == HRG_OK) rc = her_goal_check(desc);
-  if (rc != HRG_OK) return rc;
-  d.view.n_obs_cols = desc->n_obs_cols;
-  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
-  if (!(m.zeros(d.pre, slots * HRG_OBS_DIM) && m.zeros(d.post, slots * HRG_OBS_DIM) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
-        m.zeros(d.done, slots) && m.zeros(d.trunc, slots) && m.zeros(d.ctype, slots) && m.zeros(d.ep_start, slots) && m.zeros(d.ep_len, slots) && m.zeros(d.w, n) &&
-        m.zeros(d.tail, n) && m.zeros(d.open, n) && m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) &&
-        m.zeros(d.ep.acc, n * HRG_HER_STATS_DIM)))
-    return nomem("her", m);
-  if (hipHostMalloc((void**)&h->d_total, sizeof(int64_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(HRG_ERR_HIP, "her: upload failed");
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_her_destroy(hrg_her* h) { destroy_handle(h); }
-
-int hrg_her_observe(hrg_her* h, const float* obs_dev, const uint8_t* mask_dev, int64_t* counts_dev, void* stream) {
-  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_env(hrg_her_observe_kernel, h->desc.n_envs, stream, h->desc, h->d, obs_dev, mask_dev, counts_dev);
-}
-
-int hrg_her_add(hrg_her* h, const double* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
-                const int32_t* info_dev, int64_t* counts_dev, void* stream) {
-  if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_env(hrg_her_add_kernel, h->desc.n_envs, stream, h->desc, h->d, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, counts_dev);
-}
-
-int hrg_her_sample(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* observation_dev, float* achieved_goal_dev, float* desired_goal_dev,
-                   float* next_observation_dev, float* next_achieved_goal_dev, float* next_desired_goal_dev, float* action_dev, float* reward_dev,
-                   float* done_dev, int64_t* index_dev, void* stream) {
-  if (!h || !counts_cum_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (batch_size < 1) return fail(HRG_ERR_INVALID, "her: batch_size must be positive");
-  if (!observation_dev || !achieved_goal_dev || !desired_goal_dev || !next_observation_dev || !next_achieved_goal_dev || !next_desired_goal_dev || !action_dev ||
-      !reward_dev || !done_dev)
-    return fail(HRG_ERR_INVALID, "her: null output");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemcpyAsync(h->d_total, counts_cum_dev + h->desc.n_envs, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  if (*h->d_total < 1) return fail(HRG_ERR_INVALID, "her: no finished episode in the buffer yet (nothing to sample)");
-  const int rc = launch_per_wave(hrg_her_sample_kernel, batch_size, stream, h->desc, h->d, counts_cum_dev, h->calls, (int)batch_size, observation_dev, achieved_goal_dev,
-                                 desired_goal_dev, next_observation_dev, next_achieved_goal_dev, next_desired_goal_dev, action_dev, reward_dev, done_dev, index_dev);
-  if (rc != HRG_OK) return rc;
-  h->calls++;
-  return HRG_OK;
-}
-
-// the width of the feature row achieved_goal | desired_goal | observation; the feature kernels keep one value per lane
-static int her_feature_dim(const hrg_her_desc& p) { return (p.goal_kind == HRG_GOAL_REACH ? 6 + 6 : 7 + 3) + p.n_obs_cols; }
-static int her_feature_check(const hrg_her_desc& p) {
-  if (her_feature_dim(p) > HRG_OBS_DIM) return fail(HRG_ERR_INVALID, "her: achieved_goal + desired_goal + observation exceed HRG_OBS_DIM values (the feature kernels keep one per lane)");
-  return HRG_OK;
-}
-
-int hrg_her_sample_features(hrg_her* h, int32_t batch_size, const int64_t* counts_cum_dev, float* features_dev, float* next_features_dev, float* action_dev,
-                            float* reward_dev, float* done_dev, int64_t* index_dev, void* stream) {
-  if (!h || !counts_cum_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (batch_size < 1) return fail(HRG_ERR_INVALID, "her: batch_size must be positive");
-  if (!features_dev || !next_features_dev || !action_dev || !reward_dev || !done_dev) return fail(HRG_ERR_INVALID, "her: null output");
-  int rc = her_feature_check(h->desc);
-  if (rc != HRG_OK) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  rc = launch_per_wave(hrg_her_sample_features_kernel, batch_size, stream, h->desc, h->d, counts_cum_dev, h->calls, (int)batch_size, features_dev, next_features_dev,
-                       action_dev, reward_dev, done_dev, index_dev);
-  if (rc != HRG_OK) return rc;
-  h->calls++;
-  return HRG_OK;
-}
-
-int hrg_her_features(hrg_her* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream) {
-  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!rows_dev) {   // the envs' current rows
-    rows_dev = h->d.ep.cur_obs;
-    n_rows = h->desc.n_envs;
-  }
-  if (n_rows < 1) return fail(HRG_ERR_INVALID, "her: n_rows must be positive");
-  const int rc = her_feature_check(h->desc);
-  if (rc != HRG_OK) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_wave(hrg_her_features_kernel, n_rows, stream, h->d.view, (int)h->desc.goal_kind, rows_dev, (int)n_rows, out_dev);
-}
-
-int hrg_her_stats(hrg_her* h, double* per_env_host, int32_t clear) {
-  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
-  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_HER_STATS_DIM, per_env_host, clear);
-}
-
-int hrg_her_counts(hrg_her* h, int64_t* counts_host) {
-  if (!h || !counts_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)h->desc.n_envs;
-  std::vector<int64_t> w(n), tail(n), open(n);
-  HIPCHK(hipMemcpy(w.data(), h->d.w, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(tail.data(), h->d.tail, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(open.data(), h->d.open, sizeof(int64_t) * n, hipMemcpyDeviceToHost));
-  counts_host[0] = counts_host[1] = 0;
-  for (size_t e = 0; e < n; e++) { counts_host[0] += w[e] - tail[e]; counts_host[1] += open[e] - tail[e]; }
-  counts_host[2] = (int64_t)h->calls;
-  return HRG_OK;
-}
-
-int hrg_her_export(hrg_her* h, int32_t env, float* pre_host, float* post_host, float* action_host, float* reward_host, uint8_t* done_host,
-                   uint8_t* truncated_host, int32_t* ctype_host, int64_t* ep_start_host, int32_t* ep_len_host, int64_t* state_host, float* cur_obs_host) {
-  if (!h || !pre_host || !post_host || !action_host || !reward_host || !done_host || !truncated_host || !ctype_host || !ep_start_host || !ep_len_host || !state_host ||
-      !cur_obs_host)
-    return fail(HRG_ERR_INVALID, "null argument");
-  if (env < 0 || env >= h->desc.n_envs) return fail(HRG_ERR_INVALID, "bad env index");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const HerDev& d = h->d;
-  const size_t cap = (size_t)h->desc.capacity, r0 = (size_t)env * cap, row = sizeof(float) * HRG_OBS_DIM, ad = (size_t)h->desc.act_dim;
-  HIPCHK(hipMemcpy(pre_host, d.pre + r0 * HRG_OBS_DIM, cap * row, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(post_host, d.post + r0 * HRG_OBS_DIM, cap * row, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(action_host, d.act + r0 * ad, cap * ad * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(reward_host, d.reward + r0, cap * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(done_host, d.done + r0, cap, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(truncated_host, d.trunc + r0, cap, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ctype_host, d.ctype + r0, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ep_start_host, d.ep_start + r0, cap * sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ep_len_host, d.ep_len + r0, cap * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(state_host + 0, d.w + env, sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(state_host + 1, d.tail + env, sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(state_host + 2, d.open + env, sizeof(int64_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs + (size_t)env * HRG_OBS_DIM, row, hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-int hrg_goal_reward_done(const hrg_her_desc* desc, const float* ag_dev, const float* dg_dev, const int32_t* ctype_dev, int32_t n, float* reward_dev,
-                         uint8_t* done_dev, void* stream) {
-  if (!desc || !ag_dev || !dg_dev || !ctype_dev || !reward_dev || !done_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (n < 1) return fail(HRG_ERR_INVALID, "her: n must be positive");
-  const int rc = her_desc_check(desc, false);
-  if (rc != HRG_OK) return rc;
-  hipLaunchKernelGGL(hrg_goal_reward_done_kernel, dim3(((unsigned)n + HRG_BUFFER_BLOCK - 1) / HRG_BUFFER_BLOCK), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, *desc, ag_dev, dg_dev,
-                     ctype_dev, (int)n, reward_dev, done_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-// ---- PPO rollout buffer (csrc/hrgym_rollout.h) ----
-struct hrg_rollout {
-  int device = 0;
-  hrg_rollout_desc desc;
-  RolloutDev d;
-  DeviceMem mem;           // behind every pointer of `d`
-  int32_t pos = 0;         // the next slot (the write position lives on the host)
-  bool computed = false;   // advantages and returns belong to the stored steps
-};
-
-int hrg_rollout_create(const hrg_rollout_desc* desc, int32_t device, hrg_rollout** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (desc->n_envs < 1 || desc->n_steps < 1) return fail(HRG_ERR_INVALID, "rollout: n_envs and n_steps must be positive");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_rollout> h(new hrg_rollout());
-  h->device = device;
-  h->desc = *desc;
-  RolloutDev& d = h->d;
-  DeviceMem& m = h->mem;
-  const int rc = buffer_columns("rollout", desc->n_obs_cols, desc->obs_cols, nullptr, desc->act_dim, m, d.view.obs_cols);
-  if (rc != HRG_OK) return rc;
-  if (!(desc->gamma >= 0 && desc->gamma <= 1)) return fail(HRG_ERR_INVALID, "rollout: gamma must lie in [0, 1]");
-  if (!(desc->gae_lambda >= 0 && desc->gae_lambda <= 1)) return fail(HRG_ERR_INVALID, "rollout: gae_lambda must lie in [0, 1]");
-  d.view.n_obs_cols = desc->n_obs_cols;
-  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->n_steps;
-  if (!(m.zeros(d.obs, slots * (size_t)desc->n_obs_cols) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) && m.zeros(d.value, slots) &&
-        m.zeros(d.log_prob, slots) && m.zeros(d.ep_start, slots) && m.zeros(d.adv, slots) && m.zeros(d.ret, slots) && m.zeros(d.flag, n) &&
-        m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_ROLLOUT_STATS_DIM)))
-    return nomem("rollout", m);
-  if (hipDeviceSynchronize() != hipSuccess) return fail(HRG_ERR_HIP, "rollout: upload failed");
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_rollout_destroy(hrg_rollout* h) { destroy_handle(h); }
-
-int hrg_rollout_view(hrg_rollout* h, const float* rows_dev, int32_t n_rows, float* out_dev, void* stream) {
-  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!rows_dev) {   // the envs' current rows
-    rows_dev = h->d.ep.cur_obs;
-    n_rows = h->desc.n_envs;
-  }
-  if (n_rows < 1) return fail(HRG_ERR_INVALID, "rollout: n_rows must be positive");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_wave(hrg_buffer_view_kernel, n_rows, stream, h->d.view, rows_dev, (const float*)nullptr, (int)n_rows, out_dev);
-}
-
-int hrg_rollout_observe(hrg_rollout* h, const float* obs_dev, const uint8_t* mask_dev, void* stream) {
-  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_env(hrg_rollout_observe_kernel, h->desc.n_envs, stream, h->desc, h->d, obs_dev, mask_dev);
-}
-
-int hrg_rollout_add(hrg_rollout* h, const float* actions_dev, const float* values_dev, const float* log_probs_dev, const float* terminal_values_dev,
-                    const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, void* stream) {
-  if (!h || !actions_dev || !values_dev || !log_probs_dev || !obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (h->pos >= h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is full (hrg_rollout_reset starts the next rollout)");
-  HIPCHK(hipSetDevice(h->device));
-  const int rc = launch_per_env(hrg_rollout_add_kernel, h->desc.n_envs, stream, h->desc, h->d, (int)h->pos, actions_dev, values_dev, log_probs_dev, terminal_values_dev, obs_dev,
-                                reward_dev, done_dev, info_dev);
-  if (rc != HRG_OK) return rc;
-  h->pos++;
-  h->computed = false;
-  return HRG_OK;
-}
-
-int hrg_rollout_compute(hrg_rollout* h, const float* last_values_dev, void* stream) {
-  if (!h || !last_values_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (h->pos < h->desc.n_steps) return fail(HRG_ERR_INVALID, "rollout: the buffer is not full yet (returns and advantages are computed over n_steps steps)");
-  HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_rollout_gae_kernel, dim3(((unsigned)h->desc.n_envs + HRG_BUFFER_BLOCK - 1) / HRG_BUFFER_BLOCK), dim3(HRG_BUFFER_BLOCK), 0, (hipStream_t)stream, h->desc,
-                     h->d, last_values_dev);
-  HIPCHK(hipGetLastError());
-  h->computed = true;
-  return HRG_OK;
-}
-
-int hrg_rollout_get(hrg_rollout* h, const int64_t* index_dev, int32_t batch_size, float* observations_dev, float* actions_dev, float* old_values_dev,
-                    float* old_log_prob_dev, float* advantages_dev, float* returns_dev, void* stream) {
-  if (!h || !index_dev || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev)
-    return fail(HRG_ERR_INVALID, "null argument");
-  if (batch_size < 1) return fail(HRG_ERR_INVALID, "rollout: batch_size must be positive");
-  if (!h->computed) return fail(HRG_ERR_INVALID, "rollout: no returns and advantages yet (hrg_rollout_compute comes first)");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_wave(hrg_rollout_get_kernel, batch_size, stream, h->desc, h->d, index_dev, (int)batch_size, observations_dev, actions_dev, old_values_dev, old_log_prob_dev,
-                         advantages_dev, returns_dev);
-}
-
-int hrg_rollout_reset(hrg_rollout* h) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  h->pos = 0;
-  h->computed = false;
-  return HRG_OK;
-}
-
-int hrg_rollout_stats(hrg_rollout* h, double* per_env_host, int32_t clear) {
-  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
-  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_ROLLOUT_STATS_DIM, per_env_host, clear);
-}
-
-int hrg_rollout_export(hrg_rollout* h, float* observations_host, float* actions_host, float* rewards_host, float* values_host, float* log_probs_host,
-                       float* episode_starts_host, float* advantages_host, float* returns_host, float* cur_obs_host, float* flags_host, double* run_return_host,
-                       int32_t* run_length_host, double* stats_host, int64_t* state_host) {
-  if (!h || !observations_host || !actions_host || !rewards_host || !values_host || !log_probs_host || !episode_starts_host || !advantages_host || !returns_host ||
-      !cur_obs_host || !flags_host || !run_return_host || !run_length_host || !stats_host || !state_host)
-    return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const RolloutDev& d = h->d;
-  const size_t n = (size_t)h->desc.n_envs, T = (size_t)h->desc.n_steps, slots = n * T;
-  HIPCHK(hipMemcpy(observations_host, d.obs, slots * sizeof(float) * (size_t)h->desc.n_obs_cols, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(actions_host, d.act, slots * sizeof(float) * (size_t)h->desc.act_dim, hipMemcpyDeviceToHost));
-  std::vector<float> tm(slots);   // a time-major array on its way into the flat order
-  const float* scalars[6] = {d.reward, d.value, d.log_prob, d.ep_start, d.adv, d.ret};
-  float* flat[6] = {rewards_host, values_host, log_probs_host, episode_starts_host, advantages_host, returns_host};
-  for (int a = 0; a < 6; a++) {
-    HIPCHK(hipMemcpy(tm.data(), scalars[a], slots * sizeof(float), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < n; e++)
-      for (size_t t = 0; t < T; t++) flat[a][e * T + t] = tm[t * n + e];
-  }
-  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(flags_host, d.flag, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_return_host, d.ep.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_length_host, d.ep.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(stats_host, d.ep.acc, n * sizeof(double) * HRG_ROLLOUT_STATS_DIM, hipMemcpyDeviceToHost));
-  state_host[0] = h->pos;
-  state_host[1] = h->computed ? 1 : 0;
-  return HRG_OK;
-}
-
-// ---- uniform replay buffer (csrc/hrgym_replay.h) ----
-struct hrg_replay {
-  int device = 0;
-  hrg_replay_desc desc;
-  ReplayDev d;
-  int32_t pos = 0;      // the next slot (the write position lives on the host)
-  bool full = false;    // every slot holds a transition
-  uint64_t calls = 0;   // sample calls that drew their indices (key of the draws)
-  DeviceMem mem;        // behind every pointer of `d`
-};
-
-int hrg_replay_create(const hrg_replay_desc* desc, int32_t device, hrg_replay** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (desc->n_envs < 1 || desc->capacity < 1) return fail(HRG_ERR_INVALID, "replay: n_envs and capacity must be positive");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_replay> h(new hrg_replay());
-  h->device = device;
-  h->desc = *desc;
-  ReplayDev& d = h->d;
-  BufferView& v = d.view;
-  DeviceMem& m = h->mem;
-  const size_t n = (size_t)desc->n_envs, slots = n * (size_t)desc->capacity;
-  v.observe_time = desc->observe_time ? 1 : 0;
-  const int K = desc->n_obs_cols + v.observe_time;
-  const int rc = buffer_columns("replay", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols);
-  if (rc != HRG_OK) return rc;
-  double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
-  if (int rs = view_statistics("replay", K, desc->normalize, desc->squash, desc->squash_factor, desc->mean, desc->std, mean, sd)) return rs;
-  d.n_envs = desc->n_envs; d.capacity = desc->capacity; d.act_dim = desc->act_dim; d.seed = desc->seed;
-  v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
-  if (!(m.zeros(d.obs, slots * (size_t)K) && m.zeros(d.nobs, slots * (size_t)K) && m.zeros(d.act, slots * (size_t)desc->act_dim) && m.zeros(d.reward, slots) &&
-        m.zeros(d.done, slots) && m.zeros(d.timeout, slots) && m.zeros(d.cur_time, n) && m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) &&
-        m.zeros(d.ep.run_len, n) && m.zeros(d.ep.acc, n * HRG_REPLAY_STATS_DIM)))
-    return nomem("replay", m);
-  if (int ru = view_statistics_upload("replay", m, v, mean, sd)) return ru;
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_replay_destroy(hrg_replay* h) { destroy_handle(h); }
-
-int hrg_replay_view(hrg_replay* h, const float* rows_dev, const float* time_dev, int32_t n_rows, float* out_dev, void* stream) {
-  if (!h || !out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!rows_dev) {   // the envs' current rows
-    rows_dev = h->d.ep.cur_obs;
-    time_dev = h->d.cur_time;
-    n_rows = h->desc.n_envs;
-  }
-  if (n_rows < 1) return fail(HRG_ERR_INVALID, "replay: n_rows must be positive");
-  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_wave(hrg_buffer_view_kernel, n_rows, stream, h->d.view, rows_dev, time_dev, (int)n_rows, out_dev);
-}
-
-int hrg_replay_observe(hrg_replay* h, const float* obs_dev, const float* time_dev, const uint8_t* mask_dev, void* stream) {
-  if (!h || !obs_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the rows' time values");
-  HIPCHK(hipSetDevice(h->device));
-  return launch_per_env(hrg_replay_observe_kernel, h->desc.n_envs, stream, h->d, obs_dev, time_dev, mask_dev);
-}
-
-int hrg_replay_add(hrg_replay* h, const float* actions_dev, const float* obs_dev, const float* term_obs_dev, const float* reward_dev, const uint8_t* done_dev,
-                   const int32_t* info_dev, const float* imit_dev, const float* sir_dev, void* stream) {
-  if (!h || !actions_dev || !obs_dev || !term_obs_dev || !reward_dev || !done_dev || !info_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "replay: an imitation row or a state imitation row, not both");
-  if (h->d.view.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "replay: observe_time needs the state imitation rows (their time columns)");
-  HIPCHK(hipSetDevice(h->device));
-  const int rc = launch_per_env(hrg_replay_add_kernel, h->desc.n_envs, stream, h->d, (int)h->pos, actions_dev, obs_dev, term_obs_dev, reward_dev, done_dev, info_dev, imit_dev, sir_dev);
-  if (rc != HRG_OK) return rc;
-  if (++h->pos == h->desc.capacity) {   // ReplayBuffer.add: self.full = True; self.pos = 0
-    h->pos = 0;
-    h->full = true;
-  }
-  return HRG_OK;
-}
-
-int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in_dev, float* observations_dev, float* actions_dev, float* next_observations_dev,
-                      float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  if (batch_size < 1) return fail(HRG_ERR_INVALID, "replay: batch_size must be positive");
-  if (!observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev) return fail(HRG_ERR_INVALID, "replay: null output");
-  const int64_t upper = h->full ? h->desc.capacity : h->pos;
-  if (upper < 1) return fail(HRG_ERR_INVALID, "replay: the buffer is empty (nothing to sample)");
-  HIPCHK(hipSetDevice(h->device));
-  const int rc = launch_per_wave(hrg_replay_sample_kernel, batch_size, stream, h->d, upper, h->calls, index_in_dev, (int)batch_size, observations_dev, actions_dev,
-                                 next_observations_dev, dones_dev, rewards_dev, index_out_dev);
-  if (rc != HRG_OK) return rc;
-  if (!index_in_dev) h->calls++;
-  return HRG_OK;
-}
-
-int hrg_replay_stats(hrg_replay* h, double* per_env_host, int32_t clear) {
-  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
-  return buffer_stats(h->device, h->d.ep.acc, h->desc.n_envs, HRG_REPLAY_STATS_DIM, per_env_host, clear);
-}
-
-int hrg_replay_export(hrg_replay* h, float* observations_host, float* next_observations_host, float* actions_host, float* rewards_host, uint8_t* dones_host,
-                      uint8_t* timeouts_host, float* cur_obs_host, float* cur_time_host, double* run_return_host, int32_t* run_length_host, double* stats_host,
-                      int64_t* state_host) {
-  if (!h || !observations_host || !next_observations_host || !actions_host || !rewards_host || !dones_host || !timeouts_host || !cur_obs_host || !cur_time_host ||
-      !run_return_host || !run_length_host || !stats_host || !state_host)
-    return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const ReplayDev& d = h->d;
-  const size_t n = (size_t)h->desc.n_envs, slots = n * (size_t)h->desc.capacity, K = (size_t)(d.view.n_obs_cols + d.view.observe_time);
-  HIPCHK(hipMemcpy(observations_host, d.obs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(next_observations_host, d.nobs, slots * sizeof(float) * K, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(actions_host, d.act, slots * sizeof(float) * (size_t)d.act_dim, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rewards_host, d.reward, slots * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(dones_host, d.done, slots, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(timeouts_host, d.timeout, slots, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cur_obs_host, d.ep.cur_obs, n * sizeof(float) * HRG_OBS_DIM, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(cur_time_host, d.cur_time, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_return_host, d.ep.run_ret, n * sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(run_length_host, d.ep.run_len, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(stats_host, d.ep.acc, n * sizeof(double) * HRG_REPLAY_STATS_DIM, hipMemcpyDeviceToHost));
-  state_host[0] = h->pos;
-  state_host[1] = h->full ? 1 : 0;
-  state_host[2] = (int64_t)h->calls;
-  return HRG_OK;
-}
-
-int hrg_replay_size(hrg_replay* h, int64_t* size_host) {
-  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
-  size_host[0] = h->pos;
-  size_host[1] = h->full ? 1 : 0;
-  size_host[2] = (int64_t)h->calls;
-  size_host[3] = (int64_t)h->mem.bytes;
-  return HRG_OK;
-}
-
-// ---- SAC learner (csrc/hrgym_sac.h) ----
-struct hrg_sac {
-  int device = 0;
-  hrg_sac_desc desc;
-  SacDev d;
-  uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
-  uint64_t act_calls = 0;   // act calls that drew their noise
-  DeviceMem mem;            // one allocation behind every pointer of `d`
-};
-
-// the offsets of the parameter layout (csrc/hrgym_sac.h) into d; returns the number of parameters
-static int32_t sac_layout(const hrg_sac_desc& c, SacDev& d) {
-  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_SAC_HIDDEN;
-  int32_t o = 0;
-  for (int l = 0; l < c.depth; l++) {
-    d.a_w[l] = o; o += H * (l ? H : K);
-    d.a_b[l] = o; o += H;
-  }
-  d.a_hw = o; o += 2 * A * H;
-  d.a_hb = o; o += 2 * A;
-  d.n_actor = o;
-  for (int q = 0; q < 2; q++) {
-    for (int l = 0; l < c.depth; l++) {
-      d.q_w[q][l] = o; o += H * (l ? H : K + A);
-      d.q_b[q][l] = o; o += H;
-    }
-    d.q_ow[q] = o; o += H;
-    d.q_ob[q] = o; o += 1;
-  }
-  d.n_critic = (o - d.n_actor) / 2;
-  d.n_params = o + 1;   // log_ent_coef
-  return d.n_params;
-}
-
-int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (int rc = learner_shape("sac", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_SAC_MAX_BATCH)) return rc;
-  if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
-  if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
-    return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
-  if (!desc->auto_ent_coef && desc->ent_coef <= 0.0) return fail(HRG_ERR_INVALID, "sac: a fixed ent_coef must be positive");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_sac> h(new hrg_sac());
-  h->device = device;
-  h->desc = *desc;
-  SacDev& d = h->d;
-  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE;
-  d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
-  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
-  const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
-  Carver<float> f;
-  f.take(d.a_pi, B * A);
-  f.take(d.logp, B);
-  f.take(d.logp_next, B);
-  f.take(d.y, B);
-  f.take(d.q, SAC_NQ * B);
-  f.take(d.dqda, 2 * B * A);
-  f.take(d.part, (size_t)d.tiles * P);
-  f.take(d.grad, P);
-  f.take(d.loss_part, (size_t)d.tiles * SAC_NLOSS);
-  f.take(d.losses, 4);
-  if (!f.alloc(h->mem)) return nomem("sac", h->mem);
-  HIPCHK(hipDeviceSynchronize());
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_sac_destroy(hrg_sac* h) { destroy_handle(h); }
-
-int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
-  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
-  size_host[0] = h->d.n_params;
-  size_host[1] = h->d.n_actor;
-  size_host[2] = h->d.n_critic;
-  size_host[3] = (int64_t)h->steps;
-  size_host[4] = (int64_t)h->act_calls;
-  size_host[5] = (int64_t)h->mem.bytes;
-  return HRG_OK;
-}
-
-int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions_dev, const float* next_observations_dev, const float* dones_dev, const float* rewards_dev,
-                 const float* eps_pi_dev, const float* eps_next_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, float* target_dev, double learning_rate,
-                 void* stream) {
-  if (!h || !observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev || !params_dev || !adam_m_dev || !adam_v_dev || !target_dev)
-    return fail(HRG_ERR_INVALID, "null argument");
-  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "sac: learning_rate must be finite and not negative");
-  HIPCHK(hipSetDevice(h->device));
-  const SacDev& d = h->d;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 pair((unsigned)d.tiles, 2), block(MLP_BLOCK);
-  double bc1, bc2;
-  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimisers' step count
-  const bool polyak = h->steps % (uint64_t)h->desc.target_update_interval == 0;
-  const int n_crit2 = 2 * d.n_critic;
-  hipLaunchKernelGGL(hrg_sac_policy_kernel, pair, block, 0, st, d, (const float*)params_dev, (const float*)target_dev, observations_dev, next_observations_dev, dones_dev,
-                     rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
-  hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
-                     (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
-  hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
-  hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
-                     learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
-  HIPCHK(hipGetLastError());
-  h->steps++;
-  return HRG_OK;
-}
-
-int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream) {
-  if (!h || !params_dev || !obs_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (n < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
-  HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
-                     (int)(deterministic != 0), h->act_calls, actions_dev);
-  HIPCHK(hipGetLastError());
-  if (!deterministic && !eps_dev) h->act_calls++;
-  return HRG_OK;
-}
-
-int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  const SacDev& d = h->d;
-  const size_t B = (size_t)d.B;
-  return export_floats(h->device, {{y_host, d.y, B}, {logp_host, d.logp, B}, {logp_next_host, d.logp_next, B}, {q_host, d.q, SAC_NQ * B},
-                                   {grad_host, d.grad, (size_t)d.n_params}, {losses_host, d.losses, 4}});
-}
-
-// ---- PPO learner (csrc/hrgym_ppo.h) ----
-struct hrg_ppo {
-  int device = 0;
-  hrg_ppo_desc desc;
-  PpoDev d;
-  uint64_t steps = 0;           // minibatch steps so far: Adam's step count
-  uint64_t forward_calls = 0;   // forward calls that drew their noise
-  int n_blocks = 0;             // blocks of 256 parameters
-  DeviceMem mem;                // one allocation behind every float pointer of `d`, one behind every double pointer
-};
-
-// the offsets of the parameter layout (csrc/hrgym_ppo.h) into d; returns the number of parameters
-static int32_t ppo_layout(const hrg_ppo_desc& c, PpoDev& d) {
-  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_PPO_HIDDEN;
-  int32_t o = 0;
-  for (int n = 0; n < d.nets; n++)
-    for (int l = 0; l < c.depth; l++) {
-      d.w[n][l] = o; o += H * (l ? H : K);
-      d.b[n][l] = o; o += H;
-    }
-  d.hw = o; o += (A + 1) * H;
-  d.hb = o; o += A + 1;
-  d.ls = o; o += A;
-  d.n_params = o;
-  return o;
-}
-
-int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (desc->use_sde) return fail(HRG_ERR_UNSUPPORTED, "ppo: use_sde: state dependent exploration is not covered");
-  if (desc->target_kl_set) return fail(HRG_ERR_UNSUPPORTED, "ppo: target_kl: the early stop needs a host readback per minibatch");
-  if (desc->policy != HRG_PPO_MLP_POLICY) return fail(HRG_ERR_UNSUPPORTED, "ppo: policy = " + std::to_string(desc->policy) + ": the kernels cover MlpPolicy");
-  if (int rc = learner_shape("ppo", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_PPO_MAX_BATCH)) return rc;
-  if (desc->separate != 0 && desc->separate != 1) return fail(HRG_ERR_UNSUPPORTED, "ppo: separate must be 0 (shared trunk) or 1 (separate trunks)");
-  if (desc->rollout_size < 0 || desc->rollout_size % desc->batch_size)
-    return fail(HRG_ERR_UNSUPPORTED, "ppo: rollout_size = " + std::to_string(desc->rollout_size) + " is not divisible by batch_size = " + std::to_string(desc->batch_size) +
-                                         ": the learner takes no short last minibatch");
-  if (!std::isfinite(desc->ent_coef) || !std::isfinite(desc->vf_coef) || !std::isfinite(desc->max_grad_norm) || desc->ent_coef < 0.0 || desc->vf_coef < 0.0 ||
-      desc->max_grad_norm <= 0.0)
-    return fail(HRG_ERR_INVALID, "ppo: ent_coef and vf_coef must be finite and not negative, max_grad_norm finite and positive");
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_ppo> h(new hrg_ppo());
-  h->device = device;
-  h->desc = *desc;
-  PpoDev& d = h->d;
-  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_PPO_TILE;
-  d.nets = desc->separate ? 2 : 1;
-  d.normalize = desc->normalize_advantage ? 1 : 0;
-  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm; d.seed = desc->seed;
-  const size_t P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;
-  h->n_blocks = (int)((P + MLP_BLOCK - 1) / MLP_BLOCK);
-  Carver<float> f;
-  f.take(d.values, B);
-  f.take(d.logp, B);
-  f.take(d.ratio, B);
-  f.take(d.part, (size_t)d.tiles * P);
-  f.take(d.grad, P);
-  f.take(d.loss_part, (size_t)d.tiles * PPO_NPART);
-  f.take(d.diag, HRG_PPO_NDIAG);
-  Carver<double> dbl;
-  dbl.take(d.adv_stat, 2);
-  dbl.take(d.block_sq, (size_t)h->n_blocks);
-  if (!f.alloc(h->mem) || !dbl.alloc(h->mem)) return nomem("ppo", h->mem);
-  HIPCHK(hipDeviceSynchronize());
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_ppo_destroy(hrg_ppo* h) { destroy_handle(h); }
-
-int hrg_ppo_sizes(hrg_ppo* h, int64_t* size_host) {
-  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
-  size_host[0] = h->d.n_params;
-  size_host[1] = h->d.nets == 2 ? h->d.w[1][0] : h->d.hw;   // (the first network starts at 0)
-  size_host[2] = h->d.nets;
-  size_host[3] = (int64_t)h->steps;
-  size_host[4] = (int64_t)h->forward_calls;
-  size_host[5] = (int64_t)h->mem.bytes;
-  return HRG_OK;
-}
-
-int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions_dev, const float* old_values_dev, const float* old_log_prob_dev,
-                 const float* advantages_dev, const float* returns_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, double learning_rate, double clip_range,
-                 double clip_range_vf, void* stream) {
-  if (!h || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev || !params_dev || !adam_m_dev || !adam_v_dev)
-    return fail(HRG_ERR_INVALID, "null argument");
-  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "ppo: learning_rate must be finite and not negative");
-  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(HRG_ERR_INVALID, "ppo: clip_range must be finite and positive");
-  if (std::isnan(clip_range_vf)) return fail(HRG_ERR_INVALID, "ppo: clip_range_vf must be a number (negative: no clipping)");
-  HIPCHK(hipSetDevice(h->device));
-  const PpoDev& d = h->d;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks);
-  double bc1, bc2;
-  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimiser's step count
-  if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1), block, 0, st, d, advantages_dev);
-  hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
-                     old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
-  hipLaunchKernelGGL(hrg_ppo_reduce_kernel, flat, block, 0, st, d);
-  hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, learning_rate, bc1, bc2);
-  HIPCHK(hipGetLastError());
-  h->steps++;
-  return HRG_OK;
-}
-
-int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
-                    float* values_dev, float* log_probs_dev, void* stream) {
-  if (!h || !params_dev || !obs_dev || !values_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (actions_dev && !log_probs_dev) return fail(HRG_ERR_INVALID, "ppo: actions without log_probs");
-  if (n < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
-  HIPCHK(hipSetDevice(h->device));
-  const int value_only = actions_dev ? 0 : 1;
-  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T, value_only ? 1u : (unsigned)h->d.nets), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d,
-                     params_dev, obs_dev, (int)n, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev, log_probs_dev);
-  HIPCHK(hipGetLastError());
-  if (!value_only && !deterministic && !eps_dev) h->forward_calls++;
-  return HRG_OK;
-}
-
-int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  const PpoDev& d = h->d;
-  const size_t B = (size_t)d.B;
-  return export_floats(h->device, {{values_host, d.values, B}, {log_prob_host, d.logp, B}, {ratio_host, d.ratio, B}, {grad_host, d.grad, (size_t)d.n_params},
-                                   {diag_host, d.diag, HRG_PPO_NDIAG}});
-}
-
-int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  h->steps = steps;
-  h->act_calls = act_calls;
-  return HRG_OK;
-}
-
-int hrg_ppo_restore(hrg_ppo* h, uint64_t steps, uint64_t forward_calls) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  h->steps = steps;
-  h->forward_calls = forward_calls;
-  return HRG_OK;
-}
-
-// ---- evaluation (csrc/hrgym_eval.h) ----
-struct hrg_eval {
-  int device = 0;
-  hrg_eval_desc desc;
-  EvalDev d;
-  int64_t steps = 0;   // steps since begin: the finishing step index of the records
-  DeviceMem mem;       // behind every pointer of `d`
-};
-
-int hrg_eval_create(const hrg_eval_desc* desc, int32_t device, hrg_eval** out) {
-  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (desc->n_envs < 1 || desc->n_policies < 1) return fail(HRG_ERR_INVALID, "eval: n_envs and n_policies must be positive");
-  if (desc->n_envs % desc->n_policies)
-    return fail(HRG_ERR_INVALID, "eval: n_envs = " + std::to_string(desc->n_envs) + " is not divisible by n_policies = " + std::to_string(desc->n_policies) +
-                                     ": every parameter set steps a group of the same size");
-  if (desc->n_eval_episodes < 1) return fail(HRG_ERR_INVALID, "eval: n_eval_episodes must be positive");
-  const int32_t group = desc->n_envs / desc->n_policies;
-  const int64_t max_quota = ((int64_t)desc->n_eval_episodes + group - 1) / group;
-  if (max_quota > HRG_EVAL_MAX_EPISODES_PER_ENV)
-    return fail(HRG_ERR_INVALID, "eval: " + std::to_string(desc->n_eval_episodes) + " episodes over groups of " + std::to_string(group) + " envs are " +
-                                     std::to_string(max_quota) + " per env, above HRG_EVAL_MAX_EPISODES_PER_ENV = " + std::to_string(HRG_EVAL_MAX_EPISODES_PER_ENV));
-  const int time_col = desc->observe_time ? 1 : 0;
-  int width = desc->n_obs_cols + time_col;
-  if (desc->goal_env) {
-    if (desc->observe_time || desc->normalize) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_env with observe_time or normalize: a goal env's feature row is a plain selection");
-    if (desc->goal_kind != HRG_GOAL_REACH && desc->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_kind = " + std::to_string(desc->goal_kind));
-    width = (desc->goal_kind == HRG_GOAL_REACH ? 6 + 6 : 7 + 3) + desc->n_obs_cols;
-    if (width > HRG_OBS_DIM)
-      return fail(HRG_ERR_UNSUPPORTED, "eval: a feature row of " + std::to_string(width) + " values; the kernels handle one value per lane, at most HRG_OBS_DIM");
-  }
-  for (int j = 0; j < HRG_ACT_DIM; j++)
-    if (j < desc->act_dim && (!std::isfinite(desc->act_low[j]) || !std::isfinite(desc->act_high[j]) || desc->act_low[j] > desc->act_high[j]))
-      return fail(HRG_ERR_INVALID, "eval: act_low and act_high must be finite and ordered");
-  double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
-  if (int rs = view_statistics("eval", desc->n_obs_cols + time_col, desc->normalize, desc->squash, desc->squash_factor, desc->mean, desc->std, mean, sd)) return rs;
-  HIPCHK(hipSetDevice(device));
-  std::unique_ptr<hrg_eval> h(new hrg_eval());
-  h->device = device;
-  h->desc = *desc;
-  EvalDev& d = h->d;
-  BufferView& v = d.view;
-  DeviceMem& m = h->mem;
-  v.observe_time = time_col;
-  if (int rc = buffer_columns("eval", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols)) return rc;
-  v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
-  d.n_envs = desc->n_envs; d.n_policies = desc->n_policies; d.group = group; d.n_episodes = desc->n_eval_episodes; d.max_quota = (int32_t)max_quota;
-  d.act_dim = desc->act_dim; d.goal_env = desc->goal_env ? 1 : 0; d.goal_kind = desc->goal_kind; d.width = width;
-  const size_t n = (size_t)desc->n_envs;
-  double *low_dev = nullptr, *high_dev = nullptr;
-  if (!(m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) && m.zeros(d.cur_time, n) && m.zeros(d.count, n) &&
-        m.zeros(d.quota, n) && m.zeros(d.records, n * (size_t)max_quota * HRG_EVAL_RECORD_DIM) && m.zeros(d.remaining, 1) && m.zeros(low_dev, HRG_ACT_DIM) &&
-        m.zeros(high_dev, HRG_ACT_DIM)))
-    return nomem("eval", m);
-  if (hipMemcpy(low_dev, desc->act_low, sizeof desc->act_low, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(high_dev, desc->act_high, sizeof desc->act_high, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(HRG_ERR_HIP, "eval: upload failed");
-  d.act_low = low_dev;
-  d.act_high = high_dev;
-  if (int ru = view_statistics_upload("eval", m, v, mean, sd)) return ru;
-  *out = h.release();
-  return HRG_OK;
-}
-
-void hrg_eval_destroy(hrg_eval* h) { destroy_handle(h); }
-
-int hrg_eval_begin(hrg_eval* h, const float* obs_dev, const float* time_dev, float* view_dev, void* stream) {
-  if (!h || !obs_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the rows' time values");
-  HIPCHK(hipSetDevice(h->device));
-  h->steps = 0;
-  return launch_per_env(hrg_eval_begin_kernel, h->desc.n_envs, stream, h->d, obs_dev, time_dev, view_dev);
-}
-
-int hrg_eval_step(hrg_eval* h, const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, const float* imit_dev,
-                  const float* sir_dev, float* view_dev, void* stream) {
-  if (!h || !obs_dev || !reward_dev || !done_dev || !info_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "eval: an imitation row or a state imitation row, not both");
-  if (h->d.view.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the state imitation rows (their time columns)");
-  HIPCHK(hipSetDevice(h->device));
-  const int rc = launch_per_env(hrg_eval_step_kernel, h->desc.n_envs, stream, h->d, h->steps, obs_dev, reward_dev, done_dev, info_dev, imit_dev, sir_dev, view_dev);
-  if (rc != HRG_OK) return rc;
-  h->steps++;
-  return HRG_OK;
-}
-
-// what both policy entries end with: the widths of the learner against the evaluator's, then the launch
-static int eval_policy(hrg_eval* h, bool sac, const EvalActor& a, int learner_device, const char* name, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
-  if (!params_dev || !view_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (learner_device != h->device)
-    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner lives on device " + std::to_string(learner_device) + ", the evaluator on device " +
-                                     std::to_string(h->device));
-  if (a.K != h->d.width || a.A != h->d.act_dim)
-    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner takes observations of " + std::to_string(a.K) + " and emits actions of " + std::to_string(a.A) +
-                                     " values, the evaluator's view has " + std::to_string(h->d.width) + " and its actions " + std::to_string(h->d.act_dim));
-  HIPCHK(hipSetDevice(h->device));
-  const dim3 grid(((unsigned)h->d.group + MLP_T - 1) / MLP_T, (unsigned)h->d.n_policies), block(MLP_BLOCK);
-  if (sac) hipLaunchKernelGGL(hrg_eval_policy_kernel<true>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
-  else hipLaunchKernelGGL(hrg_eval_policy_kernel<false>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
-  HIPCHK(hipGetLastError());
-  return HRG_OK;
-}
-
-int hrg_eval_policy_sac(hrg_eval* h, hrg_sac* sac, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
-  if (!h || !sac) return fail(HRG_ERR_INVALID, "null argument");
-  const SacDev& s = sac->d;
-  EvalActor a;
-  for (int l = 0; l < HRG_SAC_MAX_DEPTH; l++) { a.w[l] = s.a_w[l]; a.b[l] = s.a_b[l]; }
-  a.hw = s.a_hw; a.hb = s.a_hb; a.nout = 2 * s.A;   // (sac_squash reads both heads)
-  a.depth = s.depth; a.K = s.K; a.A = s.A; a.n_params = s.n_params;
-  return eval_policy(h, true, a, sac->device, "sac", params_dev, view_dev, actions_dev, stream);
-}
-
-int hrg_eval_policy_ppo(hrg_eval* h, hrg_ppo* ppo, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
-  if (!h || !ppo) return fail(HRG_ERR_INVALID, "null argument");
-  const PpoDev& p = ppo->d;
-  EvalActor a;
-  for (int l = 0; l < HRG_PPO_MAX_DEPTH; l++) { a.w[l] = p.w[0][l]; a.b[l] = p.b[0][l]; }   // network 0: the shared trunk, or the policy's
-  a.hw = p.hw; a.hb = p.hb; a.nout = p.A;   // the first A rows of the [A + 1][64] heads: action_net
-  a.depth = p.depth; a.K = p.K; a.A = p.A; a.n_params = p.n_params;
-  return eval_policy(h, false, a, ppo->device, "ppo", params_dev, view_dev, actions_dev, stream);
-}
-
-int hrg_eval_remaining(hrg_eval* h, int64_t* remaining_host, void* stream) {
-  if (!h || !remaining_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(hrg_eval_remaining_kernel, dim3(1), dim3(MLP_BLOCK), 0, st, h->d);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(remaining_host, h->d.remaining, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return HRG_OK;
-}
-
-int hrg_eval_export(hrg_eval* h, int32_t* counts_host, int32_t* quota_host, double* records_host) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipDeviceSynchronize());
-  const EvalDev& d = h->d;
-  const size_t n = (size_t)d.n_envs;
-  if (counts_host) HIPCHK(hipMemcpy(counts_host, d.count, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (quota_host) HIPCHK(hipMemcpy(quota_host, d.quota, n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (records_host) HIPCHK(hipMemcpy(records_host, d.records, n * (size_t)d.max_quota * HRG_EVAL_RECORD_DIM * sizeof(double), hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-int hrg_eval_size(hrg_eval* h, int64_t* size_host) {
-  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
-  size_host[0] = h->d.max_quota;
-  size_host[1] = h->steps;
-  size_host[2] = h->d.width;
-  size_host[3] = (int64_t)h->mem.bytes;
-  return HRG_OK;
-}
-
-int hrg_batch_launch_order(hrg_batch* b, int32_t* order_host, int32_t* n_busy_host) {
-  if (!b || !order_host || !n_busy_host) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  const size_t n = (size_t)b->n_envs;
-  HIPCHK(hipMemcpy(order_host, b->d_order + (size_t)b->parity * n, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n_busy_host, b->d_order + 2 * n + 2 * (size_t)b->parity, sizeof(int32_t), hipMemcpyDeviceToHost));   // the front counter that filled this order
-  return HRG_OK;
-}
-
-int hrg_batch_contacts(hrg_batch* b, int32_t* pairs_host, int32_t* ncon_host) {
-  if (!b) return fail(HRG_ERR_INVALID, "null batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  std::vector<hrg_env_state> st((size_t)b->n_envs);
-  HIPCHK(hipMemcpy(st.data(), b->d_states, sizeof(hrg_env_state) * (size_t)b->n_envs, hipMemcpyDeviceToHost));
-  for (int e = 0; e < b->n_envs; e++) {
-    ncon_host[e] = st[e].ncon;
-    memcpy(pairs_host + (size_t)e * HRG_NCON_MAX * 2, st[e].con_pairs, sizeof(int32_t) * HRG_NCON_MAX * 2);
-  }
-  return HRG_OK;
-}
-
-int hrg_batch_capsules(hrg_batch* b, double* robot_host, double* human_host, int32_t* n_human_host) {
-  if (!b) return fail(HRG_ERR_INVALID, "null batch");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(robot_host, b->d_rcaps, sizeof(double) * 7 * HRG_NSHIELD_RCAP * (size_t)b->n_envs, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(human_host, b->d_hcaps, sizeof(double) * 7 * HRG_NHCAP_MAX * (size_t)b->n_envs, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n_human_host, b->d_nh, sizeof(int32_t) * (size_t)b->n_envs, hipMemcpyDeviceToHost));
-  return HRG_OK;
-}
-
-int hrg_batch_get_state(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, buf_host, bytes, true, nullptr); }
-int hrg_batch_set_state(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, (void*)buf_host, bytes, false, nullptr); }
-int hrg_batch_get_box(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, buf_host, bytes, true, nullptr); }
-int hrg_batch_set_box(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, (void*)buf_host, bytes, false, nullptr); }
-int hrg_batch_get_stack(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_stacks, buf_host, bytes, true, "not a CollaborativeStackingCart batch");
-}
-int hrg_batch_set_stack(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_stacks, (void*)buf_host, bytes, false, "not a CollaborativeStackingCart batch");
-}
-int hrg_batch_get_hammer(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_hammers, buf_host, bytes, true, "not a CollaborativeHammeringCart batch");
-}
-int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_hammers, (void*)buf_host, bytes, false, "not a CollaborativeHammeringCart batch");
-}
-
-int hrg_batch_get_states(hrg_batch* b, const int32_t* envs_host, int32_t n, void* states_host, void* boxes_host) {
-  if (!b || !envs_host || !states_host || n < 0) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  for (int32_t k = 0; k < n; k++) {
-    const int32_t e = envs_host[k];
-    if (e < 0 || e >= b->n_envs) return fail(HRG_ERR_INVALID, "bad env index");
-    HIPCHK(hipMemcpyAsync((hrg_env_state*)states_host + k, b->d_states + e, sizeof(hrg_env_state), hipMemcpyDeviceToHost, 0));
-    if (boxes_host) HIPCHK(hipMemcpyAsync((hrg_box_state*)boxes_host + k, b->d_boxes + e, sizeof(hrg_box_state), hipMemcpyDeviceToHost, 0));
-  }
-  HIPCHK(hipDeviceSynchronize());
-  return HRG_OK;
-}
-
-int hrg_batch_set_states(hrg_batch* b, const int32_t* envs_host, int32_t n, const void* states_host, const void* boxes_host) {
-  if (!b || !envs_host || !states_host || n < 0) return fail(HRG_ERR_INVALID, "null argument");
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  for (int32_t k = 0; k < n; k++) {
-    const int32_t e = envs_host[k];
-    if (e < 0 || e >= b->n_envs) return fail(HRG_ERR_INVALID, "bad env index");
-    HIPCHK(hipMemcpyAsync(b->d_states + e, (const hrg_env_state*)states_host + k, sizeof(hrg_env_state), hipMemcpyHostToDevice, 0));
-    if (boxes_host) HIPCHK(hipMemcpyAsync(b->d_boxes + e, (const hrg_box_state*)boxes_host + k, sizeof(hrg_box_state), hipMemcpyHostToDevice, 0));
-  }
-  HIPCHK(hipDeviceSynchronize());
-  return HRG_OK;
-}
-
-int hrg_batch_mpr_fallbacks(hrg_batch* b, int64_t* count_host) {
-  if (!b || !count_host) return fail(HRG_ERR_INVALID, "null argument");
-  *count_host = 0;
-  if (!b->d_mpr_fallback) return HRG_OK;   // no hulls: no MPR
-  HIPCHK(hipSetDevice(b->device));
-  HIPCHK(hipDeviceSynchronize());
-  unsigned long long c = 0;
-  HIPCHK(hipMemcpy(&c, b->d_mpr_fallback, sizeof c, hipMemcpyDeviceToHost));
-  *count_host = (int64_t)c;
-  return HRG_OK;
-}
-
-int hrg_batch_enable_taps(hrg_batch* b, int32_t on) {
-  if (!b) return fail(HRG_ERR_INVALID, "null batch");
-  b->taps = on != 0;
-  return HRG_OK;
-}
-
-
-int hrg_batch_kernel_time(hrg_batch* b, double* avg_ms, int64_t* n_launches) {
-  if (!b) return fail(HRG_ERR_INVALID, "null batch");
-  HIPCHK(hipSetDevice(b->device));
-  double tot = 0;
-  int64_t n = 0;
-  for (auto& p : b->events) {
-    HIPCHK(hipEventSynchronize(p.second));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, p.first, p.second));
-    tot += ms; n++;
-    b->pool.push_back(p);
-  }
-  b->events.clear();
-  b->timing = true; // first call arms the timer
-  if (avg_ms) *avg_ms = n ? tot / (double)n : 0.0;
-  if (n_launches) *n_launches = n;
-  return HRG_OK;
-}
-
-} // extern "C"
+#include "hrgym_host.h"            // what the host files share: the error string, a handle's device memory, the launch grids
+#include "hrgym_host_batch.h"      // hrg_batch_*, hrg_debug_*: the batch, its variant table, experts and datasets, the test taps
+#include "hrgym_host_buffers.h"    // hrg_her_*, hrg_rollout_*, hrg_replay_*
+#include "hrgym_host_learners.h"   // hrg_sac_*, hrg_ppo_*, hrg_eval_*
 #endif // HRG_BASE_TU

@@ -1,0 +1,445 @@
+// hrgym_host_learners.h -- the learners of the C ABI (include/hrgym.h): SAC (hrg_sac_*), PPO (hrg_ppo_*) and the evaluation of their policies (hrg_eval_*), with what
+// the two learners check and compute alike.  Included by the base unit only, behind hrgym_host.h and hrgym_host_buffers.h (the evaluator reads rows through a buffer's view).
+
+// What both learners check of their networks and batch (csrc/hrgym_mlp.h).  `name`: the learner's message prefix; max_batch: its largest batch.
+static int learner_shape(const char* name, int32_t hidden, int32_t depth, int32_t obs_dim, int32_t act_dim, int32_t batch_size, int32_t max_batch) {
+  const auto refuse = [name](const char* what, int32_t value, const std::string& why) {
+    return fail(HRG_ERR_UNSUPPORTED, std::string(name) + ": " + what + " = " + std::to_string(value) + why);
+  };
+  if (hidden != HRG_SAC_HIDDEN) return refuse("hidden", hidden, ": the kernels cover hidden width 64 only");
+  if (depth < 1 || depth > HRG_SAC_MAX_DEPTH) return refuse("depth", depth, " outside 1 .. 3");
+  if (obs_dim < 1 || obs_dim > HRG_OBS_DIM) return refuse("obs_dim", obs_dim, " outside 1 .. HRG_OBS_DIM");
+  if (act_dim < 1 || act_dim > HRG_ACT_DIM) return refuse("act_dim", act_dim, " outside 1 .. HRG_ACT_DIM");
+  if (batch_size < MLP_T || batch_size > max_batch || batch_size % MLP_T) return refuse("batch_size", batch_size, " is not a multiple of 32 in 32 .. " + std::to_string(max_batch));
+  return HRG_OK;
+}
+
+// Adam's bias corrections 1 - beta^t for the step after `steps` finished ones (betas 0.9, 0.999)
+static void adam_bias_corrections(uint64_t steps, double& bc1, double& bc2) {
+  const double t = (double)(steps + 1);
+  bc1 = 1.0 - std::pow(0.9, t);
+  bc2 = 1.0 - std::pow(0.999, t);
+}
+
+extern "C" {
+
+// ---- SAC learner (csrc/hrgym_sac.h) ----
+struct hrg_sac {
+  int device = 0;
+  hrg_sac_desc desc;
+  SacDev d;
+  uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
+  uint64_t act_calls = 0;   // act calls that drew their noise
+  DeviceMem mem;            // one allocation behind every pointer of `d`
+};
+
+// the offsets of the parameter layout (csrc/hrgym_sac.h) into d; returns the number of parameters
+static int32_t sac_layout(const hrg_sac_desc& c, SacDev& d) {
+  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_SAC_HIDDEN;
+  int32_t o = 0;
+  for (int l = 0; l < c.depth; l++) {
+    d.a_w[l] = o; o += H * (l ? H : K);
+    d.a_b[l] = o; o += H;
+  }
+  d.a_hw = o; o += 2 * A * H;
+  d.a_hb = o; o += 2 * A;
+  d.n_actor = o;
+  for (int q = 0; q < 2; q++) {
+    for (int l = 0; l < c.depth; l++) {
+      d.q_w[q][l] = o; o += H * (l ? H : K + A);
+      d.q_b[q][l] = o; o += H;
+    }
+    d.q_ow[q] = o; o += H;
+    d.q_ob[q] = o; o += 1;
+  }
+  d.n_critic = (o - d.n_actor) / 2;
+  d.n_params = o + 1;   // log_ent_coef
+  return d.n_params;
+}
+
+int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = learner_shape("sac", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_SAC_MAX_BATCH)) return rc;
+  if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
+  if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
+    return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
+  if (!desc->auto_ent_coef && desc->ent_coef <= 0.0) return fail(HRG_ERR_INVALID, "sac: a fixed ent_coef must be positive");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_sac> h(new hrg_sac());
+  h->device = device;
+  h->desc = *desc;
+  SacDev& d = h->d;
+  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE;
+  d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
+  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
+  const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
+  Carver<float> f;
+  f.take(d.a_pi, B * A);
+  f.take(d.logp, B);
+  f.take(d.logp_next, B);
+  f.take(d.y, B);
+  f.take(d.q, SAC_NQ * B);
+  f.take(d.dqda, 2 * B * A);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.loss_part, (size_t)d.tiles * SAC_NLOSS);
+  f.take(d.losses, 4);
+  if (!f.alloc(h->mem)) return nomem("sac", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_sac_destroy(hrg_sac* h) { destroy_handle(h); }
+
+int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_params;
+  size_host[1] = h->d.n_actor;
+  size_host[2] = h->d.n_critic;
+  size_host[3] = (int64_t)h->steps;
+  size_host[4] = (int64_t)h->act_calls;
+  size_host[5] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions_dev, const float* next_observations_dev, const float* dones_dev, const float* rewards_dev,
+                 const float* eps_pi_dev, const float* eps_next_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, float* target_dev, double learning_rate,
+                 void* stream) {
+  if (!h || !observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev || !params_dev || !adam_m_dev || !adam_v_dev || !target_dev)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "sac: learning_rate must be finite and not negative");
+  HIPCHK(hipSetDevice(h->device));
+  const SacDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 pair((unsigned)d.tiles, 2), block(MLP_BLOCK);
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimisers' step count
+  const bool polyak = h->steps % (uint64_t)h->desc.target_update_interval == 0;
+  const int n_crit2 = 2 * d.n_critic;
+  hipLaunchKernelGGL(hrg_sac_policy_kernel, pair, block, 0, st, d, (const float*)params_dev, (const float*)target_dev, observations_dev, next_observations_dev, dones_dev,
+                     rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
+  hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
+                     (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
+  hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
+  hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
+                     learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream) {
+  if (!h || !params_dev || !obs_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (n < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
+                     (int)(deterministic != 0), h->act_calls, actions_dev);
+  HIPCHK(hipGetLastError());
+  if (!deterministic && !eps_dev) h->act_calls++;
+  return HRG_OK;
+}
+
+int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  const SacDev& d = h->d;
+  const size_t B = (size_t)d.B;
+  return export_floats(h->device, {{y_host, d.y, B}, {logp_host, d.logp, B}, {logp_next_host, d.logp_next, B}, {q_host, d.q, SAC_NQ * B},
+                                   {grad_host, d.grad, (size_t)d.n_params}, {losses_host, d.losses, 4}});
+}
+
+// ---- PPO learner (csrc/hrgym_ppo.h) ----
+struct hrg_ppo {
+  int device = 0;
+  hrg_ppo_desc desc;
+  PpoDev d;
+  uint64_t steps = 0;           // minibatch steps so far: Adam's step count
+  uint64_t forward_calls = 0;   // forward calls that drew their noise
+  int n_blocks = 0;             // blocks of 256 parameters
+  DeviceMem mem;                // one allocation behind every float pointer of `d`, one behind every double pointer
+};
+
+// the offsets of the parameter layout (csrc/hrgym_ppo.h) into d; returns the number of parameters
+static int32_t ppo_layout(const hrg_ppo_desc& c, PpoDev& d) {
+  const int32_t K = c.obs_dim, A = c.act_dim, H = HRG_PPO_HIDDEN;
+  int32_t o = 0;
+  for (int n = 0; n < d.nets; n++)
+    for (int l = 0; l < c.depth; l++) {
+      d.w[n][l] = o; o += H * (l ? H : K);
+      d.b[n][l] = o; o += H;
+    }
+  d.hw = o; o += (A + 1) * H;
+  d.hb = o; o += A + 1;
+  d.ls = o; o += A;
+  d.n_params = o;
+  return o;
+}
+
+int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->use_sde) return fail(HRG_ERR_UNSUPPORTED, "ppo: use_sde: state dependent exploration is not covered");
+  if (desc->target_kl_set) return fail(HRG_ERR_UNSUPPORTED, "ppo: target_kl: the early stop needs a host readback per minibatch");
+  if (desc->policy != HRG_PPO_MLP_POLICY) return fail(HRG_ERR_UNSUPPORTED, "ppo: policy = " + std::to_string(desc->policy) + ": the kernels cover MlpPolicy");
+  if (int rc = learner_shape("ppo", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_PPO_MAX_BATCH)) return rc;
+  if (desc->separate != 0 && desc->separate != 1) return fail(HRG_ERR_UNSUPPORTED, "ppo: separate must be 0 (shared trunk) or 1 (separate trunks)");
+  if (desc->rollout_size < 0 || desc->rollout_size % desc->batch_size)
+    return fail(HRG_ERR_UNSUPPORTED, "ppo: rollout_size = " + std::to_string(desc->rollout_size) + " is not divisible by batch_size = " + std::to_string(desc->batch_size) +
+                                         ": the learner takes no short last minibatch");
+  if (!std::isfinite(desc->ent_coef) || !std::isfinite(desc->vf_coef) || !std::isfinite(desc->max_grad_norm) || desc->ent_coef < 0.0 || desc->vf_coef < 0.0 ||
+      desc->max_grad_norm <= 0.0)
+    return fail(HRG_ERR_INVALID, "ppo: ent_coef and vf_coef must be finite and not negative, max_grad_norm finite and positive");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_ppo> h(new hrg_ppo());
+  h->device = device;
+  h->desc = *desc;
+  PpoDev& d = h->d;
+  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_PPO_TILE;
+  d.nets = desc->separate ? 2 : 1;
+  d.normalize = desc->normalize_advantage ? 1 : 0;
+  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm; d.seed = desc->seed;
+  const size_t P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;
+  h->n_blocks = (int)((P + MLP_BLOCK - 1) / MLP_BLOCK);
+  Carver<float> f;
+  f.take(d.values, B);
+  f.take(d.logp, B);
+  f.take(d.ratio, B);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.loss_part, (size_t)d.tiles * PPO_NPART);
+  f.take(d.diag, HRG_PPO_NDIAG);
+  Carver<double> dbl;
+  dbl.take(d.adv_stat, 2);
+  dbl.take(d.block_sq, (size_t)h->n_blocks);
+  if (!f.alloc(h->mem) || !dbl.alloc(h->mem)) return nomem("ppo", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_ppo_destroy(hrg_ppo* h) { destroy_handle(h); }
+
+int hrg_ppo_sizes(hrg_ppo* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_params;
+  size_host[1] = h->d.nets == 2 ? h->d.w[1][0] : h->d.hw;   // (the first network starts at 0)
+  size_host[2] = h->d.nets;
+  size_host[3] = (int64_t)h->steps;
+  size_host[4] = (int64_t)h->forward_calls;
+  size_host[5] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions_dev, const float* old_values_dev, const float* old_log_prob_dev,
+                 const float* advantages_dev, const float* returns_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, double learning_rate, double clip_range,
+                 double clip_range_vf, void* stream) {
+  if (!h || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev || !params_dev || !adam_m_dev || !adam_v_dev)
+    return fail(HRG_ERR_INVALID, "null argument");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "ppo: learning_rate must be finite and not negative");
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(HRG_ERR_INVALID, "ppo: clip_range must be finite and positive");
+  if (std::isnan(clip_range_vf)) return fail(HRG_ERR_INVALID, "ppo: clip_range_vf must be a number (negative: no clipping)");
+  HIPCHK(hipSetDevice(h->device));
+  const PpoDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks);
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);   // by the optimiser's step count
+  if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1), block, 0, st, d, advantages_dev);
+  hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
+                     old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
+  hipLaunchKernelGGL(hrg_ppo_reduce_kernel, flat, block, 0, st, d);
+  hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, learning_rate, bc1, bc2);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                    float* values_dev, float* log_probs_dev, void* stream) {
+  if (!h || !params_dev || !obs_dev || !values_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (actions_dev && !log_probs_dev) return fail(HRG_ERR_INVALID, "ppo: actions without log_probs");
+  if (n < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
+  HIPCHK(hipSetDevice(h->device));
+  const int value_only = actions_dev ? 0 : 1;
+  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T, value_only ? 1u : (unsigned)h->d.nets), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d,
+                     params_dev, obs_dev, (int)n, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev, log_probs_dev);
+  HIPCHK(hipGetLastError());
+  if (!value_only && !deterministic && !eps_dev) h->forward_calls++;
+  return HRG_OK;
+}
+
+int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  const PpoDev& d = h->d;
+  const size_t B = (size_t)d.B;
+  return export_floats(h->device, {{values_host, d.values, B}, {log_prob_host, d.logp, B}, {ratio_host, d.ratio, B}, {grad_host, d.grad, (size_t)d.n_params},
+                                   {diag_host, d.diag, HRG_PPO_NDIAG}});
+}
+
+int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->steps = steps;
+  h->act_calls = act_calls;
+  return HRG_OK;
+}
+
+int hrg_ppo_restore(hrg_ppo* h, uint64_t steps, uint64_t forward_calls) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->steps = steps;
+  h->forward_calls = forward_calls;
+  return HRG_OK;
+}
+
+// ---- evaluation (csrc/hrgym_eval.h) ----
+struct hrg_eval {
+  int device = 0;
+  hrg_eval_desc desc;
+  EvalDev d;
+  int64_t steps = 0;   // steps since begin: the finishing step index of the records
+  DeviceMem mem;       // behind every pointer of `d`
+};
+
+int hrg_eval_create(const hrg_eval_desc* desc, int32_t device, hrg_eval** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->n_envs < 1 || desc->n_policies < 1) return fail(HRG_ERR_INVALID, "eval: n_envs and n_policies must be positive");
+  if (desc->n_envs % desc->n_policies)
+    return fail(HRG_ERR_INVALID, "eval: n_envs = " + std::to_string(desc->n_envs) + " is not divisible by n_policies = " + std::to_string(desc->n_policies) +
+                                     ": every parameter set steps a group of the same size");
+  if (desc->n_eval_episodes < 1) return fail(HRG_ERR_INVALID, "eval: n_eval_episodes must be positive");
+  const int32_t group = desc->n_envs / desc->n_policies;
+  const int64_t max_quota = ((int64_t)desc->n_eval_episodes + group - 1) / group;
+  if (max_quota > HRG_EVAL_MAX_EPISODES_PER_ENV)
+    return fail(HRG_ERR_INVALID, "eval: " + std::to_string(desc->n_eval_episodes) + " episodes over groups of " + std::to_string(group) + " envs are " +
+                                     std::to_string(max_quota) + " per env, above HRG_EVAL_MAX_EPISODES_PER_ENV = " + std::to_string(HRG_EVAL_MAX_EPISODES_PER_ENV));
+  const int time_col = desc->observe_time ? 1 : 0;
+  int width = desc->n_obs_cols + time_col;
+  if (desc->goal_env) {
+    if (desc->observe_time || desc->normalize) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_env with observe_time or normalize: a goal env's feature row is a plain selection");
+    if (desc->goal_kind != HRG_GOAL_REACH && desc->goal_kind != HRG_GOAL_CUBE) return fail(HRG_ERR_UNSUPPORTED, "eval: goal_kind = " + std::to_string(desc->goal_kind));
+    width = (desc->goal_kind == HRG_GOAL_REACH ? 6 + 6 : 7 + 3) + desc->n_obs_cols;
+    if (width > HRG_OBS_DIM)
+      return fail(HRG_ERR_UNSUPPORTED, "eval: a feature row of " + std::to_string(width) + " values; the kernels handle one value per lane, at most HRG_OBS_DIM");
+  }
+  for (int j = 0; j < HRG_ACT_DIM; j++)
+    if (j < desc->act_dim && (!std::isfinite(desc->act_low[j]) || !std::isfinite(desc->act_high[j]) || desc->act_low[j] > desc->act_high[j]))
+      return fail(HRG_ERR_INVALID, "eval: act_low and act_high must be finite and ordered");
+  double mean[HRG_OBS_DIM], sd[HRG_OBS_DIM];
+  if (int rs = view_statistics("eval", desc->n_obs_cols + time_col, desc->normalize, desc->squash, desc->squash_factor, desc->mean, desc->std, mean, sd)) return rs;
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_eval> h(new hrg_eval());
+  h->device = device;
+  h->desc = *desc;
+  EvalDev& d = h->d;
+  BufferView& v = d.view;
+  DeviceMem& m = h->mem;
+  v.observe_time = time_col;
+  if (int rc = buffer_columns("eval", desc->n_obs_cols, desc->obs_cols, &desc->observe_time, desc->act_dim, m, v.obs_cols)) return rc;
+  v.n_obs_cols = desc->n_obs_cols; v.normalize = desc->normalize ? 1 : 0; v.squash = desc->squash ? 1 : 0; v.squash_factor = desc->squash_factor;
+  d.n_envs = desc->n_envs; d.n_policies = desc->n_policies; d.group = group; d.n_episodes = desc->n_eval_episodes; d.max_quota = (int32_t)max_quota;
+  d.act_dim = desc->act_dim; d.goal_env = desc->goal_env ? 1 : 0; d.goal_kind = desc->goal_kind; d.width = width;
+  const size_t n = (size_t)desc->n_envs;
+  if (!(m.zeros(d.ep.cur_obs, n * HRG_OBS_DIM) && m.zeros(d.ep.run_ret, n) && m.zeros(d.ep.run_len, n) && m.zeros(d.cur_time, n) && m.zeros(d.count, n) &&
+        m.zeros(d.quota, n) && m.zeros(d.records, n * (size_t)max_quota * HRG_EVAL_RECORD_DIM) && m.zeros(d.remaining, 1) &&
+        m.upload(d.act_low, desc->act_low, HRG_ACT_DIM) && m.upload(d.act_high, desc->act_high, HRG_ACT_DIM)))
+    return nomem("eval", m);
+  if (int ru = view_statistics_upload("eval", m, v, mean, sd)) return ru;
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_eval_destroy(hrg_eval* h) { destroy_handle(h); }
+
+int hrg_eval_begin(hrg_eval* h, const float* obs_dev, const float* time_dev, float* view_dev, void* stream) {
+  if (!h || !obs_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (h->d.view.observe_time && !time_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the rows' time values");
+  HIPCHK(hipSetDevice(h->device));
+  h->steps = 0;
+  return launch_per_env(hrg_eval_begin_kernel, h->desc.n_envs, stream, h->d, obs_dev, time_dev, view_dev);
+}
+
+int hrg_eval_step(hrg_eval* h, const float* obs_dev, const float* reward_dev, const uint8_t* done_dev, const int32_t* info_dev, const float* imit_dev,
+                  const float* sir_dev, float* view_dev, void* stream) {
+  if (!h || !obs_dev || !reward_dev || !done_dev || !info_dev || !view_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (imit_dev && sir_dev) return fail(HRG_ERR_INVALID, "eval: an imitation row or a state imitation row, not both");
+  if (h->d.view.observe_time && !sir_dev) return fail(HRG_ERR_INVALID, "eval: observe_time needs the state imitation rows (their time columns)");
+  HIPCHK(hipSetDevice(h->device));
+  const int rc = launch_per_env(hrg_eval_step_kernel, h->desc.n_envs, stream, h->d, h->steps, obs_dev, reward_dev, done_dev, info_dev, imit_dev, sir_dev, view_dev);
+  if (rc != HRG_OK) return rc;
+  h->steps++;
+  return HRG_OK;
+}
+
+// what both policy entries end with: the widths of the learner against the evaluator's, then the launch
+static int eval_policy(hrg_eval* h, bool sac, const EvalActor& a, int learner_device, const char* name, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!params_dev || !view_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (learner_device != h->device)
+    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner lives on device " + std::to_string(learner_device) + ", the evaluator on device " +
+                                     std::to_string(h->device));
+  if (a.K != h->d.width || a.A != h->d.act_dim)
+    return fail(HRG_ERR_INVALID, std::string("eval: the ") + name + " learner takes observations of " + std::to_string(a.K) + " and emits actions of " + std::to_string(a.A) +
+                                     " values, the evaluator's view has " + std::to_string(h->d.width) + " and its actions " + std::to_string(h->d.act_dim));
+  HIPCHK(hipSetDevice(h->device));
+  const dim3 grid(((unsigned)h->d.group + MLP_T - 1) / MLP_T, (unsigned)h->d.n_policies), block(MLP_BLOCK);
+  if (sac) hipLaunchKernelGGL(hrg_eval_policy_kernel<true>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
+  else hipLaunchKernelGGL(hrg_eval_policy_kernel<false>, grid, block, 0, (hipStream_t)stream, h->d, a, params_dev, view_dev, actions_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_eval_policy_sac(hrg_eval* h, hrg_sac* sac, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!h || !sac) return fail(HRG_ERR_INVALID, "null argument");
+  const SacDev& s = sac->d;
+  EvalActor a;
+  for (int l = 0; l < HRG_SAC_MAX_DEPTH; l++) { a.w[l] = s.a_w[l]; a.b[l] = s.a_b[l]; }
+  a.hw = s.a_hw; a.hb = s.a_hb; a.nout = 2 * s.A;   // (sac_squash reads both heads)
+  a.depth = s.depth; a.K = s.K; a.A = s.A; a.n_params = s.n_params;
+  return eval_policy(h, true, a, sac->device, "sac", params_dev, view_dev, actions_dev, stream);
+}
+
+int hrg_eval_policy_ppo(hrg_eval* h, hrg_ppo* ppo, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
+  if (!h || !ppo) return fail(HRG_ERR_INVALID, "null argument");
+  const PpoDev& p = ppo->d;
+  EvalActor a;
+  for (int l = 0; l < HRG_PPO_MAX_DEPTH; l++) { a.w[l] = p.w[0][l]; a.b[l] = p.b[0][l]; }   // network 0: the shared trunk, or the policy's
+  a.hw = p.hw; a.hb = p.hb; a.nout = p.A;   // the first A rows of the [A + 1][64] heads: action_net
+  a.depth = p.depth; a.K = p.K; a.A = p.A; a.n_params = p.n_params;
+  return eval_policy(h, false, a, ppo->device, "ppo", params_dev, view_dev, actions_dev, stream);
+}
+
+int hrg_eval_remaining(hrg_eval* h, int64_t* remaining_host, void* stream) {
+  if (!h || !remaining_host) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(hrg_eval_remaining_kernel, dim3(1), dim3(MLP_BLOCK), 0, st, h->d);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(remaining_host, h->d.remaining, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return HRG_OK;
+}
+
+int hrg_eval_export(hrg_eval* h, int32_t* counts_host, int32_t* quota_host, double* records_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  const EvalDev& d = h->d;
+  const size_t n = (size_t)d.n_envs;
+  if (counts_host) HIPCHK(hipMemcpy(counts_host, d.count, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (quota_host) HIPCHK(hipMemcpy(quota_host, d.quota, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (records_host) HIPCHK(hipMemcpy(records_host, d.records, n * (size_t)d.max_quota * HRG_EVAL_RECORD_DIM * sizeof(double), hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+int hrg_eval_size(hrg_eval* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.max_quota;
+  size_host[1] = h->steps;
+  size_host[2] = h->d.width;
+  size_host[3] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+} // extern "C"

@@ -4,6 +4,7 @@
 // simplex in the collide part of the LDS union).  Its own translation unit, so the capsule-geometry kernels carry none of it: no code, no LDS, no registers.
 #define HRG_HULLS 1
 #include "hrgym_hip.hip"
+#include "hrgym_host.h"   // hrg_run_tap
 
 // ---- test tap (include/hrgym.h: hrg_test_hull_queries): the wave routines on their own, one query per wavefront -- tests/test_hulls.py compares them with the
 // oracle's hull_support / gjk_hull_segment / hull_lowest over random poses.  Pose and segment go through LDS as in the step kernel (kR / kp, hcap).

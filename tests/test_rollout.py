@@ -198,7 +198,7 @@ def test_abi_names_and_the_header_stays_in_the_base_translation_unit():
     at = base.index('#include "hrgym_rollout.h"')
     assert base.rindex("#if HRG_BASE_TU", 0, at) > base.rindex("#endif", 0, at)   # inside the block that only the base translation unit compiles
     assert at > base.index('#include "hrgym_her.h"')
-    assert "// ---- PPO rollout buffer" in base
+    assert "// ---- PPO rollout buffer" in open(_lib.SRC.replace("hrgym_hip.hip", "hrgym_host_buffers.h")).read()   # its host side
     for src in _lib.SOURCES[1:]:
         assert "hrgym_rollout.h" not in open(src).read(), src
     assert len(_lib.SOURCES) == 12
