@@ -35,9 +35,9 @@ def __getattr__(name):
     if name == "ReplayBuffer":
         from .replay import ReplayBuffer
         return ReplayBuffer
-    if name == "SacLearner":
-        from .sac import SacLearner
-        return SacLearner
+    if name in ("SacLearner", "SacPopulation"):
+        from . import sac
+        return getattr(sac, name)
     if name == "PpoLearner":
         from .ppo import PpoLearner
         return PpoLearner

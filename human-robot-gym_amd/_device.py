@@ -31,7 +31,8 @@ class DeviceHandle:
     checked, not converted; the calls are ordered on torch's current stream of the device."""
     _create = _destroy = None   # names of the entry points (hrg_*_create, hrg_*_destroy)
 
-    def _open(self, desc, device):
+    def _open(self, desc, device, *create_args):
+        """`create_args`: what the create entry takes between the descriptor and the device."""
         import torch
         from ._lib import _check, load_library
         if not torch.cuda.is_available():
@@ -41,7 +42,7 @@ class DeviceHandle:
         self.device = torch.device("cuda", device)
         self.h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _check(self.lib, getattr(self.lib, self._create)(ctypes.byref(desc), device, ctypes.byref(self.h)))
+            _check(self.lib, getattr(self.lib, self._create)(ctypes.byref(desc), *create_args, device, ctypes.byref(self.h)))
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -126,14 +127,20 @@ class EpisodeBuffer(DeviceHandle):
         self._check(self.lib, getattr(self.lib, self._prefix + "_stats")(self.h, acc.ctypes.data_as(ctypes.c_void_p), int(bool(clear))))
         return acc
 
-    def episode_stats(self, clear=True):
+    def episode_stats(self, clear=True, groups=None):
         """The episodes that finished since the last clear, summed over the envs on the host: dict(episodes, r, l, **sums of the info columns at the
         episodes' last steps, by key name) -- what safe_mean over SB3's ep_info_buffer and LoggingCallback._info_buffer divide by `episodes`; `r` is Monitor's
-        return.  A buffer that keeps the imitation reward sums adds `ep_im_rew`, the sum of the infos' ep_im_rew_mean.  Synchronous."""
+        return.  A buffer that keeps the imitation reward sums adds `ep_im_rew`, the sum of the infos' ep_im_rew_mean.  `groups`: a list of that many dicts
+        instead, one per group of n / groups consecutive envs (a population's members).  Synchronous."""
         n_info = CONST["HRG_INFO_DIM"]
-        tot = self.episode_stats_per_env(clear).sum(axis=0)
-        out = dict(episodes=int(tot[0]), r=float(tot[1]), l=int(tot[2]))
-        out.update({k: float(v) for k, v in zip(self.info_keys, tot[3:3 + n_info])})
-        if self._stats_dim > 3 + n_info:
-            out["ep_im_rew"] = float(tot[3 + n_info])
-        return out
+        if groups is not None and (int(groups) < 1 or self.n % int(groups)):
+            raise ValueError(f"episode_stats: {self.n} envs are not {groups} groups of the same size")
+        per_env = self.episode_stats_per_env(clear)
+        out = []
+        for tot in per_env.reshape(1 if groups is None else int(groups), -1, self._stats_dim).sum(axis=1):
+            d = dict(episodes=int(tot[0]), r=float(tot[1]), l=int(tot[2]))
+            d.update({k: float(v) for k, v in zip(self.info_keys, tot[3:3 + n_info])})
+            if self._stats_dim > 3 + n_info:
+                d["ep_im_rew"] = float(tot[3 + n_info])
+            out.append(d)
+        return out[0] if groups is None else out

@@ -156,9 +156,9 @@ class Learner(DeviceHandle):
     keeps its LearnerParams as `p`."""
     _prefix = None
 
-    def _open(self, desc, device):
-        self._create, self._destroy = self._prefix + "_create", self._prefix + "_destroy"
-        super()._open(desc, device)
+    def _open(self, desc, device, *create_args, create="_create"):
+        self._create, self._destroy = self._prefix + create, self._prefix + "_destroy"
+        super()._open(desc, device, *create_args)
 
     def _sizes(self):
         w = (ctypes.c_int64 * 6)()

@@ -368,6 +368,7 @@ struct hrg_replay {
   int32_t pos = 0;      // the next slot (the write position lives on the host)
   bool full = false;    // every slot holds a transition
   uint64_t calls = 0;   // sample calls that drew their indices (key of the draws)
+  uint64_t group_calls = 0;   // ... of the grouped sample (hrg_sac_population_sample), a counter of its own
   DeviceMem mem;        // behind every pointer of `d`
 };
 
@@ -437,19 +438,37 @@ int hrg_replay_add(hrg_replay* h, const float* actions_dev, const float* obs_dev
   return HRG_OK;
 }
 
-int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in_dev, float* observations_dev, float* actions_dev, float* next_observations_dev,
-                      float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
-  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+// what both sample entries end with; seeds_dev null: one group under the buffer's seed
+static int replay_sample(hrg_replay* h, int32_t n_groups, int32_t batch_size, const uint64_t* seeds_dev, uint64_t& calls, const int64_t* index_in_dev, float* observations_dev,
+                         float* actions_dev, float* next_observations_dev, float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
   if (batch_size < 1) return fail(HRG_ERR_INVALID, "replay: batch_size must be positive");
   if (!observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev) return fail(HRG_ERR_INVALID, "replay: null output");
   const int64_t upper = h->full ? h->desc.capacity : h->pos;
   if (upper < 1) return fail(HRG_ERR_INVALID, "replay: the buffer is empty (nothing to sample)");
   HIPCHK(hipSetDevice(h->device));
-  const int rc = launch_per_wave(hrg_replay_sample_kernel, batch_size, stream, h->d, upper, h->calls, index_in_dev, (int)batch_size, observations_dev, actions_dev,
-                                 next_observations_dev, dones_dev, rewards_dev, index_out_dev);
+  const int rc = launch_per_wave(hrg_replay_sample_kernel, n_groups * batch_size, stream, h->d, upper, calls, index_in_dev, (int)batch_size, (int)n_groups, seeds_dev,
+                                 observations_dev, actions_dev, next_observations_dev, dones_dev, rewards_dev, index_out_dev);
   if (rc != HRG_OK) return rc;
-  if (!index_in_dev) h->calls++;
+  if (!index_in_dev) calls++;
   return HRG_OK;
+}
+
+int hrg_replay_sample(hrg_replay* h, int32_t batch_size, const int64_t* index_in_dev, float* observations_dev, float* actions_dev, float* next_observations_dev,
+                      float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  return replay_sample(h, 1, batch_size, nullptr, h->calls, index_in_dev, observations_dev, actions_dev, next_observations_dev, dones_dev, rewards_dev, index_out_dev, stream);
+}
+
+int hrg_sac_population_sample(hrg_replay* h, int32_t n_groups, int32_t batch_size, const uint64_t* seeds_dev, float* observations_dev, float* actions_dev,
+                              float* next_observations_dev, float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  if (n_groups < 1 || h->desc.n_envs % n_groups)
+    return fail(HRG_ERR_INVALID, "replay: n_envs = " + std::to_string(h->desc.n_envs) + " is not divisible by n_groups = " + std::to_string(n_groups) +
+                                     ": every member samples a group of the same size");
+  if (!seeds_dev) return fail(HRG_ERR_INVALID, "replay: a grouped sample needs its seeds table (n_groups values on the device)");
+  if ((int64_t)n_groups * batch_size > INT32_MAX) return fail(HRG_ERR_INVALID, "replay: n_groups * batch_size above the 2^31 - 1 rows of a launch");
+  return replay_sample(h, n_groups, batch_size, seeds_dev, h->group_calls, nullptr, observations_dev, actions_dev, next_observations_dev, dones_dev, rewards_dev,
+                       index_out_dev, stream);
 }
 
 int hrg_replay_stats(hrg_replay* h, double* per_env_host, int32_t clear) {

@@ -27,6 +27,7 @@ extern "C" {
 struct hrg_sac {
   int device = 0;
   hrg_sac_desc desc;
+  int32_t n_members = 1;    // a population's members (csrc/hrgym_sac.h); the lone learner is the population of one
   SacDev d;
   uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
   uint64_t act_calls = 0;   // act calls that drew their noise
@@ -57,9 +58,12 @@ static int32_t sac_layout(const hrg_sac_desc& c, SacDev& d) {
   return d.n_params;
 }
 
-int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
+int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_sac** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
+  if (n_members < 1 || n_members > HRG_SAC_MAX_POPULATION)
+    return fail(HRG_ERR_UNSUPPORTED, "sac: n_members = " + std::to_string(n_members) + " outside 1 .. " + std::to_string(HRG_SAC_MAX_POPULATION));
+  if (!seeds) return fail(HRG_ERR_INVALID, "sac: a population needs its seeds table (n_members values)");
   if (int rc = learner_shape("sac", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_SAC_MAX_BATCH)) return rc;
   if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
   if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
@@ -69,26 +73,32 @@ int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
   std::unique_ptr<hrg_sac> h(new hrg_sac());
   h->device = device;
   h->desc = *desc;
+  h->n_members = n_members;
   SacDev& d = h->d;
   d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE;
   d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
-  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy; d.seed = desc->seed;
-  const size_t P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;
+  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy;
+  const size_t M = (size_t)n_members, P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;   // (the pieces: sac_member)
   Carver<float> f;
-  f.take(d.a_pi, B * A);
-  f.take(d.logp, B);
-  f.take(d.logp_next, B);
-  f.take(d.y, B);
-  f.take(d.q, SAC_NQ * B);
-  f.take(d.dqda, 2 * B * A);
-  f.take(d.part, (size_t)d.tiles * P);
-  f.take(d.grad, P);
-  f.take(d.loss_part, (size_t)d.tiles * SAC_NLOSS);
-  f.take(d.losses, 4);
-  if (!f.alloc(h->mem)) return nomem("sac", h->mem);
+  f.take(d.all.a_pi, M * B * A);
+  f.take(d.all.logp, M * B);
+  f.take(d.all.logp_next, M * B);
+  f.take(d.all.y, M * B);
+  f.take(d.all.q, M * SAC_NQ * B);
+  f.take(d.all.dqda, M * 2 * B * A);
+  f.take(d.all.part, M * (size_t)d.tiles * P);
+  f.take(d.all.grad, M * P);
+  f.take(d.all.loss_part, M * (size_t)d.tiles * SAC_NLOSS);
+  f.take(d.all.losses, M * 4);
+  if (!f.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M)) return nomem("sac", h->mem);
   HIPCHK(hipDeviceSynchronize());
   *out = h.release();
   return HRG_OK;
+}
+
+int hrg_sac_create(const hrg_sac_desc* desc, int32_t device, hrg_sac** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  return hrg_sac_population_create(desc, 1, &desc->seed, device, out);
 }
 
 void hrg_sac_destroy(hrg_sac* h) { destroy_handle(h); }
@@ -104,6 +114,7 @@ int hrg_sac_sizes(hrg_sac* h, int64_t* size_host) {
   return HRG_OK;
 }
 
+// (a population's step: every array [n_members] times the lone learner's, member p's part at p times its size)
 int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions_dev, const float* next_observations_dev, const float* dones_dev, const float* rewards_dev,
                  const float* eps_pi_dev, const float* eps_next_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, float* target_dev, double learning_rate,
                  void* stream) {
@@ -113,7 +124,8 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
   HIPCHK(hipSetDevice(h->device));
   const SacDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 pair((unsigned)d.tiles, 2), block(MLP_BLOCK);
+  const unsigned members = (unsigned)h->n_members;
+  const dim3 pair((unsigned)d.tiles, 2, members), block(MLP_BLOCK);
   double bc1, bc2;
   adam_bias_corrections(h->steps, bc1, bc2);   // by the optimisers' step count
   const bool polyak = h->steps % (uint64_t)h->desc.target_update_interval == 0;
@@ -121,34 +133,45 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
   hipLaunchKernelGGL(hrg_sac_policy_kernel, pair, block, 0, st, d, (const float*)params_dev, (const float*)target_dev, observations_dev, next_observations_dev, dones_dev,
                      rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
   hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK, 1, members), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
                      (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
   hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
-  hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
-  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
+  hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles, 1, members), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
+  hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK, 1, members), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
                      learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
   HIPCHK(hipGetLastError());
   h->steps++;
   return HRG_OK;
 }
 
-int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream) {
+int hrg_sac_population_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                           void* stream) {
   if (!h || !params_dev || !obs_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (n < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
+  if (n_group < 1) return fail(HRG_ERR_INVALID, "sac: n must be positive");
   HIPCHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n, eps_dev,
-                     (int)(deterministic != 0), h->act_calls, actions_dev);
+  hipLaunchKernelGGL(hrg_sac_act_kernel, dim3(((unsigned)n_group + MLP_T - 1) / MLP_T, (unsigned)h->n_members), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev,
+                     obs_dev, (int)n_group, eps_dev, (int)(deterministic != 0), h->act_calls, actions_dev);
   HIPCHK(hipGetLastError());
   if (!deterministic && !eps_dev) h->act_calls++;
   return HRG_OK;
 }
 
-int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
+int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream) {
+  if (h && h->n_members != 1) return fail(HRG_ERR_INVALID, "sac: a population of " + std::to_string(h->n_members) + " acts through hrg_sac_population_act (a group of rows per member)");
+  return hrg_sac_population_act(h, params_dev, obs_dev, n, eps_dev, deterministic, actions_dev, stream);
+}
+
+int hrg_sac_population_export(hrg_sac* h, int32_t member, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
   if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  if (member < 0 || member >= h->n_members) return fail(HRG_ERR_INVALID, "sac: member = " + std::to_string(member) + " outside the " + std::to_string(h->n_members) + " members");
   const SacDev& d = h->d;
-  const size_t B = (size_t)d.B;
-  return export_floats(h->device, {{y_host, d.y, B}, {logp_host, d.logp, B}, {logp_next_host, d.logp_next, B}, {q_host, d.q, SAC_NQ * B},
-                                   {grad_host, d.grad, (size_t)d.n_params}, {losses_host, d.losses, 4}});
+  const size_t m = (size_t)member, B = (size_t)d.B, P = (size_t)d.n_params;   // (the pieces: sac_member)
+  return export_floats(h->device, {{y_host, d.all.y + m * B, B}, {logp_host, d.all.logp + m * B, B}, {logp_next_host, d.all.logp_next + m * B, B},
+                                   {q_host, d.all.q + m * SAC_NQ * B, SAC_NQ * B}, {grad_host, d.all.grad + m * P, P}, {losses_host, d.all.losses + m * 4, 4}});
+}
+
+int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
+  return hrg_sac_population_export(h, 0, y_host, logp_host, logp_next_host, q_host, grad_host, losses_host);
 }
 
 // ---- PPO learner (csrc/hrgym_ppo.h) ----

@@ -8,7 +8,8 @@
 //   hrg_replay_observe_kernel  after a reset: the current row and time value of the masked envs, their running return and length.
 //   hrg_replay_add_kernel      _store_transition + ReplayBuffer.add for slot `pos` of every env; one wavefront per env.
 //   hrg_replay_sample_kernel   ReplayBuffer.sample + _get_samples: B (slot, env) pairs, drawn or supplied -> observations, actions, next observations,
-//                              dones * (1 - timeouts), rewards; one wavefront per sample.
+//                              dones * (1 - timeouts), rewards; one wavefront per sample.  With a seeds table (a SAC population's grouped sample): `groups` batches of
+//                              `batch` samples, batch g from the envs of group g under seeds[g].
 //
 // Layout.  Everything is time-major, [capacity][n_envs][.], as SB3 keeps it: one step writes one contiguous block of each array.  Observations are stored as the
 // policy sees them (selected, with the time column, normalised): K = n_obs_cols + observe_time floats, not the 64 of the superset.
@@ -82,21 +83,25 @@ __global__ __launch_bounds__(64) void hrg_replay_add_kernel(const ReplayDev h, i
 
 // grid = ceil(batch / 4) blocks of four wavefronts, one sample each.  upper: slots that hold a transition (>= 1, checked by the host); index_in [batch][2]
 // (slot, env) or null: drawn; index_out [batch][2] or null.  Slot and env are clamped to the buffer: a supplied pair never reads outside it.
+// The grouped sample: grid = ceil(groups * batch / 4), seeds [groups], n_envs a multiple of groups (checked by the host); sample k of group g is output row
+// g * batch + k and draws the lone buffer's pair of (seeds[g], call, k) within the m = n_envs / groups envs of its group.  seeds null: groups = 1, the buffer's seed.
 __global__ __launch_bounds__(HRG_BUFFER_BLOCK) void hrg_replay_sample_kernel(const ReplayDev h, int64_t upper, uint64_t call, const int64_t* __restrict__ index_in,
-                                                                             int batch, float* __restrict__ o_obs, float* __restrict__ o_act,
+                                                                             int batch, int groups, const uint64_t* __restrict__ seeds, float* __restrict__ o_obs, float* __restrict__ o_act,
                                                                              float* __restrict__ o_nobs, float* __restrict__ o_done, float* __restrict__ o_rew,
                                                                              int64_t* __restrict__ index_out) {
   const int lane = (int)(threadIdx.x & 63);
   const int k = buffer_wave_item();
-  if (k >= batch) return;
+  if (k >= batch * groups) return;
   int64_t slot, env;
   if (index_in) {
     slot = index_in[2 * (size_t)k];
     env = index_in[2 * (size_t)k + 1];
   } else {   // np.random.randint(0, upper_bound), np.random.randint(0, n_envs)
-    const double u0 = rng_u01(h.seed, call, (uint64_t)k, STREAM_REPLAY, 0), u1 = rng_u01(h.seed, call, (uint64_t)k, STREAM_REPLAY, 1);
+    const int g = k / batch, m = h.n_envs / groups;
+    const uint64_t seed = seeds ? seeds[g] : h.seed, kg = (uint64_t)(k - g * batch);
+    const double u0 = rng_u01(seed, call, kg, STREAM_REPLAY, 0), u1 = rng_u01(seed, call, kg, STREAM_REPLAY, 1);
     slot = (int64_t)floor(u0 * (double)upper);
-    env = (int64_t)floor(u1 * (double)h.n_envs);
+    env = (int64_t)g * m + min((int64_t)floor(u1 * (double)m), (int64_t)m - 1);   // (u1 < 1: the bound keeps a group's draw inside the group whatever the rounding)
   }
   slot = min(max(slot, (int64_t)0), min(upper, (int64_t)h.capacity) - 1);
   env = min(max(env, (int64_t)0), (int64_t)h.n_envs - 1);

@@ -28,18 +28,20 @@
 //
 // Draws: rng_gauss keyed by (learner seed, gradient step count, batch row, STREAM_SAC, component), component j for eps_pi and HRG_ACT_DIM + j for eps_next; the
 // act kernel by (seed, act call count, row, STREAM_SAC_ACT, j).  None depends on the grid.
+//
+// A population is n_members learners of one descriptor that differ in their seed and step in the same six launches: blockIdx.z = p is the member
+// (the act kernel: blockIdx.y).  Parameters, moments and targets are [P][n_params] and [P][2 n_critic], the batch arrays [P][B][.], every piece of the handle's
+// scratch has a member stride (sac_member), the seeds are a [P] table.  The counters are the handle's: members step in lockstep.  A member's draws are keyed by its
+// own seed and the row's index in its own batch (the act kernel: in its group of rows), its sums are its own: member p is, bit for bit, the lone learner of seed p
+// on batch p.  The lone learner is the population of one member.
 #pragma once
 
 enum { STREAM_SAC = 12, STREAM_SAC_ACT = 13 };   // after STREAM_REPLAY = 11 (hrgym_replay.h)
 #define SAC_NQ HRG_SAC_NQ   // Q columns kept for the export: Q1, Q2 on (obs, act); Q1t, Q2t on (next_obs, a'); Q1, Q2 (updated) on (obs, a_pi)
 #define SAC_NLOSS 4       // per tile: sum (Q1 - y)^2, sum (Q2 - y)^2, sum (alpha logp - min Q), sum logp
 
-// one hrg_sac: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
-struct SacDev {
-  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, n_actor = 0, n_critic = 0, auto_alpha = 0;
-  int32_t a_w[HRG_SAC_MAX_DEPTH] = {0}, a_b[HRG_SAC_MAX_DEPTH] = {0}, a_hw = 0, a_hb = 0;   // actor: hidden layers, the heads' [2A][64] weights and [2A] biases
-  int32_t q_w[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_b[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_ow[2] = {0}, q_ob[2] = {0};
-  float gamma = 0.0f, alpha_fixed = 0.0f, target_entropy = 0.0f;
+// a member's seed and its pieces of the scratch the handle owns
+struct SacScratch {
   uint64_t seed = 0;
   float* a_pi = nullptr;       // [B][A]
   float* logp = nullptr;       // [B]
@@ -52,6 +54,38 @@ struct SacDev {
   float* loss_part = nullptr;  // [tiles][SAC_NLOSS]
   float* losses = nullptr;     // [4] actor_loss, critic_loss, ent_coef_loss, ent_coef (the alpha the step used)
 };
+
+// one hrg_sac: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
+struct SacDev {
+  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, n_actor = 0, n_critic = 0, auto_alpha = 0;
+  int32_t a_w[HRG_SAC_MAX_DEPTH] = {0}, a_b[HRG_SAC_MAX_DEPTH] = {0}, a_hw = 0, a_hb = 0;   // actor: hidden layers, the heads' [2A][64] weights and [2A] biases
+  int32_t q_w[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_b[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_ow[2] = {0}, q_ob[2] = {0};
+  float gamma = 0.0f, alpha_fixed = 0.0f, target_entropy = 0.0f;
+  const uint64_t* seeds = nullptr;   // [P] the members' seeds
+  SacScratch all;                    // the scratch of every member, [P] pieces of each array: member 0's pointers (`seed` is not used)
+};
+
+// member p's seed and pieces of the scratch.  The kernels move the arrays they are passed themselves (sac_rows).  (A copy of the pointers alone: a copy of the
+// whole handle, whose offset tables the kernels index by the critic, would live in scratch memory.)
+DI SacScratch sac_member(const SacDev& h, int p) {
+  const size_t i = (size_t)p, B = (size_t)h.B, A = (size_t)h.A, n = (size_t)h.n_params, tiles = (size_t)h.tiles;
+  SacScratch m = h.all;
+  m.seed = h.seeds[p];
+  m.a_pi += i * B * A;
+  m.logp += i * B;
+  m.logp_next += i * B;
+  m.y += i * B;
+  m.q += i * SAC_NQ * B;
+  m.dqda += i * 2 * B * A;
+  m.part += i * tiles * n;
+  m.grad += i * n;
+  m.loss_part += i * tiles * SAC_NLOSS;
+  m.losses += i * 4;
+  return m;
+}
+
+// member p's part of an array of `stride` values per member; null stays null
+template <class T> DI T* sac_rows(T* x, int p, size_t stride) { return x ? x + (size_t)p * stride : x; }
 
 // [UPSTREAM] SquashedDiagGaussianDistribution: s.D [.][0 .. A) = mu, [A .. 2A) = the log_std head (kept: the clamp's gradient reads it); s.eps -> s.act = tanh(u),
 // s.std = exp(clamp(log_std, -20, 2)), s.row[0] = logp, in double and rounded once.  One thread per row, components ascending.  The caller places the barriers.
@@ -77,18 +111,23 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev 
                                                                    const float* __restrict__ nobs, const float* __restrict__ dones, const float* __restrict__ rewards,
                                                                    const float* __restrict__ eps_pi, const float* __restrict__ eps_next, uint64_t count) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, next = (int)blockIdx.y, K = h.K, A = h.A;
+  const int row0 = (int)blockIdx.x * MLP_T, next = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
+  const SacScratch m = sac_member(h, p);
+  const size_t B = (size_t)h.B;
+  P = sac_rows(P, p, (size_t)h.n_params); PT = sac_rows(PT, p, 2 * (size_t)h.n_critic);
+  obs = sac_rows(obs, p, B * K); nobs = sac_rows(nobs, p, B * K); dones = sac_rows(dones, p, B); rewards = sac_rows(rewards, p, B);
+  eps_pi = sac_rows(eps_pi, p, B * A); eps_next = sac_rows(eps_next, p, B * A);
   mlp_load(s, next ? nobs : obs, K, 0, row0, h.B);
-  mlp_noise(s, next ? eps_next : eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, next ? HRG_ACT_DIM : 0);
+  mlp_noise(s, next ? eps_next : eps_pi, A, row0, h.B, m.seed, count, STREAM_SAC, next ? HRG_ACT_DIM : 0);
   mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
   mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
   const int t = (int)threadIdx.x;
   if (!next) {
-    for (int i = t; i < MLP_T * A; i += (int)blockDim.x) h.a_pi[(size_t)(row0 + i / A) * A + i % A] = s.act[(i / A) * 8 + i % A];
-    for (int r = t; r < MLP_T; r += (int)blockDim.x) h.logp[row0 + r] = s.row[0][r];
+    for (int i = t; i < MLP_T * A; i += (int)blockDim.x) m.a_pi[(size_t)(row0 + i / A) * A + i % A] = s.act[(i / A) * 8 + i % A];
+    for (int r = t; r < MLP_T; r += (int)blockDim.x) m.logp[row0 + r] = s.row[0][r];
     return;
   }
   for (int r = t; r < MLP_T; r += (int)blockDim.x) s.row[3][r] = s.row[0][r];   // logp' (s.row[0] is each head's scratch no longer, but keep it apart)
@@ -104,26 +143,28 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev 
   const float alpha = sac_alpha(h, P);
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const float q1 = s.row[1][r], q2 = s.row[2][r], lp = s.row[3][r];
-    h.q[2 * h.B + row0 + r] = q1;
-    h.q[3 * h.B + row0 + r] = q2;
-    h.logp_next[row0 + r] = lp;
-    h.y[row0 + r] = rewards[row0 + r] + (1.0f - dones[row0 + r]) * h.gamma * (fminf(q1, q2) - alpha * lp);
+    m.q[2 * h.B + row0 + r] = q1;
+    m.q[3 * h.B + row0 + r] = q2;
+    m.logp_next[row0 + r] = lp;
+    m.y[row0 + r] = rewards[row0 + r] + (1.0f - dones[row0 + r]) * h.gamma * (fminf(q1, q2) - alpha * lp);
   }
 }
 
 // ---- 2: critic blockIdx.y on (obs, act): forward, (q - y) / B, backward
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_critic_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
+  const SacScratch m = sac_member(h, p);
+  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K); act = sac_rows(act, p, (size_t)h.B * A);
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_load(s, act, A, K, row0, h.B);
   mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
   mlp_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
   const float inv_b = 1.0f / (float)h.B;
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
-    const float q = s.D[r * MLP_DLD], d = q - h.y[row0 + r];
-    h.q[c * h.B + row0 + r] = q;
+    const float q = s.D[r * MLP_DLD], d = q - m.y[row0 + r];
+    m.q[c * h.B + row0 + r] = q;
     s.row[0][r] = d * d;
     s.D[r * MLP_DLD] = d * inv_b;   // d (0.5 (mean (Q1 - y)^2 + mean (Q2 - y)^2)) / d q
   }
@@ -131,45 +172,49 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_critic_kernel(const SacDev 
   if (t == 0) {
     double sum = 0.0;
     for (int r = 0; r < MLP_T; r++) sum += (double)s.row[0][r];
-    h.loss_part[blockIdx.x * SAC_NLOSS + c] = (float)sum;
+    m.loss_part[blockIdx.x * SAC_NLOSS + c] = (float)sum;
   }
-  mlp_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, h.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
+  mlp_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, m.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
 }
 
 // ---- 4: the updated critic blockIdx.y on (obs, a_pi): q and d q / d a
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_q_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+  const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
+  const SacScratch m = sac_member(h, p);
+  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K);
   mlp_load(s, obs, K, 0, row0, h.B);
-  mlp_load(s, h.a_pi, A, K, row0, h.B);
+  mlp_load(s, m.a_pi, A, K, row0, h.B);
   mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
   mlp_head(s, P, h.q_ow[c], h.q_ob[c], h.depth, 1);
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
-    h.q[(4 + c) * h.B + row0 + r] = s.D[r * MLP_DLD];
+    m.q[(4 + c) * h.B + row0 + r] = s.D[r * MLP_DLD];
     s.D[r * MLP_DLD] = 1.0f;
   }
   __syncthreads();
   mlp_backward(s, P, h.q_w[c], h.q_b[c], h.q_ow[c], h.q_ob[c], h.depth, K + A, 1, nullptr, false, K + 1, MLP_ACT_RELU);
-  for (int i = t; i < MLP_T * A; i += (int)blockDim.x) h.dqda[((size_t)c * h.B + row0 + i / A) * A + i % A] = s.D[(i / A) * MLP_DLD + i % A];
+  for (int i = t; i < MLP_T * A; i += (int)blockDim.x) m.dqda[((size_t)c * h.B + row0 + i / A) * A + i % A] = s.D[(i / A) * MLP_DLD + i % A];
 }
 
 // ---- 5: the actor's loss mean(alpha logp - min(Q1, Q2)(obs, a_pi)) and its gradient
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ eps_pi,
                                                                   uint64_t count) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, K = h.K, A = h.A, t = (int)threadIdx.x;
+  const int row0 = (int)blockIdx.x * MLP_T, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
+  const SacScratch m = sac_member(h, p);
+  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K); eps_pi = sac_rows(eps_pi, p, (size_t)h.B * A);
   mlp_load(s, obs, K, 0, row0, h.B);
-  mlp_noise(s, eps_pi, A, row0, h.B, h.seed, count, STREAM_SAC, 0);
+  mlp_noise(s, eps_pi, A, row0, h.B, m.seed, count, STREAM_SAC, 0);
   mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
   mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
   const float alpha = sac_alpha(h, P), inv_b = 1.0f / (float)h.B;
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
-    const float q1 = h.q[4 * h.B + row0 + r], q2 = h.q[5 * h.B + row0 + r];
-    const float* dq = h.dqda + ((size_t)(q1 <= q2 ? 0 : 1) * h.B + row0 + r) * A;
+    const float q1 = m.q[4 * h.B + row0 + r], q2 = m.q[5 * h.B + row0 + r];
+    const float* dq = m.dqda + ((size_t)(q1 <= q2 ? 0 : 1) * h.B + row0 + r) * A;
     s.row[1][r] = alpha * s.row[0][r] - fminf(q1, q2);
     for (int j = 0; j < A; j++) {
       const float raw = s.D[r * MLP_DLD + A + j];
@@ -185,60 +230,66 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h
   if (t == 0) {
     double la = 0.0, lp = 0.0;
     for (int r = 0; r < MLP_T; r++) { la += (double)s.row[1][r]; lp += (double)s.row[0][r]; }
-    h.loss_part[blockIdx.x * SAC_NLOSS + 2] = (float)la;
-    h.loss_part[blockIdx.x * SAC_NLOSS + 3] = (float)lp;
+    m.loss_part[blockIdx.x * SAC_NLOSS + 2] = (float)la;
+    m.loss_part[blockIdx.x * SAC_NLOSS + 3] = (float)lp;
   }
-  mlp_backward(s, P, h.a_w, h.a_b, h.a_hw, h.a_hb, h.depth, K, 2 * A, h.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
+  mlp_backward(s, P, h.a_w, h.a_b, h.a_hw, h.a_hb, h.depth, K, 2 * A, m.part + (size_t)blockIdx.x * h.n_params, true, 0, MLP_ACT_RELU);
 }
 
 // ---- 3 and 6: parameters [lo, hi): the gradient (the tiles' parts in tile order), torch's Adam with eps 1e-8 (mlp_adam).  `target` non-null: target[i - lo] <-
 // (1 - tau) target + tau param, the polyak update of the critics (lo = n_actor).  `coef` (the actor's launch): thread 0 of block 0 also sums the losses and, when
-// the coefficient is learned, takes its gradient -mean(logp + target_entropy) and its Adam step.
+// the coefficient is learned, takes its gradient -mean(logp + target_entropy) and its Adam step.  Grid (blocks of [lo, hi), 1, members): the tail runs once per member.
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int lo, int hi, double lr,
                                                                  double bc1, double bc2, float* __restrict__ target, double tau, int coef) {
-  const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x), p = (int)blockIdx.z;
+  const SacScratch m = sac_member(h, p);
+  P = sac_rows(P, p, (size_t)h.n_params); M = sac_rows(M, p, (size_t)h.n_params); V = sac_rows(V, p, (size_t)h.n_params);
+  target = sac_rows(target, p, 2 * (size_t)h.n_critic);
   if (i < hi) {
-    float g = h.part[i];
-    for (int tl = 1; tl < h.tiles; tl++) g += h.part[(size_t)tl * h.n_params + i];
-    h.grad[i] = g;
+    float g = m.part[i];
+    for (int tl = 1; tl < h.tiles; tl++) g += m.part[(size_t)tl * h.n_params + i];
+    m.grad[i] = g;
     const float p = mlp_adam(P, M, V, i, (double)g, lr, bc1, bc2, 1e-8);
     if (target) target[i - lo] = (float)((1.0 - tau) * (double)target[i - lo] + tau * (double)p);
   }
   if (coef && blockIdx.x == 0 && threadIdx.x == 0) {
     double sq1 = 0.0, sq2 = 0.0, la = 0.0, lp = 0.0;
     for (int tl = 0; tl < h.tiles; tl++) {
-      sq1 += (double)h.loss_part[tl * SAC_NLOSS];
-      sq2 += (double)h.loss_part[tl * SAC_NLOSS + 1];
-      la += (double)h.loss_part[tl * SAC_NLOSS + 2];
-      lp += (double)h.loss_part[tl * SAC_NLOSS + 3];
+      sq1 += (double)m.loss_part[tl * SAC_NLOSS];
+      sq2 += (double)m.loss_part[tl * SAC_NLOSS + 1];
+      la += (double)m.loss_part[tl * SAC_NLOSS + 2];
+      lp += (double)m.loss_part[tl * SAC_NLOSS + 3];
     }
     const double inv_b = 1.0 / (double)h.B;
     const int ia = h.n_params - 1;
     const float mean_lp = (float)(lp * inv_b + (double)h.target_entropy);   // mean(logp + target_entropy)
-    h.losses[0] = (float)(la * inv_b);
-    h.losses[1] = (float)(0.5 * (sq1 + sq2) * inv_b);
-    h.losses[2] = h.auto_alpha ? -P[ia] * mean_lp : 0.0f;
-    h.losses[3] = h.auto_alpha ? expf(P[ia]) : h.alpha_fixed;
-    h.grad[ia] = 0.0f;
+    m.losses[0] = (float)(la * inv_b);
+    m.losses[1] = (float)(0.5 * (sq1 + sq2) * inv_b);
+    m.losses[2] = h.auto_alpha ? -P[ia] * mean_lp : 0.0f;
+    m.losses[3] = h.auto_alpha ? expf(P[ia]) : h.alpha_fixed;
+    m.grad[ia] = 0.0f;
     if (h.auto_alpha) {
       const float g = -mean_lp;
-      h.grad[ia] = g;
+      m.grad[ia] = g;
       mlp_adam(P, M, V, ia, (double)g, lr, bc1, bc2, 1e-8);
     }
   }
 }
 
-// ---- the actor's forward pass on any number of rows: tanh(mu + std eps) or, deterministic, tanh(mu); a tile of rows per workgroup
+// ---- the actor's forward pass on any number of rows: tanh(mu + std eps) or, deterministic, tanh(mu); a tile of rows per workgroup.  Grid (tiles of a group,
+// members): obs, eps_in and out are [P][n][.], member blockIdx.y's actor on its group of n rows.  The tile's bound is the end of the group, and a draw's key
+// the row's index in the group.
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_act_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ obs, int n, const float* __restrict__ eps_in,
                                                                 int deterministic, uint64_t call, float* __restrict__ out) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, K = h.K, A = h.A;
+  const int row0 = (int)blockIdx.x * MLP_T, p = (int)blockIdx.y, K = h.K, A = h.A;
   if (row0 >= n) return;
+  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)n * K); eps_in = sac_rows(eps_in, p, (size_t)n * A); out = sac_rows(out, p, (size_t)n * A);
   mlp_load(s, obs, K, 0, row0, n);
   if (deterministic) {
     for (int i = (int)threadIdx.x; i < MLP_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
   } else {
-    mlp_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_SAC_ACT, 0);
+    mlp_noise(s, eps_in, A, row0, n, h.seeds[p], call, STREAM_SAC_ACT, 0);
   }
   mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
   mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);

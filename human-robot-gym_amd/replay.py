@@ -143,6 +143,29 @@ class ReplayBuffer(EpisodeBuffer):
         self.last_index = idx
         return ReplayBufferSamples(observations=obs, actions=act, next_observations=nobs, dones=done, rewards=rew)
 
+    def sample_groups(self, n_groups, batch_size, seeds):
+        """A population's sample: the envs are `n_groups` groups of n / n_groups consecutive envs, and group g's `batch_size` transitions come from its own
+        envs under `seeds[g]` -- the draws of `sample` on a buffer of the group's envs with that seed, at the same call (a counter of this method's own).
+        ReplayBufferSamples with [n_groups * batch_size, .] rows, group g's at g * batch_size.  `record_index` / `last_index` as for `sample`."""
+        t = self.torch
+        G, B = int(n_groups), int(batch_size)
+        if G < 1 or self.n % G:
+            raise ValueError(f"sample_groups: n_envs = {self.n} is not divisible by n_groups = {G}: every member samples a group of the same size")
+        if B < 1:
+            raise ValueError("sample_groups: batch_size must be positive")
+        key = tuple(int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds)
+        if len(key) != G:
+            raise ValueError(f"sample_groups: {len(key)} seeds for {G} groups")
+        if getattr(self, "_group_seeds", (None, None))[0] != key:   # the table the kernel reads: uploaded once per set of seeds
+            self._group_seeds = (key, t.from_numpy(np.array(key, np.uint64).view(np.int64)).to(self.device))
+        new = lambda w: t.empty(G * B, w, dtype=t.float32, device=self.device)   # noqa: E731
+        obs, act, nobs, done, rew = new(self.obs_dim), new(self.act_dim), new(self.obs_dim), new(1), new(1)
+        idx = t.empty(G * B, INDEX_DIM, dtype=t.int64, device=self.device) if self.record_index else None
+        with t.cuda.device(self.device):
+            self._check(self.lib, self.lib.hrg_sac_population_sample(self.h, G, B, _ptr(self._group_seeds[1]), *map(_ptr, (obs, act, nobs, done, rew, idx)), self._stream()))
+        self.last_index = idx
+        return ReplayBufferSamples(observations=obs, actions=act, next_observations=nobs, dones=done, rewards=rew)
+
     def _size_words(self):
         w = (ctypes.c_int64 * 4)()
         self._check(self.lib, self.lib.hrg_replay_size(self.h, w))

@@ -558,6 +558,7 @@ class HipVecEnv(_VecEnvBase):
         self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
         self._replay_args = None     # arguments of attach_replay, likewise
         self.sac = None              # the SAC learner (sac.SacLearner), once attached
+        self.sac_population = None   # the SAC population (sac.SacPopulation), once attached
         self.ppo = None              # the PPO learner (ppo.PpoLearner), once attached
         self._buffers_behind = False   # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
@@ -750,6 +751,9 @@ class HipVecEnv(_VecEnvBase):
         if self.sac is not None:
             self.sac.close()
             self.sac = None
+        if self.sac_population is not None:
+            self.sac_population.close()
+            self.sac_population = None
         if self.ppo is not None:
             self.ppo.close()
             self.ppo = None
@@ -1107,6 +1111,31 @@ class HipVecEnv(_VecEnvBase):
                                           f"observation); the kernels cover {CONST['HRG_OBS_DIM']}: construct the env with obs_keys that select fewer columns")
         from .sac import SacLearner
         return self._attach_learner("sac", SacLearner, obs_dim, rb, **kwargs)
+
+    def attach_sac_population(self, n_members, seeds=None, **kwargs):
+        """`n_members` SAC learners that differ in their seed only, stepped in the same launches (sac.SacPopulation; SacLearner's keywords but `seed`), after
+        attach_replay: the envs are n_members groups of num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`:
+        one per member (default: the env's seed + p).  Refused: a goal env, envs that the members do not divide, the mixed batch.  Returns the population and
+        keeps it as `env.sac_population`: `env.collect_steps(pop.act, train_freq)`, then `pop.train(env.replay, gradient_steps)`."""
+        from .sac import SacPopulation, check_seeds
+        P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]
+        if "seed" in kwargs:
+            raise TypeError("attach_sac_population: the members' seeds are `seeds` (one per member), not `seed`")
+        if self.goal_env:
+            raise NotImplementedError("attach_sac_population: goal_env: the hindsight buffer has no grouped sample (populations cover SAC on flat observations)")
+        if self.num_envs % P:
+            raise NotImplementedError(f"attach_sac_population: num_envs = {self.num_envs} is not divisible by n_members = {P}: every member steps a group of the same size")
+        why = self._replay_refusal()
+        if why is not None:
+            raise NotImplementedError(f"attach_sac_population: {why}")
+        rb = self.replay
+        if rb is None:
+            raise NotImplementedError("attach_sac_population: call attach_replay(buffer_size) first (the members take their observation and action widths from the buffer)")
+        pop = SacPopulation(rb.obs_dim, rb.act_dim, P, [int(self._desc.seed) + p for p in range(P)] if seeds is None else seeds, device=rb.device.index, **kwargs)
+        if self.sac_population is not None:
+            self.sac_population.close()
+        self.sac_population = pop
+        return pop
 
     def collect_steps(self, policy, n_steps):
         """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`, on a goal env into `env.her`.

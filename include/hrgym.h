@@ -516,6 +516,7 @@ typedef struct hrg_replay_desc {
 #define HRG_SAC_MAX_DEPTH 3   /* hidden layers: 1 .. 3 */
 #define HRG_SAC_TILE 32       /* rows of the batch per workgroup: batch_size is a multiple */
 #define HRG_SAC_MAX_BATCH 256
+#define HRG_SAC_MAX_POPULATION 64 /* members of a population: learners of one descriptor that differ in their seed and step in the same launches */
 #define HRG_SAC_NQ 6          /* Q columns of hrg_sac_export: Q1, Q2 on (obs, act); the targets' Q1, Q2 on (next_obs, a'); the updated Q1, Q2 on (obs, a_pi) */
 /* One learner: SB3 1.5.0's SAC(MlpPolicy, net_arch = [64] * depth, use_sde = False).  The learning rate is an argument of hrg_sac_step. */
 typedef struct hrg_sac_desc {
@@ -926,6 +927,33 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
                  void* stream);
 int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream);
 int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
+
+/* A SAC population (csrc/hrgym_sac.h): n_members learners of one descriptor that differ in their seed only and take their gradient step in the same
+ * six launches.  The handle is an hrg_sac: the lone learner is the population of one member, and hrg_sac_sizes, hrg_sac_step, hrg_sac_restore and hrg_sac_destroy
+ * serve both.  The counters (gradient steps, act calls) are the handle's: members step in lockstep.  Member p is, bit for bit, the lone learner of seeds[p] on the
+ * same rows: its draws are keyed by its seed and the row's index in its own batch (hrg_sac_population_act: in its own group), its sums are its own.
+ *   hrg_sac_population_create  hrg_sac_create with n_members seeds in place of the descriptor's (which is not read).  Before anything is allocated or launched:
+ *                              HRG_ERR_UNSUPPORTED for n_members outside 1 .. HRG_SAC_MAX_POPULATION, HRG_ERR_INVALID for a null seeds table, then whatever
+ *                              hrg_sac_create refuses.
+ *   hrg_sac_step               on a population: every array is [n_members] times the lone learner's, member p's part at p times its size: observations
+ *                              [P][B][obs_dim], ..., params_dev, adam_m_dev, adam_v_dev [P][n_params], target_dev [P][2 n_critic].
+ *   hrg_sac_population_act     obs_dev float [P][n_group][obs_dim] -> actions_dev float [P][n_group][act_dim], member p's actor (params_dev [P][n_params]) on
+ *                              group p; a draw's key is (seeds[p], act call count, row within the group, 13, j).  eps_dev [P][n_group][act_dim] as in hrg_sac_act,
+ *                              which is this entry for one member and refuses a handle of more.
+ *   hrg_sac_population_export  hrg_sac_export of one member; HRG_ERR_INVALID for a member outside the population. */
+int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_sac** out);
+int hrg_sac_population_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                           void* stream);
+int hrg_sac_population_export(hrg_sac* h, int32_t member, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
+
+/* The grouped sample of the uniform replay buffer, for a population: the n_envs envs are n_groups groups of n_envs / n_groups consecutive envs, and group g's
+ * batch_size samples come from its own envs: sample k draws u0, u1 = rng_u01(seeds[g], grouped call counter, k, 11, 0..1), slot = floor(u0 * upper), env =
+ * g * m + floor(u1 * m) -- hrg_replay_sample's draws of a buffer of the group's m envs with seed seeds[g].  The outputs are hrg_replay_sample's with
+ * [n_groups][batch_size] rows; seeds_dev uint64 [n_groups] is a DEVICE array.  The call counter is this entry's own (hrg_replay_sample's does not move).
+ * HRG_ERR_INVALID for n_groups that do not divide n_envs (before anything is launched), an empty buffer, batch_size < 1, a null seeds table or output.
+ * (Not under the hrg_replay_ prefix: the set of that handle's own entries is closed.) */
+int hrg_sac_population_sample(hrg_replay* h, int32_t n_groups, int32_t batch_size, const uint64_t* seeds_dev, float* observations_dev, float* actions_dev,
+                              float* next_observations_dev, float* dones_dev, float* rewards_dev, int64_t* index_out_dev, void* stream);
 
 /* The PPO learner on the device (csrc/hrgym_ppo.h): one minibatch step of SB3 1.5.0's PPO.train (MlpPolicy, use_sde = False, Box actions) in four launches on one
  * stream, and the forward pass of the policy and of the value function.  Parameters and Adam moments are flat float32 device arrays of the caller's (layout:

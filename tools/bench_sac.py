@@ -4,7 +4,12 @@ tests/sac_ref.py in float32 on the same GPU, eager (autograd, one launch per ope
 
 Both sides draw their batches with replay.sample from the same full buffer; the baseline draws its noise with torch.randn.  Warm-up block first; then blocks of
 `--steps` gradient steps, alternating between the two sides in one process, HIP events around each block, no synchronisation inside a block.
-python tools/bench_sac.py [--blocks 7] [--steps 200]"""
+python tools/bench_sac.py [--blocks 7] [--steps 200]
+
+--population P [P ...] times the step of a population instead (sac.SacPopulation: P learners in the same six launches), written to
+profiles/r21_sac_population.json: milliseconds per (replay.sample_groups, population.step) over P groups of 64 envs at the same shapes, and that time per member.
+No eager baseline: the figure to compare with is P lone steps.
+python tools/bench_sac.py --population 1 2 4 5 8 16 32 64"""
 import argparse
 import json
 import os
@@ -18,13 +23,16 @@ import torch   # noqa: E402
 import sac_ref as R   # noqa: E402
 from human_robot_gym_amd._cstruct import CONST   # noqa: E402
 from human_robot_gym_amd.replay import ReplayBuffer, build_replay_desc   # noqa: E402
-from human_robot_gym_amd.sac import SacLearner   # noqa: E402
+from human_robot_gym_amd.sac import SacLearner, SacPopulation   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--blocks", type=int, default=7)
 ap.add_argument("--steps", type=int, default=200)
-ap.add_argument("--out", default="profiles/r12_sac.json")
+ap.add_argument("--population", type=int, nargs="+", default=None, help="time a population of this many members (several: one after the other)")
+ap.add_argument("--out", default=None, help="default: profiles/r12_sac.json, with --population profiles/r21_sac_population.json")
 args = ap.parse_args()
+if args.out is None:
+    args.out = "profiles/r21_sac_population.json" if args.population else "profiles/r12_sac.json"
 B, A, ARCH, LR, n_envs, slots = 128, 4, [64, 64, 64], 5e-4, 64, 16
 
 
@@ -38,15 +46,33 @@ def timed(fn):
     return e0.elapsed_time(e1)
 
 
-out = dict(batch_size=B, net_arch=ARCH, act_dim=A, steps_per_block=args.steps, blocks=args.blocks, device=torch.cuda.get_device_name(0))
-rng = np.random.RandomState(0)
-for K in (6, 18):
+def full_buffer(rng, n_envs, K):
+    """A replay buffer of `n_envs` envs with every slot filled."""
     rb = ReplayBuffer(build_replay_desc(n_envs, n_envs * slots, list(range(K)), act_dim=A, seed=1))
     dev = lambda x: torch.from_numpy(np.ascontiguousarray(x, np.float32)).cuda()   # noqa: E731
     rb.observe(dev(rng.uniform(-1, 1, (n_envs, 64))))
     for _ in range(slots):
         rb.add_step(dev(rng.uniform(-1, 1, (n_envs, A))), dev(rng.uniform(-1, 1, (n_envs, 64))), dev(rng.uniform(-1, 1, (n_envs, 64))), dev(rng.normal(size=n_envs)),
                     torch.from_numpy((rng.uniform(size=n_envs) < 0.05).astype(np.uint8)).cuda(), torch.zeros(n_envs, CONST["HRG_INFO_DIM"], dtype=torch.int32).cuda())
+    return rb
+
+
+out = dict(batch_size=B, net_arch=ARCH, act_dim=A, steps_per_block=args.steps, blocks=args.blocks, device=torch.cuda.get_device_name(0))
+rng = np.random.RandomState(0)
+for P in args.population or ():
+    for K in (6, 18):
+        rb = full_buffer(rng, P * n_envs, K)
+        pop = SacPopulation(K, A, P, list(range(P)), net_arch=ARCH, learning_rate=LR, ent_coef="auto_0.2", batch_size=B)
+        pop.train(rb, args.steps)   # warm-up
+        ms = [timed(lambda: pop.train(rb, args.steps)) / args.steps for _ in range(args.blocks)]
+        med = float(np.median(ms))
+        out["population_%d_obs_%d" % (P, K)] = dict(n_members=P, obs_dim=K, ms_per_step=ms, ms_median=med, ms_spread=float(np.max(ms) - np.min(ms)), ms_per_member=med / P,
+                                                   finite=bool(torch.isfinite(pop.p.params).all()), n_updates=pop.n_updates)
+        print("population %2d, obs %2d: %.4f ms per population step (sampling included; blocks %s), %.4f ms per member" % (P, K, med, " ".join("%.4f" % x for x in ms), med / P))
+        pop.close()
+        rb.close()
+for K in () if args.population else (6, 18):
+    rb = full_buffer(rng, n_envs, K)
     learner = SacLearner(K, A, net_arch=ARCH, learning_rate=LR, ent_coef="auto_0.2", batch_size=B, seed=0)
     ref = R.RefState({k: v.clone() for k, v in learner.state_dict().items()}, torch.float32, device="cuda")
     cfg = R.Cfg(len(ARCH), LR, 0.99, 0.005, True, 0.2, -float(A), 1)

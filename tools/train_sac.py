@@ -6,9 +6,16 @@
 transitions were collected in the rollout", train_freq * n_envs.  With 8 envs that is 800 per block; with 4096 it would be 409 600: whether a run at thousands of
 envs keeps that ratio is the user's decision.
 
-python tools/train_sac.py --n-envs 1024 --gradient-steps 800 --blocks 20"""
+python tools/train_sac.py --n-envs 1024 --gradient-steps 800 --blocks 20
+
+--seeds 0 1 2 3 4 trains the five seeds of one cell of a study side by side as a population (sac.SacPopulation): the envs are five groups of n-envs / 5, member p
+acts in and learns from group p only and equals, bit for bit, the lone run of its seed on its group's transitions.  --learning-starts then counts a member's
+transitions; the JSON line carries `members`, one dict of episode stats and diagnostics per member; --model-dir receives model_<step>/member_<p>.npz.
+
+python tools/train_sac.py --n-envs 1280 --seeds 0 1 2 3 4 --gradient-steps 800 --blocks 5"""
 import argparse
 import json
+import os
 import sys
 import time
 
@@ -30,36 +37,82 @@ ap.add_argument("--batch-size", type=int, default=128)
 ap.add_argument("--learning-rate", type=float, default=5e-4)
 ap.add_argument("--ent-coef", default="auto_0.2")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--seeds", type=int, nargs="+", default=None, help="a population: one member per seed, n-envs / len(seeds) envs each (the env itself is seeded with --seed)")
 ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
 ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
 ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
 ap.add_argument("--eval-n-envs", type=int, default=64)
 ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
-args = ap.parse_args()
-
-env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
-env.attach_replay(args.buffer_size)
-learner = env.attach_sac(batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef, seed=args.seed)
-gen = torch.Generator(device=learner.device).manual_seed(args.seed)
 
 
-def uniform(obs):
-    return torch.rand(obs.shape[0], learner.act_dim, generator=gen, device=obs.device) * 2.0 - 1.0
+def main(args):
+    env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
+    env.attach_replay(args.buffer_size)
+
+    def run_population():
+        """The loop below for the members of --seeds."""
+        P = len(args.seeds)
+        pop = env.attach_sac_population(P, seeds=args.seeds, batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef)
+        gen = torch.Generator(device=pop.device).manual_seed(args.seed)
+        uniform = lambda obs: torch.rand(obs.shape[0], pop.act_dim, generator=gen, device=obs.device) * 2.0 - 1.0   # noqa: E731
+        eval_env, first, saved_until = None, None, 0
+        if args.eval_episodes > 0:
+            eval_env = hrg.HipVecEnv(args.eval_n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed + 1 if args.eval_seed is None else args.eval_seed))
+            first = pop.member(0)   # (the shapes the stacked parameters follow)
+        per_member = args.n_envs // P
+        t0 = time.time()
+        for block in range(args.blocks):
+            warm = env.replay.size() * per_member < args.learning_starts
+            env.collect_steps(uniform if warm else pop.act, args.train_freq)
+            if env.replay.size() * per_member >= args.learning_starts:
+                pop.train(env.replay, args.gradient_steps)
+            env_steps = (block + 1) * args.train_freq * args.n_envs
+            line = dict(block=block, env_steps=env_steps, policy="uniform" if warm else "actor", seconds=round(time.time() - t0, 3))
+            members = [dict(seed=s, **stats) for s, stats in zip(pop.seeds, env.replay.episode_stats(groups=P))]
+            if pop.n_updates:
+                for m, diag in zip(members, pop.diagnostics()):
+                    m.update(diag)
+            if eval_env is not None:
+                for m, res in zip(members, eval_env.evaluate(pop.p.params, args.eval_episodes, learner=first).by_policy()):
+                    m.update(eval_mean_reward=res.mean_reward, eval_std_reward=res.std_reward, eval_mean_ep_length=res.mean_ep_length)
+            if args.model_dir is not None and args.save_freq > 0 and env_steps // args.save_freq > saved_until:
+                saved_until = env_steps // args.save_freq
+                line["checkpoint"] = pop.save(os.path.join(args.model_dir, f"model_{env_steps}"))
+            line["members"] = members
+            print(json.dumps(line), flush=True)
+        if args.model_dir is not None:
+            pop.save(os.path.join(args.model_dir, "model_final"))
+        if first is not None:
+            first.close()
+            eval_env.close()
+
+    if args.seeds is not None:
+        run_population()
+        env.close()
+        return
+    learner = env.attach_sac(batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef, seed=args.seed)
+    gen = torch.Generator(device=learner.device).manual_seed(args.seed)
+
+    def uniform(obs):
+        return torch.rand(obs.shape[0], learner.act_dim, generator=gen, device=obs.device) * 2.0 - 1.0
+
+    run = run_folder_from_args(args)
+    t0 = time.time()
+    for block in range(args.blocks):
+        stored = env.replay.size() * args.n_envs
+        warm = stored < args.learning_starts
+        env.collect_steps(uniform if warm else learner.act, args.train_freq)
+        if env.replay.size() * args.n_envs >= args.learning_starts:
+            learner.train(env.replay, args.gradient_steps)
+        line = dict(block=block, env_steps=(block + 1) * args.train_freq * args.n_envs, policy="uniform" if warm else "actor", seconds=round(time.time() - t0, 3))
+        line.update(env.replay.episode_stats())
+        if learner.n_updates:
+            line.update(learner.diagnostics())
+        line.update(run.after(learner, line["env_steps"]))
+        print(json.dumps(line), flush=True)
+    run.finish(learner)
+    env.close()
 
 
-run = run_folder_from_args(args)
-t0 = time.time()
-for block in range(args.blocks):
-    stored = env.replay.size() * args.n_envs
-    warm = stored < args.learning_starts
-    env.collect_steps(uniform if warm else learner.act, args.train_freq)
-    if env.replay.size() * args.n_envs >= args.learning_starts:
-        learner.train(env.replay, args.gradient_steps)
-    line = dict(block=block, env_steps=(block + 1) * args.train_freq * args.n_envs, policy="uniform" if warm else "actor", seconds=round(time.time() - t0, 3))
-    line.update(env.replay.episode_stats())
-    if learner.n_updates:
-        line.update(learner.diagnostics())
-    line.update(run.after(learner, line["env_steps"]))
-    print(json.dumps(line), flush=True)
-run.finish(learner)
-env.close()
+if __name__ == "__main__":   # (imported: the parser `ap` only)
+    main(ap.parse_args())
