@@ -338,7 +338,6 @@ struct Lds {
 #define HRG_LDS_ENVS_PER_CU 16
 #endif
 static_assert(sizeof(Lds) * HRG_LDS_ENVS_PER_CU <= 160 * 1024, "the per-env LDS image has outgrown this variant's envs per CU");
-
 // The per-env LDS image is a file-scope __shared__ object: every device function addresses it directly (ds_* instructions),
 // nothing is passed around as a generic pointer.
 // HRG_WG_WAVES envs (one wave each) may share a workgroup: with W = 4 the dispatcher has to place the four waves of a workgroup at once, one per
@@ -981,6 +980,15 @@ DI double uniform_f64(double v) {
   const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffLL));
   const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+// A lane's own base address inside the LDS image, for a stretch of accesses at compile-time offsets from it: p = constant + lane term, opaque from here on.  The
+// compiler otherwise keeps the lane term alone in a register and adds the constant back in front of every two-address access (ds_read2 / ds_write2 take 8-bit offsets,
+// the image is 10 KB): one v_add_u32 per access.  From an opaque base the offsets are the small ones and go into the instructions.
+typedef __attribute__((address_space(3))) double LdsF64;
+DI LdsF64* lds_lane_base(double* p) {
+  unsigned a = (unsigned)(size_t)(LdsF64*)p;
+  asm volatile("" : "+v"(a));
+  return (LdsF64*)(size_t)a;
 }
 // a value of lane K (compile-time) in every lane: two v_readlane into SGPRs instead of an LDS-crossbar shuffle
 template <int K>

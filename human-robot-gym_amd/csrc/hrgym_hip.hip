@@ -3163,7 +3163,25 @@ __global__ __launch_bounds__(64) void hrg_model_constants_tap_kernel(const DevMo
 }
 #endif
 
-// Launch shims: every translation unit defines this pair for its own kernels, under the variant's name and with hidden visibility; the host side (the base
+// test tap (hrg_debug_chain_fk): robot_chain_fk on its own, one wave per triple q[k] = [3][NARM] of joint angles: the shield's current configuration, the one at the
+// end of the brake, the simulation state (fingers at 0).  out[k] = [kR NV x 9 | kp NV x 3 | scap 2 x 7 x 6]; without the shield only the simulation state is walked
+// and the scap block is 0.  Every variant compiles it against its own LDS image.
+__global__ __launch_bounds__(64) void HRG_SYM(hrg_chain_fk_kernel)(const DevModel* __restrict__ dm_, const double* __restrict__ q, int n, int shield_on, double* __restrict__ out) {
+  const int lane = hrg_lane(), k = (int)blockIdx.x;
+  if (k >= n) return;
+  Lds& L = g_L;
+  const double* qk = q + (size_t)k * 3 * NARM;
+  if (lane < NARM) { L.cq[lane] = qk[lane]; L.qe[lane] = qk[NARM + lane]; }
+  if (lane < NV) L.st.qpos[lane] = lane < NARM ? qk[2 * NARM + lane] : 0.0;
+  wave_sync();
+  robot_chain_fk(dm_, lane, shield_on != 0);
+  double* o = out + (size_t)k * HRG_CFK_DIM;
+  for (int j = lane; j < 9 * NV; j += 64) o[HRG_CFK_KR + j] = (&L.kR[0][0])[j];
+  if (lane < 3 * NV) o[HRG_CFK_KP + lane] = (&L.kp[0][0])[lane];
+  for (int j = lane; j < 2 * HRG_NSHIELD_RCAP * 6; j += 64) o[HRG_CFK_SCAP + j] = shield_on ? (&L.scap[0][0][0])[j] : 0.0;
+}
+
+// Launch shims: every translation unit defines these for its own kernels, under the variant's name and with hidden visibility; the host side (the base
 // translation unit) reaches them through its variant table (HRG_VARIANTS, hrgym_host_batch.h).  objs = the variant's object array (ObjState), null for the ReachHuman kernels.
 typedef void hrg_launch_step_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
                                 int32_t* info, double* dbg_r, double* dbg_h, int32_t* dbg_nh, int64_t env_id0, float* scratch_obs, void* objs, StepOrder ord);
@@ -3177,6 +3195,11 @@ extern "C" void HRG_SYM(hrg_launch_step)(int n_envs, hipStream_t st, const DevMo
 }
 extern "C" void HRG_SYM(hrg_launch_reset)(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, const uint8_t* mask, float* obs, int64_t env_id0, void* objs) {
   hipLaunchKernelGGL(HRG_SYM(hrg_reset_kernel), HRG_LAUNCH_DIMS(n_envs), 0, st, dm, states, mask, obs, env_id0, (ObjState*)objs, n_envs);
+}
+typedef void hrg_launch_chain_fk_fn(int n, const DevModel* dm, const double* q, int shield_on, double* out);
+extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn HRG_SYM(hrg_launch_chain_fk);
+extern "C" void HRG_SYM(hrg_launch_chain_fk)(int n, const DevModel* dm, const double* q, int shield_on, double* out) {
+  hipLaunchKernelGGL(HRG_SYM(hrg_chain_fk_kernel), dim3((unsigned)n), dim3(64), 0, 0, dm, q, n, shield_on, out);
 }
 
 #ifdef HRG_STAMPS

@@ -69,14 +69,15 @@ enum { HRG_FAM_REACH, HRG_FAM_BOX, HRG_FAM_HO, HRG_FAM_LIFT, HRG_FAM_STACK, HRG_
   X(HRG_FAM_HAMMER, 0, _hammer)  X(HRG_FAM_HAMMER, 1, _hammer_hull)
 #define X(family, hulls, sfx)                                                                  \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn hrg_launch_step##sfx;    \
-  extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;  \
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn hrg_launch_chain_fk##sfx;
 HRG_VARIANTS(X)
 #undef X
-struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; };
+struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; hrg_launch_chain_fk_fn* chain_fk; };
 struct VariantTable { Variant v[HRG_NFAMILY][2]; };   // [family][hulls]
 static constexpr VariantTable make_variants() {
   VariantTable t{};
-#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx};
+#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx, hrg_launch_chain_fk##sfx};
   HRG_VARIANTS(X)
 #undef X
   return t;
@@ -732,6 +733,17 @@ int hrg_debug_model_constants(hrg_batch* b, double* out_host) {
     hipMemset(d[0], 0, sizeof(double) * 2 * HRG_MC_DIM);
     hipLaunchKernelGGL(hrg_model_constants_tap_kernel, dim3(1), dim3(64), 0, 0, b->d_model, 0.0, (double*)d[0]);
   }), "hrg_debug_model_constants");
+}
+
+int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t shield_on, double* out_host) {
+  if (!b || !q_host || !out_host || n < 1 || n > 64) return fail(HRG_ERR_INVALID, "null argument or n outside 1..64");
+  HIPCHK(hipSetDevice(b->device));
+  void* objs;
+  const Variant& v = batch_variant(b, &objs);
+  const TapBuf in[] = {{q_host, sizeof(double) * 3 * NARM * (size_t)n}};
+  return tap_result(hrg_run_tap(in, 1, out_host, sizeof(double) * HRG_CFK_DIM * (size_t)n, [&](void** d) {
+    v.chain_fk((int)n, b->d_model, (const double*)d[0], shield_on ? 1 : 0, (double*)d[1]);
+  }), "hrg_debug_chain_fk");
 }
 
 } // extern "C"

@@ -7,6 +7,16 @@
 #endif
 
 // ================================================================================================ robot tree
+// The chain walk's sums in the instruction shapes the step kernels have always computed them in, written out so that no rearrangement of the code around them
+// changes how they contract (outputs are compared bit for bit across changes): a . b as fma(a2, b2, fma(a0, b0, a1 b1)), and a sum that starts from zero and takes
+// its terms in order, fma(a2, b2, fma(a1, b1, fma(a0, b0, 0))).
+DI double chain_dot(double a0, double a1, double a2, double b0, double b1, double b2) {
+#pragma clang fp contract(off)
+  return __builtin_fma(a2, b2, __builtin_fma(a0, b0, a1 * b1));
+}
+DI double chain_acc(double a0, double a1, double a2, double b0, double b1, double b2) {
+  return __builtin_fma(a2, b2, __builtin_fma(a1, b1, __builtin_fma(a0, b0, 0.0)));
+}
 // Chain kinematics for THREE configurations at once (lanes 0,1,2): 0 = shield's current commanded motion,
 // 1 = configuration at the end of the fail-safe brake (both feed RobotReach), 2 = simulation state
 // (mj_kinematics of sim.forward(), environments/manipulation/human_env.py:504).
@@ -15,13 +25,13 @@ DI void robot_chain_fk(const DevModel* __restrict__ dm_, int lane, bool shield_o
   Lds& L = g_L;
   // the 18 joint angles (3 configurations x 6 hinges) take their sine and cosine on 18 lanes at once; the walk along the chain below reads them back (scratch:
   // the robot reach capsules L.rc, which the shield fills only after this call)
-  double* sc = &L.rc[0][0];
   if (lane < 3 * NARM && (lane >= 2 * NARM || shield_on)) {
     const int cfg = lane / NARM, i = lane - NARM * cfg;
     const double q = cfg == 0 ? L.cq[i] : (cfg == 1 ? L.qe[i] : L.st.qpos[i]);
     double sn, cs;
     sincos_small(q, &sn, &cs);
-    sc[2 * lane] = sn; sc[2 * lane + 1] = cs;
+    LdsF64* o = lds_lane_base(&L.rc[0][0] + 2 * lane);
+    o[0] = sn; o[1] = cs;
   }
   wave_sync();
   // lanes = (configuration, row): row r of a product R A is (row r of R) A and component r of R v is (row r of R) . v, so a
@@ -32,32 +42,40 @@ DI void robot_chain_fk(const DevModel* __restrict__ dm_, int lane, bool shield_o
     const int cfg = lane / 3, row = lane - 3 * cfg;
     double r0 = dm->Rbase[3 * row], r1 = dm->Rbase[3 * row + 1], r2 = dm->Rbase[3 * row + 2];
     double p = m.base_pos[row];
-#pragma unroll 1
+    // Unrolled, from one opaque per-lane base per array: every model constant sits at a constant offset from the scalar base and every LDS access at a constant
+    // offset in its instruction, so the walk issues no address arithmetic.  (Taking the six numbers cs c0 + sn c1, cs c1 - sn c0 of a joint, which are the same in
+    // the three row lanes, off the walk into a table that the 18 sine / cosine lanes fill removes 53 more vector instructions per cycle and makes the kernel
+    // slower: the table's LDS traffic costs more than they do, and an LDS image that grows by its 472 B costs 3.5 % by itself.  DESIGN.md section 7, r22.)
+    const LdsF64* sc = lds_lane_base(&L.rc[0][0] + 2 * NARM * cfg);
+    LdsF64* kR = lds_lane_base(&L.kR[0][3 * row]), *kp = lds_lane_base(&L.kp[0][row]), *scap = lds_lane_base(&L.scap[cfg < 2 ? cfg : 0][0][row]);
+#pragma unroll
     for (int i = 0; i < NARM; i++) {
-      const double sn = sc[2 * (NARM * cfg + i)], cs = sc[2 * (NARM * cfg + i) + 1];
-      p += r0 * m.body_pos[i][0] + r1 * m.body_pos[i][1] + r2 * m.body_pos[i][2];
+      p += chain_dot(r0, r1, r2, m.body_pos[i][0], m.body_pos[i][1], m.body_pos[i][2]);
       // arm hinges turn about the local z axis (robot.xml:33-58, checked at create): Rq Rz(q) mixes the first two columns
-      double n0 = 0, n1 = 0, n2 = 0;
+      double A[3], B[3];
       {
-        const double ra[3] = {r0, r1, r2};
+#pragma clang fp contract(off)
+        const double sn = sc[2 * i], cs = sc[2 * i + 1];
 #pragma unroll
         for (int a = 0; a < 3; a++) {
-          const double c0 = dm->Rq[i][3 * a], c1 = dm->Rq[i][3 * a + 1], c2 = dm->Rq[i][3 * a + 2];
-          n0 += ra[a] * (cs * c0 + sn * c1);
-          n1 += ra[a] * (cs * c1 - sn * c0);
-          n2 += ra[a] * c2;
+          const double c0 = dm->Rq[i][3 * a], c1 = dm->Rq[i][3 * a + 1];
+          A[a] = __builtin_fma(cs, c0, sn * c1);
+          B[a] = __builtin_fma(cs, c1, -(sn * c0));
         }
       }
+      const double n0 = chain_acc(r0, r1, r2, A[0], A[1], A[2]);
+      const double n1 = chain_acc(r0, r1, r2, B[0], B[1], B[2]);
+      const double n2 = chain_acc(r0, r1, r2, dm->Rq[i][2], dm->Rq[i][5], dm->Rq[i][8]);
       r0 = n0; r1 = n1; r2 = n2;
       if (cfg == 2) {
-        L.kR[i][3 * row] = r0; L.kR[i][3 * row + 1] = r1; L.kR[i][3 * row + 2] = r2;
-        L.kp[i][row] = p;
+        kR[9 * i] = r0; kR[9 * i + 1] = r1; kR[9 * i + 2] = r2;
+        kp[3 * i] = p;
       } else {
-        L.scap[cfg][i][row] = p + (r0 * m.scap_p1[i][0] + r1 * m.scap_p1[i][1] + r2 * m.scap_p1[i][2]);
-        L.scap[cfg][i][3 + row] = p + (r0 * m.scap_p2[i][0] + r1 * m.scap_p2[i][1] + r2 * m.scap_p2[i][2]);
+        scap[6 * i] = p + chain_dot(r0, r1, r2, m.scap_p1[i][0], m.scap_p1[i][1], m.scap_p1[i][2]);
+        scap[6 * i + 3] = p + chain_dot(r0, r1, r2, m.scap_p2[i][0], m.scap_p2[i][1], m.scap_p2[i][2]);
         if (i == NARM - 1) {
-          L.scap[cfg][NARM][row] = p + (r0 * m.scap_p1[NARM][0] + r1 * m.scap_p1[NARM][1] + r2 * m.scap_p1[NARM][2]);
-          L.scap[cfg][NARM][3 + row] = p + (r0 * m.scap_p2[NARM][0] + r1 * m.scap_p2[NARM][1] + r2 * m.scap_p2[NARM][2]);
+          scap[6 * NARM] = p + chain_dot(r0, r1, r2, m.scap_p1[NARM][0], m.scap_p1[NARM][1], m.scap_p1[NARM][2]);
+          scap[6 * NARM + 3] = p + chain_dot(r0, r1, r2, m.scap_p2[NARM][0], m.scap_p2[NARM][1], m.scap_p2[NARM][2]);
         }
       }
     }

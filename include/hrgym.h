@@ -699,6 +699,13 @@ int hrg_debug_cull_box(const double* in_host, int32_t n, double* out_host);
 enum { HRG_MC_FRIC_D = 0, HRG_MC_FRIC_LIM = HRG_NV + 1, HRG_MC_FRIC_IMP = 2 * (HRG_NV + 1), HRG_MC_EUL_HD = 3 * (HRG_NV + 1), HRG_MC_EUL_RHD = HRG_MC_EUL_HD + HRG_NV,
        HRG_MC_EUL_FINGERS = HRG_MC_EUL_RHD + 2, HRG_MC_RCAP_MID = HRG_MC_EUL_FINGERS + 1, HRG_MC_DIM = HRG_MC_RCAP_MID + 3 * HRG_NRCAP };
 int hrg_debug_model_constants(hrg_batch* b, double* out_host);
+/* test tap of the robot's chain kinematics (robot_chain_fk, csrc/hrgym_kernels.h) as the batch's kernel variant compiles it: n (1..64) triples q_host[n][3][HRG_NARM] of
+ * arm joint angles -- the shield's current configuration, the configuration at the end of its brake, the simulation state (fingers at 0) -- one wavefront per triple ->
+ * out_host[n][HRG_CFK_DIM]: HRG_CFK_KR the world rotation [HRG_NV][9] and HRG_CFK_KP the world position [HRG_NV][3] of the bodies at the simulation state, HRG_CFK_SCAP
+ * the robot reach capsule end points [2][HRG_NSHIELD_RCAP][6] (p1, p2) at the first two configurations.  shield_on = 0 walks the simulation state alone, as the kernels
+ * do without a shield: the HRG_CFK_SCAP block is then 0 and the first two configurations are not read.  0 / -1. */
+enum { HRG_CFK_KR = 0, HRG_CFK_KP = 9 * HRG_NV, HRG_CFK_SCAP = 12 * HRG_NV, HRG_CFK_DIM = HRG_CFK_SCAP + 2 * HRG_NSHIELD_RCAP * 6 };
+int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t shield_on, double* out_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the
