@@ -38,9 +38,9 @@ def __getattr__(name):
     if name in ("SacLearner", "SacPopulation"):
         from . import sac
         return getattr(sac, name)
-    if name == "PpoLearner":
-        from .ppo import PpoLearner
-        return PpoLearner
+    if name in ("PpoLearner", "PpoPopulation"):
+        from . import ppo
+        return getattr(ppo, name)
     if name == "HipBatch":
         from ._lib import HipBatch
         return HipBatch

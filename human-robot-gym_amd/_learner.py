@@ -1,5 +1,6 @@
 """What the device learners share (sac.SacLearner, ppo.PpoLearner; csrc/hrgym_mlp.h): the refusal of widths the tile kernels do not cover, the flat parameter
-layout, the tensors behind `state_dict()` with their seeded initialisation, and the learner's calls that differ by the entry points' prefix only."""
+layout, the tensors behind `state_dict()` with their seeded initialisation, the learner's calls that differ by the entry points' prefix only, and what the
+two populations share (sac.SacPopulation, ppo.PpoPopulation): the seeds table, the stacked tensors, a member as a lone learner, the checkpoints per member."""
 import ctypes
 import os
 from collections import OrderedDict
@@ -149,6 +150,113 @@ def restore_tensors(p, ckpt):
             raise ValueError(f"checkpoint: {name} is {src.dtype} {tuple(src.shape)}, the learner's is float32 {tuple(own.shape)} (a checkpoint of other shapes)")
         with torch.no_grad():
             own.copy_(torch.from_numpy(src).to(own.device))
+
+
+# ---- populations: what sac.SacPopulation and ppo.PpoPopulation share ----
+MAX_POPULATION = CONST["HRG_SAC_MAX_POPULATION"]
+assert MAX_POPULATION == CONST["HRG_PPO_MAX_POPULATION"]
+
+
+def check_seeds(n_members, seeds):
+    """(P, the members' seeds as uint64 [P]); NotImplementedError for a population the kernels do not cover, ValueError for a seeds table of another length."""
+    P = int(n_members)
+    if not 1 <= P <= MAX_POPULATION:
+        raise NotImplementedError(f"n_members = {P}: a population has 1 .. {MAX_POPULATION} members")
+    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+    if len(seeds) != P:
+        raise ValueError(f"seeds: {len(seeds)} seeds for {P} members")
+    return P, np.array(seeds, np.uint64)
+
+
+class PopulationParams:
+    """The tensors of a population, on any torch device: every tensor of the lone learners' LearnerParams `rows` stacked, [P, ...].  Row p is member p's,
+    initialised exactly as the lone learner of its seed; `member(p)` is the rows of member p as views."""
+
+    def __init__(self, rows, device):
+        import torch
+        self.layout, self.n_params = rows[0].layout, rows[0].n_params
+        for name in TENSORS:
+            if hasattr(rows[0], name):
+                setattr(self, name, torch.stack([getattr(r, name) for r in rows]).to(device))
+
+    def member(self, p):
+        from types import SimpleNamespace
+        return SimpleNamespace(**{name: getattr(self, name)[p] for name in TENSORS if hasattr(self, name)})
+
+
+class Population:
+    """What the populations add to their lone learner's class, ahead of it in the bases: `_lone` is that class, `n_members`, `seeds` (ints) and `_kwargs` (the
+    lone learner's constructor keywords apart from the seed, the device and the scheduled attributes of `_hyper`) are set by the subclass, `p` is a
+    PopulationParams."""
+    _lone = None
+
+    def _export(self, *arrays, member=0):
+        self._check(self.lib, getattr(self.lib, self._prefix + "_population_export")(self.h, int(member), *(None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrays)))
+
+    def export(self, member=0):
+        """The lone learner's export of one member."""
+        return super().export(member=member)
+
+    def diagnostics(self):
+        """The lone learner's diagnostics of every member: a list of n_members dicts.  Synchronous."""
+        return [super(Population, self).diagnostics(member=p) for p in range(self.n_members)]
+
+    def _restore(self, steps, calls):
+        self._check(self.lib, getattr(self.lib, self._prefix + "_restore")(self.h, int(steps), int(calls)))
+
+    def member(self, p):
+        """Member p as a lone learner of its own: copies of its tensors, the population's counters and scheduled attributes.  Fed the same batches, it
+        continues bit for bit.  The caller closes it."""
+        if not 0 <= int(p) < self.n_members:
+            raise IndexError(f"member {p} of {self.n_members}")
+        learner = self._lone(self.obs_dim, self.act_dim, seed=self.seeds[p], device=self.device.index, **self._kwargs, **self._hyper())
+        sizes = self._sizes()
+        with self.torch.no_grad():
+            for name, rows in vars(self.p.member(int(p))).items():
+                getattr(learner.p, name).copy_(rows)
+        Population._restore(learner, sizes[3], sizes[4])
+        return learner
+
+    def save(self, path):
+        """One checkpoint per member, `path`/member_<p>.npz, in the lone learner's format: its `load` and tools/evaluate.py read them.  Synchronous."""
+        sizes = self._sizes()
+        for p in range(self.n_members):
+            desc = type(self.desc).from_buffer_copy(self.desc)
+            desc.seed = self.seeds[p]
+            save_checkpoint(os.path.join(path, f"member_{p}.npz"), self._prefix, desc, self.p.member(p), (sizes[3], sizes[4]), self._hyper())
+        return path
+
+    @classmethod
+    def load(cls, path, device=0):
+        """The population of the member_<p>.npz under `path` (p = 0, 1, .. without a gap).  ValueError for members of different shapes, hyper-parameters or
+        counters: those are no population."""
+        files = []
+        while os.path.exists(os.path.join(path, f"member_{len(files)}.npz")):
+            files.append(os.path.join(path, f"member_{len(files)}.npz"))
+        if not files:
+            raise ValueError(f"{path}: no member_0.npz")
+        ckpts = [load_checkpoint(f, cls._prefix) for f in files]
+        first = ckpts[0]
+        for f, c in zip(files, ckpts):
+            differs = [k for k in first["desc"] if k != "seed" and not np.array_equal(first["desc"][k], c["desc"][k])]
+            differs += [k for k in first["hyper"] if not np.array_equal(first["hyper"][k], c["hyper"][k], equal_nan=True)]
+            if differs or not np.array_equal(first["counters"], c["counters"]):
+                raise ValueError(f"{f}: {', '.join(differs) or 'counters'} differ from member 0's: the members of a population share them")
+        pop = cls(n_members=len(ckpts), seeds=[int(c["desc"]["seed"]) for c in ckpts], device=device, **cls._checkpoint_kwargs(first["desc"], first["hyper"]))
+        try:
+            for p, c in enumerate(ckpts):
+                restore_tensors(pop.p.member(p), c)
+            pop._restore(*(int(x) for x in first["counters"]))
+        except Exception:
+            pop.close()
+            raise
+        return pop
+
+    def state_dict(self):
+        raise NotImplementedError("state_dict of a population: member(p).state_dict()")
+
+    def load_state_dict(self, state):
+        raise NotImplementedError("load_state_dict of a population: load the member's checkpoint")
 
 
 class Learner(DeviceHandle):

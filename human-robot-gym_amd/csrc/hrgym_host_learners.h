@@ -178,11 +178,12 @@ int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next
 struct hrg_ppo {
   int device = 0;
   hrg_ppo_desc desc;
+  int32_t n_members = 1;        // a population's members (csrc/hrgym_ppo.h); the lone learner is the population of one
   PpoDev d;
   uint64_t steps = 0;           // minibatch steps so far: Adam's step count
   uint64_t forward_calls = 0;   // forward calls that drew their noise
   int n_blocks = 0;             // blocks of 256 parameters
-  DeviceMem mem;                // one allocation behind every float pointer of `d`, one behind every double pointer
+  DeviceMem mem;                // one allocation behind every float pointer of `d`, one behind every double pointer, the seeds table
 };
 
 // the offsets of the parameter layout (csrc/hrgym_ppo.h) into d; returns the number of parameters
@@ -201,9 +202,12 @@ static int32_t ppo_layout(const hrg_ppo_desc& c, PpoDev& d) {
   return o;
 }
 
-int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
+int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_ppo** out) {
   if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
   *out = nullptr;
+  if (n_members < 1 || n_members > HRG_PPO_MAX_POPULATION)
+    return fail(HRG_ERR_UNSUPPORTED, "ppo: n_members = " + std::to_string(n_members) + " outside 1 .. " + std::to_string(HRG_PPO_MAX_POPULATION));
+  if (!seeds) return fail(HRG_ERR_INVALID, "ppo: a population needs its seeds table (n_members values)");
   if (desc->use_sde) return fail(HRG_ERR_UNSUPPORTED, "ppo: use_sde: state dependent exploration is not covered");
   if (desc->target_kl_set) return fail(HRG_ERR_UNSUPPORTED, "ppo: target_kl: the early stop needs a host readback per minibatch");
   if (desc->policy != HRG_PPO_MLP_POLICY) return fail(HRG_ERR_UNSUPPORTED, "ppo: policy = " + std::to_string(desc->policy) + ": the kernels cover MlpPolicy");
@@ -219,28 +223,34 @@ int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
   std::unique_ptr<hrg_ppo> h(new hrg_ppo());
   h->device = device;
   h->desc = *desc;
+  h->n_members = n_members;
   PpoDev& d = h->d;
   d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_PPO_TILE;
   d.nets = desc->separate ? 2 : 1;
   d.normalize = desc->normalize_advantage ? 1 : 0;
-  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm; d.seed = desc->seed;
-  const size_t P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;
+  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm;
+  const size_t M = (size_t)n_members, P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;   // (the pieces: ppo_member)
   h->n_blocks = (int)((P + MLP_BLOCK - 1) / MLP_BLOCK);
   Carver<float> f;
-  f.take(d.values, B);
-  f.take(d.logp, B);
-  f.take(d.ratio, B);
-  f.take(d.part, (size_t)d.tiles * P);
-  f.take(d.grad, P);
-  f.take(d.loss_part, (size_t)d.tiles * PPO_NPART);
-  f.take(d.diag, HRG_PPO_NDIAG);
+  f.take(d.all.values, M * B);
+  f.take(d.all.logp, M * B);
+  f.take(d.all.ratio, M * B);
+  f.take(d.all.part, M * (size_t)d.tiles * P);
+  f.take(d.all.grad, M * P);
+  f.take(d.all.loss_part, M * (size_t)d.tiles * PPO_NPART);
+  f.take(d.all.diag, M * HRG_PPO_NDIAG);
   Carver<double> dbl;
-  dbl.take(d.adv_stat, 2);
-  dbl.take(d.block_sq, (size_t)h->n_blocks);
-  if (!f.alloc(h->mem) || !dbl.alloc(h->mem)) return nomem("ppo", h->mem);
+  dbl.take(d.all.adv_stat, M * 2);
+  dbl.take(d.all.block_sq, M * (size_t)h->n_blocks);
+  if (!f.alloc(h->mem) || !dbl.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M)) return nomem("ppo", h->mem);
   HIPCHK(hipDeviceSynchronize());
   *out = h.release();
   return HRG_OK;
+}
+
+int hrg_ppo_create(const hrg_ppo_desc* desc, int32_t device, hrg_ppo** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  return hrg_ppo_population_create(desc, 1, &desc->seed, device, out);
 }
 
 void hrg_ppo_destroy(hrg_ppo* h) { destroy_handle(h); }
@@ -256,6 +266,7 @@ int hrg_ppo_sizes(hrg_ppo* h, int64_t* size_host) {
   return HRG_OK;
 }
 
+// (a population's step: every array [n_members] times the lone learner's, member p's part at p times its size)
 int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions_dev, const float* old_values_dev, const float* old_log_prob_dev,
                  const float* advantages_dev, const float* returns_dev, float* params_dev, float* adam_m_dev, float* adam_v_dev, double learning_rate, double clip_range,
                  double clip_range_vf, void* stream) {
@@ -267,11 +278,12 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
   HIPCHK(hipSetDevice(h->device));
   const PpoDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks);
+  const unsigned members = (unsigned)h->n_members;
+  const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks, 1, members);
   double bc1, bc2;
   adam_bias_corrections(h->steps, bc1, bc2);   // by the optimiser's step count
-  if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1), block, 0, st, d, advantages_dev);
-  hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
+  if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1, 1, members), block, 0, st, d, advantages_dev);
+  hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets, members), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
                      old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
   hipLaunchKernelGGL(hrg_ppo_reduce_kernel, flat, block, 0, st, d);
   hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, learning_rate, bc1, bc2);
@@ -280,26 +292,39 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
   return HRG_OK;
 }
 
-int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
-                    float* values_dev, float* log_probs_dev, void* stream) {
+int hrg_ppo_population_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                               float* values_dev, float* log_probs_dev, void* stream) {
   if (!h || !params_dev || !obs_dev || !values_dev) return fail(HRG_ERR_INVALID, "null argument");
   if (actions_dev && !log_probs_dev) return fail(HRG_ERR_INVALID, "ppo: actions without log_probs");
-  if (n < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
+  if (n_group < 1) return fail(HRG_ERR_INVALID, "ppo: n must be positive");
   HIPCHK(hipSetDevice(h->device));
   const int value_only = actions_dev ? 0 : 1;
-  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T, value_only ? 1u : (unsigned)h->d.nets), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d,
-                     params_dev, obs_dev, (int)n, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev, log_probs_dev);
+  hipLaunchKernelGGL(hrg_ppo_forward_kernel, dim3(((unsigned)n_group + MLP_T - 1) / MLP_T, value_only ? 1u : (unsigned)h->d.nets, (unsigned)h->n_members), dim3(MLP_BLOCK), 0,
+                     (hipStream_t)stream, h->d, params_dev, obs_dev, (int)n_group, eps_dev, (int)(deterministic != 0), h->forward_calls, value_only, actions_dev, values_dev,
+                     log_probs_dev);
   HIPCHK(hipGetLastError());
   if (!value_only && !deterministic && !eps_dev) h->forward_calls++;
   return HRG_OK;
 }
 
-int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
+int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
+                    float* values_dev, float* log_probs_dev, void* stream) {
+  if (h && h->n_members != 1)
+    return fail(HRG_ERR_INVALID, "ppo: a population of " + std::to_string(h->n_members) + " goes forward through hrg_ppo_population_forward (a group of rows per member)");
+  return hrg_ppo_population_forward(h, params_dev, obs_dev, n, eps_dev, deterministic, actions_dev, values_dev, log_probs_dev, stream);
+}
+
+int hrg_ppo_population_export(hrg_ppo* h, int32_t member, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
   if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  if (member < 0 || member >= h->n_members) return fail(HRG_ERR_INVALID, "ppo: member = " + std::to_string(member) + " outside the " + std::to_string(h->n_members) + " members");
   const PpoDev& d = h->d;
-  const size_t B = (size_t)d.B;
-  return export_floats(h->device, {{values_host, d.values, B}, {log_prob_host, d.logp, B}, {ratio_host, d.ratio, B}, {grad_host, d.grad, (size_t)d.n_params},
-                                   {diag_host, d.diag, HRG_PPO_NDIAG}});
+  const size_t m = (size_t)member, B = (size_t)d.B, P = (size_t)d.n_params;   // (the pieces: ppo_member)
+  return export_floats(h->device, {{values_host, d.all.values + m * B, B}, {log_prob_host, d.all.logp + m * B, B}, {ratio_host, d.all.ratio + m * B, B},
+                                   {grad_host, d.all.grad + m * P, P}, {diag_host, d.all.diag + m * HRG_PPO_NDIAG, HRG_PPO_NDIAG}});
+}
+
+int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {
+  return hrg_ppo_population_export(h, 0, values_host, log_prob_host, ratio_host, grad_host, diag_host);
 }
 
 int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls) {

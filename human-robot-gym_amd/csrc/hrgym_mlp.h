@@ -180,6 +180,12 @@ DI void mlp_noise(MlpLds& s, const float* __restrict__ eps_in, int A, int row0, 
   }
 }
 
+// member p's part of an array of `stride` values per member (a population: hrgym_sac.h, hrgym_ppo.h).  mlp_rows_or_null: of an array that may be absent, null
+// stays null -- at the price of a select, behind which the compiler no longer sees that the pointer is the kernel's read-only argument and loads what is uniform
+// over the wave through the vector path; mlp_rows is for the arrays that are always there.
+template <class T> DI T* mlp_rows(T* x, int p, size_t stride) { return x + (size_t)p * stride; }
+template <class T> DI T* mlp_rows_or_null(T* x, int p, size_t stride) { return x ? x + (size_t)p * stride : x; }
+
 // torch's Adam on parameter i with the gradient g (betas 0.9, 0.999, no weight decay; bias corrections bc1, bc2 = 1 - beta^t from the host), in double, rounded
 // once into the float32 parameter, which it returns
 DI float mlp_adam(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int i, double g, double lr, double bc1, double bc2, double eps) {

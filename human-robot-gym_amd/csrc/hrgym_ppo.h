@@ -31,17 +31,19 @@
 //   log_std : [A]
 //
 // Draws of the forward pass: rng_gauss keyed by (learner seed, forward call count, row, STREAM_PPO_ACT, component); none depends on the grid.
+//
+// A population is n_members learners of one descriptor that differ in their seed and step in the same four launches: blockIdx.z = p is the member.
+// Parameters and moments are [P][n_params], the batch arrays [P][B][.], every piece of the handle's scratch has a member stride (ppo_member), the seeds are a [P]
+// table.  The counters are the handle's: members step in lockstep.  A member's advantage statistics, clip coefficient and diagnostics come from its own sums, its
+// draws are keyed by its own seed and the row's index in its group of rows: member p is, bit for bit, the lone learner of seed p on batch p.  The lone learner is
+// the population of one member.
 #pragma once
 
 enum { STREAM_PPO_ACT = 14 };   // after STREAM_SAC_ACT = 13 (hrgym_sac.h)
 #define PPO_NPART 6   // per tile: sum of -min(.,.), of (ratio - 1) - log ratio, of [|ratio - 1| > c], of (return - vpred)^2; a row's entropy; mean_j exp(log_std_j)
 
-// one hrg_ppo: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
-struct PpoDev {
-  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, nets = 0, normalize = 0;
-  int32_t w[2][HRG_PPO_MAX_DEPTH] = {{0}}, b[2][HRG_PPO_MAX_DEPTH] = {{0}}, hw = 0, hb = 0, ls = 0;   // the networks' layers; the heads' [A + 1][64] weights and [A + 1] biases; log_std
-  float ent_coef = 0.0f, vf_coef = 0.0f, max_grad_norm = 0.0f;
-  uint64_t seed = 0;
+// a member's pieces of the scratch the handle owns
+struct PpoScratch {
   float* values = nullptr;     // [B]
   float* logp = nullptr;       // [B]
   float* ratio = nullptr;      // [B]
@@ -52,6 +54,32 @@ struct PpoDev {
   double* adv_stat = nullptr;  // [2] mean, std of the minibatch's advantages
   double* block_sq = nullptr;  // [ceil(n_params / 256)]
 };
+
+// one hrg_ppo: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
+struct PpoDev {
+  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, nets = 0, normalize = 0;
+  int32_t w[2][HRG_PPO_MAX_DEPTH] = {{0}}, b[2][HRG_PPO_MAX_DEPTH] = {{0}}, hw = 0, hb = 0, ls = 0;   // the networks' layers; the heads' [A + 1][64] weights and [A + 1] biases; log_std
+  float ent_coef = 0.0f, vf_coef = 0.0f, max_grad_norm = 0.0f;
+  const uint64_t* seeds = nullptr;   // [P] the members' seeds
+  PpoScratch all;                    // the scratch of every member, [P] pieces of each array: member 0's pointers
+};
+
+// member p's pieces of the scratch.  The kernels move the arrays they are passed themselves (mlp_rows).  (A copy of the pointers alone: a copy of the whole
+// handle, whose offset tables the kernels index by the network, would live in scratch memory.)
+DI PpoScratch ppo_member(const PpoDev& h, int p) {
+  const size_t i = (size_t)p, B = (size_t)h.B, n = (size_t)h.n_params, tiles = (size_t)h.tiles;
+  PpoScratch m = h.all;
+  m.values += i * B;
+  m.logp += i * B;
+  m.ratio += i * B;
+  m.part += i * tiles * n;
+  m.grad += i * n;
+  m.loss_part += i * tiles * PPO_NPART;
+  m.diag += i * HRG_PPO_NDIAG;
+  m.adv_stat += i * 2;
+  m.block_sq += i * ((n + MLP_BLOCK - 1) / MLP_BLOCK);
+  return m;
+}
 
 // which outputs of the heads a workgroup computes: the first row of the [A + 1][64] product, the number of rows, the column of the value in s.D
 struct PpoHead {
@@ -83,10 +111,12 @@ DI double ppo_block_sum(double* red, double mine) {
   return out;
 }
 
-// ---- 1: mean and unbiased standard deviation of the minibatch's advantages
+// ---- 1: mean and unbiased standard deviation of the minibatch's advantages.  Grid (1, 1, members).
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, const float* __restrict__ adv) {
   __shared__ double red[MLP_BLOCK + 1];
-  const int t = (int)threadIdx.x;
+  const int t = (int)threadIdx.x, p = (int)blockIdx.z;
+  const PpoScratch m = ppo_member(h, p);
+  adv = mlp_rows(adv, p, (size_t)h.B);
   double sum = 0.0;
   for (int i = t; i < h.B; i += MLP_BLOCK) sum += (double)adv[i];
   const double mean = ppo_block_sum(red, sum) / (double)h.B;
@@ -94,21 +124,25 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, 
   for (int i = t; i < h.B; i += MLP_BLOCK) sq += ((double)adv[i] - mean) * ((double)adv[i] - mean);
   const double var = ppo_block_sum(red, sq) / (double)(h.B - 1);
   if (t == 0) {
-    h.adv_stat[0] = mean;
-    h.adv_stat[1] = sqrt(var);
+    m.adv_stat[0] = mean;
+    m.adv_stat[1] = sqrt(var);
   }
 }
 
-// ---- 2: network blockIdx.y on the tile: forward, the rows' losses and their gradients at the heads, backward
+// ---- 2: network blockIdx.y of member blockIdx.z on the tile: forward, the rows' losses and their gradients at the heads, backward
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act,
                                                                  const float* __restrict__ old_values, const float* __restrict__ old_logp, const float* __restrict__ adv,
                                                                  const float* __restrict__ returns, double clip_range, double clip_range_vf) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, net = (int)blockIdx.y, K = h.K, A = h.A, t = (int)threadIdx.x;
+  const int row0 = (int)blockIdx.x * MLP_T, net = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
+  const PpoScratch m = ppo_member(h, p);
+  const size_t B = (size_t)h.B;
+  P = mlp_rows(P, p, (size_t)h.n_params); obs = mlp_rows(obs, p, B * K); act = mlp_rows(act, p, B * A);
+  old_values = mlp_rows(old_values, p, B); old_logp = mlp_rows(old_logp, p, B); adv = mlp_rows(adv, p, B); returns = mlp_rows(returns, p, B);
   const PpoHead hd = ppo_head(h, net, false);
   const int hw = h.hw + hd.first * MLP_H, hb = h.hb + hd.first;
-  float* part = h.part + (size_t)blockIdx.x * h.n_params;
+  float* part = m.part + (size_t)blockIdx.x * h.n_params;
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_trunk(s, P, h.w[net], h.b[net], h.depth, K, MLP_ACT_TANH);
   mlp_head(s, P, hw, hb, h.depth, hd.nout);
@@ -120,7 +154,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
       const double dv = (double)v - (double)ov;
       const bool clip = clip_range_vf >= 0.0, pass = !clip || (dv >= -clip_range_vf && dv <= clip_range_vf);
       const double vp = clip ? (double)ov + fmin(fmax(dv, -clip_range_vf), clip_range_vf) : (double)v, d = vp - (double)returns[i];
-      h.values[i] = v;
+      m.values[i] = v;
       s.row[3][r] = (float)(d * d);
       s.D[r * MLP_DLD + hd.vcol] = pass ? (float)((double)h.vf_coef * 2.0 * d * inv_b) : 0.0f;
     }
@@ -131,7 +165,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
         lp += -0.5 * d * d * exp(-2.0 * ls) - ls - MLP_HALF_LOG_2PI;
       }
       const double log_ratio = lp - (double)old_logp[i], ratio = exp(log_ratio), c = clip_range;
-      const double a = h.normalize ? ((double)adv[i] - h.adv_stat[0]) / (h.adv_stat[1] + 1e-8) : (double)adv[i];
+      const double a = h.normalize ? ((double)adv[i] - m.adv_stat[0]) / (m.adv_stat[1] + 1e-8) : (double)adv[i];
       const bool inside = ratio >= 1.0 - c && ratio <= 1.0 + c;
       const double s1 = a * ratio, s2 = a * fmin(fmax(ratio, 1.0 - c), 1.0 + c);
       const double g = (inside || s1 < s2) ? -a * ratio * inv_b : 0.0;   // d loss / d log_prob
@@ -140,8 +174,8 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
         s.D[r * MLP_DLD + j] = (float)(g * d * iv);                                          // ... / d mu_j
         s.std[r * 8 + j] = (float)(g * (d * d * iv - 1.0) - (double)h.ent_coef * inv_b);     // ... / d log_std_j, with the entropy bonus's share of the row
       }
-      h.logp[i] = (float)lp;
-      h.ratio[i] = (float)ratio;
+      m.logp[i] = (float)lp;
+      m.ratio[i] = (float)ratio;
       s.row[0][r] = (float)(-fmin(s1, s2));
       s.row[1][r] = (float)((ratio - 1.0) - log_ratio);
       s.row[2][r] = fabs(ratio - 1.0) > c ? 1.0f : 0.0f;
@@ -149,7 +183,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
   }
   __syncthreads();
   if (t == 0) {
-    float* lpart = h.loss_part + (size_t)blockIdx.x * PPO_NPART;
+    float* lpart = m.loss_part + (size_t)blockIdx.x * PPO_NPART;
     for (int k = hd.pol ? 0 : 3; k < (hd.val ? 4 : 3); k++) {
       double sum = 0.0;
       for (int r = 0; r < MLP_T; r++) sum += (double)s.row[k][r];
@@ -173,16 +207,17 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
   mlp_backward(s, P, h.w[net], h.b[net], hw, hb, h.depth, K, hd.nout, part, true, 0, MLP_ACT_TANH);
 }
 
-// ---- 3: the gradient (the tiles' parts in tile order) and each block's squared norm (a fixed tree over the block's 256 entries)
+// ---- 3: the gradient (the tiles' parts in tile order) and each block's squared norm (a fixed tree over the block's 256 entries).  Grid (blocks, 1, members).
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev h) {
   __shared__ double red[MLP_BLOCK];
   const int t = (int)threadIdx.x, i = (int)(blockIdx.x * blockDim.x) + t;
+  const PpoScratch m = ppo_member(h, (int)blockIdx.z);
   float g = 0.0f;
   if (i < h.n_params) {
     double sum = 0.0;
-    for (int tl = 0; tl < h.tiles; tl++) sum += (double)h.part[(size_t)tl * h.n_params + i];
+    for (int tl = 0; tl < h.tiles; tl++) sum += (double)m.part[(size_t)tl * h.n_params + i];
     g = (float)sum;
-    h.grad[i] = g;
+    m.grad[i] = g;
   }
   red[t] = (double)g * (double)g;
   __syncthreads();
@@ -190,18 +225,21 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev 
     if (t < w) red[t] += red[t + w];
     __syncthreads();
   }
-  if (t == 0) h.block_sq[blockIdx.x] = red[0];
+  if (t == 0) m.block_sq[blockIdx.x] = red[0];
 }
 
-// ---- 4: clip_grad_norm_ over all parameters, torch's Adam (eps 1e-5) in double, rounded once into the float32 parameter; thread 0 of block 0: the diagnostics
+// ---- 4: clip_grad_norm_ over all parameters, torch's Adam (eps 1e-5) in double, rounded once into the float32 parameter; thread 0 of block 0: the diagnostics.
+// Grid (blocks, 1, members): the norm, the coefficient and the tail are the member's own.
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int n_blocks, double lr,
                                                                  double bc1, double bc2) {
-  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), p = (int)blockIdx.z;
+  const PpoScratch own = ppo_member(h, p);   // (`m` is Adam's first moment below)
+  P = mlp_rows(P, p, (size_t)h.n_params); M = mlp_rows(M, p, (size_t)h.n_params); V = mlp_rows(V, p, (size_t)h.n_params);
   double sq = 0.0;
-  for (int b = 0; b < n_blocks; b++) sq += h.block_sq[b];
+  for (int b = 0; b < n_blocks; b++) sq += own.block_sq[b];
   const double norm = sqrt(sq), coef = fmin(1.0, (double)h.max_grad_norm / (norm + 1e-6));
   if (i < h.n_params) {   // (mlp_adam's update written out: through the helper the compiler contracts v's products the other way round, a different rounding)
-    const double gd = (double)h.grad[i] * coef, m = 0.9 * (double)M[i] + 0.1 * gd, v = 0.999 * (double)V[i] + 0.001 * gd * gd;
+    const double gd = (double)own.grad[i] * coef, m = 0.9 * (double)M[i] + 0.1 * gd, v = 0.999 * (double)V[i] + 0.001 * gd * gd;
     P[i] = (float)((double)P[i] - lr * (m / bc1) / (sqrt(v / bc2) + 1e-5));
     M[i] = (float)m;
     V[i] = (float)v;
@@ -209,34 +247,37 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h,
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
     for (int tl = 0; tl < h.tiles; tl++)
-      for (int k = 0; k < 4; k++) sum[k] += (double)h.loss_part[(size_t)tl * PPO_NPART + k];
-    const double inv_b = 1.0 / (double)h.B, pl = sum[0] * inv_b, vl = sum[3] * inv_b, el = -(double)h.loss_part[4];
-    h.diag[0] = (float)pl;                                                  // policy_gradient_loss
-    h.diag[1] = (float)vl;                                                  // value_loss
-    h.diag[2] = (float)el;                                                  // entropy_loss
-    h.diag[3] = (float)(pl + (double)h.ent_coef * el + (double)h.vf_coef * vl);   // loss
-    h.diag[4] = (float)(sum[1] * inv_b);                                    // approx_kl
-    h.diag[5] = (float)(sum[2] * inv_b);                                    // clip_fraction
-    h.diag[6] = h.loss_part[5];                                             // std
-    h.diag[7] = (float)norm;                                                // the gradient norm before clipping
+      for (int k = 0; k < 4; k++) sum[k] += (double)own.loss_part[(size_t)tl * PPO_NPART + k];
+    const double inv_b = 1.0 / (double)h.B, pl = sum[0] * inv_b, vl = sum[3] * inv_b, el = -(double)own.loss_part[4];
+    own.diag[0] = (float)pl;                                                  // policy_gradient_loss
+    own.diag[1] = (float)vl;                                                  // value_loss
+    own.diag[2] = (float)el;                                                  // entropy_loss
+    own.diag[3] = (float)(pl + (double)h.ent_coef * el + (double)h.vf_coef * vl);   // loss
+    own.diag[4] = (float)(sum[1] * inv_b);                                    // approx_kl
+    own.diag[5] = (float)(sum[2] * inv_b);                                    // clip_fraction
+    own.diag[6] = own.loss_part[5];                                             // std
+    own.diag[7] = (float)norm;                                                // the gradient norm before clipping
   }
 }
 
-// ---- the forward pass on any number of rows, a tile of rows per workgroup.  value_only = 0, grid (tiles, networks): actions = mu + exp(log_std) eps (not clipped;
-// deterministic: mu), their log_prob, and the values.  value_only = 1, grid (tiles): the values.
+// ---- the forward pass on any number of rows, a tile of rows per workgroup.  value_only = 0, grid (tiles, networks, members): actions = mu + exp(log_std) eps (not
+// clipped; deterministic: mu), their log_prob, and the values.  value_only = 1, grid (tiles, 1, members): the values.  obs, eps_in and the outputs are [P][n][.],
+// member blockIdx.z's networks on its group of n rows.  The tile's bound is the end of the group, and a draw's key the row's index in the group.
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_forward_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, int n,
                                                                     const float* __restrict__ eps_in, int deterministic, uint64_t call, int value_only,
                                                                     float* __restrict__ actions, float* __restrict__ values, float* __restrict__ logp) {
   __shared__ MlpLds s;
-  const int row0 = (int)blockIdx.x * MLP_T, net = value_only ? h.nets - 1 : (int)blockIdx.y, K = h.K, A = h.A;
+  const int row0 = (int)blockIdx.x * MLP_T, net = value_only ? h.nets - 1 : (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A;
   if (row0 >= n) return;
+  P = mlp_rows(P, p, (size_t)h.n_params); obs = mlp_rows(obs, p, (size_t)n * K); eps_in = mlp_rows_or_null(eps_in, p, (size_t)n * A);
+  actions = mlp_rows_or_null(actions, p, (size_t)n * A); values = mlp_rows(values, p, (size_t)n); logp = mlp_rows_or_null(logp, p, (size_t)n);
   const PpoHead hd = ppo_head(h, net, value_only != 0);
   mlp_load(s, obs, K, 0, row0, n);
   if (hd.pol) {
     if (deterministic) {
       for (int i = (int)threadIdx.x; i < MLP_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;
     } else {
-      mlp_noise(s, eps_in, A, row0, n, h.seed, call, STREAM_PPO_ACT, 0);
+      mlp_noise(s, eps_in, A, row0, n, h.seeds[p], call, STREAM_PPO_ACT, 0);
     }
   }
   mlp_trunk(s, P, h.w[net], h.b[net], h.depth, K, MLP_ACT_TANH);

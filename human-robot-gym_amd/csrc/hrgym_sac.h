@@ -65,7 +65,7 @@ struct SacDev {
   SacScratch all;                    // the scratch of every member, [P] pieces of each array: member 0's pointers (`seed` is not used)
 };
 
-// member p's seed and pieces of the scratch.  The kernels move the arrays they are passed themselves (sac_rows).  (A copy of the pointers alone: a copy of the
+// member p's seed and pieces of the scratch.  The kernels move the arrays they are passed themselves (mlp_rows_or_null).  (A copy of the pointers alone: a copy of the
 // whole handle, whose offset tables the kernels index by the critic, would live in scratch memory.)
 DI SacScratch sac_member(const SacDev& h, int p) {
   const size_t i = (size_t)p, B = (size_t)h.B, A = (size_t)h.A, n = (size_t)h.n_params, tiles = (size_t)h.tiles;
@@ -83,9 +83,6 @@ DI SacScratch sac_member(const SacDev& h, int p) {
   m.losses += i * 4;
   return m;
 }
-
-// member p's part of an array of `stride` values per member; null stays null
-template <class T> DI T* sac_rows(T* x, int p, size_t stride) { return x ? x + (size_t)p * stride : x; }
 
 // [UPSTREAM] SquashedDiagGaussianDistribution: s.D [.][0 .. A) = mu, [A .. 2A) = the log_std head (kept: the clamp's gradient reads it); s.eps -> s.act = tanh(u),
 // s.std = exp(clamp(log_std, -20, 2)), s.row[0] = logp, in double and rounded once.  One thread per row, components ascending.  The caller places the barriers.
@@ -115,9 +112,9 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev 
   if (row0 >= h.B) return;   // (uniform over the workgroup)
   const SacScratch m = sac_member(h, p);
   const size_t B = (size_t)h.B;
-  P = sac_rows(P, p, (size_t)h.n_params); PT = sac_rows(PT, p, 2 * (size_t)h.n_critic);
-  obs = sac_rows(obs, p, B * K); nobs = sac_rows(nobs, p, B * K); dones = sac_rows(dones, p, B); rewards = sac_rows(rewards, p, B);
-  eps_pi = sac_rows(eps_pi, p, B * A); eps_next = sac_rows(eps_next, p, B * A);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); PT = mlp_rows_or_null(PT, p, 2 * (size_t)h.n_critic);
+  obs = mlp_rows_or_null(obs, p, B * K); nobs = mlp_rows_or_null(nobs, p, B * K); dones = mlp_rows_or_null(dones, p, B); rewards = mlp_rows_or_null(rewards, p, B);
+  eps_pi = mlp_rows_or_null(eps_pi, p, B * A); eps_next = mlp_rows_or_null(eps_next, p, B * A);
   mlp_load(s, next ? nobs : obs, K, 0, row0, h.B);
   mlp_noise(s, next ? eps_next : eps_pi, A, row0, h.B, m.seed, count, STREAM_SAC, next ? HRG_ACT_DIM : 0);
   mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_critic_kernel(const SacDev 
   const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
   const SacScratch m = sac_member(h, p);
-  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K); act = sac_rows(act, p, (size_t)h.B * A);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); obs = mlp_rows_or_null(obs, p, (size_t)h.B * K); act = mlp_rows_or_null(act, p, (size_t)h.B * A);
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_load(s, act, A, K, row0, h.B);
   mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_q_kernel(const SacDev
   const int row0 = (int)blockIdx.x * MLP_T, c = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
   const SacScratch m = sac_member(h, p);
-  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); obs = mlp_rows_or_null(obs, p, (size_t)h.B * K);
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_load(s, m.a_pi, A, K, row0, h.B);
   mlp_trunk(s, P, h.q_w[c], h.q_b[c], h.depth, K + A, MLP_ACT_RELU);
@@ -204,7 +201,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h
   const int row0 = (int)blockIdx.x * MLP_T, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
   const SacScratch m = sac_member(h, p);
-  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)h.B * K); eps_pi = sac_rows(eps_pi, p, (size_t)h.B * A);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); obs = mlp_rows_or_null(obs, p, (size_t)h.B * K); eps_pi = mlp_rows_or_null(eps_pi, p, (size_t)h.B * A);
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_noise(s, eps_pi, A, row0, h.B, m.seed, count, STREAM_SAC, 0);
   mlp_trunk(s, P, h.a_w, h.a_b, h.depth, K, MLP_ACT_RELU);
@@ -243,8 +240,8 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h,
                                                                  double bc1, double bc2, float* __restrict__ target, double tau, int coef) {
   const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x), p = (int)blockIdx.z;
   const SacScratch m = sac_member(h, p);
-  P = sac_rows(P, p, (size_t)h.n_params); M = sac_rows(M, p, (size_t)h.n_params); V = sac_rows(V, p, (size_t)h.n_params);
-  target = sac_rows(target, p, 2 * (size_t)h.n_critic);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); M = mlp_rows_or_null(M, p, (size_t)h.n_params); V = mlp_rows_or_null(V, p, (size_t)h.n_params);
+  target = mlp_rows_or_null(target, p, 2 * (size_t)h.n_critic);
   if (i < hi) {
     float g = m.part[i];
     for (int tl = 1; tl < h.tiles; tl++) g += m.part[(size_t)tl * h.n_params + i];
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_act_kernel(const SacDev h, 
   __shared__ MlpLds s;
   const int row0 = (int)blockIdx.x * MLP_T, p = (int)blockIdx.y, K = h.K, A = h.A;
   if (row0 >= n) return;
-  P = sac_rows(P, p, (size_t)h.n_params); obs = sac_rows(obs, p, (size_t)n * K); eps_in = sac_rows(eps_in, p, (size_t)n * A); out = sac_rows(out, p, (size_t)n * A);
+  P = mlp_rows_or_null(P, p, (size_t)h.n_params); obs = mlp_rows_or_null(obs, p, (size_t)n * K); eps_in = mlp_rows_or_null(eps_in, p, (size_t)n * A); out = mlp_rows_or_null(out, p, (size_t)n * A);
   mlp_load(s, obs, K, 0, row0, n);
   if (deterministic) {
     for (int i = (int)threadIdx.x; i < MLP_T * 8; i += (int)blockDim.x) s.eps[i] = 0.0f;

@@ -11,13 +11,20 @@ and Adam moments are flat float32 torch tensors; `state_dict()` hands out views 
     env.collect_rollout(learner.policy, learner.value)   # the learner supplies both callables
     learner.train(env.rollout)                           # n_epochs x (rollout.get(batch_size) -> step): no host copy, no synchronisation
     learner.diagnostics()                                # SB3's train/ keys of the last minibatch (synchronous)
+
+The seeds of one cell of a study train side by side as a population (PpoPopulation): one set of launches per minibatch step for all of them.
+
+    pop = env.attach_ppo_population(5, batch_size=64, n_epochs=20)   # 5 groups of num_envs / 5 envs; seeds: the env's seed + p
+    env.collect_rollout(pop.policy, pop.value)
+    pop.train(env.rollout)                                            # n_epochs x (rollout.get_groups(5, batch_size, pop.seeds) -> step)
 """
+import ctypes
 import math
 
 import numpy as np
 
 from ._cstruct import CONST, PpoDesc
-from ._learner import Learner, LearnerParams, build_layout, check_widths, mlp_entries
+from ._learner import MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_PPO_HIDDEN"]
@@ -135,6 +142,7 @@ class PpoLearner(Learner):
     on the learner's device; `step`, `train`, `policy` and `value` are asynchronous, ordered on torch's current stream; `diagnostics` and `export` synchronise."""
 
     _prefix = "hrg_ppo"
+    n_members = 1   # (PpoPopulation: more)
 
     def __init__(self, obs_dim, act_dim, net_arch=None, learning_rate=3e-4, batch_size=64, n_epochs=10, clip_range=0.2, clip_range_vf=None, normalize_advantage=True,
                  ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, use_sde=False, target_kl=None, policy="MlpPolicy", log_std_init=0.0, ortho_init=True, rollout_size=0,
@@ -146,34 +154,47 @@ class PpoLearner(Learner):
             raise ValueError(f"n_epochs = {n_epochs} must be positive")
         desc = build_ppo_desc(obs_dim, act_dim, net_arch=net_arch, batch_size=batch_size, rollout_size=rollout_size, normalize_advantage=normalize_advantage,
                               ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm, use_sde=use_sde, target_kl=target_kl, policy=policy, seed=seed)
-        self._open(desc, device)
+        self._kwargs = dict(net_arch=net_arch, batch_size=batch_size, normalize_advantage=normalize_advantage, ent_coef=ent_coef, vf_coef=vf_coef,
+                            max_grad_norm=max_grad_norm, rollout_size=rollout_size, log_std_init=log_std_init, ortho_init=ortho_init)   # (a population's member())
+        self._open_handle(desc, device)
         self.obs_dim, self.act_dim, self.depth, self.separate = int(obs_dim), int(act_dim), int(desc.depth), bool(desc.separate)
         self.batch_size, self.n_epochs = int(batch_size), int(n_epochs)
         self.learning_rate, self.clip_range = float(learning_rate), float(clip_range)
         self.clip_range_vf = None if clip_range_vf is None else float(clip_range_vf)
-        self.p = PpoParams(obs_dim, act_dim, self.depth, self.separate, seed=seed, log_std_init=log_std_init, ortho_init=ortho_init, device=self.device)
+        self.p = self._make_params(seed, log_std_init, ortho_init)
         if self._sizes()[0] != self.p.n_params:
-            raise RuntimeError(f"PpoLearner: the library lays out {self._sizes()[0]} parameters, ppo.param_layout {self.p.n_params}: rebuild")
+            raise RuntimeError(f"{type(self).__name__}: the library lays out {self._sizes()[0]} parameters, ppo.param_layout {self.p.n_params}: rebuild")
         self._keep = None
+
+    def _open_handle(self, desc, device):
+        self._open(desc, device)
+
+    def _make_params(self, seed, log_std_init, ortho_init):
+        return PpoParams(self.obs_dim, self.act_dim, self.depth, self.separate, seed=seed, log_std_init=log_std_init, ortho_init=ortho_init, device=self.device)
 
     def _hyper(self):
         return dict(learning_rate=self.learning_rate, clip_range=self.clip_range, clip_range_vf=self.clip_range_vf, n_epochs=self.n_epochs)
 
-    @classmethod
-    def _from_checkpoint(cls, d, hyper, device):
-        """The learner of a checkpoint's descriptor fields `d` and scheduled attributes `hyper` (Learner.load).  log_std_init and ortho_init shape the initial
-        parameters only, which the checkpoint's replace."""
+    @staticmethod
+    def _checkpoint_kwargs(d, hyper):
+        """The constructor's arguments, the seed apart, from a checkpoint's descriptor fields `d` and scheduled attributes `hyper`.  log_std_init and ortho_init
+        shape the initial parameters only, which the checkpoint's replace."""
         layers = [int(d["hidden"])] * int(d["depth"])
         vf = float(hyper["clip_range_vf"])
-        return cls(int(d["obs_dim"]), int(d["act_dim"]), net_arch=[dict(pi=layers, vf=list(layers))] if int(d["separate"]) else layers,
-                   learning_rate=float(hyper["learning_rate"]), batch_size=int(d["batch_size"]), n_epochs=int(hyper["n_epochs"]), clip_range=float(hyper["clip_range"]),
-                   clip_range_vf=None if math.isnan(vf) else vf, normalize_advantage=bool(int(d["normalize_advantage"])), ent_coef=float(d["ent_coef"]),
-                   vf_coef=float(d["vf_coef"]), max_grad_norm=float(d["max_grad_norm"]), rollout_size=int(d["rollout_size"]), seed=int(d["seed"]), device=device)
+        return dict(obs_dim=int(d["obs_dim"]), act_dim=int(d["act_dim"]), net_arch=[dict(pi=layers, vf=list(layers))] if int(d["separate"]) else layers,
+                    learning_rate=float(hyper["learning_rate"]), batch_size=int(d["batch_size"]), n_epochs=int(hyper["n_epochs"]), clip_range=float(hyper["clip_range"]),
+                    clip_range_vf=None if math.isnan(vf) else vf, normalize_advantage=bool(int(d["normalize_advantage"])), ent_coef=float(d["ent_coef"]),
+                    vf_coef=float(d["vf_coef"]), max_grad_norm=float(d["max_grad_norm"]), rollout_size=int(d["rollout_size"]))
+
+    @classmethod
+    def _from_checkpoint(cls, d, hyper, device):
+        """The learner of a checkpoint's descriptor fields `d` and scheduled attributes `hyper` (Learner.load)."""
+        return cls(seed=int(d["seed"]), device=device, **cls._checkpoint_kwargs(d, hyper))
 
     def step(self, batch):
         """One minibatch step on `batch`, a RolloutBufferSamples of `batch_size` rows (observations [B, obs_dim], actions [B, act_dim], old_values,
-        old_log_prob, advantages, returns [B])."""
-        B, K, A, p = self.batch_size, self.obs_dim, self.act_dim, self.p
+        old_log_prob, advantages, returns [B]).  A population takes its members' minibatches one behind the other, [P * B] rows."""
+        B, K, A, p = self.n_members * self.batch_size, self.obs_dim, self.act_dim, self.p
         if self.clip_range_vf is not None and not self.clip_range_vf > 0.0:
             raise ValueError(f"clip_range_vf = {self.clip_range_vf} must be positive (None: no clipping)")
         args = (self._tensor(batch.observations, (B, K), "observations"), self._tensor(batch.actions, (B, A), "actions"), self._tensor(batch.old_values, (B,), "old_values"),
@@ -195,14 +216,17 @@ class PpoLearner(Learner):
                 self.step(batch)
 
     def _forward(self, obs, eps, deterministic, with_actions):
+        """(actions, values, log_probs) on `obs` [n, obs_dim]; a population: [P m, obs_dim], member p's networks on the rows of group p."""
         t = self.torch
         n, o, e = self._rows(obs, eps)
+        if n % self.n_members:
+            raise ValueError(f"forward: {n} rows are not {self.n_members} groups of the same size")
         values =t.empty(n, dtype=t.float32, device=self.device)
         actions = t.empty(n, self.act_dim, dtype=t.float32, device=self.device) if with_actions else None
         log_probs = t.empty(n, dtype=t.float32, device=self.device) if with_actions else None
-        with t.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_ppo_forward(self.h, _ptr(self.p.params), o, n, e, int(bool(deterministic)), _ptr(actions), _ptr(values), _ptr(log_probs),
-                                                            self._stream()))
+        with t.cuda.device(self.device):   # (hrg_ppo_forward is this entry for one member)
+            self._check(self.lib, self.lib.hrg_ppo_population_forward(self.h, _ptr(self.p.params), o, n // self.n_members, e, int(bool(deterministic)), _ptr(actions),
+                                                                       _ptr(values), _ptr(log_probs), self._stream()))
         return actions, values, log_probs
 
     def policy(self, obs, deterministic=False, eps=None):
@@ -215,22 +239,67 @@ class PpoLearner(Learner):
         """ActorCriticPolicy.predict_values on `obs` float32 [n, obs_dim]: float32 [n].  This is the `value_fn` HipVecEnv.collect_rollout takes."""
         return self._forward(obs, None, True, False)[1]
 
-    def export(self):
+    def export(self, **which):
         """The last step's intermediates on the host (synchronous; tests): values, log_prob, ratio [B]; grad [n_params] in the parameters' layout, before
-        clipping (`self.p.group(grad, "trunk")`, ...); diag: dict of DIAG_KEYS."""
+        clipping (`self.p.group(grad, "trunk")`, ...); diag: dict of DIAG_KEYS.  (`which`: PpoPopulation's `member`.)"""
         B = self.batch_size
         values, log_prob, ratio = np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.float32)
         grad, diag = np.zeros(self.p.n_params, np.float32), np.zeros(NDIAG, np.float32)
-        self._export(values, log_prob, ratio, grad, diag)
+        self._export(values, log_prob, ratio, grad, diag, **which)
         return dict(values=values, log_prob=log_prob, ratio=ratio, grad=grad, diag=dict(zip(DIAG_KEYS, (float(x) for x in diag))))
 
-    def diagnostics(self):
+    def diagnostics(self, **which):
         """What SB3 logs under train/ after a call of train(), from the last minibatch: policy_gradient_loss, value_loss, entropy_loss, loss, approx_kl,
         clip_fraction, std, plus grad_norm (before clipping), clip_range, clip_range_vf where set, learning_rate and n_updates.  Synchronous."""
         diag = np.zeros(NDIAG, np.float32)
-        self._export(None, None, None, None, diag)
+        self._export(None, None, None, None, diag, **which)
         out = dict(zip(DIAG_KEYS, (float(x) for x in diag)))
         out.update(clip_range=self.clip_range, learning_rate=self.learning_rate, n_updates=self.n_updates)
         if self.clip_range_vf is not None:
             out["clip_range_vf"] = self.clip_range_vf
         return out
+
+
+class PpoPopulationParams(PopulationParams):
+    """The tensors of a population, on any torch device: `params`, `adam_m`, `adam_v` float32 [P, n_params].  Row p is initialised exactly as
+    PpoParams(seed=seeds[p], ...); `member(p)` is the rows of member p as views."""
+
+    def __init__(self, obs_dim, act_dim, depth, separate, seeds, log_std_init=0.0, ortho_init=True, device="cpu"):
+        super().__init__([PpoParams(obs_dim, act_dim, depth, separate, seed=int(s), log_std_init=log_std_init, ortho_init=ortho_init) for s in seeds], device)
+
+
+class PpoPopulation(Population, PpoLearner):
+    """`n_members` PPO learners of the same shapes and hyper-parameters (PpoLearner's keywords) that differ in their seed only and take their minibatch step
+    in the same four launches (csrc/hrgym_ppo.h): the seeds of one cell of a study, side by side on one GPU.  The batch of n = P m envs is P
+    groups of m consecutive envs; member p acts in, and learns from, group p only.  The counters are shared, and so are learning_rate, clip_range and
+    clip_range_vf: members step in lockstep.  Member p is, bit for bit, PpoLearner(seed=seeds[p]) on the same rows.  `rollout_size`: m * n_steps, a member's
+    share of the buffer.  export(member), diagnostics (a list of P dicts), member(p), save and load (member_<p>.npz): _learner.Population.
+
+        env.attach_rollout(n_steps=64, gamma=0.99, gae_lambda=0.9)
+        pop = env.attach_ppo_population(5, batch_size=64)            # seeds: the env's seed + p
+        env.collect_rollout(pop.policy, pop.value)
+        pop.train(env.rollout)
+        pop.diagnostics()                                            # a list of 5 dicts
+    """
+    _lone = PpoLearner
+
+    def __init__(self, obs_dim, act_dim, n_members, seeds, device=0, **kwargs):
+        self.n_members, self._table = check_seeds(n_members, seeds)
+        self.seeds = [int(s) for s in self._table]
+        if "seed" in kwargs:
+            raise TypeError("PpoPopulation: the members' seeds are `seeds` (one per member), not `seed`")
+        super().__init__(obs_dim, act_dim, seed=self.seeds[0], device=device, **kwargs)   # (the entry reads the table, not the descriptor's seed)
+
+    def _open_handle(self, desc, device):
+        self._open(desc, device, self.n_members, self._table.ctypes.data_as(ctypes.c_void_p), create="_population_create")
+
+    def _make_params(self, seed, log_std_init, ortho_init):
+        return PpoPopulationParams(self.obs_dim, self.act_dim, self.depth, self.separate, self.seeds, log_std_init=log_std_init, ortho_init=ortho_init, device=self.device)
+
+    def train(self, rollout):
+        """PPO.train of every member: `n_epochs` x (rollout.get_groups(n_members, batch_size, seeds) -> step), with no copy to the host and no
+        synchronisation.  `rollout`: a rollout.RolloutBuffer over n_members groups of envs; batch_size must divide a group's m * n_steps rows."""
+        self._check_buffer(rollout.obs_dim, rollout.act_dim)
+        for _ in range(self.n_epochs):
+            for batch in rollout.get_groups(self.n_members, self.batch_size, self.seeds):
+                self.step(batch)

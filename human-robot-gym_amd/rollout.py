@@ -44,6 +44,31 @@ def build_rollout_desc(n_envs, n_steps, obs_cols, act_dim=CONST["HRG_ACT_DIM"], 
     return d
 
 
+# ---- the index arithmetic of the grouped minibatches (RolloutBuffer.get_groups), on tensors of any device
+def group_rows(n_envs, n_steps, n_groups, batch_size):
+    """(n_groups, the m * n_steps rows of a group) for `n_envs` envs in `n_groups` groups of m consecutive envs; NotImplementedError for groups that do not
+    divide the envs and for a batch_size that does not divide a group's rows (the learner takes no short last minibatch)."""
+    n, T, P, B = int(n_envs), int(n_steps), int(n_groups), int(batch_size)
+    if P < 1 or n % P:
+        raise NotImplementedError(f"n_envs = {n} is not divisible by n_groups = {P}: every member reads a group of the same size")
+    rows = n // P * T
+    if B < 1 or rows % B:
+        raise NotImplementedError(f"batch_size = {B} does not divide m * n_steps = {rows} (m = {n // P} envs per group): the learner takes no short last minibatch")
+    return P, rows
+
+
+def group_table(perms, rows):
+    """The permutations of 0 .. rows - 1, one per group, as the int64 [n_groups, rows] table of flat indices: group p's moved by p * rows."""
+    import torch
+    table = torch.stack(list(perms))
+    return table + rows * torch.arange(table.shape[0], dtype=table.dtype, device=table.device)[:, None]
+
+
+def group_batch(table, k0, batch_size):
+    """Minibatch k0 / batch_size of every group, one behind the other: cat_p(table[p, k0:k0 + batch_size]), int64 [n_groups * batch_size]."""
+    return table[:, k0:k0 + batch_size].reshape(-1)
+
+
 class RolloutBuffer(EpisodeBuffer):
     """A device-resident rollout buffer of `desc.n_steps` slots for each of `desc.n_envs` envs (hrg_rollout_desc; `build_rollout_desc`).  All arguments and
     results are torch tensors on the buffer's device; the calls are asynchronous, ordered on torch's current stream (`episode_stats` and `export`
@@ -143,6 +168,27 @@ class RolloutBuffer(EpisodeBuffer):
         self.last_indices = perm
         for k0 in range(0, N, B):
             yield self._gather(perm[k0:k0 + B])
+
+    def get_groups(self, n_groups, batch_size, seeds=None):
+        """`get` for a population (ppo.PpoPopulation): the envs are `n_groups` groups of m = n_envs / n_groups consecutive envs, group p the flat range
+        [p m n_steps, (p + 1) m n_steps).  Yields RolloutBufferSamples of n_groups * batch_size samples, group p's rows at p * batch_size, that cover one
+        `torch.randperm(m * n_steps)` per group, drawn on the device with a generator of the group's own, seeded `seeds[p]` (default: p) -- what `get` of a
+        lone buffer of the group's m envs with that seed draws.  The generators are made on first use and kept; another seeds list reseeds them.  Each
+        minibatch is one gather; `last_indices` is the int64 [n_groups, m * n_steps] table of the epoch."""
+        t = self.torch
+        P, rows = group_rows(self.n, self.n_steps, n_groups, batch_size)
+        seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in (range(P) if seeds is None else seeds)]
+        if len(seeds) != P:
+            raise ValueError(f"get_groups: {len(seeds)} seeds for {P} groups")
+        with t.cuda.device(self.device):
+            if getattr(self, "_group_seeds", None) != seeds:
+                self._group_generators = [t.Generator(device=self.device) for _ in seeds]
+                for g, s in zip(self._group_generators, seeds):
+                    g.manual_seed(s)
+                self._group_seeds = seeds
+            table = group_table([t.randperm(rows, device=self.device, generator=g) for g in self._group_generators], rows)
+        self.last_indices = table
+        return (self._gather(group_batch(table, k0, int(batch_size))) for k0 in range(0, rows, int(batch_size)))   # (the refusals above come with the call)
 
     def reset(self):
         """SB3's rollout_buffer.reset(): the position back to 0.  Current rows, flags, running returns and episode accumulators stay."""

@@ -23,20 +23,17 @@ read the row achieved_goal | desired_goal | observation; her.HerBuffer hands out
 """
 import ctypes
 import math
-import os
-from types import SimpleNamespace
 
 import numpy as np
 
 from ._cstruct import CONST, SacDesc
-from ._learner import TENSORS, Learner, LearnerParams, build_layout, check_widths, load_checkpoint, mlp_entries, restore_tensors, save_checkpoint
+from ._learner import MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries  # noqa: F401 (check_seeds: importable from here)
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_SAC_HIDDEN"]
 MAX_DEPTH = CONST["HRG_SAC_MAX_DEPTH"]
 TILE = CONST["HRG_SAC_TILE"]
 MAX_BATCH = CONST["HRG_SAC_MAX_BATCH"]
-MAX_POPULATION = CONST["HRG_SAC_MAX_POPULATION"]
 NQ = CONST["HRG_SAC_NQ"]
 Q_COLUMNS = ("q1", "q2", "q1_target", "q2_target", "q1_pi", "q2_pi")   # the rows of hrg_sac_export's q, in its order
 
@@ -242,38 +239,22 @@ class SacLearner(Learner):
         return dict(ent_coef=float(losses[3]), actor_loss=float(losses[0]), critic_loss=float(losses[1]), ent_coef_loss=float(losses[2]), n_updates=self.n_updates)
 
 
-def check_seeds(n_members, seeds):
-    """(P, the members' seeds as uint64 [P]); NotImplementedError for a population the kernels do not cover, ValueError for a seeds table of another length."""
-    P = int(n_members)
-    if not 1 <= P <= MAX_POPULATION:
-        raise NotImplementedError(f"n_members = {P}: a population has 1 .. {MAX_POPULATION} members")
-    seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
-    if len(seeds) != P:
-        raise ValueError(f"seeds: {len(seeds)} seeds for {P} members")
-    return P, np.array(seeds, np.uint64)
-
-
-class SacPopulationParams:
+class SacPopulationParams(PopulationParams):
     """The tensors of a population, on any torch device: `params`, `adam_m`, `adam_v` float32 [P, n_params] and `target` float32 [P, 2 n_critic].  Row p is
     initialised exactly as SacParams(seed=seeds[p]); `member(p)` is the rows of member p as views."""
 
     def __init__(self, obs_dim, act_dim, depth, seeds, ent_coef_init=1.0, device="cpu"):
-        import torch
         rows = [SacParams(obs_dim, act_dim, depth, seed=int(s), ent_coef_init=ent_coef_init) for s in seeds]
-        self.layout, self.n_params, self.n_actor, self.n_critic = rows[0].layout, rows[0].n_params, rows[0].n_actor, rows[0].n_critic
-        self.params = torch.stack([r.params for r in rows]).to(device)
-        self.target = torch.stack([r.target for r in rows]).to(device)
-        self.adam_m, self.adam_v = torch.zeros_like(self.params), torch.zeros_like(self.params)
-
-    def member(self, p):
-        return SimpleNamespace(**{name: getattr(self, name)[p] for name in TENSORS})
+        super().__init__(rows, device)
+        self.n_actor, self.n_critic = rows[0].n_actor, rows[0].n_critic
 
 
-class SacPopulation(SacLearner):
+class SacPopulation(Population, SacLearner):
     """`n_members` SAC learners of the same shapes and hyper-parameters (SacLearner's keywords) that differ in their seed only and take their gradient step in
     the same six launches (csrc/hrgym_sac.h): the seeds of one cell of a study, side by side on one GPU.  The batch of n = P m envs is P groups
     of m consecutive envs; member p acts in, and learns from, group p only.  The counters are shared: members step in lockstep.  Member p is, bit for bit,
-    SacLearner(seed=seeds[p]) on the same transitions.
+    SacLearner(seed=seeds[p]) on the same transitions.  export(member), diagnostics (a list of P dicts), member(p), save and load (member_<p>.npz):
+    _learner.Population.
 
         env.attach_replay(buffer_size)
         pop = env.attach_sac_population(5, batch_size=128)       # seeds: the env's seed + p
@@ -281,13 +262,14 @@ class SacPopulation(SacLearner):
         pop.train(env.replay, 800)                               # 800 x (env.replay.sample_groups(5, 128, pop.seeds), step)
         pop.diagnostics()                                        # a list of 5 dicts
     """
+    _lone = SacLearner
 
     def __init__(self, obs_dim, act_dim, n_members, seeds, net_arch=(64, 64, 64), learning_rate=3e-4, gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto",
                  batch_size=256, target_update_interval=1, device=0):
         self.n_members, table = check_seeds(n_members, seeds)
         self.seeds = [int(s) for s in table]
         self._kwargs = dict(net_arch=net_arch, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, batch_size=batch_size,
-                            target_update_interval=target_update_interval)
+                            target_update_interval=target_update_interval)   # (member, save and load: _learner.Population)
         desc = build_sac_desc(obs_dim, act_dim, seed=self.seeds[0], **self._kwargs)   # (the entry reads the table, not the descriptor's seed)
         self._open(desc, device, self.n_members, table.ctypes.data_as(ctypes.c_void_p), create="_population_create")
         self.obs_dim, self.act_dim, self.depth, self.batch_size = int(obs_dim), int(act_dim), int(self.desc.depth), int(batch_size)
@@ -317,69 +299,3 @@ class SacPopulation(SacLearner):
         with t.cuda.device(self.device):
             self._check(self.lib, self.lib.hrg_sac_population_act(self.h, _ptr(self.p.params), o, n // self.n_members, e, int(bool(deterministic)), _ptr(out), self._stream()))
         return out
-
-    def _export(self, *arrays, member=0):
-        self._check(self.lib, self.lib.hrg_sac_population_export(self.h, int(member), *(None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrays)))
-
-    def export(self, member=0):
-        """SacLearner.export of one member."""
-        return super().export(member=member)
-
-    def diagnostics(self):
-        """SacLearner.diagnostics of every member: a list of n_members dicts.  Synchronous."""
-        return [super(SacPopulation, self).diagnostics(member=p) for p in range(self.n_members)]
-
-    def member(self, p):
-        """Member p as a SacLearner of its own: copies of its tensors, the population's counters and learning rate.  Fed the same batches, it continues bit
-        for bit.  The caller closes it."""
-        if not 0 <= int(p) < self.n_members:
-            raise IndexError(f"member {p} of {self.n_members}")
-        learner = SacLearner(self.obs_dim, self.act_dim, learning_rate=self.learning_rate, seed=self.seeds[p], device=self.device.index, **self._kwargs)
-        sizes = self._sizes()
-        with self.torch.no_grad():
-            for name, rows in vars(self.p.member(int(p))).items():
-                getattr(learner.p, name).copy_(rows)
-        learner._check(learner.lib, learner.lib.hrg_sac_restore(learner.h, sizes[3], sizes[4]))
-        return learner
-
-    def save(self, path):
-        """One checkpoint per member, `path`/member_<p>.npz, in SacLearner's format: SacLearner.load and tools/evaluate.py read them.  Synchronous."""
-        sizes = self._sizes()
-        for p in range(self.n_members):
-            desc = SacDesc.from_buffer_copy(self.desc)
-            desc.seed = self.seeds[p]
-            save_checkpoint(os.path.join(path, f"member_{p}.npz"), self._prefix, desc, self.p.member(p), (sizes[3], sizes[4]), self._hyper())
-        return path
-
-    @classmethod
-    def load(cls, path, device=0):
-        """The population of the member_<p>.npz under `path` (p = 0, 1, .. without a gap).  ValueError for members of different shapes, hyper-parameters or
-        counters: those are no population."""
-        files = []
-        while os.path.exists(os.path.join(path, f"member_{len(files)}.npz")):
-            files.append(os.path.join(path, f"member_{len(files)}.npz"))
-        if not files:
-            raise ValueError(f"{path}: no member_0.npz")
-        ckpts = [load_checkpoint(f, cls._prefix) for f in files]
-        first = ckpts[0]
-        for f, c in zip(files, ckpts):
-            differs = [k for k in first["desc"] if k != "seed" and not np.array_equal(first["desc"][k], c["desc"][k])]
-            differs += [k for k in first["hyper"] if not np.array_equal(first["hyper"][k], c["hyper"][k], equal_nan=True)]
-            if differs or not np.array_equal(first["counters"], c["counters"]):
-                raise ValueError(f"{f}: {', '.join(differs) or 'counters'} differ from member 0's: the members of a population share them")
-        pop = cls(n_members=len(ckpts), seeds=[int(c["desc"]["seed"]) for c in ckpts], device=device, **cls._checkpoint_kwargs(first["desc"], first["hyper"]))
-        try:
-            for p, c in enumerate(ckpts):
-                restore_tensors(pop.p.member(p), c)
-            steps, calls = (int(x) for x in first["counters"])
-            pop._check(pop.lib, pop.lib.hrg_sac_restore(pop.h, steps, calls))
-        except Exception:
-            pop.close()
-            raise
-        return pop
-
-    def state_dict(self):
-        raise NotImplementedError("state_dict of a population: member(p).state_dict()")
-
-    def load_state_dict(self, state):
-        raise NotImplementedError("load_state_dict of a population: load the member's checkpoint")

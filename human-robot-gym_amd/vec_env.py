@@ -560,6 +560,7 @@ class HipVecEnv(_VecEnvBase):
         self.sac = None              # the SAC learner (sac.SacLearner), once attached
         self.sac_population = None   # the SAC population (sac.SacPopulation), once attached
         self.ppo = None              # the PPO learner (ppo.PpoLearner), once attached
+        self.ppo_population = None   # the PPO population (ppo.PpoPopulation), once attached
         self._buffers_behind = False   # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
 
@@ -757,6 +758,9 @@ class HipVecEnv(_VecEnvBase):
         if self.ppo is not None:
             self.ppo.close()
             self.ppo = None
+        if self.ppo_population is not None:
+            self.ppo_population.close()
+            self.ppo_population = None
         self._backend.close()
 
     def seed(self, seed=None):
@@ -1017,6 +1021,36 @@ class HipVecEnv(_VecEnvBase):
             raise NotImplementedError("attach_ppo: call attach_rollout(n_steps, gamma, gae_lambda) first (the learner takes its observation and action widths from the buffer)")
         from .ppo import PpoLearner
         return self._attach_learner("ppo", PpoLearner, rb.obs_dim, rb, rollout_size=rb.n * rb.n_steps, **kwargs)
+
+    def attach_ppo_population(self, n_members, seeds=None, **kwargs):
+        """`n_members` PPO learners that differ in their seed only, stepped in the same launches (ppo.PpoPopulation; PpoLearner's keywords but `seed`), after
+        attach_rollout: the envs are n_members groups of m = num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`:
+        one per member (default: the env's seed + p).  Refused before anything is allocated: another backend and the mixed batch, no rollout buffer, envs
+        that the members do not divide, a batch_size that does not divide m * n_steps.  Returns the population and keeps it as `env.ppo_population`:
+        `env.collect_rollout(pop.policy, pop.value)`, then `pop.train(env.rollout)`; `env.evaluate(pop.p.params, n, learner=pop.member(0))` evaluates the
+        members side by side."""
+        from .ppo import PpoPopulation, check_seeds
+        from .rollout import group_rows
+        P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]
+        if "seed" in kwargs:
+            raise TypeError("attach_ppo_population: the members' seeds are `seeds` (one per member), not `seed`")
+        why = self._rollout_refusal()
+        if why is not None:
+            raise NotImplementedError(f"attach_ppo_population: {why}")
+        rb = self.rollout
+        if rb is None:
+            raise NotImplementedError("attach_ppo_population: call attach_rollout(n_steps, gamma, gae_lambda) first (the members take their observation and action "
+                                      "widths from the buffer)")
+        try:
+            rows = group_rows(rb.n, rb.n_steps, P, kwargs.get("batch_size", 64))[1]
+        except NotImplementedError as e:
+            raise NotImplementedError(f"attach_ppo_population: {e}") from None
+        pop = PpoPopulation(rb.obs_dim, rb.act_dim, P, [int(self._desc.seed) + p for p in range(P)] if seeds is None else seeds, device=rb.device.index,
+                            rollout_size=rows, **kwargs)
+        if self.ppo_population is not None:
+            self.ppo_population.close()
+        self.ppo_population = pop
+        return pop
 
     def _attach_learner(self, slot, cls, obs_dim, rb, **kwargs):
         """What attach_ppo and attach_sac end with: the learner of the buffer's action width and device, seeded like the env unless told otherwise, kept as

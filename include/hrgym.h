@@ -540,6 +540,7 @@ typedef struct hrg_sac_desc {
 #define HRG_PPO_MAX_DEPTH HRG_SAC_MAX_DEPTH /* hidden layers: 1 .. 3 */
 #define HRG_PPO_TILE HRG_SAC_TILE           /* rows of the minibatch per workgroup: batch_size is a multiple */
 #define HRG_PPO_MAX_BATCH 4096
+#define HRG_PPO_MAX_POPULATION 64           /* members of a population: learners of one descriptor that differ in their seed and step in the same launches */
 #define HRG_PPO_NDIAG 8                     /* floats of hrg_ppo_export's diag */
 #define HRG_PPO_MLP_POLICY 0                /* hrg_ppo_desc.policy: SB3's "MlpPolicy", the only one covered */
 /* One learner: SB3 1.5.0's PPO(MlpPolicy, use_sde = False) with net_arch = [64] * depth (separate = 0: the shared trunk) or [dict(pi = [64] * depth, vf = [64] * depth)]
@@ -990,6 +991,26 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
 int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev,
                     float* values_dev, float* log_probs_dev, void* stream);
 int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
+
+/* A PPO population (csrc/hrgym_ppo.h): n_members learners of one descriptor that differ in their seed only and take their minibatch step in the same
+ * four launches.  The handle is an hrg_ppo: the lone learner is the population of one member, and hrg_ppo_sizes, hrg_ppo_step, hrg_ppo_restore, hrg_ppo_destroy and
+ * hrg_eval_policy_ppo serve both; hrg_ppo_export is member 0's.  The counters (minibatch steps, forward calls) are the handle's: members step in lockstep, and
+ * learning_rate, clip_range and clip_range_vf of a step are shared.  Member p is, bit for bit, the lone learner of seeds[p] on the same rows: its advantage
+ * statistics, clip coefficient and diagnostics come from its own sums, its draws are keyed by its seed and the row's index in its own group.
+ *   hrg_ppo_population_create   hrg_ppo_create with n_members seeds in place of the descriptor's (which is not read).  Before anything is allocated or launched:
+ *                               HRG_ERR_UNSUPPORTED for n_members outside 1 .. HRG_PPO_MAX_POPULATION, HRG_ERR_INVALID for a null seeds table, then whatever
+ *                               hrg_ppo_create refuses.
+ *   hrg_ppo_step                on a population: every array is [n_members] times the lone learner's, member p's part at p times its size: observations
+ *                               [P][B][obs_dim], ..., returns [P][B], params_dev, adam_m_dev, adam_v_dev [P][n_params].
+ *   hrg_ppo_population_forward  obs_dev float [P][n_group][obs_dim] -> actions_dev float [P][n_group][act_dim], values_dev, log_probs_dev float [P][n_group], member
+ *                               p's networks (params_dev [P][n_params]) on group p; a draw's key is (seeds[p], forward call count, row within the group, 14, j).
+ *                               eps_dev [P][n_group][act_dim], deterministic and a NULL actions_dev (the values only) as in hrg_ppo_forward, which is this entry
+ *                               for one member and refuses a handle of more.  HRG_ERR_INVALID for n_group < 1.
+ *   hrg_ppo_population_export   hrg_ppo_export of one member; HRG_ERR_INVALID for a member outside the population. */
+int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_ppo** out);
+int hrg_ppo_population_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic,
+                               float* actions_dev, float* values_dev, float* log_probs_dev, void* stream);
+int hrg_ppo_population_export(hrg_ppo* h, int32_t member, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
 
 /* A learner's counters, for a checkpoint that is loaded into a fresh handle: Adam's bias corrections, the keys of the draws and (SAC) the phase of the target
  * update follow from them.

@@ -6,9 +6,14 @@ log_std_init -2.7, ortho_init false).  A demonstration of the plumbing; it carri
 With n_envs * n_steps rows per rollout, n_epochs 20 and batch_size 64 a rollout of 4096 envs is 81 920 minibatch steps: whether a run at thousands of envs
 keeps the reference's batch size is the user's decision.
 
-python tools/train_ppo.py --n-envs 256 --rollouts 10"""
+--seeds: the seeds of one cell as a population (ppo.PpoPopulation), --n-envs split into equal groups, one set of launches per minibatch step for all of them;
+a JSON line then carries a list `members` with an entry per seed.
+
+python tools/train_ppo.py --n-envs 256 --rollouts 10
+python tools/train_ppo.py --n-envs 50 --rollouts 10 --seeds 0 1 2 3 4"""
 import argparse
 import json
+import os
 import sys
 import time
 
@@ -30,26 +35,67 @@ ap.add_argument("--gae-lambda", type=float, default=0.9)
 ap.add_argument("--log-std-init", type=float, default=-2.7)
 ap.add_argument("--separate", action="store_true", help="net_arch [dict(pi=[64, 64], vf=[64, 64])] instead of the shared [64, 64]")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--seeds", type=int, nargs="+", default=None, help="a population: one member per seed, n-envs / len(seeds) envs each (the env itself is seeded with --seed)")
 ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
 ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
 ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
 ap.add_argument("--eval-n-envs", type=int, default=64)
 ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
-args = ap.parse_args()
 
-env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
-env.attach_rollout(n_steps=args.n_steps, gamma=args.gamma, gae_lambda=args.gae_lambda)
-learner = env.attach_ppo(batch_size=args.batch_size, n_epochs=args.n_epochs, learning_rate=args.learning_rate, log_std_init=args.log_std_init, ortho_init=False,
-                         net_arch=[dict(pi=[64, 64], vf=[64, 64])] if args.separate else [64, 64], seed=args.seed)
-run = run_folder_from_args(args)
-t0 = time.time()
-for k in range(args.rollouts):
-    env.collect_rollout(learner.policy, learner.value)
-    learner.train(env.rollout)
-    line = dict(rollout=k, env_steps=(k + 1) * args.n_steps * args.n_envs, seconds=round(time.time() - t0, 3))
-    line.update(env.rollout.episode_stats())
-    line.update(learner.diagnostics())
-    line.update(run.after(learner, line["env_steps"]))
-    print(json.dumps(line), flush=True)
-run.finish(learner)
-env.close()
+
+def main(args):
+    env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
+    env.attach_rollout(n_steps=args.n_steps, gamma=args.gamma, gae_lambda=args.gae_lambda)
+    kw = dict(batch_size=args.batch_size, n_epochs=args.n_epochs, learning_rate=args.learning_rate, log_std_init=args.log_std_init, ortho_init=False,
+              net_arch=[dict(pi=[64, 64], vf=[64, 64])] if args.separate else [64, 64])
+    if args.seeds is not None:
+        run_population(args, env, kw)
+        env.close()
+        return
+    learner = env.attach_ppo(seed=args.seed, **kw)
+    run = run_folder_from_args(args)
+    t0 = time.time()
+    for k in range(args.rollouts):
+        env.collect_rollout(learner.policy, learner.value)
+        learner.train(env.rollout)
+        line = dict(rollout=k, env_steps=(k + 1) * args.n_steps * args.n_envs, seconds=round(time.time() - t0, 3))
+        line.update(env.rollout.episode_stats())
+        line.update(learner.diagnostics())
+        line.update(run.after(learner, line["env_steps"]))
+        print(json.dumps(line), flush=True)
+    run.finish(learner)
+    env.close()
+
+
+def run_population(args, env, kw):
+    """The loop of `main` for the members of --seeds."""
+    P = len(args.seeds)
+    pop = env.attach_ppo_population(P, seeds=args.seeds, **kw)
+    eval_env, first, saved_until = None, None, 0
+    if args.eval_episodes > 0:
+        eval_env = hrg.HipVecEnv(args.eval_n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed + 1 if args.eval_seed is None else args.eval_seed))
+        first = pop.member(0)   # (the shapes the stacked parameters follow)
+    t0 = time.time()
+    for k in range(args.rollouts):
+        env.collect_rollout(pop.policy, pop.value)
+        pop.train(env.rollout)
+        env_steps = (k + 1) * args.n_steps * args.n_envs
+        line = dict(rollout=k, env_steps=env_steps, seconds=round(time.time() - t0, 3))
+        members = [dict(seed=s, **stats, **diag) for s, stats, diag in zip(pop.seeds, env.rollout.episode_stats(groups=P), pop.diagnostics())]
+        if eval_env is not None:
+            for m, res in zip(members, eval_env.evaluate(pop.p.params, args.eval_episodes, learner=first).by_policy()):
+                m.update(eval_mean_reward=res.mean_reward, eval_std_reward=res.std_reward, eval_mean_ep_length=res.mean_ep_length)
+        if args.model_dir is not None and args.save_freq > 0 and env_steps // args.save_freq > saved_until:
+            saved_until = env_steps // args.save_freq
+            line["checkpoint"] = pop.save(os.path.join(args.model_dir, f"model_{env_steps}"))
+        line["members"] = members
+        print(json.dumps(line), flush=True)
+    if args.model_dir is not None:
+        pop.save(os.path.join(args.model_dir, "model_final"))
+    if first is not None:
+        first.close()
+        eval_env.close()
+
+
+if __name__ == "__main__":   # (imported: the parser `ap` only)
+    main(ap.parse_args())
