@@ -117,6 +117,8 @@ RolloutDesc = _STRUCTS["hrg_rollout_desc"]
 ReplayDesc = _STRUCTS["hrg_replay_desc"]
 SacDesc = _STRUCTS["hrg_sac_desc"]
 PpoDesc = _STRUCTS["hrg_ppo_desc"]
+SacHyper = _STRUCTS["hrg_sac_hyper"]
+PpoHyper = _STRUCTS["hrg_ppo_hyper"]
 EvalDesc = _STRUCTS["hrg_eval_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 

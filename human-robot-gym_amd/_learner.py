@@ -1,6 +1,7 @@
 """What the device learners share (sac.SacLearner, ppo.PpoLearner; csrc/hrgym_mlp.h): the refusal of widths the tile kernels do not cover, the flat parameter
 layout, the tensors behind `state_dict()` with their seeded initialisation, the learner's calls that differ by the entry points' prefix only, and what the
-two populations share (sac.SacPopulation, ppo.PpoPopulation): the seeds table, the stacked tensors, a member as a lone learner, the checkpoints per member."""
+two populations share (sac.SacPopulation, ppo.PpoPopulation): the seeds table, a value per member of every hyper-parameter the device table holds, the stacked
+tensors, a member as a lone learner, the checkpoints per member and their manifest."""
 import ctypes
 import os
 from collections import OrderedDict
@@ -168,6 +169,85 @@ def check_seeds(n_members, seeds):
     return P, np.array(seeds, np.uint64)
 
 
+def per_member(name, value, n_members):
+    """`value` of the hyper-parameter `name` for every member, a list of n_members: a scalar (a number, a string such as "auto_0.2", None) means every member,
+    a list, tuple or array is one value per member; ValueError, naming the field, for a sequence of another length."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        values = [v.item() if isinstance(v, np.generic) else v for v in value]
+        if len(values) != int(n_members):
+            raise ValueError(f"{name}: {len(values)} values for {int(n_members)} members (a scalar, or one value per member)")
+        return values
+    return [value] * int(n_members)
+
+
+def refuse_shared_sequences(shared, kwargs):
+    """NotImplementedError where `kwargs` holds one value per member for a keyword of `shared` (name -> why every member of a population shares it).  net_arch
+    is a list by itself: one per member would be a list of lists."""
+    for name, why in shared.items():
+        value = kwargs.get(name)
+        many = isinstance(value, (list, tuple, np.ndarray))
+        if name == "net_arch":
+            many = many and len(value) > 0 and all(isinstance(v, (list, tuple)) for v in value)
+        if many:
+            raise NotImplementedError(f"{name} = {value}: one value per member is not supported: {why}")
+
+
+# ---- the manifest of a population's folder: which fields of the members' checkpoints differ (one .npz of arrays, read without pickle) ----
+MANIFEST = "population.npz"
+
+
+def write_manifest(folder, kind, varies):
+    """`folder`/population.npz for a population of `kind` whose members differ in the checkpoint fields `varies` (names of the desc.* and hyper.* entries);
+    with nothing that varies no manifest is written, and one that is there is removed."""
+    path = os.path.join(folder, MANIFEST)
+    if not varies:
+        if os.path.exists(path):
+            os.remove(path)
+        return None
+    with open(path, "wb") as f:
+        np.savez(f, format=np.array(CHECKPOINT_FORMAT, np.int64), kind=np.array(str(kind)), varies=np.array(sorted(str(v) for v in varies)))
+    return path
+
+
+def read_manifest(folder, kind):
+    """The field names `folder`/population.npz lists, () without the file; ValueError for a manifest of another learner or format."""
+    path = os.path.join(folder, MANIFEST)
+    if not os.path.exists(path):
+        return ()
+    with np.load(path, allow_pickle=False) as f:
+        arrays = {k: f[k] for k in f.files}
+    if "varies" not in arrays or int(arrays.get("format", -1)) != CHECKPOINT_FORMAT or str(arrays.get("kind")) != kind:
+        raise ValueError(f"{path}: no manifest of a population of {kind!r} in format {CHECKPOINT_FORMAT}")
+    return tuple(str(v) for v in np.atleast_1d(arrays["varies"]))
+
+
+def check_members(files, ckpts, varies=(), may_vary=()):
+    """ValueError unless the checkpoints `ckpts` (load_checkpoint's dicts, of `files`) are the members of one population: the same descriptor fields (the seed
+    apart), scheduled attributes and counters, but for the fields the manifest names (`varies`), which have to be among the ones the table holds (`may_vary`)."""
+    unknown = sorted(set(varies) - set(may_vary))
+    if unknown:
+        raise ValueError(f"{os.path.dirname(files[0])}: the manifest names {', '.join(unknown)}: the members of a population share them (per member: {', '.join(may_vary)})")
+    first = ckpts[0]
+    for f, c in zip(files, ckpts):
+        differs = [k for k in first["desc"] if k != "seed" and k not in varies and not np.array_equal(first["desc"][k], c["desc"][k])]
+        differs += [k for k in first["hyper"] if k not in varies and not np.array_equal(first["hyper"][k], c["hyper"][k], equal_nan=True)]
+        if differs or not np.array_equal(first["counters"], c["counters"]):
+            raise ValueError(f"{f}: {', '.join(differs) or 'counters'} differ from member 0's: the members of a population share them")
+
+
+def scheduled_attribute(name):
+    """A scheduled attribute of a population (Population._scheduled): every member's value where they agree, else the list of them; a scalar or one value per
+    member may be assigned between any two steps, and the table is uploaded again where it is the caller's."""
+    def get(self):
+        values = self._values[name]
+        return values[0] if all(v == values[0] for v in values) else list(values)
+
+    def put(self, value):
+        self._set_values(**{name: value})
+        self._sync_table()
+    return property(get, put, doc=scheduled_attribute.__doc__)
+
+
 class PopulationParams:
     """The tensors of a population, on any torch device: every tensor of the lone learners' LearnerParams `rows` stacked, [P, ...].  Row p is member p's,
     initialised exactly as the lone learner of its seed; `member(p)` is the rows of member p as views."""
@@ -187,8 +267,58 @@ class PopulationParams:
 class Population:
     """What the populations add to their lone learner's class, ahead of it in the bases: `_lone` is that class, `n_members`, `seeds` (ints) and `_kwargs` (the
     lone learner's constructor keywords apart from the seed, the device and the scheduled attributes of `_hyper`) are set by the subclass, `p` is a
-    PopulationParams."""
+    PopulationParams.
+
+    Hyper-parameters per member.  `_fields` names the constructor keywords the handle's device table holds a row of per member, `_scheduled`
+    those of them that are plain attributes of the lone learner (a scalar or a sequence may be assigned between steps), `_shared` the keywords every member
+    shares, with the reason; `_convert(name, value)` checks one member's value and `_row(p)` is member p's row of the table (hrg_*_hyper).  `_values[name]` is the
+    list of the members' values.  While every member has the same values nothing is uploaded: the step's scalar arguments fill the table, as for the lone
+    learner.  From the first upload on the table is the caller's (`_per_member`), and every assignment uploads it again."""
     _lone = None
+    _fields = _scheduled = _manifest_fields = ()
+    _shared = {}
+    _per_member = False
+
+    @classmethod
+    def member_values(cls, n_members, **values):
+        """{name: the n_members members' values} of the table fields named, a scalar or a sequence each (per_member), every value checked (`_convert`)."""
+        return {name: [cls._convert(name, v) for v in per_member(name, value, n_members)] for name, value in values.items()}
+
+    def _set_values(self, **values):
+        if "_values" not in self.__dict__:
+            self._values = {}
+        self._values.update(self.member_values(self.n_members, **values))
+        self._member0 = tuple(self._values[name][0] for name in self._scheduled if name in self._values)   # (what a step passes as its scalars)
+
+    @staticmethod
+    def _convert(name, value):
+        return float(value)
+
+    def varying(self):
+        """The table's fields in which the members differ, in the table's order."""
+        return [name for name in self._fields if any(v != self._values[name][0] for v in self._values[name])]
+
+    def member_hyper(self, p):
+        """Every field of member p's row of the table, under the constructor's keywords and in its forms ("auto_0.2", clip_range_vf None)."""
+        if not 0 <= int(p) < self.n_members:
+            raise IndexError(f"member {p} of {self.n_members}")
+        return {name: self._values[name][int(p)] for name in self._fields}
+
+    def _scalar(self, name, member=0):
+        return self._values[name][int(member)]
+
+    def _sync_table(self):
+        """Uploads the table where the members differ, or have differed before; ordered on torch's current stream behind the steps queued there."""
+        if not (self._per_member or self.varying()) or not getattr(self, "h", None):
+            return
+        rows = (type(self._row(0)) * self.n_members)(*(self._row(p) for p in range(self.n_members)))
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib, getattr(self.lib, self._prefix + "_population_set_hyper")(self.h, ctypes.byref(rows), self.n_members, self._stream()))
+        self._per_member = True
+
+    def _hyper_of(self, p):
+        """The lone learner's `_hyper()` of member p."""
+        return {k: (self._values[k][p] if k in self._scheduled else v) for k, v in self._hyper().items()}
 
     def _export(self, *arrays, member=0):
         self._check(self.lib, getattr(self.lib, self._prefix + "_population_export")(self.h, int(member), *(None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrays)))
@@ -205,11 +335,11 @@ class Population:
         self._check(self.lib, getattr(self.lib, self._prefix + "_restore")(self.h, int(steps), int(calls)))
 
     def member(self, p):
-        """Member p as a lone learner of its own: copies of its tensors, the population's counters and scheduled attributes.  Fed the same batches, it
-        continues bit for bit.  The caller closes it."""
+        """Member p as a lone learner of its own: copies of its tensors, the population's counters, member p's hyper-parameters and scheduled attributes.  Fed
+        the same batches, it continues bit for bit.  The caller closes it."""
         if not 0 <= int(p) < self.n_members:
             raise IndexError(f"member {p} of {self.n_members}")
-        learner = self._lone(self.obs_dim, self.act_dim, seed=self.seeds[p], device=self.device.index, **self._kwargs, **self._hyper())
+        learner = self._lone(self.obs_dim, self.act_dim, seed=self.seeds[p], device=self.device.index, **{**self._kwargs, **self._hyper_of(int(p)), **self.member_hyper(p)})
         sizes = self._sizes()
         with self.torch.no_grad():
             for name, rows in vars(self.p.member(int(p))).items():
@@ -218,18 +348,23 @@ class Population:
         return learner
 
     def save(self, path):
-        """One checkpoint per member, `path`/member_<p>.npz, in the lone learner's format: its `load` and tools/evaluate.py read them.  Synchronous."""
+        """One checkpoint per member, `path`/member_<p>.npz, in the lone learner's format with the member's own descriptor fields and scheduled attributes: its
+        `load` and tools/evaluate.py read them.  Where the members differ in more than their seed, `path`/population.npz names the fields (write_manifest).
+        Synchronous."""
         sizes = self._sizes()
+        descs, hypers = [self._member_desc(p) for p in range(self.n_members)], [self._hyper_of(p) for p in range(self.n_members)]
         for p in range(self.n_members):
-            desc = type(self.desc).from_buffer_copy(self.desc)
-            desc.seed = self.seeds[p]
-            save_checkpoint(os.path.join(path, f"member_{p}.npz"), self._prefix, desc, self.p.member(p), (sizes[3], sizes[4]), self._hyper())
+            save_checkpoint(os.path.join(path, f"member_{p}.npz"), self._prefix, descs[p], self.p.member(p), (sizes[3], sizes[4]), hypers[p])
+        fields = [desc_fields(d) for d in descs]
+        varies = [k for k in fields[0] if k != "seed" and any(not np.array_equal(f[k], fields[0][k]) for f in fields)]
+        varies += [k for k in hypers[0] if any(h[k] != hypers[0][k] for h in hypers)]
+        write_manifest(path, self._prefix, varies)
         return path
 
     @classmethod
     def load(cls, path, device=0):
-        """The population of the member_<p>.npz under `path` (p = 0, 1, .. without a gap).  ValueError for members of different shapes, hyper-parameters or
-        counters: those are no population."""
+        """The population of the member_<p>.npz under `path` (p = 0, 1, .. without a gap).  ValueError for members of different shapes, counters or
+        hyper-parameters, but for those the folder's manifest names (population.npz, written by `save`): those are no population."""
         files = []
         while os.path.exists(os.path.join(path, f"member_{len(files)}.npz")):
             files.append(os.path.join(path, f"member_{len(files)}.npz"))
@@ -237,12 +372,13 @@ class Population:
             raise ValueError(f"{path}: no member_0.npz")
         ckpts = [load_checkpoint(f, cls._prefix) for f in files]
         first = ckpts[0]
-        for f, c in zip(files, ckpts):
-            differs = [k for k in first["desc"] if k != "seed" and not np.array_equal(first["desc"][k], c["desc"][k])]
-            differs += [k for k in first["hyper"] if not np.array_equal(first["hyper"][k], c["hyper"][k], equal_nan=True)]
-            if differs or not np.array_equal(first["counters"], c["counters"]):
-                raise ValueError(f"{f}: {', '.join(differs) or 'counters'} differ from member 0's: the members of a population share them")
-        pop = cls(n_members=len(ckpts), seeds=[int(c["desc"]["seed"]) for c in ckpts], device=device, **cls._checkpoint_kwargs(first["desc"], first["hyper"]))
+        varies = read_manifest(path, cls._prefix)
+        check_members(files, ckpts, varies, cls._manifest_fields)
+        kwargs = cls._checkpoint_kwargs(first["desc"], first["hyper"])
+        if varies:
+            members = [cls._checkpoint_kwargs(c["desc"], c["hyper"]) for c in ckpts]
+            kwargs.update({name: [m[name] for m in members] for name in cls._fields if any(m[name] != members[0][name] for m in members)})
+        pop = cls(n_members=len(ckpts), seeds=[int(c["desc"]["seed"]) for c in ckpts], device=device, **kwargs)
         try:
             for p, c in enumerate(ckpts):
                 restore_tensors(pop.p.member(p), c)
@@ -267,6 +403,10 @@ class Learner(DeviceHandle):
     def _open(self, desc, device, *create_args, create="_create"):
         self._create, self._destroy = self._prefix + create, self._prefix + "_destroy"
         super()._open(desc, device, *create_args)
+
+    def _scalar(self, name, member=0):
+        """The scheduled attribute `name` as a step or a diagnostic reads it (a population: the member's)."""
+        return getattr(self, name)
 
     def _sizes(self):
         w = (ctypes.c_int64 * 6)()

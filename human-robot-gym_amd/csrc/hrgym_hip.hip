@@ -3,10 +3,13 @@
 // One 64-lane wavefront per environment; see hrgym_device.h for the lane-role map.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <initializer_list>
+#include <limits>
 #include <memory>
 #include <string>
 #include <vector>

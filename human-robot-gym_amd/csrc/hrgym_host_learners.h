@@ -21,6 +21,93 @@ static void adam_bias_corrections(uint64_t steps, double& bc1, double& bc2) {
   bc2 = 1.0 - std::pow(0.999, t);
 }
 
+// ---- the hyper-parameter table of a population (csrc/hrgym_sac.h: SacHyper, csrc/hrgym_ppo.h: PpoHyper) ----
+// rows [n] into table[0 .. n) on `stream`, or rows[0] into every one of them (`same`): launches of hrg_hyper_rows_kernel, a chunk of rows each
+template <class Row> static int hyper_upload(Row* table, const Row* rows, int n, bool same, hipStream_t st) {
+  for (int first = 0; first < n; first += same ? n : MLP_HYPER_CHUNK) {
+    const int count = same ? n : std::min(n - first, (int)MLP_HYPER_CHUNK);
+    MlpHyperChunk<Row> c;
+    for (int i = 0; i < (same ? 1 : count); i++) c.rows[i] = rows[first + i];
+    hipLaunchKernelGGL(hrg_hyper_rows_kernel<Row>, dim3(((unsigned)count + 63) / 64), dim3(64), 0, st, table, first, count, c, same ? 1 : 0);
+  }
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+// What a handle keeps of its table on the host: whether the caller set the rows (hrg_*_population_set_hyper: the step's scalar arguments are not read any more), and
+// otherwise the row every member holds, written again by the step that is called with other scalars or on another stream than the one the last write was ordered on
+// (a handle's steps belong on one stream, as its scratch does; a step that moves to another stream must at least not read a table whose write it is not ordered behind).
+template <class Row> struct HyperTable {
+  Row* dev = nullptr;       // [n_members]
+  bool per_member = false;
+  bool filled = false;      // `uniform` is what the table holds, written on `stream`
+  Row uniform;
+  hipStream_t stream = nullptr;
+  int fill(const Row& row, int n, hipStream_t st) {
+    if (per_member || (filled && st == stream && std::memcmp(&row, &uniform, sizeof(Row)) == 0)) return HRG_OK;
+    if (int rc = hyper_upload(dev, &row, n, true, st)) return rc;
+    uniform = row;
+    stream = st;
+    filled = true;
+    return HRG_OK;
+  }
+  int set(const std::vector<Row>& rows, hipStream_t st) {
+    if (int rc = hyper_upload(dev, rows.data(), (int)rows.size(), false, st)) return rc;
+    per_member = true;
+    return HRG_OK;
+  }
+};
+
+// "<name>: set_hyper: member <p>: <what>"
+static int hyper_refuse(const char* name, int member, const std::string& what) {
+  return fail(HRG_ERR_INVALID, std::string(name) + ": set_hyper: member " + std::to_string(member) + ": " + what);
+}
+static std::string hyper_value(const char* field, double v) { return std::string(field) + " = " + std::to_string(v); }
+// the first of the named values that is not finite, or less than its lower bound `lo` (`open`: or equal to it), as "<field> = <value> must be ..."; "" when all pass
+struct HyperField { const char* name; double value, lo; bool open; };
+static std::string hyper_fields_refusal(std::initializer_list<HyperField> fields) {
+  for (const HyperField& f : fields) {
+    if (!std::isfinite(f.value)) return hyper_value(f.name, f.value) + " must be finite";
+    if (f.value < f.lo || (f.open && f.value == f.lo)) return hyper_value(f.name, f.value) + (f.open ? " must be greater than " : " must not be less than ") + std::to_string(f.lo);
+  }
+  return "";
+}
+
+// what hrg_sac_create checks of the descriptor's values and hrg_sac_population_set_hyper of a row's; "" or what is wrong
+static std::string sac_values_refusal(double gamma, double tau, double ent_coef, double target_entropy, int32_t auto_ent_coef) {
+  if (!std::isfinite(gamma) || !std::isfinite(tau) || !std::isfinite(ent_coef) || !std::isfinite(target_entropy))
+    return "gamma, tau, ent_coef and target_entropy must be finite";
+  if (!auto_ent_coef && ent_coef <= 0.0) return "a fixed ent_coef must be positive";
+  return "";
+}
+static SacHyper sac_hyper_row(double learning_rate, double gamma, double tau, double ent_coef, double target_entropy, int32_t auto_ent_coef) {
+  SacHyper r;
+  r.lr = learning_rate; r.tau = tau;
+  r.gamma = (float)gamma; r.alpha_fixed = (float)ent_coef; r.target_entropy = (float)target_entropy;
+  r.auto_alpha = auto_ent_coef ? 1 : 0;
+  return r;
+}
+
+// the same for hrg_ppo_create and hrg_ppo_population_set_hyper
+static std::string ppo_values_refusal(double ent_coef, double vf_coef, double max_grad_norm) {
+  if (!std::isfinite(ent_coef) || !std::isfinite(vf_coef) || !std::isfinite(max_grad_norm) || ent_coef < 0.0 || vf_coef < 0.0 || max_grad_norm <= 0.0)
+    return "ent_coef and vf_coef must be finite and not negative, max_grad_norm finite and positive";
+  return "";
+}
+// ... and of the scheduled values: hrg_ppo_step's arguments, a row's fields
+static std::string ppo_schedule_refusal(double learning_rate, double clip_range, double clip_range_vf) {
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return "learning_rate must be finite and not negative";
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return "clip_range must be finite and positive";
+  if (std::isnan(clip_range_vf)) return "clip_range_vf must be a number (negative: no clipping)";
+  return "";
+}
+static PpoHyper ppo_hyper_row(double learning_rate, double clip_range, double clip_range_vf, double ent_coef, double vf_coef, double max_grad_norm) {
+  PpoHyper r;
+  r.lr = learning_rate; r.clip_range = clip_range; r.clip_range_vf = clip_range_vf < 0.0 ? -1.0 : clip_range_vf;
+  r.ent_coef = (float)ent_coef; r.vf_coef = (float)vf_coef; r.max_grad_norm = (float)max_grad_norm;
+  return r;
+}
+
 extern "C" {
 
 // ---- SAC learner (csrc/hrgym_sac.h) ----
@@ -29,6 +116,7 @@ struct hrg_sac {
   hrg_sac_desc desc;
   int32_t n_members = 1;    // a population's members (csrc/hrgym_sac.h); the lone learner is the population of one
   SacDev d;
+  HyperTable<SacHyper> hyper;   // behind d.hyper
   uint64_t steps = 0;       // gradient steps so far: Adam's step count, the key of the step's draws, the phase of the target update
   uint64_t act_calls = 0;   // act calls that drew their noise
   DeviceMem mem;            // one allocation behind every pointer of `d`
@@ -66,9 +154,8 @@ int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const
   if (!seeds) return fail(HRG_ERR_INVALID, "sac: a population needs its seeds table (n_members values)");
   if (int rc = learner_shape("sac", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_SAC_MAX_BATCH)) return rc;
   if (desc->target_update_interval < 1) return fail(HRG_ERR_INVALID, "sac: target_update_interval must be positive");
-  if (!std::isfinite(desc->gamma) || !std::isfinite(desc->tau) || !std::isfinite(desc->ent_coef) || !std::isfinite(desc->target_entropy))
-    return fail(HRG_ERR_INVALID, "sac: gamma, tau, ent_coef and target_entropy must be finite");
-  if (!desc->auto_ent_coef && desc->ent_coef <= 0.0) return fail(HRG_ERR_INVALID, "sac: a fixed ent_coef must be positive");
+  const std::string why = sac_values_refusal(desc->gamma, desc->tau, desc->ent_coef, desc->target_entropy, desc->auto_ent_coef);
+  if (!why.empty()) return fail(HRG_ERR_INVALID, "sac: " + why);
   HIPCHK(hipSetDevice(device));
   std::unique_ptr<hrg_sac> h(new hrg_sac());
   h->device = device;
@@ -76,8 +163,6 @@ int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const
   h->n_members = n_members;
   SacDev& d = h->d;
   d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE;
-  d.auto_alpha = desc->auto_ent_coef ? 1 : 0;
-  d.gamma = (float)desc->gamma; d.alpha_fixed = (float)desc->ent_coef; d.target_entropy = (float)desc->target_entropy;
   const size_t M = (size_t)n_members, P = (size_t)sac_layout(*desc, d), B = (size_t)d.B, A = (size_t)d.A;   // (the pieces: sac_member)
   Carver<float> f;
   f.take(d.all.a_pi, M * B * A);
@@ -90,7 +175,8 @@ int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const
   f.take(d.all.grad, M * P);
   f.take(d.all.loss_part, M * (size_t)d.tiles * SAC_NLOSS);
   f.take(d.all.losses, M * 4);
-  if (!f.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M)) return nomem("sac", h->mem);
+  if (!f.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M) || !h->mem.zeros(h->hyper.dev, M)) return nomem("sac", h->mem);
+  d.hyper = h->hyper.dev;   // (filled by the first step, or by hrg_sac_population_set_hyper)
   HIPCHK(hipDeviceSynchronize());
   *out = h.release();
   return HRG_OK;
@@ -120,10 +206,12 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
                  void* stream) {
   if (!h || !observations_dev || !actions_dev || !next_observations_dev || !dones_dev || !rewards_dev || !params_dev || !adam_m_dev || !adam_v_dev || !target_dev)
     return fail(HRG_ERR_INVALID, "null argument");
-  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "sac: learning_rate must be finite and not negative");
+  if (!h->hyper.per_member && (!std::isfinite(learning_rate) || learning_rate < 0.0)) return fail(HRG_ERR_INVALID, "sac: learning_rate must be finite and not negative");
   HIPCHK(hipSetDevice(h->device));
   const SacDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
+  const hrg_sac_desc& c = h->desc;
+  if (int rc = h->hyper.fill(sac_hyper_row(learning_rate, c.gamma, c.tau, c.ent_coef, c.target_entropy, c.auto_ent_coef), h->n_members, st)) return rc;
   const unsigned members = (unsigned)h->n_members;
   const dim3 pair((unsigned)d.tiles, 2, members), block(MLP_BLOCK);
   double bc1, bc2;
@@ -134,11 +222,11 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
                      rewards_dev, eps_pi_dev, eps_next_dev, h->steps);
   hipLaunchKernelGGL(hrg_sac_critic_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev);
   hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)n_crit2 + MLP_BLOCK - 1) / MLP_BLOCK, 1, members), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, (int)d.n_actor,
-                     (int)(d.n_actor + n_crit2), learning_rate, bc1, bc2, polyak ? target_dev : (float*)nullptr, h->desc.tau, 0);
+                     (int)(d.n_actor + n_crit2), bc1, bc2, polyak ? target_dev : (float*)nullptr, 0);
   hipLaunchKernelGGL(hrg_sac_actor_q_kernel, pair, block, 0, st, d, (const float*)params_dev, observations_dev);
   hipLaunchKernelGGL(hrg_sac_actor_kernel, dim3((unsigned)d.tiles, 1, members), block, 0, st, d, (const float*)params_dev, observations_dev, eps_pi_dev, h->steps);
   hipLaunchKernelGGL(hrg_sac_adam_kernel, dim3(((unsigned)d.n_actor + MLP_BLOCK - 1) / MLP_BLOCK, 1, members), block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, 0, (int)d.n_actor,
-                     learning_rate, bc1, bc2, (float*)nullptr, 0.0, 1);
+                     bc1, bc2, (float*)nullptr, 1);
   HIPCHK(hipGetLastError());
   h->steps++;
   return HRG_OK;
@@ -170,6 +258,26 @@ int hrg_sac_population_export(hrg_sac* h, int32_t member, float* y_host, float* 
                                    {q_host, d.all.q + m * SAC_NQ * B, SAC_NQ * B}, {grad_host, d.all.grad + m * P, P}, {losses_host, d.all.losses + m * 4, 4}});
 }
 
+int hrg_sac_population_set_hyper(hrg_sac* h, const hrg_sac_hyper* rows_host, int32_t n_members, void* stream) {
+  if (!h || !rows_host) return fail(HRG_ERR_INVALID, "sac: set_hyper: null argument");
+  if (n_members != h->n_members)
+    return fail(HRG_ERR_INVALID, "sac: set_hyper: n_members = " + std::to_string(n_members) + ", the handle has " + std::to_string(h->n_members) + " members");
+  std::vector<SacHyper> rows;
+  for (int p = 0; p < n_members; p++) {   // every row, before anything is written
+    const hrg_sac_hyper& r = rows_host[p];
+    const double inf = -std::numeric_limits<double>::infinity();
+    std::string why = hyper_fields_refusal({{"learning_rate", r.learning_rate, 0.0, false}, {"gamma", r.gamma, 0.0, false}, {"tau", r.tau, 0.0, false},
+                                            {"ent_coef", r.ent_coef, r.auto_ent_coef ? inf : 0.0, !r.auto_ent_coef}, {"target_entropy", r.target_entropy, inf, false}});
+    if (why.empty()) why = sac_values_refusal(r.gamma, r.tau, r.ent_coef, r.target_entropy, r.auto_ent_coef);   // (what hrg_sac_create refuses is refused above, by field)
+    if (why.empty() && r.gamma > 1.0) why = hyper_value("gamma", r.gamma) + " outside [0, 1]";
+    if (why.empty() && r.tau > 1.0) why = hyper_value("tau", r.tau) + " outside [0, 1]";
+    if (!why.empty()) return hyper_refuse("sac", p, why);
+    rows.push_back(sac_hyper_row(r.learning_rate, r.gamma, r.tau, r.ent_coef, r.target_entropy, r.auto_ent_coef));
+  }
+  HIPCHK(hipSetDevice(h->device));
+  return h->hyper.set(rows, (hipStream_t)stream);
+}
+
 int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host) {
   return hrg_sac_population_export(h, 0, y_host, logp_host, logp_next_host, q_host, grad_host, losses_host);
 }
@@ -180,6 +288,7 @@ struct hrg_ppo {
   hrg_ppo_desc desc;
   int32_t n_members = 1;        // a population's members (csrc/hrgym_ppo.h); the lone learner is the population of one
   PpoDev d;
+  HyperTable<PpoHyper> hyper;   // behind d.hyper
   uint64_t steps = 0;           // minibatch steps so far: Adam's step count
   uint64_t forward_calls = 0;   // forward calls that drew their noise
   int n_blocks = 0;             // blocks of 256 parameters
@@ -216,9 +325,8 @@ int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const
   if (desc->rollout_size < 0 || desc->rollout_size % desc->batch_size)
     return fail(HRG_ERR_UNSUPPORTED, "ppo: rollout_size = " + std::to_string(desc->rollout_size) + " is not divisible by batch_size = " + std::to_string(desc->batch_size) +
                                          ": the learner takes no short last minibatch");
-  if (!std::isfinite(desc->ent_coef) || !std::isfinite(desc->vf_coef) || !std::isfinite(desc->max_grad_norm) || desc->ent_coef < 0.0 || desc->vf_coef < 0.0 ||
-      desc->max_grad_norm <= 0.0)
-    return fail(HRG_ERR_INVALID, "ppo: ent_coef and vf_coef must be finite and not negative, max_grad_norm finite and positive");
+  const std::string why = ppo_values_refusal(desc->ent_coef, desc->vf_coef, desc->max_grad_norm);
+  if (!why.empty()) return fail(HRG_ERR_INVALID, "ppo: " + why);
   HIPCHK(hipSetDevice(device));
   std::unique_ptr<hrg_ppo> h(new hrg_ppo());
   h->device = device;
@@ -228,7 +336,6 @@ int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const
   d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_PPO_TILE;
   d.nets = desc->separate ? 2 : 1;
   d.normalize = desc->normalize_advantage ? 1 : 0;
-  d.ent_coef = (float)desc->ent_coef; d.vf_coef = (float)desc->vf_coef; d.max_grad_norm = (float)desc->max_grad_norm;
   const size_t M = (size_t)n_members, P = (size_t)ppo_layout(*desc, d), B = (size_t)d.B;   // (the pieces: ppo_member)
   h->n_blocks = (int)((P + MLP_BLOCK - 1) / MLP_BLOCK);
   Carver<float> f;
@@ -242,7 +349,8 @@ int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const
   Carver<double> dbl;
   dbl.take(d.all.adv_stat, M * 2);
   dbl.take(d.all.block_sq, M * (size_t)h->n_blocks);
-  if (!f.alloc(h->mem) || !dbl.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M)) return nomem("ppo", h->mem);
+  if (!f.alloc(h->mem) || !dbl.alloc(h->mem) || !h->mem.upload(d.seeds, seeds, M) || !h->mem.zeros(h->hyper.dev, M)) return nomem("ppo", h->mem);
+  d.hyper = h->hyper.dev;   // (filled by the first step, or by hrg_ppo_population_set_hyper)
   HIPCHK(hipDeviceSynchronize());
   *out = h.release();
   return HRG_OK;
@@ -272,21 +380,24 @@ int hrg_ppo_step(hrg_ppo* h, const float* observations_dev, const float* actions
                  double clip_range_vf, void* stream) {
   if (!h || !observations_dev || !actions_dev || !old_values_dev || !old_log_prob_dev || !advantages_dev || !returns_dev || !params_dev || !adam_m_dev || !adam_v_dev)
     return fail(HRG_ERR_INVALID, "null argument");
-  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "ppo: learning_rate must be finite and not negative");
-  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(HRG_ERR_INVALID, "ppo: clip_range must be finite and positive");
-  if (std::isnan(clip_range_vf)) return fail(HRG_ERR_INVALID, "ppo: clip_range_vf must be a number (negative: no clipping)");
+  if (!h->hyper.per_member) {
+    const std::string why = ppo_schedule_refusal(learning_rate, clip_range, clip_range_vf);
+    if (!why.empty()) return fail(HRG_ERR_INVALID, "ppo: " + why);
+  }
   HIPCHK(hipSetDevice(h->device));
   const PpoDev& d = h->d;
   hipStream_t st = (hipStream_t)stream;
+  const hrg_ppo_desc& c = h->desc;
+  if (int rc = h->hyper.fill(ppo_hyper_row(learning_rate, clip_range, clip_range_vf, c.ent_coef, c.vf_coef, c.max_grad_norm), h->n_members, st)) return rc;
   const unsigned members = (unsigned)h->n_members;
   const dim3 block(MLP_BLOCK), flat((unsigned)h->n_blocks, 1, members);
   double bc1, bc2;
   adam_bias_corrections(h->steps, bc1, bc2);   // by the optimiser's step count
   if (d.normalize) hipLaunchKernelGGL(hrg_ppo_adv_kernel, dim3(1, 1, members), block, 0, st, d, advantages_dev);
   hipLaunchKernelGGL(hrg_ppo_grad_kernel, dim3((unsigned)d.tiles, (unsigned)d.nets, members), block, 0, st, d, (const float*)params_dev, observations_dev, actions_dev, old_values_dev,
-                     old_log_prob_dev, advantages_dev, returns_dev, clip_range, clip_range_vf < 0.0 ? -1.0 : clip_range_vf);
+                     old_log_prob_dev, advantages_dev, returns_dev);
   hipLaunchKernelGGL(hrg_ppo_reduce_kernel, flat, block, 0, st, d);
-  hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, learning_rate, bc1, bc2);
+  hipLaunchKernelGGL(hrg_ppo_adam_kernel, flat, block, 0, st, d, params_dev, adam_m_dev, adam_v_dev, h->n_blocks, bc1, bc2);
   HIPCHK(hipGetLastError());
   h->steps++;
   return HRG_OK;
@@ -321,6 +432,25 @@ int hrg_ppo_population_export(hrg_ppo* h, int32_t member, float* values_host, fl
   const size_t m = (size_t)member, B = (size_t)d.B, P = (size_t)d.n_params;   // (the pieces: ppo_member)
   return export_floats(h->device, {{values_host, d.all.values + m * B, B}, {log_prob_host, d.all.logp + m * B, B}, {ratio_host, d.all.ratio + m * B, B},
                                    {grad_host, d.all.grad + m * P, P}, {diag_host, d.all.diag + m * HRG_PPO_NDIAG, HRG_PPO_NDIAG}});
+}
+
+int hrg_ppo_population_set_hyper(hrg_ppo* h, const hrg_ppo_hyper* rows_host, int32_t n_members, void* stream) {
+  if (!h || !rows_host) return fail(HRG_ERR_INVALID, "ppo: set_hyper: null argument");
+  if (n_members != h->n_members)
+    return fail(HRG_ERR_INVALID, "ppo: set_hyper: n_members = " + std::to_string(n_members) + ", the handle has " + std::to_string(h->n_members) + " members");
+  std::vector<PpoHyper> rows;
+  for (int p = 0; p < n_members; p++) {   // every row, before anything is written
+    const hrg_ppo_hyper& r = rows_host[p];
+    std::string why = hyper_fields_refusal({{"learning_rate", r.learning_rate, 0.0, false}, {"clip_range", r.clip_range, 0.0, true}, {"ent_coef", r.ent_coef, 0.0, false},
+                                            {"vf_coef", r.vf_coef, 0.0, false}, {"max_grad_norm", r.max_grad_norm, 0.0, true}});
+    if (why.empty() && std::isnan(r.clip_range_vf)) why = hyper_value("clip_range_vf", r.clip_range_vf) + " must be a number (negative: no clipping)";
+    if (why.empty()) why = ppo_schedule_refusal(r.learning_rate, r.clip_range, r.clip_range_vf);   // (what hrg_ppo_step and hrg_ppo_create refuse is refused above, by field)
+    if (why.empty()) why = ppo_values_refusal(r.ent_coef, r.vf_coef, r.max_grad_norm);
+    if (!why.empty()) return hyper_refuse("ppo", p, why);
+    rows.push_back(ppo_hyper_row(r.learning_rate, r.clip_range, r.clip_range_vf, r.ent_coef, r.vf_coef, r.max_grad_norm));
+  }
+  HIPCHK(hipSetDevice(h->device));
+  return h->hyper.set(rows, (hipStream_t)stream);
 }
 
 int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host) {

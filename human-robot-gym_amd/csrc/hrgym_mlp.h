@@ -196,3 +196,15 @@ DI float mlp_adam(float* __restrict__ P, float* __restrict__ M, float* __restric
   P[i] = p;
   return p;
 }
+
+// The rows of a population's hyper-parameter table (hrgym_sac.h: SacHyper, hrgym_ppo.h: PpoHyper) written from the launch's arguments, so that the upload is one
+// more launch on the learner's stream: behind the steps queued there, ahead of the next, with no host memory the device reads later.  table[first + i] = c.rows[i]
+// for i < count, or c.rows[0] in every one of them (`same`: the lone learner and the population whose members share their values).  One thread per row.
+#define MLP_HYPER_CHUNK 16
+template <class Row> struct MlpHyperChunk {
+  Row rows[MLP_HYPER_CHUNK];
+};
+template <class Row> __global__ __launch_bounds__(64) void hrg_hyper_rows_kernel(Row* __restrict__ table, int first, int count, const MlpHyperChunk<Row> c, int same) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < count) table[first + i] = c.rows[same ? 0 : i % MLP_HYPER_CHUNK];
+}

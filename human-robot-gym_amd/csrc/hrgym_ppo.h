@@ -32,15 +32,25 @@
 //
 // Draws of the forward pass: rng_gauss keyed by (learner seed, forward call count, row, STREAM_PPO_ACT, component); none depends on the grid.
 //
-// A population is n_members learners of one descriptor that differ in their seed and step in the same four launches: blockIdx.z = p is the member.
+// A population is n_members learners of one shape that step in the same four launches: blockIdx.z = p is the member.  They differ in their seed
+// and, where the caller set them (hrg_ppo_population_set_hyper), in their row of the hyper-parameter table: learning rate, the two clip ranges, ent_coef, vf_coef,
+// max_grad_norm (PpoHyper).  A kernel reads its member's row once per workgroup, an address every lane shares, and uses the values as the lone learner does.
 // Parameters and moments are [P][n_params], the batch arrays [P][B][.], every piece of the handle's scratch has a member stride (ppo_member), the seeds are a [P]
 // table.  The counters are the handle's: members step in lockstep.  A member's advantage statistics, clip coefficient and diagnostics come from its own sums, its
-// draws are keyed by its own seed and the row's index in its group of rows: member p is, bit for bit, the lone learner of seed p on batch p.  The lone learner is
+// draws are keyed by its own seed and the row's index in its group of rows: member p is, bit for bit, the lone learner of seed p and row p on batch p.  The lone learner is
 // the population of one member.
 #pragma once
 
 enum { STREAM_PPO_ACT = 14 };   // after STREAM_SAC_ACT = 13 (hrgym_sac.h)
 #define PPO_NPART 6   // per tile: sum of -min(.,.), of (ratio - 1) - log ratio, of [|ratio - 1| > c], of (return - vpred)^2; a row's entropy; mean_j exp(log_std_j)
+
+// a member's row of the handle's hyper-parameter table (include/hrgym.h: hrg_ppo_hyper, in the types the kernels compute with)
+struct PpoHyper {
+  double lr = 0.0, clip_range = 0.0, clip_range_vf = -1.0;   // (negative: the value function is not clipped)
+  float ent_coef = 0.0f, vf_coef = 0.0f, max_grad_norm = 0.0f;
+  int32_t reserved = 0;   // (no padding: the host compares rows as bytes)
+};
+static_assert(sizeof(PpoHyper) == 40, "no padding in a row of the PPO hyper-parameter table");
 
 // a member's pieces of the scratch the handle owns
 struct PpoScratch {
@@ -59,7 +69,7 @@ struct PpoScratch {
 struct PpoDev {
   int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, nets = 0, normalize = 0;
   int32_t w[2][HRG_PPO_MAX_DEPTH] = {{0}}, b[2][HRG_PPO_MAX_DEPTH] = {{0}}, hw = 0, hb = 0, ls = 0;   // the networks' layers; the heads' [A + 1][64] weights and [A + 1] biases; log_std
-  float ent_coef = 0.0f, vf_coef = 0.0f, max_grad_norm = 0.0f;
+  const PpoHyper* hyper = nullptr;   // [P] the members' hyper-parameters
   const uint64_t* seeds = nullptr;   // [P] the members' seeds
   PpoScratch all;                    // the scratch of every member, [P] pieces of each array: member 0's pointers
 };
@@ -132,11 +142,13 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adv_kernel(const PpoDev h, 
 // ---- 2: network blockIdx.y of member blockIdx.z on the tile: forward, the rows' losses and their gradients at the heads, backward
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h, const float* __restrict__ P, const float* __restrict__ obs, const float* __restrict__ act,
                                                                  const float* __restrict__ old_values, const float* __restrict__ old_logp, const float* __restrict__ adv,
-                                                                 const float* __restrict__ returns, double clip_range, double clip_range_vf) {
+                                                                 const float* __restrict__ returns) {
   __shared__ MlpLds s;
   const int row0 = (int)blockIdx.x * MLP_T, net = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
   const PpoScratch m = ppo_member(h, p);
+  const PpoHyper hy = h.hyper[p];
+  const double clip_range = hy.clip_range, clip_range_vf = hy.clip_range_vf;
   const size_t B = (size_t)h.B;
   P = mlp_rows(P, p, (size_t)h.n_params); obs = mlp_rows(obs, p, B * K); act = mlp_rows(act, p, B * A);
   old_values = mlp_rows(old_values, p, B); old_logp = mlp_rows(old_logp, p, B); adv = mlp_rows(adv, p, B); returns = mlp_rows(returns, p, B);
@@ -156,7 +168,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
       const double vp = clip ? (double)ov + fmin(fmax(dv, -clip_range_vf), clip_range_vf) : (double)v, d = vp - (double)returns[i];
       m.values[i] = v;
       s.row[3][r] = (float)(d * d);
-      s.D[r * MLP_DLD + hd.vcol] = pass ? (float)((double)h.vf_coef * 2.0 * d * inv_b) : 0.0f;
+      s.D[r * MLP_DLD + hd.vcol] = pass ? (float)((double)hy.vf_coef * 2.0 * d * inv_b) : 0.0f;
     }
     if (hd.pol) {
       double lp = 0.0;
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_grad_kernel(const PpoDev h,
       for (int j = 0; j < A; j++) {
         const double ls = (double)P[h.ls + j], iv = exp(-2.0 * ls), d = (double)act[(size_t)i * A + j] - (double)s.D[r * MLP_DLD + j];
         s.D[r * MLP_DLD + j] = (float)(g * d * iv);                                          // ... / d mu_j
-        s.std[r * 8 + j] = (float)(g * (d * d * iv - 1.0) - (double)h.ent_coef * inv_b);     // ... / d log_std_j, with the entropy bonus's share of the row
+        s.std[r * 8 + j] = (float)(g * (d * d * iv - 1.0) - (double)hy.ent_coef * inv_b);     // ... / d log_std_j, with the entropy bonus's share of the row
       }
       m.logp[i] = (float)lp;
       m.ratio[i] = (float)ratio;
@@ -230,14 +242,16 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_reduce_kernel(const PpoDev 
 
 // ---- 4: clip_grad_norm_ over all parameters, torch's Adam (eps 1e-5) in double, rounded once into the float32 parameter; thread 0 of block 0: the diagnostics.
 // Grid (blocks, 1, members): the norm, the coefficient and the tail are the member's own.
-__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int n_blocks, double lr,
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int n_blocks,
                                                                  double bc1, double bc2) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), p = (int)blockIdx.z;
   const PpoScratch own = ppo_member(h, p);   // (`m` is Adam's first moment below)
+  const PpoHyper hy = h.hyper[p];
+  const double lr = hy.lr;
   P = mlp_rows(P, p, (size_t)h.n_params); M = mlp_rows(M, p, (size_t)h.n_params); V = mlp_rows(V, p, (size_t)h.n_params);
   double sq = 0.0;
   for (int b = 0; b < n_blocks; b++) sq += own.block_sq[b];
-  const double norm = sqrt(sq), coef = fmin(1.0, (double)h.max_grad_norm / (norm + 1e-6));
+  const double norm = sqrt(sq), coef = fmin(1.0, (double)hy.max_grad_norm / (norm + 1e-6));
   if (i < h.n_params) {   // (mlp_adam's update written out: through the helper the compiler contracts v's products the other way round, a different rounding)
     const double gd = (double)own.grad[i] * coef, m = 0.9 * (double)M[i] + 0.1 * gd, v = 0.999 * (double)V[i] + 0.001 * gd * gd;
     P[i] = (float)((double)P[i] - lr * (m / bc1) / (sqrt(v / bc2) + 1e-5));
@@ -252,7 +266,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_ppo_adam_kernel(const PpoDev h,
     own.diag[0] = (float)pl;                                                  // policy_gradient_loss
     own.diag[1] = (float)vl;                                                  // value_loss
     own.diag[2] = (float)el;                                                  // entropy_loss
-    own.diag[3] = (float)(pl + (double)h.ent_coef * el + (double)h.vf_coef * vl);   // loss
+    own.diag[3] = (float)(pl + (double)hy.ent_coef * el + (double)hy.vf_coef * vl);   // loss
     own.diag[4] = (float)(sum[1] * inv_b);                                    // approx_kl
     own.diag[5] = (float)(sum[2] * inv_b);                                    // clip_fraction
     own.diag[6] = own.loss_part[5];                                             // std

@@ -29,16 +29,26 @@
 // Draws: rng_gauss keyed by (learner seed, gradient step count, batch row, STREAM_SAC, component), component j for eps_pi and HRG_ACT_DIM + j for eps_next; the
 // act kernel by (seed, act call count, row, STREAM_SAC_ACT, j).  None depends on the grid.
 //
-// A population is n_members learners of one descriptor that differ in their seed and step in the same six launches: blockIdx.z = p is the member
-// (the act kernel: blockIdx.y).  Parameters, moments and targets are [P][n_params] and [P][2 n_critic], the batch arrays [P][B][.], every piece of the handle's
+// A population is n_members learners of one shape that step in the same six launches: blockIdx.z = p is the member (the act kernel:
+// blockIdx.y).  They differ in their seed and, where the caller set them (hrg_sac_population_set_hyper), in their row of the hyper-parameter table: learning rate,
+// gamma, tau, target entropy, the entropy coefficient's fixed value and whether it is learned (SacHyper).  A kernel reads its member's row once per workgroup, an
+// address every lane shares, and uses the values as the lone learner does: the same types, the same order.  Parameters, moments and targets are [P][n_params] and [P][2 n_critic], the batch arrays [P][B][.], every piece of the handle's
 // scratch has a member stride (sac_member), the seeds are a [P] table.  The counters are the handle's: members step in lockstep.  A member's draws are keyed by its
 // own seed and the row's index in its own batch (the act kernel: in its group of rows), its sums are its own: member p is, bit for bit, the lone learner of seed p
-// on batch p.  The lone learner is the population of one member.
+// and row p on batch p.  The lone learner is the population of one member.
 #pragma once
 
 enum { STREAM_SAC = 12, STREAM_SAC_ACT = 13 };   // after STREAM_REPLAY = 11 (hrgym_replay.h)
 #define SAC_NQ HRG_SAC_NQ   // Q columns kept for the export: Q1, Q2 on (obs, act); Q1t, Q2t on (next_obs, a'); Q1, Q2 (updated) on (obs, a_pi)
 #define SAC_NLOSS 4       // per tile: sum (Q1 - y)^2, sum (Q2 - y)^2, sum (alpha logp - min Q), sum logp
+
+// a member's row of the handle's hyper-parameter table (include/hrgym.h: hrg_sac_hyper, in the types the kernels compute with)
+struct SacHyper {
+  double lr = 0.0, tau = 0.0;
+  float gamma = 0.0f, alpha_fixed = 0.0f, target_entropy = 0.0f;
+  int32_t auto_alpha = 0;
+};
+static_assert(sizeof(SacHyper) == 32, "no padding in a row of the SAC hyper-parameter table: the host compares rows as bytes");
 
 // a member's seed and its pieces of the scratch the handle owns
 struct SacScratch {
@@ -57,10 +67,10 @@ struct SacScratch {
 
 // one hrg_sac: sizes, offsets into the parameter vector, the scratch it owns; passed to the kernels by value
 struct SacDev {
-  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, n_actor = 0, n_critic = 0, auto_alpha = 0;
+  int32_t K = 0, A = 0, depth = 0, B = 0, tiles = 0, n_params = 0, n_actor = 0, n_critic = 0;
   int32_t a_w[HRG_SAC_MAX_DEPTH] = {0}, a_b[HRG_SAC_MAX_DEPTH] = {0}, a_hw = 0, a_hb = 0;   // actor: hidden layers, the heads' [2A][64] weights and [2A] biases
   int32_t q_w[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_b[2][HRG_SAC_MAX_DEPTH] = {{0}}, q_ow[2] = {0}, q_ob[2] = {0};
-  float gamma = 0.0f, alpha_fixed = 0.0f, target_entropy = 0.0f;
+  const SacHyper* hyper = nullptr;   // [P] the members' hyper-parameters
   const uint64_t* seeds = nullptr;   // [P] the members' seeds
   SacScratch all;                    // the scratch of every member, [P] pieces of each array: member 0's pointers (`seed` is not used)
 };
@@ -101,7 +111,7 @@ DI void sac_squash(MlpLds& s, int A) {
   }
 }
 
-DI float sac_alpha(const SacDev& h, const float* __restrict__ P) { return h.auto_alpha ? expf(P[h.n_params - 1]) : h.alpha_fixed; }
+DI float sac_alpha(const SacDev& h, const SacHyper& hy, const float* __restrict__ P) { return hy.auto_alpha ? expf(P[h.n_params - 1]) : hy.alpha_fixed; }
 
 // ---- 1: the actor on obs (blockIdx.y = 0); the actor on next_obs and the targets (blockIdx.y = 1)
 __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev h, const float* __restrict__ P, const float* __restrict__ PT, const float* __restrict__ obs,
@@ -111,6 +121,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev 
   const int row0 = (int)blockIdx.x * MLP_T, next = (int)blockIdx.y, p = (int)blockIdx.z, K = h.K, A = h.A;
   if (row0 >= h.B) return;   // (uniform over the workgroup)
   const SacScratch m = sac_member(h, p);
+  const SacHyper hy = h.hyper[p];
   const size_t B = (size_t)h.B;
   P = mlp_rows_or_null(P, p, (size_t)h.n_params); PT = mlp_rows_or_null(PT, p, 2 * (size_t)h.n_critic);
   obs = mlp_rows_or_null(obs, p, B * K); nobs = mlp_rows_or_null(nobs, p, B * K); dones = mlp_rows_or_null(dones, p, B); rewards = mlp_rows_or_null(rewards, p, B);
@@ -137,13 +148,13 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_policy_kernel(const SacDev 
     for (int r = t; r < MLP_T; r += (int)blockDim.x) s.row[1 + c][r] = s.D[r * MLP_DLD];
     __syncthreads();
   }
-  const float alpha = sac_alpha(h, P);
+  const float alpha = sac_alpha(h, hy, P);
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const float q1 = s.row[1][r], q2 = s.row[2][r], lp = s.row[3][r];
     m.q[2 * h.B + row0 + r] = q1;
     m.q[3 * h.B + row0 + r] = q2;
     m.logp_next[row0 + r] = lp;
-    m.y[row0 + r] = rewards[row0 + r] + (1.0f - dones[row0 + r]) * h.gamma * (fminf(q1, q2) - alpha * lp);
+    m.y[row0 + r] = rewards[row0 + r] + (1.0f - dones[row0 + r]) * hy.gamma * (fminf(q1, q2) - alpha * lp);
   }
 }
 
@@ -201,6 +212,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h
   const int row0 = (int)blockIdx.x * MLP_T, p = (int)blockIdx.z, K = h.K, A = h.A, t = (int)threadIdx.x;
   if (row0 >= h.B) return;
   const SacScratch m = sac_member(h, p);
+  const SacHyper hy = h.hyper[p];
   P = mlp_rows_or_null(P, p, (size_t)h.n_params); obs = mlp_rows_or_null(obs, p, (size_t)h.B * K); eps_pi = mlp_rows_or_null(eps_pi, p, (size_t)h.B * A);
   mlp_load(s, obs, K, 0, row0, h.B);
   mlp_noise(s, eps_pi, A, row0, h.B, m.seed, count, STREAM_SAC, 0);
@@ -208,7 +220,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h
   mlp_head(s, P, h.a_hw, h.a_hb, h.depth, 2 * A);
   sac_squash(s, A);
   __syncthreads();
-  const float alpha = sac_alpha(h, P), inv_b = 1.0f / (float)h.B;
+  const float alpha = sac_alpha(h, hy, P), inv_b = 1.0f / (float)h.B;
   for (int r = t; r < MLP_T; r += (int)blockDim.x) {
     const float q1 = m.q[4 * h.B + row0 + r], q2 = m.q[5 * h.B + row0 + r];
     const float* dq = m.dqda + ((size_t)(q1 <= q2 ? 0 : 1) * h.B + row0 + r) * A;
@@ -236,10 +248,13 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_actor_kernel(const SacDev h
 // ---- 3 and 6: parameters [lo, hi): the gradient (the tiles' parts in tile order), torch's Adam with eps 1e-8 (mlp_adam).  `target` non-null: target[i - lo] <-
 // (1 - tau) target + tau param, the polyak update of the critics (lo = n_actor).  `coef` (the actor's launch): thread 0 of block 0 also sums the losses and, when
 // the coefficient is learned, takes its gradient -mean(logp + target_entropy) and its Adam step.  Grid (blocks of [lo, hi), 1, members): the tail runs once per member.
-__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int lo, int hi, double lr,
-                                                                 double bc1, double bc2, float* __restrict__ target, double tau, int coef) {
+// The learning rate and tau are the member's (SacHyper).
+__global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h, float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int lo, int hi,
+                                                                 double bc1, double bc2, float* __restrict__ target, int coef) {
   const int i = lo + (int)(blockIdx.x * blockDim.x + threadIdx.x), p = (int)blockIdx.z;
   const SacScratch m = sac_member(h, p);
+  const SacHyper hy = h.hyper[p];
+  const double lr = hy.lr, tau = hy.tau;
   P = mlp_rows_or_null(P, p, (size_t)h.n_params); M = mlp_rows_or_null(M, p, (size_t)h.n_params); V = mlp_rows_or_null(V, p, (size_t)h.n_params);
   target = mlp_rows_or_null(target, p, 2 * (size_t)h.n_critic);
   if (i < hi) {
@@ -259,13 +274,13 @@ __global__ __launch_bounds__(MLP_BLOCK) void hrg_sac_adam_kernel(const SacDev h,
     }
     const double inv_b = 1.0 / (double)h.B;
     const int ia = h.n_params - 1;
-    const float mean_lp = (float)(lp * inv_b + (double)h.target_entropy);   // mean(logp + target_entropy)
+    const float mean_lp = (float)(lp * inv_b + (double)hy.target_entropy);   // mean(logp + target_entropy)
     m.losses[0] = (float)(la * inv_b);
     m.losses[1] = (float)(0.5 * (sq1 + sq2) * inv_b);
-    m.losses[2] = h.auto_alpha ? -P[ia] * mean_lp : 0.0f;
-    m.losses[3] = h.auto_alpha ? expf(P[ia]) : h.alpha_fixed;
+    m.losses[2] = hy.auto_alpha ? -P[ia] * mean_lp : 0.0f;
+    m.losses[3] = hy.auto_alpha ? expf(P[ia]) : hy.alpha_fixed;
     m.grad[ia] = 0.0f;
-    if (h.auto_alpha) {
+    if (hy.auto_alpha) {
       const float g = -mean_lp;
       m.grad[ia] = g;
       mlp_adam(P, M, V, ia, (double)g, lr, bc1, bc2, 1e-8);

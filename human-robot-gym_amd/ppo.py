@@ -23,8 +23,9 @@ import math
 
 import numpy as np
 
-from ._cstruct import CONST, PpoDesc
-from ._learner import MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries
+from ._cstruct import CONST, PpoDesc, PpoHyper
+from ._learner import (MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries,  # noqa: F401 (MAX_POPULATION: importable from here)
+                       refuse_shared_sequences, scheduled_attribute)
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_PPO_HIDDEN"]
@@ -195,14 +196,19 @@ class PpoLearner(Learner):
         """One minibatch step on `batch`, a RolloutBufferSamples of `batch_size` rows (observations [B, obs_dim], actions [B, act_dim], old_values,
         old_log_prob, advantages, returns [B]).  A population takes its members' minibatches one behind the other, [P * B] rows."""
         B, K, A, p = self.n_members * self.batch_size, self.obs_dim, self.act_dim, self.p
-        if self.clip_range_vf is not None and not self.clip_range_vf > 0.0:
-            raise ValueError(f"clip_range_vf = {self.clip_range_vf} must be positive (None: no clipping)")
+        lr, clip, clip_vf = self._step_scalars()
+        if clip_vf is not None and not clip_vf > 0.0:
+            raise ValueError(f"clip_range_vf = {clip_vf} must be positive (None: no clipping)")
         args = (self._tensor(batch.observations, (B, K), "observations"), self._tensor(batch.actions, (B, A), "actions"), self._tensor(batch.old_values, (B,), "old_values"),
                 self._tensor(batch.old_log_prob, (B,), "old_log_prob"), self._tensor(batch.advantages, (B,), "advantages"), self._tensor(batch.returns, (B,), "returns"))
         with self.torch.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_ppo_step(self.h, *args, _ptr(p.params), _ptr(p.adam_m), _ptr(p.adam_v), float(self.learning_rate), float(self.clip_range),
-                                                         -1.0 if self.clip_range_vf is None else float(self.clip_range_vf), self._stream()))
+            self._check(self.lib, self.lib.hrg_ppo_step(self.h, *args, _ptr(p.params), _ptr(p.adam_m), _ptr(p.adam_v), float(lr), float(clip),
+                                                         -1.0 if clip_vf is None else float(clip_vf), self._stream()))
         self._keep = batch
+
+    def _step_scalars(self):
+        """learning_rate, clip_range, clip_range_vf as `step` passes them."""
+        return self.learning_rate, self.clip_range, self.clip_range_vf
 
     def train(self, rollout):
         """PPO.train: `n_epochs` x (rollout.get(batch_size) -> step), with no copy to the host and no synchronisation.  batch_size must divide the buffer's
@@ -254,9 +260,9 @@ class PpoLearner(Learner):
         diag = np.zeros(NDIAG, np.float32)
         self._export(None, None, None, None, diag, **which)
         out = dict(zip(DIAG_KEYS, (float(x) for x in diag)))
-        out.update(clip_range=self.clip_range, learning_rate=self.learning_rate, n_updates=self.n_updates)
-        if self.clip_range_vf is not None:
-            out["clip_range_vf"] = self.clip_range_vf
+        out.update(clip_range=self._scalar("clip_range", **which), learning_rate=self._scalar("learning_rate", **which), n_updates=self.n_updates)
+        if self._scalar("clip_range_vf", **which) is not None:
+            out["clip_range_vf"] = self._scalar("clip_range_vf", **which)
         return out
 
 
@@ -269,11 +275,14 @@ class PpoPopulationParams(PopulationParams):
 
 
 class PpoPopulation(Population, PpoLearner):
-    """`n_members` PPO learners of the same shapes and hyper-parameters (PpoLearner's keywords) that differ in their seed only and take their minibatch step
-    in the same four launches (csrc/hrgym_ppo.h): the seeds of one cell of a study, side by side on one GPU.  The batch of n = P m envs is P
-    groups of m consecutive envs; member p acts in, and learns from, group p only.  The counters are shared, and so are learning_rate, clip_range and
-    clip_range_vf: members step in lockstep.  Member p is, bit for bit, PpoLearner(seed=seeds[p]) on the same rows.  `rollout_size`: m * n_steps, a member's
-    share of the buffer.  export(member), diagnostics (a list of P dicts), member(p), save and load (member_<p>.npz): _learner.Population.
+    """`n_members` PPO learners of the same shapes (PpoLearner's keywords) that take their minibatch step in the same four launches (csrc/hrgym_ppo.h;
+    DESIGN.md D29, D30): the seeds of one cell of a study, or the cells of a sweep, side by side on one GPU.  The batch of n = P m envs is P groups of m
+    consecutive envs; member p acts in, and learns from, group p only.  The counters are shared: members step in lockstep.  `learning_rate`, `clip_range`,
+    `clip_range_vf` (None: not clipped), `ent_coef`, `vf_coef` and `max_grad_norm` take a scalar (every member) or a sequence of one value per member; the first
+    three may be assigned between steps, a scalar or a sequence.  What shapes a launch, the lockstep or the host's loop is shared (`_shared`).  Member p is, bit
+    for bit, PpoLearner(seed=seeds[p], **member_hyper(p)) on the same rows.  `rollout_size`: m * n_steps, a member's share of the buffer.  export(member),
+    diagnostics (a list of P dicts), member(p), member_hyper(p), save and load (member_<p>.npz and, where the members differ, population.npz):
+    _learner.Population.
 
         env.attach_rollout(n_steps=64, gamma=0.99, gae_lambda=0.9)
         pop = env.attach_ppo_population(5, batch_size=64)            # seeds: the env's seed + p
@@ -282,13 +291,60 @@ class PpoPopulation(Population, PpoLearner):
         pop.diagnostics()                                            # a list of 5 dicts
     """
     _lone = PpoLearner
+    _fields = ("learning_rate", "clip_range", "clip_range_vf", "ent_coef", "vf_coef", "max_grad_norm")
+    _scheduled = ("learning_rate", "clip_range", "clip_range_vf")
+    _manifest_fields = _fields
+    learning_rate, clip_range, clip_range_vf = (scheduled_attribute(name) for name in _scheduled)
+    _defaults = dict(learning_rate=3e-4, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5)   # PpoLearner's
+    _shared = dict(net_arch="the depth and the trunks shape every launch", batch_size="the minibatch shapes every launch", n_epochs="the epochs are the host's loop over all members",
+                   normalize_advantage="it decides whether the advantage kernel is launched", rollout_size="the members' shares of the buffer are equal",
+                   log_std_init="it shapes the initial parameters, not the step", ortho_init="it shapes the initial parameters, not the step",
+                   use_sde="not covered", target_kl="not covered", policy="one policy class per handle")
 
     def __init__(self, obs_dim, act_dim, n_members, seeds, device=0, **kwargs):
         self.n_members, self._table = check_seeds(n_members, seeds)
         self.seeds = [int(s) for s in self._table]
         if "seed" in kwargs:
             raise TypeError("PpoPopulation: the members' seeds are `seeds` (one per member), not `seed`")
-        super().__init__(obs_dim, act_dim, seed=self.seeds[0], device=device, **kwargs)   # (the entry reads the table, not the descriptor's seed)
+        refuse_shared_sequences(self._shared, kwargs)
+        values = {name: kwargs.pop(name, self._defaults[name]) for name in self._fields}
+        self._set_values(**values)   # (every member's values are checked before anything is allocated)
+        first = self.member_hyper(0)
+        super().__init__(obs_dim, act_dim, seed=self.seeds[0], device=device, **first, **kwargs)   # (the entry reads the table, not the descriptor's seed)
+        self._set_values(**values)   # (the lone learner's constructor assigned member 0's scheduled attributes to all)
+        self._sync_table()
+
+    @staticmethod
+    def _convert(name, value):
+        """One member's value of a table field as the constructor takes it; ValueError for what no learner takes."""
+        if name == "clip_range_vf" and value is None:
+            return None
+        value = float(value)
+        positive = name in ("clip_range", "clip_range_vf", "max_grad_norm")
+        if not math.isfinite(value) or value < 0.0 or (positive and value == 0.0):
+            raise ValueError(f"{name} = {value} must be finite and {'positive' if positive else 'not negative'}" + (" (None: no clipping)" if name == "clip_range_vf" else ""))
+        return value
+
+    def _step_scalars(self):
+        """Member 0's, kept as a tuple: `step` runs once per minibatch, and the library reads its table once that is the caller's."""
+        return self._member0
+
+    def _member_desc(self, p):
+        """Member p's descriptor: the lone learner's of its seed and its values."""
+        desc, v = type(self.desc).from_buffer_copy(self.desc), self.member_hyper(p)
+        desc.seed, desc.ent_coef, desc.vf_coef, desc.max_grad_norm = self.seeds[p], v["ent_coef"], v["vf_coef"], v["max_grad_norm"]
+        return desc
+
+    def _row(self, p):
+        return self.table_row(self.member_hyper(p))
+
+    @staticmethod
+    def table_row(v):
+        """hrg_ppo_hyper of one member's values `v` (member_hyper's dict): clip_range_vf None is the negative sentinel."""
+        row = PpoHyper()
+        row.learning_rate, row.clip_range, row.clip_range_vf = v["learning_rate"], v["clip_range"], -1.0 if v["clip_range_vf"] is None else v["clip_range_vf"]
+        row.ent_coef, row.vf_coef, row.max_grad_norm = v["ent_coef"], v["vf_coef"], v["max_grad_norm"]
+        return row
 
     def _open_handle(self, desc, device):
         self._open(desc, device, self.n_members, self._table.ctypes.data_as(ctypes.c_void_p), create="_population_create")

@@ -26,8 +26,9 @@ import math
 
 import numpy as np
 
-from ._cstruct import CONST, SacDesc
-from ._learner import MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries  # noqa: F401 (check_seeds: importable from here)
+from ._cstruct import CONST, SacDesc, SacHyper
+from ._learner import (MAX_POPULATION, Learner, LearnerParams, Population, PopulationParams, build_layout, check_seeds, check_widths, mlp_entries,  # noqa: F401 (check_seeds: importable from here)
+                       per_member, refuse_shared_sequences, scheduled_attribute)
 from ._lib import _ptr
 
 HIDDEN = CONST["HRG_SAC_HIDDEN"]
@@ -197,8 +198,12 @@ class SacLearner(Learner):
                 self._tensor(batch.rewards, (B, 1), "rewards"), None if eps_pi is None else self._tensor(eps_pi, (B, A), "eps_pi"),
                 None if eps_next is None else self._tensor(eps_next, (B, A), "eps_next"))
         with self.torch.cuda.device(self.device):
-            self._check(self.lib, self.lib.hrg_sac_step(self.h, *args, _ptr(p.params), _ptr(p.adam_m), _ptr(p.adam_v), _ptr(p.target), float(self.learning_rate), self._stream()))
+            self._check(self.lib, self.lib.hrg_sac_step(self.h, *args, _ptr(p.params), _ptr(p.adam_m), _ptr(p.adam_v), _ptr(p.target), float(self._step_scalars()[0]), self._stream()))
         self._keep = (batch, eps_pi, eps_next)
+
+    def _step_scalars(self):
+        """(learning_rate,) as `step` passes it."""
+        return (self.learning_rate,)
 
     def train(self, replay, gradient_steps):
         """SAC.train(gradient_steps, batch_size): `gradient_steps` x (replay.sample(batch_size), step), with no copy to the host and no synchronisation.
@@ -241,44 +246,88 @@ class SacLearner(Learner):
 
 class SacPopulationParams(PopulationParams):
     """The tensors of a population, on any torch device: `params`, `adam_m`, `adam_v` float32 [P, n_params] and `target` float32 [P, 2 n_critic].  Row p is
-    initialised exactly as SacParams(seed=seeds[p]); `member(p)` is the rows of member p as views."""
+    initialised exactly as SacParams(seed=seeds[p], ent_coef_init=ent_coef_init[p]) (`ent_coef_init`: a scalar, or one value per member); `member(p)` is the
+    rows of member p as views."""
 
     def __init__(self, obs_dim, act_dim, depth, seeds, ent_coef_init=1.0, device="cpu"):
-        rows = [SacParams(obs_dim, act_dim, depth, seed=int(s), ent_coef_init=ent_coef_init) for s in seeds]
+        inits = per_member("ent_coef_init", ent_coef_init, len(seeds))
+        rows = [SacParams(obs_dim, act_dim, depth, seed=int(s), ent_coef_init=e) for s, e in zip(seeds, inits)]
         super().__init__(rows, device)
         self.n_actor, self.n_critic = rows[0].n_actor, rows[0].n_critic
 
 
 class SacPopulation(Population, SacLearner):
-    """`n_members` SAC learners of the same shapes and hyper-parameters (SacLearner's keywords) that differ in their seed only and take their gradient step in
-    the same six launches (csrc/hrgym_sac.h): the seeds of one cell of a study, side by side on one GPU.  The batch of n = P m envs is P groups
-    of m consecutive envs; member p acts in, and learns from, group p only.  The counters are shared: members step in lockstep.  Member p is, bit for bit,
-    SacLearner(seed=seeds[p]) on the same transitions.  export(member), diagnostics (a list of P dicts), member(p), save and load (member_<p>.npz):
-    _learner.Population.
+    """`n_members` SAC learners of the same shapes (SacLearner's keywords) that take their gradient step in the same six launches (csrc/hrgym_sac.h; DESIGN.md
+    D27, D30): the seeds of one cell of a study, or the cells of a sweep, side by side on one GPU.  The batch of n = P m envs is P groups of m consecutive
+    envs; member p acts in, and learns from, group p only.  The counters are shared: members step in lockstep.  `learning_rate`, `gamma`, `tau`, `ent_coef` and
+    `target_entropy` take a scalar (every member) or a sequence of one value per member ("auto_0.2" next to a fixed 0.1 included); `learning_rate` may be
+    assigned between steps, a scalar or a sequence.  What shapes a launch or the lockstep is shared (`_shared`).  Member p is, bit for bit,
+    SacLearner(seed=seeds[p], **member_hyper(p)) on the same transitions.  export(member), diagnostics (a list of P dicts), member(p), member_hyper(p), save and
+    load (member_<p>.npz and, where the members differ, population.npz): _learner.Population.
 
         env.attach_replay(buffer_size)
         pop = env.attach_sac_population(5, batch_size=128)       # seeds: the env's seed + p
         env.collect_steps(pop.act, 100)
         pop.train(env.replay, 800)                               # 800 x (env.replay.sample_groups(5, 128, pop.seeds), step)
         pop.diagnostics()                                        # a list of 5 dicts
+
+        pop = env.attach_sac_population(6, seeds=[0, 1, 2] * 2, learning_rate=[1e-3] * 3 + [3e-4] * 3)   # a sweep: two learning rates x three seeds
     """
     _lone = SacLearner
+    _fields = ("learning_rate", "gamma", "tau", "ent_coef", "target_entropy")
+    _scheduled = ("learning_rate",)
+    learning_rate = scheduled_attribute("learning_rate")
+    _manifest_fields = ("learning_rate", "gamma", "tau", "ent_coef", "auto_ent_coef", "target_entropy")   # (the checkpoint's names: ent_coef is two descriptor fields)
+    _shared = dict(net_arch="the depth shapes every launch", batch_size="the batch shapes every launch",
+                   target_update_interval="the host decides per step whether the targets move, for all members of the lockstep")
 
     def __init__(self, obs_dim, act_dim, n_members, seeds, net_arch=(64, 64, 64), learning_rate=3e-4, gamma=0.99, tau=0.005, ent_coef="auto", target_entropy="auto",
                  batch_size=256, target_update_interval=1, device=0):
         self.n_members, table = check_seeds(n_members, seeds)
         self.seeds = [int(s) for s in table]
-        self._kwargs = dict(net_arch=net_arch, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy, batch_size=batch_size,
-                            target_update_interval=target_update_interval)   # (member, save and load: _learner.Population)
-        desc = build_sac_desc(obs_dim, act_dim, seed=self.seeds[0], **self._kwargs)   # (the entry reads the table, not the descriptor's seed)
-        self._open(desc, device, self.n_members, table.ctypes.data_as(ctypes.c_void_p), create="_population_create")
-        self.obs_dim, self.act_dim, self.depth, self.batch_size = int(obs_dim), int(act_dim), int(self.desc.depth), int(batch_size)
-        self.learning_rate = float(learning_rate)
-        self.auto_ent_coef = bool(self.desc.auto_ent_coef)
-        self.p = SacPopulationParams(obs_dim, act_dim, self.depth, self.seeds, ent_coef_init=self.desc.ent_coef, device=self.device)
+        self._kwargs = dict(net_arch=net_arch, batch_size=batch_size, target_update_interval=target_update_interval)   # (member, save and load: _learner.Population)
+        refuse_shared_sequences(self._shared, self._kwargs)
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self._set_values(learning_rate=learning_rate, gamma=gamma, tau=tau, ent_coef=ent_coef, target_entropy=target_entropy)
+        descs = [self._member_desc(p) for p in range(self.n_members)]   # (every member's values are checked before anything is allocated)
+        self._open(descs[0], device, self.n_members, table.ctypes.data_as(ctypes.c_void_p), create="_population_create")   # (the entry reads the table, not the descriptor's seed)
+        self.depth, self.batch_size = int(self.desc.depth), int(batch_size)
+        self.auto_ent_coef = bool(self.desc.auto_ent_coef)   # (member 0's; per member: member_hyper)
+        self.p = SacPopulationParams(obs_dim, act_dim, self.depth, self.seeds, ent_coef_init=[d.ent_coef for d in descs], device=self.device)
         if self._sizes()[:3] != [self.p.n_params, self.p.n_actor, self.p.n_critic]:
             raise RuntimeError("SacPopulation: the library lays out other parameters than sac.param_layout: rebuild")
         self._keep = None
+        self._sync_table()
+
+    @staticmethod
+    def _convert(name, value):
+        """One member's value of a table field as the constructor takes it; ValueError for what no learner takes."""
+        if name == "ent_coef":
+            parse_ent_coef(value)
+            return value if isinstance(value, str) else float(value)
+        if name == "target_entropy" and isinstance(value, str):
+            if value != "auto":
+                raise ValueError(f"target_entropy = {value!r}: 'auto' or a float")
+            return value
+        value = float(value)
+        if not math.isfinite(value) or (name == "learning_rate" and value < 0.0) or (name in ("gamma", "tau") and not 0.0 <= value <= 1.0):
+            raise ValueError(f"{name} = {value}: " + ("a finite learning rate that is not negative" if name == "learning_rate" else "finite" if name == "target_entropy" else "in [0, 1]"))
+        return value
+
+    def _step_scalars(self):
+        """Member 0's, kept as a tuple: the library reads its table once that is the caller's."""
+        return self._member0
+
+    def _member_desc(self, p):
+        """Member p's descriptor: the lone learner's of its seed and its values."""
+        v = self.member_hyper(p)
+        return build_sac_desc(self.obs_dim, self.act_dim, seed=self.seeds[p], gamma=v["gamma"], tau=v["tau"], ent_coef=v["ent_coef"], target_entropy=v["target_entropy"],
+                              **self._kwargs)
+
+    def _row(self, p):
+        d, row = self._member_desc(p), SacHyper()
+        row.learning_rate, row.gamma, row.tau, row.ent_coef, row.target_entropy, row.auto_ent_coef = self._values["learning_rate"][p], d.gamma, d.tau, d.ent_coef, d.target_entropy, d.auto_ent_coef
+        return row
 
     def train(self, replay, gradient_steps):
         """`gradient_steps` x (replay.sample_groups(n_members, batch_size, seeds), step), with no copy to the host and no synchronisation.  `replay`: a

@@ -355,6 +355,66 @@ class RunFolder:
         return None if self.model_dir is None else learner.save(self.path("final"))
 
 
+def sweep_members(sweeps, seeds, n_envs, fields, max_members):
+    """The members of a training tool's --sweep NAME=v1,v2,... (repeatable) and --seeds: the values of every sweep crossed with each other and with the seeds,
+    value-major and seed-minor (the first sweep's value changes slowest, the seed fastest) -> (seeds [P], {name: values [P]}).  A value is a float where it
+    reads as one, None for "none", otherwise the string itself ("auto_0.2").  ValueError, before any env is built: an option that is no NAME=v1,v2,..., a name
+    that is no per-member field (`fields`) or given twice, more than `max_members` members, `n_envs` that the members do not divide."""
+    from itertools import product
+
+    def value(text):
+        if text.strip().lower() == "none":
+            return None
+        try:
+            return float(text)
+        except ValueError:
+            return text.strip()
+
+    names, lists = [], []
+    for opt in sweeps or ():
+        name, sep, rest = str(opt).partition("=")
+        name = name.strip().replace("-", "_")
+        if not sep or not name or not rest.strip() or any(not v.strip() for v in rest.split(",")):
+            raise ValueError(f"--sweep {opt}: expected NAME=v1,v2,...")
+        if name not in fields:
+            raise ValueError(f"--sweep {opt}: {name} is no per-member field (those are {', '.join(fields)}); what shapes a launch or the lockstep is shared by the members")
+        if name in names:
+            raise ValueError(f"--sweep {opt}: {name} is swept twice")
+        names.append(name)
+        lists.append([value(v) for v in rest.split(",")])
+    seeds = [int(s) for s in seeds]
+    members = list(product(*lists, seeds))
+    P = len(members)
+    if not 1 <= P <= int(max_members):
+        raise ValueError(f"{' x '.join(str(len(v)) for v in lists + [seeds])} = {P} members: a population has 1 .. {int(max_members)}")
+    if int(n_envs) % P:
+        raise ValueError(f"--n-envs {n_envs} is not divisible by the {P} members: every member steps a group of the same size")
+    return [m[-1] for m in members], {name: [m[i] for m in members] for i, name in enumerate(names)}
+
+
+def checked_sweep(population, sweeps, seeds, n_envs, max_members):
+    """sweep_members for the fields of the population class `population`, with every swept value checked as its constructor checks it
+    (Population.member_values): a value no learner takes (gamma=nan, learning_rate=-1) is refused here, before any env is built, too."""
+    seeds, swept = sweep_members(sweeps, seeds, n_envs, population._fields, max_members)
+    population.member_values(len(seeds), **swept)
+    return seeds, swept
+
+
+def member_lines(seeds, swept, *parts):
+    """The `members` list of a population's JSON line: per member dict(seed, **its entry of every list of dicts in `parts` -- episode stats, diagnostics) and, where
+    something is swept, `hyper`: the member's value of every swept field.  The values stand under a key of their own because the diagnostics report
+    `learning_rate`, `clip_range` and the live `ent_coef` under the fields' own names."""
+    lines = []
+    for p, seed in enumerate(seeds):
+        line = dict(seed=seed)
+        if swept:
+            line["hyper"] = {name: values[p] for name, values in swept.items()}
+        for part in parts:
+            line.update(part[p])
+        lines.append(line)
+    return lines
+
+
 def run_folder_from_args(args, **env_kw) -> RunFolder:
     """The RunFolder of a training tool's --model-dir / --save-freq / --eval-episodes / --eval-n-envs / --eval-seed, with a second env of the tool's task for
     the evaluations (its own seed: the reference's eval_seed; `env_kw`: further HipVecEnv keywords).  Without the flags nothing is built."""

@@ -1023,17 +1023,19 @@ class HipVecEnv(_VecEnvBase):
         return self._attach_learner("ppo", PpoLearner, rb.obs_dim, rb, rollout_size=rb.n * rb.n_steps, **kwargs)
 
     def attach_ppo_population(self, n_members, seeds=None, **kwargs):
-        """`n_members` PPO learners that differ in their seed only, stepped in the same launches (ppo.PpoPopulation; PpoLearner's keywords but `seed`), after
-        attach_rollout: the envs are n_members groups of m = num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`:
-        one per member (default: the env's seed + p).  Refused before anything is allocated: another backend and the mixed batch, no rollout buffer, envs
+        """`n_members` PPO learners stepped in the same launches (ppo.PpoPopulation; PpoLearner's keywords but `seed`), after attach_rollout: the envs are
+        n_members groups of m = num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`: one per member (default:
+        the env's seed + p).  learning_rate, clip_range, clip_range_vf, ent_coef, vf_coef and max_grad_norm take a scalar or one value per member (a sweep);
+        a sequence for a keyword the members share (batch_size, net_arch, n_epochs, ...) is refused.  Refused before anything is allocated: another backend and the mixed batch, no rollout buffer, envs
         that the members do not divide, a batch_size that does not divide m * n_steps.  Returns the population and keeps it as `env.ppo_population`:
         `env.collect_rollout(pop.policy, pop.value)`, then `pop.train(env.rollout)`; `env.evaluate(pop.p.params, n, learner=pop.member(0))` evaluates the
         members side by side."""
-        from .ppo import PpoPopulation, check_seeds
+        from .ppo import PpoPopulation, check_seeds, refuse_shared_sequences
         from .rollout import group_rows
         P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]
         if "seed" in kwargs:
             raise TypeError("attach_ppo_population: the members' seeds are `seeds` (one per member), not `seed`")
+        refuse_shared_sequences(PpoPopulation._shared, kwargs)
         why = self._rollout_refusal()
         if why is not None:
             raise NotImplementedError(f"attach_ppo_population: {why}")
@@ -1147,9 +1149,10 @@ class HipVecEnv(_VecEnvBase):
         return self._attach_learner("sac", SacLearner, obs_dim, rb, **kwargs)
 
     def attach_sac_population(self, n_members, seeds=None, **kwargs):
-        """`n_members` SAC learners that differ in their seed only, stepped in the same launches (sac.SacPopulation; SacLearner's keywords but `seed`), after
-        attach_replay: the envs are n_members groups of num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`:
-        one per member (default: the env's seed + p).  Refused: a goal env, envs that the members do not divide, the mixed batch.  Returns the population and
+        """`n_members` SAC learners stepped in the same launches (sac.SacPopulation; SacLearner's keywords but `seed`), after attach_replay: the envs are
+        n_members groups of num_envs / n_members consecutive envs, and member p acts in and learns from group p only.  `seeds`: one per member (default: the
+        env's seed + p).  learning_rate, gamma, tau, ent_coef and target_entropy take a scalar or one value per member (a sweep); a sequence for a keyword
+        the members share (batch_size, net_arch, target_update_interval) is refused.  Refused: a goal env, envs that the members do not divide, the mixed batch.  Returns the population and
         keeps it as `env.sac_population`: `env.collect_steps(pop.act, train_freq)`, then `pop.train(env.replay, gradient_steps)`."""
         from .sac import SacPopulation, check_seeds
         P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]

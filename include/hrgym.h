@@ -516,7 +516,7 @@ typedef struct hrg_replay_desc {
 #define HRG_SAC_MAX_DEPTH 3   /* hidden layers: 1 .. 3 */
 #define HRG_SAC_TILE 32       /* rows of the batch per workgroup: batch_size is a multiple */
 #define HRG_SAC_MAX_BATCH 256
-#define HRG_SAC_MAX_POPULATION 64 /* members of a population: learners of one descriptor that differ in their seed and step in the same launches */
+#define HRG_SAC_MAX_POPULATION 64 /* members of a population: learners of one shape that step in the same launches (their seeds and hrg_sac_hyper rows may differ) */
 #define HRG_SAC_NQ 6          /* Q columns of hrg_sac_export: Q1, Q2 on (obs, act); the targets' Q1, Q2 on (next_obs, a'); the updated Q1, Q2 on (obs, a_pi) */
 /* One learner: SB3 1.5.0's SAC(MlpPolicy, net_arch = [64] * depth, use_sde = False).  The learning rate is an argument of hrg_sac_step. */
 typedef struct hrg_sac_desc {
@@ -534,13 +534,24 @@ typedef struct hrg_sac_desc {
   double target_entropy;
   uint64_t seed;                  /* key of the noise draws */
 } hrg_sac_desc;
+/* One member's row of a SAC population's hyper-parameter table (hrg_sac_population_set_hyper): what may differ between the members of one handle.  What shapes a
+ * launch or the lockstep (the dimensions, depth, batch_size, target_update_interval) stays the descriptor's. */
+typedef struct hrg_sac_hyper {
+  double learning_rate;           /* finite, not negative */
+  double gamma;                   /* in [0, 1] */
+  double tau;                     /* in [0, 1] */
+  double ent_coef;                /* the fixed coefficient (auto_ent_coef = 0: positive); the learned one starts from the member's log_ent_coef entry */
+  double target_entropy;
+  int32_t auto_ent_coef;          /* 1: this member's entropy coefficient is learned; 0: its entry gets no gradient and no Adam step */
+  int32_t reserved_;
+} hrg_sac_hyper;
 
 /* ------------------------------------------------------------------------- the PPO learner on the device (POD) */
 #define HRG_PPO_HIDDEN HRG_SAC_HIDDEN       /* hidden width the kernels cover */
 #define HRG_PPO_MAX_DEPTH HRG_SAC_MAX_DEPTH /* hidden layers: 1 .. 3 */
 #define HRG_PPO_TILE HRG_SAC_TILE           /* rows of the minibatch per workgroup: batch_size is a multiple */
 #define HRG_PPO_MAX_BATCH 4096
-#define HRG_PPO_MAX_POPULATION 64           /* members of a population: learners of one descriptor that differ in their seed and step in the same launches */
+#define HRG_PPO_MAX_POPULATION 64           /* members of a population: learners of one shape that step in the same launches (their seeds and hrg_ppo_hyper rows may differ) */
 #define HRG_PPO_NDIAG 8                     /* floats of hrg_ppo_export's diag */
 #define HRG_PPO_MLP_POLICY 0                /* hrg_ppo_desc.policy: SB3's "MlpPolicy", the only one covered */
 /* One learner: SB3 1.5.0's PPO(MlpPolicy, use_sde = False) with net_arch = [64] * depth (separate = 0: the shared trunk) or [dict(pi = [64] * depth, vf = [64] * depth)]
@@ -561,6 +572,16 @@ typedef struct hrg_ppo_desc {
   double ent_coef, vf_coef, max_grad_norm;
   uint64_t seed;                  /* key of the noise draws */
 } hrg_ppo_desc;
+/* One member's row of a PPO population's hyper-parameter table (hrg_ppo_population_set_hyper): what may differ between the members of one handle.  What shapes a
+ * launch or the lockstep (the dimensions, depth, separate, batch_size, rollout_size, normalize_advantage) stays the descriptor's; n_epochs is the caller's loop. */
+typedef struct hrg_ppo_hyper {
+  double learning_rate;           /* finite, not negative */
+  double clip_range;              /* finite, positive */
+  double clip_range_vf;           /* negative: the value function is not clipped */
+  double ent_coef;                /* finite, not negative */
+  double vf_coef;                 /* finite, not negative */
+  double max_grad_norm;           /* finite, positive */
+} hrg_ppo_hyper;
 
 /* ------------------------------------------------------------------------- evaluation of deterministic policies on the device (POD) */
 #define HRG_EVAL_MAX_EPISODES_PER_ENV 4096 /* the largest quota of an env: ceil(n_eval_episodes / (n_envs / n_policies)) may not exceed it */
@@ -936,8 +957,8 @@ int hrg_sac_step(hrg_sac* h, const float* observations_dev, const float* actions
 int hrg_sac_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n, const float* eps_dev, int32_t deterministic, float* actions_dev, void* stream);
 int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
 
-/* A SAC population (csrc/hrgym_sac.h): n_members learners of one descriptor that differ in their seed only and take their gradient step in the same
- * six launches.  The handle is an hrg_sac: the lone learner is the population of one member, and hrg_sac_sizes, hrg_sac_step, hrg_sac_restore and hrg_sac_destroy
+/* A SAC population (csrc/hrgym_sac.h): n_members learners of one shape that differ in their seed, and where hrg_sac_population_set_hyper
+ * was called in their hrg_sac_hyper rows, and take their gradient step in the same six launches.  The handle is an hrg_sac: the lone learner is the population of one member, and hrg_sac_sizes, hrg_sac_step, hrg_sac_restore and hrg_sac_destroy
  * serve both.  The counters (gradient steps, act calls) are the handle's: members step in lockstep.  Member p is, bit for bit, the lone learner of seeds[p] on the
  * same rows: its draws are keyed by its seed and the row's index in its own batch (hrg_sac_population_act: in its own group), its sums are its own.
  *   hrg_sac_population_create  hrg_sac_create with n_members seeds in place of the descriptor's (which is not read).  Before anything is allocated or launched:
@@ -948,11 +969,22 @@ int hrg_sac_export(hrg_sac* h, float* y_host, float* logp_host, float* logp_next
  *   hrg_sac_population_act     obs_dev float [P][n_group][obs_dim] -> actions_dev float [P][n_group][act_dim], member p's actor (params_dev [P][n_params]) on
  *                              group p; a draw's key is (seeds[p], act call count, row within the group, 13, j).  eps_dev [P][n_group][act_dim] as in hrg_sac_act,
  *                              which is this entry for one member and refuses a handle of more.
- *   hrg_sac_population_export  hrg_sac_export of one member; HRG_ERR_INVALID for a member outside the population. */
+ *   hrg_sac_population_export  hrg_sac_export of one member; HRG_ERR_INVALID for a member outside the population.
+ *   hrg_sac_population_set_hyper  the members' hyper-parameters: rows_host hrg_sac_hyper [n_members] (host memory, read before the entry returns) into the handle's
+ *                              device table, which the step kernels read by member.  Without a call every row holds the descriptor's gamma, tau, ent_coef and
+ *                              target_entropy and the learning_rate argument of hrg_sac_step; AFTER a call hrg_sac_step's learning_rate argument is not read for
+ *                              this handle any more (nor checked): the table's is.  The table is ordered on the stream it was written on: the steps of one handle belong on one stream
+ *                              (a caller that changes streams orders them itself and calls this entry again on the new one).  Every row is checked before anything is written, as hrg_sac_create checks the
+ *                              descriptor and hrg_sac_step its argument, and gamma and tau must lie in [0, 1]: HRG_ERR_INVALID naming member and field (also for a
+ *                              null table or an n_members that is not the handle's), and the table stays as it was.  The rows are written by a launch on `stream`,
+ *                              behind the steps queued there and ahead of the next; it may be called between any two steps (a schedule).  Member p's arithmetic
+ *                              reads row p only, in the types and the order the lone learner uses: member p is, bit for bit, the lone learner created with row
+ *                              p's values. */
 int hrg_sac_population_create(const hrg_sac_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_sac** out);
 int hrg_sac_population_act(hrg_sac* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic, float* actions_dev,
                            void* stream);
 int hrg_sac_population_export(hrg_sac* h, int32_t member, float* y_host, float* logp_host, float* logp_next_host, float* q_host, float* grad_host, float* losses_host);
+int hrg_sac_population_set_hyper(hrg_sac* h, const hrg_sac_hyper* rows_host, int32_t n_members, void* stream);
 
 /* The grouped sample of the uniform replay buffer, for a population: the n_envs envs are n_groups groups of n_envs / n_groups consecutive envs, and group g's
  * batch_size samples come from its own envs: sample k draws u0, u1 = rng_u01(seeds[g], grouped call counter, k, 11, 0..1), slot = floor(u0 * upper), env =
@@ -992,10 +1024,11 @@ int hrg_ppo_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, i
                     float* values_dev, float* log_probs_dev, void* stream);
 int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
 
-/* A PPO population (csrc/hrgym_ppo.h): n_members learners of one descriptor that differ in their seed only and take their minibatch step in the same
- * four launches.  The handle is an hrg_ppo: the lone learner is the population of one member, and hrg_ppo_sizes, hrg_ppo_step, hrg_ppo_restore, hrg_ppo_destroy and
+/* A PPO population (csrc/hrgym_ppo.h): n_members learners of one shape that differ in their seed, and where hrg_ppo_population_set_hyper
+ * was called in their hrg_ppo_hyper rows, and take their minibatch step in the same four launches.  The handle is an hrg_ppo: the lone learner is the population of one member, and hrg_ppo_sizes, hrg_ppo_step, hrg_ppo_restore, hrg_ppo_destroy and
  * hrg_eval_policy_ppo serve both; hrg_ppo_export is member 0's.  The counters (minibatch steps, forward calls) are the handle's: members step in lockstep, and
- * learning_rate, clip_range and clip_range_vf of a step are shared.  Member p is, bit for bit, the lone learner of seeds[p] on the same rows: its advantage
+ * learning_rate, clip_range and clip_range_vf of a step are every member's until hrg_ppo_population_set_hyper gives each member its own.  Member p is, bit for
+ * bit, the lone learner of seeds[p] (and of its row) on the same rows: its advantage
  * statistics, clip coefficient and diagnostics come from its own sums, its draws are keyed by its seed and the row's index in its own group.
  *   hrg_ppo_population_create   hrg_ppo_create with n_members seeds in place of the descriptor's (which is not read).  Before anything is allocated or launched:
  *                               HRG_ERR_UNSUPPORTED for n_members outside 1 .. HRG_PPO_MAX_POPULATION, HRG_ERR_INVALID for a null seeds table, then whatever
@@ -1006,11 +1039,21 @@ int hrg_ppo_export(hrg_ppo* h, float* values_host, float* log_prob_host, float* 
  *                               p's networks (params_dev [P][n_params]) on group p; a draw's key is (seeds[p], forward call count, row within the group, 14, j).
  *                               eps_dev [P][n_group][act_dim], deterministic and a NULL actions_dev (the values only) as in hrg_ppo_forward, which is this entry
  *                               for one member and refuses a handle of more.  HRG_ERR_INVALID for n_group < 1.
- *   hrg_ppo_population_export   hrg_ppo_export of one member; HRG_ERR_INVALID for a member outside the population. */
+ *   hrg_ppo_population_export   hrg_ppo_export of one member; HRG_ERR_INVALID for a member outside the population.
+ *   hrg_ppo_population_set_hyper  the members' hyper-parameters: rows_host hrg_ppo_hyper [n_members] (host memory, read before the entry returns) into the handle's
+ *                               device table, which the step kernels read by member.  Without a call every row holds the descriptor's ent_coef, vf_coef and
+ *                               max_grad_norm and the learning_rate, clip_range and clip_range_vf arguments of hrg_ppo_step; AFTER a call those three arguments of
+ *                               hrg_ppo_step are not read for this handle any more (nor checked): the table's are.  The table is ordered on the stream it was written on: the
+ *                               steps of one handle belong on one stream (as for hrg_sac_population_set_hyper).  Every row is checked before anything is
+ *                               written, as hrg_ppo_create checks the descriptor and hrg_ppo_step its arguments: HRG_ERR_INVALID naming member and field (also for
+ *                               a null table or an n_members that is not the handle's), and the table stays as it was.  The rows are written by a launch on
+ *                               `stream`, behind the steps queued there and ahead of the next; it may be called between any two steps (a schedule).  Member p's
+ *                               arithmetic reads row p only, in the types and the order the lone learner uses. */
 int hrg_ppo_population_create(const hrg_ppo_desc* desc, int32_t n_members, const uint64_t* seeds, int32_t device, hrg_ppo** out);
 int hrg_ppo_population_forward(hrg_ppo* h, const float* params_dev, const float* obs_dev, int32_t n_group, const float* eps_dev, int32_t deterministic,
                                float* actions_dev, float* values_dev, float* log_probs_dev, void* stream);
 int hrg_ppo_population_export(hrg_ppo* h, int32_t member, float* values_host, float* log_prob_host, float* ratio_host, float* grad_host, float* diag_host);
+int hrg_ppo_population_set_hyper(hrg_ppo* h, const hrg_ppo_hyper* rows_host, int32_t n_members, void* stream);
 
 /* A learner's counters, for a checkpoint that is loaded into a fresh handle: Adam's bias corrections, the keys of the draws and (SAC) the phase of the target
  * update follow from them.

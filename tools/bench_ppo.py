@@ -11,7 +11,10 @@ python tools/bench_ppo.py [--blocks 7] [--epochs 2] [--out profiles/r14_ppo.json
 7 actions, net_arch [64, 64] shared, batch 64 per member -- on fixed minibatches, the steps alone; 0 stands for the lone PpoLearner through its own class.  Blocks of
 --min-steps steps, the sizes taking turns within a round, HIP events around each block.  With --train also one train() of the reference's rollout (10 envs per
 member, n_steps 64, 20 epochs: 200 minibatch steps with their permutations and gathers) for the largest P, beside that many lone train() calls in turn.
-python tools/bench_ppo.py --population 0 1 2 5 16 --train --out profiles/r23_ppo_population.json"""
+python tools/bench_ppo.py --population 0 1 2 5 16 --train --out profiles/r23_ppo_population.json
+
+--distinct (with --population): every member gets its own learning rate, clip ranges, ent_coef, vf_coef and max_grad_norm, so that the step reads a table the
+caller uploaded instead of the one the scalar arguments fill."""
 import argparse
 import json
 import os
@@ -33,6 +36,7 @@ ap.add_argument("--epochs", type=int, default=2, help="passes over the buffer pe
 ap.add_argument("--min-steps", type=int, default=128, help="minibatch steps per block, at least")
 ap.add_argument("--out", default="profiles/r14_ppo.json")
 ap.add_argument("--population", type=int, nargs="+", default=None, help="time the step of populations of these sizes instead (0: the lone learner)")
+ap.add_argument("--distinct", action="store_true", help="with --population: distinct hyper-parameters per member")
 ap.add_argument("--train", action="store_true", help="with --population: also one train() of the reference's rollout shape against lone train() calls in turn")
 args = ap.parse_args()
 A, ARCH, LR, n_envs, n_steps = 7, [64, 64], 7e-5, 256, 64   # the buffer: 16384 rows, 256 minibatches of 64 or 4 of 4096 per pass
@@ -72,7 +76,12 @@ def population_bench():
     for P in args.population:
         if P:
             from human_robot_gym_amd.ppo import PpoPopulation
-            learner = PpoPopulation(K, A, P, list(range(P)), **kw)
+            hyper = {}
+            if args.distinct:
+                hyper = dict(learning_rate=[LR * (1.0 + 0.1 * p) for p in range(P)], clip_range=[0.2 + 0.01 * p for p in range(P)],
+                             clip_range_vf=[None if p % 2 == 0 else 0.2 + 0.01 * p for p in range(P)], ent_coef=[0.001 * p for p in range(P)],
+                             vf_coef=[0.5 + 0.01 * p for p in range(P)], max_grad_norm=[0.5 + 0.05 * p for p in range(P)])
+            learner = PpoPopulation(K, A, P, list(range(P)), **{**kw, **hyper})
         else:
             learner = PpoLearner(K, A, seed=0, **kw)
         obs = dev(rng.uniform(-1, 1, (max(P, 1) * B, K)))
@@ -86,7 +95,7 @@ def population_bench():
         for _, learner, batch, ms in sides:
             ms.append(timed(lambda: [learner.step(batch) for _ in range(args.min_steps)]) / args.min_steps)
     for P, learner, _, ms in sides:
-        res["step"].append(dict(population=P, ms_per_step=ms, ms_median=float(np.median(ms)), ms_spread=float(np.max(ms) - np.min(ms)),
+        res["step"].append(dict(population=P, distinct=bool(args.distinct and P), ms_per_step=ms, ms_median=float(np.median(ms)), ms_spread=float(np.max(ms) - np.min(ms)),
                                 finite=bool(torch.isfinite(learner.p.params).all()), n_updates=learner.n_updates))
         print("population %2d: %.4f ms per minibatch step (blocks %s)" % (P, np.median(ms), " ".join("%.4f" % x for x in ms)), flush=True)
         learner.close()

@@ -9,7 +9,10 @@ python tools/bench_sac.py [--blocks 7] [--steps 200]
 --population P [P ...] times the step of a population instead (sac.SacPopulation: P learners in the same six launches), written to
 profiles/r21_sac_population.json: milliseconds per (replay.sample_groups, population.step) over P groups of 64 envs at the same shapes, and that time per member.
 No eager baseline: the figure to compare with is P lone steps.
-python tools/bench_sac.py --population 1 2 4 5 8 16 32 64"""
+python tools/bench_sac.py --population 1 2 4 5 8 16 32 64
+
+--distinct (with --population): every member gets its own learning rate, gamma, tau, target entropy and entropy coefficient (every third one fixed), so that the
+step reads a table the caller uploaded instead of the one the scalar arguments fill."""
 import argparse
 import json
 import os
@@ -29,6 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--blocks", type=int, default=7)
 ap.add_argument("--steps", type=int, default=200)
 ap.add_argument("--population", type=int, nargs="+", default=None, help="time a population of this many members (several: one after the other)")
+ap.add_argument("--distinct", action="store_true", help="with --population: distinct hyper-parameters per member")
 ap.add_argument("--out", default=None, help="default: profiles/r12_sac.json, with --population profiles/r21_sac_population.json")
 args = ap.parse_args()
 if args.out is None:
@@ -62,11 +66,15 @@ rng = np.random.RandomState(0)
 for P in args.population or ():
     for K in (6, 18):
         rb = full_buffer(rng, P * n_envs, K)
-        pop = SacPopulation(K, A, P, list(range(P)), net_arch=ARCH, learning_rate=LR, ent_coef="auto_0.2", batch_size=B)
+        hyper = dict(learning_rate=LR, ent_coef="auto_0.2")
+        if args.distinct:
+            hyper = dict(learning_rate=[LR * (1.0 + 0.1 * p) for p in range(P)], gamma=[0.99 - 0.001 * p for p in range(P)], tau=[0.005 + 0.001 * p for p in range(P)],
+                         ent_coef=[0.1 + 0.01 * p if p % 3 == 2 else "auto_%g" % (0.2 + 0.01 * p) for p in range(P)], target_entropy=[-float(A) - 0.1 * p for p in range(P)])
+        pop = SacPopulation(K, A, P, list(range(P)), net_arch=ARCH, batch_size=B, **hyper)
         pop.train(rb, args.steps)   # warm-up
         ms = [timed(lambda: pop.train(rb, args.steps)) / args.steps for _ in range(args.blocks)]
         med = float(np.median(ms))
-        out["population_%d_obs_%d" % (P, K)] = dict(n_members=P, obs_dim=K, ms_per_step=ms, ms_median=med, ms_spread=float(np.max(ms) - np.min(ms)), ms_per_member=med / P,
+        out["population_%d_obs_%d" % (P, K)] = dict(n_members=P, obs_dim=K, distinct=bool(args.distinct), ms_per_step=ms, ms_median=med, ms_spread=float(np.max(ms) - np.min(ms)), ms_per_member=med / P,
                                                    finite=bool(torch.isfinite(pop.p.params).all()), n_updates=pop.n_updates)
         print("population %2d, obs %2d: %.4f ms per population step (sampling included; blocks %s), %.4f ms per member" % (P, K, med, " ".join("%.4f" % x for x in ms), med / P))
         pop.close()

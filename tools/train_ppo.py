@@ -10,7 +10,13 @@ keeps the reference's batch size is the user's decision.
 a JSON line then carries a list `members` with an entry per seed.
 
 python tools/train_ppo.py --n-envs 256 --rollouts 10
-python tools/train_ppo.py --n-envs 50 --rollouts 10 --seeds 0 1 2 3 4"""
+python tools/train_ppo.py --n-envs 50 --rollouts 10 --seeds 0 1 2 3 4
+
+--sweep NAME=v1,v2,... (repeatable; NAME one of learning_rate, clip_range, clip_range_vf, ent_coef, vf_coef, max_grad_norm; "none" is clip_range_vf's None) crosses
+the values with each other and with --seeds (default: --seed alone) into one population, value-major and seed-minor.  Each entry of `members` then carries its
+own values under `hyper`; the model folders hold member_<p>.npz and population.npz, which names what varies.
+
+python tools/train_ppo.py --n-envs 60 --rollouts 10 --seeds 0 1 2 --sweep clip_range=0.1,0.2 --sweep ent_coef=0,0.01"""
 import argparse
 import json
 import os
@@ -19,7 +25,8 @@ import time
 
 sys.path.insert(0, '.')
 import human_robot_gym_amd as hrg   # noqa: E402
-from human_robot_gym_amd.training_utils import run_folder_from_args   # noqa: E402
+from human_robot_gym_amd.ppo import MAX_POPULATION, PpoPopulation   # noqa: E402
+from human_robot_gym_amd.training_utils import checked_sweep, member_lines, run_folder_from_args   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--env-id", default="ReachHuman")
@@ -36,6 +43,8 @@ ap.add_argument("--log-std-init", type=float, default=-2.7)
 ap.add_argument("--separate", action="store_true", help="net_arch [dict(pi=[64, 64], vf=[64, 64])] instead of the shared [64, 64]")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--seeds", type=int, nargs="+", default=None, help="a population: one member per seed, n-envs / len(seeds) envs each (the env itself is seeded with --seed)")
+ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...", help="a population over these values of a per-member hyper-parameter, crossed with "
+                "further --sweep options and with --seeds (value-major, seed-minor); n-envs / members envs each")
 ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
 ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
 ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
@@ -43,13 +52,20 @@ ap.add_argument("--eval-n-envs", type=int, default=64)
 ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
 
 
+def members_of(args):
+    """(the members' seeds, the members' values of the swept fields) of --seeds and --sweep; ValueError before any env is built."""
+    return checked_sweep(PpoPopulation, args.sweep, [args.seed] if args.seeds is None else args.seeds, args.n_envs, MAX_POPULATION)
+
+
 def main(args):
+    population = args.seeds is not None or args.sweep is not None
+    seeds, swept = members_of(args) if population else (None, {})
     env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
     env.attach_rollout(n_steps=args.n_steps, gamma=args.gamma, gae_lambda=args.gae_lambda)
     kw = dict(batch_size=args.batch_size, n_epochs=args.n_epochs, learning_rate=args.learning_rate, log_std_init=args.log_std_init, ortho_init=False,
               net_arch=[dict(pi=[64, 64], vf=[64, 64])] if args.separate else [64, 64])
-    if args.seeds is not None:
-        run_population(args, env, kw)
+    if population:
+        run_population(args, env, {**kw, **swept}, seeds, swept)
         env.close()
         return
     learner = env.attach_ppo(seed=args.seed, **kw)
@@ -67,10 +83,10 @@ def main(args):
     env.close()
 
 
-def run_population(args, env, kw):
-    """The loop of `main` for the members of --seeds."""
-    P = len(args.seeds)
-    pop = env.attach_ppo_population(P, seeds=args.seeds, **kw)
+def run_population(args, env, kw, seeds, swept):
+    """The loop of `main` for the members of --seeds and --sweep."""
+    P = len(seeds)
+    pop = env.attach_ppo_population(P, seeds=seeds, **kw)
     eval_env, first, saved_until = None, None, 0
     if args.eval_episodes > 0:
         eval_env = hrg.HipVecEnv(args.eval_n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed + 1 if args.eval_seed is None else args.eval_seed))
@@ -81,7 +97,7 @@ def run_population(args, env, kw):
         pop.train(env.rollout)
         env_steps = (k + 1) * args.n_steps * args.n_envs
         line = dict(rollout=k, env_steps=env_steps, seconds=round(time.time() - t0, 3))
-        members = [dict(seed=s, **stats, **diag) for s, stats, diag in zip(pop.seeds, env.rollout.episode_stats(groups=P), pop.diagnostics())]
+        members = member_lines(pop.seeds, swept, env.rollout.episode_stats(groups=P), pop.diagnostics())
         if eval_env is not None:
             for m, res in zip(members, eval_env.evaluate(pop.p.params, args.eval_episodes, learner=first).by_policy()):
                 m.update(eval_mean_reward=res.mean_reward, eval_std_reward=res.std_reward, eval_mean_ep_length=res.mean_ep_length)

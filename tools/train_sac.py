@@ -12,7 +12,13 @@ python tools/train_sac.py --n-envs 1024 --gradient-steps 800 --blocks 20
 acts in and learns from group p only and equals, bit for bit, the lone run of its seed on its group's transitions.  --learning-starts then counts a member's
 transitions; the JSON line carries `members`, one dict of episode stats and diagnostics per member; --model-dir receives model_<step>/member_<p>.npz.
 
-python tools/train_sac.py --n-envs 1280 --seeds 0 1 2 3 4 --gradient-steps 800 --blocks 5"""
+python tools/train_sac.py --n-envs 1280 --seeds 0 1 2 3 4 --gradient-steps 800 --blocks 5
+
+--sweep NAME=v1,v2,... (repeatable; NAME one of learning_rate, gamma, tau, ent_coef, target_entropy) crosses the values with each other and with --seeds (default:
+--seed alone) into one population, value-major and seed-minor: a sweep of V values x S seeds costs what V S seeds cost.  Each entry of `members` then carries its
+own values under `hyper`; the model folders hold member_<p>.npz and population.npz, which names what varies.
+
+python tools/train_sac.py --n-envs 1536 --seeds 0 1 2 --sweep learning_rate=1e-3,3e-4 --sweep ent_coef=auto_0.2,0.1 --gradient-steps 800 --blocks 5"""
 import argparse
 import json
 import os
@@ -22,7 +28,8 @@ import time
 sys.path.insert(0, '.')
 import torch   # noqa: E402
 import human_robot_gym_amd as hrg   # noqa: E402
-from human_robot_gym_amd.training_utils import run_folder_from_args   # noqa: E402
+from human_robot_gym_amd.sac import MAX_POPULATION, SacPopulation   # noqa: E402
+from human_robot_gym_amd.training_utils import checked_sweep, member_lines, run_folder_from_args   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--env-id", default="ReachHuman")
@@ -38,6 +45,8 @@ ap.add_argument("--learning-rate", type=float, default=5e-4)
 ap.add_argument("--ent-coef", default="auto_0.2")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--seeds", type=int, nargs="+", default=None, help="a population: one member per seed, n-envs / len(seeds) envs each (the env itself is seeded with --seed)")
+ap.add_argument("--sweep", action="append", default=None, metavar="NAME=v1,v2,...", help="a population over these values of a per-member hyper-parameter, crossed with "
+                "further --sweep options and with --seeds (value-major, seed-minor); n-envs / members envs each")
 ap.add_argument("--model-dir", default=None, help="models/<run_id>: checkpoints model_<step>.npz every --save-freq env steps and model_final.npz at the end")
 ap.add_argument("--save-freq", type=int, default=0, help="env steps between checkpoints (with --model-dir)")
 ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
@@ -45,14 +54,21 @@ ap.add_argument("--eval-n-envs", type=int, default=64)
 ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
 
 
+def members_of(args):
+    """(the members' seeds, the members' values of the swept fields) of --seeds and --sweep; ValueError before any env is built."""
+    return checked_sweep(SacPopulation, args.sweep, [args.seed] if args.seeds is None else args.seeds, args.n_envs, MAX_POPULATION)
+
+
 def main(args):
+    population = args.seeds is not None or args.sweep is not None
+    seeds, swept = members_of(args) if population else (None, {})
     env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
     env.attach_replay(args.buffer_size)
 
     def run_population():
         """The loop below for the members of --seeds."""
-        P = len(args.seeds)
-        pop = env.attach_sac_population(P, seeds=args.seeds, batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef)
+        P = len(seeds)
+        pop = env.attach_sac_population(P, seeds=seeds, **{**dict(batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef), **swept})
         gen = torch.Generator(device=pop.device).manual_seed(args.seed)
         uniform = lambda obs: torch.rand(obs.shape[0], pop.act_dim, generator=gen, device=obs.device) * 2.0 - 1.0   # noqa: E731
         eval_env, first, saved_until = None, None, 0
@@ -68,10 +84,7 @@ def main(args):
                 pop.train(env.replay, args.gradient_steps)
             env_steps = (block + 1) * args.train_freq * args.n_envs
             line = dict(block=block, env_steps=env_steps, policy="uniform" if warm else "actor", seconds=round(time.time() - t0, 3))
-            members = [dict(seed=s, **stats) for s, stats in zip(pop.seeds, env.replay.episode_stats(groups=P))]
-            if pop.n_updates:
-                for m, diag in zip(members, pop.diagnostics()):
-                    m.update(diag)
+            members = member_lines(pop.seeds, swept, env.replay.episode_stats(groups=P), *([pop.diagnostics()] if pop.n_updates else []))
             if eval_env is not None:
                 for m, res in zip(members, eval_env.evaluate(pop.p.params, args.eval_episodes, learner=first).by_policy()):
                     m.update(eval_mean_reward=res.mean_reward, eval_std_reward=res.std_reward, eval_mean_ep_length=res.mean_ep_length)
@@ -86,7 +99,7 @@ def main(args):
             first.close()
             eval_env.close()
 
-    if args.seeds is not None:
+    if population:
         run_population()
         env.close()
         return
