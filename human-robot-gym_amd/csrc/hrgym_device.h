@@ -43,6 +43,10 @@
 #ifndef HRG_HAMMER
 #define HRG_HAMMER 0  // HRG_HAMMER=1 (hrgym_hammer.hip, HRG_BOX=0): CollaborativeHammeringCart -- board + nail + hammer, a 24-DoF system in three 8-wide blocks; its own collision tail and solver
 #endif
+// ReachHumanCart (HRG_TASK_REACH_CART) is stepped by the plain cube kernels alone (hrgym_box.hip, hrgym_box_hulls.hip): in every other unit the test is false at
+// compile time, so the handover and lifting kernels carry none of the task's branches.
+#define HRG_CART (HRG_BOX && !HRG_HANDOVER && !HRG_LIFT)
+#define HRG_IS_REACH_CART(task) (HRG_CART && (task) == HRG_TASK_REACH_CART)
 #define HRG_BASE_TU (!HRG_BOX && !HRG_STACK && !HRG_HAMMER && !HRG_HULLS)   // hrgym_hip.hip itself: the ReachHuman kernels, the pre-check kernel and the host side (C ABI: hrgym_host*.h)
 // The name of this translation unit's kernel variant: <stem><family><hull>, family = the task's kernel family, hull = the arm links' collision geometry.  HRG_SYM names
 // the kernels (hrg_step_kernel_lift_hull), their launch shims and the -DHRG_STAMPS exports; the host side lists the twelve combinations once (HRG_VARIANTS, hrgym_host_batch.h).

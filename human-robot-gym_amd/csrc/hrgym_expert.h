@@ -113,6 +113,17 @@ DI void expert_hammering(const float* __restrict__ o, double* a) {
   a[3] = 1.0;
 }
 
+// ReachHumanCartExpert.__call__ (reach_human_cart_expert.py:70-87): the end effector moves straight to the goal position (goal_difference[0:3]); gripper action 0
+DI void expert_reach_cart(const hrg_expert_desc& p, const float* __restrict__ o, const double* y, double* a) {
+  const double lim = p.act_high[0], snr = p.signal_to_noise_ratio;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double m = expert_clip((double)o[EXO_GOAL_DIFF + k], -lim, lim);
+    a[k] = expert_clip(snr * m + y[k] * (1.0 - snr), -lim, lim);
+  }
+  a[3] = 0.0;
+}
+
 // similarity_fn (utils/expert_imitation_reward_utils.py:51-73)
 DI double expert_similarity(int fn, double delta, double iota) {
   if (fn == HRG_SIM_TANH) return -tanh(HRG_EXPERT_TAN_HALF * delta / iota) + 1.0;
@@ -137,6 +148,7 @@ __global__ __launch_bounds__(HRG_EXPERT_BLOCK) void hrg_expert_pre_kernel(const 
   } else {
     expert_ou_step<3>(p, 0.5, p.act_high[0] * 0.5, gid, yrow, ou_calls + e, y);
     if (p.expert == HRG_EXPERT_PICK_PLACE) expert_pick_place(p, o, y, a);
+    else if (p.expert == HRG_EXPERT_REACH_CART) expert_reach_cart(p, o, y, a);
     else expert_lifting(p, o, y, a);
   }
   double* out = act_out + (size_t)e * HRG_ACT_DIM;

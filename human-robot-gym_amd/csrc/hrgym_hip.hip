@@ -1698,7 +1698,39 @@ DI bool config_collides(const DevModel* __restrict__ dm_, int lane) {
   return any;
 }
 
+#if HRG_CART
+// End-effector (grip site) position of the configuration in L.cq (PinocchioManipulatorModel.get_eef_transformation, reach_human_cartesian_env.py:457): lane 0 walks
+// the chain as config_collides does -> three doubles of shield scratch behind that function's capsules.
+DI const double* config_eef(const DevModel* __restrict__ dm_, int lane) {
+  const ModelPtr dm = uniform_model(dm_);
+  Lds& L = g_L;
+  const auto& m = dm->m;
+  double* ee = &L.scap[0][0][0] + 6 * NCAP_CHECK;
+  static_assert(6 * NCAP_CHECK + 3 <= 2 * HRG_NSHIELD_RCAP * 6, "config_eef: the shield scratch holds the check capsules and the eef position");
+  if (lane == 0) {
+    double R[9], p[3], t[3];
+    for (int k = 0; k < 9; k++) R[k] = dm->Rbase[k];
+    v3cpy(p, m.base_pos);
+#pragma unroll 1
+    for (int i = 0; i < NARM; i++) {
+      double Rl[9], Rj[9];
+      m3mul(Rl, R, dm->Rq[i]);
+      m3mulv(t, R, m.body_pos[i]);
+      v3add(p, p, t);
+      axisangle2mat(Rj, m.jnt_axis[i], L.cq[i]);
+      m3mul(R, Rl, Rj);
+    }
+    m3mulv(t, R, m.eef_pos);
+    v3add(ee, p, t);
+  }
+  wave_sync();
+  return ee;
+}
+#endif
+
 // ReachHuman._sample_valid_pos (reach_human_env.py:525-548) -> L.st.cur_goal
+// ReachHumanCart._sample_valid_pos (reach_human_cartesian_env.py:436-465): a candidate also has to put the end effector inside sampling_space; L.bx.target is the
+// accepted goal's eef position (goal_marker_trans = desired_goal), and after 20 rejected candidates the goal is the initial posture
 DI void goal_sample(const DevModel* __restrict__ dm_, int lane, int64_t gid, int idx) {
   const ModelPtr dm = uniform_model(dm_);
   Lds& L = g_L;
@@ -1711,13 +1743,31 @@ DI void goal_sample(const DevModel* __restrict__ dm_, int lane, int64_t gid, int
       L.cq[lane] = m.qpos_limits[0][lane] + (m.qpos_limits[1][lane] - m.qpos_limits[0][lane]) * u;
     }
     wave_sync();
-    const bool bad = m.goal_check && config_collides(dm_, lane);
+    bool bad = m.goal_check && config_collides(dm_, lane);
+#if HRG_CART
+    if (m.task == HRG_TASK_REACH_CART && !bad) {
+      const double* ee = config_eef(dm_, lane);
+      for (int a = 0; a < 3; a++) bad = bad || !(ee[a] >= m.sampling_space[0][a] && ee[a] <= m.sampling_space[1][a]);
+      if (!bad && lane < 3) L.bx.target[lane] = ee[lane];
+    }
+#endif
     if (!bad) {
       if (lane < NARM) s.cur_goal[lane] = L.cq[lane];
       wave_sync();
       return;
     }
   }
+#if HRG_CART
+  if (m.task == HRG_TASK_REACH_CART) {
+    wave_sync();
+    if (lane < NARM) { L.cq[lane] = m.init_qpos[lane]; s.cur_goal[lane] = m.init_qpos[lane]; }
+    wave_sync();
+    const double* ee = config_eef(dm_, lane);
+    if (lane < 3) L.bx.target[lane] = ee[lane];
+    wave_sync();
+    return;
+  }
+#endif
   if (lane < NARM) s.cur_goal[lane] = 0.0;
   wave_sync();
 }
@@ -1942,10 +1992,27 @@ DI void write_obs(const DevModel* __restrict__ dm_, int lane, const double* goal
 #if HRG_BOX
     // PickPlaceHumanCart._setup_observables (pick_place_human_cartesian_env.py:726-841), gripper_aperture (human_env.py:1508-1524)
     const hrg_box_state& bx = L.bx;
-    if (m.task == HRG_TASK_REACH_BOX) {}   // ReachHuman does not observe its smallBox: the ReachHuman layout above stands
+    const bool reach_layout = m.task == HRG_TASK_REACH_BOX || HRG_IS_REACH_CART(m.task);
+    if (reach_layout) {}   // ReachHuman does not observe its smallBox: the ReachHuman layout above stands
     else
     if ((lane >= 12 && lane < 18) || (lane >= 33 && lane < 39)) v = 0.0;
-    if (m.task == HRG_TASK_REACH_BOX) {}
+#if HRG_CART
+    if (m.task == HRG_TASK_REACH_CART) {   // ReachHumanCart._setup_observables (reach_human_cartesian_env.py:385-434): the goal is the eef position L.bx.target
+      if (lane >= 12 && lane < 15) v = bx.target[lane - 12] - s.eef_pos[lane - 12];   // goal_difference
+      else if (lane >= 33 && lane < 36) v = bx.target[lane - 33];                     // desired_goal
+      else if ((lane >= 15 && lane < 18) || (lane >= 36 && lane < 39)) v = 0.0;
+      else if (lane >= 40 && lane < 43) {   // robot0_eef_velp: site_xvelp of the grip site from the frames of the last forward pass, sum_j (axis_j x (p_eef - p_j)) qvel_j
+        const int a = lane - 40, a1 = (a + 1) % 3, a2 = (a + 2) % 3;
+        v = 0.0;
+        for (int j = 0; j < NARM; j++) {
+          double ax[3];
+          m3mulv(ax, L.kR[j], m.jnt_axis[j]);
+          v += (ax[a1] * (s.eef_pos[a2] - L.kp[j][a2]) - ax[a2] * (s.eef_pos[a1] - L.kp[j][a1])) * s.qvel[j];
+        }
+      }
+    }
+#endif
+    if (reach_layout) {}
     else
     if (lane >= 12 && lane < 16) v = bx.quat[lane == 15 ? 0 : lane - 11];   // object_quat, (x, y, z, w) like T.convert_quat(..., to="xyzw") (human_robot_handover_cartesian_env.py:849-858)
     else if (lane == 39) v = (double)bx.gripped;
@@ -2233,7 +2300,7 @@ __device__ __noinline__ void env_reset(const DevModel* __restrict__ dm_, int lan
     }
 #endif
   }
-  if (m.task == HRG_TASK_REACH_BOX) goal_sample(dm_, lane, gid, 0);   // ReachHuman with its smallBox: the reach goals of ReachHuman._reset_internal
+  if (m.task == HRG_TASK_REACH_BOX || HRG_IS_REACH_CART(m.task)) goal_sample(dm_, lane, gid, 0);   // ReachHuman with its smallBox: the reach goals of ReachHuman._reset_internal (ReachHumanCart: L.bx.target too)
 #elif HRG_STACK
   { // CollaborativeStackingCart._reset_internal (938-959): the robot's cubes in their bin, the human's cubes in the hands, phase APPROACH
     hrg_stack_state& sk = L.sk;
@@ -2606,6 +2673,13 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
     goal_reached = !crash && reach_dist <= m.goal_dist;
     r = goal_reached ? m.task_reward : -1.0;
   }
+  if (m.task == HRG_TASK_REACH_CART) {   // ReachHumanCart: achieved goal = robot0_eef_pos, desired goal = goal_marker_trans (reach_human_cartesian_env.py:338-378)
+    double dist2 = 0;
+    for (int a = 0; a < 3; a++) dist2 += (s.eef_pos[a] - bx.target[a]) * (s.eef_pos[a] - bx.target[a]);
+    reach_dist = fsqrt(dist2);
+    goal_reached = !crash && reach_dist <= m.goal_dist;
+    r = goal_reached ? m.task_reward : -1.0;
+  }
 #endif
 #if HRG_HANDOVER
   if (m.task == HRG_TASK_HANDOVER_R2H)   // robot_human_handover_cartesian_env.py:507-555
@@ -2613,7 +2687,7 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
 #endif
   double dense = -(fsqrt(e2o) * 0.2 + fsqrt(o2t)) * 0.1;
 #if !HRG_HANDOVER && !HRG_LIFT
-  if (m.task == HRG_TASK_REACH_BOX) dense = -0.1 * reach_dist;
+  if (m.task == HRG_TASK_REACH_BOX || m.task == HRG_TASK_REACH_CART) dense = -0.1 * reach_dist;
 #endif
 #if HRG_LIFT
   double balance = 1.0;
@@ -2799,8 +2873,8 @@ DI int env_step(const DevModel* __restrict__ dm_, int lane, int e, int64_t own_g
     wave_sync();
   } else
 #if !HRG_HANDOVER && !HRG_LIFT
-  if (m.task == HRG_TASK_REACH_BOX) {
-    if (goal_reached && !d) { // reach_human_env.py:399-407
+  if (m.task == HRG_TASK_REACH_BOX || m.task == HRG_TASK_REACH_CART) {
+    if (goal_reached && !d) { // reach_human_env.py:399-407 (ReachHumanCart: goal_sample moves L.bx.target along)
       s.goal_index = (s.goal_index + 1) % m.n_goals;
       goal_sample(dm_, lane, gid, s.goal_index);   // (the step's observation, written above, still shows the goal that was reached)
     }

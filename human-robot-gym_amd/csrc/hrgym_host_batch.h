@@ -152,7 +152,7 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
   for (int c = 0; c < HRG_NSHIELD_RCAP; c++)
     if (desc->scap_body[c] != (c < NARM ? c : NARM - 1)) return fail(HRG_ERR_INVALID, "shield capsule c must sit on link c (gripper on link 6)");
   if (desc->n_bodypart > HRG_NBODYPART_MAX || desc->n_extremity > HRG_NEXTREMITY_MAX) return fail(HRG_ERR_INVALID, "too many body parts");
-  if (desc->task < HRG_TASK_REACH || desc->task > HRG_TASK_HAMMERING) return fail(HRG_ERR_UNSUPPORTED, "unknown task");
+  if (desc->task < HRG_TASK_REACH || desc->task > HRG_TASK_REACH_CART) return fail(HRG_ERR_UNSUPPORTED, "unknown task");
   if (desc->task == HRG_TASK_STACKING) {
     if (!(desc->box_inertia[0] == desc->box_inertia[1] && desc->box_inertia[1] == desc->box_inertia[2]))
       return fail(HRG_ERR_UNSUPPORTED, "CollaborativeStackingCart: the HIP stepper stacks cubes (object_full_size with three equal edges)");
@@ -204,8 +204,8 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
   if (tot != clips->total_frames) return fail(HRG_ERR_INVALID, "clip table total_frames mismatch");
   if (desc->robot_hulls) {
     // every kernel has a hull variant: ReachHuman (hrg_step_kernel_hull), the cube tasks (_box_hull: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman
-    // with its box), the handover tasks (_ho_hull), lifting (_lift_hull), stacking (_stack_hull) and hammering (_hammer_hull)
-    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX ||
+    // with its box, ReachHumanCart), the handover tasks (_ho_hull), lifting (_lift_hull), stacking (_stack_hull) and hammering (_hammer_hull)
+    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX || desc->task == HRG_TASK_REACH_CART ||
           HRG_IS_HANDOVER(desc->task) || desc->task == HRG_TASK_LIFTING || desc->task == HRG_TASK_STACKING || desc->task == HRG_TASK_HAMMERING))
       return fail(HRG_ERR_UNSUPPORTED, "robot_hulls: no hull variant of the step kernel for this task");
     if (!desc->hull_verts || desc->hull_off[0] != 0) return fail(HRG_ERR_INVALID, "robot_hulls: hull_verts / hull_off missing");
@@ -522,6 +522,7 @@ static bool expert_fits_task(int expert, int task) {
     case HRG_EXPERT_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || task == HRG_TASK_STACKING || HRG_IS_HANDOVER(task);   // PP-AIR, CS-AIR, HRH-AIR, RHH-AIR
     case HRG_EXPERT_LIFTING: return task == HRG_TASK_LIFTING;
     case HRG_EXPERT_HAMMERING: return task == HRG_TASK_HAMMERING;
+    case HRG_EXPERT_REACH_CART: return task == HRG_TASK_REACH_CART;
   }
   return false;
 }
@@ -529,7 +530,7 @@ static bool expert_fits_task(int expert, int task) {
 int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc) {
   if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
   b->has_expert = false;   // until the descriptor has passed and every buffer below exists and is zeroed: a refused attach leaves no expert attached
-  if (desc->expert < HRG_EXPERT_REACH || desc->expert > HRG_EXPERT_HAMMERING) return fail(HRG_ERR_UNSUPPORTED, "unknown expert");
+  if (desc->expert < HRG_EXPERT_REACH || desc->expert > HRG_EXPERT_REACH_CART) return fail(HRG_ERR_UNSUPPORTED, "unknown expert");
   if (!expert_fits_task(desc->expert, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this expert does not read the observation of the batch's task");
   if ((desc->cartesian != 0) != (desc->expert != HRG_EXPERT_REACH)) return fail(HRG_ERR_UNSUPPORTED, "ReachHumanExpert acts in joint space, every other expert in Cartesian space");
   if ((desc->cartesian != 0) != b->ik) return fail(HRG_ERR_UNSUPPORTED, "the expert's action form is not the batch's (Cartesian experts need the IK front-end, ik_enabled)");
@@ -591,7 +592,7 @@ static bool dataset_task_ok(int task) { return task != HRG_TASK_STACKING && task
 static bool sir_fits_task(int kind, int task) {
   switch (kind) {
     case HRG_SIR_NONE: return true;
-    case HRG_SIR_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
+    case HRG_SIR_REACH: return task == HRG_TASK_REACH || task == HRG_TASK_REACH_CART;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns; ReachHumanCart: three goal_difference columns, the other three zero
     case HRG_SIR_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || HRG_IS_HANDOVER(task);   // "any environment that can be solved using the PickPlaceHumanCartExpert"
     case HRG_SIR_LIFTING: return task == HRG_TASK_LIFTING;
   }

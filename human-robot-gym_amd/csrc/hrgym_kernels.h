@@ -1742,7 +1742,7 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
 DI int geom_class(int g, int task) {
   if (g < HRG_NRCAP) return HRG_GEOM_ROBOT;
   if (g < GEOM_TABLE) return HRG_GEOM_HUMAN;
-  if (g < GEOM_BOX || task == HRG_TASK_REACH_BOX) return HRG_GEOM_STATIC;
+  if (g < GEOM_BOX || task == HRG_TASK_REACH_BOX || HRG_IS_REACH_CART(task)) return HRG_GEOM_STATIC;
   if (task == HRG_TASK_HAMMERING) return g == GEOM_BOX + HRG_HG_HANDLE || g == GEOM_BOX + HRG_HG_HEAD ? HRG_GEOM_ALLOWED : HRG_GEOM_STATIC;
   return HRG_GEOM_ALLOWED;
 }

@@ -27,7 +27,7 @@ STATE_BYTES, BOX_BYTES = ctypes.sizeof(EnvState), ctypes.sizeof(BoxState)
 NO_DATASET_ENVS = ("CollaborativeStackingCart", "CollaborativeHammeringCart")   # their state lives in further arrays (hrg_stack_state, hrg_hammer_state)
 # StateBasedExpertImitationRewardWrapper subclass per task (state_based_expert_imitation_reward_wrapper.py; the pick-place wrapper serves "any environment
 # that can be solved using the PickPlaceHumanCartExpert")
-SIR_KINDS = {"ReachHuman": CONST["HRG_SIR_REACH"], "PickPlaceHumanCart": CONST["HRG_SIR_PICK_PLACE"], "HumanRobotHandoverCart": CONST["HRG_SIR_PICK_PLACE"],
+SIR_KINDS = {"ReachHuman": CONST["HRG_SIR_REACH"], "ReachHumanCart": CONST["HRG_SIR_REACH"], "PickPlaceHumanCart": CONST["HRG_SIR_PICK_PLACE"], "HumanRobotHandoverCart": CONST["HRG_SIR_PICK_PLACE"],
              "RobotHumanHandoverCart": CONST["HRG_SIR_PICK_PLACE"], "CollaborativeLiftingCart": CONST["HRG_SIR_LIFTING"]}
 SIR_COLUMNS = ("r_im", "r_env", "r_motion", "r_gripper", "r_full", "ep_im", "ep_env", "ep_motion", "ep_gripper", "ep_len", "ep_len_mg", "early", "time",
                "time_obs")   # HRG_SIR_*

@@ -9,9 +9,10 @@ import numpy as np
 
 from ._cstruct import CONST, ExpertDesc
 
-# REGISTERED_EXPERTS (demonstrations/experts/__init__.py:8-14) -> HRG_EXPERT_*; ReachHumanCart has no environment in this package
+# REGISTERED_EXPERTS (demonstrations/experts/__init__.py:8-14) -> HRG_EXPERT_*
 EXPERT_IDS = {"ReachHuman": CONST["HRG_EXPERT_REACH"], "PickPlaceHumanCart": CONST["HRG_EXPERT_PICK_PLACE"],
-              "CollaborativeLiftingCart": CONST["HRG_EXPERT_LIFTING"], "CollaborativeHammeringCart": CONST["HRG_EXPERT_HAMMERING"]}
+              "CollaborativeLiftingCart": CONST["HRG_EXPERT_LIFTING"], "CollaborativeHammeringCart": CONST["HRG_EXPERT_HAMMERING"],
+              "ReachHumanCart": CONST["HRG_EXPERT_REACH_CART"]}
 _REQUIRED = object()
 # constructor arguments and their defaults, per expert class
 EXPERT_KWARGS = {
@@ -20,6 +21,7 @@ EXPERT_KWARGS = {
                                gripper_fully_opened_threshold=0.02, release_when_delivered=True, delta_time=0.01, seed=None),
     "CollaborativeLiftingCart": dict(signal_to_noise_ratio=_REQUIRED, board_size=_REQUIRED, human_grip_offset=0.1, delta_time=0.01, seed=None),
     "CollaborativeHammeringCart": dict(signal_to_noise_ratio=1.0, delta_time=0.1, seed=None),
+    "ReachHumanCart": dict(signal_to_noise_ratio=1.0, delta_time=0.01, seed=None),
 }
 # the tasks whose observation an expert reads (CS-AIR, HRH-AIR, RHH-AIR run the pick-place expert)
 EXPERT_ENVS = {
@@ -27,6 +29,7 @@ EXPERT_ENVS = {
     "PickPlaceHumanCart": ("PickPlaceHumanCart", "CollaborativeStackingCart", "HumanRobotHandoverCart", "RobotHumanHandoverCart"),
     "CollaborativeLiftingCart": ("CollaborativeLiftingCart",),
     "CollaborativeHammeringCart": ("CollaborativeHammeringCart",),
+    "ReachHumanCart": ("ReachHumanCart",),
 }
 SIM_FNS = {"gaussian": CONST["HRG_SIM_GAUSSIAN"], "tanh": CONST["HRG_SIM_TANH"]}
 IMITATION_REWARD_KWARGS = dict(alpha=0.0, beta=0.0, iota_m=0.1, iota_g=0.25, m_sim_fn="gaussian", g_sim_fn="gaussian", normalize_joint_actions=False)   # the last: Joint form only
@@ -38,8 +41,6 @@ def expert_kwargs(expert):
     kw = dict(expert)
     eid = kw.pop("id", None)
     kw.pop("obs_keys", None)
-    if eid == "ReachHumanCart":
-        raise NotImplementedError("expert ReachHumanCart: there is no ReachHumanCart environment in this package")
     if eid not in EXPERT_KWARGS:
         raise NotImplementedError(f"expert id {eid!r}: available {sorted(EXPERT_KWARGS)}")
     known = EXPERT_KWARGS[eid]

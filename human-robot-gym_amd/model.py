@@ -57,6 +57,17 @@ DEFAULT_ENV_KWARGS = dict(
     seed=0,
 )
 
+# ReachHumanCart: config/environment/reach_human_cart.yaml, which composes default/reach_human_cart.yaml (goal_dist, table_friction) over default/reach_human.yaml
+# and repeats reach_human.yaml's own keys.  init_joint_pos is the constructor's default (reach_human_cartesian_env.py:280); sampling_space is an attribute the
+# reference's constructor sets (283) -- a keyword here: [lower corner, upper corner] of the box a goal's end-effector position has to lie in
+REACH_CART_ENV_KWARGS = dict(
+    DEFAULT_ENV_KWARGS,
+    goal_dist=0.05,
+    table_full_size=[1.5, 2.0, 0.05],     # default/reach_human.yaml: the arena compiled into the asset tables; accepted at this value only, like table_friction
+    table_friction=[1.0, 5e-3, 1e-4],
+    init_joint_pos=[0.0, 0.0, -math.pi / 2, 0.0, -math.pi / 2, math.pi / 4],
+    sampling_space=[[0.1, -0.5, 0.8], [0.5, 0.5, 1.3]],
+)
 # PickPlaceHumanCart constructor defaults overlaid with config/environment/pick_place_human_cart.yaml (+ default/human_env.yaml)
 PICK_PLACE_ENV_KWARGS = dict(
     DEFAULT_ENV_KWARGS,
@@ -189,7 +200,7 @@ HAMMERING_ENV_KWARGS = dict(
     hammer_anchors=[[-0.1, 0.2, 0.0], [-0.5, -0.2, 0.0]],   # l_anchor / r_anchor of _postprocess_model (1001-1002)
     hammer_weld_relquat=[0.0, 0.0, 0.0, 1.0],               # relpose of rh_eq: "0 0 0 0 0 0 1" (1123-1131)
 )
-ENV_DEFAULTS = {"CollaborativeHammeringCart": HAMMERING_ENV_KWARGS, "CollaborativeStackingCart": STACKING_ENV_KWARGS, "CollaborativeLiftingCart": LIFTING_ENV_KWARGS, "ReachHuman": DEFAULT_ENV_KWARGS, "PickPlaceHumanCart": PICK_PLACE_ENV_KWARGS, "HumanRobotHandoverCart": HANDOVER_H2R_ENV_KWARGS,
+ENV_DEFAULTS = {"CollaborativeHammeringCart": HAMMERING_ENV_KWARGS, "CollaborativeStackingCart": STACKING_ENV_KWARGS, "CollaborativeLiftingCart": LIFTING_ENV_KWARGS, "ReachHuman": DEFAULT_ENV_KWARGS, "ReachHumanCart": REACH_CART_ENV_KWARGS, "PickPlaceHumanCart": PICK_PLACE_ENV_KWARGS, "HumanRobotHandoverCart": HANDOVER_H2R_ENV_KWARGS,
                 "RobotHumanHandoverCart": HANDOVER_R2H_ENV_KWARGS,
                 "PickPlaceCloseHumanCart": PICK_PLACE_CLOSE_ENV_KWARGS, "PickPlacePointingHumanCart": POINTING_ENV_KWARGS,
                 "HumanObjectInspectionCart": INSPECTION_ENV_KWARGS}
@@ -295,6 +306,10 @@ def _seg_seg_dist(p1, q1, p2, q2):
     return float(np.linalg.norm((p1 + s * d1) - (p2 + t * d2)))
 
 
+def _same_list(a, b):
+    return len(a) == len(b) and all(float(x) == float(y) for x, y in zip(a, b))
+
+
 def load_assets(name="reach_human_schunk.json"):
     with open(os.path.join(_ASSETS, name)) as f:
         return json.load(f)
@@ -340,7 +355,7 @@ def load_robot_hulls():
 
 def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None, collision_prevention=None, goal_check=True,
                      env_id="ReachHuman", ik_position_delta=None, reach_box=False, robot_geometry="capsule"):
-    """Return a filled `ModelDesc` for `env_id` ("ReachHuman" or "PickPlaceHumanCart") on the Schunk arm.
+    """Return a filled `ModelDesc` for `env_id` (a key of ENV_DEFAULTS) on the Schunk arm.
 
     `env_kwargs` takes the same keys as the reference's environment config
     (training/config/environment/reach_human.yaml, default/human_env.yaml).
@@ -624,10 +639,22 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
     for f in range(CONST["HRG_NFINGER"]):
         d.finger_qpos_range[0][f], d.finger_qpos_range[1][f] = FINGER_QPOS_RANGE[0][f], FINGER_QPOS_RANGE[1][f]
     d.task = CONST["HRG_TASK_REACH"]
-    if reach_box:
-        if env_id != "ReachHuman":
-            raise ValueError("reach_box: the smallBox object belongs to ReachHuman")
+    if reach_box and env_id != "ReachHuman":
+        raise ValueError("reach_box: the smallBox object belongs to ReachHuman")   # (ReachHumanCart always steps with it)
+    if reach_box or env_id == "ReachHumanCart":
         d.task = CONST["HRG_TASK_REACH_BOX"]
+        if env_id == "ReachHumanCart":   # ReachHuman's world, the goal an end-effector position (reach_human_cartesian_env.py)
+            d.task = CONST["HRG_TASK_REACH_CART"]
+            for k in ("table_friction", "table_full_size"):   # (a settings file read without OmegaConf hands 5e-3 over as a string)
+                if not _same_list(kw[k], ENV_DEFAULTS[env_id][k]):
+                    raise NotImplementedError(f"{env_id}: env kwarg {k}={kw[k]!r} is not implemented by the HIP stepper (only {ENV_DEFAULTS[env_id][k]!r})")
+            q0 = np.asarray(kw["init_joint_pos"], float).ravel()
+            sp_ = np.asarray(kw["sampling_space"], float)
+            if q0.shape != (NARM,) or sp_.shape != (2, 3):
+                raise ValueError(f"{env_id}: init_joint_pos takes {NARM} joint angles, sampling_space [[x, y, z] lower, [x, y, z] upper]")
+            d.init_qpos[:] = q0.tolist()   # _reset_internal (380-383)
+            for c in range(2):
+                d.sampling_space[c][:] = sp_[c].tolist()
         size = [0.05, 0.05, 0.05]                       # box_size of reach_human_env.py:573
         half = [0.5 * x for x in size]
         d.box_half[:] = half

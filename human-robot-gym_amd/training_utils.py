@@ -147,7 +147,9 @@ def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
             from .expert import expert_kwargs
             ek = dict(_plain(expert))   # _compose_expert_kwargs / create_expert (training_utils.py:138-174): id selects the class, obs_keys is dropped
             ek.pop("obs_keys", None)
-            expert_kwargs(ek)           # unknown ids (ReachHumanCart: no such environment here) and arguments raise now, not at the first step
+            if ek.get("id") == "ReachHumanCart" and _get(_get(config, "environment"), "env_id") != "ReachHumanCart":
+                raise NotImplementedError("expert ReachHumanCart reads the goal_difference of the ReachHumanCart environment only (config.environment.env_id)")
+            expert_kwargs(ek)           # unknown ids and arguments raise now, not at the first step
             out["expert"] = ek
             out["imitation_reward"] = abk
     dn = _get(w, "dataset_obs_norm")

@@ -82,7 +82,7 @@ STACKING_OBS_KEYS = ["object_gripped", "vec_eef_to_all_objects", "gripper_apertu
 LIFTING_OBS_KEYS = ["board_quat", "dist_eef_to_human_head", "vec_eef_to_human_lh", "vec_eef_to_human_rh"]   # CL-SAC.yaml run.obs_keys
 HAMMERING_OBS_KEYS = ["hammer_gripped", "vec_eef_to_nail", "nail_hammering_progress", "vec_eef_to_board", "board_quat", "dist_eef_to_human_head", "dist_eef_to_human_lh",
                       "dist_eef_to_human_rh"]   # no run config ships for this task; the expert reads vec_eef_to_nail (collaborative_hammering_cart_expert.py:24-25)
-_TASK_OBS_KEYS = {"ReachHuman": OBS_KEYS, "CollaborativeLiftingCart": LIFTING_OBS_KEYS, "CollaborativeStackingCart": STACKING_OBS_KEYS,
+_TASK_OBS_KEYS = {"ReachHuman": OBS_KEYS, "ReachHumanCart": OBS_KEYS, "CollaborativeLiftingCart": LIFTING_OBS_KEYS, "CollaborativeStackingCart": STACKING_OBS_KEYS,
                   "CollaborativeHammeringCart": HAMMERING_OBS_KEYS}
 DEFAULT_OBS_KEYS = {k: _TASK_OBS_KEYS.get(k, PICK_PLACE_OBS_KEYS) for k in ENV_DEFAULTS}   # the pick-place, inspection and handover tasks: the pick-place keys
 # columns of the kernel's observation superset (include/hrgym.h HRG_OBS_DIM) per robosuite observable / modality key
@@ -120,6 +120,10 @@ OBS_COLUMNS_TASK = {
         "quat_eef_to_hammer": [62, 63, 62, 63], "quat_eef_to_board": [62, 63, 62, 63],
         "desired_goal": range(50, 53),   # _get_desired_goal_from_obs: nail_pos (606-621)
     },
+    "ReachHumanCart": {   # reach_human_cartesian_env.py:385-434: the ReachHuman layout, the goal an end-effector position (three values; the other three columns are zero)
+        "goal_difference": range(12, 15), "desired_goal": range(33, 36), "robot0_eef_velp": range(40, 43),
+        "goal-state": list(range(33, 36)) + list(range(12, 15)),
+    },
 }
 for _k in ("hammer_quat", "hammer_gripped", "vec_eef_to_hammer", "vec_eef_to_nail", "hammer_pos", "nail_pos", "nail_hammering_progress", "quat_eef_to_hammer"):
     OBS_COLUMNS.setdefault(_k, OBS_COLUMNS_TASK["CollaborativeHammeringCart"][_k])
@@ -129,7 +133,7 @@ OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (h
 def task_columns(env_id):
     """OBS_COLUMNS as `env_id` fills them."""
     cols_of = dict(OBS_COLUMNS)
-    if env_id != "ReachHuman":
+    if env_id not in ("ReachHuman", "ReachHumanCart"):
         cols_of["desired_goal"] = OBS_COLUMNS["target_pos"]   # _get_desired_goal_from_obs of the cube tasks
     cols_of.update(OBS_COLUMNS_TASK.get(env_id, {}))
     return cols_of
@@ -501,9 +505,11 @@ class HipVecEnv(_VecEnvBase):
                 raise NotImplementedError("goal_env: this task's success is a task phase, not a function of the goals")
             self._ag_cols = np.array(list(range(18, 24)) if env_id == "ReachHuman" else [30, 31, 32, 47, 48, 49, 39], dtype=np.int64)
             self._dg_cols = np.array(list(range(33, 39)) if env_id == "ReachHuman" else [50, 51, 52], dtype=np.int64)
-        unknown = [k for k in keys or [] if k not in OBS_COLUMNS]
+            if env_id == "ReachHumanCart":   # achieved goal = robot0_eef_pos, desired goal = the goal's eef position (reach_human_cartesian_env.py:338-378)
+                self._ag_cols, self._dg_cols = np.array([30, 31, 32], dtype=np.int64), np.array([33, 34, 35], dtype=np.int64)
+        unknown = [k for k in keys or [] if k not in OBS_COLUMNS and k not in cols_of]   # (a key of OBS_COLUMNS_TASK alone, robot0_eef_velp, exists on its task only)
         if unknown:
-            raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(OBS_COLUMNS)}")
+            raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(set(OBS_COLUMNS) | set(cols_of))}")
         self.obs_keys = list(keys) if keys is not None else None
         # ExpertObsWrapper (wrappers/expert_obs_wrapper.py:155-184): infos carry the expert's view of the state before and after the step
         bad = [k for k in (expert_obs_keys or []) if k not in OBS_COLUMNS]
@@ -859,7 +865,7 @@ class HipVecEnv(_VecEnvBase):
         ag, dg = np.atleast_2d(np.asarray(achieved_goal, np.float64)), np.atleast_2d(np.asarray(desired_goal, np.float64))
         infos = [info] if isinstance(info, dict) else list(info)
         ctype = np.array([int(i.get("collision_type", 0)) for i in infos])
-        if self.env_id == "ReachHuman":
+        if self.env_id in ("ReachHuman", "ReachHumanCart"):   # joint angles / eef positions: the Euclidean distance of the goals
             dist = np.linalg.norm(ag - dg, axis=-1)
             r = np.where(dist <= d.goal_dist, d.task_reward, -1.0)
             dense = -0.1 * dist
@@ -884,7 +890,7 @@ class HipVecEnv(_VecEnvBase):
         ag, dg = np.atleast_2d(np.asarray(achieved_goal, np.float64)), np.atleast_2d(np.asarray(desired_goal, np.float64))
         infos = [info] if isinstance(info, dict) else list(info)
         ctype = np.array([int(i.get("collision_type", 0)) for i in infos])
-        dist = np.linalg.norm(ag - dg, axis=-1) if self.env_id == "ReachHuman" else np.linalg.norm(dg - ag[:, 3:6], axis=-1)
+        dist = np.linalg.norm(ag - dg, axis=-1) if self.env_id in ("ReachHuman", "ReachHumanCart") else np.linalg.norm(dg - ag[:, 3:6], axis=-1)
         illegal = (ctype & (CONST["HRG_COL_STATIC"] | CONST["HRG_COL_ROBOT"] | CONST["HRG_COL_HUMAN_CRIT"])) != 0
         done = (bool(d.done_at_collision) & illegal) | (bool(d.done_at_success) & (dist <= d.goal_dist))
         return bool(done[0]) if isinstance(info, dict) and np.ndim(achieved_goal) == 1 else done
@@ -921,6 +927,9 @@ class HipVecEnv(_VecEnvBase):
         again replaces the buffer with an empty one (and, between two runs of the device loop, resets the envs).  Returns the buffer."""
         if not self.goal_env:
             raise NotImplementedError("attach_her: construct with goal_env=True / make_vec_env(type='goal_env')")
+        if self.env_id == "ReachHumanCart":
+            raise NotImplementedError("attach_her: the device buffer has no goal kind for ReachHumanCart (achieved = robot0_eef_pos, desired = the goal's eef position: "
+                                      "HRG_GOAL_REACH relabels joint angles, HRG_GOAL_CUBE object positions)")
         if not online_sampling:
             raise NotImplementedError("attach_her(online_sampling=False): offline sampling copies relabelled transitions into a second buffer; the device buffer "
                                       "relabels when it samples")
@@ -1228,6 +1237,8 @@ class HipVecEnv(_VecEnvBase):
         """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature
         row), the action bounds."""
         from .evaluation import build_eval_desc
+        if self.goal_env and self.env_id == "ReachHumanCart":
+            raise NotImplementedError("evaluate on a ReachHumanCart goal env: the device feature row has no goal kind for this task (as attach_her)")
         mean, std, squash = self._norm if self._norm is not None else (None, None, None)
         return build_eval_desc(n_envs, n_policies, n_eval_episodes, [int(c) for c in self._cols], self.action_space.low, self.action_space.high,
                                observe_time=self._observe_time, mean=mean, std=std, squash_factor=squash,
@@ -1351,8 +1362,9 @@ class HipGymEnv:
     def observation_dict(self, obs):
         """Split a flat observation back into the reference's observable / modality keys."""
         out, k0 = OrderedDict(), 0
+        cols_of = task_columns("ReachHumanCart") if getattr(self._vec, "env_id", None) == "ReachHumanCart" else OBS_COLUMNS   # (its goal keys are three wide)
         for key in self._vec.obs_keys:
-            n = len(OBS_COLUMNS[key])
+            n = len(cols_of[key])
             out[key] = obs[k0:k0 + n]
             k0 += n
         return out

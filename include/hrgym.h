@@ -70,7 +70,9 @@ extern "C" {
                           *  demonstrations/experts/pick_place_human_cart_expert.py:24-41)
                           *  [57:61] quat_eef_to_object of the handover tasks / quat_eef_to_board of CollaborativeLiftingCart (x, y, z, w;
                           *  human_robot_handover_cartesian_env.py:860-875, collaborative_lifting_cartesian_env.py:1010-1031), board_quat of
-                          *  CollaborativeHammeringCart; [61] its nail_hammering_progress; [62:64] unused (zero) */
+                          *  CollaborativeHammeringCart; [61] its nail_hammering_progress; [62:64] unused (zero)
+                          *  ReachHumanCart (reach_human_cartesian_env.py:385-434): the ReachHuman layout with goal_difference = target - eef_pos in [12:15], desired_goal =
+                          *  the goal's eef position in [33:36] ([15:18], [36:39] zero) and robot0_eef_velp in [40:43] */
 #define HRG_ACT_DIM 7     /* 6 joint deltas + 1 gripper (reach_human_expert.py:82-83) */
 #define HRG_INFO_DIM 14
 #define HRG_NCON_MAX 24   /* contacts reported per env per substep */
@@ -126,7 +128,9 @@ enum { HRG_TASK_REACH = 0, HRG_TASK_PICK_PLACE = 1, HRG_TASK_INSPECTION = 2 /* H
        HRG_TASK_REACH_BOX = 8 /* ReachHuman with its free `smallBox` object (reach_human_env.py:573-579, 5 cm cube placed anywhere on the table; not whitelisted: a
                                * robot contact with it is a static collision); task logic of ReachHuman, stepped by the cube kernel */,
        HRG_TASK_HAMMERING = 9 /* CollaborativeHammeringCart (collaborative_hammering_cartesian_env.py): the robot holds a hammer and drives a nail into a board the
-                               * human presents -- two free bodies (board, hammer), the nail on a slide joint of the board, a weld + a connect to the hands */ };
+                               * human presents -- two free bodies (board, hammer), the nail on a slide joint of the board, a weld + a connect to the hands */,
+       HRG_TASK_REACH_CART = 10 /* ReachHumanCart (reach_human_cartesian_env.py): ReachHuman's world with its smallBox, the goal an end-effector position -- the eef position of
+                                 * a sampled joint goal that lies inside sampling_space; stepped by the cube kernel like HRG_TASK_REACH_BOX */ };
 #define HRG_IS_HANDOVER(task) ((task) == HRG_TASK_HANDOVER_H2R || (task) == HRG_TASK_HANDOVER_R2H)
 /* ObjectInspectionPhase, human_object_inspection_cartesian_env.py:43-49 */
 enum { HRG_PHASE_APPROACH = 0, HRG_PHASE_READY = 1, HRG_PHASE_INSPECTION = 2, HRG_PHASE_RETREAT = 3, HRG_PHASE_COMPLETE = 4 };
@@ -341,6 +345,8 @@ typedef struct hrg_model_desc {
   int32_t hull_off[HRG_NHULL + 1];
   const double* hull_verts;
   uint64_t seed;
+  /* ---- ReachHumanCart (reach_human_cartesian_env.py:283, 436-465): a goal configuration is accepted when its end-effector position lies in this box ---- */
+  double sampling_space[2][3];  /* [0] lower, [1] upper corner (world) */
 } hrg_model_desc;
 
 /* Human animation clips, shared by all envs of a batch.  Frame layout (doubles):
@@ -378,11 +384,12 @@ typedef struct hrg_clip_table {
 } hrg_clip_table;
 
 /* ------------------------------------------------------------------------- scripted experts + action imitation reward (POD) */
-/* the scripted experts of demonstrations/experts/ (REGISTERED_EXPERTS, __init__.py:8-14; ReachHumanCart has no environment here) */
+/* the scripted experts of demonstrations/experts/ (REGISTERED_EXPERTS, __init__.py:8-14) */
 enum { HRG_EXPERT_REACH = 0           /* ReachHumanExpert (reach_human_expert.py): joint action, reads goal_difference */,
        HRG_EXPERT_PICK_PLACE = 1      /* PickPlaceHumanCartExpert (pick_place_human_cart_expert.py): PickPlaceHumanCart, CollaborativeStackingCart, both handover tasks */,
        HRG_EXPERT_LIFTING = 2         /* CollaborativeLiftingCartExpert (collaborative_lifting_cart_expert.py) */,
-       HRG_EXPERT_HAMMERING = 3       /* CollaborativeHammeringCartExpert (collaborative_hammering_cart_expert.py) */ };
+       HRG_EXPERT_HAMMERING = 3       /* CollaborativeHammeringCartExpert (collaborative_hammering_cart_expert.py) */,
+       HRG_EXPERT_REACH_CART = 4      /* ReachHumanCartExpert (reach_human_cart_expert.py): Cartesian action, reads goal_difference[0:3]; ReachHumanCart only */ };
 /* similarity functions of utils/expert_imitation_reward_utils.py */
 enum { HRG_SIM_GAUSSIAN = 0 /* 2^-(delta / iota)^2 */, HRG_SIM_TANH = 1 /* 1 - tanh(tan(0.5) delta / iota) */ };
 #define HRG_IMIT_DIM 8    /* floats per env of the imitation row (hrg_batch_step_imitation) */
@@ -415,7 +422,7 @@ typedef struct hrg_expert_desc {
 /* ------------------------------------------------------------------------- demonstration datasets: RSI + state imitation reward (POD) */
 /* StateBasedExpertImitationRewardWrapper subclasses (wrappers/state_based_expert_imitation_reward_wrapper.py) */
 enum { HRG_SIR_NONE = 0        /* DatasetRSIWrapper alone (dataset_wrapper.py:88-157): resets to dataset states, no state reward */,
-       HRG_SIR_REACH = 1       /* ReachHumanStateBasedExpertImitationRewardWrapper (283-413): goal_difference, all six columns */,
+       HRG_SIR_REACH = 1       /* ReachHumanStateBasedExpertImitationRewardWrapper (283-413): goal_difference, all six columns (ReachHumanCart: three, the rest zero) */,
        HRG_SIR_PICK_PLACE = 2  /* PickPlaceHumanCartStateBasedExpertImitationRewardWrapper (416-619): vec_eef_to_target, robot0_gripper_qpos, object_gripped */,
        HRG_SIR_LIFTING = 3     /* CollaborativeLiftingCartStateBasedExpertImitationRewardWrapper (622-758): vec_eef_to_human_lh, board_gripped */ };
 #define HRG_SIR_DIM 16    /* floats per env of the state imitation row (hrg_batch_step_dataset) */

@@ -2,7 +2,7 @@
 """Record a demonstration dataset with a scripted expert on the batched stepper (the reference's training/create_expert_dataset.py):
 
   python tools/create_expert_dataset.py --env PickPlaceHumanCart --name pp-demo --episodes 100 [--envs 64] [--snr 0.98] [--seed 0] [--horizon 1000]
-                                        [--shield SSM|PFL|OFF] [--geometry capsule|hull] [--expert-arg board_size=[1.0,0.4,0.03] ...]
+                                        [--shield SSM|PFL|OFF] [--geometry capsule|hull] [--done-at-success true|false] [--expert-arg board_size=[1.0,0.4,0.03] ...]
 
 writes datasets/<name>/hrg_dataset.npz (+ observations.csv, stats.csv) below the working directory, where
 wrappers.state_based_expert_imitation_reward / action_based_expert_imitation_reward (dataset_name: <name>) and wrappers.dataset_obs_norm find it.
@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--horizon", type=int, default=None)
     ap.add_argument("--shield", default="SSM")
     ap.add_argument("--geometry", default="capsule")
+    ap.add_argument("--done-at-success", choices=["true", "false"], default=None, help="environment.done_at_success (default: the task's; the reference's data-collection "
+                    "configs set it, e.g. reach_human_cart_expert_data_collection.yaml: false)")
     ap.add_argument("--action-limit", type=float, default=0.1, help="ik_position_delta.action_limit of the Cartesian tasks")
     ap.add_argument("--capacity-gib", type=float, default=DEFAULT_CAPACITY_BYTES / 2 ** 30, help="device memory the tape may take")
     ap.add_argument("--expert-arg", action="append", default=[], metavar="KEY=VALUE", help="further constructor arguments of the expert (Python literals)")
@@ -43,6 +45,8 @@ def main():
     kw = dict(shield_type=a.shield, seed=a.seed, **task_env_kwargs(a.env))
     if a.horizon is not None:
         kw["horizon"] = a.horizon
+    if a.done_at_success is not None:
+        kw["done_at_success"] = a.done_at_success == "true"
     ds = collect_expert_dataset(a.env, a.episodes, a.envs, expert=expert, dataset_name=a.name, capacity_bytes=int(a.capacity_gib * 2 ** 30), env_kwargs=kw,
                                 clips=task_clips(a.env), robot_geometry=a.geometry, ik_position_delta=None if a.env == "ReachHuman" else dict(action_limit=a.action_limit))
     import numpy as np

@@ -37,6 +37,11 @@ SETTINGS = ["controllers/failsafe_controller/config/failsafe.json", "models/robo
             "training/config/wrappers/ik_position_delta/default_ik_position_delta.yaml",
             "training/config/wrappers/collision_prevention/default_collision_prevention.yaml",
             "models/assets/robots/schunk/robot.xml", "models/assets/human/human.xml", "models/assets/objects/nail.xml"]
+# ReachHumanCart (tests/test_reach_cart.py): the task's environment, expert and state-based wrapper yamls with what their defaults lists compose, and its
+# data-collection config (the top-level file alone: its robot / wrappers / run groups are the other fixtures' and the test's own)
+REACH_CART_YAMLS = ["training/config/environment/reach_human_cart.yaml", "training/config/expert/reach_human_cart.yaml",
+                    "training/config/wrappers/state_based_expert_imitation_reward/reach_human_cart_state_based_expert_imitation_reward.yaml"]
+REACH_CART_FILES = ["training/config/reach_human_cart_expert_data_collection.yaml"]
 ICRA_SHORT = ["R", "PP", "CL", "RHH", "HRH", "CS"]
 
 
@@ -84,6 +89,9 @@ def main():
     for name in ENV_YAMLS:
         files += [os.path.relpath(p, ref) for p in composed_files(os.path.join(env_dir, name + ".yaml"))]
     files.append("training/config/environment/default/collaborative_hammering_cart.yaml")
+    for rel in REACH_CART_YAMLS:
+        files += [os.path.relpath(p, ref) for p in composed_files(os.path.join(ref, rel))]
+    files += REACH_CART_FILES
     files += [f"training/config_icra_2024/environment_evaluation/training/{s}-SAC.yaml" for s in ICRA_SHORT]
     if os.path.isdir(OUT):
         shutil.rmtree(OUT)

@@ -1,4 +1,4 @@
-"""Kernel time of one task's step at a batch size: python tools/task_time.py ENV_ID N_ENVS [SHIELD] (HRG_TT_LIB=path times a variant build through _lib.use_variant_library)."""
+"""Kernel time of one task's step at a batch size: python tools/task_time.py ENV_ID N_ENVS [SHIELD] [box] (ENV_ID: any task of model.ENV_DEFAULTS; `box`: ReachHuman with its smallBox, the cube kernel's ReachHuman world; HRG_TT_LIB=path times a variant build through _lib.use_variant_library)."""
 import os
 import sys
 import time
@@ -17,7 +17,8 @@ env_id = sys.argv[1] if len(sys.argv) > 1 else "HumanRobotHandoverCart"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
 shield = sys.argv[3] if len(sys.argv) > 3 else ("PFL" if "Handover" in env_id else "SSM")
 clips = mixed.task_clips(env_id, 13)
-d = hrg.build_model_desc(dict(shield_type=shield, horizon=1000, seed=9), n_clips=clips.n_clips, env_id=env_id)
+reach_box = len(sys.argv) > 4 and sys.argv[4] == "box"
+d = hrg.build_model_desc(dict(shield_type=shield, horizon=1000, seed=9), n_clips=clips.n_clips, env_id=env_id, reach_box=reach_box)
 G = HipBatch(d, clips, n)
 G.reset()
 torch.cuda.synchronize()
@@ -37,5 +38,5 @@ for k in range(40):
 torch.cuda.synchronize()
 dt = time.time() - t0
 ms, nl = G.kernel_time()
-print(f"{env_id} {shield} n={n} lib={os.path.basename(_lib.variant_library() or 'default')}: {n * 40 / dt / 1e6:.3f} M env steps/s, kernel {ms:.3f} ms x{nl}", flush=True)
+print(f"{env_id}{' + smallBox' if reach_box else ''} {shield} n={n} lib={os.path.basename(_lib.variant_library() or 'default')}: {n * 40 / dt / 1e6:.3f} M env steps/s, kernel {ms:.3f} ms x{nl}", flush=True)
 G.close()
