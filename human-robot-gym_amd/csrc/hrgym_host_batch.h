@@ -1,7 +1,8 @@
-// hrgym_host_batch.h -- the batch handle of the C ABI (include/hrgym.h: hrg_batch_*, hrg_debug_*): the variant table that picks a batch's kernels, create as its named
-// steps, destroy, reset / check / step, the accessors, the scripted experts and demonstration datasets attached to a batch, and the test taps of the base unit's
+// hrgym_host_batch.h -- the batch handle of the C ABI (include/hrgym.h: hrg_batch_*, hrg_debug_*): the variant table that picks a batch's kernels, the task table that
+// says what a task is, create as its named steps, destroy, reset / check / step, the accessors, the scripted experts and demonstration datasets attached to a batch, and the test taps of the base unit's
 // kernels.  Included by the base unit only (hrgym_hip.hip), behind hrgym_host.h.
 
+struct TaskTraits;
 struct hrg_batch {
   int device = 0;
   int32_t n_envs = 0;
@@ -9,7 +10,7 @@ struct hrg_batch {
   DeviceMem mem;                       // behind every d_ pointer below
   DevModel* d_model = nullptr;
   double* d_frames = nullptr;
-  double* d_pose = nullptr;            // per-frame human pose table (DevModel::pose_tab): the tasks whose kernels read it (hrg_task_uses_pose_table)
+  double* d_pose = nullptr;            // per-frame human pose table (DevModel::pose_tab): the tasks whose kernels read it (TaskTraits::pose_table)
   size_t pose_bytes = 0;
   double* d_hull = nullptr;            // hull vertices of the arm links (robot_hulls)
   bool hulls = false;                  // a hull variant steps this batch: of the ReachHuman kernels (hrgym_hulls.hip), the cube kernels (hrgym_box_hulls.hip) or a task's own (hrgym_*_hulls.hip)
@@ -24,7 +25,7 @@ struct hrg_batch {
   hrg_hammer_state* d_hammers = nullptr; // board, hammer, nail of each env (CollaborativeHammeringCart)
   int32_t* d_order = nullptr;          // launch order of the step kernel (StepOrder): two orders of n_envs + two pairs of counters
   int32_t parity = 0;                  // which of the two orders the next step launch reads
-  int32_t task = HRG_TASK_REACH;
+  const TaskTraits* traits = nullptr;  // the row of the batch's task (HRG_TASKS)
   bool ik = false;                     // the Cartesian action front-end is on: action rows are [dx, dy, dz, gripper, -, -, -]
   bool has_expert = false;             // hrg_batch_expert_attach
   hrg_expert_desc expert;              // the attached expert (a kernel argument of the two expert kernels)
@@ -84,36 +85,62 @@ static constexpr VariantTable make_variants() {
 }
 static const VariantTable g_variants = make_variants();
 
+// Every task of the library, once: what the host has to know about an HRG_TASK_* beyond the values of its descriptor.  A row here, its row in the Python package's
+// tasks.py and whatever is new in the kernel and the descriptor are what a new task of an existing family needs.
+enum { HRG_OBJ_NONE, HRG_OBJ_BOXES, HRG_OBJ_STACKS, HRG_OBJ_HAMMERS };   // the per-env object block a task's kernels stream: none, d_boxes, d_stacks, d_hammers
+struct TaskTraits {
+  int task, family, objs;   // HRG_TASK_*, HRG_FAM_*, HRG_OBJ_*
+  bool pose_table;          // its kernels are built with HRG_POSE_TABLE; every other task steps with a cube kernel or a hand-mocap kernel, which keep the live tree kinematics
+  bool dataset;             // a dataset or snapshot can hold its state: (hrg_env_state, hrg_box_state) is all of it
+  unsigned experts, sirs;   // bit k: HRG_EXPERT_k / HRG_SIR_k reads the observation of this task (HRG_SIR_NONE fits every task that a dataset can hold)
+};
+#define E(x) (1u << HRG_EXPERT_##x)
+#define S(x) (1u << HRG_SIR_##x)
+static constexpr TaskTraits HRG_TASKS[] = {
+  {HRG_TASK_REACH, HRG_FAM_REACH, HRG_OBJ_NONE, true, true, E(REACH), S(REACH)},                    // hrgym_hip.hip, hrgym_hulls.hip
+  {HRG_TASK_PICK_PLACE, HRG_FAM_BOX, HRG_OBJ_BOXES, false, true, E(PICK_PLACE), S(PICK_PLACE)},      // PP-AIR; (also PickPlaceCloseHumanCart)
+  {HRG_TASK_INSPECTION, HRG_FAM_BOX, HRG_OBJ_BOXES, false, true, 0, 0},
+  {HRG_TASK_POINTING, HRG_FAM_BOX, HRG_OBJ_BOXES, false, true, 0, 0},
+  // the handover tasks: HRH-AIR, RHH-AIR; the pick-place state reward serves "any environment that can be solved using the PickPlaceHumanCartExpert"
+  {HRG_TASK_HANDOVER_H2R, HRG_FAM_HO, HRG_OBJ_BOXES, false, true, E(PICK_PLACE), S(PICK_PLACE)},
+  {HRG_TASK_HANDOVER_R2H, HRG_FAM_HO, HRG_OBJ_BOXES, false, true, E(PICK_PLACE), S(PICK_PLACE)},
+  {HRG_TASK_LIFTING, HRG_FAM_LIFT, HRG_OBJ_BOXES, true, true, E(LIFTING), S(LIFTING)},               // hrgym_lift.hip: the board is its box
+  {HRG_TASK_STACKING, HRG_FAM_STACK, HRG_OBJ_STACKS, false, false, E(PICK_PLACE), 0},                // CS-AIR; its state lives in a further array (d_stacks)
+  // ReachHuman with its box: no expert and no state reward, the cube kernel serves object_quat in the goal_difference columns
+  {HRG_TASK_REACH_BOX, HRG_FAM_BOX, HRG_OBJ_BOXES, false, true, 0, 0},
+  {HRG_TASK_HAMMERING, HRG_FAM_HAMMER, HRG_OBJ_HAMMERS, false, false, E(HAMMERING), 0},              // its state lives in a further array (d_hammers)
+  {HRG_TASK_REACH_CART, HRG_FAM_BOX, HRG_OBJ_BOXES, false, true, E(REACH_CART), S(REACH)},           // the Reach state reward: three goal_difference columns, the other three zero
+};
+#undef E
+#undef S
+static const TaskTraits* task_traits(int task) {   // null: no such task
+  for (const TaskTraits& t : HRG_TASKS)
+    if (t.task == task) return &t;
+  return nullptr;
+}
+// what hrg_batch_get_ / set_ of an object block answer on a batch whose task streams another one, by HRG_OBJ_* (null: every batch has the array)
+static const char* const g_objs_missing[] = {nullptr, nullptr, "not a CollaborativeStackingCart batch", "not a CollaborativeHammeringCart batch"};
+
 // the variant that steps a batch, and the object array its kernels stream (null: the ReachHuman kernels stream none)
 static const Variant& batch_variant(const hrg_batch* b, void** objs) {
-  int family = HRG_FAM_REACH;
-  *objs = nullptr;
-  if (b->task == HRG_TASK_HAMMERING) { family = HRG_FAM_HAMMER; *objs = b->d_hammers; }
-  else if (b->task == HRG_TASK_STACKING) { family = HRG_FAM_STACK; *objs = b->d_stacks; }
-  else if (b->task != HRG_TASK_REACH) {
-    family = b->task == HRG_TASK_LIFTING ? HRG_FAM_LIFT : (HRG_IS_HANDOVER(b->task) ? HRG_FAM_HO : HRG_FAM_BOX);
-    *objs = b->d_boxes;
-  }
-  return g_variants.v[family][b->hulls ? 1 : 0];
+  const TaskTraits& t = *b->traits;
+  *objs = t.objs == HRG_OBJ_BOXES ? (void*)b->d_boxes : t.objs == HRG_OBJ_STACKS ? (void*)b->d_stacks : t.objs == HRG_OBJ_HAMMERS ? (void*)b->d_hammers : nullptr;
+  return g_variants.v[t.family][b->hulls ? 1 : 0];
 }
 
-// one env's block of a per-env device array <-> the host (hrg_batch_get_ / set_ state, box, stack, hammer); missing = the error of a batch of another task,
-// which has no such array (null: every batch has it)
+// one env's block of a per-env device array <-> the host (hrg_batch_get_ / set_ state, box, stack, hammer); objs = the HRG_OBJ_* the array belongs to: a batch of
+// a task with another block has no such array (g_objs_missing)
 template <class T>
-static int env_block_copy(hrg_batch* b, int32_t env, T* hrg_batch::*arr, void* buf_host, size_t bytes, bool get, const char* missing) {
+static int env_block_copy(hrg_batch* b, int32_t env, T* hrg_batch::*arr, void* buf_host, size_t bytes, bool get, int objs) {
   if (!b || env < 0 || env >= b->n_envs || bytes != sizeof(T)) return fail(HRG_ERR_INVALID, "bad env index or buffer size");
+  if (g_objs_missing[objs] && b->traits->objs != objs) return fail(HRG_ERR_INVALID, g_objs_missing[objs]);
   T* const dev = b->*arr;
-  if (missing && !dev) return fail(HRG_ERR_INVALID, missing);
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipDeviceSynchronize());
   if (get) HIPCHK(hipMemcpy(buf_host, dev + env, bytes, hipMemcpyDeviceToHost));
   else HIPCHK(hipMemcpy(dev + env, buf_host, bytes, hipMemcpyHostToDevice));
   return HRG_OK;
 }
-
-// the kernels built with HRG_POSE_TABLE: ReachHuman (hrgym_hip.hip, hrgym_hulls.hip) and lifting (hrgym_lift.hip); every other task steps with a cube kernel
-// or a hand-mocap kernel, which keep the live tree kinematics
-static bool hrg_task_uses_pose_table(int task) { return task == HRG_TASK_REACH || task == HRG_TASK_LIFTING; }
 
 static void mat_from_quat(double* M, const double* q) {
   double w = q[0], x = q[1], y = q[2], z = q[3];
@@ -152,7 +179,8 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
   for (int c = 0; c < HRG_NSHIELD_RCAP; c++)
     if (desc->scap_body[c] != (c < NARM ? c : NARM - 1)) return fail(HRG_ERR_INVALID, "shield capsule c must sit on link c (gripper on link 6)");
   if (desc->n_bodypart > HRG_NBODYPART_MAX || desc->n_extremity > HRG_NEXTREMITY_MAX) return fail(HRG_ERR_INVALID, "too many body parts");
-  if (desc->task < HRG_TASK_REACH || desc->task > HRG_TASK_REACH_CART) return fail(HRG_ERR_UNSUPPORTED, "unknown task");
+  const TaskTraits* const t = task_traits(desc->task);
+  if (!t) return fail(HRG_ERR_UNSUPPORTED, "unknown task");
   if (desc->task == HRG_TASK_STACKING) {
     if (!(desc->box_inertia[0] == desc->box_inertia[1] && desc->box_inertia[1] == desc->box_inertia[2]))
       return fail(HRG_ERR_UNSUPPORTED, "CollaborativeStackingCart: the HIP stepper stacks cubes (object_full_size with three equal edges)");
@@ -181,9 +209,9 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
     for (int c = 0; c < clips->n_clips; c++)
       if (!(clips->clip_keyframes[c][0] >= 0 && clips->clip_keyframes[c][0] <= clips->clip_keyframes[c][1] && clips->clip_n_loop[c] >= 0 && clips->clip_n_loop[c] <= HRG_MAX_LOOP))
         return fail(HRG_ERR_INVALID, "CollaborativeHammeringCart: every clip needs two ascending keyframes and at most 4 loop sines in its info");
-  } else
-  if (desc->task != HRG_TASK_REACH && !(desc->box_half[0] > 0 && desc->box_half[1] > 0 && desc->box_half[2] > 0 && desc->box_mass > 0 && desc->box_inertia[0] > 0 && desc->box_inertia[1] > 0 &&
-                                       desc->box_inertia[2] > 0 && desc->box_inertia_mean > 0 && desc->box_invweight_rot > 0 && desc->n_targets > 0 && desc->n_obj_placements > 0))
+  } else   // a box block, or the stack: its four cubes share box_half / box_mass / box_inertia
+  if (t->objs != HRG_OBJ_NONE && !(desc->box_half[0] > 0 && desc->box_half[1] > 0 && desc->box_half[2] > 0 && desc->box_mass > 0 && desc->box_inertia[0] > 0 && desc->box_inertia[1] > 0 &&
+                                     desc->box_inertia[2] > 0 && desc->box_inertia_mean > 0 && desc->box_invweight_rot > 0 && desc->n_targets > 0 && desc->n_obj_placements > 0))
     return fail(HRG_ERR_INVALID, "PickPlaceHumanCart needs box_half, box_mass, box_inertia, n_targets, n_obj_placements > 0");
   int maxd = 0;
   for (int i = 0; i < HRG_NHB; i++) maxd = desc->hb_depth[i] > maxd ? desc->hb_depth[i] : maxd;
@@ -203,10 +231,7 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
   }
   if (tot != clips->total_frames) return fail(HRG_ERR_INVALID, "clip table total_frames mismatch");
   if (desc->robot_hulls) {
-    // every kernel has a hull variant: ReachHuman (hrg_step_kernel_hull), the cube tasks (_box_hull: PickPlace and its variants, HumanObjectInspectionCart, ReachHuman
-    // with its box, ReachHumanCart), the handover tasks (_ho_hull), lifting (_lift_hull), stacking (_stack_hull) and hammering (_hammer_hull)
-    if (!(desc->task == HRG_TASK_REACH || desc->task == HRG_TASK_PICK_PLACE || desc->task == HRG_TASK_INSPECTION || desc->task == HRG_TASK_POINTING || desc->task == HRG_TASK_REACH_BOX || desc->task == HRG_TASK_REACH_CART ||
-          HRG_IS_HANDOVER(desc->task) || desc->task == HRG_TASK_LIFTING || desc->task == HRG_TASK_STACKING || desc->task == HRG_TASK_HAMMERING))
+    if (!g_variants.v[t->family][1].step)   // HRG_VARIANTS has no [family][1] line (today every family has one)
       return fail(HRG_ERR_UNSUPPORTED, "robot_hulls: no hull variant of the step kernel for this task");
     if (!desc->hull_verts || desc->hull_off[0] != 0) return fail(HRG_ERR_INVALID, "robot_hulls: hull_verts / hull_off missing");
     for (int h = 0; h < HRG_NHULL; h++)
@@ -290,7 +315,7 @@ static int batch_upload(hrg_batch* b, const hrg_model_desc* desc, const hrg_clip
   DeviceMem& m = b->mem;
   const size_t frames = (size_t)clips->total_frames;
   bool ok = m.upload(b->d_frames, clips->frames, HRG_FRAME_DIM * frames);
-  if (ok && hrg_task_uses_pose_table(desc->task)) {   // filled by hrg_pose_table_kernel once the model is on the device
+  if (ok && b->traits->pose_table) {   // filled by hrg_pose_table_kernel once the model is on the device
     b->pose_bytes = sizeof(double) * HRG_POSE_DIM * frames;
     ok = m.zeros(b->d_pose, HRG_POSE_DIM * frames);
   }
@@ -322,8 +347,8 @@ static int batch_env_arrays(hrg_batch* b) {
   for (size_t e = 0; e < n; e++) ord[e] = ord[n + e] = (int32_t)e;
   DeviceMem& m = b->mem;
   if (!(m.upload(b->d_states, init.data(), n) && m.zeros(b->d_rcaps, 7 * HRG_NSHIELD_RCAP * n) && m.zeros(b->d_hcaps, 7 * HRG_NHCAP_MAX * n) && m.zeros(b->d_nh, n) &&
-        m.zeros(b->d_scratch_obs, HRG_OBS_DIM * n) && m.zeros(b->d_boxes, n) && (b->task != HRG_TASK_HAMMERING || m.zeros(b->d_hammers, n)) &&
-        (b->task != HRG_TASK_STACKING || m.zeros(b->d_stacks, n)) && m.upload(b->d_order, ord.data(), ord.size())))
+        m.zeros(b->d_scratch_obs, HRG_OBS_DIM * n) && m.zeros(b->d_boxes, n) && (b->traits->objs != HRG_OBJ_HAMMERS || m.zeros(b->d_hammers, n)) &&
+        (b->traits->objs != HRG_OBJ_STACKS || m.zeros(b->d_stacks, n)) && m.upload(b->d_order, ord.data(), ord.size())))
     return nomem("batch", m);
   HIPCHK(hipDeviceSynchronize());
   return HRG_OK;
@@ -334,7 +359,7 @@ int hrg_batch_create(const hrg_model_desc* desc, const hrg_clip_table* clips, in
   if (int rc = batch_check(desc, clips)) return rc;
   HIPCHK(hipSetDevice(device));
   std::unique_ptr<hrg_batch> b(new hrg_batch());
-  b->device = device; b->n_envs = n_envs; b->env_id0 = env_id0; b->task = desc->task; b->ik = desc->ik_enabled != 0; b->hulls = desc->robot_hulls != 0;
+  b->device = device; b->n_envs = n_envs; b->env_id0 = env_id0; b->traits = task_traits(desc->task); b->ik = desc->ik_enabled != 0; b->hulls = desc->robot_hulls != 0;
   std::unique_ptr<DevModel> hm(new DevModel());
   batch_fill_model(desc, clips, hm.get());
   if (int rc = batch_upload(b.get(), desc, clips, hm.get())) return rc;
@@ -419,22 +444,14 @@ int hrg_batch_capsules(hrg_batch* b, double* robot_host, double* human_host, int
   return HRG_OK;
 }
 
-int hrg_batch_get_state(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, buf_host, bytes, true, nullptr); }
-int hrg_batch_set_state(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, (void*)buf_host, bytes, false, nullptr); }
-int hrg_batch_get_box(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, buf_host, bytes, true, nullptr); }
-int hrg_batch_set_box(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, (void*)buf_host, bytes, false, nullptr); }
-int hrg_batch_get_stack(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_stacks, buf_host, bytes, true, "not a CollaborativeStackingCart batch");
-}
-int hrg_batch_set_stack(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_stacks, (void*)buf_host, bytes, false, "not a CollaborativeStackingCart batch");
-}
-int hrg_batch_get_hammer(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_hammers, buf_host, bytes, true, "not a CollaborativeHammeringCart batch");
-}
-int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) {
-  return env_block_copy(b, env, &hrg_batch::d_hammers, (void*)buf_host, bytes, false, "not a CollaborativeHammeringCart batch");
-}
+int hrg_batch_get_state(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, buf_host, bytes, true, HRG_OBJ_NONE); }
+int hrg_batch_set_state(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_states, (void*)buf_host, bytes, false, HRG_OBJ_NONE); }
+int hrg_batch_get_box(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, buf_host, bytes, true, HRG_OBJ_BOXES); }
+int hrg_batch_set_box(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_boxes, (void*)buf_host, bytes, false, HRG_OBJ_BOXES); }
+int hrg_batch_get_stack(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_stacks, buf_host, bytes, true, HRG_OBJ_STACKS); }
+int hrg_batch_set_stack(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_stacks, (void*)buf_host, bytes, false, HRG_OBJ_STACKS); }
+int hrg_batch_get_hammer(hrg_batch* b, int32_t env, void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_hammers, buf_host, bytes, true, HRG_OBJ_HAMMERS); }
+int hrg_batch_set_hammer(hrg_batch* b, int32_t env, const void* buf_host, size_t bytes) { return env_block_copy(b, env, &hrg_batch::d_hammers, (void*)buf_host, bytes, false, HRG_OBJ_HAMMERS); }
 
 int hrg_batch_get_states(hrg_batch* b, const int32_t* envs_host, int32_t n, void* states_host, void* boxes_host) {
   if (!b || !envs_host || !states_host || n < 0) return fail(HRG_ERR_INVALID, "null argument");
@@ -516,22 +533,11 @@ int hrg_batch_pose_table_bytes(hrg_batch* b, int64_t* bytes_host) {
 }
 
 // ---- scripted experts + action-based imitation reward (csrc/hrgym_expert.h) ----
-static bool expert_fits_task(int expert, int task) {
-  switch (expert) {
-    case HRG_EXPERT_REACH: return task == HRG_TASK_REACH;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns
-    case HRG_EXPERT_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || task == HRG_TASK_STACKING || HRG_IS_HANDOVER(task);   // PP-AIR, CS-AIR, HRH-AIR, RHH-AIR
-    case HRG_EXPERT_LIFTING: return task == HRG_TASK_LIFTING;
-    case HRG_EXPERT_HAMMERING: return task == HRG_TASK_HAMMERING;
-    case HRG_EXPERT_REACH_CART: return task == HRG_TASK_REACH_CART;
-  }
-  return false;
-}
-
 int hrg_batch_expert_attach(hrg_batch* b, const hrg_expert_desc* desc) {
   if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
   b->has_expert = false;   // until the descriptor has passed and every buffer below exists and is zeroed: a refused attach leaves no expert attached
   if (desc->expert < HRG_EXPERT_REACH || desc->expert > HRG_EXPERT_REACH_CART) return fail(HRG_ERR_UNSUPPORTED, "unknown expert");
-  if (!expert_fits_task(desc->expert, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this expert does not read the observation of the batch's task");
+  if (!(b->traits->experts >> desc->expert & 1u)) return fail(HRG_ERR_UNSUPPORTED, "this expert does not read the observation of the batch's task");
   if ((desc->cartesian != 0) != (desc->expert != HRG_EXPERT_REACH)) return fail(HRG_ERR_UNSUPPORTED, "ReachHumanExpert acts in joint space, every other expert in Cartesian space");
   if ((desc->cartesian != 0) != b->ik) return fail(HRG_ERR_UNSUPPORTED, "the expert's action form is not the batch's (Cartesian experts need the IK front-end, ik_enabled)");
   const int width = desc->cartesian ? 4 : HRG_ACT_DIM;
@@ -588,23 +594,12 @@ int hrg_batch_step_imitation(hrg_batch* b, double* actions_dev, float* obs_dev, 
 }
 
 // ---- demonstration datasets: reference state initialisation + state-based imitation reward (csrc/hrgym_dataset.h) ----
-static bool dataset_task_ok(int task) { return task != HRG_TASK_STACKING && task != HRG_TASK_HAMMERING; }   // their state lives in further arrays (d_stacks, d_hammers)
-static bool sir_fits_task(int kind, int task) {
-  switch (kind) {
-    case HRG_SIR_NONE: return true;
-    case HRG_SIR_REACH: return task == HRG_TASK_REACH || task == HRG_TASK_REACH_CART;   // not ReachHuman with its box: the cube kernel serves object_quat in the goal_difference columns; ReachHumanCart: three goal_difference columns, the other three zero
-    case HRG_SIR_PICK_PLACE: return task == HRG_TASK_PICK_PLACE || HRG_IS_HANDOVER(task);   // "any environment that can be solved using the PickPlaceHumanCartExpert"
-    case HRG_SIR_LIFTING: return task == HRG_TASK_LIFTING;
-  }
-  return false;
-}
-
 int hrg_batch_snapshot(hrg_batch* b, void* states_out_dev, void* boxes_out_dev, void* stream) {
   if (!b || !states_out_dev) return fail(HRG_ERR_INVALID, "null argument");
-  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "snapshot: the stacking and hammering tasks keep their state in further arrays");
+  if (!b->traits->dataset) return fail(HRG_ERR_UNSUPPORTED, "snapshot: the stacking and hammering tasks keep their state in further arrays");
   HIPCHK(hipSetDevice(b->device));
   HIPCHK(hipMemcpyAsync(states_out_dev, b->d_states, sizeof(hrg_env_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (boxes_out_dev && b->task != HRG_TASK_REACH)
+  if (boxes_out_dev && b->traits->objs == HRG_OBJ_BOXES)
     HIPCHK(hipMemcpyAsync(boxes_out_dev, b->d_boxes, sizeof(hrg_box_state) * (size_t)b->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return HRG_OK;
 }
@@ -612,11 +607,11 @@ int hrg_batch_snapshot(hrg_batch* b, void* states_out_dev, void* boxes_out_dev, 
 int hrg_batch_dataset_attach(hrg_batch* b, const hrg_dataset_desc* desc) {
   if (!b || !desc) return fail(HRG_ERR_INVALID, "null argument");
   b->has_dataset = false;   // until the descriptor has passed and every buffer below exists: a refused attach leaves no dataset attached
-  if (!dataset_task_ok(b->task)) return fail(HRG_ERR_UNSUPPORTED, "dataset: the stacking and hammering tasks keep their state in further arrays, which a dataset does not hold");
+  if (!b->traits->dataset) return fail(HRG_ERR_UNSUPPORTED, "dataset: the stacking and hammering tasks keep their state in further arrays, which a dataset does not hold");
   if (desc->sir_kind < HRG_SIR_NONE || desc->sir_kind > HRG_SIR_LIFTING) return fail(HRG_ERR_UNSUPPORTED, "unknown sir_kind");
-  if (!sir_fits_task(desc->sir_kind, b->task)) return fail(HRG_ERR_UNSUPPORTED, "this state imitation reward does not read the observation of the batch's task");
+  if (desc->sir_kind != HRG_SIR_NONE && !(b->traits->sirs >> desc->sir_kind & 1u)) return fail(HRG_ERR_UNSUPPORTED, "this state imitation reward does not read the observation of the batch's task");
   if (!desc->ep_offset || !desc->states || !desc->obs || desc->n_episodes <= 0) return fail(HRG_ERR_INVALID, "dataset: null array or no episode");
-  if ((desc->boxes != nullptr) != (b->task != HRG_TASK_REACH)) return fail(HRG_ERR_INVALID, "dataset: a box array is needed exactly when the batch's task has a box block");
+  if ((desc->boxes != nullptr) != (b->traits->objs == HRG_OBJ_BOXES)) return fail(HRG_ERR_INVALID, "dataset: a box array is needed exactly when the batch's task has a box block");
   if (desc->ep_offset[0] != 0 || desc->ep_offset[desc->n_episodes] != desc->total_T) return fail(HRG_ERR_INVALID, "dataset: ep_offset must run from 0 to total_T");
   for (int64_t k = 0; k < desc->n_episodes; k++) {
     const int64_t T = desc->ep_offset[k + 1] - desc->ep_offset[k];

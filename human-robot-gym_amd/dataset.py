@@ -21,14 +21,11 @@ import os
 import numpy as np
 
 from ._cstruct import CONST, BoxState, DatasetDesc, EnvState
+from .tasks import TASKS, task_row
 
 FILE_NAME = "hrg_dataset.npz"
 STATE_BYTES, BOX_BYTES = ctypes.sizeof(EnvState), ctypes.sizeof(BoxState)
-NO_DATASET_ENVS = ("CollaborativeStackingCart", "CollaborativeHammeringCart")   # their state lives in further arrays (hrg_stack_state, hrg_hammer_state)
-# StateBasedExpertImitationRewardWrapper subclass per task (state_based_expert_imitation_reward_wrapper.py; the pick-place wrapper serves "any environment
-# that can be solved using the PickPlaceHumanCartExpert")
-SIR_KINDS = {"ReachHuman": CONST["HRG_SIR_REACH"], "ReachHumanCart": CONST["HRG_SIR_REACH"], "PickPlaceHumanCart": CONST["HRG_SIR_PICK_PLACE"], "HumanRobotHandoverCart": CONST["HRG_SIR_PICK_PLACE"],
-             "RobotHumanHandoverCart": CONST["HRG_SIR_PICK_PLACE"], "CollaborativeLiftingCart": CONST["HRG_SIR_LIFTING"]}
+SIR_KINDS = {env_id: t.sir for env_id, t in TASKS.items() if t.sir is not None}   # StateBasedExpertImitationRewardWrapper subclass per task
 SIR_COLUMNS = ("r_im", "r_env", "r_motion", "r_gripper", "r_full", "ep_im", "ep_env", "ep_motion", "ep_gripper", "ep_len", "ep_len_mg", "early", "time",
                "time_obs")   # HRG_SIR_*
 _SIM_FNS = {"gaussian": CONST["HRG_SIM_GAUSSIAN"], "tanh": CONST["HRG_SIM_TANH"]}
@@ -42,6 +39,12 @@ DEFAULT_CAPACITY_BYTES = 2 << 30
 def library_version():
     from ._lib import load_library
     return load_library().hrg_version().decode()
+
+
+def check_holds_state(env_id):
+    """A dataset holds (hrg_env_state, hrg_box_state) per transition: refuse a task whose state lives in a further array (hrg_stack_state, hrg_hammer_state)."""
+    if TASKS[env_id].block in ("stack", "hammer"):
+        raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
 
 
 def dataset_path(name_or_path):
@@ -256,11 +259,9 @@ def collect_expert_dataset(env_id, n_episodes, n_envs, expert, dataset_name=None
     written to datasets/<dataset_name>/.  Returns the ExpertDataset."""
     import torch
     from .vec_env import HipVecEnv
-    if env_id in NO_DATASET_ENVS:
-        raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
-    from .model import ENV_DEFAULTS
-    has_box = env_id != "ReachHuman" or bool(env_kwargs.get("reach_box"))
-    horizon = int((env_kwargs.get("env_kwargs") or {}).get("horizon", ENV_DEFAULTS[env_id]["horizon"]))
+    check_holds_state(env_id)
+    has_box = task_row(env_id, bool(env_kwargs.get("reach_box"))).block == "box"
+    horizon = int((env_kwargs.get("env_kwargs") or {}).get("horizon", TASKS[env_id].env_kwargs["horizon"]))
     steps = int(max_steps) if max_steps is not None else -(-int(n_episodes) // int(n_envs)) * horizon
     need = tape_bytes(steps, n_envs, has_box)
     if need > capacity_bytes:   # before anything is allocated, the batch included

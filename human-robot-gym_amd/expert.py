@@ -8,6 +8,7 @@ csrc/hrgym_expert.h.
 import numpy as np
 
 from ._cstruct import CONST, ExpertDesc
+from .tasks import TASKS
 
 # REGISTERED_EXPERTS (demonstrations/experts/__init__.py:8-14) -> HRG_EXPERT_*
 EXPERT_IDS = {"ReachHuman": CONST["HRG_EXPERT_REACH"], "PickPlaceHumanCart": CONST["HRG_EXPERT_PICK_PLACE"],
@@ -23,14 +24,7 @@ EXPERT_KWARGS = {
     "CollaborativeHammeringCart": dict(signal_to_noise_ratio=1.0, delta_time=0.1, seed=None),
     "ReachHumanCart": dict(signal_to_noise_ratio=1.0, delta_time=0.01, seed=None),
 }
-# the tasks whose observation an expert reads (CS-AIR, HRH-AIR, RHH-AIR run the pick-place expert)
-EXPERT_ENVS = {
-    "ReachHuman": ("ReachHuman",),
-    "PickPlaceHumanCart": ("PickPlaceHumanCart", "CollaborativeStackingCart", "HumanRobotHandoverCart", "RobotHumanHandoverCart"),
-    "CollaborativeLiftingCart": ("CollaborativeLiftingCart",),
-    "CollaborativeHammeringCart": ("CollaborativeHammeringCart",),
-    "ReachHumanCart": ("ReachHumanCart",),
-}
+EXPERT_ENVS = {eid: tuple(env_id for env_id, t in TASKS.items() if eid in t.experts) for eid in EXPERT_KWARGS}   # the tasks whose observation an expert reads
 SIM_FNS = {"gaussian": CONST["HRG_SIM_GAUSSIAN"], "tanh": CONST["HRG_SIM_TANH"]}
 IMITATION_REWARD_KWARGS = dict(alpha=0.0, beta=0.0, iota_m=0.1, iota_g=0.25, m_sim_fn="gaussian", g_sim_fn="gaussian", normalize_joint_actions=False)   # the last: Joint form only
 IMIT_COLUMNS = ("r_im", "r_env", "r_motion", "r_gripper", "ep_im", "ep_env", "ep_len", "r_full")   # HRG_IMIT_*

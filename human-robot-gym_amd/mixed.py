@@ -11,6 +11,7 @@ from ._cstruct import CONST
 from ._lib import HipBatch, as_actions
 from .animation import synthetic_clips
 from .model import build_model_desc
+from .tasks import TASKS, value
 
 # training/icra_2024_run_experiments.sh:4-9 (horizons as there) with the environment blocks of training/config_icra_2024/environment_evaluation/training/<task>-SAC.yaml: where
 # those differ from the task's general training config (ENV_DEFAULTS) the experiment's value is listed here (tests/test_assets.py compares every common keyword)
@@ -35,24 +36,12 @@ _STEP_MS = {"CollaborativeHammeringCart": 11.5, "CollaborativeStackingCart": 6.2
 
 def task_clips(env_id, n_clips=13, seed=0, **kw):
     """Synthetic clip set carrying the animation info `env_id` reads."""
-    extra = {"HumanObjectInspectionCart": dict(inspection=True), "HumanRobotHandoverCart": dict(handover=True),
-             "RobotHumanHandoverCart": dict(handover="r2h"), "CollaborativeStackingCart": dict(stacking=True),
-             }.get(env_id, {})
-    if env_id == "CollaborativeHammeringCart":
-        from .animation import HAMMERING_HANDS
-        extra = dict(hammering=HAMMERING_HANDS)
-    if env_id == "CollaborativeLiftingCart":
-        from .animation import lifting_hands_nominal
-        extra = dict(lifting=lifting_hands_nominal(build_model_desc(None, env_id=env_id)), fps=20.0)
-    return synthetic_clips(n_clips, seed=seed, **extra, **kw)
+    return synthetic_clips(n_clips, seed=seed, **value(TASKS[env_id].clip_extra), **kw)
 
 
 def task_env_kwargs(env_id):
     """Environment keyword arguments that go with the synthetic clips of `task_clips` (the reference's defaults belong to its recorded clips)."""
-    if env_id == "CollaborativeHammeringCart":
-        from .animation import hammering_relquat
-        return dict(hammer_weld_relquat=hammering_relquat())
-    return {}
+    return value(TASKS[env_id].clip_env_kwargs)
 
 
 def split_evenly(n_envs, n_tasks):

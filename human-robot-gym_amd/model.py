@@ -16,8 +16,10 @@ import os
 import numpy as np
 
 from ._cstruct import CONST, ModelDesc
+from .tasks import DEFAULT_ENV_KWARGS, HAMMERING_ENV_KWARGS, TASKS, task_row  # noqa: F401  (a task's default kwargs are its data: tasks.py)
 
 _ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
+ENV_DEFAULTS = {env_id: t.env_kwargs for env_id, t in TASKS.items()}   # what make_vec_env(env_id) steps: the reference's training config for that env
 
 # models/robots/config/schunk.json (qpos_limits) — the only key of that file the controller reads
 SCHUNK_QPOS_LIMITS = [[-2.9, -1.8, -2.60, -2.9, -1.85, -2.9], [2.9, 1.8, 2.60, 2.9, 1.85, 2.9]]
@@ -31,140 +33,6 @@ HUMAN_JOINT_ELEMENTS = [
     "R_Wrist", "L_Hand", "R_Hand",
 ]
 
-# default kwargs = HumanEnv/ReachHuman constructor defaults overlaid with config/environment/reach_human.yaml
-DEFAULT_ENV_KWARGS = dict(
-    robots="Schunk",
-    robot_base_offset=[0.0, 0.0, 0.0],
-    reward_scale=1.0,
-    reward_shaping=False,
-    collision_reward=0,
-    task_reward=1,
-    done_at_collision=False,
-    done_at_success=True,
-    control_freq=10,
-    horizon=100,
-    shield_type="SSM",
-    control_sample_time=0.004,
-    base_human_pos_offset=[0.0, 0.0, 0.0],
-    human_animation_freq=120,
-    human_rand=[0.0, 0.0, 0.0],
-    n_animations_sampled_per_100_steps=5,
-    n_goals_sampled_per_100_steps=20,
-    goal_dist=0.1,
-    safe_vel=0.01,
-    self_collision_safety=0.012,
-    collision_debounce_delay=0.01,
-    seed=0,
-)
-
-# ReachHumanCart: config/environment/reach_human_cart.yaml, which composes default/reach_human_cart.yaml (goal_dist, table_friction) over default/reach_human.yaml
-# and repeats reach_human.yaml's own keys.  init_joint_pos is the constructor's default (reach_human_cartesian_env.py:280); sampling_space is an attribute the
-# reference's constructor sets (283) -- a keyword here: [lower corner, upper corner] of the box a goal's end-effector position has to lie in
-REACH_CART_ENV_KWARGS = dict(
-    DEFAULT_ENV_KWARGS,
-    goal_dist=0.05,
-    table_full_size=[1.5, 2.0, 0.05],     # default/reach_human.yaml: the arena compiled into the asset tables; accepted at this value only, like table_friction
-    table_friction=[1.0, 5e-3, 1e-4],
-    init_joint_pos=[0.0, 0.0, -math.pi / 2, 0.0, -math.pi / 2, math.pi / 4],
-    sampling_space=[[0.1, -0.5, 0.8], [0.5, 0.5, 1.3]],
-)
-# PickPlaceHumanCart constructor defaults overlaid with config/environment/pick_place_human_cart.yaml (+ default/human_env.yaml)
-PICK_PLACE_ENV_KWARGS = dict(
-    DEFAULT_ENV_KWARGS,
-    horizon=1000,
-    done_at_success=False,
-    safe_vel=0.001,
-    self_collision_safety=0.01,
-    table_full_size=[1.5, 2.0, 0.05],
-    object_full_size=[0.04, 0.04, 0.04],
-    n_object_placements_sampled_per_100_steps=3,
-    n_targets_sampled_per_100_steps=3,
-    object_gripped_reward=-0.25,
-)
-# HumanObjectInspectionCart constructor defaults overlaid with config/environment/(default/)human_object_inspection_cart.yaml
-INSPECTION_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    human_rand=[0.0, 0.5, 0.0],
-    n_animations_sampled_per_100_steps=2,
-    n_targets_sampled_per_100_steps=0,      # the target comes with the animation (human_object_inspection_cartesian_env.py:394)
-    object_gripped_reward=-1.0,
-    object_at_target_reward=-1.0,
-    goal_exit_tolerance=0.02,
-)
-# PickPlaceCloseHumanCart: PickPlaceHumanCart with clips recorded at 60 Hz (pick_place_close_human_cartesian_env.py:219-285)
-PICK_PLACE_CLOSE_ENV_KWARGS = dict(PICK_PLACE_ENV_KWARGS, human_animation_freq=60, object_gripped_reward=-1.0)
-# PickPlacePointingHumanCart + config/environment/pick_place_pointing_human_cart.yaml
-POINTING_ENV_KWARGS = dict(PICK_PLACE_ENV_KWARGS, horizon=500, object_gripped_reward=-1.0)
-# HumanRobotHandoverCart constructor defaults overlaid with config/environment/(default/)human_robot_handover_cart.yaml
-HANDOVER_H2R_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    shield_type="PFL",
-    table_full_size=[1.0, 2.0, 0.05],
-    human_animation_freq=90,
-    human_rand=[0.0, 0.2, 0.1],
-    n_animations_sampled_per_100_steps=2,
-    n_targets_sampled_per_100_steps=3,
-    object_at_target_reward=0.0,
-    object_gripped_reward=-0.25,
-    collision_reward=-1.0,
-    goal_exit_tolerance=0.0,
-    done_at_success=True,
-)
-# RobotHumanHandoverCart constructor defaults overlaid with config/environment/(default/)robot_human_handover_cart.yaml
-HANDOVER_R2H_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    shield_type="PFL",
-    table_full_size=[1.5, 2.0, 0.05],   # (round 3: was the human-to-robot task's 1.0 m table by mistake; robot_human_handover_cartesian_env.py:305, RHH-*.yaml:63-66)
-    human_animation_freq=90,
-    human_rand=[0.0, 0.2, 0.1],
-    n_animations_sampled_per_100_steps=2,
-    n_targets_sampled_per_100_steps=0,
-    goal_dist=0.06,
-    object_in_human_hand_reward=0.0,
-    object_gripped_reward=-0.25,
-    collision_reward=-1.0,
-    done_at_success=True,
-)
-# CollaborativeLiftingCart constructor defaults (collaborative_lifting_cartesian_env.py:215-280) overlaid with
-# config/environment/(default/)collaborative_lifting_cart.yaml
-LIFTING_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    horizon=5000,
-    table_full_size=[0.4, 1.5, 0.05],
-    board_full_size=[1.0, 0.4, 0.03],
-    board_density=20.0,                 # BoxObject(name="board", density=20), 755-760
-    board_released_reward=-10.0,
-    imbalance_failure_reward=-10.0,
-    min_balance=0.8,
-    collision_reward=0,
-    reward_shaping=True,
-    done_at_success=True,
-    human_animation_freq=20,
-    human_rand=[0.0, 0.0, 0.0],
-    n_animations_sampled_per_100_steps=0.2,
-    safe_vel=0.001,
-    lift_anchors=[[-0.45, 0.25, 0.0], [-0.45, -0.25, 0.0]],   # l_anchor / r_anchor of _postprocess_model, 786-795
-)
-# CollaborativeStackingCart constructor defaults (collaborative_stacking_cartesian_env.py:316-386) overlaid with
-# config/environment/(default/)collaborative_stacking_cart.yaml
-STACKING_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    horizon=3000,
-    table_full_size=[1.2, 2.0, 0.05],
-    object_full_size=[0.045, 0.045, 0.045],
-    goal_dist=0.025,
-    n_object_placements_sampled_per_100_steps=2,
-    n_animations_sampled_per_100_steps=5,
-    collision_reward=0.0,
-    stack_toppled_reward=-10.0,
-    task_reward=2.0,
-    second_cube_at_target_reward=0.0,
-    fourth_cube_at_target_reward=1.0,
-    object_gripped_reward=0.75,
-    human_rand=[0.02, 0.1, 0.1],
-    done_at_success=True,
-    stack_weld_relpos=[0.0, 0.045, 0.0],   # relpose of lh_weld_eq / rh_weld_eq (1263-1281)
-)
 # Stand-in for robosuite 1.3.2's composite HammerObject (absent; its dimensions are drawn at random per instance): a box handle at the middle of the
 # reference's ranges (handle_radius 0.015-0.02, handle_length 0.1-0.25, handle_density 100-250) and ONE box for head + neck + face
 # (head_halfsize between 1 and 1.2 handle radii, head_density_ratio 2); no claw.  Body frame: origin = middle of the handle, handle along z, head along x.
@@ -172,43 +40,6 @@ HAMMER = dict(handle_half=[0.0175, 0.0175, 0.0875], handle_density=175.0, head_h
 # models/assets/objects/nail.xml: nail_head body 0.06 above nail_base, collision cylinder r 0.02 / half height 0.002 at +0.001 (stand-in: a box of the same
 # extents), slide joint along -z, range [0, 0.06], frictionloss 10000, solreffriction (-100, -100)
 NAIL = dict(head_half=[0.02, 0.02, 0.002], head_dz=0.001, stem=0.06, range=0.06, frictionloss=10000.0, fric_damping=100.0, dummy_half=0.01)
-# CollaborativeHammeringCart constructor defaults (collaborative_hammering_cartesian_env.py:291-367) overlaid with training/config/environment/default/
-# collaborative_hammering_cart.yaml (table / board sizes, sampling rates) and, on top, the TOP-LEVEL training/config/environment/collaborative_hammering_cart.yaml
-# -- the convention of every other task here (what make_vec_env(env_id) steps is what the reference's training config for that env would step).  The top-level
-# file sets collision_reward 0, nail_hammered_in_reward 0.0, done_at_success false; its defaults list composes default/pick_place_human_cart instead of
-# default/collaborative_hammering_cart (a quirk of the reference: the task has no experiment config), which is NOT followed -- the task's own default file is.
-HAMMERING_ENV_KWARGS = dict(
-    PICK_PLACE_ENV_KWARGS,
-    horizon=1000,
-    table_full_size=[1.5, 2.0, 0.05],
-    board_full_size=[1.0, 0.4, 0.03],
-    n_nail_placements_sampled_per_100_steps=1,
-    goal_tolerance=0.05,
-    collision_reward=0.0,
-    hammer_gripped_reward_bonus=0.0,
-    nail_hammered_in_reward=0.0,
-    done_at_collision=False,
-    done_at_success=False,
-    task_reward=1.0,
-    human_animation_freq=100,
-    human_rand=[0.0, 0.0, 0.0],
-    n_animations_sampled_per_100_steps=5,   # default/human_env.yaml:60 through the task's default file (the constructor's own default is 1; round 3: was 1)
-    gripper_controllable=False,
-    noslip_iterations=20,       # self.sim.model.opt.noslip_iterations = 20 (_setup_references, 1161); 0 switches the pass off (round 2's model: the nail creeps)
-    noslip_tolerance=1e-6,      # MuJoCo's default opt.noslip_tolerance
-    nail_frictionloss=NAIL["frictionloss"],   # nail.xml:7 (10 000 N); a model parameter so that tests can show a nail yielding to a force above it
-    hammer_anchors=[[-0.1, 0.2, 0.0], [-0.5, -0.2, 0.0]],   # l_anchor / r_anchor of _postprocess_model (1001-1002)
-    hammer_weld_relquat=[0.0, 0.0, 0.0, 1.0],               # relpose of rh_eq: "0 0 0 0 0 0 1" (1123-1131)
-)
-ENV_DEFAULTS = {"CollaborativeHammeringCart": HAMMERING_ENV_KWARGS, "CollaborativeStackingCart": STACKING_ENV_KWARGS, "CollaborativeLiftingCart": LIFTING_ENV_KWARGS, "ReachHuman": DEFAULT_ENV_KWARGS, "ReachHumanCart": REACH_CART_ENV_KWARGS, "PickPlaceHumanCart": PICK_PLACE_ENV_KWARGS, "HumanRobotHandoverCart": HANDOVER_H2R_ENV_KWARGS,
-                "RobotHumanHandoverCart": HANDOVER_R2H_ENV_KWARGS,
-                "PickPlaceCloseHumanCart": PICK_PLACE_CLOSE_ENV_KWARGS, "PickPlacePointingHumanCart": POINTING_ENV_KWARGS,
-                "HumanObjectInspectionCart": INSPECTION_ENV_KWARGS}
-BOX_TASKS = ("CollaborativeStackingCart", "CollaborativeLiftingCart", "PickPlaceHumanCart", "PickPlaceCloseHumanCart", "PickPlacePointingHumanCart", "HumanObjectInspectionCart", "HumanRobotHandoverCart",
-             "RobotHumanHandoverCart")
-_TASK_OF = {"CollaborativeStackingCart": "HRG_TASK_STACKING", "CollaborativeLiftingCart": "HRG_TASK_LIFTING", "PickPlaceHumanCart": "HRG_TASK_PICK_PLACE", "PickPlaceCloseHumanCart": "HRG_TASK_PICK_PLACE",
-            "PickPlacePointingHumanCart": "HRG_TASK_POINTING", "HumanObjectInspectionCart": "HRG_TASK_INSPECTION",
-            "HumanRobotHandoverCart": "HRG_TASK_HANDOVER_H2R", "RobotHumanHandoverCart": "HRG_TASK_HANDOVER_R2H"}
 # RethinkValidGripper.qpos_range (models/grippers/rethink_valid_gripper.py:29-42)
 FINGER_QPOS_RANGE = [[-0.0118366, 0.011499], [0.0118366, -0.011499]]
 
@@ -371,7 +202,8 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
     penetration of that box by MPR, one contact per pair; the finger and gripper capsules stay capsules."""
     if env_id not in ENV_DEFAULTS:
         raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)}")
-    kw = dict(ENV_DEFAULTS[env_id])
+    task = task_row(env_id, reach_box)
+    kw = dict(task.env_kwargs)
     _check_env_kwargs(env_id, kw, env_kwargs or {})
     kw.update(env_kwargs or {})
     sp = dict(SHIELD_DEFAULTS)
@@ -633,18 +465,16 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
         raise ValueError("collision_prevention: replace_type in {0,1,2}, n_resamples <= 64")
     d.goal_check = int(bool(goal_check))
     d.self_collision_safety = float(kw["self_collision_safety"])
-    d.obstacle_margin = 0.0 if env_id in BOX_TASKS else 0.01   # safety_margin: pick_place_human_cartesian_env.py:696-700 / reach_human_env.py:589-593
+    d.obstacle_margin = 0.0 if task.world == "pick_place" else 0.01   # safety_margin: pick_place_human_cartesian_env.py:696-700 / reach_human_env.py:589-593
     d.base_cyl_r, d.base_cyl_z = 0.2, 0.91
     # ---- manipulation object / task (pick_place_human_cartesian_env.py:257-404, 613-708, 843-875)
     for f in range(CONST["HRG_NFINGER"]):
         d.finger_qpos_range[0][f], d.finger_qpos_range[1][f] = FINGER_QPOS_RANGE[0][f], FINGER_QPOS_RANGE[1][f]
-    d.task = CONST["HRG_TASK_REACH"]
     if reach_box and env_id != "ReachHuman":
         raise ValueError("reach_box: the smallBox object belongs to ReachHuman")   # (ReachHumanCart always steps with it)
-    if reach_box or env_id == "ReachHumanCart":
-        d.task = CONST["HRG_TASK_REACH_BOX"]
-        if env_id == "ReachHumanCart":   # ReachHuman's world, the goal an end-effector position (reach_human_cartesian_env.py)
-            d.task = CONST["HRG_TASK_REACH_CART"]
+    d.task = task.task
+    if task.world == "reach" and task.block == "box":   # the ReachHuman world with its smallBox
+        if env_id == "ReachHumanCart":   # the goal an end-effector position (reach_human_cartesian_env.py)
             for k in ("table_friction", "table_full_size"):   # (a settings file read without OmegaConf hands 5e-3 over as a string)
                 if not _same_list(kw[k], ENV_DEFAULTS[env_id][k]):
                     raise NotImplementedError(f"{env_id}: env kwarg {k}={kw[k]!r} is not implemented by the HIP stepper (only {ENV_DEFAULTS[env_id][k]!r})")
@@ -668,8 +498,7 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
         d.tgt_bin[:] = [-bx, bx, -by, by]
         d.obj_z = d.tgt_z = 0.8 + half[2]
         d.n_obj_placements = d.n_targets = 1
-    if env_id in BOX_TASKS:
-        d.task = CONST[_TASK_OF[env_id]]
+    if task.world == "pick_place":
         d.init_qpos[:] = [0.0, 0.0, -math.pi / 2, 0.0, -math.pi / 2, math.pi / 4]   # _reset_internal, 616
         lifting = env_id == "CollaborativeLiftingCart"
         size = [float(x) for x in kw["board_full_size" if lifting else "object_full_size"]]
@@ -724,7 +553,7 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
         d.n_obj_placements = max(int(kw["horizon"] * kw["n_object_placements_sampled_per_100_steps"] / 100), 1)
         d.n_targets = max(int(kw["horizon"] * kw["n_targets_sampled_per_100_steps"] / 100), 1)
         d.object_gripped_reward = float(kw["object_gripped_reward"])
-    if env_id == "CollaborativeHammeringCart":
+    if task.world == "hammering":
         # diagonal of M at qpos0 over the human's 69 hinges (they are dynamic DoF of the reference's model: stat.meaninertia counts them): every body has mass 1,
         # inertia diag(1, 1, 1) and its inertial frame at the common origin (human.xml:46); a hinge carries the bodies of its subtree
         n_sub = [1] * len(HB)
@@ -771,7 +600,6 @@ def build_model_desc(env_kwargs=None, n_clips=1, shield_params=None, assets=None
 def _fill_hammering(d, kw, tree_M0_diag):
     """CollaborativeHammeringCart (collaborative_hammering_cartesian_env.py): board, hammer stand-in, nail, the two hand equalities, task parameters."""
     NARM, NF = CONST["HRG_NARM"], CONST["HRG_NFINGER"]
-    d.task = CONST["HRG_TASK_HAMMERING"]
     d.init_qpos[:] = [0.0, 0.0, -math.pi / 2, 0.0, -math.pi / 2, math.pi / 4]   # _reset_internal, 720
     tx, ty = kw["table_full_size"][0], kw["table_full_size"][1]
     d.table_half[:] = [0.5 * tx, 0.5 * ty]

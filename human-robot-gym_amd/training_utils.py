@@ -144,10 +144,11 @@ def wrapper_kwargs_from_config(config) -> Dict[str, Any]:
             if float(abk.get("alpha") or 0.0) != 0.0:   # alpha = 0 without an expert: the environment reward unchanged; skipped as before
                 raise NotImplementedError("wrappers.action_based_expert_imitation_reward without a config.expert node (the reference asserts: No expert specified in config!)")
         else:
-            from .expert import expert_kwargs
+            from .expert import EXPERT_ENVS, expert_kwargs
             ek = dict(_plain(expert))   # _compose_expert_kwargs / create_expert (training_utils.py:138-174): id selects the class, obs_keys is dropped
             ek.pop("obs_keys", None)
-            if ek.get("id") == "ReachHumanCart" and _get(_get(config, "environment"), "env_id") != "ReachHumanCart":
+            # (every other expert on a task it does not fit is refused when the env is built, HipVecEnv._check_expert; this one also before its arguments are read)
+            if ek.get("id") == "ReachHumanCart" and _get(_get(config, "environment"), "env_id") not in EXPERT_ENVS["ReachHumanCart"]:
                 raise NotImplementedError("expert ReachHumanCart reads the goal_difference of the ReachHumanCart environment only (config.environment.env_id)")
             expert_kwargs(ek)           # unknown ids and arguments raise now, not at the first step
             out["expert"] = ek

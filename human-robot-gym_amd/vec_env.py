@@ -21,7 +21,8 @@ import numpy as np
 
 from ._cstruct import CONST
 from .animation import synthetic_clips
-from .model import build_model_desc, DEFAULT_ENV_KWARGS, ENV_DEFAULTS
+from .model import build_model_desc
+from .tasks import OBS_KEYS, PICK_PLACE_OBS_KEYS, TASKS, Goal, task_row  # noqa: F401  (the two key lists: names other code imports from here)
 
 try:  # pragma: no cover - not installed in the build image
     from stable_baselines3.common.vec_env import VecEnv as _VecEnvBase
@@ -71,20 +72,9 @@ INFO_KEYS = [  # column order of the kernel's info block (include/hrgym.h)
     "n_collisions_critical", "timeout", "failsafe_interventions", "n_goal_reached", "TimeLimit.truncated", "sim_crash",
     "action_resamples", "n_object_handed_over",
 ]
-INFO_KEY_ALIASES = {"CollaborativeStackingCart": {"n_object_handed_over": "max_stack_height"}}   # the task-specific info column (include/hrgym.h HRG_INFO_MAX_STACK_HEIGHT)
 _BOOL_KEYS = {"collision", "timeout", "TimeLimit.truncated", "sim_crash"}
 _BOOL_ITEMS = [(j, k) for j, k in enumerate(INFO_KEYS) if k in _BOOL_KEYS]
-OBS_KEYS = ["object-state", "goal_difference"]  # default: training/config/human_reach_ppo_parallel.yaml:14-16
-# training/config/run/obs_keys of the pick-place experiments (e.g. PP-SAC): the observables the policy sees
-PICK_PLACE_OBS_KEYS = ["object_gripped", "vec_eef_to_object", "vec_eef_to_target", "gripper_aperture", "dist_eef_to_human_head",
-                       "dist_eef_to_human_lh", "dist_eef_to_human_rh"]
-STACKING_OBS_KEYS = ["object_gripped", "vec_eef_to_all_objects", "gripper_aperture", "dist_eef_to_human_head", "dist_eef_to_human_lh", "dist_eef_to_human_rh"]   # CS-SAC.yaml run.obs_keys
-LIFTING_OBS_KEYS = ["board_quat", "dist_eef_to_human_head", "vec_eef_to_human_lh", "vec_eef_to_human_rh"]   # CL-SAC.yaml run.obs_keys
-HAMMERING_OBS_KEYS = ["hammer_gripped", "vec_eef_to_nail", "nail_hammering_progress", "vec_eef_to_board", "board_quat", "dist_eef_to_human_head", "dist_eef_to_human_lh",
-                      "dist_eef_to_human_rh"]   # no run config ships for this task; the expert reads vec_eef_to_nail (collaborative_hammering_cart_expert.py:24-25)
-_TASK_OBS_KEYS = {"ReachHuman": OBS_KEYS, "ReachHumanCart": OBS_KEYS, "CollaborativeLiftingCart": LIFTING_OBS_KEYS, "CollaborativeStackingCart": STACKING_OBS_KEYS,
-                  "CollaborativeHammeringCart": HAMMERING_OBS_KEYS}
-DEFAULT_OBS_KEYS = {k: _TASK_OBS_KEYS.get(k, PICK_PLACE_OBS_KEYS) for k in ENV_DEFAULTS}   # the pick-place, inspection and handover tasks: the pick-place keys
+DEFAULT_OBS_KEYS = {env_id: t.obs_keys for env_id, t in TASKS.items()}
 # columns of the kernel's observation superset (include/hrgym.h HRG_OBS_DIM) per robosuite observable / modality key
 OBS_COLUMNS = {
     "object-state": range(0, 12), "goal_difference": range(12, 18), "robot0_joint_pos": range(18, 24),
@@ -110,21 +100,7 @@ OBS_COLUMNS = {
 }
 
 
-# per-task column overrides: the same observable name sits in other columns of the superset (oracle: compute_obs_hammer)
-OBS_COLUMNS_TASK = {
-    "CollaborativeHammeringCart": {   # collaborative_hammering_cartesian_env.py:1151-1323
-        "hammer_quat": range(12, 16), "board_pos": range(33, 36), "vec_eef_to_board": range(36, 39), "hammer_gripped": range(39, 40),
-        "vec_eef_to_hammer": range(40, 43), "vec_eef_to_nail": range(43, 46), "hammer_pos": range(47, 50), "nail_pos": range(50, 53),
-        "board_quat": range(57, 61), "nail_hammering_progress": range(61, 62),
-        # "object_quat" is never in this env's observation cache, so the two relative quaternions are constant zeros in the reference (1217-1225, 1259-1267)
-        "quat_eef_to_hammer": [62, 63, 62, 63], "quat_eef_to_board": [62, 63, 62, 63],
-        "desired_goal": range(50, 53),   # _get_desired_goal_from_obs: nail_pos (606-621)
-    },
-    "ReachHumanCart": {   # reach_human_cartesian_env.py:385-434: the ReachHuman layout, the goal an end-effector position (three values; the other three columns are zero)
-        "goal_difference": range(12, 15), "desired_goal": range(33, 36), "robot0_eef_velp": range(40, 43),
-        "goal-state": list(range(33, 36)) + list(range(12, 15)),
-    },
-}
+OBS_COLUMNS_TASK = {env_id: t.columns for env_id, t in TASKS.items()}   # per-task column overrides: the same observable name sits in other columns of the superset
 for _k in ("hammer_quat", "hammer_gripped", "vec_eef_to_hammer", "vec_eef_to_nail", "hammer_pos", "nail_pos", "nail_hammering_progress", "quat_eef_to_hammer"):
     OBS_COLUMNS.setdefault(_k, OBS_COLUMNS_TASK["CollaborativeHammeringCart"][_k])
 OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (hammering overrides it with its constant zeros)
@@ -132,11 +108,7 @@ OBS_COLUMNS["quat_eef_to_board"] = range(57, 61)   # CollaborativeLiftingCart (h
 
 def task_columns(env_id):
     """OBS_COLUMNS as `env_id` fills them."""
-    cols_of = dict(OBS_COLUMNS)
-    if env_id not in ("ReachHuman", "ReachHumanCart"):
-        cols_of["desired_goal"] = OBS_COLUMNS["target_pos"]   # _get_desired_goal_from_obs of the cube tasks
-    cols_of.update(OBS_COLUMNS_TASK.get(env_id, {}))
-    return cols_of
+    return dict(OBS_COLUMNS, **TASKS[env_id].columns)
 
 
 # ActionBasedExpertImitationRewardWrapper._add_reward_to_info (action_based_expert_imitation_reward_wrapper.py:107-130): on the infos of done steps
@@ -393,16 +365,17 @@ class HipVecEnv(_VecEnvBase):
                  device=0, env_id0=0, backend=None, info_dicts=True, collision_prevention=None, goal_check=True, ik_position_delta=None,
                  expert_obs_keys=None, goal_env=False, obs_norm=None, monitor_dir=None, monitor_kwargs=None, reach_box=False, robot_geometry="capsule",
                  expert=None, imitation_reward=None, dataset=None, rsi_prob=None, state_imitation_reward=None):
-        if env_id not in ENV_DEFAULTS:
-            raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(ENV_DEFAULTS)} (DESIGN.md §6)")
+        if env_id not in TASKS:
+            raise NotImplementedError(f"env_id {env_id!r}: the HIP stepper covers {sorted(TASKS)} (DESIGN.md §6)")
         self.env_id = env_id
         self._reach_box = bool(reach_box)   # ReachHuman with its free smallBox object (stepped by the cube kernel); default: the lean model
+        self._task = task_row(env_id, self._reach_box)
         self._robot_geometry = robot_geometry   # "capsule" (default) | "hull": the arm links collide as the convex hulls of their meshes (every task)
         self._init_dataset(self._check_dataset(dataset, rsi_prob, state_imitation_reward, imitation_reward, backend, goal_env), rsi_prob, state_imitation_reward)
         self._check_expert(expert, imitation_reward, backend, goal_env)
         if goal_env and obs_keys is None:  # goal_env_wrapper.py:62-71
             obs_keys = ["object-state", "robot0_proprio-state", "desired_goal"]
-        self._init_columns(obs_keys if obs_keys is not None else DEFAULT_OBS_KEYS[env_id], task_columns(env_id), goal_env=goal_env, expert_obs_keys=expert_obs_keys)
+        self._init_columns(obs_keys if obs_keys is not None else self._task.obs_keys, task_columns(env_id), goal_env=goal_env, expert_obs_keys=expert_obs_keys)
         kw = dict(env_kwargs or {})
         if seed is not None:
             kw["seed"] = int(seed)
@@ -436,14 +409,13 @@ class HipVecEnv(_VecEnvBase):
             if rsi_prob is not None or state_imitation_reward is not None:
                 raise ValueError("rsi_prob / state_imitation_reward need a dataset (the reference's wrappers load one by dataset_name)")
             return None
-        from .dataset import NO_DATASET_ENVS, ExpertDataset
-        env_id, has_box = self.env_id, self._has_box
+        from .dataset import ExpertDataset, check_holds_state
+        env_id, has_box = self.env_id, self._task.block == "box"
         if backend is not None:
             raise NotImplementedError("dataset / state_imitation_reward: the restore and reward kernels run in the HIP library; another backend has none")
         if goal_env:
             raise NotImplementedError("dataset / state_imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
-        if env_id in NO_DATASET_ENVS:
-            raise NotImplementedError(f"dataset: {env_id} keeps its state in further arrays (hrg_stack_state / hrg_hammer_state), which a dataset does not hold")
+        check_holds_state(env_id)
         if state_imitation_reward is not None and imitation_reward is not None:
             raise NotImplementedError("state_imitation_reward with imitation_reward: the reference wraps one imitation reward, state based or action based")
         if not isinstance(dataset, ExpertDataset):
@@ -479,7 +451,7 @@ class HipVecEnv(_VecEnvBase):
         if goal_env:
             raise NotImplementedError("expert / imitation_reward with goal_env: the imitation reward is not a function of the goals (no compute_reward)")
         eid, _ = expert_kwargs(expert)
-        if self.env_id not in EXPERT_ENVS[eid] or self._reach_box:
+        if eid not in self._task.experts:
             raise NotImplementedError(f"expert {eid}: it reads the observation of {EXPERT_ENVS[eid]}, not of {self.env_id}")
 
     def _init_expert(self, expert=None, imitation_reward=None):
@@ -495,18 +467,14 @@ class HipVecEnv(_VecEnvBase):
 
     def _init_columns(self, keys, cols_of, goal_env=False, expert_obs_keys=None):
         """The policy's view of the kernel's observation superset: `keys` concatenated in order (GymWrapper), each looked up in `cols_of`; None: every column."""
-        env_id = self.env_id
         # GoalEnvironmentGymWrapper (wrappers/goal_env_wrapper.py): dict observations {observation, achieved_goal, desired_goal} and an
-        # externalised reward for hindsight relabelling.  Goals per task: ReachHuman joint angles (reach_human_env.py:477-507),
-        # the cube tasks [eef_pos, object_pos, object_gripped] vs target_pos (pick_place_human_cartesian_env.py:574-611)
+        # externalised reward for hindsight relabelling.  The goals per task: tasks.Goal
         self.goal_env = bool(goal_env)
         if self.goal_env:
-            if env_id in ("HumanObjectInspectionCart", "CollaborativeLiftingCart", "CollaborativeStackingCart", "CollaborativeHammeringCart"):
-                raise NotImplementedError("goal_env: this task's success is a task phase, not a function of the goals")
-            self._ag_cols = np.array(list(range(18, 24)) if env_id == "ReachHuman" else [30, 31, 32, 47, 48, 49, 39], dtype=np.int64)
-            self._dg_cols = np.array(list(range(33, 39)) if env_id == "ReachHuman" else [50, 51, 52], dtype=np.int64)
-            if env_id == "ReachHumanCart":   # achieved goal = robot0_eef_pos, desired goal = the goal's eef position (reach_human_cartesian_env.py:338-378)
-                self._ag_cols, self._dg_cols = np.array([30, 31, 32], dtype=np.int64), np.array([33, 34, 35], dtype=np.int64)
+            goal = self._task.goal
+            if not isinstance(goal, Goal):
+                raise NotImplementedError(f"goal_env: {goal}")
+            self._ag_cols, self._dg_cols = np.array(goal.achieved, dtype=np.int64), np.array(goal.desired, dtype=np.int64)
         unknown = [k for k in keys or [] if k not in OBS_COLUMNS and k not in cols_of]   # (a key of OBS_COLUMNS_TASK alone, robot0_eef_velp, exists on its task only)
         if unknown:
             raise NotImplementedError(f"obs_keys {unknown!r}: available {sorted(set(OBS_COLUMNS) | set(cols_of))}")
@@ -555,7 +523,7 @@ class HipVecEnv(_VecEnvBase):
 
     def _init_accounting(self, n_envs, info_dicts):
         self.info_dicts = info_dicts
-        self._info_keys = [INFO_KEY_ALIASES.get(self.env_id, {}).get(k, k) for k in INFO_KEYS]   # names of the info columns (a task may rename its task-specific one)
+        self._info_keys = [dict(self._task.info_aliases).get(k, k) for k in INFO_KEYS] if self.env_id in TASKS else list(INFO_KEYS)   # names of the info columns (a task may rename its task-specific one; a mixed batch does not)
         self._ep_ret = np.zeros(n_envs, np.float64)
         self._ep_len = np.zeros(n_envs, np.int64)
         self._t_start = time.time()
@@ -604,11 +572,6 @@ class HipVecEnv(_VecEnvBase):
         self._monitor.write("#" + json.dumps({"t_start": self._t_start, "env_id": self.env_id, "n_envs": int(n_envs)}) + "\n")
         self._monitor.write(",".join(("r", "l", "t") + self._monitor_keys) + "\n")
         self._monitor.flush()
-
-    @property
-    def _has_box(self):
-        """Does an env carry the object block (hrg_box_state)?  Every task but the lean ReachHuman (with reach_box it does too)."""
-        return self._reach_box or self.env_id != "ReachHuman"
 
     # ---- VecEnv API -------------------------------------------------------------------------------------
     def reset(self):
@@ -805,12 +768,11 @@ class HipVecEnv(_VecEnvBase):
         batch = self._hip_batch("get_states", "get_environment_state")
         idx = self._indices(indices)
         states, boxes = batch.get_states(np.asarray(idx, np.int32))
-        if self.env_id == "CollaborativeStackingCart":   # CollaborativeStackingEnvState (collaborative_stacking_cartesian_env.py:63-97): the four cubes + stack bookkeeping
-            return [(st, batch.get_stack(i)) for st, i in zip(states, idx)]
-        if self.env_id == "CollaborativeHammeringCart":  # CollaborativeHammeringEnvState (collaborative_hammering_cartesian_env.py:56-89): board, hammer, nail + bookkeeping
-            return [(st, batch.get_hammer(i)) for st, i in zip(states, idx)]
-        has_box = self._has_box
-        return [(st, boxes[k] if has_box else None) for k, st in enumerate(states)]
+        block = self._task.block
+        if block in ("stack", "hammer"):   # CollaborativeStackingEnvState / CollaborativeHammeringEnvState: the task's own block next to the state
+            get = batch.get_stack if block == "stack" else batch.get_hammer
+            return [(st, get(i)) for st, i in zip(states, idx)]
+        return [(st, boxes[k] if block == "box" else None) for k, st in enumerate(states)]
 
     def set_environment_state(self, states, indices=None):
         batch = self._hip_batch("set_states", "set_environment_state")
@@ -819,13 +781,14 @@ class HipVecEnv(_VecEnvBase):
             raise ValueError(f"{len(states)} states for {len(idx)} envs")
         from ._cstruct import BoxState, EnvState
         st_arr = (EnvState * len(idx))(*[st for st, _ in states])
-        if self.env_id in ("CollaborativeStackingCart", "CollaborativeHammeringCart"):
+        block = self._task.block
+        if block in ("stack", "hammer"):
             batch.set_states(np.asarray(idx, np.int32), st_arr, None)
             for i, (_, sk) in zip(idx, states):
-                (batch.set_stack if self.env_id == "CollaborativeStackingCart" else batch.set_hammer)(i, sk)
+                (batch.set_stack if block == "stack" else batch.set_hammer)(i, sk)
             return
         boxes = [b for _, b in states]
-        bx_arr = (BoxState * len(idx))(*boxes) if all(b is not None for b in boxes) and self._has_box else None
+        bx_arr = (BoxState * len(idx))(*boxes) if all(b is not None for b in boxes) and block == "box" else None
         batch.set_states(np.asarray(idx, np.int32), st_arr, bx_arr)
 
     def check_collision_action(self, actions):
@@ -865,7 +828,7 @@ class HipVecEnv(_VecEnvBase):
         ag, dg = np.atleast_2d(np.asarray(achieved_goal, np.float64)), np.atleast_2d(np.asarray(desired_goal, np.float64))
         infos = [info] if isinstance(info, dict) else list(info)
         ctype = np.array([int(i.get("collision_type", 0)) for i in infos])
-        if self.env_id in ("ReachHuman", "ReachHumanCart"):   # joint angles / eef positions: the Euclidean distance of the goals
+        if self._task.goal.rule == "distance":   # joint angles / eef positions: the Euclidean distance of the goals
             dist = np.linalg.norm(ag - dg, axis=-1)
             r = np.where(dist <= d.goal_dist, d.task_reward, -1.0)
             dense = -0.1 * dist
@@ -890,7 +853,7 @@ class HipVecEnv(_VecEnvBase):
         ag, dg = np.atleast_2d(np.asarray(achieved_goal, np.float64)), np.atleast_2d(np.asarray(desired_goal, np.float64))
         infos = [info] if isinstance(info, dict) else list(info)
         ctype = np.array([int(i.get("collision_type", 0)) for i in infos])
-        dist = np.linalg.norm(ag - dg, axis=-1) if self.env_id in ("ReachHuman", "ReachHumanCart") else np.linalg.norm(dg - ag[:, 3:6], axis=-1)
+        dist = np.linalg.norm(ag - dg, axis=-1) if self._task.goal.rule == "distance" else np.linalg.norm(dg - ag[:, 3:6], axis=-1)
         illegal = (ctype & (CONST["HRG_COL_STATIC"] | CONST["HRG_COL_ROBOT"] | CONST["HRG_COL_HUMAN_CRIT"])) != 0
         done = (bool(d.done_at_collision) & illegal) | (bool(d.done_at_success) & (dist <= d.goal_dist))
         return bool(done[0]) if isinstance(info, dict) and np.ndim(achieved_goal) == 1 else done
@@ -916,7 +879,7 @@ class HipVecEnv(_VecEnvBase):
         # since the env receives it at env scale (+-ik_action_limit), the same rescaling brings it back to the policy's scale
         front_end = self._cp is not None or self._ik is not None
         low, high = self.action_space.low, self.action_space.high
-        return build_her_desc(n_envs, buffer_size, self.horizon, "reach" if self.env_id == "ReachHuman" else "cube", cols, act_dim=len(low), model_desc=self._desc,
+        return build_her_desc(n_envs, buffer_size, self.horizon, self._task.goal.kind, cols, act_dim=len(low), model_desc=self._desc,
                               n_sampled_goal=n_sampled_goal, goal_selection_strategy=goal_selection_strategy, seed=int(self._desc.seed) if seed is None else seed,
                               act_low=low if front_end else None, act_high=high if front_end else None, dg_in_obs=dg_in_obs, relabel_observation=relabel_observation)
 
@@ -927,9 +890,8 @@ class HipVecEnv(_VecEnvBase):
         again replaces the buffer with an empty one (and, between two runs of the device loop, resets the envs).  Returns the buffer."""
         if not self.goal_env:
             raise NotImplementedError("attach_her: construct with goal_env=True / make_vec_env(type='goal_env')")
-        if self.env_id == "ReachHumanCart":
-            raise NotImplementedError("attach_her: the device buffer has no goal kind for ReachHumanCart (achieved = robot0_eef_pos, desired = the goal's eef position: "
-                                      "HRG_GOAL_REACH relabels joint angles, HRG_GOAL_CUBE object positions)")
+        if self._task.goal.kind is None:
+            raise NotImplementedError(f"attach_her: the device buffer has no goal kind for {self.env_id} ({self._task.goal.no_kind})")
         if not online_sampling:
             raise NotImplementedError("attach_her(online_sampling=False): offline sampling copies relabelled transitions into a second buffer; the device buffer "
                                       "relabels when it samples")
@@ -1237,12 +1199,12 @@ class HipVecEnv(_VecEnvBase):
         """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature
         row), the action bounds."""
         from .evaluation import build_eval_desc
-        if self.goal_env and self.env_id == "ReachHumanCart":
-            raise NotImplementedError("evaluate on a ReachHumanCart goal env: the device feature row has no goal kind for this task (as attach_her)")
+        if self.goal_env and self._task.goal.kind is None:
+            raise NotImplementedError(f"evaluate on a {self.env_id} goal env: the device feature row has no goal kind for this task (as attach_her)")
         mean, std, squash = self._norm if self._norm is not None else (None, None, None)
         return build_eval_desc(n_envs, n_policies, n_eval_episodes, [int(c) for c in self._cols], self.action_space.low, self.action_space.high,
                                observe_time=self._observe_time, mean=mean, std=std, squash_factor=squash,
-                               goal_kind=None if not self.goal_env else "reach" if self.env_id == "ReachHuman" else "cube")
+                               goal_kind=self._task.goal.kind if self.goal_env else None)
 
     def evaluate(self, learner_or_params, n_eval_episodes=10, sync_every=16, learner=None, deterministic=True, render=False):
         """SB3's evaluate_policy(deterministic=True) on the device: `n_eval_episodes` episodes of the deterministic policy, three launches per env step (the
@@ -1362,7 +1324,7 @@ class HipGymEnv:
     def observation_dict(self, obs):
         """Split a flat observation back into the reference's observable / modality keys."""
         out, k0 = OrderedDict(), 0
-        cols_of = task_columns("ReachHumanCart") if getattr(self._vec, "env_id", None) == "ReachHumanCart" else OBS_COLUMNS   # (its goal keys are three wide)
+        cols_of = task_columns(self._vec.env_id)   # (as HipVecEnv put the row together: a task's keys can be narrower than the superset's)
         for key in self._vec.obs_keys:
             n = len(cols_of[key])
             out[key] = obs[k0:k0 + n]
