@@ -3258,6 +3258,90 @@ __global__ __launch_bounds__(64) void HRG_SYM(hrg_chain_fk_kernel)(const DevMode
   for (int j = lane; j < 2 * HRG_NSHIELD_RCAP * 6; j += 64) o[HRG_CFK_SCAP + j] = shield_on ? (&L.scap[0][0][0])[j] : 0.0;
 }
 
+// test tap (hrg_debug_narrowphase): the primitive narrowphase routines on their own, as this variant compiles them.  One query per lane on as many lanes of the wave
+// as the step uses (64 for the segment pair, 32 against a box; box - box: 6 in the stacking, 4 in the hammering, 1 in the lifting kernel, each with a BB_WORK slice of its own, so that lanes diverge between the edge and face branches as in
+// collide_cubes); rotation matrices, centres and extents go through LDS (the dead solver rows) as in the step.  Layouts: include/hrgym.h.
+#define HRG_NP_HAS_BOX (HRG_BOX || HRG_STACK || HRG_HAMMER)
+#define HRG_NP_HAS_BB (HRG_STACK || HRG_HAMMER || HRG_LIFT)
+#define HRG_NP_BOX_LANES 32                                        // segment - box, capsule - box: a rotation matrix and a centre per lane fit every variant's rows
+#define HRG_NP_BB_LANES (HRG_STACK ? 6 : HRG_HAMMER ? 4 : 1)        // box - box: the six cube pairs, the four box pairs, the board against the slab
+__global__ __launch_bounds__(64) void HRG_SYM(hrg_narrowphase_kernel)(int kind, const double* __restrict__ qs, int n, double* __restrict__ out) {
+  const int lane = hrg_lane(), per = kind == HRG_NP_SEGSEG ? 64 : kind == HRG_NP_BOXBOX ? HRG_NP_BB_LANES : HRG_NP_BOX_LANES, k = (int)blockIdx.x * per + lane;
+  const bool on = lane < per && k < n;
+  const double* q = qs + (size_t)(on ? k : 0) * HRG_NP_QDIM;
+  double* o = out + (size_t)(on ? k : 0) * HRG_NP_ODIM;
+  if (on) for (int a = 0; a < HRG_NP_ODIM; a++) o[a] = 0.0;
+  if (kind == HRG_NP_SEGSEG) {
+    if (on) {
+      double c1[3], c2[3];
+      o[0] = seg_seg(q, q + 3, q + 6, q + 9, c1, c2);
+      for (int a = 0; a < 3; a++) { o[1 + a] = c1[a]; o[4 + a] = c2[a]; }
+    }
+    return;
+  }
+#if HRG_NP_HAS_BOX || HRG_NP_HAS_BB
+  Lds& L = g_L;
+  double* W = &L.Jc[0][0];
+  const int sl = on ? lane : 0;
+#endif
+#if HRG_NP_HAS_BOX
+  if (kind == HRG_NP_SEGBOX || kind == HRG_NP_CAPBOX) {
+    static_assert(sizeof(L.Jc) >= sizeof(double) * HRG_NP_BOX_LANES * 12, "a rotation matrix and a centre per lane");
+    double *Rl = W + 12 * sl, *cl = Rl + 9;
+    if (on) {
+      double Rm[9];
+      const double qq[4] = {q[9], q[10], q[11], q[12]};
+      quat2mat(Rm, qq);
+      for (int a = 0; a < 9; a++) Rl[a] = Rm[a];
+      for (int a = 0; a < 3; a++) cl[a] = q[6 + a];
+    }
+    wave_sync();
+    if (on) {
+      const double p1[3] = {q[0], q[1], q[2]}, p2[3] = {q[3], q[4], q[5]}, hb[3] = {q[13], q[14], q[15]}, r = q[16];
+      double cs[3], cb[3];
+      const double e2 = seg_box(p1, p2, cl, Rl, hb, cs, cb);
+      o[0] = e2;
+      for (int a = 0; a < 3; a++) { o[1 + a] = cs[a]; o[4 + a] = cb[a]; }
+      if (kind == HRG_NP_CAPBOX && fsqrt(e2) > 1e-9) {
+        double s2[2][3], b2[2][3];
+        bool two = true;
+        for (int e = 0; e < 2; e++) two = two && cap_box_two(p1, p2, cl, Rl, hb, r, cs, cb, e, s2[e], b2[e]);   // one end per call, as the contact lists ask
+        if (two) {
+          o[7] = 1.0;
+          for (int e = 0; e < 2; e++) for (int a = 0; a < 3; a++) { o[8 + 6 * e + a] = s2[e][a]; o[11 + 6 * e + a] = b2[e][a]; }
+        }
+      }
+    }
+    return;
+  }
+#endif
+#if HRG_NP_HAS_BB
+  if (kind == HRG_NP_BOXBOX) {
+    constexpr int SL = BB_WORK + 30;   // the workspace, then Ra 9 | Rb 9 | pa 3 | pb 3 | ha 3 | hb 3
+    static_assert(sizeof(L.Jc) >= sizeof(double) * HRG_NP_BB_LANES * SL, "box_box2 workspace and arguments of every lane");
+    double *T = W + SL * sl, *Ra = T + BB_WORK, *Rb = Ra + 9, *pa = Rb + 9, *pb = pa + 3, *ha = pb + 3, *hb = ha + 3;
+    if (on) {
+      double Rm[9];
+      const double qa[4] = {q[3], q[4], q[5], q[6]}, qb[4] = {q[13], q[14], q[15], q[16]};
+      quat2mat(Rm, qa);
+      for (int a = 0; a < 9; a++) Ra[a] = Rm[a];
+      quat2mat(Rm, qb);
+      for (int a = 0; a < 9; a++) Rb[a] = Rm[a];
+      for (int a = 0; a < 3; a++) { pa[a] = q[a]; ha[a] = q[7 + a]; pb[a] = q[10 + a]; hb[a] = q[17 + a]; }
+    }
+    wave_sync();
+    if (on) {
+      BBContact bc[4];
+      const int nc = box_box2(pa, Ra, ha, pb, Rb, hb, bc, T);
+      o[0] = (double)nc;
+      for (int z = 0; z < 4; z++)
+        if (z < nc) { for (int a = 0; a < 3; a++) { o[1 + 7 * z + a] = bc[z].pos[a]; o[4 + 7 * z + a] = bc[z].n[a]; } o[7 + 7 * z] = bc[z].dist; }
+    }
+    return;
+  }
+#endif
+}
+
 // Launch shims: every translation unit defines these for its own kernels, under the variant's name and with hidden visibility; the host side (the base
 // translation unit) reaches them through its variant table (HRG_VARIANTS, hrgym_host_batch.h).  objs = the variant's object array (ObjState), null for the ReachHuman kernels.
 typedef void hrg_launch_step_fn(int n_envs, hipStream_t st, const DevModel* dm, hrg_env_state* states, double* actions, float* obs, float* term_obs, float* reward, uint8_t* done,
@@ -3277,6 +3361,16 @@ typedef void hrg_launch_chain_fk_fn(int n, const DevModel* dm, const double* q, 
 extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn HRG_SYM(hrg_launch_chain_fk);
 extern "C" void HRG_SYM(hrg_launch_chain_fk)(int n, const DevModel* dm, const double* q, int shield_on, double* out) {
   hipLaunchKernelGGL(HRG_SYM(hrg_chain_fk_kernel), dim3((unsigned)n), dim3(64), 0, 0, dm, q, n, shield_on, out);
+}
+// (returns 0 without a launch for a kind this variant does not compile)
+typedef int hrg_launch_narrowphase_fn(int kind, int n, const double* q, double* out);
+extern "C" __attribute__((visibility("hidden"))) hrg_launch_narrowphase_fn HRG_SYM(hrg_launch_narrowphase);
+extern "C" int HRG_SYM(hrg_launch_narrowphase)(int kind, int n, const double* q, double* out) {
+  const bool has = kind == HRG_NP_SEGSEG || (HRG_NP_HAS_BOX && (kind == HRG_NP_SEGBOX || kind == HRG_NP_CAPBOX)) || (HRG_NP_HAS_BB && kind == HRG_NP_BOXBOX);
+  if (!has) return 0;
+  const int per = kind == HRG_NP_SEGSEG ? 64 : kind == HRG_NP_BOXBOX ? HRG_NP_BB_LANES : HRG_NP_BOX_LANES;
+  hipLaunchKernelGGL(HRG_SYM(hrg_narrowphase_kernel), dim3((unsigned)((n + per - 1) / per)), dim3(64), 0, 0, kind, q, n, out);
+  return 1;
 }
 
 #ifdef HRG_STAMPS

@@ -71,14 +71,15 @@ enum { HRG_FAM_REACH, HRG_FAM_BOX, HRG_FAM_HO, HRG_FAM_LIFT, HRG_FAM_STACK, HRG_
 #define X(family, hulls, sfx)                                                                  \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn hrg_launch_step##sfx;    \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;  \
-  extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn hrg_launch_chain_fk##sfx;
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn hrg_launch_chain_fk##sfx;  \
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_narrowphase_fn hrg_launch_narrowphase##sfx;
 HRG_VARIANTS(X)
 #undef X
-struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; hrg_launch_chain_fk_fn* chain_fk; };
+struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; hrg_launch_chain_fk_fn* chain_fk; hrg_launch_narrowphase_fn* narrowphase; };
 struct VariantTable { Variant v[HRG_NFAMILY][2]; };   // [family][hulls]
 static constexpr VariantTable make_variants() {
   VariantTable t{};
-#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx, hrg_launch_chain_fk##sfx};
+#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx, hrg_launch_chain_fk##sfx, hrg_launch_narrowphase##sfx};
   HRG_VARIANTS(X)
 #undef X
   return t;
@@ -740,6 +741,21 @@ int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t sh
   return tap_result(hrg_run_tap(in, 1, out_host, sizeof(double) * HRG_CFK_DIM * (size_t)n, [&](void** d) {
     v.chain_fk((int)n, b->d_model, (const double*)d[0], shield_on ? 1 : 0, (double*)d[1]);
   }), "hrg_debug_chain_fk");
+}
+
+int hrg_debug_narrowphase(hrg_batch* b, int32_t kind, const double* queries_host, int32_t n, double* out_host) {
+  if (!b || !queries_host || !out_host || n < 1 || n > HRG_NP_MAX) return fail(HRG_ERR_INVALID, "null argument or n outside 1..HRG_NP_MAX");
+  if (kind < HRG_NP_SEGSEG || kind > HRG_NP_BOXBOX) return fail(HRG_ERR_INVALID, "no such kind of narrowphase query");
+  HIPCHK(hipSetDevice(b->device));
+  void* objs;
+  const Variant& v = batch_variant(b, &objs);
+  bool has = true;
+  const TapBuf in[] = {{queries_host, sizeof(double) * HRG_NP_QDIM * (size_t)n}};
+  const bool ok = hrg_run_tap(in, 1, out_host, sizeof(double) * HRG_NP_ODIM * (size_t)n, [&](void** d) {
+    has = v.narrowphase((int)kind, (int)n, (const double*)d[0], (double*)d[1]) != 0;
+  });
+  if (!has) return fail(HRG_ERR_UNSUPPORTED, "this batch's kernel variant does not compile that routine");
+  return tap_result(ok, "hrg_debug_narrowphase");
 }
 
 } // extern "C"

@@ -846,10 +846,12 @@ DI void shield_reset(const DevModel* __restrict__ /*dm_*/, int lane) {
 #if HRG_STACK || HRG_HAMMER || HRG_LIFT
 // Contacts of two boxes with half extents ha / hb (centres pa / pb, rotations Ra / Rb row-major in LDS; the stacking task's cubes share one h): separating-axis test over the 15 axes, then
 // the reference face's rectangle clipped against the incident face (candidates: incident vertices, rectangle corners under the incident face, edge
-// crossings; at most four penetrating candidates that span the patch are kept) or one edge-edge contact.  Restated as in
+// crossings; at most four penetrating candidates that span the patch are kept: the deepest, the farthest from it, the farthest from their line on either side or, where
+// one side is empty, the farthest outside the triangle kept so far) or one edge-edge contact.  Restated as in
 // oracle/hrg_oracle.c box_box; one lane runs one pair.  Normal from box a to box b.  Returns the number of contacts (<= 4).
 // near-ties between separating axes / candidate depths go to the earlier one unless the later wins by this margin (1 nm)
 #define BB_TIE 1e-9
+#define BB_ON (1 + 1e-12)   // where no candidate is found at all (two outlines that coincide up to rounding), the incident vertices are offered again with this slack
 struct BBContact { double pos[3], n[3], dist; };
 // T: 144 doubles of the caller's LDS scratch -- the candidate table (72) and the function's index-addressed arrays (axes, their products, the clipping frame: as
 // private arrays they live in scratch memory, and a single lane's scratch stores cost a partial cache line each: 5.6 KB of HBM writes per call)
@@ -973,12 +975,16 @@ DI int box_box2(const double* pa, const double* Ra, const double* ha, const doub
   // keep at most four that span the patch: the deepest, the one farthest from it, the farthest from their line on either side (ties -> lowest index)
   int pick[4], np_ = 0;
   const double eps2 = 1e-12 * (hu * hu + hv * hv);
-  {
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
     int arg = -1;
     double bd = 0;
 #pragma unroll 1
     for (int q = 0; q < 24; q++) { const double dq = T[48 + q]; if (dq < 0 && (arg < 0 || dq < bd - BB_TIE)) { arg = q; bd = dq; } }
     if (arg >= 0) pick[np_++] = arg;
+    if (arg >= 0 || pass) break;
+    for (int q = 0; q < 4; q++)   // no candidate: coinciding outlines (BB_ON)
+      if (fabs(vu[q]) <= hu * BB_ON && fabs(vv[q]) <= hv * BB_ON) offer(q, vu[q], vv[q], vd[q]);
   }
   if (np_ == 1) {
     int arg = -1;
@@ -1005,6 +1011,23 @@ DI int box_box2(const double* pa, const double* Ra, const double* ha, const doub
     }
     if (argp >= 0) pick[np_++] = argp;
     if (argn >= 0) pick[np_++] = argn;
+  }
+  if (np_ == 3) {   // the line of the first two is an edge of the patch, one side of it is empty: the fourth is the candidate farthest outside the kept triangle's other two edges
+    int arg = -1;
+    double bo = fsqrt(eps2);
+    const double u2 = T[pick[2]], v2 = T[24 + pick[2]];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      const double ue = T[pick[e]], ve = T[24 + pick[e]], lu = u2 - ue, lv = v2 - ve, il = 1.0 / fsqrt(lu * lu + lv * lv);
+      const double in_ = lu * (T[24 + pick[1 - e]] - ve) - lv * (T[pick[1 - e]] - ue) > 0 ? -il : il;   // the third kept point lies inside
+#pragma unroll 1
+      for (int q = 0; q < 24; q++) {
+        if (!(T[48 + q] < 0)) continue;
+        const double o_ = in_ * (lu * (T[24 + q] - ve) - lv * (T[q] - ue));
+        if (o_ > bo * (1 + 1e-9)) { arg = q; bo = o_; }
+      }
+    }
+    if (arg >= 0) pick[np_++] = arg;
   }
   for (int z = 0; z < np_; z++) {
     const double u = T[pick[z]], v = T[24 + pick[z]], dpt = T[48 + pick[z]];

@@ -735,6 +735,20 @@ int hrg_debug_model_constants(hrg_batch* b, double* out_host);
  * do without a shield: the HRG_CFK_SCAP block is then 0 and the first two configurations are not read.  0 / -1. */
 enum { HRG_CFK_KR = 0, HRG_CFK_KP = 9 * HRG_NV, HRG_CFK_SCAP = 12 * HRG_NV, HRG_CFK_DIM = HRG_CFK_SCAP + 2 * HRG_NSHIELD_RCAP * 6 };
 int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t shield_on, double* out_host);
+/* test tap of the primitive narrowphase (seg_seg, seg_box, cap_box_two: csrc/hrgym_device.h; box_box2: csrc/hrgym_kernels.h) as the batch's kernel variant compiles
+ * the routines: n (1..HRG_NP_MAX) queries of one `kind`, queries_host[n][HRG_NP_QDIM] -> out_host[n][HRG_NP_ODIM], everything the routine returns.  Rotations are
+ * unit quaternions (w, x, y, z).
+ *   HRG_NP_SEGSEG  {p1 3, q1 3, p2 3, q2 3}                     -> {d^2, c1 3, c2 3}
+ *   HRG_NP_SEGBOX  {p1 3, p2 3, centre 3, quat 4, half 3}        -> {d^2, on_seg 3, on_box 3}
+ *   HRG_NP_CAPBOX  {p1 3, p2 3, centre 3, quat 4, half 3, r}     -> {d^2, on_seg 3, on_box 3, two, s[0] 3, b[0] 3, s[1] 3, b[1] 3}: seg_box, then cap_box_two for each end
+ *                                                                   as the contact lists call it (only for a closest pair farther apart than 1e-9); the ends are 0 unless `two`
+ *   HRG_NP_BOXBOX  {pa 3, qa 4, ha 3, pb 3, qb 4, hb 3}          -> {count, 4 x (pos 3, normal 3, dist)}; the contacts past `count` are 0
+ * One query per lane, on as many lanes of a wavefront as the step kernels use (64 for the segment pair, 32 against a box; box - box: the stacking kernel's 6, the
+ * hammering kernel's 4, the lifting kernel's 1, each with its own BB_WORK slice of LDS);
+ * rotation matrices and centres go through LDS as in the step.  HRG_ERR_UNSUPPORTED for a kind the batch's variant does not compile (the ReachHuman kernels: the
+ * segment pair only; box - box: the stacking, hammering and lifting kernels).  0 / error code. */
+enum { HRG_NP_SEGSEG = 0, HRG_NP_SEGBOX = 1, HRG_NP_CAPBOX = 2, HRG_NP_BOXBOX = 3, HRG_NP_QDIM = 24, HRG_NP_ODIM = 32, HRG_NP_MAX = 4096 };
+int hrg_debug_narrowphase(hrg_batch* b, int32_t kind, const double* queries_host, int32_t n, double* out_host);
 
 /* HumanEnv.check_collision_action (human_env.py:588-627; called by CollisionPreventionWrapper, wrappers/collision_prevention_wrapper.py:38-51, and
  * utils/training_utils.py:362-366): would the joint-space action drive the robot into the static scene or itself?  The goal configuration the

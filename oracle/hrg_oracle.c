@@ -2545,11 +2545,16 @@ static void stack_animation_time(const hrgo_batch* b, int64_t gid, const hrg_env
  * least penetration decides.  A face axis: the face of the other box most anti-parallel to it is clipped against the reference face's rectangle --
  * candidates = incident vertices inside the rectangle (0..3), rectangle corners under the incident face (4..7), crossings of the incident edges with the
  * rectangle's sides (8..23); of those that penetrate, at most four are kept: the deepest, the one farthest from it, and the farthest from their line on
- * either side (a resting face keeps a quadrilateral that spans its support polygon).  An edge-edge axis (only when clearly less penetrating, factor 1.05): one contact between the closest points of the two
+ * either side; where that line is an edge of the patch and one side of it is empty, the candidate farthest outside the triangle kept so far (a resting face whose
+ * overlap has four or more corners keeps four of them, a rectangle or parallelogram all four: DESIGN.md section 2d).  An edge-edge axis (only when clearly less penetrating, factor 1.05): one contact between the closest points of the two
  * edges.  Normal from box a to box b.  Stand-in for mjc_BoxBox [UPSTREAM]. */
 /* near-ties between separating axes / candidate depths are broken towards the earlier one unless the later wins by this margin (1 nm): two nearly
  * parallel cubes keep their reference face while rounding-level differences come and go */
 #define BB_TIE 1e-9
+/* Two faces whose outlines coincide up to rounding (equal cubes stacked at a yaw of 90 degrees, where the rotation matrix carries 2e-16) have every vertex and corner
+ * just outside the other outline and no edge that crosses one: where no candidate is found at all, the incident vertices are offered again with this slack, so
+ * that the boxes do not fall through each other */
+#define BB_ON (1 + 1e-12)
 static int box_box2(const double* pa, const double* Ra, const double* ha, const double* pb, const double* Rb, const double* hb, bb_contact out[4]) {
   double A[3][3], B[3][3], C[3][3], AC[3][3], t[3], ta[3], tb[3];
   v3sub(t, pb, pa);
@@ -2664,14 +2669,18 @@ static int box_box2(const double* pa, const double* Ra, const double* ha, const 
     }
   }
   /* of the penetrating candidates keep at most four that span the contact patch: the deepest, the one farthest from it, then the one farthest from
-   * their line on either side (ties -> the lowest candidate index; a candidate closer than 1e-6 of an edge to what is already kept adds nothing) */
+   * their line on either side, or farthest outside the triangle where one side is empty (ties -> the lowest candidate index; a candidate closer than 1e-6 of an
+   * edge to what is already kept adds nothing) */
   int pick[4], np_ = 0;
   const double eps2 = 1e-12 * (hu * hu + hv * hv);
   for (int c_ = 0; c_ < 24; c_++) if (ok[c_] && !(cd[c_] < 0)) ok[c_] = 0;
-  {
+  for (int pass = 0; pass < 2; pass++) {
     int arg = -1;
     for (int c_ = 0; c_ < 24; c_++) if (ok[c_] && (arg < 0 || cd[c_] < cd[arg] - BB_TIE)) arg = c_;
     if (arg >= 0) pick[np_++] = arg;
+    if (arg >= 0 || pass) break;
+    for (int q = 0; q < 4; q++) /* no candidate: coinciding outlines (BB_ON) */
+      if (fabs(vu[q]) <= hu * BB_ON && fabs(vv[q]) <= hv * BB_ON && vd[q] < 0) { ok[q] = 1; cu[q] = vu[q]; cv[q] = vv[q]; cd[q] = vd[q]; }
   }
   if (np_ == 1) {
     int arg = -1;
@@ -2695,6 +2704,20 @@ static int box_box2(const double* pa, const double* Ra, const double* ha, const 
     }
     if (argp >= 0) pick[np_++] = argp;
     if (argn >= 0) pick[np_++] = argn;
+  }
+  if (np_ == 3) { /* the line of the first two is an edge of the patch, one side of it is empty: the fourth is the candidate farthest outside the kept triangle's other two edges */
+    int arg = -1;
+    double bo = sqrt(eps2);
+    for (int e = 0; e < 2; e++) {
+      const double lu = cu[pick[2]] - cu[pick[e]], lv = cv[pick[2]] - cv[pick[e]], il = 1.0 / sqrt(lu * lu + lv * lv);
+      const double in_ = lu * (cv[pick[1 - e]] - cv[pick[e]]) - lv * (cu[pick[1 - e]] - cu[pick[e]]) > 0 ? -il : il; /* the third kept point lies inside */
+      for (int c_ = 0; c_ < 24; c_++) {
+        if (!ok[c_]) continue;
+        const double o_ = in_ * (lu * (cv[c_] - cv[pick[e]]) - lv * (cu[c_] - cu[pick[e]]));
+        if (o_ > bo * (1 + 1e-9)) { arg = c_; bo = o_; }
+      }
+    }
+    if (arg >= 0) pick[np_++] = arg;
   }
   for (int z = 0; z < np_; z++) {
     const int c_ = pick[z];
@@ -3808,6 +3831,17 @@ void hrgo_test_segbox(const double* p1, const double* p2, const double* c, const
   double R[9], t;
   quat2mat(R, quat);
   out[0] = seg_box(p1, p2, c, R, hb, &t, out + 1, out + 4);
+}
+/* seg_box, then cap_box_two as the contact lists call it (only for a closest pair farther apart than 1e-9): out = [e2 | cs 3 | cb 3 | two | s2[0] 3 | b2[0] 3 | s2[1] 3 | b2[1] 3] */
+void hrgo_test_capbox(const double* p1, const double* p2, const double* c, const double* quat, const double* hb, double r, double* out) {
+  double R[9], t, s2[2][3], b2[2][3];
+  quat2mat(R, quat);
+  for (int k = 0; k < 20; k++) out[k] = 0;
+  out[0] = seg_box(p1, p2, c, R, hb, &t, out + 1, out + 4);
+  if (sqrt(out[0]) > 1e-9 && cap_box_two(p1, p2, c, R, hb, r, out + 1, out + 4, s2, b2)) {
+    out[7] = 1;
+    for (int e = 0; e < 2; e++) for (int k = 0; k < 3; k++) { out[8 + 6 * e + k] = s2[e][k]; out[11 + 6 * e + k] = b2[e][k]; }
+  }
 }
 void hrgo_test_ik(const hrg_model_desc* m, const double* q6, double* act7) {
   hrg_env_state s;

@@ -27,6 +27,8 @@ def load(path=None):
     lib.hrgo_state_bytes.restype = ctypes.c_size_t
     lib.hrgo_desc_bytes.restype = ctypes.c_size_t
     lib.hrgo_test_segseg.restype = ctypes.c_double
+    if hasattr(lib, "hrgo_test_capbox"):   # (an older build compared by tools/oracle_diff.py has none)
+        lib.hrgo_test_capbox.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_double, ctypes.c_void_p]
     lib.hrgo_test_u01.restype = ctypes.c_double
     lib.hrgo_test_u01.argtypes = [ctypes.c_uint64] * 5
     lib.hrgo_test_path.argtypes = [ctypes.c_double] * 7 + [ctypes.c_void_p]
