@@ -195,9 +195,12 @@ struct DevModel {
   // One 32-byte record per capsule: the lane fetches its values with two 16-byte loads from one address instead of seven loads from seven.  th: thickness, v: v_max,
   // al: a_max (ACC) or the ball's length (POS ball; no kind reads both), kj = kind | joint 1 << 8 | joint 2 << 16
   struct alignas(32) HcRec { double th, v, al; int32_t kj, pad; } hc[HRG_NHCAP_MAX];
-  // robot self-collision candidate pairs (i, j) in enumeration order
+  // robot self-collision candidate pairs (i, j) in enumeration order.  One 32-byte record per pair: round 0 of collide fetches what it needs of its pair with two
+  // 16-byte loads from one address.  ij = i | j << 8 | s << 16 | o << 24: s is the LONGER capsule of the pair, which the cull takes as a segment, o the other one, which
+  // it takes as its bounding sphere (self_near).  inv_len2 = 1 / |p2 - p1|^2 of capsule s, 0 for a squared length <= 1e-12 (the closest point is then p1);
+  // bound = hl_o + r_i + r_j + 1e-9; r_j, body_j: rcap_r[j], rcap_body[j]
   int32_t n_self;
-  struct alignas(8) SelfPair { int32_t i, j; } self_ij[64];
+  struct alignas(32) SelfRec { int32_t ij, body_j; double inv_len2, bound, r_j; } self_rec[64];
   // pre-check model pairs (capsules 0..6 + gripper cylinder)
   int32_t n_chk;
   int32_t chk_i[32], chk_j[32];

@@ -3258,6 +3258,42 @@ __global__ __launch_bounds__(64) void HRG_SYM(hrg_chain_fk_kernel)(const DevMode
   for (int j = lane; j < 2 * HRG_NSHIELD_RCAP * 6; j += 64) o[HRG_CFK_SCAP + j] = shield_on ? (&L.scap[0][0][0])[j] : 0.0;
 }
 
+// test tap (hrg_debug_self_pairs): round 0 of collide on its own, one wave per posture q[k] = [NARM] of joint angles (fingers at 0): the chain walk, the capsule end
+// points and, on lane p, candidate pair p through the routines collide calls -- its broadphase verdict, the contact the round reports (the narrowphase behind
+// `__any(near) && valid && near`, as in collide) and the contact the narrowphase reports with the cull compiled out (every valid lane).  Layout: include/hrgym.h.
+__global__ __launch_bounds__(64) void HRG_SYM(hrg_self_pairs_kernel)(const DevModel* __restrict__ dm_, const double* __restrict__ q, int n, double* __restrict__ out) {
+  const int lane = hrg_lane(), k = (int)blockIdx.x;
+  if (k >= n) return;
+  const ModelPtr dm = uniform_model(dm_);
+  Lds& L = g_L;
+  if (lane < NV) L.st.qpos[lane] = lane < NARM ? q[(size_t)k * NARM + lane] : 0.0;
+  wave_sync();
+  robot_chain_fk(dm_, lane, false);
+  wave_sync();
+  robot_capsules_world(dm, lane);
+  wave_sync();
+  double* o = out + (size_t)k * HRG_SP_DIM;
+  if (lane < 6 * HRG_NRCAP) o[HRG_SP_CAPS + lane] = (&L.rcapw[0][0])[lane];
+  const bool valid = lane < dm->n_self;
+  const SelfPair sp = self_pair(dm, valid ? lane : 0);
+  const bool near = valid && self_near(sp);
+  double* op = o + HRG_SP_PAIRS + HRG_SP_PDIM * lane;
+  for (int a = 0; a < HRG_SP_PDIM; a++) op[a] = 0.0;
+  if (valid) { op[0] = sp.i; op[1] = sp.j; op[2] = near ? 1.0 : 0.0; }
+#pragma unroll
+  for (int off = 0; off < 2; off++) {   // 0: the round as collide runs it, 1: without the cull
+    Contact c;
+    c.g1 = c.g2 = c.b1 = c.b2 = 0; c.dist = 0; v3set(c.n, 0, 0, 1); v3set(c.pos, 0, 0, 0);
+    bool hit = false;
+    if (off ? valid : (__any(near) && valid && near)) hit = capsule_pair_contact(dm->m, sp.i, &L.rcapw[sp.j][0], &L.rcapw[sp.j][3], sp.r_j, 0.0, sp.j, c);
+    if (hit) {
+      double* oc = op + 3 + 8 * off;
+      oc[0] = 1.0; oc[1] = c.dist;
+      for (int a = 0; a < 3; a++) { oc[2 + a] = c.n[a]; oc[5 + a] = c.pos[a]; }
+    }
+  }
+}
+
 // test tap (hrg_debug_narrowphase): the primitive narrowphase routines on their own, as this variant compiles them.  One query per lane on as many lanes of the wave
 // as the step uses (64 for the segment pair, 32 against a box; box - box: 6 in the stacking, 4 in the hammering, 1 in the lifting kernel, each with a BB_WORK slice of its own, so that lanes diverge between the edge and face branches as in
 // collide_cubes); rotation matrices, centres and extents go through LDS (the dead solver rows) as in the step.  Layouts: include/hrgym.h.
@@ -3361,6 +3397,11 @@ typedef void hrg_launch_chain_fk_fn(int n, const DevModel* dm, const double* q, 
 extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn HRG_SYM(hrg_launch_chain_fk);
 extern "C" void HRG_SYM(hrg_launch_chain_fk)(int n, const DevModel* dm, const double* q, int shield_on, double* out) {
   hipLaunchKernelGGL(HRG_SYM(hrg_chain_fk_kernel), dim3((unsigned)n), dim3(64), 0, 0, dm, q, n, shield_on, out);
+}
+typedef void hrg_launch_self_pairs_fn(int n, const DevModel* dm, const double* q, double* out);
+extern "C" __attribute__((visibility("hidden"))) hrg_launch_self_pairs_fn HRG_SYM(hrg_launch_self_pairs);
+extern "C" void HRG_SYM(hrg_launch_self_pairs)(int n, const DevModel* dm, const double* q, double* out) {
+  hipLaunchKernelGGL(HRG_SYM(hrg_self_pairs_kernel), dim3((unsigned)n), dim3(64), 0, 0, dm, q, n, out);
 }
 // (returns 0 without a launch for a kind this variant does not compile)
 typedef int hrg_launch_narrowphase_fn(int kind, int n, const double* q, double* out);

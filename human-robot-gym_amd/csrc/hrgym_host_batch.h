@@ -72,14 +72,15 @@ enum { HRG_FAM_REACH, HRG_FAM_BOX, HRG_FAM_HO, HRG_FAM_LIFT, HRG_FAM_STACK, HRG_
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_step_fn hrg_launch_step##sfx;    \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_reset_fn hrg_launch_reset##sfx;  \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_chain_fk_fn hrg_launch_chain_fk##sfx;  \
+  extern "C" __attribute__((visibility("hidden"))) hrg_launch_self_pairs_fn hrg_launch_self_pairs##sfx;  \
   extern "C" __attribute__((visibility("hidden"))) hrg_launch_narrowphase_fn hrg_launch_narrowphase##sfx;
 HRG_VARIANTS(X)
 #undef X
-struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; hrg_launch_chain_fk_fn* chain_fk; hrg_launch_narrowphase_fn* narrowphase; };
+struct Variant { hrg_launch_step_fn* step; hrg_launch_reset_fn* reset; hrg_launch_chain_fk_fn* chain_fk; hrg_launch_self_pairs_fn* self_pairs; hrg_launch_narrowphase_fn* narrowphase; };
 struct VariantTable { Variant v[HRG_NFAMILY][2]; };   // [family][hulls]
 static constexpr VariantTable make_variants() {
   VariantTable t{};
-#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx, hrg_launch_chain_fk##sfx, hrg_launch_narrowphase##sfx};
+#define X(family, hulls, sfx) t.v[family][hulls] = Variant{hrg_launch_step##sfx, hrg_launch_reset##sfx, hrg_launch_chain_fk##sfx, hrg_launch_self_pairs##sfx, hrg_launch_narrowphase##sfx};
   HRG_VARIANTS(X)
 #undef X
   return t;
@@ -289,7 +290,23 @@ static void batch_fill_model(const hrg_model_desc* desc, const hrg_clip_table* c
   int ns = 0;
   for (int i = 0; i < HRG_NRCAP; i++)
     for (int j = i + 1; j < HRG_NRCAP; j++)
-      if ((desc->rcap_selfmask[i] >> j) & 1u) { hm->self_ij[ns].i = i; hm->self_ij[ns].j = j; ns++; }
+      if ((desc->rcap_selfmask[i] >> j) & 1u) {
+        // the longer capsule of the pair is the cull's segment (s), the other one its sphere (o): collide, self_near
+        double len2[2];
+        for (int e = 0; e < 2; e++) {
+          const int c = e ? j : i;
+          len2[e] = 0;
+          for (int a = 0; a < 3; a++) len2[e] += (desc->rcap_p2[c][a] - desc->rcap_p1[c][a]) * (desc->rcap_p2[c][a] - desc->rcap_p1[c][a]);
+        }
+        const bool seg_j = len2[1] > len2[0];
+        const int s = seg_j ? j : i, o = seg_j ? i : j;
+        DevModel::SelfRec& r = hm->self_rec[ns++];
+        r.ij = i | (j << 8) | (s << 16) | (o << 24);
+        r.body_j = desc->rcap_body[j];
+        r.inv_len2 = len2[seg_j] <= 1e-12 ? 0.0 : 1.0 / len2[seg_j];
+        r.bound = hm->rcap_hl[o] + desc->rcap_r[i] + desc->rcap_r[j] + 1e-9;
+        r.r_j = desc->rcap_r[j];
+      }
   hm->n_self = ns;
   int nc = 0;
   for (int i = 0; i < 8; i++)
@@ -741,6 +758,17 @@ int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t sh
   return tap_result(hrg_run_tap(in, 1, out_host, sizeof(double) * HRG_CFK_DIM * (size_t)n, [&](void** d) {
     v.chain_fk((int)n, b->d_model, (const double*)d[0], shield_on ? 1 : 0, (double*)d[1]);
   }), "hrg_debug_chain_fk");
+}
+
+int hrg_debug_self_pairs(hrg_batch* b, const double* q_host, int32_t n, double* out_host) {
+  if (!b || !q_host || !out_host || n < 1 || n > HRG_SP_MAX) return fail(HRG_ERR_INVALID, "null argument or n outside 1..HRG_SP_MAX");
+  HIPCHK(hipSetDevice(b->device));
+  void* objs;
+  const Variant& v = batch_variant(b, &objs);
+  const TapBuf in[] = {{q_host, sizeof(double) * NARM * (size_t)n}};
+  return tap_result(hrg_run_tap(in, 1, out_host, sizeof(double) * HRG_SP_DIM * (size_t)n, [&](void** d) {
+    v.self_pairs((int)n, b->d_model, (const double*)d[0], (double*)d[1]);
+  }), "hrg_debug_self_pairs");
 }
 
 int hrg_debug_narrowphase(hrg_batch* b, int32_t kind, const double* queries_host, int32_t n, double* out_host) {

@@ -1402,9 +1402,8 @@ DI void collide_hammer(const DevModel* __restrict__ dm_, int lane, int* base_io)
   *base_io = base;
 }
 #endif
-// Stand-in for mj_collision (bounding capsules, table top face, floor plane), pair order = contact order.
-PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_out) {
-  const ModelPtr dm = uniform_model(dm_);
+// World-frame end points of the robot's collision capsules (lane c: capsule c) from the tree kinematics in LDS -> L.rcapw.
+DI void robot_capsules_world(ModelPtr dm, int lane) {
   Lds& L = g_L;
   const auto& m = dm->m;
   if (lane < HRG_NRCAP) {
@@ -1415,6 +1414,51 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
     m3mulv(t, R, m.rcap_p1[c]); v3add(&L.rcapw[c][0], p, t);
     m3mulv(t, R, m.rcap_p2[c]); v3add(&L.rcapw[c][3], p, t);
   }   // (the capsule's centre is computed by classify, for the one capsule whose speed it asks for)
+}
+// One robot self pair as round 0 of collide reads it: adjacent fields of DevModel::self_rec[k], two 16-byte loads.
+struct SelfPair { int i, j, s, o, body_j; double inv_len2, bound, r_j; };
+DI SelfPair self_pair(ModelPtr dm, int k) {
+  const struct { int ij, body_j; double inv_len2, bound, r_j; } rec = {dm->self_rec[k].ij, dm->self_rec[k].body_j, dm->self_rec[k].inv_len2, dm->self_rec[k].bound, dm->self_rec[k].r_j};
+  return SelfPair{rec.ij & 0xff, (rec.ij >> 8) & 0xff, (rec.ij >> 16) & 0xff, rec.ij >> 24, rec.body_j, rec.inv_len2, rec.bound, rec.r_j};
+}
+// Broadphase of a robot self pair: the longer capsule s as its axis segment, the other one, o, as its bounding sphere (centre c_o, radius hl_o + r_o).
+//   dist(segment_s, segment_o) >= dist(c_o, segment_s) - hl_o   (every point of segment o lies within hl_o of its centre),
+// so the pair cannot be a contact (segment distance below r_i + r_j) when the closest point of segment s to c_o, with its parameter clamped to the segment, is farther
+// from c_o than bound = hl_o + r_i + r_j + 1e-9.  Two bounding spheres keep the pair of a long link and a short one two links further on for ever (capsules 4 and 7
+// of the Schunk arm: their spheres always overlap, the capsules never touch); with the SHORTER capsule as the segment that pair would pass as well, hence the choice.
+// Conservative in floating point: hl_o and 1 / |p2 - p1|^2 are model constants (rigid capsules) where the world-frame end points carry the rounding of the chain
+// kinematics, some 1e-16 m; the slack of 1e-9 m is seven orders of magnitude above it.  Any parameter in [0, 1] names a point of the segment, and the distance is
+// stationary at the closest one (or the clamp holds it at an end), so an error of the parameter moves the distance only to second order.  inv_len2 = 0 (a capsule
+// of length 0, both of one pair of the arm) puts the closest point at p1.  No square root, no division.
+DI bool self_near(const SelfPair& sp) {
+  const Lds& L = g_L;
+  const double *p = &L.rcapw[sp.s][0], *q = &L.rcapw[sp.o][0];
+  double d[3], w[3], e[3];
+  for (int a = 0; a < 3; a++) { d[a] = p[3 + a] - p[a]; w[a] = 0.5 * (q[a] + q[3 + a]) - p[a]; }
+  const double t = fmin(fmax(v3dot(w, d) * sp.inv_len2, 0.0), 1.0);
+  for (int a = 0; a < 3; a++) e[a] = w[a] - t * d[a];
+  return v3dot(e, e) <= sp.bound * sp.bound;
+}
+// Narrowphase of robot capsule i against the capsule (a1, a2, r2), geom g2: the contact goes into c (g1, g2, b1, dist, n, pos; b2 is the caller's) when the surfaces
+// are closer than `margin`.
+template <class Model>
+DI bool capsule_pair_contact(const Model& m, int i, const double* a1, const double* a2, double r2, double margin, int g2, Contact& c) {
+  const Lds& L = g_L;
+  double c1[3], c2[3], d[3];
+  const double d2 = seg_seg(&L.rcapw[i][0], &L.rcapw[i][3], a1, a2, c1, c2), dd = fsqrt(d2), dist = dd - m.rcap_r[i] - r2;
+  if (!(dist < margin)) return false;
+  v3sub(d, c2, c1);
+  if (dd > 1e-12) v3scl(c.n, d, 1.0 / dd);
+  v3madd(c.pos, c1, c.n, m.rcap_r[i] + 0.5 * dist);
+  c.g1 = i; c.g2 = g2; c.b1 = m.rcap_body[i]; c.dist = dist;
+  return true;
+}
+// Stand-in for mj_collision (bounding capsules, table top face, floor plane), pair order = contact order.
+PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_out) {
+  const ModelPtr dm = uniform_model(dm_);
+  Lds& L = g_L;
+  const auto& m = dm->m;
+  robot_capsules_world(dm, lane);
   wave_sync();
   // Cull of the 240 robot-human pairs: the box around all robot capsules, each inflated by its radius and the human contact margin, against the bounding sphere
   // of every human capsule.  A human capsule whose sphere misses the box cannot be in contact with any robot capsule (conservative); the capsules that come near
@@ -1458,14 +1502,15 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
       int i = 0, g2 = 0;
       double r2 = 0, margin = 0, hl2 = 0;
       const double *a1, *a2;
-      bool valid;
+      bool valid, near = false;
       if (round == 0) {
         valid = lane < dm->n_self;
-        const int sl = valid ? lane : 0;
-        i = valid ? dm->self_ij[sl].i : 0;
-        const int j = valid ? dm->self_ij[sl].j : 1;
-        g2 = j; a1 = &L.rcapw[j][0]; a2 = &L.rcapw[j][3]; r2 = m.rcap_r[j]; hl2 = dm->rcap_hl[j];
-        c.b2 = m.rcap_body[j];
+        const SelfPair sp = self_pair(dm, valid ? lane : 0);
+        i = sp.i;
+        g2 = sp.j; a1 = &L.rcapw[sp.j][0]; a2 = &L.rcapw[sp.j][3]; r2 = sp.r_j;
+        c.b2 = sp.body_j;
+        // broadphase: segment against bounding sphere (self_near); in the steady state of a reaching arm no pair survives it
+        near = valid && self_near(sp);
       } else {
         const int q = (round - 1) * 64 + lane;
         valid = q < n_hpairs;
@@ -1474,29 +1519,19 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
         g2 = GEOM_HUMAN0 + hb; a1 = &L.hcap[hb][0]; a2 = &L.hcap[hb][3]; r2 = m.hcap_r[hb]; hl2 = dm->hcap_hl[hb];
         margin = m.contact_margin_human;
         c.b2 = -2;
-      }
-      // broadphase: bounding spheres of the two capsules (conservative: a culled pair cannot be a contact); the whole
-      // wave skips the narrowphase when no lane survives, which is the common case
-      bool near = false;
-      if (valid) {
-        double ca[3], cb[3], dc[3];
-        for (int a = 0; a < 3; a++) { ca[a] = 0.5 * (L.rcapw[i][a] + L.rcapw[i][3 + a]); cb[a] = 0.5 * (a1[a] + a2[a]); }
-        v3sub(dc, ca, cb);
-        // half lengths are model constants (rigid capsules); 1e-9 m of slack covers the rounding of the world-frame end points
-        const double reach = dm->rcap_hl[i] + hl2 + m.rcap_r[i] + r2 + margin + 1e-9;
-        near = v3dot(dc, dc) <= reach * reach;
-      }
-      if (__any(near) && valid && near) {
-        double c1[3], c2[3], d[3];
-        const double d2 = seg_seg(&L.rcapw[i][0], &L.rcapw[i][3], a1, a2, c1, c2), dd = fsqrt(d2), dist = dd - m.rcap_r[i] - r2;
-        if (dist < margin) {
-          hit = true;
-          v3sub(d, c2, c1);
-          if (dd > 1e-12) v3scl(c.n, d, 1.0 / dd);
-          v3madd(c.pos, c1, c.n, m.rcap_r[i] + 0.5 * dist);
-          c.g1 = i; c.g2 = g2; c.b1 = m.rcap_body[i]; c.dist = dist;
+        // broadphase: bounding spheres of the two capsules (conservative: a culled pair cannot be a contact); these rounds run only for the human capsules that
+        // the cull box above lets through
+        if (valid) {
+          double ca[3], cb[3], dc[3];
+          for (int a = 0; a < 3; a++) { ca[a] = 0.5 * (L.rcapw[i][a] + L.rcapw[i][3 + a]); cb[a] = 0.5 * (a1[a] + a2[a]); }
+          v3sub(dc, ca, cb);
+          // half lengths are model constants (rigid capsules); 1e-9 m of slack covers the rounding of the world-frame end points
+          const double reach = dm->rcap_hl[i] + hl2 + m.rcap_r[i] + r2 + margin + 1e-9;
+          near = v3dot(dc, dc) <= reach * reach;
         }
       }
+      // the whole wave skips the narrowphase when no lane survives its broadphase, which is the common case
+      if (__any(near) && valid && near) hit = capsule_pair_contact(m, i, a1, a2, r2, margin, g2, c);
     } else if (lane < 4 * HRG_NRCAP) {
       const int pl = lane / (2 * HRG_NRCAP), i = (lane % (2 * HRG_NRCAP)) >> 1, en = lane & 1;
       if (m.rcap_body[i] >= 0) {

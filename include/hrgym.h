@@ -735,6 +735,16 @@ int hrg_debug_model_constants(hrg_batch* b, double* out_host);
  * do without a shield: the HRG_CFK_SCAP block is then 0 and the first two configurations are not read.  0 / -1. */
 enum { HRG_CFK_KR = 0, HRG_CFK_KP = 9 * HRG_NV, HRG_CFK_SCAP = 12 * HRG_NV, HRG_CFK_DIM = HRG_CFK_SCAP + 2 * HRG_NSHIELD_RCAP * 6 };
 int hrg_debug_chain_fk(hrg_batch* b, const double* q_host, int32_t n, int32_t shield_on, double* out_host);
+/* test tap of the robot - robot round of collide (csrc/hrgym_kernels.h) as the batch's kernel variant compiles it: n (1..HRG_SP_MAX) postures q_host[n][HRG_NARM] of
+ * arm joint angles (fingers at 0), one wavefront per posture: the chain walk, the world-frame capsule end points, then candidate pair p (the pairs of rcap_selfmask,
+ * i major, j minor) on lane p -> out_host[n][HRG_SP_DIM]: HRG_SP_CAPS the capsule end points [HRG_NRCAP][6] (p1, p2), HRG_SP_PAIRS one record of HRG_SP_PDIM
+ * doubles per pair slot [HRG_SP_NPAIR]:
+ *   {i, j, near, hit, dist, n 3, pos 3, hit_off, dist_off, n_off 3, pos_off 3}
+ * near: the pair passed the broadphase (segment of the longer capsule against the bounding sphere of the shorter one); hit .. pos: the contact the round reports
+ * (narrowphase behind the broadphase, as in the step); hit_off .. pos_off: the contact the narrowphase reports with the broadphase compiled out.  A contact that is
+ * not reported and the slots past the model's pairs are 0.  0 / error code. */
+enum { HRG_SP_NPAIR = 64, HRG_SP_PDIM = 19, HRG_SP_CAPS = 0, HRG_SP_PAIRS = 6 * HRG_NRCAP, HRG_SP_DIM = HRG_SP_PAIRS + HRG_SP_NPAIR * HRG_SP_PDIM, HRG_SP_MAX = 4096 };
+int hrg_debug_self_pairs(hrg_batch* b, const double* q_host, int32_t n, double* out_host);
 /* test tap of the primitive narrowphase (seg_seg, seg_box, cap_box_two: csrc/hrgym_device.h; box_box2: csrc/hrgym_kernels.h) as the batch's kernel variant compiles
  * the routines: n (1..HRG_NP_MAX) queries of one `kind`, queries_host[n][HRG_NP_QDIM] -> out_host[n][HRG_NP_ODIM], everything the routine returns.  Rotations are
  * unit quaternions (w, x, y, z).
