@@ -218,6 +218,10 @@ struct DevModel {
   double eul_hd[NV], eul_rhd[2];             // mj_Euler's implicit joint damping (euler_robot_tree): h * jnt_damping of every joint; 1 / (h * jnt_damping) of the two
   int32_t eul_fingers, eul_pad;              // fingers, 0 unless both are damped (eul_fingers: the Woodbury term is in)
   double rcap_mid[HRG_NRCAP][3];             // mid point 0.5 (p1 + p2) of each robot collision capsule, body frame (classify: the speed of a robot geom at a human contact)
+  // robot_capsules_world, one 32-byte record per lane 6 c + 3 e + a = coordinate a of end point e of capsule c: v = the end point in the frame of body b = rcap_body[c],
+  // k = 3 b + a (row a of kR[b] starts at double 3 k of kR, kp[b][a] is double k of kp).  A capsule of the base does not move: k = -1 and v[0] is the world
+  // coordinate itself, which hrg_model_constants_kernel writes in the device's arithmetic
+  struct alignas(32) RcapLane { double v[3]; int32_t k, pad; } rcap_lane[6 * HRG_NRCAP];
 };
 
 struct Contact {
@@ -1011,7 +1015,11 @@ DI double lane_value(double v) {
 // a capsule.  A lane computes its own bound alone: max(p1, p2) + rr, or -(min(p1, p2) - rr) = max(-p1, -p2) + rr (a negation is exact, and rounding is symmetric);
 // a lane without a capsule holds -1e300.  A maximum does not depend on the order it is taken in, so the bounds are the doubles of one reduction per bound over the
 // lanes 0..15; only the sign of a bound that is zero may differ (max_f64).
-DI void cull_box(const double* cap, double rr, bool has, int lane, double* lo, double* hi) {
+// ZMIN (collide's plane verdict): row 2 of the second reduction carries -(min(z1, z2) - rz) = max(-z1, -z2) + rz over the capsules with `hasz`, with a radius
+// and a capsule set of its own -> *zmin = the lowest point of those capsules, the double that min over them of (z - rz) gives (a difference rounds
+// symmetrically, and a minimum does not depend on the order it is taken in); 1e300 when no capsule has `hasz`.
+template <bool ZMIN = false>
+DI void cull_box(const double* cap, double rr, bool has, int lane, double* lo, double* hi, double rz = 0, bool hasz = false, double* zmin = nullptr) {
   const int g = lane >> 4;
   const long long flip = (long long)(g & 1) << 63;   // the odd rows reduce the negated coordinates
   double e1 = -1e300, e2 = -1e300;
@@ -1019,7 +1027,12 @@ DI void cull_box(const double* cap, double rr, bool has, int lane, double* lo, d
     const int a = g >> 1;
     const double p1 = __longlong_as_double(__double_as_longlong(cap[a]) ^ flip), p2 = __longlong_as_double(__double_as_longlong(cap[3 + a]) ^ flip);
     e1 = max_f64(p1, p2) + rr;
-    if (g < 2) {
+    if (ZMIN) {
+      const long long flipz = (long long)((g | (g >> 1)) & 1) << 63;   // rows 1 and 2 negate z
+      const double z1 = __longlong_as_double(__double_as_longlong(cap[2]) ^ flipz), z2 = __longlong_as_double(__double_as_longlong(cap[5]) ^ flipz);
+      const double ez = max_f64(z1, z2) + (g < 2 ? rr : rz);
+      if (g < 2 || (g == 2 && hasz)) e2 = ez;
+    } else if (g < 2) {
       const double z1 = __longlong_as_double(__double_as_longlong(cap[2]) ^ flip), z2 = __longlong_as_double(__double_as_longlong(cap[5]) ^ flip);
       e2 = max_f64(z1, z2) + rr;
     }
@@ -1027,6 +1040,7 @@ DI void cull_box(const double* cap, double rr, bool has, int lane, double* lo, d
   e1 = row16_max(e1); e2 = row16_max(e2);
   hi[0] = lane_value<0>(e1); lo[0] = -lane_value<16>(e1); hi[1] = lane_value<32>(e1); lo[1] = -lane_value<48>(e1);
   hi[2] = lane_value<0>(e2); lo[2] = -lane_value<16>(e2);
+  if (ZMIN) *zmin = -lane_value<32>(e2);
 }
 // Inverse of a symmetric positive definite 8x8 matrix across the wave: in-place Gauss-Jordan sweeps, lane (i,j) owns entry (i,j), three shuffles and one reciprocal
 // per pivot -- the cost of a factorisation, but what comes out turns every later solve with the matrix (unconstrained acceleration, the Newton direction while no

@@ -2415,14 +2415,14 @@ DI int fair_begin(int* g_fair, int lane, int progress) {
 // ... and after it: behind a sibling -> higher issue priority, ahead of them -> lower
 DI void fair_apply(int lane, int progress, int v, bool busy) {
   const int me = fair_key() & 7;
-  const bool other = lane < 8 && lane != me && v > 0;
-  int vmin = other ? v : 0x7fffffff, vmax = other ? v : 0;
+  (void)lane;
+  // the eight entries sit in lanes 0..7 and `me` is scalar: eight lane reads, then minimum and maximum on the scalar unit (no LDS-crossbar shuffles)
+  int vmin = 0x7fffffff, vmax = 0;
 #pragma unroll
-  for (int o = 4; o > 0; o >>= 1) {
-    const int a = __shfl_xor(vmin, o, 64), b = __shfl_xor(vmax, o, 64);
-    vmin = a < vmin ? a : vmin; vmax = b > vmax ? b : vmax;
+  for (int k = 0; k < 8; k++) {
+    const int vk = __builtin_amdgcn_readlane(v, k);
+    if (k != me && vk > 0) { vmin = vk < vmin ? vk : vmin; vmax = vk > vmax ? vk : vmax; }
   }
-  vmin = __builtin_amdgcn_readfirstlane(vmin); vmax = __builtin_amdgcn_readfirstlane(vmax);
   const int own = progress + 1;
   int pr;
   if (vmax == 0) pr = 0;                           // no sibling
@@ -3180,15 +3180,21 @@ __global__ __launch_bounds__(64) void hrg_cull_box_kernel(const double* __restri
   if (lane == 0) for (int a = 0; a < 3; a++) { out[a] = lo[a]; out[3 + a] = hi[a]; }
 }
 
-// The model constants of DevModel that are expressions a substep (or cycle) used to evaluate (fric_*, eul_*, rcap_mid): one wave, launched once at batch create when the model is on
+// The model constants of DevModel that are expressions a substep (or cycle) used to evaluate (fric_*, eul_*, rcap_mid, the base capsules of rcap_lane): one wave, launched once at batch create when the model is on
 // the device.  model_constants is those expressions as the step kernels hold them (row_D is the steppers' own), for one lane's share; x0 = the position term of a
 // friction row, 0.  The test tap (hrg_debug_model_constants) runs it again with x0 from a kernel argument, so that impedance() runs as it did in a substep instead of
 // folding, and returns its values next to the stored ones: out[0][HRG_MC_DIM] stored | out[1][HRG_MC_DIM] recomputed.
-struct ModelConstants { double fric_D, fric_lim, fric_imp, eul_hd, eul_rhd, rcap_mid; int eul_fingers; };
+struct ModelConstants { double fric_D, fric_lim, fric_imp, eul_hd, eul_rhd, rcap_mid, rcap_base; int eul_fingers; };
 static_assert(3 * HRG_NRCAP <= 64, "one lane per coordinate of a capsule's mid point");
+static_assert(6 * HRG_NRCAP <= 64, "one lane per coordinate of a capsule's end points");
 DI ModelConstants model_constants(ModelPtr dm, int lane, double x0) {
   const auto& m = dm->m;
-  ModelConstants c = {0, 0, 0, 0, 0, 0, 0};
+  ModelConstants c = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (lane < 6 * HRG_NRCAP) {   // lane 6 c + 3 e + a: world coordinate a of end point e of capsule c on the base frame (robot_capsules_world's expression; read for a capsule of the base)
+    const int cc = lane / 6, e = (lane - 6 * cc) / 3, a = lane - 6 * cc - 3 * e;
+    const auto* v = e ? m.rcap_p2[cc] : m.rcap_p1[cc];
+    c.rcap_base = m.base_pos[a] + chain_dot(dm->Rbase[3 * a], dm->Rbase[3 * a + 1], dm->Rbase[3 * a + 2], v[0], v[1], v[2]);
+  }
   if (lane <= NV) {   // friction-loss row of dof `lane`; lane NV: the nail's slide joint
     const bool nail = lane == NV;
     const int r = nail ? 0 : lane;
@@ -3221,6 +3227,7 @@ __global__ __launch_bounds__(64) void hrg_model_constants_kernel(DevModel* __res
   if (lane < 2) dmw->eul_rhd[lane] = c.eul_rhd;
   if (lane == 0) dmw->eul_fingers = c.eul_fingers;
   if (lane < 3 * HRG_NRCAP) (&dmw->rcap_mid[0][0])[lane] = c.rcap_mid;
+  if (lane < 6 * HRG_NRCAP && dm->m.rcap_body[lane / 6] < 0) dmw->rcap_lane[lane].v[0] = c.rcap_base;
 }
 __global__ __launch_bounds__(64) void hrg_model_constants_tap_kernel(const DevModel* __restrict__ dm_, double x0, double* __restrict__ out) {
   const ModelPtr dm = uniform_model(dm_);

@@ -232,6 +232,8 @@ static int batch_check(const hrg_model_desc* desc, const hrg_clip_table* clips) 
     tot += clips->clip_len[c];
   }
   if (tot != clips->total_frames) return fail(HRG_ERR_INVALID, "clip table total_frames mismatch");
+  for (int c = 0; c < HRG_NRCAP; c++)   // (the kernels index the tree kinematics in LDS with it: DevModel::rcap_lane)
+    if (desc->rcap_body[c] < -1 || desc->rcap_body[c] >= NV) return fail(HRG_ERR_INVALID, "rcap_body: a robot capsule rides on the base (-1) or on a body of the tree");
   if (desc->robot_hulls) {
     if (!g_variants.v[t->family][1].step)   // HRG_VARIANTS has no [family][1] line (today every family has one)
       return fail(HRG_ERR_UNSUPPORTED, "robot_hulls: no hull variant of the step kernel for this task");
@@ -308,6 +310,12 @@ static void batch_fill_model(const hrg_model_desc* desc, const hrg_clip_table* c
         r.r_j = desc->rcap_r[j];
       }
   hm->n_self = ns;
+  for (int l = 0; l < 6 * HRG_NRCAP; l++) {   // robot_capsules_world's lanes (v[0] of a base capsule: hrg_model_constants_kernel)
+    const int c = l / 6, e = (l % 6) / 3, a = l % 3, bd = desc->rcap_body[c];
+    DevModel::RcapLane& r = hm->rcap_lane[l];
+    for (int q = 0; q < 3; q++) r.v[q] = e ? desc->rcap_p2[c][q] : desc->rcap_p1[c][q];
+    r.k = bd < 0 ? -1 : 3 * bd + a;
+  }
   int nc = 0;
   for (int i = 0; i < 8; i++)
     for (int j = i + 1; j < 8; j++)
@@ -344,7 +352,7 @@ static int batch_upload(hrg_batch* b, const hrg_model_desc* desc, const hrg_clip
   hm->hull_dev = b->d_hull;
   hm->mpr_fallback = b->d_mpr_fallback;
   if (!ok || !m.upload(b->d_model, hm, 1)) return nomem("batch", m);
-  hipLaunchKernelGGL(hrg_model_constants_kernel, dim3(1), dim3(64), 0, 0, b->d_model);   // fric_*, eul_*, rcap_mid: in the device's own arithmetic
+  hipLaunchKernelGGL(hrg_model_constants_kernel, dim3(1), dim3(64), 0, 0, b->d_model);   // fric_*, eul_*, rcap_mid, rcap_lane of the base: in the device's own arithmetic
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
   if (b->d_pose) {

@@ -1402,19 +1402,19 @@ DI void collide_hammer(const DevModel* __restrict__ dm_, int lane, int* base_io)
   *base_io = base;
 }
 #endif
-// World-frame end points of the robot's collision capsules (lane c: capsule c) from the tree kinematics in LDS -> L.rcapw.
+// World-frame end points of the robot's collision capsules from the tree kinematics in LDS -> L.rcapw.  Lane 6 c + 3 e + a: coordinate a of end point e of capsule
+// c, kp[b][a] + (row a of kR[b]) . v with the lane's record of the model (DevModel::rcap_lane); the sum in the shape it has always had (chain_dot, then the add).
+// A capsule of the base takes its coordinate from the record.
 DI void robot_capsules_world(ModelPtr dm, int lane) {
   Lds& L = g_L;
-  const auto& m = dm->m;
-  if (lane < HRG_NRCAP) {
-    const int c = lane, b = m.rcap_body[c];
-    double R[9], p[3], t[3];
-    if (b < 0) { for (int a = 0; a < 9; a++) R[a] = dm->Rbase[a]; v3cpy(p, m.base_pos); }
-    else { for (int a = 0; a < 9; a++) R[a] = L.kR[b][a]; v3cpy(p, L.kp[b]); }
-    m3mulv(t, R, m.rcap_p1[c]); v3add(&L.rcapw[c][0], p, t);
-    m3mulv(t, R, m.rcap_p2[c]); v3add(&L.rcapw[c][3], p, t);
-  }   // (the capsule's centre is computed by classify, for the one capsule whose speed it asks for)
-}
+  if (lane < 6 * HRG_NRCAP) {
+    const struct { double v0, v1, v2; int k; } rec = {dm->rcap_lane[lane].v[0], dm->rcap_lane[lane].v[1], dm->rcap_lane[lane].v[2], dm->rcap_lane[lane].k};
+    const int k = rec.k < 0 ? 0 : rec.k;
+    const double* R = &L.kR[0][0] + 3 * k;
+    const double w = (&L.kp[0][0])[k] + chain_dot(R[0], R[1], R[2], rec.v0, rec.v1, rec.v2);
+    (&L.rcapw[0][0])[lane] = rec.k < 0 ? rec.v0 : w;
+  }
+}   // (the capsule's centre is computed by classify, for the one capsule whose speed it asks for)
 // One robot self pair as round 0 of collide reads it: adjacent fields of DevModel::self_rec[k], two 16-byte loads.
 struct SelfPair { int i, j, s, o, body_j; double inv_len2, bound, r_j; };
 DI SelfPair self_pair(ModelPtr dm, int k) {
@@ -1466,13 +1466,15 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
   // robot capsule x listed human capsule only: one round of 64 lanes for up to six of them instead of four rounds over all 240 pairs.  The pairs keep their
   // order (robot capsule major, human capsule minor), so the contact list is the one of the full enumeration.
   int n_hnear;
+  double zmin;   // lowest point of the capsules that move (those of the base stand on the table): min over both end points of p[2] - rcap_r
   {
     static_assert(HRG_NRCAP <= 16 && HRG_NSHIELD_RCAP <= 16, "cull_box: one DPP row of capsules");
     double lo[3], hi[3];
     {
       const bool has = (lane & 15) < HRG_NRCAP;
       const int rc = has ? lane & 15 : 0;
-      cull_box(&L.rcapw[rc][0], m.rcap_r[rc] + m.contact_margin_human + 1e-9, has, lane, lo, hi);
+      const double rz = m.rcap_r[rc];
+      cull_box<true>(&L.rcapw[rc][0], rz + m.contact_margin_human + 1e-9, has, lane, lo, hi, rz, m.rcap_body[rc] >= 0, &zmin);
     }
     double d2 = 0;
     const int hb = lane < HRG_NHB ? lane : 0;
@@ -1492,9 +1494,22 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
   const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
   const int n_hpairs = HRG_NRCAP * n_hnear, n_hrounds = (n_hpairs + 63) >> 6;
   const float inv_hnear = n_hnear ? 1.0f / (float)n_hnear : 0.0f;
+  // The three broadphase verdicts, before any round is set up: a substep in which no self pair passes self_near, no human capsule is listed and the capsules that
+  // move are clear of both planes has no contact of the robot's own, which is nearly every substep -> the rounds are skipped as a whole (base stays 0).  The
+  // plane verdict is exact: the plane round reports an end point only for p[2] - r - z0 < 0, x >= y implies x - y >= 0 in IEEE arithmetic, and zmin is the
+  // smallest p[2] - r of the round's own lanes.  Round 0 takes its lanes' self verdicts from the ballot.
+  uint64_t self_mask;   // lane p: candidate pair p passes the broadphase (segment against bounding sphere, self_near); in the steady state of a reaching arm none does
+  {
+    const bool valid = lane < dm->n_self;
+    self_mask = __ballot(valid && self_near(self_pair(dm, valid ? lane : 0)));
+  }
+  const bool rounds = self_mask != 0 || n_hnear != 0 || !(zmin >= m.table_top_z && zmin >= m.floor_z);
+#if !HRG_HAMMER
+  if (!rounds) COUNT(30, 1);   // substeps that skip the rounds (the hammering kernels count their noslip sweeps in this slot)
+#endif
   // rounds: 0 = robot-robot, 1..n_hrounds = robot-human (the listed capsules), last = planes
 #pragma unroll 1
-  for (int round = 0; round < 2 + n_hrounds; round++) {
+  for (int round = 0; rounds && round < 2 + n_hrounds; round++) {
     bool hit = false;
     Contact c;
     c.g1 = c.g2 = c.b1 = c.b2 = 0; c.dist = 0; v3set(c.n, 0, 0, 1); v3set(c.pos, 0, 0, 0);
@@ -1509,8 +1524,7 @@ PH_COLLIDE void collide(const DevModel* __restrict__ dm_, int lane, int* ncon_ou
         i = sp.i;
         g2 = sp.j; a1 = &L.rcapw[sp.j][0]; a2 = &L.rcapw[sp.j][3]; r2 = sp.r_j;
         c.b2 = sp.body_j;
-        // broadphase: segment against bounding sphere (self_near); in the steady state of a reaching arm no pair survives it
-        near = valid && self_near(sp);
+        near = (self_mask >> lane) & 1;   // (implies valid)
       } else {
         const int q = (round - 1) * 64 + lane;
         valid = q < n_hpairs;
