@@ -461,11 +461,11 @@ def create_training_vec_env(config, evaluation_mode: bool = False, wrapper_class
     rollout = rollout_kwargs_from_config(config)
     # PPO: the rollout buffer lives beside the stepper (env.rollout, env.collect_rollout).  Only where the device path covers the env: another backend, or a
     # wrapper that works on the host path (obs_norm, a dataset, an imitation reward), trains through step() as before
-    if rollout is not None and hasattr(env, "_rollout_refusal") and env._rollout_refusal() is None:
+    if rollout is not None and env.device_refusal("rollout") is None:
         env.attach_rollout(**rollout)
     replay = replay_kwargs_from_config(config)
     # SAC on flat observations: the replay buffer lives beside the stepper (env.replay, env.collect_steps), with the wrappers of the config on; another
     # backend and the mixed batch train through step() as before
-    if replay is not None and hasattr(env, "_replay_refusal") and env._replay_refusal() is None:
+    if replay is not None and env.device_refusal("replay") is None:
         env.attach_replay(**replay)
     return env

@@ -22,6 +22,7 @@ import numpy as np
 from ._cstruct import CONST
 from .animation import synthetic_clips
 from .model import build_model_desc
+from .device_path import DevicePath
 from .tasks import OBS_KEYS, PICK_PLACE_OBS_KEYS, TASKS, Goal, task_row  # noqa: F401  (the two key lists: names other code imports from here)
 
 try:  # pragma: no cover - not installed in the build image
@@ -201,7 +202,8 @@ class _TorchBackend:
                 that stay valid until the next step;  executed_actions() -> the action rows as the kernel left them;  close()
       optional  batch (the device batch: state access, collision checks, the dataset collector);  attach_expert(desc) / expert_actions();
                 attach_dataset(dataset, rsi_prob, state_imitation_reward, seed);  imit / sir (host rows of the last step, None until attached);
-                reset_time (after a dataset reset);  reseed(desc) (for seed(); this backend is rebuilt instead)"""
+                reset_time (after a dataset reset);  reseed(desc) (for seed(); this backend is rebuilt instead)
+    Next to it, what device_path.DevicePath drives: reset_device(), launch_step(rows), reset_time_device(), imitation_rows(); the buffers are that `path`'s."""
 
     def __init__(self, desc=None, clips=None, n_envs=None, env_id0=0, device=0, batch=None):
         import torch
@@ -215,12 +217,7 @@ class _TorchBackend:
         self.obs, self.term_obs, self.reward, self.info, self.done = v["obs"], v["term_obs"], v["reward"], v["info"], v["done"]
         self.imit = None   # host copy of the imitation rows, once an expert with a reward is attached
         self.sir = None    # host copy of the state imitation rows, once a dataset is attached
-        self.her = None    # the hindsight replay buffer (her.HerBuffer), once attached: filled on the device behind every reset / step
-        self._her_agent = False
-        self.rollout = None   # the PPO rollout buffer (rollout.RolloutBuffer), once attached: filled by HipVecEnv.collect_rollout
-        self.replay = None    # the uniform replay buffer (replay.ReplayBuffer), once attached: filled on the device behind every reset / step
-        self._replay_bounds = None   # (low, high) float64 device tensors: the action bounds the agent's rows are brought back to [-1, 1] by
-        self._stepped = False        # the rows on the device are a step's (their time column: the state imitation row's), not a reset's
+        self.path = None   # the env's device path (device_path.DevicePath), once the env is built: called after a reset, before and after a step
 
     def _fetch(self):
         if self.sir is not None:
@@ -243,46 +240,19 @@ class _TorchBackend:
     def expert_actions(self):
         return self.batch.expert_actions().cpu().numpy()
 
-    def attach_her(self, desc, keep_agent_actions=False, info_keys=None):
-        """`keep_agent_actions`: the buffer stores the rows the agent sent (copied before the step rewrites them), not the rows the step left."""
-        from .her import HerBuffer
-        if self.her is not None:
-            self.her.close()
-        self.her = HerBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
-        self._her_agent = bool(keep_agent_actions)
-
-    def attach_rollout(self, desc, info_keys=None):
-        from .rollout import RolloutBuffer
-        if self.rollout is not None:
-            self.rollout.close()
-        self.rollout = RolloutBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
-
-    def attach_replay(self, desc, low, high, info_keys=None):
-        """`low` / `high`: the bounds of the action space; the buffer stores the rows the agent sent (copied before the step rewrites them), brought back to
-        the policy's scale [-1, 1] by them."""
-        from .replay import ReplayBuffer
-        if self.replay is not None:
-            self.replay.close()
-        t = self.torch
-        self.replay = ReplayBuffer(desc, device=self.batch.device.index, info_keys=info_keys)
-        self._replay_bounds = tuple(t.from_numpy(np.asarray(x, np.float64)).to(self.batch.device) for x in (low, high))
-
     def reset_device(self):
-        """The reset and what the attached buffers take from it, without the copy to the host (the device loops start here)."""
+        """The reset, to a dataset state where a dataset is attached, without the copy to the host (the device loops start here)."""
         if self.sir is not None:
             self.batch.dataset_reset()
             cur = self.batch.dataset_cursor()   # (synchronous; a whole-batch reset is not on the step path)
             self.reset_time = (cur[:, 1] / cur[:, 2]).astype(np.float32)   # StateBasedExpertImitationRewardWrapper.reset (107): start step / T
         else:
             self.batch.reset()
-        self._stepped = False
-        if self.her is not None:
-            self.her.observe(self.batch.obs)
-        if self.replay is not None:
-            self.replay_observe()
 
     def reset(self):
         self.reset_device()
+        if self.path is not None:
+            self.path.after_reset(host=True)
         self._fetch()
         return self.obs
 
@@ -294,24 +264,10 @@ class _TorchBackend:
             self.batch.step_imitation(act)
         else:
             self.batch.step(act)
-        self._stepped = True
-
-    def replay_observe(self):
-        """The rows on the device (a reset's or the last step's) become the replay buffer's current rows."""
-        time = None
-        if self.replay.observe_time:
-            time = self.batch.sir[:, CONST["HRG_SIR_TIME_OBS"]].contiguous() if self._stepped else self.reset_time_device()
-        self.replay.observe(self.batch.obs, time=time)
 
     def reset_time_device(self):
         """The time values of the rows the last dataset reset left (the state imitation reward's time column): float32 [n] on the device."""
         return self.torch.from_numpy(np.ascontiguousarray(self.reset_time, np.float32)).to(self.batch.device)
-
-    def replay_add(self, actions):
-        """The last step's transition into the replay buffer; `actions`: float32 [n, act_dim] at the policy's scale.  The imitation rows go along where a
-        reward of that kind is attached: the episode return is the env's own reward, the time columns are the state imitation reward's."""
-        b = self.batch
-        self.replay.add_step(actions, b.obs, b.term_obs, b.reward, b.done, b.info, **self.imitation_rows())
 
     def imitation_rows(self):
         """The last step's imitation rows as the replay buffer and the evaluator take them: dict(sir=...) with a state imitation reward, dict(imit=...) with an
@@ -325,19 +281,13 @@ class _TorchBackend:
 
     def step_async(self, actions):
         self._act = self.torch.from_numpy(np.ascontiguousarray(actions, np.float64)).to(self.batch.device, non_blocking=True)
-        self._her_act = self._act.clone() if self.her is not None and self._her_agent else self._act
-        if self.replay is not None:   # the agent's own rows, before collision prevention or the IK front-end rewrite them, at the policy's scale
-            low, high = self._replay_bounds
-            A = self.replay.act_dim
-            self._replay_act = (2.0 * ((self._act[:, :A] - low) / (high - low)) - 1.0).to(self.torch.float32).contiguous()
+        if self.path is not None:
+            self.path.before_step(self._act)
         self.launch_step(self._act)
 
     def step_wait(self):
-        if self.her is not None:   # on the step's stream, ahead of the host copy: the transition never leaves the device
-            b = self.batch
-            self.her.add_step(self._her_act, b.obs, b.term_obs, b.reward, b.done, b.info)
-        if self.replay is not None:
-            self.replay_add(self._replay_act)
+        if self.path is not None:
+            self.path.after_step()
         self._fetch()
         return self.obs, self.term_obs, self.reward, self.done, self.info
 
@@ -346,12 +296,6 @@ class _TorchBackend:
         return self._act.cpu().numpy()
 
     def close(self):
-        if self.her is not None:
-            self.her.close()
-        if self.rollout is not None:
-            self.rollout.close()
-        if self.replay is not None:
-            self.replay.close()
         self.batch.close()
 
 
@@ -497,12 +441,6 @@ class HipVecEnv(_VecEnvBase):
             backend.attach_expert(self._expert_desc)
         if self._dataset is not None:
             backend.attach_dataset(self._dataset, self._rsi_prob, self._sir_arg, int(self._desc.seed))
-        if getattr(self, "_her_args", None) is not None:   # after seed(): a new, empty buffer
-            backend.attach_her(self._her_desc(n_envs, **self._her_args), keep_agent_actions=self._ik is not None, info_keys=self._info_keys)
-        if getattr(self, "_rollout_args", None) is not None:   # after seed(): a new, empty buffer
-            backend.attach_rollout(self._rollout_desc(n_envs, **self._rollout_args), info_keys=self._info_keys)
-        if getattr(self, "_replay_args", None) is not None:   # after seed(): a new, empty buffer
-            backend.attach_replay(self._replay_desc(n_envs, **self._replay_args), self.action_space.low, self.action_space.high, info_keys=self._info_keys)
         return backend
 
     def _init_spaces(self, n_envs, collision_prevention=None, ik_position_delta=None):
@@ -529,14 +467,7 @@ class HipVecEnv(_VecEnvBase):
         self._t_start = time.time()
         self._actions = None
         self._last_full = None
-        self._rollout_args = None    # arguments of attach_rollout, for the re-attach after seed()
-        self._replay_args = None     # arguments of attach_replay, likewise
-        self.sac = None              # the SAC learner (sac.SacLearner), once attached
-        self.sac_population = None   # the SAC population (sac.SacPopulation), once attached
-        self.ppo = None              # the PPO learner (ppo.PpoLearner), once attached
-        self.ppo_population = None   # the PPO population (ppo.PpoPopulation), once attached
-        self._buffers_behind = False   # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
-        self._device_loop = False    # the name of the device loop (collect_rollout, collect_steps) that has stepped the envs past the host accounting: step_async waits for a reset()
+        self._device_path = DevicePath(self)   # the buffers, learners and loops beside the stepper; survives seed()
 
     def _init_obs_norm(self, obs_norm=None):
         """DatasetObsNormWrapper (wrappers/dataset_wrapper.py:160-300): (obs - mean) / std, optionally tanh(squash_factor * .), applied to the policy's
@@ -577,8 +508,6 @@ class HipVecEnv(_VecEnvBase):
     def reset(self):
         self._ep_ret[:] = 0
         self._ep_len[:] = 0
-        self._device_loop = False
-        self._buffers_behind = False   # (the reset below hands the rows to the attached buffers)
         full = np.asarray(self._backend.reset())
         self._last_full = full
         if self.expert_obs_keys is not None:
@@ -586,8 +515,8 @@ class HipVecEnv(_VecEnvBase):
         return self._view(full, self._backend.reset_time if self._observe_time else None)
 
     def step_async(self, actions):
-        if self._device_loop:
-            raise RuntimeError(f"step_async after {self._device_loop}: the device loop moved the envs on without the host accounting (episode returns, the last "
+        if self._device_path.loop:
+            raise RuntimeError(f"step_async after {self._device_path.loop}: the device loop moved the envs on without the host accounting (episode returns, the last "
                                "observation); call reset() first")
         if self._ik is not None:  # [dx, dy, dz, gripper] in the first four columns of the 7-wide action rows
             a4 = np.asarray(actions, np.float64).reshape(self.num_envs, 4)
@@ -718,18 +647,7 @@ class HipVecEnv(_VecEnvBase):
         if self._monitor is not None:
             self._monitor.close()
             self._monitor = None
-        if self.sac is not None:
-            self.sac.close()
-            self.sac = None
-        if self.sac_population is not None:
-            self.sac_population.close()
-            self.sac_population = None
-        if self.ppo is not None:
-            self.ppo.close()
-            self.ppo = None
-        if self.ppo_population is not None:
-            self.ppo_population.close()
-            self.ppo_population = None
+        self._device_path.close()
         self._backend.close()
 
     def seed(self, seed=None):
@@ -739,9 +657,10 @@ class HipVecEnv(_VecEnvBase):
         self.env_kwargs["seed"] = int(seed)
         self._desc = self._compose_desc()
         if isinstance(self._backend, _TorchBackend):
+            self._device_path.close_buffers()
             self._backend.close()
             self._backend = self._build_backend(self.num_envs)
-            self._device_loop = False
+            self._device_path.rebind()   # (every attached buffer anew, empty)
         else:
             self._backend.reseed(self._desc)
         return [int(seed) + i for i in range(self.num_envs)]
@@ -900,36 +819,24 @@ class HipVecEnv(_VecEnvBase):
         if self._cp is not None and self._ik is not None:
             raise NotImplementedError("attach_her: with collision prevention behind the IK front-end the executed action is a joint action, not one of the policy's "
                                       "Cartesian action space")
-        if not isinstance(self._backend, _TorchBackend):
-            raise NotImplementedError("attach_her: the add and sample kernels run in the HIP library; another backend has none")
-        args = dict(buffer_size=int(buffer_size), n_sampled_goal=int(n_sampled_goal), goal_selection_strategy=goal_selection_strategy,
-                    relabel_observation=bool(relabel_observation), seed=seed)
-        self._backend.attach_her(self._her_desc(self.num_envs, **args), keep_agent_actions=self._ik is not None, info_keys=self._info_keys)
-        self._her_args = args
-        if self._device_loop:   # attached between two runs of the device loop: the new buffer has no current rows, so the envs start again
-            self._restart_device_loop()
-        elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
-            self._backend.her.observe(self._backend.batch.obs)
-        return self._backend.her
+        self._refuse("attach_her", "her")
+        return self._device_path.attach("her", dict(buffer_size=int(buffer_size), n_sampled_goal=int(n_sampled_goal), goal_selection_strategy=goal_selection_strategy,
+                                                    relabel_observation=bool(relabel_observation), seed=seed))
 
-    @property
-    def her(self):
-        """The attached hindsight replay buffer (attach_her), or None."""
-        return getattr(self._backend, "her", None)
+    # the attached buffers (attach_her, attach_rollout, attach_replay) and learners (attach_sac, attach_ppo and their populations), or None: device_path.DevicePath holds them
+    her, rollout, replay = (property(lambda self, k=k: self._device_path.buffers.get(k)) for k in ("her", "rollout", "replay"))
+    sac, sac_population, ppo, ppo_population = (property(lambda self, k=k: self._device_path.learners[k]) for k in ("sac", "sac_population", "ppo", "ppo_population"))
+
+    def device_refusal(self, kind):
+        """Why this env cannot carry a device buffer of `kind` ("her" | "rollout" | "replay": its backend, or what it is wrapped in), or None."""
+        return self._device_path.refusal(kind)
+
+    def _refuse(self, name, kind):
+        why = self.device_refusal(kind)
+        if why is not None:
+            raise NotImplementedError(f"{name}: {why}")
 
     # ---- the on-policy device path: SB3's RolloutBuffer and collect_rollouts next to the stepper (rollout.py, csrc/hrgym_rollout.h) ----
-    def _rollout_refusal(self):
-        """Why this env cannot carry a device rollout buffer, or None."""
-        if not isinstance(self._backend, _TorchBackend):
-            return "the rollout kernels run in the HIP library; another backend has none"
-        if self.goal_env:
-            return "goal_env: dict observations belong to the off-policy path (attach_her)"
-        if self._norm is not None:
-            return "obs_norm: the normalisation runs on the host path"
-        if self._dataset is not None or self._sir is not None or self._imit_alpha is not None:
-            return "a dataset or an imitation reward: their rewards and time column live on the host path"
-        return None
-
     def _rollout_desc(self, n_envs, n_steps, gamma, gae_lambda):
         from .rollout import build_rollout_desc
         return build_rollout_desc(n_envs, n_steps, [int(c) for c in self._cols], act_dim=len(self.action_space.low), gamma=gamma, gae_lambda=gae_lambda)
@@ -938,21 +845,8 @@ class HipVecEnv(_VecEnvBase):
         """A PPO rollout buffer on the device (rollout.RolloutBuffer; the arguments of SB3's RolloutBuffer, training/config/algorithm/ppo.yaml): `n_steps`
         slots per env.  `collect_rollout` fills it; `env.rollout.get(batch_size)` yields minibatches of device tensors.  Attaching again replaces the
         buffer with an empty one (and, between two rollouts of the device loop, resets the envs).  Collision prevention and the IK front-end run in the step kernel and are accepted.  Returns the buffer."""
-        why = self._rollout_refusal()
-        if why is not None:
-            raise NotImplementedError(f"attach_rollout: {why}")
-        args = dict(n_steps=int(n_steps), gamma=float(gamma), gae_lambda=float(gae_lambda))
-        self._backend.attach_rollout(self._rollout_desc(self.num_envs, **args), info_keys=self._info_keys)
-        self._rollout_args = args
-        if self._device_loop:   # attached between two rollouts of the device loop: the new buffer has no current rows, so the envs start again
-            self._backend.batch.reset()
-            self._backend.rollout.observe(self._backend.batch.obs)
-        return self._backend.rollout
-
-    @property
-    def rollout(self):
-        """The attached rollout buffer (attach_rollout), or None."""
-        return getattr(self._backend, "rollout", None)
+        self._refuse("attach_rollout", "rollout")
+        return self._device_path.attach("rollout", dict(n_steps=int(n_steps), gamma=float(gamma), gae_lambda=float(gae_lambda)))
 
     def collect_rollout(self, policy, value_fn):
         """OnPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env into `env.rollout`, then its returns and advantages.
@@ -961,26 +855,7 @@ class HipVecEnv(_VecEnvBase):
         float64 rows the kernel reads, the step, the value of every env's terminal observation (used where the time limit truncated), the slot.  No
         device-to-host copy and no stream synchronisation.  The first call (and the first after reset() or seed()) resets the envs.  Afterwards step_async
         raises until reset(): the host accounting did not see these steps; `env.rollout.episode_stats()` is this path's account of episodes."""
-        rb = self.rollout
-        if rb is None:
-            raise NotImplementedError("collect_rollout: call attach_rollout(n_steps, gamma, gae_lambda) first")
-        self._enter_device_loop("collect_rollout", "env.rollout.episode_stats()")
-        import torch
-        b = self._backend.batch
-        dev, n, A = b.device, self.num_envs, rb.act_dim
-        rb.reset()
-        low, high = torch.from_numpy(self.action_space.low).to(dev), torch.from_numpy(self.action_space.high).to(dev)
-        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
-        for _ in range(rb.n_steps):
-            actions, values, log_probs = policy(rb.observation())
-            rows[:, :A] = torch.clamp(actions, low, high)   # SB3 clips what the env gets, not what the buffer stores
-            if A < CONST["HRG_ACT_DIM"]:
-                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
-            b.step(rows)
-            terminal_values = value_fn(rb.view(b.term_obs))
-            rb.add_step(actions, values, log_probs, terminal_values, b.obs, b.term_obs, b.reward, b.done, b.info)
-        rb.compute_returns_and_advantage(value_fn(rb.observation()))
-        return rb
+        return self._device_path.collect_rollout(policy, value_fn)
 
     def attach_ppo(self, **kwargs):
         """The PPO learner on the device next to the rollout buffer (ppo.PpoLearner; its keywords: net_arch, learning_rate, batch_size, n_epochs, clip_range,
@@ -991,7 +866,7 @@ class HipVecEnv(_VecEnvBase):
         if rb is None:
             raise NotImplementedError("attach_ppo: call attach_rollout(n_steps, gamma, gae_lambda) first (the learner takes its observation and action widths from the buffer)")
         from .ppo import PpoLearner
-        return self._attach_learner("ppo", PpoLearner, rb.obs_dim, rb, rollout_size=rb.n * rb.n_steps, **kwargs)
+        return self._device_path.attach_learner("ppo", PpoLearner, rb.obs_dim, rb, rollout_size=rb.n * rb.n_steps, seed=kwargs.pop("seed", int(self._desc.seed)), **kwargs)
 
     def attach_ppo_population(self, n_members, seeds=None, **kwargs):
         """`n_members` PPO learners stepped in the same launches (ppo.PpoPopulation; PpoLearner's keywords but `seed`), after attach_rollout: the envs are
@@ -1001,15 +876,11 @@ class HipVecEnv(_VecEnvBase):
         that the members do not divide, a batch_size that does not divide m * n_steps.  Returns the population and keeps it as `env.ppo_population`:
         `env.collect_rollout(pop.policy, pop.value)`, then `pop.train(env.rollout)`; `env.evaluate(pop.p.params, n, learner=pop.member(0))` evaluates the
         members side by side."""
-        from .ppo import PpoPopulation, check_seeds, refuse_shared_sequences
+        from .ppo import PpoPopulation, refuse_shared_sequences
         from .rollout import group_rows
-        P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]
-        if "seed" in kwargs:
-            raise TypeError("attach_ppo_population: the members' seeds are `seeds` (one per member), not `seed`")
+        P = self._device_path.members("attach_ppo_population", n_members, seeds, kwargs)
         refuse_shared_sequences(PpoPopulation._shared, kwargs)
-        why = self._rollout_refusal()
-        if why is not None:
-            raise NotImplementedError(f"attach_ppo_population: {why}")
+        self._refuse("attach_ppo_population", "rollout")
         rb = self.rollout
         if rb is None:
             raise NotImplementedError("attach_ppo_population: call attach_rollout(n_steps, gamma, gae_lambda) first (the members take their observation and action "
@@ -1018,52 +889,9 @@ class HipVecEnv(_VecEnvBase):
             rows = group_rows(rb.n, rb.n_steps, P, kwargs.get("batch_size", 64))[1]
         except NotImplementedError as e:
             raise NotImplementedError(f"attach_ppo_population: {e}") from None
-        pop = PpoPopulation(rb.obs_dim, rb.act_dim, P, [int(self._desc.seed) + p for p in range(P)] if seeds is None else seeds, device=rb.device.index,
-                            rollout_size=rows, **kwargs)
-        if self.ppo_population is not None:
-            self.ppo_population.close()
-        self.ppo_population = pop
-        return pop
-
-    def _attach_learner(self, slot, cls, obs_dim, rb, **kwargs):
-        """What attach_ppo and attach_sac end with: the learner of the buffer's action width and device, seeded like the env unless told otherwise, kept as
-        `env.<slot>` in place of the previous one, which is closed."""
-        kwargs.setdefault("seed", int(self._desc.seed))
-        learner = cls(obs_dim, rb.act_dim, device=rb.device.index, **kwargs)
-        if getattr(self, slot) is not None:
-            getattr(self, slot).close()
-        setattr(self, slot, learner)
-        return learner
-
-    def _enter_device_loop(self, name, account, fresh=False):
-        """What collect_rollout, collect_steps and evaluate share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs -- to a
-        dataset state where a dataset is attached -- and hands the rows to the attached buffers; from then on step_async raises until reset().  `fresh`: reset
-        whatever ran before (evaluate).  A loop that follows an evaluation resets too: the evaluation stepped the envs past the attached buffers, whose current
-        rows, running returns and lengths are its reset's."""
-        if self._monitor is not None:
-            raise NotImplementedError(f"{name} with monitor_dir: the Monitor csv is written by the host path; {account} is the device path's account of episodes")
-        if fresh or not self._device_loop or self._buffers_behind:
-            self._restart_device_loop()
-            self._last_full = None   # (the host's copy of the rows is stale from here on)
-        self._device_loop = name
-
-    def _restart_device_loop(self):
-        """The reset a device loop starts from: the envs, and the rows handed to every attached buffer."""
-        be = self._backend
-        be.reset_device()
-        if be.rollout is not None:
-            be.rollout.observe(be.batch.obs)
-        self._buffers_behind = False
+        return self._device_path.attach_learner("ppo_population", PpoPopulation, rb.obs_dim, rb, P, self._device_path.member_seeds(P, seeds), rollout_size=rows, **kwargs)
 
     # ---- the off-policy device path on flat observations: SB3's ReplayBuffer next to the stepper (replay.py, csrc/hrgym_replay.h) ----
-    def _replay_refusal(self):
-        """Why this env cannot carry a device replay buffer, or None."""
-        if not isinstance(self._backend, _TorchBackend):
-            return "the replay kernels run in the HIP library; another backend has none"
-        if self.goal_env:
-            return "goal_env: dict observations and relabelling belong to attach_her"
-        return None
-
     def _replay_desc(self, n_envs, buffer_size, seed):
         from .replay import build_replay_desc
         mean, std, squash = self._norm if self._norm is not None else (None, None, None)
@@ -1076,26 +904,12 @@ class HipVecEnv(_VecEnvBase):
         into it without leaving the device -- as the policy sees them: obs_norm, the time column of a state imitation reward --, `collect_steps` does the same
         without the host; `env.replay.sample(n)` returns device tensors.  The action-based and the state-based imitation reward, a dataset, collision
         prevention and the IK front-end are accepted (the ICRA stack).  Attaching again replaces the buffer with an empty one.  Returns the buffer."""
-        why = self._replay_refusal()
-        if why is not None:
-            raise NotImplementedError(f"attach_replay: {why}")
+        self._refuse("attach_replay", "replay")
         if not handle_timeout_termination:
             raise NotImplementedError("attach_replay(handle_timeout_termination=False): the device buffer never hands a timeout out as a termination")
         if optimize_memory_usage:
             raise NotImplementedError("attach_replay(optimize_memory_usage=True): the device buffer keeps observations and next observations apart")
-        args = dict(buffer_size=int(buffer_size), seed=seed)
-        self._backend.attach_replay(self._replay_desc(self.num_envs, **args), self.action_space.low, self.action_space.high, info_keys=self._info_keys)
-        self._replay_args = args
-        if self._device_loop:   # attached between two runs of a device loop: the new buffer has no current rows, so the envs start again
-            self._restart_device_loop()
-        elif self._last_full is not None:   # attached in mid-run: the next transitions start from the rows the last reset / step left on the device
-            self._backend.replay_observe()
-        return self._backend.replay
-
-    @property
-    def replay(self):
-        """The attached replay buffer (attach_replay), or None."""
-        return getattr(self._backend, "replay", None)
+        return self._device_path.attach("replay", dict(buffer_size=int(buffer_size), seed=seed))
 
     def attach_sac(self, **kwargs):
         """The SAC learner on the device next to its buffer (sac.SacLearner; its keywords: net_arch, learning_rate, gamma, tau, ent_coef, target_entropy,
@@ -1117,7 +931,7 @@ class HipVecEnv(_VecEnvBase):
                 raise NotImplementedError(f"attach_sac: {policy} would see {rb.ag_dim} + {rb.dg_dim} + {rb.obs_dim} = {obs_dim} values (achieved_goal, desired_goal, "
                                           f"observation); the kernels cover {CONST['HRG_OBS_DIM']}: construct the env with obs_keys that select fewer columns")
         from .sac import SacLearner
-        return self._attach_learner("sac", SacLearner, obs_dim, rb, **kwargs)
+        return self._device_path.attach_learner("sac", SacLearner, obs_dim, rb, seed=kwargs.pop("seed", int(self._desc.seed)), **kwargs)
 
     def attach_sac_population(self, n_members, seeds=None, **kwargs):
         """`n_members` SAC learners stepped in the same launches (sac.SacPopulation; SacLearner's keywords but `seed`), after attach_replay: the envs are
@@ -1125,25 +939,17 @@ class HipVecEnv(_VecEnvBase):
         env's seed + p).  learning_rate, gamma, tau, ent_coef and target_entropy take a scalar or one value per member (a sweep); a sequence for a keyword
         the members share (batch_size, net_arch, target_update_interval) is refused.  Refused: a goal env, envs that the members do not divide, the mixed batch.  Returns the population and
         keeps it as `env.sac_population`: `env.collect_steps(pop.act, train_freq)`, then `pop.train(env.replay, gradient_steps)`."""
-        from .sac import SacPopulation, check_seeds
-        P = check_seeds(n_members, range(int(n_members)) if seeds is None else seeds)[0]
-        if "seed" in kwargs:
-            raise TypeError("attach_sac_population: the members' seeds are `seeds` (one per member), not `seed`")
+        from .sac import SacPopulation
+        P = self._device_path.members("attach_sac_population", n_members, seeds, kwargs)
         if self.goal_env:
             raise NotImplementedError("attach_sac_population: goal_env: the hindsight buffer has no grouped sample (populations cover SAC on flat observations)")
         if self.num_envs % P:
             raise NotImplementedError(f"attach_sac_population: num_envs = {self.num_envs} is not divisible by n_members = {P}: every member steps a group of the same size")
-        why = self._replay_refusal()
-        if why is not None:
-            raise NotImplementedError(f"attach_sac_population: {why}")
+        self._refuse("attach_sac_population", "replay")
         rb = self.replay
         if rb is None:
             raise NotImplementedError("attach_sac_population: call attach_replay(buffer_size) first (the members take their observation and action widths from the buffer)")
-        pop = SacPopulation(rb.obs_dim, rb.act_dim, P, [int(self._desc.seed) + p for p in range(P)] if seeds is None else seeds, device=rb.device.index, **kwargs)
-        if self.sac_population is not None:
-            self.sac_population.close()
-        self.sac_population = pop
-        return pop
+        return self._device_path.attach_learner("sac_population", SacPopulation, rb.obs_dim, rb, P, self._device_path.member_seeds(P, seeds), **kwargs)
 
     def collect_steps(self, policy, n_steps):
         """OffPolicyAlgorithm.collect_rollouts on the device: `n_steps` steps of every env (train_freq) into `env.replay`, on a goal env into `env.her`.
@@ -1154,45 +960,7 @@ class HipVecEnv(_VecEnvBase):
         or behind the IK front-end a copy of the agent's rows).  No device-to-host copy and no stream synchronisation.  The first call (and the first after
         reset() or seed()) resets the envs.  Afterwards step_async raises until reset(): the host accounting did not see these steps;
         `env.replay.episode_stats()` / `env.her.episode_stats()` is this path's account of episodes."""
-        if self.her is not None:
-            return self._collect_steps_her(policy, n_steps)
-        rb = self.replay
-        if rb is None:
-            raise NotImplementedError("collect_steps: call attach_replay(buffer_size) first, or attach_her(buffer_size) on a goal env")
-        self._enter_device_loop("collect_steps", "env.replay.episode_stats()")
-        import torch
-        be = self._backend
-        dev, n, A = be.batch.device, self.num_envs, rb.act_dim
-        low, high = be._replay_bounds
-        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
-        for _ in range(int(n_steps)):
-            actions = policy(rb.observation())
-            rows[:, :A] = low + 0.5 * (actions.to(torch.float64) + 1.0) * (high - low)   # SB3's unscale_action
-            if A < CONST["HRG_ACT_DIM"]:
-                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
-            be.launch_step(rows)
-            be.replay_add(actions)
-        return rb
-
-    def _collect_steps_her(self, policy, n_steps):
-        """collect_steps into the hindsight buffer: the tensors step_async / step_wait hand it, without the copy to the host."""
-        hb = self.her
-        self._enter_device_loop("collect_steps", "env.her.episode_stats()")
-        import torch
-        be = self._backend
-        b = be.batch
-        dev, n, A = b.device, self.num_envs, hb.act_dim
-        low, high = (torch.from_numpy(np.asarray(x, np.float64)).to(dev) for x in (self.action_space.low, self.action_space.high))
-        rows = torch.zeros(n, CONST["HRG_ACT_DIM"], dtype=torch.float64, device=dev)
-        for _ in range(int(n_steps)):
-            actions = policy(hb.observation())
-            rows[:, :A] = low + 0.5 * (actions.to(torch.float64) + 1.0) * (high - low)   # SB3's unscale_action
-            if A < CONST["HRG_ACT_DIM"]:
-                rows[:, A:] = 0.0   # behind the IK front-end: [dx, dy, dz, gripper, 0, 0, 0], as step_async sends it (the step rewrites the row)
-            sent = rows.clone() if be._her_agent else rows   # (as step_async keeps them)
-            be.launch_step(rows)
-            hb.add_step(sent, b.obs, b.term_obs, b.reward, b.done, b.info)
-        return hb
+        return self._device_path.collect_steps(policy, n_steps)
 
     # ---- evaluation on the device: SB3's evaluate_policy next to the stepper (evaluation.py, csrc/hrgym_eval.h) ----
     def _eval_desc(self, n_envs, n_policies, n_eval_episodes):
@@ -1236,28 +1004,7 @@ class HipVecEnv(_VecEnvBase):
         sync_every = int(sync_every)
         if sync_every < 1:
             raise ValueError(f"evaluate: sync_every = {sync_every} must be positive")
-        from .evaluation import Evaluator
-        desc = self._eval_desc(self.num_envs, 1 if params is None else int(params.shape[0]), n_eval_episodes)
-        self._enter_device_loop("evaluate", "the EvalResult it returns", fresh=True)   # evaluate_policy starts from env.reset()
-        self._buffers_behind = True
-        be = self._backend
-        b = be.batch
-        ev = Evaluator(desc, device=b.device.index, info_keys=self._info_keys)
-        try:
-            ev.begin(b.obs, be.reset_time_device() if self._observe_time else None)
-            bound, missing = ev.max_quota * self.horizon + sync_every, -1
-            for step in range(1, bound + 1):
-                be.launch_step(ev.policy(learner, params))
-                ev.step(b.obs, b.reward, b.done, b.info, **be.imitation_rows())
-                if step % sync_every == 0 or step == bound:
-                    missing = ev.remaining()
-                    if missing == 0:
-                        break
-            if missing:
-                raise RuntimeError(f"evaluate: {missing} episodes missing after {bound} steps (horizon {self.horizon}): an episode outlived the time limit")
-            return ev.result()
-        finally:
-            ev.close()
+        return self._device_path.evaluate(learner, params, n_eval_episodes, sync_every)
 
     def env_method(self, method_name, *method_args, indices=None, **method_kwargs):
         if method_name == "check_collision_action":   # per-env call of the reference: env_method("check_collision_action", action, indices=[i])

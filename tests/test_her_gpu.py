@@ -342,7 +342,7 @@ def test_the_buffer_behind_reset_and_step_holds_what_the_host_received(oracle_li
     for k in range(30):
         act = rng.uniform(-1, 1, (4, 7))
         obs, rew, done, infos = env.step(act)
-        plain.add_step(back._her_act, back.batch.obs, back.batch.term_obs, back.batch.reward, back.batch.done, back.batch.info)
+        plain.add_step(back._act, back.batch.obs, back.batch.term_obs, back.batch.reward, back.batch.done, back.batch.info)
         post = {key: np.stack([infos[i]["terminal_observation"][key] if done[i] else obs[key][i] for i in range(4)]) for key in obs}
         tape.append(dict(pre=prev, post=post, reward=rew, done=done, trunc=np.array([bool(i.get("TimeLimit.truncated", False)) for i in infos]),
                          action=np.stack([i["action"] for i in infos]), ctype=np.array([i["collision_type"] for i in infos])))

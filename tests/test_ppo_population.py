@@ -88,17 +88,17 @@ def test_attach_refusals_by_name():
     with pytest.raises(NotImplementedError, match="attach_ppo_population: the rollout kernels run in the HIP library"):   # another backend
         env.attach_ppo_population(3)
     # an env that could carry a buffer and has none: the oracle env with its backend's refusal lifted (the device is not reached: the buffer is looked at first)
-    env._rollout_refusal = lambda: None
+    env.device_refusal = lambda kind: None
     with pytest.raises(NotImplementedError, match=r"attach_ppo_population: call attach_rollout\(n_steps, gamma, gae_lambda\) first"):
         env.attach_ppo_population(3)
     # ... and with a buffer's sizes in its place: the groups and the minibatches are checked before a learner is made
-    env._backend.rollout = NS(n=3, n_steps=8, obs_dim=6, act_dim=7, device=torch.device("cpu"), close=lambda: None)
+    env._device_path.buffers["rollout"] = NS(n=3, n_steps=8, obs_dim=6, act_dim=7, device=torch.device("cpu"), close=lambda: None)
     with pytest.raises(NotImplementedError, match="attach_ppo_population: n_envs = 3 is not divisible by n_groups = 2"):
         env.attach_ppo_population(2)
     with pytest.raises(NotImplementedError, match=r"attach_ppo_population: batch_size = 32 does not divide m \* n_steps = 8"):
         env.attach_ppo_population(3, batch_size=32)
     assert env.ppo_population is None
-    env._backend.rollout = None
+    del env._device_path.buffers["rollout"]
     env.close()
     mixed = hrg.MixedHipVecEnv(NS(step_async=None, env_ids=["ReachHuman", "PickPlaceHumanCart"], slices=[slice(0, 2), slice(2, 4)]))
     with pytest.raises(NotImplementedError, match="attach_ppo_population: the mixed batch"):
