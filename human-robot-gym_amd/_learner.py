@@ -137,10 +137,10 @@ def load_checkpoint(path, kind):
     return out
 
 
-def restore_tensors(p, ckpt):
-    """Copies the checkpoint's tensors into the LearnerParams `p`; ValueError, naming the field, where a shape differs."""
+def restore_tensors(p, ckpt, names=TENSORS):
+    """Copies the checkpoint's tensors (`names`: which of them) into the LearnerParams `p`; ValueError, naming the field, where a shape differs."""
     import torch
-    for name in TENSORS:
+    for name in names:
         if not hasattr(p, name):
             continue
         own = getattr(p, name)
@@ -457,6 +457,12 @@ class Learner(DeviceHandle):
             learner.close()
             raise
         return learner
+
+    def load_parameters(self, path):
+        """The parameters of a checkpoint `save` wrote -- the tensors behind `state_dict()`: `params` and, where the learner keeps one, `target` -- into this
+        learner, whose Adam moments, counters and scheduled attributes stay as they are: a run that starts from pre-trained weights (bc.BehaviourCloning)
+        with a fresh optimiser.  ValueError, naming the field, for a file of another learner or of other shapes."""
+        restore_tensors(self.p, load_checkpoint(path, self._prefix), names=("params", "target"))
 
     def state_dict(self):
         """Views of the parameters under SB3's names, torch's [out, in] weight layout (the names: `p`'s class)."""

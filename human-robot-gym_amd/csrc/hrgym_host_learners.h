@@ -551,6 +551,22 @@ int hrg_eval_step(hrg_eval* h, const float* obs_dev, const float* reward_dev, co
   return HRG_OK;
 }
 
+// the actor of a learner by the offsets of its handle, as the evaluator's and the behaviour cloning's kernels take it (csrc/hrgym_eval.h: EvalActor)
+static EvalActor sac_actor(const SacDev& s) {
+  EvalActor a;
+  for (int l = 0; l < HRG_SAC_MAX_DEPTH; l++) { a.w[l] = s.a_w[l]; a.b[l] = s.a_b[l]; }
+  a.hw = s.a_hw; a.hb = s.a_hb; a.nout = 2 * s.A;   // (sac_squash reads both heads)
+  a.depth = s.depth; a.K = s.K; a.A = s.A; a.n_params = s.n_params;
+  return a;
+}
+static EvalActor ppo_actor(const PpoDev& p) {
+  EvalActor a;
+  for (int l = 0; l < HRG_PPO_MAX_DEPTH; l++) { a.w[l] = p.w[0][l]; a.b[l] = p.b[0][l]; }   // network 0: the shared trunk, or the policy's
+  a.hw = p.hw; a.hb = p.hb; a.nout = p.A;   // the first A rows of the [A + 1][64] heads: action_net
+  a.depth = p.depth; a.K = p.K; a.A = p.A; a.n_params = p.n_params;
+  return a;
+}
+
 // what both policy entries end with: the widths of the learner against the evaluator's, then the launch
 static int eval_policy(hrg_eval* h, bool sac, const EvalActor& a, int learner_device, const char* name, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
   if (!params_dev || !view_dev || !actions_dev) return fail(HRG_ERR_INVALID, "null argument");
@@ -570,22 +586,12 @@ static int eval_policy(hrg_eval* h, bool sac, const EvalActor& a, int learner_de
 
 int hrg_eval_policy_sac(hrg_eval* h, hrg_sac* sac, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
   if (!h || !sac) return fail(HRG_ERR_INVALID, "null argument");
-  const SacDev& s = sac->d;
-  EvalActor a;
-  for (int l = 0; l < HRG_SAC_MAX_DEPTH; l++) { a.w[l] = s.a_w[l]; a.b[l] = s.a_b[l]; }
-  a.hw = s.a_hw; a.hb = s.a_hb; a.nout = 2 * s.A;   // (sac_squash reads both heads)
-  a.depth = s.depth; a.K = s.K; a.A = s.A; a.n_params = s.n_params;
-  return eval_policy(h, true, a, sac->device, "sac", params_dev, view_dev, actions_dev, stream);
+  return eval_policy(h, true, sac_actor(sac->d), sac->device, "sac", params_dev, view_dev, actions_dev, stream);
 }
 
 int hrg_eval_policy_ppo(hrg_eval* h, hrg_ppo* ppo, const float* params_dev, const float* view_dev, double* actions_dev, void* stream) {
   if (!h || !ppo) return fail(HRG_ERR_INVALID, "null argument");
-  const PpoDev& p = ppo->d;
-  EvalActor a;
-  for (int l = 0; l < HRG_PPO_MAX_DEPTH; l++) { a.w[l] = p.w[0][l]; a.b[l] = p.b[0][l]; }   // network 0: the shared trunk, or the policy's
-  a.hw = p.hw; a.hb = p.hb; a.nout = p.A;   // the first A rows of the [A + 1][64] heads: action_net
-  a.depth = p.depth; a.K = p.K; a.A = p.A; a.n_params = p.n_params;
-  return eval_policy(h, false, a, ppo->device, "ppo", params_dev, view_dev, actions_dev, stream);
+  return eval_policy(h, false, ppo_actor(ppo->d), ppo->device, "ppo", params_dev, view_dev, actions_dev, stream);
 }
 
 int hrg_eval_remaining(hrg_eval* h, int64_t* remaining_host, void* stream) {
@@ -617,6 +623,98 @@ int hrg_eval_size(hrg_eval* h, int64_t* size_host) {
   size_host[1] = h->steps;
   size_host[2] = h->d.width;
   size_host[3] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+// ---- behaviour cloning (csrc/hrgym_bc.h) ----
+struct hrg_bc {
+  int device = 0;
+  hrg_bc_desc desc;
+  BcDev d;
+  uint64_t steps = 0;   // bc steps so far: Adam's step count and the key of the step's draws
+  DeviceMem mem;        // behind every pointer of `d`
+};
+
+// what both create entries end with: `a` the learner's actor (sac_actor / ppo_actor), the learner's device and members
+static int bc_create(const hrg_bc_desc* desc, int32_t kind, EvalActor a, int learner_device, int32_t n_members, int32_t device, hrg_bc** out) {
+  if (desc->kind != kind)
+    return fail(HRG_ERR_INVALID, "bc: kind = " + std::to_string(desc->kind) + ": this entry creates from " + (kind == HRG_BC_SAC ? "an hrg_sac (HRG_BC_SAC)" : "an hrg_ppo (HRG_BC_PPO)"));
+  if (n_members != 1) return fail(HRG_ERR_UNSUPPORTED, "bc: a population of " + std::to_string(n_members) + " members: behaviour cloning covers lone learners");
+  if (device != learner_device)
+    return fail(HRG_ERR_INVALID, "bc: the learner lives on device " + std::to_string(learner_device) + ", not on device " + std::to_string(device));
+  if (int rc = learner_shape("bc", HRG_SAC_HIDDEN, a.depth, a.K, a.A, desc->batch_size, HRG_BC_MAX_BATCH)) return rc;
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_bc> h(new hrg_bc());
+  h->device = device;
+  h->desc = *desc;
+  BcDev& d = h->d;
+  a.nout = a.A;   // the mean head alone: the first A rows of the learner's head product
+  d.a = a;
+  d.sac = kind == HRG_BC_SAC ? 1 : 0;
+  d.B = desc->batch_size; d.tiles = desc->batch_size / HRG_SAC_TILE; d.seed = desc->seed;
+  d.lo[0] = a.w[0]; d.n[0] = a.b[a.depth - 1] + MLP_H - a.w[0];   // a network's layers lie one behind the other: W_0, b_0, W_1, ..
+  d.lo[1] = a.hw; d.n[1] = a.A * MLP_H;
+  d.lo[2] = a.hb; d.n[2] = a.A;
+  d.n_reach = d.n[0] + d.n[1] + d.n[2];
+  const size_t P = (size_t)a.n_params, B = (size_t)d.B;
+  Carver<float> f;
+  f.take(d.pred, B * (size_t)a.A);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.loss_part, (size_t)d.tiles);
+  f.take(d.loss, 1);
+  if (!f.alloc(h->mem) || !h->mem.zeros(d.index, B)) return nomem("bc", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
+  return HRG_OK;
+}
+
+int hrg_bc_create_sac(const hrg_bc_desc* desc, hrg_sac* learner, int32_t device, hrg_bc** out) {
+  if (!desc || !learner || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  return bc_create(desc, HRG_BC_SAC, sac_actor(learner->d), learner->device, learner->n_members, device, out);
+}
+
+int hrg_bc_create_ppo(const hrg_bc_desc* desc, hrg_ppo* learner, int32_t device, hrg_bc** out) {
+  if (!desc || !learner || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  return bc_create(desc, HRG_BC_PPO, ppo_actor(learner->d), learner->device, learner->n_members, device, out);
+}
+
+void hrg_bc_destroy(hrg_bc* h) { destroy_handle(h); }
+
+int hrg_bc_sizes(hrg_bc* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_reach;
+  size_host[1] = (int64_t)h->steps;
+  size_host[2] = h->d.a.n_params;
+  size_host[3] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+int hrg_bc_step(hrg_bc* h, const float* table_obs_dev, const float* table_act_dev, int64_t n_rows, const int64_t* index_in_dev, float* params_dev, float* bc_m_dev,
+                float* bc_v_dev, double learning_rate, void* stream) {
+  if (!h || !params_dev || !bc_m_dev || !bc_v_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!table_obs_dev || !table_act_dev) return fail(HRG_ERR_INVALID, "bc: null table (observations and actions of n_rows rows)");
+  if (n_rows < 1) return fail(HRG_ERR_INVALID, "bc: n_rows = " + std::to_string(n_rows) + " must be positive");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "bc: learning_rate must be finite and not negative");
+  HIPCHK(hipSetDevice(h->device));
+  const BcDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);
+  hipLaunchKernelGGL(hrg_bc_grad_kernel, dim3((unsigned)d.tiles), dim3(MLP_BLOCK), 0, st, d, (const float*)params_dev, table_obs_dev, table_act_dev, n_rows, index_in_dev, h->steps);
+  hipLaunchKernelGGL(hrg_bc_adam_kernel, dim3(((unsigned)d.n_reach + MLP_BLOCK - 1) / MLP_BLOCK), dim3(MLP_BLOCK), 0, st, d, params_dev, bc_m_dev, bc_v_dev, learning_rate, bc1, bc2);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_bc_export(hrg_bc* h, int64_t* index_host, float* pred_host, float* grad_host, float* loss_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  const BcDev& d = h->d;
+  if (int rc = export_floats(h->device, {{pred_host, d.pred, (size_t)d.B * (size_t)d.a.A}, {grad_host, d.grad, (size_t)d.a.n_params}, {loss_host, d.loss, 1}})) return rc;
+  if (index_host) HIPCHK(hipMemcpy(index_host, d.index, (size_t)d.B * sizeof(int64_t), hipMemcpyDeviceToHost));
   return HRG_OK;
 }
 

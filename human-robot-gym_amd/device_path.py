@@ -45,6 +45,9 @@ KINDS = {
     "replay": BufferKind("ReplayBuffer", "replay", "goal_env: dict observations and relabelling belong to attach_her", None, _observe_timed, _policy_scale),
 }
 LEARNERS = ("sac", "sac_population", "ppo", "ppo_population")
+# the table of demonstration rows (bc.DemoTable) is no buffer, but is refused as one is: it is built by an attached buffer's view kernel
+DEMONSTRATIONS = BufferKind(None, "view", "goal_env: the hindsight feature row is another layout (behaviour cloning covers flat observations)", None, None, None)
+TABLE_KINDS = {"sac": "replay", "ppo": "rollout"}   # the buffer whose view a learner's table is built through
 
 
 def widen(rows, A, actions):
@@ -62,6 +65,7 @@ class DevicePath:
         self.buffers = {}    # kind -> the attached buffer
         self.args = {}       # kind -> the arguments it was attached with, for the new, empty buffer after seed()
         self.learners = dict.fromkeys(LEARNERS)   # env.sac, env.sac_population, env.ppo, env.ppo_population
+        self.bc = None       # env.bc: the behaviour cloning of one of the lone learners (bc.BehaviourCloning)
         self.loop = False    # the name of the device loop (collect_rollout, collect_steps, evaluate) that has stepped the envs past the host accounting: step_async waits for a reset()
         self.behind = False  # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self.rebind()
@@ -83,7 +87,7 @@ class DevicePath:
 
     def refusal(self, kind):
         """Why the env cannot carry a device buffer of `kind`, or None."""
-        env, row = self.env, KINDS[kind]
+        env, row = self.env, DEMONSTRATIONS if kind == "demonstrations" else KINDS[kind]
         if not self.on_hip():
             return f"the {row.kernels} kernels run in the HIP library; another backend has none"
         if env.goal_env and row.goal_env is not None:
@@ -155,9 +159,73 @@ class DevicePath:
         """What every attach of a learner or population ends with: one of the buffer's action width and device, kept as `env.<slot>`; the previous one is closed."""
         learner = cls(obs_dim, rb.act_dim, *args, device=rb.device.index, **kwargs)
         if self.learners[slot] is not None:
+            if self.bc is not None and self.bc.learner is self.learners[slot]:
+                self.close_bc()
             self.learners[slot].close()
         self.learners[slot] = learner
         return learner
+
+    def demonstrations(self, dataset, algorithm=None):
+        """bc.DemoTable of `dataset` through the attached buffer's own view: the replay buffer's for SAC, the rollout buffer's for PPO."""
+        from .bc import DemoTable, demonstration_actions, demonstration_rows
+        from .dataset import ExpertDataset
+        env = self.env
+        why = env.device_refusal("demonstrations")
+        if why is not None:
+            raise NotImplementedError(f"demonstrations: {why}")
+        if algorithm is not None and algorithm not in TABLE_KINDS:
+            raise ValueError(f"demonstrations: algorithm = {algorithm!r}: one of {sorted(TABLE_KINDS)}")
+        attached = [a for a, kind in TABLE_KINDS.items() if kind in self.buffers and algorithm in (None, a)]
+        if not attached:
+            need = "attach_replay(buffer_size) (SAC) or attach_rollout(n_steps) (PPO)" if algorithm is None else f"attach_{TABLE_KINDS[algorithm]}"
+            raise NotImplementedError(f"demonstrations: call {need} first: the table holds the attached buffer's view of the rows, what the policy will be shown")
+        if len(attached) > 1:
+            raise ValueError("demonstrations: a replay and a rollout buffer are attached: pass algorithm='sac' or algorithm='ppo'")
+        buf = self.buffers[TABLE_KINDS[attached[0]]]
+        if not isinstance(dataset, ExpertDataset):
+            dataset = ExpertDataset.load(dataset, env_id=env.env_id, has_box=env._task.block == "box")
+        if dataset.env_id != env.env_id:
+            raise ValueError(f"demonstrations: a dataset of {dataset.env_id}, the env steps {env.env_id}")
+        if dataset.cartesian != (env._ik is not None):
+            raise ValueError(f"demonstrations: the dataset's actions are {'Cartesian [dx, dy, dz, gripper]' if dataset.cartesian else 'joint space'} (cartesian = "
+                             f"{dataset.cartesian}), the env's {'are' if env._ik is not None else 'are not'} (ik_position_delta)")
+        if dataset.robot_geometry != env._robot_geometry:
+            raise ValueError(f"demonstrations: the dataset was recorded with robot_geometry = {dataset.robot_geometry!r}, the env collides the arm as "
+                             f"{env._robot_geometry!r}")
+        torch = self.torch
+        rows, time = demonstration_rows(dataset)
+        obs = torch.from_numpy(dataset.obs[rows]).to(buf.device)
+        if attached[0] == "sac":
+            view = buf.view(obs, time=torch.from_numpy(time).to(buf.device) if buf.observe_time else None)
+        else:
+            view = buf.view(obs)
+        space = env.action_space
+        actions = torch.from_numpy(demonstration_actions(dataset, space.low, space.high, scale=attached[0] == "sac")).to(buf.device)
+        if actions.shape[1] != buf.act_dim:
+            raise ValueError(f"demonstrations: actions of {actions.shape[1]} values for a buffer of {buf.act_dim}")
+        return DemoTable(view, actions, attached[0])
+
+    def attach_bc(self, table, seed=None, **kwargs):
+        """bc.BehaviourCloning of the lone learner of the table's kind, kept as `env.bc`; the previous one is closed.  `seed` None: the env's."""
+        from .bc import BehaviourCloning
+        slot = getattr(table, "kind", None)
+        if slot not in TABLE_KINDS:
+            raise ValueError(f"attach_bc: {type(table).__name__} is no table of demonstrations (env.demonstrations(dataset))")
+        learner = self.learners[slot]
+        if learner is None:
+            if self.learners[slot + "_population"] is not None:
+                raise NotImplementedError(f"attach_bc: env.{slot}_population: behaviour cloning covers lone learners, not a population (pre-train one learner and load "
+                                          "its parameters into the members)")
+            raise NotImplementedError(f"attach_bc: call attach_{slot} first: behaviour cloning trains the actor of the attached learner")
+        bc = BehaviourCloning(learner, table, seed=int(self.env._desc.seed) if seed is None else seed, **kwargs)
+        self.close_bc()
+        self.bc = bc
+        return bc
+
+    def close_bc(self):
+        if self.bc is not None:
+            self.bc.close()
+            self.bc = None
 
     def members(self, name, n_members, seeds, kwargs):
         """What both population attaches begin with: the number of members."""
@@ -171,6 +239,7 @@ class DevicePath:
         return [int(self.env._desc.seed) + p for p in range(P)] if seeds is None else seeds
 
     def close(self):
+        self.close_bc()
         for learner in filter(None, self.learners.values()):
             learner.close()
         self.learners = dict.fromkeys(LEARNERS)

@@ -210,7 +210,8 @@ def _mixed_cls():
             raise NotImplementedError("goal-env relabelling is per task; use one HipVecEnv(goal_env=True) per task")
 
         def device_refusal(self, kind):
-            return {"rollout": "the mixed batch steps one HipBatch per task", "replay": "the mixed batch has its observation columns per task"}.get(kind, "goal-env relabelling is per task") + "; use one HipVecEnv per task"
+            return {"rollout": "the mixed batch steps one HipBatch per task", "replay": "the mixed batch has its observation columns per task",
+                    "demonstrations": "a demonstration dataset is per task"}.get(kind, "goal-env relabelling is per task") + "; use one HipVecEnv per task"
 
         def expert_actions(self):
             raise NotImplementedError("scripted experts are per task and action form; use one HipVecEnv(expert=...) per task")

@@ -962,6 +962,27 @@ class HipVecEnv(_VecEnvBase):
         `env.replay.episode_stats()` / `env.her.episode_stats()` is this path's account of episodes."""
         return self._device_path.collect_steps(policy, n_steps)
 
+    # ---- behaviour cloning on the device: pre-training an attached learner's actor from a demonstration dataset (bc.py, csrc/hrgym_bc.h) ----
+    bc = property(lambda self: self._device_path.bc, doc="the attached behaviour cloning (attach_bc), or None")
+
+    def demonstrations(self, dataset, algorithm=None):
+        """The (observation, expert action) pairs of a demonstration dataset as a device table (bc.DemoTable) for `attach_bc`.  `dataset`: a name
+        (datasets/<name>/hrg_dataset.npz), a path or a dataset.ExpertDataset.  Observations: every episode's rows 0 .. T_k - 1 (the terminal row has no
+        action), with a time column the value t / T_k, passed through the attached buffer's own view -- exactly what collect_steps / collect_rollout will show
+        the policy.  Actions: the first act_dim columns, clipped to the action bounds; with the replay buffer attached (SAC) rescaled to [-1, 1] by the bounds,
+        the scale the buffer stores; with the rollout buffer (PPO) left at the env's scale, which PpoLearner.policy emits.  `algorithm` "sac" | "ppo": which of
+        the two, where both buffers are attached.  ValueError for a dataset of another task, of the other action form (cartesian) or of the other arm geometry
+        (robot_geometry); NotImplementedError without an attached buffer, on a goal env and on the mixed batch."""
+        return self._device_path.demonstrations(dataset, algorithm)
+
+    def attach_bc(self, table, batch_size=128, learning_rate=1e-3, seed=None):
+        """Behaviour cloning of the attached lone learner's actor on `table` (env.demonstrations(dataset)): bc.BehaviourCloning, kept as `env.bc`.  Call it
+        after attach_sac / attach_ppo; a population is refused.  `bc.train(n)` runs n steps of two launches each, nothing synchronises; it writes into
+        `learner.p.params` in place -- the actor's hidden layers and mean head only; the learner's optimiser state, counters and every other parameter stay
+        bit for bit -- so that learner.act / learner.policy, evaluate, learner.save and learner.train go on as before.  `seed` (of the index draws): default the
+        env's."""
+        return self._device_path.attach_bc(table, batch_size=batch_size, learning_rate=learning_rate, seed=seed)
+
     # ---- evaluation on the device: SB3's evaluate_policy next to the stepper (evaluation.py, csrc/hrgym_eval.h) ----
     def _eval_desc(self, n_envs, n_policies, n_eval_episodes):
         """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature

@@ -590,6 +590,17 @@ typedef struct hrg_ppo_hyper {
   double max_grad_norm;           /* finite, positive */
 } hrg_ppo_hyper;
 
+/* ------------------------------------------------------------------------- behaviour cloning on the device (POD) */
+#define HRG_BC_MAX_BATCH 256                /* rows of a behaviour-cloning batch: a multiple of HRG_SAC_TILE, HRG_SAC_TILE .. HRG_BC_MAX_BATCH */
+enum { HRG_BC_SAC = 0, HRG_BC_PPO = 1 };   /* hrg_bc_desc.kind: the learner whose actor is trained */
+/* One behaviour-cloning handle: supervised steps on the actor of a lone learner, mean squared error between its deterministic action and a table's action rows.
+ * The shapes and the actor's offsets are the learner's; the learning rate is an argument of hrg_bc_step. */
+typedef struct hrg_bc_desc {
+  int32_t kind;                   /* HRG_BC_SAC (hrg_bc_create_sac: tanh(mu), ReLU units) | HRG_BC_PPO (hrg_bc_create_ppo: mu, tanh units) */
+  int32_t batch_size;             /* a multiple of HRG_SAC_TILE, HRG_SAC_TILE .. HRG_BC_MAX_BATCH */
+  uint64_t seed;                  /* of the index draws */
+} hrg_bc_desc;
+
 /* ------------------------------------------------------------------------- evaluation of deterministic policies on the device (POD) */
 #define HRG_EVAL_MAX_EPISODES_PER_ENV 4096 /* the largest quota of an env: ceil(n_eval_episodes / (n_envs / n_policies)) may not exceed it */
 #define HRG_EVAL_RECORD_DIM (5 + HRG_INFO_DIM) /* doubles per record of hrg_eval_export */
@@ -626,6 +637,7 @@ typedef struct hrg_rollout hrg_rollout; /* opaque */
 typedef struct hrg_replay hrg_replay;   /* opaque */
 typedef struct hrg_sac hrg_sac;         /* opaque */
 typedef struct hrg_ppo hrg_ppo;         /* opaque */
+typedef struct hrg_bc hrg_bc;           /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -1092,6 +1104,30 @@ int hrg_ppo_population_set_hyper(hrg_ppo* h, const hrg_ppo_hyper* rows_host, int
  *   hrg_ppo_restore  minibatch steps so far, forward calls that drew their noise (hrg_ppo_sizes' entries 3 and 4). */
 int hrg_sac_restore(hrg_sac* h, uint64_t steps, uint64_t act_calls);
 int hrg_ppo_restore(hrg_ppo* h, uint64_t steps, uint64_t forward_calls);
+
+/* Behaviour cloning on the device (csrc/hrgym_bc.h): supervised pre-training of a lone learner's actor on a table of (observation, action) rows.
+ * One step is two launches: rows drawn from the table (or supplied), the actor's trunk and mean head forward, the loss mean((a(obs) - action)^2) over rows and
+ * components -- a = tanh(mu) for SAC, mu for PPO --, backward, then torch's Adam (eps 1e-8) on the entries the loss reaches: the actor's hidden layers and mean
+ * head (SAC: actor.latent_pi.*, actor.mu.*; PPO: the shared trunk or mlp_extractor.policy_net.*, action_net.*).  Nothing else of params_dev is written, and the
+ * learner handle is only read at create: its Adam moments, counters and every other parameter stay as they were.  The handle owns its step count (Adam's, and
+ * the key of its draws) and its scratch; the moments bc_m_dev, bc_v_dev are the caller's float [n_params] device arrays in the parameters' layout, zero at the start.
+ *   hrg_bc_create_sac  from a lone hrg_sac on `device`.  Before anything is allocated: HRG_ERR_INVALID for a null argument, a desc->kind other than HRG_BC_SAC, a
+ *                      device other than the learner's; HRG_ERR_UNSUPPORTED for a population and for a batch_size that is not a multiple of HRG_SAC_TILE in
+ *                      HRG_SAC_TILE .. HRG_BC_MAX_BATCH.  (hrg_bc_create_ppo: the same from a lone hrg_ppo and HRG_BC_PPO.)
+ *   hrg_bc_sizes       size_host int64[4] = entries of the parameter vector a step updates, bc steps so far, parameters in all, bytes of device memory held.
+ *   hrg_bc_step        one step, asynchronous on `stream`.  table_obs_dev float [n_rows][obs_dim], table_act_dev float [n_rows][act_dim]; index_in_dev int64
+ *                      [batch_size] (clamped into the table) or NULL: row k of the batch is floor(u n_rows), clamped to n_rows - 1, with u = u01(seed, bc step
+ *                      count, k, 15, 0).  HRG_ERR_INVALID for a null table, parameter or moment array, n_rows < 1, a learning_rate that is not finite or negative.
+ *   hrg_bc_export      synchronous parity hook, the last step's: index_host int64 [batch_size], pred_host float [batch_size][act_dim] (the actor's
+ *                      deterministic actions), grad_host float [n_params] (the parameters' layout; zero where the loss does not reach), loss_host float [1].  Any
+ *                      pointer may be NULL. */
+int hrg_bc_create_sac(const hrg_bc_desc* desc, hrg_sac* learner, int32_t device, hrg_bc** out);
+int hrg_bc_create_ppo(const hrg_bc_desc* desc, hrg_ppo* learner, int32_t device, hrg_bc** out);
+void hrg_bc_destroy(hrg_bc* h);
+int hrg_bc_sizes(hrg_bc* h, int64_t* size_host);
+int hrg_bc_step(hrg_bc* h, const float* table_obs_dev, const float* table_act_dev, int64_t n_rows, const int64_t* index_in_dev, float* params_dev, float* bc_m_dev,
+                float* bc_v_dev, double learning_rate, void* stream);
+int hrg_bc_export(hrg_bc* h, int64_t* index_host, float* pred_host, float* grad_host, float* loss_host);
 
 /* Evaluation on the device (csrc/hrgym_eval.h): SB3 1.5.0's evaluate_policy with deterministic = True as a loop of three launches per env step -- the step entry
  * that fits what is attached, hrg_eval_step, hrg_eval_policy_* -- with no copy to the host between them.  The view float [n_envs][width] and the action rows double

@@ -52,6 +52,8 @@ ap.add_argument("--save-freq", type=int, default=0, help="env steps between chec
 ap.add_argument("--eval-episodes", type=int, default=0, help="evaluate the deterministic policy on a second env after every block (n_test_episodes)")
 ap.add_argument("--eval-n-envs", type=int, default=64)
 ap.add_argument("--eval-seed", type=int, default=None, help="seed of the evaluation env (default: --seed + 1)")
+ap.add_argument("--init-checkpoint", default=None, metavar="PATH", help="start from the parameters of this checkpoint (tools/pretrain_bc.py --out): the state_dict only, "
+                "with fresh optimiser state and counters; a lone learner of the checkpoint's shapes")
 
 
 def members_of(args):
@@ -61,6 +63,8 @@ def members_of(args):
 
 def main(args):
     population = args.seeds is not None or args.sweep is not None
+    if population and args.init_checkpoint is not None:
+        raise NotImplementedError("--init-checkpoint with --seeds / --sweep: the checkpoint is a lone learner's")
     seeds, swept = members_of(args) if population else (None, {})
     env = hrg.HipVecEnv(args.n_envs, env_id=args.env_id, env_kwargs=dict(horizon=args.horizon, seed=args.seed))
     env.attach_replay(args.buffer_size)
@@ -104,6 +108,8 @@ def main(args):
         env.close()
         return
     learner = env.attach_sac(batch_size=args.batch_size, learning_rate=args.learning_rate, ent_coef=args.ent_coef, seed=args.seed)
+    if args.init_checkpoint is not None:
+        learner.load_parameters(args.init_checkpoint)
     gen = torch.Generator(device=learner.device).manual_seed(args.seed)
 
     def uniform(obs):
