@@ -120,6 +120,7 @@ PpoDesc = _STRUCTS["hrg_ppo_desc"]
 SacHyper = _STRUCTS["hrg_sac_hyper"]
 PpoHyper = _STRUCTS["hrg_ppo_hyper"]
 BcDesc = _STRUCTS["hrg_bc_desc"]
+DaggerDesc = _STRUCTS["hrg_dagger_desc"]
 EvalDesc = _STRUCTS["hrg_eval_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 

@@ -125,6 +125,8 @@ class BehaviourCloning(DeviceHandle):
         """One step on `batch_size` rows of the table: drawn by the handle, or `indices` int64 [batch_size] on the device (tests; IndexError for a row outside
         the table, which reads their extremes back)."""
         t, tb, p = self.torch, self.table, self.learner.p
+        if tb.n_rows == 0:   # (a dagger.DaggerTable without pinned rows, before its first step)
+            raise ValueError("behaviour cloning: the table is empty (n_rows = 0): a step draws its rows from the table (env.collect_dagger fills a DaggerTable)")
         pi = None
         if indices is not None:
             pi = self._tensor(indices, t.int64, (self.batch_size,), "indices")

@@ -1,5 +1,5 @@
 // hrgym_host_learners.h -- the learners of the C ABI (include/hrgym.h): SAC (hrg_sac_*), PPO (hrg_ppo_*) and the evaluation of their policies (hrg_eval_*), with what
-// the two learners check and compute alike.  Included by the base unit only, behind hrgym_host.h and hrgym_host_buffers.h (the evaluator reads rows through a buffer's view).
+// the two learners check and compute alike; behind them behaviour cloning of their actors (hrg_bc_*) and the DAgger step that fills its table (hrg_dagger_*).  Included by the base unit only, behind hrgym_host.h and hrgym_host_buffers.h (the evaluator reads rows through a buffer's view).
 
 // What both learners check of their networks and batch (csrc/hrgym_mlp.h).  `name`: the learner's message prefix; max_batch: its largest batch.
 static int learner_shape(const char* name, int32_t hidden, int32_t depth, int32_t obs_dim, int32_t act_dim, int32_t batch_size, int32_t max_batch) {
@@ -716,6 +716,74 @@ int hrg_bc_export(hrg_bc* h, int64_t* index_host, float* pred_host, float* grad_
   if (int rc = export_floats(h->device, {{pred_host, d.pred, (size_t)d.B * (size_t)d.a.A}, {grad_host, d.grad, (size_t)d.a.n_params}, {loss_host, d.loss, 1}})) return rc;
   if (index_host) HIPCHK(hipMemcpy(index_host, d.index, (size_t)d.B * sizeof(int64_t), hipMemcpyDeviceToHost));
   return HRG_OK;
+}
+
+// ---- DAgger (csrc/hrgym_dagger.h) ----
+struct hrg_dagger {
+  int device = 0;
+  hrg_dagger_desc desc;
+  DaggerDev d;
+  uint64_t calls = 0;   // steps so far: the key of the next step's draws
+  int32_t slot = 0;     // the next step slot (the write position lives on the host)
+  DeviceMem mem;        // behind every pointer of `d`
+};
+
+int hrg_dagger_create(const hrg_dagger_desc* desc, int32_t device, hrg_dagger** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (desc->kind != HRG_BC_SAC && desc->kind != HRG_BC_PPO) return fail(HRG_ERR_INVALID, "dagger: kind = " + std::to_string(desc->kind) + ": HRG_BC_SAC or HRG_BC_PPO");
+  if (desc->n_envs < 1) return fail(HRG_ERR_INVALID, "dagger: n_envs = " + std::to_string(desc->n_envs) + " must be positive");
+  if (desc->obs_dim < 1 || desc->obs_dim > HRG_OBS_DIM) return fail(HRG_ERR_UNSUPPORTED, "dagger: obs_dim = " + std::to_string(desc->obs_dim) + " outside 1 .. HRG_OBS_DIM");
+  if (desc->act_dim < 1 || desc->act_dim > HRG_ACT_DIM) return fail(HRG_ERR_UNSUPPORTED, "dagger: act_dim = " + std::to_string(desc->act_dim) + " outside 1 .. HRG_ACT_DIM");
+  if (desc->capacity_steps < 1) return fail(HRG_ERR_INVALID, "dagger: capacity_steps = " + std::to_string(desc->capacity_steps) + " must be positive");
+  if (desc->pinned_rows < 0) return fail(HRG_ERR_INVALID, "dagger: pinned_rows = " + std::to_string(desc->pinned_rows) + " must not be negative");
+  for (int j = 0; j < desc->act_dim; j++)
+    if (!std::isfinite(desc->act_low[j]) || !std::isfinite(desc->act_high[j]) || desc->act_high[j] <= desc->act_low[j])
+      return fail(HRG_ERR_INVALID, "dagger: action bound " + std::to_string(j) + ": act_low and act_high must be finite with act_high > act_low");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_dagger> h(new hrg_dagger());
+  h->device = device;
+  h->desc = *desc;
+  DaggerDev& d = h->d;
+  d.sac = desc->kind == HRG_BC_SAC ? 1 : 0;
+  d.n = desc->n_envs; d.K = desc->obs_dim; d.A = desc->act_dim; d.pinned = desc->pinned_rows;
+  d.env_id0 = desc->env_id0; d.seed = desc->seed;
+  if (!h->mem.upload(d.low, desc->act_low, HRG_ACT_DIM) || !h->mem.upload(d.high, desc->act_high, HRG_ACT_DIM) ||
+      !h->mem.zeros(d.stats, (size_t)d.n * HRG_DAGGER_STATS_DIM))
+    return nomem("dagger", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_dagger_destroy(hrg_dagger* h) { destroy_handle(h); }
+
+int hrg_dagger_sizes(hrg_dagger* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = (int64_t)h->calls;
+  size_host[1] = h->slot;
+  size_host[2] = (int64_t)h->desc.pinned_rows + (int64_t)std::min<uint64_t>(h->calls, (uint64_t)h->desc.capacity_steps) * (int64_t)h->desc.n_envs;
+  size_host[3] = (int64_t)h->mem.bytes;
+  return HRG_OK;
+}
+
+int hrg_dagger_step(hrg_dagger* h, const float* view_dev, const float* learner_act_dev, const double* expert_act_dev, double beta, float* table_obs_dev,
+                    float* table_act_dev, double* rows_out_dev, float* kept_out_dev, void* stream) {
+  if (!h || !view_dev || !learner_act_dev || !expert_act_dev || !rows_out_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!table_obs_dev || !table_act_dev) return fail(HRG_ERR_INVALID, "dagger: null table (observations and actions of pinned_rows + capacity_steps * n_envs rows)");
+  if (!(beta >= 0.0 && beta <= 1.0)) return fail(HRG_ERR_INVALID, "dagger: beta = " + std::to_string(beta) + " outside [0, 1]");
+  HIPCHK(hipSetDevice(h->device));
+  const int rc = launch_per_wave(hrg_dagger_step_kernel, h->desc.n_envs, stream, h->d, view_dev, learner_act_dev, expert_act_dev, beta, h->calls, (int64_t)h->slot, table_obs_dev,
+                                 table_act_dev, rows_out_dev, kept_out_dev);
+  if (rc) return rc;
+  h->calls++;
+  if (++h->slot == h->desc.capacity_steps) h->slot = 0;   // the oldest step is overwritten
+  return HRG_OK;
+}
+
+int hrg_dagger_stats(hrg_dagger* h, double* per_env_host, int32_t clear) {
+  if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
+  return buffer_stats(h->device, h->d.stats, h->desc.n_envs, HRG_DAGGER_STATS_DIM, per_env_host, clear);
 }
 
 } // extern "C"

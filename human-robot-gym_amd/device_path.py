@@ -1,5 +1,5 @@
 """The device training path of `HipVecEnv`: the buffers beside the stepper (her.HerBuffer, rollout.RolloutBuffer, replay.ReplayBuffer), the learners and
-populations next to them, and the loops that step the envs without the host (`collect_rollout`, `collect_steps`, `evaluate`).  `DevicePath` owns all of its
+populations next to them, and the loops that step the envs without the host (`collect_rollout`, `collect_steps`, `collect_dagger`, `evaluate`).  `DevicePath` owns all of its
 mutable state; `HipVecEnv` keeps the public methods and their docstrings and calls in here, and on the host path the HIP backend does at three points:
 `after_reset`, `before_step`, `after_step`.  Nothing in here allocates pinned memory, calls torch.cuda or opens the library: with a recording batch and CPU
 tensors behind the backend the whole lifecycle runs without a GPU (tests/test_device_path.py)."""
@@ -48,6 +48,9 @@ LEARNERS = ("sac", "sac_population", "ppo", "ppo_population")
 # the table of demonstration rows (bc.DemoTable) is no buffer, but is refused as one is: it is built by an attached buffer's view kernel
 DEMONSTRATIONS = BufferKind(None, "view", "goal_env: the hindsight feature row is another layout (behaviour cloning covers flat observations)", None, None, None)
 TABLE_KINDS = {"sac": "replay", "ppo": "rollout"}   # the buffer whose view a learner's table is built through
+# the DAgger step (dagger.Dagger) is refused as a buffer is too: it labels the rows of an attached buffer's view with the batch's scripted expert
+DAGGER = BufferKind(None, "dagger", "goal_env: the scripted experts read flat observations, and the hindsight feature row is another layout (DAgger covers flat "
+                    "observations)", None, None, None)
 
 
 def widen(rows, A, actions):
@@ -66,7 +69,9 @@ class DevicePath:
         self.args = {}       # kind -> the arguments it was attached with, for the new, empty buffer after seed()
         self.learners = dict.fromkeys(LEARNERS)   # env.sac, env.sac_population, env.ppo, env.ppo_population
         self.bc = None       # env.bc: the behaviour cloning of one of the lone learners (bc.BehaviourCloning)
-        self.loop = False    # the name of the device loop (collect_rollout, collect_steps, evaluate) that has stepped the envs past the host accounting: step_async waits for a reset()
+        self.dagger = None   # env.dagger: the DAgger step and its table (dagger.Dagger)
+        self.dagger_args = None   # the arguments it was attached with, for the new, empty one after seed()
+        self.loop = False    # the name of the device loop (collect_rollout, collect_steps, collect_dagger, evaluate) that has stepped the envs past the host accounting: step_async waits for a reset()
         self.behind = False  # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self.rebind()
 
@@ -84,10 +89,12 @@ class DevicePath:
         self.stepped = False   # the rows on the device are a step's (their time column: the state imitation row's), not a reset's
         for kind, args in self.args.items():
             self._create(kind, args)
+        if self.dagger_args is not None:
+            self._create_dagger(**self.dagger_args)
 
     def refusal(self, kind):
         """Why the env cannot carry a device buffer of `kind`, or None."""
-        env, row = self.env, DEMONSTRATIONS if kind == "demonstrations" else KINDS[kind]
+        env, row = self.env, {"demonstrations": DEMONSTRATIONS, "dagger": DAGGER}.get(kind) or KINDS[kind]
         if not self.on_hip():
             return f"the {row.kernels} kernels run in the HIP library; another backend has none"
         if env.goal_env and row.goal_env is not None:
@@ -227,6 +234,53 @@ class DevicePath:
             self.bc.close()
             self.bc = None
 
+    def dagger_kind(self, name):
+        """The kind ("sac" | "ppo") of the lone learner a DAgger step serves, with the buffer its view comes from attached; the refusals of `name`."""
+        env = self.env
+        why = env.device_refusal("dagger")
+        if why is not None:
+            raise NotImplementedError(f"{name}: {why}")
+        if env._expert_desc is None:
+            raise NotImplementedError(f"{name}: no expert: construct the env with expert=dict(id=..., ...); the labels are the scripted expert's actions")
+        if env._imit_alpha is not None:
+            raise NotImplementedError(f"{name}: imitation_reward: the step's own expert call would advance the expert's noise a second time, so the label and the "
+                                      "reward would see different expert actions (construct the env with the expert alone)")
+        populations = [slot for slot in LEARNERS if slot.endswith("_population") and self.learners[slot] is not None]
+        if populations:
+            raise NotImplementedError(f"{name}: env.{populations[0]}: DAgger covers lone learners, not a population (train one learner and load its parameters into "
+                                      "the members)")
+        lone = [slot for slot in TABLE_KINDS if self.learners[slot] is not None]
+        if len(lone) != 1:
+            raise NotImplementedError(f"{name}: {'no learner is' if not lone else 'a sac and a ppo learner are'} attached: DAgger serves one lone learner; call "
+                                      "attach_sac (after attach_replay) or attach_ppo (after attach_rollout)")
+        if TABLE_KINDS[lone[0]] not in self.buffers:
+            raise NotImplementedError(f"{name}: call attach_{TABLE_KINDS[lone[0]]} first: the table holds the attached buffer's view of the rows, what the learner is shown")
+        return lone[0]
+
+    def _create_dagger(self, capacity, beta, table, seed):
+        from .dagger import Dagger
+        env, kind = self.env, self.dagger_kind("attach_dagger")
+        buf, space = self.buffers[TABLE_KINDS[kind]], env.action_space
+        new = Dagger(kind, env.num_envs, buf.obs_dim, buf.act_dim, max(int(capacity) // env.num_envs, 1), space.low, space.high, beta=beta, pinned=table,
+                     seed=int(env._desc.seed) if seed is None else seed, env_id0=env._env_id0, device=buf.device.index)
+        old = self.dagger
+        self.close_dagger()
+        if self.bc is not None and old is not None and self.bc.table is old.table:
+            self.bc.table = new.table   # (the cloning goes on, on the new, empty table)
+        self.dagger, self.dagger_args = new, dict(capacity=capacity, beta=beta, table=table, seed=seed)
+        return new
+
+    def attach_dagger(self, capacity, beta, table, seed):
+        """dagger.Dagger for the attached lone learner, kept as `env.dagger`; the previous one is closed."""
+        if table is not None and getattr(table, "kind", None) not in TABLE_KINDS:
+            raise ValueError(f"attach_dagger: {type(table).__name__} is no table of demonstrations (env.demonstrations(dataset))")
+        return self._create_dagger(capacity, beta, table, seed)
+
+    def close_dagger(self):
+        if self.dagger is not None:
+            self.dagger.close()
+            self.dagger = None
+
     def members(self, name, n_members, seeds, kwargs):
         """What both population attaches begin with: the number of members."""
         from ._learner import check_seeds
@@ -240,13 +294,14 @@ class DevicePath:
 
     def close(self):
         self.close_bc()
+        self.close_dagger()
         for learner in filter(None, self.learners.values()):
             learner.close()
         self.learners = dict.fromkeys(LEARNERS)
         self.close_buffers()
 
     def enter(self, name, account, fresh=False):
-        """What collect_rollout, collect_steps and evaluate share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs and
+        """What collect_rollout, collect_steps, collect_dagger and evaluate share: no Monitor csv; the first call (and the first after reset() or seed()) resets the envs and
         hands the rows to the attached buffers; from then on step_async raises until reset().  `fresh`: reset whatever ran before (evaluate).  A loop that
         follows an evaluation resets too: the evaluation stepped the envs past the attached buffers, whose current rows, running returns and lengths are its
         reset's."""
@@ -297,6 +352,33 @@ class DevicePath:
             self._step(rows)
             self._add(kind, kept)
         return rb
+
+    def collect_dagger(self, n_steps, deterministic):
+        dg = self.dagger
+        if dg is None:
+            raise NotImplementedError("collect_dagger: call attach_dagger(capacity) first")
+        kind = self.dagger_kind("collect_dagger")
+        if kind != dg.table.kind:
+            raise NotImplementedError(f"collect_dagger: env.dagger was attached for a {dg.table.kind} learner, the attached learner is a {kind} one: call attach_dagger again")
+        learner, buf, on_policy = self.learners[kind], self.buffers[TABLE_KINDS[kind]], kind == "ppo"
+        if on_policy and self.loop == "collect_dagger":
+            self.behind = False   # (the last collect_dagger kept the rollout buffer's current rows in step: this one continues)
+        self.enter("collect_dagger", "env.dagger.stats()")
+        b = self.env._backend.batch
+        rows = self._rows()
+        kept = None if on_policy else self.torch.empty(buf.n, buf.act_dim, dtype=self.torch.float32, device=b.device)
+        for _ in range(int(n_steps)):
+            view = buf.observation()
+            actions = learner.policy(view, deterministic)[0] if on_policy else learner.act(view, deterministic)
+            dg.step(view, actions, b.expert_actions(), rows, kept)
+            self._step(rows)
+            if on_policy:
+                buf.observe(b.obs)   # a mixture policy is not on-policy: no slot is written; the current rows follow the envs
+            else:
+                self._add("replay", kept)
+        if on_policy:
+            self.behind = True   # the rollout buffer's episode flags and running returns did not see these steps: collect_rollout starts from a reset
+        return dg
 
     def evaluate(self, learner, params, n_eval_episodes, sync_every):
         from .evaluation import Evaluator

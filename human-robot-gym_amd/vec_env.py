@@ -983,6 +983,36 @@ class HipVecEnv(_VecEnvBase):
         env's."""
         return self._device_path.attach_bc(table, batch_size=batch_size, learning_rate=learning_rate, seed=seed)
 
+    # ---- DAgger on the device: the learner's own states, labelled by the live scripted expert (dagger.py, csrc/hrgym_dagger.h) ----
+    dagger = property(lambda self: self._device_path.dagger, doc="the attached DAgger step and its table (attach_dagger), or None")
+
+    def attach_dagger(self, capacity, beta=0.5, table=None, seed=None):
+        """The DAgger step for the attached lone learner and the table it fills (dagger.Dagger, kept as `env.dagger`; `env.dagger.table` is what
+        `env.attach_bc` takes).  Call it after attach_sac (with attach_replay) or attach_ppo (with attach_rollout), on an env constructed with expert=....
+        `capacity`: transitions in all, like attach_replay's buffer_size: max(capacity // num_envs, 1) step slots of one row per env, the oldest step
+        overwritten.  `beta`: the probability that the expert drives an env's step, drawn per env and step (`env.dagger.beta` may be scheduled).  `table`: a
+        bc.DemoTable of `env.demonstrations(...)`, copied into the head of the table and never overwritten (DAgger's iteration 0); without one the table is
+        empty until the first step.  `seed` (of the mixing draws): default the env's.  Attaching again replaces the handle and its table; seed() rebuilds them
+        empty; close() frees them.  NotImplementedError, before anything is allocated: no expert; an imitation_reward (the step's own expert call would advance
+        the expert's noise a second time: label and reward would see different expert actions); no lone learner, or a population; a goal env; the mixed
+        batch; another backend.
+        Every collect_dagger step calls the expert once, which advances its Ornstein-Uhlenbeck noise once: clean labels need the expert's
+        signal_to_noise_ratio = 1."""
+        return self._device_path.attach_dagger(capacity, beta, table, seed)
+
+    def collect_dagger(self, n_steps, deterministic=True):
+        """`n_steps` steps of every env driven by the mixture of the attached learner and the scripted expert, every visited row labelled by the expert and
+        written into `env.dagger.table`.  Per step: the attached buffer's view of the current rows, the learner's action (`env.sac.act(obs, deterministic)` or
+        `env.ppo.policy(obs, deterministic)[0]`), the expert's action for the same rows, the dagger step (label, per-env draw of who drives, the table's rows,
+        the rows the kernel reads), the env step with whatever reward kernels are attached, and with a replay buffer the slot: the executed action at the
+        policy's scale, so that with beta = 1 the buffer fills with the expert's transitions, rewards included.  The rollout buffer is not filled (a mixture
+        policy is not on-policy); its current rows follow the envs, and the next collect_rollout starts from a reset.  No device-to-host copy and no stream
+        synchronisation.  With beta = 0 the envs execute bit for bit the rows collect_steps(learner.act) sends.  The first call (and the first after reset() or
+        seed()) resets the envs; afterwards step_async raises until reset(); `env.dagger.stats()` is this loop's account: steps, the share the expert drove, the
+        on-policy imitation error.  A Monitor csv is refused.
+        Every step advances the expert's Ornstein-Uhlenbeck noise once; clean labels need the expert's signal_to_noise_ratio = 1.  Returns env.dagger."""
+        return self._device_path.collect_dagger(n_steps, deterministic)
+
     # ---- evaluation on the device: SB3's evaluate_policy next to the stepper (evaluation.py, csrc/hrgym_eval.h) ----
     def _eval_desc(self, n_envs, n_policies, n_eval_episodes):
         """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature

@@ -601,6 +601,25 @@ typedef struct hrg_bc_desc {
   uint64_t seed;                  /* of the index draws */
 } hrg_bc_desc;
 
+/* ------------------------------------------------------------------------- DAgger on the device (POD) */
+#define HRG_DAGGER_STATS_DIM 3              /* doubles per env of hrg_dagger_stats */
+/* columns of hrg_dagger_stats: steps, steps the expert drove, sum over the steps of sum_j (a_j - label_j)^2 (the learner's action at the label's scale) */
+enum { HRG_DAGGER_STEPS = 0, HRG_DAGGER_EXPERT_STEPS = 1, HRG_DAGGER_SQ_ERROR = 2 };
+/* One DAgger handle: per step, the expert's label for every env's current row, the per-env draw of who drives the step, and the (view, label) pair written into a
+ * caller-owned table [pinned_rows + capacity_steps * n_envs] that hrg_bc_step trains on.  kind: the learner's (HRG_BC_SAC: actions at the policy's scale [-1, 1];
+ * HRG_BC_PPO: at the env's). */
+typedef struct hrg_dagger_desc {
+  int32_t kind;                   /* HRG_BC_SAC | HRG_BC_PPO */
+  int32_t n_envs;
+  int64_t env_id0;                /* global id of env 0: the draws are keyed by env_id0 + e */
+  int32_t obs_dim;                /* values of the policy's view of a row, 1 .. HRG_OBS_DIM */
+  int32_t act_dim;                /* values of an action, 1 .. HRG_ACT_DIM */
+  int32_t capacity_steps;         /* step slots of n_envs rows each behind the pinned rows; the oldest is overwritten */
+  int32_t pinned_rows;            /* rows at the head of the table that no step writes (a demonstration table) */
+  uint64_t seed;                  /* of the mixing draws */
+  double act_low[HRG_ACT_DIM], act_high[HRG_ACT_DIM]; /* the action space's bounds; the first act_dim are read */
+} hrg_dagger_desc;
+
 /* ------------------------------------------------------------------------- evaluation of deterministic policies on the device (POD) */
 #define HRG_EVAL_MAX_EPISODES_PER_ENV 4096 /* the largest quota of an env: ceil(n_eval_episodes / (n_envs / n_policies)) may not exceed it */
 #define HRG_EVAL_RECORD_DIM (5 + HRG_INFO_DIM) /* doubles per record of hrg_eval_export */
@@ -638,6 +657,7 @@ typedef struct hrg_replay hrg_replay;   /* opaque */
 typedef struct hrg_sac hrg_sac;         /* opaque */
 typedef struct hrg_ppo hrg_ppo;         /* opaque */
 typedef struct hrg_bc hrg_bc;           /* opaque */
+typedef struct hrg_dagger hrg_dagger;   /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -1128,6 +1148,30 @@ int hrg_bc_sizes(hrg_bc* h, int64_t* size_host);
 int hrg_bc_step(hrg_bc* h, const float* table_obs_dev, const float* table_act_dev, int64_t n_rows, const int64_t* index_in_dev, float* params_dev, float* bc_m_dev,
                 float* bc_v_dev, double learning_rate, void* stream);
 int hrg_bc_export(hrg_bc* h, int64_t* index_host, float* pred_host, float* grad_host, float* loss_host);
+
+/* DAgger on the device (csrc/hrgym_dagger.h): one launch per env step between the learner's action and the step kernel.  With c =
+ * clip(expert_act[e][j], low[j], high[j]) in double, the label of env e is (float)(2 ((c - low) / (high - low)) - 1) for HRG_BC_SAC and (float)c for HRG_BC_PPO; the
+ * expert drives env e this step iff u01(seed, call, env_id0 + e, 16, 0) < beta (call: steps of this handle so far).  The table is the caller's: table_obs_dev float
+ * [pinned_rows + capacity_steps * n_envs][obs_dim], table_act_dev float [..][act_dim]; step slot s, env e is row pinned_rows + s * n_envs + e.  The slot and the call
+ * counter live in the handle on the host; the slot wraps.
+ *   hrg_dagger_create  checks the descriptor before anything is allocated: HRG_ERR_INVALID for a null argument, a kind that is neither HRG_BC_SAC nor HRG_BC_PPO, n_envs
+ *                      < 1, capacity_steps < 1, pinned_rows < 0, a bound that is not finite or act_high[j] <= act_low[j]; HRG_ERR_UNSUPPORTED for obs_dim outside 1 ..
+ *                      HRG_OBS_DIM and act_dim outside 1 .. HRG_ACT_DIM.
+ *   hrg_dagger_sizes   size_host int64[4] = steps so far (the next call's key), the next slot, the table's valid rows pinned_rows + min(steps, capacity_steps) * n_envs,
+ *                      bytes of device memory held.
+ *   hrg_dagger_step    one step, asynchronous on `stream`.  view_dev float [n_envs][obs_dim] (copied bit for bit into the table), learner_act_dev float [n_envs][act_dim]
+ *                      (SAC: at the policy's scale; PPO: at the env's, not clamped yet), expert_act_dev double [n_envs][HRG_ACT_DIM].  Writes the slot's rows of the table;
+ *                      rows_out_dev double [n_envs][HRG_ACT_DIM], what the step kernel reads: c where the expert drives, else low + 0.5 (a + 1) (high - low) in double
+ *                      (SAC; four rounded operations, as torch evaluates it) or clamp(a, low, high) in float (PPO), zeros behind act_dim; kept_out_dev float
+ *                      [n_envs][act_dim] or NULL: the executed action at the policy's scale (the label, or the learner's own row); and adds to the statistics.  beta
+ *                      outside [0, 1] or not finite: HRG_ERR_INVALID.
+ *   hrg_dagger_stats   synchronous: per_env_host double [n_envs][HRG_DAGGER_STATS_DIM], the sums since the last clear; `clear` zeroes them on the device. */
+int hrg_dagger_create(const hrg_dagger_desc* desc, int32_t device, hrg_dagger** out);
+void hrg_dagger_destroy(hrg_dagger* h);
+int hrg_dagger_sizes(hrg_dagger* h, int64_t* size_host);
+int hrg_dagger_step(hrg_dagger* h, const float* view_dev, const float* learner_act_dev, const double* expert_act_dev, double beta, float* table_obs_dev,
+                    float* table_act_dev, double* rows_out_dev, float* kept_out_dev, void* stream);
+int hrg_dagger_stats(hrg_dagger* h, double* per_env_host, int32_t clear);
 
 /* Evaluation on the device (csrc/hrgym_eval.h): SB3 1.5.0's evaluate_policy with deterministic = True as a loop of three launches per env step -- the step entry
  * that fits what is attached, hrg_eval_step, hrg_eval_policy_* -- with no copy to the host between them.  The view float [n_envs][width] and the action rows double
