@@ -121,6 +121,7 @@ SacHyper = _STRUCTS["hrg_sac_hyper"]
 PpoHyper = _STRUCTS["hrg_ppo_hyper"]
 BcDesc = _STRUCTS["hrg_bc_desc"]
 DaggerDesc = _STRUCTS["hrg_dagger_desc"]
+DiscDesc = _STRUCTS["hrg_disc_desc"]
 EvalDesc = _STRUCTS["hrg_eval_desc"]
 PROTOTYPES = parse_prototypes(open(os.path.join(_INCLUDE, "hrgym.h")).read())
 

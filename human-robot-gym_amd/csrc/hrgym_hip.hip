@@ -3458,6 +3458,7 @@ extern "C" int HRG_SYM(hrg_debug_envcyc)(unsigned long long* out, int n) { retur
 #include "hrgym_eval.h"     // evaluation of deterministic policies: begin / step (the episode ledger) / remaining / fused actor kernels (hrg_eval_*)
 #include "hrgym_bc.h"       // behaviour cloning of a learner's actor from a table of demonstration rows: gradient / Adam kernels (hrg_bc_*)
 #include "hrgym_dagger.h"   // DAgger: the expert's label for the learner's own states, the per-env mixing draw, the table row: one kernel per env step (hrg_dagger_*)
+#include "hrgym_disc.h"     // adversarial imitation: a discriminator on (observation, action) rows and the reward it gives a batch: gradient / Adam / reward kernels (hrg_disc_*)
 
 // ================================================================================================ host side
 #include "hrgym_host.h"            // what the host files share: the error string, a handle's device memory, the launch grids

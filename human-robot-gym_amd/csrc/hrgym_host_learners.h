@@ -1,5 +1,5 @@
 // hrgym_host_learners.h -- the learners of the C ABI (include/hrgym.h): SAC (hrg_sac_*), PPO (hrg_ppo_*) and the evaluation of their policies (hrg_eval_*), with what
-// the two learners check and compute alike; behind them behaviour cloning of their actors (hrg_bc_*) and the DAgger step that fills its table (hrg_dagger_*).  Included by the base unit only, behind hrgym_host.h and hrgym_host_buffers.h (the evaluator reads rows through a buffer's view).
+// the two learners check and compute alike; behind them behaviour cloning of their actors (hrg_bc_*) and the DAgger step that fills its table (hrg_dagger_*), and the discriminator of adversarial imitation (hrg_disc_*).  Included by the base unit only, behind hrgym_host.h and hrgym_host_buffers.h (the evaluator reads rows through a buffer's view).
 
 // What both learners check of their networks and batch (csrc/hrgym_mlp.h).  `name`: the learner's message prefix; max_batch: its largest batch.
 static int learner_shape(const char* name, int32_t hidden, int32_t depth, int32_t obs_dim, int32_t act_dim, int32_t batch_size, int32_t max_batch) {
@@ -784,6 +784,107 @@ int hrg_dagger_step(hrg_dagger* h, const float* view_dev, const float* learner_a
 int hrg_dagger_stats(hrg_dagger* h, double* per_env_host, int32_t clear) {
   if (!h || !per_env_host) return fail(HRG_ERR_INVALID, "null argument");
   return buffer_stats(h->device, h->d.stats, h->desc.n_envs, HRG_DAGGER_STATS_DIM, per_env_host, clear);
+}
+
+// ---- adversarial imitation: the discriminator (csrc/hrgym_disc.h) ----
+struct hrg_disc {
+  int device = 0;
+  hrg_disc_desc desc;
+  DiscDev d;
+  uint64_t steps = 0;   // updates so far: Adam's step count and the key of the step's draws
+  DeviceMem mem;        // behind every pointer of `d`
+};
+
+int hrg_disc_create(const hrg_disc_desc* desc, int32_t device, hrg_disc** out) {
+  if (!desc || !out) return fail(HRG_ERR_INVALID, "null argument");
+  *out = nullptr;
+  if (int rc = learner_shape("disc", desc->hidden, desc->depth, desc->obs_dim, desc->act_dim, desc->batch_size, HRG_DISC_MAX_BATCH)) return rc;
+  if (desc->activation != HRG_DISC_RELU && desc->activation != HRG_DISC_TANH)
+    return fail(HRG_ERR_INVALID, "disc: activation = " + std::to_string(desc->activation) + ": HRG_DISC_RELU or HRG_DISC_TANH");
+  if (desc->reward_kind != HRG_DISC_REWARD_GAIL && desc->reward_kind != HRG_DISC_REWARD_AIRL)
+    return fail(HRG_ERR_INVALID, "disc: reward_kind = " + std::to_string(desc->reward_kind) + ": HRG_DISC_REWARD_GAIL or HRG_DISC_REWARD_AIRL");
+  HIPCHK(hipSetDevice(device));
+  std::unique_ptr<hrg_disc> h(new hrg_disc());
+  h->device = device;
+  h->desc = *desc;
+  DiscDev& d = h->d;
+  d.K = desc->obs_dim; d.A = desc->act_dim; d.depth = desc->depth; d.B = desc->batch_size; d.tiles = 2 * desc->batch_size / HRG_SAC_TILE;
+  d.unit = desc->activation == HRG_DISC_RELU ? MLP_ACT_RELU : MLP_ACT_TANH; d.kind = desc->reward_kind; d.seed = desc->seed;
+  int32_t o = 0;
+  for (int l = 0; l < d.depth; l++) {
+    d.w[l] = o; o += MLP_H * (l ? MLP_H : d.K + d.A);
+    d.b[l] = o; o += MLP_H;
+  }
+  d.hw = o; o += MLP_H;
+  d.hb = o; o += 1;
+  d.n_params = o;
+  const size_t P = (size_t)d.n_params, B = (size_t)d.B;
+  Carver<float> f;
+  f.take(d.logits, 2 * B);
+  f.take(d.part, (size_t)d.tiles * P);
+  f.take(d.grad, P);
+  f.take(d.stat_part, (size_t)d.tiles * DISC_NSTAT);
+  f.take(d.diag, 3);
+  if (!f.alloc(h->mem) || !h->mem.zeros(d.index, B)) return nomem("disc", h->mem);
+  HIPCHK(hipDeviceSynchronize());
+  *out = h.release();
+  return HRG_OK;
+}
+
+void hrg_disc_destroy(hrg_disc* h) { destroy_handle(h); }
+
+int hrg_disc_sizes(hrg_disc* h, int64_t* size_host) {
+  if (!h || !size_host) return fail(HRG_ERR_INVALID, "null argument");
+  size_host[0] = h->d.n_params;
+  size_host[1] = (int64_t)h->steps;
+  size_host[2] = h->d.tiles;
+  size_host[3] = h->d.B;
+  return HRG_OK;
+}
+
+int hrg_disc_step(hrg_disc* h, const float* table_obs_dev, const float* table_act_dev, int64_t n_rows, const int64_t* index_in_dev, const float* policy_obs_dev,
+                  const float* policy_act_dev, float* params_dev, float* m_dev, float* v_dev, double learning_rate, void* stream) {
+  if (!h || !policy_obs_dev || !policy_act_dev || !params_dev || !m_dev || !v_dev) return fail(HRG_ERR_INVALID, "null argument");
+  if (!table_obs_dev || !table_act_dev) return fail(HRG_ERR_INVALID, "disc: null table (observations and actions of n_rows rows)");
+  if (n_rows < 1) return fail(HRG_ERR_INVALID, "disc: n_rows = " + std::to_string(n_rows) + " must be positive");
+  if (!std::isfinite(learning_rate) || learning_rate < 0.0) return fail(HRG_ERR_INVALID, "disc: learning_rate must be finite and not negative");
+  HIPCHK(hipSetDevice(h->device));
+  const DiscDev& d = h->d;
+  hipStream_t st = (hipStream_t)stream;
+  double bc1, bc2;
+  adam_bias_corrections(h->steps, bc1, bc2);
+  hipLaunchKernelGGL(hrg_disc_grad_kernel, dim3((unsigned)d.tiles), dim3(MLP_BLOCK), 0, st, d, (const float*)params_dev, table_obs_dev, table_act_dev, n_rows, index_in_dev,
+                     policy_obs_dev, policy_act_dev, h->steps);
+  hipLaunchKernelGGL(hrg_disc_adam_kernel, dim3(((unsigned)d.n_params + MLP_BLOCK - 1) / MLP_BLOCK), dim3(MLP_BLOCK), 0, st, d, params_dev, m_dev, v_dev, learning_rate, bc1, bc2);
+  HIPCHK(hipGetLastError());
+  h->steps++;
+  return HRG_OK;
+}
+
+int hrg_disc_reward(hrg_disc* h, const float* params_dev, const float* obs_dev, const float* act_dev, int32_t n, const float* env_rewards_dev, double alpha,
+                    float* rewards_out_dev, float* logits_out_dev, void* stream) {
+  if (!h || !params_dev || !obs_dev || !act_dev || (!rewards_out_dev && !logits_out_dev)) return fail(HRG_ERR_INVALID, "null argument");
+  if (n < 1) return fail(HRG_ERR_INVALID, "disc: n = " + std::to_string(n) + " must be positive");
+  if (!(alpha >= 0.0 && alpha <= 1.0)) return fail(HRG_ERR_INVALID, "disc: alpha = " + std::to_string(alpha) + " outside [0, 1]");
+  HIPCHK(hipSetDevice(h->device));
+  hipLaunchKernelGGL(hrg_disc_reward_kernel, dim3(((unsigned)n + MLP_T - 1) / MLP_T), dim3(MLP_BLOCK), 0, (hipStream_t)stream, h->d, params_dev, obs_dev, act_dev, (int)n,
+                     env_rewards_dev, alpha, rewards_out_dev, logits_out_dev);
+  HIPCHK(hipGetLastError());
+  return HRG_OK;
+}
+
+int hrg_disc_export(hrg_disc* h, int64_t* index_host, float* logits_host, float* grad_host, float* diag_host) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  const DiscDev& d = h->d;
+  if (int rc = export_floats(h->device, {{logits_host, d.logits, 2 * (size_t)d.B}, {grad_host, d.grad, (size_t)d.n_params}, {diag_host, d.diag, 3}})) return rc;
+  if (index_host) HIPCHK(hipMemcpy(index_host, d.index, (size_t)d.B * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return HRG_OK;
+}
+
+int hrg_disc_restore(hrg_disc* h, uint64_t steps) {
+  if (!h) return fail(HRG_ERR_INVALID, "null argument");
+  h->steps = steps;
+  return HRG_OK;
 }
 
 } // extern "C"

@@ -51,6 +51,8 @@ TABLE_KINDS = {"sac": "replay", "ppo": "rollout"}   # the buffer whose view a le
 # the DAgger step (dagger.Dagger) is refused as a buffer is too: it labels the rows of an attached buffer's view with the batch's scripted expert
 DAGGER = BufferKind(None, "dagger", "goal_env: the scripted experts read flat observations, and the hindsight feature row is another layout (DAgger covers flat "
                     "observations)", None, None, None)
+# the discriminator of adversarial imitation (adversarial.Discriminator) is refused as the table it reads is
+DISCRIMINATOR = BufferKind(None, "discriminator", "goal_env: the hindsight feature row is another layout (adversarial imitation covers flat observations)", None, None, None)
 
 
 def widen(rows, A, actions):
@@ -71,6 +73,7 @@ class DevicePath:
         self.bc = None       # env.bc: the behaviour cloning of one of the lone learners (bc.BehaviourCloning)
         self.dagger = None   # env.dagger: the DAgger step and its table (dagger.Dagger)
         self.dagger_args = None   # the arguments it was attached with, for the new, empty one after seed()
+        self.discriminator = None   # env.discriminator: the discriminator of adversarial imitation (adversarial.Discriminator); seed() leaves it alone, as it leaves the learners
         self.loop = False    # the name of the device loop (collect_rollout, collect_steps, collect_dagger, evaluate) that has stepped the envs past the host accounting: step_async waits for a reset()
         self.behind = False  # an evaluation stepped the envs past the attached buffers: the next device loop starts from a reset
         self.rebind()
@@ -94,7 +97,7 @@ class DevicePath:
 
     def refusal(self, kind):
         """Why the env cannot carry a device buffer of `kind`, or None."""
-        env, row = self.env, {"demonstrations": DEMONSTRATIONS, "dagger": DAGGER}.get(kind) or KINDS[kind]
+        env, row = self.env, {"demonstrations": DEMONSTRATIONS, "dagger": DAGGER, "discriminator": DISCRIMINATOR}.get(kind) or KINDS[kind]
         if not self.on_hip():
             return f"the {row.kernels} kernels run in the HIP library; another backend has none"
         if env.goal_env and row.goal_env is not None:
@@ -281,6 +284,25 @@ class DevicePath:
             self.dagger.close()
             self.dagger = None
 
+    def attach_discriminator(self, table, seed=None, **kwargs):
+        """adversarial.Discriminator of `table` (a table of demonstrations, or a dataset for `demonstrations`), kept as `env.discriminator`; the previous one is closed.
+        `seed` None: the env's."""
+        from .adversarial import Discriminator
+        why = self.env.device_refusal("discriminator")
+        if why is not None:
+            raise NotImplementedError(f"attach_discriminator: {why}")
+        if not hasattr(table, "kind"):
+            table = self.demonstrations(table, algorithm="sac" if "replay" in self.buffers else None)
+        disc = Discriminator(table, seed=int(self.env._desc.seed) if seed is None else seed, **kwargs)
+        self.close_discriminator()
+        self.discriminator = disc
+        return disc
+
+    def close_discriminator(self):
+        if self.discriminator is not None:
+            self.discriminator.close()
+            self.discriminator = None
+
     def members(self, name, n_members, seeds, kwargs):
         """What both population attaches begin with: the number of members."""
         from ._learner import check_seeds
@@ -295,6 +317,7 @@ class DevicePath:
     def close(self):
         self.close_bc()
         self.close_dagger()
+        self.close_discriminator()
         for learner in filter(None, self.learners.values()):
             learner.close()
         self.learners = dict.fromkeys(LEARNERS)

@@ -211,7 +211,8 @@ def _mixed_cls():
 
         def device_refusal(self, kind):
             return {"rollout": "the mixed batch steps one HipBatch per task", "replay": "the mixed batch has its observation columns per task",
-                    "demonstrations": "a demonstration dataset is per task", "dagger": "scripted experts are per task and action form"}.get(kind, "goal-env relabelling is per task") + "; use one HipVecEnv per task"
+                    "demonstrations": "a demonstration dataset is per task", "dagger": "scripted experts are per task and action form",
+                    "discriminator": "a demonstration dataset is per task"}.get(kind, "goal-env relabelling is per task") + "; use one HipVecEnv per task"
 
         def expert_actions(self):
             raise NotImplementedError("scripted experts are per task and action form; use one HipVecEnv(expert=...) per task")

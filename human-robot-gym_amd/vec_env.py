@@ -1013,6 +1013,20 @@ class HipVecEnv(_VecEnvBase):
         Every step advances the expert's Ornstein-Uhlenbeck noise once; clean labels need the expert's signal_to_noise_ratio = 1.  Returns env.dagger."""
         return self._device_path.collect_dagger(n_steps, deterministic)
 
+    # ---- adversarial imitation on the device: a discriminator's reward for SAC (adversarial.py, csrc/hrgym_disc.h) ----
+    discriminator = property(lambda self: self._device_path.discriminator, doc="the attached discriminator (attach_discriminator), or None")
+
+    def attach_discriminator(self, table, net_arch=(64, 64), activation="relu", batch_size=128, learning_rate=3e-4, reward="gail", seed=None):
+        """The discriminator of adversarial imitation (adversarial.Discriminator, kept as `env.discriminator`): a network on (observation, action) rows trained
+        to tell the rows of `table` from the learner's own, whose output `adversarial.train_sac(learner, env.replay, env.discriminator, n, alpha=...)` mixes
+        into SAC's reward at sample time, r_disc alpha + r_env (1 - alpha).  `table`: a bc.DemoTable of `env.demonstrations(...)` or a dagger.DaggerTable, of
+        kind "sac" (a "ppo" table holds its actions at the env's scale: ValueError); or a dataset name, path or dataset.ExpertDataset, which goes through
+        `env.demonstrations` first, with its refusals.  `reward`: "gail" (-log(1 - D)) or "airl" (logit D).  `batch_size`: the learner's.  `seed` (of the
+        index draws and the initial weights): default the env's.  Attaching again replaces the handle; seed() leaves it alone, as it leaves the learners;
+        close() frees it.  NotImplementedError, before anything is allocated: a goal env, the mixed batch, another backend."""
+        return self._device_path.attach_discriminator(table, net_arch=net_arch, activation=activation, batch_size=batch_size, learning_rate=learning_rate, reward=reward,
+                                                      seed=seed)
+
     # ---- evaluation on the device: SB3's evaluate_policy next to the stepper (evaluation.py, csrc/hrgym_eval.h) ----
     def _eval_desc(self, n_envs, n_policies, n_eval_episodes):
         """hrg_eval_desc of this env: the groups and their quotas, the policy's view of a row (obs_keys, obs_norm, the time column; on a goal env the feature

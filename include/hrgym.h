@@ -620,6 +620,24 @@ typedef struct hrg_dagger_desc {
   double act_low[HRG_ACT_DIM], act_high[HRG_ACT_DIM]; /* the action space's bounds; the first act_dim are read */
 } hrg_dagger_desc;
 
+/* ------------------------------------------------------------------------- adversarial imitation on the device (POD) */
+#define HRG_DISC_MAX_BATCH 256              /* rows per half of a discriminator batch: a multiple of HRG_SAC_TILE, HRG_SAC_TILE .. HRG_DISC_MAX_BATCH */
+enum { HRG_DISC_REWARD_GAIL = 0, HRG_DISC_REWARD_AIRL = 1 };   /* hrg_disc_desc.reward_kind: softplus(d) = -log(1 - D) | d = logit D */
+enum { HRG_DISC_RELU = 0, HRG_DISC_TANH = 1 };                 /* hrg_disc_desc.activation: the hidden units */
+/* One discriminator: an MLP of a SAC critic's shape on [obs | action] whose one output is the logit d that the row is the expert's.  The learning rate is an
+ * argument of hrg_disc_step, alpha of hrg_disc_reward. */
+typedef struct hrg_disc_desc {
+  int32_t obs_dim;                /* 1 .. HRG_OBS_DIM */
+  int32_t act_dim;                /* 1 .. HRG_ACT_DIM */
+  int32_t depth;                  /* hidden layers, 1 .. HRG_SAC_MAX_DEPTH */
+  int32_t hidden;                 /* HRG_SAC_HIDDEN */
+  int32_t batch_size;             /* B, rows per half (B expert rows and B policy rows a step): a multiple of HRG_SAC_TILE, HRG_SAC_TILE .. HRG_DISC_MAX_BATCH */
+  int32_t activation;             /* HRG_DISC_RELU | HRG_DISC_TANH */
+  int32_t reward_kind;            /* HRG_DISC_REWARD_GAIL | HRG_DISC_REWARD_AIRL */
+  int32_t reserved_;
+  uint64_t seed;                  /* of the index draws */
+} hrg_disc_desc;
+
 /* ------------------------------------------------------------------------- evaluation of deterministic policies on the device (POD) */
 #define HRG_EVAL_MAX_EPISODES_PER_ENV 4096 /* the largest quota of an env: ceil(n_eval_episodes / (n_envs / n_policies)) may not exceed it */
 #define HRG_EVAL_RECORD_DIM (5 + HRG_INFO_DIM) /* doubles per record of hrg_eval_export */
@@ -658,6 +676,7 @@ typedef struct hrg_sac hrg_sac;         /* opaque */
 typedef struct hrg_ppo hrg_ppo;         /* opaque */
 typedef struct hrg_bc hrg_bc;           /* opaque */
 typedef struct hrg_dagger hrg_dagger;   /* opaque */
+typedef struct hrg_disc hrg_disc;       /* opaque */
 
 /* ----------------------------------------------------------------------------------------------- entry points */
 const char* hrg_last_error(void);
@@ -1172,6 +1191,37 @@ int hrg_dagger_sizes(hrg_dagger* h, int64_t* size_host);
 int hrg_dagger_step(hrg_dagger* h, const float* view_dev, const float* learner_act_dev, const double* expert_act_dev, double beta, float* table_obs_dev,
                     float* table_act_dev, double* rows_out_dev, float* kept_out_dev, void* stream);
 int hrg_dagger_stats(hrg_dagger* h, double* per_env_host, int32_t clear);
+
+/* Adversarial imitation on the device (csrc/hrgym_disc.h): a discriminator trained to tell a table's (observation, action) rows from the learner's
+ * own, and the reward it gives a batch.  The parameters are the caller's float [n_params] device array -- W_l [64][in_l], b_l [64] for l < depth (in_0 = obs_dim +
+ * act_dim), W_d [1][64], b_d [1] --, the moments m_dev, v_dev the caller's too, in the same layout, zero at the start.  The handle owns its step count (Adam's, and
+ * the key of its draws) and its scratch.
+ *   hrg_disc_create   checks the descriptor before anything is allocated: HRG_ERR_INVALID for a null argument, an activation or reward_kind that is none of the
+ *                     enumerators; HRG_ERR_UNSUPPORTED for hidden other than HRG_SAC_HIDDEN, depth outside 1 .. 3, obs_dim outside 1 .. HRG_OBS_DIM, act_dim outside
+ *                     1 .. HRG_ACT_DIM, a batch_size that is not a multiple of HRG_SAC_TILE in HRG_SAC_TILE .. HRG_DISC_MAX_BATCH.
+ *   hrg_disc_sizes    size_host int64[4] = parameters, steps so far, tiles of a step (2 batch_size / HRG_SAC_TILE), batch_size.
+ *   hrg_disc_step     one update, two launches, asynchronous on `stream`.  Expert row k < batch_size is the table's row index_in_dev[k] (int64 [batch_size], clamped
+ *                     into the table) or, with NULL, floor(u n_rows) clamped to n_rows - 1 with u = u01(seed, step count, k, 17, 0); policy row k is row k of
+ *                     policy_obs_dev float [batch_size][obs_dim] and policy_act_dev float [batch_size][act_dim].  The loss is the binary cross-entropy on the logit,
+ *                     (1 / 2B) (sum_expert softplus(-d) + sum_policy softplus(d)); then torch's Adam (eps 1e-8).  Only params_dev, m_dev, v_dev and the handle's
+ *                     scratch are written.  HRG_ERR_INVALID for a null argument, n_rows < 1, a learning_rate that is not finite or negative.
+ *   hrg_disc_reward   forward only, one launch, asynchronous on `stream`: rows obs_dev float [n][obs_dim], act_dev float [n][act_dim], n >= 1.  r_disc = softplus(d)
+ *                     (HRG_DISC_REWARD_GAIL) or d (HRG_DISC_REWARD_AIRL) in double; rewards_out_dev float [n] = r_disc, or with env_rewards_dev float [n] (it may be
+ *                     rewards_out_dev itself) r_disc alpha + r_env (1 - alpha), rounded once; logits_out_dev float [n] = d.  Either output may be NULL, not both.
+ *                     It writes nothing of the discriminator's.  HRG_ERR_INVALID for a null argument, n < 1, alpha outside [0, 1] or not finite.
+ *   hrg_disc_export   synchronous parity hook, the last step's: index_host int64 [batch_size] (the table rows), logits_host float [2 batch_size] (expert rows, then
+ *                     policy rows), grad_host float [n_params], diag_host float [3] = loss, the share of expert rows with d > 0, of policy rows with d < 0.  Any
+ *                     pointer may be NULL.
+ *   hrg_disc_restore  sets the step count (a continued run: Adam's bias corrections and the draws' key follow from it). */
+int hrg_disc_create(const hrg_disc_desc* desc, int32_t device, hrg_disc** out);
+void hrg_disc_destroy(hrg_disc* h);
+int hrg_disc_sizes(hrg_disc* h, int64_t* size_host);
+int hrg_disc_step(hrg_disc* h, const float* table_obs_dev, const float* table_act_dev, int64_t n_rows, const int64_t* index_in_dev, const float* policy_obs_dev,
+                  const float* policy_act_dev, float* params_dev, float* m_dev, float* v_dev, double learning_rate, void* stream);
+int hrg_disc_reward(hrg_disc* h, const float* params_dev, const float* obs_dev, const float* act_dev, int32_t n, const float* env_rewards_dev, double alpha,
+                    float* rewards_out_dev, float* logits_out_dev, void* stream);
+int hrg_disc_export(hrg_disc* h, int64_t* index_host, float* logits_host, float* grad_host, float* diag_host);
+int hrg_disc_restore(hrg_disc* h, uint64_t steps);
 
 /* Evaluation on the device (csrc/hrgym_eval.h): SB3 1.5.0's evaluate_policy with deterministic = True as a loop of three launches per env step -- the step entry
  * that fits what is attached, hrg_eval_step, hrg_eval_policy_* -- with no copy to the host between them.  The view float [n_envs][width] and the action rows double
